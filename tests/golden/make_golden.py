@@ -503,9 +503,9 @@ def golden_real_frames():
 def golden_real_jpegs(count=28):
     """`count` of the reference's 173 real Duckiebot camera frames (src/anti_instagram/annotation-tool/images/*.jpg: data files
     of the reference) as their JPEG BYTE STREAMS, spread evenly over the five recording sessions (night, noon, closed room, ice
-    rink, coordination LEDs): input data for the GPU tests -- device JPEG decode -> the whole front end / the KeyLine path --
-    and for bench.py's real-content rows.  No expected outputs are stored: the pinned JPEG oracle and the oracle front end
-    compute them at test time."""
+    rink, coordination LEDs): input data for the GPU tests -- device JPEG decode -> the whole front end / the KeyLine path --,
+    for the CPU tests of the JPEG decoders and the oracle on real camera content, and for bench.py's real-content rows.  No
+    expected outputs are stored: Pillow, the pinned JPEG oracle and the oracle front end compute them at test time."""
     d = os.path.join(REF, "anti_instagram/annotation-tool/images")
     names = sorted(n for n in os.listdir(d) if n.endswith(".jpg"))
     picks = [names[(2 * k + 1) * len(names) // (2 * count)] for k in range(count)]

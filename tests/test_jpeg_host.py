@@ -103,18 +103,18 @@ def test_host_decoder_builtin_tables(host, vectors):
         assert rc0 == 0 and rc1 == 0 and np.array_equal(a, b), name
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/anti_instagram/annotation-tool/images"),
-                    reason="the reference checkout (real camera JPEGs) is only present in the build container")
-def test_host_decoder_on_reference_camera_images(host):
-    """The product's entropy decoder on the reference's 173 real camera frames: coefficients equal the oracle's
-    (which equals libjpeg-turbo on these files, tests/test_oracle_jpeg.py)."""
-    import glob
+def test_host_decoder_on_reference_camera_images(host, golden_dir):
+    """The product's entropy decoder on real camera frames (the 28 streams of tests/golden/real_jpegs.npz, from all five of
+    the reference's recording sessions): coefficients equal the oracle's (which equals libjpeg-turbo on these streams,
+    tests/test_oracle_jpeg.py)."""
     from oracle.oracle import jpeg_coefficients
-    files = sorted(glob.glob("/root/reference/src/anti_instagram/annotation-tool/images/*.jpg"))[::4]
-    for f in files:
-        data = open(f, "rb").read()
+    z = np.load(os.path.join(golden_dir, "real_jpegs.npz"))
+    names = [str(n) for n in z["names"]]
+    assert len(names) == 28
+    for k in range(len(names)):
+        data = bytes(z["jpeg%02d" % k])
         rc, dense, _, _ = _coefs(host, data)
-        assert rc == 0 and np.array_equal(dense, jpeg_coefficients(data)), os.path.basename(f)
+        assert rc == 0 and np.array_equal(dense, jpeg_coefficients(data)), names[k]
 
 
 def test_decoders_survive_hostile_input_under_sanitizers(vectors, tmp_path):

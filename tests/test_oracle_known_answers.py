@@ -350,26 +350,22 @@ def test_match_beyond_128_is_no_match(oracle_parity):
     assert idx[1] >= 0 and dist[1] == 128.0
 
 
-# ------------------------------------------------------------------ realism (build container only)
-REF_IMAGES = "/root/reference/src/anti_instagram/annotation-tool/images"
-
-
+# ------------------------------------------------------------------ realism
 import os                                                       # noqa: E402
-import pytest                                                   # noqa: E402
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_IMAGES), reason="the reference's real camera frames exist only in the build container")
-def test_real_duckiebot_frames_give_plausible_segments(oracle_parity):
-    """Not parity -- plausibility: on the reference's real 640x480 camera frames, with the reference's default
-    thresholds and geometry, the restated pipeline must find lane markings of all three colours in the range
-    SURVEY 8(a) expects (5-60 segments per frame at 160x120) and line sanity must keep a sensible share."""
-    import glob
+def test_real_duckiebot_frames_give_plausible_segments(oracle_parity, golden_dir):
+    """Not parity -- plausibility: on the reference's real 640x480 camera frames (the 28 streams of
+    tests/golden/real_jpegs.npz, from all five recording sessions), with the reference's default thresholds and
+    geometry, the restated pipeline must find lane markings of all three colours in the range SURVEY 8(a) expects
+    (5-60 segments per frame at 160x120) and line sanity must keep a sensible share."""
     from oracle.oracle import jpeg_decode
     o = oracle_parity
-    files = sorted(glob.glob(os.path.join(REF_IMAGES, "*.jpg")))[::6]
+    z = np.load(os.path.join(golden_dir, "real_jpegs.npz"))
+    assert len(z["names"]) == 28
     n, kept, colours = [], [], np.zeros(3, int)
-    for f in files:
-        r = o.process_frame(jpeg_decode(open(f, "rb").read()), cap=4096)
+    for k in range(len(z["names"])):
+        r = o.process_frame(jpeg_decode(bytes(z["jpeg%02d" % k])), cap=4096)
         n.append(r["n"])
         kept.append(int(r["keep"].sum()))
         for c in range(3):
