@@ -206,16 +206,65 @@ __host__ __device__ inline uint32_t assoc_fp4_expand(uint32_t byte)
     t = (t | (t << 3)) & 0x11111111u;
     return (t << 3) | 0x22222222u;
 }
+// Owning, move-only memory: the destructor frees.  DevArray holds device memory (hipMalloc), HostArray pinned host memory
+// (hipHostMalloc).  alloc() frees what the buffer held first; a caller that must wait for a stream before that does so itself.
+// p converts to T*, so a buffer is passed to launches and copies as it is; pointers into it are views that own nothing.
+template <typename T>
+struct DevArray {
+    T* p = nullptr;
+    size_t bytes = 0;
+    DevArray() = default;
+    DevArray(DevArray&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevArray& operator=(DevArray&& o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+        return *this;
+    }
+    ~DevArray() { reset(); }
+    hipError_t alloc(size_t n_bytes)
+    {
+        reset();
+        const hipError_t e = hipMalloc((void**)&p, n_bytes);
+        if (e != hipSuccess) p = nullptr; else bytes = n_bytes;
+        return e;
+    }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    operator T*() const { return p; }
+};
+using DevBuf = DevArray<void>;
+
+template <typename T>
+struct HostArray {
+    T* p = nullptr;
+    size_t bytes = 0;
+    HostArray() = default;
+    HostArray(HostArray&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    HostArray& operator=(HostArray&& o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+        return *this;
+    }
+    ~HostArray() { reset(); }
+    hipError_t alloc(size_t n_bytes)
+    {
+        reset();
+        const hipError_t e = hipHostMalloc((void**)&p, n_bytes, hipHostMallocDefault);
+        if (e != hipSuccess) p = nullptr; else bytes = n_bytes;
+        return e;
+    }
+    void reset() { if (p) (void)hipHostFree(p); p = nullptr; bytes = 0; }
+    operator T*() const { return p; }
+};
+
 // per-caller scratch of the associator (k_assoc.hip): one key per query and map chunk + arrival counters; sized by
 // launch_assoc_core itself
 struct AssocScratch {
-    unsigned int* part = nullptr; int* done = nullptr; size_t cap_part = 0, cap_blocks = 0;
+    DevArray<unsigned int> part; DevArray<int> done; size_t cap_part = 0, cap_blocks = 0;
     // the last launch_assoc_core's split of the map (the tie pass reads part[] with it) and the tie pass's query lists
     int qblocks = 0, splits = 0, m_chunk = 0;
-    int* tie_list = nullptr; size_t cap_list = 0;
+    DevArray<int> tie_list; size_t cap_list = 0;
     unsigned long long* tie_res = nullptr;        // set by the caller before launch_assoc_core when launch_assoc_ties follows: the merge step then writes the tie pass's query lists
 };
-void assoc_scratch_free(AssocScratch& w);
 void launch_assoc_pack_map(const uint8_t* codes, const uint8_t* colors, int n, int n_pad, int fp4, int8_t* x, int8_t* cx, hipStream_t s);
 hipError_t launch_assoc_core(const uint8_t* q, const uint8_t* qcolor, int nq, const int8_t* mx, const int8_t* mcx, int nm,
                              const int* nm_dev, int gating, int max_distance, AssocScratch& w, int32_t* idx, float* dist, hipStream_t s);

@@ -584,27 +584,19 @@ static hipError_t assoc_scratch_reserve(AssocScratch& w, size_t qblocks, size_t 
 {
     hipError_t e;
     if (qblocks * splits > w.cap_part) {
-        if (w.part) { if ((e = hipStreamSynchronize(s)) != hipSuccess) return e; (void)hipFree(w.part); w.part = nullptr; w.cap_part = 0; }
+        if (w.part) { if ((e = hipStreamSynchronize(s)) != hipSuccess) return e; w.part.reset(); w.cap_part = 0; }
         const size_t cap = qblocks * splits + qblocks * splits / 2;
-        if ((e = hipMalloc((void**)&w.part, cap * AQW * sizeof(unsigned int))) != hipSuccess) return e;
+        if ((e = w.part.alloc(cap * AQW * sizeof(unsigned int))) != hipSuccess) return e;
         w.cap_part = cap;
     }
     if (counters > w.cap_blocks) {                          // (one arrival counter per workgroup column: 128-query blocks in the small shape)
-        if (w.done) { if ((e = hipStreamSynchronize(s)) != hipSuccess) return e; (void)hipFree(w.done); w.done = nullptr; w.cap_blocks = 0; }
+        if (w.done) { if ((e = hipStreamSynchronize(s)) != hipSuccess) return e; w.done.reset(); w.cap_blocks = 0; }
         const size_t cap = counters + counters / 2 + 8;
-        if ((e = hipMalloc((void**)&w.done, cap * sizeof(int))) != hipSuccess) return e;
+        if ((e = w.done.alloc(cap * sizeof(int))) != hipSuccess) return e;
         if ((e = hipMemsetAsync(w.done, 0, cap * sizeof(int), s)) != hipSuccess) return e;
         w.cap_blocks = cap;
     }
     return hipSuccess;
-}
-
-void assoc_scratch_free(AssocScratch& w)
-{
-    if (w.part) (void)hipFree(w.part);
-    if (w.done) (void)hipFree(w.done);
-    if (w.tie_list) (void)hipFree(w.tie_list);
-    w.part = nullptr; w.done = nullptr; w.cap_part = 0; w.cap_blocks = 0; w.tie_list = nullptr; w.cap_list = 0;
 }
 
 void launch_assoc_pack_map(const uint8_t* codes, const uint8_t* colors, int n, int n_pad, int fp4, int8_t* x, int8_t* cx, hipStream_t s)
@@ -650,9 +642,8 @@ hipError_t launch_assoc_core(const uint8_t* q, const uint8_t* qcolor, int nq, co
         const size_t n_pieces = (size_t)qblocks256 * 4;
         const size_t need = (size_t)splits * n_pieces * 64 + (size_t)splits * n_pieces;
         if (need > w.cap_list) {
-            if (w.tie_list) (void)hipFree(w.tie_list);
-            w.tie_list = nullptr; w.cap_list = 0;
-            e = hipMalloc(&w.tie_list, (need + need / 2) * sizeof(int));
+            w.cap_list = 0;
+            e = w.tie_list.alloc((need + need / 2) * sizeof(int));
             if (e != hipSuccess) return e;
             w.cap_list = need + need / 2;
         }

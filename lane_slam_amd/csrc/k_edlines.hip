@@ -1625,7 +1625,7 @@ void launch_kl_offsets(int n_frames, const int* frame_count, int capacity, int* 
 // -- no step back after the erase, so the KeyLine that slides into the erased place is never tested: in a run of consecutive
 // KeyLines that fail the test the 1st, 3rd, 5th ... are erased and the 2nd, 4th ... survive.  With lastgood(j) = the last KeyLine
 // in front of j that passes, erased(j) = fails(j) and (j - lastgood(j) - 1) even: a prefix maximum.  (LSDDetectorC::detect has the
-// step back, LSDDetector_custom.cpp:203-213: every failing KeyLine goes; lanefront_lsdkl.inc.)
+// step back, LSDDetector_custom.cpp:203-213: every failing KeyLine goes; lanefront_lsdkl.hip.)
 // k_kl_mask_flags: one workgroup per frame over the assembled (unmasked) KeyLines: erased[] and the frame's kept count.
 __global__ __launch_bounds__(256) void k_kl_mask_flags(const int* __restrict__ fo, const float* __restrict__ start_end, const uint8_t* __restrict__ masks,
                                                       int rows, int cols, int capacity, uint8_t* __restrict__ erased, int* __restrict__ kept_count)

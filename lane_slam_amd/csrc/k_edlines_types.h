@@ -1,4 +1,4 @@
-// Types shared by k_edlines.hip and the host-side sequencing (lanefront_keylines.inc).
+// Types shared by k_edlines.hip and the host-side sequencing (lanefront_keylines.hip).
 #pragma once
 #include "common.h"
 

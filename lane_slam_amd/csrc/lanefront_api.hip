@@ -12,9 +12,8 @@
 #include <chrono>
 #include <cstdlib>
 #include <functional>
-#include "common.h"
+#include "lanefront_handle.h"
 #include "lsd_bitplane.h"
-#include "jpeg_entropy.h"
 
 using namespace lf;
 
@@ -23,140 +22,8 @@ static const char* kStageNames[LF_N_STAGES] = {
     "lsd_order", "lsd_grow", "segments(normal+project+sanity)", "lbd_gray_blur_sobel", "lbd_descriptor",
     "assoc_pack", "assoc_mfma", "misc", "jpeg(idct+upsample+color)", "lsd_label(components+launch order)" };
 
-struct EvPair { hipEvent_t a, b; int st; };
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
 
-// JPEG ingest state (allocated on first use, grown on demand)
-struct JpegState {
-    lf::jpeg::WorkerPool pool;                      // persistent host threads
-    std::vector<lf::jpeg::FrameCoefs> frames;       // per-frame host coefficient lists (capacity is kept)
-    int rows = 0, cols = 0, max_frames = 0;         // geometry the planes were sized for
-    DevBuf planes, entries, block_end, hdrs, out;   // device
-    DevBuf gh_clean, gh_sub, gh_seg, gh_info, gh_coef;   // entropy decoding on the device (k_jhuff.hip)
-    std::vector<int> h_status;
-    void* h_stage = nullptr;                        // pinned staging: headers | block_end | entries
-    size_t h_stage_bytes = 0;
-    hipEvent_t staged = nullptr;                    // the last H2D out of h_stage has completed
-    bool staged_pending = false;
-    int* h_status_pinned = nullptr;                 // lf_jpeg_decode_batch_gpu_async: the per-frame status, read back behind status_done
-    int h_status_pinned_n = 0, status_frames = 0;
-    hipEvent_t status_done = nullptr;
-};
 
-struct lf_handle {
-    lf_config cfg;
-    int device = 0;
-    int max_frames = 0, cap_lines = 0;
-    hipStream_t stream = nullptr;
-    char err[512];
-    int err_code = 0;
-    // geometry
-    int Hc = 0, W = 0, Hs = 0, Ws = 0, Ww = 0;
-    size_t P = 0, Ps = 0;
-    lf_descriptor_params desc_params = { 1, 7, 2, 5 };      // BinaryDescriptor::Params (lf_set_descriptor_params)
-    bool lists_lost = false;     // lsd_grow_lists ran out of memory twice: no per-problem lists, run_detect refuses
-    int label_items_full = 0;    // LsdParams::label_items of a handle whose lists hold whole images (alloc_lsd_lists lowers it with rec_cap)
-    PreParams pre;
-    CannyParams canny;
-    LsdParams lsd;
-    SegParams seg;
-    ResizeTables rt;
-    int max_nsx = 0, max_nsy = 0;
-    // device buffers
-    uint8_t *d_frames = nullptr, *d_edges_u8 = nullptr;
-    DevBuf dbg_masks;                   // 0/255 byte form of the colour masks, expanded from the bit planes on demand
-    size_t frames_bytes = 0;            // allocation behind d_frames
-    uint32_t* d_bgr = nullptr;          // corrected working image, BGRX dword per pixel
-    uint8_t* d_gray = nullptr;          // BGR2GRAY of it, 1 byte per pixel (read by the LBD gradient stage)
-    DevBuf dbg_bgr;
-    uint32_t *d_strong = nullptr, *d_weak = nullptr, *d_maskbits = nullptr;
-    int *d_sdiv = nullptr, *d_hdiv = nullptr;
-    // unordered per-problem records of defined LSD pixels (k_lsd_grad -> k_lsd_order)
-    uint32_t* d_raddr = nullptr;
-    float* d_rdeg = nullptr;
-    double *d_rmod = nullptr, *d_rcs = nullptr, *d_rsn = nullptr;
-    float *d_rsd = nullptr, *d_csd = nullptr;      // LsdParams::r_sd, c_sd
-    int* d_nrec = nullptr;
-    uint8_t* d_zero = nullptr; size_t zero_bytes = 0;   // d_maxgrad | d_nrec | d_nlow | d_tile_count | d_overflow: the counters a batch starts from zero, ONE memset (each memset is a dispatch of its own and waited 0.3 ms in a busy pipeline)
-    bool overflow_zeroed = false;
-    // lsd_seed_order = OPENCV32 only: pixels with a non-zero but undefined gradient (k_lsd_grad -> k_lsd_seed32)
-    uint32_t* d_laddr = nullptr; double* d_lmod = nullptr; int* d_nlow = nullptr;
-    unsigned long long *d_sort_a = nullptr, *d_sort_b = nullptr;
-    DevBuf dbg_ang, dbg_mod;
-    unsigned long long* d_maxgrad = nullptr;
-    uint32_t *d_order_a = nullptr, *d_order_b = nullptr, *d_reg = nullptr;
-    uint32_t *d_cxy = nullptr, *d_gused = nullptr;
-    float* d_cdeg = nullptr;
-    double *d_cmod = nullptr, *d_ccs = nullptr, *d_csn = nullptr;
-    uint32_t* d_tile_list = nullptr;
-    int* d_tile_count = nullptr;
-    int* d_row_start = nullptr;
-    int *d_norder = nullptr, *d_counts = nullptr, *d_seg_offset = nullptr, *d_frame_offset = nullptr, *d_overflow = nullptr;
-    float* d_slot_lines = nullptr;
-    uint16_t *d_clabel = nullptr, *d_comp_list = nullptr;     // connected components of the LSD problems (k_lsd_label)
-    int* d_comp_count = nullptr;
-    int* d_perm = nullptr;
-    int* d_comp_key = nullptr;
-    float* d_tmp_lines = nullptr;                             // lines in completion order + their seed positions (k_lsd_grow)
-    int* d_tmp_tags = nullptr;
-    double* d_pend_rec = nullptr;     // pending regions of every LSD problem (k_lsd_grow -> k_lsd_eval): 12 doubles each,
-    int* d_pend_tag = nullptr;        // their seed positions,
-    int* d_pend_count = nullptr;      // and how many per problem
-    int* d_seg_frame = nullptr;
-    uint32_t* d_dxy = nullptr;          // LBD gradients, dx | dy << 16 per pixel
-    DevBuf dbg_dx, dbg_dy;
-    float *d_gauss_g = nullptr, *d_gauss_l = nullptr;
-    int *d_xofs = nullptr, *d_y0 = nullptr, *d_y1 = nullptr;
-    float *d_xa = nullptr, *d_yb = nullptr;
-    // output staging (device side of host-output calls, and the plugin path)
-    lf_segments d_out;
-    double* d_normals64 = nullptr;
-    float* d_centers = nullptr;
-    int out_capacity = 0;
-    // associator scratch (grown on demand)
-    DevBuf a_q, a_m, a_mx, a_mcx, a_best, a_idx, a_dist, a_qn, a_mn;
-    DevBuf km_pts, km_lab, km_f64, km_cnt;
-    DevBuf kn_hist, kn_count, kn_off, kn_total;       // radiusMatch scratch
-    AssocScratch a_ws;
-    struct MatcherState* matcher = nullptr;     // BinaryDescriptorMatcher's dataset (lanefront_matcher.inc)
-    // pinned host scalars
-    int* h_pinned = nullptr;     // [0] total segments, [1] overflow ... [6] entries the per-problem lists would have needed (d_overflow[5])
-    const uint8_t* pend_in = nullptr; int pend_n = 0; lf_segments pend_out; bool pend_describe = false;   // the batch in flight (lsd_records_retry)
-    int lists_grown = 0;         // times the per-problem lists were reallocated
-    int last_frames = 0;
-    bool plugin_ready = false;
-    bool pending = false;
-    // plugin path: what lf_detect_lines hands out is fetched ONCE per image, behind the kernels of lf_set_image, into pinned host
-    // memory (the first kPlugEager segments of the SegmentList + the three mask images): lf_detect_lines is then a host copy
-    uint8_t* plug_host = nullptr; size_t plug_host_bytes = 0; uint8_t* plug_in = nullptr; size_t plug_in_bytes = 0;
-    int plug_eager = 0;
-    bool pending_keylines = false;        // the batch in flight is lf_keylines_batch_async's: lf_wait reads the KeyLine state
-    bool grow_mixed = false;     // the last batch had problems beyond the slice in numbers (> 1 %): one launch with both kinds of problem code
-    int grow_lds_level = 0;      // index into kGrowLdsKb: k_lsd_grow's LDS slice, moved by the share of problems that overflowed it in the last batch
-    int detector = LF_DETECTOR_LSD;       // what lf_process_batch runs for a-2 .. a-4 (lf_set_detector)
-    lf_edlines_params ed_params;
-    int detector_failures = 0;            // frames of the last completed batch on which the EDLines detector gave up
-    int tie_rule = LF_TIE_MIHASHER;   // lf_associate: the reference's rule unless lf_set_tie_rule says otherwise
-    int env_lds_level = -1;      // LF_GROW_LDS_LEVEL / LF_GROW_MIXED: test and tuning overrides, read when the handle is created, clamped
-    int env_mixed = -1;
-    int env_bitmap = 1;          // LF_GROW_BITMAP=0: the row-list form of k_lsd_grow (rounds 1 - 3) instead of the bit-plane form (A/B measurements); > 1: see launch_lsd_grow
-    int env_kl_lds_lines = 0;    // LF_KL_LDS_LINES (test hook of the KeyLine grouping, lanefront_keylines.inc)
-    int pending_problems = 0;
-    int pending_capacity = 0;
-    std::vector<int> h_counts, h_seg_offset;
-    JpegState* jpeg = nullptr;
-    struct KlState* kl = nullptr;       // EDLines / KeyLines state (lanefront_keylines.inc), allocated on first use
-    struct LsdKlState* lsdkl = nullptr; // LSDDetectorC over octaves (lanefront_lsdkl.inc): sub-handles per pyramid level
-    DevBuf m_fo, m_color, m_pn, m_nm, m_gr, m_keep, m_counts, m_boff, m_body, m_bad;   // SegmentList glue scratch
-    // profiling
-    bool profiling = false;
-    std::vector<EvPair> ev_free, ev_used;
-    double ms[LF_N_STAGES];
-    int32_t launches[LF_N_STAGES];
-};
 
 extern "C" void lf_set_error(lf_handle* h, int code, const char* fmt, ...)
 {
@@ -170,32 +37,11 @@ extern "C" void lf_set_error(lf_handle* h, int code, const char* fmt, ...)
 
 static char g_create_err[512] = "no error";
 
-// LF_ALLOC_TRACE=1: one line per device allocation of a handle on stderr (what the footprint figures in DESIGN.md §3 are made of)
-static bool alloc_trace() { static const bool on = [] { const char* e = getenv("LF_ALLOC_TRACE"); return e && *e && *e != '0'; }(); return on; }
-template <typename T>
-static int dalloc_(lf_handle* h, T** p, size_t count, const char* what)
-{
-    const size_t bytes = count ? count * sizeof(T) : sizeof(T);
-    LF_HIP_CHECK(h, hipMalloc((void**)p, bytes));
-    if (alloc_trace()) fprintf(stderr, "lanefront alloc %-28s %12zu B\n", what, bytes);
-    return LF_OK;
-}
-#define dalloc(h, p, count) dalloc_(h, p, count, #p)
 
-static int ensure(lf_handle* h, DevBuf& b, size_t bytes)
-{
-    if (b.bytes >= bytes) return LF_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr; b.bytes = 0;
-    size_t want = bytes + bytes / 4 + 256;
-    LF_HIP_CHECK(h, hipMalloc(&b.p, want));
-    b.bytes = want;
-    return LF_OK;
-}
 
 // Per-stage timing with HIP events recorded on the handle's stream.  Events are only
 // recorded here (no host synchronisation inside the pipeline); lf_get_timing resolves them.
-static void timing_resolve(lf_handle* h)
+void lf::timing_resolve(lf_handle* h)
 {
     for (EvPair& e : h->ev_used) {
         (void)hipEventSynchronize(e.b);
@@ -206,33 +52,11 @@ static void timing_resolve(lf_handle* h)
     h->ev_used.clear();
 }
 
-struct StageTimer {
-    lf_handle* h; int st; EvPair e; bool on;
-    StageTimer(lf_handle* h_, int st_) : h(h_), st(st_), on(h_->profiling)
-    {
-        if (!on) return;
-        if (h->ev_free.empty()) {
-            if (h->ev_used.size() >= 8192) timing_resolve(h);
-            else {
-                EvPair n; n.st = 0;
-                if (hipEventCreate(&n.a) != hipSuccess || hipEventCreate(&n.b) != hipSuccess) { on = false; return; }
-                h->ev_free.push_back(n);
-            }
-        }
-        e = h->ev_free.back(); h->ev_free.pop_back();
-        e.st = st;
-        (void)hipEventRecord(e.a, h->stream);
-    }
-    ~StageTimer()
-    {
-        if (on) { (void)hipEventRecord(e.b, h->stream); h->ev_used.push_back(e); }
-        h->launches[st] += 1;
-    }
-};
 
 static int cv_round_host(double v) { return dm::round_half_even(v); }
 
-static thread_local bool g_lsd_only_create = false;      // set around the lf_create of an LSD-only sub-handle (lanefront_lsdkl.inc)
+thread_local bool lf::g_lsd_only_create = false;      // set around the lf_create of an LSD-only sub-handle (lanefront_lsdkl.hip)
+
 
 static int build_params(lf_handle* h)
 {
@@ -245,7 +69,7 @@ static int build_params(lf_handle* h)
         return LF_ERR_BAD_ARG;
     }
     // (the bit planes of the front end are whole 32-bit words per row; a sub-handle that only runs the LSD stages on gray pyramid
-    // levels -- lanefront_lsdkl.inc -- never touches them)
+    // levels -- lanefront_lsdkl.hip -- never touches them)
     if (h->W % 32 != 0 && !g_lsd_only_create) { lf_set_error(h, LF_ERR_UNSUPPORTED, "img_cols must be a multiple of 32 (got %d)", h->W); return LF_ERR_UNSUPPORTED; }
     h->P = (size_t)h->Hc * h->W;
     h->Ww = (h->W + 31) / 32;
@@ -497,13 +321,11 @@ extern "C" int lf_set_descriptor_params(lf_handle* h, const lf_descriptor_params
 // the arrays whose stride is LsdParams::rec_cap: records, sort scratch, seed lists, compact arrays, labels, the region scratch, low records
 static void free_lsd_lists(lf_handle* h)
 {
-    void* ptrs[] = { h->d_raddr, h->d_rdeg, h->d_rmod, h->d_rcs, h->d_rsn, h->d_sort_a, h->d_sort_b, h->d_order_a, h->d_order_b, h->d_cxy, h->d_cdeg,
-                     h->d_cmod, h->d_ccs, h->d_reg, h->d_clabel, h->d_laddr, h->d_lmod, h->d_rsd, h->d_csd };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    h->d_rsd = nullptr; h->d_csd = nullptr; h->lsd.r_sd = nullptr; h->lsd.c_sd = nullptr;
-    h->d_raddr = nullptr; h->d_rdeg = nullptr; h->d_rmod = nullptr; h->d_rcs = nullptr; h->d_rsn = nullptr; h->d_sort_a = nullptr; h->d_sort_b = nullptr;
-    h->d_order_a = nullptr; h->d_order_b = nullptr; h->d_cxy = nullptr; h->d_cdeg = nullptr; h->d_cmod = nullptr; h->d_ccs = nullptr; h->d_csn = nullptr;
-    h->d_reg = nullptr; h->d_clabel = nullptr; h->d_laddr = nullptr; h->d_lmod = nullptr;
+    for (auto* b : { &h->d_raddr, &h->d_order_a, &h->d_order_b, &h->d_cxy, &h->d_reg, &h->d_laddr }) b->reset();
+    for (auto* b : { &h->d_rdeg, &h->d_cdeg, &h->d_rsd, &h->d_csd }) b->reset();
+    for (auto* b : { &h->d_rmod, &h->d_rcs, &h->d_rsn, &h->d_cmod, &h->d_ccs, &h->d_lmod }) b->reset();
+    h->d_sort_a.reset(); h->d_sort_b.reset(); h->d_clabel.reset();
+    h->lsd.r_sd = nullptr; h->lsd.c_sd = nullptr; h->d_csn = nullptr;
 }
 
 static int alloc_lsd_lists(lf_handle* h, int rec_cap)
@@ -568,7 +390,7 @@ static int alloc_buffers(lf_handle* h)
     {
         h->zero_bytes = nprob * 8 + nprob * 4 + nprob * 4 + 16 + 32;
         if (dalloc(h, &h->d_zero, h->zero_bytes)) return LF_ERR_HIP;
-        h->d_maxgrad = reinterpret_cast<unsigned long long*>(h->d_zero);
+        h->d_maxgrad = reinterpret_cast<unsigned long long*>(h->d_zero.p);
         h->d_nrec = reinterpret_cast<int*>(h->d_zero + nprob * 8);
         int* nlow = h->d_nrec + nprob;
         if (h->cfg.lsd_seed_order == LF_LSD_SEED_OPENCV32) h->d_nlow = nlow;
@@ -580,12 +402,14 @@ static int alloc_buffers(lf_handle* h)
     lf_segments& o = h->d_out;
     memset(&o, 0, sizeof(o));
     o.capacity = (int)cap;
-    if (dalloc(h, &o.lines, cap * 4) || dalloc(h, &o.normals, cap * 2) || dalloc(h, &o.color, cap) ||
-        dalloc(h, &o.pixels_normalized, cap * 4) || dalloc(h, &o.ground, cap * 4) || dalloc(h, &o.keep, cap) ||
-        dalloc(h, &o.desc, cap * 72) || dalloc(h, &o.code, cap * 32))
+    if (dalloc(h, &h->out_lines, cap * 4) || dalloc(h, &h->out_normals, cap * 2) || dalloc(h, &h->out_color, cap) ||
+        dalloc(h, &h->out_pixels_normalized, cap * 4) || dalloc(h, &h->out_ground, cap * 4) || dalloc(h, &h->out_keep, cap) ||
+        dalloc(h, &h->out_desc, cap * 72) || dalloc(h, &h->out_code, cap * 32))
         return LF_ERR_HIP;
+    o.lines = h->out_lines; o.normals = h->out_normals; o.color = h->out_color; o.pixels_normalized = h->out_pixels_normalized;
+    o.ground = h->out_ground; o.keep = h->out_keep; o.desc = h->out_desc; o.code = h->out_code;
     o.frame_offset = h->d_frame_offset;
-    LF_HIP_CHECK(h, hipHostMalloc((void**)&h->h_pinned, 16 * sizeof(int)));
+    LF_HIP_CHECK(h, h->h_pinned.alloc(16 * sizeof(int)));
     return LF_OK;
 }
 
@@ -603,48 +427,16 @@ extern "C" const char* lf_last_error(const lf_handle* h) { return h ? h->err : g
 
 extern "C" const char* lf_stage_name(int stage) { return (stage >= 0 && stage < LF_N_STAGES) ? kStageNames[stage] : "?"; }
 
-struct KlState;
-static void kl_free(KlState* k);
-struct LsdKlState;
-static void lsdkl_free(LsdKlState* k);
-
-static void matcher_free(struct MatcherState* m);
 extern "C" void lf_destroy(lf_handle* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* ptrs[] = { h->d_frames, h->d_bgr, h->d_gray, h->dbg_masks.p, h->d_edges_u8, h->d_strong, h->d_weak, h->d_maskbits, h->d_sdiv, h->d_hdiv,
-                     h->d_zero, h->dbg_ang.p, h->dbg_mod.p, h->d_gused, h->d_row_start, h->d_tile_list,
-                     h->d_norder, h->d_counts, h->d_seg_offset, h->d_frame_offset, h->d_slot_lines,
-                     h->d_seg_frame, h->d_comp_list, h->d_comp_count, h->d_perm, h->d_comp_key, h->d_tmp_lines, h->d_tmp_tags, h->d_pend_rec, h->d_pend_tag, h->d_pend_count, h->d_dxy, h->dbg_dx.p, h->dbg_dy.p, h->d_gauss_g, h->d_gauss_l, h->d_xofs, h->d_y0, h->d_y1,
-                     h->d_xa, h->d_yb, h->d_out.lines, h->d_out.normals, h->d_out.color, h->d_out.pixels_normalized,
-                     h->d_out.ground, h->d_out.keep, h->d_out.desc, h->d_out.code, h->d_normals64, h->d_centers,
-                     h->km_pts.p, h->km_lab.p, h->km_f64.p, h->km_cnt.p, h->kn_hist.p, h->kn_count.p, h->kn_off.p, h->kn_total.p, h->a_q.p, h->a_m.p, h->a_mx.p, h->a_mcx.p, h->a_best.p, h->a_idx.p, h->a_dist.p, h->a_qn.p, h->a_mn.p, h->dbg_bgr.p };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    free_lsd_lists(h);
-    assoc_scratch_free(h->a_ws);
-    if (h->h_pinned) (void)hipHostFree(h->h_pinned);
-    if (h->plug_host) (void)hipHostFree(h->plug_host);
-    if (h->plug_in) (void)hipHostFree(h->plug_in);
-    for (DevBuf* b : { &h->m_fo, &h->m_color, &h->m_pn, &h->m_nm, &h->m_gr, &h->m_keep, &h->m_counts, &h->m_boff, &h->m_body, &h->m_bad })
-        if (b->p) (void)hipFree(b->p);
-    if (h->jpeg) {
-        JpegState* j = h->jpeg;
-        for (DevBuf* b : { &j->planes, &j->entries, &j->block_end, &j->hdrs, &j->out, &j->gh_clean, &j->gh_sub, &j->gh_seg, &j->gh_info, &j->gh_coef }) if (b->p) (void)hipFree(b->p);
-        if (j->h_stage) (void)hipHostFree(j->h_stage);
-        if (j->staged) (void)hipEventDestroy(j->staged);
-        if (j->status_done) (void)hipEventDestroy(j->status_done);
-        if (j->h_status_pinned) (void)hipHostFree(j->h_status_pinned);
-        delete j;
-    }
-    kl_free(h->kl);
-    lsdkl_free(h->lsdkl);
-    matcher_free(h->matcher);
+    h->lsdkl.reset();            // (its sub-handles borrow this handle's stream)
     timing_resolve(h);
     for (EvPair& e : h->ev_free) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                    // the buffers and the substates free themselves
 }
 
 extern "C" int lf_create(const lf_config* cfg, int device_id, int max_frames, int max_lines_per_color, lf_handle** out)
@@ -700,7 +492,7 @@ extern "C" int lf_synchronize(lf_handle* h)
 }
 
 // detect stages a-1..a-4 on device-resident frames
-static int run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_working_image)
+int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_working_image)
 {
     hipStream_t s = h->stream;
     if (h->lists_lost) { lf_set_error(h, LF_ERR_HIP, "the handle lost its LSD lists to an out-of-memory growth (lf_wait / lf_set_image reported it)"); return LF_ERR_HIP; }
@@ -760,10 +552,8 @@ static int run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_wo
     return LF_OK;
 }
 
-static int run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n);     // lanefront_keylines.inc
-static void keylines_pending_result(lf_handle* h, int* total, int* overflow);
 
-static int run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe)
+int lf::run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe)
 {
     hipStream_t s = h->stream;
     {
@@ -939,15 +729,10 @@ constexpr int kPlugEager = 1024;     // segments fetched with the image (more th
 
 // the caller's image -> pinned staging (it may reuse its buffer at once, np.copy in line_detector_lsd.py:136) -> the device,
 // asynchronously: no synchronisation before the kernels
-static int plugin_stage_image(lf_handle* h, const uint8_t* bgr, int rows, int cols, int row_stride_bytes)
+int lf::plugin_stage_image(lf_handle* h, const uint8_t* bgr, int rows, int cols, int row_stride_bytes)
 {
     const size_t need = (size_t)rows * cols * 3;
-    if (h->plug_in_bytes < need) {
-        if (h->plug_in) (void)hipHostFree(h->plug_in);
-        h->plug_in = nullptr; h->plug_in_bytes = 0;
-        LF_HIP_CHECK(h, hipHostMalloc((void**)&h->plug_in, need));
-        h->plug_in_bytes = need;
-    }
+    if (h->plug_in.bytes < need) LF_HIP_CHECK(h, h->plug_in.alloc(need));
     LF_HIP_CHECK(h, hipStreamSynchronize(h->stream));          // the previous image's copy out of the staging buffer (normally long done)
     for (int y = 0; y < rows; ++y) memcpy(h->plug_in + (size_t)y * cols * 3, bgr + (size_t)y * row_stride_bytes, (size_t)cols * 3);
     LF_HIP_CHECK(h, hipMemcpyAsync(h->d_frames, h->plug_in, need, hipMemcpyHostToDevice, h->stream));
@@ -956,17 +741,12 @@ static int plugin_stage_image(lf_handle* h, const uint8_t* bgr, int rows, int co
 
 // queue the copies of everything lf_detect_lines returns behind the kernels; layout of plug_host:
 // [lines eager x 16][normals64 eager x 16][centers eager x 8][3 mask images]
-static int plugin_fetch_results(lf_handle* h)
+int lf::plugin_fetch_results(lf_handle* h)
 {
     hipStream_t s = h->stream;
     const int eager = kPlugEager < 3 * h->cap_lines ? kPlugEager : 3 * h->cap_lines;
     const size_t need = (size_t)eager * 40 + 3 * h->P;
-    if (h->plug_host_bytes < need) {
-        if (h->plug_host) (void)hipHostFree(h->plug_host);
-        h->plug_host = nullptr; h->plug_host_bytes = 0;
-        LF_HIP_CHECK(h, hipHostMalloc((void**)&h->plug_host, need));
-        h->plug_host_bytes = need;
-    }
+    if (h->plug_host.bytes < need) LF_HIP_CHECK(h, h->plug_host.alloc(need));
     h->plug_eager = eager;
     uint8_t* p = h->plug_host;
     LF_HIP_CHECK(h, hipMemcpyAsync(p, h->d_out.lines, (size_t)eager * 16, hipMemcpyDeviceToHost, s));
@@ -1543,7 +1323,7 @@ extern "C" int lf_jpeg_decode_batch(lf_handle* h, const uint8_t* const* jpeg, co
     }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     if (!h->jpeg) {
-        h->jpeg = new (std::nothrow) JpegState();
+        h->jpeg.reset(new (std::nothrow) JpegState());
         if (!h->jpeg) { lf_set_error(h, LF_ERR_HIP, "out of host memory"); return LF_ERR_HIP; }
         LF_HIP_CHECK(h, hipEventCreateWithFlags(&h->jpeg->staged, hipEventDisableTiming));
     }
@@ -1598,17 +1378,11 @@ extern "C" int lf_jpeg_decode_batch(lf_handle* h, const uint8_t* const* jpeg, co
     const auto t_w = now();
     if (J.staged_pending) { LF_HIP_CHECK(h, hipEventSynchronize(J.staged)); J.staged_pending = false; }
     t_wait = ms_since(t_w);
-    if (J.h_stage_bytes < stage_bytes) {
-        if (J.h_stage) (void)hipHostFree(J.h_stage);
-        J.h_stage = nullptr; J.h_stage_bytes = 0;
-        const size_t want = stage_bytes + stage_bytes / 4 + 4096;
-        LF_HIP_CHECK(h, hipHostMalloc(&J.h_stage, want, hipHostMallocDefault));
-        J.h_stage_bytes = want;
-    }
+    if (J.h_stage.bytes < stage_bytes) LF_HIP_CHECK(h, J.h_stage.alloc(stage_bytes + stage_bytes / 4 + 4096));
     const auto t_p = now();
     {
         // pack headers | block ends | entries into the pinned staging buffer, frames in parallel
-        uint8_t* st = static_cast<uint8_t*>(J.h_stage);
+        uint8_t* st = static_cast<uint8_t*>(J.h_stage.p);
         std::atomic<int> next(0);
         J.pool.run(nt, [&](int) {
             for (;;) {
@@ -1795,8 +1569,3 @@ extern "C" int lf_deserialize_segments(lf_handle* h, const uint8_t* bodies, int 
     }
     return LF_OK;
 }
-
-#include "lanefront_keylines.inc"
-#include "lanefront_lsdkl.inc"
-#include "lanefront_matcher.inc"
-#include "lanefront_jpeg_gpu.inc"

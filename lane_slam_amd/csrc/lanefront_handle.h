@@ -1,0 +1,258 @@
+// lanefront's host side: the handle, its substates and the few helpers the translation units of the C ABI share
+// (lanefront_api.hip, lanefront_keylines.hip, lanefront_lsdkl.hip, lanefront_matcher.hip, lanefront_jpeg_gpu.hip).
+// Host code only; common.h does not include it (tests/hostsim builds lsd_grow.h on the CPU).
+#pragma once
+#include <stdio.h>
+#include <stdlib.h>
+#include <memory>
+#include <utility>
+#include <vector>
+#include "common.h"
+#include "jpeg_entropy.h"
+#include "k_edlines_types.h"
+
+namespace lf {
+
+struct EvPair { hipEvent_t a, b; int st; };
+
+// JPEG ingest state (allocated on first use, grown on demand)
+struct JpegState {
+    lf::jpeg::WorkerPool pool;                      // persistent host threads
+    std::vector<lf::jpeg::FrameCoefs> frames;       // per-frame host coefficient lists (capacity is kept)
+    int rows = 0, cols = 0, max_frames = 0;         // geometry the planes were sized for
+    DevBuf planes, entries, block_end, hdrs, out;   // device
+    DevBuf gh_clean, gh_sub, gh_seg, gh_info, gh_coef;   // entropy decoding on the device (k_jhuff.hip)
+    std::vector<int> h_status;
+    HostArray<void> h_stage;                        // pinned staging: headers | block_end | entries
+    hipEvent_t staged = nullptr;                    // the last H2D out of h_stage has completed
+    bool staged_pending = false;
+    HostArray<int> h_status_pinned;                 // lf_jpeg_decode_batch_gpu_async: the per-frame status, read back behind status_done
+    int status_frames = 0;
+    hipEvent_t status_done = nullptr;
+    ~JpegState()
+    {
+        if (staged) (void)hipEventDestroy(staged);
+        if (status_done) (void)hipEventDestroy(status_done);
+    }
+};
+
+struct KlState {
+    int n_octaves = 0, max_frames = 0;
+    int W[LF_MAX_OCTAVES], H[LF_MAX_OCTAVES], cap[LF_MAX_OCTAVES], max_edges[LF_MAX_OCTAVES], max_lines[LF_MAX_OCTAVES];
+    DevBuf src[LF_MAX_OCTAVES], blur[LF_MAX_OCTAVES], dxy[LF_MAX_OCTAVES], g[LF_MAX_OCTAVES], anchors[LF_MAX_OCTAVES], part[LF_MAX_OCTAVES],
+           chain[LF_MAX_OCTAVES], sid[LF_MAX_OCTAVES], gmarks[LF_MAX_OCTAVES], counts[LF_MAX_OCTAVES], l_ep[LF_MAX_OCTAVES],
+           l_c[LF_MAX_OCTAVES], l_dir[LF_MAX_OCTAVES], l_npx[LF_MAX_OCTAVES], l_sal[LF_MAX_OCTAVES], tl[LF_MAX_OCTAVES], rs_tab[LF_MAX_OCTAVES], ework[LF_MAX_OCTAVES];
+    DevBuf frame_count, frame_offset, status, totals, line_frame, big;      // big: grouping tables of frames with more than 4096 lines
+    // the detect mask (round 5): the KeyLines are assembled into these, the kept ones move to the caller's arrays
+    DevBuf m_fo, m_totals, m_erased, m_kept, m_masks, t_start_end, t_in_octave, t_angle, t_npx, t_len, t_octave, t_class, t_response, t_size, t_pt, t_sal, t_frame;
+    DevBuf o_start_end, o_in_octave, o_angle, o_npx, o_len, o_octave, o_class, o_response, o_size, o_pt, o_sal, o_desc, o_code;
+    int out_capacity = 0;
+    DevBuf in_gray;                 // staging of host gray images
+    DevBuf any_tmp, any_blur;       // Params::ksize_ other than 5: the row sums (int32) and the blurred image of the octave at hand
+    DevBuf d_frame, d_io, d_angle, d_npx, d_oct, d_desc, d_code, d_n;     // lf_describe_keylines staging
+    HostArray<int> h_pinned;        // totals [2], then frame status [max_frames]
+    bool marks_in_lds[LF_MAX_OCTAVES];
+    DevBuf aflags[LF_MAX_OCTAVES];  // the anchor candidate planes k_ed_grad writes (scan interval 2)
+    bool aflags_on[LF_MAX_OCTAVES] = {};
+    size_t lds_bytes = 0;
+    int last_octaves = 0, last_frames = 0;
+};
+
+struct LsdKlState {
+    lf_handle* sub[LF_MAX_OCTAVES] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    DevBuf pyr[LF_MAX_OCTAVES];          // levels 1.. of the detect pyramid (level 0 is the caller's gray image)
+    DevBuf gray0, frame_count, frame_offset, line_frame, totals;
+    DevBuf o_start_end, o_in_octave, o_angle, o_npx, o_len, o_octave, o_class, o_response, o_size, o_pt, o_desc, o_code;
+    int H[LF_MAX_OCTAVES], W[LF_MAX_OCTAVES];
+    HostArray<int> h_pinned;
+    lf_lsd_options sub_opts[LF_MAX_OCTAVES];        // the options each cached sub-handle was made with
+    DevBuf masks;                                   // a host caller's masks on the device
+    ~LsdKlState();                                  // destroys the sub-handles (lanefront_lsdkl.hip)
+};
+
+struct MatcherState {
+    DevBuf codes;                  // the set: [total][32]
+    std::vector<std::pair<int, int> > index_map;   // indexesMap: (first row, image number), keys ascending
+    int num_images = 0;            // numImages
+    int total = 0;                 // nextAddedIndex
+    DevBuf q, idx, dist, off;      // staging for host callers
+};
+
+}  // namespace lf
+
+struct lf_handle {
+    lf_config cfg;
+    int device = 0;
+    int max_frames = 0, cap_lines = 0;
+    hipStream_t stream = nullptr;
+    char err[512];
+    int err_code = 0;
+    // geometry
+    int Hc = 0, W = 0, Hs = 0, Ws = 0, Ww = 0;
+    size_t P = 0, Ps = 0;
+    lf_descriptor_params desc_params = { 1, 7, 2, 5 };      // BinaryDescriptor::Params (lf_set_descriptor_params)
+    bool lists_lost = false;     // lsd_grow_lists ran out of memory twice: no per-problem lists, run_detect refuses
+    int label_items_full = 0;    // LsdParams::label_items of a handle whose lists hold whole images (alloc_lsd_lists lowers it with rec_cap)
+    lf::PreParams pre;
+    lf::CannyParams canny;
+    lf::LsdParams lsd;
+    lf::SegParams seg;
+    lf::ResizeTables rt;
+    int max_nsx = 0, max_nsy = 0;
+    // device buffers
+    lf::DevArray<uint8_t> d_frames, d_edges_u8;
+    lf::DevBuf dbg_masks;                   // 0/255 byte form of the colour masks, expanded from the bit planes on demand
+    size_t frames_bytes = 0;            // allocation behind d_frames
+    lf::DevArray<uint32_t> d_bgr;         // corrected working image, BGRX dword per pixel
+    lf::DevArray<uint8_t> d_gray;         // BGR2GRAY of it, 1 byte per pixel (read by the LBD gradient stage)
+    lf::DevBuf dbg_bgr;
+    lf::DevArray<uint32_t> d_strong, d_weak, d_maskbits;
+    lf::DevArray<int> d_sdiv, d_hdiv;
+    // unordered per-problem records of defined LSD pixels (k_lsd_grad -> k_lsd_order)
+    lf::DevArray<uint32_t> d_raddr;
+    lf::DevArray<float> d_rdeg;
+    lf::DevArray<double> d_rmod, d_rcs, d_rsn;
+    lf::DevArray<float> d_rsd, d_csd;     // LsdParams::r_sd, c_sd
+    int* d_nrec = nullptr;
+    lf::DevArray<uint8_t> d_zero; size_t zero_bytes = 0;  // d_maxgrad | d_nrec | d_nlow | d_tile_count | d_overflow: the counters a batch starts from zero, ONE memset (each memset is a dispatch of its own and waited 0.3 ms in a busy pipeline)
+    bool overflow_zeroed = false;
+    // lsd_seed_order = OPENCV32 only: pixels with a non-zero but undefined gradient (k_lsd_grad -> k_lsd_seed32)
+    lf::DevArray<uint32_t> d_laddr; lf::DevArray<double> d_lmod; int* d_nlow = nullptr;
+    lf::DevArray<unsigned long long> d_sort_a, d_sort_b;
+    lf::DevBuf dbg_ang, dbg_mod;
+    unsigned long long* d_maxgrad = nullptr;
+    lf::DevArray<uint32_t> d_order_a, d_order_b, d_reg;
+    lf::DevArray<uint32_t> d_cxy, d_gused;
+    lf::DevArray<float> d_cdeg;
+    lf::DevArray<double> d_cmod, d_ccs;
+    double* d_csn = nullptr;          // d_ccs + 1
+    lf::DevArray<uint32_t> d_tile_list;
+    int* d_tile_count = nullptr;
+    lf::DevArray<int> d_row_start;
+    lf::DevArray<int> d_norder, d_counts, d_seg_offset, d_frame_offset;
+    int* d_overflow = nullptr;
+    lf::DevArray<float> d_slot_lines;
+    lf::DevArray<uint16_t> d_clabel, d_comp_list;    // connected components of the LSD problems (k_lsd_label)
+    lf::DevArray<int> d_comp_count;
+    lf::DevArray<int> d_perm;
+    lf::DevArray<int> d_comp_key;
+    lf::DevArray<float> d_tmp_lines;                            // lines in completion order + their seed positions (k_lsd_grow)
+    lf::DevArray<int> d_tmp_tags;
+    lf::DevArray<double> d_pend_rec;    // pending regions of every LSD problem (k_lsd_grow -> k_lsd_eval): 12 doubles each,
+    lf::DevArray<int> d_pend_tag;       // their seed positions,
+    lf::DevArray<int> d_pend_count;     // and how many per problem
+    lf::DevArray<int> d_seg_frame;
+    lf::DevArray<uint32_t> d_dxy;         // LBD gradients, dx | dy << 16 per pixel
+    lf::DevBuf dbg_dx, dbg_dy;
+    lf::DevArray<float> d_gauss_g, d_gauss_l;
+    lf::DevArray<int> d_xofs, d_y0, d_y1;
+    lf::DevArray<float> d_xa, d_yb;
+    // output staging (device side of host-output calls, and the plugin path)
+    lf_segments d_out;                  // views of the out_* arrays
+    lf::DevArray<float> out_lines, out_normals, out_pixels_normalized;
+    lf::DevArray<uint8_t> out_color, out_keep, out_code;
+    lf::DevArray<double> out_ground;
+    lf::DevArray<float> out_desc;
+    lf::DevArray<double> d_normals64;
+    lf::DevArray<float> d_centers;
+    int out_capacity = 0;
+    // associator scratch (grown on demand)
+    lf::DevBuf a_q, a_m, a_mx, a_mcx, a_best, a_idx, a_dist, a_qn, a_mn;
+    lf::DevBuf km_pts, km_lab, km_f64, km_cnt;
+    lf::DevBuf kn_hist, kn_count, kn_off, kn_total;       // radiusMatch scratch
+    lf::AssocScratch a_ws;
+    std::unique_ptr<lf::MatcherState> matcher;    // BinaryDescriptorMatcher's dataset (lanefront_matcher.hip)
+    // pinned host scalars
+    lf::HostArray<int> h_pinned;     // [0] total segments, [1] overflow ... [6] entries the per-problem lists would have needed (d_overflow[5])
+    const uint8_t* pend_in = nullptr; int pend_n = 0; lf_segments pend_out; bool pend_describe = false;   // the batch in flight (lsd_records_retry)
+    int lists_grown = 0;         // times the per-problem lists were reallocated
+    int last_frames = 0;
+    bool plugin_ready = false;
+    bool pending = false;
+    // plugin path: what lf_detect_lines hands out is fetched ONCE per image, behind the kernels of lf_set_image, into pinned host
+    // memory (the first kPlugEager segments of the SegmentList + the three mask images): lf_detect_lines is then a host copy
+    lf::HostArray<uint8_t> plug_host, plug_in;
+    int plug_eager = 0;
+    bool pending_keylines = false;        // the batch in flight is lf_keylines_batch_async's: lf_wait reads the KeyLine state
+    bool grow_mixed = false;     // the last batch had problems beyond the slice in numbers (> 1 %): one launch with both kinds of problem code
+    int grow_lds_level = 0;      // index into kGrowLdsKb: k_lsd_grow's LDS slice, moved by the share of problems that overflowed it in the last batch
+    int detector = LF_DETECTOR_LSD;       // what lf_process_batch runs for a-2 .. a-4 (lf_set_detector)
+    lf_edlines_params ed_params;
+    int detector_failures = 0;            // frames of the last completed batch on which the EDLines detector gave up
+    int tie_rule = LF_TIE_MIHASHER;   // lf_associate: the reference's rule unless lf_set_tie_rule says otherwise
+    int env_lds_level = -1;      // LF_GROW_LDS_LEVEL / LF_GROW_MIXED: test and tuning overrides, read when the handle is created, clamped
+    int env_mixed = -1;
+    int env_bitmap = 1;          // LF_GROW_BITMAP=0: the row-list form of k_lsd_grow (rounds 1 - 3) instead of the bit-plane form (A/B measurements); > 1: see launch_lsd_grow
+    int env_kl_lds_lines = 0;    // LF_KL_LDS_LINES (test hook of the KeyLine grouping, lanefront_keylines.hip)
+    int pending_problems = 0;
+    int pending_capacity = 0;
+    std::vector<int> h_counts, h_seg_offset;
+    std::unique_ptr<lf::JpegState> jpeg;
+    std::unique_ptr<lf::KlState> kl;      // EDLines / KeyLines state (lanefront_keylines.hip), allocated on first use
+    std::unique_ptr<lf::LsdKlState> lsdkl; // LSDDetectorC over octaves (lanefront_lsdkl.hip): sub-handles per pyramid level
+    lf::DevBuf m_fo, m_color, m_pn, m_nm, m_gr, m_keep, m_counts, m_boff, m_body, m_bad;   // SegmentList glue scratch
+    // profiling
+    bool profiling = false;
+    std::vector<lf::EvPair> ev_free, ev_used;
+    double ms[LF_N_STAGES];
+    int32_t launches[LF_N_STAGES];
+};
+
+namespace lf {
+
+// LF_ALLOC_TRACE=1: one line per device allocation of a handle on stderr (what the footprint figures in DESIGN.md §3 are made of)
+inline bool alloc_trace() { static const bool on = [] { const char* e = getenv("LF_ALLOC_TRACE"); return e && *e && *e != '0'; }(); return on; }
+template <typename T>
+inline int dalloc_(lf_handle* h, DevArray<T>* p, size_t count, const char* what)
+{
+    const size_t bytes = count ? count * sizeof(T) : sizeof(T);
+    LF_HIP_CHECK(h, p->alloc(bytes));
+    if (alloc_trace()) fprintf(stderr, "lanefront alloc %-28s %12zu B\n", what, bytes);
+    return LF_OK;
+}
+#define dalloc(h, p, count) dalloc_(h, p, count, #p)
+
+inline int ensure(lf_handle* h, DevBuf& b, size_t bytes)
+{
+    if (b.bytes >= bytes) return LF_OK;
+    LF_HIP_CHECK(h, b.alloc(bytes + bytes / 4 + 256));       // (hipFree of the old buffer waits for the device)
+    return LF_OK;
+}
+
+void timing_resolve(lf_handle* h);
+struct StageTimer {
+    lf_handle* h; int st; EvPair e; bool on;
+    StageTimer(lf_handle* h_, int st_) : h(h_), st(st_), on(h_->profiling)
+    {
+        if (!on) return;
+        if (h->ev_free.empty()) {
+            if (h->ev_used.size() >= 8192) timing_resolve(h);
+            else {
+                EvPair n; n.st = 0;
+                if (hipEventCreate(&n.a) != hipSuccess || hipEventCreate(&n.b) != hipSuccess) { on = false; return; }
+                h->ev_free.push_back(n);
+            }
+        }
+        e = h->ev_free.back(); h->ev_free.pop_back();
+        e.st = st;
+        (void)hipEventRecord(e.a, h->stream);
+    }
+    ~StageTimer()
+    {
+        if (on) { (void)hipEventRecord(e.b, h->stream); h->ev_used.push_back(e); }
+        h->launches[st] += 1;
+    }
+};
+
+extern thread_local bool g_lsd_only_create;      // set around the lf_create of an LSD-only sub-handle (lanefront_lsdkl.hip; defined in lanefront_api.hip)
+
+// lanefront_api.hip
+int run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_working_image);
+int run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe);
+int plugin_stage_image(lf_handle* h, const uint8_t* bgr, int rows, int cols, int row_stride_bytes);
+int plugin_fetch_results(lf_handle* h);
+// lanefront_keylines.hip
+int run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n);
+void keylines_pending_result(lf_handle* h, int* total, int* overflow);
+
+}  // namespace lf

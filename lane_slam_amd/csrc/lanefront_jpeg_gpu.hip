@@ -2,10 +2,16 @@
 #define LF_JH_SB 48
 #endif
 #define LF_JH_SB_HOST LF_JH_SB
-// lanefront C ABI: JPEG ingest with the ENTROPY DECODER ON THE DEVICE (k_jhuff.hip).  Included at the end of
-// lanefront_api.hip.  The host parses the headers of every stream (markers, quantisation and Huffman tables: microseconds
+// lanefront C ABI: JPEG ingest with the ENTROPY DECODER ON THE DEVICE (k_jhuff.hip).  The host parses the headers of every stream (markers, quantisation and Huffman tables: microseconds
 // per frame) and copies the entropy-coded bytes into pinned memory; everything else -- unstuffing, Huffman decoding, DC
 // prediction, dequantisation, inverse DCT, upsampling, colour conversion -- runs on the handle's stream.
+
+#include <string.h>
+#include <algorithm>
+#include <atomic>
+#include "lanefront_handle.h"
+
+using namespace lf;
 
 // queued = true: lf_jpeg_decode_batch_gpu_async -- nothing waits for the stream, the per-frame status lands in pinned memory behind
 // an event (lf_jpeg_status)
@@ -25,7 +31,7 @@ static int jpeg_decode_gpu(lf_handle* h, const uint8_t* const* jpeg, const size_
     }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     if (!h->jpeg) {
-        h->jpeg = new (std::nothrow) JpegState();
+        h->jpeg.reset(new (std::nothrow) JpegState());
         if (!h->jpeg) { lf_set_error(h, LF_ERR_HIP, "out of host memory"); return LF_ERR_HIP; }
         LF_HIP_CHECK(h, hipEventCreateWithFlags(&h->jpeg->staged, hipEventDisableTiming));
     }
@@ -45,14 +51,8 @@ static int jpeg_decode_gpu(lf_handle* h, const uint8_t* const* jpeg, const size_
     for (int i = 0; i < n_frames; ++i) raw_total += (jpeg[i] ? jpeg_size[i] : 0) + 64;
     const size_t stage_bytes = fr_bytes + st_bytes + raw_total + 4096;
     if (stage_bytes >= (1ull << 32)) { lf_set_error(h, LF_ERR_CAPACITY, "batch too large"); return LF_ERR_CAPACITY; }
-    if (J.h_stage_bytes < stage_bytes) {
-        if (J.h_stage) (void)hipHostFree(J.h_stage);
-        J.h_stage = nullptr; J.h_stage_bytes = 0;
-        const size_t want = stage_bytes + stage_bytes / 4 + 4096;
-        LF_HIP_CHECK(h, hipHostMalloc(&J.h_stage, want, hipHostMallocDefault));
-        J.h_stage_bytes = want;
-    }
-    uint8_t* st = static_cast<uint8_t*>(J.h_stage);
+    if (J.h_stage.bytes < stage_bytes) LF_HIP_CHECK(h, J.h_stage.alloc(stage_bytes + stage_bytes / 4 + 4096));
+    uint8_t* st = static_cast<uint8_t*>(J.h_stage.p);
     DevFrame* hf = reinterpret_cast<DevFrame*>(st);
     int* hstat = reinterpret_cast<int*>(st + fr_bytes);
     uint8_t* hbytes = st + fr_bytes + st_bytes;
@@ -141,12 +141,7 @@ static int jpeg_decode_gpu(lf_handle* h, const uint8_t* const* jpeg, const size_
     LF_HIP_CHECK(h, hipGetLastError());
     // the per-frame status is only known once the device has decoded: one small read-back per call
     if (queued) {
-        if (J.h_status_pinned_n < n_frames) {
-            if (J.h_status_pinned) (void)hipHostFree(J.h_status_pinned);
-            J.h_status_pinned = nullptr; J.h_status_pinned_n = 0;
-            LF_HIP_CHECK(h, hipHostMalloc(reinterpret_cast<void**>(&J.h_status_pinned), (size_t)n_frames * sizeof(int), hipHostMallocDefault));
-            J.h_status_pinned_n = n_frames;
-        }
+        if (J.h_status_pinned.bytes < (size_t)n_frames * sizeof(int)) LF_HIP_CHECK(h, J.h_status_pinned.alloc((size_t)n_frames * sizeof(int)));
         LF_HIP_CHECK(h, hipMemcpyAsync(J.h_status_pinned, d_status, (size_t)n_frames * sizeof(int), hipMemcpyDeviceToHost, s));
         LF_HIP_CHECK(h, hipEventRecord(J.status_done, s));
         J.status_frames = n_frames;

@@ -1,48 +1,11 @@
 // lanefront C ABI, EDLines / multi-octave KeyLines part (include/lanefront.h, "EDLines detector"): device memory plan
-// and stage sequencing of k_edlines.hip + the KeyLine form of k_lbd.  Included at the end of lanefront_api.hip (it
-// needs lf_handle's internals).  Semantics: oracle/lf_oracle_edlines.c.
+// and stage sequencing of k_edlines.hip + the KeyLine form of k_lbd.  Semantics: oracle/lf_oracle_edlines.c.
 
-#include "k_edlines_types.h"
+#include <string.h>
+#include <algorithm>
+#include "lanefront_handle.h"
 
-struct KlState {
-    int n_octaves = 0, max_frames = 0;
-    int W[LF_MAX_OCTAVES], H[LF_MAX_OCTAVES], cap[LF_MAX_OCTAVES], max_edges[LF_MAX_OCTAVES], max_lines[LF_MAX_OCTAVES];
-    DevBuf src[LF_MAX_OCTAVES], blur[LF_MAX_OCTAVES], dxy[LF_MAX_OCTAVES], g[LF_MAX_OCTAVES], anchors[LF_MAX_OCTAVES], part[LF_MAX_OCTAVES],
-           chain[LF_MAX_OCTAVES], sid[LF_MAX_OCTAVES], gmarks[LF_MAX_OCTAVES], counts[LF_MAX_OCTAVES], l_ep[LF_MAX_OCTAVES],
-           l_c[LF_MAX_OCTAVES], l_dir[LF_MAX_OCTAVES], l_npx[LF_MAX_OCTAVES], l_sal[LF_MAX_OCTAVES], tl[LF_MAX_OCTAVES], rs_tab[LF_MAX_OCTAVES], ework[LF_MAX_OCTAVES];
-    DevBuf frame_count, frame_offset, status, totals, line_frame, big;      // big: grouping tables of frames with more than 4096 lines
-    // the detect mask (round 5): the KeyLines are assembled into these, the kept ones move to the caller's arrays
-    DevBuf m_fo, m_totals, m_erased, m_kept, m_masks, t_start_end, t_in_octave, t_angle, t_npx, t_len, t_octave, t_class, t_response, t_size, t_pt, t_sal, t_frame;
-    DevBuf o_start_end, o_in_octave, o_angle, o_npx, o_len, o_octave, o_class, o_response, o_size, o_pt, o_sal, o_desc, o_code;
-    int out_capacity = 0;
-    DevBuf in_gray;                 // staging of host gray images
-    DevBuf any_tmp, any_blur;       // Params::ksize_ other than 5: the row sums (int32) and the blurred image of the octave at hand
-    DevBuf d_frame, d_io, d_angle, d_npx, d_oct, d_desc, d_code, d_n;     // lf_describe_keylines staging
-    int* h_pinned = nullptr;        // totals [2], then frame status [max_frames]
-    bool marks_in_lds[LF_MAX_OCTAVES];
-    DevBuf aflags[LF_MAX_OCTAVES];  // the anchor candidate planes k_ed_grad writes (scan interval 2)
-    bool aflags_on[LF_MAX_OCTAVES] = {};
-    size_t lds_bytes = 0;
-    int last_octaves = 0, last_frames = 0;
-};
-
-static void kl_free(KlState* k)
-{
-    if (!k) return;
-    for (int o = 0; o < LF_MAX_OCTAVES; ++o)
-        for (DevBuf* b : { &k->src[o], &k->blur[o], &k->dxy[o], &k->g[o], &k->anchors[o], &k->part[o], &k->chain[o], &k->sid[o], &k->gmarks[o],
-                           &k->counts[o], &k->l_ep[o], &k->l_c[o], &k->l_dir[o], &k->l_npx[o], &k->l_sal[o], &k->tl[o], &k->rs_tab[o], &k->ework[o], &k->aflags[o] })
-            if (b->p) (void)hipFree(b->p);
-    for (DevBuf* b : { &k->frame_count, &k->frame_offset, &k->status, &k->totals, &k->line_frame, &k->o_start_end, &k->o_in_octave, &k->o_angle,
-                       &k->o_npx, &k->o_len, &k->o_octave, &k->o_class, &k->o_response, &k->o_size, &k->o_pt, &k->o_sal, &k->o_desc, &k->o_code,
-                       &k->in_gray, &k->any_tmp, &k->any_blur, &k->d_frame, &k->d_io, &k->d_angle, &k->d_npx, &k->d_oct, &k->d_desc, &k->d_code, &k->d_n, &k->big })
-        if (b->p) (void)hipFree(b->p);
-    for (DevBuf* b : { &k->m_fo, &k->m_totals, &k->m_erased, &k->m_kept, &k->m_masks, &k->t_start_end, &k->t_in_octave, &k->t_angle, &k->t_npx, &k->t_len, &k->t_octave,
-                       &k->t_class, &k->t_response, &k->t_size, &k->t_pt, &k->t_sal, &k->t_frame })
-        if (b->p) (void)hipFree(b->p);
-    if (k->h_pinned) (void)hipHostFree(k->h_pinned);
-    delete k;
-}
+using namespace lf;
 
 extern "C" void lf_edlines_default_params(lf_edlines_params* p)
 {
@@ -95,8 +58,8 @@ static bool kl_ksize_ok(int ksize) { return ksize >= 1 && ksize <= 31 && (ksize 
 
 static int kl_prepare(lf_handle* h, int n_octaves, int scan)
 {
-    if (!h->kl) { h->kl = new (std::nothrow) KlState(); if (!h->kl) return LF_ERR_HIP; }
-    KlState* k = h->kl;
+    if (!h->kl) { h->kl.reset(new (std::nothrow) KlState()); if (!h->kl) return LF_ERR_HIP; }
+    KlState* k = h->kl.get();
     const size_t B = (size_t)h->max_frames;
     if (k->n_octaves >= n_octaves && k->max_frames == h->max_frames) return LF_OK;
     int W = h->W, Hh = h->Hc;
@@ -139,15 +102,14 @@ static int kl_prepare(lf_handle* h, int n_octaves, int scan)
     k->lds_bytes = lds;
     int rc;
     if ((rc = ensure(h, k->frame_count, B * 4)) || (rc = ensure(h, k->frame_offset, (B + 1) * 4)) || (rc = ensure(h, k->status, B * 4)) || (rc = ensure(h, k->totals, 16))) return rc;
-    if (!k->h_pinned) LF_HIP_CHECK(h, hipHostMalloc((void**)&k->h_pinned, (2 + B) * sizeof(int)));
-    else if (k->max_frames != h->max_frames) { (void)hipHostFree(k->h_pinned); k->h_pinned = nullptr; LF_HIP_CHECK(h, hipHostMalloc((void**)&k->h_pinned, (2 + B) * sizeof(int))); }
+    if (!k->h_pinned || k->max_frames != h->max_frames) LF_HIP_CHECK(h, k->h_pinned.alloc((2 + B) * sizeof(int)));
     k->n_octaves = n_octaves; k->max_frames = h->max_frames;
     return LF_OK;
 }
 
 static int kl_out_buffers(lf_handle* h, int capacity)
 {
-    KlState* k = h->kl;
+    KlState* k = h->kl.get();
     const size_t c = (size_t)capacity;
     int rc;
     if ((rc = ensure(h, k->line_frame, c * 4)) || (rc = ensure(h, k->o_start_end, c * 16)) || (rc = ensure(h, k->o_in_octave, c * 16)) || (rc = ensure(h, k->o_angle, c * 4)) ||
@@ -182,7 +144,7 @@ static void kl_fill_all(const KlState* k, int n_octaves, EdAll& all)
 // line fitting of all octaves in one launch
 static int kl_run_octaves(lf_handle* h, const uint8_t* gray0, int n_frames, int n_octaves, const lf_edlines_params& P, EdAll& all)
 {
-    KlState* k = h->kl;
+    KlState* k = h->kl.get();
     hipStream_t s = h->stream;
     {
         StageTimer t(h, ST_LBD_GRAD);
@@ -238,7 +200,7 @@ static int keylines_batch_impl(lf_handle* h, const uint8_t* images, int n_frames
                                const lf_edlines_params* params_or_null, lf_keylines* out, int out_on_device, int describe,
                                int* n_keylines, int32_t* frame_status, bool async_only, const uint8_t* masks = nullptr, int masks_on_device = 0);
 
-static void keylines_pending_result(lf_handle* h, int* total, int* overflow)
+void lf::keylines_pending_result(lf_handle* h, int* total, int* overflow)
 {
     *total = h->kl ? h->kl->h_pinned[0] : 0;
     *overflow = h->kl ? h->kl->h_pinned[1] : 0;
@@ -274,7 +236,7 @@ extern "C" int lf_keylines_batch_async(lf_handle* h, const uint8_t* images_dev, 
 extern "C" int lf_keylines_frame_status(lf_handle* h, int32_t* frame_status, int n_frames)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
-    KlState* k = h->kl;
+    KlState* k = h->kl.get();
     if (!k || !frame_status || n_frames < 0 || n_frames > k->last_frames) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_keylines_frame_status: no such batch"); return LF_ERR_BAD_ARG; }
     if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
     for (int f = 0; f < n_frames; ++f) frame_status[f] = k->h_pinned[2 + f];
@@ -306,7 +268,7 @@ static int keylines_batch_impl(lf_handle* h, const uint8_t* images, int n_frames
     hipStream_t s = h->stream;
     int rc;
     if ((rc = kl_prepare(h, n_octaves, P.scan_intervals)) != LF_OK) return rc;
-    KlState* k = h->kl;
+    KlState* k = h->kl.get();
     // scan_intervals enters the LDS plan
     {
         size_t lds = 0;
@@ -470,8 +432,8 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
     if (n == 0) return LF_OK;
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    if (!h->kl) { h->kl = new (std::nothrow) KlState(); if (!h->kl) return LF_ERR_HIP; }
-    KlState* k = h->kl;
+    if (!h->kl) { h->kl.reset(new (std::nothrow) KlState()); if (!h->kl) return LF_ERR_HIP; }
+    KlState* k = h->kl.get();
     int rc;
     // the highest octave the lines name decides how much of the pyramid is built (:547-558); host arrays: look here,
     // device arrays: build all LF_MAX_OCTAVES levels that exist
@@ -555,7 +517,7 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
 extern "C" int lf_keylines_debug_fetch(lf_handle* h, int octave, int what, void* dst, size_t bytes, int32_t* dims5)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
-    KlState* k = h->kl;
+    KlState* k = h->kl.get();
     if (!k || octave < 0 || octave >= k->last_octaves) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_keylines_debug_fetch: no such octave in the last batch"); return LF_ERR_BAD_ARG; }
     if (dims5) { dims5[0] = k->H[octave]; dims5[1] = k->W[octave]; dims5[2] = k->cap[octave]; dims5[3] = k->max_edges[octave]; dims5[4] = k->max_lines[octave]; }
     if (!dst) return LF_OK;
@@ -589,7 +551,7 @@ static int kl_prepare_one_octave(lf_handle* h, const lf_edlines_params& P)
 {
     int rc;
     if ((rc = kl_prepare(h, 1, P.scan_intervals)) != LF_OK) return rc;
-    KlState* k = h->kl;
+    KlState* k = h->kl.get();
     bool in_lds = false;
     k->lds_bytes = ed_detect_lds_bytes(k->W[0], k->H[0], P.scan_intervals, &in_lds);
     if (k->lds_bytes > 160 * 1024) { lf_set_error(h, LF_ERR_UNSUPPORTED, "EDLines: scan_intervals %d needs %zu B of LDS", P.scan_intervals, k->lds_bytes); return LF_ERR_UNSUPPORTED; }
@@ -610,7 +572,7 @@ static bool edlines_params_ok(const lf_edlines_params& P)
 // detector of lf_set_image_edlines in place of Canny + LSD -- k_pre (working image, gray plane, dilated colour masks),
 // EDLines on the gray plane (one octave: a SegmentList has no octave), every line to the colours whose mask is set under its
 // centre.  No host synchronisation: the batch stays queued on the handle's stream like the LSD one.
-static int run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n)
+int lf::run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n)
 {
     hipStream_t s = h->stream;
     const lf_edlines_params& P = h->ed_params;
@@ -683,7 +645,7 @@ extern "C" int lf_set_image_edlines(lf_handle* h, const uint8_t* bgr, int rows, 
     int rc;
     if ((rc = plugin_stage_image(h, bgr, rows, cols, row_stride_bytes)) != LF_OK) return rc;
     if ((rc = kl_prepare_one_octave(h, P)) != LF_OK) return rc;
-    KlState* k = h->kl;
+    KlState* k = h->kl.get();
     PreParams pp = h->pre;         // the caller already resized, cropped and colour-corrected (line_detector_node.py:163-180)
     pp.in_rows = h->Hc; pp.in_cols = h->W; pp.img_rows = h->Hc; pp.img_cols = h->W; pp.top_cutoff = 0; pp.resize = 0;
     for (int i = 0; i < 3; ++i) { pp.ai_scale[i] = 1.f; pp.ai_shift[i] = 0.f; }

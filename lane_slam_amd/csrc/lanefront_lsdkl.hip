@@ -1,4 +1,4 @@
-// LSDDetectorC::detect over octaves (included into lanefront_api.hip): the line_descriptor library's OTHER detector
+// LSDDetectorC::detect over octaves: the line_descriptor library's OTHER detector
 // (ref: src/line_descriptor/src/LSDDetector_custom.cpp:49-72 computeGaussianPyramid, :130-215 detectImpl) --
 //   gray image -> pyramid by pyrDown (no blur, :62-71) -> cv::createLineSegmentDetector() with its DEFAULTS (REFINE_STD, scale 0.8,
 //   sigma_scale 0.6, quant 2, ang_th 22.5, log_eps 0, density_th 0.7, n_bins 1024) on every level (:155-160) -> one KeyLine per
@@ -14,29 +14,17 @@
 // Gray camera images are DENSE problems (tens of thousands of defined pixels in one connected component, grown by one wave):
 // this path is about completeness of detect -> compute for both detectors of the library, not about throughput.
 
-struct LsdKlState {
-    lf_handle* sub[LF_MAX_OCTAVES] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    DevBuf pyr[LF_MAX_OCTAVES];          // levels 1.. of the detect pyramid (level 0 is the caller's gray image)
-    DevBuf gray0, frame_count, frame_offset, line_frame, totals;
-    DevBuf o_start_end, o_in_octave, o_angle, o_npx, o_len, o_octave, o_class, o_response, o_size, o_pt, o_desc, o_code;
-    int H[LF_MAX_OCTAVES], W[LF_MAX_OCTAVES];
-    int* h_pinned = nullptr;
-    lf_lsd_options sub_opts[LF_MAX_OCTAVES];        // the options each cached sub-handle was made with
-    DevBuf masks;                                   // a host caller's masks on the device
-};
+#include <string.h>
+#include <algorithm>
+#include "lanefront_handle.h"
 
-static void lsdkl_free(LsdKlState* k)
+using namespace lf;
+
+
+lf::LsdKlState::~LsdKlState()
 {
-    if (!k) return;
-    for (int o = 0; o < LF_MAX_OCTAVES; ++o) {
-        if (k->sub[o]) { k->sub[o]->stream = nullptr; lf_destroy(k->sub[o]); }      // the stream is the parent's
-        if (k->pyr[o].p) (void)hipFree(k->pyr[o].p);
-    }
-    for (DevBuf* b : { &k->gray0, &k->frame_count, &k->frame_offset, &k->line_frame, &k->totals, &k->o_start_end, &k->o_in_octave, &k->o_angle, &k->o_npx,
-                       &k->o_len, &k->o_octave, &k->o_class, &k->o_response, &k->o_size, &k->o_pt, &k->o_desc, &k->o_code, &k->masks })
-        if (b->p) (void)hipFree(b->p);
-    if (k->h_pinned) (void)hipHostFree(k->h_pinned);
-    delete k;
+    for (lf_handle* s : sub)
+        if (s) { s->stream = nullptr; lf_destroy(s); }      // the stream is the parent's
 }
 
 extern "C" void lf_lsd_default_options(lf_lsd_options* o)
@@ -227,8 +215,8 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
     if (out->capacity < 1) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_lsd_keylines_batch: out->capacity < 1"); return LF_ERR_BAD_ARG; }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    if (!h->lsdkl) { h->lsdkl = new (std::nothrow) LsdKlState(); if (!h->lsdkl) return LF_ERR_HIP; }
-    LsdKlState* k = h->lsdkl;
+    if (!h->lsdkl) { h->lsdkl.reset(new (std::nothrow) LsdKlState()); if (!h->lsdkl) return LF_ERR_HIP; }
+    LsdKlState* k = h->lsdkl.get();
     const size_t B = (size_t)h->max_frames;
     int rc;
     // level 0: BGR2GRAY of the working image (k_pre), or the caller's gray images
@@ -278,7 +266,7 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
     const int cap_out = out->capacity;
     if ((rc = ensure(h, k->frame_count, B * 4)) || (rc = ensure(h, k->frame_offset, (B + 1) * 4)) || (rc = ensure(h, k->totals, 16)) ||
         (rc = ensure(h, k->line_frame, (size_t)cap_out * 4))) return rc;
-    if (!k->h_pinned) LF_HIP_CHECK(h, hipHostMalloc((void**)&k->h_pinned, 4 * sizeof(int)));
+    if (!k->h_pinned) LF_HIP_CHECK(h, k->h_pinned.alloc(4 * sizeof(int)));
     lf_keylines dev = *out;
     if (!out_on_device) {
         const size_t c = (size_t)cap_out;

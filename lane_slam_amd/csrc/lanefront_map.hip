@@ -9,27 +9,28 @@
 
 using namespace lf;
 
-namespace {
-struct Buf { void* p = nullptr; size_t bytes = 0; };
-}
-
 struct lf_map {
     lf_map_config cfg;
     int tie_rule = LF_TIE_LOWEST;
     int device = 0;
     hipStream_t stream = nullptr;
     char err[512];
-    MapDevice d;
+    MapDevice d;                             // the kernels' view of the arrays below
+    DevArray<uint8_t> code, color;
+    DevArray<double> ground;
+    DevArray<int> hits, last_seen, winner, state;
+    DevArray<int8_t> mx, mcx;
+    DevArray<unsigned long long> totals;
     size_t cap_pad = 0;
     // host mirror of the device state, refreshed behind every update
-    int* h_state = nullptr;                  // pinned: [0..15] state, then 2 x u64 totals at +16 ints
+    HostArray<int> h_state;                  // pinned: [0..15] state, then 2 x u64 totals at +16 ints
     int errors_reported = 0;                 // failing updates (state[8]) the host has already returned an error for
     hipEvent_t ev_state = nullptr, ev_in = nullptr, ev_out = nullptr;
     bool state_pending = false;
     long long rows_in_flight = 0;            // rows handed to updates whose state copy has not been seen yet
     AssocScratch ws;
-    Buf act, own_block, pose, q_in, c_in, idx_out, dist_out, seed_code, seed_color, seed_ground, tie_res;
-    Buf st_fo, st_code, st_color, st_keep, st_ground, st_idx, st_dist;     // staging of lf_map_step_host
+    DevBuf act, own_block, pose, q_in, c_in, idx_out, dist_out, seed_code, seed_color, seed_ground, tie_res;
+    DevBuf st_fo, st_code, st_color, st_keep, st_ground, st_idx, st_dist;     // staging of lf_map_step_host
     std::vector<double> h_pose;
     // per-stage timing with HIP events on the map's stream (resolved by lf_map_get_timing)
     struct Ev { hipEvent_t a, b; int st; };
@@ -81,14 +82,11 @@ static void map_error(lf_map* m, const char* fmt, ...)
         }                                                                                         \
     } while (0)
 
-static int grow(lf_map* m, Buf& b, size_t bytes)
+static int grow(lf_map* m, DevBuf& b, size_t bytes)
 {
     if (b.bytes >= bytes) return LF_OK;
-    if (b.p) { MAP_HIP(m, hipStreamSynchronize(m->stream)); (void)hipFree(b.p); }
-    b.p = nullptr; b.bytes = 0;
-    const size_t want = bytes + bytes / 4 + 256;
-    MAP_HIP(m, hipMalloc(&b.p, want));
-    b.bytes = want;
+    if (b.p) { MAP_HIP(m, hipStreamSynchronize(m->stream)); b.reset(); }
+    MAP_HIP(m, b.alloc(bytes + bytes / 4 + 256));
     return LF_OK;
 }
 
@@ -190,18 +188,11 @@ extern "C" void lf_map_destroy(lf_map* m)
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
-    void* ptrs[] = { m->d.code, m->d.color, m->d.ground, m->d.hits, m->d.last_seen, m->d.winner, m->d.mx, m->d.mcx, m->d.state, m->d.totals };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    assoc_scratch_free(m->ws);
-    for (Buf* b : { &m->act, &m->own_block, &m->pose, &m->q_in, &m->c_in, &m->idx_out, &m->dist_out, &m->seed_code, &m->seed_color, &m->seed_ground, &m->tie_res,
-                     &m->st_fo, &m->st_code, &m->st_color, &m->st_keep, &m->st_ground, &m->st_idx, &m->st_dist })
-        if (b->p) (void)hipFree(b->p);
-    if (m->h_state) (void)hipHostFree(m->h_state);
     for (lf_map::Ev& e : m->ev_used) m->ev_free.push_back(e);
     for (lf_map::Ev& e : m->ev_free) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (hipEvent_t e : { m->ev_state, m->ev_in, m->ev_out }) if (e) (void)hipEventDestroy(e);
     if (m->stream) (void)hipStreamDestroy(m->stream);
-    delete m;
+    delete m;                    // the buffers free themselves
 }
 
 extern "C" int lf_map_create(int device_id, const lf_map_config* cfg, lf_map** out)
@@ -246,17 +237,19 @@ extern "C" int lf_map_create(int device_id, const lf_map_config* cfg, lf_map** o
     CREATE_HIP(hipEventCreateWithFlags(&m->ev_state, hipEventDisableTiming));
     CREATE_HIP(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
     CREATE_HIP(hipEventCreateWithFlags(&m->ev_out, hipEventDisableTiming));
-    CREATE_HIP(hipMalloc((void**)&m->d.code, cap * 32));
-    CREATE_HIP(hipMalloc((void**)&m->d.color, cap));
-    CREATE_HIP(hipMalloc((void**)&m->d.ground, cap * 4 * sizeof(double)));
-    CREATE_HIP(hipMalloc((void**)&m->d.hits, cap * sizeof(int)));
-    CREATE_HIP(hipMalloc((void**)&m->d.last_seen, cap * sizeof(int)));
-    CREATE_HIP(hipMalloc((void**)&m->d.winner, cap * sizeof(int)));
-    CREATE_HIP(hipMalloc((void**)&m->d.mx, m->cap_pad * 256));
-    CREATE_HIP(hipMalloc((void**)&m->d.mcx, m->cap_pad * 32));
-    CREATE_HIP(hipMalloc((void**)&m->d.state, 16 * sizeof(int)));
-    CREATE_HIP(hipMalloc((void**)&m->d.totals, 2 * sizeof(unsigned long long)));
-    CREATE_HIP(hipHostMalloc((void**)&m->h_state, 24 * sizeof(int)));
+    CREATE_HIP(m->code.alloc(cap * 32));
+    CREATE_HIP(m->color.alloc(cap));
+    CREATE_HIP(m->ground.alloc(cap * 4 * sizeof(double)));
+    CREATE_HIP(m->hits.alloc(cap * sizeof(int)));
+    CREATE_HIP(m->last_seen.alloc(cap * sizeof(int)));
+    CREATE_HIP(m->winner.alloc(cap * sizeof(int)));
+    CREATE_HIP(m->mx.alloc(m->cap_pad * 256));
+    CREATE_HIP(m->mcx.alloc(m->cap_pad * 32));
+    CREATE_HIP(m->state.alloc(16 * sizeof(int)));
+    CREATE_HIP(m->totals.alloc(2 * sizeof(unsigned long long)));
+    CREATE_HIP(m->h_state.alloc(24 * sizeof(int)));
+    m->d.code = m->code; m->d.color = m->color; m->d.ground = m->ground; m->d.hits = m->hits; m->d.last_seen = m->last_seen;
+    m->d.winner = m->winner; m->d.mx = m->mx; m->d.mcx = m->mcx; m->d.state = m->state; m->d.totals = m->totals;
     memset(m->h_state, 0, 24 * sizeof(int));
     // rows beyond the map's size must read as "all zero" operands (distance 128): zero everything once
     CREATE_HIP(hipMemsetAsync(m->d.mx, 0, m->cap_pad * 256, m->stream));

@@ -1,4 +1,4 @@
-// BinaryDescriptorMatcher's DATASET form (included into lanefront_api.hip; round 5): descriptors of several train images are
+// BinaryDescriptorMatcher's DATASET form (round 5): descriptors of several train images are
 // added one Mat at a time, searched as ONE set, and every match says which image it came from.
 //   ref: src/line_descriptor/src/binary_descriptor_matcher.cpp
 //     :70-80    add      descriptorsMat.push_back(descriptors[i]); indexesMap[nextAddedIndex] = numImages; nextAddedIndex += rows
@@ -11,20 +11,12 @@
 //     :508-595  radiusMatch  K = all, results with distance <= maxDistance, same image lookup / mask / compactResult
 // The searches are this library's own (lf_associate / lf_knn_match / lf_radius_match on the concatenated codes, with the
 // handle's tie rule); what is added here is the set, the image lookup and the mask rule.
-struct MatcherState {
-    DevBuf codes;                  // the set: [total][32]
-    std::vector<std::pair<int, int> > index_map;   // indexesMap: (first row, image number), keys ascending
-    int num_images = 0;            // numImages
-    int total = 0;                 // nextAddedIndex
-    DevBuf q, idx, dist, off;      // staging for host callers
-};
 
-static void matcher_free(MatcherState* m)
-{
-    if (!m) return;
-    for (DevBuf* b : { &m->codes, &m->q, &m->idx, &m->dist, &m->off }) if (b->p) (void)hipFree(b->p);
-    delete m;
-}
+#include <string.h>
+#include <algorithm>
+#include "lanefront_handle.h"
+
+using namespace lf;
 
 static int matcher_image_of(const MatcherState* m, int row)
 {
@@ -37,20 +29,18 @@ extern "C" int lf_matcher_add(lf_handle* h, const uint8_t* codes32, int n, int o
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
     if (n < 0 || (n > 0 && !codes32)) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_matcher_add: bad argument"); return LF_ERR_BAD_ARG; }
-    if (!h->matcher) { h->matcher = new (std::nothrow) MatcherState(); if (!h->matcher) return LF_ERR_HIP; }
-    MatcherState* m = h->matcher;
+    if (!h->matcher) { h->matcher.reset(new (std::nothrow) MatcherState()); if (!h->matcher) return LF_ERR_HIP; }
+    MatcherState* m = h->matcher.get();
     if ((long long)m->total + n > (1 << 21)) { lf_set_error(h, LF_ERR_CAPACITY, "lf_matcher_add: the set would hold more than 2^21 descriptors"); return LF_ERR_CAPACITY; }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     if (n > 0) {
         const size_t need = (size_t)(m->total + n) * 32;
         if (need > m->codes.bytes) {                                       // grow, keeping what is there
-            void* p = nullptr;
-            const size_t want = need + need / 2 + 4096;
-            LF_HIP_CHECK(h, hipMalloc(&p, want));
-            if (m->total) LF_HIP_CHECK(h, hipMemcpyAsync(p, m->codes.p, (size_t)m->total * 32, hipMemcpyDeviceToDevice, h->stream));
+            DevBuf grown;
+            LF_HIP_CHECK(h, grown.alloc(need + need / 2 + 4096));
+            if (m->total) LF_HIP_CHECK(h, hipMemcpyAsync(grown.p, m->codes.p, (size_t)m->total * 32, hipMemcpyDeviceToDevice, h->stream));
             LF_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-            if (m->codes.p) (void)hipFree(m->codes.p);
-            m->codes.p = p; m->codes.bytes = want;
+            m->codes = std::move(grown);
         }
         LF_HIP_CHECK(h, hipMemcpyAsync(static_cast<uint8_t*>(m->codes.p) + (size_t)m->total * 32, codes32, (size_t)n * 32,
                                        on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
@@ -93,7 +83,7 @@ extern "C" int lf_matcher_match(lf_handle* h, const uint8_t* query32, int nq, co
     int rc = matcher_ready(h, query32, nq, "lf_matcher_match");
     if (rc != LF_OK) return rc;
     if (!out || !n_out) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_matcher_match: null output"); return LF_ERR_BAD_ARG; }
-    MatcherState* m = h->matcher;
+    MatcherState* m = h->matcher.get();
     std::vector<int32_t> idx((size_t)nq);
     std::vector<float> dist((size_t)nq);
     if ((rc = ensure(h, m->q, (size_t)nq * 32)) || (rc = ensure(h, m->idx, (size_t)nq * 4)) || (rc = ensure(h, m->dist, (size_t)nq * 4))) return rc;
@@ -121,7 +111,7 @@ extern "C" int lf_matcher_knn_match(lf_handle* h, const uint8_t* query32, int nq
     int rc = matcher_ready(h, query32, nq, "lf_matcher_knn_match");
     if (rc != LF_OK) return rc;
     if (!out || !n_lists || !list_offsets || k < 1 || k > 16) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_matcher_knn_match: null output or k outside 1..16"); return LF_ERR_BAD_ARG; }
-    MatcherState* m = h->matcher;
+    MatcherState* m = h->matcher.get();
     const size_t nk = (size_t)nq * k;
     std::vector<int32_t> idx(nk);
     std::vector<float> dist(nk);
@@ -157,7 +147,7 @@ extern "C" int lf_matcher_radius_match(lf_handle* h, const uint8_t* query32, int
     int rc = matcher_ready(h, query32, nq, "lf_matcher_radius_match");
     if (rc != LF_OK) return rc;
     if (!n_lists || !list_offsets || !total || cap < 0 || (cap > 0 && !out)) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_matcher_radius_match: bad argument"); return LF_ERR_BAD_ARG; }
-    MatcherState* m = h->matcher;
+    MatcherState* m = h->matcher.get();
     if ((rc = ensure(h, m->q, (size_t)nq * 32)) || (rc = ensure(h, m->off, ((size_t)nq + 1) * 4)) ||
         (rc = ensure(h, m->idx, (size_t)(cap > 0 ? cap : 1) * 4)) || (rc = ensure(h, m->dist, (size_t)(cap > 0 ? cap : 1) * 4))) return rc;
     LF_HIP_CHECK(h, hipMemcpyAsync(m->q.p, query32, (size_t)nq * 32, hipMemcpyHostToDevice, h->stream));
