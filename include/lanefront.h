@@ -38,7 +38,8 @@
 extern "C" {
 #endif
 
-#define LF_ABI_VERSION 5   /* 2: JPEG ingest, SegmentList glue, LF_ERR_DECODE, 13 timing stages; 3: live map (lf_map_*); 4: EDLines / KeyLines, block overflow marker; 5: lf_config.lsd_seed_order, tie rules */
+#define LF_ABI_VERSION 5   /* 2: JPEG ingest, SegmentList glue, LF_ERR_DECODE, 13 timing stages; 3: live map (lf_map_*); 4: EDLines / KeyLines, block overflow marker; 5: lf_config.lsd_seed_order, tie rules.
+                              Still 5 with the histogram lane filter (lf_lane_filter_*): purely additive, no existing declaration changed */
 
 typedef enum lf_status {
     LF_OK = 0,
@@ -376,6 +377,85 @@ LF_API int lf_map_fetch(lf_map* m, int first, int n, uint8_t* code32, uint8_t* c
 LF_API int lf_map_set_profiling(lf_map* m, int enabled);
 LF_API int lf_map_get_timing(lf_map* m, double* ms_per_stage, int32_t* launches_per_stage, int n);
 LF_API const char* lf_map_stage_name(int stage);
+
+/* ---- Histogram lane filter: lane pose from ground segments -----------------------------------------
+ * LaneFilterHistogram (src/lane_filter/include/lane_filter/lane_filter.py:12-161) as lane_filter_node.processSegments
+ * drives it (src/lane_filter/src/lane_filter_node.py:49-87): per frame predict(dt, v, w) -> update(segments) ->
+ * getEstimate / getMax -> LanePose (d, phi, in_lane = max > min_max).  A filter holds n_streams independent beliefs
+ * (one per robot / camera stream) on one device; a step takes a batch of frames, each tagged with its stream, and runs
+ * every stream's frames in batch order.  Every f64 operation is the reference's, in its order (numpy's pairwise sum,
+ * scipy's gaussian_filter, the first argmax): results are bit-identical to the reference given the same tables.
+ *
+ * lf_lane_filter_config  the 17 keys of the node's `filter` configuration
+ *                        (src/duckietown/config/baseline/lane_filter/lane_filter_node/default.yaml), in its order; sigma_d_0 /
+ *                        sigma_phi_0 are variances, as in the reference; cov_v is accepted and unused, as in the reference.
+ *                        The grid is np.mgrid[d_min:d_max:delta_d, phi_min:phi_max:delta_phi]: ceil((max - min) / delta) rows
+ *                        (d) and columns (phi), at most 4096 cells (else LF_ERR_BAD_ARG); sigma_*_mask in (0, 63.6].
+ * Tables.  The transcendentals depend on the configuration only: sin of the phi grid [rows][cols] (constant along d, as
+ *   np.sin of the mgrid is), the two Gaussian weight vectors w[0 .. r] (r = int(4 * sigma_mask + 0.5), w[k] =
+ *   exp(-0.5 / sigma^2 * k^2) / sum over -r .. r) and the initial belief [rows][cols] (multivariate_normal(mean_0,
+ *   diag(sigma_d_0, sigma_phi_0)).pdf, not normalised).  lf_lane_filter_create computes them with libm: that default is
+ *   NOT pinned to numpy / scipy (an ulp here and there).  lf_lane_filter_set_tables replaces them with the caller's (the
+ *   Python mirror passes numpy's / scipy's own); NULL keeps a table.  It does not touch the beliefs: lf_lane_filter_reset.
+ * Votes.  generateVote (:124-154) with arcsin through the library's deterministic f64 arcsin (<= 2 ulp of libm: a vote can
+ *   move only when it lies on a bin edge).  Only WHITE and YELLOW vote; a segment with points[k].x < 0 does not; a vote outside
+ *   [d_min, d_max] x [phi_min, phi_max] is dropped.  Where the reference raises (a vote or a predicted cell that floors onto
+ *   index rows / cols, a degenerate segment) the library drops the vote / the cell.
+ * lf_lane_filter_step
+ *   h                  the front-end handle whose stream produced device segments (the filter's stream waits for it, and the
+ *                      handle's next batch waits until the votes have been read), or NULL
+ *   segs               frame_offset [n_frames + 1], color, ground of the batch; host arrays (segs_on_device = 0), or device
+ *                      arrays with segs->capacity = the arrays' length in segments (reads are clamped to it).  NULL when phases
+ *                      has no LF_LANE_FILTER_UPDATE.  Device segments of lf_process_batch_async are defined only after lf_wait
+ *                      returned for that batch (lf_wait may run a batch a second time when its lists had to grow): call this
+ *                      after lf_wait.  Nothing in between blocks the host: the step is queued behind the handle's stream.
+ *   frame_stream       host [n_frames] stream of each frame (0 .. n_streams - 1), or NULL = all stream 0
+ *   dt_v_w             host [n_frames][3]: dt (s), v (m/s), omega (rad/s) of predict; NULL when phases has no PREDICT.
+ *                      Non-finite products v * dt, w * dt are LF_ERR_BAD_ARG (the reference raises on them)
+ *   phases             LF_LANE_FILTER_PREDICT | LF_LANE_FILTER_UPDATE (the node runs both; the mirror one at a time)
+ *   poses              host [n_frames] lf_lane_pose after each frame, or NULL
+ *   belief_out, ml_out host [n_frames][rows][cols] belief after the frame / its likelihood (zeros when it had no votes), or NULL
+ *   The call returns when the host outputs are in place; with all three NULL it returns at once (asynchronous) and
+ *   lf_lane_filter_get_poses fetches that step's poses later.
+ */
+typedef struct lf_lane_filter lf_lane_filter;
+typedef struct lf_lane_filter_config {
+    double mean_d_0, mean_phi_0, sigma_d_0, sigma_phi_0, delta_d, delta_phi, d_max, d_min, phi_max, phi_min, cov_v,
+        linewidth_white, linewidth_yellow, lanewidth, min_max, sigma_d_mask, sigma_phi_mask;
+} lf_lane_filter_config;
+typedef struct lf_lane_pose {
+    double d, phi, max;        /* getEstimate() (cell centre of the first maximum), getMax() */
+    int32_t in_lane;           /* max > min_max */
+    int32_t has_ml;            /* the frame voted (update returned a likelihood, the node publishes ml_img) */
+    int32_t n_votes;           /* votes that landed in the histogram */
+    int32_t reserved;          /* 0 */
+} lf_lane_pose;
+#define LF_LANE_FILTER_PREDICT 1
+#define LF_LANE_FILTER_UPDATE 2
+#define LF_LANE_FILTER_MAX_CELLS 4096
+LF_API void lf_lane_filter_default_config(lf_lane_filter_config* cfg);       /* default.yaml's values */
+LF_API int lf_lane_filter_create(int device_id, const lf_lane_filter_config* cfg, int n_streams, int max_frames, lf_lane_filter** out);
+LF_API void lf_lane_filter_destroy(lf_lane_filter* lf);
+LF_API const char* lf_lane_filter_last_error(const lf_lane_filter* lf);      /* lf == NULL: the last lf_lane_filter_create failure */
+LF_API int lf_lane_filter_grid(const lf_lane_filter* lf, int* rows, int* cols);
+LF_API int lf_lane_filter_set_tables(lf_lane_filter* lf, const double* sin_phi_grid, const double* w_d, const double* w_phi,
+                                     const double* initial_belief);
+/* stream's belief <- belief (host [rows][cols]) or, NULL, the initial belief; stream -1: every stream.  Blocking. */
+LF_API int lf_lane_filter_reset(lf_lane_filter* lf, int stream, const double* belief_or_null);
+LF_API int lf_lane_filter_step(lf_lane_filter* lf, lf_handle* h, const lf_segments* segs, int segs_on_device, int n_frames,
+                               const int32_t* frame_stream_or_null, const double* dt_v_w, int phases, lf_lane_pose* poses,
+                               double* belief_out_or_null, double* ml_out_or_null);
+/* the poses of the last step (n_frames of them); waits for it */
+LF_API int lf_lane_filter_get_poses(lf_lane_filter* lf, lf_lane_pose* poses, int n_frames);
+/* host [rows][cols] copy of a stream's current belief; waits for the filter's queued work */
+LF_API int lf_lane_filter_get_belief(lf_lane_filter* lf, int stream, double* belief);
+LF_API int lf_lane_filter_synchronize(lf_lane_filter* lf);
+/* per-kernel timing with HIP events on the filter's stream: 0 k_lf_vote, 1 k_lf_chain; lf_lane_filter_get_timing returns what
+ * accumulated since the previous call (waiting for it) and resets it */
+#define LF_LANE_FILTER_N_STAGES 2
+LF_API int lf_lane_filter_set_profiling(lf_lane_filter* lf, int enabled);
+LF_API int lf_lane_filter_get_timing(lf_lane_filter* lf, double* ms_per_stage, int32_t* launches_per_stage, int n);
+LF_API const char* lf_lane_filter_stage_name(int stage);
 
 /* ---- EDLines detector + multi-octave KeyLines / LBD --------------------------------
  * The reference's second detector: BinaryDescriptor::operator() with useProvidedKeyLines = false

@@ -30,7 +30,16 @@ EXPORTS = (
     "lf_set_tie_rule", "lf_map_set_tie_rule", "lf_debug_std_sort", "lf_suggested_depth", "lf_lsd_list_capacity", "lf_lsd_scratch_stride", "lf_set_detector", "lf_detector_failures", "lf_keylines_batch_async", "lf_keylines_frame_status", "lf_lsd_keylines_batch", "lf_select_queries",
     "lf_lsd_default_options", "lf_lsd_keylines_batch_ex", "lf_keylines_batch_masked",
     "lf_matcher_add", "lf_matcher_clear", "lf_matcher_size", "lf_matcher_match", "lf_matcher_knn_match", "lf_matcher_radius_match",
+    "lf_lane_filter_default_config", "lf_lane_filter_create", "lf_lane_filter_destroy", "lf_lane_filter_last_error", "lf_lane_filter_grid",
+    "lf_lane_filter_set_tables", "lf_lane_filter_reset", "lf_lane_filter_step", "lf_lane_filter_get_poses", "lf_lane_filter_get_belief",
+    "lf_lane_filter_synchronize", "lf_lane_filter_set_profiling", "lf_lane_filter_get_timing", "lf_lane_filter_stage_name",
 )
+LF_LANE_FILTER_PREDICT, LF_LANE_FILTER_UPDATE = 1, 2
+LF_LANE_FILTER_MAX_CELLS = 4096
+LF_LANE_FILTER_N_STAGES = 2
+# the 17 keys of LaneFilterHistogram's configuration, in lf_lane_filter_config's (and the reference's param_names) order
+LANE_FILTER_PARAMS = ("mean_d_0", "mean_phi_0", "sigma_d_0", "sigma_phi_0", "delta_d", "delta_phi", "d_max", "d_min", "phi_max",
+                      "phi_min", "cov_v", "linewidth_white", "linewidth_yellow", "lanewidth", "min_max", "sigma_d_mask", "sigma_phi_mask")
 DETECTORS = {"lsd": 0, "edlines": 1}
 TIE_RULES = {"lowest": 0, "mihasher": 1}
 LF_MAX_OCTAVES = 5
@@ -72,6 +81,17 @@ class LfLsdOptions(ctypes.Structure):
     _fields_ = [("refine", ctypes.c_int32), ("n_bins", ctypes.c_int32), ("scale", ctypes.c_double), ("sigma_scale", ctypes.c_double),
                 ("quant", ctypes.c_double), ("ang_th", ctypes.c_double), ("log_eps", ctypes.c_double), ("density_th", ctypes.c_double),
                 ("min_length", ctypes.c_double)]
+
+
+class LfLaneFilterConfig(ctypes.Structure):
+    """ctypes mirror of `lf_lane_filter_config` (include/lanefront.h)."""
+    _fields_ = [(k, ctypes.c_double) for k in LANE_FILTER_PARAMS]
+
+
+class LfLanePose(ctypes.Structure):
+    """ctypes mirror of `lf_lane_pose` (include/lanefront.h)."""
+    _fields_ = [("d", ctypes.c_double), ("phi", ctypes.c_double), ("max", ctypes.c_double), ("in_lane", ctypes.c_int32),
+                ("has_ml", ctypes.c_int32), ("n_votes", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class LfMapConfig(ctypes.Structure):
@@ -234,6 +254,28 @@ def load():
     lib.lf_knn_match.restype = ci
     lib.lf_radius_match.argtypes = [vp, vp, ci, vp, ci, ctypes.c_float, vp, vp, vp, ci, ctypes.POINTER(ci), ci]
     lib.lf_radius_match.restype = ci
+    lib.lf_lane_filter_default_config.argtypes = [ctypes.POINTER(LfLaneFilterConfig)]
+    lib.lf_lane_filter_default_config.restype = None
+    lib.lf_lane_filter_create.argtypes = [ci, ctypes.POINTER(LfLaneFilterConfig), ci, ci, ctypes.POINTER(vp)]
+    lib.lf_lane_filter_destroy.argtypes = [vp]
+    lib.lf_lane_filter_destroy.restype = None
+    lib.lf_lane_filter_last_error.argtypes = [vp]
+    lib.lf_lane_filter_last_error.restype = ctypes.c_char_p
+    lib.lf_lane_filter_grid.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.lf_lane_filter_set_tables.argtypes = [vp, vp, vp, vp, vp]
+    lib.lf_lane_filter_reset.argtypes = [vp, ci, vp]
+    lib.lf_lane_filter_step.argtypes = [vp, vp, ctypes.POINTER(LfSegments), ci, ci, vp, vp, ci, vp, vp, vp]
+    lib.lf_lane_filter_get_poses.argtypes = [vp, vp, ci]
+    lib.lf_lane_filter_get_belief.argtypes = [vp, ci, vp]
+    lib.lf_lane_filter_synchronize.argtypes = [vp]
+    lib.lf_lane_filter_set_profiling.argtypes = [vp, ci]
+    lib.lf_lane_filter_get_timing.argtypes = [vp, vp, vp, ci]
+    lib.lf_lane_filter_stage_name.argtypes = [ci]
+    lib.lf_lane_filter_stage_name.restype = ctypes.c_char_p
+    for f in ("lf_lane_filter_create", "lf_lane_filter_grid", "lf_lane_filter_set_tables", "lf_lane_filter_reset", "lf_lane_filter_step",
+              "lf_lane_filter_get_poses", "lf_lane_filter_get_belief", "lf_lane_filter_synchronize",
+              "lf_lane_filter_set_profiling", "lf_lane_filter_get_timing"):
+        getattr(lib, f).restype = ci
     for f in ("lf_map_create", "lf_map_get_stream", "lf_map_synchronize", "lf_map_seed", "lf_map_size", "lf_map_associate",
               "lf_map_pack_block", "lf_map_update", "lf_map_step", "lf_map_fetch"):
         getattr(lib, f).restype = ci

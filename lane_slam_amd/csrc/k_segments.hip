@@ -11,6 +11,7 @@
 // Also compacts the fixed-capacity LSD slots [frame][colour][cap] into the frame-major,
 // colour-minor SegmentList order.  Byte traffic is negligible (~130 B per segment).
 #include "common.h"
+#include "lane_vote.h"
 
 namespace lf {
 
@@ -155,24 +156,8 @@ __global__ void k_segments(SegParams p, int n_frames, const float* __restrict__ 
     if (out.ground) { double* o = out.ground + 4 * (size_t)idx; o[0] = p1x; o[1] = p1y; o[2] = p2x; o[3] = p2y; }
     // a-8
     if (out.keep) {
-        int state = 0;
-        const double gx_ = p2x - p1x, gy_ = p2y - p1y;
-        const double nrm = dm::dsqrt(gx_ * gx_ + gy_ * gy_);
-        const double tx = gx_ / nrm, ty = gy_ / nrm;
-        const double hx = -ty, hy = tx;
-        const double d1 = hx * p1x + hy * p1y;
-        const double d2 = hx * p2x + hy * p2y;
-        double d_i = (d1 + d2) / 2;
-        double phi_i = dm::dasin(ty);
-        if (col == LF_WHITE) {
-            if (p1x > p2x) { d_i = d_i - p.linewidth_white; state = 1; }
-            else { d_i = -d_i; phi_i = -phi_i; state = 2; }
-            d_i = d_i - p.lanewidth / 2;
-        } else if (col == LF_YELLOW) {
-            if (p2x > p1x) { d_i = d_i - p.linewidth_yellow; phi_i = -phi_i; state = 3; }
-            else { d_i = -d_i; state = 4; }
-            d_i = p.lanewidth / 2 - d_i;
-        }
+        double d_i, phi_i;
+        const int state = lane_vote(col, p1x, p1y, p2x, p2y, p.lanewidth, p.linewidth_white, p.linewidth_yellow, d_i, phi_i);
         int k = 1;
         if (p1x < 0 || p2x < 0) k = 0;
         else if (col != LF_WHITE && col != LF_YELLOW) k = 0;
