@@ -191,9 +191,28 @@ LF_API int lf_wait(lf_handle* h, int* n_segments);
  * params: NULL = lf_edlines_default_params.  Not while a batch is in flight. */
 #define LF_DETECTOR_LSD 0
 #define LF_DETECTOR_EDLINES 1
+/*   LF_DETECTOR_HOUGH    the reference's LineDetectorHSV (line_detector1.py:11-136): the LSD plugin with cv2.HoughLinesP
+ *                        (rho 1, theta pi/180) in place of LSD on the same colour's edge map (Canny AND the dilated mask); its
+ *                        int32 lines go through the plugin's _findNormal / ordering in its integer arithmetic, then the same
+ *                        normalisation, projection, line sanity and LBD stages, pipelined the same way.  params_or_null is
+ *                        not read: the Hough parameters are the handle's (lf_set_hough_params).  Working images up to 8192
+ *                        pixels a side whose edge bit plane fits 48 KB; larger ones are LF_ERR_UNSUPPORTED.  The plugin path
+ *                        (lf_set_image / lf_detect_lines) runs the handle's detector when it is this one. */
+#define LF_DETECTOR_HOUGH 2
 struct lf_edlines_params;
 LF_API int lf_set_detector(lf_handle* h, int detector, const struct lf_edlines_params* params_or_null);
 LF_API int lf_detector_failures(const lf_handle* h);
+/* cv2.HoughLinesP's arguments (line_detector1.py:65): threshold (>= 1), min_line_length, max_line_gap (>= 0) -- the
+ * hough_threshold, hough_min_line_length and hough_max_line_gap configuration keys -- and rho, theta, of which only 1 and
+ * pi/180 (as the float HoughLinesP takes) are supported: LF_ERR_UNSUPPORTED otherwise.  Defaults (lf_hough_default_params,
+ * and a new handle's): the reference's default.yaml, 2, 3, 1, 1.0, pi/180.  Not while a batch is in flight. */
+typedef struct lf_hough_params {
+    int32_t threshold, min_line_length, max_line_gap;
+    double rho, theta;
+} lf_hough_params;
+LF_API void lf_hough_default_params(lf_hough_params* p);
+LF_API int lf_set_hough_params(lf_handle* h, const lf_hough_params* p);
+LF_API int lf_get_hough_params(const lf_handle* h, lf_hough_params* p);
 
 /* ---- association: replaces BinaryDescriptorMatcher::match ------------------
  * (binary_descriptor_matcher.cpp:197-254): exact Hamming nearest neighbour of
@@ -732,7 +751,7 @@ LF_API int lf_lsd_list_capacity(const lf_handle* h, int* entries, int* grown);
 LF_API int lf_lsd_scratch_stride(const lf_handle* h);
 
 /* per-kernel timing with HIP events on the handle's stream */
-#define LF_N_STAGES 14
+#define LF_N_STAGES 15     /* stage 14: hough (LF_DETECTOR_HOUGH) */
 LF_API int lf_set_profiling(lf_handle* h, int enabled);
 /* ms accumulated per stage since the last reset, and launches counted */
 LF_API int lf_get_timing(lf_handle* h, double* ms_per_stage, int32_t* launches_per_stage, int n);

@@ -24,7 +24,7 @@ constexpr int kCompCap = 1024;      // component list entries per problem (more 
 
 enum Stage {
     ST_PRE = 0, ST_CANNY, ST_HYST, ST_LSD_GRAD, ST_LSD_ORDER, ST_LSD_GROW, ST_SEGMENTS,
-    ST_LBD_GRAD, ST_LBD, ST_ASSOC_PACK, ST_ASSOC, ST_MISC, ST_JPEG, ST_LSD_LABEL, ST_COUNT
+    ST_LBD_GRAD, ST_LBD, ST_ASSOC_PACK, ST_ASSOC, ST_MISC, ST_JPEG, ST_LSD_LABEL, ST_HOUGH, ST_COUNT
 };
 static_assert(ST_COUNT == LF_N_STAGES, "stage table out of sync with lanefront.h");
 
@@ -172,7 +172,7 @@ void launch_seg_offsets(int n_frames, int cap_lines, const int* counts, int* seg
                         int* overflow, const int* norder, int cap_small, int cap_medium, hipStream_t s);
 void launch_segments(const SegParams& p, int n_frames, const float* slot_lines, const int* counts,
                      const int* seg_offset, const uint32_t* maskbits, int Ww, lf_segments out, int* seg_frame,
-                     double* normals64, float* centers, hipStream_t s);
+                     double* normals64, float* centers, hipStream_t s, bool int_lines = false);
 void launch_lbd_grad(int Hc, int W, int n_frames, const uint8_t* gray, uint32_t* dxy, hipStream_t s);
 // gradient planes of the octaves of a KeyLine batch: [B][H*W] dx | dy << 16 each
 struct LbdPlanes { const uint32_t* base[LF_MAX_OCTAVES]; int W[LF_MAX_OCTAVES], H[LF_MAX_OCTAVES]; };

@@ -100,6 +100,11 @@ __device__ void ground_point(const SegParams& p, double vx, double vy, double& g
     gy = g1 / g2;
 }
 
+// kIntLines: the lines are cv2.HoughLinesP's int32 ones (LF_DETECTOR_HOUGH, held exactly as floats in the slots) and a-5 is the
+// Hough plugin's arithmetic on them (line_detector1.py:80-119, the same statements as the LSD plugin's): the length is the
+// square root of an integer sum in f64, dx / dy are f64, the centres are Python 2's floor division of int sums, the ordering
+// test is int x f64.  The LSD / EDLines instantiation (false) is the float32 arithmetic of line_detector_lsd.py.
+template <bool kIntLines>
 __global__ void k_segments(SegParams p, int n_frames, const float* __restrict__ slot_lines,
                            const int* __restrict__ counts, const int* __restrict__ seg_offset,
                            const uint32_t* __restrict__ maskbits, int Ww, lf_segments out, int* __restrict__ seg_frame,
@@ -116,6 +121,32 @@ __global__ void k_segments(SegParams p, int n_frames, const float* __restrict__ 
     const int f = pc / 3, col = pc - 3 * f;
     const float* L = slot_lines + ((size_t)pc * p.cap_lines + i) * 4;
     float x1 = L[0], y1 = L[1], x2 = L[2], y2 = L[3];
+    if constexpr (kIntLines) {
+        int ix1 = (int)x1, iy1 = (int)y1, ix2 = (int)x2, iy2 = (int)y2;
+        // a-5 on int32 lines: length = (int sum of squares) ** 0.5, dx = 1.*(y2-y1)/length, dy = 1.*(x1-x2)/length (f64)
+        const int ex = ix1 - ix2, ey = iy1 - iy2;
+        const double len = dm::dsqrt((double)(ex * ex + ey * ey));
+        const double dx = (double)(iy2 - iy1) / len;
+        const double dy = (double)(ix1 - ix2) / len;
+        const int cx = (ix1 + ix2) >> 1, cy = (iy1 + iy2) >> 1;          // (x1+x2)/2 on int arrays under Python 2: floor division
+        int x3 = (int)((double)cx - 3. * dx), y3 = (int)((double)cy - 3. * dy);
+        int x4 = (int)((double)cx + 3. * dx), y4 = (int)((double)cy + 3. * dy);
+        x3 = check_bounds(x3, p.W); y3 = check_bounds(y3, p.Hc);
+        x4 = check_bounds(x4, p.W); y4 = check_bounds(y4, p.Hc);
+        const uint32_t* bw = maskbits + (size_t)pc * p.Hc * Ww;
+        const bool on3 = (bw[(size_t)y3 * Ww + (x3 >> 5)] >> (x3 & 31)) & 1u;
+        const bool on4 = (bw[(size_t)y4 * Ww + (x4 >> 5)] >> (x4 & 31)) & 1u;
+        const int sign = (on3 && !on4) ? 1 : -1;
+        const double nx = dx * sign, ny = dy * sign;
+        const double flag = (double)(ix2 - ix1) * ny - (double)(iy2 - iy1) * nx;
+        if (flag > 0) { int tx = ix1, ty = iy1; ix1 = ix2; iy1 = iy2; ix2 = tx; iy2 = ty; }
+        x1 = (float)ix1; y1 = (float)iy1; x2 = (float)ix2; y2 = (float)iy2;
+        if (out.lines) { float* o = out.lines + 4 * (size_t)idx; o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2; }
+        if (out.normals) { out.normals[2 * (size_t)idx] = (float)nx; out.normals[2 * (size_t)idx + 1] = (float)ny; }
+        if (out.color) out.color[idx] = (uint8_t)col;
+        if (normals64) { normals64[2 * (size_t)idx] = nx; normals64[2 * (size_t)idx + 1] = ny; }
+        if (centers) { centers[2 * (size_t)idx] = (float)cx; centers[2 * (size_t)idx + 1] = (float)cy; }
+    } else {
     // a-5
     const float ex = x1 - x2, ey = y1 - y2;
     const float len = dm::fsqrt(ex * ex + ey * ey);
@@ -139,6 +170,7 @@ __global__ void k_segments(SegParams p, int n_frames, const float* __restrict__ 
     if (out.color) out.color[idx] = (uint8_t)col;
     if (normals64) { normals64[2 * (size_t)idx] = nx; normals64[2 * (size_t)idx + 1] = ny; }
     if (centers) { centers[2 * (size_t)idx] = cx; centers[2 * (size_t)idx + 1] = cy; }
+    }
     if (seg_frame) seg_frame[idx] = f;
     // a-6
     const float pn0 = (float)(((double)x1 + 0.0) * p.rx);
@@ -169,11 +201,15 @@ __global__ void k_segments(SegParams p, int n_frames, const float* __restrict__ 
 
 void launch_segments(const SegParams& p, int n_frames, const float* slot_lines, const int* counts,
                      const int* seg_offset, const uint32_t* maskbits, int Ww, lf_segments out, int* seg_frame,
-                     double* normals64, float* centers, hipStream_t s)
+                     double* normals64, float* centers, hipStream_t s, bool int_lines)
 {
     const int total = n_frames * 3 * p.cap_lines;
-    hipLaunchKernelGGL(k_segments, dim3((total + 255) / 256), dim3(256), 0, s, p, n_frames, slot_lines, counts,
-                       seg_offset, maskbits, Ww, out, seg_frame, normals64, centers);
+    if (int_lines)
+        hipLaunchKernelGGL(k_segments<true>, dim3((total + 255) / 256), dim3(256), 0, s, p, n_frames, slot_lines, counts,
+                           seg_offset, maskbits, Ww, out, seg_frame, normals64, centers);
+    else
+        hipLaunchKernelGGL(k_segments<false>, dim3((total + 255) / 256), dim3(256), 0, s, p, n_frames, slot_lines, counts,
+                           seg_offset, maskbits, Ww, out, seg_frame, normals64, centers);
 }
 
 }  // namespace lf

@@ -20,7 +20,8 @@ using namespace lf;
 static const char* kStageNames[LF_N_STAGES] = {
     "pre(resize+correct+hsv+masks+dilate)", "canny_nms", "canny_hysteresis", "lsd_blur_resample_grad",
     "lsd_order", "lsd_grow", "segments(normal+project+sanity)", "lbd_gray_blur_sobel", "lbd_descriptor",
-    "assoc_pack", "assoc_mfma", "misc", "jpeg(idct+upsample+color)", "lsd_label(components+launch order)" };
+    "assoc_pack", "assoc_mfma", "misc", "jpeg(idct+upsample+color)", "lsd_label(components+launch order)",
+    "hough(probabilistic lines)" };
 
 
 
@@ -514,6 +515,23 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
             return LF_ERR_UNSUPPORTED;
         }
     }
+    if (h->detector == LF_DETECTOR_HOUGH) {
+        // LineDetectorHSV: HoughLinesP on the same edge maps in place of the LSD stages (k_hough.hip)
+        int rc = hough_prepare(h);
+        if (rc != LF_OK) return rc;
+        StageTimer t(h, ST_HOUGH);
+        LF_HIP_CHECK(h, hipMemsetAsync(h->d_zero, 0, h->zero_bytes, s));           // every counter of the batch (see d_zero)
+        HoughParams hp = h->hough_p;
+        hp.threshold = h->hough_params.threshold; hp.line_length = h->hough_params.min_line_length; hp.line_gap = h->hough_params.max_line_gap;
+        launch_hough(hp, n * 3, h->hough_slots < n * 3 ? h->hough_slots : n * 3, h->d_strong, h->d_maskbits, h->d_hough_tab, h->d_hough_acc,
+                     h->d_hough_nz, h->d_slot_lines, h->d_counts, s);
+        LF_HIP_CHECK(h, hipGetLastError());
+        h->slots_int = true;
+        h->last_frames = n;
+        h->overflow_zeroed = true;
+        return LF_OK;
+    }
+    h->slots_int = false;
     {
         StageTimer t(h, ST_LSD_GRAD);
         LF_HIP_CHECK(h, hipMemsetAsync(h->d_zero, 0, h->zero_bytes, s));           // every counter of the batch (see d_zero)
@@ -561,9 +579,9 @@ int lf::run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe)
         if (!h->overflow_zeroed) LF_HIP_CHECK(h, hipMemsetAsync(h->d_overflow, 0, 4 * sizeof(int), s));
         h->overflow_zeroed = false;
         launch_seg_offsets(n, h->cap_lines, h->d_counts, h->d_seg_offset, dev_out.frame_offset ? dev_out.frame_offset : h->d_frame_offset,
-                           h->d_overflow, h->d_norder, lsd_grow_def_lds(h->lsd, kGrowLdsKb[0]), lsd_grow_def_lds(h->lsd, kGrowLdsKb[1]), s);
+                           h->d_overflow, h->slots_int ? nullptr : h->d_norder, lsd_grow_def_lds(h->lsd, kGrowLdsKb[0]), lsd_grow_def_lds(h->lsd, kGrowLdsKb[1]), s);
         launch_segments(h->seg, n, h->d_slot_lines, h->d_counts, h->d_seg_offset, h->d_maskbits, h->Ww, dev_out, h->d_seg_frame,
-                        h->d_normals64, h->d_centers, s);
+                        h->d_normals64, h->d_centers, s, h->slots_int);
     }
     if (describe) {
         { StageTimer t(h, ST_LBD_GRAD); launch_lbd_grad(h->Hc, h->W, n, h->d_gray, h->d_dxy, s); }
@@ -657,7 +675,7 @@ extern "C" int lf_wait(lf_handle* h, int* n_segments)
         if (overflow) { lf_set_error(h, LF_ERR_CAPACITY, "%d KeyLines exceed the output capacity %d", total_kl, h->pending_capacity); return LF_ERR_CAPACITY; }
         return LF_OK;
     }
-    for (int attempt = 0; h->detector != LF_DETECTOR_EDLINES && h->h_pinned[6] > h->lsd.rec_cap; ++attempt) {
+    for (int attempt = 0; h->detector == LF_DETECTOR_LSD && h->h_pinned[6] > h->lsd.rec_cap; ++attempt) {
         // a problem did not fit the per-problem lists: grow them and run the batch again (its inputs are still where they were)
         if (attempt == 4) { lf_set_error(h, LF_ERR_CAPACITY, "the LSD lists keep overflowing (%d entries needed)", h->h_pinned[6]); return LF_ERR_CAPACITY; }
         int rc = lsd_grow_lists(h, h->h_pinned[6]);
@@ -678,7 +696,7 @@ extern "C" int lf_wait(lf_handle* h, int* n_segments)
         h->grow_lds_level = over_medium * 4 > np ? 2 : (over_small * 20 > np ? 1 : 0);
         h->grow_mixed = (h->grow_lds_level == 0 ? over_small : over_medium) * 100 > np;
     }
-    if (h->h_pinned[1]) { lf_set_error(h, LF_ERR_CAPACITY, "an LSD run produced more than max_lines_per_color=%d lines", h->cap_lines); return LF_ERR_CAPACITY; }
+    if (h->h_pinned[1]) { lf_set_error(h, LF_ERR_CAPACITY, "an %s run produced more than max_lines_per_color=%d lines", h->detector == LF_DETECTOR_HOUGH ? "HoughLinesP" : "LSD", h->cap_lines); return LF_ERR_CAPACITY; }
     if (total > h->pending_capacity) { lf_set_error(h, LF_ERR_CAPACITY, "%d segments exceed the output capacity %d", total, h->pending_capacity); return LF_ERR_CAPACITY; }
     return LF_OK;
 }

@@ -10,6 +10,7 @@
 #include "common.h"
 #include "jpeg_entropy.h"
 #include "k_edlines_types.h"
+#include "k_hough.h"
 
 namespace lf {
 
@@ -179,6 +180,13 @@ struct lf_handle {
     int detector = LF_DETECTOR_LSD;       // what lf_process_batch runs for a-2 .. a-4 (lf_set_detector)
     lf_edlines_params ed_params;
     int detector_failures = 0;            // frames of the last completed batch on which the EDLines detector gave up
+    lf_hough_params hough_params = { 2, 3, 1, 1.0, 3.14159265358979323846 / 180 };   // LF_DETECTOR_HOUGH (lf_set_hough_params)
+    lf::DevArray<lf::HoughTables> d_hough_tab;   // the per-angle tables of the geometry (k_hough.h), made by hough_prepare
+    lf::DevArray<int> d_hough_acc;               // compacted accumulators, one per resident workgroup
+    lf::DevArray<uint32_t> d_hough_nz;           // the points of problems that do not fit LDS, one list per resident workgroup
+    lf::HoughParams hough_p{};
+    int hough_slots = 0;
+    bool slots_int = false;               // the slot lines of the last detect are HoughLinesP's ints (k_segments' integer a-5)
     int tie_rule = LF_TIE_MIHASHER;   // lf_associate: the reference's rule unless lf_set_tie_rule says otherwise
     int env_lds_level = -1;      // LF_GROW_LDS_LEVEL / LF_GROW_MIXED: test and tuning overrides, read when the handle is created, clamped
     int env_mixed = -1;
@@ -251,6 +259,8 @@ int run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_working_i
 int run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe);
 int plugin_stage_image(lf_handle* h, const uint8_t* bgr, int rows, int cols, int row_stride_bytes);
 int plugin_fetch_results(lf_handle* h);
+// lanefront_hough.hip
+int hough_prepare(lf_handle* h);
 // lanefront_keylines.hip
 int run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n);
 void keylines_pending_result(lf_handle* h, int* total, int* overflow);

@@ -171,11 +171,37 @@ class FrontEnd(object):
                                                     ctypes.byref(s), int(bool(describe))))
 
     def set_detector(self, detector, params=None):
-        """Which detector process_batch / submit_* run: "lsd" (the reference's, default) or "edlines" (EDLines on the gray
-        working image + the colour masks: include/lanefront.h, lf_set_detector).  params: edlines_params(...) or None."""
+        """Which detector process_batch / submit_* run: "lsd" (the reference's, default), "edlines" (EDLines on the gray
+        working image + the colour masks: include/lanefront.h, lf_set_detector) or "hough" (LineDetectorHSV's
+        cv2.HoughLinesP on the colour's edge map).  params: for "edlines" edlines_params(...) or None; for "hough" a mapping
+        with the three configuration keys hough_threshold, hough_min_line_length and hough_max_line_gap (a whole
+        13-key detector configuration will do), which it requires."""
         if detector not in _lib.DETECTORS:
             raise ValueError("detector must be one of %r" % (sorted(_lib.DETECTORS),))
+        if detector == "hough":
+            if params is None or any(k not in params for k in _lib.HOUGH_KEYS):
+                raise ValueError("the hough detector takes its parameters: a mapping with %r" % (_lib.HOUGH_KEYS,))
+            self._check(self.lib.lf_set_hough_params(self.h, ctypes.byref(self.hough_params(*(params[k] for k in _lib.HOUGH_KEYS)))))
+            self._check(self.lib.lf_set_detector(self.h, _lib.DETECTORS[detector], None))
+            return
         self._check(self.lib.lf_set_detector(self.h, _lib.DETECTORS[detector], ctypes.byref(params) if params is not None else None))
+
+    def hough_params(self, threshold=None, min_line_length=None, max_line_gap=None):
+        """lf_hough_params: the reference's default.yaml values (2, 3, 1; rho 1, theta pi/180), optionally overridden."""
+        p = _lib.LfHoughParams()
+        self.lib.lf_hough_default_params(ctypes.byref(p))
+        for k, v in (("threshold", threshold), ("min_line_length", min_line_length), ("max_line_gap", max_line_gap)):
+            if v is not None:
+                if int(v) != v:
+                    raise ValueError("%s must be an integer, got %r" % (k, v))
+                setattr(p, k, int(v))
+        return p
+
+    def get_hough_params(self):
+        """(threshold, min_line_length, max_line_gap) the handle's Hough detector uses."""
+        p = _lib.LfHoughParams()
+        self._check(self.lib.lf_get_hough_params(self.h, ctypes.byref(p)))
+        return int(p.threshold), int(p.min_line_length), int(p.max_line_gap)
 
     def detector_failures(self):
         """Frames of the last completed batch on which the EDLines detector gave up (they have no segments)."""

@@ -147,3 +147,33 @@ class LineDetectorEDLines(LineDetectorHIP):
         p = fe.edlines_params(**self._edlines)
         fe._check(fe.lib.lf_set_image_edlines(fe.h, img.ctypes.data_as(ctypes.c_void_p), img.shape[0], img.shape[1], img.strides[0],
                                               ctypes.byref(p)))
+
+
+class LineDetectorHSV(LineDetectorHIP):
+    """Drop-in for the reference's other LineDetectorInterface plugin, line_detector.LineDetectorHSV
+    (the reference's src/line_detector/include/line_detector/line_detector1.py:11-136): LineDetectorLSD with
+    cv2.HoughLinesP(edge_color, 1, np.pi/180, hough_threshold, np.empty(1), hough_min_line_length, hough_max_line_gap)
+    in place of LSD (the detector LF_DETECTOR_HOUGH of include/lanefront.h, on the GPU).  Same constructor contract: the 13
+    configuration keys, of which this one reads the three hough_* keys.  detectLines(color) returns Detections with int32
+    `lines` (N, 4), float64 `normals`, int32 `centers` (the plugin's `(x1 + x2) / 2` on int arrays under Python 2: floor
+    division) and `area`, like the reference; empty lists when nothing is found.
+
+        detector:
+          - lane_slam_amd.LineDetectorHSV
+          - configuration: { ...same 13 keys... }"""
+
+    def __init__(self, configuration, device=0, max_lines_per_color=2048):
+        LineDetectorHIP.__init__(self, configuration, device=device, max_lines_per_color=max_lines_per_color)
+
+    def _frontend(self, rows, cols):
+        fresh = self._fe is None or self._shape != (rows, cols)
+        fe = LineDetectorHIP._frontend(self, rows, cols)
+        if fresh:
+            fe.set_detector("hough", self._configuration)
+        return fe
+
+    def detectLines(self, color):
+        d = LineDetectorHIP.detectLines(self, color)
+        if len(d.lines) == 0:
+            return d
+        return Detections(lines=d.lines.astype(np.int32), normals=d.normals, area=d.area, centers=d.centers.astype(np.int32))
