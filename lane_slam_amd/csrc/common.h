@@ -184,16 +184,10 @@ void launch_lbd(int Hc, int W, int n_seg_cap, const int* n_seg, const float* lin
                 const uint32_t* dxy, const float* gauss_g, const float* gauss_l,
                 float* desc, uint8_t* code, hipStream_t s, int wband = 7);
 int lbd_max_width_of_band();
-// ---- associator (k_assoc.hip): packed operands = [rows][256] int8 code bytes + [rows][32] int8 ninth-step operand
+// ---- associator (k_assoc.hip): packed operands = [rows][128] e2m1 code nibbles (+ [rows][32] colour rows when gated)
 size_t assoc_rows_padded_m(int nm);
-// Packed map operand layout (k_assoc.hip): blocked by the associator's 64-row LDS tile, [tile][16-byte chunk][row][16 B];
-// byte `byte` (0..255) of map row `row` lives at
-__host__ __device__ inline size_t assoc_map_offset(size_t row, int byte)
-{
-    return (row >> 6) * 16384 + (size_t)(byte >> 4) * 1024 + (row & 63) * 16 + (size_t)(byte & 15);
-}
-// The ungated associator runs on the FP4 matrix instruction: one e2m1 nibble per code bit, 128 bytes per map row, blocked the
-// same way with 8 KB tiles: byte `byte` (0..127) of map row `row` lives at
+// Packed map operand layout: one e2m1 nibble per code bit, 128 bytes per map row, blocked by the associator's 64-row LDS tile,
+// [8 KB tile][16-byte chunk][row][16 B]: byte `byte` (0..127) of map row `row` lives at
 __host__ __device__ inline size_t assoc_map_offset_fp4(size_t row, int byte)
 {
     return (row >> 6) * 8192 + (size_t)(byte >> 4) * 1024 + (row & 63) * 16 + (size_t)(byte & 15);
@@ -265,14 +259,13 @@ struct AssocScratch {
     DevArray<int> tie_list; size_t cap_list = 0;
     unsigned long long* tie_res = nullptr;        // set by the caller before launch_assoc_core when launch_assoc_ties follows: the merge step then writes the tie pass's query lists
 };
-void launch_assoc_pack_map(const uint8_t* codes, const uint8_t* colors, int n, int n_pad, int fp4, int8_t* x, int8_t* cx, hipStream_t s);
+void launch_assoc_pack_map(const uint8_t* codes, int n, int n_pad, int8_t* x, hipStream_t s);
 hipError_t launch_assoc_core(const uint8_t* q, const uint8_t* qcolor, int nq, const int8_t* mx, const int8_t* mcx, int nm,
                              const int* nm_dev, int gating, int max_distance, AssocScratch& w, int32_t* idx, float* dist, hipStream_t s);
 // the reference's tie rule as a second pass over the packed map (k_assoc_ties.hip); after launch_assoc_core on the same stream
 hipError_t launch_assoc_ties(const uint8_t* q, const uint8_t* qcolor, int nq, const int8_t* mx, const uint8_t* mcode, const uint8_t* mcolor,
                              int nm, const int* nm_dev, int gating, AssocScratch& w, unsigned long long* res, int32_t* idx, const float* dist, hipStream_t s);
-hipError_t launch_assoc(const uint8_t* q, int nq, const uint8_t* m, int nm, int8_t* mx, int8_t* mcx, AssocScratch& w, int32_t* idx,
-                        float* dist, hipStream_t s);
+hipError_t launch_assoc(const uint8_t* q, int nq, const uint8_t* m, int nm, int8_t* mx, AssocScratch& w, int32_t* idx, float* dist, hipStream_t s);
 void launch_assoc_nomatch(int nq, int32_t* idx, float* dist, hipStream_t s);
 // ---- anti-instagram colour clustering (k_kmeans.hip)
 void launch_kmeans(const uint8_t* bgr, int n, int k, const double* init, int max_iter, double tol_rel, uint8_t* lab, double* out,
@@ -280,7 +273,6 @@ void launch_kmeans(const uint8_t* bgr, int n, int k, const double* init, int max
 // ---- live map (k_map.hip)
 struct MapDevice {
     int capacity, policy, kept_only, merge_distance, when_full;
-    int fp4;                       // packed operands are e2m1 nibbles (ungated maps) instead of int8 bytes + ninth-step rows
     uint8_t* code; uint8_t* color; double* ground; int* hits; int* last_seen; int* winner;
     int8_t* mx; int8_t* mcx;
     int* state;                    // 16 ints: [0] size [1] head [2] flags of the latest failing update [3] n_app [4] n_ref [5] old head

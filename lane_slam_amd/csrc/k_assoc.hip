@@ -9,22 +9,17 @@
 // contraction of +-1 operands: dot = 256 - 2 * hamming, exactly.
 //
 // Kernels (one launch per association; DESIGN.md section 4 and 5 have the measurements):
-//   k_assoc_fp4 / k_assoc_fp4_gated   the product path: every code bit is an e2m1 nibble (+1.0 / -1.0), 64 bits per
-//       v_mfma_scale_f32_32x32x64_f8f6f4, query side scaled by 2^9 through the E8M0 block scale, exact f32 accumulation;
+//   k_assoc_fp4 / k_assoc_fp4_gated (+ the small shape's _s forms): every code bit is an e2m1 nibble (+1.0 / -1.0), 64 bits
+//       per v_mfma_scale_f32_32x32x64_f8f6f4, query side scaled by 2^9 through the E8M0 block scale, exact f32 accumulation;
 //       the 32-column block number t enters through a fifth matrix step (weights 64, 8, 1 x minus the octal digits of
 //       t), colour gating through one more (-147 456 when the colours differ): key = 512 * dot - t - penalty orders
 //       candidates by distance, then by column block, so the running arg-max is ONE v_max_f32 per accumulator register.
 //       Map rows: 128 bytes, blocked by 64-row tile (assoc_map_offset_fp4); colour rows: 32 bytes per map row.
-//   k_assoc / k_assoc_plain           the int8 form (LF_ASSOC_INT8=1, kept for A/B runs): query bits +-32, map bits +-16,
-//       v_mfma_i32_32x32x32_i8, K = 256; the block number is the chain's start value (plain) or, with gating, part of
-//       a ninth step (K = 32: [16, 1] x [-(t >> 4), -(t & 15)], and 127 x -127 over ten bytes per colour group =
-//       -161 290 when the colours differ).  Map rows: 256 bytes blocked by tile (assoc_map_offset) + 32-byte ninth-step rows.
-//   All of them: 256 queries per workgroup (4 waves x 2 x 32 rows), query operands expanded from the raw 32-byte codes
-//   into registers, map chunk streamed by LDS-DMA through tile buffers, hand-scheduled tile loop (k_assoc_loop.inc,
-//   tools/gen_assoc_loop.py), per-chunk key rows written through and merged by the last workgroup to arrive; ties
-//   resolve to the lowest map index.  Algorithmic ops: 2*N*M*256.
+//       256 queries per workgroup (4 waves x 2 x 32 rows; the small shape 128), query operands expanded from the raw 32-byte
+//       codes into registers, map chunk streamed by LDS-DMA through tile buffers, hand-scheduled tile loop (k_assoc_loop.inc,
+//       tools/gen_assoc_loop.py), per-chunk key rows written through and merged by the last workgroup to arrive; ties
+//       resolve to the lowest map index.  Algorithmic ops: 2*N*M*256.
 //   k_assoc_float: 72-d float LBD, Euclidean, on v_mfma_f32_32x32x2_f32 (exact fp32 FMA chain).
-#include <cstdlib>
 #include <cstdio>
 #include "common.h"
 #include "k_assoc_loop.inc"
@@ -53,49 +48,14 @@ constexpr int kMaxBlocksPerChunk = 512;   // the in-accumulator block counter t 
 constexpr int kAssocSmallMax = LF_ASSOC_SMALL_MAX;   // associations of up to this many queries take the small shape (launch_assoc_core)
 
 // Packs map rows for lf_associate's raw-map form (the live map keeps its rows packed: k_map.hip).  One thread per
-// (row, code byte): 8 int8 = 2 dwords; thread 0 of a row also writes the row's ninth-step operand (zero counter bytes,
-// -127 in the other colours' groups; colour >= 3 or no colours: matches every colour).
-__global__ void k_assoc_pack_map(const uint8_t* __restrict__ codes, const uint8_t* __restrict__ colors, int n, int n_pad, int fp4,
-                                 int8_t* __restrict__ out, int8_t* __restrict__ outc)
+// (row, code byte): one e2m1 nibble per bit (padding rows: zeros = the value 0.0, "distance 128").
+__global__ void k_assoc_pack_map(const uint8_t* __restrict__ codes, int n, int n_pad, int8_t* __restrict__ out)
 {
     size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     size_t total = (size_t)n_pad * 32;
     if (t >= total) return;
     size_t row = t >> 5;
-    uint32_t lo = 0, hi = 0;
-    const bool live = row < (size_t)n;
-    if (live) {
-        uint32_t b = codes[t];
-        // nibble -> 4 bytes of 0/1, then 0 -> +16, 1 -> -16
-        uint32_t w0 = ((b & 15u) * 0x00204081u) & 0x01010101u;
-        uint32_t w1 = ((b >> 4) * 0x00204081u) & 0x01010101u;
-        lo = (w0 * 0xE0u) ^ 0x10101010u; hi = (w1 * 0xE0u) ^ 0x10101010u;
-    }
-    if (fp4) {
-        // one e2m1 nibble per bit (padding rows: zeros = the value 0.0, "distance 128")
-        *reinterpret_cast<uint32_t*>(out + assoc_map_offset_fp4(row, (int)(t & 31) * 4)) = live ? assoc_fp4_expand(codes[t]) : 0u;
-        return;
-    }
-    *reinterpret_cast<uint2*>(out + assoc_map_offset(row, (int)(t & 31) * 8)) = make_uint2(lo, hi);
-    if ((t & 31) == 0) {
-        uint32_t w[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-        if (live) {
-            const int c = colors ? colors[row] : 255;
-            uint8_t* wb = reinterpret_cast<uint8_t*>(w);
-            if (c < 3)
-                for (int g = 0; g < 3; ++g)
-                    if (g != c) for (int k = 0; k < 10; ++k) wb[2 + 10 * g + k] = (uint8_t)(-127);
-        }
-        uint4* o = reinterpret_cast<uint4*>(outc + row * 32);
-        o[0] = make_uint4(w[0], w[1], w[2], w[3]);
-        o[1] = make_uint4(w[4], w[5], w[6], w[7]);
-    }
-}
-
-// four code bits -> four int8 query operand bytes: 0 -> +32, 1 -> -32
-__device__ __forceinline__ int q_expand(uint32_t nibble)
-{
-    return (int)((((nibble & 15u) * 0x00204081u) & 0x01010101u) * 0xC0u ^ 0x20202020u);
+    *reinterpret_cast<uint32_t*>(out + assoc_map_offset_fp4(row, (int)(t & 31) * 4)) = row < (size_t)n ? assoc_fp4_expand(codes[t]) : 0u;
 }
 
 template <int QW>
@@ -177,150 +137,13 @@ __device__ __forceinline__ void assoc_publish_and_merge(unsigned int mine, int m
     if (threadIdx.x == 0) __hip_atomic_store(done + blockIdx.x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// One workgroup: 256 queries (4 waves x 2 x 32 rows) against one chunk of the map.
-//  * The query operands are expanded from the raw 32-byte codes straight into the A-fragment registers (no packed query
-//    array in memory, no pack kernel): lane (r32, half) of a wave holds, for row block b and step s, the 16 bits
-//    [32 s + 16 half, +16) of query q0 + 32 b + r32 as 16 int8.
-//  * The map chunk streams through three 16 KB LDS buffers; the tile loop is hand-scheduled assembly
-//    (k_assoc_loop.inc, generated by tools/gen_assoc_loop.py: register map, schedule, hazard notes there).  It leaves
+// One workgroup: QW queries (4 waves x NRB x 32 rows) against one chunk of the map, on the FP4 matrix instruction
+// (k_assoc_loop.inc, LF_ASSOC_LOOP_FP4*; gen_assoc_loop.py gen_fp4 has the arithmetic, register map, schedule and hazard notes).
+//  * The query operands are expanded from the raw 32-byte codes straight into the A-fragment registers through a byte ->
+//    8 nibbles table (no packed query array in memory, no pack kernel).
+//  * The map rows are e2m1 nibbles (128 bytes per row, 8 KB tiles) streamed through LDS tile buffers; the tile loop leaves
 //    the running keys in LDS.
-//  * Keys are decoded and reduced to one word per query and chunk; the merge over the chunks is at the end of the body.
-template <bool GATED>
-__device__ __forceinline__ void assoc_body(const uint8_t* __restrict__ q, const uint8_t* __restrict__ qcolor, int nq,
-                                           const int8_t* __restrict__ mx, const int8_t* __restrict__ mcx,
-                                           int nm_bound, const int* __restrict__ nm_dev, int nm_pad, int m_chunk,
-                                           int max_distance, unsigned int* __restrict__ part, int* __restrict__ done,
-                                           int32_t* __restrict__ idx, float* __restrict__ dist, int8_t* tile, int8_t* ctile, uint2* xtab,
-                                           int* __restrict__ tie_pieces, int* __restrict__ tie_counts, unsigned long long* __restrict__ tie_res)
-{
-    // nm_bound sized the grid on the host; when the exact size is only known on the device (the live map's size
-    // after an update still in flight) it is read here.  Rows in [size, bound) are all-zero operands and are dropped
-    // below exactly like padding rows, so the result does not depend on how loose the bound was.
-    LF_STAMP(0); LF_STAMP(1);
-    const int nm = nm_dev ? min(nm_bound, *nm_dev) : nm_bound;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int q0 = blockIdx.x * AQW + wave * 64;
-    const int r32 = lane & 31, half = lane >> 5;
-    const int m_begin = blockIdx.y * m_chunk;
-    const int m_end = min(nm_pad, m_begin + m_chunk);
-    const int n_tiles = __builtin_amdgcn_readfirstlane((m_end - m_begin) / AM);
-    unsigned int mine = 0x7fffffffu;            // this thread's query of the block (mine_q) against this chunk
-    int mine_q = threadIdx.x;
-    if (n_tiles > 0) {
-        // byte -> eight int8 operand bytes (bit j of the byte -> +32 / -32), one table for the workgroup: the expansion
-        // of the 2 x 8 fragments is then two 8-byte LDS reads each instead of ~20 vector instructions each (code size
-        // matters here: this straight-line code runs once, and every cold instruction line is a fetch stall)
-        if (threadIdx.x < 256) {
-            const uint32_t t = threadIdx.x;
-            xtab[t] = make_uint2((uint32_t)q_expand(t), (uint32_t)q_expand(t >> 4));
-        }
-        __syncthreads();
-        v4i A[2][8], AX[2];
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int qi = q0 + 32 * b + r32;
-            uint4 c0 = make_uint4(0, 0, 0, 0), c1 = c0;        // padding rows: any operand will do, they are never reported
-            if (qi < nq) {
-                c0 = *reinterpret_cast<const uint4*>(q + (size_t)qi * 32);
-                c1 = *reinterpret_cast<const uint4*>(q + (size_t)qi * 32 + 16);
-            }
-            const uint32_t d[8] = { c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w };
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const uint32_t hw = d[s] >> (16 * half);               // code bytes 4 s + 2 half, + 1
-                const uint2 e0 = xtab[hw & 0xffu], e1 = xtab[(hw >> 8) & 0xffu];
-                A[b][s] = v4i{ (int)e0.x, (int)e0.y, (int)e1.x, (int)e1.y };
-            }
-            if (GATED) {
-                // ninth-step operand of a query: [16, 1] counter weights, then 127 in the ten bytes of ITS colour's group
-                const int c = qi < nq ? (int)qcolor[qi] : 255;
-                const int g0 = c == 0 ? 0x7f7f7f7f : 0, g1 = c == 1 ? 0x7f7f7f7f : 0, g2 = c == 2 ? 0x7f7f7f7f : 0;
-                if (half == 0) AX[b] = v4i{ (qi < nq ? 0x0110 : 0) | (g0 & (int)0x7f7f0000), g0, g0, g1 };
-                else AX[b] = v4i{ g1, (g1 & 0x00007f7f) | (g2 & (int)0x7f7f0000), g2, g2 };
-            }
-        }
-        const uint32_t lds_tile = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)tile;
-        const uint32_t vfrag = lds_tile + half * 1024 + r32 * 16;
-        const uint32_t voff = (uint32_t)lane * 16u;
-        const uint32_t vdump = lds_tile + wave * 8192 + lane * 16;
-        const uint64_t mbase = (uint64_t)(size_t)(mx + (size_t)m_begin * 256 + wave * 1024);
-        const uint32_t mlo = __builtin_amdgcn_readfirstlane((uint32_t)mbase), mhi = __builtin_amdgcn_readfirstlane((uint32_t)(mbase >> 32));
-        const uint32_t m0base = __builtin_amdgcn_readfirstlane(lds_tile + wave * 1024);
-        LF_STAMP(2);
-#define LF_A_OPERANDS \
-        [a00] "{v[40:43]}"(A[0][0]), [a01] "{v[44:47]}"(A[0][1]), [a02] "{v[48:51]}"(A[0][2]), [a03] "{v[52:55]}"(A[0][3]), \
-        [a04] "{v[56:59]}"(A[0][4]), [a05] "{v[60:63]}"(A[0][5]), [a06] "{v[64:67]}"(A[0][6]), [a07] "{v[68:71]}"(A[0][7]), \
-        [a10] "{v[72:75]}"(A[1][0]), [a11] "{v[76:79]}"(A[1][1]), [a12] "{v[80:83]}"(A[1][2]), [a13] "{v[84:87]}"(A[1][3]), \
-        [a14] "{v[88:91]}"(A[1][4]), [a15] "{v[92:95]}"(A[1][5]), [a16] "{v[96:99]}"(A[1][6]), [a17] "{v[100:103]}"(A[1][7])
-        if (GATED) {
-            const uint32_t lds_ctile = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)ctile;
-            const uint32_t vcfrag = lds_ctile + r32 * 32 + 16 * half;
-            const uint64_t cbase = (uint64_t)(size_t)(mcx + (size_t)m_begin * 32 + (wave & 1) * 1024);
-            const uint32_t clo = __builtin_amdgcn_readfirstlane((uint32_t)cbase), chi = __builtin_amdgcn_readfirstlane((uint32_t)(cbase >> 32));
-            const uint32_t m0c = __builtin_amdgcn_readfirstlane(lds_ctile + (wave & 1) * 1024);
-            const uint32_t tmaskv = half == 0 ? 0xffffu : 0u;          // the counter bytes live in k = 0, 1 (lanes 0..31)
-            const uint64_t mpair = ((uint64_t)mhi << 32) | mlo, cpair = ((uint64_t)chi << 32) | clo;
-            asm volatile(LF_ASSOC_LOOP_GATED
-                         :
-                         : LF_A_OPERANDS, [ax0] "{v[232:235]}"(AX[0]), [ax1] "{v[236:239]}"(AX[1]), [vfrag] "v"(vfrag),
-                           [vcfrag] "v"(vcfrag), [voff] "v"(voff), [vdump] "v"(vdump), [tmaskv] "v"(tmaskv), [mbase] "s"(mpair),
-                           [cbase] "s"(cpair), [m0base] "s"(m0base), [m0c] "s"(m0c), [ntiles] "s"(n_tiles)
-                         : LF_ASSOC_LOOP_CLOBBERS_GATED);
-        } else {
-            const uint64_t mpair = ((uint64_t)mhi << 32) | mlo;
-            asm volatile(LF_ASSOC_LOOP_PLAIN
-                         :
-                         : LF_A_OPERANDS, [vfrag] "v"(vfrag), [voff] "v"(voff), [vdump] "v"(vdump), [mbase] "s"(mpair),
-                           [m0base] "s"(m0base), [ntiles] "s"(n_tiles)
-                         : LF_ASSOC_LOOP_CLOBBERS_PLAIN);
-        }
-#undef LF_A_OPERANDS
-        LF_STAMP(3);
-        // key -> (distance, column): 512 * dot = ceil(key / 512) * 512, t = 512 * dot - key; this lane's column inside
-        // block t is r32.  Padding columns (>= nm; their rows are zero, i.e. "distance 128") are dropped here: a padding
-        // column can only have displaced candidates with a negative dot, which are beyond 128 and never reported.  A
-        // candidate of another colour (gating) decodes to a distance beyond 128 and is dropped below.  Running key
-        // i = 16 b + r of this lane sits in the wave's 8 KB of LDS.
-        // 1) every lane decodes its 32 keys in place (column = 32 t + this lane's r32)
-        int* dump = reinterpret_cast<int*>(tile) + wave * 2048;
-#pragma unroll 2
-        for (int g = 0; g < 8; ++g) {                                  // four keys per 16-byte access: no bank conflicts
-            int4* slot = reinterpret_cast<int4*>(dump + g * 256 + lane * 4);
-            const int4 k4 = *slot;
-            const int key[4] = { k4.x, k4.y, k4.z, k4.w };
-            int v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                v[j] = 0x7fffffff;
-                if (key[j] != (int)0x80000000) {
-                    const int dot512 = (key[j] + 511) & ~511;
-                    const int col = m_begin + 32 * (dot512 - key[j]) + r32;
-                    if (col < nm) v[j] = (((256 << 9) - dot512) << 12) | col;      // hamming << 22 | col
-                }
-            }
-            *slot = make_int4(v[0], v[1], v[2], v[3]);
-        }
-        __syncthreads();
-        // 2) one lane per query: key i = 16 b + r of the 32 lanes (r32) of half h is query row (r & 3) + 8 (r >> 2) + 4 h
-        //    of block b; lane (i, h) takes the minimum over r32, reading in an order rotated by i >> 2 (bank spread)
-        {
-            const int i = lane & 31, h = lane >> 5;
-            const int* src = dump + (i >> 2) * 256 + h * 128 + (i & 3);
-            int v = 0x7fffffff;
-#pragma unroll 8
-            for (int k = 0; k < 32; ++k) v = min(v, src[((k + (i >> 2)) & 31) * 4]);
-            const int b = i >> 4, r = i & 15;
-            mine = (unsigned int)v;
-            mine_q = wave * 64 + 32 * b + (r & 3) + 8 * (r >> 2) + 4 * h;
-        }
-    }
-    LF_STAMP(4);
-    assoc_publish_and_merge<AQW>(mine, mine_q, nq, max_distance, part, done, idx, dist, tie_pieces, tie_counts, tie_res);
-}
-
-// The ungated kernel on the FP4 matrix instruction (k_assoc_loop.inc, LF_ASSOC_LOOP_FP4; gen_assoc_loop.py gen_fp4 has the
-// arithmetic): same work split and the same reduce / publish / merge tail as assoc_body; the map rows are e2m1 nibbles
-// (128 bytes per row, 8 KB tiles), the queries are expanded from the raw codes through a byte -> 8 nibbles table.
+//  * Keys are decoded and reduced to one word per query and chunk; assoc_publish_and_merge merges the chunks.
 template <bool GATED, int NRB = 2>
 __device__ __forceinline__ void assoc_body_fp4(const uint8_t* __restrict__ q, const uint8_t* __restrict__ qcolor, int nq,
                                                const int8_t* __restrict__ mx, const int8_t* __restrict__ mcx,
@@ -534,31 +357,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     assoc_body_fp4<true>(q, qcolor, nq, mx, mcx, nm_bound, nm_dev, nm_pad, m_chunk, max_distance, part, done, idx, dist, tile, ctile, xtab, ttab, tie_pieces, tie_counts, tie_res);
 }
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_assoc(const uint8_t* __restrict__ q, const uint8_t* __restrict__ qcolor, int nq,
-                                               const int8_t* __restrict__ mx, const int8_t* __restrict__ mcx,
-                                               int nm_bound, const int* __restrict__ nm_dev, int nm_pad, int m_chunk, int max_distance,
-                                               unsigned int* __restrict__ part, int* __restrict__ done, int32_t* __restrict__ idx, float* __restrict__ dist,
-                                               int* __restrict__ tie_pieces, int* __restrict__ tie_counts, unsigned long long* __restrict__ tie_res)
-{
-    __shared__ __attribute__((aligned(1024))) int8_t tile[3 * AM * 256];     // triple buffered map tile
-    __shared__ __attribute__((aligned(1024))) int8_t ctile[3 * AM * 32];     // the tiles' ninth-step operands
-    __shared__ uint2 xtab[256];
-    assoc_body<true>(q, qcolor, nq, mx, mcx, nm_bound, nm_dev, nm_pad, m_chunk, max_distance, part, done, idx, dist, tile, ctile, xtab, tie_pieces, tie_counts, tie_res);
-}
-
-// the same without colour gating: 8 MFMA steps per block (the block counter is the chain's start value), no ninth-step
-// operands streamed
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_assoc_plain(const uint8_t* __restrict__ q, const uint8_t* __restrict__ qcolor, int nq,
-                                               const int8_t* __restrict__ mx, const int8_t* __restrict__ mcx,
-                                               int nm_bound, const int* __restrict__ nm_dev, int nm_pad, int m_chunk, int max_distance,
-                                               unsigned int* __restrict__ part, int* __restrict__ done, int32_t* __restrict__ idx, float* __restrict__ dist,
-                                               int* __restrict__ tie_pieces, int* __restrict__ tie_counts, unsigned long long* __restrict__ tie_res)
-{
-    __shared__ __attribute__((aligned(1024))) int8_t tile[3 * AM * 256];
-    __shared__ uint2 xtab[256];
-    assoc_body<false>(q, qcolor, nq, mx, mcx, nm_bound, nm_dev, nm_pad, m_chunk, max_distance, part, done, idx, dist, tile, nullptr, xtab, tie_pieces, tie_counts, tie_res);
-}
-
 __global__ void k_fill_u32(unsigned int* p, size_t n, unsigned int v)
 {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -599,10 +397,10 @@ static hipError_t assoc_scratch_reserve(AssocScratch& w, size_t qblocks, size_t 
     return hipSuccess;
 }
 
-void launch_assoc_pack_map(const uint8_t* codes, const uint8_t* colors, int n, int n_pad, int fp4, int8_t* x, int8_t* cx, hipStream_t s)
+void launch_assoc_pack_map(const uint8_t* codes, int n, int n_pad, int8_t* x, hipStream_t s)
 {
     if (n_pad <= 0) return;
-    hipLaunchKernelGGL(k_assoc_pack_map, dim3(((size_t)n_pad * 32 + 255) / 256), dim3(256), 0, s, codes, colors, n, n_pad, fp4, x, cx);
+    hipLaunchKernelGGL(k_assoc_pack_map, dim3(((size_t)n_pad * 32 + 255) / 256), dim3(256), 0, s, codes, n, n_pad, x);
 }
 
 // association of raw query codes against a packed map (the live map keeps its side packed across calls; lf_associate
@@ -615,16 +413,13 @@ hipError_t launch_assoc_core(const uint8_t* q, const uint8_t* qcolor, int nq, co
     const int min_splits = (nm_pad + (kMaxBlocksPerChunk * 32) - 1) / (kMaxBlocksPerChunk * 32);
     // The shape: big = 256 queries per workgroup (two row blocks per wave, six tile buffers: 54 KB, 239 registers -- the fastest alone);
     // small = 128 (one row block, three buffers: 29 KB, ~160 registers -- the one that finds room beside other batches' region growing).
-    // LF_ASSOC_SHAPE=big|small forces one; otherwise small up to kAssocSmallMax queries (the pipelined front end's batches), big beyond.
-    static const int shape_env = getenv("LF_ASSOC_SHAPE") ? (getenv("LF_ASSOC_SHAPE")[0] == 's' ? 1 : (getenv("LF_ASSOC_SHAPE")[0] == 'b' ? 2 : 0)) : 0;
-    static const bool force_i8 = getenv("LF_ASSOC_INT8") != nullptr;
-    const bool small = !force_i8 && (shape_env == 1 || (shape_env == 0 && nq <= kAssocSmallMax));
+    // Small up to kAssocSmallMax queries (the pipelined front end's batches), big beyond.
+    const bool small = nq <= kAssocSmallMax;
     const int qw = small ? AQW / 2 : AQW;
     const int qblocks = (nq + qw - 1) / qw;
     // 2 workgroups are resident per CU: split the map so that the grid is one round of the 512 slots -- long chunks
     // amortise the query expansion and the final cross-lane reduction (measured: 512 > 1024 > 768 > 256); the small shape: 3 per CU
-    static const int slots_env = getenv("LF_ASSOC_SLOTS") ? atoi(getenv("LF_ASSOC_SLOTS")) : 0;
-    const int slots = slots_env > 0 ? slots_env : (small ? 1024 : 512);
+    const int slots = small ? 1024 : 512;
     int splits = slots / qblocks;
     if (splits > 128) splits = 128;            // one or two query blocks: more, shorter chunks only lengthen the merge (32 -> 19 us at 256 x 50 000)
     if (splits < min_splits) splits = min_splits;
@@ -651,14 +446,10 @@ hipError_t launch_assoc_core(const uint8_t* q, const uint8_t* qcolor, int nq, co
         tie_counts = w.tie_list + (size_t)splits * n_pieces * 64;
     }
     unsigned long long* tie_res = w.tie_res;
-    // ungated: the FP4 kernel (its map operands are e2m1 rows: MapDevice::fp4 / launch_assoc_pack_map(fp4 = 1));
-    // LF_ASSOC_INT8=1 keeps the int8 kernel for A/B runs -- the caller's operands must then be int8 rows
     if (small && gating) hipLaunchKernelGGL(k_assoc_fp4_gated_s, dim3(qblocks, splits), dim3(256), 0, s, q, qcolor, nq, mx, mcx, nm, nm_dev, nm_pad, m_chunk, max_distance, w.part, w.done, idx, dist, tie_pieces, tie_counts, tie_res);
     else if (small) hipLaunchKernelGGL(k_assoc_fp4_s, dim3(qblocks, splits), dim3(256), 0, s, q, nq, mx, nm, nm_dev, nm_pad, m_chunk, max_distance, w.part, w.done, idx, dist, tie_pieces, tie_counts, tie_res);
-    else if (gating && !force_i8) hipLaunchKernelGGL(k_assoc_fp4_gated, dim3(qblocks, splits), dim3(256), 0, s, q, qcolor, nq, mx, mcx, nm, nm_dev, nm_pad, m_chunk, max_distance, w.part, w.done, idx, dist, tie_pieces, tie_counts, tie_res);
-    else if (gating) hipLaunchKernelGGL(k_assoc, dim3(qblocks, splits), dim3(256), 0, s, q, qcolor, nq, mx, mcx, nm, nm_dev, nm_pad, m_chunk, max_distance, w.part, w.done, idx, dist, tie_pieces, tie_counts, tie_res);
-    else if (!force_i8) hipLaunchKernelGGL(k_assoc_fp4, dim3(qblocks, splits), dim3(256), 0, s, q, nq, mx, nm, nm_dev, nm_pad, m_chunk, max_distance, w.part, w.done, idx, dist, tie_pieces, tie_counts, tie_res);
-    else hipLaunchKernelGGL(k_assoc_plain, dim3(qblocks, splits), dim3(256), 0, s, q, qcolor, nq, mx, mcx, nm, nm_dev, nm_pad, m_chunk, max_distance, w.part, w.done, idx, dist, tie_pieces, tie_counts, tie_res);
+    else if (gating) hipLaunchKernelGGL(k_assoc_fp4_gated, dim3(qblocks, splits), dim3(256), 0, s, q, qcolor, nq, mx, mcx, nm, nm_dev, nm_pad, m_chunk, max_distance, w.part, w.done, idx, dist, tie_pieces, tie_counts, tie_res);
+    else hipLaunchKernelGGL(k_assoc_fp4, dim3(qblocks, splits), dim3(256), 0, s, q, nq, mx, nm, nm_dev, nm_pad, m_chunk, max_distance, w.part, w.done, idx, dist, tie_pieces, tie_counts, tie_res);
 #ifdef LF_ASSOC_STAMPS
     {
         static int calls = 0;
@@ -679,12 +470,10 @@ hipError_t launch_assoc_core(const uint8_t* q, const uint8_t* qcolor, int nq, co
     return hipGetLastError();
 }
 
-hipError_t launch_assoc(const uint8_t* q, int nq, const uint8_t* m, int nm, int8_t* mx, int8_t* mcx, AssocScratch& w, int32_t* idx,
-                        float* dist, hipStream_t s)
+hipError_t launch_assoc(const uint8_t* q, int nq, const uint8_t* m, int nm, int8_t* mx, AssocScratch& w, int32_t* idx, float* dist, hipStream_t s)
 {
-    static const bool force_i8 = getenv("LF_ASSOC_INT8") != nullptr;
-    launch_assoc_pack_map(m, nullptr, nm, (int)assoc_rows_padded_m(nm), force_i8 ? 0 : 1, mx, mcx, s);
-    return launch_assoc_core(q, nullptr, nq, mx, mcx, nm, nullptr, 0, 128, w, idx, dist, s);
+    launch_assoc_pack_map(m, nm, (int)assoc_rows_padded_m(nm), mx, s);
+    return launch_assoc_core(q, nullptr, nq, mx, nullptr, nm, nullptr, 0, 128, w, idx, dist, s);
 }
 
 // ---------------------------------------------------------------- float LBD (72-d)

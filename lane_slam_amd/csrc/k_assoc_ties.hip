@@ -22,7 +22,6 @@
 // per chunk, the queries that have to look there (their row of part[] against their optimum), and the matrix pass here runs on those
 // (chunk, 256 listed queries) pieces alone: about 1 / (number of chunks) of the N x M products instead of all of them.  A chunk is
 // cut into `subs` pieces of whole tile groups so that the few pieces still fill the chip.
-#include <cstdlib>
 #include "common.h"
 #include "mih_rank.h"
 
@@ -315,9 +314,7 @@ hipError_t launch_assoc_ties(const uint8_t* q, const uint8_t* qcolor, int nq, co
     // the distance pass must have been launched with w.tie_res = res: its merge step wrote the lists and reset the result words
     if (splits < 1 || splits > 128 || w.qblocks != qblocks || w.tie_res != res || !w.tie_list) return hipErrorInvalidValue;
     // the shape: SMALL up to 12 288 queries (a front end's batch: the pass must find room between other kernels), BIG beyond
-    // (LF_TIE_SHAPE=small|big overrides, for A/B runs)
-    static const char* forced = getenv("LF_TIE_SHAPE");
-    const bool small = forced ? forced[0] == 's' : nq <= 12288;
+    const bool small = nq <= 12288;
     const int trb = small ? 1 : 2, tgroup = small ? 1 : 2;
     if ((size_t)qblocks * 4 + 1 > (size_t)tgroup * 8192 / 4) return hipErrorInvalidValue;      // (the running piece counts of a chunk sit in one tile buffer)
     const int n_pieces = qblocks * 4;
@@ -333,8 +330,7 @@ hipError_t launch_assoc_ties(const uint8_t* q, const uint8_t* qcolor, int nq, co
     int sub_len = (tiles_chunk + subs - 1) / subs;
     sub_len = (sub_len + tgroup - 1) / tgroup * tgroup * 64;
     subs = (m_chunk + sub_len - 1) / sub_len;
-    static const int grid = getenv("LF_TIE_GRID") ? atoi(getenv("LF_TIE_GRID")) : 512;
-#define LF_TIE_LAUNCH(K) hipLaunchKernelGGL(K, dim3(grid), dim3(256), 0, s, q, qcolor, nq, mx, mcode, mcolor, nm, nm_dev, nm_pad, m_chunk, splits, subs, sub_len, pieces, counts, n_pieces, dist, res)
+#define LF_TIE_LAUNCH(K) hipLaunchKernelGGL(K, dim3(512), dim3(256), 0, s, q, qcolor, nq, mx, mcode, mcolor, nm, nm_dev, nm_pad, m_chunk, splits, subs, sub_len, pieces, counts, n_pieces, dist, res)
     if (small) { if (gating) LF_TIE_LAUNCH(k_assoc_ties_small<true>); else LF_TIE_LAUNCH(k_assoc_ties_small<false>); }
     else { if (gating) LF_TIE_LAUNCH(k_assoc_ties_big<true>); else LF_TIE_LAUNCH(k_assoc_ties_big<false>); }
 #undef LF_TIE_LAUNCH

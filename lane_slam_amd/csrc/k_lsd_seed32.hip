@@ -47,8 +47,6 @@
 // runs the final passes with 28 KB and 94 registers; the dense array and the chain's result (elements used, ranges) wait in global memory
 // in between.  As one kernel every problem held the larger footprint of both phases for the whole 0.45 ms, and in a pipeline whose SIMDs are
 // full of region-growing waves a stage costs its registers and LDS times its duration (123 k -> 129 k frames/s).
-// The dense phase exists in two forms: the wave form (default) and the level-synchronous block engine (-DLF_SEED_ENGINE=1: faster alone,
-// slower in the pipeline; tools/seed_engine_ab.sh).
 //
 // One workgroup per problem (frame, colour).  Elements are u32: bin << 20 | payload (compact index + 1 of a pixel with a
 // defined gradient, 0 for the others: only seeds need to be told apart).  A RANGE WITHOUT A SEED IS NEVER PARTITIONED: the loop
@@ -92,18 +90,9 @@ namespace lf {
 #endif
 constexpr int ST = LF_SEED_THREADS;  // threads of the list + chain kernel
 constexpr int SW = ST / 64;
-// the dense kernel in two forms (A/B): 1 = the block engine (all ranges of a block level by level, 512 threads), 0 = the wave form
-// (workgroup partitions down to 1024 elements, then single waves; 256 threads)
-#ifndef LF_SEED_ENGINE
-#define LF_SEED_ENGINE 0
-#endif
-#ifndef LF_SEED_DENSE_THREADS
-#define LF_SEED_DENSE_THREADS (LF_SEED_ENGINE ? 512 : 256)      // (wave form with two waves per problem: - 1.5 % in the pipeline; with one: does not run)
-#endif
-#ifndef LF_SEED_DENSE_OCC
-#define LF_SEED_DENSE_OCC (LF_SEED_ENGINE ? 2 : 4)      // waves per SIMD the register allocation must allow
-#endif
-constexpr int DT = LF_SEED_DENSE_THREADS;   // threads of the dense kernel (the block engine: one element per thread and row group)
+// the dense kernel: workgroup partitions down to 1024 elements, then single waves
+constexpr int DT = 256;              // threads of the dense kernel (with two waves per problem: - 1.5 % in the pipeline; with one: does not run)
+constexpr int kDenseOcc = 4;         // waves per SIMD the dense kernel's register allocation must allow
 constexpr int kBlock = LF_SEED_BLOCK; // ranges up to this size are worked off in an LDS block
 constexpr int SW2 = LF_SEED_WAVES2;  // waves that work in phase 2 of the wave form (each with a private LDS range)
 constexpr int kSmall = 1024;         // wave form: ranges up to this size are one wave's work, in LDS (16 rows)
@@ -114,7 +103,7 @@ constexpr int kWaveWords = kSmall + kSmall / 2 + 2 * 18 * 2 + 18 + 20 + 8 + 128;
 constexpr int kBlkWaveWords = kSmall / 2 + 2 * 18 * 2 + 18 + 20 + 8 + 128;
 constexpr int kBlkX = SW2 * kBlkWaveWords > kBlock / 2 ? SW2 * kBlkWaveWords : kBlock / 2;
 constexpr int kBlkRows = kBlock / 64 + 2;
-[[maybe_unused]] constexpr int kBlkWords = kBlock + kBlkX + (kBlkRows * 6 + 8) + 2 * (kBlock / 16);
+constexpr int kBlkWords = kBlock + kBlkX + (kBlkRows * 6 + 8) + 2 * (kBlock / 16);
 
 constexpr int kSortThreshold = 16;   // libstdc++ _S_threshold
 constexpr int kMaxLdsBytes = 150 * 1024;
@@ -865,412 +854,6 @@ __device__ __forceinline__ void introsort_loop_waves(uint32_t* E, int n, const S
 #endif
 }
 
-
-// ============================================================================================================================
-// The block engine (round 5, second form of the dense phase).  Ranges of up to kBlock elements are gathered into an LDS block --
-// several at a time -- and ALL the ranges of the loop inside the block are partitioned AT THE SAME TIME, level by level, by the whole
-// workgroup: element x of the block is thread ((x >> 6) % waves, x & 63)'s, which carries the bounds [f, l) and the depth allowance
-// of the range x currently belongs to in one register (the loop's ranges are disjoint: no table of ranges exists).  One level:
-//   (a) the leader (x == f) of every live range reads the three candidates and swaps the median to the front (__move_median_to_first);
-//   (b) every element compares itself with its range's pivot D[f]; the L / R ballots of its row become two bit planes, kept as 32-bit
-//       words beside their running popcount: the number of L (R) elements in front of any position is ONE 8-byte read, a mask and a
-//       count;
-//   (d) ranks from the planes: L elements in front of x minus those in front of f + 1, R elements from x to l; an L element of rank k
-//       is swapped iff k R elements lie to its right, an R element of rank k iff k L elements lie to its left (the header's rule); both
-//       publish their place under their rank in ONE u16 list (L under f + k, R under l - k: 2 K < l - f), and the first candidate of
-//       every (row, range) lowers the range's cut (min of the first L that stays and the leftmost swapped R);
-//   (e) the swapped elements fetch their partner's value, (f) store it, read the cut and shrink their bounds to [f, cut) or [cut, l).
-// Five barriers per level whatever the number of ranges, ~log2(n / 16) + a few levels; rows without a live range are skipped.  A range
-// whose depth allowance is used up is heap sorted by its leader lane (libstdc++'s fallback; adversarial inputs only).
-// It replaces the workgroup partitions in an LDS block, the single-wave partitions and the 64-element register windows (which cost
-// 5.3 k and 3.6 k cycles apiece as chains of dependent LDS round trips in a lone wave: 160 us of a 4 k-element problem's 200).
-#ifdef LF_SEED_STAMPS
-#define ENG_T0 long long et_ = (long long)wall_clock64(); if (threadIdx.x == 0) g_dbg_w[blockIdx.x % 8][0] += 1
-#define ENG_T(k) do { const long long n_ = (long long)wall_clock64(); if (threadIdx.x == 0) g_dbg_w[blockIdx.x % 8][k] += n_ - et_; et_ = n_; } while (0)
-#else
-#define ENG_T0 do { } while (0)
-#define ENG_T(k) do { } while (0)
-#endif
-constexpr int kEngRows = kBlock / 64;
-constexpr int kEngWordsP = 2 * kEngRows;                 // 32-bit words of a plane
-constexpr int kEngCut = kBlock / 16;                     // one cut slot per 16 positions: ranges are longer than 16 and disjoint
-constexpr int kEngBatch = 64;                            // ranges per block at most
-[[maybe_unused]] constexpr int kEngWords = kBlock + kBlock / 2 + 4 * (kEngWordsP + 2) + 2 * kEngCut + 8 + (kEngBatch + 2) + 2 * kEngBatch;
-static_assert(kBlock <= 8192 && kBlock % 512 == 0, "13-bit positions, whole rows per wave");
-typedef uint32_t eng_u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) eng_u32x2 lds_u32x2;
-
-__device__ __forceinline__ uint32_t eng_pack(int f, int l, int d) { return (uint32_t)f | ((uint32_t)(l - 1) << 13) | ((uint32_t)d << 26); }
-// elements of a plane in front of position q, given the plane's entry (bits, count in front of the word) for q >> 5
-__device__ __forceinline__ int eng_rank(eng_u32x2 e, int q) { return (int)e.y + __popc(e.x & ((1u << (q & 31)) - 1u)); }
-
-template <int NT>
-__device__ __forceinline__ void dense_blocks(uint32_t* E, const unsigned long long* list, int n_items, uint32_t* lds)
-{
-    constexpr int NW = NT / 64, RPT = kEngRows / NW, G = RPT < 4 ? RPT : 4;
-    static_assert(kEngRows % NW == 0 && RPT % G == 0 && RPT <= 32, "rows per thread");
-    lds_u32* D = as_lds<lds_u32>(lds);
-    lds_u16* PP = (lds_u16*)(D + kBlock);
-    lds_u32x2* LT = (lds_u32x2*)(D + kBlock + kBlock / 2);
-    lds_u32x2* RT = LT + (kEngWordsP + 2);
-    lds_i32* cutT = (lds_i32*)(RT + (kEngWordsP + 2));
-    lds_i32* flags = cutT + 2 * kEngCut;                  // [0], [1] per level: 1 = a live range, 2 = one without depth allowance; [2] seeds; [3] ranges; [4] elements
-    lds_i32* boff = flags + 8;                            // [ranges + 1] block offsets
-    lds_i32* bsrc = boff + (kEngBatch + 2);               // where a range lies in E
-    lds_i32* bdep = bsrc + kEngBatch;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    for (int i = t; i < kEngWordsP + 2; i += NT) { const eng_u32x2 z = { 0u, 0u }; LT[i] = z; RT[i] = z; }
-    int next = 0;
-    while (next < n_items) {
-        __syncthreads();
-        // ---- the next block: as many listed ranges as fit (wave 0)
-        if (w == 0) {
-            const int i = next + lane;
-            const unsigned long long it = i < n_items ? list[i] : 0ull;
-            const int rf = (int)(it & 0xffffffu), rl = (int)((it >> 24) & 0xffffffu);
-            const int sz = i < n_items ? rl - rf : 0;
-            const int inc = wave_incl_scan_i(sz, lane);
-            const bool fits = i < n_items && inc <= kBlock;
-            const int cnt = __popcll(__ballot(fits));             // sizes are positive: the fitting ones are a prefix
-            if (fits) { boff[lane] = inc - sz; bsrc[lane] = rf; bdep[lane] = (int)(it >> 48); }
-            if (lane == cnt - 1) { boff[cnt] = inc; flags[4] = inc; }
-            if (lane == 0) { flags[3] = cnt; flags[2] = 0; flags[0] = 0; flags[1] = 0; }
-        }
-        for (int i = t; i < kEngCut; i += NT) cutT[i] = 0x7fffffff;
-        __syncthreads();
-        const int cnt = flags[3], total = flags[4];
-        next += cnt;
-        // ---- copy in; every element's range
-        uint32_t st[RPT], tmp[RPT];
-        int gidx[RPT];
-        {
-            int seeds = 0, fl = 0;
-#pragma unroll
-            for (int j = 0; j < RPT; ++j) {
-                const int x = ((j * NW + w) << 6) | lane;
-                int k = 0;
-                if (cnt > 1) {
-                    int a = 0, b = cnt;                                   // the last range with boff <= x
-                    while (b - a > 1) { const int mid = (a + b) >> 1; if (boff[mid] <= x) a = mid; else b = mid; }
-                    k = a;
-                }
-                const bool in = x < total;
-                const int f = boff[k], l = boff[k + 1], d = bdep[k];
-                gidx[j] = in ? bsrc[k] + (x - f) : -1;
-                st[j] = in ? eng_pack(f, l, d) : 0u;
-                if (in) fl |= d == 0 ? 3 : 1;
-            }
-#pragma unroll
-            for (int j = 0; j < RPT; ++j) tmp[j] = gidx[j] >= 0 ? E[gidx[j]] : 0u;
-#pragma unroll
-            for (int j = 0; j < RPT; ++j) {
-                const int x = ((j * NW + w) << 6) | lane;
-                if (gidx[j] >= 0) { D[x] = tmp[j]; seeds |= (tmp[j] & 0xfffffu) != 0u; }
-            }
-            const unsigned long long sb = __ballot(seeds != 0);
-            fl = (__ballot(fl & 1) ? 1 : 0) | (__ballot(fl & 2) ? 2 : 0);
-            if (lane == 0) { if (sb) lds_or(&flags[2], 1); if (fl) lds_or(&flags[0], fl); }
-        }
-        __syncthreads();
-        if (flags[2] == 0) continue;                                      // no seed in the block: nothing to order
-        // ---- the levels
-        for (int lvl = 0;; ++lvl) {
-            ENG_T0;
-            const int p = lvl & 1;
-            lds_i32* cut_cur = cutT + p * kEngCut;
-            lds_i32* cut_nxt = cutT + (p ^ 1) * kEngCut;
-            const int fl = flags[p];
-            if (!(fl & 1)) break;
-            for (int i = t; i < kEngCut; i += NT) cut_nxt[i] = 0x7fffffff;
-            if (t == 0) flags[p ^ 1] = 0;
-            if (fl & 2) {                                                 // depth limit used up somewhere: libstdc++ heap sorts that range
-#pragma unroll
-                for (int j = 0; j < RPT; ++j) {
-                    const uint32_t s = st[j];
-                    const int x = ((j * NW + w) << 6) | lane;
-                    const int f = (int)(s & 0x1fffu), l = (int)((s >> 13) & 0x1fffu) + 1;
-                    if (l - f > kSortThreshold && (s >> 26) == 0u && x == f) heap_sort_range(lds, f, l);
-                }
-                __syncthreads();
-#pragma unroll
-                for (int j = 0; j < RPT; ++j) {
-                    const uint32_t s = st[j];
-                    const int f = (int)(s & 0x1fffu), l = (int)((s >> 13) & 0x1fffu) + 1;
-                    if (l - f > kSortThreshold && (s >> 26) == 0u) st[j] = 0u;
-                }
-            }
-            // (a) the leaders: the median of three to the front
-#pragma unroll
-            for (int g = 0; g < RPT; g += G) {
-                bool lead[G];
-                int f[G], l[G];
-                bool any = false;
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    const uint32_t s = st[g + u];
-                    const int x = (((g + u) * NW + w) << 6) | lane;
-                    f[u] = (int)(s & 0x1fffu); l[u] = (int)((s >> 13) & 0x1fffu) + 1;
-                    lead[u] = l[u] - f[u] > kSortThreshold && x == f[u];
-                    any |= lead[u];
-                }
-                if (__ballot(any) == 0ull) continue;
-                uint32_t ea[G], eb[G], ec[G], ef[G];
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    const int x = (((g + u) * NW + w) << 6) | lane;
-                    ea[u] = D[lead[u] ? f[u] + 1 : x]; eb[u] = D[lead[u] ? f[u] + ((l[u] - f[u]) >> 1) : x]; ec[u] = D[lead[u] ? l[u] - 1 : x]; ef[u] = D[x];
-                }
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    const int ia = f[u] + 1, ib = f[u] + ((l[u] - f[u]) >> 1), ic = l[u] - 1;
-                    int pick;
-                    if (comp(ea[u], eb[u])) pick = comp(eb[u], ec[u]) ? ib : (comp(ea[u], ec[u]) ? ic : ia);
-                    else pick = comp(ea[u], ec[u]) ? ia : (comp(eb[u], ec[u]) ? ic : ib);
-                    const uint32_t pv = pick == ia ? ea[u] : (pick == ib ? eb[u] : ec[u]);
-                    if (lead[u]) { D[f[u]] = pv; D[pick] = ef[u]; }
-                }
-            }
-            __syncthreads();
-            ENG_T(1);
-            // (b) L / R planes
-            uint32_t lmask = 0u, rmask = 0u;
-#pragma unroll
-            for (int g = 0; g < RPT; g += G) {
-                bool act[G];
-                int f[G];
-                bool any = false;
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    const uint32_t s = st[g + u];
-                    f[u] = (int)(s & 0x1fffu);
-                    act[u] = (int)((s >> 13) & 0x1fffu) + 1 - f[u] > kSortThreshold;
-                    any |= act[u];
-                }
-                if (__ballot(any) == 0ull) continue;
-                uint32_t v[G], pv[G];
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    const int x = (((g + u) * NW + w) << 6) | lane;
-                    v[u] = D[x]; pv[u] = D[act[u] ? f[u] : x];
-                }
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    const int row = (g + u) * NW + w;
-                    const int x = (row << 6) | lane;
-                    const bool part = act[u] && x > f[u];
-                    const uint32_t kp = key_of(pv[u]), kv = key_of(v[u]);
-                    const bool isL = part && kv <= kp, isR = part && kv >= kp;
-                    const unsigned long long bl = __ballot(isL), br = __ballot(isR);
-                    if (isL) lmask |= 1u << (g + u);
-                    if (isR) rmask |= 1u << (g + u);
-                    if (lane == 0) { LT[2 * row].x = (uint32_t)bl; LT[2 * row + 1].x = (uint32_t)(bl >> 32); RT[2 * row].x = (uint32_t)br; RT[2 * row + 1].x = (uint32_t)(br >> 32); }
-                }
-            }
-            __syncthreads();
-            ENG_T(2);
-            // (d) running counts of the planes (every wave writes the same table), ranks, places, cuts
-            {
-                int cL = 0, cR = 0;
-#pragma unroll
-                for (int r0 = 0; r0 < kEngWordsP; r0 += 64) {
-                    const int a = __popc(LT[r0 + lane].x), b = __popc(RT[r0 + lane].x);
-                    const int ia = wave_incl_scan_i(a, lane), ib = wave_incl_scan_i(b, lane);
-                    LT[r0 + lane].y = (uint32_t)(cL + ia - a); RT[r0 + lane].y = (uint32_t)(cR + ib - b);
-                    cL += wave_last(ia); cR += wave_last(ib);
-                }
-                if (lane == 0) { LT[kEngWordsP].y = (uint32_t)cL; RT[kEngWordsP].y = (uint32_t)cR; }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-            }
-            uint32_t swm = 0u;
-#pragma unroll
-            for (int g = 0; g < RPT; g += G) {
-                bool act[G];
-                int f[G], l[G];
-                bool any = false;
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    const uint32_t s = st[g + u];
-                    f[u] = (int)(s & 0x1fffu); l[u] = (int)((s >> 13) & 0x1fffu) + 1;
-                    act[u] = l[u] - f[u] > kSortThreshold;
-                    any |= act[u];
-                }
-                if (__ballot(any) == 0ull) continue;
-                eng_u32x2 lx[G], rx[G], lf[G], rl[G];
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    const int x = (((g + u) * NW + w) << 6) | lane;
-                    lx[u] = LT[x >> 5]; rx[u] = RT[x >> 5];
-                    lf[u] = LT[act[u] ? (f[u] + 1) >> 5 : x >> 5]; rl[u] = RT[act[u] ? l[u] >> 5 : x >> 5];
-                }
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    const int x = (((g + u) * NW + w) << 6) | lane;
-                    const bool isL = (lmask >> (g + u)) & 1u, isR = (rmask >> (g + u)) & 1u;
-                    const int l_left = eng_rank(lx[u], x) - eng_rank(lf[u], f[u] + 1), kl = l_left + 1;
-                    const int kr = eng_rank(rl[u], l[u]) - eng_rank(rx[u], x), r_right = kr - (isR ? 1 : 0);
-                    const bool swl = isL && r_right >= kl, swr = isR && l_left >= kr;
-                    if (swl) PP[f[u] + kl] = (uint16_t)x;
-                    if (swr) PP[l[u] - kr] = (uint16_t)x;
-                    tmp[g + u] = swl ? (uint32_t)(l[u] - kl) : (swr ? (uint32_t)(f[u] + kr) : 0u);
-                    if (swl || swr) swm |= 1u << (g + u);
-                    // the first candidate of this range in this row lowers the cut
-                    const bool cand = (isL && !swl) || swr;
-                    const unsigned long long cm = __ballot(cand);
-                    const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u));
-                    const int at_start = __builtin_amdgcn_ds_bpermute(4 * max(f[u] - (x & ~63), 0), before);
-                    if (cand && before == at_start) lds_min(&cut_cur[f[u] >> 4], x);
-                }
-            }
-            __syncthreads();
-            ENG_T(3);
-            // (e) the partner's value
-#pragma unroll
-            for (int g = 0; g < RPT; g += G) {
-                if (__ballot(((swm >> g) & ((1u << G) - 1u)) != 0u) == 0ull) continue;
-                int y[G];
-#pragma unroll
-                for (int u = 0; u < G; ++u) y[u] = (int)PP[((swm >> (g + u)) & 1u) ? tmp[g + u] : 0u];
-#pragma unroll
-                for (int u = 0; u < G; ++u) { const uint32_t vy = D[y[u]]; if ((swm >> (g + u)) & 1u) tmp[g + u] = vy; }
-            }
-            __syncthreads();
-            // (f) the swap, the cut, the bounds of the next level
-            {
-                int more = 0;
-#pragma unroll
-                for (int g = 0; g < RPT; g += G) {
-                    bool act[G];
-                    int f[G], l[G], cut[G];
-                    bool any = false;
-#pragma unroll
-                    for (int u = 0; u < G; ++u) {
-                        const uint32_t s = st[g + u];
-                        f[u] = (int)(s & 0x1fffu); l[u] = (int)((s >> 13) & 0x1fffu) + 1;
-                        act[u] = l[u] - f[u] > kSortThreshold;
-                        any |= act[u];
-                    }
-                    if (__ballot(any) == 0ull) continue;
-#pragma unroll
-                    for (int u = 0; u < G; ++u) cut[u] = cut_cur[act[u] ? f[u] >> 4 : 0];
-#pragma unroll
-                    for (int u = 0; u < G; ++u) {
-                        const int x = (((g + u) * NW + w) << 6) | lane;
-                        if ((swm >> (g + u)) & 1u) D[x] = tmp[g + u];
-                        if (act[u]) {
-                            const int d = (int)(st[g + u] >> 26) - 1;
-                            const int nf = x < cut[u] ? f[u] : cut[u], nl = x < cut[u] ? cut[u] : l[u];
-                            st[g + u] = eng_pack(nf, nl, d);
-                            if (nl - nf > kSortThreshold) more |= d == 0 ? 3 : 1;
-                        }
-                    }
-                }
-                more = (__ballot(more & 1) ? 1 : 0) | (__ballot(more & 2) ? 2 : 0);
-                if (lane == 0 && more) lds_or(&flags[p ^ 1], more);
-            }
-            __syncthreads();
-            ENG_T(4);
-        }
-        // ---- copy out
-#pragma unroll
-        for (int j = 0; j < RPT; ++j) {
-            const int x = ((j * NW + w) << 6) | lane;
-            if (gidx[j] >= 0) tmp[j] = D[x];
-        }
-#pragma unroll
-        for (int j = 0; j < RPT; ++j) if (gidx[j] >= 0) E[gidx[j]] = tmp[j];
-    }
-    __syncthreads();
-}
-
-
-// The introsort loop over the listed ranges of E (n = their total extent).  scratch: global, 3 n / 4 + 192 u64 entries (the list of
-// ranges of <= kBlock elements, then the two place lists of the global partitions); gtab: global row tables (6 words per 64 elements
-// of the longest range + 16) for ranges beyond rows_cap rows.
-template <int NT>
-__device__ __forceinline__ void introsort_loop_wg(uint32_t* E, int n, const SeedRange* ranges, int n_ranges, unsigned long long* scratch,
-                                                  uint32_t* lds, int rows_cap, uint32_t* gtab)
-{
-    // LDS: phase 1 = the row tables of the global partitions; phase 2 = the block engine's (aliased)
-    lds_u64* BL = as_lds<lds_u64>(lds);
-    lds_u64* BR = BL + rows_cap;
-    lds_i32* PL = (lds_i32*)(BR + rows_cap);
-    lds_i32* SX = PL + rows_cap;                          // rows_cap + 1 entries
-    unsigned long long* work_list = scratch;                           // ranges of 17 .. kBlock elements: phase 2
-    uint32_t* Lpos = reinterpret_cast<uint32_t*>(scratch + (n / 16 + 64) + (n / 1024 + 64));
-    uint32_t* Rpos = Lpos + (n / 2 + 8);
-    __shared__ int acc_[4];
-    lds_i32* acc = as_lds<lds_i32>(acc_);
-    __shared__ int big_stack[3 * (72 + kMaxRanges)];
-    __shared__ int n_big, n_work;
-    __shared__ int cur[4];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    auto pack = [](int f, int l, int depth) { return (unsigned long long)f | ((unsigned long long)l << 24) | ((unsigned long long)depth << 48); };
-    if (t == 0) {
-        n_big = 0; n_work = 0;
-        for (int i = 0; i < n_ranges; ++i) {
-            const int f = ranges[i].off, l = f + ranges[i].len, d = ranges[i].depth, sz = ranges[i].len;
-            if (sz > kBlock) { big_stack[3 * n_big] = f; big_stack[3 * n_big + 1] = l; big_stack[3 * n_big + 2] = d; ++n_big; }
-            else if (sz > kSortThreshold) work_list[n_work++] = pack(f, l, d);
-        }
-    }
-    __syncthreads();
-    SEED_T(ta);
-    // ---- phase 1: ranges of more than kBlock elements, in global memory
-    for (;;) {
-        if (t == 0) {
-            if (n_big > 0) { --n_big; cur[0] = big_stack[3 * n_big]; cur[1] = big_stack[3 * n_big + 1]; cur[2] = big_stack[3 * n_big + 2]; cur[3] = 1; }
-            else cur[3] = 0;
-        }
-        __syncthreads();
-        if (!cur[3]) break;
-        int f = cur[0], l = cur[1], depth = cur[2];
-        __syncthreads();
-        // the libstdc++ loop on this range: go on with the left part while it is big, park the right part
-        while (l - f > kBlock) {
-            if (depth == 0) {
-                if (t == 0) heap_sort_range(E, f, l);
-                __syncthreads();
-                l = f;
-                break;
-            }
-            --depth;
-            if (t == 0) median_to_first(E, f, l);
-            __syncthreads();
-            int cut;
-            if (((l - f - 1 + 63) >> 6) <= rows_cap - 1) cut = partition_global<NT>(E, f, l, BL, BR, PL, SX, acc, Lpos, Rpos, w, lane);
-            else {
-                const int rc = ((l - f) >> 6) + 2;
-                unsigned long long* gBL = reinterpret_cast<unsigned long long*>(gtab);
-                unsigned long long* gBR = gBL + rc;
-                int* gPL = reinterpret_cast<int*>(gBR + rc);
-                int* gSX = gPL + rc;
-                cut = partition_global<NT>(E, f, l, gBL, gBR, gPL, gSX, acc, Lpos, Rpos, w, lane);
-            }
-#ifdef LF_SEED_STAMPS
-            if (t == 0) atomicAdd(&g_dbg_big[blockIdx.x % 8], 1);
-#endif
-            if (cut < 0) { l = f; break; }                           // no seed in the range: nothing to order
-            if (t == 0) {
-                const int rs = l - cut;
-                if (rs > kBlock) { big_stack[3 * n_big] = cut; big_stack[3 * n_big + 1] = l; big_stack[3 * n_big + 2] = depth; ++n_big; }
-                else if (rs > kSortThreshold) work_list[n_work++] = pack(cut, l, depth);
-            }
-            l = cut;
-            __syncthreads();
-        }
-        if (t == 0 && l - f > kSortThreshold) work_list[n_work++] = pack(f, l, depth);
-        __syncthreads();
-    }
-    SEED_T(tb);
-    // ---- phase 2: everything else, block by block in LDS
-    const int nw = n_work;
-    __syncthreads();
-    dense_blocks<NT>(E, work_list, nw, lds);
-#ifdef LF_SEED_STAMPS
-    { const long long tc = (long long)wall_clock64(); if (t == 0) { g_dbg_t[blockIdx.x % 8][0] = tb - ta; g_dbg_t[blockIdx.x % 8][1] = tc - tb; g_dbg_small[blockIdx.x % 8] = nw; } }
-#endif
-}
 
 // ============================================================================================================================
 // The chain: the top of the introsort loop on the explicit list (header).  One problem's global work areas, each of at least
@@ -2120,7 +1703,7 @@ __device__ __forceinline__ void seed_radix_pass(const uint32_t* __restrict__ src
 
 // The sort of one problem is two kernels (round 5, second half): k_lsd_seed32 builds the explicit list and runs the CHAIN on it -- bit
 // planes of the whole gradient image in LDS, 256 threads --, k_lsd_seed32_dense the introsort loop on the dense ranges the chain left and
-// the final insertion sort -- the block engine, 512 threads, half the LDS.  Between them: the dense array E in global memory and the
+// the final insertion sort -- the wave form, 256 threads, half the LDS.  Between them: the dense array E in global memory and the
 // chain's result (elements used, ranges) in the first words of the problem's RT area.
 
 // kernel 1: the chain on the explicit list (m entries; positions in W.P0, values in W.V0) over an array of n elements with n_seeds seeds
@@ -2155,12 +1738,8 @@ __device__ __forceinline__ void seed32_dense(const SeedWork& W, int n_seeds, int
     for (int i = t; i < n_ranges; i += NT) { ranges[i].off = state[2 + 3 * i]; ranges[i].len = state[3 + 3 * i]; ranges[i].depth = state[4 + 3 * i]; }
     __syncthreads();
     SEED_T(t1);
-#if LF_SEED_ENGINE
-    introsort_loop_wg<NT>(W.E, M, ranges, n_ranges, W.dscratch, lds, rows_cap, W.PP);
-#else
     static_assert(NT == 64 * SW2, "the wave form's workgroup");
     introsort_loop_waves<NT>(W.E, M, ranges, n_ranges, W.dscratch, lds, rows_cap, W.PP);
-#endif
     SEED_T(t2);
     // ---- the seeds in array order ...
     uint32_t* A = W.out;
@@ -2363,7 +1942,7 @@ __global__ __launch_bounds__(ST, LF_SEED_OCC) void k_lsd_seed32(LsdParams p, int
 }
 
 // kernel 2 of a problem: see seed32_dense
-__global__ __launch_bounds__(DT, LF_SEED_DENSE_OCC) void k_lsd_seed32_dense(LsdParams p, const int* __restrict__ n_rec, double* l_mod,
+__global__ __launch_bounds__(DT, kDenseOcc) void k_lsd_seed32_dense(LsdParams p, const int* __restrict__ n_rec, double* l_mod,
                                                             unsigned long long* __restrict__ sort_a, unsigned long long* __restrict__ sort_b,
                                                             uint32_t* __restrict__ order_a, uint32_t* __restrict__ order_b, int rows_cap)
 {
@@ -2415,7 +1994,7 @@ __global__ __launch_bounds__(ST, LF_SEED_OCC) void k_std_sort_debug(const uint32
     if (seed32_chain(W, n, m, m, seed_lds, lds_words) && t == 0) *count = 0;      // (cannot happen: cap >= n)
 }
 
-__global__ __launch_bounds__(DT, LF_SEED_DENSE_OCC) void k_std_sort_debug_dense(uint32_t* __restrict__ work, int cap, int rows_cap, const int* __restrict__ count)
+__global__ __launch_bounds__(DT, kDenseOcc) void k_std_sort_debug_dense(uint32_t* __restrict__ work, int cap, int rows_cap, const int* __restrict__ count)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t seed_lds[];
     __shared__ int tot[SNB];
@@ -2442,16 +2021,12 @@ static size_t seed_lds_bytes(long long n)
     if (!planes && words < 8192) words = 8192;                            // room for the planes of a range once it is short enough
     return words * sizeof(uint32_t);
 }
-// ... of the dense kernel: the block engine, the row tables of the global partitions, the counters of the final passes
+// ... of the dense kernel: the row tables of the global partitions, the waves' private ranges, an LDS block, the counters of the final passes
 static size_t seed_dense_lds_bytes(int rows_cap)
 {
     size_t words = (size_t)rows_cap * 6 + 128;
-#if LF_SEED_ENGINE
-    if (words < (size_t)kEngWords) words = (size_t)kEngWords;
-#else
     if (words < (size_t)SW2 * kWaveWords) words = (size_t)SW2 * kWaveWords;
     if (words < (size_t)kBlkWords) words = (size_t)kBlkWords;
-#endif
     if (words < (size_t)SNB * DT) words = (size_t)SNB * DT;
     return words * sizeof(uint32_t);
 }

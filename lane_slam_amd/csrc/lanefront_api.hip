@@ -869,10 +869,8 @@ extern "C" int lf_associate(lf_handle* h, const uint8_t* query32, int nq, const 
     }
     const size_t nm_pad = assoc_rows_padded_m(nm);
     int rc;
-    if ((rc = ensure(h, h->a_mx, nm_pad * 256)) || (rc = ensure(h, h->a_mcx, nm_pad * 32))) return rc;
-    // the int8 A/B kernels (LF_ASSOC_INT8) have no tie pass: the lowest index there, said once
-    const bool ties = h->tie_rule == LF_TIE_MIHASHER && !getenv("LF_ASSOC_INT8");
-    if (h->tie_rule == LF_TIE_MIHASHER && !ties) { static bool told = false; if (!told) { told = true; fprintf(stderr, "lanefront: LF_ASSOC_INT8 is set: lf_associate falls back to LF_TIE_LOWEST (the int8 A/B kernels have no tie pass)\n"); } }
+    if ((rc = ensure(h, h->a_mx, nm_pad * 256)) != LF_OK) return rc;     // 256 B per 128-B row: the tile loop's LDS-DMA read-ahead is not shown to stay within 128 B x nm_pad
+    const bool ties = h->tie_rule == LF_TIE_MIHASHER;
     if (ties && (rc = ensure(h, h->a_best, (size_t)nq * 8)) != LF_OK) return rc;
     const uint8_t *dq = query32, *dmp = map32;
     int32_t* didx = idx; float* ddist = dist;
@@ -886,7 +884,7 @@ extern "C" int lf_associate(lf_handle* h, const uint8_t* query32, int nq, const 
     {
         StageTimer t(h, ST_ASSOC);
         h->a_ws.tie_res = ties ? static_cast<unsigned long long*>(h->a_best.p) : nullptr;      // (the distance pass then lists the queries of the tie pass)
-        LF_HIP_CHECK(h, launch_assoc(dq, nq, dmp, nm, (int8_t*)h->a_mx.p, (int8_t*)h->a_mcx.p, h->a_ws, didx, ddist, s));
+        LF_HIP_CHECK(h, launch_assoc(dq, nq, dmp, nm, (int8_t*)h->a_mx.p, h->a_ws, didx, ddist, s));
         if (ties)
             LF_HIP_CHECK(h, launch_assoc_ties(dq, nullptr, nq, (const int8_t*)h->a_mx.p, dmp, nullptr, nm, nullptr, 0, h->a_ws,
                                               static_cast<unsigned long long*>(h->a_best.p), didx, ddist, s));

@@ -158,7 +158,7 @@ struct lf_handle {
     lf::DevArray<float> d_centers;
     int out_capacity = 0;
     // associator scratch (grown on demand)
-    lf::DevBuf a_q, a_m, a_mx, a_mcx, a_best, a_idx, a_dist, a_qn, a_mn;
+    lf::DevBuf a_q, a_m, a_mx, a_best, a_idx, a_dist, a_qn, a_mn;
     lf::DevBuf km_pts, km_lab, km_f64, km_cnt;
     lf::DevBuf kn_hist, kn_count, kn_off, kn_total;       // radiusMatch scratch
     lf::AssocScratch a_ws;

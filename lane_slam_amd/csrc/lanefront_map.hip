@@ -11,7 +11,7 @@ using namespace lf;
 
 struct lf_map {
     lf_map_config cfg;
-    int tie_rule = LF_TIE_LOWEST;
+    int tie_rule = LF_TIE_MIHASHER;          // the reference's tie rule (round 5)
     int device = 0;
     hipStream_t stream = nullptr;
     char err[512];
@@ -226,10 +226,9 @@ extern "C" int lf_map_create(int device_id, const lf_map_config* cfg, lf_map** o
     {
         // The map's steps are the one serial chain of a pipelined front end (step k's association needs step k - 1's update): its
         // kernels go to a HIGH-PRIORITY stream, so that their workgroups (76 KB of LDS each) are not the last to find room between the
-        // region-growing workgroups of the batches in flight (LF_MAP_PRIORITY=0: a plain stream, for A/B)
+        // region-growing workgroups of the batches in flight (a plain stream where the device has no priority range)
         int least = 0, greatest = 0;
-        static const bool plain = getenv("LF_MAP_PRIORITY") && atoi(getenv("LF_MAP_PRIORITY")) == 0;
-        if (!plain && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
             CREATE_HIP(hipStreamCreateWithPriority(&m->stream, hipStreamNonBlocking, greatest));
         else
             CREATE_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
@@ -243,7 +242,7 @@ extern "C" int lf_map_create(int device_id, const lf_map_config* cfg, lf_map** o
     CREATE_HIP(m->hits.alloc(cap * sizeof(int)));
     CREATE_HIP(m->last_seen.alloc(cap * sizeof(int)));
     CREATE_HIP(m->winner.alloc(cap * sizeof(int)));
-    CREATE_HIP(m->mx.alloc(m->cap_pad * 256));
+    CREATE_HIP(m->mx.alloc(m->cap_pad * 256));      // 256 B per 128-B row: the tile loop's LDS-DMA read-ahead is not shown to stay within 128 B x cap_pad
     CREATE_HIP(m->mcx.alloc(m->cap_pad * 32));
     CREATE_HIP(m->state.alloc(16 * sizeof(int)));
     CREATE_HIP(m->totals.alloc(2 * sizeof(unsigned long long)));
@@ -267,10 +266,6 @@ extern "C" int lf_map_create(int device_id, const lf_map_config* cfg, lf_map** o
 #undef CREATE_HIP
     m->d.capacity = cfg->capacity; m->d.policy = cfg->policy; m->d.kept_only = cfg->kept_only;
     m->d.merge_distance = cfg->merge_distance; m->d.when_full = cfg->when_full;
-    m->d.fp4 = getenv("LF_ASSOC_INT8") ? 0 : 1;          // e2m1 operands for the FP4 matrix instruction (int8 rows only for A/B runs)
-    // the reference's tie rule is the default (round 5); the int8 A/B kernels have no tie pass: the lowest index there, said once
-    m->tie_rule = m->d.fp4 ? LF_TIE_MIHASHER : LF_TIE_LOWEST;
-    if (!m->d.fp4) { static bool told = false; if (!told) { told = true; fprintf(stderr, "lanefront: LF_ASSOC_INT8 is set: the live map falls back to LF_TIE_LOWEST (the int8 A/B kernels have no tie pass)\n"); } }
     *out = m;
     return LF_OK;
 }
@@ -423,7 +418,6 @@ extern "C" int lf_map_set_tie_rule(lf_map* m, int tie_rule)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
     if (tie_rule != LF_TIE_LOWEST && tie_rule != LF_TIE_MIHASHER) { map_error(m, "lf_map_set_tie_rule: unknown rule"); return LF_ERR_BAD_ARG; }
-    if (tie_rule == LF_TIE_MIHASHER && !m->d.fp4) { map_error(m, "LF_ASSOC_INT8 (the int8 A/B kernels) supports LF_TIE_LOWEST only"); return LF_ERR_UNSUPPORTED; }
     m->tie_rule = tie_rule;
     return LF_OK;
 }

@@ -8,8 +8,6 @@ python bench.py > $R/gpurun_out/$T/bench_n1.json 2> $R/gpurun_out/$T/bench_n1.er
 python bench.py --gpus 1 --steps 20 --warmup 5 --secondary none > $R/gpurun_out/$T/bench_driver_form.json 2>/dev/null
 python tools/assoc_rate.py --tie-rule lowest > $R/gpurun_out/$T/assoc_rate.txt 2>&1
 python tools/assoc_rate.py --tie-rule mihasher >> $R/gpurun_out/$T/assoc_rate.txt 2>&1
-LF_TIE_SHAPE=big python tools/assoc_rate.py --tie-rule mihasher --pairs 4096x50000,16384x50000 >> $R/gpurun_out/$T/assoc_rate.txt 2>&1
-LF_TIE_SHAPE=small python tools/assoc_rate.py --tie-rule mihasher --pairs 4096x50000,16384x50000 >> $R/gpurun_out/$T/assoc_rate.txt 2>&1
 # round 5: the A/B options beside the defaults (opencv32 + mihasher), same call
 for ab in "opencv32 lowest" "opencv30 mihasher" "opencv30 lowest"; do set -- $ab; python bench.py --steps 100 --secondary none --cpu-frames -1 --seed-order $1 --tie-rule $2 > $R/gpurun_out/$T/bench_ab_$1_$2.json 2>/dev/null; done
 python bench.py --geometry hd --steps 30 --secondary none --cpu-frames -1 > $R/gpurun_out/$T/bench_hd.json 2>/dev/null
@@ -22,8 +20,6 @@ for c in real clutter; do for sk in "" grow; do echo -n "$c skip=[$sk] "; LF_DIA
 LF_ALLOC_TRACE=1 python tools/handle_footprint.py 2> $R/gpurun_out/$T/handle_footprint.txt
 bash tools/whatif_round.sh > $R/gpurun_out/$T/whatif.txt 2>&1
 python tools/assoc_rate.py --gating --pairs 16384x50000 >> $R/gpurun_out/$T/assoc_rate.txt 2>&1
-LF_ASSOC_INT8=1 python tools/assoc_rate.py --pairs 16384x50000,65536x262144 >> $R/gpurun_out/$T/assoc_rate.txt 2>&1
-LF_ASSOC_INT8=1 python tools/assoc_rate.py --gating --pairs 16384x50000 >> $R/gpurun_out/$T/assoc_rate.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
 B="--secondary none --cpu-frames -1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/$T/d6 -- python3 $R/bench.py --steps 12 --warmup 4 $B > $R/gpurun_out/$T/bench_d6_rocprof.json 2>/dev/null
