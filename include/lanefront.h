@@ -213,6 +213,26 @@ typedef struct lf_hough_params {
 LF_API void lf_hough_default_params(lf_hough_params* p);
 LF_API int lf_set_hough_params(lf_handle* h, const lf_hough_params* p);
 LF_API int lf_get_hough_params(const lf_handle* h, lf_hough_params* p);
+/*   LF_DETECTOR_DENSE    the reference's LineDetector2Dense (line_detector2.py:8-119, selected by default_ld2.yaml): every
+ *                        pixel of the colour's edge map (Canny AND the dilated mask) whose negated 5x5 Sobel gradient of the
+ *                        UNDILATED 0/1 mask (reflect-101 border) has a float32 magnitude above sobel_threshold becomes a line:
+ *                        the unit gradient is its normal (float32, signed zeros kept), the line runs 6 pixels either side of
+ *                        the pixel along it (coordinates truncated toward zero, clipped to the working image), with no
+ *                        _findNormal and no reordering; the pixel is its centre.  Lines come in raster order per colour; then
+ *                        the same normalisation, projection, line sanity and LBD stages, pipelined the same way.
+ *                        params_or_null is not read: the threshold is the handle's (lf_set_dense_params).  The line count
+ *                        grows with the edge pixels: a colour with more than max_lines_per_color is LF_ERR_CAPACITY.  The
+ *                        plugin path runs it too; lf_detect_lines' area is then the undilated mask, as the reference's. */
+#define LF_DETECTOR_DENSE 3
+/* LineDetector2Dense's sobel_threshold key (default_ld2.yaml: 40), compared in float32 as the reference's numpy does.  NaN and
+ * negative values are LF_ERR_BAD_ARG (a negative threshold would keep every pixel, zero gradients included).  Defaults
+ * (lf_dense_default_params, and a new handle's): 40.0.  Not while a batch is in flight. */
+typedef struct lf_dense_params {
+    double sobel_threshold;
+} lf_dense_params;
+LF_API void lf_dense_default_params(lf_dense_params* p);
+LF_API int lf_set_dense_params(lf_handle* h, const lf_dense_params* p);
+LF_API int lf_get_dense_params(const lf_handle* h, lf_dense_params* p);
 
 /* ---- association: replaces BinaryDescriptorMatcher::match ------------------
  * (binary_descriptor_matcher.cpp:197-254): exact Hamming nearest neighbour of
@@ -751,7 +771,7 @@ LF_API int lf_lsd_list_capacity(const lf_handle* h, int* entries, int* grown);
 LF_API int lf_lsd_scratch_stride(const lf_handle* h);
 
 /* per-kernel timing with HIP events on the handle's stream */
-#define LF_N_STAGES 15     /* stage 14: hough (LF_DETECTOR_HOUGH) */
+#define LF_N_STAGES 16     /* stage 14: hough (LF_DETECTOR_HOUGH), 15: dense (LF_DETECTOR_DENSE) */
 LF_API int lf_set_profiling(lf_handle* h, int enabled);
 /* ms accumulated per stage since the last reset, and launches counted */
 LF_API int lf_get_timing(lf_handle* h, double* ms_per_stage, int32_t* launches_per_stage, int n);

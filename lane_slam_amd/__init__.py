@@ -4,6 +4,7 @@ ground-project, sanity-filter, associate) behind a C ABI (include/lanefront.h).
 The package is a thin host-side mirror of the reference's interfaces for this path:
   LineDetectorHIP  <->  line_detector.LineDetectorLSD (LineDetectorInterface plugin)
   LineDetectorHSV  <->  line_detector.LineDetectorHSV: the same plugin with cv2.HoughLinesP in place of LSD (LF_DETECTOR_HOUGH)
+  LineDetector2Dense <-> line_detector.LineDetector2Dense: a line per steep-gradient edge pixel (LF_DETECTOR_DENSE)
   LineDetectorEDLines   the same plugin interface over the line_descriptor library's EDLines detector; FrontEnd.keylines_batch /
                         describe_keylines <-> BinaryDescriptor::detect / compute with octaves (SURVEY 8f-4)
   LineAssociator   <->  line_associator node (a stub in the reference) + show_map's segment store: device-resident
@@ -21,7 +22,7 @@ from .frontend import FrontEnd, LanefrontError, Segments
 from .lane_filter import LaneFilterBatch, LaneFilterHistogram
 from .line_associator import LineAssociator
 from .matcher import BinaryDescriptorMatcher, BinaryDescriptorParams, DMatch
-from .line_detector_hip import Detections, LineDetectorEDLines, LineDetectorHIP, LineDetectorHSV, LineDetectorInterface
+from .line_detector_hip import Detections, LineDetector2Dense, LineDetectorEDLines, LineDetectorHIP, LineDetectorHSV, LineDetectorInterface
 
-__all__ = ["LaneFilterBatch", "LaneFilterHistogram", "BinaryDescriptorMatcher", "BinaryDescriptorParams", "DMatch", "LineAssociator", "FrontEnd", "LanefrontError", "Segments", "LineDetectorHIP", "LineDetectorHSV", "LineDetectorEDLines", "LineDetectorInterface", "Detections",
+__all__ = ["LaneFilterBatch", "LaneFilterHistogram", "BinaryDescriptorMatcher", "BinaryDescriptorParams", "DMatch", "LineAssociator", "FrontEnd", "LanefrontError", "Segments", "LineDetectorHIP", "LineDetectorHSV", "LineDetector2Dense", "LineDetectorEDLines", "LineDetectorInterface", "Detections",
            "default_config", "DEFAULT_DETECTOR_CONFIGURATION", "WHITE", "YELLOW", "RED", "COLOR_NAMES"]

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # -DLFG_STAMPS); the default is the in-tree product build.
 SO_PATH = os.environ.get("LANEFRONT_LIBRARY") or os.path.join(_HERE, "liblanefront.so")
 
-LF_N_STAGES = 15
+LF_N_STAGES = 16
 LF_MAP_N_STAGES = 4
 LF_MSG_DETECTOR, LF_MSG_GROUND, LF_MSG_FILTERED = 0, 1, 2
 (LF_BUF_BGR, LF_BUF_MASKS, LF_BUF_EDGES, LF_BUF_LSD_ANGLE, LF_BUF_LSD_MODGRAD, LF_BUF_LSD_ORDER,
@@ -34,6 +34,7 @@ EXPORTS = (
     "lf_lane_filter_set_tables", "lf_lane_filter_reset", "lf_lane_filter_step", "lf_lane_filter_get_poses", "lf_lane_filter_get_belief",
     "lf_lane_filter_synchronize", "lf_lane_filter_set_profiling", "lf_lane_filter_get_timing", "lf_lane_filter_stage_name",
     "lf_hough_default_params", "lf_set_hough_params", "lf_get_hough_params",
+    "lf_dense_default_params", "lf_set_dense_params", "lf_get_dense_params",
 )
 LF_LANE_FILTER_PREDICT, LF_LANE_FILTER_UPDATE = 1, 2
 LF_LANE_FILTER_MAX_CELLS = 4096
@@ -41,9 +42,11 @@ LF_LANE_FILTER_N_STAGES = 2
 # the 17 keys of LaneFilterHistogram's configuration, in lf_lane_filter_config's (and the reference's param_names) order
 LANE_FILTER_PARAMS = ("mean_d_0", "mean_phi_0", "sigma_d_0", "sigma_phi_0", "delta_d", "delta_phi", "d_max", "d_min", "phi_max",
                       "phi_min", "cov_v", "linewidth_white", "linewidth_yellow", "lanewidth", "min_max", "sigma_d_mask", "sigma_phi_mask")
-DETECTORS = {"lsd": 0, "edlines": 1, "hough": 2}
+DETECTORS = {"lsd": 0, "edlines": 1, "hough": 2, "dense": 3}
 # the configuration keys of LineDetectorHSV that cv2.HoughLinesP reads, in lf_hough_params' order
 HOUGH_KEYS = ("hough_threshold", "hough_min_line_length", "hough_max_line_gap")
+# the configuration key of LineDetector2Dense that lf_dense_params holds
+DENSE_KEYS = ("sobel_threshold",)
 TIE_RULES = {"lowest": 0, "mihasher": 1}
 LF_MAX_OCTAVES = 5
 
@@ -68,6 +71,11 @@ class LfHoughParams(ctypes.Structure):
     """ctypes mirror of `lf_hough_params` (include/lanefront.h)."""
     _fields_ = [("threshold", ctypes.c_int32), ("min_line_length", ctypes.c_int32), ("max_line_gap", ctypes.c_int32),
                 ("rho", ctypes.c_double), ("theta", ctypes.c_double)]
+
+
+class LfDenseParams(ctypes.Structure):
+    """ctypes mirror of `lf_dense_params` (include/lanefront.h)."""
+    _fields_ = [("sobel_threshold", ctypes.c_double)]
 
 
 class LfDescriptorParams(ctypes.Structure):
@@ -253,6 +261,12 @@ def load():
     lib.lf_set_hough_params.restype = ci
     lib.lf_get_hough_params.argtypes = [vp, ctypes.POINTER(LfHoughParams)]
     lib.lf_get_hough_params.restype = ci
+    lib.lf_dense_default_params.argtypes = [ctypes.POINTER(LfDenseParams)]
+    lib.lf_dense_default_params.restype = None
+    lib.lf_set_dense_params.argtypes = [vp, ctypes.POINTER(LfDenseParams)]
+    lib.lf_set_dense_params.restype = ci
+    lib.lf_get_dense_params.argtypes = [vp, ctypes.POINTER(LfDenseParams)]
+    lib.lf_get_dense_params.restype = ci
     lib.lf_suggested_depth.argtypes = [vp]
     lib.lf_lsd_list_capacity.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
     lib.lf_lsd_list_capacity.restype = ci

@@ -24,7 +24,7 @@ constexpr int kCompCap = 1024;      // component list entries per problem (more 
 
 enum Stage {
     ST_PRE = 0, ST_CANNY, ST_HYST, ST_LSD_GRAD, ST_LSD_ORDER, ST_LSD_GROW, ST_SEGMENTS,
-    ST_LBD_GRAD, ST_LBD, ST_ASSOC_PACK, ST_ASSOC, ST_MISC, ST_JPEG, ST_LSD_LABEL, ST_HOUGH, ST_COUNT
+    ST_LBD_GRAD, ST_LBD, ST_ASSOC_PACK, ST_ASSOC, ST_MISC, ST_JPEG, ST_LSD_LABEL, ST_HOUGH, ST_DENSE, ST_COUNT
 };
 static_assert(ST_COUNT == LF_N_STAGES, "stage table out of sync with lanefront.h");
 
@@ -129,7 +129,7 @@ extern "C" void lf_set_error(lf_handle* h, int code, const char* fmt, ...);
 namespace lf {
 void launch_pre_gray(const PreParams& p, const uint8_t* frames, int n_frames, uint8_t* gray, hipStream_t s);
 void launch_pre(const PreParams& p, const uint8_t* frames, int n_frames, uint32_t* bgr, uint8_t* gray,
-                uint32_t* maskbits, const int* sdiv, const int* hdiv, hipStream_t s);
+                uint32_t* maskbits, const int* sdiv, const int* hdiv, hipStream_t s, uint32_t* bwbits = nullptr);
 void launch_canny(const CannyParams& p, const uint32_t* bgr, int n_frames, uint32_t* strong, uint32_t* weak,
                   hipStream_t s);
 int launch_hysteresis(const CannyParams& p, int n_frames, uint32_t* strong, const uint32_t* weak, hipStream_t s);
@@ -170,9 +170,15 @@ constexpr int kGrowLdsKb[3] = { 13, 28, 40 };           // the slice sizes a han
 int lsd_grow_pend_cap(const LsdParams& p);      // entries per problem of the pending-region list (k_lsd_eval)
 void launch_seg_offsets(int n_frames, int cap_lines, const int* counts, int* seg_offset, int* frame_offset,
                         int* overflow, const int* norder, int cap_small, int cap_medium, hipStream_t s);
+// LineDetector2Dense's per-pixel lines (k_dense.hip): slots [pc][cap] of lines (exact ints as floats) and (nx, ny, x, y) records
+void launch_dense(int Hc, int W, int Ww, int cap_lines, float thr, int n_problems, const uint32_t* strong, const uint32_t* maskbits,
+                  const uint32_t* bwbits, float* slot_lines, float* rec, int* counts, hipStream_t s);
+// what the slots of the last detect hold, and so which a-5 k_segments applies (k_segments.hip)
+enum SegMode { SEG_FLOAT = 0, SEG_HOUGH = 1, SEG_DENSE = 2 };
+// side: the dilated mask bit planes (SEG_FLOAT, SEG_HOUGH) or the dense slots' (nx, ny, x, y) float4 records (SEG_DENSE)
 void launch_segments(const SegParams& p, int n_frames, const float* slot_lines, const int* counts,
-                     const int* seg_offset, const uint32_t* maskbits, int Ww, lf_segments out, int* seg_frame,
-                     double* normals64, float* centers, hipStream_t s, bool int_lines = false);
+                     const int* seg_offset, const uint32_t* side, int Ww, lf_segments out, int* seg_frame,
+                     double* normals64, float* centers, hipStream_t s, SegMode mode = SEG_FLOAT);
 void launch_lbd_grad(int Hc, int W, int n_frames, const uint8_t* gray, uint32_t* dxy, hipStream_t s);
 // gradient planes of the octaves of a KeyLine batch: [B][H*W] dx | dy << 16 each
 struct LbdPlanes { const uint32_t* base[LF_MAX_OCTAVES]; int W[LF_MAX_OCTAVES], H[LF_MAX_OCTAVES]; };

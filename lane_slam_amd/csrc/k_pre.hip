@@ -83,10 +83,13 @@ __device__ __forceinline__ uint32_t convert_pixel(uint32_t p24, const PreParams&
     return pk | ((uint32_t)bits << 24);
 }
 
+// kUndilated (LF_DETECTOR_DENSE only): the undilated colour masks go to bwbits as bit planes as well, in the layout of maskbits
+// (LineDetector2Dense's Sobel reads the mask before dilation).  The other instantiation never touches bwbits.
+template <bool kUndilated>
 __global__ __launch_bounds__(PRE_THREADS) void k_pre(PreParams p, const uint8_t* __restrict__ frames,
                                                       uint32_t* __restrict__ bgrx_out, uint8_t* __restrict__ gray_out,
                                                       uint32_t* __restrict__ maskbits, const int* __restrict__ sdiv_g,
-                                                      const int* __restrict__ hdiv_g)
+                                                      const int* __restrict__ hdiv_g, uint32_t* __restrict__ bwbits)
 {
     // LDS tile rows: [4 - r pad][r halo][TW interior, 16-byte aligned][r halo][pad]
     constexpr int tw = TW + 8, XO = 4;
@@ -189,6 +192,7 @@ __global__ __launch_bounds__(PRE_THREADS) void k_pre(PreParams p, const uint8_t*
         const bool valid = ly < TH && gx < p.W && gy < p.Hc;
         uint32_t px[4] = {0, 0, 0, 0};
         uint32_t nib[3] = {0, 0, 0};
+        uint32_t unib[3] = {0, 0, 0};
         if (valid) {
             const uint32_t* ctr = tile + (ly + r) * tw + XO + lx;
             const uint4 c4 = *reinterpret_cast<const uint4*>(ctr);
@@ -219,6 +223,13 @@ __global__ __launch_bounds__(PRE_THREADS) void k_pre(PreParams p, const uint8_t*
 #pragma unroll
             for (int c = 0; c < 3; ++c)
                 nib[c] = __builtin_amdgcn_udot4(t4 & (0x01010101u << c), 0x08040201u, 0u, false) >> c;
+            if constexpr (kUndilated) {
+                // the same gather on the four centre pixels: their own mask bits, before the OR of the structuring element
+                const uint32_t u4 = __builtin_amdgcn_perm(px[1], px[0], 0x0c0c0703u) | __builtin_amdgcn_perm(px[3], px[2], 0x07030c0cu);
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    unib[c] = __builtin_amdgcn_udot4(u4 & (0x01010101u << c), 0x08040201u, 0u, false) >> c;
+            }
         }
         // bit-plane copy of the dilated masks (1 bit / pixel): 8 lanes x 4 pixels = one 32-pixel word
 #pragma unroll
@@ -229,12 +240,28 @@ __global__ __launch_bounds__(PRE_THREADS) void k_pre(PreParams p, const uint8_t*
             w |= __shfl_xor(w, 4);
             nib[c] = w;
         }
+        if constexpr (kUndilated) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                uint32_t w = unib[c] << (4 * sub);
+                w |= __shfl_xor(w, 1);
+                w |= __shfl_xor(w, 2);
+                w |= __shfl_xor(w, 4);
+                unib[c] = w;
+            }
+        }
         if (!valid) continue;
         if (sub == 0) {
             uint32_t* mb = maskbits + ((size_t)f * 3 * p.Hc + gy) * Ww + (gx >> 5);
             mb[0] = nib[0];
             mb[(size_t)p.Hc * Ww] = nib[1];
             mb[(size_t)2 * p.Hc * Ww] = nib[2];
+            if constexpr (kUndilated) {
+                uint32_t* ub = bwbits + ((size_t)f * 3 * p.Hc + gy) * Ww + (gx >> 5);
+                ub[0] = unib[0];
+                ub[(size_t)p.Hc * Ww] = unib[1];
+                ub[(size_t)2 * p.Hc * Ww] = unib[2];
+            }
         }
         // corrected working image as BGRX dwords: one 16-byte store for the lane's 4 pixels
         const size_t pix = (size_t)gy * p.W + gx;
@@ -292,10 +319,13 @@ void launch_pre_gray(const PreParams& p, const uint8_t* frames, int n_frames, ui
 }
 
 void launch_pre(const PreParams& p, const uint8_t* frames, int n_frames, uint32_t* bgr, uint8_t* gray,
-                uint32_t* maskbits, const int* sdiv, const int* hdiv, hipStream_t s)
+                uint32_t* maskbits, const int* sdiv, const int* hdiv, hipStream_t s, uint32_t* bwbits)
 {
     dim3 grid((p.W + TW - 1) / TW, (p.Hc + TH - 1) / TH, n_frames);
-    hipLaunchKernelGGL(k_pre, grid, dim3(PRE_THREADS), 0, s, p, frames, bgr, gray, maskbits, sdiv, hdiv);
+    if (bwbits)
+        hipLaunchKernelGGL(k_pre<true>, grid, dim3(PRE_THREADS), 0, s, p, frames, bgr, gray, maskbits, sdiv, hdiv, bwbits);
+    else
+        hipLaunchKernelGGL(k_pre<false>, grid, dim3(PRE_THREADS), 0, s, p, frames, bgr, gray, maskbits, sdiv, hdiv, nullptr);
 }
 
 }  // namespace lf

@@ -100,11 +100,14 @@ __device__ void ground_point(const SegParams& p, double vx, double vy, double& g
     gy = g1 / g2;
 }
 
-// kIntLines: the lines are cv2.HoughLinesP's int32 ones (LF_DETECTOR_HOUGH, held exactly as floats in the slots) and a-5 is the
-// Hough plugin's arithmetic on them (line_detector1.py:80-119, the same statements as the LSD plugin's): the length is the
+// kMode SEG_HOUGH: the lines are cv2.HoughLinesP's int32 ones (LF_DETECTOR_HOUGH, held exactly as floats in the slots) and a-5
+// is the Hough plugin's arithmetic on them (line_detector1.py:80-119, the same statements as the LSD plugin's): the length is the
 // square root of an integer sum in f64, dx / dy are f64, the centres are Python 2's floor division of int sums, the ordering
-// test is int x f64.  The LSD / EDLines instantiation (false) is the float32 arithmetic of line_detector_lsd.py.
-template <bool kIntLines>
+// test is int x f64.  SEG_FLOAT (LSD / EDLines) is the float32 arithmetic of line_detector_lsd.py.
+// SEG_DENSE: LineDetector2Dense has no a-5 of its own (line_detector2.py:56-102): k_dense made the int lines, their float32
+// normals and pixels already; they are copied as they are, the normals widened exactly (signed zeros kept).  maskbits then
+// carries k_dense's per-slot (nx, ny, x, y) records instead of mask planes (one kernel signature for the three modes).
+template <int kMode>
 __global__ void k_segments(SegParams p, int n_frames, const float* __restrict__ slot_lines,
                            const int* __restrict__ counts, const int* __restrict__ seg_offset,
                            const uint32_t* __restrict__ maskbits, int Ww, lf_segments out, int* __restrict__ seg_frame,
@@ -121,7 +124,14 @@ __global__ void k_segments(SegParams p, int n_frames, const float* __restrict__ 
     const int f = pc / 3, col = pc - 3 * f;
     const float* L = slot_lines + ((size_t)pc * p.cap_lines + i) * 4;
     float x1 = L[0], y1 = L[1], x2 = L[2], y2 = L[3];
-    if constexpr (kIntLines) {
+    if constexpr (kMode == SEG_DENSE) {
+        const float4 r = reinterpret_cast<const float4*>(maskbits)[(size_t)pc * p.cap_lines + i];
+        if (out.lines) { float* o = out.lines + 4 * (size_t)idx; o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2; }
+        if (out.normals) { out.normals[2 * (size_t)idx] = r.x; out.normals[2 * (size_t)idx + 1] = r.y; }
+        if (out.color) out.color[idx] = (uint8_t)col;
+        if (normals64) { normals64[2 * (size_t)idx] = (double)r.x; normals64[2 * (size_t)idx + 1] = (double)r.y; }
+        if (centers) { centers[2 * (size_t)idx] = r.z; centers[2 * (size_t)idx + 1] = r.w; }
+    } else if constexpr (kMode == SEG_HOUGH) {
         int ix1 = (int)x1, iy1 = (int)y1, ix2 = (int)x2, iy2 = (int)y2;
         // a-5 on int32 lines: length = (int sum of squares) ** 0.5, dx = 1.*(y2-y1)/length, dy = 1.*(x1-x2)/length (f64)
         const int ex = ix1 - ix2, ey = iy1 - iy2;
@@ -200,16 +210,19 @@ __global__ void k_segments(SegParams p, int n_frames, const float* __restrict__ 
 }
 
 void launch_segments(const SegParams& p, int n_frames, const float* slot_lines, const int* counts,
-                     const int* seg_offset, const uint32_t* maskbits, int Ww, lf_segments out, int* seg_frame,
-                     double* normals64, float* centers, hipStream_t s, bool int_lines)
+                     const int* seg_offset, const uint32_t* side, int Ww, lf_segments out, int* seg_frame,
+                     double* normals64, float* centers, hipStream_t s, SegMode mode)
 {
     const int total = n_frames * 3 * p.cap_lines;
-    if (int_lines)
-        hipLaunchKernelGGL(k_segments<true>, dim3((total + 255) / 256), dim3(256), 0, s, p, n_frames, slot_lines, counts,
-                           seg_offset, maskbits, Ww, out, seg_frame, normals64, centers);
+    if (mode == SEG_DENSE)
+        hipLaunchKernelGGL(k_segments<SEG_DENSE>, dim3((total + 255) / 256), dim3(256), 0, s, p, n_frames, slot_lines, counts,
+                           seg_offset, side, Ww, out, seg_frame, normals64, centers);
+    else if (mode == SEG_HOUGH)
+        hipLaunchKernelGGL(k_segments<SEG_HOUGH>, dim3((total + 255) / 256), dim3(256), 0, s, p, n_frames, slot_lines, counts,
+                           seg_offset, side, Ww, out, seg_frame, normals64, centers);
     else
-        hipLaunchKernelGGL(k_segments<false>, dim3((total + 255) / 256), dim3(256), 0, s, p, n_frames, slot_lines, counts,
-                           seg_offset, maskbits, Ww, out, seg_frame, normals64, centers);
+        hipLaunchKernelGGL(k_segments<SEG_FLOAT>, dim3((total + 255) / 256), dim3(256), 0, s, p, n_frames, slot_lines, counts,
+                           seg_offset, side, Ww, out, seg_frame, normals64, centers);
 }
 
 }  // namespace lf

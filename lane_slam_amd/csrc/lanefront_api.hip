@@ -21,7 +21,7 @@ static const char* kStageNames[LF_N_STAGES] = {
     "pre(resize+correct+hsv+masks+dilate)", "canny_nms", "canny_hysteresis", "lsd_blur_resample_grad",
     "lsd_order", "lsd_grow", "segments(normal+project+sanity)", "lbd_gray_blur_sobel", "lbd_descriptor",
     "assoc_pack", "assoc_mfma", "misc", "jpeg(idct+upsample+color)", "lsd_label(components+launch order)",
-    "hough(probabilistic lines)" };
+    "hough(probabilistic lines)", "dense(sobel-vote lines)" };
 
 
 
@@ -492,6 +492,12 @@ extern "C" int lf_synchronize(lf_handle* h)
     return LF_OK;
 }
 
+// what lf_wait / lf_detect_lines call the handle's detector in their capacity messages
+static const char* detector_name(int detector)
+{
+    return detector == LF_DETECTOR_HOUGH ? "HoughLinesP" : (detector == LF_DETECTOR_DENSE ? "LineDetector2Dense" : "LSD");
+}
+
 // detect stages a-1..a-4 on device-resident frames
 int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_working_image)
 {
@@ -506,7 +512,13 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
         for (int i = 0; i < 3; ++i) { pp.ai_scale[i] = 1.f; pp.ai_shift[i] = 0.f; }
         pp.identity_ai = 1;
     }
-    { StageTimer t(h, ST_PRE); launch_pre(pp, d_frames, n, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s); }
+    const bool dense = h->detector == LF_DETECTOR_DENSE;
+    if (dense) {
+        int rc = dense_prepare(h);
+        if (rc != LF_OK) return rc;
+    }
+    // (LineDetector2Dense also reads the masks before dilation: k_pre's other instantiation writes them as well)
+    { StageTimer t(h, ST_PRE); launch_pre(pp, d_frames, n, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s, dense ? h->d_bwbits.p : nullptr); }
     { StageTimer t(h, ST_CANNY); launch_canny(h->canny, h->d_bgr, n, h->d_strong, h->d_weak, s); }
     {
         StageTimer t(h, ST_HYST);
@@ -526,12 +538,24 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
         launch_hough(hp, n * 3, h->hough_slots < n * 3 ? h->hough_slots : n * 3, h->d_strong, h->d_maskbits, h->d_hough_tab, h->d_hough_acc,
                      h->d_hough_nz, h->d_slot_lines, h->d_counts, s);
         LF_HIP_CHECK(h, hipGetLastError());
-        h->slots_int = true;
+        h->slot_mode = SEG_HOUGH;
         h->last_frames = n;
         h->overflow_zeroed = true;
         return LF_OK;
     }
-    h->slots_int = false;
+    if (dense) {
+        // LineDetector2Dense: a line per edge pixel with a steep undilated mask in place of the LSD stages (k_dense.hip)
+        StageTimer t(h, ST_DENSE);
+        LF_HIP_CHECK(h, hipMemsetAsync(h->d_zero, 0, h->zero_bytes, s));           // every counter of the batch (see d_zero)
+        launch_dense(h->Hc, h->W, h->Ww, h->cap_lines, (float)h->dense_params.sobel_threshold, n * 3, h->d_strong, h->d_maskbits,
+                     h->d_bwbits, h->d_slot_lines, h->d_dense_rec, h->d_counts, s);
+        LF_HIP_CHECK(h, hipGetLastError());
+        h->slot_mode = SEG_DENSE;
+        h->last_frames = n;
+        h->overflow_zeroed = true;
+        return LF_OK;
+    }
+    h->slot_mode = SEG_FLOAT;
     {
         StageTimer t(h, ST_LSD_GRAD);
         LF_HIP_CHECK(h, hipMemsetAsync(h->d_zero, 0, h->zero_bytes, s));           // every counter of the batch (see d_zero)
@@ -579,9 +603,10 @@ int lf::run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe)
         if (!h->overflow_zeroed) LF_HIP_CHECK(h, hipMemsetAsync(h->d_overflow, 0, 4 * sizeof(int), s));
         h->overflow_zeroed = false;
         launch_seg_offsets(n, h->cap_lines, h->d_counts, h->d_seg_offset, dev_out.frame_offset ? dev_out.frame_offset : h->d_frame_offset,
-                           h->d_overflow, h->slots_int ? nullptr : h->d_norder, lsd_grow_def_lds(h->lsd, kGrowLdsKb[0]), lsd_grow_def_lds(h->lsd, kGrowLdsKb[1]), s);
-        launch_segments(h->seg, n, h->d_slot_lines, h->d_counts, h->d_seg_offset, h->d_maskbits, h->Ww, dev_out, h->d_seg_frame,
-                        h->d_normals64, h->d_centers, s, h->slots_int);
+                           h->d_overflow, h->slot_mode != SEG_FLOAT ? nullptr : h->d_norder, lsd_grow_def_lds(h->lsd, kGrowLdsKb[0]), lsd_grow_def_lds(h->lsd, kGrowLdsKb[1]), s);
+        launch_segments(h->seg, n, h->d_slot_lines, h->d_counts, h->d_seg_offset,
+                        h->slot_mode == SEG_DENSE ? reinterpret_cast<const uint32_t*>(h->d_dense_rec.p) : h->d_maskbits.p, h->Ww, dev_out,
+                        h->d_seg_frame, h->d_normals64, h->d_centers, s, h->slot_mode);
     }
     if (describe) {
         { StageTimer t(h, ST_LBD_GRAD); launch_lbd_grad(h->Hc, h->W, n, h->d_gray, h->d_dxy, s); }
@@ -696,7 +721,7 @@ extern "C" int lf_wait(lf_handle* h, int* n_segments)
         h->grow_lds_level = over_medium * 4 > np ? 2 : (over_small * 20 > np ? 1 : 0);
         h->grow_mixed = (h->grow_lds_level == 0 ? over_small : over_medium) * 100 > np;
     }
-    if (h->h_pinned[1]) { lf_set_error(h, LF_ERR_CAPACITY, "an %s run produced more than max_lines_per_color=%d lines", h->detector == LF_DETECTOR_HOUGH ? "HoughLinesP" : "LSD", h->cap_lines); return LF_ERR_CAPACITY; }
+    if (h->h_pinned[1]) { lf_set_error(h, LF_ERR_CAPACITY, "%s %s run produced more than max_lines_per_color=%d lines", h->detector == LF_DETECTOR_DENSE ? "a" : "an", detector_name(h->detector), h->cap_lines); return LF_ERR_CAPACITY; }
     if (total > h->pending_capacity) { lf_set_error(h, LF_ERR_CAPACITY, "%d segments exceed the output capacity %d", total, h->pending_capacity); return LF_ERR_CAPACITY; }
     return LF_OK;
 }
@@ -793,9 +818,9 @@ extern "C" int lf_set_image(lf_handle* h, const uint8_t* bgr, int rows, int cols
     rc = run_segments(h, 1, dev, false);
     if (rc != LF_OK) return rc;
     // Detections.area = the dilated colour mask as 0/255 bytes (line_detector_lsd.py:127-133): expanded once for the
-    // three colours from the bit planes
+    // three colours from the bit planes.  LineDetector2Dense returns the undilated mask (line_detector2.py:104-107).
     if ((rc = ensure(h, h->dbg_masks, 3 * h->P)) != LF_OK) return rc;
-    launch_edges_u8(h->canny, 3, h->d_maskbits, (uint8_t*)h->dbg_masks.p, s);
+    launch_edges_u8(h->canny, 3, h->detector == LF_DETECTOR_DENSE ? h->d_bwbits.p : h->d_maskbits.p, (uint8_t*)h->dbg_masks.p, s);
     h->h_counts.resize(3); h->h_seg_offset.resize(4);
     if ((rc = plugin_fetch_results(h)) != LF_OK) return rc;
     LF_HIP_CHECK(h, hipMemcpyAsync(h->h_counts.data(), h->d_counts, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -821,7 +846,7 @@ extern "C" int lf_detect_lines(lf_handle* h, int color, float* lines4, double* n
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     int n = h->h_counts[color];
-    if (n > h->cap_lines) { lf_set_error(h, LF_ERR_CAPACITY, "LSD found %d lines, max_lines_per_color is %d", n, h->cap_lines); return LF_ERR_CAPACITY; }
+    if (n > h->cap_lines) { lf_set_error(h, LF_ERR_CAPACITY, "%s found %d lines, max_lines_per_color is %d", detector_name(h->detector), n, h->cap_lines); return LF_ERR_CAPACITY; }
     if (n > cap) { lf_set_error(h, LF_ERR_CAPACITY, "%d lines exceed caller capacity %d", n, cap); return LF_ERR_CAPACITY; }
     const size_t off = (size_t)h->h_seg_offset[color];
     if (h->plug_host && off + (size_t)n <= (size_t)h->plug_eager) {

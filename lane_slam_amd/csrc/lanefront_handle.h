@@ -186,7 +186,10 @@ struct lf_handle {
     lf::DevArray<uint32_t> d_hough_nz;           // the points of problems that do not fit LDS, one list per resident workgroup
     lf::HoughParams hough_p{};
     int hough_slots = 0;
-    bool slots_int = false;               // the slot lines of the last detect are HoughLinesP's ints (k_segments' integer a-5)
+    lf_dense_params dense_params = { 40.0 };   // LF_DETECTOR_DENSE (lf_set_dense_params)
+    lf::DevArray<uint32_t> d_bwbits;             // the UNDILATED colour masks as bit planes, [frame][colour][Hc][Ww] (k_pre<true>)
+    lf::DevArray<float> d_dense_rec;             // per slot (nx, ny, x, y) of the dense lines, [frame][colour][cap_lines] (k_dense)
+    lf::SegMode slot_mode = lf::SEG_FLOAT;      // what the slots of the last detect hold: which a-5 k_segments applies
     int tie_rule = LF_TIE_MIHASHER;   // lf_associate: the reference's rule unless lf_set_tie_rule says otherwise
     int env_lds_level = -1;      // LF_GROW_LDS_LEVEL / LF_GROW_MIXED: test and tuning overrides, read when the handle is created, clamped
     int env_mixed = -1;
@@ -261,6 +264,8 @@ int plugin_stage_image(lf_handle* h, const uint8_t* bgr, int rows, int cols, int
 int plugin_fetch_results(lf_handle* h);
 // lanefront_hough.hip
 int hough_prepare(lf_handle* h);
+// lanefront_dense.hip
+int dense_prepare(lf_handle* h);
 // lanefront_keylines.hip
 int run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n);
 void keylines_pending_result(lf_handle* h, int* total, int* overflow);

@@ -582,7 +582,7 @@ int lf::run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n)
     EdAll all;
     if ((rc = kl_run_octaves(h, h->d_gray, n, 1, P, all)) != LF_OK) return rc;
     LF_HIP_CHECK(h, hipMemsetAsync(h->d_norder, 0, (size_t)n * 3 * sizeof(int), s));        // (LSD's slice statistics: nothing to learn from this batch)
-    h->slots_int = false;
+    h->slot_mode = SEG_FLOAT;
     LF_HIP_CHECK(h, hipMemsetAsync(h->d_overflow + 4, 0, sizeof(int), s));
     {
         StageTimer t(h, ST_SEGMENTS);
@@ -596,7 +596,7 @@ int lf::run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n)
 extern "C" int lf_set_detector(lf_handle* h, int detector, const lf_edlines_params* params_or_null)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
-    if (detector != LF_DETECTOR_LSD && detector != LF_DETECTOR_EDLINES && detector != LF_DETECTOR_HOUGH) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_detector: unknown detector %d", detector); return LF_ERR_BAD_ARG; }
+    if (detector != LF_DETECTOR_LSD && detector != LF_DETECTOR_EDLINES && detector != LF_DETECTOR_HOUGH && detector != LF_DETECTOR_DENSE) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_detector: unknown detector %d", detector); return LF_ERR_BAD_ARG; }
     if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
     lf_edlines_params P;
     lf_edlines_default_params(&P);
@@ -611,6 +611,10 @@ extern "C" int lf_set_detector(lf_handle* h, int detector, const lf_edlines_para
     if (detector == LF_DETECTOR_HOUGH) {
         int rc;
         if ((rc = hough_prepare(h)) != LF_OK) return rc;                   // the tables and scratch now; an unsupported geometry fails here
+    }
+    if (detector == LF_DETECTOR_DENSE) {
+        int rc;
+        if ((rc = dense_prepare(h)) != LF_OK) return rc;                   // the undilated planes and the slot records now
     }
     h->detector = detector;
     return LF_OK;
@@ -660,7 +664,7 @@ extern "C" int lf_set_image_edlines(lf_handle* h, const uint8_t* bgr, int rows, 
     if ((rc = kl_run_octaves(h, h->d_gray, 1, 1, P, all)) != LF_OK) return rc;
     launch_ed_slots(all, 1, h->d_maskbits, h->Ww, h->cap_lines, h->d_slot_lines, h->d_counts, nullptr, s);
     h->last_frames = 1;
-    h->slots_int = false;
+    h->slot_mode = SEG_FLOAT;
     lf_segments dev = h->d_out;
     dev.desc = nullptr; dev.code = nullptr;
     if ((rc = run_segments(h, 1, dev, false)) != LF_OK) return rc;

@@ -172,12 +172,20 @@ class FrontEnd(object):
 
     def set_detector(self, detector, params=None):
         """Which detector process_batch / submit_* run: "lsd" (the reference's, default), "edlines" (EDLines on the gray
-        working image + the colour masks: include/lanefront.h, lf_set_detector) or "hough" (LineDetectorHSV's
-        cv2.HoughLinesP on the colour's edge map).  params: for "edlines" edlines_params(...) or None; for "hough" a mapping
+        working image + the colour masks: include/lanefront.h, lf_set_detector), "hough" (LineDetectorHSV's
+        cv2.HoughLinesP on the colour's edge map) or "dense" (LineDetector2Dense: a line per edge pixel where the undilated
+        mask's Sobel gradient is steep).  params: for "edlines" edlines_params(...) or None; for "hough" a mapping
         with the three configuration keys hough_threshold, hough_min_line_length and hough_max_line_gap (a whole
-        13-key detector configuration will do), which it requires."""
+        13-key detector configuration will do), which it requires; for "dense" a mapping with the key sobel_threshold
+        (a whole 11-key LineDetector2Dense configuration will do), which it requires."""
         if detector not in _lib.DETECTORS:
             raise ValueError("detector must be one of %r" % (sorted(_lib.DETECTORS),))
+        if detector == "dense":
+            if params is None or any(k not in params for k in _lib.DENSE_KEYS):
+                raise ValueError("the dense detector takes its parameters: a mapping with %r" % (_lib.DENSE_KEYS,))
+            self._check(self.lib.lf_set_dense_params(self.h, ctypes.byref(self.dense_params(params["sobel_threshold"]))))
+            self._check(self.lib.lf_set_detector(self.h, _lib.DETECTORS[detector], None))
+            return
         if detector == "hough":
             if params is None or any(k not in params for k in _lib.HOUGH_KEYS):
                 raise ValueError("the hough detector takes its parameters: a mapping with %r" % (_lib.HOUGH_KEYS,))
@@ -202,6 +210,20 @@ class FrontEnd(object):
         p = _lib.LfHoughParams()
         self._check(self.lib.lf_get_hough_params(self.h, ctypes.byref(p)))
         return int(p.threshold), int(p.min_line_length), int(p.max_line_gap)
+
+    def dense_params(self, sobel_threshold=None):
+        """lf_dense_params: the reference's default_ld2.yaml value (sobel_threshold 40), optionally overridden."""
+        p = _lib.LfDenseParams()
+        self.lib.lf_dense_default_params(ctypes.byref(p))
+        if sobel_threshold is not None:
+            p.sobel_threshold = float(sobel_threshold)
+        return p
+
+    def get_dense_params(self):
+        """The sobel_threshold the handle's dense detector uses."""
+        p = _lib.LfDenseParams()
+        self._check(self.lib.lf_get_dense_params(self.h, ctypes.byref(p)))
+        return float(p.sobel_threshold)
 
     def detector_failures(self):
         """Frames of the last completed batch on which the EDLines detector gave up (they have no segments)."""

@@ -19,7 +19,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from .config import DETECTOR_KEYS, default_config
+from .config import DEFAULT_DETECTOR_CONFIGURATION, DETECTOR_KEYS, default_config
 from .frontend import FrontEnd
 
 Detections = namedtuple("Detections", ["lines", "normals", "area", "centers"])   # line_detector_interface.py:6-7
@@ -177,3 +177,59 @@ class LineDetectorHSV(LineDetectorHIP):
         if len(d.lines) == 0:
             return d
         return Detections(lines=d.lines.astype(np.int32), normals=d.normals, area=d.area, centers=d.centers.astype(np.int32))
+
+
+# LineDetector2Dense's configuration keys (line_detector2.py:15-29)
+DENSE_DETECTOR_KEYS = ("hsv_white1", "hsv_white2", "hsv_yellow1", "hsv_yellow2", "hsv_red1", "hsv_red2", "hsv_red3", "hsv_red4",
+                       "dilation_kernel_size", "canny_thresholds", "sobel_threshold")
+
+
+class LineDetector2Dense(LineDetectorHIP):
+    """Drop-in for the reference's third LineDetectorInterface plugin, line_detector.LineDetector2Dense
+    (the reference's src/line_detector/include/line_detector/line_detector2.py:8-119, selected by default_ld2.yaml): every
+    pixel of the colour's edge map whose 5x5 Sobel gradient of the undilated mask is above sobel_threshold becomes a
+    12-pixel line across that gradient (the detector LF_DETECTOR_DENSE of include/lanefront.h, on the GPU).  The
+    constructor takes exactly the 11 configuration keys of line_detector2.py:15-29 (ValueError on extra or missing ones).
+    detectLines(color) returns Detections with int64 `lines` (N, 4), float32 `normals` (N, 2), int64 `centers` (N, 2) --
+    the pixels, in raster order -- and `area`, the UNDILATED colour mask; with no line, `lines` is [] and `normals` and
+    `centers` are empty (0, 2) arrays, as the reference's.
+
+        detector:
+          - lane_slam_amd.LineDetector2Dense
+          - configuration: { ...the 11 keys of default_ld2.yaml... }
+
+    A line per qualifying edge pixel makes many more lines than LSD: up to 436 in a colour of the 28 camera frames at the
+    node's 160 x 80 working image, 3 256 at 640 x 320, hence a larger default max_lines_per_color than the
+    other plugins'.  A colour beyond it is LanefrontError (LF_ERR_CAPACITY)."""
+
+    def __init__(self, configuration, device=0, max_lines_per_color=8192):
+        if not isinstance(configuration, dict):
+            raise ValueError("Expecting a dict, obtained %r" % (configuration,))
+        extra = set(configuration) - set(DENSE_DETECTOR_KEYS)
+        missing = set(DENSE_DETECTOR_KEYS) - set(configuration)
+        if extra or missing:
+            raise ValueError("Error while loading configuration for %r from %r.\nExtra parameters: %r\n"
+                             "Missing parameters: %r\n" % (self, configuration, extra, missing))
+        dense = copy.deepcopy(configuration)
+        # the front end's configuration carries the LSD plugin's 13 keys: the three hough_* ones are not read by this detector
+        full = {k: v for k, v in dense.items() if k in DETECTOR_KEYS}
+        for k in DETECTOR_KEYS:
+            if k not in full:
+                full[k] = copy.deepcopy(DEFAULT_DETECTOR_CONFIGURATION[k])
+        LineDetectorHIP.__init__(self, full, device=device, max_lines_per_color=max_lines_per_color)
+        self.sobel_threshold = dense["sobel_threshold"]
+        self._dense = dense
+
+    def _frontend(self, rows, cols):
+        fresh = self._fe is None or self._shape != (rows, cols)
+        fe = LineDetectorHIP._frontend(self, rows, cols)
+        if fresh:
+            fe.set_detector("dense", self._dense)
+        return fe
+
+    def detectLines(self, color):
+        d = LineDetectorHIP.detectLines(self, color)
+        if len(d.lines) == 0:
+            return Detections(lines=[], normals=np.zeros((0, 2), np.float32), area=d.area, centers=np.zeros((0, 2), np.int64))
+        return Detections(lines=d.lines.astype(np.int64), normals=d.normals.astype(np.float32), area=d.area,
+                          centers=d.centers.astype(np.int64))
