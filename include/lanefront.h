@@ -588,8 +588,8 @@ LF_API int lf_keylines_frame_status(lf_handle* h, int32_t* frame_status, int n_f
  * one KeyLine per line (checkLineExtremes, start / end points scaled back to level 0, lineLength, numOfPixels = LineIterator's
  * count, angle, size, response, pt; class_id counts through the octaves of a frame; no mask) -- and with describe != 0
  * BinaryDescriptor::compute on those KeyLines (lf_describe_keylines).  Same lf_keylines block as lf_keylines_batch (salience is 0:
- * not a KeyLine field); same input kinds.  Synchronous.  Every level runs the front end's LSD kernels on a GRAY image through a
- * sub-handle of the level's geometry: dense problems, one wave per connected component -- a completeness path (detect -> compute
+ * not a KeyLine field); same input kinds.  Synchronous.  Every level runs the front end's LSD kernels on a GRAY image with LSD
+ * state of the level's geometry: dense problems, one wave per connected component -- a completeness path (detect -> compute
  * for both detectors of the library), not a fast one.  LF_ERR_CAPACITY: more KeyLines than out->capacity, or a level with more
  * lines than max_lines_per_color. */
 LF_API int lf_lsd_keylines_batch(lf_handle* h, const uint8_t* images, int n_frames, int input_kind, int images_on_device, int n_octaves,

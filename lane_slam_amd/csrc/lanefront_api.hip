@@ -13,7 +13,6 @@
 #include <cstdlib>
 #include <functional>
 #include "lanefront_handle.h"
-#include "lsd_bitplane.h"
 
 using namespace lf;
 
@@ -56,8 +55,6 @@ void lf::timing_resolve(lf_handle* h)
 
 static int cv_round_host(double v) { return dm::round_half_even(v); }
 
-thread_local bool lf::g_lsd_only_create = false;      // set around the lf_create of an LSD-only sub-handle (lanefront_lsdkl.hip)
-
 
 static int build_params(lf_handle* h)
 {
@@ -69,9 +66,8 @@ static int build_params(lf_handle* h)
                      c.img_cols, c.top_cutoff);
         return LF_ERR_BAD_ARG;
     }
-    // (the bit planes of the front end are whole 32-bit words per row; a sub-handle that only runs the LSD stages on gray pyramid
-    // levels -- lanefront_lsdkl.hip -- never touches them)
-    if (h->W % 32 != 0 && !g_lsd_only_create) { lf_set_error(h, LF_ERR_UNSUPPORTED, "img_cols must be a multiple of 32 (got %d)", h->W); return LF_ERR_UNSUPPORTED; }
+    // (the bit planes of the front end are whole 32-bit words per row)
+    if (h->W % 32 != 0) { lf_set_error(h, LF_ERR_UNSUPPORTED, "img_cols must be a multiple of 32 (got %d)", h->W); return LF_ERR_UNSUPPORTED; }
     h->P = (size_t)h->Hc * h->W;
     h->Ww = (h->W + 31) / 32;
     // ---- pre
@@ -108,62 +104,9 @@ static int build_params(lf_handle* h)
     double lo = c.canny_lo, hi = c.canny_hi;
     if (lo > hi) { double t = lo; lo = hi; hi = t; }
     h->canny.low = dm::ifloor(lo); h->canny.high = dm::ifloor(hi);
-    // ---- LSD
-    LsdParams& L = h->lsd;
-    memset(&L, 0, sizeof(L));
-    L.Hc = h->Hc; L.W = h->W; L.Ww = h->Ww;
-    L.scaled = c.lsd_scale != 1.0;
-    L.scale = c.lsd_scale;
-    if (c.lsd_scale <= 0 || c.lsd_scale > 1.0) { lf_set_error(h, LF_ERR_UNSUPPORTED, "lsd_scale must be in (0,1]"); return LF_ERR_UNSUPPORTED; }
-    if (L.scaled) { L.Ws = cv_round_host(h->W * c.lsd_scale); L.Hs = cv_round_host(h->Hc * c.lsd_scale); }
-    else { L.Ws = h->W; L.Hs = h->Hc; }
-    h->Hs = L.Hs; h->Ws = L.Ws; h->Ps = (size_t)L.Hs * L.Ws;
-    if (h->Ps >= (1u << 20) || L.Ws > 65535 || L.Hs > 65535) { lf_set_error(h, LF_ERR_UNSUPPORTED, "scaled LSD image too large"); return LF_ERR_UNSUPPORTED; }
-    // LDS limits of the two LDS-resident stages, checked once here so that an unsupported geometry fails at
-    // lf_create instead of as a launch error later: region growing keeps the row-start table of its problem in
-    // LDS (k_lsd_grow.hip), canny hysteresis sweeps strips of >= 1 row + 2 halo rows (k_canny.hip)
-    if ((size_t)((L.Hs + 2) & ~1) * 4 + 512 * 4 + 1024 > 64 * 1024) { lf_set_error(h, LF_ERR_UNSUPPORTED, "scaled LSD image has %d rows: the row table exceeds the LDS of one problem", L.Hs); return LF_ERR_UNSUPPORTED; }
+    // LDS limit of hysteresis, checked once here so that an unsupported geometry fails at lf_create instead of as a launch error
+    // later: it sweeps strips of >= 1 row + 2 halo rows (k_canny.hip).  (The LSD stages check theirs in LsdState::init.)
     if ((size_t)h->Hc * h->Ww > 8 * 1024 && (8192 / h->Ww < 1 || (int)((60 * 1024 / 4) / (2 * (size_t)h->Ww)) - 1 < 1)) { lf_set_error(h, LF_ERR_UNSUPPORTED, "img_cols %d: one row of the edge bit planes exceeds the hysteresis strip budget", h->W); return LF_ERR_UNSUPPORTED; }
-    if (c.lsd_n_bins < 2 || c.lsd_n_bins > 4096) { lf_set_error(h, LF_ERR_UNSUPPORTED, "lsd_n_bins must be in [2,4096] (a seed is its bin above a 20-bit pixel index in one word)"); return LF_ERR_UNSUPPORTED; }
-    if (L.scaled) {
-        const double sigma = (c.lsd_scale < 1) ? (c.lsd_sigma_scale / c.lsd_scale) : c.lsd_sigma_scale;
-        const double sprec = 3;
-        const unsigned hh = (unsigned)ceil(sigma * sqrt(2 * sprec * dm::dlog(10.0)));
-        const int n = 1 + 2 * (int)hh;
-        if (n > kMaxGaussTaps) { lf_set_error(h, LF_ERR_UNSUPPORTED, "LSD Gaussian needs %d taps (max %d)", n, kMaxGaussTaps); return LF_ERR_UNSUPPORTED; }
-        const double scale2X = -0.5 / (sigma * sigma);
-        double sum = 0;
-        for (int i = 0; i < n; ++i) { double x = i - (n - 1) * 0.5; double t = dm::dexp(scale2X * x * x); L.k[i] = t; sum += t; }
-        sum = 1.0 / sum;
-        for (int i = 0; i < n; ++i) L.k[i] *= sum;
-        L.ntaps = n; L.half = n / 2;
-    } else { L.ntaps = 1; L.half = 0; L.k[0] = 1.0; }
-    L.prec = 3.14159265358979323846 * c.lsd_ang_th / 180;
-    L.p = c.lsd_ang_th / 180;
-    L.rho = c.lsd_quant / dm::dsin(L.prec);
-    L.log_nt = 5 * (dm::dlog10((double)L.Ws) + dm::dlog10((double)L.Hs)) / 2 + dm::dlog10(11.0);
-    L.min_reg_size = (int)(-L.log_nt / dm::dlog10(L.p));
-    L.log_eps = c.lsd_log_eps; L.density_th = c.lsd_density_th;
-    L.n_bins = c.lsd_n_bins; L.refine = c.lsd_refine; L.cap_lines = h->cap_lines;
-    if (c.lsd_seed_order != LF_LSD_SEED_OPENCV30 && c.lsd_seed_order != LF_LSD_SEED_OPENCV32) { lf_set_error(h, LF_ERR_BAD_ARG, "lsd_seed_order %d: LF_LSD_SEED_OPENCV30 or LF_LSD_SEED_OPENCV32", c.lsd_seed_order); return LF_ERR_BAD_ARG; }
-    if (c.lsd_seed_order == LF_LSD_SEED_OPENCV32 && !lsd_seed32_supported(L)) { lf_set_error(h, LF_ERR_UNSUPPORTED, "lsd_seed_order OPENCV32: the %dx%d LSD image exceeds the row tables of the sort emulation, or (n_bins - 1) * quant / sin(ang_th) < 361 (k_lsd_seed32.hip)", L.Ws, L.Hs); return LF_ERR_UNSUPPORTED; }
-    // component labelling (k_lsd_label): problems of up to label_lds = 6144 defined pixels in LDS (24 KB per workgroup: what one
-    // workgroup of k_lsd_grow gives back when it leaves a CU), the larger ones in the problem's region scratch, up to label_items
-    // -- a third of the scaled image (every growing wave has a region list of that size in the scratch) and below 2^16 (the
-    // labels are u16).  Rounds 2 - 3 had every problem's tables in LDS, 48 KB per workgroup growing with the workload to 144 KB.
-    L.label_lds = kLabelLds;
-    {
-        // images whose bit plane is larger than that anyway (1080p: 124 KB, one workgroup per CU): the LDS form for every problem
-        // that fits the same request
-        const size_t plane = bitplane_lds_words(h->Ps) * 4;
-        if (plane <= 150 * 1024 && plane / 4 > (size_t)L.label_lds) L.label_lds = (int)((plane / 4 < 65534 ? plane / 4 : 65534) & ~(size_t)1);
-    }
-    L.label_items = (int)(h->Ps / 3 / 1024) * 1024;
-    if (L.label_items > 64512) L.label_items = 64512;
-    if (L.label_items < kLabelItems) L.label_items = kLabelItems;
-    L.label_items_max = L.label_items;
-    h->label_items_full = L.label_items;
-    L.rec_cap = (int)h->Ps;                               // (alloc_buffers chooses the batch handles' starting capacity)
     // ---- segments
     SegParams& S = h->seg;
     memset(&S, 0, sizeof(S));
@@ -213,71 +156,6 @@ static int upload_tables(lf_handle* h)
     if (dalloc(h, &h->d_sdiv, 256) || dalloc(h, &h->d_hdiv, 256)) return LF_ERR_HIP;
     LF_HIP_CHECK(h, hipMemcpy(h->d_sdiv, sdiv.data(), 256 * sizeof(int), hipMemcpyHostToDevice));
     LF_HIP_CHECK(h, hipMemcpy(h->d_hdiv, hdiv.data(), 256 * sizeof(int), hipMemcpyHostToDevice));
-    // LSD resize tables (cv::resize INTER_LINEAR, CV_64F)
-    const LsdParams& L = h->lsd;
-    const int Ws = L.Ws, Hs = L.Hs, W = h->W, Hc = h->Hc;
-    std::vector<int> xofs(Ws), y0(Hs), y1(Hs);
-    std::vector<float> xa(2 * (size_t)Ws), yb(2 * (size_t)Hs);
-    int xmax = Ws;
-    const double scale_x = 1.0 / L.scale, scale_y = 1.0 / L.scale;
-    for (int dx = 0; dx < Ws; ++dx) {
-        float fx; int sx;
-        if (L.scaled) {
-            fx = (float)((dx + 0.5) * scale_x - 0.5);
-            sx = dm::ifloor((double)fx);
-            fx -= sx;
-        } else { fx = 0.f; sx = dx; }
-        if (sx < 0) { fx = 0; sx = 0; }
-        if (sx + 1 >= W) {
-            if (dx < xmax) xmax = dx;
-            if (sx >= W - 1) { fx = 0; sx = W - 1; }
-        }
-        xofs[dx] = sx; xa[2 * dx] = 1.f - fx; xa[2 * dx + 1] = fx;
-    }
-    for (int dy = 0; dy < Hs; ++dy) {
-        float fy; int sy;
-        if (L.scaled) {
-            fy = (float)((dy + 0.5) * scale_y - 0.5);
-            sy = dm::ifloor((double)fy);
-            fy -= sy;
-        } else { fy = 0.f; sy = dy; }
-        yb[2 * dy] = 1.f - fy; yb[2 * dy + 1] = fy;
-        y0[dy] = sy < 0 ? 0 : (sy > Hc - 1 ? Hc - 1 : sy);
-        y1[dy] = sy + 1 < 0 ? 0 : (sy + 1 > Hc - 1 ? Hc - 1 : sy + 1);
-    }
-    // LDS footprint of the worst tile
-    const int GT = 32;
-    int mx = 0, my = 0;
-    for (int X0 = 0; X0 < Ws; X0 += GT) {
-        int X1 = X0 + GT < Ws - 1 ? X0 + GT : Ws - 1;
-        int lo = xofs[X0], hi = xofs[X1] + 1 < W - 1 ? xofs[X1] + 1 : W - 1;
-        if (hi - lo + 1 > mx) mx = hi - lo + 1;
-    }
-    for (int Y0 = 0; Y0 < Hs; Y0 += GT) {
-        int Y1 = Y0 + GT < Hs - 1 ? Y0 + GT : Hs - 1;
-        int lo = y0[Y0], hi = y1[Y1];
-        if (hi - lo + 1 > my) my = hi - lo + 1;
-    }
-    h->max_nsx = mx; h->max_nsy = my;
-    {
-        const int hh = L.half;
-        // same carve as launch_lsd_grad: F|Hb|pixel list share one region, Bl|Sc the other
-        const size_t szF = (size_t)(my + 2 * hh) * mx, szBl = (size_t)my * mx;
-        const size_t szHb = (size_t)my * (GT + 1), szSc = (size_t)(GT + 1) * (GT + 1);
-        size_t regA = szF > szHb ? szF : szHb;
-        if (regA < (size_t)2 * GT * GT) regA = (size_t)2 * GT * GT;
-        const size_t regB = szBl > szSc ? szBl : szSc;
-        size_t lds = sizeof(double) * (regA + regB);
-        if (lds > 64 * 1024) { lf_set_error(h, LF_ERR_UNSUPPORTED, "lsd_scale %.3f needs %zu B of LDS per tile (max 65536)", L.scale, lds); return LF_ERR_UNSUPPORTED; }
-    }
-    if (dalloc(h, &h->d_xofs, Ws) || dalloc(h, &h->d_y0, Hs) || dalloc(h, &h->d_y1, Hs) || dalloc(h, &h->d_xa, 2 * (size_t)Ws) ||
-        dalloc(h, &h->d_yb, 2 * (size_t)Hs)) return LF_ERR_HIP;
-    LF_HIP_CHECK(h, hipMemcpy(h->d_xofs, xofs.data(), Ws * sizeof(int), hipMemcpyHostToDevice));
-    LF_HIP_CHECK(h, hipMemcpy(h->d_y0, y0.data(), Hs * sizeof(int), hipMemcpyHostToDevice));
-    LF_HIP_CHECK(h, hipMemcpy(h->d_y1, y1.data(), Hs * sizeof(int), hipMemcpyHostToDevice));
-    LF_HIP_CHECK(h, hipMemcpy(h->d_xa, xa.data(), 2 * (size_t)Ws * sizeof(float), hipMemcpyHostToDevice));
-    LF_HIP_CHECK(h, hipMemcpy(h->d_yb, yb.data(), 2 * (size_t)Hs * sizeof(float), hipMemcpyHostToDevice));
-    h->rt.xofs = h->d_xofs; h->rt.xa = h->d_xa; h->rt.y0 = h->d_y0; h->rt.y1 = h->d_y1; h->rt.yb = h->d_yb; h->rt.xmax = xmax;
     const int mw = lbd_max_width_of_band();
     if (dalloc(h, &h->d_gauss_g, 9 * (size_t)mw) || dalloc(h, &h->d_gauss_l, 3 * (size_t)mw)) return LF_ERR_HIP;
     return lbd_weights(h, h->desc_params.width_of_band);
@@ -319,43 +197,31 @@ extern "C" int lf_set_descriptor_params(lf_handle* h, const lf_descriptor_params
     return LF_OK;
 }
 
-// the arrays whose stride is LsdParams::rec_cap: records, sort scratch, seed lists, compact arrays, labels, the region scratch, low records
-static void free_lsd_lists(lf_handle* h)
+// The front end's LSD state: the configuration's options, and per-problem lists.  A batch handle starts with an eighth of the LSD
+// image per problem (a lane frame's colour has 3 - 6 % of its pixels defined, a camera frame's 10 - 20 %) and grows when a batch
+// needs more (LsdState::grow_lists); handles of a few frames hold whole images.  LF_LSD_RECORDS=<entries> | full overrides.
+static int init_lsd(lf_handle* h)
 {
-    for (auto* b : { &h->d_raddr, &h->d_order_a, &h->d_order_b, &h->d_cxy, &h->d_reg, &h->d_laddr }) b->reset();
-    for (auto* b : { &h->d_rdeg, &h->d_cdeg, &h->d_rsd, &h->d_csd }) b->reset();
-    for (auto* b : { &h->d_rmod, &h->d_rcs, &h->d_rsn, &h->d_cmod, &h->d_ccs, &h->d_lmod }) b->reset();
-    h->d_sort_a.reset(); h->d_sort_b.reset(); h->d_clabel.reset();
-    h->lsd.r_sd = nullptr; h->lsd.c_sd = nullptr; h->d_csn = nullptr;
-}
-
-static int alloc_lsd_lists(lf_handle* h, int rec_cap)
-{
-    const size_t nprob = (size_t)h->max_frames * 3, S = (size_t)rec_cap;
-    LsdParams& L = h->lsd;
-    L.rec_cap = rec_cap;
-    // (components are only kept apart for problems of up to label_items defined pixels; no problem has more than rec_cap)
-    // (... but not below kLabelItems: the labelling kernel's LDS form and the growing waves' scratch slices are laid out for that)
-    const int li = rec_cap > kLabelItems ? rec_cap : kLabelItems;
-    L.label_items = h->label_items_full < li ? h->label_items_full : li;
-    L.label_items_max = L.label_items;
-    if (dalloc(h, &h->d_raddr, nprob * S) || dalloc(h, &h->d_rdeg, nprob * S) || dalloc(h, &h->d_rmod, nprob * S) ||
-        dalloc(h, &h->d_rcs, nprob * S) || dalloc(h, &h->d_rsn, nprob * S) || dalloc(h, &h->d_sort_a, nprob * S) || dalloc(h, &h->d_sort_b, nprob * S) ||
-        dalloc(h, &h->d_order_a, nprob * S) || dalloc(h, &h->d_order_b, nprob * S) || dalloc(h, &h->d_cxy, nprob * S) || dalloc(h, &h->d_cdeg, nprob * S) ||
-        dalloc(h, &h->d_cmod, nprob * S) || dalloc(h, &h->d_ccs, nprob * S * 2) || dalloc(h, &h->d_reg, nprob * lsd_grow_reg_stride(L)) ||
-        dalloc(h, &h->d_clabel, nprob * S))
-        return LF_ERR_HIP;
-    h->d_csn = h->d_ccs + 1;          // (cos, sin) pairs in one array: k_lsd_order.hip
-    if (dalloc(h, &h->d_rsd, nprob * S * 2) || dalloc(h, &h->d_csd, nprob * S * 2)) return LF_ERR_HIP;
-    L.r_sd = h->d_rsd; L.c_sd = h->d_csd;
-    if (h->cfg.lsd_seed_order == LF_LSD_SEED_OPENCV32 && (dalloc(h, &h->d_laddr, nprob * S) || dalloc(h, &h->d_lmod, nprob * S)))
-        return LF_ERR_HIP;
-    return LF_OK;
+    const lf_config& c = h->cfg;
+    lf_lsd_options o;
+    o.refine = c.lsd_refine; o.n_bins = c.lsd_n_bins; o.scale = c.lsd_scale; o.sigma_scale = c.lsd_sigma_scale; o.quant = c.lsd_quant;
+    o.ang_th = c.lsd_ang_th; o.log_eps = c.lsd_log_eps; o.density_th = c.lsd_density_th; o.min_length = 0.0;
+    const int rc = h->lsd.init(h, h->Hc, h->W, o, c.lsd_seed_order, h->max_frames, h->cap_lines);
+    if (rc != LF_OK) return rc;
+    const size_t Ps = h->lsd.Ps;
+    size_t cap = Ps;
+    if (h->max_frames > 16) cap = (Ps / 8 + 4095) / 4096 * 4096;
+    const char* e = getenv("LF_LSD_RECORDS");
+    if (e && *e) { if (!strcmp(e, "full")) cap = Ps; else if (atol(e) > 0) cap = (size_t)atol(e); }
+    else if (cap < 8192) cap = 8192;
+    if (cap < 1024) cap = 1024;
+    if (cap > Ps) cap = Ps;
+    return h->lsd.alloc_lists(h, (int)cap);
 }
 
 static int alloc_buffers(lf_handle* h)
 {
-    const size_t B = (size_t)h->max_frames, P = h->P, Ps = h->Ps;
+    const size_t B = (size_t)h->max_frames, P = h->P;
     const size_t in_px = (size_t)h->cfg.in_rows * h->cfg.in_cols;
     const size_t nprob = B * 3;
     const size_t cap = nprob * (size_t)h->cap_lines;
@@ -364,41 +230,11 @@ static int alloc_buffers(lf_handle* h)
     h->frames_bytes = B * in_px * 3 > P * 3 ? B * in_px * 3 : P * 3;
     if (dalloc(h, &h->d_frames, h->frames_bytes) || dalloc(h, &h->d_bgr, B * P) || dalloc(h, &h->d_gray, B * P) || 
         dalloc(h, &h->d_edges_u8, B * P) || dalloc(h, &h->d_strong, B * h->Hc * h->Ww) || dalloc(h, &h->d_weak, B * h->Hc * h->Ww) || dalloc(h, &h->d_maskbits, nprob * h->Hc * h->Ww) ||
-        dalloc(h, &h->d_tile_list, nprob * (size_t)(((h->Ws + 31) / 32) * ((h->Hs + 31) / 32))) ||
-        dalloc(h, &h->d_gused, nprob * ((Ps + 31) / 32)) || dalloc(h, &h->d_row_start, nprob * (size_t)(h->Hs + 1)) ||
-        dalloc(h, &h->d_comp_list, nprob * (size_t)kCompCap) || dalloc(h, &h->d_comp_count, nprob) || dalloc(h, &h->d_perm, nprob) || dalloc(h, &h->d_comp_key, nprob) ||
-        dalloc(h, &h->d_tmp_lines, cap * 4) || dalloc(h, &h->d_tmp_tags, cap) ||
-        dalloc(h, &h->d_pend_rec, nprob * (size_t)lsd_grow_pend_cap(h->lsd) * 12 + 2) || dalloc(h, &h->d_pend_tag, nprob * (size_t)lsd_grow_pend_cap(h->lsd) + 1) || dalloc(h, &h->d_pend_count, nprob) || dalloc(h, &h->d_norder, nprob) ||
         dalloc(h, &h->d_counts, nprob) || dalloc(h, &h->d_seg_offset, nprob + 1) || dalloc(h, &h->d_frame_offset, B + 1) ||
         dalloc(h, &h->d_slot_lines, cap * 4) || dalloc(h, &h->d_seg_frame, cap) ||
         dalloc(h, &h->d_dxy, B * P) || dalloc(h, &h->d_normals64, cap * 2) ||
         dalloc(h, &h->d_centers, cap * 2))
         return LF_ERR_HIP;
-    // The per-problem lists.  A batch handle starts with an eighth of the LSD image per problem (a lane frame's colour has 3 - 6 % of its
-    // pixels defined, a camera frame's 10 - 20 %) and grows when a batch needs more (lsd_records_retry); handles of a few frames and the
-    // LSD-only sub-handles (gray images: every pixel can be defined) hold whole images.  LF_LSD_RECORDS=<entries> | full overrides.
-    {
-        size_t cap = Ps;
-        if (h->max_frames > 16 && !g_lsd_only_create) cap = (Ps / 8 + 4095) / 4096 * 4096;
-        const char* e = g_lsd_only_create ? nullptr : getenv("LF_LSD_RECORDS");
-        if (e && *e) { if (!strcmp(e, "full")) cap = Ps; else if (atol(e) > 0) cap = (size_t)atol(e); }
-        else if (cap < 8192) cap = 8192;
-        if (cap < 1024) cap = 1024;
-        if (cap > Ps) cap = Ps;
-        const int rc = alloc_lsd_lists(h, (int)cap);
-        if (rc != LF_OK) return rc;
-    }
-    {
-        h->zero_bytes = nprob * 8 + nprob * 4 + nprob * 4 + 16 + 32;
-        if (dalloc(h, &h->d_zero, h->zero_bytes)) return LF_ERR_HIP;
-        h->d_maxgrad = reinterpret_cast<unsigned long long*>(h->d_zero.p);
-        h->d_nrec = reinterpret_cast<int*>(h->d_zero + nprob * 8);
-        int* nlow = h->d_nrec + nprob;
-        if (h->cfg.lsd_seed_order == LF_LSD_SEED_OPENCV32) h->d_nlow = nlow;
-        h->d_tile_count = nlow + nprob;
-        h->d_overflow = h->d_tile_count + 4;
-        LF_HIP_CHECK(h, hipMemset(h->d_zero, 0, h->zero_bytes));
-    }
     h->out_capacity = (int)cap;
     lf_segments& o = h->d_out;
     memset(&o, 0, sizeof(o));
@@ -433,7 +269,6 @@ extern "C" void lf_destroy(lf_handle* h)
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->lsdkl.reset();            // (its sub-handles borrow this handle's stream)
     timing_resolve(h);
     for (EvPair& e : h->ev_free) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -463,14 +298,12 @@ extern "C" int lf_create(const lf_config* cfg, int device_id, int max_frames, in
     h->cfg = *cfg; h->device = device_id; h->max_frames = max_frames; h->cap_lines = max_lines_per_color;
     h->err[0] = 0;
     memset(h->ms, 0, sizeof(h->ms)); memset(h->launches, 0, sizeof(h->launches));
-    if (const char* ev = getenv("LF_GROW_LDS_LEVEL")) { const int v = atoi(ev); h->env_lds_level = v < 0 ? 0 : (v > 2 ? 2 : v); }
-    if (const char* ev = getenv("LF_GROW_MIXED")) h->env_mixed = atoi(ev) != 0 ? 1 : 0;
-    if (const char* ev = getenv("LF_GROW_BITMAP")) { const int v = atoi(ev); h->env_bitmap = v < 0 ? 0 : v; }       // > 1: that many USED bits (tests)
     if (const char* ev = getenv("LF_KL_LDS_LINES")) { const int v = atoi(ev); h->env_kl_lds_lines = v < 1 ? 1 : (v > 4096 ? 4096 : v); }
     int rc = LF_OK;
     do {
         if (hipSetDevice(device_id) != hipSuccess) { lf_set_error(h, LF_ERR_HIP, "hipSetDevice(%d) failed", device_id); rc = LF_ERR_HIP; break; }
         if ((rc = build_params(h)) != LF_OK) break;
+        if ((rc = init_lsd(h)) != LF_OK) break;
         if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { lf_set_error(h, LF_ERR_HIP, "hipStreamCreate failed"); rc = LF_ERR_HIP; break; }
         if ((rc = upload_tables(h)) != LF_OK) break;
         if ((rc = alloc_buffers(h)) != LF_OK) break;
@@ -502,7 +335,7 @@ static const char* detector_name(int detector)
 int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_working_image)
 {
     hipStream_t s = h->stream;
-    if (h->lists_lost) { lf_set_error(h, LF_ERR_HIP, "the handle lost its LSD lists to an out-of-memory growth (lf_wait / lf_set_image reported it)"); return LF_ERR_HIP; }
+    if (h->lsd.lists_lost) { lf_set_error(h, LF_ERR_HIP, "the handle lost its LSD lists to an out-of-memory growth (lf_wait / lf_set_image reported it)"); return LF_ERR_HIP; }
     h->overflow_zeroed = false;          // (set at the successful END only: an error exit must not leave run_segments believing the overflow words are zero)
     PreParams pp = h->pre;
     if (from_working_image) {
@@ -532,7 +365,7 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
         int rc = hough_prepare(h);
         if (rc != LF_OK) return rc;
         StageTimer t(h, ST_HOUGH);
-        LF_HIP_CHECK(h, hipMemsetAsync(h->d_zero, 0, h->zero_bytes, s));           // every counter of the batch (see d_zero)
+        LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_zero, 0, h->lsd.zero_bytes, s));           // every counter of the batch (see d_zero)
         HoughParams hp = h->hough_p;
         hp.threshold = h->hough_params.threshold; hp.line_length = h->hough_params.min_line_length; hp.line_gap = h->hough_params.max_line_gap;
         launch_hough(hp, n * 3, h->hough_slots < n * 3 ? h->hough_slots : n * 3, h->d_strong, h->d_maskbits, h->d_hough_tab, h->d_hough_acc,
@@ -546,7 +379,7 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
     if (dense) {
         // LineDetector2Dense: a line per edge pixel with a steep undilated mask in place of the LSD stages (k_dense.hip)
         StageTimer t(h, ST_DENSE);
-        LF_HIP_CHECK(h, hipMemsetAsync(h->d_zero, 0, h->zero_bytes, s));           // every counter of the batch (see d_zero)
+        LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_zero, 0, h->lsd.zero_bytes, s));           // every counter of the batch (see d_zero)
         launch_dense(h->Hc, h->W, h->Ww, h->cap_lines, (float)h->dense_params.sobel_threshold, n * 3, h->d_strong, h->d_maskbits,
                      h->d_bwbits, h->d_slot_lines, h->d_dense_rec, h->d_counts, s);
         LF_HIP_CHECK(h, hipGetLastError());
@@ -558,35 +391,22 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
     h->slot_mode = SEG_FLOAT;
     {
         StageTimer t(h, ST_LSD_GRAD);
-        LF_HIP_CHECK(h, hipMemsetAsync(h->d_zero, 0, h->zero_bytes, s));           // every counter of the batch (see d_zero)
-        launch_lsd_grad(h->lsd, h->rt, n, h->d_strong, h->d_maskbits, h->d_raddr, h->d_rdeg, h->d_rmod, h->d_rcs, h->d_rsn, h->d_nrec,
-                        h->d_maxgrad, h->max_nsx, h->max_nsy, h->d_tile_list, h->d_tile_count, h->d_laddr, h->d_lmod, h->d_nlow, h->d_overflow + 5, true, s);
+        LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_zero, 0, h->lsd.zero_bytes, s));           // every counter of the batch (see d_zero)
+        h->lsd.grad(n, h->d_strong, h->d_maskbits, true, s);
     }
-    {
-        StageTimer t(h, ST_LSD_ORDER);
-        launch_lsd_order(h->lsd, n, h->d_raddr, h->d_rdeg, h->d_rmod, h->d_rcs, h->d_rsn, h->d_nrec, h->d_maxgrad, h->d_sort_a, h->d_sort_b, h->d_order_a, h->d_order_b, h->d_norder, h->d_cxy, h->d_cdeg, h->d_cmod, h->d_ccs, h->d_csn, h->d_row_start, s);
-        // OpenCV >= 3.2: the seeds in the order std::sort leaves them in (the compact arrays and row starts stay as they are)
-        if (h->cfg.lsd_seed_order == LF_LSD_SEED_OPENCV32)
-            launch_lsd_seed32(h->lsd, n, h->d_nrec, h->d_norder, h->d_overflow + 5, h->d_maxgrad, h->d_cxy, h->d_cmod, h->d_laddr, h->d_lmod, h->d_nlow, h->d_sort_a, h->d_sort_b, h->d_order_a, h->d_order_b, 0, s);
-    }
+    { StageTimer t(h, ST_LSD_ORDER); h->lsd.order(n, 0, s); }
+    static const bool no_rank = getenv("LF_DIAG_NO_RANK") != nullptr;
     {
         StageTimer t(h, ST_LSD_LABEL);          // (its own stage since round 6: two brackets of different content under one name made the average meaningless)
-        launch_lsd_label(h->lsd, n, h->d_norder, h->d_cxy, h->d_row_start, h->d_clabel, h->d_comp_list, h->d_comp_count, h->d_comp_key, h->d_reg, s);
-        static const bool no_rank = getenv("LF_DIAG_NO_RANK") != nullptr;
-        if (!no_rank) launch_lsd_rank(n * 3, h->d_comp_key, h->d_perm, s);
+        h->lsd.label(n, !no_rank, s);
     }
     static const char* diag_skip = getenv("LF_DIAG_SKIP");     // diagnostic only (what-if timing, results are wrong): "grow"
     if (diag_skip && strstr(diag_skip, "grow")) LF_HIP_CHECK(h, hipMemsetAsync(h->d_counts, 0, (size_t)n * 3 * sizeof(int), s));
     else {
         StageTimer t(h, ST_LSD_GROW);
-        static const bool no_rank = getenv("LF_DIAG_NO_RANK") != nullptr;
-        const int env_lds_level = h->env_lds_level, env_mixed = h->env_mixed;
-        launch_lsd_grow(h->lsd, n, h->d_order_a, h->d_norder, h->d_cxy, h->d_cdeg, h->d_cmod, h->d_ccs, h->d_csn, h->d_row_start,
-                        h->d_clabel, h->d_comp_list, h->d_comp_count, kCompCap, h->d_reg, h->d_gused, h->d_tmp_lines, h->d_tmp_tags,
-                        h->d_slot_lines, h->d_counts, no_rank ? nullptr : h->d_perm, h->d_pend_rec, h->d_pend_tag, h->d_pend_count,
-                        kGrowLdsKb[env_lds_level >= 0 ? env_lds_level : h->grow_lds_level],
-                        env_mixed >= 0 ? env_mixed != 0 : h->grow_mixed,
-                        h->env_bitmap, s);
+        const LsdState& L = h->lsd;
+        h->lsd.grow(n, h->d_slot_lines, h->d_counts, kGrowLdsKb[L.env_lds_level >= 0 ? L.env_lds_level : L.grow_lds_level],
+                    L.env_mixed >= 0 ? L.env_mixed != 0 : L.grow_mixed, !no_rank, s);
     }
     LF_HIP_CHECK(h, hipGetLastError());
     h->last_frames = n;
@@ -600,10 +420,11 @@ int lf::run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe)
     hipStream_t s = h->stream;
     {
         StageTimer t(h, ST_SEGMENTS);
-        if (!h->overflow_zeroed) LF_HIP_CHECK(h, hipMemsetAsync(h->d_overflow, 0, 4 * sizeof(int), s));
+        if (!h->overflow_zeroed) LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_overflow, 0, 4 * sizeof(int), s));
         h->overflow_zeroed = false;
         launch_seg_offsets(n, h->cap_lines, h->d_counts, h->d_seg_offset, dev_out.frame_offset ? dev_out.frame_offset : h->d_frame_offset,
-                           h->d_overflow, h->slot_mode != SEG_FLOAT ? nullptr : h->d_norder, lsd_grow_def_lds(h->lsd, kGrowLdsKb[0]), lsd_grow_def_lds(h->lsd, kGrowLdsKb[1]), s);
+                           h->lsd.d_overflow, h->slot_mode != SEG_FLOAT ? nullptr : h->lsd.d_norder, lsd_grow_def_lds(h->lsd.params, kGrowLdsKb[0]),
+                           lsd_grow_def_lds(h->lsd.params, kGrowLdsKb[1]), s);
         launch_segments(h->seg, n, h->d_slot_lines, h->d_counts, h->d_seg_offset,
                         h->slot_mode == SEG_DENSE ? reinterpret_cast<const uint32_t*>(h->d_dense_rec.p) : h->d_maskbits.p, h->Ww, dev_out,
                         h->d_seg_frame, h->d_normals64, h->d_centers, s, h->slot_mode);
@@ -654,35 +475,13 @@ extern "C" int lf_process_batch_async(lf_handle* h, const uint8_t* frames, int n
     if (rc != LF_OK) return rc;
     // total + overflow flag travel to pinned host memory behind the kernels
     // one copy: overflow[0..3] -> h_pinned[1..4], the detector's failure count -> [5], the segment total (overflow[7]) -> [8]
-    LF_HIP_CHECK(h, hipMemcpyAsync(&h->h_pinned[1], h->d_overflow, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(h, hipMemcpyAsync(&h->h_pinned[1], h->lsd.d_overflow, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
     h->pending = true;
     h->pending_keylines = false;
     h->pending_problems = n_frames * 3;
     h->pending_capacity = out_dev->capacity;
     h->pend_in = d_in; h->pend_n = n_frames; h->pend_out = *out_dev; h->pend_describe = describe != 0;
     return LF_OK;
-}
-
-// The per-problem lists of the LSD stages hold LsdParams::rec_cap entries.  When a batch had a problem with more (d_overflow[5], read
-// by the caller: the largest need), that problem was dropped on the device; here the lists are reallocated with room to spare and the
-// caller runs the batch again.  The stream must be idle.  Results never depend on the capacity -- only whether a batch runs twice.
-static int lsd_grow_lists(lf_handle* h, int need)
-{
-    size_t cap = ((size_t)need + (size_t)need / 4 + 4095) / 4096 * 4096;
-    if (cap > h->Ps) cap = h->Ps;
-    if (alloc_trace()) fprintf(stderr, "lanefront: a problem needs %d list entries, the handle holds %d: growing to %zu\n", need, h->lsd.rec_cap, cap);
-    const int old_cap = h->lsd.rec_cap;
-    free_lsd_lists(h);
-    int rc = alloc_lsd_lists(h, (int)cap);
-    if (rc == LF_OK) { ++h->lists_grown; h->lists_lost = false; return LF_OK; }
-    // Out of memory part way: never leave the handle with null lists behind a capacity that says otherwise (the next batch would launch
-    // the LSD kernels on them -- a GPU fault, not an error code).  Back to the capacity that did fit; when even that fails now, the
-    // handle refuses every later detect call (lists_lost) until a growth succeeds.
-    free_lsd_lists(h);
-    if (alloc_lsd_lists(h, old_cap) != LF_OK) { free_lsd_lists(h); h->lsd.rec_cap = old_cap; h->lists_lost = true; }
-    lf_set_error(h, LF_ERR_HIP, "out of device memory growing the LSD lists from %d to %zu entries per problem%s", old_cap, cap,
-                 h->lists_lost ? "; the lists are gone: the handle refuses detection" : "; the handle keeps its old lists");
-    return LF_ERR_HIP;
 }
 
 extern "C" int lf_wait(lf_handle* h, int* n_segments)
@@ -700,27 +499,20 @@ extern "C" int lf_wait(lf_handle* h, int* n_segments)
         if (overflow) { lf_set_error(h, LF_ERR_CAPACITY, "%d KeyLines exceed the output capacity %d", total_kl, h->pending_capacity); return LF_ERR_CAPACITY; }
         return LF_OK;
     }
-    for (int attempt = 0; h->detector == LF_DETECTOR_LSD && h->h_pinned[6] > h->lsd.rec_cap; ++attempt) {
+    for (int attempt = 0; h->detector == LF_DETECTOR_LSD && h->h_pinned[6] > h->lsd.params.rec_cap; ++attempt) {
         // a problem did not fit the per-problem lists: grow them and run the batch again (its inputs are still where they were)
         if (attempt == 4) { lf_set_error(h, LF_ERR_CAPACITY, "the LSD lists keep overflowing (%d entries needed)", h->h_pinned[6]); return LF_ERR_CAPACITY; }
-        int rc = lsd_grow_lists(h, h->h_pinned[6]);
+        int rc = h->lsd.grow_lists(h, h->h_pinned[6]);
         if (rc == LF_OK) rc = run_detect(h, h->pend_in, h->pend_n, false);
         if (rc == LF_OK) rc = run_segments(h, h->pend_n, h->pend_out, h->pend_describe);
         if (rc != LF_OK) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(&h->h_pinned[1], h->d_overflow, 8 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        LF_HIP_CHECK(h, hipMemcpyAsync(&h->h_pinned[1], h->lsd.d_overflow, 8 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         LF_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     }
     h->detector_failures = h->detector == LF_DETECTOR_EDLINES ? h->h_pinned[5] : 0;
     const int total = h->h_pinned[8];
     if (n_segments) *n_segments = total;
-    // The next batch's region-growing slices (performance only: the results do not depend on them): 13 KB while nearly every
-    // problem fits it (the synthetic lane frames), 28 KB when more than 5 % overflow it (real camera frames have two to three
-    // times the edge pixels), 40 KB when more than 25 % overflow 28 KB.
-    if (h->pending_problems > 0) {
-        const int over_small = h->h_pinned[2], over_medium = h->h_pinned[3], np = h->pending_problems;
-        h->grow_lds_level = over_medium * 4 > np ? 2 : (over_small * 20 > np ? 1 : 0);
-        h->grow_mixed = (h->grow_lds_level == 0 ? over_small : over_medium) * 100 > np;
-    }
+    if (h->pending_problems > 0) h->lsd.adapt_slice(h->h_pinned[2], h->h_pinned[3], h->pending_problems);
     if (h->h_pinned[1]) { lf_set_error(h, LF_ERR_CAPACITY, "%s %s run produced more than max_lines_per_color=%d lines", h->detector == LF_DETECTOR_DENSE ? "a" : "an", detector_name(h->detector), h->cap_lines); return LF_ERR_CAPACITY; }
     if (total > h->pending_capacity) { lf_set_error(h, LF_ERR_CAPACITY, "%d segments exceed the output capacity %d", total, h->pending_capacity); return LF_ERR_CAPACITY; }
     return LF_OK;
@@ -825,12 +617,12 @@ extern "C" int lf_set_image(lf_handle* h, const uint8_t* bgr, int rows, int cols
     if ((rc = plugin_fetch_results(h)) != LF_OK) return rc;
     LF_HIP_CHECK(h, hipMemcpyAsync(h->h_counts.data(), h->d_counts, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
     LF_HIP_CHECK(h, hipMemcpyAsync(h->h_seg_offset.data(), h->d_seg_offset, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipMemcpyAsync(&h->h_pinned[6], h->d_overflow + 5, sizeof(int), hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(h, hipMemcpyAsync(&h->h_pinned[6], h->lsd.d_overflow + 5, sizeof(int), hipMemcpyDeviceToHost, s));
     LF_HIP_CHECK(h, hipStreamSynchronize(s));          // the ONE synchronisation of an image: counts, segments and masks are on the host
     // (a handle made for batches holds short per-problem lists: grow them and detect again when this image needs more)
-    if (h->h_pinned[6] <= h->lsd.rec_cap) break;
+    if (h->h_pinned[6] <= h->lsd.params.rec_cap) break;
     if (attempt == 4) { lf_set_error(h, LF_ERR_CAPACITY, "the LSD lists keep overflowing (%d entries needed)", h->h_pinned[6]); return LF_ERR_CAPACITY; }
-    if ((rc = lsd_grow_lists(h, h->h_pinned[6])) != LF_OK) return rc;
+    if ((rc = h->lsd.grow_lists(h, h->h_pinned[6])) != LF_OK) return rc;
     }
     h->plugin_ready = true;
     return LF_OK;
@@ -1126,21 +918,21 @@ extern "C" int lf_kmeans(lf_handle* h, const uint8_t* bgr_points, int n, int on_
 extern "C" int lf_lsd_list_capacity(const lf_handle* h, int* entries, int* grown)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
-    if (entries) *entries = h->lsd.rec_cap;
-    if (grown) *grown = h->lists_grown;
+    if (entries) *entries = h->lsd.params.rec_cap;
+    if (grown) *grown = h->lsd.lists_grown;
     return LF_OK;
 }
 
 extern "C" int lf_lsd_scratch_stride(const lf_handle* h)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
-    return (int)lsd_grow_reg_stride(h->lsd);
+    return (int)lsd_grow_reg_stride(h->lsd.params);
 }
 
 extern "C" int lf_suggested_depth(const lf_handle* h)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
-    return h->grow_lds_level == 0 && !h->grow_mixed ? 8 : 18;
+    return h->lsd.grow_lds_level == 0 && !h->lsd.grow_mixed ? 8 : 18;
 }
 
 extern "C" int lf_debug_std_sort(lf_handle* h, const int32_t* keys, int n, int32_t* order)
@@ -1181,9 +973,9 @@ extern "C" int lf_debug_lsd_binary(lf_handle* h, const uint8_t* img, int rows, i
     if (!img || !lines4 || !n_out || rows != h->Hc || cols != h->W) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_debug_lsd_binary: bad argument (image must be %dx%d)", h->Hc, h->W); return LF_ERR_BAD_ARG; }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    if ((size_t)h->lsd.rec_cap < h->Ps) {                 // (a debug entry: any binary image must fit -- whole-image lists from here on)
+    if ((size_t)h->lsd.params.rec_cap < h->lsd.Ps) {        // (a debug entry: any binary image must fit -- whole-image lists from here on)
         LF_HIP_CHECK(h, hipStreamSynchronize(s));
-        const int rc = lsd_grow_lists(h, (int)h->Ps);
+        const int rc = h->lsd.grow_lists(h, (int)h->lsd.Ps);
         if (rc != LF_OK) return rc;
     }
     const size_t nw = (size_t)h->Hc * h->Ww;
@@ -1193,18 +985,11 @@ extern "C" int lf_debug_lsd_binary(lf_handle* h, const uint8_t* img, int rows, i
             if (img[(size_t)y * cols + x]) bits[(size_t)y * h->Ww + (x >> 5)] |= 1u << (x & 31);
     LF_HIP_CHECK(h, hipMemcpyAsync(h->d_strong, bits.data(), nw * 4, hipMemcpyHostToDevice, s));
     LF_HIP_CHECK(h, hipMemcpyAsync(h->d_maskbits, ones.data(), nw * 12, hipMemcpyHostToDevice, s));
-    LF_HIP_CHECK(h, hipMemsetAsync(h->d_maxgrad, 0, 3 * sizeof(unsigned long long), s));
-    launch_lsd_grad(h->lsd, h->rt, 1, h->d_strong, h->d_maskbits, h->d_raddr, h->d_rdeg, h->d_rmod, h->d_rcs, h->d_rsn, h->d_nrec, h->d_maxgrad,
-                    h->max_nsx, h->max_nsy, h->d_tile_list, h->d_tile_count, h->d_laddr, h->d_lmod, h->d_nlow, h->d_overflow + 5, false, s);
-    launch_lsd_order(h->lsd, 1, h->d_raddr, h->d_rdeg, h->d_rmod, h->d_rcs, h->d_rsn, h->d_nrec, h->d_maxgrad, h->d_sort_a, h->d_sort_b, h->d_order_a, h->d_order_b, h->d_norder,
-                     h->d_cxy, h->d_cdeg, h->d_cmod, h->d_ccs, h->d_csn, h->d_row_start, s);
-    if (h->cfg.lsd_seed_order == LF_LSD_SEED_OPENCV32)
-        launch_lsd_seed32(h->lsd, 1, h->d_nrec, h->d_norder, h->d_overflow + 5, h->d_maxgrad, h->d_cxy, h->d_cmod, h->d_laddr, h->d_lmod, h->d_nlow, h->d_sort_a, h->d_sort_b, h->d_order_a, h->d_order_b, 0, s);
-    launch_lsd_label(h->lsd, 1, h->d_norder, h->d_cxy, h->d_row_start, h->d_clabel, h->d_comp_list, h->d_comp_count, h->d_comp_key, h->d_reg, s);
-    launch_lsd_grow(h->lsd, 1, h->d_order_a, h->d_norder, h->d_cxy, h->d_cdeg, h->d_cmod, h->d_ccs, h->d_csn, h->d_row_start,
-                    h->d_clabel, h->d_comp_list, h->d_comp_count, kCompCap, h->d_reg, h->d_gused, h->d_tmp_lines, h->d_tmp_tags,
-                    h->d_slot_lines, h->d_counts, nullptr, h->d_pend_rec, h->d_pend_tag, h->d_pend_count, kGrowLdsKb[h->grow_lds_level], true,
-                    h->env_bitmap, s);
+    LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_maxgrad, 0, 3 * sizeof(unsigned long long), s));
+    h->lsd.grad(1, h->d_strong, h->d_maskbits, false, s);
+    h->lsd.order(1, 0, s);
+    h->lsd.label(1, false, s);
+    h->lsd.grow(1, h->d_slot_lines, h->d_counts, kGrowLdsKb[h->lsd.grow_lds_level], true, false, s);
     LF_HIP_CHECK(h, hipGetLastError());
     int n = 0;
     LF_HIP_CHECK(h, hipMemcpyAsync(&n, h->d_counts, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1221,7 +1006,7 @@ extern "C" int lf_debug_lsd_binary(lf_handle* h, const uint8_t* img, int rows, i
 extern "C" int lf_lsd_size(const lf_handle* h, int* rows, int* cols)
 {
     if (!h || !rows || !cols) return LF_ERR_BAD_ARG;
-    *rows = h->Hs; *cols = h->Ws;
+    *rows = h->lsd.params.Hs; *cols = h->lsd.params.Ws;
     return LF_OK;
 }
 
@@ -1253,23 +1038,24 @@ extern "C" int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t byt
     case LF_BUF_LSD_ANGLE:
     case LF_BUF_LSD_MODGRAD: {
         // the pipeline keeps no dense LSD planes: rebuild them from the compact arrays
-        int rc = ensure(h, h->dbg_ang, n * 3 * h->Ps * sizeof(float));
-        if (rc == LF_OK) rc = ensure(h, h->dbg_mod, n * 3 * h->Ps * sizeof(double));
+        const LsdState& L = h->lsd;
+        int rc = ensure(h, h->dbg_ang, n * 3 * L.Ps * sizeof(float));
+        if (rc == LF_OK) rc = ensure(h, h->dbg_mod, n * 3 * L.Ps * sizeof(double));
         if (rc != LF_OK) return rc;
-        launch_lsd_dense_debug(h->lsd, (int)n, h->d_norder, h->d_cxy, h->d_cdeg, h->d_cmod, (float*)h->dbg_ang.p, (double*)h->dbg_mod.p, s);
-        if (buffer_id == LF_BUF_LSD_ANGLE) { src = h->dbg_ang.p; avail = n * 3 * h->Ps * sizeof(float); }
-        else { src = h->dbg_mod.p; avail = n * 3 * h->Ps * sizeof(double); }
+        launch_lsd_dense_debug(L.params, (int)n, L.d_norder, L.d_cxy, L.d_cdeg, L.d_cmod, (float*)h->dbg_ang.p, (double*)h->dbg_mod.p, s);
+        if (buffer_id == LF_BUF_LSD_ANGLE) { src = h->dbg_ang.p; avail = n * 3 * L.Ps * sizeof(float); }
+        else { src = h->dbg_mod.p; avail = n * 3 * L.Ps * sizeof(double); }
         break;
     }
     case LF_BUF_LSD_ORDER: {
         // [frames][3][Hs * Ws] for the caller; the handle's lists have rec_cap entries per problem
-        const size_t row = h->Ps * sizeof(uint32_t), have = (size_t)h->lsd.rec_cap * sizeof(uint32_t);
+        const size_t row = h->lsd.Ps * sizeof(uint32_t), have = (size_t)h->lsd.params.rec_cap * sizeof(uint32_t);
         if (bytes > n * 3 * row) { lf_set_error(h, LF_ERR_CAPACITY, "buffer %d holds %zu bytes, %zu requested", buffer_id, n * 3 * row, bytes); return LF_ERR_CAPACITY; }
-        LF_HIP_CHECK(h, hipMemcpy2DAsync(dst, row, h->d_order_a, have, have, bytes / row, hipMemcpyDeviceToHost, s));
+        LF_HIP_CHECK(h, hipMemcpy2DAsync(dst, row, h->lsd.d_order_a, have, have, bytes / row, hipMemcpyDeviceToHost, s));
         LF_HIP_CHECK(h, hipStreamSynchronize(s));
         return LF_OK;
     }
-    case LF_BUF_LSD_NORDER: src = h->d_norder; avail = n * 3 * sizeof(int); break;
+    case LF_BUF_LSD_NORDER: src = h->lsd.d_norder; avail = n * 3 * sizeof(int); break;
     case LF_BUF_LBD_DX:
     case LF_BUF_LBD_DY: {
         // the pipeline keeps dx and dy interleaved: split them for the caller
@@ -1283,9 +1069,9 @@ extern "C" int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t byt
     }
     case LF_BUF_LSD_COUNTS: src = h->d_counts; avail = n * 3 * sizeof(int); break;
     case LF_BUF_LSD_NLOW:
-        if (!h->d_nlow) { memset(dst, 0, bytes < n * 3 * sizeof(int) ? bytes : n * 3 * sizeof(int)); return LF_OK; }
-        src = h->d_nlow; avail = n * 3 * sizeof(int); break;
-    case LF_BUF_LSD_SCRATCH: src = h->d_reg; avail = n * 3 * lsd_grow_reg_stride(h->lsd) * sizeof(uint32_t); break;
+        if (!h->lsd.d_nlow) { memset(dst, 0, bytes < n * 3 * sizeof(int) ? bytes : n * 3 * sizeof(int)); return LF_OK; }
+        src = h->lsd.d_nlow; avail = n * 3 * sizeof(int); break;
+    case LF_BUF_LSD_SCRATCH: src = h->lsd.d_reg; avail = n * 3 * lsd_grow_reg_stride(h->lsd.params) * sizeof(uint32_t); break;
     default: lf_set_error(h, LF_ERR_BAD_ARG, "unknown buffer id %d", buffer_id); return LF_ERR_BAD_ARG;
     }
     if (bytes > avail) { lf_set_error(h, LF_ERR_CAPACITY, "buffer %d holds %zu bytes, %zu requested", buffer_id, avail, bytes); return LF_ERR_CAPACITY; }

@@ -1,5 +1,5 @@
 // lanefront's host side: the handle, its substates and the few helpers the translation units of the C ABI share
-// (lanefront_api.hip, lanefront_keylines.hip, lanefront_lsdkl.hip, lanefront_matcher.hip, lanefront_jpeg_gpu.hip).
+// (lanefront_api.hip, lanefront_lsd.hip, lanefront_keylines.hip, lanefront_lsdkl.hip, lanefront_matcher.hip, lanefront_jpeg_gpu.hip).
 // Host code only; common.h does not include it (tests/hostsim builds lsd_grow.h on the CPU).
 #pragma once
 #include <stdio.h>
@@ -59,16 +59,72 @@ struct KlState {
     int last_octaves = 0, last_frames = 0;
 };
 
+// The LSD detector (lanefront_lsd.hip): parameters, resize tables, the per-problem lists and arrays, the counter block and k_lsd_grow's
+// slice.  The front end holds one, every pyramid level of the LSD KeyLines one of its own geometry; the slot lines and counts the
+// stages write are the caller's.
+struct LsdState {
+    LsdParams params;
+    ResizeTables rt{};
+    int seed_order = LF_LSD_SEED_OPENCV30, max_frames = 0;       // max_frames * 3 problems
+    size_t Ps = 0;                    // pixels of the scaled image, params.Hs x params.Ws
+    int max_nsx = 0, max_nsy = 0;
+    int label_items_full = 0;    // LsdParams::label_items of lists that hold whole images (alloc_lists lowers it with rec_cap)
+    DevArray<int> d_xofs, d_y0, d_y1;
+    DevArray<float> d_xa, d_yb;
+    // stride LsdParams::rec_cap: records (k_lsd_grad -> k_lsd_order), sort scratch, seed lists, compact arrays, labels, the region
+    // scratch; seed order OPENCV32 only: pixels with a non-zero but undefined gradient (k_lsd_grad -> k_lsd_seed32)
+    DevArray<uint32_t> d_raddr, d_order_a, d_order_b, d_cxy, d_reg, d_laddr;
+    DevArray<float> d_rdeg, d_cdeg, d_rsd, d_csd;     // d_rsd, d_csd: LsdParams::r_sd, c_sd
+    DevArray<double> d_rmod, d_rcs, d_rsn, d_cmod, d_ccs, d_lmod;
+    DevArray<unsigned long long> d_sort_a, d_sort_b;
+    DevArray<uint16_t> d_clabel, d_comp_list;         // connected components (k_lsd_label)
+    double* d_csn = nullptr;                          // d_ccs + 1
+    DevArray<uint32_t> d_tile_list, d_gused;
+    DevArray<int> d_row_start, d_norder, d_comp_count, d_comp_key, d_perm;
+    DevArray<float> d_tmp_lines;                      // lines in completion order + their seed positions (k_lsd_grow)
+    DevArray<int> d_tmp_tags;
+    DevArray<double> d_pend_rec;                      // pending regions (k_lsd_grow -> k_lsd_eval): 12 doubles each, their seed
+    DevArray<int> d_pend_tag, d_pend_count;           // positions, and how many per problem
+    DevArray<uint8_t> d_zero; size_t zero_bytes = 0;  // d_maxgrad | d_nrec | d_nlow | d_tile_count | d_overflow: the counters a batch starts from zero, ONE memset (each memset is a dispatch of its own and waited 0.3 ms in a busy pipeline)
+    unsigned long long* d_maxgrad = nullptr;
+    int *d_nrec = nullptr, *d_nlow = nullptr, *d_tile_count = nullptr, *d_overflow = nullptr;      // (d_nlow: seed order OPENCV32 only)
+    int lists_grown = 0;         // times the per-problem lists were reallocated
+    bool lists_lost = false;     // grow_lists ran out of memory twice: no per-problem lists, detection refuses
+    bool grow_mixed = false;     // the last batch had problems beyond the slice in numbers (> 1 %): one launch with both kinds of problem code
+    int grow_lds_level = 0;      // index into kGrowLdsKb: k_lsd_grow's LDS slice, moved by the share of problems that overflowed it in the last batch
+    int env_lds_level = -1;      // LF_GROW_LDS_LEVEL / LF_GROW_MIXED: test and tuning overrides, read by init, clamped
+    int env_mixed = -1;
+    int env_bitmap = 1;          // LF_GROW_BITMAP=0: the row-list form of k_lsd_grow (rounds 1 - 3) instead of the bit-plane form (A/B measurements); > 1: see launch_lsd_grow
+
+    // parameters, tables, fixed arrays and the zeroed counter block of an Hc x W image; alloc_lists adds the lists (errors go to h)
+    int init(lf_handle* h, int Hc, int W, const lf_lsd_options& o, int seed_order, int max_frames, int cap_lines);
+    int alloc_lists(lf_handle* h, int rec_cap);
+    void free_lists();
+    int grow_lists(lf_handle* h, int need);
+    void adapt_slice(int over_small, int over_medium, int problems);
+    // the stages on n frames; the caller zeroes the counters
+    void grad(int n, const uint32_t* edge_bits, const uint32_t* mask_bits, bool counters_zeroed, hipStream_t s);
+    void grad_gray(int n, const uint8_t* gray, hipStream_t s);
+    void order(int n, int big, hipStream_t s);       // + k_lsd_seed32 with seed order OPENCV32
+    void label(int n, bool rank, hipStream_t s);
+    void grow(int n, float* lines, int* counts, int lds_kb, bool mixed, bool use_perm, hipStream_t s);
+};
+
+struct LsdKlLevel {
+    LsdState lsd;
+    DevArray<float> lines;                // the level's slot lines and counts
+    DevArray<int> counts;
+    lf_lsd_options opts{};                // the options the state was made with
+    bool ready = false;
+};
+
 struct LsdKlState {
-    lf_handle* sub[LF_MAX_OCTAVES] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    LsdKlLevel level[LF_MAX_OCTAVES];     // made on first use, remade for another geometry or other options
     DevBuf pyr[LF_MAX_OCTAVES];          // levels 1.. of the detect pyramid (level 0 is the caller's gray image)
     DevBuf gray0, frame_count, frame_offset, line_frame, totals;
     DevBuf o_start_end, o_in_octave, o_angle, o_npx, o_len, o_octave, o_class, o_response, o_size, o_pt, o_desc, o_code;
-    int H[LF_MAX_OCTAVES], W[LF_MAX_OCTAVES];
     HostArray<int> h_pinned;
-    lf_lsd_options sub_opts[LF_MAX_OCTAVES];        // the options each cached sub-handle was made with
     DevBuf masks;                                   // a host caller's masks on the device
-    ~LsdKlState();                                  // destroys the sub-handles (lanefront_lsdkl.hip)
 };
 
 struct MatcherState {
@@ -89,17 +145,13 @@ struct lf_handle {
     char err[512];
     int err_code = 0;
     // geometry
-    int Hc = 0, W = 0, Hs = 0, Ws = 0, Ww = 0;
-    size_t P = 0, Ps = 0;
+    int Hc = 0, W = 0, Ww = 0;
+    size_t P = 0;
     lf_descriptor_params desc_params = { 1, 7, 2, 5 };      // BinaryDescriptor::Params (lf_set_descriptor_params)
-    bool lists_lost = false;     // lsd_grow_lists ran out of memory twice: no per-problem lists, run_detect refuses
-    int label_items_full = 0;    // LsdParams::label_items of a handle whose lists hold whole images (alloc_lsd_lists lowers it with rec_cap)
     lf::PreParams pre;
     lf::CannyParams canny;
-    lf::LsdParams lsd;
+    lf::LsdState lsd;
     lf::SegParams seg;
-    lf::ResizeTables rt;
-    int max_nsx = 0, max_nsy = 0;
     // device buffers
     lf::DevArray<uint8_t> d_frames, d_edges_u8;
     lf::DevBuf dbg_masks;                   // 0/255 byte form of the colour masks, expanded from the bit planes on demand
@@ -109,45 +161,14 @@ struct lf_handle {
     lf::DevBuf dbg_bgr;
     lf::DevArray<uint32_t> d_strong, d_weak, d_maskbits;
     lf::DevArray<int> d_sdiv, d_hdiv;
-    // unordered per-problem records of defined LSD pixels (k_lsd_grad -> k_lsd_order)
-    lf::DevArray<uint32_t> d_raddr;
-    lf::DevArray<float> d_rdeg;
-    lf::DevArray<double> d_rmod, d_rcs, d_rsn;
-    lf::DevArray<float> d_rsd, d_csd;     // LsdParams::r_sd, c_sd
-    int* d_nrec = nullptr;
-    lf::DevArray<uint8_t> d_zero; size_t zero_bytes = 0;  // d_maxgrad | d_nrec | d_nlow | d_tile_count | d_overflow: the counters a batch starts from zero, ONE memset (each memset is a dispatch of its own and waited 0.3 ms in a busy pipeline)
-    bool overflow_zeroed = false;
-    // lsd_seed_order = OPENCV32 only: pixels with a non-zero but undefined gradient (k_lsd_grad -> k_lsd_seed32)
-    lf::DevArray<uint32_t> d_laddr; lf::DevArray<double> d_lmod; int* d_nlow = nullptr;
-    lf::DevArray<unsigned long long> d_sort_a, d_sort_b;
+    bool overflow_zeroed = false;         // the batch's one memset of lsd.d_zero covered the overflow words (run_segments)
     lf::DevBuf dbg_ang, dbg_mod;
-    unsigned long long* d_maxgrad = nullptr;
-    lf::DevArray<uint32_t> d_order_a, d_order_b, d_reg;
-    lf::DevArray<uint32_t> d_cxy, d_gused;
-    lf::DevArray<float> d_cdeg;
-    lf::DevArray<double> d_cmod, d_ccs;
-    double* d_csn = nullptr;          // d_ccs + 1
-    lf::DevArray<uint32_t> d_tile_list;
-    int* d_tile_count = nullptr;
-    lf::DevArray<int> d_row_start;
-    lf::DevArray<int> d_norder, d_counts, d_seg_offset, d_frame_offset;
-    int* d_overflow = nullptr;
+    lf::DevArray<int> d_counts, d_seg_offset, d_frame_offset;
     lf::DevArray<float> d_slot_lines;
-    lf::DevArray<uint16_t> d_clabel, d_comp_list;    // connected components of the LSD problems (k_lsd_label)
-    lf::DevArray<int> d_comp_count;
-    lf::DevArray<int> d_perm;
-    lf::DevArray<int> d_comp_key;
-    lf::DevArray<float> d_tmp_lines;                            // lines in completion order + their seed positions (k_lsd_grow)
-    lf::DevArray<int> d_tmp_tags;
-    lf::DevArray<double> d_pend_rec;    // pending regions of every LSD problem (k_lsd_grow -> k_lsd_eval): 12 doubles each,
-    lf::DevArray<int> d_pend_tag;       // their seed positions,
-    lf::DevArray<int> d_pend_count;     // and how many per problem
     lf::DevArray<int> d_seg_frame;
     lf::DevArray<uint32_t> d_dxy;         // LBD gradients, dx | dy << 16 per pixel
     lf::DevBuf dbg_dx, dbg_dy;
     lf::DevArray<float> d_gauss_g, d_gauss_l;
-    lf::DevArray<int> d_xofs, d_y0, d_y1;
-    lf::DevArray<float> d_xa, d_yb;
     // output staging (device side of host-output calls, and the plugin path)
     lf_segments d_out;                  // views of the out_* arrays
     lf::DevArray<float> out_lines, out_normals, out_pixels_normalized;
@@ -166,7 +187,6 @@ struct lf_handle {
     // pinned host scalars
     lf::HostArray<int> h_pinned;     // [0] total segments, [1] overflow ... [6] entries the per-problem lists would have needed (d_overflow[5])
     const uint8_t* pend_in = nullptr; int pend_n = 0; lf_segments pend_out; bool pend_describe = false;   // the batch in flight (lsd_records_retry)
-    int lists_grown = 0;         // times the per-problem lists were reallocated
     int last_frames = 0;
     bool plugin_ready = false;
     bool pending = false;
@@ -175,8 +195,6 @@ struct lf_handle {
     lf::HostArray<uint8_t> plug_host, plug_in;
     int plug_eager = 0;
     bool pending_keylines = false;        // the batch in flight is lf_keylines_batch_async's: lf_wait reads the KeyLine state
-    bool grow_mixed = false;     // the last batch had problems beyond the slice in numbers (> 1 %): one launch with both kinds of problem code
-    int grow_lds_level = 0;      // index into kGrowLdsKb: k_lsd_grow's LDS slice, moved by the share of problems that overflowed it in the last batch
     int detector = LF_DETECTOR_LSD;       // what lf_process_batch runs for a-2 .. a-4 (lf_set_detector)
     lf_edlines_params ed_params;
     int detector_failures = 0;            // frames of the last completed batch on which the EDLines detector gave up
@@ -191,16 +209,13 @@ struct lf_handle {
     lf::DevArray<float> d_dense_rec;             // per slot (nx, ny, x, y) of the dense lines, [frame][colour][cap_lines] (k_dense)
     lf::SegMode slot_mode = lf::SEG_FLOAT;      // what the slots of the last detect hold: which a-5 k_segments applies
     int tie_rule = LF_TIE_MIHASHER;   // lf_associate: the reference's rule unless lf_set_tie_rule says otherwise
-    int env_lds_level = -1;      // LF_GROW_LDS_LEVEL / LF_GROW_MIXED: test and tuning overrides, read when the handle is created, clamped
-    int env_mixed = -1;
-    int env_bitmap = 1;          // LF_GROW_BITMAP=0: the row-list form of k_lsd_grow (rounds 1 - 3) instead of the bit-plane form (A/B measurements); > 1: see launch_lsd_grow
     int env_kl_lds_lines = 0;    // LF_KL_LDS_LINES (test hook of the KeyLine grouping, lanefront_keylines.hip)
     int pending_problems = 0;
     int pending_capacity = 0;
     std::vector<int> h_counts, h_seg_offset;
     std::unique_ptr<lf::JpegState> jpeg;
     std::unique_ptr<lf::KlState> kl;      // EDLines / KeyLines state (lanefront_keylines.hip), allocated on first use
-    std::unique_ptr<lf::LsdKlState> lsdkl; // LSDDetectorC over octaves (lanefront_lsdkl.hip): sub-handles per pyramid level
+    std::unique_ptr<lf::LsdKlState> lsdkl; // LSDDetectorC over octaves (lanefront_lsdkl.hip): an LSD state per pyramid level
     lf::DevBuf m_fo, m_color, m_pn, m_nm, m_gr, m_keep, m_counts, m_boff, m_body, m_bad;   // SegmentList glue scratch
     // profiling
     bool profiling = false;
@@ -254,8 +269,6 @@ struct StageTimer {
         h->launches[st] += 1;
     }
 };
-
-extern thread_local bool g_lsd_only_create;      // set around the lf_create of an LSD-only sub-handle (lanefront_lsdkl.hip; defined in lanefront_api.hip)
 
 // lanefront_api.hip
 int run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_working_image);

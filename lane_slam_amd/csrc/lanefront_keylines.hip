@@ -581,12 +581,12 @@ int lf::run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n)
     { StageTimer t(h, ST_PRE); launch_pre(h->pre, d_frames, n, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s); }
     EdAll all;
     if ((rc = kl_run_octaves(h, h->d_gray, n, 1, P, all)) != LF_OK) return rc;
-    LF_HIP_CHECK(h, hipMemsetAsync(h->d_norder, 0, (size_t)n * 3 * sizeof(int), s));        // (LSD's slice statistics: nothing to learn from this batch)
+    LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_norder, 0, (size_t)n * 3 * sizeof(int), s));        // (LSD's slice statistics: nothing to learn from this batch)
     h->slot_mode = SEG_FLOAT;
-    LF_HIP_CHECK(h, hipMemsetAsync(h->d_overflow + 4, 0, sizeof(int), s));
+    LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_overflow + 4, 0, sizeof(int), s));
     {
         StageTimer t(h, ST_SEGMENTS);
-        launch_ed_slots(all, n, h->d_maskbits, h->Ww, h->cap_lines, h->d_slot_lines, h->d_counts, h->d_overflow + 4, s);
+        launch_ed_slots(all, n, h->d_maskbits, h->Ww, h->cap_lines, h->d_slot_lines, h->d_counts, h->lsd.d_overflow + 4, s);
     }
     h->kl->last_octaves = 1; h->kl->last_frames = n;
     h->last_frames = n;

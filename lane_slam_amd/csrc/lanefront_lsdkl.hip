@@ -9,23 +9,18 @@
 // followed, on request, by BinaryDescriptor::compute on those KeyLines (lf_describe_keylines: ITS pyramid, blurred, :350-371).
 //
 // The LSD stages are the front end's own kernels run on GRAY levels: k_lsd_grad's gray form (the raw tile is the image, every
-// tile listed), then k_lsd_order / label / rank / grow unchanged.  Every level has its own geometry, so every level gets a
-// sub-handle of that geometry (created on first use, sharing this handle's stream); a level's frame f is LSD problem 3 f.
+// tile listed), then k_lsd_order / label / grow unchanged.  Every level has its own geometry, so every level gets an LSD state
+// of that geometry (lf::LsdState, made on first use) and its own slot lines and counts; a level's frame f is LSD problem 3 f.
 // Gray camera images are DENSE problems (tens of thousands of defined pixels in one connected component, grown by one wave):
 // this path is about completeness of detect -> compute for both detectors of the library, not about throughput.
 
 #include <string.h>
 #include <algorithm>
+#include <string>
 #include "lanefront_handle.h"
 
 using namespace lf;
 
-
-lf::LsdKlState::~LsdKlState()
-{
-    for (lf_handle* s : sub)
-        if (s) { s->stream = nullptr; lf_destroy(s); }      // the stream is the parent's
-}
 
 extern "C" void lf_lsd_default_options(lf_lsd_options* o)
 {
@@ -41,26 +36,23 @@ static bool lsdkl_same_opts(const lf_lsd_options& a, const lf_lsd_options& b)
            a.log_eps == b.log_eps && a.density_th == b.density_th && a.n_bins == b.n_bins;          // (min_length is applied outside the detector)
 }
 
-// the sub-handle of level o: the level's geometry, the caller's LSD parameters, this handle's stream
-static int lsdkl_sub(lf_handle* h, LsdKlState* k, int o, int Ho, int Wo, const lf_lsd_options& opts, lf_handle** out)
+// a level's LSD state: the level's geometry, the caller's LSD parameters, lists that hold whole images
+static int lsdkl_level(lf_handle* h, LsdKlLevel& lv, int Ho, int Wo, const lf_lsd_options& opts)
 {
-    if (k->sub[o] && k->sub[o]->Hc == Ho && k->sub[o]->W == Wo && lsdkl_same_opts(k->sub_opts[o], opts)) { *out = k->sub[o]; return LF_OK; }
-    if (k->sub[o]) { k->sub[o]->stream = nullptr; lf_destroy(k->sub[o]); k->sub[o] = nullptr; }
-    lf_config c = h->cfg;
-    c.in_rows = Ho; c.in_cols = Wo; c.img_rows = Ho; c.img_cols = Wo; c.top_cutoff = 0;
-    c.lsd_refine = opts.refine; c.lsd_n_bins = opts.n_bins; c.lsd_scale = opts.scale; c.lsd_sigma_scale = opts.sigma_scale; c.lsd_quant = opts.quant;
-    c.lsd_ang_th = opts.ang_th; c.lsd_log_eps = opts.log_eps; c.lsd_density_th = opts.density_th;
-    k->sub_opts[o] = opts;
-    lf_handle* s = nullptr;
-    g_lsd_only_create = true;
-    const int rc = lf_create(&c, h->device, h->max_frames, h->cap_lines, &s);
-    g_lsd_only_create = false;
-    if (rc != LF_OK) { lf_set_error(h, rc, "LSD KeyLines: no handle for the %dx%d level (%s)", Wo, Ho, lf_last_error(nullptr)); return rc; }
-    (void)hipStreamSynchronize(s->stream);
-    (void)hipStreamDestroy(s->stream);
-    s->stream = h->stream;
-    k->sub[o] = s;
-    *out = s;
+    if (lv.ready && lv.lsd.params.Hc == Ho && lv.lsd.params.W == Wo && lsdkl_same_opts(lv.opts, opts)) return LF_OK;
+    lv = LsdKlLevel();
+    const size_t nprob = (size_t)h->max_frames * 3;
+    int rc = lv.lsd.init(h, Ho, Wo, opts, h->cfg.lsd_seed_order, h->max_frames, h->cap_lines);
+    if (rc == LF_OK) rc = lv.lsd.alloc_lists(h, (int)lv.lsd.Ps);
+    if (rc == LF_OK && (dalloc(h, &lv.lines, nprob * h->cap_lines * 4) || dalloc(h, &lv.counts, nprob))) rc = LF_ERR_HIP;
+    if (rc != LF_OK) {
+        const std::string why = h->err;
+        lf_set_error(h, rc, "LSD KeyLines: no LSD state for the %dx%d level (%s)", Wo, Ho, why.c_str());
+        lv = LsdKlLevel();
+        return rc;
+    }
+    lv.lsd.env_bitmap = h->lsd.env_bitmap;        // (k_lsd_grow's form: the handle's)
+    lv.opts = opts; lv.ready = true;
     return LF_OK;
 }
 
@@ -162,22 +154,16 @@ __global__ __launch_bounds__(64) void k_lsdkl_fill(LsdKlLevels L, int n_octaves,
     }
 }
 
-// LSD of n gray images of the sub-handle's geometry -> its slot lines / counts (problem 3 f = frame f)
-static int lsdkl_run_level(lf_handle* h, lf_handle* s, const uint8_t* d_gray, int n)
+// LSD of n gray images of the level's geometry -> its slot lines / counts (problem 3 f = frame f); dense problems: the labelling
+// tables at their largest (a gray level has tens of thousands of defined pixels), no rank, both kinds of problem code in one launch
+static int lsdkl_run_level(lf_handle* h, LsdKlLevel& lv, const uint8_t* d_gray, int n)
 {
-    hipStream_t st = s->stream;
-    LF_HIP_CHECK(h, hipMemsetAsync(s->d_maxgrad, 0, (size_t)n * 3 * sizeof(unsigned long long), st));
-    launch_lsd_grad_gray(s->lsd, s->rt, n, d_gray, s->d_raddr, s->d_rdeg, s->d_rmod, s->d_rcs, s->d_rsn, s->d_nrec, s->d_maxgrad, s->max_nsx, s->max_nsy,
-                         s->d_tile_list, s->d_tile_count, s->d_laddr, s->d_lmod, s->d_nlow, st);
-    launch_lsd_order(s->lsd, n, s->d_raddr, s->d_rdeg, s->d_rmod, s->d_rcs, s->d_rsn, s->d_nrec, s->d_maxgrad, s->d_sort_a, s->d_sort_b, s->d_order_a, s->d_order_b,
-                     s->d_norder, s->d_cxy, s->d_cdeg, s->d_cmod, s->d_ccs, s->d_csn, s->d_row_start, st);
-    if (s->cfg.lsd_seed_order == LF_LSD_SEED_OPENCV32)
-        launch_lsd_seed32(s->lsd, n, s->d_nrec, s->d_norder, s->d_overflow + 5, s->d_maxgrad, s->d_cxy, s->d_cmod, s->d_laddr, s->d_lmod, s->d_nlow, s->d_sort_a, s->d_sort_b, s->d_order_a, s->d_order_b, 1, st);
-    // dense problems: the labelling tables at their largest (a gray level has tens of thousands of defined pixels)
-    launch_lsd_label(s->lsd, n, s->d_norder, s->d_cxy, s->d_row_start, s->d_clabel, s->d_comp_list, s->d_comp_count, s->d_comp_key, s->d_reg, st);
-    launch_lsd_grow(s->lsd, n, s->d_order_a, s->d_norder, s->d_cxy, s->d_cdeg, s->d_cmod, s->d_ccs, s->d_csn, s->d_row_start,
-                    s->d_clabel, s->d_comp_list, s->d_comp_count, kCompCap, s->d_reg, s->d_gused, s->d_tmp_lines, s->d_tmp_tags,
-                    s->d_slot_lines, s->d_counts, nullptr, s->d_pend_rec, s->d_pend_tag, s->d_pend_count, kGrowLdsKb[2], true, h->env_bitmap, st);
+    hipStream_t st = h->stream;
+    LF_HIP_CHECK(h, hipMemsetAsync(lv.lsd.d_maxgrad, 0, (size_t)n * 3 * sizeof(unsigned long long), st));
+    lv.lsd.grad_gray(n, d_gray, st);
+    lv.lsd.order(n, 1, st);
+    lv.lsd.label(n, false, st);
+    lv.lsd.grow(n, lv.lines, lv.counts, kGrowLdsKb[2], true, false, st);
     LF_HIP_CHECK(h, hipGetLastError());
     return LF_OK;
 }
@@ -251,11 +237,9 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
     const uint8_t* level = gray0;
     for (int o = 0; o < n_octaves; ++o) {
         if (W < 16 || Hh < 16) { lf_set_error(h, LF_ERR_UNSUPPORTED, "LSD KeyLines: level %d would be %dx%d", o, W, Hh); return LF_ERR_UNSUPPORTED; }
-        k->H[o] = Hh; k->W[o] = W;
-        lf_handle* sub = nullptr;
-        if ((rc = lsdkl_sub(h, k, o, Hh, W, opts, &sub)) != LF_OK) return rc;
-        if ((rc = lsdkl_run_level(h, sub, level, n_frames)) != LF_OK) return rc;
-        L.lines[o] = sub->d_slot_lines; L.counts[o] = sub->d_counts; L.H[o] = Hh; L.W[o] = W;
+        LsdKlLevel& lv = k->level[o];
+        if ((rc = lsdkl_level(h, lv, Hh, W, opts)) != LF_OK || (rc = lsdkl_run_level(h, lv, level, n_frames)) != LF_OK) return rc;
+        L.lines[o] = lv.lines; L.counts[o] = lv.counts; L.H[o] = Hh; L.W[o] = W;
         if (o + 1 < n_octaves) {
             if ((rc = ensure(h, k->pyr[o + 1], B * (size_t)(W / 2) * (Hh / 2))) != LF_OK) return rc;
             launch_pyrdown(Hh, W, n_frames, level, static_cast<uint8_t*>(k->pyr[o + 1].p), s);
@@ -299,7 +283,7 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
     LF_HIP_CHECK(h, hipStreamSynchronize(s));
     for (int o = 0; o < n_octaves && !level_counts_bad; ++o) {
         std::vector<int> c((size_t)n_frames * 3);
-        LF_HIP_CHECK(h, hipMemcpy(c.data(), k->sub[o]->d_counts, c.size() * sizeof(int), hipMemcpyDeviceToHost));
+        LF_HIP_CHECK(h, hipMemcpy(c.data(), k->level[o].counts, c.size() * sizeof(int), hipMemcpyDeviceToHost));
         for (int f = 0; f < n_frames; ++f) if (c[3 * (size_t)f] > h->cap_lines) { level_counts_bad = c[3 * (size_t)f]; break; }
     }
     const int total = k->h_pinned[0];
