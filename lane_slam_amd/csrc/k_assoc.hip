@@ -357,12 +357,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     assoc_body_fp4<true>(q, qcolor, nq, mx, mcx, nm_bound, nm_dev, nm_pad, m_chunk, max_distance, part, done, idx, dist, tile, ctile, xtab, ttab, tie_pieces, tie_counts, tie_res);
 }
 
-__global__ void k_fill_u32(unsigned int* p, size_t n, unsigned int v)
-{
-    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
 __global__ void k_fill_nomatch(int n, int32_t* idx, float* dist)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;

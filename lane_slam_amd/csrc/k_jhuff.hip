@@ -19,8 +19,8 @@
 //                  state, never re-synchronises by itself -- DESIGN.md section 8).  Then the blocks completed per subsequence are
 //                  prefix-summed and a last decode writes the quantised coefficients (int16, natural order, dense 64 per
 //                  block; DC still as differences) and performs the checks of a sequential decoder: invalid code, run past
-//                  63, DC size > 11, reading beyond the interval, a restart interval of the wrong length.
-//   k_jh_dc        DC prediction: running sum per component over the blocks of a restart interval
+//                  63, DC size > 11, reading beyond the interval, a restart interval of the wrong length.  Last, DC
+//                  prediction: a running sum per component over the blocks of a restart interval.
 //   k_jpeg_idct_dense  dequantisation + the 13-bit integer inverse DCT of k_jpeg.hip on the dense blocks
 // Chroma upsampling and colour conversion are k_jpeg.hip's k_jpeg_color, unchanged.
 #include <cstdio>
@@ -717,61 +717,6 @@ __global__ __launch_bounds__(JH_TD) void k_jh_decode(jpeg::DevFrame* __restrict_
     }
 }
 
-// ---------------------------------------------------------------------------------------------- k_jh_dc
-// DC prediction (T.81 F.2.2.1): DIFF -> DC, per component, restarting at every interval.  One wave per frame walks the MCUs
-// 64 at a time; the blocks of a component inside an MCU chain serially (at most four).
-__global__ __launch_bounds__(64) void k_jh_dc(const jpeg::DevFrame* __restrict__ frames, int16_t* __restrict__ coef_all)
-{
-    const int f = blockIdx.x, lane = threadIdx.x;
-    const jpeg::DevFrame& F = frames[f];
-    if (!F.hdr.valid) return;
-    int16_t* coef = coef_all + (size_t)F.coef_base * 64;
-    const int n_mcu = F.n_mcu, bpm = F.bpm, luma = F.luma, R = F.restart > 0 ? F.restart : n_mcu;
-    const int ncomp = F.hdr.ncomp;
-    int carry[3] = { 0, 0, 0 };
-    for (int base = 0; base < n_mcu; base += 64) {
-        const int m = base + lane;
-        const bool act = m < n_mcu;
-        // sum of this MCU's differences per component
-        int sum[3] = { 0, 0, 0 };
-        if (act) {
-            for (int r = 0; r < bpm; ++r) {
-                const int c = r < luma ? 0 : r - luma + 1;
-                sum[c] += (int)coef[((size_t)m * bpm + r) * 64];
-            }
-        }
-        // segmented inclusive scan over the lanes: a lane whose MCU starts an interval does not take what is below it
-        const bool head = act && (m % R == 0);
-        int inc[3] = { sum[0], sum[1], sum[2] };
-        bool flag = head;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int a0 = __shfl_up(inc[0], d), a1 = __shfl_up(inc[1], d), a2 = __shfl_up(inc[2], d);
-            const bool fl = __shfl_up((int)flag, d) != 0;
-            if (lane >= d) {
-                if (!flag) { inc[0] += a0; inc[1] += a1; inc[2] += a2; }
-                flag = flag || fl;
-            }
-        }
-        // predictor before this MCU: the exclusive sum inside its interval, plus what the previous 64 MCUs carried over
-        // unless an interval starts at or below this lane in this group
-        int pred[3];
-        for (int c = 0; c < 3; ++c) pred[c] = inc[c] - sum[c] + (flag ? 0 : carry[c]);
-        if (act) {
-            for (int r = 0; r < bpm; ++r) {
-                const int c = r < luma ? 0 : r - luma + 1;
-                int16_t* p = coef + ((size_t)m * bpm + r) * 64;
-                pred[c] = (int)((unsigned)pred[c] + (unsigned)(int)*p);
-                *p = (int16_t)pred[c];
-            }
-        }
-        // carry = predictor after the last MCU of this group of 64
-        const int lastl = (n_mcu - base < 64 ? n_mcu - base : 64) - 1;
-        for (int c = 0; c < 3; ++c) carry[c] = __shfl(pred[c], lastl);
-        (void)ncomp;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------- dense IDCT
 namespace {
 __device__ __forceinline__ int32_t jd_mulw(int32_t a, int32_t c) { return (int32_t)((uint32_t)a * (uint32_t)c); }
@@ -881,7 +826,7 @@ void launch_jh_decode(const JpegGeom& g, int n_frames, int max_blocks, size_t ma
     }
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_jh_decode), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipLaunchKernelGGL(k_jh_decode, dim3(n_frames), dim3(JH_TD), (size_t)lds, s, frames, bytes, clean, seg_begin, I, sub, coef, status, dbg, lds, unstuff_here);
-    // (DC prediction happens at the end of k_jh_decode; k_jh_dc is the stand-alone form, kept for scans decoded elsewhere)
+    // (DC prediction happens at the end of k_jh_decode)
     if (max_blocks > 0) {
         const dim3 grid((unsigned)((max_blocks + kDBlocksPerWg - 1) / kDBlocksPerWg), (unsigned)n_frames);
         hipLaunchKernelGGL(k_jpeg_idct_dense, grid, dim3(256), 0, s, g, frames, coef, planes);

@@ -395,10 +395,9 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
         h->lsd.grad(n, h->d_strong, h->d_maskbits, true, s);
     }
     { StageTimer t(h, ST_LSD_ORDER); h->lsd.order(n, 0, s); }
-    static const bool no_rank = getenv("LF_DIAG_NO_RANK") != nullptr;
     {
         StageTimer t(h, ST_LSD_LABEL);          // (its own stage since round 6: two brackets of different content under one name made the average meaningless)
-        h->lsd.label(n, !no_rank, s);
+        h->lsd.label(n, true, s);
     }
     static const char* diag_skip = getenv("LF_DIAG_SKIP");     // diagnostic only (what-if timing, results are wrong): "grow"
     if (diag_skip && strstr(diag_skip, "grow")) LF_HIP_CHECK(h, hipMemsetAsync(h->d_counts, 0, (size_t)n * 3 * sizeof(int), s));
@@ -406,7 +405,7 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
         StageTimer t(h, ST_LSD_GROW);
         const LsdState& L = h->lsd;
         h->lsd.grow(n, h->d_slot_lines, h->d_counts, kGrowLdsKb[L.env_lds_level >= 0 ? L.env_lds_level : L.grow_lds_level],
-                    L.env_mixed >= 0 ? L.env_mixed != 0 : L.grow_mixed, !no_rank, s);
+                    L.env_mixed >= 0 ? L.env_mixed != 0 : L.grow_mixed, true, s);
     }
     LF_HIP_CHECK(h, hipGetLastError());
     h->last_frames = n;

@@ -83,8 +83,6 @@ struct LsdState {
     DevArray<int> d_row_start, d_norder, d_comp_count, d_comp_key, d_perm;
     DevArray<float> d_tmp_lines;                      // lines in completion order + their seed positions (k_lsd_grow)
     DevArray<int> d_tmp_tags;
-    DevArray<double> d_pend_rec;                      // pending regions (k_lsd_grow -> k_lsd_eval): 12 doubles each, their seed
-    DevArray<int> d_pend_tag, d_pend_count;           // positions, and how many per problem
     DevArray<uint8_t> d_zero; size_t zero_bytes = 0;  // d_maxgrad | d_nrec | d_nlow | d_tile_count | d_overflow: the counters a batch starts from zero, ONE memset (each memset is a dispatch of its own and waited 0.3 ms in a busy pipeline)
     unsigned long long* d_maxgrad = nullptr;
     int *d_nrec = nullptr, *d_nlow = nullptr, *d_tile_count = nullptr, *d_overflow = nullptr;      // (d_nlow: seed order OPENCV32 only)

@@ -135,9 +135,7 @@ int LsdState::init(lf_handle* h, int Hc, int W, const lf_lsd_options& o, int see
     if (dalloc(h, &d_tile_list, nprob * (size_t)(((Ws + 31) / 32) * ((Hs + 31) / 32))) ||
         dalloc(h, &d_gused, nprob * ((Ps + 31) / 32)) || dalloc(h, &d_row_start, nprob * (size_t)(Hs + 1)) ||
         dalloc(h, &d_comp_list, nprob * (size_t)kCompCap) || dalloc(h, &d_comp_count, nprob) || dalloc(h, &d_perm, nprob) || dalloc(h, &d_comp_key, nprob) ||
-        dalloc(h, &d_tmp_lines, cap * 4) || dalloc(h, &d_tmp_tags, cap) ||
-        dalloc(h, &d_pend_rec, nprob * (size_t)lsd_grow_pend_cap(L) * 12 + 2) || dalloc(h, &d_pend_tag, nprob * (size_t)lsd_grow_pend_cap(L) + 1) ||
-        dalloc(h, &d_pend_count, nprob) || dalloc(h, &d_norder, nprob))
+        dalloc(h, &d_tmp_lines, cap * 4) || dalloc(h, &d_tmp_tags, cap) || dalloc(h, &d_norder, nprob))
         return LF_ERR_HIP;
     // ---- the counter block, zeroed once here
     zero_bytes = nprob * 8 + nprob * 4 + nprob * 4 + 16 + 32;
@@ -251,8 +249,8 @@ void LsdState::label(int n, bool rank, hipStream_t s)
 void LsdState::grow(int n, float* lines, int* counts, int lds_kb, bool mixed, bool use_perm, hipStream_t s)
 {
     launch_lsd_grow(params, n, d_order_a, d_norder, d_cxy, d_cdeg, d_cmod, d_ccs, d_csn, d_row_start, d_clabel, d_comp_list, d_comp_count,
-                    kCompCap, d_reg, d_gused, d_tmp_lines, d_tmp_tags, lines, counts, use_perm ? d_perm : nullptr, d_pend_rec, d_pend_tag,
-                    d_pend_count, lds_kb, mixed, env_bitmap, s);
+                    kCompCap, d_reg, d_gused, d_tmp_lines, d_tmp_tags, lines, counts, use_perm ? d_perm : nullptr, lds_kb, mixed,
+                    env_bitmap, s);
 }
 
 }  // namespace lf

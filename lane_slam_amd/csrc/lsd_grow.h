@@ -160,26 +160,11 @@ struct Rect { double x1, y1, x2, y2, width, x, y, theta, dx, dy, prec, p; };
 // does not have to happen before the next region is grown: the growing wave pushes (rectangle, seed tag) into a small
 // ring in LDS and goes on to the next seed; waves of the workgroup that have run out of components pop and evaluate.
 // Lines carry their seed's tag, so the order in which they are emitted does not matter (k_lsd_grow.hip restores it).
-// Nobody ever waits on the ring: a push that finds it full (or the slot not yet copied out) evaluates in place, a pop
-// that finds it empty returns; the only spin is a consumer waiting for the handful of stores of the producer whose
-// ticket it has claimed.
+// A push that finds the ring full (or the slot not yet copied out) fails and the grower retries after a short sleep
+// (detect()), a pop that finds it empty returns; the only spin is a consumer waiting for the handful of stores of the
+// producer whose ticket it has claimed.
 #ifndef LFG_QN
 #define LFG_QN 16
-#endif
-// LFG_EVAL_KERNEL=1 (round 3, measured and NOT the default): the evaluation in a kernel of its own -- the growing waves
-// append (rectangle, tag) to the problem's PENDING list in HBM and k_lsd_eval (k_lsd_grow.hip), launched behind the
-// growing kernel, evaluates the list with every wave of its workgroup working, so no wave sits through a problem's
-// growth waiting for regions.  Same-call A/B on configs[1] (3 x 3 alternating runs): six batches in flight 139.7 k ->
-// 139.3 k frames/s (+-0: a fifth fewer wave-slot-cycles per problem buy nothing, i.e. the pipelined rate is NOT bound by
-// wave slots), one batch alone 2.77 -> 3.28 ms for growing + evaluation (the evaluation, 0.45 ms = its slowest wave's
-// eleven regions at ~100 k cycles each, no longer hides under the growth).  Kept as a build option.
-#ifndef LFG_EVAL_KERNEL
-#define LFG_EVAL_KERNEL 0
-#elif LFG_EVAL_KERNEL
-#error "LFG_EVAL_KERNEL=1 fails a parity test since round 4 (tools/experiments/README.md): not buildable until that is fixed"
-#endif
-#ifndef LFG_EVAL_QUEUE
-#define LFG_EVAL_QUEUE (LFG_EVAL_KERNEL ? 0 : 1)
 #endif
 struct EvalQueue {
     int tail, head;            // tickets reserved by producers / claimed by consumers
@@ -220,10 +205,6 @@ struct Ctx {
     int root;
     int* tags;                // seed position of every emitted line (HBM), or nullptr
     int* line_count;          // shared line counter (GPU: LDS, bumped atomically by the workgroup's waves)
-    double* pend_rec;         // HBM  pending list of the problem: 12 doubles per finished region (LFG_EVAL_KERNEL) ...
-    int* pend_tag;            // HBM  ... and its seed's position
-    int* pend_n;              // LDS  entries appended so far (may pass pend_cap: the evaluation kernel reports it)
-    int pend_cap;
 #if defined(LFG_STAMPS) && !defined(LF_HOST_SIM)
     mutable unsigned long long stamps[32];  // 0 seed scan, 1 grow, 2 rect, 3 refine, 4 nfa scan, 5 nfa math, 6 emit, 7 nfa calls/px,
                                             // 8 seed fetch, 9 regions, 10 region points, 11 grow batches
@@ -1446,7 +1427,8 @@ LFG_DEV bool evaluate_region(const Ctx& c, Rect& rec, int tag, float* lines, int
 #ifndef LF_HOST_SIM
     (void)n_lines;
     // lane 0 takes the slot, EVERY lane stores the (same) line: a function that ends in lane-0-only code is not safe at the end
-    // of a loop body (see evaluate_pending)
+    // of a loop body (the compiler once sent lanes 1..63 back to the loop header while lane 0 was still emitting, and the wave
+    // never came out again)
     int slot = 0;
     if (lane_id() == 0) slot = atomicAdd(c.line_count, 1);     // any order: the tags restore the sequential one
     slot = __builtin_amdgcn_readfirstlane(slot);
@@ -1470,36 +1452,6 @@ LFG_DEV bool evaluate_region(const Ctx& c, Rect& rec, int tag, float* lines, int
 }
 
 #ifndef LF_HOST_SIM
-// k_lsd_eval's form of evaluate_region: rect_improve and the final coordinates of one pending region, WITHOUT any
-// lane-dependent control flow -- every lane returns the same answer and the caller stores it from all lanes.  (A loop
-// whose body ends in `if (lane == 0) { emit }` is not safe: the compiler sent lanes 1..63 straight back to the loop
-// header with their own, never-assigned ticket while lane 0 was still emitting, and the wave never came out again.)
-LFG_DEV bool evaluate_pending(const Ctx& c, Rect& rec, float4& line)
-{
-    const double log_nfa = rect_improve(c, rec);
-    if (log_nfa <= c.log_eps) return false;
-    rec.x1 += 0.5; rec.y1 += 0.5; rec.x2 += 0.5; rec.y2 += 0.5;
-    if (c.scale != 1) {
-        rec.x1 /= c.scale; rec.y1 /= c.scale; rec.x2 /= c.scale; rec.y2 /= c.scale;
-    }
-    line = make_float4((float)rec.x1, (float)rec.y1, (float)rec.x2, (float)rec.y2);
-    return true;
-}
-
-// LFG_EVAL_KERNEL: one more entry of the problem's pending list (lane 0 stores; the rectangle is wave-uniform)
-LFG_DEV void eval_append(const Ctx& c, const Rect& rec, int tag)
-{
-    int slot = 0;
-    if (lane_id() == 0) slot = atomicAdd(c.pend_n, 1);
-    slot = __builtin_amdgcn_readfirstlane(slot);
-    if (slot < c.pend_cap) {                                   // every lane stores the same entry (no lane-0-only tail)
-        double2* d = reinterpret_cast<double2*>(c.pend_rec + (size_t)slot * 12);
-        d[0] = make_double2(rec.x1, rec.y1); d[1] = make_double2(rec.x2, rec.y2); d[2] = make_double2(rec.width, rec.x);
-        d[3] = make_double2(rec.y, rec.theta); d[4] = make_double2(rec.dx, rec.dy); d[5] = make_double2(rec.prec, rec.p);
-        c.pend_tag[slot] = tag;
-    }
-}
-
 LFG_DEV bool eval_push(const Ctx& c, const Rect& rec, int tag)
 {
     EvalQueue* q = c.q;
@@ -1648,11 +1600,7 @@ LFG_DEV int detect(const Ctx& c, const uint32_t* order, int n_order, float* line
         }
         LFG_T1(c, 3)
         if (rejected) continue;
-#if !defined(LF_HOST_SIM) && LFG_EVAL_KERNEL
-        // rect_improve and the emission happen in k_lsd_eval, from the problem's pending list
-        if (c.refine >= 2) { eval_append(c, rec, tag); continue; }
-        if (!evaluate_region<false>(c, rec, tag, lines, cap, n_lines)) { LFG_T1(c, 6) continue; }
-#elif !defined(LF_HOST_SIM) && LFG_EVAL_QUEUE
+#ifndef LF_HOST_SIM
         // rect_improve lives in ONE place, the helper loop of k_lsd_grow.hip (a second inlined copy here made the kernel
         // 71 KB of code against a 64 KB instruction cache): regions that need it always go through the ring.  The
         // workgroup's last wave never grows, so a full ring (sixteen regions waiting: the helper would have to fall
