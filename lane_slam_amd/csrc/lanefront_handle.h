@@ -37,24 +37,60 @@ struct JpegState {
     }
 };
 
+// A block of KeyLines on the device: lf_keylines' arrays and the frame of every KeyLine.  Staging of a host caller's block
+// (KlBatch::keylines), or the mask path's unmasked KeyLines (all).
+struct KlArrays {
+    DevBuf start_end, in_octave, angle, num_pixels, line_length, octave, class_id, response, size, pt, salience, desc, code, frame;
+    // the host block `out` on the device, for out.capacity KeyLines: an array out leaves NULL stays NULL, except in_octave, angle,
+    // num_pixels and octave, which LBD reads; desc and code only with describe.  dev->frame_offset is left to the caller.
+    int stage(lf_handle* h, const lf_keylines& out, bool describe, lf_keylines* dev);
+    // every array of a KlOut, frame included, for capacity KeyLines
+    int all(lf_handle* h, int capacity, KlOut* ko);
+    // the first n KeyLines and the n_frames + 1 offsets of the device block dev into the host block out; waits for the copies
+    static int copy_back(lf_handle* h, const lf_keylines& dev, const lf_keylines& out, int n, int n_frames);
+};
+
+// One batch of a KeyLine detector: KeyLines per frame, their offsets, the totals (KeyLines, overflow) and the frame of every KeyLine
+// on the device, the totals read back, and the staging of a host caller's images, masks and KeyLines.
+struct KlBatch {
+    DevBuf frame_count, frame_offset, totals, line_frame;
+    DevBuf gray, masks;             // a host caller's gray images / masks, max_frames working-size planes
+    KlArrays staged;                // a host caller's KeyLines
+    HostArray<int> h_pinned;        // totals [2], then (EDLines) the frame status [max_frames]
+    int alloc(lf_handle* h);        // all but line_frame (KlBatch::keylines) and the staging
+    // the batch's images on the device: the caller's, or a copy of a host caller's -- raw frames (input_kind 0) into h->d_frames,
+    // for the caller's k_pre; gray images (1) into `gray`
+    int images(lf_handle* h, const uint8_t* images, int n, int input_kind, int on_device, const uint8_t** d);
+    // n working-size planes of a host caller (gray images, masks) into buf
+    int upload(lf_handle* h, DevBuf& buf, const uint8_t* planes, int n, const uint8_t** d);
+    // the device block the kernels write for the caller's block out (line_frame sized for out.capacity): a host caller's staged,
+    // frame_offset here; a device caller's own, frame_offset here when it has none.  who names the entry point in errors.
+    int keylines(lf_handle* h, const char* who, const lf_keylines& out, int on_device, int describe, lf_keylines* dev);
+};
+
+// the argument checks both KeyLine batches start with (null arguments, n_frames, n_octaves, input_kind, max_frames, a batch in flight)
+int kl_batch_check(lf_handle* h, const char* who, const uint8_t* images, const lf_keylines* out, int n_frames, int n_octaves, int input_kind);
+KlOut kl_out(const lf_keylines& k, int32_t* frame);       // the kernels' view of a device block; frame: the frame of every KeyLine
+
+// one octave of the EDLines detector: its geometry, where k_ed_detect keeps its edge marks, its device arrays
+struct KlOctave {
+    int W = 0, H = 0, cap = 0, max_edges = 0, max_lines = 0;
+    bool marks_in_lds = false;
+    bool aflags_on = false;         // aflags holds this batch's anchor candidates (scan interval 2)
+    DevBuf src, blur, dxy, g, anchors, part, chain, sid, gmarks, counts, l_ep, l_c, l_dir, l_npx, l_sal, tl, rs_tab, ework;
+    DevBuf aflags;                  // the anchor candidate planes k_ed_grad writes (scan interval 2)
+};
+
 struct KlState {
-    int n_octaves = 0, max_frames = 0;
-    int W[LF_MAX_OCTAVES], H[LF_MAX_OCTAVES], cap[LF_MAX_OCTAVES], max_edges[LF_MAX_OCTAVES], max_lines[LF_MAX_OCTAVES];
-    DevBuf src[LF_MAX_OCTAVES], blur[LF_MAX_OCTAVES], dxy[LF_MAX_OCTAVES], g[LF_MAX_OCTAVES], anchors[LF_MAX_OCTAVES], part[LF_MAX_OCTAVES],
-           chain[LF_MAX_OCTAVES], sid[LF_MAX_OCTAVES], gmarks[LF_MAX_OCTAVES], counts[LF_MAX_OCTAVES], l_ep[LF_MAX_OCTAVES],
-           l_c[LF_MAX_OCTAVES], l_dir[LF_MAX_OCTAVES], l_npx[LF_MAX_OCTAVES], l_sal[LF_MAX_OCTAVES], tl[LF_MAX_OCTAVES], rs_tab[LF_MAX_OCTAVES], ework[LF_MAX_OCTAVES];
-    DevBuf frame_count, frame_offset, status, totals, line_frame, big;      // big: grouping tables of frames with more than 4096 lines
-    // the detect mask (round 5): the KeyLines are assembled into these, the kept ones move to the caller's arrays
-    DevBuf m_fo, m_totals, m_erased, m_kept, m_masks, t_start_end, t_in_octave, t_angle, t_npx, t_len, t_octave, t_class, t_response, t_size, t_pt, t_sal, t_frame;
-    DevBuf o_start_end, o_in_octave, o_angle, o_npx, o_len, o_octave, o_class, o_response, o_size, o_pt, o_sal, o_desc, o_code;
-    int out_capacity = 0;
-    DevBuf in_gray;                 // staging of host gray images
+    int n_octaves = 0;              // octaves the buffers are made for
+    KlOctave oct[LF_MAX_OCTAVES];
+    KlBatch batch;
+    DevBuf status, big;             // big: grouping tables of frames with more than 4096 lines
+    // the detect mask (round 5): the KeyLines are assembled into `unmasked`, the kept ones move to the caller's arrays
+    DevBuf m_fo, m_totals, m_erased, m_kept;
+    KlArrays unmasked;
     DevBuf any_tmp, any_blur;       // Params::ksize_ other than 5: the row sums (int32) and the blurred image of the octave at hand
     DevBuf d_frame, d_io, d_angle, d_npx, d_oct, d_desc, d_code, d_n;     // lf_describe_keylines staging
-    HostArray<int> h_pinned;        // totals [2], then frame status [max_frames]
-    bool marks_in_lds[LF_MAX_OCTAVES];
-    DevBuf aflags[LF_MAX_OCTAVES];  // the anchor candidate planes k_ed_grad writes (scan interval 2)
-    bool aflags_on[LF_MAX_OCTAVES] = {};
     size_t lds_bytes = 0;
     int last_octaves = 0, last_frames = 0;
 };
@@ -119,10 +155,7 @@ struct LsdKlLevel {
 struct LsdKlState {
     LsdKlLevel level[LF_MAX_OCTAVES];     // made on first use, remade for another geometry or other options
     DevBuf pyr[LF_MAX_OCTAVES];          // levels 1.. of the detect pyramid (level 0 is the caller's gray image)
-    DevBuf gray0, frame_count, frame_offset, line_frame, totals;
-    DevBuf o_start_end, o_in_octave, o_angle, o_npx, o_len, o_octave, o_class, o_response, o_size, o_pt, o_desc, o_code;
-    HostArray<int> h_pinned;
-    DevBuf masks;                                   // a host caller's masks on the device
+    KlBatch batch;                        // its own: lf_keylines_frame_status reads the EDLines batch's h_pinned
 };
 
 struct MatcherState {

@@ -192,35 +192,21 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
                      "sigma_scale > 0, quant >= 0, 0 < ang_th < 180, 0 <= density_th < 1)");
         return LF_ERR_BAD_ARG;
     }
-    if (!images || !out || n_frames < 1 || n_octaves < 1 || n_octaves > LF_MAX_OCTAVES || (input_kind != 0 && input_kind != 1)) {
-        lf_set_error(h, LF_ERR_BAD_ARG, "lf_lsd_keylines_batch: null argument, n_frames < 1, n_octaves outside 1..%d or bad input_kind", LF_MAX_OCTAVES);
-        return LF_ERR_BAD_ARG;
-    }
-    if (n_frames > h->max_frames) { lf_set_error(h, LF_ERR_CAPACITY, "n_frames %d exceeds max_frames %d", n_frames, h->max_frames); return LF_ERR_CAPACITY; }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    int rc;
+    if ((rc = kl_batch_check(h, "lf_lsd_keylines_batch", images, out, n_frames, n_octaves, input_kind)) != LF_OK) return rc;
     if (out->capacity < 1) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_lsd_keylines_batch: out->capacity < 1"); return LF_ERR_BAD_ARG; }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     if (!h->lsdkl) { h->lsdkl.reset(new (std::nothrow) LsdKlState()); if (!h->lsdkl) return LF_ERR_HIP; }
     LsdKlState* k = h->lsdkl.get();
+    KlBatch& b = k->batch;
     const size_t B = (size_t)h->max_frames;
-    int rc;
     // level 0: BGR2GRAY of the working image (k_pre), or the caller's gray images
     const uint8_t* gray0;
+    if ((rc = b.images(h, images, n_frames, input_kind, images_on_device, &gray0)) != LF_OK) return rc;
     if (input_kind == 0) {
-        const uint8_t* d_in = images;
-        if (!images_on_device) {
-            const size_t frame_bytes = (size_t)h->cfg.in_rows * h->cfg.in_cols * 3;
-            LF_HIP_CHECK(h, hipMemcpyAsync(h->d_frames, images, frame_bytes * n_frames, hipMemcpyHostToDevice, s));
-            d_in = h->d_frames;
-        }
-        launch_pre_gray(h->pre, d_in, n_frames, h->d_gray, s);
+        launch_pre_gray(h->pre, gray0, n_frames, h->d_gray, s);
         gray0 = h->d_gray;
-    } else if (images_on_device) gray0 = images;
-    else {
-        if ((rc = ensure(h, k->gray0, B * h->P)) != LF_OK) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(k->gray0.p, images, h->P * n_frames, hipMemcpyHostToDevice, s));
-        gray0 = static_cast<const uint8_t*>(k->gray0.p);
     }
     // the pyramid (:62-71): pyrDown to Size(cols / 2, rows / 2), no blur
     int W = h->W, Hh = h->Hc;
@@ -229,11 +215,8 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
     L.cap_lines = h->cap_lines;
     L.min_length = opts.min_length;
     L.mask_rows = h->Hc; L.mask_cols = h->W;
-    if (masks && !masks_on_device) {
-        if ((rc = ensure(h, k->masks, B * h->P)) != LF_OK) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(k->masks.p, masks, h->P * n_frames, hipMemcpyHostToDevice, s));
-        L.masks = static_cast<const uint8_t*>(k->masks.p);
-    } else L.masks = masks;
+    L.masks = masks;
+    if (masks && !masks_on_device && (rc = b.upload(h, b.masks, masks, n_frames, &L.masks)) != LF_OK) return rc;
     const uint8_t* level = gray0;
     for (int o = 0; o < n_octaves; ++o) {
         if (W < 16 || Hh < 16) { lf_set_error(h, LF_ERR_UNSUPPORTED, "LSD KeyLines: level %d would be %dx%d", o, W, Hh); return LF_ERR_UNSUPPORTED; }
@@ -248,36 +231,13 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
         W /= 2; Hh /= 2;
     }
     const int cap_out = out->capacity;
-    if ((rc = ensure(h, k->frame_count, B * 4)) || (rc = ensure(h, k->frame_offset, (B + 1) * 4)) || (rc = ensure(h, k->totals, 16)) ||
-        (rc = ensure(h, k->line_frame, (size_t)cap_out * 4))) return rc;
-    if (!k->h_pinned) LF_HIP_CHECK(h, k->h_pinned.alloc(4 * sizeof(int)));
-    lf_keylines dev = *out;
-    if (!out_on_device) {
-        const size_t c = (size_t)cap_out;
-        if ((rc = ensure(h, k->o_start_end, c * 16)) || (rc = ensure(h, k->o_in_octave, c * 16)) || (rc = ensure(h, k->o_angle, c * 4)) || (rc = ensure(h, k->o_npx, c * 4)) ||
-            (rc = ensure(h, k->o_len, c * 4)) || (rc = ensure(h, k->o_octave, c * 4)) || (rc = ensure(h, k->o_class, c * 4)) || (rc = ensure(h, k->o_response, c * 4)) ||
-            (rc = ensure(h, k->o_size, c * 4)) || (rc = ensure(h, k->o_pt, c * 8)) || (describe && ((rc = ensure(h, k->o_desc, c * 288)) || (rc = ensure(h, k->o_code, c * 32)))))
-            return rc;
-        dev.frame_offset = static_cast<int32_t*>(k->frame_offset.p);
-        dev.start_end = static_cast<float*>(k->o_start_end.p); dev.in_octave = static_cast<float*>(k->o_in_octave.p); dev.angle = static_cast<float*>(k->o_angle.p);
-        dev.num_pixels = static_cast<int32_t*>(k->o_npx.p); dev.line_length = static_cast<float*>(k->o_len.p); dev.octave = static_cast<int32_t*>(k->o_octave.p);
-        dev.class_id = static_cast<int32_t*>(k->o_class.p); dev.response = static_cast<float*>(k->o_response.p); dev.size = static_cast<float*>(k->o_size.p);
-        dev.pt = static_cast<float*>(k->o_pt.p); dev.salience = nullptr;
-        dev.desc = describe ? static_cast<float*>(k->o_desc.p) : nullptr; dev.code = describe ? static_cast<uint8_t*>(k->o_code.p) : nullptr;
-    } else if (describe && (!dev.in_octave || !dev.angle || !dev.num_pixels || !dev.octave)) {
-        lf_set_error(h, LF_ERR_BAD_ARG, "lf_lsd_keylines_batch: describe needs out->in_octave, angle, num_pixels and octave");
-        return LF_ERR_BAD_ARG;
-    }
-    int* d_fo = dev.frame_offset ? dev.frame_offset : static_cast<int*>(k->frame_offset.p);
-    hipLaunchKernelGGL(k_lsdkl_count, dim3(n_frames), dim3(64), 0, s, L, n_octaves, n_frames, static_cast<int*>(k->frame_count.p));
-    launch_kl_offsets(n_frames, static_cast<const int*>(k->frame_count.p), cap_out, d_fo, static_cast<int*>(k->totals.p), s);
-    KlOut ko;
-    ko.start_end = dev.start_end; ko.in_octave = dev.in_octave; ko.angle = dev.angle; ko.num_pixels = dev.num_pixels; ko.line_length = dev.line_length;
-    ko.octave = dev.octave; ko.class_id = dev.class_id; ko.response = dev.response; ko.size = dev.size; ko.pt = dev.pt; ko.salience = dev.salience;
-    ko.frame = static_cast<int32_t*>(k->line_frame.p);
-    hipLaunchKernelGGL(k_lsdkl_fill, dim3(n_frames), dim3(64), 0, s, L, n_octaves, d_fo, cap_out, ko);
+    lf_keylines dev;
+    if ((rc = b.alloc(h)) != LF_OK || (rc = b.keylines(h, "lf_lsd_keylines_batch", *out, out_on_device, describe, &dev)) != LF_OK) return rc;
+    hipLaunchKernelGGL(k_lsdkl_count, dim3(n_frames), dim3(64), 0, s, L, n_octaves, n_frames, static_cast<int*>(b.frame_count.p));
+    launch_kl_offsets(n_frames, static_cast<const int*>(b.frame_count.p), cap_out, dev.frame_offset, static_cast<int*>(b.totals.p), s);
+    hipLaunchKernelGGL(k_lsdkl_fill, dim3(n_frames), dim3(64), 0, s, L, n_octaves, dev.frame_offset, cap_out, kl_out(dev, static_cast<int32_t*>(b.line_frame.p)));
     LF_HIP_CHECK(h, hipGetLastError());
-    LF_HIP_CHECK(h, hipMemcpyAsync(k->h_pinned, k->totals.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(h, hipMemcpyAsync(b.h_pinned, b.totals.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     // a level whose LSD found more lines than max_lines_per_color: reported like the front end's own overflow
     int level_counts_bad = 0;
     LF_HIP_CHECK(h, hipStreamSynchronize(s));
@@ -286,25 +246,15 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
         LF_HIP_CHECK(h, hipMemcpy(c.data(), k->level[o].counts, c.size() * sizeof(int), hipMemcpyDeviceToHost));
         for (int f = 0; f < n_frames; ++f) if (c[3 * (size_t)f] > h->cap_lines) { level_counts_bad = c[3 * (size_t)f]; break; }
     }
-    const int total = k->h_pinned[0];
+    const int total = b.h_pinned[0];
     if (n_keylines) *n_keylines = total;
     if (level_counts_bad) { lf_set_error(h, LF_ERR_CAPACITY, "an LSD run on a pyramid level produced %d lines, max_lines_per_color is %d", level_counts_bad, h->cap_lines); return LF_ERR_CAPACITY; }
-    if (k->h_pinned[1]) { lf_set_error(h, LF_ERR_CAPACITY, "%d KeyLines exceed the output capacity %d", total, cap_out); return LF_ERR_CAPACITY; }
+    if (b.h_pinned[1]) { lf_set_error(h, LF_ERR_CAPACITY, "%d KeyLines exceed the output capacity %d", total, cap_out); return LF_ERR_CAPACITY; }
     if (describe && total > 0 && (dev.desc || dev.code)) {
         // BinaryDescriptor::compute on these KeyLines: its own (blurred) pyramid over the same gray image
-        if ((rc = lf_describe_keylines(h, gray0, n_frames, static_cast<const int32_t*>(k->line_frame.p), dev.in_octave, dev.angle, dev.num_pixels, dev.octave, total,
+        if ((rc = lf_describe_keylines(h, gray0, n_frames, static_cast<const int32_t*>(b.line_frame.p), dev.in_octave, dev.angle, dev.num_pixels, dev.octave, total,
                                        dev.desc, dev.code, 1)) != LF_OK) return rc;
     }
-    if (!out_on_device) {
-        const size_t n = (size_t)total;
-#define KL_COPY(field, bytes) if (out->field && dev.field && n) LF_HIP_CHECK(h, hipMemcpyAsync(out->field, dev.field, n * (bytes), hipMemcpyDeviceToHost, s))
-        if (out->frame_offset) LF_HIP_CHECK(h, hipMemcpyAsync(out->frame_offset, d_fo, (size_t)(n_frames + 1) * 4, hipMemcpyDeviceToHost, s));
-        KL_COPY(start_end, 16); KL_COPY(in_octave, 16); KL_COPY(angle, 4); KL_COPY(num_pixels, 4); KL_COPY(line_length, 4); KL_COPY(octave, 4);
-        KL_COPY(class_id, 4); KL_COPY(response, 4); KL_COPY(size, 4); KL_COPY(pt, 8);
-        if (describe) { KL_COPY(desc, 288); KL_COPY(code, 32); }
-#undef KL_COPY
-        if (out->salience && n) memset(out->salience, 0, n * 4);
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    }
-    return LF_OK;
+    return out_on_device ? LF_OK : KlArrays::copy_back(h, dev, *out, total, n_frames);
 }
+

@@ -367,6 +367,22 @@ class FrontEnd(object):
         fields, include/lanefront.h) + 'n', 'frame_offset' and 'frame_status'.
         masks: (n, rows, cols) u8 of the working size = detect's mask argument (:509-519): a KeyLine with both end points on zero
         pixels is erased, by the reference's loop as written (no step back after an erase: see include/lanefront.h)."""
+        def run(images, n, masks, s, total):
+            status = np.zeros(n, np.int32)
+            p = ctypes.byref(params) if params is not None else None
+            if masks is not None:
+                self._check(self.lib.lf_keylines_batch_masked(self.h, _ptr(images), n, 1 if gray else 0, 0, int(n_octaves), p, _ptr(masks), 0,
+                                                              ctypes.byref(s), 0, int(bool(describe)), ctypes.byref(total), _ptr(status)))
+            else:
+                self._check(self.lib.lf_keylines_batch(self.h, _ptr(images), n, 1 if gray else 0, 0, int(n_octaves), p, ctypes.byref(s), 0,
+                                                       int(bool(describe)), ctypes.byref(total), _ptr(status)))
+            return {"frame_status": status}
+        return self._keylines(images, gray, capacity, describe, masks, run)
+
+    def _keylines(self, images, gray, capacity, describe, masks, run):
+        """keylines_batch / lsd_keylines_batch: the shape checks of images and masks, the output arrays and their lf_keylines block;
+        run(images, n, masks, block, total) calls the entry point and returns more entries of the dict.  The arrays come back cut to
+        the KeyLine total."""
         images = np.ascontiguousarray(images, np.uint8)
         want = (self.rows, self.cols) if gray else (self.in_rows, self.in_cols, 3)
         if images.ndim == len(want):
@@ -374,6 +390,12 @@ class FrontEnd(object):
         if images.shape[1:] != want:
             raise ValueError("images must be (n,%s), got %r" % (",".join(map(str, want)), images.shape))
         n = images.shape[0]
+        if masks is not None:
+            masks = np.ascontiguousarray(masks, np.uint8)
+            if masks.ndim == 2:
+                masks = masks[None]
+            if masks.shape != (n, self.rows, self.cols):
+                raise ValueError("masks must be (%d,%d,%d), got %r" % (n, self.rows, self.cols, masks.shape))
         cap = int(capacity) if capacity else n * 2048
         out = {"frame_offset": np.zeros(n + 1, np.int32)}
         s = _lib.LfKeylines()
@@ -385,26 +407,13 @@ class FrontEnd(object):
             out[k] = np.zeros((cap, c) if c > 1 else cap, np.dtype(dt))
             setattr(s, k, out[k].ctypes.data)
         total = ctypes.c_int()
-        status = np.zeros(n, np.int32)
-        if masks is not None:
-            masks = np.ascontiguousarray(masks, np.uint8)
-            if masks.ndim == 2:
-                masks = masks[None]
-            if masks.shape != (n, self.rows, self.cols):
-                raise ValueError("masks must be (%d,%d,%d), got %r" % (n, self.rows, self.cols, masks.shape))
-            self._check(self.lib.lf_keylines_batch_masked(self.h, _ptr(images), n, 1 if gray else 0, 0, int(n_octaves),
-                                                          ctypes.byref(params) if params is not None else None, _ptr(masks), 0, ctypes.byref(s), 0,
-                                                          int(bool(describe)), ctypes.byref(total), _ptr(status)))
-        else:
-            self._check(self.lib.lf_keylines_batch(self.h, _ptr(images), n, 1 if gray else 0, 0, int(n_octaves),
-                                                   ctypes.byref(params) if params is not None else None, ctypes.byref(s), 0,
-                                                   int(bool(describe)), ctypes.byref(total), _ptr(status)))
+        more = run(images, n, masks, s, total)
         t = total.value
         for k, _, _ in _lib.KEYLINE_FIELDS:
             if k in out:
                 out[k] = out[k][:t]
         out["n"] = t
-        out["frame_status"] = status
+        out.update(more)
         return out
 
     def lsd_options(self, **kw):
@@ -424,40 +433,13 @@ class FrontEnd(object):
         options (lsd_options(...)): the fork's detect(..., LSDOptions, mask) / detectFast overloads (:218-438) -- the detector's
         parameters and the min_length filter; masks: (n, rows, cols) u8 of the working size -- KeyLines with both end points on zero
         mask pixels are erased (:203-213)."""
-        images = np.ascontiguousarray(images, np.uint8)
-        want = (self.rows, self.cols) if gray else (self.in_rows, self.in_cols, 3)
-        if images.ndim == len(want):
-            images = images[None]
-        if images.shape[1:] != want:
-            raise ValueError("images must be (n,%s), got %r" % (",".join(map(str, want)), images.shape))
-        n = images.shape[0]
-        cap = int(capacity) if capacity else n * 2048
-        out = {"frame_offset": np.zeros(n + 1, np.int32)}
-        s = _lib.LfKeylines()
-        s.capacity = cap
-        s.frame_offset = out["frame_offset"].ctypes.data
-        for k, dt, c in _lib.KEYLINE_FIELDS:
-            if k in ("desc", "code") and not describe:
-                continue
-            out[k] = np.zeros((cap, c) if c > 1 else cap, np.dtype(dt))
-            setattr(s, k, out[k].ctypes.data)
-        total = ctypes.c_int()
-        if masks is not None:
-            masks = np.ascontiguousarray(masks, np.uint8)
-            if masks.ndim == 2:
-                masks = masks[None]
-            if masks.shape != (n, self.rows, self.cols):
-                raise ValueError("masks must be (%d,%d,%d), got %r" % (n, self.rows, self.cols, masks.shape))
-        self._check(self.lib.lf_lsd_keylines_batch_ex(self.h, _ptr(images), n, 1 if gray else 0, 0, int(n_octaves),
-                                                      ctypes.byref(options) if options is not None else None,
-                                                      _ptr(masks) if masks is not None else None, 0, ctypes.byref(s), 0,
-                                                      int(bool(describe)), ctypes.byref(total)))
-        t = total.value
-        for k, _, _ in _lib.KEYLINE_FIELDS:
-            if k in out:
-                out[k] = out[k][:t]
-        out["n"] = t
-        return out
+        def run(images, n, masks, s, total):
+            self._check(self.lib.lf_lsd_keylines_batch_ex(self.h, _ptr(images), n, 1 if gray else 0, 0, int(n_octaves),
+                                                          ctypes.byref(options) if options is not None else None,
+                                                          _ptr(masks) if masks is not None else None, 0, ctypes.byref(s), 0,
+                                                          int(bool(describe)), ctypes.byref(total)))
+            return {}
+        return self._keylines(images, gray, capacity, describe, masks, run)
 
     def keylines_submit_device(self, images_ptr, n_frames, out_ptrs, capacity, n_octaves=1, describe=True, params=None, gray=False):
         """Queue lf_keylines_batch_async: images_ptr = device address of the frames ((n, in_rows, in_cols, 3) BGR, or with
