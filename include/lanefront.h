@@ -552,8 +552,9 @@ LF_API void lf_edlines_default_params(lf_edlines_params* p);
  *                     1 .. 21, else LF_ERR_UNSUPPORTED
  *   reduction_ratio   reductionRatio (2): computeGaussianPyramid (:366) asks pyrDown for Size(cols / r, rows / r), which cv::pyrDown
  *                     only accepts within 2 pixels of half the source -- i.e. r = 2; with any other value a compute over more than one
- *                     octave fails there (cv::Exception) and here (LF_ERR_UNSUPPORTED from lf_describe_keylines / the describe step of
- *                     lf_lsd_keylines_batch); one octave never reaches the call
+ *                     octave fails there (cv::Exception) and here (LF_ERR_UNSUPPORTED from lf_describe_keylines when a line names an
+ *                     octave above 0, host or device arrays alike, and from lf_lsd_keylines_batch[_ex] with describe and n_octaves > 1,
+ *                     before any work); one octave never reaches the call
  *   ksize             ksize_ (5): the Gaussian of OctaveKeyLines (:708) when lf_keylines_batch is given no lf_edlines_params (a params
  *                     block names its own ksize); odd, 1 .. 31
  * Params::read / write (:189-204: a cv::FileStorage node with numOfOctave_, widthOfBand_, reductionRatio; write adds numOfBand_ = 9)

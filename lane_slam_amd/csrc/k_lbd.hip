@@ -253,8 +253,8 @@ __global__ __launch_bounds__(256) void k_lbd(int Hc_, int W_, const int* __restr
     float direction;
     if (KL) {
         const int oc = kl_octave[seg];
-        // caller-supplied KeyLines (lf_describe_keylines with device arrays) are not validated on the host: a line that
-        // names a plane that was not built gets a zero descriptor instead of a wild read
+        // lf_describe_keylines checks every line's octave and frame on the host first, device arrays included; a line that
+        // still names a plane that was not built gets a zero descriptor instead of a wild read
         if (oc < 0 || oc >= LF_MAX_OCTAVES || planes.base[oc] == nullptr || f < 0 || f >= n_frames) {
             if (desc) for (int i = lane; i < 72; i += 64) desc[(size_t)seg * 72 + i] = 0.f;
             if (code && lane < 32) code[(size_t)seg * 32 + lane] = 0;

@@ -466,35 +466,46 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
         return LF_ERR_BAD_ARG;
     }
     if (n_frames > h->max_frames) { lf_set_error(h, LF_ERR_CAPACITY, "n_frames %d exceeds max_frames %d", n_frames, h->max_frames); return LF_ERR_CAPACITY; }
+    // the octave buffers re-ensured below are the ones a queued lf_keylines_batch_async reads
+    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
     if (n == 0) return LF_OK;
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     if (!h->kl) { h->kl.reset(new (std::nothrow) KlState()); if (!h->kl) return LF_ERR_HIP; }
     KlState* k = h->kl.get();
     int rc;
-    // the highest octave the lines name decides how much of the pyramid is built (:547-558); host arrays: look here,
-    // device arrays: build all LF_MAX_OCTAVES levels that exist
-    int max_oct = h->desc_params.reduction_ratio == 2 ? LF_MAX_OCTAVES - 1 : 0;      // (device arrays and a ratio pyrDown refuses: level 0 only; lines of other levels get zero descriptors)
     const size_t P0 = h->P, nn = (size_t)n;
+    // every line's octave and frame on the host, whatever side the arrays live on (8 bytes a line; the call synchronises at its end
+    // anyway): both sides check them alike and build the pyramid up to the highest octave named (:547-558), no further
+    const int32_t* h_oct = octave;
+    const int32_t* h_frame = line_frame;
+    std::vector<int32_t> staged;
+    if (on_device) {
+        staged.resize(2 * nn);
+        LF_HIP_CHECK(h, hipMemcpyAsync(staged.data(), octave, nn * 4, hipMemcpyDeviceToHost, s));
+        LF_HIP_CHECK(h, hipMemcpyAsync(staged.data() + nn, line_frame, nn * 4, hipMemcpyDeviceToHost, s));
+        LF_HIP_CHECK(h, hipStreamSynchronize(s));
+        h_oct = staged.data(); h_frame = staged.data() + nn;
+    }
+    int max_oct = 0;
+    for (int i = 0; i < n; ++i) {
+        if (h_oct[i] < 0 || h_oct[i] >= LF_MAX_OCTAVES || h_frame[i] < 0 || h_frame[i] >= n_frames) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_describe_keylines: line %d names octave %d / frame %d", i, h_oct[i], h_frame[i]); return LF_ERR_BAD_ARG; }
+        if (h_oct[i] > max_oct) max_oct = h_oct[i];
+    }
+    if (max_oct > 0 && h->desc_params.reduction_ratio != 2) {
+        // computeGaussianPyramid (:366): pyrDown(cur, cur, Size(cols / r, rows / r)) -- cv::pyrDown asserts |dst * 2 - src| <= 2
+        lf_set_error(h, LF_ERR_UNSUPPORTED, "lf_describe_keylines: reductionRatio %d: cv::pyrDown only takes a destination within 2 pixels of half the source (the reference raises cv::Exception here)", h->desc_params.reduction_ratio);
+        return LF_ERR_UNSUPPORTED;
+    }
     const uint8_t* d_gray = gray;
     const int32_t *d_frame = line_frame, *d_npx = num_pixels, *d_oct = octave;
     const float *d_io = in_octave4, *d_ang = angle;
     float* d_desc = desc72; uint8_t* d_code = code32;
     if (!on_device) {
-        max_oct = 0;
-        for (int i = 0; i < n; ++i) {
-            if (octave[i] < 0 || octave[i] >= LF_MAX_OCTAVES || line_frame[i] < 0 || line_frame[i] >= n_frames) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_describe_keylines: line %d names octave %d / frame %d", i, octave[i], line_frame[i]); return LF_ERR_BAD_ARG; }
-            if (octave[i] > max_oct) max_oct = octave[i];
-        }
         if ((rc = ensure(h, k->batch.gray, (size_t)h->max_frames * P0)) || (rc = ensure(h, k->d_frame, nn * 4)) || (rc = ensure(h, k->d_io, nn * 16)) ||
             (rc = ensure(h, k->d_angle, nn * 4)) || (rc = ensure(h, k->d_npx, nn * 4)) || (rc = ensure(h, k->d_oct, nn * 4)) ||
             (rc = ensure(h, k->d_desc, nn * 288)) || (rc = ensure(h, k->d_code, nn * 32)))
             return rc;
-        if (max_oct > 0 && h->desc_params.reduction_ratio != 2) {
-            // computeGaussianPyramid (:366): pyrDown(cur, cur, Size(cols / r, rows / r)) -- cv::pyrDown asserts |dst * 2 - src| <= 2
-            lf_set_error(h, LF_ERR_UNSUPPORTED, "lf_describe_keylines: reductionRatio %d: cv::pyrDown only takes a destination within 2 pixels of half the source (the reference raises cv::Exception here)", h->desc_params.reduction_ratio);
-            return LF_ERR_UNSUPPORTED;
-        }
         LF_HIP_CHECK(h, hipMemcpyAsync(k->batch.gray.p, gray, P0 * n_frames, hipMemcpyHostToDevice, s));
         LF_HIP_CHECK(h, hipMemcpyAsync(k->d_frame.p, line_frame, nn * 4, hipMemcpyHostToDevice, s));
         LF_HIP_CHECK(h, hipMemcpyAsync(k->d_io.p, in_octave4, nn * 16, hipMemcpyHostToDevice, s));
@@ -538,7 +549,8 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
             W /= 2; Hh /= 2;
         }
     }
-    if (!on_device) for (int i = 0; i < n; ++i) if (!pl.base[octave[i]]) { lf_set_error(h, LF_ERR_UNSUPPORTED, "lf_describe_keylines: octave %d of a %dx%d image is too small", octave[i], h->Hc, h->W); return LF_ERR_UNSUPPORTED; }
+    // (k_lbd writes zero descriptors for a line whose level was not built: the checks above keep every line off that path)
+    for (int i = 0; i < n; ++i) if (!pl.base[h_oct[i]]) { lf_set_error(h, LF_ERR_UNSUPPORTED, "lf_describe_keylines: octave %d of a %dx%d image is too small", h_oct[i], h->Hc, h->W); return LF_ERR_UNSUPPORTED; }
     {
         StageTimer t(h, ST_LBD);
         launch_lbd_keylines(pl, n, n_frames, static_cast<const int*>(k->d_n.p), d_io, d_ang, d_npx, d_oct, d_frame, h->d_gauss_g, h->d_gauss_l, d_desc, d_code, s,

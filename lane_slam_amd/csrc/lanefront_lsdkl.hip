@@ -195,6 +195,12 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
     int rc;
     if ((rc = kl_batch_check(h, "lf_lsd_keylines_batch", images, out, n_frames, n_octaves, input_kind)) != LF_OK) return rc;
     if (out->capacity < 1) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_lsd_keylines_batch: out->capacity < 1"); return LF_ERR_BAD_ARG; }
+    if (describe && n_octaves > 1 && h->desc_params.reduction_ratio != 2) {
+        // compute's pyramid over the octaves the KeyLines may name: computeGaussianPyramid's pyrDown refuses (lf_describe_keylines)
+        lf_set_error(h, LF_ERR_UNSUPPORTED, "lf_lsd_keylines_batch: describe over %d octaves with reductionRatio %d: cv::pyrDown only takes a destination "
+                     "within 2 pixels of half the source (the reference raises cv::Exception here)", n_octaves, h->desc_params.reduction_ratio);
+        return LF_ERR_UNSUPPORTED;
+    }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     if (!h->lsdkl) { h->lsdkl.reset(new (std::nothrow) LsdKlState()); if (!h->lsdkl) return LF_ERR_HIP; }

@@ -2,11 +2,16 @@
 ref: src/line_descriptor/src/binary_descriptor_custom.cpp:134-176), ksize_ (the Gaussian of OctaveKeyLines, :708), reductionRatio
 (computeGaussianPyramid, :366), and LSDOptions.n_bins above 1024 (descriptor_custom.hpp:906-916) -- every one against the oracle's
 composition, which restates the same statements with the same parameter."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
-from lane_slam_amd import FrontEnd, LanefrontError, default_config, synth
-from oracle import oracle as O
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import handle_calls as HC  # noqa: E402
+from lane_slam_amd import FrontEnd, LanefrontError, default_config, synth  # noqa: E402
+from oracle import oracle as O  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -145,3 +150,55 @@ def test_lsd_options_n_bins_above_1024(seed_order):
     with pytest.raises(LanefrontError):
         k.lsd_keylines_batch(gray, 1, gray=True, options=k.lsd_options(n_bins=4097))
     k.close()
+
+
+def test_reduction_ratio_other_than_two_on_the_lsd_keylines_and_device_paths(band_width):
+    """reductionRatio 3 where the KeyLines reach compute without a host array in between: lf_lsd_keylines_batch with describe over more than
+    one octave hands its device arrays to lf_describe_keylines and fails before any work (LF_ERR_UNSUPPORTED, never zero descriptors);
+    one octave, or no descriptors, still give the oracle's KeyLines.  lf_describe_keylines with device arrays returns what the host call
+    returns for the same lines: the ratio, a level too small to build, an octave or a frame out of range."""
+    cfg = default_config("parity")
+    frames = synth.make_batch(2, seed0=95)
+    fe = FrontEnd(cfg, max_frames=2, max_lines_per_color=1024)
+    o = O.Oracle(cfg)
+    gray = np.stack([o.bgr2gray(o.preprocess(f)) for f in frames])
+    seed_order = cfg["lsd"]["seed_order"]
+    fe.set_descriptor_params(reduction_ratio=3)
+    with pytest.raises(LanefrontError) as e:
+        fe.lsd_keylines_batch(gray, 2, describe=True, gray=True)
+    assert e.value.code == HC.LF_ERR_UNSUPPORTED
+    for n_octaves, describe in ((1, True), (2, False)):
+        got = HC.run_keylines(fe, "lsd", gray, n_octaves, gray=True, describe=describe)
+        seen = 0
+        for f in range(2):
+            r = O.lsd_octave_keylines(gray[f], n_octaves, describe=describe, seed_order=seed_order)
+            a, b = int(got["frame_offset"][f]), int(got["frame_offset"][f + 1])
+            assert b - a == r["n"], (n_octaves, f, b - a, r["n"])
+            for name in KL_FIELDS + (("code", "desc") if describe else ()):
+                assert np.array_equal(got[name][a:b], r[name]), (n_octaves, f, name)
+            seen += r["n"]
+        assert seen > 5 and (n_octaves == 1 or (got["octave"] > 0).any())
+    # the same lines through both sides of lf_describe_keylines: the same return code, the same descriptors
+    r = O.octave_keylines(gray[1], 2)
+    assert (r["octave"] > 0).any() and (r["octave"] == 0).any()
+    fr = np.ones(r["n"], np.int32)
+    lines = (fr, r["in_octave"], r["angle"], r["num_pixels"], r["octave"])
+    one = r["octave"] == 0
+    for ratio, sel, octave, frame, want_rc in ((3, one, None, None, 0), (3, slice(None), None, None, HC.LF_ERR_UNSUPPORTED),
+                                               (2, slice(None), None, None, 0), (2, slice(None), 4, None, HC.LF_ERR_UNSUPPORTED),
+                                               (2, slice(None), 5, None, HC.LF_ERR_BAD_ARG), (2, slice(None), -1, None, HC.LF_ERR_BAD_ARG),
+                                               (2, slice(None), None, 2, HC.LF_ERR_BAD_ARG)):
+        fe.set_descriptor_params(reduction_ratio=ratio)
+        ls = [np.array(a[sel]) for a in lines]
+        if octave is not None:
+            ls[4][-1] = octave                           # (octave 4 of an 80 x 160 image is 5 x 10: too small for compute's pyramid)
+        if frame is not None:
+            ls[0][0] = frame
+        rh, dh, ch = HC.describe_host(fe, gray, *ls)
+        rd, dd, cd = HC.describe_device(fe, gray, *ls)
+        assert rh == rd == want_rc, (ratio, octave, frame, rh, rd)
+        if want_rc == 0:
+            wd, wc = O.describe_keylines(gray[1], ls[1], ls[2], ls[3], ls[4])
+            assert np.array_equal(ch, wc) and np.array_equal(cd, wc) and np.array_equal(dd, dh), (ratio, octave)
+            assert np.abs(dd - wd).max() <= 1e-4
+    fe.close()
