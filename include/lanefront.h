@@ -39,7 +39,8 @@ extern "C" {
 #endif
 
 #define LF_ABI_VERSION 5   /* 2: JPEG ingest, SegmentList glue, LF_ERR_DECODE, 13 timing stages; 3: live map (lf_map_*); 4: EDLines / KeyLines, block overflow marker; 5: lf_config.lsd_seed_order, tie rules.
-                              Still 5 with the histogram lane filter (lf_lane_filter_*): purely additive, no existing declaration changed */
+                              Still 5 with the histogram lane filter (lf_lane_filter_*) and the anti-instagram estimate (lf_ai_transform_batch,
+                              lf_set_ai_transform, lf_get_ai_transform): purely additive, no existing declaration changed */
 
 typedef enum lf_status {
     LF_OK = 0,
@@ -310,6 +311,42 @@ LF_API int lf_matcher_radius_match(lf_handle* h, const uint8_t* query32, int nq,
  * cluster stays empty (fewer distinct samples than clusters); LF_ERR_UNSUPPORTED for n > 2^24 points. */
 LF_API int lf_kmeans(lf_handle* h, const uint8_t* bgr_points, int n, int on_device, int k, const double* init_centers, int max_iter,
               double tol, double* centers_out, long long* counts_out, double* inertia_out, int* n_iter_out);
+
+/* Anti-instagram colour transform, batched.  Replaces
+ *   anti_instagram/AntiInstagram.py:7-50  calculate_transform(image) -> (success, health, {scale, shift})
+ * for each of n_frames BGR u8 frames [n_frames][rows][cols][3] (host, or any device address with frames_on_device = 1, such as
+ * lf_frames_buffer after a GPU JPEG decode).  Per frame: the two k-means fits of runKMeans on the last min(rows, 100) rows
+ * (4 colours from CENTERS2, 3 from CENTERS; exactly lf_kmeans on the reference's column-major point order, bit for bit), the
+ * 3- / 4-colour decision (score3 + 3e7 > score4; the 4-colour fit without its red cluster), then getparameters2's weighted
+ * least-squares fit of the 15 x 6 system for p = (a0, b0, a1, b1, a2, b2) (channel c = BGR column c), in f64 by Householder QR;
+ * cost = its residual sum of squares, + 1e6 when any a_c < 0; success = (a0 != 0); health = 1 / (cost + DBL_EPSILON).
+ *
+ * Channel order quirk, reproduced: getparameters2 returns its tuples as (ch0, ch2, ch1) and calculate_transform unpacks them as
+ * r, g, b, so scale = (a0, a2, a1) and shift = (b0, b2, b1): applied in B, G, R order (scaleandshift2, k_pre), the G and R
+ * corrections are swapped.  The node publishes shift || scale only when health > 0.001 (anti_instagram_node.py:110-122).
+ *
+ * out[f].status is LF_OK, or LF_ERR_BAD_ARG when a fit ends with an empty cluster, as lf_kmeans reports it (the empty-cluster
+ * re-seed fills every cluster unless the strip has fewer points than clusters); the other frames are unaffected.  Returns
+ * LF_ERR_UNSUPPORTED for strips above 2^24 points.  Blocking; refused while a batch is in flight. */
+typedef struct lf_ai_transform {
+    int32_t status;              /* LF_OK or LF_ERR_BAD_ARG (a fit kept an empty cluster: nothing else of the frame is set) */
+    int32_t success;             /* a0 != 0 */
+    int32_t n_colors;            /* 3 or 4: the fit the transform came from */
+    int32_t n_iter3, n_iter4;    /* Lloyd iterations of the 3- and 4-colour fits */
+    int32_t reserved;
+    double scale[3], shift[3];   /* the reference's order: (a0, a2, a1), (b0, b2, b1) */
+    double cost, health;
+    double score3, score4;       /* -inertia of both fits */
+    double centers[3][3];        /* the chosen fit's centres (4 colours: rows 0, 2, 3) */
+    int64_t counts[3];           /* and their member counts */
+} lf_ai_transform;
+LF_API int lf_ai_transform_batch(lf_handle* h, const uint8_t* frames, int n_frames, int frames_on_device, int rows, int cols,
+                                 lf_ai_transform* out);
+/* The colour correction k_pre applies (lf_config.ai_scale / ai_shift, B, G, R order) on a live handle: each value is rounded to
+ * float, as scaleandshift2 does; later batches and lf_set_image calls use it.  Refused while a batch is in flight.  To follow the
+ * reference's node, pass scale = s[3:6] and shift = s[0:3] of its AntiInstagramTransform message (line_detector_node.py:112-114). */
+LF_API int lf_set_ai_transform(lf_handle* h, const double scale[3], const double shift[3]);
+LF_API int lf_get_ai_transform(const lf_handle* h, double scale[3], double shift[3]);
 
 /* ---- live map + associator (SURVEY a-11, 8f-3) ------------------------------------------------
  * What the package offers in place of the reference's line_associator node, which is an unfinished stub

@@ -35,6 +35,7 @@ EXPORTS = (
     "lf_lane_filter_synchronize", "lf_lane_filter_set_profiling", "lf_lane_filter_get_timing", "lf_lane_filter_stage_name",
     "lf_hough_default_params", "lf_set_hough_params", "lf_get_hough_params",
     "lf_dense_default_params", "lf_set_dense_params", "lf_get_dense_params",
+    "lf_ai_transform_batch", "lf_set_ai_transform", "lf_get_ai_transform",
 )
 LF_LANE_FILTER_PREDICT, LF_LANE_FILTER_UPDATE = 1, 2
 LF_LANE_FILTER_MAX_CELLS = 4096
@@ -76,6 +77,14 @@ class LfHoughParams(ctypes.Structure):
 class LfDenseParams(ctypes.Structure):
     """ctypes mirror of `lf_dense_params` (include/lanefront.h)."""
     _fields_ = [("sobel_threshold", ctypes.c_double)]
+
+
+class LfAiTransform(ctypes.Structure):
+    """ctypes mirror of `lf_ai_transform` (include/lanefront.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("success", ctypes.c_int32), ("n_colors", ctypes.c_int32), ("n_iter3", ctypes.c_int32),
+                ("n_iter4", ctypes.c_int32), ("reserved", ctypes.c_int32), ("scale", ctypes.c_double * 3), ("shift", ctypes.c_double * 3),
+                ("cost", ctypes.c_double), ("health", ctypes.c_double), ("score3", ctypes.c_double), ("score4", ctypes.c_double),
+                ("centers", ctypes.c_double * 9), ("counts", ctypes.c_int64 * 3)]
 
 
 class LfDescriptorParams(ctypes.Structure):
@@ -154,6 +163,9 @@ def load():
     lib.lf_associate.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci]
     lib.lf_associate_float.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci]
     lib.lf_kmeans.argtypes = [vp, vp, ci, ci, ci, vp, ci, ctypes.c_double, vp, vp, vp, vp]
+    lib.lf_ai_transform_batch.argtypes = [vp, vp, ci, ci, ci, ci, vp]
+    lib.lf_set_ai_transform.argtypes = [vp, vp, vp]
+    lib.lf_get_ai_transform.argtypes = [vp, vp, vp]
     lib.lf_jpeg_decode_batch.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t), ci, ci, ci, vp, ci, ci,
                                          ctypes.POINTER(ci)]
     lib.lf_jpeg_decode_batch.restype = ci
@@ -309,7 +321,7 @@ def load():
               "lf_map_pack_block", "lf_map_update", "lf_map_step", "lf_map_fetch"):
         getattr(lib, f).restype = ci
     for f in ("lf_synchronize", "lf_set_image", "lf_detect_lines", "lf_process_batch", "lf_process_batch_async", "lf_wait", "lf_associate",
-              "lf_associate_float", "lf_kmeans", "lf_jpeg_decode_batch", "lf_jpeg_info", "lf_frames_buffer", "lf_serialize_segments", "lf_deserialize_segments",
+              "lf_associate_float", "lf_kmeans", "lf_ai_transform_batch", "lf_set_ai_transform", "lf_get_ai_transform", "lf_jpeg_decode_batch", "lf_jpeg_info", "lf_frames_buffer", "lf_serialize_segments", "lf_deserialize_segments",
     "lf_debug_fetch", "lf_debug_detmath", "lf_debug_lsd_binary", "lf_lsd_size", "lf_set_profiling", "lf_get_timing",
               "lf_reset_timing"):
         getattr(lib, f).restype = ci

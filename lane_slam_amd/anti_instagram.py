@@ -1,8 +1,11 @@
-"""Host-side mirror of the reference's anti_instagram k-means entry points (k-means part).
+"""Host-side mirror of the reference's anti_instagram library.
 
-Reference: /root/reference/src/anti_instagram/include/anti_instagram/kmeans.py
-  CENTERS, CENTERS2 (:9-10), getimgdatapts (:14-19), runKMeans (:22-47).
-Same names, same arguments, same return values; the clustering itself runs on the GPU (lf_kmeans, k_kmeans.hip).
+Reference: /root/reference/src/anti_instagram/include/anti_instagram/
+  kmeans.py          CENTERS, CENTERS2 (:9-10), getimgdatapts (:14-19), runKMeans (:22-47)
+  AntiInstagram.py   calculate_transform (:7-50), AntiInstagram (:79-101)
+  scale_and_shift.py scaleandshift2 (:25-33)
+Same names, same arguments, same return values.  The clustering runs on the GPU (lf_kmeans, k_kmeans.hip) and so does the whole
+transform estimate (lf_ai_transform_batch, k_ai.hip: both k-means fits and the least-squares colour fit of every frame).
 """
 from collections import Counter
 
@@ -44,3 +47,55 @@ def runKMeans(cv_img, num_colors, init, frontend=None):
     for i in range(num_colors):
         labelcount[i] = int(counts[i])
     return centers, labelcount, -inertia
+
+
+def calculate_transform_batch(frames, frontend=None):
+    """calculate_transform for each frame of a [n, rows, cols, 3] u8 BGR batch in one lf_ai_transform_batch call.  Returns the
+    dict of FrontEnd.ai_transform_batch: success [n], health [n], scale [n, 3], shift [n, 3], ... (status -1: a fit kept an
+    empty cluster -- a strip of fewer points than clusters -- and the frame has no transform)."""
+    fe = frontend if frontend is not None else _frontend()
+    return fe.ai_transform_batch(frames)
+
+
+def calculate_transform(image, frontend=None):
+    """AntiInstagram.py:7-50.  Returns (success, health, {"scale": [3], "shift": [3]}), or (False, 0.0, None) as the reference
+    does when the fit's first scale is zero.  scale / shift come in the reference's order (its G and R entries are swapped
+    against B, G, R: include/lanefront.h, lf_ai_transform_batch)."""
+    r = calculate_transform_batch(np.asarray(image)[None], frontend)
+    if r["status"][0] != 0:
+        raise ValueError("calculate_transform: a k-means cluster stayed empty (fewer points than clusters)")
+    if not r["success"][0]:
+        return False, 0.0, None
+    return True, float(r["health"][0]), dict(scale=r["scale"][0].copy(), shift=r["shift"][0].copy())
+
+
+def scaleandshift2(img, scale, shift):
+    """scale_and_shift.py:25-33: a float32 image, img[..., i] * float32(scale[i]) + float32(shift[i])."""
+    out = np.zeros(img.shape, np.float32)
+    for i in range(3):
+        np.multiply(img[:, :, i], np.array(scale[i]).astype(np.float32), out=out[:, :, i])
+        out[:, :, i] += np.array(shift[i]).astype(np.float32)
+    return out
+
+
+class AntiInstagram(object):
+    """AntiInstagram.py:79-101 with the estimate on the GPU."""
+
+    def __init__(self, frontend=None):
+        self.scale = [1.0, 1.0, 1.0]
+        self.shift = [0.0, 0.0, 0.0]
+        self.health = 0
+        self._fe = frontend
+
+    def applyTransform(self, image):
+        return scaleandshift2(image, self.scale, self.shift)
+
+    def calculateTransform(self, image, testframe=False):
+        success, self.health, parameters = calculate_transform(image, self._fe)
+        if not success:
+            raise Exception('calculate_transform failed')
+        self.scale = parameters['scale']
+        self.shift = parameters['shift']
+
+    def calculateHealth(self):
+        return self.health

@@ -275,6 +275,10 @@ void launch_assoc_nomatch(int nq, int32_t* idx, float* dist, hipStream_t s);
 // ---- anti-instagram colour clustering (k_kmeans.hip)
 void launch_kmeans(const uint8_t* bgr, int n, int k, const double* init, int max_iter, double tol_rel, uint8_t* lab, double* out,
                    long long* counts, int* status, hipStream_t s);
+// ---- anti-instagram colour transform (k_ai.hip): strips [n_frames] at frame_stride bytes, S rows x cols; lab [2 n][S cols],
+//      fo [2 n][16] f64, fc [2 n][4], fs [2 n] scratch
+void launch_ai_transform(const uint8_t* strips, long long frame_stride, int n_frames, int S, int cols, uint8_t* lab, double* fo,
+                         long long* fc, int* fs, lf_ai_transform* out, hipStream_t s);
 // ---- live map (k_map.hip)
 struct MapDevice {
     int capacity, policy, kept_only, merge_distance, when_full;

@@ -212,6 +212,7 @@ struct lf_handle {
     // associator scratch (grown on demand)
     lf::DevBuf a_q, a_m, a_mx, a_best, a_idx, a_dist, a_qn, a_mn;
     lf::DevBuf km_pts, km_lab, km_f64, km_cnt;
+    lf::DevBuf ai_strip, ai_lab, ai_fit, ai_out;      // lf_ai_transform_batch: host strips, labels, per-fit results, per-frame results
     lf::DevBuf kn_hist, kn_count, kn_off, kn_total;       // radiusMatch scratch
     lf::AssocScratch a_ws;
     std::unique_ptr<lf::MatcherState> matcher;    // BinaryDescriptorMatcher's dataset (lanefront_matcher.hip)

@@ -334,6 +334,45 @@ class FrontEnd(object):
                                         _ptr(counts), ctypes.byref(inertia), ctypes.byref(n_iter)))
         return centers, counts, inertia.value, n_iter.value
 
+    def ai_transform_batch(self, frames, n_frames=None, rows=None, cols=None):
+        """anti_instagram's calculate_transform (AntiInstagram.py:7-50) for every frame: lf_ai_transform_batch.  frames: a
+        [n, rows, cols, 3] u8 BGR array, or a device address (int, e.g. frames_buffer()[0] after decode_jpeg_batch_async) with
+        n_frames, rows and cols given.  Returns a dict of arrays: status (0, or -1 where a fit kept an empty cluster), success,
+        n_colors, n_iter3, n_iter4, scale [n, 3], shift [n, 3] (the reference's channel order), cost, health, score3, score4,
+        centers [n, 3, 3] and counts [n, 3] of the chosen fit."""
+        if isinstance(frames, int):
+            if n_frames is None or rows is None or cols is None:
+                raise ValueError("a device address needs n_frames, rows and cols")
+            ptr, on_dev, n, r, c = ctypes.c_void_p(frames), 1, int(n_frames), int(rows), int(cols)
+        else:
+            fr = np.ascontiguousarray(frames, np.uint8)
+            if fr.ndim == 3:
+                fr = fr[None]
+            if fr.ndim != 4 or fr.shape[3] != 3:
+                raise ValueError("frames must be [n, rows, cols, 3] u8 BGR")
+            ptr, on_dev, (n, r, c) = _ptr(fr), 0, fr.shape[:3]
+        out = (_lib.LfAiTransform * max(n, 1))()
+        self._check(self.lib.lf_ai_transform_batch(self.h, ptr, n, on_dev, r, c, out))
+        res = np.ctypeslib.as_array(out)[:n]
+        return {"status": res["status"].copy(), "success": res["success"].astype(bool), "n_colors": res["n_colors"].copy(),
+                "n_iter3": res["n_iter3"].copy(), "n_iter4": res["n_iter4"].copy(), "scale": res["scale"].copy(),
+                "shift": res["shift"].copy(), "cost": res["cost"].copy(), "health": res["health"].copy(),
+                "score3": res["score3"].copy(), "score4": res["score4"].copy(), "centers": res["centers"].reshape(n, 3, 3).copy(),
+                "counts": res["counts"].copy()}
+
+    def set_ai_transform(self, scale, shift):
+        """The colour correction k_pre applies from now on (lf_config.ai_scale / ai_shift, B, G, R): lf_set_ai_transform.
+        Each value is rounded to float32, as the reference's scaleandshift2 does."""
+        sc = np.ascontiguousarray(scale, np.float64).reshape(3)
+        sh = np.ascontiguousarray(shift, np.float64).reshape(3)
+        self._check(self.lib.lf_set_ai_transform(self.h, _ptr(sc), _ptr(sh)))
+
+    def ai_transform(self):
+        """(scale [3], shift [3]) the handle applies now."""
+        sc, sh = np.zeros(3), np.zeros(3)
+        self._check(self.lib.lf_get_ai_transform(self.h, _ptr(sc), _ptr(sh)))
+        return sc, sh
+
     # ------------------------------------------------------------------ EDLines / multi-octave KeyLines (SURVEY 8f-4)
     def set_descriptor_params(self, num_of_octave=None, width_of_band=None, reduction_ratio=None, ksize=None):
         """BinaryDescriptor's setters (setNumOfOctaves / setWidthOfBand / setReductionRatio, Params::ksize_;
