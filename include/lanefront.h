@@ -40,7 +40,8 @@ extern "C" {
 
 #define LF_ABI_VERSION 5   /* 2: JPEG ingest, SegmentList glue, LF_ERR_DECODE, 13 timing stages; 3: live map (lf_map_*); 4: EDLines / KeyLines, block overflow marker; 5: lf_config.lsd_seed_order, tie rules.
                               Still 5 with the histogram lane filter (lf_lane_filter_*) and the anti-instagram estimate (lf_ai_transform_batch,
-                              lf_set_ai_transform, lf_get_ai_transform): purely additive, no existing declaration changed */
+                              lf_set_ai_transform, lf_get_ai_transform) and the overlay (lf_draw_lines, lf_draw_lines_image): purely additive, no existing
+                              declaration changed */
 
 typedef enum lf_status {
     LF_OK = 0,
@@ -754,6 +755,32 @@ LF_API int lf_serialize_segments(lf_handle* h, const lf_segments* segs, int segs
                           uint8_t* out, size_t out_capacity, int out_on_device, int64_t* frame_byte_offset);
 LF_API int lf_deserialize_segments(lf_handle* h, const uint8_t* bodies, int bodies_on_device, const int64_t* frame_byte_offset,
                             int n_frames, lf_segments* out, int out_on_device, int* n_segments);
+
+/* ---- image_with_lines: the line detector's overlay -------------------------------------------------
+ * What line_detector_node.py:221-231 publishes on ~image_with_lines_lsd for every frame: a copy of the corrected working image
+ * (image_cv_corr) with drawLines (line_detector_plot.py:12-19) applied to the white, yellow and red lines -- per line
+ * cv2.line(thickness 2, paint (0,0,0) / (255,0,0) / (0,255,0) for colour 0 / 1 / 2, BGR as written), cv2.circle(p1, 2, (0,255,0)),
+ * cv2.circle(p2, 2, (0,0,255)) -- in the block's row order (frame, then white, yellow, red, then detection order).  Every row is
+ * drawn, keep is not read.  Coordinates are the lines' values truncated toward zero (cv2's "ii" parsing of float32); the
+ * rasteriser is OpenCV 3.3.1's (drawing.cpp: ThickLine / FillConvexPoly / Line2 / Circle, LINE_8), restated, not pinned
+ * (DESIGN.md section 9h).  Output: u8 [n_frames][img_rows - top_cutoff][img_cols][3], step 3 * img_cols: the data of
+ * cv2_to_imgmsg(image, "bgr8").  Images and truncated coordinates must lie within +-4096 px (3.3.1's int arithmetic and later
+ * int64 agree there), colours <= 2: else LF_ERR_BAD_ARG -- checked before anything runs for host segments; device segments are
+ * checked on the device, the offending line is not drawn and the call reports LF_ERR_BAD_ARG when it waits for a host output (with
+ * a device output it returns at once and nothing is reported).  A frame whose JPEG failed to decode has a zero image and no
+ * lines: the reference publishes nothing for it, skip it by its status.
+ *
+ * lf_draw_lines: the overlay of the handle's LAST COMPLETED batch (lf_process_batch returned or lf_wait returned LF_OK -- after a
+ *   lf_wait that re-ran the batch with grown LSD lists, of the final run), any detector (lf_set_detector).  seg: frame_offset,
+ *   lines, color of that batch's block (host or device pointers, all alike; capacity 0 = unchecked).  n_frames: the first
+ *   n_frames frames of the batch.  Queued on the handle's stream (a following batch on the handle is ordered after it): with
+ *   device segments and a device output it returns at once; with a host output when the data is in place.  LF_ERR_BAD_ARG:
+ *   no completed batch, a batch in flight, n_frames < 1 or above the batch's, a NULL array, a colour above 2.
+ * lf_draw_lines_image: the same drawing on caller images bgr [n_frames][rows][cols][3] (host or device, as out_bgr; on the
+ *   device out_bgr may be bgr itself) with the caller's block: lines of any origin, colours interleaved as the rows say. */
+LF_API int lf_draw_lines(lf_handle* h, int n_frames, const lf_segments* seg, int seg_on_device, uint8_t* out_bgr, int out_on_device);
+LF_API int lf_draw_lines_image(lf_handle* h, const uint8_t* bgr, int n_frames, int rows, int cols, const lf_segments* seg, int seg_on_device,
+                               uint8_t* out_bgr, int images_on_device);
 
 /* ---- introspection for tests and the benchmark ---------------------------- */
 typedef enum lf_buffer_id {

@@ -36,6 +36,7 @@ EXPORTS = (
     "lf_hough_default_params", "lf_set_hough_params", "lf_get_hough_params",
     "lf_dense_default_params", "lf_set_dense_params", "lf_get_dense_params",
     "lf_ai_transform_batch", "lf_set_ai_transform", "lf_get_ai_transform",
+    "lf_draw_lines", "lf_draw_lines_image",
 )
 LF_LANE_FILTER_PREDICT, LF_LANE_FILTER_UPDATE = 1, 2
 LF_LANE_FILTER_MAX_CELLS = 4096
@@ -166,6 +167,8 @@ def load():
     lib.lf_ai_transform_batch.argtypes = [vp, vp, ci, ci, ci, ci, vp]
     lib.lf_set_ai_transform.argtypes = [vp, vp, vp]
     lib.lf_get_ai_transform.argtypes = [vp, vp, vp]
+    lib.lf_draw_lines.argtypes = [vp, ci, ctypes.POINTER(LfSegments), ci, vp, ci]
+    lib.lf_draw_lines_image.argtypes = [vp, vp, ci, ci, ci, ctypes.POINTER(LfSegments), ci, vp, ci]
     lib.lf_jpeg_decode_batch.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t), ci, ci, ci, vp, ci, ci,
                                          ctypes.POINTER(ci)]
     lib.lf_jpeg_decode_batch.restype = ci
@@ -321,7 +324,7 @@ def load():
               "lf_map_pack_block", "lf_map_update", "lf_map_step", "lf_map_fetch"):
         getattr(lib, f).restype = ci
     for f in ("lf_synchronize", "lf_set_image", "lf_detect_lines", "lf_process_batch", "lf_process_batch_async", "lf_wait", "lf_associate",
-              "lf_associate_float", "lf_kmeans", "lf_ai_transform_batch", "lf_set_ai_transform", "lf_get_ai_transform", "lf_jpeg_decode_batch", "lf_jpeg_info", "lf_frames_buffer", "lf_serialize_segments", "lf_deserialize_segments",
+              "lf_associate_float", "lf_kmeans", "lf_ai_transform_batch", "lf_set_ai_transform", "lf_get_ai_transform", "lf_draw_lines", "lf_draw_lines_image", "lf_jpeg_decode_batch", "lf_jpeg_info", "lf_frames_buffer", "lf_serialize_segments", "lf_deserialize_segments",
     "lf_debug_fetch", "lf_debug_detmath", "lf_debug_lsd_binary", "lf_lsd_size", "lf_set_profiling", "lf_get_timing",
               "lf_reset_timing"):
         getattr(lib, f).restype = ci

@@ -277,6 +277,9 @@ void launch_kmeans(const uint8_t* bgr, int n, int k, const double* init, int max
                    long long* counts, int* status, hipStream_t s);
 // ---- anti-instagram colour transform (k_ai.hip): strips [n_frames] at frame_stride bytes, S rows x cols; lab [2 n][S cols],
 //      fo [2 n][16] f64, fc [2 n][4], fs [2 n] scratch
+// image_with_lines (k_draw.hip): src is BGRX dwords (src_bgrx, the handle's d_bgr) or packed BGR (may equal out); out packed BGR
+void launch_draw(const void* src, bool src_bgrx, uint8_t* out, int n_frames, int Hc, int W, const int32_t* frame_offset, const float* lines,
+                 const uint8_t* color, int capacity, int* bad, hipStream_t s);
 void launch_ai_transform(const uint8_t* strips, long long frame_stride, int n_frames, int S, int cols, uint8_t* lab, double* fo,
                          long long* fc, int* fs, lf_ai_transform* out, hipStream_t s);
 // ---- live map (k_map.hip)

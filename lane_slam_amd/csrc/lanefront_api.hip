@@ -337,6 +337,7 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
     hipStream_t s = h->stream;
     if (h->lsd.lists_lost) { lf_set_error(h, LF_ERR_HIP, "the handle lost its LSD lists to an out-of-memory growth (lf_wait / lf_set_image reported it)"); return LF_ERR_HIP; }
     h->overflow_zeroed = false;          // (set at the successful END only: an error exit must not leave run_segments believing the overflow words are zero)
+    h->draw_frames = 0;                  // k_pre rewrites d_bgr: lf_draw_lines waits for the next completed batch
     PreParams pp = h->pre;
     if (from_working_image) {
         // plugin path: the caller already resized, cropped and colour-corrected (line_detector_node.py:163-180)
@@ -509,11 +510,13 @@ extern "C" int lf_wait(lf_handle* h, int* n_segments)
         LF_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     }
     h->detector_failures = h->detector == LF_DETECTOR_EDLINES ? h->h_pinned[5] : 0;
+    h->draw_frames = 0;
     const int total = h->h_pinned[8];
     if (n_segments) *n_segments = total;
     if (h->pending_problems > 0) h->lsd.adapt_slice(h->h_pinned[2], h->h_pinned[3], h->pending_problems);
     if (h->h_pinned[1]) { lf_set_error(h, LF_ERR_CAPACITY, "%s %s run produced more than max_lines_per_color=%d lines", h->detector == LF_DETECTOR_DENSE ? "a" : "an", detector_name(h->detector), h->cap_lines); return LF_ERR_CAPACITY; }
     if (total > h->pending_capacity) { lf_set_error(h, LF_ERR_CAPACITY, "%d segments exceed the output capacity %d", total, h->pending_capacity); return LF_ERR_CAPACITY; }
+    h->draw_frames = h->pend_n;          // d_bgr holds this batch's corrected images (lf_draw_lines)
     return LF_OK;
 }
 

@@ -213,6 +213,8 @@ struct lf_handle {
     lf::DevBuf a_q, a_m, a_mx, a_best, a_idx, a_dist, a_qn, a_mn;
     lf::DevBuf km_pts, km_lab, km_f64, km_cnt;
     lf::DevBuf ai_strip, ai_lab, ai_fit, ai_out;      // lf_ai_transform_batch: host strips, labels, per-fit results, per-frame results
+    lf::DevBuf dr_img, dr_fo, dr_lines, dr_color, dr_bad;   // lf_draw_lines*: staging of host images / segments, the bad-line flag
+    int draw_frames = 0;                  // frames of the last completed batch whose corrected images d_bgr holds (lf_draw_lines); 0: none
     lf::DevBuf kn_hist, kn_count, kn_off, kn_total;       // radiusMatch scratch
     lf::AssocScratch a_ws;
     std::unique_ptr<lf::MatcherState> matcher;    // BinaryDescriptorMatcher's dataset (lanefront_matcher.hip)

@@ -608,6 +608,7 @@ int lf::run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n)
     const lf_edlines_params& P = h->ed_params;
     int rc;
     if ((rc = kl_prepare(h, 1, P.scan_intervals)) != LF_OK) return rc;
+    h->draw_frames = 0;                  // d_bgr is rewritten (lf_draw_lines)
     { StageTimer t(h, ST_PRE); launch_pre(h->pre, d_frames, n, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s); }
     EdAll all;
     if ((rc = kl_run_octaves(h, h->d_gray, n, 1, P, all)) != LF_OK) return rc;
@@ -685,6 +686,7 @@ extern "C" int lf_set_image_edlines(lf_handle* h, const uint8_t* bgr, int rows, 
     pp.in_rows = h->Hc; pp.in_cols = h->W; pp.img_rows = h->Hc; pp.img_cols = h->W; pp.top_cutoff = 0; pp.resize = 0;
     for (int i = 0; i < 3; ++i) { pp.ai_scale[i] = 1.f; pp.ai_shift[i] = 0.f; }
     pp.identity_ai = 1;
+    h->draw_frames = 0;                  // d_bgr is rewritten (lf_draw_lines)
     { StageTimer t(h, ST_PRE); launch_pre(pp, h->d_frames, 1, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s); }
     EdAll all;
     if ((rc = kl_run_octaves(h, h->d_gray, 1, 1, P, all)) != LF_OK) return rc;

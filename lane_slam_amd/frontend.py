@@ -45,6 +45,17 @@ def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _draw_block(frame_offset, lines, colors):
+    """An LfSegments of host frame_offset / lines / color for lf_draw_lines*, and the arrays it points into."""
+    fo = np.ascontiguousarray(frame_offset, dtype=np.int32)
+    ln = np.ascontiguousarray(np.asarray(lines, dtype=np.float32).reshape(-1, 4))
+    co = np.ascontiguousarray(colors, dtype=np.uint8)
+    s = _lib.LfSegments()
+    s.capacity = min(ln.shape[0], co.shape[0])
+    s.frame_offset, s.lines, s.color = fo.ctypes.data, ln.ctypes.data, co.ctypes.data
+    return s, (fo, ln, co)
+
+
 class FrontEnd(object):
     def __init__(self, cfg=None, device=0, max_frames=1, max_lines_per_color=512):
         self.lib = _lib.load()
@@ -246,6 +257,49 @@ class FrontEnd(object):
         total = ctypes.c_int()
         self._check(self.lib.lf_wait(self.h, ctypes.byref(total)))
         return total.value
+
+    # ------------------------------------------------------------------ image_with_lines
+    def draw_lines(self, seg, n_frames=None):
+        """The overlay line_detector_node publishes on ~image_with_lines_lsd for the frames of the last completed batch: its
+        corrected working images with every line of `seg` (the host `Segments` that batch returned) drawn as drawLines draws it
+        (include/lanefront.h, lf_draw_lines).  Returns uint8 (n, rows, cols, 3) BGR."""
+        n = len(seg.frame_offset) - 1 if n_frames is None else int(n_frames)
+        out = np.empty((n, self.rows, self.cols, 3), np.uint8)
+        s, alive = _draw_block(seg.frame_offset, seg.lines, seg.color)
+        self._check(self.lib.lf_draw_lines(self.h, n, ctypes.byref(s), 0, _ptr(out), 0))
+        del alive
+        return out
+
+    def draw_lines_device(self, n_frames, seg_ptrs, out_ptr, capacity=0):
+        """Device form of draw_lines, beside submit_device / wait: seg_ptrs holds the device addresses of frame_offset, lines and
+        color (the out_ptrs given to submit_device), out_ptr a device buffer of n_frames x rows x cols x 3 bytes.  Queued on the
+        handle's stream; returns at once."""
+        s = _lib.LfSegments()
+        s.capacity = int(capacity)
+        for k in ("frame_offset", "lines", "color"):
+            setattr(s, k, int(seg_ptrs[k]))
+        self._check(self.lib.lf_draw_lines(self.h, int(n_frames), ctypes.byref(s), 1, ctypes.c_void_p(int(out_ptr)), 1))
+
+    def draw_lines_image(self, images, lines, colors, frame_offset):
+        """drawLines' drawing on caller images: images uint8 (n, rows, cols, 3) BGR, a block of lines (N, 4), colors (N,) and
+        frame_offset (n + 1,), drawn in row order.  Returns the drawn copy."""
+        images = np.ascontiguousarray(images, dtype=np.uint8)
+        n, rows, cols = images.shape[0], images.shape[1], images.shape[2]
+        out = np.empty_like(images)
+        s, alive = _draw_block(frame_offset, lines, colors)
+        self._check(self.lib.lf_draw_lines_image(self.h, _ptr(images), n, rows, cols, ctypes.byref(s), 0, _ptr(out), 0))
+        del alive
+        return out
+
+    def draw_lines_image_device(self, images_ptr, n_frames, rows, cols, seg_ptrs, out_ptr, capacity=0):
+        """draw_lines_image on device images and a device block (seg_ptrs as in draw_lines_device); out_ptr may equal images_ptr.
+        Queued on the handle's stream; returns at once."""
+        s = _lib.LfSegments()
+        s.capacity = int(capacity)
+        for k in ("frame_offset", "lines", "color"):
+            setattr(s, k, int(seg_ptrs[k]))
+        self._check(self.lib.lf_draw_lines_image(self.h, ctypes.c_void_p(int(images_ptr)), int(n_frames), int(rows), int(cols),
+                                                 ctypes.byref(s), 1, ctypes.c_void_p(int(out_ptr)), 1))
 
     # ------------------------------------------------------------------ association
     def set_tie_rule(self, rule):

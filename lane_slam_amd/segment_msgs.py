@@ -5,7 +5,8 @@ Message layout (ref: src/duckietown_msgs/msg/SegmentList.msg:1-2, Segment.msg:1-
 std_msgs/Header, geometry_msgs/Point; ROS 1 serialisation, little endian):
     Header   u32 seq | u32 stamp.secs | u32 stamp.nsecs | u32 len + frame_id bytes
     body     u32 count | count x 73-byte Segment records          <- lf_serialize_segments writes these
-The record as a packed numpy dtype is SEGMENT_DTYPE, so a subscriber can read a body with np.frombuffer."""
+The record as a packed numpy dtype is SEGMENT_DTYPE, so a subscriber can read a body with np.frombuffer.
+image_message serialises the node's second topic, ~image_with_lines (sensor_msgs/Image, bgr8), from FrontEnd.draw_lines."""
 import ctypes
 import struct
 
@@ -28,6 +29,19 @@ def header_bytes(seq, secs, nsecs, frame_id=""):
 def segment_list_message(header, body):
     """A complete serialised SegmentList: header_bytes(...) + one body from serialize_segments."""
     return bytes(header) + bytes(body)
+
+
+def image_message(header, bgr):
+    """The serialised sensor_msgs/Image that cv_bridge.cv2_to_imgmsg(bgr, "bgr8") fills (line_detector_node.py:229-230): header_bytes(...)
+    + u32 height | u32 width | string encoding "bgr8" | u8 is_bigendian 0 | u32 step = 3 * width | uint8[] data (u32 length + bytes).
+    bgr: one uint8 (rows, cols, 3) image, e.g. a frame of FrontEnd.draw_lines."""
+    img = np.ascontiguousarray(bgr, dtype=np.uint8)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("image_message: a (rows, cols, 3) bgr8 image, got %r" % (img.shape,))
+    rows, cols = img.shape[0], img.shape[1]
+    enc = b"bgr8"
+    return (bytes(header) + struct.pack("<III", rows, cols, len(enc)) + enc + struct.pack("<BII", 0, 3 * cols, img.nbytes)
+            + img.tobytes())
 
 
 def split_segment_list(msg):
