@@ -255,7 +255,14 @@ LF_API int lf_associate(lf_handle* h, const uint8_t* query32, int nq, const uint
                  int32_t* idx, float* dist, int on_device);
 /* tie rule of this handle's lf_associate, lf_knn_match and lf_radius_match (LF_TIE_MIHASHER unless set) */
 LF_API int lf_set_tie_rule(lf_handle* h, int tie_rule);
-/* float LBD (72-d, unit norm) Euclidean nearest neighbour on fp32 MFMA */
+/* Float LBD (72 floats per row) Euclidean nearest neighbour; the search runs on the fp32 MFMA.  idx[i] is the map row
+ * nearest to query i (where the fp32 search cannot tell two rows apart, fp64 direct sums decide), the LOWEST index among
+ * rows at the same distance (bit-equal rows in particular); dist[i] is the float nearest to the square root of the fp64
+ * direct sum of the 72 squared differences: within 1e-4 absolute of the true distance wherever half a float ulp is, i.e.
+ * below 2048.  A query equal to a map row returns that row and 0.  Rows need not be of unit length;
+ * zero rows are rows like any other.  Exactly nq results are written.  nq <= 0, nm <= 0 or a null pointer:
+ * LF_ERR_BAD_ARG, nothing is written and the handle stays usable.  on_device: all four arrays are device memory and the
+ * call is queued on the handle's stream.  tests/test_gpu_float_match.py pins all of this against a float64 reference. */
 LF_API int lf_associate_float(lf_handle* h, const float* query72, int nq, const float* map72, int nm,
                        int32_t* idx, float* dist, int on_device);
 

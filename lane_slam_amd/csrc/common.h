@@ -304,8 +304,10 @@ void launch_select_queries(const uint8_t* q, const uint8_t* mask, int nq, uint8_
 void launch_knn(const uint8_t* q, int nq, const uint8_t* m, int nm, int k, int max_distance, int mih, int32_t* idx, float* dist, hipStream_t s);
 void launch_radius(const uint8_t* q, int nq, const uint8_t* m, int nm, int max_distance, int32_t* hist, int32_t* count, int32_t* offsets,
                    int* total, int cap, int mih, int32_t* idx, float* dist, hipStream_t s);
-void launch_assoc_float(const float* q, int nq, const float* m, int nm, float* qn, float* mn,
-                        unsigned long long* best, int32_t* idx, float* dist, hipStream_t s);
+// float LBD: scratch of assoc_float_scratch_bytes(nq, nm) bytes, 16-byte aligned
+size_t assoc_float_scratch_bytes(int nq, int nm);
+hipError_t launch_assoc_float(const float* q, int nq, const float* m, int nm, float* qn, float* mn,
+                              void* scratch, int32_t* idx, float* dist, hipStream_t s);
 // ---- JPEG ingest (k_jpeg.hip)
 namespace jpeg { struct FrameHeader; }
 struct JpegGeom { int rows, cols, Wp, Hp; int first_row = 0; };     // Wp x Hp: padded component plane (multiples of 16); first_row: rows above it are not wanted (the dense IDCT and the colour kernel skip them)

@@ -19,7 +19,8 @@
 //       codes into registers, map chunk streamed by LDS-DMA through tile buffers, hand-scheduled tile loop (k_assoc_loop.inc,
 //       tools/gen_assoc_loop.py), per-chunk key rows written through and merged by the last workgroup to arrive; ties
 //       resolve to the lowest map index.  Algorithmic ops: 2*N*M*256.
-//   k_assoc_float: 72-d float LBD, Euclidean, on v_mfma_f32_32x32x2_f32 (exact fp32 FMA chain).
+//   k_assoc_float (+ k_sqnorm72, k_assoc_float_finish, k_assoc_float_exact, k_assoc_float_exact_merge): 72-d float LBD, Euclidean;
+//       the search on v_mfma_f32_32x32x2_f32 ranks, fp64 direct sums give the distance and decide what it cannot (below).
 #include <cstdio>
 #include "common.h"
 #include "k_assoc_loop.inc"
@@ -471,20 +472,70 @@ hipError_t launch_assoc(const uint8_t* q, int nq, const uint8_t* m, int nm, int8
 }
 
 // ---------------------------------------------------------------- float LBD (72-d)
-// dist^2 = |q|^2 + |m|^2 - 2 q.m ; the dot product runs on the fp32-input MFMA (K = 2 per
-// instruction, 36 steps).  One wave = 32 queries x 32 map entries per step.
-__global__ void k_sqnorm72(const float* __restrict__ x, int n, float* __restrict__ out)
+// Euclidean nearest neighbour in three steps:
+//   search  dist^2 = (|q|^2 + |m|^2) - 2 q.m ; the dot product runs on the fp32-input MFMA (K = 2 per instruction, 36
+//           steps).  One wave = 32 queries x 32 map entries per step.  The expansion cancels where an associator is
+//           used (q equal or nearly equal to a map row: an error of a few fp32 ulps of |q|^2 + |m|^2 is a distance of
+//           several 1e-4 at unit length), so its d2 only RANKS: beside the best row every query keeps a lower bound of
+//           the d2 of every other row (FloatCand).
+//   finish  the best row is the true nearest one if no other row's lower bound reaches its upper bound; its distance is
+//           then the direct sum of the 72 squared differences in fp64.  Otherwise the query goes on a list,
+//   exact   whose queries are matched against the whole map by direct fp64 sums (lowest column among equal sums), the
+//           map in the same pieces as in the search, and a merge of the pieces.
+// The error bound of the expansion, u = 2^-24, S = |q|^2 + |m|^2, gamma_n = n u / (1 - n u):
+//   k_sqnorm72: 72 products and 71 additions in sequence    |qn - |q|^2| <= gamma_72 |q|^2, the same for mn
+//   the MFMA's 72-term dot product, whatever its order     |acc - q.m| <= gamma_72 |q| |m| <= gamma_72 S / 2, twice that for 2 acc
+//   the addition qn + mn and the subtraction               <= u S and <= 2 u S (|d2| <= 2 S)
+//   forming d2 -+ E                                        <= 2 u S
+// in all < (72 + 72 + 5) u S (1 + 73 u) < 150 u S; E = 2^-16 S (256 u, the next power of two) + 1e-35 for products that
+// underflow (at most 216 of them, 2^-126 each where subnormals are flushed).
+struct __attribute__((aligned(16))) FloatCand {
+    float d2;             // the smallest d2 of the expansion (+inf: no row)
+    unsigned int col;     // its row, the lowest among equal d2
+    float lo;             // d2 - E of that row
+    float lo2;            // min of d2 - E over every other row
+};
+
+__device__ __forceinline__ float assoc_float_err(float s) { return __fmaf_rn(1.52587890625e-05f, s, 1e-35f); }
+
+__device__ __forceinline__ void float_cand_merge(float& d2, unsigned int& col, float& lo, float& lo2, float od2, unsigned int ocol, float olo, float olo2)
 {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float s = 0;
-    for (int k = 0; k < 72; ++k) { float v = x[(size_t)i * 72 + k]; s += v * v; }
-    out[i] = s;
+    const bool keep = d2 < od2 || (d2 == od2 && col <= ocol);
+    lo2 = fminf(fminf(lo2, olo2), keep ? olo : lo);
+    d2 = keep ? d2 : od2; col = keep ? col : ocol; lo = keep ? lo : olo;
 }
 
+// the 72 squared differences in fp64 (relative error < 12 * 2^-53), by 8 neighbouring lanes (sub = 0 .. 7) of 9 elements
+// each; every one of the 8 lanes returns the same sum
+__device__ __forceinline__ double float_dist2_direct8(const float* __restrict__ a, const float* __restrict__ b, int sub)
+{
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { const double d = (double)a[9 * sub + k] - (double)b[9 * sub + k]; s = fma(d, d, s); }
+#pragma unroll
+    for (int d = 4; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+    return s;
+}
+
+struct __attribute__((aligned(16))) ExactCand { double d2; int col; int pad; };
+
+// |row|^2 of the nq query rows and the nm map rows; the first thread empties the list of the exact step
+__global__ void k_sqnorm72(const float* __restrict__ q, int nq, float* __restrict__ qn, const float* __restrict__ m, int nm,
+                           float* __restrict__ mn, int* __restrict__ n_exact)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) *n_exact = 0;
+    if (i >= nq + nm) return;
+    const float* x = i < nq ? q + (size_t)i * 72 : m + (size_t)(i - nq) * 72;
+    float s = 0;
+    for (int k = 0; k < 72; ++k) { float v = x[k]; s += v * v; }
+    if (i < nq) qn[i] = s; else mn[i - nq] = s;
+}
+
+// part: [splits][nq], one FloatCand per query and piece of the map (every one is written: no initialisation, no atomics)
 __global__ __launch_bounds__(256) void k_assoc_float(const float* __restrict__ q, const float* __restrict__ qn, int nq,
                                                      const float* __restrict__ m, const float* __restrict__ mn, int nm,
-                                                     int m_chunk, unsigned long long* __restrict__ best)
+                                                     int m_chunk, FloatCand* __restrict__ part)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q0 = (blockIdx.x * 4 + wave) * 32;
@@ -500,9 +551,10 @@ __global__ __launch_bounds__(256) void k_assoc_float(const float* __restrict__ q
         int row = (r & 3) + 8 * (r >> 2) + 4 * half;
         qnr[r] = qn[min(q0 + row, nq - 1)];
     }
-    unsigned long long running[16];
+    float b1[16], l1[16], l2[16];
+    unsigned int c1[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) running[r] = ~0ull;
+    for (int r = 0; r < 16; ++r) { b1[r] = l1[r] = l2[r] = __builtin_inff(); c1[r] = ~0u; }
     const int m_begin = blockIdx.y * m_chunk, m_end = min(nm, m_begin + m_chunk);
     for (int m0 = m_begin; m0 < m_end; m0 += 32) {
         const int col = m0 + r32;
@@ -519,59 +571,155 @@ __global__ __launch_bounds__(256) void k_assoc_float(const float* __restrict__ q
         const bool valid = col < m_end;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            float d2 = (qnr[r] + mnc) - 2.f * acc[r];
-            d2 = d2 < 0.f ? 0.f : d2;
-            unsigned long long v = valid ? (((unsigned long long)__float_as_uint(d2) << 32) | (unsigned int)col) : ~0ull;
-            running[r] = v < running[r] ? v : running[r];
+            const float S = qnr[r] + mnc;
+            float d2 = S - 2.f * acc[r];              // (may come out below 0: it is not clamped, d2 -+ E holds the truth as it is)
+            float lo = d2 - assoc_float_err(S);
+            d2 = valid ? d2 : __builtin_inff();
+            lo = valid ? lo : __builtin_inff();
+            const bool lt = d2 < b1[r];               // this lane's columns ascend: the first of equal d2 stays
+            l2[r] = fminf(l2[r], lt ? l1[r] : lo);
+            l1[r] = lt ? lo : l1[r];
+            c1[r] = lt ? (unsigned int)col : c1[r];
+            b1[r] = lt ? d2 : b1[r];
         }
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        unsigned long long v = running[r];
+        float d2 = b1[r], lo = l1[r], lo2 = l2[r];
+        unsigned int c = c1[r];
 #pragma unroll
-        for (int d = 16; d >= 1; d >>= 1) {
-            unsigned long long o = __shfl_xor(v, d);
-            v = o < v ? o : v;
-        }
+        for (int d = 16; d >= 1; d >>= 1)
+            float_cand_merge(d2, c, lo, lo2, __shfl_xor(d2, d), __shfl_xor(c, d), __shfl_xor(lo, d), __shfl_xor(lo2, d));
         if (r32 == 0) {
             int row = (r & 3) + 8 * (r >> 2) + 4 * half;
             int qq = q0 + row;
-            if (qq < nq) atomicMin(best + qq, v);
+            if (qq < nq) part[(size_t)blockIdx.y * nq + qq] = FloatCand{ d2, c, lo, lo2 };
         }
     }
 }
 
-__global__ void k_assoc_float_finish(const unsigned long long* __restrict__ best, int nq, int32_t* __restrict__ idx,
-                                     float* __restrict__ dist)
+// 8 neighbouring lanes per query: they merge the pieces, then sum the 72 squared differences to the best row
+__global__ __launch_bounds__(256) void k_assoc_float_finish(const FloatCand* __restrict__ part, int splits, const float* __restrict__ q,
+                                                            const float* __restrict__ qn, int nq, const float* __restrict__ m,
+                                                            const float* __restrict__ mn, int* __restrict__ n_exact,
+                                                            int* __restrict__ exact_list, int32_t* __restrict__ idx, float* __restrict__ dist)
 {
-    int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nq) return;
-    unsigned long long v = best[q];
-    if (v == ~0ull) { idx[q] = -1; dist[q] = -1.f; }
-    else { idx[q] = (int)(v & 0xffffffffull); dist[q] = dm::fsqrt(__uint_as_float((unsigned int)(v >> 32))); }
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, sub = t & 7;
+    const bool live = (t >> 3) < nq;
+    const int qi = min(t >> 3, nq - 1);
+    FloatCand b = { __builtin_inff(), ~0u, __builtin_inff(), __builtin_inff() };
+    for (int p = sub; p < splits; p += 8) {
+        const FloatCand o = part[(size_t)p * nq + qi];
+        float_cand_merge(b.d2, b.col, b.lo, b.lo2, o.d2, o.col, o.lo, o.lo2);
+    }
+#pragma unroll
+    for (int d = 4; d >= 1; d >>= 1)
+        float_cand_merge(b.d2, b.col, b.lo, b.lo2, __shfl_xor(b.d2, d), __shfl_xor(b.col, d), __shfl_xor(b.lo, d), __shfl_xor(b.lo2, d));
+    const bool none = b.col == ~0u;
+    const unsigned int col = none ? 0u : b.col;
+    const bool sure = !none && b.lo2 > b.d2 + assoc_float_err(qn[qi] + mn[col]);       // no other row can be as near
+    const double s = float_dist2_direct8(q + (size_t)qi * 72, m + (size_t)col * 72, sub);
+    if (!live || sub != 0) return;
+    if (none) { idx[qi] = -1; dist[qi] = -1.f; }
+    else if (sure) { idx[qi] = (int)col; dist[qi] = (float)dm::dsqrt(s); }
+    else exact_list[atomicAdd(n_exact, 1)] = qi;
 }
 
-__global__ void k_fill_u64(unsigned long long* p, int n, unsigned long long v)
+// the listed queries against the rows of one piece of the map (blockIdx.y), by direct fp64 sums: 8 lanes per row, 32 rows
+// per step; epart: [splits][nq], indexed by the place in the list
+__global__ __launch_bounds__(256) void k_assoc_float_exact(const float* __restrict__ q, const float* __restrict__ m, int nq, int nm,
+                                                           int m_chunk, const int* __restrict__ n_exact, const int* __restrict__ exact_list,
+                                                           ExactCand* __restrict__ epart)
 {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
+    __shared__ float qs[72];
+    __shared__ double wd[4];
+    __shared__ int wc[4];
+    const int n = *n_exact;
+    const int sub = threadIdx.x & 7, group = threadIdx.x >> 3;
+    const int m_begin = blockIdx.y * m_chunk, m_end = min(nm, m_begin + m_chunk);
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const int qi = exact_list[i];
+        __syncthreads();
+        if (threadIdx.x < 72) qs[threadIdx.x] = q[(size_t)qi * 72 + threadIdx.x];
+        __syncthreads();
+        double bd = dm::inf();
+        int bc = 0x7fffffff;
+        for (int j = m_begin + group; j < m_end; j += 32) {
+            const double s = float_dist2_direct8(qs, m + (size_t)j * 72, sub);
+            if (s < bd) { bd = s; bc = j; }           // j ascends: the first of equal sums stays
+        }
+#pragma unroll
+        for (int d = 32; d >= 8; d >>= 1) {
+            const double od = __shfl_xor(bd, d);
+            const int oc = __shfl_xor(bc, d);
+            if (od < bd || (od == bd && oc < bc)) { bd = od; bc = oc; }
+        }
+        if ((threadIdx.x & 63) == 0) { wd[threadIdx.x >> 6] = bd; wc[threadIdx.x >> 6] = bc; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < 4; ++w)
+                if (wd[w] < bd || (wd[w] == bd && wc[w] < bc)) { bd = wd[w]; bc = wc[w]; }
+            epart[(size_t)blockIdx.y * nq + i] = ExactCand{ bd, bc, 0 };
+        }
+    }
 }
 
-void launch_assoc_float(const float* q, int nq, const float* m, int nm, float* qn, float* mn,
-                        unsigned long long* best, int32_t* idx, float* dist, hipStream_t s)
+__global__ void k_assoc_float_exact_merge(const ExactCand* __restrict__ epart, int splits, int nq, const int* __restrict__ n_exact,
+                                          const int* __restrict__ exact_list, int32_t* __restrict__ idx, float* __restrict__ dist)
 {
-    hipLaunchKernelGGL(k_sqnorm72, dim3((nq + 255) / 256), dim3(256), 0, s, q, nq, qn);
-    hipLaunchKernelGGL(k_sqnorm72, dim3((nm + 255) / 256), dim3(256), 0, s, m, nm, mn);
-    hipLaunchKernelGGL(k_fill_u64, dim3((nq + 255) / 256), dim3(256), 0, s, best, nq, ~0ull);
-    const int qblocks = (nq + 127) / 128;
-    int splits = (1024 + qblocks - 1) / qblocks;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= *n_exact) return;
+    ExactCand b = epart[i];
+    for (int p = 1; p < splits; ++p) {
+        const ExactCand o = epart[(size_t)p * nq + i];
+        if (o.d2 < b.d2 || (o.d2 == b.d2 && o.col < b.col)) b = o;
+    }
+    const int qi = exact_list[i];
+    const bool none = b.col == 0x7fffffff;            // (only rows with a NaN)
+    idx[qi] = none ? -1 : b.col;
+    dist[qi] = none ? -1.f : (float)dm::dsqrt(b.d2);
+}
+
+// the map in `splits` pieces of m_chunk rows (whole tiles) over blockIdx.y: about 1024 workgroups of 128 queries
+static void assoc_float_plan(int nq, int nm, int& qblocks, int& splits, int& m_chunk)
+{
+    qblocks = (nq + 127) / 128;
+    splits = (1024 + qblocks - 1) / qblocks;
     const int tiles = (nm + 31) / 32;
     if (splits > tiles) splits = tiles;
     if (splits < 1) splits = 1;
-    const int m_chunk = (tiles + splits - 1) / splits * 32;
+    m_chunk = (tiles + splits - 1) / splits * 32;
     splits = (nm + m_chunk - 1) / m_chunk;
-    hipLaunchKernelGGL(k_assoc_float, dim3(qblocks, splits), dim3(256), 0, s, q, qn, nq, m, mn, nm, m_chunk, best);
-    hipLaunchKernelGGL(k_assoc_float_finish, dim3((nq + 255) / 256), dim3(256), 0, s, best, nq, idx, dist);
+}
+
+// scratch: FloatCand[splits][nq] (the exact step's ExactCand[splits][nq] afterwards) | the list's length (16 bytes) | int list[nq]
+size_t assoc_float_scratch_bytes(int nq, int nm)
+{
+    int qblocks, splits, m_chunk;
+    assoc_float_plan(nq, nm, qblocks, splits, m_chunk);
+    return ((size_t)splits * nq + 1) * sizeof(FloatCand) + (size_t)nq * sizeof(int);
+}
+
+hipError_t launch_assoc_float(const float* q, int nq, const float* m, int nm, float* qn, float* mn,
+                              void* scratch, int32_t* idx, float* dist, hipStream_t s)
+{
+    static_assert(sizeof(FloatCand) == 16 && sizeof(ExactCand) == 16, "the two steps share one scratch array");
+    int qblocks, splits, m_chunk;
+    assoc_float_plan(nq, nm, qblocks, splits, m_chunk);
+    FloatCand* part = static_cast<FloatCand*>(scratch);
+    int* n_exact = reinterpret_cast<int*>(part + (size_t)splits * nq);
+    int* exact_list = n_exact + sizeof(FloatCand) / sizeof(int);
+    hipLaunchKernelGGL(k_sqnorm72, dim3((unsigned)(((size_t)nq + nm + 255) / 256)), dim3(256), 0, s, q, nq, qn, m, nm, mn, n_exact);
+    hipLaunchKernelGGL(k_assoc_float, dim3(qblocks, splits), dim3(256), 0, s, q, qn, nq, m, mn, nm, m_chunk, part);
+    hipLaunchKernelGGL(k_assoc_float_finish, dim3((unsigned)(((size_t)nq * 8 + 255) / 256)), dim3(256), 0, s, part, splits, q, qn, nq, m, mn, n_exact,
+                       exact_list, idx, dist);
+    // few queries are listed as a rule: about 2048 workgroups, each striding over the list
+    const int per_piece = 2048 / splits < 1 ? 1 : 2048 / splits;
+    hipLaunchKernelGGL(k_assoc_float_exact, dim3(nq < per_piece ? nq : per_piece, splits), dim3(256), 0, s, q, m, nq, nm, m_chunk, n_exact,
+                       exact_list, reinterpret_cast<ExactCand*>(part));
+    hipLaunchKernelGGL(k_assoc_float_exact_merge, dim3((nq + 255) / 256), dim3(256), 0, s, reinterpret_cast<const ExactCand*>(part), splits, nq,
+                       n_exact, exact_list, idx, dist);
+    return hipGetLastError();
 }
 
 }  // namespace lf

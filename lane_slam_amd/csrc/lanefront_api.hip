@@ -733,7 +733,7 @@ extern "C" int lf_associate_float(lf_handle* h, const float* query72, int nq, co
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = ensure(h, h->a_best, (size_t)nq * 8)) || (rc = ensure(h, h->a_qn, (size_t)nq * 4)) || (rc = ensure(h, h->a_mn, (size_t)nm * 4))) return rc;
+    if ((rc = ensure(h, h->a_best, assoc_float_scratch_bytes(nq, nm))) || (rc = ensure(h, h->a_qn, (size_t)nq * 4)) || (rc = ensure(h, h->a_mn, (size_t)nm * 4))) return rc;
     const float *dq = query72, *dmp = map72;
     int32_t* didx = idx; float* ddist = dist;
     if (!on_device) {
@@ -745,7 +745,7 @@ extern "C" int lf_associate_float(lf_handle* h, const float* query72, int nq, co
     }
     {
         StageTimer t(h, ST_ASSOC);
-        launch_assoc_float(dq, nq, dmp, nm, (float*)h->a_qn.p, (float*)h->a_mn.p, (unsigned long long*)h->a_best.p, didx, ddist, s);
+        LF_HIP_CHECK(h, launch_assoc_float(dq, nq, dmp, nm, (float*)h->a_qn.p, (float*)h->a_mn.p, h->a_best.p, didx, ddist, s));
     }
     LF_HIP_CHECK(h, hipGetLastError());
     if (!on_device) {

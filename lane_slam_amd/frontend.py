@@ -366,12 +366,20 @@ class FrontEnd(object):
             return offsets, idx[:total.value], dist[:total.value]
 
     def associate_float(self, query_desc, map_desc):
+        """Euclidean nearest neighbour of 72-float LBD descriptors (lf_associate_float): (idx int32, dist float32), the
+        true nearest row (the lowest index among equally near ones) and its distance to 1e-4; rows need not be unit length."""
         q = np.ascontiguousarray(query_desc, dtype=np.float32).reshape(-1, 72)
         m = np.ascontiguousarray(map_desc, dtype=np.float32).reshape(-1, 72)
         idx = np.empty(q.shape[0], np.int32)
         dist = np.empty(q.shape[0], np.float32)
         self._check(self.lib.lf_associate_float(self.h, _ptr(q), q.shape[0], _ptr(m), m.shape[0], _ptr(idx), _ptr(dist), 0))
         return idx, dist
+
+    def associate_float_device(self, q_ptr, nq, m_ptr, nm, idx_ptr, dist_ptr):
+        """associate_float on device arrays (float32 [nq, 72] and [nm, 72]; int32 and float32 [nq] results), queued on the
+        handle's stream: synchronize() before reading."""
+        self._check(self.lib.lf_associate_float(self.h, ctypes.c_void_p(int(q_ptr)), int(nq), ctypes.c_void_p(int(m_ptr)),
+                                                int(nm), ctypes.c_void_p(int(idx_ptr)), ctypes.c_void_p(int(dist_ptr)), 1))
 
     def kmeans(self, bgr_points, init_centers, max_iter=25, tol=1e-4):
         """Lloyd's k-means from an explicit init on [N, 3] u8 B, G, R points (anti_instagram/kmeans.py:24-26, i.e.
