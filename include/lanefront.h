@@ -40,8 +40,9 @@ extern "C" {
 
 #define LF_ABI_VERSION 5   /* 2: JPEG ingest, SegmentList glue, LF_ERR_DECODE, 13 timing stages; 3: live map (lf_map_*); 4: EDLines / KeyLines, block overflow marker; 5: lf_config.lsd_seed_order, tie rules.
                               Still 5 with the histogram lane filter (lf_lane_filter_*) and the anti-instagram estimate (lf_ai_transform_batch,
-                              lf_set_ai_transform, lf_get_ai_transform) and the overlay (lf_draw_lines, lf_draw_lines_image): purely additive, no existing
-                              declaration changed */
+                              lf_set_ai_transform, lf_get_ai_transform) and the overlay (lf_draw_lines, lf_draw_lines_image) and the JPEG encoder
+                              (lf_jpeg_encode_bound, lf_jpeg_encode_batch, lf_jpeg_encode_timing, lf_jpeg_encode_stage_name): purely additive, no
+                              existing declaration changed */
 
 typedef enum lf_status {
     LF_OK = 0,
@@ -788,6 +789,30 @@ LF_API int lf_deserialize_segments(lf_handle* h, const uint8_t* bodies, int bodi
 LF_API int lf_draw_lines(lf_handle* h, int n_frames, const lf_segments* seg, int seg_on_device, uint8_t* out_bgr, int out_on_device);
 LF_API int lf_draw_lines_image(lf_handle* h, const uint8_t* bgr, int n_frames, int rows, int cols, const lf_segments* seg, int seg_on_device,
                                uint8_t* out_bgr, int images_on_device);
+
+/* ---- jpg_from_image_cv: replaces cv2.imencode('.jpg', image) -------------------------------------------
+ * The reference's duckietown_utils.jpg.jpg_from_image_cv (jpg.py:16-18), which write_jpg_to_file and
+ * d8_compressed_image_from_cv_image (image_jpg_create.py:4-23, the CompressedImage a node publishes) rest on, for a batch of BGR u8
+ * frames [n_frames][rows][cols][3] on the device: the file libjpeg(-turbo) writes with cv2.imencode's defaults -- baseline, quality
+ * 95 through jpeg_set_quality(q, force_baseline), YCbCr 4:2:0, the integer "islow" DCT, the standard Huffman tables, one scan, no
+ * restart markers, the JFIF APP0 header -- byte for byte what Pillow on libjpeg-turbo writes (tests/golden/jpeg_encode_vectors.npz).
+ *
+ * lf_jpeg_encode_bound: bytes that always suffice for one frame of rows x cols (header, a scan of nothing but stuffed bytes, EOI);
+ *   0 for sizes the encoder refuses.
+ * lf_jpeg_encode_batch: frame i is out[i * out_stride .. + out_size[i]).  bgr_on_device says where bgr is, out_on_device where out
+ *   and out_size are.  quality 1 .. 100 (cv2.IMWRITE_JPEG_QUALITY), 0 = 95.  rows, cols 1 .. 8192, n_frames 1 .. 65535; any size, not
+ *   only multiples of 16.  Queued on the handle's stream, also while a batch is in flight (it runs behind it): with device outputs
+ *   it returns at once, with host outputs when the data is in place.  A frame that needs more than out_stride bytes gets
+ *   out_size[i] = 0 and nothing of it is written; with host outputs the call then returns LF_ERR_CAPACITY (the other frames are in
+ *   place).  LF_ERR_BAD_ARG for a NULL array, sizes or a quality outside the ranges.
+ * lf_jpeg_encode_timing: milliseconds of the LF_JPEG_ENCODE_STAGES kernels of the last lf_jpeg_encode_batch that ran with
+ *   profiling on (lf_set_profiling), by HIP events; waits for that call.  lf_jpeg_encode_stage_name: the kernels' names. */
+#define LF_JPEG_ENCODE_STAGES 8
+LF_API size_t lf_jpeg_encode_bound(int rows, int cols);
+LF_API int lf_jpeg_encode_batch(lf_handle* h, const uint8_t* bgr, int bgr_on_device, int n_frames, int rows, int cols, int quality, uint8_t* out,
+                                size_t out_stride, uint32_t* out_size, int out_on_device);
+LF_API int lf_jpeg_encode_timing(lf_handle* h, double* ms_per_stage, int n);
+LF_API const char* lf_jpeg_encode_stage_name(int stage);
 
 /* ---- introspection for tests and the benchmark ---------------------------- */
 typedef enum lf_buffer_id {

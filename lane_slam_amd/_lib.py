@@ -37,7 +37,9 @@ EXPORTS = (
     "lf_dense_default_params", "lf_set_dense_params", "lf_get_dense_params",
     "lf_ai_transform_batch", "lf_set_ai_transform", "lf_get_ai_transform",
     "lf_draw_lines", "lf_draw_lines_image",
+    "lf_jpeg_encode_bound", "lf_jpeg_encode_batch", "lf_jpeg_encode_timing", "lf_jpeg_encode_stage_name",
 )
+LF_JPEG_ENCODE_STAGES = 8
 LF_LANE_FILTER_PREDICT, LF_LANE_FILTER_UPDATE = 1, 2
 LF_LANE_FILTER_MAX_CELLS = 4096
 LF_LANE_FILTER_N_STAGES = 2
@@ -169,6 +171,14 @@ def load():
     lib.lf_get_ai_transform.argtypes = [vp, vp, vp]
     lib.lf_draw_lines.argtypes = [vp, ci, ctypes.POINTER(LfSegments), ci, vp, ci]
     lib.lf_draw_lines_image.argtypes = [vp, vp, ci, ci, ci, ctypes.POINTER(LfSegments), ci, vp, ci]
+    lib.lf_jpeg_encode_bound.argtypes = [ci, ci]
+    lib.lf_jpeg_encode_bound.restype = ctypes.c_size_t
+    lib.lf_jpeg_encode_batch.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, ci]
+    lib.lf_jpeg_encode_batch.restype = ci
+    lib.lf_jpeg_encode_timing.argtypes = [vp, vp, ci]
+    lib.lf_jpeg_encode_timing.restype = ci
+    lib.lf_jpeg_encode_stage_name.argtypes = [ci]
+    lib.lf_jpeg_encode_stage_name.restype = ctypes.c_char_p
     lib.lf_jpeg_decode_batch.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t), ci, ci, ci, vp, ci, ci,
                                          ctypes.POINTER(ci)]
     lib.lf_jpeg_decode_batch.restype = ci

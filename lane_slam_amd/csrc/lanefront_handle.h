@@ -11,6 +11,7 @@
 #include "jpeg_entropy.h"
 #include "k_edlines_types.h"
 #include "k_hough.h"
+#include "k_jenc.h"
 
 namespace lf {
 
@@ -34,6 +35,20 @@ struct JpegState {
     {
         if (staged) (void)hipEventDestroy(staged);
         if (status_done) (void)hipEventDestroy(status_done);
+    }
+};
+
+// JPEG encoder state (lanefront_jenc.hip): allocated on the first lf_jpeg_encode_batch, grown on demand
+struct JencState {
+    DevBuf tab, in, coef, bits, dcdiff, total, bitbuf, ff, out, sizes;
+    HostArray<jenc::Tables> h_tab;                  // pinned: what `tab` was copied from
+    HostArray<uint32_t> h_sizes;
+    int rows = 0, cols = 0, quality = 0;            // what `tab` holds
+    hipEvent_t ev[jenc::kStages + 1] = {};          // around the stages of the last call, with profiling on
+    bool timed = false;
+    ~JencState()
+    {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -248,6 +263,7 @@ struct lf_handle {
     int pending_capacity = 0;
     std::vector<int> h_counts, h_seg_offset;
     std::unique_ptr<lf::JpegState> jpeg;
+    std::unique_ptr<lf::JencState> jenc;  // lf_jpeg_encode_batch (lanefront_jenc.hip), allocated on first use
     std::unique_ptr<lf::KlState> kl;      // EDLines / KeyLines state (lanefront_keylines.hip), allocated on first use
     std::unique_ptr<lf::LsdKlState> lsdkl; // LSDDetectorC over octaves (lanefront_lsdkl.hip): an LSD state per pyramid level
     lf::DevBuf m_fo, m_color, m_pn, m_nm, m_gr, m_keep, m_counts, m_boff, m_body, m_bad;   // SegmentList glue scratch

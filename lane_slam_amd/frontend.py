@@ -301,6 +301,48 @@ class FrontEnd(object):
         self._check(self.lib.lf_draw_lines_image(self.h, ctypes.c_void_p(int(images_ptr)), int(n_frames), int(rows), int(cols),
                                                  ctypes.byref(s), 1, ctypes.c_void_p(int(out_ptr)), 1))
 
+    # ------------------------------------------------------------------ JPEG out (jpg_from_image_cv)
+    def jpeg_encode_bound(self, rows, cols):
+        """Bytes that always suffice for one encoded frame of rows x cols (lf_jpeg_encode_bound)."""
+        return int(self.lib.lf_jpeg_encode_bound(int(rows), int(cols)))
+
+    def encode_jpeg_batch(self, frames, quality=95, device_ptr=None, n_frames=None, rows=None, cols=None):
+        """The batched form of duckietown_utils.jpg.jpg_from_image_cv = cv2.imencode('.jpg', image) (ref: duckietown_utils/jpg.py:16-18):
+        frames uint8 (n, rows, cols, 3) BGR on the host -- or, with frames None, device_ptr the device address of such a block of
+        n_frames x rows x cols x 3 bytes (e.g. what draw_lines_device wrote).  Returns a list of n `bytes`, each the JPEG file
+        libjpeg-turbo writes with cv2's defaults (quality 1 .. 100, 95 unless given).  Queued behind the handle's work; waits."""
+        if device_ptr is None:
+            frames = np.ascontiguousarray(frames, dtype=np.uint8)
+            if frames.ndim != 4 or frames.shape[3] != 3:
+                raise ValueError("frames must be (n, rows, cols, 3) uint8")
+            n, rows, cols = frames.shape[:3]
+            src, on_device = _ptr(frames), 0
+        else:
+            n, rows, cols = int(n_frames), int(rows), int(cols)
+            src, on_device = ctypes.c_void_p(int(device_ptr)), 1
+        bound = self.jpeg_encode_bound(rows, cols)
+        # slots of the raw frame's size hold all but pathological content (noise at quality 100); the bound is the second try
+        for stride in (min(bound, 1024 + rows * cols * 3), bound):
+            out = np.empty((n, stride), np.uint8)
+            sizes = np.zeros(n, np.uint32)
+            rc = self.lib.lf_jpeg_encode_batch(self.h, src, on_device, n, rows, cols, int(quality), _ptr(out), stride, _ptr(sizes), 0)
+            if rc != -2 or stride == bound:
+                break
+        self._check(rc)
+        return [out[i, :int(sizes[i])].tobytes() for i in range(n)]
+
+    def encode_jpeg_device(self, frames_ptr, n_frames, rows, cols, out_ptr, out_stride, sizes_ptr, quality=95):
+        """Device form of encode_jpeg_batch, beside draw_lines_device: frames at frames_ptr, frame i's file to out_ptr + i * out_stride,
+        its size (uint32; 0 when it needs more than out_stride bytes) to sizes_ptr + 4 i.  Queued on the handle's stream; returns at once."""
+        self._check(self.lib.lf_jpeg_encode_batch(self.h, ctypes.c_void_p(int(frames_ptr)), 1, int(n_frames), int(rows), int(cols), int(quality),
+                                                  ctypes.c_void_p(int(out_ptr)), int(out_stride), ctypes.c_void_p(int(sizes_ptr)), 1))
+
+    def jpeg_encode_timing(self):
+        """{kernel name: ms} of the last encode call that ran with set_profiling(True) (HIP events)."""
+        ms = np.zeros(_lib.LF_JPEG_ENCODE_STAGES, np.float64)
+        self._check(self.lib.lf_jpeg_encode_timing(self.h, _ptr(ms), ms.size))
+        return dict((self.lib.lf_jpeg_encode_stage_name(k).decode(), float(ms[k])) for k in range(ms.size))
+
     # ------------------------------------------------------------------ association
     def set_tie_rule(self, rule):
         """Which of several equally near map codes `associate` returns: "mihasher" (the default: the one the reference's

@@ -1,7 +1,9 @@
-"""Mirror of the reference's duckietown_utils.jpg decode helper on the HIP ingest path
-(ref: src/duckietown/include/duckietown_utils/jpg.py:21-31).
+"""Mirror of the reference's duckietown_utils.jpg helpers on the HIP ingest and encode paths
+(ref: src/duckietown/include/duckietown_utils/jpg.py:16-45).
 
     image_cv_from_jpg(data) -> BGR u8 (rows, cols, 3)      # same name, argument and error behaviour
+    jpg_from_image_cv(image) -> bytes                      # cv2.imencode('.jpg', image)[1].tostring(): lf_jpeg_encode_batch
+    write_jpg_to_file(image_cv, fn)
 
 The reference calls cv2.imdecode(np.fromstring(data, np.uint8), cv2.IMREAD_COLOR) and raises ValueError
 when it returns None.  Here the stream goes through lf_jpeg_decode_batch (Huffman decoding on the host,
@@ -15,6 +17,8 @@ import numpy as np
 from . import _lib
 from .config import default_config
 from .frontend import FrontEnd
+
+__all__ = ["jpg_info", "image_cv_from_jpg", "jpg_from_image_cv", "write_jpg_to_file"]
 
 _decoder = None
 
@@ -47,3 +51,17 @@ def image_cv_from_jpg(data):
         msg += 'This is usual a sign of data corruption.'
         raise ValueError(msg)
     return frames[0]
+
+
+def jpg_from_image_cv(image):
+    """The JPEG file, as bytes, of one BGR uint8 image (rows, cols, 3), with cv2.imencode's defaults: quality 95, 4:2:0."""
+    image = np.asarray(image)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("jpg_from_image_cv encodes BGR uint8 images (rows, cols, 3), got %s %r" % (image.dtype, image.shape))
+    return _handle().encode_jpeg_batch(image[None])[0]
+
+
+def write_jpg_to_file(image_cv, fn):
+    """The JPEG file of the BGR image image_cv, written to the path fn."""
+    with open(fn, "wb") as f:
+        f.write(jpg_from_image_cv(image_cv))

@@ -44,6 +44,15 @@ def image_message(header, bgr):
             + img.tobytes())
 
 
+def compressed_image_message(header, jpg_bytes):
+    """The serialised sensor_msgs/CompressedImage that d8_compressed_image_from_cv_image builds (image_jpg_create.py:4-23):
+    header_bytes(...) + string format "jpeg" (u32 length + bytes) | uint8[] data (u32 length + bytes).  jpg_bytes: one JPEG file, e.g.
+    an element of FrontEnd.encode_jpeg_batch or jpg.jpg_from_image_cv's result."""
+    data = bytes(jpg_bytes)
+    fmt = b"jpeg"
+    return bytes(header) + struct.pack("<I", len(fmt)) + fmt + struct.pack("<I", len(data)) + data
+
+
 def split_segment_list(msg):
     """(seq, secs, nsecs, frame_id, body bytes, records view) of a serialised SegmentList."""
     msg = bytes(msg)
