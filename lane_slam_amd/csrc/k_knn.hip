@@ -3,7 +3,10 @@
 //   BinaryDescriptorMatcher::radiusMatch  :428-504
 // Both run Mihasher(256, 32) with K = k / K = N (:756-819, 635-753): the K nearest train codes within D = 128 bits,
 // nearest first; radiusMatch then keeps those within maxDistance.  Among equally near codes the reference lists them in
-// its hash tables' discovery order; here (as for lf_associate, include/lanefront.h a-10) in index order.
+// its hash tables' discovery order, and so do these kernels by default (LF_TIE_MIHASHER, as for lf_associate, include/lanefront.h
+// a-10): (distance, discovery key, index) -- k_knn_mih, k_radius_order_mih; under LF_TIE_LOWEST in index order -- k_knn.  The
+// lists are held against a literal walk of Mihasher::query (tests/mih_ref.py) through the oracle: tests/test_mih_lists_cpu.py,
+// tests/test_gpu_knn_radius.py.
 //
 // These are the secondary forms of the matcher -- the 1-NN association of the hot path runs on the matrix cores
 // (k_assoc.hip); a list of neighbours per query has no arg-max epilogue to ride on, so this is the plain formulation:

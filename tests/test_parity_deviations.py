@@ -11,54 +11,14 @@ The counts are printed (run with -s) and quoted in DESIGN.md section 2; the asse
 import numpy as np
 
 from lane_slam_amd import default_config, synth
+from mih_ref import MihIndex, mih_query
 from oracle.oracle import Oracle
 
 
 def _mih_literal(q, train):
-    """Mihasher::query, literally (:635-753): 32 tables of 8-bit substrings, radius s = 0..4, substring k = 0..31, the
-    combination loop of :681-741, buckets in insertion order, first index per distance, stop once a code at distance
-    s * 32 + k has been seen.  Returns (index, distance) or (-1, -1)."""
-    m, b, D, d = 32, 8, 128, 4
-    tables = [dict() for _ in range(m)]
-    for i, code in enumerate(train):
-        for k in range(m):
-            tables[k].setdefault(int(code[k]), []).append(i)
-    seen, first, numres = set(), {}, [0] * 257
-    n = 0
-    for s in range(d + 1):
-        if n >= 1:
-            break
-        for k in range(m):
-            chunk = int(q[k])
-            power = list(range(s)) + [b + 1]
-            bit, bitstr = s - 1, 0
-            while True:
-                if bit != -1:
-                    bitstr ^= (1 << power[bit]) if power[bit] == bit else (3 << (power[bit] - 1))
-                    power[bit] += 1
-                    bit -= 1
-                else:
-                    for idx in tables[k].get(chunk ^ bitstr, ()):
-                        if idx not in seen:
-                            seen.add(idx)
-                            hd = int(np.unpackbits(train[idx] ^ q).sum())
-                            if hd <= D and numres[hd] < 1:
-                                first[hd] = idx
-                            numres[hd] += 1
-                    bit += 1
-                    while bit < s and power[bit] == power[bit + 1] - 1:
-                        bitstr ^= 1 << (power[bit] - 1)
-                        power[bit] = bit
-                        bit += 1
-                    if bit == s:
-                        break
-            n += numres[s * m + k]
-            if n >= 1:
-                break
-    for hd in range(D + 1):
-        if numres[hd]:
-            return first[hd], hd
-    return -1, -1
+    """Mihasher::query, literally (:635-753), with K = 1: tests/mih_ref.py.  Returns (index, distance) or (-1, -1)."""
+    found = mih_query(q, train, 1)
+    return found[0] if found else (-1, -1)
 
 
 def test_first_discovered_rule_is_restated_correctly():
@@ -79,8 +39,9 @@ def test_first_discovered_rule_is_restated_correctly():
     low_idx, low_dist = o.match(q, train)
     assert np.array_equal(dist, low_dist)                         # the distance never depends on the rule
     differ = 0
+    tables = MihIndex(train)
     for i in range(q.shape[0]):
-        wi, wd = _mih_literal(q[i], train)
+        wi, wd = _mih_literal(q[i], tables)
         assert (idx[i], dist[i]) == (wi, wd), i
         differ += int(idx[i] != low_idx[i])
         if ties[i] == 1:
