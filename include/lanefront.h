@@ -41,8 +41,9 @@ extern "C" {
 #define LF_ABI_VERSION 5   /* 2: JPEG ingest, SegmentList glue, LF_ERR_DECODE, 13 timing stages; 3: live map (lf_map_*); 4: EDLines / KeyLines, block overflow marker; 5: lf_config.lsd_seed_order, tie rules.
                               Still 5 with the histogram lane filter (lf_lane_filter_*) and the anti-instagram estimate (lf_ai_transform_batch,
                               lf_set_ai_transform, lf_get_ai_transform) and the overlay (lf_draw_lines, lf_draw_lines_image) and the JPEG encoder
-                              (lf_jpeg_encode_bound, lf_jpeg_encode_batch, lf_jpeg_encode_timing, lf_jpeg_encode_stage_name): purely additive, no
-                              existing declaration changed */
+                              (lf_jpeg_encode_bound, lf_jpeg_encode_batch, lf_jpeg_encode_timing, lf_jpeg_encode_stage_name) and the rectifier
+                              (lf_set_camera, lf_set_rectified_input, lf_get_rectified_input, lf_rectify_map, lf_rectify_batch, lf_rectify_timing,
+                              lf_rectify_stage_name): purely additive, no existing declaration changed */
 
 typedef enum lf_status {
     LF_OK = 0,
@@ -813,6 +814,41 @@ LF_API int lf_jpeg_encode_batch(lf_handle* h, const uint8_t* bgr, int bgr_on_dev
                                 size_t out_stride, uint32_t* out_size, int out_on_device);
 LF_API int lf_jpeg_encode_timing(lf_handle* h, double* ms_per_stage, int n);
 LF_API const char* lf_jpeg_encode_stage_name(int stage);
+
+/* ---- GroundProjection.rectify, rectified_input and the camera of a live handle ---------------------------
+ * The reference's GroundProjection (ground_projection/include/ground_projection/GroundProjection.py) beyond the projection of
+ * segment end points that lf_process_batch does:
+ *
+ * lf_set_camera: initialize_pinhole_camera_model (:33-36) on a live handle -- K [9], D [5] (plumb bob: k1 k2 p1 p2 k3), R [9],
+ *   P [12], row major, and the camera's size, as lf_config holds them.  Everything after it uses the new camera: the undistortion
+ *   of segment end points (stage a-7) and the rectification below, whose map is made again on its next use.  LF_ERR_BAD_ARG, and
+ *   nothing changes: a batch in flight (lf_wait first), a NULL array, a size outside 1 .. 8192, a singular P[:3,:3] . R.
+ * lf_set_rectified_input / lf_get_rectified_input: GroundProjection.rectified_input (:21,66-67).  0 (the default, the reference's):
+ *   stage a-7 undistorts a segment's pixels (cv2.undistortPoints' five iterations, then P . R) before the homography.  Not 0: the
+ *   frames are rectified already (what lf_rectify_batch wrote, say) and a-7 applies vector2pixel and the homography alone.
+ *   LF_ERR_BAD_ARG while a batch is in flight.
+ * lf_rectify_map: the float32 maps of cv2.initUndistortRectifyMap(K, D, R, P, (cam_w, cam_h), CV_32FC1) for the handle's camera,
+ *   mapx and mapy [cam_h][cam_w] each, host pointers.  Evaluated on the host in float64, statement for statement OpenCV 3.3.1's
+ *   (restated, not pinned to a cv2: tests/rectify_ref.py).
+ * lf_rectify_batch: rectify (:95-101) = cv2.remap(image, mapx, mapy, cv2.INTER_CUBIC) with those maps, for a batch of u8 frames
+ *   src [n_frames][rows][cols][channels] -> dst [n_frames][cam_h][cam_w][channels]: OpenCV's fixed-point bicubic (5 fractional
+ *   bits, int16 weights summing to 1 << 15, A = -0.75), BORDER_CONSTANT 0.  channels 1 or 3; rows, cols 1 .. 8192 (the source need
+ *   not have the camera's size); n_frames 1 .. 65535.  src_on_device / dst_on_device say where each is.  The camera's map is made
+ *   on the first call and kept on the device (6 bytes per pixel + a 32 KB table) until lf_set_camera.  Queued on the handle's
+ *   stream, also while a batch is in flight (it runs behind it): with device buffers it returns at once, with a host dst when the
+ *   data is in place.  LF_ERR_BAD_ARG for a NULL array, sizes or channels outside the ranges, a camera lf_set_camera would refuse,
+ *   dst overlapping src.
+ * lf_rectify_timing: milliseconds of the LF_RECTIFY_STAGES kernels of the last lf_rectify_batch that ran with profiling on
+ *   (lf_set_profiling), by HIP events; waits for that call.  lf_rectify_stage_name: the kernels' names. */
+#define LF_RECTIFY_STAGES 1
+LF_API int lf_set_camera(lf_handle* h, const double* K, const double* D, const double* R, const double* P, int cam_w, int cam_h);
+LF_API int lf_set_rectified_input(lf_handle* h, int flag);
+LF_API int lf_get_rectified_input(lf_handle* h, int* flag);
+LF_API int lf_rectify_map(lf_handle* h, float* mapx, float* mapy);
+LF_API int lf_rectify_batch(lf_handle* h, const uint8_t* src, int src_on_device, int n_frames, int rows, int cols, int channels, uint8_t* dst,
+                            int dst_on_device);
+LF_API int lf_rectify_timing(lf_handle* h, double* ms_per_stage, int n);
+LF_API const char* lf_rectify_stage_name(int stage);
 
 /* ---- introspection for tests and the benchmark ---------------------------- */
 typedef enum lf_buffer_id {

@@ -38,8 +38,11 @@ EXPORTS = (
     "lf_ai_transform_batch", "lf_set_ai_transform", "lf_get_ai_transform",
     "lf_draw_lines", "lf_draw_lines_image",
     "lf_jpeg_encode_bound", "lf_jpeg_encode_batch", "lf_jpeg_encode_timing", "lf_jpeg_encode_stage_name",
+    "lf_set_camera", "lf_set_rectified_input", "lf_get_rectified_input", "lf_rectify_map", "lf_rectify_batch", "lf_rectify_timing",
+    "lf_rectify_stage_name",
 )
 LF_JPEG_ENCODE_STAGES = 8
+LF_RECTIFY_STAGES = 1
 LF_LANE_FILTER_PREDICT, LF_LANE_FILTER_UPDATE = 1, 2
 LF_LANE_FILTER_MAX_CELLS = 4096
 LF_LANE_FILTER_N_STAGES = 2
@@ -179,6 +182,16 @@ def load():
     lib.lf_jpeg_encode_timing.restype = ci
     lib.lf_jpeg_encode_stage_name.argtypes = [ci]
     lib.lf_jpeg_encode_stage_name.restype = ctypes.c_char_p
+    lib.lf_set_camera.argtypes = [vp, vp, vp, vp, vp, ci, ci]
+    lib.lf_set_rectified_input.argtypes = [vp, ci]
+    lib.lf_get_rectified_input.argtypes = [vp, ctypes.POINTER(ci)]
+    lib.lf_rectify_map.argtypes = [vp, vp, vp]
+    lib.lf_rectify_batch.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, ci]
+    lib.lf_rectify_timing.argtypes = [vp, vp, ci]
+    for f in ("lf_set_camera", "lf_set_rectified_input", "lf_get_rectified_input", "lf_rectify_map", "lf_rectify_batch", "lf_rectify_timing"):
+        getattr(lib, f).restype = ci
+    lib.lf_rectify_stage_name.argtypes = [ci]
+    lib.lf_rectify_stage_name.restype = ctypes.c_char_p
     lib.lf_jpeg_decode_batch.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t), ci, ci, ci, vp, ci, ci,
                                          ctypes.POINTER(ci)]
     lib.lf_jpeg_decode_batch.restype = ci

@@ -75,6 +75,7 @@ struct SegParams {
     double cw, ch;
     double H[9], K[9], D[5], RR[9];
     double lanewidth, linewidth_white, linewidth_yellow, d_min, d_max, phi_min, phi_max;
+    int rectified_input;   // GroundProjection.rectified_input: the pixels are rectified already, a-7 applies the homography alone
 };
 
 // device resize tables for the LSD bilinear step (cv::resize INTER_LINEAR on CV_64F)

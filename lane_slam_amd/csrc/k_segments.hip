@@ -5,7 +5,7 @@
 //       _correctPixelOrdering (float32 numpy arithmetic, int truncation, float64 ordering test)
 //   a-6 src/line_detector/src/line_detector_node.py:195-205,251-265  normalisation, colour order, float32 msg fields
 //   a-7 src/ground_projection/include/ground_projection/GroundProjection.py:38-48,64-78  vector2pixel (+ the
-//       v > ch-1 -> 0 quirk), rectifyPoint (cv2.undistortPoints, 5 iterations), homography
+//       v > ch-1 -> 0 quirk), rectifyPoint (cv2.undistortPoints, 5 iterations; skipped with rectified_input, :66-67), homography
 //   a-8 src/line_sanity/src/line_sanity_node.py:48-117  processSegmentList + fancyFilters
 //
 // Also compacts the fixed-capacity LSD slots [frame][colour][cap] into the frame-major,
@@ -74,6 +74,8 @@ __device__ void ground_point(const SegParams& p, double vx, double vy, double& g
     if (u > p.cw - 1) u = p.cw - 1;
     if (v < 0) v = 0;
     if (v > p.ch - 1) v = 0;
+    double ur = u, vr = v;
+    if (!p.rectified_input) {
     const double fx = p.K[0], fy = p.K[4], cx = p.K[2], cy = p.K[5];
     const double ifx = 1. / fx, ify = 1. / fy;
     const double* k = p.D;
@@ -91,7 +93,8 @@ __device__ void ground_point(const SegParams& p, double vx, double vy, double& g
     double xx = RR[0] * x + RR[1] * y + RR[2];
     double yy = RR[3] * x + RR[4] * y + RR[5];
     double ww = 1. / (RR[6] * x + RR[7] * y + RR[8]);
-    double ur = xx * ww, vr = yy * ww;
+    ur = xx * ww; vr = yy * ww;
+    }
     const double* H = p.H;
     double g0 = H[0] * ur + H[1] * vr + H[2] * 1.0;
     double g1 = H[3] * ur + H[4] * vr + H[5] * 1.0;

@@ -113,14 +113,8 @@ static int build_params(lf_handle* h)
     S.Hc = h->Hc; S.W = h->W; S.img_rows = c.img_rows; S.img_cols = c.img_cols; S.top_cutoff = c.top_cutoff;
     S.cap_lines = h->cap_lines;
     S.rx = 1.0 / (double)c.img_cols; S.ry = 1.0 / (double)c.img_rows; S.cut = (double)c.top_cutoff;
-    S.cw = (double)c.cam_w; S.ch = (double)c.cam_h;
-    memcpy(S.H, c.H, sizeof(S.H)); memcpy(S.K, c.K, sizeof(S.K)); memcpy(S.D, c.D, sizeof(S.D));
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double s = 0;
-            for (int t = 0; t < 3; ++t) s += c.P[4 * i + t] * c.R[3 * t + j];
-            S.RR[3 * i + j] = s;
-        }
+    memcpy(S.H, c.H, sizeof(S.H));
+    seg_camera(h);
     S.lanewidth = c.lanewidth; S.linewidth_white = c.linewidth_white; S.linewidth_yellow = c.linewidth_yellow;
     S.d_min = c.d_min; S.d_max = c.d_max; S.phi_min = c.phi_min; S.phi_max = c.phi_max;
     return LF_OK;

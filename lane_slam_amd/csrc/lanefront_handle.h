@@ -4,6 +4,7 @@
 #pragma once
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <memory>
 #include <utility>
 #include <vector>
@@ -47,6 +48,21 @@ struct JencState {
     hipEvent_t ev[jenc::kStages + 1] = {};          // around the stages of the last call, with profiling on
     bool timed = false;
     ~JencState()
+    {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// GroundProjection.rectify state (lanefront_rectify.hip): made on the first lf_rectify_batch, the map remade after lf_set_camera
+struct RectState {
+    DevBuf xy, frac, tab;                           // the camera's map in remap's fixed-point form (k_rectify.h) and the weight table
+    DevBuf in, out;                                 // staging of a host caller's frames
+    int w = 0, h = 0;                               // the camera the map was made for
+    bool map_ready = false;
+    int maps_built = 0;
+    hipEvent_t ev[2] = {};                          // around the kernel of the last call, with profiling on
+    bool timed = false;
+    ~RectState()
     {
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     }
@@ -264,6 +280,7 @@ struct lf_handle {
     std::vector<int> h_counts, h_seg_offset;
     std::unique_ptr<lf::JpegState> jpeg;
     std::unique_ptr<lf::JencState> jenc;  // lf_jpeg_encode_batch (lanefront_jenc.hip), allocated on first use
+    std::unique_ptr<lf::RectState> rect;  // lf_rectify_batch (lanefront_rectify.hip), allocated on first use
     std::unique_ptr<lf::KlState> kl;      // EDLines / KeyLines state (lanefront_keylines.hip), allocated on first use
     std::unique_ptr<lf::LsdKlState> lsdkl; // LSDDetectorC over octaves (lanefront_lsdkl.hip): an LSD state per pyramid level
     lf::DevBuf m_fo, m_color, m_pn, m_nm, m_gr, m_keep, m_counts, m_boff, m_body, m_bad;   // SegmentList glue scratch
@@ -293,6 +310,21 @@ inline int ensure(lf_handle* h, DevBuf& b, size_t bytes)
     if (b.bytes >= bytes) return LF_OK;
     LF_HIP_CHECK(h, b.alloc(bytes + bytes / 4 + 256));       // (hipFree of the old buffer waits for the device)
     return LF_OK;
+}
+
+// the camera of h->cfg (K, D, P . R, its size) into the parameters of a-7 (k_segments.hip); lf_create and lf_set_camera
+inline void seg_camera(lf_handle* h)
+{
+    const lf_config& c = h->cfg;
+    SegParams& S = h->seg;
+    S.cw = (double)c.cam_w; S.ch = (double)c.cam_h;
+    memcpy(S.K, c.K, sizeof(S.K)); memcpy(S.D, c.D, sizeof(S.D));
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double s = 0;
+            for (int t = 0; t < 3; ++t) s += c.P[4 * i + t] * c.R[3 * t + j];
+            S.RR[3 * i + j] = s;
+        }
 }
 
 void timing_resolve(lf_handle* h);

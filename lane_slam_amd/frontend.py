@@ -343,6 +343,60 @@ class FrontEnd(object):
         self._check(self.lib.lf_jpeg_encode_timing(self.h, _ptr(ms), ms.size))
         return dict((self.lib.lf_jpeg_encode_stage_name(k).decode(), float(ms[k])) for k in range(ms.size))
 
+    # ------------------------------------------------------------------ the camera, GroundProjection.rectify
+    def set_camera(self, K, D, R, P, cam_size):
+        """GroundProjection.initialize_pinhole_camera_model on a live handle (lf_set_camera): K (9), D (5), R (9), P (12) row major
+        and cam_size = (height, width), as the configuration holds them.  Segment undistortion and rectification use it from now on."""
+        arr = [np.ascontiguousarray(np.asarray(v, np.float64).reshape(-1)) for v in (K, D, R, P)]
+        for a, n, name in zip(arr, (9, 5, 9, 12), "KDRP"):
+            if a.size != n:
+                raise ValueError("%s must have %d entries, got %d" % (name, n, a.size))
+        cam_h, cam_w = (int(v) for v in cam_size)
+        self._check(self.lib.lf_set_camera(self.h, _ptr(arr[0]), _ptr(arr[1]), _ptr(arr[2]), _ptr(arr[3]), cam_w, cam_h))
+        self.cfg = dict(self.cfg, K=arr[0].tolist(), D=arr[1].tolist(), R=arr[2].tolist(), P=arr[3].tolist(), cam_size=[cam_h, cam_w])
+
+    def set_rectified_input(self, flag):
+        """GroundProjection.rectified_input: with True the frames are rectified already and ground projection applies the homography
+        alone (lf_set_rectified_input); False is the reference's default."""
+        self._check(self.lib.lf_set_rectified_input(self.h, int(bool(flag))))
+
+    def get_rectified_input(self):
+        v = ctypes.c_int()
+        self._check(self.lib.lf_get_rectified_input(self.h, ctypes.byref(v)))
+        return bool(v.value)
+
+    def rectify_map(self):
+        """(mapx, mapy), float32 (cam_h, cam_w) each: cv2.initUndistortRectifyMap(K, D, R, P, (w, h), CV_32FC1) for the handle's camera."""
+        cam_h, cam_w = (int(v) for v in self.cfg["cam_size"])
+        mapx, mapy = np.empty((cam_h, cam_w), np.float32), np.empty((cam_h, cam_w), np.float32)
+        self._check(self.lib.lf_rectify_map(self.h, _ptr(mapx), _ptr(mapy)))
+        return mapx, mapy
+
+    def rectify_batch(self, frames):
+        """The batched form of GroundProjection.rectify (ref: GroundProjection.py:95-101): frames uint8 (n, rows, cols) grey or
+        (n, rows, cols, 3) on the host; returns the rectified frames, (n, cam_h, cam_w[, 3]).  Queued behind the handle's work; waits."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.ndim not in (3, 4) or (frames.ndim == 4 and frames.shape[3] not in (1, 3)):
+            raise ValueError("frames must be (n, rows, cols) or (n, rows, cols, 1 or 3) uint8, got %r" % (frames.shape,))
+        n, rows, cols = frames.shape[:3]
+        channels = 1 if frames.ndim == 3 else frames.shape[3]
+        cam_h, cam_w = (int(v) for v in self.cfg["cam_size"])
+        out = np.empty((n, cam_h, cam_w) + frames.shape[3:], np.uint8)
+        self._check(self.lib.lf_rectify_batch(self.h, _ptr(frames), 0, n, rows, cols, channels, _ptr(out), 0))
+        return out
+
+    def rectify_device(self, src_ptr, n_frames, rows, cols, channels, dst_ptr):
+        """Device form of rectify_batch: n_frames x rows x cols x channels bytes at src_ptr, n_frames x cam_h x cam_w x channels
+        bytes to dst_ptr.  Queued on the handle's stream; returns at once."""
+        self._check(self.lib.lf_rectify_batch(self.h, ctypes.c_void_p(int(src_ptr)), 1, int(n_frames), int(rows), int(cols), int(channels),
+                                              ctypes.c_void_p(int(dst_ptr)), 1))
+
+    def rectify_timing(self):
+        """{kernel name: ms} of the last rectify call that ran with set_profiling(True) (HIP events)."""
+        ms = np.zeros(_lib.LF_RECTIFY_STAGES, np.float64)
+        self._check(self.lib.lf_rectify_timing(self.h, _ptr(ms), ms.size))
+        return dict((self.lib.lf_rectify_stage_name(k).decode(), float(ms[k])) for k in range(ms.size))
+
     # ------------------------------------------------------------------ association
     def set_tie_rule(self, rule):
         """Which of several equally near map codes `associate` returns: "mihasher" (the default: the one the reference's
