@@ -464,6 +464,66 @@ LF_API int lf_map_set_profiling(lf_map* m, int enabled);
 LF_API int lf_map_get_timing(lf_map* m, double* ms_per_stage, int32_t* launches_per_stage, int n);
 LF_API const char* lf_map_stage_name(int stage);
 
+/* ---- the live map, seen from above: lf_map_render ------------------------------------------------
+ * The picture the reference's README shows: show_map.py publishes one LINE_LIST marker per segment, white, yellow or red
+ * (src/show_map/src/show_map.py:44-72), odometry.py a blue LINE_STRIP of the trajectory (src/odometry/src/odometry.py:50-62), and
+ * RViz draws them with show_map/rviz_conf/map_view.rviz: TopDownOrtho, Scale 30, Angle 0, background 48; 48; 48.  RViz has no
+ * pixel-level behaviour to match, so the pixels are this package's OWN contract, written so that a sequential painter
+ * (tests/map_render_ref.py) and the tiled kernels (k_map_render.hip) agree byte for byte.  The image is BGR, [rows][cols][3], and
+ * can go straight into lf_jpeg_encode_batch.
+ *
+ *   pixel of (X, Y)   x to the right, y up:  u = floor((X - x_min) * ppm)  (column),  v = floor((y_max - Y) * ppm)  (row)
+ *                     (f64, unfused: a subtraction, then a multiplication).  An entry one of whose four pixel coordinates -- the
+ *                     floored f64 values -- is not finite or has magnitude >= 2^28 is SKIPPED: counted, not drawn.
+ *   line (u0, v0) -> (u1, v1), the entry's stored endpoint order; dx = u1 - u0, dy = v1 - v0.  |dx| >= |dy| (x-major), n = |dx|:
+ *                     for i = 0 .. n the pixel (u0 + i sgn(dx), v0 + sgn(dy) floor((2 i |dy| + n) / (2 n))); n = 0: the one pixel.
+ *                     Otherwise (y-major) the same with the roles exchanged.  This is the midpoint line in closed form: every i
+ *                     stands alone, clipping restricts i and never changes a pixel, and 64-bit integers hold it all.
+ *   thickness t       a line pixel (u, v) paints columns u - (t - 1) / 2 .. u + t / 2 and rows v - (t - 1) / 2 .. v + t / 2
+ *                     (integer division); pixels outside the image are dropped one by one.
+ *   colour (BGR)      colour 0 white (255, 255, 255), 1 yellow (0, 255, 255), every other value red (0, 0, 255): show_map.py:59-70
+ *   the winner        of a pixel, among the drawn entries that paint it: the largest (last_seen, slot), slot as lf_map_fetch
+ *                     numbers it.  A property of the map's state, not of scheduling: two renders give the same bytes.
+ *   trajectory        host f64 [n_points][2], map frame, or NULL / n_points 0: consecutive points are joined by lines of the same
+ *                     thickness in blue (255, 0, 0) (odometry.py:59-61), above every entry, a later line above an earlier one; a
+ *                     line with a skipped endpoint is skipped; one point alone draws nothing.
+ *   n_drawn           the entries that pass the three filters and are not skipped, whether or not a pixel of theirs is inside the
+ *                     image; n_skipped those that pass and are skipped.  Trajectory lines are counted in both like entries.
+ * lf_map_render reads the map and never changes it; it runs on the map's stream in call order, so it sees exactly the updates
+ * queued before it.  It waits once for that stream (the size of the per-tile lists is read back); with out_on_device = 1 the
+ * image itself is still being painted when it returns (lf_map_synchronize, or stream order).  A pending failing update is
+ * reported by the calls that report it (above), not by these.  A bad view -- rows, cols or thickness out of range,
+ * pixels_per_metre not finite or <= 0, x_min or y_max not finite, out NULL, n_points < 0 -- is LF_ERR_BAD_ARG and touches nothing;
+ * more than 2^30 (line, tile) pairs are LF_ERR_CAPACITY. */
+typedef struct lf_map_view {
+    int32_t rows, cols;          /* 1 .. 8192 each */
+    double  x_min, y_max;        /* map-frame metres of the top-left corner of pixel (row 0, col 0) */
+    double  pixels_per_metre;    /* finite, > 0 */
+    int32_t thickness;           /* 1 .. 16 pixels */
+    int32_t min_hits;            /* entries with hits < min_hits are left out (1 = all) */
+    int32_t min_last_seen;       /* entries with last_seen < this are left out (-1 = all: seeded entries have -1) */
+    uint32_t color_mask;         /* bit c: draw entries of colour c = 0 (white), 1 (yellow), 2 (red); bit 3: every other colour value */
+    uint8_t background[3];       /* BGR */
+    uint8_t pad_[1];
+} lf_map_view;
+
+/* the reference's RViz view: 512 x 512 at 30 pixels per metre, the origin in the centre (x_min = -cols / (2 ppm), y_max = rows /
+ * (2 ppm)), thickness 1, min_hits 1, min_last_seen -1, mask 0xF, background (48, 48, 48) */
+LF_API void lf_map_default_view(lf_map_view* v);
+/* xmin, ymin, xmax, ymax over the finite endpoints (x and y both finite) of the entries the view's three filters (min_hits,
+ * min_last_seen, color_mask) select (v == NULL: all entries); *n_entries = how many entries contributed an endpoint.  0 entries:
+ * bounds4 untouched.  Waits for the map's stream. */
+LF_API int lf_map_bounds(lf_map* m, const lf_map_view* v, double* bounds4, int* n_entries);
+/* out: [rows][cols][3] u8, on the device (out_on_device = 1) or on the host (returns when the image is in place).  n_drawn /
+ * n_skipped may be NULL; lf_map_render_counts returns those of the last render again. */
+LF_API int lf_map_render(lf_map* m, const lf_map_view* v, const double* trajectory, int n_points, uint8_t* out, int out_on_device,
+                  int* n_drawn, int* n_skipped);
+LF_API int lf_map_render_counts(lf_map* m, int* n_drawn, int* n_skipped);     /* of the last render; waits for it */
+/* per-kernel time of the last render with profiling on (lf_map_set_profiling), as lf_rectify_timing: 0 project, 1 scan, 2 bin, 3 paint */
+#define LF_MAP_RENDER_STAGES 4
+LF_API int lf_map_render_timing(lf_map* m, double* ms_per_stage, int n);
+LF_API const char* lf_map_render_stage_name(int stage);
+
 /* ---- Histogram lane filter: lane pose from ground segments -----------------------------------------
  * LaneFilterHistogram (src/lane_filter/include/lane_filter/lane_filter.py:12-161) as lane_filter_node.processSegments
  * drives it (src/lane_filter/src/lane_filter_node.py:49-87): per frame predict(dt, v, w) -> update(segments) ->

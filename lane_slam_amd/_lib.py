@@ -40,7 +40,9 @@ EXPORTS = (
     "lf_jpeg_encode_bound", "lf_jpeg_encode_batch", "lf_jpeg_encode_timing", "lf_jpeg_encode_stage_name",
     "lf_set_camera", "lf_set_rectified_input", "lf_get_rectified_input", "lf_rectify_map", "lf_rectify_batch", "lf_rectify_timing",
     "lf_rectify_stage_name",
+    "lf_map_default_view", "lf_map_bounds", "lf_map_render", "lf_map_render_counts", "lf_map_render_timing", "lf_map_render_stage_name",
 )
+LF_MAP_RENDER_STAGES = 4
 LF_JPEG_ENCODE_STAGES = 8
 LF_RECTIFY_STAGES = 1
 LF_LANE_FILTER_PREDICT, LF_LANE_FILTER_UPDATE = 1, 2
@@ -130,6 +132,14 @@ class LfMapConfig(ctypes.Structure):
     """ctypes mirror of `lf_map_config` (include/lanefront.h)."""
     _fields_ = [(k, ctypes.c_int32) for k in ("capacity", "color_gating", "max_distance", "policy", "kept_only",
                                               "merge_distance", "when_full")]
+
+
+class LfMapView(ctypes.Structure):
+    """ctypes mirror of `lf_map_view` (include/lanefront.h)."""
+    _fields_ = [("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("x_min", ctypes.c_double), ("y_max", ctypes.c_double),
+                ("pixels_per_metre", ctypes.c_double), ("thickness", ctypes.c_int32), ("min_hits", ctypes.c_int32),
+                ("min_last_seen", ctypes.c_int32), ("color_mask", ctypes.c_uint32), ("background", ctypes.c_uint8 * 3),
+                ("pad_", ctypes.c_uint8 * 1)]
 
 
 _lib = None
@@ -249,6 +259,16 @@ def load():
     lib.lf_map_get_timing.restype = ci
     lib.lf_map_stage_name.argtypes = [ci]
     lib.lf_map_stage_name.restype = ctypes.c_char_p
+    lib.lf_map_default_view.argtypes = [ctypes.POINTER(LfMapView)]
+    lib.lf_map_default_view.restype = None
+    lib.lf_map_bounds.argtypes = [vp, ctypes.POINTER(LfMapView), vp, ctypes.POINTER(ci)]
+    lib.lf_map_render.argtypes = [vp, ctypes.POINTER(LfMapView), vp, ci, vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.lf_map_render_counts.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.lf_map_render_timing.argtypes = [vp, vp, ci]
+    for f in ("lf_map_bounds", "lf_map_render", "lf_map_render_counts", "lf_map_render_timing"):
+        getattr(lib, f).restype = ci
+    lib.lf_map_render_stage_name.argtypes = [ci]
+    lib.lf_map_render_stage_name.restype = ctypes.c_char_p
     lib.lf_descriptor_default_params.argtypes = [ctypes.POINTER(LfDescriptorParams)]
     lib.lf_descriptor_default_params.restype = None
     lib.lf_set_descriptor_params.argtypes = [vp, ctypes.POINTER(LfDescriptorParams)]

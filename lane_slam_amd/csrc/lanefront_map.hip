@@ -5,40 +5,7 @@
 #include <string.h>
 #include <new>
 #include <vector>
-#include "common.h"
-
-using namespace lf;
-
-struct lf_map {
-    lf_map_config cfg;
-    int tie_rule = LF_TIE_MIHASHER;          // the reference's tie rule (round 5)
-    int device = 0;
-    hipStream_t stream = nullptr;
-    char err[512];
-    MapDevice d;                             // the kernels' view of the arrays below
-    DevArray<uint8_t> code, color;
-    DevArray<double> ground;
-    DevArray<int> hits, last_seen, winner, state;
-    DevArray<int8_t> mx, mcx;
-    DevArray<unsigned long long> totals;
-    size_t cap_pad = 0;
-    // host mirror of the device state, refreshed behind every update
-    HostArray<int> h_state;                  // pinned: [0..15] state, then 2 x u64 totals at +16 ints
-    int errors_reported = 0;                 // failing updates (state[8]) the host has already returned an error for
-    hipEvent_t ev_state = nullptr, ev_in = nullptr, ev_out = nullptr;
-    bool state_pending = false;
-    long long rows_in_flight = 0;            // rows handed to updates whose state copy has not been seen yet
-    AssocScratch ws;
-    DevBuf act, own_block, pose, q_in, c_in, idx_out, dist_out, seed_code, seed_color, seed_ground, tie_res;
-    DevBuf st_fo, st_code, st_color, st_keep, st_ground, st_idx, st_dist;     // staging of lf_map_step_host
-    std::vector<double> h_pose;
-    // per-stage timing with HIP events on the map's stream (resolved by lf_map_get_timing)
-    struct Ev { hipEvent_t a, b; int st; };
-    bool profiling = false;
-    std::vector<Ev> ev_free, ev_used;
-    double ms[LF_MAP_N_STAGES];
-    int32_t launches[LF_MAP_N_STAGES];
-};
+#include "lanefront_map_handle.h"
 
 namespace {
 struct MapTimer {

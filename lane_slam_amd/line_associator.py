@@ -130,6 +130,95 @@ class LineAssociator(object):
                                           out["ground"].ctypes.data, out["hits"].ctypes.data, out["last_seen"].ctypes.data))
         return out
 
+    # ------------------------------------------------------------------ the map seen from above (lf_map_render)
+    def default_view(self):
+        """The reference's RViz view (map_view.rviz) as an `_lib.LfMapView`: 512 x 512 at 30 px/m, the origin in the centre."""
+        v = _lib.LfMapView()
+        self.lib.lf_map_default_view(ctypes.byref(v))
+        return v
+
+    @staticmethod
+    def _filters(v, min_hits=None, min_last_seen=None, color_mask=None):
+        if min_hits is not None:
+            v.min_hits = int(min_hits)
+        if min_last_seen is not None:
+            v.min_last_seen = int(min_last_seen)
+        if color_mask is not None:
+            v.color_mask = int(color_mask)
+        return v
+
+    def bounds(self, **filters):
+        """((xmin, ymin, xmax, ymax) or None, n_entries) over the finite endpoints of the entries that min_hits, min_last_seen and
+        color_mask select (none given: every entry)."""
+        v = self._filters(self.default_view(), **filters) if filters else None
+        b, n = np.zeros(4, np.float64), ctypes.c_int()
+        self._check(self.lib.lf_map_bounds(self.m, None if v is None else ctypes.byref(v), b.ctypes.data, ctypes.byref(n)))
+        return (tuple(float(x) for x in b) if n.value else None), n.value
+
+    def make_view(self, rows=512, cols=512, view=None, pixels_per_metre=30.0, thickness=None, x_min=None, y_max=None, background=None,
+                  **filters):
+        """An `_lib.LfMapView`.  view=None: pixels_per_metre with the origin in the centre, or the corner given by x_min / y_max;
+        view="fit": the box of `bounds(**filters)` centred in the image with a margin of `thickness` pixels, at the largest
+        pixels_per_metre that fits (an empty or one-point map keeps pixels_per_metre); an LfMapView is used as it is.
+        thickness=None: max(1, round(0.02 * pixels_per_metre)), show_map's 0.02 m marker width (show_map.py:53)."""
+        if isinstance(view, _lib.LfMapView):
+            return view
+        if view not in (None, "fit"):
+            raise ValueError("view must be None, 'fit' or an LfMapView")
+        v = self._filters(self.default_view(), **filters)
+        v.rows, v.cols = int(rows), int(cols)
+        ppm = float(pixels_per_metre)
+        cx = cy = 0.0
+        if view == "fit":
+            box, n = self.bounds(min_hits=v.min_hits, min_last_seen=v.min_last_seen, color_mask=v.color_mask)
+            if n:
+                cx, cy = 0.5 * (box[0] + box[2]), 0.5 * (box[1] + box[3])
+                w, h = box[2] - box[0], box[3] - box[1]
+                for _ in range(2):          # the margin depends on the thickness, which may depend on the scale
+                    t = int(thickness) if thickness is not None else max(1, int(round(0.02 * ppm)))
+                    t = min(t, 16)
+                    fits = [(size - 2 * t - 1) / ext for size, ext in ((v.cols, w), (v.rows, h)) if ext > 0 and size - 2 * t - 1 > 0]
+                    if fits:
+                        ppm = min(fits)
+        v.pixels_per_metre = ppm
+        v.thickness = min(16, int(thickness) if thickness is not None else max(1, int(round(0.02 * ppm))))
+        v.x_min = float(x_min) if x_min is not None else cx - v.cols / (2.0 * ppm)
+        v.y_max = float(y_max) if y_max is not None else cy + v.rows / (2.0 * ppm)
+        if background is not None:
+            v.background[0], v.background[1], v.background[2] = (int(c) for c in background)
+        return v
+
+    def render_device(self, out_ptr, rows=512, cols=512, view=None, pixels_per_metre=30.0, thickness=None, trajectory=None, **kw):
+        """Render the map into device memory at out_ptr ([rows][cols][3] u8, BGR) on the map's stream; returns
+        (n_drawn, n_skipped, view).  The image is complete after `synchronize()` (or in stream order)."""
+        return self._render(int(out_ptr), 1, self.make_view(rows, cols, view, pixels_per_metre, thickness, **kw), trajectory)
+
+    def render(self, rows=512, cols=512, view=None, pixels_per_metre=30.0, thickness=None, trajectory=None, counts=False, **kw):
+        """The map as a (rows, cols, 3) uint8 BGR ndarray: white, yellow and red segments, the newest on top, `trajectory`
+        ((n, 2) map-frame points) in blue above them.  counts=True: (image, n_drawn, n_skipped)."""
+        v = self.make_view(rows, cols, view, pixels_per_metre, thickness, **kw)
+        out = np.empty((v.rows, v.cols, 3), np.uint8)
+        nd, ns, _ = self._render(out.ctypes.data, 0, v, trajectory)
+        return (out, nd, ns) if counts else out
+
+    def _render(self, out_ptr, on_device, v, trajectory):
+        tr = None if trajectory is None else np.ascontiguousarray(trajectory, np.float64).reshape(-1, 2)
+        nd, ns = ctypes.c_int(), ctypes.c_int()
+        self._check(self.lib.lf_map_render(self.m, ctypes.byref(v), None if tr is None or not len(tr) else tr.ctypes.data,
+                                           0 if tr is None else len(tr), out_ptr, on_device, ctypes.byref(nd), ctypes.byref(ns)))
+        return nd.value, ns.value, v
+
+    def render_counts(self):
+        nd, ns = ctypes.c_int(), ctypes.c_int()
+        self._check(self.lib.lf_map_render_counts(self.m, ctypes.byref(nd), ctypes.byref(ns)))
+        return nd.value, ns.value
+
+    def render_timing(self):
+        """{kernel: ms} of the last render (needs set_profiling(True))."""
+        ms = np.zeros(_lib.LF_MAP_RENDER_STAGES, np.float64)
+        self._check(self.lib.lf_map_render_timing(self.m, ms.ctypes.data, _lib.LF_MAP_RENDER_STAGES))
+        return {self.lib.lf_map_render_stage_name(i).decode(): float(ms[i]) for i in range(_lib.LF_MAP_RENDER_STAGES)}
+
     # ------------------------------------------------------------------ device resident
     @staticmethod
     def _segs(out_ptrs):

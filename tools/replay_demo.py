@@ -4,7 +4,10 @@ messages -> batched ingest -> detect / describe / project / sanity -> associatio
 receives the kept segments (append-only, src/show_map/src/show_map.py:28-42) -> the three SegmentList topics'
 wire bodies.  The first batch is checked against the oracle (pixels, segments, matches); the rest is timed.
 
-    python tools/replay_demo.py [--frames 1024] [--batch 128] [--threads 32] [--geometry fullres|parity]
+    python tools/replay_demo.py [--frames 1024] [--batch 128] [--threads 32] [--geometry fullres|parity] [--map-jpeg map.jpg]
+
+--map-jpeg writes the final map as the reference's README shows it (show_map's coloured segments seen from above, lf_map_render
+fitted to the map) as a JPEG: rendered and encoded on the device, only the file's bytes cross the bus.
 """
 import argparse, io, os, sys, time
 import numpy as np
@@ -22,6 +25,8 @@ ap.add_argument("--batch", type=int, default=128)
 ap.add_argument("--threads", type=int, default=32)
 ap.add_argument("--geometry", default="fullres", choices=["fullres", "parity"])
 ap.add_argument("--map", type=int, default=50000)
+ap.add_argument("--map-jpeg", default=None, help="write the final map, rendered and JPEG-encoded on the device, to this file")
+ap.add_argument("--map-size", type=int, default=1024, help="rows = cols of that picture")
 args = ap.parse_args()
 torch.cuda.init()
 B = args.batch
@@ -80,3 +85,20 @@ dt = time.perf_counter() - t0
 nb = (args.frames // B) * B
 print("replayed %d frames in %.2f s: %.0f frames/s (synchronous, host-resident results, one handle); %d segments, %d kept, "
       "%d matched within 128 bits, map %d codes, %.1f MB of SegmentList bodies" % (nb, dt, nb / dt, n_seg, n_kept, n_matched, live.state()["size"], wire / 1e6))
+
+if args.map_jpeg:
+    side = args.map_size
+    image = torch.empty((1, side, side, 3), dtype=torch.uint8, device="cuda")
+    stride = fe.jpeg_encode_bound(side, side)
+    files = torch.zeros(stride, dtype=torch.uint8, device="cuda")
+    sizes = torch.zeros(1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    n_drawn, n_skipped, view = live.render_device(image.data_ptr(), rows=side, cols=side, view="fit", min_last_seen=0)     # (the seeded codes have no place)
+    live.synchronize()
+    fe.encode_jpeg_device(image.data_ptr(), 1, side, side, files.data_ptr(), stride, sizes.data_ptr())
+    fe.synchronize()
+    size = int(sizes.cpu()[0])
+    with open(args.map_jpeg, "wb") as f:
+        f.write(files[:size].cpu().numpy().tobytes())
+    print("map: %d segments drawn (%d skipped) at %.1f px/m, thickness %d -> %s (%d bytes, %d x %d)"
+          % (n_drawn, n_skipped, view.pixels_per_metre, view.thickness, args.map_jpeg, size, side, side))
