@@ -524,6 +524,65 @@ LF_API int lf_map_render_counts(lf_map* m, int* n_drawn, int* n_skipped);     /*
 LF_API int lf_map_render_timing(lf_map* m, double* ms_per_stage, int n);
 LF_API const char* lf_map_render_stage_name(int stage);
 
+/* ---- the live map, seen through the camera: lf_map_render_camera -----------------------------------
+ * The reference's augmented reality (duckietown_utils/augmented_reality_utils.py): BaseAugmenter.render_segments draws every map
+ * segment with cv2.line(..., 5) at the pixels ground2pixel returns, and the rectified branch of GroundProjection.ground2pixel
+ * (GroundProjection.py:80-93) is Hinv . (x, y, 1), normalised.  The reference leaves BaseAugmenter.ground2pixel as `pass` and
+ * GroundProjection.ground2pixel returns nothing, so, as for lf_map_render, the pixels are this package's OWN contract, written so
+ * that a sequential painter (tests/map_camera_ref.py) and the tiled kernels (k_map_camera.hip) agree byte for byte.  A call draws
+ * the map into n_frames RECTIFIED frames (lf_rectify_batch), BGR [n_frames][rows][cols][3], each at its own pose.
+ *
+ * Frame f, all f64 and unfused:
+ *   pose              (x, y, theta) = frame_pose[3 f ..], map -> duck as lf_map_pack_block takes it, cs = cos(theta), sn = sin(theta)
+ *                     by the same routine; frame_pose NULL: (0, 0, 0) for every frame -- the entries are in the robot frame already.
+ *   robot frame       of an endpoint (X, Y): dx = X - x, dy = Y - y, px = cs dx + sn dy, py = cs dy - sn dx: the inverse of
+ *                     lf_map_pack_block's transform.
+ *   homogeneous pixel q_k = (h_k0 px + h_k1 py) + h_k2 for k = x, y, z, h = hinv row by row.
+ *   clip              endpoints a, b in stored order.  q_z < w_near at both: the entry is BEHIND, counted and not drawn.  At exactly
+ *                     one, say a: t = (w_near - a_z) / (b_z - a_z), a'_k = a_k + t (b_k - a_k) for k = x, y, a'_z = w_near exactly;
+ *                     the same with the roles exchanged for b.  The order of the endpoints is kept.
+ *   pixel             u = floor((q_x / q_z) (cols / cam_w)), v = floor((q_y / q_z) ((rows + top_cutoff) / cam_h)) - top_cutoff; the
+ *                     two scale factors are f64 quotients, computed once.  An entry one of whose four floored values, before the
+ *                     cutoff is subtracted, is not finite or has magnitude >= 2^28 is SKIPPED: counted, not drawn.
+ *   line, thickness, the winner of a pixel: exactly lf_map_render's (the largest (last_seen, slot)); there is no trajectory.
+ *   colour            palette[min(colour, palette_size - 1)]; color_mask as lf_map_view's: bit 3 stands for every colour value >= 3.
+ *   out[f]            src[f] with the painted pixels replaced, every other byte identical to src; src NULL: the background colour
+ *                     there; src == out works in place (any other overlap of the two is not supported).  on_device applies to src
+ *                     and out; with host arrays the call returns when out is in place, with device arrays the frames are still
+ *                     being painted when it returns (lf_map_synchronize, or stream order).
+ *   counts[f]         {n_drawn, n_skipped, n_behind} over the entries that pass the three filters; n_drawn: neither skipped nor
+ *                     behind, whether or not a pixel of theirs is inside the image.  May be NULL.
+ * The call reads the map and never changes it, runs on the map's stream in call order and waits once for that stream, as
+ * lf_map_render does.  LF_ERR_BAD_ARG, touching nothing: a NULL view or out, n_frames outside 1 .. 4096, rows, cols, thickness or
+ * palette_size out of range, cam_w or cam_h <= 0, top_cutoff < 0 or > 2^24, a non-finite hinv entry, w_near not finite or <= 0, a
+ * non-finite pose.  More than 2^30 (line, tile) pairs over the batch are LF_ERR_CAPACITY. */
+typedef struct lf_camera_view {
+    int32_t rows, cols;          /* the images drawn on, 1 .. 8192 each */
+    int32_t top_cutoff;          /* rows cut off above the image (line_detector_node's crop), 0 .. 2^24 */
+    int32_t cam_w, cam_h;        /* the image size the homography was calibrated for (640 x 480) */
+    double  hinv[9];             /* ground -> rectified pixel, row major, scaled so that visible ground has q_z > 0 */
+    double  w_near;              /* finite, > 0: the clip value of q_z */
+    int32_t thickness;           /* 1 .. 16, the brush of lf_map_render */
+    int32_t min_hits, min_last_seen;
+    uint32_t color_mask;
+    int32_t palette_size;        /* 1 .. 8 */
+    uint8_t palette[8][3];       /* BGR of colour values 0 .. palette_size - 1; larger values take the last */
+    uint8_t background[3];       /* BGR, used when src == NULL */
+    uint8_t pad_[1];
+} lf_camera_view;
+LF_API int lf_sizeof_camera_view(void);
+/* The default view of a camera with homography H (pixel -> ground, row major, as lf_config.H), on the host in f64: hinv = the
+ * adjugate of H over its determinant, then divided by s = (hinv . g)_z for g = H . (cam_w / 2, cam_h - 1, 1), g /= g_z -- the ground
+ * point seen at the bottom centre has q_z = 1, which also fixes the sign; w_near 0.25, thickness 5, min_hits 1, min_last_seen -1,
+ * mask 0xF, palette white / yellow / red (size 3: every other colour value is red, as lf_map_render), background (48, 48, 48).
+ * cam_w / 2 is the integer quotient.  LF_ERR_BAD_ARG for a NULL, singular or non-finite H, s == 0 or not finite, cam_w or cam_h <= 0. */
+LF_API int lf_map_camera_view(const double* H, int cam_w, int cam_h, int rows, int cols, int top_cutoff, lf_camera_view* v);
+LF_API int lf_map_render_camera(lf_map* m, const lf_camera_view* v, const double* frame_pose, int n_frames, const uint8_t* src, uint8_t* out,
+                         int on_device, int32_t* counts /* [n_frames][3] or NULL */);
+/* per-kernel time of the last lf_map_render_camera with profiling on: the four stages of lf_map_render_stage_name (3 bin is the
+ * second run of the project kernel, which writes the lists) */
+LF_API int lf_map_render_camera_timing(lf_map* m, double* ms_per_stage, int n);
+
 /* ---- Histogram lane filter: lane pose from ground segments -----------------------------------------
  * LaneFilterHistogram (src/lane_filter/include/lane_filter/lane_filter.py:12-161) as lane_filter_node.processSegments
  * drives it (src/lane_filter/src/lane_filter_node.py:49-87): per frame predict(dt, v, w) -> update(segments) ->

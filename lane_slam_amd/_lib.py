@@ -41,6 +41,7 @@ EXPORTS = (
     "lf_set_camera", "lf_set_rectified_input", "lf_get_rectified_input", "lf_rectify_map", "lf_rectify_batch", "lf_rectify_timing",
     "lf_rectify_stage_name",
     "lf_map_default_view", "lf_map_bounds", "lf_map_render", "lf_map_render_counts", "lf_map_render_timing", "lf_map_render_stage_name",
+    "lf_sizeof_camera_view", "lf_map_camera_view", "lf_map_render_camera", "lf_map_render_camera_timing",
 )
 LF_MAP_RENDER_STAGES = 4
 LF_JPEG_ENCODE_STAGES = 8
@@ -139,6 +140,15 @@ class LfMapView(ctypes.Structure):
     _fields_ = [("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("x_min", ctypes.c_double), ("y_max", ctypes.c_double),
                 ("pixels_per_metre", ctypes.c_double), ("thickness", ctypes.c_int32), ("min_hits", ctypes.c_int32),
                 ("min_last_seen", ctypes.c_int32), ("color_mask", ctypes.c_uint32), ("background", ctypes.c_uint8 * 3),
+                ("pad_", ctypes.c_uint8 * 1)]
+
+
+class LfCameraView(ctypes.Structure):
+    """ctypes mirror of `lf_camera_view` (include/lanefront.h)."""
+    _fields_ = [("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("top_cutoff", ctypes.c_int32), ("cam_w", ctypes.c_int32),
+                ("cam_h", ctypes.c_int32), ("hinv", ctypes.c_double * 9), ("w_near", ctypes.c_double), ("thickness", ctypes.c_int32),
+                ("min_hits", ctypes.c_int32), ("min_last_seen", ctypes.c_int32), ("color_mask", ctypes.c_uint32),
+                ("palette_size", ctypes.c_int32), ("palette", (ctypes.c_uint8 * 3) * 8), ("background", ctypes.c_uint8 * 3),
                 ("pad_", ctypes.c_uint8 * 1)]
 
 
@@ -269,6 +279,12 @@ def load():
         getattr(lib, f).restype = ci
     lib.lf_map_render_stage_name.argtypes = [ci]
     lib.lf_map_render_stage_name.restype = ctypes.c_char_p
+    lib.lf_sizeof_camera_view.argtypes = []
+    lib.lf_map_camera_view.argtypes = [vp, ci, ci, ci, ci, ci, ctypes.POINTER(LfCameraView)]
+    lib.lf_map_render_camera.argtypes = [vp, ctypes.POINTER(LfCameraView), vp, ci, vp, vp, ci, vp]
+    lib.lf_map_render_camera_timing.argtypes = [vp, vp, ci]
+    for f in ("lf_sizeof_camera_view", "lf_map_camera_view", "lf_map_render_camera", "lf_map_render_camera_timing"):
+        getattr(lib, f).restype = ci
     lib.lf_descriptor_default_params.argtypes = [ctypes.POINTER(LfDescriptorParams)]
     lib.lf_descriptor_default_params.restype = None
     lib.lf_set_descriptor_params.argtypes = [vp, ctypes.POINTER(LfDescriptorParams)]

@@ -1,5 +1,7 @@
 // The live map's handle (lanefront_map.hip), shared with the translation unit that renders it (lanefront_map_render.hip).
 #pragma once
+#include <stdarg.h>
+#include <stdio.h>
 #include <memory>
 #include <vector>
 #include "common.h"
@@ -18,6 +20,19 @@ struct MapRenderState {
     {
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
         if (done) (void)hipEventDestroy(done);
+    }
+};
+
+// what lf_map_render_camera keeps between calls (lanefront_map_camera.hip)
+struct MapCameraState {
+    DevBuf tiles, rec, pose, counters, frames;               // tiles: count | start | cursor, [3][n_frames x tiles]; frames: host images staged
+    HostArray<int> h_counters;                               // pinned: grows with the frames
+    std::vector<double> h_pose;
+    bool rendered = false, timed = false;
+    hipEvent_t ev[8] = {};                                   // a pair per stage
+    ~MapCameraState()
+    {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -55,4 +70,54 @@ struct lf_map {
     double ms[LF_MAP_N_STAGES];
     int32_t launches[LF_MAP_N_STAGES];
     std::unique_ptr<lf::MapRenderState> render;   // lf_map_render / lf_map_bounds (lanefront_map_render.hip), made by their first call
+    std::unique_ptr<lf::MapCameraState> camera;   // lf_map_render_camera (lanefront_map_camera.hip), likewise
 };
+
+// ---- what the translation units that draw the map share (lanefront_map_render.hip, lanefront_map_camera.hip)
+inline void map_draw_error(lf_map* m, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(m->err, sizeof(m->err), fmt, ap);
+    va_end(ap);
+}
+
+#define MAP_DRAW_HIP(m, expr)                                                                          \
+    do {                                                                                               \
+        hipError_t _e = (expr);                                                                        \
+        if (_e != hipSuccess) {                                                                        \
+            map_draw_error((m), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+            return LF_ERR_HIP;                                                                         \
+        }                                                                                              \
+    } while (0)
+
+// a scratch buffer of at least `bytes`; what it held is lost (kernels of an earlier call may still use it: wait for them first)
+inline int map_draw_scratch(lf_map* m, DevBuf& b, size_t bytes)
+{
+    if (b.bytes >= bytes) return LF_OK;
+    if (b.p) { MAP_DRAW_HIP(m, hipStreamSynchronize(m->stream)); b.reset(); }
+    MAP_DRAW_HIP(m, b.alloc(bytes + bytes / 4 + 256));
+    return LF_OK;
+}
+
+// HIP events around stage `st` of a drawing call when its state is timed (State: MapRenderState or MapCameraState)
+template <typename State>
+struct MapStageTimer {
+    lf_map* m; State* e; int st;
+    MapStageTimer(lf_map* m_, State* e_, int st_) : m(m_), e(e_), st(st_) { if (e->timed) (void)hipEventRecord(e->ev[2 * st], m->stream); }
+    ~MapStageTimer() { if (e->timed) (void)hipEventRecord(e->ev[2 * st + 1], m->stream); }
+};
+
+// the per-stage milliseconds of the last timed call of a state, n_stages of them
+template <typename State>
+inline int map_draw_timing(lf_map* m, State& e, int n_stages, double* ms_per_stage)
+{
+    MAP_DRAW_HIP(m, hipSetDevice(m->device));
+    MAP_DRAW_HIP(m, hipEventSynchronize(e.ev[2 * n_stages - 1]));
+    for (int st = 0; st < n_stages; ++st) {
+        float ms = 0.f;
+        MAP_DRAW_HIP(m, hipEventElapsedTime(&ms, e.ev[2 * st], e.ev[2 * st + 1]));
+        ms_per_stage[st] = ms;
+    }
+    return LF_OK;
+}

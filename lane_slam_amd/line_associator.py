@@ -219,6 +219,87 @@ class LineAssociator(object):
         self._check(self.lib.lf_map_render_timing(self.m, ms.ctypes.data, _lib.LF_MAP_RENDER_STAGES))
         return {self.lib.lf_map_render_stage_name(i).decode(): float(ms[i]) for i in range(_lib.LF_MAP_RENDER_STAGES)}
 
+    # ------------------------------------------------------------------ the map seen through the camera (lf_map_render_camera)
+    def camera_view(self, rows, cols, top_cutoff=0, H=None, cam_size=None, **overrides):
+        """The default `_lib.LfCameraView` (lf_map_camera_view) of images rows x cols with top_cutoff rows cut off above them.  H
+        (pixel -> ground, 9 values) and cam_size = (height, width) default to those of `default_config()` -- the package's default
+        camera, NOT what a FrontEnd was configured with: the map knows no camera, so a caller with another calibration passes its
+        cfg["H"] and cfg["cam_size"].  overrides: any field of the
+        view -- thickness, w_near, min_hits, min_last_seen, color_mask, background, palette (a list of 1 .. 8 BGR triples)."""
+        from .config import default_config
+        cfg = default_config()
+        Hm = np.ascontiguousarray(cfg["H"] if H is None else H, np.float64).reshape(9)
+        cam_h, cam_w = (int(c) for c in (cfg["cam_size"] if cam_size is None else cam_size))
+        v = _lib.LfCameraView()
+        if self.lib.lf_map_camera_view(Hm.ctypes.data, cam_w, cam_h, int(rows), int(cols), int(top_cutoff), ctypes.byref(v)) != 0:
+            raise ValueError("camera_view: H must be finite and invertible, cam_size positive")
+        for k, val in overrides.items():
+            if k == "palette":
+                pal = np.asarray(val, np.uint8).reshape(-1, 3)
+                if not 1 <= len(pal) <= 8:
+                    raise ValueError("palette holds 1 .. 8 BGR triples")
+                v.palette_size = len(pal)
+                for i, bgr in enumerate(pal):
+                    for c in range(3):
+                        v.palette[i][c] = int(bgr[c])
+            elif k == "background":
+                for c in range(3):
+                    v.background[c] = int(val[c])
+            elif k == "hinv":
+                for i, h in enumerate(np.asarray(val, np.float64).reshape(9)):
+                    v.hinv[i] = float(h)
+            elif k in ("thickness", "min_hits", "min_last_seen", "color_mask", "palette_size", "cam_w", "cam_h"):
+                setattr(v, k, int(val))
+            elif k == "w_near":
+                v.w_near = float(val)
+            else:
+                raise TypeError("camera_view: unknown field %r" % (k,))
+        return v
+
+    def render_camera(self, frames, poses=None, view=None, counts=False):
+        """The map drawn into rectified frames: frames is an (n, rows, cols, 3) uint8 BGR array, or None for one frame of the view's
+        background (view is needed then; n = len(poses) when poses are given).  poses: (n, 3) map -> duck (x, y, theta) per frame,
+        None = the map is in the robot frame.  view: an LfCameraView (camera_view), None = the default for the frames' size.
+        Returns a new array; counts=True: (images, (n, 3) int32 of n_drawn, n_skipped, n_behind)."""
+        if frames is None:
+            if view is None:
+                raise ValueError("render_camera: frames=None needs a view")
+            n = 1 if poses is None else len(np.asarray(poses).reshape(-1, 3))
+            src = None
+            out = np.empty((n, view.rows, view.cols, 3), np.uint8)
+        else:
+            src = np.ascontiguousarray(frames, np.uint8)
+            if src.ndim != 4 or src.shape[3] != 3:
+                raise ValueError("render_camera: frames must be (n, rows, cols, 3) uint8")
+            n = src.shape[0]
+            if view is None:
+                view = self.camera_view(src.shape[1], src.shape[2])
+            if (view.rows, view.cols) != src.shape[1:3]:
+                raise ValueError("render_camera: the view is %d x %d, the frames are %d x %d" % ((view.rows, view.cols) + src.shape[1:3]))
+            out = np.empty_like(src)
+        c = self._render_camera(None if src is None else src.ctypes.data, out.ctypes.data, n, poses, view, 0)
+        return (out, c) if counts else out
+
+    def render_camera_device(self, src_ptr, out_ptr, n_frames, poses=None, view=None):
+        """Draw the map into n_frames device-resident frames on the map's stream: out = src with the map painted over it (src_ptr
+        None or 0: the background; src_ptr == out_ptr: in place).  Returns the (n_frames, 3) counts; the frames are complete after
+        `synchronize()` (or in stream order)."""
+        if view is None:
+            raise ValueError("render_camera_device: a view is needed (camera_view)")
+        return self._render_camera(int(src_ptr) if src_ptr else None, int(out_ptr), int(n_frames), poses, view, 1)
+
+    def _render_camera(self, src_ptr, out_ptr, n, poses, view, on_device):
+        pose_array, pp = self._poses(poses, n)            # (pp points into pose_array: it lives until the call has returned)
+        c = np.zeros((n, 3), np.int32)
+        self._check(self.lib.lf_map_render_camera(self.m, ctypes.byref(view), pp, n, src_ptr, out_ptr, on_device, c.ctypes.data))
+        return c
+
+    def render_camera_timing(self):
+        """{kernel: ms} of the last render_camera (needs set_profiling(True))."""
+        ms = np.zeros(_lib.LF_MAP_RENDER_STAGES, np.float64)
+        self._check(self.lib.lf_map_render_camera_timing(self.m, ms.ctypes.data, _lib.LF_MAP_RENDER_STAGES))
+        return {self.lib.lf_map_render_stage_name(i).decode(): float(ms[i]) for i in range(_lib.LF_MAP_RENDER_STAGES)}
+
     # ------------------------------------------------------------------ device resident
     @staticmethod
     def _segs(out_ptrs):

@@ -5,9 +5,13 @@ receives the kept segments (append-only, src/show_map/src/show_map.py:28-42) -> 
 wire bodies.  The first batch is checked against the oracle (pixels, segments, matches); the rest is timed.
 
     python tools/replay_demo.py [--frames 1024] [--batch 128] [--threads 32] [--geometry fullres|parity] [--map-jpeg map.jpg]
+                                [--overlay-jpeg DIR]
 
 --map-jpeg writes the final map as the reference's README shows it (show_map's coloured segments seen from above, lf_map_render
 fitted to the map) as a JPEG: rendered and encoded on the device, only the file's bytes cross the bus.
+--overlay-jpeg replays the frames once more when the map is final: each batch is decoded, rectified (lf_rectify_batch), has the map
+drawn into it as the camera sees it (lf_map_render_camera; the replay has no odometry, so every frame's pose is the identity, as the
+map's entries are in the robot frame) and is encoded on the device; the files go to DIR/%06d.jpg.
 """
 import argparse, io, os, sys, time
 import numpy as np
@@ -27,6 +31,8 @@ ap.add_argument("--geometry", default="fullres", choices=["fullres", "parity"])
 ap.add_argument("--map", type=int, default=50000)
 ap.add_argument("--map-jpeg", default=None, help="write the final map, rendered and JPEG-encoded on the device, to this file")
 ap.add_argument("--map-size", type=int, default=1024, help="rows = cols of that picture")
+ap.add_argument("--overlay-jpeg", default=None, metavar="DIR",
+                help="write every replayed frame, rectified and with the final map drawn into it on the device, as DIR/%%06d.jpg")
 args = ap.parse_args()
 torch.cuda.init()
 B = args.batch
@@ -102,3 +108,32 @@ if args.map_jpeg:
         f.write(files[:size].cpu().numpy().tobytes())
     print("map: %d segments drawn (%d skipped) at %.1f px/m, thickness %d -> %s (%d bytes, %d x %d)"
           % (n_drawn, n_skipped, view.pixels_per_metre, view.thickness, args.map_jpeg, size, side, side))
+
+if args.overlay_jpeg:
+    os.makedirs(args.overlay_jpeg, exist_ok=True)
+    in_rows, in_cols = cfg["in_size"]
+    cam_h, cam_w = cfg["cam_size"]
+    rect = torch.empty((B, cam_h, cam_w, 3), dtype=torch.uint8, device="cuda")
+    stride = fe.jpeg_encode_bound(cam_h, cam_w)
+    files = torch.zeros((B, stride), dtype=torch.uint8, device="cuda")
+    sizes = torch.zeros(B, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    view = live.camera_view(cam_h, cam_w, H=cfg["H"], cam_size=cfg["cam_size"], min_last_seen=0)     # (the seeded codes have no place)
+    n_files = n_bytes = 0
+    drawn = np.zeros(3, np.int64)
+    for b0 in range(0, args.frames - B + 1, B):
+        fe.decode_jpeg_batch(msgs[b0:b0 + B], n_threads=args.threads, device_ptr=dev_frames)
+        fe.rectify_device(dev_frames, B, in_rows, in_cols, 3, rect.data_ptr())
+        fe.synchronize()                                              # (the map's stream does not wait for the handle's)
+        drawn += live.render_camera_device(rect.data_ptr(), rect.data_ptr(), B, None, view).sum(axis=0)
+        live.synchronize()
+        fe.encode_jpeg_device(rect.data_ptr(), B, cam_h, cam_w, files.data_ptr(), stride, sizes.data_ptr())
+        fe.synchronize()
+        host, sz = files.cpu().numpy(), sizes.cpu().numpy()
+        for i in range(B):
+            with open(os.path.join(args.overlay_jpeg, "%06d.jpg" % (b0 + i)), "wb") as f:
+                f.write(host[i, :sz[i]].tobytes())
+            n_bytes += int(sz[i])
+        n_files += B
+    print("overlay: %d frames %d x %d -> %s (%d bytes); per frame %.1f segments drawn, %.1f behind the camera, %.1f skipped"
+          % (n_files, cam_h, cam_w, args.overlay_jpeg, n_bytes, drawn[0] / max(n_files, 1), drawn[2] / max(n_files, 1), drawn[1] / max(n_files, 1)))
