@@ -583,6 +583,90 @@ LF_API int lf_map_render_camera(lf_map* m, const lf_camera_view* v, const double
  * second run of the project kernel, which writes the lists) */
 LF_API int lf_map_render_camera_timing(lf_map* m, double* ms_per_stage, int n);
 
+/* ---- a batch's odometry poses corrected against the live map: lf_map_align -------------------------
+ * The reference integrates wheel commands open loop (src/odometry/src/odometry.py:80-108) and its README leaves pose optimisation
+ * to "future improvements", so this is the package's OWN contract, written so that a sequential restatement
+ * (tests/map_align_ref.py) and the kernel (k_map_align.hip) agree bit for bit.  Per frame, `iterations` Gauss-Newton steps on the
+ * point-to-line residuals between the frame's matched segments (robot frame) and the map entries lf_map_associate matched them
+ * with (map frame); frame_pose is the start and the prior.  Frames are independent of one another.  The map is read as it stands
+ * on the map's stream when the call is reached; nothing of the map is changed.  All f64, unfused, in the order written here.
+ *
+ * Frame f holds the segments frame_offset[f] <= i < frame_offset[f + 1] (offsets are clamped to 0 .. n; no frame_offset: empty).
+ *   pair              segment i is a pair when ALL hold, t = idx[i]:  0 <= t < the map's size;  keep NULL or keep[i] != 0;  its four
+ *                     ground values are finite;  the entry's four ground values Ax Ay Bx By are finite;  dx = Bx - Ax, dy = By - Ay,
+ *                     l2 = dx dx + dy dy is finite and > 0;  the entry's hits >= min_hits;  color_match == 0 or segs->color NULL or
+ *                     color[i] == the entry's colour;  dist NULL or (double)dist[i] <= max_dist.  n_pairs counts them.
+ *   line              len = sqrt(l2) (correctly rounded), nx = (-dy) / len, ny = dx / len.
+ *   iterate           (x, y, th), at first frame_pose[3 f ..] = (x0, y0, th0).  (sn, cs) = sin, cos of th by the library's routine.
+ *   endpoint          e = 0, 1 of a pair, (px, py) = ground[4 i + 2 e ..]:  a = cs px, b = sn py, c = sn px, d = cs py;
+ *                     qx = x + (a - b), qy = y + (c + d)  (lf_map_pack_block's transform);  r = nx (qx - Ax) + ny (qy - Ay);
+ *                     jt = nx ((-c) - d) + ny (a - b);  J = (nx, ny, jt).
+ *   weight            ar = |r|.  Not (ar <= gate): w = 0.  Else w = 1 when ar <= huber, huber / ar otherwise.  The endpoint is USED
+ *                     when w > 0; an endpoint that is not used adds nothing.
+ *   sums              of a used endpoint, wj_k = w J_k:  N00 += wj0 nx, N01 += wj0 ny, N02 += wj0 jt, N11 += wj1 ny, N12 += wj1 jt,
+ *                     N22 += wj2 jt, g0 += wj0 r, g1 += wj1 r, g2 += wj2 r, cost += (w r) r, used += 1.
+ *   order             64 partial sums per frame, all +0 at the start of an iteration.  Segment i adds to partial
+ *                     (i - frame_offset[f]) mod 64, in increasing i, endpoint 0 before endpoint 1.  Then the fold, for each of the
+ *                     sums: s[l] = s[l] + s[l + 32] for l < 32, then the same with 16, 8, 4, 2, 1.  s[0] is the sum.
+ *   iteration k       = 0 .. iterations - 1: the sums at the iterate; cost0 = cost when k = 0; result.cost = cost, n_used = used.
+ *                     used < 2 min_pairs: LF_ALIGN_FEW, the frame stops.  Else the solve; a failing solve: LF_ALIGN_DEGENERATE, the
+ *                     frame stops.  Else x += t0, y += t1, th += t2 (th is not wrapped) and result.iterations += 1.
+ *   solve             A00 = N00 + prior_xy, A11 = N11 + prior_xy, A22 = N22 + prior_theta, A01 = N01, A02 = N02, A12 = N12;
+ *                     b0 = -(g0 + prior_xy (x - x0)), b1 = -(g1 + prior_xy (y - y0)), b2 = -(g2 + prior_theta (th - th0)).
+ *                     d0 = A00;  l10 = A01 / d0, l20 = A02 / d0;  d1 = A11 - l10 A01;  l21 = (A12 - l20 A01) / d1;
+ *                     d2 = (A22 - l20 A02) - (l21 d1) l21.  A pivot d0, d1, d2 that is not finite or <= 0 fails, tested before it
+ *                     divides.  z1 = b1 - l10 b0, z2 = (b2 - l20 b0) - l21 z1;  e0 = b0 / d0, e1 = z1 / d1, e2 = z2 / d2;
+ *                     t2 = e2, t1 = e1 - l21 t2, t0 = (e0 - l10 t1) - l20 t2.  A t that is not finite fails too.
+ *   a stopped frame   keeps the iterate it had: before the first accepted step that is frame_pose, bit for bit.
+ *   the limits        after the frame's last iteration, whatever its status: ddx = x - x0, ddy = y - y0, shift = sqrt(ddx ddx +
+ *                     ddy ddy), turn = |th - th0|.  shift > max_shift or turn > max_turn: LF_ALIGN_REJECTED and the pose is
+ *                     frame_pose again.  Otherwise the status is the one the iterations left, LF_ALIGN_OK when none stopped them.
+ *   an empty frame    has no used endpoint: LF_ALIGN_FEW, cost0 = cost = 0, its pose frame_pose.
+ * LF_ERR_BAD_ARG, touching nothing: NULL segs, frame_pose, cfg or results; n < 0; n_frames outside 1 .. 4096; n > 0 without
+ * segs->frame_offset, segs->ground or idx; a non-finite pose; iterations outside 1 .. 32; min_pairs < 1; a prior, max_shift or
+ * max_turn that is negative or NaN; a gate or huber that is <= 0 or NaN.
+ *
+ * lf_map_align returns when `results` (host) are in place.  lf_map_step_aligned = lf_map_associate, the alignment, then
+ * lf_map_pack_block and lf_map_update with the CORRECTED poses, all queued on the map's stream: the poses stay on the device (the
+ * alignment kernel writes x, y, cos, sin where the packing kernel reads them); it returns when `results` are in place.  Its map is
+ * byte-identical to the map of lf_map_step with frame_pose = the (x, y, theta) of `results`; idx / dist are lf_map_associate's. */
+typedef struct lf_align_config {
+    int32_t iterations;          /* Gauss-Newton steps, 1 .. 32; default 5 */
+    int32_t min_pairs;           /* an iteration with fewer USED endpoints than 2 min_pairs stops the frame; >= 1, default 3 */
+    int32_t min_hits;            /* entries with hits < min_hits are not paired; default 1 */
+    int32_t color_match;         /* 1: a pair needs equal colours; default 1 */
+    double  gate;                /* metres, > 0 or +inf: an endpoint with |r| > gate at the current iterate has weight 0; default 0.10 */
+    double  huber;               /* metres, > 0 or +inf (off, the default): |r| <= huber weighs 1, else huber / |r| */
+    double  max_dist;            /* pairs need dist[i] <= max_dist; default +inf */
+    double  prior_xy, prior_theta;   /* >= 0: added to the normal matrix's diagonal, pulling towards frame_pose; defaults 0 */
+    double  max_shift, max_turn;     /* >= 0: the limits above, metres and radians; defaults +inf */
+} lf_align_config;
+typedef struct lf_align_result {
+    double  x, y, theta;         /* the corrected pose */
+    double  cost0, cost;         /* sum of w r^2 over the used endpoints at frame_pose / at the last iterate evaluated */
+    int32_t n_pairs, n_used;     /* pairs of the frame; used endpoints of the last iteration evaluated */
+    int32_t iterations;          /* accepted steps */
+    int32_t status;
+} lf_align_result;
+enum { LF_ALIGN_OK = 0, LF_ALIGN_FEW = 1, LF_ALIGN_DEGENERATE = 2, LF_ALIGN_REJECTED = 3 };
+LF_API int lf_sizeof_align_config(void);
+LF_API int lf_sizeof_align_result(void);
+LF_API void lf_map_align_default_config(lf_align_config* c);
+/* segs: frame_offset, ground, color, keep are read; they, idx and dist are device (on_device = 1) or host (0) arrays.  h as for
+ * lf_map_associate. */
+LF_API int lf_map_align(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist,
+                 const double* frame_pose /* host [n_frames][3] */, const lf_align_config* cfg, int on_device,
+                 lf_align_result* results /* host [n_frames] */);
+/* as lf_map_step (device arrays; idx / dist device [n]) with cfg and host results [n_frames]; frame_pose is required */
+LF_API int lf_map_step_aligned(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const double* frame_pose,
+                        const lf_align_config* cfg, int step, int32_t* idx, float* dist, lf_align_result* results);
+/* as lf_map_step_host (host arrays) with cfg and results */
+LF_API int lf_map_step_aligned_host(lf_map* m, const lf_segments* segs, int n, int n_frames, const double* frame_pose,
+                             const lf_align_config* cfg, int step, int32_t* idx, float* dist, lf_align_result* results);
+/* ms and launches of the alignment kernel accumulated since the previous call, with profiling on (lf_map_set_profiling); resets
+ * them.  A stage of its own: lf_map_get_timing's stages and indices are unchanged. */
+LF_API int lf_map_align_timing(lf_map* m, double* ms, int32_t* launches);
+
 /* ---- Histogram lane filter: lane pose from ground segments -----------------------------------------
  * LaneFilterHistogram (src/lane_filter/include/lane_filter/lane_filter.py:12-161) as lane_filter_node.processSegments
  * drives it (src/lane_filter/src/lane_filter_node.py:49-87): per frame predict(dt, v, w) -> update(segments) ->

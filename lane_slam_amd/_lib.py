@@ -42,7 +42,11 @@ EXPORTS = (
     "lf_rectify_stage_name",
     "lf_map_default_view", "lf_map_bounds", "lf_map_render", "lf_map_render_counts", "lf_map_render_timing", "lf_map_render_stage_name",
     "lf_sizeof_camera_view", "lf_map_camera_view", "lf_map_render_camera", "lf_map_render_camera_timing",
+    "lf_sizeof_align_config", "lf_sizeof_align_result", "lf_map_align_default_config", "lf_map_align", "lf_map_step_aligned",
+    "lf_map_step_aligned_host", "lf_map_align_timing",
 )
+LF_ALIGN_OK, LF_ALIGN_FEW, LF_ALIGN_DEGENERATE, LF_ALIGN_REJECTED = 0, 1, 2, 3
+ALIGN_STATUS = ("ok", "few", "degenerate", "rejected")
 LF_MAP_RENDER_STAGES = 4
 LF_JPEG_ENCODE_STAGES = 8
 LF_RECTIFY_STAGES = 1
@@ -151,6 +155,24 @@ class LfCameraView(ctypes.Structure):
                 ("palette_size", ctypes.c_int32), ("palette", (ctypes.c_uint8 * 3) * 8), ("background", ctypes.c_uint8 * 3),
                 ("pad_", ctypes.c_uint8 * 1)]
 
+
+class LfAlignConfig(ctypes.Structure):
+    """ctypes mirror of `lf_align_config` (include/lanefront.h)."""
+    _fields_ = [("iterations", ctypes.c_int32), ("min_pairs", ctypes.c_int32), ("min_hits", ctypes.c_int32), ("color_match", ctypes.c_int32),
+                ("gate", ctypes.c_double), ("huber", ctypes.c_double), ("max_dist", ctypes.c_double), ("prior_xy", ctypes.c_double),
+                ("prior_theta", ctypes.c_double), ("max_shift", ctypes.c_double), ("max_turn", ctypes.c_double)]
+
+
+class LfAlignResult(ctypes.Structure):
+    """ctypes mirror of `lf_align_result` (include/lanefront.h)."""
+    _fields_ = [("x", ctypes.c_double), ("y", ctypes.c_double), ("theta", ctypes.c_double), ("cost0", ctypes.c_double),
+                ("cost", ctypes.c_double), ("n_pairs", ctypes.c_int32), ("n_used", ctypes.c_int32), ("iterations", ctypes.c_int32),
+                ("status", ctypes.c_int32)]
+
+
+# the same layout as a numpy record: what LineAssociator.align returns
+ALIGN_RESULT_DTYPE = [("x", "<f8"), ("y", "<f8"), ("theta", "<f8"), ("cost0", "<f8"), ("cost", "<f8"), ("n_pairs", "<i4"), ("n_used", "<i4"),
+                      ("iterations", "<i4"), ("status", "<i4")]
 
 _lib = None
 
@@ -284,6 +306,17 @@ def load():
     lib.lf_map_render_camera.argtypes = [vp, ctypes.POINTER(LfCameraView), vp, ci, vp, vp, ci, vp]
     lib.lf_map_render_camera_timing.argtypes = [vp, vp, ci]
     for f in ("lf_sizeof_camera_view", "lf_map_camera_view", "lf_map_render_camera", "lf_map_render_camera_timing"):
+        getattr(lib, f).restype = ci
+    lib.lf_sizeof_align_config.argtypes = []
+    lib.lf_sizeof_align_result.argtypes = []
+    lib.lf_map_align_default_config.argtypes = [ctypes.POINTER(LfAlignConfig)]
+    lib.lf_map_align_default_config.restype = None
+    lib.lf_map_align.argtypes = [vp, vp, ctypes.POINTER(LfSegments), ci, ci, vp, vp, vp, ctypes.POINTER(LfAlignConfig), ci, vp]
+    lib.lf_map_step_aligned.argtypes = [vp, vp, ctypes.POINTER(LfSegments), ci, ci, vp, ctypes.POINTER(LfAlignConfig), ci, vp, vp, vp]
+    lib.lf_map_step_aligned_host.argtypes = [vp, ctypes.POINTER(LfSegments), ci, ci, vp, ctypes.POINTER(LfAlignConfig), ci, vp, vp, vp]
+    lib.lf_map_align_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
+    for f in ("lf_sizeof_align_config", "lf_sizeof_align_result", "lf_map_align", "lf_map_step_aligned", "lf_map_step_aligned_host",
+              "lf_map_align_timing"):
         getattr(lib, f).restype = ci
     lib.lf_descriptor_default_params.argtypes = [ctypes.POINTER(LfDescriptorParams)]
     lib.lf_descriptor_default_params.restype = None

@@ -7,29 +7,6 @@
 #include <vector>
 #include "lanefront_map_handle.h"
 
-namespace {
-struct MapTimer {
-    lf_map* m; int st; lf_map::Ev e; bool on;
-    MapTimer(lf_map* m_, int st_) : m(m_), st(st_), on(m_->profiling)
-    {
-        if (!on) return;
-        if (m->ev_free.empty()) {
-            lf_map::Ev n; n.st = 0;
-            if (m->ev_used.size() >= 4096 || hipEventCreate(&n.a) != hipSuccess || hipEventCreate(&n.b) != hipSuccess) { on = false; return; }
-            m->ev_free.push_back(n);
-        }
-        e = m->ev_free.back(); m->ev_free.pop_back();
-        e.st = st;
-        (void)hipEventRecord(e.a, m->stream);
-    }
-    ~MapTimer()
-    {
-        if (on) { (void)hipEventRecord(e.b, m->stream); m->ev_used.push_back(e); }
-        m->launches[st] += 1;
-    }
-};
-}
-
 static char g_map_create_err[512] = "no error";
 
 static void map_error(lf_map* m, const char* fmt, ...)
@@ -88,7 +65,7 @@ static int queue_state_copy(lf_map* m)
 }
 
 // the map's stream waits for everything queued so far on the handle's stream
-static int after_handle(lf_map* m, lf_handle* h)
+int after_handle(lf_map* m, lf_handle* h)
 {
     if (!h) return LF_OK;
     void* hs = nullptr;
@@ -99,7 +76,7 @@ static int after_handle(lf_map* m, lf_handle* h)
 }
 
 // the handle's later work (its next batch overwrites the segment arrays) waits for what the map has queued so far
-static int release_handle(lf_map* m, lf_handle* h)
+int release_handle(lf_map* m, lf_handle* h)
 {
     if (!h) return LF_OK;
     void* hs = nullptr;
@@ -129,10 +106,9 @@ extern "C" int lf_map_set_profiling(lf_map* m, int enabled)
     return LF_OK;
 }
 
-// ms accumulated and launches counted per stage since the last call; resets both
-extern "C" int lf_map_get_timing(lf_map* m, double* ms_per_stage, int32_t* launches_per_stage, int n)
+// the events recorded so far become milliseconds of their stages
+static void resolve_events(lf_map* m)
 {
-    if (!m) return LF_ERR_NOT_INITIALISED;
     for (lf_map::Ev& e : m->ev_used) {
         (void)hipEventSynchronize(e.b);
         float t = 0;
@@ -140,6 +116,24 @@ extern "C" int lf_map_get_timing(lf_map* m, double* ms_per_stage, int32_t* launc
         m->ev_free.push_back(e);
     }
     m->ev_used.clear();
+}
+
+// the alignment kernel's stage (lanefront_map_align.hip), kept apart from lf_map_get_timing's table
+extern "C" int lf_map_align_timing(lf_map* m, double* ms, int32_t* launches)
+{
+    if (!m) return LF_ERR_NOT_INITIALISED;
+    resolve_events(m);
+    if (ms) *ms = m->ms[kMapAlignStage];
+    if (launches) *launches = m->launches[kMapAlignStage];
+    m->ms[kMapAlignStage] = 0; m->launches[kMapAlignStage] = 0;
+    return LF_OK;
+}
+
+// ms accumulated and launches counted per stage since the last call; resets both
+extern "C" int lf_map_get_timing(lf_map* m, double* ms_per_stage, int32_t* launches_per_stage, int n)
+{
+    if (!m) return LF_ERR_NOT_INITIALISED;
+    resolve_events(m);
     for (int i = 0; i < LF_MAP_N_STAGES; ++i) {
         if (i < n && ms_per_stage) ms_per_stage[i] = m->ms[i];
         if (i < n && launches_per_stage) launches_per_stage[i] = m->launches[i];
@@ -253,8 +247,7 @@ extern "C" int lf_map_synchronize(lf_map* m)
     return LF_OK;
 }
 
-// rows_hint: how many segment rows the blocks really hold when the host knows it (-1: assume they are full)
-static int update_blocks(lf_map* m, const uint8_t* blocks, int n_blocks, int block_rows, int force_append, long long rows_hint = -1)
+int update_blocks(lf_map* m, const uint8_t* blocks, int n_blocks, int block_rows, int force_append, long long rows_hint)
 {
     int rc;
     const size_t rows = (size_t)n_blocks * (size_t)(block_rows - 1);

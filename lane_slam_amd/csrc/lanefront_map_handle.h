@@ -61,17 +61,48 @@ struct lf_map {
     long long rows_in_flight = 0;            // rows handed to updates whose state copy has not been seen yet
     AssocScratch ws;
     DevBuf act, own_block, pose, q_in, c_in, idx_out, dist_out, seed_code, seed_color, seed_ground, tie_res;
-    DevBuf st_fo, st_code, st_color, st_keep, st_ground, st_idx, st_dist;     // staging of lf_map_step_host
+    DevBuf st_fo, st_code, st_color, st_keep, st_ground, st_idx, st_dist;     // staging of lf_map_step_host and of lf_map_align's host arrays
+    DevBuf al_pose0, al_res;                 // lf_map_align: the prior poses [n_frames][3], the results [n_frames]
     std::vector<double> h_pose;
     // per-stage timing with HIP events on the map's stream (resolved by lf_map_get_timing)
     struct Ev { hipEvent_t a, b; int st; };
     bool profiling = false;
     std::vector<Ev> ev_free, ev_used;
-    double ms[LF_MAP_N_STAGES];
-    int32_t launches[LF_MAP_N_STAGES];
+    double ms[LF_MAP_N_STAGES + 1];          // the stages of lf_map_get_timing, then kMapAlignStage (lf_map_align_timing)
+    int32_t launches[LF_MAP_N_STAGES + 1];
     std::unique_ptr<lf::MapRenderState> render;   // lf_map_render / lf_map_bounds (lanefront_map_render.hip), made by their first call
     std::unique_ptr<lf::MapCameraState> camera;   // lf_map_render_camera (lanefront_map_camera.hip), likewise
 };
+
+constexpr int kMapAlignStage = LF_MAP_N_STAGES;
+
+// HIP events around one stage of the map's chain while profiling is on; the launch is counted either way
+struct MapTimer {
+    lf_map* m; int st; lf_map::Ev e; bool on;
+    MapTimer(lf_map* m_, int st_) : m(m_), st(st_), on(m_->profiling)
+    {
+        if (!on) return;
+        if (m->ev_free.empty()) {
+            lf_map::Ev n; n.st = 0;
+            if (m->ev_used.size() >= 4096 || hipEventCreate(&n.a) != hipSuccess || hipEventCreate(&n.b) != hipSuccess) { on = false; return; }
+            m->ev_free.push_back(n);
+        }
+        e = m->ev_free.back(); m->ev_free.pop_back();
+        e.st = st;
+        (void)hipEventRecord(e.a, m->stream);
+    }
+    ~MapTimer()
+    {
+        if (on) { (void)hipEventRecord(e.b, m->stream); m->ev_used.push_back(e); }
+        m->launches[st] += 1;
+    }
+};
+
+// ---- lanefront_map.hip's sequencing, for the translation unit that aligns poses before the update (lanefront_map_align.hip)
+int after_handle(lf_map* m, lf_handle* h);        // the map's stream waits for everything queued so far on the handle's stream
+int release_handle(lf_map* m, lf_handle* h);      // the handle's later work waits for what the map has queued so far
+// rows_hint: how many segment rows the blocks really hold when the host knows it (-1: assume they are full)
+int update_blocks(lf_map* m, const uint8_t* blocks, int n_blocks, int block_rows, int force_append, long long rows_hint = -1);
 
 // ---- what the translation units that draw the map share (lanefront_map_render.hip, lanefront_map_camera.hip)
 inline void map_draw_error(lf_map* m, const char* fmt, ...)

@@ -104,23 +104,86 @@ class LineAssociator(object):
                                               idx.ctypes.data, dist.ctypes.data, 0))
         return idx, dist
 
-    def step(self, seg, poses=None, step=0):
+    def step(self, seg, poses=None, step=0, align=None):
         """Associate the segments of a host `Segments` block (FrontEnd.process_batch) against the map, then update the
-        map with them; returns (idx, dist).  poses: (n_frames, 3) map -> duck (x, y, theta) per frame, or None."""
+        map with them; returns (idx, dist).  poses: (n_frames, 3) map -> duck (x, y, theta) per frame, or None.
+        align: an `_lib.LfAlignConfig` (align_config) -- the poses are corrected against the map between association and update
+        (lf_map_step_aligned_host) and the call returns (idx, dist, poses_out, results) as `align` does."""
         n, n_frames = int(seg.n), len(seg.frame_offset) - 1
         keep_alive, pp = self._poses(poses, n_frames)
+        s, alive = self._host_segs(seg, ("frame_offset", "code", "color", "keep", "ground"))
+        idx, dist = np.empty(n, np.int32), np.empty(n, np.float32)
+        if align is None:
+            self._check(self.lib.lf_map_step_host(self.m, ctypes.byref(s), n, n_frames, pp, int(step), idx.ctypes.data, dist.ctypes.data))
+            return idx, dist
+        res = np.zeros(n_frames, _lib.ALIGN_RESULT_DTYPE)
+        self._check(self.lib.lf_map_step_aligned_host(self.m, ctypes.byref(s), n, n_frames, pp, ctypes.byref(align), int(step),
+                                                      idx.ctypes.data, dist.ctypes.data, res.ctypes.data))
+        return idx, dist, self._poses_out(res), res
+
+    @staticmethod
+    def _host_segs(seg, keys):
         s = _lib.LfSegments()
-        s.capacity = n
+        s.capacity = int(seg.n)
         alive = []
-        for k in ("frame_offset", "code", "color", "keep", "ground"):
-            v = getattr(seg, k)
+        for k in keys:
+            v = getattr(seg, k, None)
             if v is not None:
                 a = np.ascontiguousarray(v)
                 alive.append(a)
                 setattr(s, k, a.ctypes.data)
-        idx, dist = np.empty(n, np.int32), np.empty(n, np.float32)
-        self._check(self.lib.lf_map_step_host(self.m, ctypes.byref(s), n, n_frames, pp, int(step), idx.ctypes.data, dist.ctypes.data))
-        return idx, dist
+        return s, alive
+
+    # ------------------------------------------------------------------ odometry poses corrected against the map (lf_map_align)
+    def align_config(self, **overrides):
+        """The library's default `_lib.LfAlignConfig` (lf_map_align_default_config) with the overrides applied: iterations,
+        min_pairs, min_hits, color_match, gate, huber, max_dist, prior_xy, prior_theta, max_shift, max_turn."""
+        c = _lib.LfAlignConfig()
+        self.lib.lf_map_align_default_config(ctypes.byref(c))
+        kinds = dict((k, t) for k, t in _lib.LfAlignConfig._fields_)
+        for k, val in overrides.items():
+            if k not in kinds:
+                raise TypeError("align_config: unknown field %r" % (k,))
+            setattr(c, k, int(val) if kinds[k] is ctypes.c_int32 else float(val))
+        return c
+
+    @staticmethod
+    def _poses_out(res):
+        return np.stack([res["x"], res["y"], res["theta"]], axis=1)
+
+    def align(self, seg, idx, dist, poses, config=None):
+        """Correct the poses of a batch against the map as it stands: seg is a host `Segments` block (frame_offset, ground, color,
+        keep are read), idx / dist its association (`associate`), poses (n_frames, 3) the odometry's map -> duck (x, y, theta).
+        Returns (poses_out (n_frames, 3) float64, results): results is a record array of `_lib.ALIGN_RESULT_DTYPE`, one
+        lf_align_result per frame (status: `_lib.ALIGN_STATUS`).  The map is not changed."""
+        n, n_frames = int(seg.n), len(seg.frame_offset) - 1
+        keep_alive, pp = self._poses(poses, n_frames)
+        s, alive = self._host_segs(seg, ("frame_offset", "color", "keep", "ground"))
+        idx = np.ascontiguousarray(idx, np.int32)
+        dist = None if dist is None else np.ascontiguousarray(dist, np.float32)
+        if len(idx) != n or (dist is not None and len(dist) != n):
+            raise ValueError("align: idx and dist hold one value per segment")
+        config = self.align_config() if config is None else config
+        res = np.zeros(n_frames, _lib.ALIGN_RESULT_DTYPE)
+        self._check(self.lib.lf_map_align(self.m, None, ctypes.byref(s), n, n_frames, idx.ctypes.data, None if dist is None else dist.ctypes.data,
+                                          pp, ctypes.byref(config), 0, res.ctypes.data))
+        return self._poses_out(res), res
+
+    def align_device(self, fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, poses, config=None):
+        """`align` for a batch that is resident on the device (out_ptrs as for step_device; idx_ptr / dist_ptr device arrays)."""
+        keep_alive, pp = self._poses(poses, n_frames)
+        s = self._segs(out_ptrs)
+        config = self.align_config() if config is None else config
+        res = np.zeros(int(n_frames), _lib.ALIGN_RESULT_DTYPE)
+        self._check(self.lib.lf_map_align(self.m, fe.h if fe is not None else None, ctypes.byref(s), int(n), int(n_frames), int(idx_ptr),
+                                          dist_ptr and int(dist_ptr), pp, ctypes.byref(config), 1, res.ctypes.data))
+        return self._poses_out(res), res
+
+    def align_timing(self):
+        """(ms, launches) of the alignment kernel since the previous call (needs set_profiling(True)); resets."""
+        ms, ln = ctypes.c_double(), ctypes.c_int32()
+        self._check(self.lib.lf_map_align_timing(self.m, ctypes.byref(ms), ctypes.byref(ln)))
+        return ms.value, ln.value
 
     def fetch(self, first=0, n=None):
         n = self.capacity - first if n is None else n
@@ -333,10 +396,16 @@ class LineAssociator(object):
     def update_device(self, blocks_ptr, n_blocks, block_rows):
         self._check(self.lib.lf_map_update(self.m, int(blocks_ptr), int(n_blocks), int(block_rows)))
 
-    def step_device(self, fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, poses=None, step=0):
+    def step_device(self, fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, poses=None, step=0, align=None):
         """associate + update for the n segments of a batch that is resident on the device (out_ptrs: the dict given to
-        FrontEnd.submit_device; frame_offset, code, color, keep, ground are read)."""
+        FrontEnd.submit_device; frame_offset, code, color, keep, ground are read).  align: an `_lib.LfAlignConfig` -- the poses are
+        corrected on the device between the two (lf_map_step_aligned) and the call returns (idx_ptr, dist_ptr, poses_out, results)."""
         keep_alive, pp = self._poses(poses, n_frames)
         s = self._segs(out_ptrs)
+        if align is not None:
+            res = np.zeros(int(n_frames), _lib.ALIGN_RESULT_DTYPE)
+            self._check(self.lib.lf_map_step_aligned(self.m, fe.h if fe is not None else None, ctypes.byref(s), int(n), int(n_frames), pp,
+                                                     ctypes.byref(align), int(step), int(idx_ptr), int(dist_ptr), res.ctypes.data))
+            return idx_ptr, dist_ptr, self._poses_out(res), res
         self._check(self.lib.lf_map_step(self.m, fe.h if fe is not None else None, ctypes.byref(s), int(n), int(n_frames), pp,
                                          int(step), int(idx_ptr), int(dist_ptr)))

@@ -1,0 +1,75 @@
+"""One run of the alignment kernel and of the aligned step beside the plain step: 256 frames x 40 segments against a
+50 000-entry map at 5 iterations, timed with HIP events on the map's stream (set_profiling)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from lane_slam_amd import LineAssociator  # noqa: E402
+
+
+class Segs(object):
+    pass
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=256)
+    ap.add_argument("--segments", type=int, default=40)
+    ap.add_argument("--entries", type=int, default=50000)
+    ap.add_argument("--iterations", type=int, default=5)
+    ap.add_argument("--repeat", type=int, default=5)
+    args = ap.parse_args()
+    rng = np.random.default_rng(0)
+    nm, nf, n = args.entries, args.frames, args.frames * args.segments
+    c = np.stack([rng.uniform(0, 40, nm), rng.uniform(-1, 1, nm)], 1)
+    ang, half = rng.uniform(0, np.pi, nm), rng.uniform(0.03, 0.15, nm)
+    d = np.stack([np.cos(ang), np.sin(ang)], 1) * half[:, None]
+    m_ground, m_code = np.concatenate([c - d, c + d], 1), rng.integers(0, 256, (nm, 32), dtype=np.uint8)
+    m_color = rng.integers(0, 3, nm).astype(np.uint8)
+    true = np.stack([rng.uniform(0, 39, nf), rng.uniform(-0.2, 0.2, nf), rng.uniform(-0.3, 0.3, nf)], 1)
+    poses = true + np.stack([rng.uniform(-0.05, 0.05, nf), rng.uniform(-0.05, 0.05, nf), rng.uniform(-0.05, 0.05, nf)], 1)
+    seg = Segs()
+    seg.n, seg.frame_offset = n, (np.arange(nf + 1) * args.segments).astype(np.int32)
+    g = np.zeros((n, 4))
+    pick = np.zeros(n, np.int64)
+    for f in range(nf):
+        near = np.flatnonzero(np.abs(c[:, 0] - true[f, 0]) < 1.0)
+        t = rng.choice(near, args.segments)
+        pick[f * args.segments:(f + 1) * args.segments] = t
+        x, y, th = true[f]
+        cs, sn = np.cos(th), np.sin(th)
+        e = m_ground[t].reshape(-1, 2) - [x, y]
+        g[f * args.segments:(f + 1) * args.segments] = np.stack([cs * e[:, 0] + sn * e[:, 1], cs * e[:, 1] - sn * e[:, 0]], 1).reshape(-1, 4)
+    seg.ground, seg.code, seg.color, seg.keep = g, m_code[pick], m_color[pick], np.ones(n, np.uint8)
+    out = {"frames": nf, "segments_per_frame": args.segments, "entries": nm, "iterations": args.iterations}
+    maps = [LineAssociator(capacity=65536, kept_only=False, policy="merge", merge_distance=0) for _ in range(2)]
+    for a in maps:
+        a.seed(m_code, m_color, m_ground)
+        a.set_profiling(True)
+    plain, aligned = maps
+    cfg = aligned.align_config(iterations=args.iterations)
+    idx, dist = plain.associate(seg.code, seg.color)
+    runs = []
+    for r in range(args.repeat):
+        aligned.align(seg, idx, dist, poses, cfg)
+        runs.append(aligned.align_timing()[0])
+    out["align_kernel_ms"] = runs
+    plain.timing(); aligned.timing()
+    steps = []
+    for r in range(args.repeat):
+        plain.step(seg, poses, step=r)
+        _, _, _, res = aligned.step(seg, poses, step=r, align=cfg)
+        tp, ta = plain.timing(), aligned.timing()
+        steps.append({"plain_ms": sum(v[0] for v in tp.values()), "aligned_ms": sum(v[0] for v in ta.values()), "align_ms": aligned.align_timing()[0],
+                      "plain": {k: round(v[0], 4) for k, v in tp.items()}, "aligned": {k: round(v[0], 4) for k, v in ta.items()}})
+    out["steps"] = steps
+    out["status_counts"] = np.bincount(res["status"], minlength=4).tolist()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -21,7 +21,7 @@ import torch
 from PIL import Image
 from lane_slam_amd import FrontEnd, default_config, synth
 from lane_slam_amd import segment_msgs as sm
-from lane_slam_amd import LineAssociator
+from lane_slam_amd import LineAssociator, _lib
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--frames", type=int, default=1024)
@@ -33,6 +33,9 @@ ap.add_argument("--map-jpeg", default=None, help="write the final map, rendered 
 ap.add_argument("--map-size", type=int, default=1024, help="rows = cols of that picture")
 ap.add_argument("--overlay-jpeg", default=None, metavar="DIR",
                 help="write every replayed frame, rectified and with the final map drawn into it on the device, as DIR/%%06d.jpg")
+ap.add_argument("--align", action="store_true",
+                help="correct every batch's poses against the map before the update (lf_map_step_aligned, the default configuration) and "
+                     "print, per batch, how many frames came back with each status")
 args = ap.parse_args()
 torch.cuda.init()
 B = args.batch
@@ -79,7 +82,15 @@ for b0 in range(0, args.frames - B + 1, B):
         di = torch.zeros(seg.n, dtype=torch.int32, device="cuda")
         dd = torch.zeros(seg.n, dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()
-        live.step_device(None, {k: v.data_ptr() for k, v in d.items()}, seg.n, B, di.data_ptr(), dd.data_ptr(), step=b0 // B)
+        ptrs = {k: v.data_ptr() for k, v in d.items()}
+        if args.align:
+            # (the replay has no odometry: every prior is the identity, and the seeded map has no geometry to align with)
+            res = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=np.zeros((B, 3)), step=b0 // B,
+                                   align=live.align_config())[3]
+            counts = np.bincount(res["status"], minlength=4)
+            print("batch %d aligned: %s" % (b0 // B, ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, counts))))
+        else:
+            live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), step=b0 // B)
         live.synchronize()
         n_matched += int((di >= 0).sum().item())
         n_kept += int(seg.keep.sum())
