@@ -114,16 +114,7 @@ __device__ __forceinline__ void lf_xcd_tile(int& bx, int& by, int& bz)
 }
 #endif
 
-#define LF_HIP_CHECK(h, expr)                                                              \
-    do {                                                                                   \
-        hipError_t _e = (expr);                                                            \
-        if (_e != hipSuccess) {                                                            \
-            lf_set_error((h), LF_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
-                         __FILE__, __LINE__);                                              \
-            return LF_ERR_HIP;                                                             \
-        }                                                                                  \
-    } while (0)
-
+// (LF_HIP_CHECK and what else the handles share on the host: lanefront_core.h)
 extern "C" void lf_set_error(lf_handle* h, int code, const char* fmt, ...);
 
 // kernel launchers (one per translation unit)

@@ -24,8 +24,8 @@ extern "C" int lf_ai_transform_batch(lf_handle* h, const uint8_t* frames, int n_
     const size_t strip_bytes = (size_t)n * 3, frame_bytes = (size_t)rows * cols * 3, fits = 2 * (size_t)n_frames;
     int rc;
     // per fit: 16 f64 (centres, inertia) | 4 counts | 1 status word
-    if ((rc = ensure(h, h->ai_lab, fits * (size_t)n)) || (rc = ensure(h, h->ai_fit, fits * (16 * sizeof(double) + 4 * sizeof(long long) + sizeof(int)))) ||
-        (rc = ensure(h, h->ai_out, (size_t)n_frames * sizeof(lf_ai_transform)))) return rc;
+    if ((rc = scratch(h, h->ai_lab, fits * (size_t)n)) || (rc = scratch(h, h->ai_fit, fits * (16 * sizeof(double) + 4 * sizeof(long long) + sizeof(int)))) ||
+        (rc = scratch(h, h->ai_out, (size_t)n_frames * sizeof(lf_ai_transform)))) return rc;
     const uint8_t* strips;
     long long stride;
     if (frames_on_device) {
@@ -33,7 +33,7 @@ extern "C" int lf_ai_transform_batch(lf_handle* h, const uint8_t* frames, int n_
         stride = (long long)frame_bytes;
     } else {
         // only the strip rows travel: one 2-D copy of n_frames rows of strip_bytes
-        if ((rc = ensure(h, h->ai_strip, (size_t)n_frames * strip_bytes)) != LF_OK) return rc;
+        if ((rc = scratch(h, h->ai_strip, (size_t)n_frames * strip_bytes)) != LF_OK) return rc;
         LF_HIP_CHECK(h, hipMemcpy2DAsync(h->ai_strip.p, strip_bytes, frames + (frame_bytes - strip_bytes), frame_bytes, strip_bytes, n_frames,
                                          hipMemcpyHostToDevice, s));
         strips = static_cast<const uint8_t*>(h->ai_strip.p);

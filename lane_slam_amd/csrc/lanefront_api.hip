@@ -27,30 +27,14 @@ static const char* kStageNames[LF_N_STAGES] = {
 
 extern "C" void lf_set_error(lf_handle* h, int code, const char* fmt, ...)
 {
-    if (!h) return;
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(h->err, sizeof(h->err), fmt, ap);
+    vset_error(h, code, fmt, ap);
     va_end(ap);
-    h->err_code = code;
 }
 
 static char g_create_err[512] = "no error";
 
-
-
-// Per-stage timing with HIP events recorded on the handle's stream.  Events are only
-// recorded here (no host synchronisation inside the pipeline); lf_get_timing resolves them.
-void lf::timing_resolve(lf_handle* h)
-{
-    for (EvPair& e : h->ev_used) {
-        (void)hipEventSynchronize(e.b);
-        float t = 0;
-        if (hipEventElapsedTime(&t, e.a, e.b) == hipSuccess) h->ms[e.st] += t;
-        h->ev_free.push_back(e);
-    }
-    h->ev_used.clear();
-}
 
 
 static int cv_round_host(double v) { return dm::round_half_even(v); }
@@ -263,8 +247,6 @@ extern "C" void lf_destroy(lf_handle* h)
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    timing_resolve(h);
-    for (EvPair& e : h->ev_free) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;                    // the buffers and the substates free themselves
 }
@@ -276,22 +258,10 @@ extern "C" int lf_create(const lf_config* cfg, int device_id, int max_frames, in
         return LF_ERR_BAD_ARG;
     }
     *out = nullptr;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        snprintf(g_create_err, sizeof(g_create_err), "lf_create: no HIP device (%s); lanefront has no CPU fallback",
-                 e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-        return LF_ERR_HIP;
-    }
-    if (device_id < 0 || device_id >= ndev) {
-        snprintf(g_create_err, sizeof(g_create_err), "lf_create: device %d out of range (%d devices)", device_id, ndev);
-        return LF_ERR_BAD_ARG;
-    }
+    if (const int rc = check_device(device_id, "lf_create", g_create_err, sizeof(g_create_err))) return rc;
     lf_handle* h = new (std::nothrow) lf_handle();
     if (!h) return LF_ERR_HIP;
     h->cfg = *cfg; h->device = device_id; h->max_frames = max_frames; h->cap_lines = max_lines_per_color;
-    h->err[0] = 0;
-    memset(h->ms, 0, sizeof(h->ms)); memset(h->launches, 0, sizeof(h->launches));
     if (const char* ev = getenv("LF_KL_LDS_LINES")) { const int v = atoi(ev); h->env_kl_lds_lines = v < 1 ? 1 : (v > 4096 ? 4096 : v); }
     int rc = LF_OK;
     do {
@@ -346,10 +316,10 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
         if (rc != LF_OK) return rc;
     }
     // (LineDetector2Dense also reads the masks before dilation: k_pre's other instantiation writes them as well)
-    { StageTimer t(h, ST_PRE); launch_pre(pp, d_frames, n, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s, dense ? h->d_bwbits.p : nullptr); }
-    { StageTimer t(h, ST_CANNY); launch_canny(h->canny, h->d_bgr, n, h->d_strong, h->d_weak, s); }
+    { StageClock::Scope t(h, h->clock, ST_PRE); launch_pre(pp, d_frames, n, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s, dense ? h->d_bwbits.p : nullptr); }
+    { StageClock::Scope t(h, h->clock, ST_CANNY); launch_canny(h->canny, h->d_bgr, n, h->d_strong, h->d_weak, s); }
     {
-        StageTimer t(h, ST_HYST);
+        StageClock::Scope t(h, h->clock, ST_HYST);
         if (launch_hysteresis(h->canny, n, h->d_strong, h->d_weak, s) != 0) {
             lf_set_error(h, LF_ERR_UNSUPPORTED, "canny hysteresis: a %dx%d working image does not fit the LDS-resident strips", h->Hc, h->W);
             return LF_ERR_UNSUPPORTED;
@@ -359,7 +329,7 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
         // LineDetectorHSV: HoughLinesP on the same edge maps in place of the LSD stages (k_hough.hip)
         int rc = hough_prepare(h);
         if (rc != LF_OK) return rc;
-        StageTimer t(h, ST_HOUGH);
+        StageClock::Scope t(h, h->clock, ST_HOUGH);
         LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_zero, 0, h->lsd.zero_bytes, s));           // every counter of the batch (see d_zero)
         HoughParams hp = h->hough_p;
         hp.threshold = h->hough_params.threshold; hp.line_length = h->hough_params.min_line_length; hp.line_gap = h->hough_params.max_line_gap;
@@ -373,7 +343,7 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
     }
     if (dense) {
         // LineDetector2Dense: a line per edge pixel with a steep undilated mask in place of the LSD stages (k_dense.hip)
-        StageTimer t(h, ST_DENSE);
+        StageClock::Scope t(h, h->clock, ST_DENSE);
         LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_zero, 0, h->lsd.zero_bytes, s));           // every counter of the batch (see d_zero)
         launch_dense(h->Hc, h->W, h->Ww, h->cap_lines, (float)h->dense_params.sobel_threshold, n * 3, h->d_strong, h->d_maskbits,
                      h->d_bwbits, h->d_slot_lines, h->d_dense_rec, h->d_counts, s);
@@ -385,19 +355,19 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
     }
     h->slot_mode = SEG_FLOAT;
     {
-        StageTimer t(h, ST_LSD_GRAD);
+        StageClock::Scope t(h, h->clock, ST_LSD_GRAD);
         LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_zero, 0, h->lsd.zero_bytes, s));           // every counter of the batch (see d_zero)
         h->lsd.grad(n, h->d_strong, h->d_maskbits, true, s);
     }
-    { StageTimer t(h, ST_LSD_ORDER); h->lsd.order(n, 0, s); }
+    { StageClock::Scope t(h, h->clock, ST_LSD_ORDER); h->lsd.order(n, 0, s); }
     {
-        StageTimer t(h, ST_LSD_LABEL);          // (its own stage since round 6: two brackets of different content under one name made the average meaningless)
+        StageClock::Scope t(h, h->clock, ST_LSD_LABEL);          // (its own stage since round 6: two brackets of different content under one name made the average meaningless)
         h->lsd.label(n, true, s);
     }
     static const char* diag_skip = getenv("LF_DIAG_SKIP");     // diagnostic only (what-if timing, results are wrong): "grow"
     if (diag_skip && strstr(diag_skip, "grow")) LF_HIP_CHECK(h, hipMemsetAsync(h->d_counts, 0, (size_t)n * 3 * sizeof(int), s));
     else {
-        StageTimer t(h, ST_LSD_GROW);
+        StageClock::Scope t(h, h->clock, ST_LSD_GROW);
         const LsdState& L = h->lsd;
         h->lsd.grow(n, h->d_slot_lines, h->d_counts, kGrowLdsKb[L.env_lds_level >= 0 ? L.env_lds_level : L.grow_lds_level],
                     L.env_mixed >= 0 ? L.env_mixed != 0 : L.grow_mixed, true, s);
@@ -413,7 +383,7 @@ int lf::run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe)
 {
     hipStream_t s = h->stream;
     {
-        StageTimer t(h, ST_SEGMENTS);
+        StageClock::Scope t(h, h->clock, ST_SEGMENTS);
         if (!h->overflow_zeroed) LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_overflow, 0, 4 * sizeof(int), s));
         h->overflow_zeroed = false;
         launch_seg_offsets(n, h->cap_lines, h->d_counts, h->d_seg_offset, dev_out.frame_offset ? dev_out.frame_offset : h->d_frame_offset,
@@ -424,9 +394,9 @@ int lf::run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe)
                         h->d_seg_frame, h->d_normals64, h->d_centers, s, h->slot_mode);
     }
     if (describe) {
-        { StageTimer t(h, ST_LBD_GRAD); launch_lbd_grad(h->Hc, h->W, n, h->d_gray, h->d_dxy, s); }
+        { StageClock::Scope t(h, h->clock, ST_LBD_GRAD); launch_lbd_grad(h->Hc, h->W, n, h->d_gray, h->d_dxy, s); }
         {
-            StageTimer t(h, ST_LBD);
+            StageClock::Scope t(h, h->clock, ST_LBD);
             int cap = dev_out.capacity < n * 3 * h->cap_lines ? dev_out.capacity : n * 3 * h->cap_lines;
             launch_lbd(h->Hc, h->W, cap, h->d_seg_offset + n * 3, dev_out.lines, h->d_seg_frame, h->d_dxy,
                        h->d_gauss_g, h->d_gauss_l, dev_out.desc, dev_out.code, s, h->desc_params.width_of_band);
@@ -607,7 +577,7 @@ extern "C" int lf_set_image(lf_handle* h, const uint8_t* bgr, int rows, int cols
     if (rc != LF_OK) return rc;
     // Detections.area = the dilated colour mask as 0/255 bytes (line_detector_lsd.py:127-133): expanded once for the
     // three colours from the bit planes.  LineDetector2Dense returns the undilated mask (line_detector2.py:104-107).
-    if ((rc = ensure(h, h->dbg_masks, 3 * h->P)) != LF_OK) return rc;
+    if ((rc = scratch(h, h->dbg_masks, 3 * h->P)) != LF_OK) return rc;
     launch_edges_u8(h->canny, 3, h->detector == LF_DETECTOR_DENSE ? h->d_bwbits.p : h->d_maskbits.p, (uint8_t*)h->dbg_masks.p, s);
     h->h_counts.resize(3); h->h_seg_offset.resize(4);
     if ((rc = plugin_fetch_results(h)) != LF_OK) return rc;
@@ -682,20 +652,20 @@ extern "C" int lf_associate(lf_handle* h, const uint8_t* query32, int nq, const 
     }
     const size_t nm_pad = assoc_rows_padded_m(nm);
     int rc;
-    if ((rc = ensure(h, h->a_mx, nm_pad * 256)) != LF_OK) return rc;     // 256 B per 128-B row: the tile loop's LDS-DMA read-ahead is not shown to stay within 128 B x nm_pad
+    if ((rc = scratch(h, h->a_mx, nm_pad * 256)) != LF_OK) return rc;     // 256 B per 128-B row: the tile loop's LDS-DMA read-ahead is not shown to stay within 128 B x nm_pad
     const bool ties = h->tie_rule == LF_TIE_MIHASHER;
-    if (ties && (rc = ensure(h, h->a_best, (size_t)nq * 8)) != LF_OK) return rc;
+    if (ties && (rc = scratch(h, h->a_best, (size_t)nq * 8)) != LF_OK) return rc;
     const uint8_t *dq = query32, *dmp = map32;
     int32_t* didx = idx; float* ddist = dist;
     if (!on_device) {
-        if ((rc = ensure(h, h->a_q, (size_t)nq * 32)) || (rc = ensure(h, h->a_m, (size_t)nm * 32)) ||
-            (rc = ensure(h, h->a_idx, (size_t)nq * 4)) || (rc = ensure(h, h->a_dist, (size_t)nq * 4))) return rc;
+        if ((rc = scratch(h, h->a_q, (size_t)nq * 32)) || (rc = scratch(h, h->a_m, (size_t)nm * 32)) ||
+            (rc = scratch(h, h->a_idx, (size_t)nq * 4)) || (rc = scratch(h, h->a_dist, (size_t)nq * 4))) return rc;
         LF_HIP_CHECK(h, hipMemcpyAsync(h->a_q.p, query32, (size_t)nq * 32, hipMemcpyHostToDevice, s));
         LF_HIP_CHECK(h, hipMemcpyAsync(h->a_m.p, map32, (size_t)nm * 32, hipMemcpyHostToDevice, s));
         dq = (const uint8_t*)h->a_q.p; dmp = (const uint8_t*)h->a_m.p; didx = (int32_t*)h->a_idx.p; ddist = (float*)h->a_dist.p;
     }
     {
-        StageTimer t(h, ST_ASSOC);
+        StageClock::Scope t(h, h->clock, ST_ASSOC);
         h->a_ws.tie_res = ties ? static_cast<unsigned long long*>(h->a_best.p) : nullptr;      // (the distance pass then lists the queries of the tie pass)
         LF_HIP_CHECK(h, launch_assoc(dq, nq, dmp, nm, (int8_t*)h->a_mx.p, h->a_ws, didx, ddist, s));
         if (ties)
@@ -727,18 +697,18 @@ extern "C" int lf_associate_float(lf_handle* h, const float* query72, int nq, co
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = ensure(h, h->a_best, assoc_float_scratch_bytes(nq, nm))) || (rc = ensure(h, h->a_qn, (size_t)nq * 4)) || (rc = ensure(h, h->a_mn, (size_t)nm * 4))) return rc;
+    if ((rc = scratch(h, h->a_best, assoc_float_scratch_bytes(nq, nm))) || (rc = scratch(h, h->a_qn, (size_t)nq * 4)) || (rc = scratch(h, h->a_mn, (size_t)nm * 4))) return rc;
     const float *dq = query72, *dmp = map72;
     int32_t* didx = idx; float* ddist = dist;
     if (!on_device) {
-        if ((rc = ensure(h, h->a_q, (size_t)nq * 288)) || (rc = ensure(h, h->a_m, (size_t)nm * 288)) ||
-            (rc = ensure(h, h->a_idx, (size_t)nq * 4)) || (rc = ensure(h, h->a_dist, (size_t)nq * 4))) return rc;
+        if ((rc = scratch(h, h->a_q, (size_t)nq * 288)) || (rc = scratch(h, h->a_m, (size_t)nm * 288)) ||
+            (rc = scratch(h, h->a_idx, (size_t)nq * 4)) || (rc = scratch(h, h->a_dist, (size_t)nq * 4))) return rc;
         LF_HIP_CHECK(h, hipMemcpyAsync(h->a_q.p, query72, (size_t)nq * 288, hipMemcpyHostToDevice, s));
         LF_HIP_CHECK(h, hipMemcpyAsync(h->a_m.p, map72, (size_t)nm * 288, hipMemcpyHostToDevice, s));
         dq = (const float*)h->a_q.p; dmp = (const float*)h->a_m.p; didx = (int32_t*)h->a_idx.p; ddist = (float*)h->a_dist.p;
     }
     {
-        StageTimer t(h, ST_ASSOC);
+        StageClock::Scope t(h, h->clock, ST_ASSOC);
         LF_HIP_CHECK(h, launch_assoc_float(dq, nq, dmp, nm, (float*)h->a_qn.p, (float*)h->a_mn.p, h->a_best.p, didx, ddist, s));
     }
     LF_HIP_CHECK(h, hipGetLastError());
@@ -761,11 +731,11 @@ extern "C" int lf_select_queries(lf_handle* h, const uint8_t* query32, int nq, c
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     int rc;
-    if ((rc = ensure(h, h->kn_total, 4 * sizeof(int))) != LF_OK) return rc;
+    if ((rc = scratch(h, h->kn_total, 4 * sizeof(int))) != LF_OK) return rc;
     const uint8_t *dq = query32, *dmask = mask;
     uint8_t* dsel = selected32; int32_t* dqi = query_idx;
     if (!on_device) {
-        if ((rc = ensure(h, h->a_q, (size_t)nq * 32)) || (rc = ensure(h, h->a_m, (size_t)nq * 33)) || (rc = ensure(h, h->a_idx, (size_t)nq * 4))) return rc;
+        if ((rc = scratch(h, h->a_q, (size_t)nq * 32)) || (rc = scratch(h, h->a_m, (size_t)nq * 33)) || (rc = scratch(h, h->a_idx, (size_t)nq * 4))) return rc;
         LF_HIP_CHECK(h, hipMemcpyAsync(h->a_q.p, query32, (size_t)nq * 32, hipMemcpyHostToDevice, s));
         uint8_t* m8 = static_cast<uint8_t*>(h->a_m.p) + (size_t)nq * 32;
         LF_HIP_CHECK(h, hipMemcpyAsync(m8, mask, (size_t)nq, hipMemcpyHostToDevice, s));
@@ -802,13 +772,13 @@ extern "C" int lf_knn_match(lf_handle* h, const uint8_t* query32, int nq, const 
     int32_t* didx = idx; float* ddist = dist;
     const size_t out = (size_t)nq * k;
     if (!on_device) {
-        if ((rc = ensure(h, h->a_q, (size_t)nq * 32)) || (rc = ensure(h, h->a_m, (size_t)(nm > 0 ? nm : 1) * 32)) ||
-            (rc = ensure(h, h->a_idx, out * 4)) || (rc = ensure(h, h->a_dist, out * 4))) return rc;
+        if ((rc = scratch(h, h->a_q, (size_t)nq * 32)) || (rc = scratch(h, h->a_m, (size_t)(nm > 0 ? nm : 1) * 32)) ||
+            (rc = scratch(h, h->a_idx, out * 4)) || (rc = scratch(h, h->a_dist, out * 4))) return rc;
         LF_HIP_CHECK(h, hipMemcpyAsync(h->a_q.p, query32, (size_t)nq * 32, hipMemcpyHostToDevice, s));
         if (nm > 0) LF_HIP_CHECK(h, hipMemcpyAsync(h->a_m.p, map32, (size_t)nm * 32, hipMemcpyHostToDevice, s));
         dq = (const uint8_t*)h->a_q.p; dm_ = (const uint8_t*)h->a_m.p; didx = (int32_t*)h->a_idx.p; ddist = (float*)h->a_dist.p;
     }
-    { StageTimer t(h, ST_ASSOC); launch_knn(dq, nq, dm_, nm, k, 128, h->tie_rule == LF_TIE_MIHASHER, didx, ddist, s); }
+    { StageClock::Scope t(h, h->clock, ST_ASSOC); launch_knn(dq, nq, dm_, nm, k, 128, h->tie_rule == LF_TIE_MIHASHER, didx, ddist, s); }
     LF_HIP_CHECK(h, hipGetLastError());
     if (!on_device) {
         LF_HIP_CHECK(h, hipMemcpyAsync(idx, didx, out * 4, hipMemcpyDeviceToHost, s));
@@ -833,19 +803,19 @@ extern "C" int lf_radius_match(lf_handle* h, const uint8_t* query32, int nq, con
     hipStream_t s = h->stream;
     if (nq == 0) { if (on_device) LF_HIP_CHECK(h, hipMemsetAsync(offsets, 0, sizeof(int32_t), s)); else offsets[0] = 0; if (total_out) *total_out = 0; return LF_OK; }
     int rc;
-    if ((rc = ensure(h, h->kn_hist, (size_t)nq * 129 * 4)) || (rc = ensure(h, h->kn_count, (size_t)nq * 4)) || (rc = ensure(h, h->kn_off, (size_t)(nq + 1) * 4)) ||
-        (rc = ensure(h, h->kn_total, 16))) return rc;
+    if ((rc = scratch(h, h->kn_hist, (size_t)nq * 129 * 4)) || (rc = scratch(h, h->kn_count, (size_t)nq * 4)) || (rc = scratch(h, h->kn_off, (size_t)(nq + 1) * 4)) ||
+        (rc = scratch(h, h->kn_total, 16))) return rc;
     const uint8_t *dq = query32, *dm_ = map32;
     int32_t *doff = offsets, *didx = idx; float* ddist = dist;
     if (!on_device) {
-        if ((rc = ensure(h, h->a_q, (size_t)nq * 32)) || (rc = ensure(h, h->a_m, (size_t)(nm > 0 ? nm : 1) * 32)) ||
-            (rc = ensure(h, h->a_idx, (size_t)(cap > 0 ? cap : 1) * 4)) || (rc = ensure(h, h->a_dist, (size_t)(cap > 0 ? cap : 1) * 4))) return rc;
+        if ((rc = scratch(h, h->a_q, (size_t)nq * 32)) || (rc = scratch(h, h->a_m, (size_t)(nm > 0 ? nm : 1) * 32)) ||
+            (rc = scratch(h, h->a_idx, (size_t)(cap > 0 ? cap : 1) * 4)) || (rc = scratch(h, h->a_dist, (size_t)(cap > 0 ? cap : 1) * 4))) return rc;
         LF_HIP_CHECK(h, hipMemcpyAsync(h->a_q.p, query32, (size_t)nq * 32, hipMemcpyHostToDevice, s));
         if (nm > 0) LF_HIP_CHECK(h, hipMemcpyAsync(h->a_m.p, map32, (size_t)nm * 32, hipMemcpyHostToDevice, s));
         dq = (const uint8_t*)h->a_q.p; dm_ = (const uint8_t*)h->a_m.p; doff = (int32_t*)h->kn_off.p; didx = (int32_t*)h->a_idx.p; ddist = (float*)h->a_dist.p;
     }
     {
-        StageTimer t(h, ST_ASSOC);
+        StageClock::Scope t(h, h->clock, ST_ASSOC);
         launch_radius(dq, nq, dm_, nm, md, (int32_t*)h->kn_hist.p, (int32_t*)h->kn_count.p, doff, (int*)h->kn_total.p, cap, h->tie_rule == LF_TIE_MIHASHER, didx, ddist, s);
     }
     LF_HIP_CHECK(h, hipGetLastError());
@@ -884,10 +854,10 @@ extern "C" int lf_kmeans(lf_handle* h, const uint8_t* bgr_points, int n, int on_
     hipStream_t s = h->stream;
     int rc;
     // f64 scratch: [0 .. 3k) init, [64 .. 64 + 3k] centres + inertia; counts: [k] + the status word behind them
-    if ((rc = ensure(h, h->km_lab, (size_t)n)) || (rc = ensure(h, h->km_f64, 128 * sizeof(double))) || (rc = ensure(h, h->km_cnt, 32 * sizeof(long long)))) return rc;
+    if ((rc = scratch(h, h->km_lab, (size_t)n)) || (rc = scratch(h, h->km_f64, 128 * sizeof(double))) || (rc = scratch(h, h->km_cnt, 32 * sizeof(long long)))) return rc;
     const uint8_t* dp = bgr_points;
     if (!on_device) {
-        if ((rc = ensure(h, h->km_pts, (size_t)n * 3)) != LF_OK) return rc;
+        if ((rc = scratch(h, h->km_pts, (size_t)n * 3)) != LF_OK) return rc;
         LF_HIP_CHECK(h, hipMemcpyAsync(h->km_pts.p, bgr_points, (size_t)n * 3, hipMemcpyHostToDevice, s));
         dp = static_cast<const uint8_t*>(h->km_pts.p);
     }
@@ -944,7 +914,7 @@ extern "C" int lf_debug_std_sort(lf_handle* h, const int32_t* keys, int n, int32
     }
     int rc;
     const size_t words = std_sort_debug_words(n);
-    if ((rc = ensure(h, h->a_q, (size_t)n * 4)) || (rc = ensure(h, h->a_m, words * 4)) || (rc = ensure(h, h->a_best, 64))) return rc;
+    if ((rc = scratch(h, h->a_q, (size_t)n * 4)) || (rc = scratch(h, h->a_m, words * 4)) || (rc = scratch(h, h->a_best, 64))) return rc;
     LF_HIP_CHECK(h, hipMemcpyAsync(h->a_q.p, e.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     launch_std_sort_debug(static_cast<const uint32_t*>(h->a_q.p), static_cast<uint32_t*>(h->a_m.p), n, static_cast<int*>(h->a_best.p), s);
     LF_HIP_CHECK(h, hipGetLastError());
@@ -1017,13 +987,13 @@ extern "C" int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t byt
     size_t avail = 0;
     switch (buffer_id) {
     case LF_BUF_BGR: {
-        int rc = ensure(h, h->dbg_bgr, n * h->P * 3);
+        int rc = scratch(h, h->dbg_bgr, n * h->P * 3);
         if (rc != LF_OK) return rc;
         launch_bgrx_to_bgr((int)(n * h->P), h->d_bgr, (uint8_t*)h->dbg_bgr.p, s);
         src = h->dbg_bgr.p; avail = n * h->P * 3; break;
     }
     case LF_BUF_MASKS: {
-        int rc = ensure(h, h->dbg_masks, n * 3 * h->P);
+        int rc = scratch(h, h->dbg_masks, n * 3 * h->P);
         if (rc != LF_OK) return rc;
         launch_edges_u8(h->canny, (int)(n * 3), h->d_maskbits, (uint8_t*)h->dbg_masks.p, s);     // same bit-plane layout as the edge map
         src = h->dbg_masks.p; avail = n * 3 * h->P; break;
@@ -1035,8 +1005,8 @@ extern "C" int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t byt
     case LF_BUF_LSD_MODGRAD: {
         // the pipeline keeps no dense LSD planes: rebuild them from the compact arrays
         const LsdState& L = h->lsd;
-        int rc = ensure(h, h->dbg_ang, n * 3 * L.Ps * sizeof(float));
-        if (rc == LF_OK) rc = ensure(h, h->dbg_mod, n * 3 * L.Ps * sizeof(double));
+        int rc = scratch(h, h->dbg_ang, n * 3 * L.Ps * sizeof(float));
+        if (rc == LF_OK) rc = scratch(h, h->dbg_mod, n * 3 * L.Ps * sizeof(double));
         if (rc != LF_OK) return rc;
         launch_lsd_dense_debug(L.params, (int)n, L.d_norder, L.d_cxy, L.d_cdeg, L.d_cmod, (float*)h->dbg_ang.p, (double*)h->dbg_mod.p, s);
         if (buffer_id == LF_BUF_LSD_ANGLE) { src = h->dbg_ang.p; avail = n * 3 * L.Ps * sizeof(float); }
@@ -1055,8 +1025,8 @@ extern "C" int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t byt
     case LF_BUF_LBD_DX:
     case LF_BUF_LBD_DY: {
         // the pipeline keeps dx and dy interleaved: split them for the caller
-        int rc = ensure(h, h->dbg_dx, n * h->P * sizeof(int16_t));
-        if (rc == LF_OK) rc = ensure(h, h->dbg_dy, n * h->P * sizeof(int16_t));
+        int rc = scratch(h, h->dbg_dx, n * h->P * sizeof(int16_t));
+        if (rc == LF_OK) rc = scratch(h, h->dbg_dy, n * h->P * sizeof(int16_t));
         if (rc != LF_OK) return rc;
         launch_lbd_split_debug(n * h->P, h->d_dxy, (int16_t*)h->dbg_dx.p, (int16_t*)h->dbg_dy.p, s);
         src = buffer_id == LF_BUF_LBD_DX ? h->dbg_dx.p : h->dbg_dy.p;
@@ -1084,12 +1054,7 @@ extern "C" int lf_set_profiling(lf_handle* h, int enabled)
     // would otherwise create some thousand events while it is being timed)
     if (h->profiling) {
         (void)hipSetDevice(h->device);
-        while (h->ev_free.size() < 1024) {
-            EvPair n; n.st = 0;
-            if (hipEventCreate(&n.a) != hipSuccess) break;
-            if (hipEventCreate(&n.b) != hipSuccess) { (void)hipEventDestroy(n.a); break; }
-            h->ev_free.push_back(n);
-        }
+        h->clock.prefill(1024);
     }
     return LF_OK;
 }
@@ -1097,18 +1062,17 @@ extern "C" int lf_set_profiling(lf_handle* h, int enabled)
 extern "C" int lf_reset_timing(lf_handle* h)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
-    timing_resolve(h);
-    memset(h->ms, 0, sizeof(h->ms)); memset(h->launches, 0, sizeof(h->launches));
+    h->clock.take(nullptr, nullptr, 0);
     return LF_OK;
 }
 
 extern "C" int lf_get_timing(lf_handle* h, double* ms_per_stage, int32_t* launches_per_stage, int n)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
-    timing_resolve(h);
+    h->clock.resolve();              // (read, not taken: lf_reset_timing resets)
     for (int i = 0; i < n && i < LF_N_STAGES; ++i) {
-        if (ms_per_stage) ms_per_stage[i] = h->ms[i];
-        if (launches_per_stage) launches_per_stage[i] = h->launches[i];
+        if (ms_per_stage) ms_per_stage[i] = h->clock.ms[i];
+        if (launches_per_stage) launches_per_stage[i] = h->clock.launches[i];
     }
     return LF_OK;
 }
@@ -1225,8 +1189,8 @@ extern "C" int lf_jpeg_decode_batch(lf_handle* h, const uint8_t* const* jpeg, co
     g.Wp = (cols + 15) / 16 * 16;
     g.Hp = (rows + 15) / 16 * 16;
     int rc;
-    if ((rc = ensure(h, J.planes, (size_t)n_frames * 3 * g.Wp * g.Hp)) != LF_OK) return rc;
-    if ((rc = ensure(h, J.hdrs, stage_bytes)) != LF_OK) return rc;       // one device image of the staging buffer
+    if ((rc = scratch(h, J.planes, (size_t)n_frames * 3 * g.Wp * g.Hp)) != LF_OK) return rc;
+    if ((rc = scratch(h, J.hdrs, stage_bytes)) != LF_OK) return rc;       // one device image of the staging buffer
     uint8_t* d_stage = static_cast<uint8_t*>(J.hdrs.p);
     LF_HIP_CHECK(h, hipMemcpyAsync(d_stage, J.h_stage, stage_bytes, hipMemcpyHostToDevice, s));
     LF_HIP_CHECK(h, hipEventRecord(J.staged, s));
@@ -1234,11 +1198,11 @@ extern "C" int lf_jpeg_decode_batch(lf_handle* h, const uint8_t* const* jpeg, co
     uint8_t* d_out = frames;
     const size_t out_bytes = (size_t)n_frames * rows * cols * 3;
     if (!frames_on_device) {
-        if ((rc = ensure(h, J.out, out_bytes)) != LF_OK) return rc;
+        if ((rc = scratch(h, J.out, out_bytes)) != LF_OK) return rc;
         d_out = static_cast<uint8_t*>(J.out.p);
     }
     {
-        StageTimer t(h, ST_JPEG);
+        StageClock::Scope t(h, h->clock, ST_JPEG);
         launch_jpeg_decode(g, n_frames, max_blocks, reinterpret_cast<const lf::jpeg::FrameHeader*>(d_stage),
                            reinterpret_cast<const uint32_t*>(d_stage + off_ent), reinterpret_cast<const uint32_t*>(d_stage + off_blk),
                            static_cast<uint8_t*>(J.planes.p), d_out, s);
@@ -1285,32 +1249,32 @@ extern "C" int lf_serialize_segments(lf_handle* h, const lf_segments* segs, int 
         const int total = segs->frame_offset[n_frames];
         if (total < 0) { lf_set_error(h, LF_ERR_BAD_ARG, "negative segment count"); return LF_ERR_BAD_ARG; }
         const size_t n = (size_t)total;
-        if ((rc = ensure(h, h->m_fo, (size_t)(n_frames + 1) * sizeof(int))) != LF_OK) return rc;
-        if ((rc = ensure(h, h->m_color, n + 1)) != LF_OK) return rc;
+        if ((rc = scratch(h, h->m_fo, (size_t)(n_frames + 1) * sizeof(int))) != LF_OK) return rc;
+        if ((rc = scratch(h, h->m_color, n + 1)) != LF_OK) return rc;
         LF_HIP_CHECK(h, hipMemcpyAsync(h->m_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * sizeof(int), hipMemcpyHostToDevice, s));
         LF_HIP_CHECK(h, hipMemcpyAsync(h->m_color.p, segs->color, n, hipMemcpyHostToDevice, s));
         d_fo = static_cast<const int*>(h->m_fo.p);
         d_color = static_cast<const uint8_t*>(h->m_color.p);
         if (stage == LF_MSG_DETECTOR) {
-            if ((rc = ensure(h, h->m_pn, n * 16 + 16)) != LF_OK) return rc;
-            if ((rc = ensure(h, h->m_nm, n * 8 + 8)) != LF_OK) return rc;
+            if ((rc = scratch(h, h->m_pn, n * 16 + 16)) != LF_OK) return rc;
+            if ((rc = scratch(h, h->m_nm, n * 8 + 8)) != LF_OK) return rc;
             LF_HIP_CHECK(h, hipMemcpyAsync(h->m_pn.p, segs->pixels_normalized, n * 16, hipMemcpyHostToDevice, s));
             LF_HIP_CHECK(h, hipMemcpyAsync(h->m_nm.p, segs->normals, n * 8, hipMemcpyHostToDevice, s));
             d_pn = static_cast<const float*>(h->m_pn.p);
             d_nm = static_cast<const float*>(h->m_nm.p);
         } else {
-            if ((rc = ensure(h, h->m_gr, n * 32 + 32)) != LF_OK) return rc;
+            if ((rc = scratch(h, h->m_gr, n * 32 + 32)) != LF_OK) return rc;
             LF_HIP_CHECK(h, hipMemcpyAsync(h->m_gr.p, segs->ground, n * 32, hipMemcpyHostToDevice, s));
             d_gr = static_cast<const double*>(h->m_gr.p);
             if (stage == LF_MSG_FILTERED) {
-                if ((rc = ensure(h, h->m_keep, n + 1)) != LF_OK) return rc;
+                if ((rc = scratch(h, h->m_keep, n + 1)) != LF_OK) return rc;
                 LF_HIP_CHECK(h, hipMemcpyAsync(h->m_keep.p, segs->keep, n, hipMemcpyHostToDevice, s));
                 d_keep = static_cast<const uint8_t*>(h->m_keep.p);
             }
         }
     }
-    if ((rc = ensure(h, h->m_counts, (size_t)n_frames * sizeof(int))) != LF_OK) return rc;
-    if ((rc = ensure(h, h->m_boff, (size_t)(n_frames + 1) * sizeof(long long))) != LF_OK) return rc;
+    if ((rc = scratch(h, h->m_counts, (size_t)n_frames * sizeof(int))) != LF_OK) return rc;
+    if ((rc = scratch(h, h->m_boff, (size_t)(n_frames + 1) * sizeof(long long))) != LF_OK) return rc;
     launch_msg_layout(n_frames, stage, d_fo, d_keep, static_cast<int*>(h->m_counts.p), static_cast<long long*>(h->m_boff.p), s);
     static_assert(sizeof(long long) == sizeof(int64_t), "byte offsets are int64");
     LF_HIP_CHECK(h, hipMemcpyAsync(frame_byte_offset, h->m_boff.p, (size_t)(n_frames + 1) * sizeof(long long), hipMemcpyDeviceToHost, s));
@@ -1322,7 +1286,7 @@ extern "C" int lf_serialize_segments(lf_handle* h, const lf_segments* segs, int 
     }
     uint8_t* d_out = out;
     if (!out_on_device) {
-        if ((rc = ensure(h, h->m_body, need + 16)) != LF_OK) return rc;
+        if ((rc = scratch(h, h->m_body, need + 16)) != LF_OK) return rc;
         d_out = static_cast<uint8_t*>(h->m_body.p);
     }
     launch_msg_write(n_frames, stage, d_fo, d_color, d_pn, d_nm, d_gr, d_keep, static_cast<const int*>(h->m_counts.p),
@@ -1352,23 +1316,23 @@ extern "C" int lf_deserialize_segments(lf_handle* h, const uint8_t* bodies, int 
     int rc;
     const uint8_t* d_body = bodies;
     if (!bodies_on_device) {
-        if ((rc = ensure(h, h->m_body, bytes + 16)) != LF_OK) return rc;
+        if ((rc = scratch(h, h->m_body, bytes + 16)) != LF_OK) return rc;
         LF_HIP_CHECK(h, hipMemcpyAsync(h->m_body.p, bodies, bytes, hipMemcpyHostToDevice, s));
         d_body = static_cast<const uint8_t*>(h->m_body.p);
     }
-    if ((rc = ensure(h, h->m_boff, (size_t)(n_frames + 1) * sizeof(long long))) != LF_OK) return rc;
-    if ((rc = ensure(h, h->m_bad, sizeof(int))) != LF_OK) return rc;
+    if ((rc = scratch(h, h->m_boff, (size_t)(n_frames + 1) * sizeof(long long))) != LF_OK) return rc;
+    if ((rc = scratch(h, h->m_bad, sizeof(int))) != LF_OK) return rc;
     LF_HIP_CHECK(h, hipMemcpyAsync(h->m_boff.p, frame_byte_offset, (size_t)(n_frames + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
     LF_HIP_CHECK(h, hipMemsetAsync(h->m_bad.p, 0, sizeof(int), s));
     lf_segments dev = *out;
     if (!out_on_device) {
-        if ((rc = ensure(h, h->m_fo, (size_t)(n_frames + 1) * sizeof(int))) != LF_OK) return rc;
+        if ((rc = scratch(h, h->m_fo, (size_t)(n_frames + 1) * sizeof(int))) != LF_OK) return rc;
         dev.frame_offset = static_cast<int32_t*>(h->m_fo.p);
         dev.color = nullptr; dev.pixels_normalized = nullptr; dev.normals = nullptr; dev.ground = nullptr;
-        if (out->color) { if ((rc = ensure(h, h->m_color, max_segs)) != LF_OK) return rc; dev.color = static_cast<uint8_t*>(h->m_color.p); }
-        if (out->pixels_normalized) { if ((rc = ensure(h, h->m_pn, max_segs * 16)) != LF_OK) return rc; dev.pixels_normalized = static_cast<float*>(h->m_pn.p); }
-        if (out->normals) { if ((rc = ensure(h, h->m_nm, max_segs * 8)) != LF_OK) return rc; dev.normals = static_cast<float*>(h->m_nm.p); }
-        if (out->ground) { if ((rc = ensure(h, h->m_gr, max_segs * 32)) != LF_OK) return rc; dev.ground = static_cast<double*>(h->m_gr.p); }
+        if (out->color) { if ((rc = scratch(h, h->m_color, max_segs)) != LF_OK) return rc; dev.color = static_cast<uint8_t*>(h->m_color.p); }
+        if (out->pixels_normalized) { if ((rc = scratch(h, h->m_pn, max_segs * 16)) != LF_OK) return rc; dev.pixels_normalized = static_cast<float*>(h->m_pn.p); }
+        if (out->normals) { if ((rc = scratch(h, h->m_nm, max_segs * 8)) != LF_OK) return rc; dev.normals = static_cast<float*>(h->m_nm.p); }
+        if (out->ground) { if ((rc = scratch(h, h->m_gr, max_segs * 32)) != LF_OK) return rc; dev.ground = static_cast<double*>(h->m_gr.p); }
     }
     const int cap = out->capacity;
     launch_msg_read(n_frames, cap, d_body, static_cast<const long long*>(h->m_boff.p), dev.frame_offset, static_cast<int*>(h->m_bad.p),

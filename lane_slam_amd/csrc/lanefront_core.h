@@ -1,0 +1,221 @@
+// What the three opaque handles of the C ABI (lf_handle, lf_map, lf_lane_filter) share on the host: the fields every one of them
+// carries, the error text, the HIP check, the device check of their creators, the two kinds of clock, the scratch grower and the
+// ordering of one stream behind another.  Host code only; common.h does not include it (tests/hostsim builds lsd_grow.h on the CPU).
+#pragma once
+#include <stdarg.h>
+#include <stdio.h>
+#include <vector>
+#include "common.h"
+
+namespace lf {
+
+// every handle type derives from it
+struct Core {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    char err[512] = "";
+    int err_code = 0;
+    bool profiling = false;
+};
+
+inline void vset_error(Core* c, int code, const char* fmt, va_list ap)
+{
+    if (!c) return;
+    vsnprintf(c->err, sizeof(c->err), fmt, ap);
+    c->err_code = code;
+}
+
+__attribute__((format(printf, 3, 4))) inline void set_error(Core* c, int code, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vset_error(c, code, fmt, ap);
+    va_end(ap);
+}
+
+#define LF_HIP_CHECK(core, expr)                                                                                             \
+    do {                                                                                                                     \
+        hipError_t _e = (expr);                                                                                              \
+        if (_e != hipSuccess) {                                                                                              \
+            lf::set_error((core), LF_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);    \
+            return LF_ERR_HIP;                                                                                               \
+        }                                                                                                                    \
+    } while (0)
+
+// a creator's check of device_id: LF_OK, or the message, with the creator's name in front, in its own buffer
+inline int check_device(int device_id, const char* who, char* buf, size_t size)
+{
+    int ndev = 0;
+    const hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) {
+        snprintf(buf, size, "%s: no HIP device (%s); lanefront has no CPU fallback", who, e != hipSuccess ? hipGetErrorString(e) : "device count 0");
+        return LF_ERR_HIP;
+    }
+    if (device_id < 0 || device_id >= ndev) { snprintf(buf, size, "%s: device %d out of range (%d devices)", who, device_id, ndev); return LF_ERR_BAD_ARG; }
+    return LF_OK;
+}
+
+// a scratch buffer of at least `bytes`; what it held is lost (kernels queued on the core's stream may still use it: they are
+// waited for first)
+template <typename T>
+inline int scratch(Core* c, DevArray<T>& b, size_t bytes)
+{
+    if (b.bytes >= bytes) return LF_OK;
+    if (b.p) { LF_HIP_CHECK(c, hipStreamSynchronize(c->stream)); b.reset(); }
+    LF_HIP_CHECK(c, b.alloc(bytes + bytes / 4 + 256));
+    return LF_OK;
+}
+
+// stream `waits` waits for everything queued so far on stream `on`; ev is an event of the core's, kept for this
+inline int stream_after(Core* c, hipEvent_t ev, hipStream_t waits, hipStream_t on)
+{
+    LF_HIP_CHECK(c, hipEventRecord(ev, on));
+    LF_HIP_CHECK(c, hipStreamWaitEvent(waits, ev, 0));
+    return LF_OK;
+}
+
+// Per-stage time accumulated over many calls, with HIP events recorded on the core's stream.  Events are only recorded inside
+// the pipeline (no host synchronisation); resolve() turns them into milliseconds.  A launch is counted whether or not the core
+// is profiling.  At most `cap` records stay outstanding: then a clock either resolves them on the spot (resolve_when_full) or
+// leaves the bracket at hand untimed.
+struct StageClock {
+    struct Rec { hipEvent_t a, b; int st; };
+    std::vector<double> ms;
+    std::vector<int32_t> launches;
+
+    StageClock(int n_stages, size_t cap, bool resolve_when_full) : ms(n_stages, 0.0), launches(n_stages, 0), cap_(cap), resolve_when_full_(resolve_when_full) {}
+    StageClock(const StageClock&) = delete;
+    StageClock& operator=(const StageClock&) = delete;
+    ~StageClock()
+    {
+        for (std::vector<Rec>* v : { &used_, &free_ })
+            for (Rec& r : *v) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+    }
+
+    // event pairs made ahead, not inside the first profiled calls
+    void prefill(size_t n)
+    {
+        Rec r;
+        while (free_.size() < n && make(&r)) free_.push_back(r);
+    }
+
+    // the events recorded so far become milliseconds of their stages (waits for them)
+    void resolve()
+    {
+        for (Rec& r : used_) {
+            (void)hipEventSynchronize(r.b);
+            float t = 0;
+            if (hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) ms[r.st] += t;
+            free_.push_back(r);
+        }
+        used_.clear();
+    }
+
+    // read and reset the stages [first, first + count) (count < 0: all from first): the first n of them go to ms_out and
+    // launches_out, either of which may be null
+    void take(double* ms_out, int32_t* launches_out, int n, int first = 0, int count = -1)
+    {
+        resolve();
+        const int end = count < 0 ? (int)ms.size() : first + count;
+        for (int i = first; i < end; ++i) {
+            if (i - first < n && ms_out) ms_out[i - first] = ms[i];
+            if (i - first < n && launches_out) launches_out[i - first] = launches[i];
+            ms[i] = 0; launches[i] = 0;
+        }
+    }
+
+    // brackets what is queued on the core's stream within its lifetime as one launch of stage st
+    struct Scope {
+        Core* c; StageClock* k; int st; Rec r; bool on;
+        Scope(Core* c_, StageClock& k_, int st_) : c(c_), k(&k_), st(st_), on(c_->profiling && k_.acquire(&r))
+        {
+            if (on) { r.st = st; (void)hipEventRecord(r.a, c->stream); }
+        }
+        Scope(const Scope&) = delete;
+        Scope& operator=(const Scope&) = delete;
+        ~Scope()
+        {
+            if (on) { (void)hipEventRecord(r.b, c->stream); k->used_.push_back(r); }
+            k->launches[st] += 1;
+        }
+    };
+
+private:
+    std::vector<Rec> free_, used_;
+    size_t cap_;
+    bool resolve_when_full_;
+
+    static bool make(Rec* r)
+    {
+        r->st = 0;
+        if (hipEventCreate(&r->a) != hipSuccess) return false;
+        if (hipEventCreate(&r->b) != hipSuccess) { (void)hipEventDestroy(r->a); return false; }
+        return true;
+    }
+    bool acquire(Rec* r)
+    {
+        if (free_.empty()) {
+            if (used_.size() >= cap_) {
+                if (!resolve_when_full_) return false;
+                resolve();
+            } else {
+                Rec n;
+                if (!make(&n)) return false;
+                free_.push_back(n);
+            }
+        }
+        *r = free_.back(); free_.pop_back();
+        return true;
+    }
+};
+
+// The per-stage times of the LAST call of one entry point: a pair of events per stage, made by the first profiled call and
+// reused by the later ones.
+struct CallClock {
+    bool timed = false;                 // the last call ran with profiling on
+
+    explicit CallClock(int n_stages) : ev_(2 * n_stages, nullptr) {}
+    CallClock(const CallClock&) = delete;
+    CallClock& operator=(const CallClock&) = delete;
+    ~CallClock()
+    {
+        for (hipEvent_t e : ev_) if (e) (void)hipEventDestroy(e);
+    }
+
+    // a call starts: it is timed when its core is profiling
+    int begin(Core* c)
+    {
+        timed = false;
+        stream_ = c->stream;
+        if (c->profiling) for (hipEvent_t& e : ev_) if (!e) LF_HIP_CHECK(c, hipEventCreate(&e));
+        timed = c->profiling;
+        return LF_OK;
+    }
+
+    struct Scope {
+        CallClock* k; int st;
+        Scope(CallClock& k_, int st_) : k(&k_), st(st_) { if (k->timed) (void)hipEventRecord(k->ev_[2 * st], k->stream_); }
+        Scope(const Scope&) = delete;
+        Scope& operator=(const Scope&) = delete;
+        ~Scope() { if (k->timed) (void)hipEventRecord(k->ev_[2 * st + 1], k->stream_); }
+    };
+
+    // the milliseconds of the last timed call's n_stages stages (waits for the last of them)
+    int read(Core* c, int n_stages, double* ms)
+    {
+        LF_HIP_CHECK(c, hipSetDevice(c->device));
+        LF_HIP_CHECK(c, hipEventSynchronize(ev_[2 * n_stages - 1]));
+        for (int st = 0; st < n_stages; ++st) {
+            float t = 0.f;
+            LF_HIP_CHECK(c, hipEventElapsedTime(&t, ev_[2 * st], ev_[2 * st + 1]));
+            ms[st] = t;
+        }
+        return LF_OK;
+    }
+
+private:
+    std::vector<hipEvent_t> ev_;
+    hipStream_t stream_ = nullptr;
+};
+
+}  // namespace lf

@@ -41,8 +41,8 @@ int draw_segments(lf_handle* h, const char* who, int n_frames, const lf_segments
     }
     int rc;
     const size_t rows = n > 0 ? (size_t)n : 1;
-    if ((rc = ensure(h, h->dr_fo, (size_t)(n_frames + 1) * sizeof(int32_t))) || (rc = ensure(h, h->dr_lines, rows * 4 * sizeof(float))) ||
-        (rc = ensure(h, h->dr_color, rows)))
+    if ((rc = scratch(h, h->dr_fo, (size_t)(n_frames + 1) * sizeof(int32_t))) || (rc = scratch(h, h->dr_lines, rows * 4 * sizeof(float))) ||
+        (rc = scratch(h, h->dr_color, rows)))
         return rc;
     hipStream_t s = h->stream;
     LF_HIP_CHECK(h, hipMemcpyAsync(h->dr_fo.p, o, (size_t)(n_frames + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -69,13 +69,13 @@ int draw_run(lf_handle* h, const char* who, const void* src, bool src_bgrx, int 
     const size_t bytes = (size_t)n_frames * rows * cols * 3;
     uint8_t* dst = out;
     if (!out_on_device) {
-        if ((rc = ensure(h, h->dr_img, bytes)) != LF_OK) return rc;
+        if ((rc = scratch(h, h->dr_img, bytes)) != LF_OK) return rc;
         dst = static_cast<uint8_t*>(h->dr_img.p);
         if (!src_bgrx && src == out) src = dst;          // (lf_draw_lines_image staged the caller's image there)
     }
     int* bad = nullptr;
     if (seg_on_device && !out_on_device) {
-        if ((rc = ensure(h, h->dr_bad, sizeof(int))) != LF_OK) return rc;
+        if ((rc = scratch(h, h->dr_bad, sizeof(int))) != LF_OK) return rc;
         bad = static_cast<int*>(h->dr_bad.p);
         LF_HIP_CHECK(h, hipMemsetAsync(bad, 0, sizeof(int), s));
     }
@@ -136,7 +136,7 @@ extern "C" int lf_draw_lines_image(lf_handle* h, const uint8_t* bgr, int n_frame
     if (!images_on_device) {
         // the host image goes to the staging buffer, and the kernel draws there in place
         const size_t bytes = (size_t)n_frames * rows * cols * 3;
-        int rc = ensure(h, h->dr_img, bytes);
+        int rc = scratch(h, h->dr_img, bytes);
         if (rc != LF_OK) return rc;
         LF_HIP_CHECK(h, hipMemcpyAsync(h->dr_img.p, bgr, bytes, hipMemcpyHostToDevice, h->stream));
         src = out_bgr;                                   // draw_run maps it to the staging buffer

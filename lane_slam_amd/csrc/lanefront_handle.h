@@ -8,15 +8,14 @@
 #include <memory>
 #include <utility>
 #include <vector>
-#include "common.h"
+#include "lanefront_core.h"
 #include "jpeg_entropy.h"
 #include "k_edlines_types.h"
 #include "k_hough.h"
 #include "k_jenc.h"
+#include "k_rectify.h"
 
 namespace lf {
-
-struct EvPair { hipEvent_t a, b; int st; };
 
 // JPEG ingest state (allocated on first use, grown on demand)
 struct JpegState {
@@ -45,12 +44,7 @@ struct JencState {
     HostArray<jenc::Tables> h_tab;                  // pinned: what `tab` was copied from
     HostArray<uint32_t> h_sizes;
     int rows = 0, cols = 0, quality = 0;            // what `tab` holds
-    hipEvent_t ev[jenc::kStages + 1] = {};          // around the stages of the last call, with profiling on
-    bool timed = false;
-    ~JencState()
-    {
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
+    CallClock clock{jenc::kStages};                 // lf_jpeg_encode_timing
 };
 
 // GroundProjection.rectify state (lanefront_rectify.hip): made on the first lf_rectify_batch, the map remade after lf_set_camera
@@ -60,12 +54,7 @@ struct RectState {
     int w = 0, h = 0;                               // the camera the map was made for
     bool map_ready = false;
     int maps_built = 0;
-    hipEvent_t ev[2] = {};                          // around the kernel of the last call, with profiling on
-    bool timed = false;
-    ~RectState()
-    {
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
+    CallClock clock{rect::kStages};                 // lf_rectify_timing
 };
 
 // A block of KeyLines on the device: lf_keylines' arrays and the frame of every KeyLine.  Staging of a host caller's block
@@ -199,13 +188,9 @@ struct MatcherState {
 
 }  // namespace lf
 
-struct lf_handle {
+struct lf_handle : lf::Core {
     lf_config cfg;
-    int device = 0;
     int max_frames = 0, cap_lines = 0;
-    hipStream_t stream = nullptr;
-    char err[512];
-    int err_code = 0;
     // geometry
     int Hc = 0, W = 0, Ww = 0;
     size_t P = 0;
@@ -284,11 +269,8 @@ struct lf_handle {
     std::unique_ptr<lf::KlState> kl;      // EDLines / KeyLines state (lanefront_keylines.hip), allocated on first use
     std::unique_ptr<lf::LsdKlState> lsdkl; // LSDDetectorC over octaves (lanefront_lsdkl.hip): an LSD state per pyramid level
     lf::DevBuf m_fo, m_color, m_pn, m_nm, m_gr, m_keep, m_counts, m_boff, m_body, m_bad;   // SegmentList glue scratch
-    // profiling
-    bool profiling = false;
-    std::vector<lf::EvPair> ev_free, ev_used;
-    double ms[LF_N_STAGES];
-    int32_t launches[LF_N_STAGES];
+    // per-stage timing (lf_get_timing): more than 8192 outstanding records are resolved where they arise
+    lf::StageClock clock{LF_N_STAGES, 8192, true};
 };
 
 namespace lf {
@@ -305,13 +287,6 @@ inline int dalloc_(lf_handle* h, DevArray<T>* p, size_t count, const char* what)
 }
 #define dalloc(h, p, count) dalloc_(h, p, count, #p)
 
-inline int ensure(lf_handle* h, DevBuf& b, size_t bytes)
-{
-    if (b.bytes >= bytes) return LF_OK;
-    LF_HIP_CHECK(h, b.alloc(bytes + bytes / 4 + 256));       // (hipFree of the old buffer waits for the device)
-    return LF_OK;
-}
-
 // the camera of h->cfg (K, D, P . R, its size) into the parameters of a-7 (k_segments.hip); lf_create and lf_set_camera
 inline void seg_camera(lf_handle* h)
 {
@@ -326,31 +301,6 @@ inline void seg_camera(lf_handle* h)
             S.RR[3 * i + j] = s;
         }
 }
-
-void timing_resolve(lf_handle* h);
-struct StageTimer {
-    lf_handle* h; int st; EvPair e; bool on;
-    StageTimer(lf_handle* h_, int st_) : h(h_), st(st_), on(h_->profiling)
-    {
-        if (!on) return;
-        if (h->ev_free.empty()) {
-            if (h->ev_used.size() >= 8192) timing_resolve(h);
-            else {
-                EvPair n; n.st = 0;
-                if (hipEventCreate(&n.a) != hipSuccess || hipEventCreate(&n.b) != hipSuccess) { on = false; return; }
-                h->ev_free.push_back(n);
-            }
-        }
-        e = h->ev_free.back(); h->ev_free.pop_back();
-        e.st = st;
-        (void)hipEventRecord(e.a, h->stream);
-    }
-    ~StageTimer()
-    {
-        if (on) { (void)hipEventRecord(e.b, h->stream); h->ev_used.push_back(e); }
-        h->launches[st] += 1;
-    }
-};
 
 // lanefront_api.hip
 int run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_working_image);

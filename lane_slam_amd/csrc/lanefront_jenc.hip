@@ -137,13 +137,13 @@ extern "C" int lf_jpeg_encode_batch(lf_handle* h, const uint8_t* bgr, int bgr_on
     int rc;
     // a host caller's slots are staged no wider than a frame can get
     const size_t bound = lf_jpeg_encode_bound(rows, cols), stage_stride = out_stride < bound ? out_stride : bound;
-    if ((rc = ensure(h, e.tab, sizeof(jenc::Tables))) || (rc = ensure(h, e.coef, nb * 64 * sizeof(int16_t))) ||
-        (rc = ensure(h, e.bits, nb * sizeof(uint32_t))) || (rc = ensure(h, e.dcdiff, nb * sizeof(int16_t))) ||
-        (rc = ensure(h, e.total, n * sizeof(uint32_t))) || (rc = ensure(h, e.bitbuf, n * g.words * sizeof(uint32_t))) ||
-        (rc = ensure(h, e.ff, n * g.chunks * sizeof(uint32_t))))
+    if ((rc = scratch(h, e.tab, sizeof(jenc::Tables))) || (rc = scratch(h, e.coef, nb * 64 * sizeof(int16_t))) ||
+        (rc = scratch(h, e.bits, nb * sizeof(uint32_t))) || (rc = scratch(h, e.dcdiff, nb * sizeof(int16_t))) ||
+        (rc = scratch(h, e.total, n * sizeof(uint32_t))) || (rc = scratch(h, e.bitbuf, n * g.words * sizeof(uint32_t))) ||
+        (rc = scratch(h, e.ff, n * g.chunks * sizeof(uint32_t))))
         return rc;
-    if (!bgr_on_device && (rc = ensure(h, e.in, n * rows * cols * 3))) return rc;
-    if (!out_on_device && ((rc = ensure(h, e.out, n * stage_stride)) || (rc = ensure(h, e.sizes, n * sizeof(uint32_t))))) return rc;
+    if (!bgr_on_device && (rc = scratch(h, e.in, n * rows * cols * 3))) return rc;
+    if (!out_on_device && ((rc = scratch(h, e.out, n * stage_stride)) || (rc = scratch(h, e.sizes, n * sizeof(uint32_t))))) return rc;
     if (!e.h_tab.p) LF_HIP_CHECK(h, e.h_tab.alloc(sizeof(jenc::Tables)));
     if (!out_on_device && e.h_sizes.bytes < n * sizeof(uint32_t)) LF_HIP_CHECK(h, e.h_sizes.alloc(n * sizeof(uint32_t)));
     if (e.rows != rows || e.cols != cols || e.quality != quality) {
@@ -168,32 +168,15 @@ extern "C" int lf_jpeg_encode_batch(lf_handle* h, const uint8_t* bgr, int bgr_on
     uint32_t* total = static_cast<uint32_t*>(e.total.p);
     uint32_t* bitbuf = static_cast<uint32_t*>(e.bitbuf.p);
     uint32_t* ff = static_cast<uint32_t*>(e.ff.p);
-    e.timed = h->profiling;
-    int stage = 0;
-    auto mark = [&]() -> hipError_t {
-        if (!e.timed) return hipSuccess;
-        if (!e.ev[stage]) { const hipError_t err = hipEventCreate(&e.ev[stage]); if (err != hipSuccess) return err; }
-        return hipEventRecord(e.ev[stage++], s);
-    };
-    {
-        LF_HIP_CHECK(h, mark());
-        jenc::launch_transform(src, n_frames, g, tab, coef, s);
-        LF_HIP_CHECK(h, mark());
-        jenc::launch_size(coef, n_frames, g, tab, bits, dcdiff, s);
-        LF_HIP_CHECK(h, mark());
-        jenc::launch_scan_bits(bits, n_frames, g, total, s);
-        LF_HIP_CHECK(h, mark());
-        jenc::launch_zero(total, n_frames, g, bitbuf, s);
-        LF_HIP_CHECK(h, mark());
-        jenc::launch_emit(coef, dcdiff, bits, total, n_frames, g, tab, bitbuf, s);
-        LF_HIP_CHECK(h, mark());
-        jenc::launch_ff_count(bitbuf, total, n_frames, g, ff, s);
-        LF_HIP_CHECK(h, mark());
-        jenc::launch_ff_scan(total, n_frames, g, tab, ff, out_stride, dsz, s);
-        LF_HIP_CHECK(h, mark());
-        jenc::launch_write(bitbuf, total, ff, dsz, n_frames, g, tab, dst, dstride, s);
-        LF_HIP_CHECK(h, mark());
-    }
+    if ((rc = e.clock.begin(h)) != LF_OK) return rc;
+    { CallClock::Scope t(e.clock, 0); jenc::launch_transform(src, n_frames, g, tab, coef, s); }
+    { CallClock::Scope t(e.clock, 1); jenc::launch_size(coef, n_frames, g, tab, bits, dcdiff, s); }
+    { CallClock::Scope t(e.clock, 2); jenc::launch_scan_bits(bits, n_frames, g, total, s); }
+    { CallClock::Scope t(e.clock, 3); jenc::launch_zero(total, n_frames, g, bitbuf, s); }
+    { CallClock::Scope t(e.clock, 4); jenc::launch_emit(coef, dcdiff, bits, total, n_frames, g, tab, bitbuf, s); }
+    { CallClock::Scope t(e.clock, 5); jenc::launch_ff_count(bitbuf, total, n_frames, g, ff, s); }
+    { CallClock::Scope t(e.clock, 6); jenc::launch_ff_scan(total, n_frames, g, tab, ff, out_stride, dsz, s); }
+    { CallClock::Scope t(e.clock, 7); jenc::launch_write(bitbuf, total, ff, dsz, n_frames, g, tab, dst, dstride, s); }
     LF_HIP_CHECK(h, hipGetLastError());
     if (out_on_device) return LF_OK;
     LF_HIP_CHECK(h, hipMemcpyAsync(e.h_sizes.p, dsz, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -217,18 +200,11 @@ extern "C" int lf_jpeg_encode_timing(lf_handle* h, double* ms_per_stage, int n)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
     if (!ms_per_stage || n < jenc::kStages) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_jpeg_encode_timing: room for %d stages", jenc::kStages); return LF_ERR_BAD_ARG; }
-    if (!h->jenc || !h->jenc->timed) {
+    if (!h->jenc || !h->jenc->clock.timed) {
         lf_set_error(h, LF_ERR_BAD_ARG, "lf_jpeg_encode_timing: no lf_jpeg_encode_batch ran with profiling on (lf_set_profiling)");
         return LF_ERR_BAD_ARG;
     }
-    JencState& e = *h->jenc;
-    LF_HIP_CHECK(h, hipEventSynchronize(e.ev[jenc::kStages]));
-    for (int k = 0; k < jenc::kStages; ++k) {
-        float ms = 0.f;
-        LF_HIP_CHECK(h, hipEventElapsedTime(&ms, e.ev[k], e.ev[k + 1]));
-        ms_per_stage[k] = ms;
-    }
-    return LF_OK;
+    return h->jenc->clock.read(h, jenc::kStages, ms_per_stage);
 }
 
 extern "C" const char* lf_jpeg_encode_stage_name(int stage)

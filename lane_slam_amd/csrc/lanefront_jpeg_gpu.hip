@@ -114,9 +114,9 @@ static int jpeg_decode_gpu(lf_handle* h, const uint8_t* const* jpeg, const size_
     g.first_row = first_row > 0 && first_row < rows ? first_row : 0;
     int rc;
     const size_t up_bytes = fr_bytes + st_bytes + raw_off + 64;
-    if ((rc = ensure(h, J.planes, (size_t)n_frames * 3 * g.Wp * g.Hp)) || (rc = ensure(h, J.hdrs, up_bytes)) ||
-        (rc = ensure(h, J.gh_clean, clean_off + 64)) || (rc = ensure(h, J.gh_sub, (sub_off + 16) * 4)) || (rc = ensure(h, J.gh_seg, (seg_off + 16) * 4)) ||
-        (rc = ensure(h, J.gh_info, (size_t)n_frames * jh_info_bytes())) || (rc = ensure(h, J.gh_coef, (coef_blocks + 1) * 128)))
+    if ((rc = scratch(h, J.planes, (size_t)n_frames * 3 * g.Wp * g.Hp)) || (rc = scratch(h, J.hdrs, up_bytes)) ||
+        (rc = scratch(h, J.gh_clean, clean_off + 64)) || (rc = scratch(h, J.gh_sub, (sub_off + 16) * 4)) || (rc = scratch(h, J.gh_seg, (seg_off + 16) * 4)) ||
+        (rc = scratch(h, J.gh_info, (size_t)n_frames * jh_info_bytes())) || (rc = scratch(h, J.gh_coef, (coef_blocks + 1) * 128)))
         return rc;
     uint8_t* d_stage = static_cast<uint8_t*>(J.hdrs.p);
     LF_HIP_CHECK(h, hipMemcpyAsync(d_stage, J.h_stage, up_bytes, hipMemcpyHostToDevice, s));
@@ -126,13 +126,13 @@ static int jpeg_decode_gpu(lf_handle* h, const uint8_t* const* jpeg, const size_
     uint8_t* d_out = frames;
     const size_t out_bytes = (size_t)n_frames * rows * cols * 3;
     if (!frames_on_device) {
-        if ((rc = ensure(h, J.out, out_bytes)) != LF_OK) return rc;
+        if ((rc = scratch(h, J.out, out_bytes)) != LF_OK) return rc;
         d_out = static_cast<uint8_t*>(J.out.p);
     }
     DevFrame* d_frames = reinterpret_cast<DevFrame*>(d_stage);
     int* d_status = reinterpret_cast<int*>(d_stage + fr_bytes);
     {
-        StageTimer t(h, ST_JPEG);
+        StageClock::Scope t(h, h->clock, ST_JPEG);
         launch_jh_decode(g, n_frames, max_blocks, max_scan, d_frames, d_stage + fr_bytes + st_bytes, static_cast<uint8_t*>(J.gh_clean.p),
                          static_cast<uint32_t*>(J.gh_seg.p), J.gh_info.p, static_cast<uint32_t*>(J.gh_sub.p), static_cast<int16_t*>(J.gh_coef.p),
                          d_status, static_cast<uint8_t*>(J.planes.p), s);

@@ -53,7 +53,7 @@ static int kl_plan_lds(lf_handle* h, int n_octaves, int scan)
         lds = std::max(lds, ed_detect_lds_bytes(q.W, q.H, scan, &in_lds));
         q.marks_in_lds = in_lds;
         int rc;
-        if (!in_lds && (rc = ensure(h, q.gmarks, (size_t)h->max_frames * (((size_t)q.W * q.H + 31) / 32) * 4))) return rc;
+        if (!in_lds && (rc = scratch(h, q.gmarks, (size_t)h->max_frames * (((size_t)q.W * q.H + 31) / 32) * 4))) return rc;
     }
     if (lds > 160 * 1024) { lf_set_error(h, LF_ERR_UNSUPPORTED, "EDLines: scan_intervals %d on a %dx%d image needs %zu B of LDS", scan, h->Hc, h->W, lds); return LF_ERR_UNSUPPORTED; }
     k->lds_bytes = lds;
@@ -80,24 +80,24 @@ static int kl_alloc_octaves(lf_handle* h, int n_octaves)
         if (ml < 16) ml = 16;
         q.max_lines = ml;
         int rc;
-        if ((o > 0 && (rc = ensure(h, q.src, B * P))) || (rc = ensure(h, q.blur, B * P)) || (rc = ensure(h, q.dxy, B * P * 4)) ||
-            (rc = ensure(h, q.g, B * P * 2)) || (rc = ensure(h, q.anchors, B * q.cap * 4)) || (rc = ensure(h, q.part, B * q.cap * 4)) ||
-            (rc = ensure(h, q.chain, B * q.cap * 8)) || (rc = ensure(h, q.sid, B * (size_t)(q.max_edges + 2) * 4)) || (rc = ensure(h, q.counts, B * 16)) ||
-            (rc = ensure(h, q.l_ep, B * ml * 16)) || (rc = ensure(h, q.l_c, B * ml * 8)) || (rc = ensure(h, q.l_dir, B * ml * 4)) ||
-            (rc = ensure(h, q.l_npx, B * ml * 4)) || (rc = ensure(h, q.l_sal, B * ml * 4)) || (rc = ensure(h, q.tl, B * (size_t)ml * 48)) || (rc = ensure(h, q.ework, B * 3 * (size_t)(q.max_edges + 2) * 4)))
+        if ((o > 0 && (rc = scratch(h, q.src, B * P))) || (rc = scratch(h, q.blur, B * P)) || (rc = scratch(h, q.dxy, B * P * 4)) ||
+            (rc = scratch(h, q.g, B * P * 2)) || (rc = scratch(h, q.anchors, B * q.cap * 4)) || (rc = scratch(h, q.part, B * q.cap * 4)) ||
+            (rc = scratch(h, q.chain, B * q.cap * 8)) || (rc = scratch(h, q.sid, B * (size_t)(q.max_edges + 2) * 4)) || (rc = scratch(h, q.counts, B * 16)) ||
+            (rc = scratch(h, q.l_ep, B * ml * 16)) || (rc = scratch(h, q.l_c, B * ml * 8)) || (rc = scratch(h, q.l_dir, B * ml * 4)) ||
+            (rc = scratch(h, q.l_npx, B * ml * 4)) || (rc = scratch(h, q.l_sal, B * ml * 4)) || (rc = scratch(h, q.tl, B * (size_t)ml * 48)) || (rc = scratch(h, q.ework, B * 3 * (size_t)(q.max_edges + 2) * 4)))
             return rc;
         // cv::resize(blur, image, Size(), 1 / factor, 1 / factor): saturate_cast<int>(n * inv) (:721)
         const int Wn = dm::round_half_even(W * inv), Hn = dm::round_half_even(Hh * inv);
         if (o + 1 < n_octaves && Wn >= 1 && Hn >= 1) {       // the tables of the resize to the next octave
             std::vector<int> tab(4 * ((size_t)Wn + Hn));
             ed_resize_tables(Hh, W, Hn, Wn, 1. / inv, tab.data());
-            if ((rc = ensure(h, q.rs_tab, tab.size() * 4))) return rc;
+            if ((rc = scratch(h, q.rs_tab, tab.size() * 4))) return rc;
             LF_HIP_CHECK(h, hipMemcpy(q.rs_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         }
         W = Wn; Hh = Hn;
     }
     int rc;
-    if ((rc = ensure(h, k->status, B * 4)) || (rc = k->batch.alloc(h))) return rc;
+    if ((rc = scratch(h, k->status, B * 4)) || (rc = k->batch.alloc(h))) return rc;
     k->n_octaves = n_octaves;
     return LF_OK;
 }
@@ -115,7 +115,7 @@ static int kl_prepare(lf_handle* h, int n_octaves, int scan)
 template <typename T>
 static int kl_stage(lf_handle* h, DevBuf& b, size_t bytes, bool need, T*& dev)
 {
-    const int rc = need ? ensure(h, b, bytes) : LF_OK;
+    const int rc = need ? scratch(h, b, bytes) : LF_OK;
     dev = need && rc == LF_OK ? static_cast<T*>(b.p) : nullptr;
     return rc;
 }
@@ -177,7 +177,7 @@ int KlBatch::alloc(lf_handle* h)
 {
     const size_t B = (size_t)h->max_frames;
     int rc;
-    if ((rc = ensure(h, frame_count, B * 4)) || (rc = ensure(h, frame_offset, (B + 1) * 4)) || (rc = ensure(h, totals, 16))) return rc;
+    if ((rc = scratch(h, frame_count, B * 4)) || (rc = scratch(h, frame_offset, (B + 1) * 4)) || (rc = scratch(h, totals, 16))) return rc;
     if (!h_pinned) LF_HIP_CHECK(h, h_pinned.alloc((2 + B) * sizeof(int)));
     return LF_OK;
 }
@@ -185,7 +185,7 @@ int KlBatch::alloc(lf_handle* h)
 int KlBatch::upload(lf_handle* h, DevBuf& buf, const uint8_t* planes, int n, const uint8_t** d)
 {
     int rc;
-    if ((rc = ensure(h, buf, (size_t)h->max_frames * h->P)) != LF_OK) return rc;
+    if ((rc = scratch(h, buf, (size_t)h->max_frames * h->P)) != LF_OK) return rc;
     LF_HIP_CHECK(h, hipMemcpyAsync(buf.p, planes, h->P * n, hipMemcpyHostToDevice, h->stream));
     *d = static_cast<const uint8_t*>(buf.p);
     return LF_OK;
@@ -205,7 +205,7 @@ int KlBatch::images(lf_handle* h, const uint8_t* images, int n, int input_kind, 
 int KlBatch::keylines(lf_handle* h, const char* who, const lf_keylines& out, int on_device, int describe, lf_keylines* dev)
 {
     int rc;
-    if ((rc = ensure(h, line_frame, (size_t)out.capacity * 4)) != LF_OK) return rc;
+    if ((rc = scratch(h, line_frame, (size_t)out.capacity * 4)) != LF_OK) return rc;
     int32_t* fo = static_cast<int32_t*>(frame_offset.p);
     if (!on_device) {
         if ((rc = staged.stage(h, out, describe, dev)) != LF_OK) return rc;
@@ -259,7 +259,7 @@ static int kl_run_octaves(lf_handle* h, const uint8_t* gray0, int n_frames, int 
     KlState* k = h->kl.get();
     hipStream_t s = h->stream;
     {
-        StageTimer t(h, ST_LBD_GRAD);
+        StageClock::Scope t(h, h->clock, ST_LBD_GRAD);
         float preSigma2 = 0.f, curSigma2 = 1.0f;
         // (the resize tables were made with scale = 1 / inv, inv = (double)(1.f) / sqrt(2): kl_alloc_octaves)
         for (int o = 0; o < n_octaves; ++o) {
@@ -272,7 +272,7 @@ static int kl_run_octaves(lf_handle* h, const uint8_t* gray0, int n_frames, int 
                 // Params::ksize_ other than the default: the general blur first, then the fused kernel with taps that change nothing
                 int rc, tk[31];
                 const size_t px = (size_t)h->max_frames * q.W * q.H;
-                if ((rc = ensure(h, k->any_tmp, px * 4)) != LF_OK || (rc = ensure(h, k->any_blur, px)) != LF_OK) return rc;
+                if ((rc = scratch(h, k->any_tmp, px * 4)) != LF_OK || (rc = scratch(h, k->any_blur, px)) != LF_OK) return rc;
                 kl_gaussian_taps_q8_any(P.ksize, (double)increaseSigma, tk);
                 launch_ed_blur_any(q.H, q.W, n_frames, src, tk, P.ksize, static_cast<int*>(k->any_tmp.p), static_cast<uint8_t*>(k->any_blur.p), s);
                 src = static_cast<const uint8_t*>(k->any_blur.p);
@@ -284,7 +284,7 @@ static int kl_run_octaves(lf_handle* h, const uint8_t* gray0, int n_frames, int 
             if (P.scan_intervals == 2) {
                 const size_t words = 2 * ed_anchor_words(q.W, q.H);
                 int rc;
-                if ((rc = ensure(h, q.aflags, (size_t)h->max_frames * words * 4 + 16)) != LF_OK) return rc;
+                if ((rc = scratch(h, q.aflags, (size_t)h->max_frames * words * 4 + 16)) != LF_OK) return rc;
                 af = static_cast<uint32_t*>(q.aflags.p);
                 LF_HIP_CHECK(h, hipMemsetAsync(af, 0, (size_t)n_frames * words * 4, s));
                 q.aflags_on = true;
@@ -304,7 +304,7 @@ static int kl_run_octaves(lf_handle* h, const uint8_t* gray0, int n_frames, int 
     EdFitParams fp;
     fp.anchor_threshold = P.anchor_threshold; fp.scan = P.scan_intervals; fp.min_line_len = P.min_line_len; fp.fit_err = P.line_fit_err_threshold;
     {
-        StageTimer t(h, ST_LSD_GROW);          // the sequential part of this detector is accounted where LSD's is
+        StageClock::Scope t(h, h->clock, ST_LSD_GROW);          // the sequential part of this detector is accounted where LSD's is
         const int e = launch_ed_detect(all, fp, n_octaves, n_frames, k->lds_bytes, s);
         if (e != 0) { lf_set_error(h, LF_ERR_HIP, "k_ed_detect: %zu B of dynamic LDS refused (%s)", k->lds_bytes, hipGetErrorString((hipError_t)e)); return LF_ERR_HIP; }
     }
@@ -387,7 +387,7 @@ static int keylines_batch_impl(lf_handle* h, const uint8_t* images, int n_frames
     if (input_kind == 0) {
         h->plugin_ready = false;
         // the gray working image alone: the octave detector reads nothing else of k_pre's (round 6)
-        { StageTimer t(h, ST_PRE); launch_pre_gray(h->pre, gray0, n_frames, h->d_gray, s); }
+        { StageClock::Scope t(h, h->clock, ST_PRE); launch_pre_gray(h->pre, gray0, n_frames, h->d_gray, s); }
         gray0 = h->d_gray;
     }
     EdAll all;
@@ -395,7 +395,7 @@ static int keylines_batch_impl(lf_handle* h, const uint8_t* images, int n_frames
     lf_keylines dev;
     if ((rc = b.keylines(h, "lf_keylines_batch", *out, out_on_device, describe, &dev)) != LF_OK) return rc;
     {
-        StageTimer t(h, ST_SEGMENTS);
+        StageClock::Scope t(h, h->clock, ST_SEGMENTS);
         launch_kl_count(all, n_octaves, n_frames, static_cast<int*>(b.frame_count.p), static_cast<int*>(k->status.p), s);
         launch_kl_offsets(n_frames, static_cast<const int*>(b.frame_count.p), cap_out, dev.frame_offset, static_cast<int*>(b.totals.p), s);
         const KlOut ko_final = kl_out(dev, static_cast<int32_t*>(b.line_frame.p));
@@ -403,8 +403,8 @@ static int keylines_batch_impl(lf_handle* h, const uint8_t* images, int n_frames
         int* d_fo = dev.frame_offset;
         if (masks) {
             // assembled into scratch arrays first; the kept KeyLines move to the caller's below
-            if ((rc = ensure(h, k->m_fo, ((size_t)h->max_frames + 1) * 4)) || (rc = ensure(h, k->m_totals, 16 + (size_t)h->max_frames * 4)) ||
-                (rc = ensure(h, k->m_erased, (size_t)cap_out)) || (rc = ensure(h, k->m_kept, (size_t)h->max_frames * 4)) || (rc = k->unmasked.all(h, cap_out, &ko)))
+            if ((rc = scratch(h, k->m_fo, ((size_t)h->max_frames + 1) * 4)) || (rc = scratch(h, k->m_totals, 16 + (size_t)h->max_frames * 4)) ||
+                (rc = scratch(h, k->m_erased, (size_t)cap_out)) || (rc = scratch(h, k->m_kept, (size_t)h->max_frames * 4)) || (rc = k->unmasked.all(h, cap_out, &ko)))
                 return rc;
             d_fo = static_cast<int*>(k->m_fo.p);
             launch_kl_offsets(n_frames, static_cast<const int*>(b.frame_count.p), cap_out, d_fo, static_cast<int*>(k->m_totals.p), s);
@@ -414,7 +414,7 @@ static int keylines_batch_impl(lf_handle* h, const uint8_t* images, int n_frames
         big_stride = big_stride > 32768 ? 32768 : ((big_stride + 7) & ~7);
         // LF_KL_LDS_LINES: test hook -- frames with more lines than this take the global-scratch variant (default: what LDS holds)
         const int lds_lines = h->env_kl_lds_lines > 0 ? h->env_kl_lds_lines : 4096;
-        if (big_stride > lds_lines && (rc = ensure(h, k->big, (size_t)h->max_frames * big_stride * 10)) != LF_OK) return rc;
+        if (big_stride > lds_lines && (rc = scratch(h, k->big, (size_t)h->max_frames * big_stride * 10)) != LF_OK) return rc;
         launch_kl_assemble(all, n_octaves, n_frames, d_fo, cap_out, ko, static_cast<uint8_t*>(k->big.p), big_stride, lds_lines, s);
         if (masks) {
             const uint8_t* dmask = masks;
@@ -424,7 +424,7 @@ static int keylines_batch_impl(lf_handle* h, const uint8_t* images, int n_frames
         }
     }
     if (describe && (dev.desc || dev.code)) {
-        StageTimer t(h, ST_LBD);
+        StageClock::Scope t(h, h->clock, ST_LBD);
         LbdPlanes pl;
         for (int o = 0; o < LF_MAX_OCTAVES; ++o) {
             pl.base[o] = o < n_octaves ? static_cast<const uint32_t*>(k->oct[o].dxy.p) : nullptr;
@@ -502,9 +502,9 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
     const float *d_io = in_octave4, *d_ang = angle;
     float* d_desc = desc72; uint8_t* d_code = code32;
     if (!on_device) {
-        if ((rc = ensure(h, k->batch.gray, (size_t)h->max_frames * P0)) || (rc = ensure(h, k->d_frame, nn * 4)) || (rc = ensure(h, k->d_io, nn * 16)) ||
-            (rc = ensure(h, k->d_angle, nn * 4)) || (rc = ensure(h, k->d_npx, nn * 4)) || (rc = ensure(h, k->d_oct, nn * 4)) ||
-            (rc = ensure(h, k->d_desc, nn * 288)) || (rc = ensure(h, k->d_code, nn * 32)))
+        if ((rc = scratch(h, k->batch.gray, (size_t)h->max_frames * P0)) || (rc = scratch(h, k->d_frame, nn * 4)) || (rc = scratch(h, k->d_io, nn * 16)) ||
+            (rc = scratch(h, k->d_angle, nn * 4)) || (rc = scratch(h, k->d_npx, nn * 4)) || (rc = scratch(h, k->d_oct, nn * 4)) ||
+            (rc = scratch(h, k->d_desc, nn * 288)) || (rc = scratch(h, k->d_code, nn * 32)))
             return rc;
         LF_HIP_CHECK(h, hipMemcpyAsync(k->batch.gray.p, gray, P0 * n_frames, hipMemcpyHostToDevice, s));
         LF_HIP_CHECK(h, hipMemcpyAsync(k->d_frame.p, line_frame, nn * 4, hipMemcpyHostToDevice, s));
@@ -517,7 +517,7 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
         d_npx = static_cast<const int32_t*>(k->d_npx.p); d_oct = static_cast<const int32_t*>(k->d_oct.p);
         d_desc = desc72 ? static_cast<float*>(k->d_desc.p) : nullptr; d_code = code32 ? static_cast<uint8_t*>(k->d_code.p) : nullptr;
     }
-    if ((rc = ensure(h, k->d_n, 16)) != LF_OK) return rc;
+    if ((rc = scratch(h, k->d_n, 16)) != LF_OK) return rc;
     LF_HIP_CHECK(h, hipMemcpyAsync(k->d_n.p, &n, sizeof(int), hipMemcpyHostToDevice, s));
     // computeGaussianPyramid (:350-371) + computeSobel (:374-398): level 0 = GaussianBlur(5x5, sigma 1), level o = pyrDown
     LbdPlanes pl;
@@ -527,15 +527,15 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
     int taps1[5], ident[5] = { 0, 0, 256, 0, 0 };
     kl_gaussian_taps_q8_any(5, 1.0, taps1);
     {
-        StageTimer t(h, ST_LBD_GRAD);
+        StageClock::Scope t(h, h->clock, ST_LBD_GRAD);
         for (int o = 0; o <= max_oct; ++o) {
             if (W < 8 || Hh < 8) break;
             KlOctave& q = k->oct[o];
             const size_t P = (size_t)W * Hh;
-            if ((rc = ensure(h, q.blur, B * P)) || (rc = ensure(h, q.dxy, B * P * 4)) || (rc = ensure(h, q.g, B * P * 2)) ||
-                (o > 0 && (rc = ensure(h, q.src, B * P))))
+            if ((rc = scratch(h, q.blur, B * P)) || (rc = scratch(h, q.dxy, B * P * 4)) || (rc = scratch(h, q.g, B * P * 2)) ||
+                (o > 0 && (rc = scratch(h, q.src, B * P))))
                 return rc;
-            // ensure() may have replaced buffers the keylines path sized: force a re-plan there
+            // scratch() may have replaced buffers the keylines path sized: force a re-plan there
             k->n_octaves = 0;
             const uint8_t* src = o == 0 ? d_gray : static_cast<const uint8_t*>(q.src.p);
             launch_ed_grad(Hh, W, n_frames, src, o == 0 ? taps1 : ident, 80, static_cast<uint8_t*>(q.blur.p), static_cast<uint32_t*>(q.dxy.p),
@@ -543,7 +543,7 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
             pl.base[o] = static_cast<const uint32_t*>(q.dxy.p); pl.W[o] = W; pl.H[o] = Hh;
             if (o < max_oct && W / 2 >= 8 && Hh / 2 >= 8) {
                 DevBuf& next = k->oct[o + 1].src;
-                if ((rc = ensure(h, next, B * (size_t)(W / 2) * (Hh / 2))) != LF_OK) return rc;
+                if ((rc = scratch(h, next, B * (size_t)(W / 2) * (Hh / 2))) != LF_OK) return rc;
                 launch_pyrdown(Hh, W, n_frames, static_cast<const uint8_t*>(q.blur.p), static_cast<uint8_t*>(next.p), s);
             }
             W /= 2; Hh /= 2;
@@ -552,7 +552,7 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
     // (k_lbd writes zero descriptors for a line whose level was not built: the checks above keep every line off that path)
     for (int i = 0; i < n; ++i) if (!pl.base[h_oct[i]]) { lf_set_error(h, LF_ERR_UNSUPPORTED, "lf_describe_keylines: octave %d of a %dx%d image is too small", h_oct[i], h->Hc, h->W); return LF_ERR_UNSUPPORTED; }
     {
-        StageTimer t(h, ST_LBD);
+        StageClock::Scope t(h, h->clock, ST_LBD);
         launch_lbd_keylines(pl, n, n_frames, static_cast<const int*>(k->d_n.p), d_io, d_ang, d_npx, d_oct, d_frame, h->d_gauss_g, h->d_gauss_l, d_desc, d_code, s,
                             h->desc_params.width_of_band);
     }
@@ -609,14 +609,14 @@ int lf::run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n)
     int rc;
     if ((rc = kl_prepare(h, 1, P.scan_intervals)) != LF_OK) return rc;
     h->draw_frames = 0;                  // d_bgr is rewritten (lf_draw_lines)
-    { StageTimer t(h, ST_PRE); launch_pre(h->pre, d_frames, n, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s); }
+    { StageClock::Scope t(h, h->clock, ST_PRE); launch_pre(h->pre, d_frames, n, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s); }
     EdAll all;
     if ((rc = kl_run_octaves(h, h->d_gray, n, 1, P, all)) != LF_OK) return rc;
     LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_norder, 0, (size_t)n * 3 * sizeof(int), s));        // (LSD's slice statistics: nothing to learn from this batch)
     h->slot_mode = SEG_FLOAT;
     LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_overflow + 4, 0, sizeof(int), s));
     {
-        StageTimer t(h, ST_SEGMENTS);
+        StageClock::Scope t(h, h->clock, ST_SEGMENTS);
         launch_ed_slots(all, n, h->d_maskbits, h->Ww, h->cap_lines, h->d_slot_lines, h->d_counts, h->lsd.d_overflow + 4, s);
     }
     h->kl->last_octaves = 1; h->kl->last_frames = n;
@@ -687,7 +687,7 @@ extern "C" int lf_set_image_edlines(lf_handle* h, const uint8_t* bgr, int rows, 
     for (int i = 0; i < 3; ++i) { pp.ai_scale[i] = 1.f; pp.ai_shift[i] = 0.f; }
     pp.identity_ai = 1;
     h->draw_frames = 0;                  // d_bgr is rewritten (lf_draw_lines)
-    { StageTimer t(h, ST_PRE); launch_pre(pp, h->d_frames, 1, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s); }
+    { StageClock::Scope t(h, h->clock, ST_PRE); launch_pre(pp, h->d_frames, 1, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s); }
     EdAll all;
     if ((rc = kl_run_octaves(h, h->d_gray, 1, 1, P, all)) != LF_OK) return rc;
     launch_ed_slots(all, 1, h->d_maskbits, h->Ww, h->cap_lines, h->d_slot_lines, h->d_counts, nullptr, s);
@@ -696,7 +696,7 @@ extern "C" int lf_set_image_edlines(lf_handle* h, const uint8_t* bgr, int rows, 
     lf_segments dev = h->d_out;
     dev.desc = nullptr; dev.code = nullptr;
     if ((rc = run_segments(h, 1, dev, false)) != LF_OK) return rc;
-    if ((rc = ensure(h, h->dbg_masks, 3 * h->P)) != LF_OK) return rc;
+    if ((rc = scratch(h, h->dbg_masks, 3 * h->P)) != LF_OK) return rc;
     launch_edges_u8(h->canny, 3, h->d_maskbits, (uint8_t*)h->dbg_masks.p, s);
     h->h_counts.resize(3); h->h_seg_offset.resize(4);
     if ((rc = plugin_fetch_results(h)) != LF_OK) return rc;

@@ -1,23 +1,21 @@
 // lanefront C ABI, histogram lane filter part (include/lanefront.h "Histogram lane filter"): configuration, tables and the
 // host-side sequencing of k_lane_filter.hip on the filter's own HIP stream.
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 #include <new>
 #include <vector>
 #include "k_lane_filter.h"
+#include "lanefront_core.h"
 
 using namespace lf;
 
-struct lf_lane_filter {
+struct lf_lane_filter : lf::Core {
     lf_lane_filter_config cfg;
     LfGrid g;
-    int device = 0, n_streams = 0, max_frames = 0, last_frames = 0;
-    hipStream_t stream = nullptr;
+    int n_streams = 0, max_frames = 0, last_frames = 0;
     hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_staged = nullptr, ev_done = nullptr;
     bool staged_pending = false;
-    char err[512];
     DevArray<double> belief, init, sinp, wd, wphi, dtvw, belief_out, ml_out, seg_ground;
     DevArray<int> plan, counts, n_votes, fstream, seg_fo;
     DevArray<uint8_t> seg_color;
@@ -27,56 +25,14 @@ struct lf_lane_filter {
     HostArray<int> h_fstream, h_fo;
     HostArray<uint8_t> h_color;
     HostArray<LfPoseDev> h_poses;
-    // per-kernel timing with HIP events on the filter's stream (lf_lane_filter_get_timing)
-    struct Ev { hipEvent_t a, b; int st; };
-    bool profiling = false;
-    std::vector<Ev> ev_free, ev_used;
-    double ms[LF_LANE_FILTER_N_STAGES] = {};
-    int32_t launches[LF_LANE_FILTER_N_STAGES] = {};
+    // per-kernel timing (lf_lane_filter_get_timing); past 4096 outstanding records a bracket goes untimed
+    StageClock clock{LF_LANE_FILTER_N_STAGES, 4096, false};
 };
-
-namespace {
-struct LfTimer {
-    lf_lane_filter* f; lf_lane_filter::Ev e; bool on;
-    LfTimer(lf_lane_filter* f_, int st) : f(f_), on(f_->profiling)
-    {
-        f->launches[st] += 1;
-        if (!on) return;
-        if (f->ev_free.empty()) {
-            lf_lane_filter::Ev n; n.st = 0;
-            if (f->ev_used.size() >= 4096 || hipEventCreate(&n.a) != hipSuccess) { on = false; return; }
-            if (hipEventCreate(&n.b) != hipSuccess) { (void)hipEventDestroy(n.a); on = false; return; }
-            f->ev_free.push_back(n);
-        }
-        e = f->ev_free.back(); f->ev_free.pop_back();
-        e.st = st;
-        (void)hipEventRecord(e.a, f->stream);
-    }
-    ~LfTimer() { if (on) { (void)hipEventRecord(e.b, f->stream); f->ev_used.push_back(e); } }
-};
-}
 
 static const char* kLfStageNames[LF_LANE_FILTER_N_STAGES] = { "lf_vote", "lf_chain" };
 extern "C" const char* lf_lane_filter_stage_name(int stage) { return (stage >= 0 && stage < LF_LANE_FILTER_N_STAGES) ? kLfStageNames[stage] : "?"; }
 
 static char g_lf_create_err[512] = "no error";
-
-static void lfl_error(lf_lane_filter* lf, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(lf ? lf->err : g_lf_create_err, 512, fmt, ap);
-    va_end(ap);
-}
-
-#define LFL_HIP(lf, expr)                                                                          \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            lfl_error((lf), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return LF_ERR_HIP;                                                                     \
-        }                                                                                          \
-    } while (0)
 
 extern "C" void lf_lane_filter_default_config(lf_lane_filter_config* c)
 {
@@ -104,8 +60,6 @@ extern "C" void lf_lane_filter_destroy(lf_lane_filter* lf)
     (void)hipSetDevice(lf->device);
     if (lf->stream) (void)hipStreamSynchronize(lf->stream);
     for (hipEvent_t e : { lf->ev_in, lf->ev_out, lf->ev_staged, lf->ev_done }) if (e) (void)hipEventDestroy(e);
-    for (lf_lane_filter::Ev& e : lf->ev_used) lf->ev_free.push_back(e);
-    for (lf_lane_filter::Ev& e : lf->ev_free) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (lf->stream) (void)hipStreamDestroy(lf->stream);
     delete lf;                   // the buffers free themselves
 }
@@ -113,16 +67,7 @@ extern "C" void lf_lane_filter_destroy(lf_lane_filter* lf)
 // the staging buffers are free once the copies queued by the previous step have run
 static int wait_staged(lf_lane_filter* lf)
 {
-    if (lf->staged_pending) { LFL_HIP(lf, hipEventSynchronize(lf->ev_staged)); lf->staged_pending = false; }
-    return LF_OK;
-}
-
-template <typename T>
-static int grow_dev(lf_lane_filter* lf, DevArray<T>& b, size_t bytes)
-{
-    if (b.bytes >= bytes) return LF_OK;
-    LFL_HIP(lf, hipStreamSynchronize(lf->stream));
-    LFL_HIP(lf, b.alloc(bytes + bytes / 4 + 256));
+    if (lf->staged_pending) { LF_HIP_CHECK(lf, hipEventSynchronize(lf->ev_staged)); lf->staged_pending = false; }
     return LF_OK;
 }
 
@@ -130,7 +75,7 @@ template <typename T>
 static int grow_host(lf_lane_filter* lf, HostArray<T>& b, size_t bytes)
 {
     if (b.bytes >= bytes) return LF_OK;
-    LFL_HIP(lf, b.alloc(bytes + bytes / 4 + 256));
+    LF_HIP_CHECK(lf, b.alloc(bytes + bytes / 4 + 256));
     return LF_OK;
 }
 
@@ -144,34 +89,34 @@ extern "C" int lf_lane_filter_set_tables(lf_lane_filter* lf, const double* sin_p
     if (sin_phi) {
         for (int c = 0; c < g.cells; ++c) {
             if (!is_finite(sin_phi[c]) || sin_phi[c] != sin_phi[c % g.cols]) {
-                lfl_error(lf, "lf_lane_filter_set_tables: sin_phi_grid[%d][%d] = %g is not finite or differs from row 0 (the table is "
+                set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_set_tables: sin_phi_grid[%d][%d] = %g is not finite or differs from row 0 (the table is "
                           "sin of the phi grid, constant along d)", c / g.cols, c % g.cols, sin_phi[c]);
                 return LF_ERR_BAD_ARG;
             }
         }
     }
-    for (int k = 0; w_d && k <= g.r_d; ++k) if (!is_finite(w_d[k])) { lfl_error(lf, "lf_lane_filter_set_tables: w_d[%d] not finite", k); return LF_ERR_BAD_ARG; }
-    for (int k = 0; w_phi && k <= g.r_phi; ++k) if (!is_finite(w_phi[k])) { lfl_error(lf, "lf_lane_filter_set_tables: w_phi[%d] not finite", k); return LF_ERR_BAD_ARG; }
-    LFL_HIP(lf, hipSetDevice(lf->device));
-    LFL_HIP(lf, hipStreamSynchronize(lf->stream));
-    if (sin_phi) LFL_HIP(lf, hipMemcpy(lf->sinp, sin_phi, g.cells * sizeof(double), hipMemcpyHostToDevice));
-    if (w_d) LFL_HIP(lf, hipMemcpy(lf->wd, w_d, (g.r_d + 1) * sizeof(double), hipMemcpyHostToDevice));
-    if (w_phi) LFL_HIP(lf, hipMemcpy(lf->wphi, w_phi, (g.r_phi + 1) * sizeof(double), hipMemcpyHostToDevice));
-    if (initial_belief) LFL_HIP(lf, hipMemcpy(lf->init, initial_belief, g.cells * sizeof(double), hipMemcpyHostToDevice));
+    for (int k = 0; w_d && k <= g.r_d; ++k) if (!is_finite(w_d[k])) { set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_set_tables: w_d[%d] not finite", k); return LF_ERR_BAD_ARG; }
+    for (int k = 0; w_phi && k <= g.r_phi; ++k) if (!is_finite(w_phi[k])) { set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_set_tables: w_phi[%d] not finite", k); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(lf, hipSetDevice(lf->device));
+    LF_HIP_CHECK(lf, hipStreamSynchronize(lf->stream));
+    if (sin_phi) LF_HIP_CHECK(lf, hipMemcpy(lf->sinp, sin_phi, g.cells * sizeof(double), hipMemcpyHostToDevice));
+    if (w_d) LF_HIP_CHECK(lf, hipMemcpy(lf->wd, w_d, (g.r_d + 1) * sizeof(double), hipMemcpyHostToDevice));
+    if (w_phi) LF_HIP_CHECK(lf, hipMemcpy(lf->wphi, w_phi, (g.r_phi + 1) * sizeof(double), hipMemcpyHostToDevice));
+    if (initial_belief) LF_HIP_CHECK(lf, hipMemcpy(lf->init, initial_belief, g.cells * sizeof(double), hipMemcpyHostToDevice));
     return LF_OK;
 }
 
 extern "C" int lf_lane_filter_reset(lf_lane_filter* lf, int stream, const double* belief)
 {
     if (!lf) return LF_ERR_NOT_INITIALISED;
-    if (stream < -1 || stream >= lf->n_streams) { lfl_error(lf, "lf_lane_filter_reset: stream %d out of range (%d streams)", stream, lf->n_streams); return LF_ERR_BAD_ARG; }
-    LFL_HIP(lf, hipSetDevice(lf->device));
-    LFL_HIP(lf, hipStreamSynchronize(lf->stream));
+    if (stream < -1 || stream >= lf->n_streams) { set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_reset: stream %d out of range (%d streams)", stream, lf->n_streams); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(lf, hipSetDevice(lf->device));
+    LF_HIP_CHECK(lf, hipStreamSynchronize(lf->stream));
     const size_t row = lf->g.cells * sizeof(double);
     for (int s = stream < 0 ? 0 : stream; s < (stream < 0 ? lf->n_streams : stream + 1); ++s) {
         double* dst = lf->belief + (size_t)s * lf->g.cells;
-        if (belief) LFL_HIP(lf, hipMemcpy(dst, belief, row, hipMemcpyHostToDevice));
-        else LFL_HIP(lf, hipMemcpy(dst, lf->init, row, hipMemcpyDeviceToDevice));
+        if (belief) LF_HIP_CHECK(lf, hipMemcpy(dst, belief, row, hipMemcpyHostToDevice));
+        else LF_HIP_CHECK(lf, hipMemcpy(dst, lf->init, row, hipMemcpyDeviceToDevice));
     }
     return LF_OK;
 }
@@ -198,37 +143,31 @@ static void default_tables(const lf_lane_filter_config& c, const LfGrid& g, doub
 
 extern "C" int lf_lane_filter_create(int device_id, const lf_lane_filter_config* cfg, int n_streams, int max_frames, lf_lane_filter** out)
 {
-    if (!cfg || !out) { lfl_error(nullptr, "lf_lane_filter_create: null argument"); return LF_ERR_BAD_ARG; }
+    if (!cfg || !out) { snprintf(g_lf_create_err, sizeof(g_lf_create_err), "lf_lane_filter_create: null argument"); return LF_ERR_BAD_ARG; }
     *out = nullptr;
     const lf_lane_filter_config& c = *cfg;
     const double* all = &c.mean_d_0;
-    for (int k = 0; k < 17; ++k) if (!is_finite(all[k])) { lfl_error(nullptr, "lf_lane_filter_create: configuration field %d is not finite", k); return LF_ERR_BAD_ARG; }
+    for (int k = 0; k < 17; ++k) if (!is_finite(all[k])) { snprintf(g_lf_create_err, sizeof(g_lf_create_err), "lf_lane_filter_create: configuration field %d is not finite", k); return LF_ERR_BAD_ARG; }
     if (!(c.delta_d > 0) || !(c.delta_phi > 0) || !(c.d_max > c.d_min) || !(c.phi_max > c.phi_min) || !(c.sigma_d_0 > 0) ||
         !(c.sigma_phi_0 > 0) || !(c.sigma_d_mask > 1e-15) || !(c.sigma_phi_mask > 1e-15) || (int)(4.0 * c.sigma_d_mask + 0.5) > LF_LF_MAX_RADIUS ||
         (int)(4.0 * c.sigma_phi_mask + 0.5) > LF_LF_MAX_RADIUS) {
-        lfl_error(nullptr, "lf_lane_filter_create: bad configuration (delta_d, delta_phi, sigma_d_0, sigma_phi_0 > 0; d_max > d_min; "
+        snprintf(g_lf_create_err, sizeof(g_lf_create_err), "lf_lane_filter_create: bad configuration (delta_d, delta_phi, sigma_d_0, sigma_phi_0 > 0; d_max > d_min; "
                   "phi_max > phi_min; sigma_d_mask, sigma_phi_mask in (1e-15, 63.6])");
         return LF_ERR_BAD_ARG;
     }
     const double fr = ceil((c.d_max - c.d_min) / c.delta_d), fc = ceil((c.phi_max - c.phi_min) / c.delta_phi);
     if (!(fr * fc <= LF_LF_MAX_CELLS)) {
-        lfl_error(nullptr, "lf_lane_filter_create: a %.0f x %.0f grid exceeds %d cells", fr, fc, LF_LF_MAX_CELLS);
+        snprintf(g_lf_create_err, sizeof(g_lf_create_err), "lf_lane_filter_create: a %.0f x %.0f grid exceeds %d cells", fr, fc, LF_LF_MAX_CELLS);
         return LF_ERR_BAD_ARG;
     }
     if (n_streams < 1 || n_streams > 65536 || max_frames < 1 || max_frames > (1 << 20)) {
-        lfl_error(nullptr, "lf_lane_filter_create: n_streams %d in [1, 65536], max_frames %d in [1, 2^20]", n_streams, max_frames);
+        snprintf(g_lf_create_err, sizeof(g_lf_create_err), "lf_lane_filter_create: n_streams %d in [1, 65536], max_frames %d in [1, 2^20]", n_streams, max_frames);
         return LF_ERR_BAD_ARG;
     }
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        lfl_error(nullptr, "lf_lane_filter_create: no HIP device (%s); lanefront has no CPU fallback", e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-        return LF_ERR_HIP;
-    }
-    if (device_id < 0 || device_id >= ndev) { lfl_error(nullptr, "lf_lane_filter_create: device %d out of range (%d devices)", device_id, ndev); return LF_ERR_BAD_ARG; }
+    if (const int rc = check_device(device_id, "lf_lane_filter_create", g_lf_create_err, sizeof(g_lf_create_err))) return rc;
     lf_lane_filter* lf = new (std::nothrow) lf_lane_filter();
     if (!lf) return LF_ERR_HIP;
-    lf->cfg = c; lf->device = device_id; lf->n_streams = n_streams; lf->max_frames = max_frames; lf->err[0] = 0;
+    lf->cfg = c; lf->device = device_id; lf->n_streams = n_streams; lf->max_frames = max_frames;
     LfGrid& g = lf->g;
     memset(&g, 0, sizeof(g));
     g.rows = (int)fr; g.cols = (int)fc; g.cells = g.rows * g.cols;
@@ -239,29 +178,29 @@ extern "C" int lf_lane_filter_create(int device_id, const lf_lane_filter_config*
     const int packed = lane_filter_sum_plan(g.cells, plan);
     g.n_leaves = packed & 0xffff; g.n_prog = packed >> 16;
     auto fail = [&](int rc) { snprintf(g_lf_create_err, sizeof(g_lf_create_err), "%s", lf->err); lf_lane_filter_destroy(lf); return rc; };
-#define CREATE_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { lfl_error(lf, "%s failed: %s", #expr, hipGetErrorString(_e)); return fail(LF_ERR_HIP); } } while (0)
-    CREATE_HIP(hipSetDevice(device_id));
-    CREATE_HIP(hipStreamCreateWithFlags(&lf->stream, hipStreamNonBlocking));
-    for (hipEvent_t* ev : { &lf->ev_in, &lf->ev_out, &lf->ev_staged, &lf->ev_done }) CREATE_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+#define TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error(lf, LF_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); return fail(LF_ERR_HIP); } } while (0)
+    TRY(hipSetDevice(device_id));
+    TRY(hipStreamCreateWithFlags(&lf->stream, hipStreamNonBlocking));
+    for (hipEvent_t* ev : { &lf->ev_in, &lf->ev_out, &lf->ev_staged, &lf->ev_done }) TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
     const size_t cells = g.cells, mf = max_frames;
-    CREATE_HIP(lf->belief.alloc(cells * n_streams * sizeof(double)));
-    CREATE_HIP(lf->init.alloc(cells * sizeof(double)));
-    CREATE_HIP(lf->sinp.alloc(cells * sizeof(double)));
-    CREATE_HIP(lf->wd.alloc((g.r_d + 1) * sizeof(double)));
-    CREATE_HIP(lf->wphi.alloc((g.r_phi + 1) * sizeof(double)));
-    CREATE_HIP(lf->plan.alloc(LF_LF_MAX_PLAN * sizeof(int)));
-    CREATE_HIP(lf->counts.alloc(cells * mf * sizeof(int)));
-    CREATE_HIP(lf->n_votes.alloc(mf * sizeof(int)));
-    CREATE_HIP(lf->fstream.alloc(mf * sizeof(int)));
-    CREATE_HIP(lf->dtvw.alloc(mf * 3 * sizeof(double)));
-    CREATE_HIP(lf->poses.alloc(mf * sizeof(LfPoseDev)));
-    CREATE_HIP(lf->h_dtvw.alloc(mf * 3 * sizeof(double)));
-    CREATE_HIP(lf->h_fstream.alloc(mf * sizeof(int)));
-    CREATE_HIP(lf->h_poses.alloc(mf * sizeof(LfPoseDev)));
-    CREATE_HIP(hipMemcpy(lf->plan, plan, LF_LF_MAX_PLAN * sizeof(int), hipMemcpyHostToDevice));
+    TRY(lf->belief.alloc(cells * n_streams * sizeof(double)));
+    TRY(lf->init.alloc(cells * sizeof(double)));
+    TRY(lf->sinp.alloc(cells * sizeof(double)));
+    TRY(lf->wd.alloc((g.r_d + 1) * sizeof(double)));
+    TRY(lf->wphi.alloc((g.r_phi + 1) * sizeof(double)));
+    TRY(lf->plan.alloc(LF_LF_MAX_PLAN * sizeof(int)));
+    TRY(lf->counts.alloc(cells * mf * sizeof(int)));
+    TRY(lf->n_votes.alloc(mf * sizeof(int)));
+    TRY(lf->fstream.alloc(mf * sizeof(int)));
+    TRY(lf->dtvw.alloc(mf * 3 * sizeof(double)));
+    TRY(lf->poses.alloc(mf * sizeof(LfPoseDev)));
+    TRY(lf->h_dtvw.alloc(mf * 3 * sizeof(double)));
+    TRY(lf->h_fstream.alloc(mf * sizeof(int)));
+    TRY(lf->h_poses.alloc(mf * sizeof(LfPoseDev)));
+    TRY(hipMemcpy(lf->plan, plan, LF_LF_MAX_PLAN * sizeof(int), hipMemcpyHostToDevice));
     {
         double* sinp = new (std::nothrow) double[3 * cells + g.r_d + g.r_phi + 2];
-        if (!sinp) { lfl_error(lf, "out of host memory"); return fail(LF_ERR_HIP); }
+        if (!sinp) { set_error(lf, LF_ERR_HIP, "out of host memory"); return fail(LF_ERR_HIP); }
         double *init = sinp + cells, *wd = init + cells, *wphi = wd + g.r_d + 1;
         default_tables(c, g, sinp, wd, wphi, init);
         const int rc = lf_lane_filter_set_tables(lf, sinp, wd, wphi, init);
@@ -269,7 +208,7 @@ extern "C" int lf_lane_filter_create(int device_id, const lf_lane_filter_config*
         if (rc != LF_OK) return fail(rc);
     }
     if (lf_lane_filter_reset(lf, -1, nullptr) != LF_OK) return fail(LF_ERR_HIP);
-#undef CREATE_HIP
+#undef TRY
     *out = lf;
     return LF_OK;
 }
@@ -277,18 +216,18 @@ extern "C" int lf_lane_filter_create(int device_id, const lf_lane_filter_config*
 extern "C" int lf_lane_filter_synchronize(lf_lane_filter* lf)
 {
     if (!lf) return LF_ERR_NOT_INITIALISED;
-    LFL_HIP(lf, hipSetDevice(lf->device));
-    LFL_HIP(lf, hipStreamSynchronize(lf->stream));
+    LF_HIP_CHECK(lf, hipSetDevice(lf->device));
+    LF_HIP_CHECK(lf, hipStreamSynchronize(lf->stream));
     return LF_OK;
 }
 
 extern "C" int lf_lane_filter_get_belief(lf_lane_filter* lf, int stream, double* belief)
 {
     if (!lf) return LF_ERR_NOT_INITIALISED;
-    if (!belief || stream < 0 || stream >= lf->n_streams) { lfl_error(lf, "lf_lane_filter_get_belief: bad argument (stream %d of %d)", stream, lf->n_streams); return LF_ERR_BAD_ARG; }
-    LFL_HIP(lf, hipSetDevice(lf->device));
-    LFL_HIP(lf, hipStreamSynchronize(lf->stream));
-    LFL_HIP(lf, hipMemcpy(belief, lf->belief + (size_t)stream * lf->g.cells, lf->g.cells * sizeof(double), hipMemcpyDeviceToHost));
+    if (!belief || stream < 0 || stream >= lf->n_streams) { set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_get_belief: bad argument (stream %d of %d)", stream, lf->n_streams); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(lf, hipSetDevice(lf->device));
+    LF_HIP_CHECK(lf, hipStreamSynchronize(lf->stream));
+    LF_HIP_CHECK(lf, hipMemcpy(belief, lf->belief + (size_t)stream * lf->g.cells, lf->g.cells * sizeof(double), hipMemcpyDeviceToHost));
     return LF_OK;
 }
 
@@ -300,8 +239,8 @@ static void to_pose(const LfPoseDev& s, lf_lane_pose& d)
 extern "C" int lf_lane_filter_get_poses(lf_lane_filter* lf, lf_lane_pose* poses, int n_frames)
 {
     if (!lf) return LF_ERR_NOT_INITIALISED;
-    if (!poses || n_frames < 0 || n_frames > lf->last_frames) { lfl_error(lf, "lf_lane_filter_get_poses: %d poses asked, the last step had %d", n_frames, lf->last_frames); return LF_ERR_BAD_ARG; }
-    LFL_HIP(lf, hipEventSynchronize(lf->ev_done));
+    if (!poses || n_frames < 0 || n_frames > lf->last_frames) { set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_get_poses: %d poses asked, the last step had %d", n_frames, lf->last_frames); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(lf, hipEventSynchronize(lf->ev_done));
     for (int f = 0; f < n_frames; ++f) to_pose(lf->h_poses[f], poses[f]);
     return LF_OK;
 }
@@ -313,97 +252,92 @@ extern "C" int lf_lane_filter_step(lf_lane_filter* lf, lf_handle* h, const lf_se
     if (!lf) return LF_ERR_NOT_INITIALISED;
     const LfGrid& g = lf->g;
     if (n_frames < 1 || n_frames > lf->max_frames || phases < 1 || phases > 3) {
-        lfl_error(lf, "lf_lane_filter_step: n_frames %d in [1, %d], phases %d in PREDICT | UPDATE", n_frames, lf->max_frames, phases);
+        set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_step: n_frames %d in [1, %d], phases %d in PREDICT | UPDATE", n_frames, lf->max_frames, phases);
         return LF_ERR_BAD_ARG;
     }
     const bool predict = phases & LF_LANE_FILTER_PREDICT, update = phases & LF_LANE_FILTER_UPDATE;
     if ((predict && !dt_v_w) || (update && (!segs || !segs->frame_offset || !segs->color || !segs->ground))) {
-        lfl_error(lf, "lf_lane_filter_step: PREDICT needs dt_v_w, UPDATE needs segs (frame_offset, color, ground)");
+        set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_step: PREDICT needs dt_v_w, UPDATE needs segs (frame_offset, color, ground)");
         return LF_ERR_BAD_ARG;
     }
     for (int f = 0; frame_stream && f < n_frames; ++f)
-        if (frame_stream[f] < 0 || frame_stream[f] >= lf->n_streams) { lfl_error(lf, "lf_lane_filter_step: frame %d: stream %d of %d", f, frame_stream[f], lf->n_streams); return LF_ERR_BAD_ARG; }
+        if (frame_stream[f] < 0 || frame_stream[f] >= lf->n_streams) { set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_step: frame %d: stream %d of %d", f, frame_stream[f], lf->n_streams); return LF_ERR_BAD_ARG; }
     for (int f = 0; predict && f < n_frames; ++f)
         if (!is_finite(dt_v_w[3 * f + 1] * dt_v_w[3 * f]) || !is_finite(dt_v_w[3 * f + 2] * dt_v_w[3 * f])) {
-            lfl_error(lf, "lf_lane_filter_step: frame %d: v * dt or w * dt is not finite", f);
+            set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_step: frame %d: v * dt or w * dt is not finite", f);
             return LF_ERR_BAD_ARG;
         }
     int n_segs = 0;
     if (update && !segs_on_device) {
         const int32_t* fo = segs->frame_offset;
-        if (fo[0] < 0) { lfl_error(lf, "lf_lane_filter_step: frame_offset[0] < 0"); return LF_ERR_BAD_ARG; }
-        for (int f = 0; f < n_frames; ++f) if (fo[f + 1] < fo[f]) { lfl_error(lf, "lf_lane_filter_step: frame_offset decreases at %d", f); return LF_ERR_BAD_ARG; }
+        if (fo[0] < 0) { set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_step: frame_offset[0] < 0"); return LF_ERR_BAD_ARG; }
+        for (int f = 0; f < n_frames; ++f) if (fo[f + 1] < fo[f]) { set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_step: frame_offset decreases at %d", f); return LF_ERR_BAD_ARG; }
         n_segs = fo[n_frames];
     }
-    if (update && segs_on_device && segs->capacity < 0) { lfl_error(lf, "lf_lane_filter_step: device segments need segs->capacity >= 0"); return LF_ERR_BAD_ARG; }
-    LFL_HIP(lf, hipSetDevice(lf->device));
+    if (update && segs_on_device && segs->capacity < 0) { set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_step: device segments need segs->capacity >= 0"); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(lf, hipSetDevice(lf->device));
     int rc;
     if ((rc = wait_staged(lf)) != LF_OK) return rc;
     const hipStream_t s = lf->stream;
     for (int f = 0; f < n_frames; ++f) lf->h_fstream[f] = frame_stream ? frame_stream[f] : 0;
-    LFL_HIP(lf, hipMemcpyAsync(lf->fstream, lf->h_fstream, n_frames * sizeof(int), hipMemcpyHostToDevice, s));
+    LF_HIP_CHECK(lf, hipMemcpyAsync(lf->fstream, lf->h_fstream, n_frames * sizeof(int), hipMemcpyHostToDevice, s));
     if (predict) {
         memcpy(lf->h_dtvw, dt_v_w, 3 * sizeof(double) * n_frames);
-        LFL_HIP(lf, hipMemcpyAsync(lf->dtvw, lf->h_dtvw, 3 * sizeof(double) * n_frames, hipMemcpyHostToDevice, s));
+        LF_HIP_CHECK(lf, hipMemcpyAsync(lf->dtvw, lf->h_dtvw, 3 * sizeof(double) * n_frames, hipMemcpyHostToDevice, s));
     }
     if (update) {
         const int* fo = segs->frame_offset;
         const uint8_t* col = segs->color;
         const double* gr = segs->ground;
         int cap = segs->capacity;
+        void* hs = nullptr;                   // the handle's stream, when its segments are read where it wrote them
         if (!segs_on_device) {
             const size_t ns = (size_t)(n_segs > 0 ? n_segs : 1);
             if ((rc = grow_host(lf, lf->h_fo, (n_frames + 1) * sizeof(int))) != LF_OK || (rc = grow_host(lf, lf->h_color, ns)) != LF_OK ||
-                (rc = grow_host(lf, lf->h_ground, ns * 4 * sizeof(double))) != LF_OK || (rc = grow_dev(lf, lf->seg_fo, (n_frames + 1) * sizeof(int))) != LF_OK ||
-                (rc = grow_dev(lf, lf->seg_color, ns)) != LF_OK || (rc = grow_dev(lf, lf->seg_ground, ns * 4 * sizeof(double))) != LF_OK)
+                (rc = grow_host(lf, lf->h_ground, ns * 4 * sizeof(double))) != LF_OK || (rc = scratch(lf, lf->seg_fo, (n_frames + 1) * sizeof(int))) != LF_OK ||
+                (rc = scratch(lf, lf->seg_color, ns)) != LF_OK || (rc = scratch(lf, lf->seg_ground, ns * 4 * sizeof(double))) != LF_OK)
                 return rc;
             memcpy(lf->h_fo, segs->frame_offset, (n_frames + 1) * sizeof(int));
             memcpy(lf->h_color, segs->color, (size_t)n_segs);
             memcpy(lf->h_ground, segs->ground, (size_t)n_segs * 4 * sizeof(double));
-            LFL_HIP(lf, hipMemcpyAsync(lf->seg_fo, lf->h_fo, (n_frames + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+            LF_HIP_CHECK(lf, hipMemcpyAsync(lf->seg_fo, lf->h_fo, (n_frames + 1) * sizeof(int), hipMemcpyHostToDevice, s));
             if (n_segs) {
-                LFL_HIP(lf, hipMemcpyAsync(lf->seg_color, lf->h_color, (size_t)n_segs, hipMemcpyHostToDevice, s));
-                LFL_HIP(lf, hipMemcpyAsync(lf->seg_ground, lf->h_ground, (size_t)n_segs * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+                LF_HIP_CHECK(lf, hipMemcpyAsync(lf->seg_color, lf->h_color, (size_t)n_segs, hipMemcpyHostToDevice, s));
+                LF_HIP_CHECK(lf, hipMemcpyAsync(lf->seg_ground, lf->h_ground, (size_t)n_segs * 4 * sizeof(double), hipMemcpyHostToDevice, s));
             }
             fo = lf->seg_fo; col = lf->seg_color; gr = lf->seg_ground; cap = n_segs;
         } else if (h) {
-            void* hs = nullptr;
-            if (lf_get_stream(h, &hs) != LF_OK) { lfl_error(lf, "lf_lane_filter_step: bad handle"); return LF_ERR_BAD_ARG; }
-            LFL_HIP(lf, hipEventRecord(lf->ev_in, static_cast<hipStream_t>(hs)));
-            LFL_HIP(lf, hipStreamWaitEvent(s, lf->ev_in, 0));
+            if (lf_get_stream(h, &hs) != LF_OK) { set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_step: bad handle"); return LF_ERR_BAD_ARG; }
+            if ((rc = stream_after(lf, lf->ev_in, s, static_cast<hipStream_t>(hs))) != LF_OK) return rc;
         }
         {
-            LfTimer tm(lf, 0);
+            StageClock::Scope tm(lf, lf->clock, 0);
             launch_lf_vote(g, n_frames, fo, cap, col, gr, lf->counts, lf->n_votes, s);
         }
-        LFL_HIP(lf, hipGetLastError());
-        if (segs_on_device && h) {            // the handle's next batch overwrites the segment arrays: it waits for the votes
-            void* hs = nullptr;
-            (void)lf_get_stream(h, &hs);
-            LFL_HIP(lf, hipEventRecord(lf->ev_out, s));
-            LFL_HIP(lf, hipStreamWaitEvent(static_cast<hipStream_t>(hs), lf->ev_out, 0));
-        }
+        LF_HIP_CHECK(lf, hipGetLastError());
+        // the handle's next batch overwrites the segment arrays: it waits for the votes
+        if (segs_on_device && h && (rc = stream_after(lf, lf->ev_out, static_cast<hipStream_t>(hs), s)) != LF_OK) return rc;
     }
-    LFL_HIP(lf, hipEventRecord(lf->ev_staged, s));
+    LF_HIP_CHECK(lf, hipEventRecord(lf->ev_staged, s));
     lf->staged_pending = true;
-    if (belief_out && (rc = grow_dev(lf, lf->belief_out, (size_t)n_frames * g.cells * sizeof(double))) != LF_OK) return rc;
-    if (ml_out && (rc = grow_dev(lf, lf->ml_out, (size_t)n_frames * g.cells * sizeof(double))) != LF_OK) return rc;
+    if (belief_out && (rc = scratch(lf, lf->belief_out, (size_t)n_frames * g.cells * sizeof(double))) != LF_OK) return rc;
+    if (ml_out && (rc = scratch(lf, lf->ml_out, (size_t)n_frames * g.cells * sizeof(double))) != LF_OK) return rc;
     int e;
     {
-        LfTimer tm(lf, 1);
+        StageClock::Scope tm(lf, lf->clock, 1);
         e = launch_lf_chain(g, lf->n_streams, n_frames, lf->fstream, lf->dtvw, phases, lf->counts, lf->n_votes, lf->sinp, lf->wd,
                             lf->wphi, lf->plan, lf->belief, lf->poses, belief_out ? (double*)lf->belief_out : nullptr,
                             ml_out ? (double*)lf->ml_out : nullptr, s);
     }
-    if (e) { lfl_error(lf, "k_lf_chain: hipFuncSetAttribute failed (%d)", e); return LF_ERR_HIP; }
-    LFL_HIP(lf, hipGetLastError());
-    LFL_HIP(lf, hipMemcpyAsync(lf->h_poses, lf->poses, n_frames * sizeof(LfPoseDev), hipMemcpyDeviceToHost, s));
-    LFL_HIP(lf, hipEventRecord(lf->ev_done, s));
+    if (e) { set_error(lf, LF_ERR_HIP, "k_lf_chain: hipFuncSetAttribute failed (%d)", e); return LF_ERR_HIP; }
+    LF_HIP_CHECK(lf, hipGetLastError());
+    LF_HIP_CHECK(lf, hipMemcpyAsync(lf->h_poses, lf->poses, n_frames * sizeof(LfPoseDev), hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(lf, hipEventRecord(lf->ev_done, s));
     lf->last_frames = n_frames;
     if (!poses && !belief_out && !ml_out) return LF_OK;
-    if (belief_out) LFL_HIP(lf, hipMemcpyAsync(belief_out, lf->belief_out, (size_t)n_frames * g.cells * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (ml_out) LFL_HIP(lf, hipMemcpyAsync(ml_out, lf->ml_out, (size_t)n_frames * g.cells * sizeof(double), hipMemcpyDeviceToHost, s));
-    LFL_HIP(lf, hipStreamSynchronize(s));
+    if (belief_out) LF_HIP_CHECK(lf, hipMemcpyAsync(belief_out, lf->belief_out, (size_t)n_frames * g.cells * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (ml_out) LF_HIP_CHECK(lf, hipMemcpyAsync(ml_out, lf->ml_out, (size_t)n_frames * g.cells * sizeof(double), hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(lf, hipStreamSynchronize(s));
     if (poses) for (int f = 0; f < n_frames; ++f) to_pose(lf->h_poses[f], poses[f]);
     return LF_OK;
 }
@@ -419,18 +353,7 @@ extern "C" int lf_lane_filter_set_profiling(lf_lane_filter* lf, int enabled)
 extern "C" int lf_lane_filter_get_timing(lf_lane_filter* lf, double* ms_per_stage, int32_t* launches_per_stage, int n)
 {
     if (!lf) return LF_ERR_NOT_INITIALISED;
-    LFL_HIP(lf, hipSetDevice(lf->device));
-    for (lf_lane_filter::Ev& e : lf->ev_used) {
-        (void)hipEventSynchronize(e.b);
-        float t = 0;
-        if (hipEventElapsedTime(&t, e.a, e.b) == hipSuccess) lf->ms[e.st] += t;
-        lf->ev_free.push_back(e);
-    }
-    lf->ev_used.clear();
-    for (int i = 0; i < LF_LANE_FILTER_N_STAGES; ++i) {
-        if (i < n && ms_per_stage) ms_per_stage[i] = lf->ms[i];
-        if (i < n && launches_per_stage) launches_per_stage[i] = lf->launches[i];
-        lf->ms[i] = 0; lf->launches[i] = 0;
-    }
+    LF_HIP_CHECK(lf, hipSetDevice(lf->device));
+    lf->clock.take(ms_per_stage, launches_per_stage, n);
     return LF_OK;
 }

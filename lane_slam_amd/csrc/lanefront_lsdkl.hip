@@ -230,7 +230,7 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
         if ((rc = lsdkl_level(h, lv, Hh, W, opts)) != LF_OK || (rc = lsdkl_run_level(h, lv, level, n_frames)) != LF_OK) return rc;
         L.lines[o] = lv.lines; L.counts[o] = lv.counts; L.H[o] = Hh; L.W[o] = W;
         if (o + 1 < n_octaves) {
-            if ((rc = ensure(h, k->pyr[o + 1], B * (size_t)(W / 2) * (Hh / 2))) != LF_OK) return rc;
+            if ((rc = scratch(h, k->pyr[o + 1], B * (size_t)(W / 2) * (Hh / 2))) != LF_OK) return rc;
             launch_pyrdown(Hh, W, n_frames, level, static_cast<uint8_t*>(k->pyr[o + 1].p), s);
             level = static_cast<const uint8_t*>(k->pyr[o + 1].p);
         }

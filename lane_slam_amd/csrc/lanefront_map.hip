@@ -1,6 +1,5 @@
 // lanefront C ABI, live map + associator part (include/lanefront.h "live map"): host-side sequencing of
 // k_assoc.hip / k_map.hip on the map's own HIP stream.  Semantics and the block format: k_map.hip.
-#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 #include <new>
@@ -9,36 +8,11 @@
 
 static char g_map_create_err[512] = "no error";
 
-static void map_error(lf_map* m, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(m ? m->err : g_map_create_err, 512, fmt, ap);
-    va_end(ap);
-}
-
-#define MAP_HIP(m, expr)                                                                          \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess) {                                                                   \
-            map_error((m), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return LF_ERR_HIP;                                                                    \
-        }                                                                                         \
-    } while (0)
-
-static int grow(lf_map* m, DevBuf& b, size_t bytes)
-{
-    if (b.bytes >= bytes) return LF_OK;
-    if (b.p) { MAP_HIP(m, hipStreamSynchronize(m->stream)); b.reset(); }
-    MAP_HIP(m, b.alloc(bytes + bytes / 4 + 256));
-    return LF_OK;
-}
-
 // make the host mirror current: wait for the copy queued behind the last update (block = false: only look)
 static int refresh_state(lf_map* m, bool block = true)
 {
     if (m->state_pending) {
-        if (block) MAP_HIP(m, hipEventSynchronize(m->ev_state));
+        if (block) LF_HIP_CHECK(m, hipEventSynchronize(m->ev_state));
         else if (hipEventQuery(m->ev_state) != hipSuccess) return LF_OK;          // still in flight: the mirror is stale
         m->state_pending = false;
         m->rows_in_flight = 0;
@@ -47,9 +21,9 @@ static int refresh_state(lf_map* m, bool block = true)
     if (m->h_state[8] != m->errors_reported) {
         const int n_new = m->h_state[8] - m->errors_reported, flags = m->h_state[2];
         m->errors_reported = m->h_state[8];
-        if (flags & 2) { map_error(m, "lf_map_update was given a block with a bad header (magic / count): that update was not applied (%d failing update(s) since the last report)", n_new); return LF_ERR_BAD_ARG; }
-        if (flags & 4) { map_error(m, "a rank's segments did not fit its block (overflow marker in a gathered header): that step's update was applied on no replica (%d failing update(s) since the last report)", n_new); return LF_ERR_CAPACITY; }
-        map_error(m, "the map is full (capacity %d, LF_MAP_FULL_ERROR): segments were dropped (%d failing update(s) since the last report)", m->cfg.capacity, n_new);
+        if (flags & 2) { set_error(m, LF_ERR_BAD_ARG, "lf_map_update was given a block with a bad header (magic / count): that update was not applied (%d failing update(s) since the last report)", n_new); return LF_ERR_BAD_ARG; }
+        if (flags & 4) { set_error(m, LF_ERR_CAPACITY, "a rank's segments did not fit its block (overflow marker in a gathered header): that step's update was applied on no replica (%d failing update(s) since the last report)", n_new); return LF_ERR_CAPACITY; }
+        set_error(m, LF_ERR_CAPACITY, "the map is full (capacity %d, LF_MAP_FULL_ERROR): segments were dropped (%d failing update(s) since the last report)", m->cfg.capacity, n_new);
         return LF_ERR_CAPACITY;
     }
     return LF_OK;
@@ -57,9 +31,9 @@ static int refresh_state(lf_map* m, bool block = true)
 
 static int queue_state_copy(lf_map* m)
 {
-    MAP_HIP(m, hipMemcpyAsync(m->h_state, m->d.state, 16 * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    MAP_HIP(m, hipMemcpyAsync(m->h_state + 16, m->d.totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
-    MAP_HIP(m, hipEventRecord(m->ev_state, m->stream));
+    LF_HIP_CHECK(m, hipMemcpyAsync(m->h_state, m->d.state, 16 * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    LF_HIP_CHECK(m, hipMemcpyAsync(m->h_state + 16, m->d.totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
+    LF_HIP_CHECK(m, hipEventRecord(m->ev_state, m->stream));
     m->state_pending = true;
     return LF_OK;
 }
@@ -69,10 +43,8 @@ int after_handle(lf_map* m, lf_handle* h)
 {
     if (!h) return LF_OK;
     void* hs = nullptr;
-    if (lf_get_stream(h, &hs) != LF_OK) { map_error(m, "bad handle"); return LF_ERR_BAD_ARG; }
-    MAP_HIP(m, hipEventRecord(m->ev_in, static_cast<hipStream_t>(hs)));
-    MAP_HIP(m, hipStreamWaitEvent(m->stream, m->ev_in, 0));
-    return LF_OK;
+    if (lf_get_stream(h, &hs) != LF_OK) { set_error(m, LF_ERR_BAD_ARG, "bad handle"); return LF_ERR_BAD_ARG; }
+    return stream_after(m, m->ev_in, m->stream, static_cast<hipStream_t>(hs));
 }
 
 // the handle's later work (its next batch overwrites the segment arrays) waits for what the map has queued so far
@@ -80,10 +52,8 @@ int release_handle(lf_map* m, lf_handle* h)
 {
     if (!h) return LF_OK;
     void* hs = nullptr;
-    if (lf_get_stream(h, &hs) != LF_OK) { map_error(m, "bad handle"); return LF_ERR_BAD_ARG; }
-    MAP_HIP(m, hipEventRecord(m->ev_out, m->stream));
-    MAP_HIP(m, hipStreamWaitEvent(static_cast<hipStream_t>(hs), m->ev_out, 0));
-    return LF_OK;
+    if (lf_get_stream(h, &hs) != LF_OK) { set_error(m, LF_ERR_BAD_ARG, "bad handle"); return LF_ERR_BAD_ARG; }
+    return stream_after(m, m->ev_out, static_cast<hipStream_t>(hs), m->stream);
 }
 
 static const char* kMapStageNames[LF_MAP_N_STAGES] = { "assoc_pack_queries", "assoc_mfma", "map_pack_block", "map_update" };   // stage 0 is gone (queries are expanded inside the association kernel): always 0 calls
@@ -96,36 +66,16 @@ extern "C" int lf_map_set_profiling(lf_map* m, int enabled)
     m->profiling = enabled != 0;
     if (m->profiling) {                       // fill the event pool now, not inside the first profiled steps
         (void)hipSetDevice(m->device);
-        while (m->ev_free.size() < 512) {
-            lf_map::Ev n; n.st = 0;
-            if (hipEventCreate(&n.a) != hipSuccess) break;
-            if (hipEventCreate(&n.b) != hipSuccess) { (void)hipEventDestroy(n.a); break; }
-            m->ev_free.push_back(n);
-        }
+        m->clock.prefill(512);
     }
     return LF_OK;
-}
-
-// the events recorded so far become milliseconds of their stages
-static void resolve_events(lf_map* m)
-{
-    for (lf_map::Ev& e : m->ev_used) {
-        (void)hipEventSynchronize(e.b);
-        float t = 0;
-        if (hipEventElapsedTime(&t, e.a, e.b) == hipSuccess) m->ms[e.st] += t;
-        m->ev_free.push_back(e);
-    }
-    m->ev_used.clear();
 }
 
 // the alignment kernel's stage (lanefront_map_align.hip), kept apart from lf_map_get_timing's table
 extern "C" int lf_map_align_timing(lf_map* m, double* ms, int32_t* launches)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    resolve_events(m);
-    if (ms) *ms = m->ms[kMapAlignStage];
-    if (launches) *launches = m->launches[kMapAlignStage];
-    m->ms[kMapAlignStage] = 0; m->launches[kMapAlignStage] = 0;
+    m->clock.take(ms, launches, 1, kMapAlignStage, 1);
     return LF_OK;
 }
 
@@ -133,12 +83,7 @@ extern "C" int lf_map_align_timing(lf_map* m, double* ms, int32_t* launches)
 extern "C" int lf_map_get_timing(lf_map* m, double* ms_per_stage, int32_t* launches_per_stage, int n)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    resolve_events(m);
-    for (int i = 0; i < LF_MAP_N_STAGES; ++i) {
-        if (i < n && ms_per_stage) ms_per_stage[i] = m->ms[i];
-        if (i < n && launches_per_stage) launches_per_stage[i] = m->launches[i];
-        m->ms[i] = 0; m->launches[i] = 0;
-    }
+    m->clock.take(ms_per_stage, launches_per_stage, n, 0, LF_MAP_N_STAGES);
     return LF_OK;
 }
 
@@ -149,8 +94,6 @@ extern "C" void lf_map_destroy(lf_map* m)
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
-    for (lf_map::Ev& e : m->ev_used) m->ev_free.push_back(e);
-    for (lf_map::Ev& e : m->ev_free) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (hipEvent_t e : { m->ev_state, m->ev_in, m->ev_out }) if (e) (void)hipEventDestroy(e);
     if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;                    // the buffers free themselves
@@ -158,73 +101,66 @@ extern "C" void lf_map_destroy(lf_map* m)
 
 extern "C" int lf_map_create(int device_id, const lf_map_config* cfg, lf_map** out)
 {
-    if (!cfg || !out) { map_error(nullptr, "lf_map_create: null argument"); return LF_ERR_BAD_ARG; }
+    if (!cfg || !out) { snprintf(g_map_create_err, sizeof(g_map_create_err), "lf_map_create: null argument"); return LF_ERR_BAD_ARG; }
     *out = nullptr;
     if (cfg->capacity < 64 || cfg->capacity > (1 << 21) || cfg->max_distance < 0 || cfg->max_distance > 128 ||
         (cfg->policy != LF_MAP_APPEND && cfg->policy != LF_MAP_MERGE) || (cfg->when_full != LF_MAP_RING && cfg->when_full != LF_MAP_FULL_ERROR) ||
         (cfg->policy == LF_MAP_MERGE && (cfg->merge_distance < 0 || cfg->merge_distance > cfg->max_distance))) {
-        map_error(nullptr, "lf_map_create: bad configuration (capacity %d in [64, 2^21], max_distance %d in [0,128], policy %d, when_full %d, merge_distance %d <= max_distance)",
+        snprintf(g_map_create_err, sizeof(g_map_create_err), "lf_map_create: bad configuration (capacity %d in [64, 2^21], max_distance %d in [0,128], policy %d, when_full %d, merge_distance %d <= max_distance)",
                   cfg->capacity, cfg->max_distance, cfg->policy, cfg->when_full, cfg->merge_distance);
         return LF_ERR_BAD_ARG;
     }
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        map_error(nullptr, "lf_map_create: no HIP device (%s); lanefront has no CPU fallback", e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-        return LF_ERR_HIP;
-    }
-    if (device_id < 0 || device_id >= ndev) { map_error(nullptr, "lf_map_create: device %d out of range (%d devices)", device_id, ndev); return LF_ERR_BAD_ARG; }
+    if (const int rc = check_device(device_id, "lf_map_create", g_map_create_err, sizeof(g_map_create_err))) return rc;
     lf_map* m = new (std::nothrow) lf_map();
     if (!m) return LF_ERR_HIP;
-    m->cfg = *cfg; m->device = device_id; m->err[0] = 0;
+    m->cfg = *cfg; m->device = device_id;
     memset(&m->d, 0, sizeof(m->d));
-    memset(m->ms, 0, sizeof(m->ms)); memset(m->launches, 0, sizeof(m->launches));
     auto fail = [&](int rc) { snprintf(g_map_create_err, sizeof(g_map_create_err), "%s", m->err); lf_map_destroy(m); return rc; };
     const size_t cap = (size_t)cfg->capacity;
     m->cap_pad = assoc_rows_padded_m(cfg->capacity);
-#define CREATE_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { map_error(m, "%s failed: %s", #expr, hipGetErrorString(_e)); return fail(LF_ERR_HIP); } } while (0)
-    CREATE_HIP(hipSetDevice(device_id));
+#define TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error(m, LF_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); return fail(LF_ERR_HIP); } } while (0)
+    TRY(hipSetDevice(device_id));
     {
         // The map's steps are the one serial chain of a pipelined front end (step k's association needs step k - 1's update): its
         // kernels go to a HIGH-PRIORITY stream, so that their workgroups (76 KB of LDS each) are not the last to find room between the
         // region-growing workgroups of the batches in flight (a plain stream where the device has no priority range)
         int least = 0, greatest = 0;
         if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
-            CREATE_HIP(hipStreamCreateWithPriority(&m->stream, hipStreamNonBlocking, greatest));
+            TRY(hipStreamCreateWithPriority(&m->stream, hipStreamNonBlocking, greatest));
         else
-            CREATE_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+            TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
     }
-    CREATE_HIP(hipEventCreateWithFlags(&m->ev_state, hipEventDisableTiming));
-    CREATE_HIP(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
-    CREATE_HIP(hipEventCreateWithFlags(&m->ev_out, hipEventDisableTiming));
-    CREATE_HIP(m->code.alloc(cap * 32));
-    CREATE_HIP(m->color.alloc(cap));
-    CREATE_HIP(m->ground.alloc(cap * 4 * sizeof(double)));
-    CREATE_HIP(m->hits.alloc(cap * sizeof(int)));
-    CREATE_HIP(m->last_seen.alloc(cap * sizeof(int)));
-    CREATE_HIP(m->winner.alloc(cap * sizeof(int)));
-    CREATE_HIP(m->mx.alloc(m->cap_pad * 256));      // 256 B per 128-B row: the tile loop's LDS-DMA read-ahead is not shown to stay within 128 B x cap_pad
-    CREATE_HIP(m->mcx.alloc(m->cap_pad * 32));
-    CREATE_HIP(m->state.alloc(16 * sizeof(int)));
-    CREATE_HIP(m->totals.alloc(2 * sizeof(unsigned long long)));
-    CREATE_HIP(m->h_state.alloc(24 * sizeof(int)));
+    TRY(hipEventCreateWithFlags(&m->ev_state, hipEventDisableTiming));
+    TRY(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
+    TRY(hipEventCreateWithFlags(&m->ev_out, hipEventDisableTiming));
+    TRY(m->code.alloc(cap * 32));
+    TRY(m->color.alloc(cap));
+    TRY(m->ground.alloc(cap * 4 * sizeof(double)));
+    TRY(m->hits.alloc(cap * sizeof(int)));
+    TRY(m->last_seen.alloc(cap * sizeof(int)));
+    TRY(m->winner.alloc(cap * sizeof(int)));
+    TRY(m->mx.alloc(m->cap_pad * 256));      // 256 B per 128-B row: the tile loop's LDS-DMA read-ahead is not shown to stay within 128 B x cap_pad
+    TRY(m->mcx.alloc(m->cap_pad * 32));
+    TRY(m->state.alloc(16 * sizeof(int)));
+    TRY(m->totals.alloc(2 * sizeof(unsigned long long)));
+    TRY(m->h_state.alloc(24 * sizeof(int)));
     m->d.code = m->code; m->d.color = m->color; m->d.ground = m->ground; m->d.hits = m->hits; m->d.last_seen = m->last_seen;
     m->d.winner = m->winner; m->d.mx = m->mx; m->d.mcx = m->mcx; m->d.state = m->state; m->d.totals = m->totals;
     memset(m->h_state, 0, 24 * sizeof(int));
     // rows beyond the map's size must read as "all zero" operands (distance 128): zero everything once
-    CREATE_HIP(hipMemsetAsync(m->d.mx, 0, m->cap_pad * 256, m->stream));
-    CREATE_HIP(hipMemsetAsync(m->d.mcx, 0, m->cap_pad * 32, m->stream));
-    CREATE_HIP(hipMemsetAsync(m->d.code, 0, cap * 32, m->stream));
-    CREATE_HIP(hipMemsetAsync(m->d.color, 0, cap, m->stream));
-    CREATE_HIP(hipMemsetAsync(m->d.ground, 0, cap * 4 * sizeof(double), m->stream));
-    CREATE_HIP(hipMemsetAsync(m->d.hits, 0, cap * sizeof(int), m->stream));
-    CREATE_HIP(hipMemsetAsync(m->d.last_seen, 0, cap * sizeof(int), m->stream));
-    CREATE_HIP(hipMemsetAsync(m->d.state, 0, 16 * sizeof(int), m->stream));
-    CREATE_HIP(hipMemsetAsync(m->d.totals, 0, 2 * sizeof(unsigned long long), m->stream));
+    TRY(hipMemsetAsync(m->d.mx, 0, m->cap_pad * 256, m->stream));
+    TRY(hipMemsetAsync(m->d.mcx, 0, m->cap_pad * 32, m->stream));
+    TRY(hipMemsetAsync(m->d.code, 0, cap * 32, m->stream));
+    TRY(hipMemsetAsync(m->d.color, 0, cap, m->stream));
+    TRY(hipMemsetAsync(m->d.ground, 0, cap * 4 * sizeof(double), m->stream));
+    TRY(hipMemsetAsync(m->d.hits, 0, cap * sizeof(int), m->stream));
+    TRY(hipMemsetAsync(m->d.last_seen, 0, cap * sizeof(int), m->stream));
+    TRY(hipMemsetAsync(m->d.state, 0, 16 * sizeof(int), m->stream));
+    TRY(hipMemsetAsync(m->d.totals, 0, 2 * sizeof(unsigned long long), m->stream));
     launch_fill_i32(m->d.winner, cap, -1, m->stream);
-    CREATE_HIP(hipGetLastError());
-    CREATE_HIP(hipStreamSynchronize(m->stream));
-#undef CREATE_HIP
+    TRY(hipGetLastError());
+    TRY(hipStreamSynchronize(m->stream));
+#undef TRY
     m->d.capacity = cfg->capacity; m->d.policy = cfg->policy; m->d.kept_only = cfg->kept_only;
     m->d.merge_distance = cfg->merge_distance; m->d.when_full = cfg->when_full;
     *out = m;
@@ -234,7 +170,7 @@ extern "C" int lf_map_create(int device_id, const lf_map_config* cfg, lf_map** o
 extern "C" int lf_map_get_stream(lf_map* m, void** hip_stream)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (!hip_stream) { map_error(m, "lf_map_get_stream: null argument"); return LF_ERR_BAD_ARG; }
+    if (!hip_stream) { set_error(m, LF_ERR_BAD_ARG, "lf_map_get_stream: null argument"); return LF_ERR_BAD_ARG; }
     *hip_stream = static_cast<void*>(m->stream);
     return LF_OK;
 }
@@ -242,8 +178,8 @@ extern "C" int lf_map_get_stream(lf_map* m, void** hip_stream)
 extern "C" int lf_map_synchronize(lf_map* m)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    MAP_HIP(m, hipSetDevice(m->device));
-    MAP_HIP(m, hipStreamSynchronize(m->stream));
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
+    LF_HIP_CHECK(m, hipStreamSynchronize(m->stream));
     return LF_OK;
 }
 
@@ -251,13 +187,13 @@ int update_blocks(lf_map* m, const uint8_t* blocks, int n_blocks, int block_rows
 {
     int rc;
     const size_t rows = (size_t)n_blocks * (size_t)(block_rows - 1);
-    if (rows >= (1u << 30)) { map_error(m, "lf_map_update: too many rows"); return LF_ERR_CAPACITY; }
-    if ((rc = grow(m, m->act, (rows + rows / 256 + 2) * sizeof(int))) != LF_OK) return rc;      // actions + per-workgroup append counts (k_map.hip: kMapWg = 256 rows each)
+    if (rows >= (1u << 30)) { set_error(m, LF_ERR_CAPACITY, "lf_map_update: too many rows"); return LF_ERR_CAPACITY; }
+    if ((rc = scratch(m, m->act, (rows + rows / 256 + 2) * sizeof(int))) != LF_OK) return rc;      // actions + per-workgroup append counts (k_map.hip: kMapWg = 256 rows each)
     {
-        MapTimer t(m, 3);
+        StageClock::Scope t(m, m->clock, 3);
         launch_map_update(m->d, blocks, n_blocks, block_rows, force_append, static_cast<int*>(m->act.p), m->stream);
     }
-    MAP_HIP(m, hipGetLastError());
+    LF_HIP_CHECK(m, hipGetLastError());
     m->rows_in_flight += rows_hint >= 0 ? rows_hint : (long long)rows;
     return queue_state_copy(m);
 }
@@ -265,8 +201,8 @@ int update_blocks(lf_map* m, const uint8_t* blocks, int n_blocks, int block_rows
 extern "C" int lf_map_update(lf_map* m, const uint8_t* blocks, int n_blocks, int block_rows)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (!blocks || n_blocks < 1 || block_rows < 1) { map_error(m, "lf_map_update: null blocks, n_blocks < 1 or block_rows < 1"); return LF_ERR_BAD_ARG; }
-    MAP_HIP(m, hipSetDevice(m->device));
+    if (!blocks || n_blocks < 1 || block_rows < 1) { set_error(m, LF_ERR_BAD_ARG, "lf_map_update: null blocks, n_blocks < 1 or block_rows < 1"); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
     if (block_rows == 1) return LF_OK;
     return update_blocks(m, blocks, n_blocks, block_rows, 0);
 }
@@ -274,39 +210,39 @@ extern "C" int lf_map_update(lf_map* m, const uint8_t* blocks, int n_blocks, int
 extern "C" int lf_map_seed(lf_map* m, const uint8_t* code32, const uint8_t* color, const double* ground4, int n, int on_device)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (n < 0 || (n > 0 && !code32)) { map_error(m, "lf_map_seed: bad argument"); return LF_ERR_BAD_ARG; }
+    if (n < 0 || (n > 0 && !code32)) { set_error(m, LF_ERR_BAD_ARG, "lf_map_seed: bad argument"); return LF_ERR_BAD_ARG; }
     if (n == 0) return LF_OK;
-    MAP_HIP(m, hipSetDevice(m->device));
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
     int rc;
     const uint8_t *dcode = code32, *dcolor = color;
     const double* dground = ground4;
     if (!on_device) {
-        if ((rc = grow(m, m->seed_code, (size_t)n * 32)) != LF_OK) return rc;
-        MAP_HIP(m, hipMemcpyAsync(m->seed_code.p, code32, (size_t)n * 32, hipMemcpyHostToDevice, m->stream));
+        if ((rc = scratch(m, m->seed_code, (size_t)n * 32)) != LF_OK) return rc;
+        LF_HIP_CHECK(m, hipMemcpyAsync(m->seed_code.p, code32, (size_t)n * 32, hipMemcpyHostToDevice, m->stream));
         dcode = static_cast<const uint8_t*>(m->seed_code.p);
         if (color) {
-            if ((rc = grow(m, m->seed_color, (size_t)n)) != LF_OK) return rc;
-            MAP_HIP(m, hipMemcpyAsync(m->seed_color.p, color, (size_t)n, hipMemcpyHostToDevice, m->stream));
+            if ((rc = scratch(m, m->seed_color, (size_t)n)) != LF_OK) return rc;
+            LF_HIP_CHECK(m, hipMemcpyAsync(m->seed_color.p, color, (size_t)n, hipMemcpyHostToDevice, m->stream));
             dcolor = static_cast<const uint8_t*>(m->seed_color.p);
         }
         if (ground4) {
-            if ((rc = grow(m, m->seed_ground, (size_t)n * 32)) != LF_OK) return rc;
-            MAP_HIP(m, hipMemcpyAsync(m->seed_ground.p, ground4, (size_t)n * 32, hipMemcpyHostToDevice, m->stream));
+            if ((rc = scratch(m, m->seed_ground, (size_t)n * 32)) != LF_OK) return rc;
+            LF_HIP_CHECK(m, hipMemcpyAsync(m->seed_ground.p, ground4, (size_t)n * 32, hipMemcpyHostToDevice, m->stream));
             dground = static_cast<const double*>(m->seed_ground.p);
         }
     }
-    if ((rc = grow(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) != LF_OK) return rc;
+    if ((rc = scratch(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) != LF_OK) return rc;
     launch_map_seed_block(n, dcode, dcolor, dground, static_cast<uint8_t*>(m->own_block.p), m->stream);
     rc = update_blocks(m, static_cast<const uint8_t*>(m->own_block.p), 1, n + 1, 1, n);
     if (rc != LF_OK) return rc;
-    if (!on_device) MAP_HIP(m, hipStreamSynchronize(m->stream));     // the host arrays may be reused on return
+    if (!on_device) LF_HIP_CHECK(m, hipStreamSynchronize(m->stream));     // the host arrays may be reused on return
     return LF_OK;
 }
 
 extern "C" int lf_map_size(lf_map* m, int* size, int* head, int64_t* total_appended, int64_t* total_refreshed)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    MAP_HIP(m, hipSetDevice(m->device));
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
     const int rc = refresh_state(m);
     if (size) *size = m->h_state[0];
     if (head) *head = m->h_state[1];
@@ -320,10 +256,10 @@ extern "C" int lf_map_associate(lf_map* m, lf_handle* h, const uint8_t* code32, 
                                 int32_t* idx, float* dist, int on_device)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (n < 0 || (n > 0 && (!code32 || !idx || !dist))) { map_error(m, "lf_map_associate: bad argument"); return LF_ERR_BAD_ARG; }
-    if (m->cfg.color_gating && n > 0 && !color) { map_error(m, "lf_map_associate: colour gating is on, colours are required"); return LF_ERR_BAD_ARG; }
+    if (n < 0 || (n > 0 && (!code32 || !idx || !dist))) { set_error(m, LF_ERR_BAD_ARG, "lf_map_associate: bad argument"); return LF_ERR_BAD_ARG; }
+    if (m->cfg.color_gating && n > 0 && !color) { set_error(m, LF_ERR_BAD_ARG, "lf_map_associate: colour gating is on, colours are required"); return LF_ERR_BAD_ARG; }
     if (n == 0) return LF_OK;
-    MAP_HIP(m, hipSetDevice(m->device));
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
     int rc;
     // The map's size after the last update is needed to size the grid.  The host does not wait for that update:
     // when its state copy has not landed yet, an upper bound (last size seen + the rows handed over since) sizes
@@ -338,38 +274,38 @@ extern "C" int lf_map_associate(lf_map* m, lf_handle* h, const uint8_t* code32, 
     const uint8_t *dq = code32, *dc = color;
     int32_t* didx = idx; float* ddist = dist;
     if (!on_device) {
-        if ((rc = grow(m, m->q_in, (size_t)n * 32)) || (rc = grow(m, m->idx_out, (size_t)n * 4)) || (rc = grow(m, m->dist_out, (size_t)n * 4))) return rc;
-        MAP_HIP(m, hipMemcpyAsync(m->q_in.p, code32, (size_t)n * 32, hipMemcpyHostToDevice, s));
+        if ((rc = scratch(m, m->q_in, (size_t)n * 32)) || (rc = scratch(m, m->idx_out, (size_t)n * 4)) || (rc = scratch(m, m->dist_out, (size_t)n * 4))) return rc;
+        LF_HIP_CHECK(m, hipMemcpyAsync(m->q_in.p, code32, (size_t)n * 32, hipMemcpyHostToDevice, s));
         dq = static_cast<const uint8_t*>(m->q_in.p);
         if (color) {
-            if ((rc = grow(m, m->c_in, (size_t)n)) != LF_OK) return rc;
-            MAP_HIP(m, hipMemcpyAsync(m->c_in.p, color, (size_t)n, hipMemcpyHostToDevice, s));
+            if ((rc = scratch(m, m->c_in, (size_t)n)) != LF_OK) return rc;
+            LF_HIP_CHECK(m, hipMemcpyAsync(m->c_in.p, color, (size_t)n, hipMemcpyHostToDevice, s));
             dc = static_cast<const uint8_t*>(m->c_in.p);
         }
         didx = static_cast<int32_t*>(m->idx_out.p); ddist = static_cast<float*>(m->dist_out.p);
     }
-    if (m->tie_rule == LF_TIE_MIHASHER && (rc = grow(m, m->tie_res, (size_t)n * 8)) != LF_OK) return rc;
+    if (m->tie_rule == LF_TIE_MIHASHER && (rc = scratch(m, m->tie_res, (size_t)n * 8)) != LF_OK) return rc;
     if (size == 0) {
         // descriptor matrices cannot be void (binary_descriptor_matcher.cpp:201-205): report "no match"
         launch_assoc_nomatch(n, didx, ddist, s);
     } else {
         {
             // one launch: query operands are expanded in registers, results are written by the last workgroup to arrive
-            MapTimer t(m, 1);
+            StageClock::Scope t(m, m->clock, 1);
             m->ws.tie_res = m->tie_rule == LF_TIE_MIHASHER ? static_cast<unsigned long long*>(m->tie_res.p) : nullptr;
-            MAP_HIP(m, launch_assoc_core(dq, m->cfg.color_gating ? dc : nullptr, n, m->d.mx, m->d.mcx, size, m->d.state, m->cfg.color_gating,
+            LF_HIP_CHECK(m, launch_assoc_core(dq, m->cfg.color_gating ? dc : nullptr, n, m->d.mx, m->d.mcx, size, m->d.state, m->cfg.color_gating,
                                          m->cfg.max_distance, m->ws, didx, ddist, s));
             if (m->tie_rule == LF_TIE_MIHASHER)       // second pass: among the equally near entries, the one the reference's search meets first
-                MAP_HIP(m, launch_assoc_ties(dq, m->cfg.color_gating ? dc : nullptr, n, m->d.mx, m->d.code, m->d.color, size, m->d.state,
+                LF_HIP_CHECK(m, launch_assoc_ties(dq, m->cfg.color_gating ? dc : nullptr, n, m->d.mx, m->d.code, m->d.color, size, m->d.state,
                                              m->cfg.color_gating, m->ws, static_cast<unsigned long long*>(m->tie_res.p), didx, ddist, s));
         }
     }
-    MAP_HIP(m, hipGetLastError());
+    LF_HIP_CHECK(m, hipGetLastError());
     if ((rc = release_handle(m, h)) != LF_OK) return rc;
     if (!on_device) {
-        MAP_HIP(m, hipMemcpyAsync(idx, didx, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        MAP_HIP(m, hipMemcpyAsync(dist, ddist, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        MAP_HIP(m, hipStreamSynchronize(s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(idx, didx, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(dist, ddist, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        LF_HIP_CHECK(m, hipStreamSynchronize(s));
     }
     return LF_OK;
 }
@@ -377,7 +313,7 @@ extern "C" int lf_map_associate(lf_map* m, lf_handle* h, const uint8_t* code32, 
 extern "C" int lf_map_set_tie_rule(lf_map* m, int tie_rule)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (tie_rule != LF_TIE_LOWEST && tie_rule != LF_TIE_MIHASHER) { map_error(m, "lf_map_set_tie_rule: unknown rule"); return LF_ERR_BAD_ARG; }
+    if (tie_rule != LF_TIE_LOWEST && tie_rule != LF_TIE_MIHASHER) { set_error(m, LF_ERR_BAD_ARG, "lf_map_set_tie_rule: unknown rule"); return LF_ERR_BAD_ARG; }
     m->tie_rule = tie_rule;
     return LF_OK;
 }
@@ -387,19 +323,19 @@ extern "C" int lf_map_pack_block(lf_map* m, lf_handle* h, const lf_segments* seg
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
     if (!segs || !block || n < 0 || (n > 0 && !segs->code) || (frame_pose && (n_frames < 1 || !segs->frame_offset))) {
-        map_error(m, "lf_map_pack_block: bad argument (segs->code is required; frame_pose needs segs->frame_offset and n_frames >= 1)");
+        set_error(m, LF_ERR_BAD_ARG, "lf_map_pack_block: bad argument (segs->code is required; frame_pose needs segs->frame_offset and n_frames >= 1)");
         return LF_ERR_BAD_ARG;
     }
-    if (block_rows < 1) { map_error(m, "lf_map_pack_block: block_rows < 1"); return LF_ERR_BAD_ARG; }
-    MAP_HIP(m, hipSetDevice(m->device));
+    if (block_rows < 1) { set_error(m, LF_ERR_BAD_ARG, "lf_map_pack_block: block_rows < 1"); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
     int rc;
     if (n + 1 > block_rows) {
         // never truncated: the block becomes a header with count 0 and the OVERFLOW marker (word 4 = n).  A rank of a
         // multi-GPU step still takes part in the all-gather with it, and lf_map_update skips, on every replica alike, an
         // update that contains such a block -- so the failure is collective instead of a hang.
         launch_map_overflow_block(n, n_frames, step, block, m->stream);
-        MAP_HIP(m, hipGetLastError());
-        map_error(m, "lf_map_pack_block: %d segments do not fit a block of %d rows (header + %d); only a header with the overflow marker was written", n, block_rows, block_rows - 1);
+        LF_HIP_CHECK(m, hipGetLastError());
+        set_error(m, LF_ERR_CAPACITY, "lf_map_pack_block: %d segments do not fit a block of %d rows (header + %d); only a header with the overflow marker was written", n, block_rows, block_rows - 1);
         return LF_ERR_CAPACITY;
     }
     if ((rc = after_handle(m, h)) != LF_OK) return rc;
@@ -413,16 +349,16 @@ extern "C" int lf_map_pack_block(lf_map* m, lf_handle* h, const lf_segments* seg
             m->h_pose[4 * f] = frame_pose[3 * f]; m->h_pose[4 * f + 1] = frame_pose[3 * f + 1];
             m->h_pose[4 * f + 2] = cs; m->h_pose[4 * f + 3] = sn;
         }
-        if ((rc = grow(m, m->pose, (size_t)n_frames * 4 * sizeof(double))) != LF_OK) return rc;
-        MAP_HIP(m, hipMemcpyAsync(m->pose.p, m->h_pose.data(), (size_t)n_frames * 4 * sizeof(double), hipMemcpyHostToDevice, m->stream));
+        if ((rc = scratch(m, m->pose, (size_t)n_frames * 4 * sizeof(double))) != LF_OK) return rc;
+        LF_HIP_CHECK(m, hipMemcpyAsync(m->pose.p, m->h_pose.data(), (size_t)n_frames * 4 * sizeof(double), hipMemcpyHostToDevice, m->stream));
         dpose = static_cast<const double*>(m->pose.p);
     }
     {
-        MapTimer t(m, 2);
+        StageClock::Scope t(m, m->clock, 2);
         launch_map_pack_block(n, n_frames, segs->frame_offset, segs->code, segs->color, segs->keep, segs->ground, idx, dist, dpose, step,
                               block, m->stream);
     }
-    MAP_HIP(m, hipGetLastError());
+    LF_HIP_CHECK(m, hipGetLastError());
     return release_handle(m, h);
 }
 
@@ -430,11 +366,11 @@ extern "C" int lf_map_step(lf_map* m, lf_handle* h, const lf_segments* segs, int
                            int step, int32_t* idx, float* dist)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (!segs || n < 0 || (n > 0 && (!idx || !dist))) { map_error(m, "lf_map_step: bad argument"); return LF_ERR_BAD_ARG; }
+    if (!segs || n < 0 || (n > 0 && (!idx || !dist))) { set_error(m, LF_ERR_BAD_ARG, "lf_map_step: bad argument"); return LF_ERR_BAD_ARG; }
     int rc;
     if (n > 0 && (rc = lf_map_associate(m, h, segs->code, segs->color, n, idx, dist, 1)) != LF_OK) return rc;
-    MAP_HIP(m, hipSetDevice(m->device));
-    if ((rc = grow(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) != LF_OK) return rc;
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
+    if ((rc = scratch(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) != LF_OK) return rc;
     if ((rc = lf_map_pack_block(m, h, segs, n, n_frames, idx, dist, frame_pose, step, static_cast<uint8_t*>(m->own_block.p), n + 1)) != LF_OK) return rc;
     if (n == 0) return LF_OK;
     return update_blocks(m, static_cast<const uint8_t*>(m->own_block.p), 1, n + 1, 0, n);
@@ -448,33 +384,33 @@ extern "C" int lf_map_step_host(lf_map* m, const lf_segments* segs, int n, int n
     if (!m) return LF_ERR_NOT_INITIALISED;
     if (!segs || n < 0 || n_frames < 1 || (n > 0 && (!segs->code || !idx || !dist)) || !segs->frame_offset ||
         (m->cfg.color_gating && n > 0 && !segs->color)) {
-        map_error(m, "lf_map_step_host: bad argument (frame_offset and code are required, color when gating is on)");
+        set_error(m, LF_ERR_BAD_ARG, "lf_map_step_host: bad argument (frame_offset and code are required, color when gating is on)");
         return LF_ERR_BAD_ARG;
     }
-    MAP_HIP(m, hipSetDevice(m->device));
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
     hipStream_t s = m->stream;
     int rc;
     const size_t c = (size_t)(n > 0 ? n : 1);
-    if ((rc = grow(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = grow(m, m->st_code, c * 32)) || (rc = grow(m, m->st_color, c)) ||
-        (rc = grow(m, m->st_keep, c)) || (rc = grow(m, m->st_ground, c * 32)) || (rc = grow(m, m->st_idx, c * 4)) || (rc = grow(m, m->st_dist, c * 4))) return rc;
+    if ((rc = scratch(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = scratch(m, m->st_code, c * 32)) || (rc = scratch(m, m->st_color, c)) ||
+        (rc = scratch(m, m->st_keep, c)) || (rc = scratch(m, m->st_ground, c * 32)) || (rc = scratch(m, m->st_idx, c * 4)) || (rc = scratch(m, m->st_dist, c * 4))) return rc;
     lf_segments d;
     memset(&d, 0, sizeof(d));
-    MAP_HIP(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
+    LF_HIP_CHECK(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
     d.frame_offset = static_cast<int32_t*>(m->st_fo.p);
     if (n > 0) {
-        MAP_HIP(m, hipMemcpyAsync(m->st_code.p, segs->code, (size_t)n * 32, hipMemcpyHostToDevice, s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_code.p, segs->code, (size_t)n * 32, hipMemcpyHostToDevice, s));
         d.code = static_cast<uint8_t*>(m->st_code.p);
-        if (segs->color) { MAP_HIP(m, hipMemcpyAsync(m->st_color.p, segs->color, (size_t)n, hipMemcpyHostToDevice, s)); d.color = static_cast<uint8_t*>(m->st_color.p); }
-        if (segs->keep) { MAP_HIP(m, hipMemcpyAsync(m->st_keep.p, segs->keep, (size_t)n, hipMemcpyHostToDevice, s)); d.keep = static_cast<uint8_t*>(m->st_keep.p); }
-        if (segs->ground) { MAP_HIP(m, hipMemcpyAsync(m->st_ground.p, segs->ground, (size_t)n * 32, hipMemcpyHostToDevice, s)); d.ground = static_cast<double*>(m->st_ground.p); }
+        if (segs->color) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_color.p, segs->color, (size_t)n, hipMemcpyHostToDevice, s)); d.color = static_cast<uint8_t*>(m->st_color.p); }
+        if (segs->keep) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_keep.p, segs->keep, (size_t)n, hipMemcpyHostToDevice, s)); d.keep = static_cast<uint8_t*>(m->st_keep.p); }
+        if (segs->ground) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_ground.p, segs->ground, (size_t)n * 32, hipMemcpyHostToDevice, s)); d.ground = static_cast<double*>(m->st_ground.p); }
     }
     rc = lf_map_step(m, nullptr, &d, n, n_frames, frame_pose, step, static_cast<int32_t*>(m->st_idx.p), static_cast<float*>(m->st_dist.p));
     if (rc != LF_OK) return rc;
     if (n > 0) {
-        MAP_HIP(m, hipMemcpyAsync(idx, m->st_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        MAP_HIP(m, hipMemcpyAsync(dist, m->st_dist.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(idx, m->st_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(dist, m->st_dist.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     }
-    MAP_HIP(m, hipStreamSynchronize(s));
+    LF_HIP_CHECK(m, hipStreamSynchronize(s));
     return LF_OK;
 }
 
@@ -482,17 +418,17 @@ extern "C" int lf_map_fetch(lf_map* m, int first, int n, uint8_t* code32, uint8_
                             int32_t* last_seen)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (first < 0 || n < 0 || (long long)first + n > m->cfg.capacity) { map_error(m, "lf_map_fetch: range [%d, %d) outside the map's capacity %d", first, first + n, m->cfg.capacity); return LF_ERR_BAD_ARG; }
-    MAP_HIP(m, hipSetDevice(m->device));
+    if (first < 0 || n < 0 || (long long)first + n > m->cfg.capacity) { set_error(m, LF_ERR_BAD_ARG, "lf_map_fetch: range [%d, %d) outside the map's capacity %d", first, first + n, m->cfg.capacity); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
     hipStream_t s = m->stream;
     const size_t f = (size_t)first, c = (size_t)n;
     if (n > 0) {
-        if (code32) MAP_HIP(m, hipMemcpyAsync(code32, m->d.code + f * 32, c * 32, hipMemcpyDeviceToHost, s));
-        if (color) MAP_HIP(m, hipMemcpyAsync(color, m->d.color + f, c, hipMemcpyDeviceToHost, s));
-        if (ground4) MAP_HIP(m, hipMemcpyAsync(ground4, m->d.ground + f * 4, c * 32, hipMemcpyDeviceToHost, s));
-        if (hits) MAP_HIP(m, hipMemcpyAsync(hits, m->d.hits + f, c * 4, hipMemcpyDeviceToHost, s));
-        if (last_seen) MAP_HIP(m, hipMemcpyAsync(last_seen, m->d.last_seen + f, c * 4, hipMemcpyDeviceToHost, s));
+        if (code32) LF_HIP_CHECK(m, hipMemcpyAsync(code32, m->d.code + f * 32, c * 32, hipMemcpyDeviceToHost, s));
+        if (color) LF_HIP_CHECK(m, hipMemcpyAsync(color, m->d.color + f, c, hipMemcpyDeviceToHost, s));
+        if (ground4) LF_HIP_CHECK(m, hipMemcpyAsync(ground4, m->d.ground + f * 4, c * 32, hipMemcpyDeviceToHost, s));
+        if (hits) LF_HIP_CHECK(m, hipMemcpyAsync(hits, m->d.hits + f, c * 4, hipMemcpyDeviceToHost, s));
+        if (last_seen) LF_HIP_CHECK(m, hipMemcpyAsync(last_seen, m->d.last_seen + f, c * 4, hipMemcpyDeviceToHost, s));
     }
-    MAP_HIP(m, hipStreamSynchronize(s));
+    LF_HIP_CHECK(m, hipStreamSynchronize(s));
     return LF_OK;
 }

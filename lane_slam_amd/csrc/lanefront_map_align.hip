@@ -22,12 +22,12 @@ const char* bad_config(const lf_align_config* c)
 int check_call(lf_map* m, const char* who, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const double* frame_pose,
                const lf_align_config* cfg, const lf_align_result* results)
 {
-    if (!segs || !frame_pose || !cfg || !results) { map_draw_error(m, "%s: null segs, frame_pose, cfg or results", who); return LF_ERR_BAD_ARG; }
-    if (n < 0 || n_frames < 1 || n_frames > ma::kMaxFrames) { map_draw_error(m, "%s: n < 0 or n_frames outside 1 .. %d", who, ma::kMaxFrames); return LF_ERR_BAD_ARG; }
-    if (n > 0 && (!segs->frame_offset || !segs->ground || !idx)) { map_draw_error(m, "%s: frame_offset, ground and idx are required", who); return LF_ERR_BAD_ARG; }
+    if (!segs || !frame_pose || !cfg || !results) { set_error(m, LF_ERR_BAD_ARG, "%s: null segs, frame_pose, cfg or results", who); return LF_ERR_BAD_ARG; }
+    if (n < 0 || n_frames < 1 || n_frames > ma::kMaxFrames) { set_error(m, LF_ERR_BAD_ARG, "%s: n < 0 or n_frames outside 1 .. %d", who, ma::kMaxFrames); return LF_ERR_BAD_ARG; }
+    if (n > 0 && (!segs->frame_offset || !segs->ground || !idx)) { set_error(m, LF_ERR_BAD_ARG, "%s: frame_offset, ground and idx are required", who); return LF_ERR_BAD_ARG; }
     for (int k = 0; k < 3 * n_frames; ++k)
-        if (!isfinite(frame_pose[k])) { map_draw_error(m, "%s: the pose of frame %d is not finite", who, k / 3); return LF_ERR_BAD_ARG; }
-    if (const char* why = bad_config(cfg)) { map_draw_error(m, "%s: bad configuration (%s)", who, why); return LF_ERR_BAD_ARG; }
+        if (!isfinite(frame_pose[k])) { set_error(m, LF_ERR_BAD_ARG, "%s: the pose of frame %d is not finite", who, k / 3); return LF_ERR_BAD_ARG; }
+    if (const char* why = bad_config(cfg)) { set_error(m, LF_ERR_BAD_ARG, "%s: bad configuration (%s)", who, why); return LF_ERR_BAD_ARG; }
     return LF_OK;
 }
 
@@ -37,10 +37,10 @@ int queue_align(lf_map* m, const lf_segments* d, int n, int n_frames, const int3
                 const lf_align_config* cfg)
 {
     int rc;
-    if ((rc = map_draw_scratch(m, m->al_pose0, (size_t)n_frames * 3 * sizeof(double))) || (rc = map_draw_scratch(m, m->pose, (size_t)n_frames * 4 * sizeof(double))) ||
-        (rc = map_draw_scratch(m, m->al_res, (size_t)n_frames * sizeof(lf_align_result)))) return rc;
+    if ((rc = scratch(m, m->al_pose0, (size_t)n_frames * 3 * sizeof(double))) || (rc = scratch(m, m->pose, (size_t)n_frames * 4 * sizeof(double))) ||
+        (rc = scratch(m, m->al_res, (size_t)n_frames * sizeof(lf_align_result)))) return rc;
     // (every call that queues this copy waits for the stream before it returns: frame_pose has left the host by then)
-    MAP_DRAW_HIP(m, hipMemcpyAsync(m->al_pose0.p, frame_pose, (size_t)n_frames * 3 * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    LF_HIP_CHECK(m, hipMemcpyAsync(m->al_pose0.p, frame_pose, (size_t)n_frames * 3 * sizeof(double), hipMemcpyHostToDevice, m->stream));
     ma::Batch b;
     b.frame_offset = n > 0 ? d->frame_offset : nullptr; b.ground = d->ground; b.color = d->color; b.keep = d->keep;
     b.idx = idx; b.dist = dist; b.n = n; b.n_frames = n_frames;
@@ -48,17 +48,17 @@ int queue_align(lf_map* m, const lf_segments* d, int n, int n_frames, const int3
     b.pose4 = static_cast<double*>(m->pose.p);
     b.res = static_cast<lf_align_result*>(m->al_res.p);
     {
-        MapTimer t(m, kMapAlignStage);
+        StageClock::Scope t(m, m->clock, kMapAlignStage);
         ma::launch_align(*cfg, m->d, b, m->stream);
     }
-    MAP_DRAW_HIP(m, hipGetLastError());
+    LF_HIP_CHECK(m, hipGetLastError());
     return LF_OK;
 }
 
 int fetch_results(lf_map* m, int n_frames, lf_align_result* results)
 {
-    MAP_DRAW_HIP(m, hipMemcpyAsync(results, m->al_res.p, (size_t)n_frames * sizeof(lf_align_result), hipMemcpyDeviceToHost, m->stream));
-    MAP_DRAW_HIP(m, hipStreamSynchronize(m->stream));
+    LF_HIP_CHECK(m, hipMemcpyAsync(results, m->al_res.p, (size_t)n_frames * sizeof(lf_align_result), hipMemcpyDeviceToHost, m->stream));
+    LF_HIP_CHECK(m, hipStreamSynchronize(m->stream));
     return LF_OK;
 }
 
@@ -83,7 +83,7 @@ extern "C" int lf_map_align(lf_map* m, lf_handle* h, const lf_segments* segs, in
     if (!m) return LF_ERR_NOT_INITIALISED;
     int rc;
     if ((rc = check_call(m, "lf_map_align", segs, n, n_frames, idx, frame_pose, cfg, results)) != LF_OK) return rc;
-    MAP_DRAW_HIP(m, hipSetDevice(m->device));
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
     if ((rc = after_handle(m, h)) != LF_OK) return rc;
     hipStream_t s = m->stream;
     lf_segments d;
@@ -94,17 +94,17 @@ extern "C" int lf_map_align(lf_map* m, lf_handle* h, const lf_segments* segs, in
         d.frame_offset = segs->frame_offset; d.ground = segs->ground; d.color = segs->color; d.keep = segs->keep;
     } else if (n > 0) {
         const size_t c = (size_t)n;
-        if ((rc = map_draw_scratch(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = map_draw_scratch(m, m->st_ground, c * 32)) ||
-            (rc = map_draw_scratch(m, m->st_idx, c * 4)) || (segs->color && (rc = map_draw_scratch(m, m->st_color, c))) ||
-            (segs->keep && (rc = map_draw_scratch(m, m->st_keep, c))) || (dist && (rc = map_draw_scratch(m, m->st_dist, c * 4)))) return rc;
-        MAP_DRAW_HIP(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
-        MAP_DRAW_HIP(m, hipMemcpyAsync(m->st_ground.p, segs->ground, c * 32, hipMemcpyHostToDevice, s));
-        MAP_DRAW_HIP(m, hipMemcpyAsync(m->st_idx.p, idx, c * 4, hipMemcpyHostToDevice, s));
+        if ((rc = scratch(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = scratch(m, m->st_ground, c * 32)) ||
+            (rc = scratch(m, m->st_idx, c * 4)) || (segs->color && (rc = scratch(m, m->st_color, c))) ||
+            (segs->keep && (rc = scratch(m, m->st_keep, c))) || (dist && (rc = scratch(m, m->st_dist, c * 4)))) return rc;
+        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_ground.p, segs->ground, c * 32, hipMemcpyHostToDevice, s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_idx.p, idx, c * 4, hipMemcpyHostToDevice, s));
         d.frame_offset = static_cast<int32_t*>(m->st_fo.p); d.ground = static_cast<double*>(m->st_ground.p);
         didx = static_cast<const int32_t*>(m->st_idx.p);
-        if (segs->color) { MAP_DRAW_HIP(m, hipMemcpyAsync(m->st_color.p, segs->color, c, hipMemcpyHostToDevice, s)); d.color = static_cast<uint8_t*>(m->st_color.p); }
-        if (segs->keep) { MAP_DRAW_HIP(m, hipMemcpyAsync(m->st_keep.p, segs->keep, c, hipMemcpyHostToDevice, s)); d.keep = static_cast<uint8_t*>(m->st_keep.p); }
-        if (dist) { MAP_DRAW_HIP(m, hipMemcpyAsync(m->st_dist.p, dist, c * 4, hipMemcpyHostToDevice, s)); ddist = static_cast<const float*>(m->st_dist.p); }
+        if (segs->color) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_color.p, segs->color, c, hipMemcpyHostToDevice, s)); d.color = static_cast<uint8_t*>(m->st_color.p); }
+        if (segs->keep) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_keep.p, segs->keep, c, hipMemcpyHostToDevice, s)); d.keep = static_cast<uint8_t*>(m->st_keep.p); }
+        if (dist) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_dist.p, dist, c * 4, hipMemcpyHostToDevice, s)); ddist = static_cast<const float*>(m->st_dist.p); }
     }
     if ((rc = queue_align(m, &d, n, n_frames, didx, ddist, frame_pose, cfg)) != LF_OK) return rc;
     if ((rc = release_handle(m, h)) != LF_OK) return rc;
@@ -117,18 +117,18 @@ extern "C" int lf_map_step_aligned(lf_map* m, lf_handle* h, const lf_segments* s
     if (!m) return LF_ERR_NOT_INITIALISED;
     int rc;
     if ((rc = check_call(m, "lf_map_step_aligned", segs, n, n_frames, idx, frame_pose, cfg, results)) != LF_OK) return rc;
-    if (n > 0 && (!dist || !segs->code)) { map_draw_error(m, "lf_map_step_aligned: code and dist are required"); return LF_ERR_BAD_ARG; }
+    if (n > 0 && (!dist || !segs->code)) { set_error(m, LF_ERR_BAD_ARG, "lf_map_step_aligned: code and dist are required"); return LF_ERR_BAD_ARG; }
     if (n > 0 && (rc = lf_map_associate(m, h, segs->code, segs->color, n, idx, dist, 1)) != LF_OK) return rc;
-    MAP_DRAW_HIP(m, hipSetDevice(m->device));
-    if ((rc = map_draw_scratch(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) != LF_OK) return rc;
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
+    if ((rc = scratch(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) != LF_OK) return rc;
     if ((rc = after_handle(m, h)) != LF_OK) return rc;
     if ((rc = queue_align(m, segs, n, n_frames, idx, dist, frame_pose, cfg)) != LF_OK) return rc;
     {
-        MapTimer t(m, 2);
+        StageClock::Scope t(m, m->clock, 2);
         launch_map_pack_block(n, n_frames, n > 0 ? segs->frame_offset : nullptr, segs->code, segs->color, segs->keep, segs->ground, idx, dist,
                               static_cast<const double*>(m->pose.p), step, static_cast<uint8_t*>(m->own_block.p), m->stream);
     }
-    MAP_DRAW_HIP(m, hipGetLastError());
+    LF_HIP_CHECK(m, hipGetLastError());
     if ((rc = release_handle(m, h)) != LF_OK) return rc;
     if (n > 0 && (rc = update_blocks(m, static_cast<const uint8_t*>(m->own_block.p), 1, n + 1, 0, n)) != LF_OK) return rc;
     return fetch_results(m, n_frames, results);
@@ -141,33 +141,33 @@ extern "C" int lf_map_step_aligned_host(lf_map* m, const lf_segments* segs, int 
     int rc;
     if ((rc = check_call(m, "lf_map_step_aligned_host", segs, n, n_frames, idx, frame_pose, cfg, results)) != LF_OK) return rc;
     if (!segs->frame_offset || (n > 0 && (!segs->code || !dist)) || (m->cfg.color_gating && n > 0 && !segs->color)) {
-        map_draw_error(m, "lf_map_step_aligned_host: bad argument (frame_offset, code and dist are required, color when gating is on)");
+        set_error(m, LF_ERR_BAD_ARG, "lf_map_step_aligned_host: bad argument (frame_offset, code and dist are required, color when gating is on)");
         return LF_ERR_BAD_ARG;
     }
-    MAP_DRAW_HIP(m, hipSetDevice(m->device));
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
     hipStream_t s = m->stream;
     const size_t c = (size_t)(n > 0 ? n : 1);
-    if ((rc = map_draw_scratch(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = map_draw_scratch(m, m->st_code, c * 32)) || (rc = map_draw_scratch(m, m->st_color, c)) ||
-        (rc = map_draw_scratch(m, m->st_keep, c)) || (rc = map_draw_scratch(m, m->st_ground, c * 32)) || (rc = map_draw_scratch(m, m->st_idx, c * 4)) ||
-        (rc = map_draw_scratch(m, m->st_dist, c * 4))) return rc;
+    if ((rc = scratch(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = scratch(m, m->st_code, c * 32)) || (rc = scratch(m, m->st_color, c)) ||
+        (rc = scratch(m, m->st_keep, c)) || (rc = scratch(m, m->st_ground, c * 32)) || (rc = scratch(m, m->st_idx, c * 4)) ||
+        (rc = scratch(m, m->st_dist, c * 4))) return rc;
     lf_segments d;
     memset(&d, 0, sizeof(d));
-    MAP_DRAW_HIP(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
+    LF_HIP_CHECK(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
     d.frame_offset = static_cast<int32_t*>(m->st_fo.p);
     if (n > 0) {
-        MAP_DRAW_HIP(m, hipMemcpyAsync(m->st_code.p, segs->code, (size_t)n * 32, hipMemcpyHostToDevice, s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_code.p, segs->code, (size_t)n * 32, hipMemcpyHostToDevice, s));
         d.code = static_cast<uint8_t*>(m->st_code.p);
-        MAP_DRAW_HIP(m, hipMemcpyAsync(m->st_ground.p, segs->ground, (size_t)n * 32, hipMemcpyHostToDevice, s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_ground.p, segs->ground, (size_t)n * 32, hipMemcpyHostToDevice, s));
         d.ground = static_cast<double*>(m->st_ground.p);
-        if (segs->color) { MAP_DRAW_HIP(m, hipMemcpyAsync(m->st_color.p, segs->color, (size_t)n, hipMemcpyHostToDevice, s)); d.color = static_cast<uint8_t*>(m->st_color.p); }
-        if (segs->keep) { MAP_DRAW_HIP(m, hipMemcpyAsync(m->st_keep.p, segs->keep, (size_t)n, hipMemcpyHostToDevice, s)); d.keep = static_cast<uint8_t*>(m->st_keep.p); }
+        if (segs->color) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_color.p, segs->color, (size_t)n, hipMemcpyHostToDevice, s)); d.color = static_cast<uint8_t*>(m->st_color.p); }
+        if (segs->keep) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_keep.p, segs->keep, (size_t)n, hipMemcpyHostToDevice, s)); d.keep = static_cast<uint8_t*>(m->st_keep.p); }
     }
     rc = lf_map_step_aligned(m, nullptr, &d, n, n_frames, frame_pose, cfg, step, static_cast<int32_t*>(m->st_idx.p), static_cast<float*>(m->st_dist.p), results);
     if (rc != LF_OK) return rc;
     if (n > 0) {
-        MAP_DRAW_HIP(m, hipMemcpyAsync(idx, m->st_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        MAP_DRAW_HIP(m, hipMemcpyAsync(dist, m->st_dist.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(idx, m->st_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(dist, m->st_dist.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     }
-    MAP_DRAW_HIP(m, hipStreamSynchronize(s));
+    LF_HIP_CHECK(m, hipStreamSynchronize(s));
     return LF_OK;
 }

@@ -83,13 +83,13 @@ extern "C" int lf_map_render_camera(lf_map* m, const lf_camera_view* v, const do
                                     uint8_t* out, int on_device, int32_t* counts)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (!v || !out) { map_draw_error(m, "lf_map_render_camera: null view or out"); return LF_ERR_BAD_ARG; }
-    if (n_frames < 1 || n_frames > mc::kMaxFrames) { map_draw_error(m, "lf_map_render_camera: n_frames is 1 .. %d", mc::kMaxFrames); return LF_ERR_BAD_ARG; }
-    if (const char* why = bad_view(v)) { map_draw_error(m, "lf_map_render_camera: bad view (%s)", why); return LF_ERR_BAD_ARG; }
+    if (!v || !out) { set_error(m, LF_ERR_BAD_ARG, "lf_map_render_camera: null view or out"); return LF_ERR_BAD_ARG; }
+    if (n_frames < 1 || n_frames > mc::kMaxFrames) { set_error(m, LF_ERR_BAD_ARG, "lf_map_render_camera: n_frames is 1 .. %d", mc::kMaxFrames); return LF_ERR_BAD_ARG; }
+    if (const char* why = bad_view(v)) { set_error(m, LF_ERR_BAD_ARG, "lf_map_render_camera: bad view (%s)", why); return LF_ERR_BAD_ARG; }
     if (frame_pose)
         for (int k = 0; k < 3 * n_frames; ++k)
-            if (!isfinite(frame_pose[k])) { map_draw_error(m, "lf_map_render_camera: the pose of frame %d is not finite", k / 3); return LF_ERR_BAD_ARG; }
-    MAP_DRAW_HIP(m, hipSetDevice(m->device));
+            if (!isfinite(frame_pose[k])) { set_error(m, LF_ERR_BAD_ARG, "lf_map_render_camera: the pose of frame %d is not finite", k / 3); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
     if (!m->camera) m->camera.reset(new MapCameraState());
     MapCameraState* e = m->camera.get();
     const mc::View dv = device_view(v);
@@ -98,15 +98,14 @@ extern "C" int lf_map_render_camera(lf_map* m, const lf_camera_view* v, const do
     const int n_counters = mc::kCounterBase + 3 * n_frames;
     hipStream_t s = m->stream;
     int rc;
-    if ((rc = map_draw_scratch(m, e->tiles, n_tiles * 3 * sizeof(unsigned))) || (rc = map_draw_scratch(m, e->counters, n_counters * sizeof(int))) ||
-        (rc = map_draw_scratch(m, e->pose, (size_t)n_frames * 4 * sizeof(double))) || (!on_device && (rc = map_draw_scratch(m, e->frames, image_bytes)))) return rc;
+    if ((rc = scratch(m, e->tiles, n_tiles * 3 * sizeof(unsigned))) || (rc = scratch(m, e->counters, n_counters * sizeof(int))) ||
+        (rc = scratch(m, e->pose, (size_t)n_frames * 4 * sizeof(double))) || (!on_device && (rc = scratch(m, e->frames, image_bytes)))) return rc;
     if (e->h_counters.bytes < n_counters * sizeof(int)) {
-        MAP_DRAW_HIP(m, hipStreamSynchronize(s));
-        MAP_DRAW_HIP(m, e->h_counters.alloc((size_t)(mc::kCounterBase + 3 * mc::kMaxFrames) * sizeof(int)));
+        LF_HIP_CHECK(m, hipStreamSynchronize(s));
+        LF_HIP_CHECK(m, e->h_counters.alloc((size_t)(mc::kCounterBase + 3 * mc::kMaxFrames) * sizeof(int)));
     }
     e->rendered = false;
-    e->timed = m->profiling;
-    if (e->timed) for (hipEvent_t& ev : e->ev) if (!ev) MAP_DRAW_HIP(m, hipEventCreate(&ev));
+    if ((rc = e->clock.begin(m)) != LF_OK) return rc;
     // cos / sin with the library's deterministic routines (detmath.h), as lf_map_pack_block
     e->h_pose.resize((size_t)n_frames * 4);
     for (int f = 0; f < n_frames; ++f) {
@@ -121,49 +120,49 @@ extern "C" int lf_map_render_camera(lf_map* m, const lf_camera_view* v, const do
     int* counters = static_cast<int*>(e->counters.p);
     const double* pose4 = static_cast<const double*>(e->pose.p);
     // (an earlier call's copy from h_pose has left the host by the time that call returned: every call waits for the stream below)
-    MAP_DRAW_HIP(m, hipMemcpyAsync(e->pose.p, e->h_pose.data(), (size_t)n_frames * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    MAP_DRAW_HIP(m, hipMemsetAsync(tile_count, 0, n_tiles * sizeof(unsigned), s));
-    MAP_DRAW_HIP(m, hipMemsetAsync(counters, 0, n_counters * sizeof(int), s));
+    LF_HIP_CHECK(m, hipMemcpyAsync(e->pose.p, e->h_pose.data(), (size_t)n_frames * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    LF_HIP_CHECK(m, hipMemsetAsync(tile_count, 0, n_tiles * sizeof(unsigned), s));
+    LF_HIP_CHECK(m, hipMemsetAsync(counters, 0, n_counters * sizeof(int), s));
     {
-        MapStageTimer<MapCameraState> t(m, e, 0);
+        CallClock::Scope t(e->clock, 0);
         mc::launch_project(dv, m->d, pose4, n_frames, tile_count, counters, nullptr, s);
     }
     {
-        MapStageTimer<MapCameraState> t(m, e, 1);
+        CallClock::Scope t(e->clock, 1);
         mr::launch_scan((int)n_tiles, tile_count, tile_start, cursor, counters, s);
     }
-    MAP_DRAW_HIP(m, hipGetLastError());
+    LF_HIP_CHECK(m, hipGetLastError());
     // the one wait of a call: how many (line, tile) pairs the lists must hold, and the counts
-    MAP_DRAW_HIP(m, hipMemcpyAsync(e->h_counters.p, counters, n_counters * sizeof(int), hipMemcpyDeviceToHost, s));
-    MAP_DRAW_HIP(m, hipStreamSynchronize(s));
+    LF_HIP_CHECK(m, hipMemcpyAsync(e->h_counters.p, counters, n_counters * sizeof(int), hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(m, hipStreamSynchronize(s));
     const int* hc = e->h_counters.p;
     const unsigned long long total = (unsigned long long)(unsigned)hc[2] | (unsigned long long)(unsigned)hc[3] << 32;
     if (total > (1ull << 30)) {
-        map_draw_error(m, "lf_map_render_camera: %llu (line, tile) pairs, more than 2^30: nothing was drawn", total);
+        set_error(m, LF_ERR_CAPACITY, "lf_map_render_camera: %llu (line, tile) pairs, more than 2^30: nothing was drawn", total);
         return LF_ERR_CAPACITY;
     }
-    if ((rc = map_draw_scratch(m, e->rec, (size_t)(total ? total : 1) * sizeof(mc::Record))) != LF_OK) return rc;
+    if ((rc = scratch(m, e->rec, (size_t)(total ? total : 1) * sizeof(mc::Record))) != LF_OK) return rc;
     mc::Record* rec = static_cast<mc::Record*>(e->rec.p);
     const uint8_t* d_src = src;
     uint8_t* d_out = out;
     if (!on_device) {
         d_out = static_cast<uint8_t*>(e->frames.p);
         d_src = src ? d_out : nullptr;
-        if (src) MAP_DRAW_HIP(m, hipMemcpyAsync(d_out, src, image_bytes, hipMemcpyHostToDevice, s));
+        if (src) LF_HIP_CHECK(m, hipMemcpyAsync(d_out, src, image_bytes, hipMemcpyHostToDevice, s));
     }
     {
-        MapStageTimer<MapCameraState> t(m, e, 2);
+        CallClock::Scope t(e->clock, 2);
         mc::launch_project(dv, m->d, pose4, n_frames, cursor, counters, rec, s);
     }
     {
-        MapStageTimer<MapCameraState> t(m, e, 3);
+        CallClock::Scope t(e->clock, 3);
         mc::launch_paint(dv, m->d, n_frames, tile_start, tile_count, rec, d_src, d_out, s);
     }
-    MAP_DRAW_HIP(m, hipGetLastError());
+    LF_HIP_CHECK(m, hipGetLastError());
     e->rendered = true;
     if (!on_device) {
-        MAP_DRAW_HIP(m, hipMemcpyAsync(out, d_out, image_bytes, hipMemcpyDeviceToHost, s));
-        MAP_DRAW_HIP(m, hipStreamSynchronize(s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(out, d_out, image_bytes, hipMemcpyDeviceToHost, s));
+        LF_HIP_CHECK(m, hipStreamSynchronize(s));
     }
     if (counts) memcpy(counts, hc + mc::kCounterBase, (size_t)n_frames * 3 * sizeof(int32_t));
     return LF_OK;
@@ -172,10 +171,10 @@ extern "C" int lf_map_render_camera(lf_map* m, const lf_camera_view* v, const do
 extern "C" int lf_map_render_camera_timing(lf_map* m, double* ms_per_stage, int n)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (!ms_per_stage || n < mc::kStages) { map_draw_error(m, "lf_map_render_camera_timing: room for %d stages", mc::kStages); return LF_ERR_BAD_ARG; }
-    if (!m->camera || !m->camera->rendered || !m->camera->timed) {
-        map_draw_error(m, "lf_map_render_camera_timing: no lf_map_render_camera ran with profiling on (lf_map_set_profiling)");
+    if (!ms_per_stage || n < mc::kStages) { set_error(m, LF_ERR_BAD_ARG, "lf_map_render_camera_timing: room for %d stages", mc::kStages); return LF_ERR_BAD_ARG; }
+    if (!m->camera || !m->camera->rendered || !m->camera->clock.timed) {
+        set_error(m, LF_ERR_BAD_ARG, "lf_map_render_camera_timing: no lf_map_render_camera ran with profiling on (lf_map_set_profiling)");
         return LF_ERR_BAD_ARG;
     }
-    return map_draw_timing(m, *m->camera, mc::kStages, ms_per_stage);
+    return m->camera->clock.read(m, mc::kStages, ms_per_stage);
 }

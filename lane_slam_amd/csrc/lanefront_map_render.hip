@@ -13,8 +13,8 @@ int state_of(lf_map* m, MapRenderState** out)
 {
     if (!m->render) {
         m->render.reset(new MapRenderState());
-        MAP_DRAW_HIP(m, m->render->h_counters.alloc(kHostInts * sizeof(int)));
-        MAP_DRAW_HIP(m, hipEventCreateWithFlags(&m->render->done, hipEventDisableTiming));
+        LF_HIP_CHECK(m, m->render->h_counters.alloc(kHostInts * sizeof(int)));
+        LF_HIP_CHECK(m, hipEventCreateWithFlags(&m->render->done, hipEventDisableTiming));
     }
     *out = m->render.get();
     return LF_OK;
@@ -63,23 +63,23 @@ extern "C" void lf_map_default_view(lf_map_view* v)
 extern "C" int lf_map_bounds(lf_map* m, const lf_map_view* v, double* bounds4, int* n_entries)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (!bounds4 || !n_entries) { map_draw_error(m, "lf_map_bounds: null argument"); return LF_ERR_BAD_ARG; }
-    MAP_DRAW_HIP(m, hipSetDevice(m->device));
+    if (!bounds4 || !n_entries) { set_error(m, LF_ERR_BAD_ARG, "lf_map_bounds: null argument"); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
     MapRenderState* e;
     int rc;
-    if ((rc = state_of(m, &e)) != LF_OK || (rc = map_draw_scratch(m, e->bounds, 5 * sizeof(unsigned long long))) != LF_OK) return rc;
+    if ((rc = state_of(m, &e)) != LF_OK || (rc = scratch(m, e->bounds, 5 * sizeof(unsigned long long))) != LF_OK) return rc;
     unsigned long long* h = reinterpret_cast<unsigned long long*>(e->h_counters.p + mr::kCounterInts);      // (8-byte aligned: kCounterInts is even)
     const double inf = HUGE_VAL;
     h[0] = h[1] = mr::encode_bound(inf); h[2] = h[3] = mr::encode_bound(-inf); h[4] = 0;
     hipStream_t s = m->stream;
-    MAP_DRAW_HIP(m, hipMemcpyAsync(e->bounds.p, h, 5 * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    LF_HIP_CHECK(m, hipMemcpyAsync(e->bounds.p, h, 5 * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
     mr::View dv;
     memset(&dv, 0, sizeof(dv));
     if (v) { dv.min_hits = v->min_hits; dv.min_last_seen = v->min_last_seen; dv.color_mask = v->color_mask; }
     mr::launch_bounds(dv, v != nullptr, m->d, static_cast<unsigned long long*>(e->bounds.p), s);
-    MAP_DRAW_HIP(m, hipGetLastError());
-    MAP_DRAW_HIP(m, hipMemcpyAsync(h, e->bounds.p, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    MAP_DRAW_HIP(m, hipStreamSynchronize(s));
+    LF_HIP_CHECK(m, hipGetLastError());
+    LF_HIP_CHECK(m, hipMemcpyAsync(h, e->bounds.p, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(m, hipStreamSynchronize(s));
     *n_entries = (int)h[4];
     if (h[4]) for (int k = 0; k < 4; ++k) bounds4[k] = mr::decode_bound(h[k]);
     return LF_OK;
@@ -89,10 +89,10 @@ extern "C" int lf_map_render(lf_map* m, const lf_map_view* v, const double* traj
                              int* n_drawn, int* n_skipped)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (!v || !out || n_points < 0 || (n_points > 0 && !trajectory)) { map_draw_error(m, "lf_map_render: null view or out, n_points < 0, or points without an array"); return LF_ERR_BAD_ARG; }
-    if (const char* why = bad_view(v)) { map_draw_error(m, "lf_map_render: bad view (%s)", why); return LF_ERR_BAD_ARG; }
-    if (n_points > (1 << 30)) { map_draw_error(m, "lf_map_render: more than 2^30 trajectory points"); return LF_ERR_CAPACITY; }
-    MAP_DRAW_HIP(m, hipSetDevice(m->device));
+    if (!v || !out || n_points < 0 || (n_points > 0 && !trajectory)) { set_error(m, LF_ERR_BAD_ARG, "lf_map_render: null view or out, n_points < 0, or points without an array"); return LF_ERR_BAD_ARG; }
+    if (const char* why = bad_view(v)) { set_error(m, LF_ERR_BAD_ARG, "lf_map_render: bad view (%s)", why); return LF_ERR_BAD_ARG; }
+    if (n_points > (1 << 30)) { set_error(m, LF_ERR_CAPACITY, "lf_map_render: more than 2^30 trajectory points"); return LF_ERR_CAPACITY; }
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
     MapRenderState* e;
     int rc;
     if ((rc = state_of(m, &e)) != LF_OK) return rc;
@@ -101,58 +101,57 @@ extern "C" int lf_map_render(lf_map* m, const lf_map_view* v, const double* traj
     const int n_tiles = dv.ntx * dv.nty;
     const size_t image_bytes = (size_t)v->rows * v->cols * 3;
     hipStream_t s = m->stream;
-    if ((rc = map_draw_scratch(m, e->px, (size_t)n_lines * sizeof(int4))) || (rc = map_draw_scratch(m, e->tiles, (size_t)n_tiles * 3 * sizeof(unsigned))) ||
-        (rc = map_draw_scratch(m, e->counters, mr::kCounterInts * sizeof(int))) || (n_traj && (rc = map_draw_scratch(m, e->traj, (size_t)n_points * 2 * sizeof(double)))) ||
-        (!out_on_device && (rc = map_draw_scratch(m, e->out, image_bytes)))) return rc;
+    if ((rc = scratch(m, e->px, (size_t)n_lines * sizeof(int4))) || (rc = scratch(m, e->tiles, (size_t)n_tiles * 3 * sizeof(unsigned))) ||
+        (rc = scratch(m, e->counters, mr::kCounterInts * sizeof(int))) || (n_traj && (rc = scratch(m, e->traj, (size_t)n_points * 2 * sizeof(double)))) ||
+        (!out_on_device && (rc = scratch(m, e->out, image_bytes)))) return rc;
     e->rendered = false;
-    e->timed = m->profiling;
-    if (e->timed) for (hipEvent_t& ev : e->ev) if (!ev) MAP_DRAW_HIP(m, hipEventCreate(&ev));
+    if ((rc = e->clock.begin(m)) != LF_OK) return rc;
     unsigned* tile_count = static_cast<unsigned*>(e->tiles.p);
     unsigned* tile_start = tile_count + n_tiles;
     unsigned* cursor = tile_start + n_tiles;
     int* counters = static_cast<int*>(e->counters.p);
     int4* px = static_cast<int4*>(e->px.p);
     // (the caller's points are on the device before this call returns: the wait for the total below comes after their copy)
-    if (n_traj) MAP_DRAW_HIP(m, hipMemcpyAsync(e->traj.p, trajectory, (size_t)n_points * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-    MAP_DRAW_HIP(m, hipMemsetAsync(tile_count, 0, (size_t)n_tiles * sizeof(unsigned), s));
-    MAP_DRAW_HIP(m, hipMemsetAsync(counters, 0, mr::kCounterInts * sizeof(int), s));
+    if (n_traj) LF_HIP_CHECK(m, hipMemcpyAsync(e->traj.p, trajectory, (size_t)n_points * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+    LF_HIP_CHECK(m, hipMemsetAsync(tile_count, 0, (size_t)n_tiles * sizeof(unsigned), s));
+    LF_HIP_CHECK(m, hipMemsetAsync(counters, 0, mr::kCounterInts * sizeof(int), s));
     {
-        MapStageTimer<MapRenderState> t(m, e, 0);
+        CallClock::Scope t(e->clock, 0);
         mr::launch_project(dv, m->d, static_cast<const double*>(e->traj.p), n_traj, px, tile_count, counters, s);
     }
     {
-        MapStageTimer<MapRenderState> t(m, e, 1);
+        CallClock::Scope t(e->clock, 1);
         mr::launch_scan(n_tiles, tile_count, tile_start, cursor, counters, s);
     }
-    MAP_DRAW_HIP(m, hipGetLastError());
+    LF_HIP_CHECK(m, hipGetLastError());
     // the one wait of a render: how many (line, tile) pairs the lists must hold
-    MAP_DRAW_HIP(m, hipMemcpyAsync(e->h_counters.p, counters, mr::kCounterInts * sizeof(int), hipMemcpyDeviceToHost, s));
-    MAP_DRAW_HIP(m, hipStreamSynchronize(s));
+    LF_HIP_CHECK(m, hipMemcpyAsync(e->h_counters.p, counters, mr::kCounterInts * sizeof(int), hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(m, hipStreamSynchronize(s));
     const int* hc = e->h_counters.p;
     const unsigned long long total = (unsigned long long)(unsigned)hc[2] | (unsigned long long)(unsigned)hc[3] << 32;
     if (total > (1ull << 30)) {
-        map_draw_error(m, "lf_map_render: %llu (line, tile) pairs, more than 2^30: nothing was drawn", total);
+        set_error(m, LF_ERR_CAPACITY, "lf_map_render: %llu (line, tile) pairs, more than 2^30: nothing was drawn", total);
         return LF_ERR_CAPACITY;
     }
-    if ((rc = map_draw_scratch(m, e->list, (size_t)(total ? total : 1) * sizeof(unsigned))) != LF_OK) return rc;
+    if ((rc = scratch(m, e->list, (size_t)(total ? total : 1) * sizeof(unsigned))) != LF_OK) return rc;
     unsigned* list = static_cast<unsigned*>(e->list.p);
     uint8_t* d_out = out_on_device ? out : static_cast<uint8_t*>(e->out.p);
     {
-        MapStageTimer<MapRenderState> t(m, e, 2);
+        CallClock::Scope t(e->clock, 2);
         mr::launch_bin(dv, m->d, n_traj, px, cursor, list, s);
     }
     {
-        MapStageTimer<MapRenderState> t(m, e, 3);
+        CallClock::Scope t(e->clock, 3);
         mr::launch_paint(dv, m->d, px, tile_start, tile_count, list, d_out, s);
     }
-    MAP_DRAW_HIP(m, hipGetLastError());
+    LF_HIP_CHECK(m, hipGetLastError());
     e->n_drawn = hc[0]; e->n_skipped = hc[1]; e->rendered = true;
     if (!out_on_device) {
-        MAP_DRAW_HIP(m, hipMemcpyAsync(out, d_out, image_bytes, hipMemcpyDeviceToHost, s));
-        MAP_DRAW_HIP(m, hipEventRecord(e->done, s));
-        MAP_DRAW_HIP(m, hipStreamSynchronize(s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(out, d_out, image_bytes, hipMemcpyDeviceToHost, s));
+        LF_HIP_CHECK(m, hipEventRecord(e->done, s));
+        LF_HIP_CHECK(m, hipStreamSynchronize(s));
     } else {
-        MAP_DRAW_HIP(m, hipEventRecord(e->done, s));
+        LF_HIP_CHECK(m, hipEventRecord(e->done, s));
     }
     if (n_drawn) *n_drawn = e->n_drawn;
     if (n_skipped) *n_skipped = e->n_skipped;
@@ -162,9 +161,9 @@ extern "C" int lf_map_render(lf_map* m, const lf_map_view* v, const double* traj
 extern "C" int lf_map_render_counts(lf_map* m, int* n_drawn, int* n_skipped)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (!m->render || !m->render->rendered) { map_draw_error(m, "lf_map_render_counts: no lf_map_render has run on this map"); return LF_ERR_BAD_ARG; }
-    MAP_DRAW_HIP(m, hipSetDevice(m->device));
-    MAP_DRAW_HIP(m, hipEventSynchronize(m->render->done));
+    if (!m->render || !m->render->rendered) { set_error(m, LF_ERR_BAD_ARG, "lf_map_render_counts: no lf_map_render has run on this map"); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
+    LF_HIP_CHECK(m, hipEventSynchronize(m->render->done));
     if (n_drawn) *n_drawn = m->render->n_drawn;
     if (n_skipped) *n_skipped = m->render->n_skipped;
     return LF_OK;
@@ -173,12 +172,12 @@ extern "C" int lf_map_render_counts(lf_map* m, int* n_drawn, int* n_skipped)
 extern "C" int lf_map_render_timing(lf_map* m, double* ms_per_stage, int n)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    if (!ms_per_stage || n < mr::kStages) { map_draw_error(m, "lf_map_render_timing: room for %d stages", mr::kStages); return LF_ERR_BAD_ARG; }
-    if (!m->render || !m->render->rendered || !m->render->timed) {
-        map_draw_error(m, "lf_map_render_timing: no lf_map_render ran with profiling on (lf_map_set_profiling)");
+    if (!ms_per_stage || n < mr::kStages) { set_error(m, LF_ERR_BAD_ARG, "lf_map_render_timing: room for %d stages", mr::kStages); return LF_ERR_BAD_ARG; }
+    if (!m->render || !m->render->rendered || !m->render->clock.timed) {
+        set_error(m, LF_ERR_BAD_ARG, "lf_map_render_timing: no lf_map_render ran with profiling on (lf_map_set_profiling)");
         return LF_ERR_BAD_ARG;
     }
-    return map_draw_timing(m, *m->render, mr::kStages, ms_per_stage);
+    return m->render->clock.read(m, mr::kStages, ms_per_stage);
 }
 
 extern "C" const char* lf_map_render_stage_name(int stage)

@@ -86,7 +86,7 @@ extern "C" int lf_matcher_match(lf_handle* h, const uint8_t* query32, int nq, co
     MatcherState* m = h->matcher.get();
     std::vector<int32_t> idx((size_t)nq);
     std::vector<float> dist((size_t)nq);
-    if ((rc = ensure(h, m->q, (size_t)nq * 32)) || (rc = ensure(h, m->idx, (size_t)nq * 4)) || (rc = ensure(h, m->dist, (size_t)nq * 4))) return rc;
+    if ((rc = scratch(h, m->q, (size_t)nq * 32)) || (rc = scratch(h, m->idx, (size_t)nq * 4)) || (rc = scratch(h, m->dist, (size_t)nq * 4))) return rc;
     LF_HIP_CHECK(h, hipMemcpyAsync(m->q.p, query32, (size_t)nq * 32, hipMemcpyHostToDevice, h->stream));
     if ((rc = lf_associate(h, static_cast<const uint8_t*>(m->q.p), nq, static_cast<const uint8_t*>(m->codes.p), m->total,
                            static_cast<int32_t*>(m->idx.p), static_cast<float*>(m->dist.p), 1)) != LF_OK) return rc;
@@ -115,7 +115,7 @@ extern "C" int lf_matcher_knn_match(lf_handle* h, const uint8_t* query32, int nq
     const size_t nk = (size_t)nq * k;
     std::vector<int32_t> idx(nk);
     std::vector<float> dist(nk);
-    if ((rc = ensure(h, m->q, (size_t)nq * 32)) || (rc = ensure(h, m->idx, nk * 4)) || (rc = ensure(h, m->dist, nk * 4))) return rc;
+    if ((rc = scratch(h, m->q, (size_t)nq * 32)) || (rc = scratch(h, m->idx, nk * 4)) || (rc = scratch(h, m->dist, nk * 4))) return rc;
     LF_HIP_CHECK(h, hipMemcpyAsync(m->q.p, query32, (size_t)nq * 32, hipMemcpyHostToDevice, h->stream));
     if ((rc = lf_knn_match(h, static_cast<const uint8_t*>(m->q.p), nq, static_cast<const uint8_t*>(m->codes.p), m->total, k,
                            static_cast<int32_t*>(m->idx.p), static_cast<float*>(m->dist.p), 1)) != LF_OK) return rc;
@@ -148,8 +148,8 @@ extern "C" int lf_matcher_radius_match(lf_handle* h, const uint8_t* query32, int
     if (rc != LF_OK) return rc;
     if (!n_lists || !list_offsets || !total || cap < 0 || (cap > 0 && !out)) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_matcher_radius_match: bad argument"); return LF_ERR_BAD_ARG; }
     MatcherState* m = h->matcher.get();
-    if ((rc = ensure(h, m->q, (size_t)nq * 32)) || (rc = ensure(h, m->off, ((size_t)nq + 1) * 4)) ||
-        (rc = ensure(h, m->idx, (size_t)(cap > 0 ? cap : 1) * 4)) || (rc = ensure(h, m->dist, (size_t)(cap > 0 ? cap : 1) * 4))) return rc;
+    if ((rc = scratch(h, m->q, (size_t)nq * 32)) || (rc = scratch(h, m->off, ((size_t)nq + 1) * 4)) ||
+        (rc = scratch(h, m->idx, (size_t)(cap > 0 ? cap : 1) * 4)) || (rc = scratch(h, m->dist, (size_t)(cap > 0 ? cap : 1) * 4))) return rc;
     LF_HIP_CHECK(h, hipMemcpyAsync(m->q.p, query32, (size_t)nq * 32, hipMemcpyHostToDevice, h->stream));
     int found = 0;
     rc = lf_radius_match(h, static_cast<const uint8_t*>(m->q.p), nq, static_cast<const uint8_t*>(m->codes.p), m->total, max_distance,

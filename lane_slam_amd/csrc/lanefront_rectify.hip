@@ -137,7 +137,7 @@ int ensure_map(lf_handle* h, const char* who)
     // (kernels of an earlier call may still read the map that is about to be replaced)
     LF_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     int rc;
-    if ((rc = ensure(h, e.xy, px * sizeof(short2))) || (rc = ensure(h, e.frac, px * sizeof(uint16_t)))) return rc;
+    if ((rc = scratch(h, e.xy, px * sizeof(short2))) || (rc = scratch(h, e.frac, px * sizeof(uint16_t)))) return rc;
     if (!e.tab.p) {
         std::vector<int16_t> tab((size_t)rect::kTabRows * 16);
         make_table(tab.data());
@@ -241,8 +241,8 @@ extern "C" int lf_rectify_batch(lf_handle* h, const uint8_t* src, int src_on_dev
     if ((rc = ensure_map(h, "lf_rectify_batch")) != LF_OK) return rc;
     RectState& e = *h->rect;
     hipStream_t s = h->stream;
-    if (!src_on_device && (rc = ensure(h, e.in, src_bytes))) return rc;
-    if (!dst_on_device && (rc = ensure(h, e.out, dst_bytes))) return rc;
+    if (!src_on_device && (rc = scratch(h, e.in, src_bytes))) return rc;
+    if (!dst_on_device && (rc = scratch(h, e.out, dst_bytes))) return rc;
     const uint8_t* d_src = src;
     if (!src_on_device) {
         LF_HIP_CHECK(h, hipMemcpyAsync(e.in.p, src, src_bytes, hipMemcpyHostToDevice, s));
@@ -262,13 +262,11 @@ extern "C" int lf_rectify_batch(lf_handle* h, const uint8_t* src, int src_on_dev
     if (split > n_frames) split = n_frames;
     if (split > (1L << 30) / tiles) split = (1L << 30) / tiles;
     if (split < 1) split = 1;
-    e.timed = h->profiling;
-    if (e.timed) {
-        for (hipEvent_t& ev : e.ev) if (!ev) LF_HIP_CHECK(h, hipEventCreate(&ev));
-        LF_HIP_CHECK(h, hipEventRecord(e.ev[0], s));
+    if ((rc = e.clock.begin(h)) != LF_OK) return rc;
+    {
+        CallClock::Scope t(e.clock, 0);
+        rect::launch_remap(m, d_src, n_frames, rows, cols, channels, d_dst, (int)split, s);
     }
-    rect::launch_remap(m, d_src, n_frames, rows, cols, channels, d_dst, (int)split, s);
-    if (e.timed) LF_HIP_CHECK(h, hipEventRecord(e.ev[1], s));
     LF_HIP_CHECK(h, hipGetLastError());
     if (dst_on_device) return LF_OK;
     LF_HIP_CHECK(h, hipMemcpyAsync(dst, d_dst, dst_bytes, hipMemcpyDeviceToHost, s));
@@ -280,16 +278,11 @@ extern "C" int lf_rectify_timing(lf_handle* h, double* ms_per_stage, int n)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
     if (!ms_per_stage || n < rect::kStages) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_rectify_timing: room for %d stages", rect::kStages); return LF_ERR_BAD_ARG; }
-    if (!h->rect || !h->rect->timed) {
+    if (!h->rect || !h->rect->clock.timed) {
         lf_set_error(h, LF_ERR_BAD_ARG, "lf_rectify_timing: no lf_rectify_batch ran with profiling on (lf_set_profiling)");
         return LF_ERR_BAD_ARG;
     }
-    RectState& e = *h->rect;
-    LF_HIP_CHECK(h, hipEventSynchronize(e.ev[1]));
-    float ms = 0.f;
-    LF_HIP_CHECK(h, hipEventElapsedTime(&ms, e.ev[0], e.ev[1]));
-    ms_per_stage[0] = ms;
-    return LF_OK;
+    return h->rect->clock.read(h, rect::kStages, ms_per_stage);
 }
 
 extern "C" const char* lf_rectify_stage_name(int stage)
