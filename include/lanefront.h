@@ -667,6 +667,100 @@ LF_API int lf_map_step_aligned_host(lf_map* m, const lf_segments* segs, int n, i
  * them.  A stage of its own: lf_map_get_timing's stages and indices are unchanged. */
 LF_API int lf_map_align_timing(lf_map* m, double* ms, int32_t* launches);
 
+/* ---- a batch's trajectory smoothed against the live map: lf_map_smooth -------------------------------
+ * lf_map_align corrects every frame on its own: a frame without enough pairs keeps its odometry pose, and nothing ties a frame to
+ * its neighbours.  The reference's README asks to "smooth odometry estimates" and names a pose graph among its future improvements;
+ * nothing of it is in the reference, so this too is the package's OWN contract, written so that a sequential restatement
+ * (tests/map_smooth_ref.py) and the kernels (k_map_smooth.hip) agree bit for bit.  One joint Gauss-Newton over all poses of a
+ * chain of consecutive frames: lf_map_align's map terms per frame, the odometry's relative motion between neighbours.  The map
+ * is read as it stands on the map's stream when the call is reached; nothing of the map is changed.  All f64, unfused, in the
+ * order written here; sin, cos and sqrt as in lf_map_align.
+ *
+ *   chains            chain c holds the frames chain_offset[c] <= f < chain_offset[c + 1]: chain_offset[0] = 0, no entry smaller
+ *                     than the one before it, chain_offset[n_chains] = n_frames.  NULL (n_chains = 1 then): one chain of all
+ *                     frames.  Chains are independent of one another; an empty chain does nothing, its chain_status is
+ *                     LF_ALIGN_OK.  Below, L is a chain's length and i = 0 .. L - 1 its nodes, node i being frame o + i.
+ *   iterate           (x, y, th) per frame, at first frame_pose[3 f ..] = (x0, y0, th0).
+ *   map factor        of frame f at its iterate: lf_map_align's pairs, endpoints, weights, 64 partial sums and fold, unchanged:
+ *                     N00 .. N22, g0 .. g2, cost, used.  used < 2 min_pairs: the frame has NO map factor in this iteration, its
+ *                     N and g are taken as +0 (cost and used are reported as they are).  n_pairs as in lf_map_align.
+ *   node              D (symmetric 3 x 3, only its upper triangle is ever computed) and b (3), in this order:
+ *                     D00 = N00 + prior_xy, D11 = N11 + prior_xy, D22 = N22 + prior_theta, D01 = N01, D02 = N02, D12 = N12;
+ *                     b0 = -(g0 + prior_xy (x - x0)), b1 = -(g1 + prior_xy (y - y0)), b2 = -(g2 + prior_theta (th - th0));
+ *                     node 0 only: D00 = D00 + anchor_xy, D11 = D11 + anchor_xy, D22 = D22 + anchor_theta, b0 = b0 - anchor_xy
+ *                     (x - x0), b1 = b1 - anchor_xy (y - y0), b2 = b2 - anchor_theta (th - th0);  then, i > 0: the edge i - 1 -> i
+ *                     adds D += Jn^T W Jn, b -= Jn^T W e and gives the coupling C_i = Jn^T W Jf (all nine; C_0 = +0);  then,
+ *                     i + 1 < L: the edge i -> i + 1 adds D += Jf^T W Jf, b -= Jf^T W e.
+ *   edge f -> n       n = f + 1.  (s0, c0) = sin, cos of th0_f;  dX = x0_n - x0_f, dY = y0_n - y0_f;  zx = c0 dX + s0 dY,
+ *                     zy = (-s0) dX + c0 dY, zt = th0_n - th0_f.  (s, c) = sin, cos of th_f;  ux = x_n - x_f, uy = y_n - y_f;
+ *                     px = c ux + s uy, py = (-s) ux + c uy;  e = (px - zx, py - zy, (th_n - th_f) - zt).
+ *                     Jf = [[-c, -s, py], [s, -c, -px], [0, 0, -1]], Jn = [[c, s, 0], [-s, c, 0], [0, 0, 1]] (the zeros are +0),
+ *                     W = diag(w0, w1, w2) = diag(odo_xy, odo_xy, odo_theta).  For 3 x 3 A, B, with every term computed, the
+ *                     zeros included:  (A^T W B)[r][c] = ((A[0][r] w0) B[0][c] + (A[1][r] w1) B[1][c]) + (A[2][r] w2) B[2][c],
+ *                     (A^T W e)[r] = ((A[0][r] w0) e[0] + (A[1][r] w1) e[1]) + (A[2][r] w2) e[2];  X += M is X = X + M.
+ *   solve3(D, v)      lf_map_align's solve of the 3 x 3 system with A = D and b = v as they are (no prior is added): the LDL^T
+ *                     in its order with its pivot test, then t.  It fails on a pivot that is not finite or <= 0, tested before
+ *                     it divides, or on a t that is not finite.
+ *   reduction         block cyclic reduction of the chain's block tridiagonal system, levels h = 1, 2, 4, .. while h < L.  In
+ *                     level h, C_i is the coupling H[i, i - h] and dot(a, v) = (a0 v0 + a1 v1) + a2 v2.
+ *                     (a) every node j = h (mod 2h), j < L, is eliminated:  y_j = solve3(D_j, b_j);  column c of P_j =
+ *                     solve3(D_j, column c of C_j);  column c of Q_j = solve3(D_j, row c of C_(j+h)) when j + h < L, else Q_j =
+ *                     +0.  One failing solve marks the chain and leaves y_j, P_j and Q_j all +0.
+ *                     (b) then every node i = 0 (mod 2h), i < L, is updated, from j = i - h first (i > 0), with C = C_i:
+ *                     D[r][c] = D[r][c] - dot(row r of C, column c of Q_j) for r <= c in the order 00 01 02 11 12 22;
+ *                     b[r] = b[r] - dot(row r of C, y_j);  C'[r][c] = -dot(row r of C, column c of P_j).  Then from j = i + h
+ *                     where j < L, with G = C_j:  D[r][c] = D[r][c] - dot(column r of G, column c of P_j), r <= c as before;
+ *                     b[r] = b[r] - dot(column r of G, y_j).  Then C_i = C' (+0 for node 0).
+ *                     Node 0 is alone after the last level:  t_0 = solve3(D_0, b_0); failing marks the chain, t_0 = +0.
+ *   substitution      levels in reverse, h = the largest power of two < L down to 1:  for every j = h (mod 2h), j < L:
+ *                     t[r] = y_j[r] - dot(row r of P_j, t_(j-h)), then, where j + h < L, t[r] = t[r] - dot(row r of Q_j, t_(j+h)).
+ *                     A t_j with a component that is not finite marks the chain.
+ *                     The order of elimination is part of the contract, and it does not depend on the data: the nodes of one
+ *                     level may be worked on at the same time.
+ *   iteration k       = 0 .. iterations - 1, per chain: the map factors of its frames at their iterates (cost0 = cost when
+ *                     k = 0; result.cost = cost, n_used = used); the nodes; the reduction and the substitution.  A marked
+ *                     chain is LF_ALIGN_DEGENERATE: it stops and keeps the iterate it had.  Else every frame of the chain
+ *                     takes its step, x = x + t[0], y = y + t[1], th = th + t[2], and the chain's iterations += 1.
+ *   the limits        after the chain's last iteration, whatever its status: shift and turn of every frame against its
+ *                     frame_pose as in lf_map_align.  One frame with shift > max_shift or turn > max_turn: the chain is
+ *                     LF_ALIGN_REJECTED, and every pose of it is frame_pose again, bit for bit.
+ *   results           one lf_align_result per frame: status = the chain's when that is LF_ALIGN_DEGENERATE or LF_ALIGN_REJECTED;
+ *                     else LF_ALIGN_OK when the frame had a map factor in the last iteration evaluated, LF_ALIGN_FEW when its
+ *                     neighbours carried it.  iterations = the chain's accepted steps.  chain_status[c] (may be NULL) = the
+ *                     chain's LF_ALIGN_OK, LF_ALIGN_DEGENERATE or LF_ALIGN_REJECTED.
+ * A chain without any map factor, prior or anchor has a singular system (the odometry fixes no absolute pose); it is DEGENERATE
+ * only where a pivot comes out <= 0, which rounding decides: give such chains a prior or an anchor.
+ * LF_ERR_BAD_ARG, touching nothing: what lf_map_align refuses (cfg->align is checked as its cfg); n_chains < 1; a chain_offset
+ * that is not as described, or NULL with n_chains != 1; an odo_xy, odo_theta, anchor_xy or anchor_theta that is negative or NaN.
+ *
+ * lf_map_smooth returns when `results` and `chain_status` (host) are in place.  lf_map_step_smoothed is lf_map_step_aligned with
+ * the smoother in the aligner's place: association, all iterations, packing and update are queued on the map's stream, the poses
+ * stay on the device, and there is one wait at the end, for the results.  Its map is byte-identical to the map of lf_map_step
+ * with frame_pose = the (x, y, theta) of `results`. */
+typedef struct lf_smooth_config {
+    lf_align_config align;       /* the map factors, the prior, the limits and the iterations: as for lf_map_align */
+    double  odo_xy, odo_theta;   /* >= 0: the weights of an odometry factor's translation (1 / m^2) and rotation (1 / rad^2) residuals;
+                                    defaults 100 and 100, starting values that no log has tuned */
+    double  anchor_xy, anchor_theta;     /* >= 0: added like the prior, to the first frame of every chain only; defaults 0 */
+} lf_smooth_config;
+LF_API int lf_sizeof_smooth_config(void);
+LF_API void lf_map_smooth_default_config(lf_smooth_config* c);
+/* as lf_map_align, with chain_offset (host, [n_chains + 1], or NULL) and chain_status (host, [n_chains], or NULL) */
+LF_API int lf_map_smooth(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist,
+                  const double* frame_pose /* host [n_frames][3] */, const int32_t* chain_offset, int n_chains,
+                  const lf_smooth_config* cfg, int on_device, lf_align_result* results /* host [n_frames] */, int32_t* chain_status);
+/* as lf_map_step_aligned */
+LF_API int lf_map_step_smoothed(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const double* frame_pose,
+                         const int32_t* chain_offset, int n_chains, const lf_smooth_config* cfg, int step, int32_t* idx, float* dist,
+                         lf_align_result* results, int32_t* chain_status);
+/* as lf_map_step_aligned_host */
+LF_API int lf_map_step_smoothed_host(lf_map* m, const lf_segments* segs, int n, int n_frames, const double* frame_pose,
+                              const int32_t* chain_offset, int n_chains, const lf_smooth_config* cfg, int step, int32_t* idx, float* dist,
+                              lf_align_result* results, int32_t* chain_status);
+/* ms and launches of the smoother (one launch = all iterations of one call) accumulated since the previous call, with profiling
+ * on; resets them.  A stage of its own: lf_map_get_timing and lf_map_align_timing are unchanged. */
+LF_API int lf_map_smooth_timing(lf_map* m, double* ms, int32_t* launches);
+
 /* ---- Histogram lane filter: lane pose from ground segments -----------------------------------------
  * LaneFilterHistogram (src/lane_filter/include/lane_filter/lane_filter.py:12-161) as lane_filter_node.processSegments
  * drives it (src/lane_filter/src/lane_filter_node.py:49-87): per frame predict(dt, v, w) -> update(segments) ->

@@ -44,6 +44,8 @@ EXPORTS = (
     "lf_sizeof_camera_view", "lf_map_camera_view", "lf_map_render_camera", "lf_map_render_camera_timing",
     "lf_sizeof_align_config", "lf_sizeof_align_result", "lf_map_align_default_config", "lf_map_align", "lf_map_step_aligned",
     "lf_map_step_aligned_host", "lf_map_align_timing",
+    "lf_sizeof_smooth_config", "lf_map_smooth_default_config", "lf_map_smooth", "lf_map_step_smoothed", "lf_map_step_smoothed_host",
+    "lf_map_smooth_timing",
 )
 LF_ALIGN_OK, LF_ALIGN_FEW, LF_ALIGN_DEGENERATE, LF_ALIGN_REJECTED = 0, 1, 2, 3
 ALIGN_STATUS = ("ok", "few", "degenerate", "rejected")
@@ -161,6 +163,12 @@ class LfAlignConfig(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_int32), ("min_pairs", ctypes.c_int32), ("min_hits", ctypes.c_int32), ("color_match", ctypes.c_int32),
                 ("gate", ctypes.c_double), ("huber", ctypes.c_double), ("max_dist", ctypes.c_double), ("prior_xy", ctypes.c_double),
                 ("prior_theta", ctypes.c_double), ("max_shift", ctypes.c_double), ("max_turn", ctypes.c_double)]
+
+
+class LfSmoothConfig(ctypes.Structure):
+    """ctypes mirror of `lf_smooth_config` (include/lanefront.h)."""
+    _fields_ = [("align", LfAlignConfig), ("odo_xy", ctypes.c_double), ("odo_theta", ctypes.c_double), ("anchor_xy", ctypes.c_double),
+                ("anchor_theta", ctypes.c_double)]
 
 
 class LfAlignResult(ctypes.Structure):
@@ -317,6 +325,15 @@ def load():
     lib.lf_map_align_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
     for f in ("lf_sizeof_align_config", "lf_sizeof_align_result", "lf_map_align", "lf_map_step_aligned", "lf_map_step_aligned_host",
               "lf_map_align_timing"):
+        getattr(lib, f).restype = ci
+    lib.lf_sizeof_smooth_config.argtypes = []
+    lib.lf_map_smooth_default_config.argtypes = [ctypes.POINTER(LfSmoothConfig)]
+    lib.lf_map_smooth_default_config.restype = None
+    lib.lf_map_smooth.argtypes = [vp, vp, ctypes.POINTER(LfSegments), ci, ci, vp, vp, vp, vp, ci, ctypes.POINTER(LfSmoothConfig), ci, vp, vp]
+    lib.lf_map_step_smoothed.argtypes = [vp, vp, ctypes.POINTER(LfSegments), ci, ci, vp, vp, ci, ctypes.POINTER(LfSmoothConfig), ci, vp, vp, vp, vp]
+    lib.lf_map_step_smoothed_host.argtypes = [vp, ctypes.POINTER(LfSegments), ci, ci, vp, vp, ci, ctypes.POINTER(LfSmoothConfig), ci, vp, vp, vp, vp]
+    lib.lf_map_smooth_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
+    for f in ("lf_sizeof_smooth_config", "lf_map_smooth", "lf_map_step_smoothed", "lf_map_step_smoothed_host", "lf_map_smooth_timing"):
         getattr(lib, f).restype = ci
     lib.lf_descriptor_default_params.argtypes = [ctypes.POINTER(LfDescriptorParams)]
     lib.lf_descriptor_default_params.restype = None

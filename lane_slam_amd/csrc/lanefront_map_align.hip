@@ -18,9 +18,10 @@ const char* bad_config(const lf_align_config* c)
     return nullptr;
 }
 
-// LF_ERR_BAD_ARG with the reason in the map's error text, or LF_OK; nothing is touched
-int check_call(lf_map* m, const char* who, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const double* frame_pose,
-               const lf_align_config* cfg, const lf_align_result* results)
+}  // namespace
+
+int align_check_call(lf_map* m, const char* who, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const double* frame_pose,
+                     const lf_align_config* cfg, const void* results)
 {
     if (!segs || !frame_pose || !cfg || !results) { set_error(m, LF_ERR_BAD_ARG, "%s: null segs, frame_pose, cfg or results", who); return LF_ERR_BAD_ARG; }
     if (n < 0 || n_frames < 1 || n_frames > ma::kMaxFrames) { set_error(m, LF_ERR_BAD_ARG, "%s: n < 0 or n_frames outside 1 .. %d", who, ma::kMaxFrames); return LF_ERR_BAD_ARG; }
@@ -30,6 +31,49 @@ int check_call(lf_map* m, const char* who, const lf_segments* segs, int n, int n
     if (const char* why = bad_config(cfg)) { set_error(m, LF_ERR_BAD_ARG, "%s: bad configuration (%s)", who, why); return LF_ERR_BAD_ARG; }
     return LF_OK;
 }
+
+int align_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist, lf_segments* d,
+                     const int32_t** didx, const float** ddist)
+{
+    int rc;
+    hipStream_t s = m->stream;
+    const size_t c = (size_t)n;
+    if ((rc = scratch(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = scratch(m, m->st_ground, c * 32)) ||
+        (rc = scratch(m, m->st_idx, c * 4)) || (segs->color && (rc = scratch(m, m->st_color, c))) ||
+        (segs->keep && (rc = scratch(m, m->st_keep, c))) || (dist && (rc = scratch(m, m->st_dist, c * 4)))) return rc;
+    LF_HIP_CHECK(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
+    LF_HIP_CHECK(m, hipMemcpyAsync(m->st_ground.p, segs->ground, c * 32, hipMemcpyHostToDevice, s));
+    LF_HIP_CHECK(m, hipMemcpyAsync(m->st_idx.p, idx, c * 4, hipMemcpyHostToDevice, s));
+    d->frame_offset = static_cast<int32_t*>(m->st_fo.p); d->ground = static_cast<double*>(m->st_ground.p);
+    *didx = static_cast<const int32_t*>(m->st_idx.p);
+    if (segs->color) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_color.p, segs->color, c, hipMemcpyHostToDevice, s)); d->color = static_cast<uint8_t*>(m->st_color.p); }
+    if (segs->keep) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_keep.p, segs->keep, c, hipMemcpyHostToDevice, s)); d->keep = static_cast<uint8_t*>(m->st_keep.p); }
+    if (dist) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_dist.p, dist, c * 4, hipMemcpyHostToDevice, s)); *ddist = static_cast<const float*>(m->st_dist.p); }
+    return LF_OK;
+}
+
+int step_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, lf_segments* d)
+{
+    int rc;
+    hipStream_t s = m->stream;
+    const size_t c = (size_t)(n > 0 ? n : 1);
+    if ((rc = scratch(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = scratch(m, m->st_code, c * 32)) || (rc = scratch(m, m->st_color, c)) ||
+        (rc = scratch(m, m->st_keep, c)) || (rc = scratch(m, m->st_ground, c * 32)) || (rc = scratch(m, m->st_idx, c * 4)) ||
+        (rc = scratch(m, m->st_dist, c * 4))) return rc;
+    LF_HIP_CHECK(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
+    d->frame_offset = static_cast<int32_t*>(m->st_fo.p);
+    if (n > 0) {
+        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_code.p, segs->code, (size_t)n * 32, hipMemcpyHostToDevice, s));
+        d->code = static_cast<uint8_t*>(m->st_code.p);
+        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_ground.p, segs->ground, (size_t)n * 32, hipMemcpyHostToDevice, s));
+        d->ground = static_cast<double*>(m->st_ground.p);
+        if (segs->color) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_color.p, segs->color, (size_t)n, hipMemcpyHostToDevice, s)); d->color = static_cast<uint8_t*>(m->st_color.p); }
+        if (segs->keep) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_keep.p, segs->keep, (size_t)n, hipMemcpyHostToDevice, s)); d->keep = static_cast<uint8_t*>(m->st_keep.p); }
+    }
+    return LF_OK;
+}
+
+namespace {
 
 // queue the alignment of device arrays on the map's stream: the prior poses go up, m->pose receives x, y, cos, sin per frame and
 // m->al_res the results
@@ -82,10 +126,9 @@ extern "C" int lf_map_align(lf_map* m, lf_handle* h, const lf_segments* segs, in
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
     int rc;
-    if ((rc = check_call(m, "lf_map_align", segs, n, n_frames, idx, frame_pose, cfg, results)) != LF_OK) return rc;
+    if ((rc = align_check_call(m, "lf_map_align", segs, n, n_frames, idx, frame_pose, cfg, results)) != LF_OK) return rc;
     LF_HIP_CHECK(m, hipSetDevice(m->device));
     if ((rc = after_handle(m, h)) != LF_OK) return rc;
-    hipStream_t s = m->stream;
     lf_segments d;
     memset(&d, 0, sizeof(d));
     const int32_t* didx = idx;
@@ -93,18 +136,7 @@ extern "C" int lf_map_align(lf_map* m, lf_handle* h, const lf_segments* segs, in
     if (on_device) {
         d.frame_offset = segs->frame_offset; d.ground = segs->ground; d.color = segs->color; d.keep = segs->keep;
     } else if (n > 0) {
-        const size_t c = (size_t)n;
-        if ((rc = scratch(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = scratch(m, m->st_ground, c * 32)) ||
-            (rc = scratch(m, m->st_idx, c * 4)) || (segs->color && (rc = scratch(m, m->st_color, c))) ||
-            (segs->keep && (rc = scratch(m, m->st_keep, c))) || (dist && (rc = scratch(m, m->st_dist, c * 4)))) return rc;
-        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
-        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_ground.p, segs->ground, c * 32, hipMemcpyHostToDevice, s));
-        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_idx.p, idx, c * 4, hipMemcpyHostToDevice, s));
-        d.frame_offset = static_cast<int32_t*>(m->st_fo.p); d.ground = static_cast<double*>(m->st_ground.p);
-        didx = static_cast<const int32_t*>(m->st_idx.p);
-        if (segs->color) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_color.p, segs->color, c, hipMemcpyHostToDevice, s)); d.color = static_cast<uint8_t*>(m->st_color.p); }
-        if (segs->keep) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_keep.p, segs->keep, c, hipMemcpyHostToDevice, s)); d.keep = static_cast<uint8_t*>(m->st_keep.p); }
-        if (dist) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_dist.p, dist, c * 4, hipMemcpyHostToDevice, s)); ddist = static_cast<const float*>(m->st_dist.p); }
+        if ((rc = align_stage_host(m, segs, n, n_frames, idx, dist, &d, &didx, &ddist)) != LF_OK) return rc;
     }
     if ((rc = queue_align(m, &d, n, n_frames, didx, ddist, frame_pose, cfg)) != LF_OK) return rc;
     if ((rc = release_handle(m, h)) != LF_OK) return rc;
@@ -116,7 +148,7 @@ extern "C" int lf_map_step_aligned(lf_map* m, lf_handle* h, const lf_segments* s
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
     int rc;
-    if ((rc = check_call(m, "lf_map_step_aligned", segs, n, n_frames, idx, frame_pose, cfg, results)) != LF_OK) return rc;
+    if ((rc = align_check_call(m, "lf_map_step_aligned", segs, n, n_frames, idx, frame_pose, cfg, results)) != LF_OK) return rc;
     if (n > 0 && (!dist || !segs->code)) { set_error(m, LF_ERR_BAD_ARG, "lf_map_step_aligned: code and dist are required"); return LF_ERR_BAD_ARG; }
     if (n > 0 && (rc = lf_map_associate(m, h, segs->code, segs->color, n, idx, dist, 1)) != LF_OK) return rc;
     LF_HIP_CHECK(m, hipSetDevice(m->device));
@@ -139,29 +171,16 @@ extern "C" int lf_map_step_aligned_host(lf_map* m, const lf_segments* segs, int 
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
     int rc;
-    if ((rc = check_call(m, "lf_map_step_aligned_host", segs, n, n_frames, idx, frame_pose, cfg, results)) != LF_OK) return rc;
+    if ((rc = align_check_call(m, "lf_map_step_aligned_host", segs, n, n_frames, idx, frame_pose, cfg, results)) != LF_OK) return rc;
     if (!segs->frame_offset || (n > 0 && (!segs->code || !dist)) || (m->cfg.color_gating && n > 0 && !segs->color)) {
         set_error(m, LF_ERR_BAD_ARG, "lf_map_step_aligned_host: bad argument (frame_offset, code and dist are required, color when gating is on)");
         return LF_ERR_BAD_ARG;
     }
     LF_HIP_CHECK(m, hipSetDevice(m->device));
     hipStream_t s = m->stream;
-    const size_t c = (size_t)(n > 0 ? n : 1);
-    if ((rc = scratch(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = scratch(m, m->st_code, c * 32)) || (rc = scratch(m, m->st_color, c)) ||
-        (rc = scratch(m, m->st_keep, c)) || (rc = scratch(m, m->st_ground, c * 32)) || (rc = scratch(m, m->st_idx, c * 4)) ||
-        (rc = scratch(m, m->st_dist, c * 4))) return rc;
     lf_segments d;
     memset(&d, 0, sizeof(d));
-    LF_HIP_CHECK(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
-    d.frame_offset = static_cast<int32_t*>(m->st_fo.p);
-    if (n > 0) {
-        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_code.p, segs->code, (size_t)n * 32, hipMemcpyHostToDevice, s));
-        d.code = static_cast<uint8_t*>(m->st_code.p);
-        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_ground.p, segs->ground, (size_t)n * 32, hipMemcpyHostToDevice, s));
-        d.ground = static_cast<double*>(m->st_ground.p);
-        if (segs->color) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_color.p, segs->color, (size_t)n, hipMemcpyHostToDevice, s)); d.color = static_cast<uint8_t*>(m->st_color.p); }
-        if (segs->keep) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_keep.p, segs->keep, (size_t)n, hipMemcpyHostToDevice, s)); d.keep = static_cast<uint8_t*>(m->st_keep.p); }
-    }
+    if ((rc = step_stage_host(m, segs, n, n_frames, &d)) != LF_OK) return rc;
     rc = lf_map_step_aligned(m, nullptr, &d, n, n_frames, frame_pose, cfg, step, static_cast<int32_t*>(m->st_idx.p), static_cast<float*>(m->st_dist.p), results);
     if (rc != LF_OK) return rc;
     if (n > 0) {

@@ -1,5 +1,6 @@
 // The live map's handle, for the translation units of lf_map_*: the map itself (lanefront_map.hip), its two views
-// (lanefront_map_render.hip, lanefront_map_camera.hip) and the pose alignment (lanefront_map_align.hip).
+// (lanefront_map_render.hip, lanefront_map_camera.hip), the pose alignment (lanefront_map_align.hip) and the trajectory smoother
+// (lanefront_map_smooth.hip).
 #pragma once
 #include <memory>
 #include <vector>
@@ -54,18 +55,34 @@ struct lf_map : lf::Core {
     DevBuf act, own_block, pose, q_in, c_in, idx_out, dist_out, seed_code, seed_color, seed_ground, tie_res;
     DevBuf st_fo, st_code, st_color, st_keep, st_ground, st_idx, st_dist;     // staging of lf_map_step_host and of lf_map_align's host arrays
     DevBuf al_pose0, al_res;                 // lf_map_align: the prior poses [n_frames][3], the results [n_frames]
+    // lf_map_smooth: the chains' offsets [n_chains + 1] and each frame's chain [n_frames], the map sums [n_frames][9], the nodes
+    // of the block tridiagonal systems [n_frames], the chains' states and statuses [n_chains]
+    DevBuf sm_offset, sm_chain_of, sm_sums, sm_node, sm_chain, sm_status;
     std::vector<double> h_pose;
-    // per-stage timing: the stages of lf_map_get_timing, then kMapAlignStage (lf_map_align_timing); past 4096 outstanding
-    // records a bracket goes untimed
-    StageClock clock{LF_MAP_N_STAGES + 1, 4096, false};
+    std::vector<int32_t> h_chains;
+    // per-stage timing: the stages of lf_map_get_timing, then kMapAlignStage (lf_map_align_timing) and kMapSmoothStage
+    // (lf_map_smooth_timing); past 4096 outstanding records a bracket goes untimed
+    StageClock clock{LF_MAP_N_STAGES + 2, 4096, false};
     std::unique_ptr<lf::MapRenderState> render;   // lf_map_render / lf_map_bounds (lanefront_map_render.hip), made by their first call
     std::unique_ptr<lf::MapCameraState> camera;   // lf_map_render_camera (lanefront_map_camera.hip), likewise
 };
 
 constexpr int kMapAlignStage = LF_MAP_N_STAGES;
+constexpr int kMapSmoothStage = LF_MAP_N_STAGES + 1;
 
 // ---- lanefront_map.hip's sequencing, for the translation unit that aligns poses before the update (lanefront_map_align.hip)
 int after_handle(lf_map* m, lf_handle* h);        // the map's stream waits for everything queued so far on the handle's stream
 int release_handle(lf_map* m, lf_handle* h);      // the handle's later work waits for what the map has queued so far
 // rows_hint: how many segment rows the blocks really hold when the host knows it (-1: assume they are full)
 int update_blocks(lf_map* m, const uint8_t* blocks, int n_blocks, int block_rows, int force_append, long long rows_hint = -1);
+
+// ---- lanefront_map_align.hip's checks and staging, shared with the smoother (lanefront_map_smooth.hip)
+// LF_ERR_BAD_ARG with the reason in the map's error text, or LF_OK; nothing is touched
+int align_check_call(lf_map* m, const char* who, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const double* frame_pose,
+                     const lf_align_config* cfg, const void* results);
+// queue the copies of the host arrays an alignment reads (frame_offset, ground, color, keep, idx, dist) into the map's staging
+// buffers; d, didx and ddist then name the device copies
+int align_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist, lf_segments* d,
+                     const int32_t** didx, const float** ddist);
+// the staging of lf_map_step_aligned_host: frame_offset, code, ground, color, keep go up; st_idx and st_dist are sized
+int step_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, lf_segments* d);

@@ -104,19 +104,28 @@ class LineAssociator(object):
                                               idx.ctypes.data, dist.ctypes.data, 0))
         return idx, dist
 
-    def step(self, seg, poses=None, step=0, align=None):
+    def step(self, seg, poses=None, step=0, align=None, smooth=None, chains=None):
         """Associate the segments of a host `Segments` block (FrontEnd.process_batch) against the map, then update the
         map with them; returns (idx, dist).  poses: (n_frames, 3) map -> duck (x, y, theta) per frame, or None.
         align: an `_lib.LfAlignConfig` (align_config) -- the poses are corrected against the map between association and update
-        (lf_map_step_aligned_host) and the call returns (idx, dist, poses_out, results) as `align` does."""
+        (lf_map_step_aligned_host) and the call returns (idx, dist, poses_out, results) as `align` does.
+        smooth: an `_lib.LfSmoothConfig` (smooth_config) -- the same with the smoother in the aligner's place
+        (lf_map_step_smoothed_host); chains: its chain offsets, None = one chain.  align and smooth exclude each other."""
+        if align is not None and smooth is not None:
+            raise ValueError("step: align and smooth exclude each other")
         n, n_frames = int(seg.n), len(seg.frame_offset) - 1
         keep_alive, pp = self._poses(poses, n_frames)
         s, alive = self._host_segs(seg, ("frame_offset", "code", "color", "keep", "ground"))
         idx, dist = np.empty(n, np.int32), np.empty(n, np.float32)
-        if align is None:
+        if align is None and smooth is None:
             self._check(self.lib.lf_map_step_host(self.m, ctypes.byref(s), n, n_frames, pp, int(step), idx.ctypes.data, dist.ctypes.data))
             return idx, dist
         res = np.zeros(n_frames, _lib.ALIGN_RESULT_DTYPE)
+        if smooth is not None:
+            co, cp, nc = self._chains(chains, n_frames)
+            self._check(self.lib.lf_map_step_smoothed_host(self.m, ctypes.byref(s), n, n_frames, pp, cp, nc, ctypes.byref(smooth), int(step),
+                                                           idx.ctypes.data, dist.ctypes.data, res.ctypes.data, None))
+            return idx, dist, self._poses_out(res), res
         self._check(self.lib.lf_map_step_aligned_host(self.m, ctypes.byref(s), n, n_frames, pp, ctypes.byref(align), int(step),
                                                       idx.ctypes.data, dist.ctypes.data, res.ctypes.data))
         return idx, dist, self._poses_out(res), res
@@ -184,6 +193,89 @@ class LineAssociator(object):
         ms, ln = ctypes.c_double(), ctypes.c_int32()
         self._check(self.lib.lf_map_align_timing(self.m, ctypes.byref(ms), ctypes.byref(ln)))
         return ms.value, ln.value
+
+    # ------------------------------------------------------------------ a batch's trajectory smoothed against the map (lf_map_smooth)
+    def smooth_config(self, align=None, **overrides):
+        """The library's default `_lib.LfSmoothConfig` (lf_map_smooth_default_config) with the overrides applied: odo_xy, odo_theta,
+        anchor_xy, anchor_theta, and any field of align_config (iterations, gate, prior_xy, ...); align: an `_lib.LfAlignConfig` that
+        replaces the default one before the overrides."""
+        c = _lib.LfSmoothConfig()
+        self.lib.lf_map_smooth_default_config(ctypes.byref(c))
+        if align is not None:
+            ctypes.memmove(ctypes.byref(c.align), ctypes.byref(align), ctypes.sizeof(_lib.LfAlignConfig))
+        own = dict((k, t) for k, t in _lib.LfSmoothConfig._fields_ if k != "align")
+        kinds = dict((k, t) for k, t in _lib.LfAlignConfig._fields_)
+        for k, val in overrides.items():
+            if k in own:
+                setattr(c, k, float(val))
+            elif k in kinds:
+                setattr(c.align, k, int(val) if kinds[k] is ctypes.c_int32 else float(val))
+            else:
+                raise TypeError("smooth_config: unknown field %r" % (k,))
+        return c
+
+    @staticmethod
+    def _chains(chains, n_frames):
+        """(the array kept alive, its address or None, n_chains)"""
+        if chains is None:
+            return None, None, 1
+        a = np.ascontiguousarray(chains, np.int32).reshape(-1)
+        return a, a.ctypes.data, len(a) - 1
+
+    def smooth(self, seg, idx, dist, poses, config=None, chains=None):
+        """Smooth the poses of a batch against the map as it stands (lf_map_smooth): the arguments of `align`, and chains, the
+        (n_chains + 1) offsets that split the frames into runs of consecutive frames (None: one chain).  Returns (poses_out,
+        results, chain_status): results as `align` returns them, chain_status (n_chains,) int32.  The map is not changed."""
+        n, n_frames = int(seg.n), len(seg.frame_offset) - 1
+        keep_alive, pp = self._poses(poses, n_frames)
+        s, alive = self._host_segs(seg, ("frame_offset", "color", "keep", "ground"))
+        idx = np.ascontiguousarray(idx, np.int32)
+        dist = None if dist is None else np.ascontiguousarray(dist, np.float32)
+        if len(idx) != n or (dist is not None and len(dist) != n):
+            raise ValueError("smooth: idx and dist hold one value per segment")
+        config = self.smooth_config() if config is None else config
+        co, cp, nc = self._chains(chains, n_frames)
+        res, cs = np.zeros(n_frames, _lib.ALIGN_RESULT_DTYPE), np.zeros(max(nc, 0), np.int32)
+        self._check(self.lib.lf_map_smooth(self.m, None, ctypes.byref(s), n, n_frames, idx.ctypes.data, None if dist is None else dist.ctypes.data,
+                                           pp, cp, nc, ctypes.byref(config), 0, res.ctypes.data, cs.ctypes.data))
+        return self._poses_out(res), res, cs
+
+    def smooth_device(self, fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, poses, config=None, chains=None):
+        """`smooth` for a batch that is resident on the device (out_ptrs as for step_device; idx_ptr / dist_ptr device arrays)."""
+        keep_alive, pp = self._poses(poses, n_frames)
+        s = self._segs(out_ptrs)
+        config = self.smooth_config() if config is None else config
+        co, cp, nc = self._chains(chains, int(n_frames))
+        res, cs = np.zeros(int(n_frames), _lib.ALIGN_RESULT_DTYPE), np.zeros(max(nc, 0), np.int32)
+        self._check(self.lib.lf_map_smooth(self.m, fe.h if fe is not None else None, ctypes.byref(s), int(n), int(n_frames), int(idx_ptr),
+                                           dist_ptr and int(dist_ptr), pp, cp, nc, ctypes.byref(config), 1, res.ctypes.data, cs.ctypes.data))
+        return self._poses_out(res), res, cs
+
+    def smooth_timing(self):
+        """(ms, launches) of the smoother since the previous call (needs set_profiling(True)); one launch is one call's iterations."""
+        ms, ln = ctypes.c_double(), ctypes.c_int32()
+        self._check(self.lib.lf_map_smooth_timing(self.m, ctypes.byref(ms), ctypes.byref(ln)))
+        return ms.value, ln.value
+
+    @staticmethod
+    def carry(poses, last_odometry, last_corrected):
+        """The next batch's odometry poses (n, 3) with the previous batch's correction applied: the rigid motion that takes
+        last_odometry (the previous batch's last odometry pose) to last_corrected (what the smoother made of it).  Pure numpy
+        float64, one operation after the other: dth = thc - tho;  (s, c) = sin, cos of dth;  dx = x - xo, dy = y - yo;
+        the pose is turned about the old pose by dth, xr = x + ((c - 1) dx - s dy), yr = y + (s dx + (c - 1) dy);  then moved,
+        x' = xr + (xc - xo), y' = yr + (yc - yo);  then th' = th + dth.  Written this way last_corrected == last_odometry adds
+        zeros only and returns `poses` bit for bit (but for a -0, which comes back +0)."""
+        p = np.array(poses, np.float64).reshape(-1, 3)
+        xo, yo, tho = (np.float64(v) for v in last_odometry)
+        xc, yc, thc = (np.float64(v) for v in last_corrected)
+        dth = thc - tho
+        s, c = np.sin(dth), np.cos(dth)
+        dx, dy = p[:, 0] - xo, p[:, 1] - yo
+        out = np.empty_like(p)
+        out[:, 0] = (p[:, 0] + ((c - 1.0) * dx - s * dy)) + (xc - xo)
+        out[:, 1] = (p[:, 1] + (s * dx + (c - 1.0) * dy)) + (yc - yo)
+        out[:, 2] = p[:, 2] + dth
+        return out
 
     def fetch(self, first=0, n=None):
         n = self.capacity - first if n is None else n
@@ -396,12 +488,21 @@ class LineAssociator(object):
     def update_device(self, blocks_ptr, n_blocks, block_rows):
         self._check(self.lib.lf_map_update(self.m, int(blocks_ptr), int(n_blocks), int(block_rows)))
 
-    def step_device(self, fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, poses=None, step=0, align=None):
+    def step_device(self, fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, poses=None, step=0, align=None, smooth=None, chains=None):
         """associate + update for the n segments of a batch that is resident on the device (out_ptrs: the dict given to
         FrontEnd.submit_device; frame_offset, code, color, keep, ground are read).  align: an `_lib.LfAlignConfig` -- the poses are
-        corrected on the device between the two (lf_map_step_aligned) and the call returns (idx_ptr, dist_ptr, poses_out, results)."""
+        corrected on the device between the two (lf_map_step_aligned) and the call returns (idx_ptr, dist_ptr, poses_out, results).
+        smooth: an `_lib.LfSmoothConfig`, chains as for `smooth` -- the same through lf_map_step_smoothed."""
+        if align is not None and smooth is not None:
+            raise ValueError("step_device: align and smooth exclude each other")
         keep_alive, pp = self._poses(poses, n_frames)
         s = self._segs(out_ptrs)
+        if smooth is not None:
+            co, cp, nc = self._chains(chains, int(n_frames))
+            res = np.zeros(int(n_frames), _lib.ALIGN_RESULT_DTYPE)
+            self._check(self.lib.lf_map_step_smoothed(self.m, fe.h if fe is not None else None, ctypes.byref(s), int(n), int(n_frames), pp, cp, nc,
+                                                      ctypes.byref(smooth), int(step), int(idx_ptr), int(dist_ptr), res.ctypes.data, None))
+            return idx_ptr, dist_ptr, self._poses_out(res), res
         if align is not None:
             res = np.zeros(int(n_frames), _lib.ALIGN_RESULT_DTYPE)
             self._check(self.lib.lf_map_step_aligned(self.m, fe.h if fe is not None else None, ctypes.byref(s), int(n), int(n_frames), pp,

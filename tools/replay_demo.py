@@ -33,7 +33,12 @@ ap.add_argument("--map-jpeg", default=None, help="write the final map, rendered 
 ap.add_argument("--map-size", type=int, default=1024, help="rows = cols of that picture")
 ap.add_argument("--overlay-jpeg", default=None, metavar="DIR",
                 help="write every replayed frame, rectified and with the final map drawn into it on the device, as DIR/%%06d.jpg")
-ap.add_argument("--align", action="store_true",
+mode = ap.add_mutually_exclusive_group()
+mode.add_argument("--smooth", action="store_true",
+                  help="smooth every batch's poses against the map before the update (lf_map_step_smoothed, the default configuration, one "
+                       "chain per batch), carry each batch's correction into the next batch's poses (LineAssociator.carry) and print, per "
+                       "batch, how many frames came back with each status")
+mode.add_argument("--align", action="store_true",
                 help="correct every batch's poses against the map before the update (lf_map_step_aligned, the default configuration) and "
                      "print, per batch, how many frames came back with each status")
 args = ap.parse_args()
@@ -74,6 +79,7 @@ print("first batch verified against the oracle: %d segments in %d frames, %d kep
 # ---- replay
 t0 = time.perf_counter()
 n_seg = n_kept = n_matched = wire = 0
+last_odometry = last_corrected = (0.0, 0.0, 0.0)
 for b0 in range(0, args.frames - B + 1, B):
     fe.decode_jpeg_batch(msgs[b0:b0 + B], n_threads=args.threads, device_ptr=dev_frames)
     seg = fe.process_batch(dev_frames, n_frames=B)
@@ -83,7 +89,15 @@ for b0 in range(0, args.frames - B + 1, B):
         dd = torch.zeros(seg.n, dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()
         ptrs = {k: v.data_ptr() for k, v in d.items()}
-        if args.align:
+        if args.smooth:
+            # (the replay has no odometry: every pose is the identity before the previous batch's correction is carried into it; a
+            # chain that finds nothing to hold on to is DEGENERATE and keeps its poses)
+            poses = LineAssociator.carry(np.zeros((B, 3)), last_odometry, last_corrected)
+            out = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=poses, step=b0 // B, smooth=live.smooth_config())
+            last_odometry, last_corrected = (0.0, 0.0, 0.0), tuple(out[2][-1])
+            counts = np.bincount(out[3]["status"], minlength=4)
+            print("batch %d smoothed: %s" % (b0 // B, ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, counts))))
+        elif args.align:
             # (the replay has no odometry: every prior is the identity, and the seeded map has no geometry to align with)
             res = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=np.zeros((B, 3)), step=b0 // B,
                                    align=live.align_config())[3]
