@@ -761,6 +761,79 @@ LF_API int lf_map_step_smoothed_host(lf_map* m, const lf_segments* segs, int n, 
  * on; resets them.  A stage of its own: lf_map_get_timing and lf_map_align_timing are unchanged. */
 LF_API int lf_map_smooth_timing(lf_map* m, double* ms, int32_t* launches);
 
+/* ---- a batch's frames localised against the live map without a prior pose: lf_map_localize ------------
+ * lf_map_align and lf_map_smooth refine a pose that is already within `gate` of the truth: an endpoint further than that from its
+ * entry's line weighs nothing.  The reference's only pose source is open-loop wheel integration (src/odometry/src/odometry.py:66-120),
+ * so the first batch against a seeded map, a batch after a gap in the odometry, a robot put down elsewhere and a return to a mapped
+ * place after drift have no such pose.  lf_map_localize finds one per frame from the frame's descriptor associations
+ * (lf_map_associate's idx) and the map's geometry alone: every ordered couple of matched segments proposes a pose, every pose is
+ * scored by the matched segments it explains, the best one wins; wrong associations propose poses that explain little.  This is
+ * the package's OWN contract, written so that a sequential restatement (tests/map_localize_ref.py) and the kernel
+ * (k_map_localize.hip) agree bit for bit.  Frames are independent of one another.  The map is read as it stands on the map's
+ * stream when the call is reached; nothing of the map is changed.  All f64, unfused, in the order written here; sqrt correctly
+ * rounded, atan2 by the library's routine, "finite" as in lf_map_align.
+ *
+ *   pair              exactly lf_map_align's, with this configuration's min_hits, color_match and max_dist; per pair the segment's
+ *                     endpoints (px0, py0), (px1, py1) and the entry's nx, ny, Ax, Ay (lf_map_align's "line").  n_pairs counts all
+ *                     pairs of the frame.
+ *   candidates        the first max_pairs pairs of the frame in increasing segment index i, numbered 0 .. K - 1 (n_candidates = K).
+ *   hypothesis        (a, b, s): a != b in 0 .. K - 1, s in 0 .. flips; its index is h = (a K + b) 2 + s.  a gives the rotation, the
+ *                     lines of a and b the translation; s = 1 takes a's segment as seen end for end.
+ *   rotation          ux = px1_a - px0_a, uy = py1_a - py0_a, l2 = ux ux + uy uy.  l2 not finite or not > 0: invalid (such a
+ *                     candidate still scores, and may be b).  ul = sqrt(l2), ux = ux / ul, uy = uy / ul.  ex = ny_a, ey = -nx_a;
+ *                     s = 1: ex = -ex, ey = -ey.  c0 = ux ex + uy ey, s0 = ux ey - uy ex, nr = sqrt(c0 c0 + s0 s0).  nr not
+ *                     finite or not > 0: invalid.  cs = c0 / nr, sn = s0 / nr.
+ *   translation       for k = a, b:  mx = (px0_k + px1_k) 0.5, my = (py0_k + py1_k) 0.5;  rx = cs mx - sn my, ry = sn mx + cs my;
+ *                     c_k = nx_k (Ax_k - rx) + ny_k (Ay_k - ry).  det = nx_a ny_b - ny_a nx_b.  Not (|det| >= min_sin): invalid.
+ *                     tx = (c_a ny_b - c_b ny_a) / det, ty = (nx_a c_b - nx_b c_a) / det.  tx or ty not finite: invalid.
+ *   score             inl = 0, cost = +0; over the candidates j = 0 .. K - 1 in order, endpoint 0 before endpoint 1, (px, py) the
+ *                     endpoint:  qx = tx + (cs px - sn py), qy = ty + (sn px + cs py);  r = nx_j (qx - Ax_j) + ny_j (qy - Ay_j);
+ *                     |r| <= gate: inl += 1, cost = cost + r r.  A cost that is not finite at the end: invalid.  The lines are
+ *                     infinite: whether the endpoint falls within the entry's extent is not tested.
+ *   winner            among the valid hypotheses (n_hypotheses counts them) the largest inl; of equal inl the smaller cost; of
+ *                     equal cost the smaller h.  A total order: neither scheduling nor the shape of a reduction can change it.
+ *   status            K < 2: LF_ALIGN_FEW.  No valid hypothesis: LF_ALIGN_DEGENERATE.  A winner with inl < min_inliers: LF_ALIGN_FEW.
+ *                     Otherwise LF_ALIGN_OK.
+ *   result            LF_ALIGN_OK: x = tx, y = ty, theta = atan2(sn, cs) of the winner, seg_a and seg_b the batch's segment indices
+ *                     of its a and b, flip = s.  Otherwise: the pose is fallback_pose[3 f ..], (+0, +0, +0) when that is NULL,
+ *                     seg_a = seg_b = -1, flip = 0.  Whatever the status: n_pairs, n_candidates, n_hypotheses as counted;
+ *                     n_inliers and cost are the winner's, 0 and +0 without one.
+ * Along a straight road with no line across it every det is below min_sin: the frame is LF_ALIGN_DEGENERATE, not a guess.
+ * LF_ERR_BAD_ARG, touching nothing: NULL segs, cfg or results; n < 0; n_frames outside 1 .. 4096; n > 0 without segs->frame_offset,
+ * segs->ground or idx; a non-finite fallback pose; max_pairs outside 2 .. 128; flips other than 0 or 1; min_inliers < 1; a gate
+ * that is <= 0, NaN or infinite; a min_sin outside (0, 1] or NaN.
+ *
+ * lf_map_localize returns when `results` (host) are in place.  Its poses are a start for lf_map_align or lf_map_smooth (hand them
+ * over as frame_pose), which refine them.  One association per segment, one frame at a time. */
+typedef struct lf_localize_config {
+    int32_t max_pairs;           /* the candidates of a frame, 2 .. 128; default 64 */
+    int32_t flips;               /* 1: every couple is also tried with a's segment end for end; 0 or 1, default 1 */
+    int32_t min_inliers;         /* a winner with fewer inlying ENDPOINTS is LF_ALIGN_FEW; >= 1, default 6 */
+    int32_t min_hits;            /* as lf_align_config; default 1 */
+    int32_t color_match;         /* as lf_align_config; default 1 */
+    int32_t reserved_;           /* 0 */
+    double  gate;                /* metres, > 0 and finite: an endpoint with |r| <= gate is an inlier; default 0.10 */
+    double  min_sin;             /* in (0, 1]: a and b need |sin| of the angle between their lines >= min_sin; default 0.2 */
+    double  max_dist;            /* as lf_align_config; default +inf */
+} lf_localize_config;            /* the defaults are starting values that no log has tuned */
+typedef struct lf_localize_result {
+    double  x, y, theta;         /* the localised pose, or the fallback */
+    double  cost;                /* the winner's sum of r^2 over its inlying endpoints */
+    int32_t n_pairs, n_candidates, n_hypotheses, n_inliers;
+    int32_t seg_a, seg_b, flip;
+    int32_t status;              /* LF_ALIGN_OK, LF_ALIGN_FEW or LF_ALIGN_DEGENERATE */
+} lf_localize_result;
+LF_API int lf_sizeof_localize_config(void);
+LF_API int lf_sizeof_localize_result(void);
+LF_API void lf_map_localize_default_config(lf_localize_config* c);
+/* segs, idx, dist, on_device and h as for lf_map_align */
+LF_API int lf_map_localize(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist,
+                    const double* fallback_pose /* host [n_frames][3] or NULL */, const lf_localize_config* cfg, int on_device,
+                    lf_localize_result* results /* host [n_frames] */);
+/* ms and launches of the localisation kernel accumulated since the previous call, with profiling on; resets them.  A stage of
+ * its own: lf_map_get_timing, lf_map_align_timing and lf_map_smooth_timing are unchanged. */
+LF_API int lf_map_localize_timing(lf_map* m, double* ms, int32_t* launches);
+
 /* ---- Histogram lane filter: lane pose from ground segments -----------------------------------------
  * LaneFilterHistogram (src/lane_filter/include/lane_filter/lane_filter.py:12-161) as lane_filter_node.processSegments
  * drives it (src/lane_filter/src/lane_filter_node.py:49-87): per frame predict(dt, v, w) -> update(segments) ->

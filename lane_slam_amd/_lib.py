@@ -46,6 +46,7 @@ EXPORTS = (
     "lf_map_step_aligned_host", "lf_map_align_timing",
     "lf_sizeof_smooth_config", "lf_map_smooth_default_config", "lf_map_smooth", "lf_map_step_smoothed", "lf_map_step_smoothed_host",
     "lf_map_smooth_timing",
+    "lf_sizeof_localize_config", "lf_sizeof_localize_result", "lf_map_localize_default_config", "lf_map_localize", "lf_map_localize_timing",
 )
 LF_ALIGN_OK, LF_ALIGN_FEW, LF_ALIGN_DEGENERATE, LF_ALIGN_REJECTED = 0, 1, 2, 3
 ALIGN_STATUS = ("ok", "few", "degenerate", "rejected")
@@ -181,6 +182,26 @@ class LfAlignResult(ctypes.Structure):
 # the same layout as a numpy record: what LineAssociator.align returns
 ALIGN_RESULT_DTYPE = [("x", "<f8"), ("y", "<f8"), ("theta", "<f8"), ("cost0", "<f8"), ("cost", "<f8"), ("n_pairs", "<i4"), ("n_used", "<i4"),
                       ("iterations", "<i4"), ("status", "<i4")]
+
+
+class LfLocalizeConfig(ctypes.Structure):
+    """ctypes mirror of `lf_localize_config` (include/lanefront.h)."""
+    _fields_ = [("max_pairs", ctypes.c_int32), ("flips", ctypes.c_int32), ("min_inliers", ctypes.c_int32), ("min_hits", ctypes.c_int32),
+                ("color_match", ctypes.c_int32), ("reserved_", ctypes.c_int32), ("gate", ctypes.c_double), ("min_sin", ctypes.c_double),
+                ("max_dist", ctypes.c_double)]
+
+
+class LfLocalizeResult(ctypes.Structure):
+    """ctypes mirror of `lf_localize_result` (include/lanefront.h)."""
+    _fields_ = [("x", ctypes.c_double), ("y", ctypes.c_double), ("theta", ctypes.c_double), ("cost", ctypes.c_double),
+                ("n_pairs", ctypes.c_int32), ("n_candidates", ctypes.c_int32), ("n_hypotheses", ctypes.c_int32),
+                ("n_inliers", ctypes.c_int32), ("seg_a", ctypes.c_int32), ("seg_b", ctypes.c_int32), ("flip", ctypes.c_int32),
+                ("status", ctypes.c_int32)]
+
+
+# the same layout as a numpy record: what LineAssociator.localize returns
+LOCALIZE_RESULT_DTYPE = [("x", "<f8"), ("y", "<f8"), ("theta", "<f8"), ("cost", "<f8"), ("n_pairs", "<i4"), ("n_candidates", "<i4"),
+                         ("n_hypotheses", "<i4"), ("n_inliers", "<i4"), ("seg_a", "<i4"), ("seg_b", "<i4"), ("flip", "<i4"), ("status", "<i4")]
 
 _lib = None
 
@@ -334,6 +355,14 @@ def load():
     lib.lf_map_step_smoothed_host.argtypes = [vp, ctypes.POINTER(LfSegments), ci, ci, vp, vp, ci, ctypes.POINTER(LfSmoothConfig), ci, vp, vp, vp, vp]
     lib.lf_map_smooth_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
     for f in ("lf_sizeof_smooth_config", "lf_map_smooth", "lf_map_step_smoothed", "lf_map_step_smoothed_host", "lf_map_smooth_timing"):
+        getattr(lib, f).restype = ci
+    lib.lf_sizeof_localize_config.argtypes = []
+    lib.lf_sizeof_localize_result.argtypes = []
+    lib.lf_map_localize_default_config.argtypes = [ctypes.POINTER(LfLocalizeConfig)]
+    lib.lf_map_localize_default_config.restype = None
+    lib.lf_map_localize.argtypes = [vp, vp, ctypes.POINTER(LfSegments), ci, ci, vp, vp, vp, ctypes.POINTER(LfLocalizeConfig), ci, vp]
+    lib.lf_map_localize_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
+    for f in ("lf_sizeof_localize_config", "lf_sizeof_localize_result", "lf_map_localize", "lf_map_localize_timing"):
         getattr(lib, f).restype = ci
     lib.lf_descriptor_default_params.argtypes = [ctypes.POINTER(LfDescriptorParams)]
     lib.lf_descriptor_default_params.restype = None

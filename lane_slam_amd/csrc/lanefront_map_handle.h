@@ -1,6 +1,6 @@
 // The live map's handle, for the translation units of lf_map_*: the map itself (lanefront_map.hip), its two views
 // (lanefront_map_render.hip, lanefront_map_camera.hip), the pose alignment (lanefront_map_align.hip) and the trajectory smoother
-// (lanefront_map_smooth.hip).
+// (lanefront_map_smooth.hip); the localisation without a prior pose (lanefront_map_localize.hip).
 #pragma once
 #include <memory>
 #include <vector>
@@ -58,17 +58,19 @@ struct lf_map : lf::Core {
     // lf_map_smooth: the chains' offsets [n_chains + 1] and each frame's chain [n_frames], the map sums [n_frames][9], the nodes
     // of the block tridiagonal systems [n_frames], the chains' states and statuses [n_chains]
     DevBuf sm_offset, sm_chain_of, sm_sums, sm_node, sm_chain, sm_status;
+    DevBuf lo_fallback, lo_res;              // lf_map_localize: the fallback poses [n_frames][3], the results [n_frames]
     std::vector<double> h_pose;
     std::vector<int32_t> h_chains;
-    // per-stage timing: the stages of lf_map_get_timing, then kMapAlignStage (lf_map_align_timing) and kMapSmoothStage
-    // (lf_map_smooth_timing); past 4096 outstanding records a bracket goes untimed
-    StageClock clock{LF_MAP_N_STAGES + 2, 4096, false};
+    // per-stage timing: the stages of lf_map_get_timing, then kMapAlignStage (lf_map_align_timing), kMapSmoothStage
+    // (lf_map_smooth_timing) and kMapLocalizeStage (lf_map_localize_timing); past 4096 outstanding records a bracket goes untimed
+    StageClock clock{LF_MAP_N_STAGES + 3, 4096, false};
     std::unique_ptr<lf::MapRenderState> render;   // lf_map_render / lf_map_bounds (lanefront_map_render.hip), made by their first call
     std::unique_ptr<lf::MapCameraState> camera;   // lf_map_render_camera (lanefront_map_camera.hip), likewise
 };
 
 constexpr int kMapAlignStage = LF_MAP_N_STAGES;
 constexpr int kMapSmoothStage = LF_MAP_N_STAGES + 1;
+constexpr int kMapLocalizeStage = LF_MAP_N_STAGES + 2;
 
 // ---- lanefront_map.hip's sequencing, for the translation unit that aligns poses before the update (lanefront_map_align.hip)
 int after_handle(lf_map* m, lf_handle* h);        // the map's stream waits for everything queued so far on the handle's stream

@@ -257,6 +257,60 @@ class LineAssociator(object):
         self._check(self.lib.lf_map_smooth_timing(self.m, ctypes.byref(ms), ctypes.byref(ln)))
         return ms.value, ln.value
 
+    # ------------------------------------------------------------------ frames localised without a prior pose (lf_map_localize)
+    def localize_config(self, **overrides):
+        """The library's default `_lib.LfLocalizeConfig` (lf_map_localize_default_config) with the overrides applied: max_pairs, flips,
+        min_inliers, min_hits, color_match, gate, min_sin, max_dist."""
+        c = _lib.LfLocalizeConfig()
+        self.lib.lf_map_localize_default_config(ctypes.byref(c))
+        kinds = dict((k, t) for k, t in _lib.LfLocalizeConfig._fields_ if k != "reserved_")
+        for k, val in overrides.items():
+            if k not in kinds:
+                raise TypeError("localize_config: unknown field %r" % (k,))
+            setattr(c, k, int(val) if kinds[k] is ctypes.c_int32 else float(val))
+        return c
+
+    def localize(self, seg, idx, dist, config=None, fallback=None, refine=None):
+        """A pose per frame from the frame's associations and the map's geometry alone (lf_map_localize): seg, idx and dist as for
+        `align`; fallback: (n_frames, 3) poses for the frames that cannot be localised, None = (0, 0, 0).  Returns (poses_out
+        (n_frames, 3) float64, results): results is a record array of `_lib.LOCALIZE_RESULT_DTYPE`, one lf_localize_result per frame
+        (status: `_lib.ALIGN_STATUS`).  refine: an `_lib.LfAlignConfig` -- `align` runs afterwards with poses_out as its poses, and
+        the call returns (aligned poses, results, align results).  The map is not changed."""
+        n, n_frames = int(seg.n), len(seg.frame_offset) - 1
+        keep_alive, pp = self._poses(fallback, n_frames)
+        s, alive = self._host_segs(seg, ("frame_offset", "color", "keep", "ground"))
+        idx = np.ascontiguousarray(idx, np.int32)
+        dist = None if dist is None else np.ascontiguousarray(dist, np.float32)
+        if len(idx) != n or (dist is not None and len(dist) != n):
+            raise ValueError("localize: idx and dist hold one value per segment")
+        config = self.localize_config() if config is None else config
+        res = np.zeros(n_frames, _lib.LOCALIZE_RESULT_DTYPE)
+        self._check(self.lib.lf_map_localize(self.m, None, ctypes.byref(s), n, n_frames, idx.ctypes.data,
+                                             None if dist is None else dist.ctypes.data, pp, ctypes.byref(config), 0, res.ctypes.data))
+        if refine is None:
+            return self._poses_out(res), res
+        poses_out, aligned = self.align(seg, idx, dist, self._poses_out(res), refine)
+        return poses_out, res, aligned
+
+    def localize_device(self, fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, config=None, fallback=None, refine=None):
+        """`localize` for a batch that is resident on the device (out_ptrs as for step_device; idx_ptr / dist_ptr device arrays)."""
+        keep_alive, pp = self._poses(fallback, int(n_frames))
+        s = self._segs(out_ptrs)
+        config = self.localize_config() if config is None else config
+        res = np.zeros(int(n_frames), _lib.LOCALIZE_RESULT_DTYPE)
+        self._check(self.lib.lf_map_localize(self.m, fe.h if fe is not None else None, ctypes.byref(s), int(n), int(n_frames), int(idx_ptr),
+                                             dist_ptr and int(dist_ptr), pp, ctypes.byref(config), 1, res.ctypes.data))
+        if refine is None:
+            return self._poses_out(res), res
+        poses_out, aligned = self.align_device(fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, self._poses_out(res), refine)
+        return poses_out, res, aligned
+
+    def localize_timing(self):
+        """(ms, launches) of the localisation kernel since the previous call (needs set_profiling(True)); resets."""
+        ms, ln = ctypes.c_double(), ctypes.c_int32()
+        self._check(self.lib.lf_map_localize_timing(self.m, ctypes.byref(ms), ctypes.byref(ln)))
+        return ms.value, ln.value
+
     @staticmethod
     def carry(poses, last_odometry, last_corrected):
         """The next batch's odometry poses (n, 3) with the previous batch's correction applied: the rigid motion that takes

@@ -5,7 +5,7 @@ receives the kept segments (append-only, src/show_map/src/show_map.py:28-42) -> 
 wire bodies.  The first batch is checked against the oracle (pixels, segments, matches); the rest is timed.
 
     python tools/replay_demo.py [--frames 1024] [--batch 128] [--threads 32] [--geometry fullres|parity] [--map-jpeg map.jpg]
-                                [--overlay-jpeg DIR]
+                                [--overlay-jpeg DIR] [--align | --smooth | --localize]
 
 --map-jpeg writes the final map as the reference's README shows it (show_map's coloured segments seen from above, lf_map_render
 fitted to the map) as a JPEG: rendered and encoded on the device, only the file's bytes cross the bus.
@@ -38,6 +38,10 @@ mode.add_argument("--smooth", action="store_true",
                   help="smooth every batch's poses against the map before the update (lf_map_step_smoothed, the default configuration, one "
                        "chain per batch), carry each batch's correction into the next batch's poses (LineAssociator.carry) and print, per "
                        "batch, how many frames came back with each status")
+mode.add_argument("--localize", action="store_true",
+                  help="localise every batch's frames against the map without a prior pose (lf_map_localize, the default configuration, the "
+                       "previous batch's last corrected pose as fallback), correct the localised poses (lf_map_step_aligned) and print, per "
+                       "batch, how many frames came back with each status and the inlying endpoints of the localised ones")
 mode.add_argument("--align", action="store_true",
                 help="correct every batch's poses against the map before the update (lf_map_step_aligned, the default configuration) and "
                      "print, per batch, how many frames came back with each status")
@@ -97,6 +101,18 @@ for b0 in range(0, args.frames - B + 1, B):
             last_odometry, last_corrected = (0.0, 0.0, 0.0), tuple(out[2][-1])
             counts = np.bincount(out[3]["status"], minlength=4)
             print("batch %d smoothed: %s" % (b0 // B, ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, counts))))
+        elif args.localize:
+            # (the replay has no odometry, and needs none here: associate, localise from the associations and the map's geometry, then
+            # correct the localised poses and update the map with them; the seeded codes have no place, so the first batch falls back)
+            live.associate_device(None, ptrs["code"], ptrs["color"], seg.n, di.data_ptr(), dd.data_ptr())
+            located, loc = live.localize_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), fallback=np.tile(last_corrected, (B, 1)))
+            out = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=located, step=b0 // B, align=live.align_config())
+            last_corrected = tuple(out[2][-1])
+            counts, found = np.bincount(loc["status"], minlength=4), loc["n_inliers"][loc["status"] == 0]
+            print("batch %d localised: %s; inliers of the ok frames %s; aligned: %s"
+                  % (b0 // B, ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, counts)),
+                     "min %d median %d max %d" % (found.min(), np.median(found), found.max()) if len(found) else "-",
+                     ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, np.bincount(out[3]["status"], minlength=4)))))
         elif args.align:
             # (the replay has no odometry: every prior is the identity, and the seeded map has no geometry to align with)
             res = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=np.zeros((B, 3)), step=b0 // B,
