@@ -33,8 +33,10 @@ __global__ __launch_bounds__(kPartials) void k_map_align(lf_align_config c, MapD
 {
     const int f = blockIdx.x, lane = threadIdx.x;
     if (f >= b.n_frames) return;
-    int size = md.state[0];
-    if (size > md.capacity) size = md.capacity;
+    const int size = map_size(md);
+    const PairRule rule = { c.min_hits, c.color_match, c.max_dist };
+    // frame_range's statements, spelled out: through the helper the register allocator ends two VGPRs above 128 and the kernel
+    // one wave per SIMD lower
     int o0 = 0, o1 = 0;
     if (b.frame_offset && b.n > 0) {
         o0 = b.frame_offset[f]; o1 = b.frame_offset[f + 1];
@@ -46,8 +48,8 @@ __global__ __launch_bounds__(kPartials) void k_map_align(lf_align_config c, MapD
     // the lane's first segment stays in registers; the pairs of the frame are counted once
     Pair first = no_pair();
     int mine = 0;
-    if (o0 + lane < o1) { first = gather(c, md, b, o0 + lane, size); mine = first.ok ? 1 : 0; }
-    for (int i = o0 + lane + kPartials; i < o1; i += kPartials) mine += gather(c, md, b, i, size).ok ? 1 : 0;
+    if (o0 + lane < o1) { first = gather(rule, md, b, o0 + lane, size); mine = first.ok ? 1 : 0; }
+    for (int i = o0 + lane + kPartials; i < o1; i += kPartials) mine += gather(rule, md, b, i, size).ok ? 1 : 0;
     const int n_pairs = fold(mine);
 
     double x = x0, y = y0, th = th0, cost0 = 0.0, cost = 0.0;
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(kPartials) void k_map_align(lf_align_config c, MapD
         Sums s;
         clear(s);
         add_pair(s, c, first, x, y, sn, cs);
-        for (int i = o0 + lane + kPartials; i < o1; i += kPartials) add_pair(s, c, gather(c, md, b, i, size), x, y, sn, cs);
+        for (int i = o0 + lane + kPartials; i < o1; i += kPartials) add_pair(s, c, gather(rule, md, b, i, size), x, y, sn, cs);
         fold(s);
         if (k == 0) cost0 = s.cost;
         cost = s.cost; n_used = s.used;

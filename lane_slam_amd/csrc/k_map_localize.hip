@@ -24,8 +24,7 @@ namespace {
 constexpr int kWaves = kThreads / 64;
 constexpr int kNoH = 0x7fffffff;
 
-// a candidate: the eight doubles of ma::Pair
-struct Cand { double px0, py0, px1, py1, nx, ny, ax, ay; };
+using Cand = ma::Line;                 // a candidate: the eight doubles of its ma::Pair
 struct Pose { double tx, ty, cs, sn; };
 
 // the contract's c_k of the translation
@@ -83,16 +82,10 @@ __global__ __launch_bounds__(kThreads) void k_map_localize(lf_localize_config c,
     __shared__ int red_inl[kWaves], red_h[kWaves], red_valid[kWaves];
 
     const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int size = md.state[0];
-    if (size > md.capacity) size = md.capacity;
-    int o0 = 0, o1 = 0;
-    if (b.a.frame_offset && b.a.n > 0) {
-        o0 = b.a.frame_offset[f]; o1 = b.a.frame_offset[f + 1];
-        o0 = o0 < 0 ? 0 : (o0 > b.a.n ? b.a.n : o0);
-        o1 = o1 < o0 ? o0 : (o1 > b.a.n ? b.a.n : o1);
-    }
-    lf_align_config ac = {};                    // what ma::gather reads of it
-    ac.min_hits = c.min_hits; ac.color_match = c.color_match; ac.max_dist = c.max_dist;
+    const int size = ma::map_size(md);
+    const ma::PairRule rule = { c.min_hits, c.color_match, c.max_dist };
+    int o0, o1;
+    ma::frame_range(b.a, f, o0, o1);
     const int max_pairs = c.max_pairs < kMaxPairs ? c.max_pairs : kMaxPairs;
 
     // ---- 1: the candidates, in increasing segment index
@@ -100,7 +93,7 @@ __global__ __launch_bounds__(kThreads) void k_map_localize(lf_localize_config c,
     for (int i0 = o0; i0 < o1; i0 += kThreads) {
         const int i = i0 + t;
         ma::Pair p = ma::no_pair();
-        if (i < o1) p = ma::gather(ac, md, b.a, i, size);
+        if (i < o1) p = ma::gather(rule, md, b.a, i, size);
         const unsigned long long mask = __ballot(p.ok);
         if (lane == 0) wave_pairs[wave] = __popcll(mask);
         __syncthreads();
@@ -113,9 +106,7 @@ __global__ __launch_bounds__(kThreads) void k_map_localize(lf_localize_config c,
         }
         place += __popcll(mask & ((1ull << lane) - 1ull));
         if (p.ok && place < max_pairs) {
-            Cand k;
-            k.px0 = p.px0; k.py0 = p.py0; k.px1 = p.px1; k.py1 = p.py1; k.nx = p.nx; k.ny = p.ny; k.ax = p.ax; k.ay = p.ay;
-            cand[place] = k;
+            cand[place] = p;
             cand_seg[place] = i;
         }
         n_pairs += all;

@@ -1,6 +1,7 @@
 // The device statements lf_map_align and lf_map_smooth share (include/lanefront.h "lf_map_align" is their contract): a frame's
 // pairs, an endpoint's contribution to the partial sums, the fold of the 64 partials and the 3 x 3 LDL^T.  k_map_align.hip and
-// k_map_smooth.hip include it and run the same statements; both are built with -ffp-contract=off.
+// k_map_smooth.hip include it and run the same statements; k_map_localize.hip takes the map's size, the frame's range and the
+// pairs from it.  All three are built with -ffp-contract=off.
 #pragma once
 #include "detmath.h"
 #include "k_map_align.h"
@@ -8,7 +9,11 @@
 namespace lf {
 namespace ma {
 
-struct Pair { double px0, py0, px1, py1, nx, ny, ax, ay; bool ok; };
+// a segment's endpoints, its matched entry's unit normal and first endpoint
+struct Line { double px0, py0, px1, py1, nx, ny, ax, ay; };
+struct Pair : Line { bool ok; };
+// what decides whether a segment and its matched entry make a pair (lf_align_config's and lf_localize_config's fields)
+struct PairRule { int min_hits, color_match; double max_dist; };
 struct Sums { double n00, n01, n02, n11, n12, n22, g0, g1, g2, cost; int used; };
 // the factor of a 3 x 3 symmetric matrix, as the contract's solve names its parts
 struct Ldl { double d0, d1, d2, l10, l20, l21; };
@@ -29,7 +34,26 @@ __device__ __forceinline__ void clear(Sums& s)
     s.used = 0;
 }
 
-__device__ __forceinline__ Pair gather(const lf_align_config& c, const MapDevice& md, const Batch& b, int i, int size)
+// the map's size, never beyond its capacity
+__device__ __forceinline__ int map_size(const MapDevice& md)
+{
+    int size = md.state[0];
+    if (size > md.capacity) size = md.capacity;
+    return size;
+}
+
+// frame f's segments [o0, o1), clamped to the batch; no frame_offset or no segments: empty
+__device__ __forceinline__ void frame_range(const Batch& b, int f, int& o0, int& o1)
+{
+    o0 = 0; o1 = 0;
+    if (b.frame_offset && b.n > 0) {
+        o0 = b.frame_offset[f]; o1 = b.frame_offset[f + 1];
+        o0 = o0 < 0 ? 0 : (o0 > b.n ? b.n : o0);
+        o1 = o1 < o0 ? o0 : (o1 > b.n ? b.n : o1);
+    }
+}
+
+__device__ __forceinline__ Pair gather(const PairRule& c, const MapDevice& md, const Batch& b, int i, int size)
 {
     Pair p = no_pair();
     const int t = b.idx[i];

@@ -193,14 +193,10 @@ __global__ __launch_bounds__(ma::kPartials) void k_map_smooth_sums(lf_align_conf
     const int f = blockIdx.x, lane = threadIdx.x;
     if (f >= b.a.n_frames) return;
     if (b.chain[b.chain_of[f]].stopped) return;
-    int size = md.state[0];
-    if (size > md.capacity) size = md.capacity;
-    int o0 = 0, o1 = 0;
-    if (b.a.frame_offset && b.a.n > 0) {
-        o0 = b.a.frame_offset[f]; o1 = b.a.frame_offset[f + 1];
-        o0 = o0 < 0 ? 0 : (o0 > b.a.n ? b.a.n : o0);
-        o1 = o1 < o0 ? o0 : (o1 > b.a.n ? b.a.n : o1);
-    }
+    const int size = ma::map_size(md);
+    const ma::PairRule rule = { c.min_hits, c.color_match, c.max_dist };
+    int o0, o1;
+    ma::frame_range(b.a, f, o0, o1);
     lf_align_result* res = b.a.res + f;
     double x, y, th;
     if (k == 0) { x = b.a.pose0[3 * f]; y = b.a.pose0[3 * f + 1]; th = b.a.pose0[3 * f + 2]; }
@@ -211,7 +207,7 @@ __global__ __launch_bounds__(ma::kPartials) void k_map_smooth_sums(lf_align_conf
     ma::clear(s);
     int mine = 0;
     for (int i = o0 + lane; i < o1; i += ma::kPartials) {
-        const ma::Pair p = ma::gather(c, md, b.a, i, size);
+        const ma::Pair p = ma::gather(rule, md, b.a, i, size);
         mine += p.ok ? 1 : 0;
         ma::add_pair(s, c, p, x, y, sn, cs);
     }

@@ -71,13 +71,15 @@ extern "C" int lf_map_set_profiling(lf_map* m, int enabled)
     return LF_OK;
 }
 
-// the alignment kernel's stage (lanefront_map_align.hip), kept apart from lf_map_get_timing's table
-extern "C" int lf_map_align_timing(lf_map* m, double* ms, int32_t* launches)
+int take_stage(lf_map* m, int stage, double* ms, int32_t* launches)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    m->clock.take(ms, launches, 1, kMapAlignStage, 1);
+    m->clock.take(ms, launches, 1, stage, 1);
     return LF_OK;
 }
+
+// the alignment kernel's stage (lanefront_map_align.hip), kept apart from lf_map_get_timing's table
+extern "C" int lf_map_align_timing(lf_map* m, double* ms, int32_t* launches) { return take_stage(m, kMapAlignStage, ms, launches); }
 
 // ms accumulated and launches counted per stage since the last call; resets both
 extern "C" int lf_map_get_timing(lf_map* m, double* ms_per_stage, int32_t* launches_per_stage, int n)
@@ -387,31 +389,9 @@ extern "C" int lf_map_step_host(lf_map* m, const lf_segments* segs, int n, int n
         set_error(m, LF_ERR_BAD_ARG, "lf_map_step_host: bad argument (frame_offset and code are required, color when gating is on)");
         return LF_ERR_BAD_ARG;
     }
-    LF_HIP_CHECK(m, hipSetDevice(m->device));
-    hipStream_t s = m->stream;
-    int rc;
-    const size_t c = (size_t)(n > 0 ? n : 1);
-    if ((rc = scratch(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = scratch(m, m->st_code, c * 32)) || (rc = scratch(m, m->st_color, c)) ||
-        (rc = scratch(m, m->st_keep, c)) || (rc = scratch(m, m->st_ground, c * 32)) || (rc = scratch(m, m->st_idx, c * 4)) || (rc = scratch(m, m->st_dist, c * 4))) return rc;
-    lf_segments d;
-    memset(&d, 0, sizeof(d));
-    LF_HIP_CHECK(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
-    d.frame_offset = static_cast<int32_t*>(m->st_fo.p);
-    if (n > 0) {
-        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_code.p, segs->code, (size_t)n * 32, hipMemcpyHostToDevice, s));
-        d.code = static_cast<uint8_t*>(m->st_code.p);
-        if (segs->color) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_color.p, segs->color, (size_t)n, hipMemcpyHostToDevice, s)); d.color = static_cast<uint8_t*>(m->st_color.p); }
-        if (segs->keep) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_keep.p, segs->keep, (size_t)n, hipMemcpyHostToDevice, s)); d.keep = static_cast<uint8_t*>(m->st_keep.p); }
-        if (segs->ground) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_ground.p, segs->ground, (size_t)n * 32, hipMemcpyHostToDevice, s)); d.ground = static_cast<double*>(m->st_ground.p); }
-    }
-    rc = lf_map_step(m, nullptr, &d, n, n_frames, frame_pose, step, static_cast<int32_t*>(m->st_idx.p), static_cast<float*>(m->st_dist.p));
-    if (rc != LF_OK) return rc;
-    if (n > 0) {
-        LF_HIP_CHECK(m, hipMemcpyAsync(idx, m->st_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(m, hipMemcpyAsync(dist, m->st_dist.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    }
-    LF_HIP_CHECK(m, hipStreamSynchronize(s));
-    return LF_OK;
+    return step_from_host(m, segs, n, n_frames, idx, dist, [&](const lf_segments* d, int32_t* d_idx, float* d_dist) {
+        return lf_map_step(m, nullptr, d, n, n_frames, frame_pose, step, d_idx, d_dist);
+    });
 }
 
 extern "C" int lf_map_fetch(lf_map* m, int first, int n, uint8_t* code32, uint8_t* color, double* ground4, int32_t* hits,

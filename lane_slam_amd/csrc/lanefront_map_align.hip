@@ -1,6 +1,8 @@
 // lanefront C ABI, a batch's poses corrected against the live map (include/lanefront.h "lf_map_align"): the checks, the staging of
 // host arrays and the sequencing of k_map_align.hip on the map's stream, between association and update.  The corrected poses
 // never visit the host on their way to the packing kernel: the alignment kernel writes them where that kernel reads them.
+// Also the home of what the map's pose solvers share (lanefront_map_handle.h): their front end, the body of the solving steps
+// and the steps' host-form wrapper.
 #include <math.h>
 #include <string.h>
 #include "lanefront_map_handle.h"
@@ -20,20 +22,35 @@ const char* bad_config(const lf_align_config* c)
 
 }  // namespace
 
+int solver_check_call(lf_map* m, const char* who, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const double* pose,
+                      bool pose_required, bool has_cfg, const void* results)
+{
+    if (!segs || (pose_required && !pose) || !has_cfg || !results) {
+        set_error(m, LF_ERR_BAD_ARG, "%s: null segs, %scfg or results", who, pose_required ? "frame_pose, " : "");
+        return LF_ERR_BAD_ARG;
+    }
+    if (n < 0 || n_frames < 1 || n_frames > ma::kMaxFrames) { set_error(m, LF_ERR_BAD_ARG, "%s: n < 0 or n_frames outside 1 .. %d", who, ma::kMaxFrames); return LF_ERR_BAD_ARG; }
+    if (n > 0 && (!segs->frame_offset || !segs->ground || !idx)) { set_error(m, LF_ERR_BAD_ARG, "%s: frame_offset, ground and idx are required", who); return LF_ERR_BAD_ARG; }
+    for (int k = 0; pose && k < 3 * n_frames; ++k)
+        if (!isfinite(pose[k])) { set_error(m, LF_ERR_BAD_ARG, "%s: the %spose of frame %d is not finite", who, pose_required ? "" : "fallback ", k / 3); return LF_ERR_BAD_ARG; }
+    return LF_OK;
+}
+
 int align_check_call(lf_map* m, const char* who, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const double* frame_pose,
                      const lf_align_config* cfg, const void* results)
 {
-    if (!segs || !frame_pose || !cfg || !results) { set_error(m, LF_ERR_BAD_ARG, "%s: null segs, frame_pose, cfg or results", who); return LF_ERR_BAD_ARG; }
-    if (n < 0 || n_frames < 1 || n_frames > ma::kMaxFrames) { set_error(m, LF_ERR_BAD_ARG, "%s: n < 0 or n_frames outside 1 .. %d", who, ma::kMaxFrames); return LF_ERR_BAD_ARG; }
-    if (n > 0 && (!segs->frame_offset || !segs->ground || !idx)) { set_error(m, LF_ERR_BAD_ARG, "%s: frame_offset, ground and idx are required", who); return LF_ERR_BAD_ARG; }
-    for (int k = 0; k < 3 * n_frames; ++k)
-        if (!isfinite(frame_pose[k])) { set_error(m, LF_ERR_BAD_ARG, "%s: the pose of frame %d is not finite", who, k / 3); return LF_ERR_BAD_ARG; }
+    int rc;
+    if ((rc = solver_check_call(m, who, segs, n, n_frames, idx, frame_pose, true, cfg != nullptr, results)) != LF_OK) return rc;
     if (const char* why = bad_config(cfg)) { set_error(m, LF_ERR_BAD_ARG, "%s: bad configuration (%s)", who, why); return LF_ERR_BAD_ARG; }
     return LF_OK;
 }
 
-int align_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist, lf_segments* d,
-                     const int32_t** didx, const float** ddist)
+namespace {
+
+// queue the copies of the host arrays a solver reads (frame_offset, ground, color, keep, idx, dist) into the map's staging
+// buffers; d, didx and ddist then name the device copies
+int solver_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist, lf_segments* d,
+                      const int32_t** didx, const float** ddist)
 {
     int rc;
     hipStream_t s = m->stream;
@@ -52,6 +69,8 @@ int align_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, co
     return LF_OK;
 }
 
+// the staging of a step's host form: frame_offset and, of code, color, keep and ground, those present go up; st_idx and st_dist
+// are sized
 int step_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, lf_segments* d)
 {
     int rc;
@@ -65,30 +84,107 @@ int step_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, lf_
     if (n > 0) {
         LF_HIP_CHECK(m, hipMemcpyAsync(m->st_code.p, segs->code, (size_t)n * 32, hipMemcpyHostToDevice, s));
         d->code = static_cast<uint8_t*>(m->st_code.p);
-        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_ground.p, segs->ground, (size_t)n * 32, hipMemcpyHostToDevice, s));
-        d->ground = static_cast<double*>(m->st_ground.p);
         if (segs->color) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_color.p, segs->color, (size_t)n, hipMemcpyHostToDevice, s)); d->color = static_cast<uint8_t*>(m->st_color.p); }
         if (segs->keep) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_keep.p, segs->keep, (size_t)n, hipMemcpyHostToDevice, s)); d->keep = static_cast<uint8_t*>(m->st_keep.p); }
+        if (segs->ground) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_ground.p, segs->ground, (size_t)n * 32, hipMemcpyHostToDevice, s)); d->ground = static_cast<double*>(m->st_ground.p); }
     }
+    return LF_OK;
+}
+
+}  // namespace
+
+ma::Batch batch_view(const lf_segments* d, int n, int n_frames, const int32_t* idx, const float* dist)
+{
+    ma::Batch b = {};
+    b.frame_offset = n > 0 ? d->frame_offset : nullptr; b.ground = d->ground; b.color = d->color; b.keep = d->keep;
+    b.idx = idx; b.dist = dist; b.n = n; b.n_frames = n_frames;
+    return b;
+}
+
+int open_batch(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist, int on_device,
+               ma::Batch* b)
+{
+    int rc;
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
+    if ((rc = after_handle(m, h)) != LF_OK) return rc;
+    lf_segments d;
+    memset(&d, 0, sizeof(d));
+    if (on_device) {
+        d.frame_offset = segs->frame_offset; d.ground = segs->ground; d.color = segs->color; d.keep = segs->keep;
+    } else if (n > 0) {
+        if ((rc = solver_stage_host(m, segs, n, n_frames, idx, dist, &d, &idx, &dist)) != LF_OK) return rc;
+    }
+    *b = batch_view(&d, n, n_frames, idx, dist);
+    return LF_OK;
+}
+
+int upload_prior_pose(lf_map* m, const double* pose, int n_frames, const double** d_pose)
+{
+    int rc;
+    const size_t bytes = (size_t)n_frames * 3 * sizeof(double);
+    if ((rc = scratch(m, m->prior_pose, bytes)) != LF_OK) return rc;
+    if (pose) LF_HIP_CHECK(m, hipMemcpyAsync(m->prior_pose.p, pose, bytes, hipMemcpyHostToDevice, m->stream));
+    else LF_HIP_CHECK(m, hipMemsetAsync(m->prior_pose.p, 0, bytes, m->stream));
+    *d_pose = static_cast<const double*>(m->prior_pose.p);
+    return LF_OK;
+}
+
+int fetch_results(lf_map* m, void* dst, const DevBuf& src, size_t bytes, void* dst2, const DevBuf* src2, size_t bytes2)
+{
+    LF_HIP_CHECK(m, hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, m->stream));
+    if (dst2) LF_HIP_CHECK(m, hipMemcpyAsync(dst2, src2->p, bytes2, hipMemcpyDeviceToHost, m->stream));
+    LF_HIP_CHECK(m, hipStreamSynchronize(m->stream));
+    return LF_OK;
+}
+
+int step_solved(lf_map* m, lf_handle* h, const char* who, const lf_segments* segs, int n, int n_frames, int step, int32_t* idx, float* dist,
+                const std::function<int(const ma::Batch&)>& queue_solver)
+{
+    int rc;
+    if (n > 0 && (!dist || !segs->code)) { set_error(m, LF_ERR_BAD_ARG, "%s: code and dist are required", who); return LF_ERR_BAD_ARG; }
+    if (n > 0 && (rc = lf_map_associate(m, h, segs->code, segs->color, n, idx, dist, 1)) != LF_OK) return rc;
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
+    if ((rc = scratch(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) != LF_OK) return rc;
+    if ((rc = after_handle(m, h)) != LF_OK) return rc;
+    if ((rc = queue_solver(batch_view(segs, n, n_frames, idx, dist))) != LF_OK) return rc;
+    {
+        StageClock::Scope t(m, m->clock, 2);
+        launch_map_pack_block(n, n_frames, n > 0 ? segs->frame_offset : nullptr, segs->code, segs->color, segs->keep, segs->ground, idx, dist,
+                              static_cast<const double*>(m->pose.p), step, static_cast<uint8_t*>(m->own_block.p), m->stream);
+    }
+    LF_HIP_CHECK(m, hipGetLastError());
+    if ((rc = release_handle(m, h)) != LF_OK) return rc;
+    if (n > 0 && (rc = update_blocks(m, static_cast<const uint8_t*>(m->own_block.p), 1, n + 1, 0, n)) != LF_OK) return rc;
+    return LF_OK;
+}
+
+int step_from_host(lf_map* m, const lf_segments* segs, int n, int n_frames, int32_t* idx, float* dist,
+                   const std::function<int(const lf_segments* d, int32_t* d_idx, float* d_dist)>& device_form)
+{
+    int rc;
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    lf_segments d;
+    memset(&d, 0, sizeof(d));
+    if ((rc = step_stage_host(m, segs, n, n_frames, &d)) != LF_OK) return rc;
+    if ((rc = device_form(&d, static_cast<int32_t*>(m->st_idx.p), static_cast<float*>(m->st_dist.p))) != LF_OK) return rc;
+    if (n > 0) {
+        LF_HIP_CHECK(m, hipMemcpyAsync(idx, m->st_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        LF_HIP_CHECK(m, hipMemcpyAsync(dist, m->st_dist.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    }
+    LF_HIP_CHECK(m, hipStreamSynchronize(s));
     return LF_OK;
 }
 
 namespace {
 
-// queue the alignment of device arrays on the map's stream: the prior poses go up, m->pose receives x, y, cos, sin per frame and
+// queue the alignment of a batch view on the map's stream: the prior poses go up, m->pose receives x, y, cos, sin per frame and
 // m->al_res the results
-int queue_align(lf_map* m, const lf_segments* d, int n, int n_frames, const int32_t* idx, const float* dist, const double* frame_pose,
-                const lf_align_config* cfg)
+int queue_align(lf_map* m, ma::Batch b, const double* frame_pose, const lf_align_config* cfg)
 {
     int rc;
-    if ((rc = scratch(m, m->al_pose0, (size_t)n_frames * 3 * sizeof(double))) || (rc = scratch(m, m->pose, (size_t)n_frames * 4 * sizeof(double))) ||
-        (rc = scratch(m, m->al_res, (size_t)n_frames * sizeof(lf_align_result)))) return rc;
-    // (every call that queues this copy waits for the stream before it returns: frame_pose has left the host by then)
-    LF_HIP_CHECK(m, hipMemcpyAsync(m->al_pose0.p, frame_pose, (size_t)n_frames * 3 * sizeof(double), hipMemcpyHostToDevice, m->stream));
-    ma::Batch b;
-    b.frame_offset = n > 0 ? d->frame_offset : nullptr; b.ground = d->ground; b.color = d->color; b.keep = d->keep;
-    b.idx = idx; b.dist = dist; b.n = n; b.n_frames = n_frames;
-    b.pose0 = static_cast<const double*>(m->al_pose0.p);
+    if ((rc = upload_prior_pose(m, frame_pose, b.n_frames, &b.pose0)) || (rc = scratch(m, m->pose, (size_t)b.n_frames * 4 * sizeof(double))) ||
+        (rc = scratch(m, m->al_res, (size_t)b.n_frames * sizeof(lf_align_result)))) return rc;
     b.pose4 = static_cast<double*>(m->pose.p);
     b.res = static_cast<lf_align_result*>(m->al_res.p);
     {
@@ -96,13 +192,6 @@ int queue_align(lf_map* m, const lf_segments* d, int n, int n_frames, const int3
         ma::launch_align(*cfg, m->d, b, m->stream);
     }
     LF_HIP_CHECK(m, hipGetLastError());
-    return LF_OK;
-}
-
-int fetch_results(lf_map* m, int n_frames, lf_align_result* results)
-{
-    LF_HIP_CHECK(m, hipMemcpyAsync(results, m->al_res.p, (size_t)n_frames * sizeof(lf_align_result), hipMemcpyDeviceToHost, m->stream));
-    LF_HIP_CHECK(m, hipStreamSynchronize(m->stream));
     return LF_OK;
 }
 
@@ -126,21 +215,12 @@ extern "C" int lf_map_align(lf_map* m, lf_handle* h, const lf_segments* segs, in
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
     int rc;
+    ma::Batch b;
     if ((rc = align_check_call(m, "lf_map_align", segs, n, n_frames, idx, frame_pose, cfg, results)) != LF_OK) return rc;
-    LF_HIP_CHECK(m, hipSetDevice(m->device));
-    if ((rc = after_handle(m, h)) != LF_OK) return rc;
-    lf_segments d;
-    memset(&d, 0, sizeof(d));
-    const int32_t* didx = idx;
-    const float* ddist = dist;
-    if (on_device) {
-        d.frame_offset = segs->frame_offset; d.ground = segs->ground; d.color = segs->color; d.keep = segs->keep;
-    } else if (n > 0) {
-        if ((rc = align_stage_host(m, segs, n, n_frames, idx, dist, &d, &didx, &ddist)) != LF_OK) return rc;
-    }
-    if ((rc = queue_align(m, &d, n, n_frames, didx, ddist, frame_pose, cfg)) != LF_OK) return rc;
+    if ((rc = open_batch(m, h, segs, n, n_frames, idx, dist, on_device, &b)) != LF_OK) return rc;
+    if ((rc = queue_align(m, b, frame_pose, cfg)) != LF_OK) return rc;
     if ((rc = release_handle(m, h)) != LF_OK) return rc;
-    return fetch_results(m, n_frames, results);
+    return fetch_results(m, results, m->al_res, (size_t)n_frames * sizeof(lf_align_result));
 }
 
 extern "C" int lf_map_step_aligned(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const double* frame_pose,
@@ -149,21 +229,10 @@ extern "C" int lf_map_step_aligned(lf_map* m, lf_handle* h, const lf_segments* s
     if (!m) return LF_ERR_NOT_INITIALISED;
     int rc;
     if ((rc = align_check_call(m, "lf_map_step_aligned", segs, n, n_frames, idx, frame_pose, cfg, results)) != LF_OK) return rc;
-    if (n > 0 && (!dist || !segs->code)) { set_error(m, LF_ERR_BAD_ARG, "lf_map_step_aligned: code and dist are required"); return LF_ERR_BAD_ARG; }
-    if (n > 0 && (rc = lf_map_associate(m, h, segs->code, segs->color, n, idx, dist, 1)) != LF_OK) return rc;
-    LF_HIP_CHECK(m, hipSetDevice(m->device));
-    if ((rc = scratch(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) != LF_OK) return rc;
-    if ((rc = after_handle(m, h)) != LF_OK) return rc;
-    if ((rc = queue_align(m, segs, n, n_frames, idx, dist, frame_pose, cfg)) != LF_OK) return rc;
-    {
-        StageClock::Scope t(m, m->clock, 2);
-        launch_map_pack_block(n, n_frames, n > 0 ? segs->frame_offset : nullptr, segs->code, segs->color, segs->keep, segs->ground, idx, dist,
-                              static_cast<const double*>(m->pose.p), step, static_cast<uint8_t*>(m->own_block.p), m->stream);
-    }
-    LF_HIP_CHECK(m, hipGetLastError());
-    if ((rc = release_handle(m, h)) != LF_OK) return rc;
-    if (n > 0 && (rc = update_blocks(m, static_cast<const uint8_t*>(m->own_block.p), 1, n + 1, 0, n)) != LF_OK) return rc;
-    return fetch_results(m, n_frames, results);
+    rc = step_solved(m, h, "lf_map_step_aligned", segs, n, n_frames, step, idx, dist,
+                     [&](const ma::Batch& b) { return queue_align(m, b, frame_pose, cfg); });
+    if (rc != LF_OK) return rc;
+    return fetch_results(m, results, m->al_res, (size_t)n_frames * sizeof(lf_align_result));
 }
 
 extern "C" int lf_map_step_aligned_host(lf_map* m, const lf_segments* segs, int n, int n_frames, const double* frame_pose,
@@ -176,17 +245,7 @@ extern "C" int lf_map_step_aligned_host(lf_map* m, const lf_segments* segs, int 
         set_error(m, LF_ERR_BAD_ARG, "lf_map_step_aligned_host: bad argument (frame_offset, code and dist are required, color when gating is on)");
         return LF_ERR_BAD_ARG;
     }
-    LF_HIP_CHECK(m, hipSetDevice(m->device));
-    hipStream_t s = m->stream;
-    lf_segments d;
-    memset(&d, 0, sizeof(d));
-    if ((rc = step_stage_host(m, segs, n, n_frames, &d)) != LF_OK) return rc;
-    rc = lf_map_step_aligned(m, nullptr, &d, n, n_frames, frame_pose, cfg, step, static_cast<int32_t*>(m->st_idx.p), static_cast<float*>(m->st_dist.p), results);
-    if (rc != LF_OK) return rc;
-    if (n > 0) {
-        LF_HIP_CHECK(m, hipMemcpyAsync(idx, m->st_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(m, hipMemcpyAsync(dist, m->st_dist.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    }
-    LF_HIP_CHECK(m, hipStreamSynchronize(s));
-    return LF_OK;
+    return step_from_host(m, segs, n, n_frames, idx, dist, [&](const lf_segments* d, int32_t* d_idx, float* d_dist) {
+        return lf_map_step_aligned(m, nullptr, d, n, n_frames, frame_pose, cfg, step, d_idx, d_dist, results);
+    });
 }

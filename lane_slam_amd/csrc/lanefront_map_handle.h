@@ -1,10 +1,14 @@
 // The live map's handle, for the translation units of lf_map_*: the map itself (lanefront_map.hip), its two views
 // (lanefront_map_render.hip, lanefront_map_camera.hip), the pose alignment (lanefront_map_align.hip) and the trajectory smoother
-// (lanefront_map_smooth.hip); the localisation without a prior pose (lanefront_map_localize.hip).
+// (lanefront_map_smooth.hip); the localisation without a prior pose (lanefront_map_localize.hip).  The three pose solvers share one
+// front end (argument check, batch opener, prior-pose upload, result fetch) and the two solving steps one body and, with
+// lf_map_step_host, one host-form wrapper: all of it lives in lanefront_map_align.hip and is declared at the end of this file.
 #pragma once
+#include <functional>
 #include <memory>
 #include <vector>
 #include "lanefront_core.h"
+#include "k_map_align.h"
 
 namespace lf {
 
@@ -53,12 +57,13 @@ struct lf_map : lf::Core {
     long long rows_in_flight = 0;            // rows handed to updates whose state copy has not been seen yet
     AssocScratch ws;
     DevBuf act, own_block, pose, q_in, c_in, idx_out, dist_out, seed_code, seed_color, seed_ground, tie_res;
-    DevBuf st_fo, st_code, st_color, st_keep, st_ground, st_idx, st_dist;     // staging of lf_map_step_host and of lf_map_align's host arrays
-    DevBuf al_pose0, al_res;                 // lf_map_align: the prior poses [n_frames][3], the results [n_frames]
+    DevBuf st_fo, st_code, st_color, st_keep, st_ground, st_idx, st_dist;     // staging of the host-form steps and of the solvers' host arrays
+    DevBuf prior_pose;                       // the solvers' prior (localize: fallback) poses [n_frames][3]; one solver runs per call
+    DevBuf al_res;                           // lf_map_align, lf_map_smooth: the results [n_frames]
     // lf_map_smooth: the chains' offsets [n_chains + 1] and each frame's chain [n_frames], the map sums [n_frames][9], the nodes
     // of the block tridiagonal systems [n_frames], the chains' states and statuses [n_chains]
     DevBuf sm_offset, sm_chain_of, sm_sums, sm_node, sm_chain, sm_status;
-    DevBuf lo_fallback, lo_res;              // lf_map_localize: the fallback poses [n_frames][3], the results [n_frames]
+    DevBuf lo_res;                           // lf_map_localize: the results [n_frames]
     std::vector<double> h_pose;
     std::vector<int32_t> h_chains;
     // per-stage timing: the stages of lf_map_get_timing, then kMapAlignStage (lf_map_align_timing), kMapSmoothStage
@@ -72,19 +77,41 @@ constexpr int kMapAlignStage = LF_MAP_N_STAGES;
 constexpr int kMapSmoothStage = LF_MAP_N_STAGES + 1;
 constexpr int kMapLocalizeStage = LF_MAP_N_STAGES + 2;
 
-// ---- lanefront_map.hip's sequencing, for the translation unit that aligns poses before the update (lanefront_map_align.hip)
+// ---- lanefront_map.hip's sequencing, for the translation units of the pose solvers
 int after_handle(lf_map* m, lf_handle* h);        // the map's stream waits for everything queued so far on the handle's stream
 int release_handle(lf_map* m, lf_handle* h);      // the handle's later work waits for what the map has queued so far
 // rows_hint: how many segment rows the blocks really hold when the host knows it (-1: assume they are full)
 int update_blocks(lf_map* m, const uint8_t* blocks, int n_blocks, int block_rows, int force_append, long long rows_hint = -1);
+// one stage of the map's clock since the previous call; resets it (the three lf_map_*_timing exports)
+int take_stage(lf_map* m, int stage, double* ms, int32_t* launches);
 
-// ---- lanefront_map_align.hip's checks and staging, shared with the smoother (lanefront_map_smooth.hip)
-// LF_ERR_BAD_ARG with the reason in the map's error text, or LF_OK; nothing is touched
+// ---- the pose solvers' front end (lanefront_map_align.hip), shared by lf_map_align, lf_map_smooth and lf_map_localize
+// what the three calls check alike; LF_ERR_BAD_ARG with the reason in the map's error text, or LF_OK; nothing is touched.
+// pose_required: pose is the caller's frame_pose and must be there; otherwise it is localize's fallback pose and may be null.
+// has_cfg: the caller's cfg pointer is not null.  The configuration's own checks follow in the caller.
+int solver_check_call(lf_map* m, const char* who, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const double* pose,
+                      bool pose_required, bool has_cfg, const void* results);
+// solver_check_call for frame_pose, then the alignment configuration's checks (the aligner's calls and the smoother's)
 int align_check_call(lf_map* m, const char* who, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const double* frame_pose,
                      const lf_align_config* cfg, const void* results);
-// queue the copies of the host arrays an alignment reads (frame_offset, ground, color, keep, idx, dist) into the map's staging
-// buffers; d, didx and ddist then name the device copies
-int align_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist, lf_segments* d,
-                     const int32_t** didx, const float** ddist);
-// the staging of lf_map_step_aligned_host: frame_offset, code, ground, color, keep go up; st_idx and st_dist are sized
-int step_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, lf_segments* d);
+// the part of an ma::Batch every solver fills alike, from DEVICE arrays; pose0, pose4 and res are null
+ma::Batch batch_view(const lf_segments* d, int n, int n_frames, const int32_t* idx, const float* dist);
+// open a solver's call: the map's stream waits for the handle's, host arrays (on_device 0: frame_offset, ground, color, keep, idx,
+// dist) are queued into the map's staging buffers, and *b is the batch_view of the device arrays
+int open_batch(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist, int on_device,
+               ma::Batch* b);
+// queue the upload of [n_frames][3] prior poses into m->prior_pose; pose null: +0 everywhere.  (Every call that queues this copy
+// waits for the stream before it returns: pose has left the host by then.)
+int upload_prior_pose(lf_map* m, const double* pose, int n_frames, const double** d_pose);
+// copy a solver's results to the host (and a second array when dst2 is given), then wait for the map's stream
+int fetch_results(lf_map* m, void* dst, const DevBuf& src, size_t bytes, void* dst2 = nullptr, const DevBuf* src2 = nullptr, size_t bytes2 = 0);
+
+// ---- the steps that solve between association and update (lf_map_step_aligned, lf_map_step_smoothed) and the host forms
+// associate, queue the solver (it leaves x, y, cos, sin per frame in m->pose), pack the block with those poses, update the map.
+// who: the exported call, for the error text
+int step_solved(lf_map* m, lf_handle* h, const char* who, const lf_segments* segs, int n, int n_frames, int step, int32_t* idx, float* dist,
+                const std::function<int(const ma::Batch&)>& queue_solver);
+// a step's host form: frame_offset, code, color, keep and ground (those present) go up, device_form runs on the copies with the
+// staged idx and dist, idx and dist come down and the stream is waited for
+int step_from_host(lf_map* m, const lf_segments* segs, int n, int n_frames, int32_t* idx, float* dist,
+                   const std::function<int(const lf_segments* d, int32_t* d_idx, float* d_dist)>& device_form);

@@ -27,13 +27,15 @@ int check_call(lf_map* m, const char* who, const lf_segments* segs, int n, int n
     return LF_OK;
 }
 
-// queue the smoothing of device arrays on the map's stream: the odometry poses and the chains go up, m->pose receives x, y, cos,
+// queue the smoothing of a batch view on the map's stream: the odometry poses and the chains go up, m->pose receives x, y, cos,
 // sin per frame, m->al_res the results and m->sm_status the chains' statuses
-int queue_smooth(lf_map* m, const lf_segments* d, int n, int n_frames, const int32_t* idx, const float* dist, const double* frame_pose,
-                 const int32_t* chain_offset, int n_chains, const lf_smooth_config* cfg)
+int queue_smooth(lf_map* m, const ma::Batch& view, const double* frame_pose, const int32_t* chain_offset, int n_chains, const lf_smooth_config* cfg)
 {
     int rc;
-    if ((rc = scratch(m, m->al_pose0, (size_t)n_frames * 3 * sizeof(double))) || (rc = scratch(m, m->pose, (size_t)n_frames * 4 * sizeof(double))) ||
+    const int n_frames = view.n_frames;
+    ms::Batch b;
+    b.a = view;
+    if ((rc = upload_prior_pose(m, frame_pose, n_frames, &b.a.pose0)) || (rc = scratch(m, m->pose, (size_t)n_frames * 4 * sizeof(double))) ||
         (rc = scratch(m, m->al_res, (size_t)n_frames * sizeof(lf_align_result))) || (rc = scratch(m, m->sm_offset, (size_t)(n_chains + 1) * 4)) ||
         (rc = scratch(m, m->sm_chain_of, (size_t)n_frames * 4)) || (rc = scratch(m, m->sm_sums, (size_t)n_frames * 9 * sizeof(double))) ||
         (rc = scratch(m, m->sm_node, (size_t)n_frames * sizeof(ms::Node))) || (rc = scratch(m, m->sm_chain, (size_t)n_chains * sizeof(ms::Chain))) ||
@@ -46,12 +48,7 @@ int queue_smooth(lf_map* m, const lf_segments* d, int n, int n_frames, const int
         for (int f = hc[c]; f < hc[c + 1]; ++f) hc[(size_t)n_chains + 1 + f] = c;
     LF_HIP_CHECK(m, hipMemcpyAsync(m->sm_offset.p, hc.data(), (size_t)(n_chains + 1) * 4, hipMemcpyHostToDevice, m->stream));
     LF_HIP_CHECK(m, hipMemcpyAsync(m->sm_chain_of.p, hc.data() + n_chains + 1, (size_t)n_frames * 4, hipMemcpyHostToDevice, m->stream));
-    LF_HIP_CHECK(m, hipMemcpyAsync(m->al_pose0.p, frame_pose, (size_t)n_frames * 3 * sizeof(double), hipMemcpyHostToDevice, m->stream));
     LF_HIP_CHECK(m, hipMemsetAsync(m->sm_chain.p, 0, (size_t)n_chains * sizeof(ms::Chain), m->stream));
-    ms::Batch b;
-    b.a.frame_offset = n > 0 ? d->frame_offset : nullptr; b.a.ground = d->ground; b.a.color = d->color; b.a.keep = d->keep;
-    b.a.idx = idx; b.a.dist = dist; b.a.n = n; b.a.n_frames = n_frames;
-    b.a.pose0 = static_cast<const double*>(m->al_pose0.p);
     b.a.pose4 = static_cast<double*>(m->pose.p);
     b.a.res = static_cast<lf_align_result*>(m->al_res.p);
     b.chain_offset = static_cast<const int32_t*>(m->sm_offset.p);
@@ -69,12 +66,9 @@ int queue_smooth(lf_map* m, const lf_segments* d, int n, int n_frames, const int
     return LF_OK;
 }
 
-int fetch_results(lf_map* m, int n_frames, int n_chains, lf_align_result* results, int32_t* chain_status)
+int fetch_smoothed(lf_map* m, int n_frames, int n_chains, lf_align_result* results, int32_t* chain_status)
 {
-    LF_HIP_CHECK(m, hipMemcpyAsync(results, m->al_res.p, (size_t)n_frames * sizeof(lf_align_result), hipMemcpyDeviceToHost, m->stream));
-    if (chain_status) LF_HIP_CHECK(m, hipMemcpyAsync(chain_status, m->sm_status.p, (size_t)n_chains * 4, hipMemcpyDeviceToHost, m->stream));
-    LF_HIP_CHECK(m, hipStreamSynchronize(m->stream));
-    return LF_OK;
+    return fetch_results(m, results, m->al_res, (size_t)n_frames * sizeof(lf_align_result), chain_status, &m->sm_status, (size_t)n_chains * 4);
 }
 
 }  // namespace
@@ -90,12 +84,7 @@ extern "C" void lf_map_smooth_default_config(lf_smooth_config* c)
     c->anchor_xy = 0.0; c->anchor_theta = 0.0;
 }
 
-extern "C" int lf_map_smooth_timing(lf_map* m, double* ms, int32_t* launches)
-{
-    if (!m) return LF_ERR_NOT_INITIALISED;
-    m->clock.take(ms, launches, 1, kMapSmoothStage, 1);
-    return LF_OK;
-}
+extern "C" int lf_map_smooth_timing(lf_map* m, double* ms, int32_t* launches) { return take_stage(m, kMapSmoothStage, ms, launches); }
 
 extern "C" int lf_map_smooth(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist,
                              const double* frame_pose, const int32_t* chain_offset, int n_chains, const lf_smooth_config* cfg, int on_device,
@@ -103,21 +92,12 @@ extern "C" int lf_map_smooth(lf_map* m, lf_handle* h, const lf_segments* segs, i
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
     int rc;
+    ma::Batch b;
     if ((rc = check_call(m, "lf_map_smooth", segs, n, n_frames, idx, frame_pose, chain_offset, n_chains, cfg, results)) != LF_OK) return rc;
-    LF_HIP_CHECK(m, hipSetDevice(m->device));
-    if ((rc = after_handle(m, h)) != LF_OK) return rc;
-    lf_segments d;
-    memset(&d, 0, sizeof(d));
-    const int32_t* didx = idx;
-    const float* ddist = dist;
-    if (on_device) {
-        d.frame_offset = segs->frame_offset; d.ground = segs->ground; d.color = segs->color; d.keep = segs->keep;
-    } else if (n > 0) {
-        if ((rc = align_stage_host(m, segs, n, n_frames, idx, dist, &d, &didx, &ddist)) != LF_OK) return rc;
-    }
-    if ((rc = queue_smooth(m, &d, n, n_frames, didx, ddist, frame_pose, chain_offset, n_chains, cfg)) != LF_OK) return rc;
+    if ((rc = open_batch(m, h, segs, n, n_frames, idx, dist, on_device, &b)) != LF_OK) return rc;
+    if ((rc = queue_smooth(m, b, frame_pose, chain_offset, n_chains, cfg)) != LF_OK) return rc;
     if ((rc = release_handle(m, h)) != LF_OK) return rc;
-    return fetch_results(m, n_frames, n_chains, results, chain_status);
+    return fetch_smoothed(m, n_frames, n_chains, results, chain_status);
 }
 
 extern "C" int lf_map_step_smoothed(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const double* frame_pose,
@@ -127,21 +107,10 @@ extern "C" int lf_map_step_smoothed(lf_map* m, lf_handle* h, const lf_segments* 
     if (!m) return LF_ERR_NOT_INITIALISED;
     int rc;
     if ((rc = check_call(m, "lf_map_step_smoothed", segs, n, n_frames, idx, frame_pose, chain_offset, n_chains, cfg, results)) != LF_OK) return rc;
-    if (n > 0 && (!dist || !segs->code)) { set_error(m, LF_ERR_BAD_ARG, "lf_map_step_smoothed: code and dist are required"); return LF_ERR_BAD_ARG; }
-    if (n > 0 && (rc = lf_map_associate(m, h, segs->code, segs->color, n, idx, dist, 1)) != LF_OK) return rc;
-    LF_HIP_CHECK(m, hipSetDevice(m->device));
-    if ((rc = scratch(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) != LF_OK) return rc;
-    if ((rc = after_handle(m, h)) != LF_OK) return rc;
-    if ((rc = queue_smooth(m, segs, n, n_frames, idx, dist, frame_pose, chain_offset, n_chains, cfg)) != LF_OK) return rc;
-    {
-        StageClock::Scope t(m, m->clock, 2);
-        launch_map_pack_block(n, n_frames, n > 0 ? segs->frame_offset : nullptr, segs->code, segs->color, segs->keep, segs->ground, idx, dist,
-                              static_cast<const double*>(m->pose.p), step, static_cast<uint8_t*>(m->own_block.p), m->stream);
-    }
-    LF_HIP_CHECK(m, hipGetLastError());
-    if ((rc = release_handle(m, h)) != LF_OK) return rc;
-    if (n > 0 && (rc = update_blocks(m, static_cast<const uint8_t*>(m->own_block.p), 1, n + 1, 0, n)) != LF_OK) return rc;
-    return fetch_results(m, n_frames, n_chains, results, chain_status);
+    rc = step_solved(m, h, "lf_map_step_smoothed", segs, n, n_frames, step, idx, dist,
+                     [&](const ma::Batch& b) { return queue_smooth(m, b, frame_pose, chain_offset, n_chains, cfg); });
+    if (rc != LF_OK) return rc;
+    return fetch_smoothed(m, n_frames, n_chains, results, chain_status);
 }
 
 extern "C" int lf_map_step_smoothed_host(lf_map* m, const lf_segments* segs, int n, int n_frames, const double* frame_pose,
@@ -155,18 +124,7 @@ extern "C" int lf_map_step_smoothed_host(lf_map* m, const lf_segments* segs, int
         set_error(m, LF_ERR_BAD_ARG, "lf_map_step_smoothed_host: bad argument (frame_offset, code and dist are required, color when gating is on)");
         return LF_ERR_BAD_ARG;
     }
-    LF_HIP_CHECK(m, hipSetDevice(m->device));
-    hipStream_t s = m->stream;
-    lf_segments d;
-    memset(&d, 0, sizeof(d));
-    if ((rc = step_stage_host(m, segs, n, n_frames, &d)) != LF_OK) return rc;
-    rc = lf_map_step_smoothed(m, nullptr, &d, n, n_frames, frame_pose, chain_offset, n_chains, cfg, step, static_cast<int32_t*>(m->st_idx.p),
-                              static_cast<float*>(m->st_dist.p), results, chain_status);
-    if (rc != LF_OK) return rc;
-    if (n > 0) {
-        LF_HIP_CHECK(m, hipMemcpyAsync(idx, m->st_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(m, hipMemcpyAsync(dist, m->st_dist.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    }
-    LF_HIP_CHECK(m, hipStreamSynchronize(s));
-    return LF_OK;
+    return step_from_host(m, segs, n, n_frames, idx, dist, [&](const lf_segments* d, int32_t* d_idx, float* d_dist) {
+        return lf_map_step_smoothed(m, nullptr, d, n, n_frames, frame_pose, chain_offset, n_chains, cfg, step, d_idx, d_dist, results, chain_status);
+    });
 }

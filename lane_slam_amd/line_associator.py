@@ -143,35 +143,62 @@ class LineAssociator(object):
                 setattr(s, k, a.ctypes.data)
         return s, alive
 
-    # ------------------------------------------------------------------ odometry poses corrected against the map (lf_map_align)
-    def align_config(self, **overrides):
-        """The library's default `_lib.LfAlignConfig` (lf_map_align_default_config) with the overrides applied: iterations,
-        min_pairs, min_hits, color_match, gate, huber, max_dist, prior_xy, prior_theta, max_shift, max_turn."""
-        c = _lib.LfAlignConfig()
-        self.lib.lf_map_align_default_config(ctypes.byref(c))
-        kinds = dict((k, t) for k, t in _lib.LfAlignConfig._fields_)
+    # ------------------------------------------------------------------ what the three pose solvers' wrappers share
+    def _config(self, who, kind, default, overrides, nested=None):
+        """The library's default `kind` with typed overrides; nested: the (field, struct) whose fields may be overridden too."""
+        c = kind()
+        default(ctypes.byref(c))
+        if nested is not None and nested[1] is not None:
+            ctypes.memmove(ctypes.byref(getattr(c, nested[0])), ctypes.byref(nested[1]), ctypes.sizeof(nested[1]))
+        own = dict((k, t) for k, t in kind._fields_ if k != "reserved_" and (nested is None or k != nested[0]))
+        inner = {} if nested is None else dict((k, t) for k, t in type(getattr(c, nested[0]))._fields_)
         for k, val in overrides.items():
-            if k not in kinds:
-                raise TypeError("align_config: unknown field %r" % (k,))
-            setattr(c, k, int(val) if kinds[k] is ctypes.c_int32 else float(val))
+            if k in own:
+                setattr(c, k, int(val) if own[k] is ctypes.c_int32 else float(val))
+            elif k in inner:
+                setattr(getattr(c, nested[0]), k, int(val) if inner[k] is ctypes.c_int32 else float(val))
+            else:
+                raise TypeError("%s: unknown field %r" % (who, k))
         return c
 
-    @staticmethod
-    def _poses_out(res):
-        return np.stack([res["x"], res["y"], res["theta"]], axis=1)
-
-    def align(self, seg, idx, dist, poses, config=None):
-        """Correct the poses of a batch against the map as it stands: seg is a host `Segments` block (frame_offset, ground, color,
-        keep are read), idx / dist its association (`associate`), poses (n_frames, 3) the odometry's map -> duck (x, y, theta).
-        Returns (poses_out (n_frames, 3) float64, results): results is a record array of `_lib.ALIGN_RESULT_DTYPE`, one
-        lf_align_result per frame (status: `_lib.ALIGN_STATUS`).  The map is not changed."""
+    def _solver_host(self, who, seg, idx, dist, poses):
+        """(n, n_frames, the poses' address, LfSegments, idx, dist, what must stay alive) of a host-form solver call"""
         n, n_frames = int(seg.n), len(seg.frame_offset) - 1
         keep_alive, pp = self._poses(poses, n_frames)
         s, alive = self._host_segs(seg, ("frame_offset", "color", "keep", "ground"))
         idx = np.ascontiguousarray(idx, np.int32)
         dist = None if dist is None else np.ascontiguousarray(dist, np.float32)
         if len(idx) != n or (dist is not None and len(dist) != n):
-            raise ValueError("align: idx and dist hold one value per segment")
+            raise ValueError("%s: idx and dist hold one value per segment" % who)
+        return n, n_frames, pp, s, idx, dist, (keep_alive, alive)
+
+    def _solver_device(self, fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, poses):
+        """(handle, LfSegments, n, n_frames, idx, dist, the poses' address, what must stay alive) of a device-form solver call"""
+        keep_alive, pp = self._poses(poses, int(n_frames))
+        return (fe.h if fe is not None else None, self._segs(out_ptrs), int(n), int(n_frames), int(idx_ptr), dist_ptr and int(dist_ptr), pp,
+                keep_alive)
+
+    def _stage_timing(self, call):
+        ms, ln = ctypes.c_double(), ctypes.c_int32()
+        self._check(call(self.m, ctypes.byref(ms), ctypes.byref(ln)))
+        return ms.value, ln.value
+
+    @staticmethod
+    def _poses_out(res):
+        return np.stack([res["x"], res["y"], res["theta"]], axis=1)
+
+    # ------------------------------------------------------------------ odometry poses corrected against the map (lf_map_align)
+    def align_config(self, **overrides):
+        """The library's default `_lib.LfAlignConfig` (lf_map_align_default_config) with the overrides applied: iterations,
+        min_pairs, min_hits, color_match, gate, huber, max_dist, prior_xy, prior_theta, max_shift, max_turn."""
+        return self._config("align_config", _lib.LfAlignConfig, self.lib.lf_map_align_default_config, overrides)
+
+    def align(self, seg, idx, dist, poses, config=None):
+        """Correct the poses of a batch against the map as it stands: seg is a host `Segments` block (frame_offset, ground, color,
+        keep are read), idx / dist its association (`associate`), poses (n_frames, 3) the odometry's map -> duck (x, y, theta).
+        Returns (poses_out (n_frames, 3) float64, results): results is a record array of `_lib.ALIGN_RESULT_DTYPE`, one
+        lf_align_result per frame (status: `_lib.ALIGN_STATUS`).  The map is not changed."""
+        n, n_frames, pp, s, idx, dist, alive = self._solver_host("align", seg, idx, dist, poses)
         config = self.align_config() if config is None else config
         res = np.zeros(n_frames, _lib.ALIGN_RESULT_DTYPE)
         self._check(self.lib.lf_map_align(self.m, None, ctypes.byref(s), n, n_frames, idx.ctypes.data, None if dist is None else dist.ctypes.data,
@@ -180,39 +207,22 @@ class LineAssociator(object):
 
     def align_device(self, fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, poses, config=None):
         """`align` for a batch that is resident on the device (out_ptrs as for step_device; idx_ptr / dist_ptr device arrays)."""
-        keep_alive, pp = self._poses(poses, n_frames)
-        s = self._segs(out_ptrs)
+        h, s, n, n_frames, idx, dist, pp, alive = self._solver_device(fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, poses)
         config = self.align_config() if config is None else config
-        res = np.zeros(int(n_frames), _lib.ALIGN_RESULT_DTYPE)
-        self._check(self.lib.lf_map_align(self.m, fe.h if fe is not None else None, ctypes.byref(s), int(n), int(n_frames), int(idx_ptr),
-                                          dist_ptr and int(dist_ptr), pp, ctypes.byref(config), 1, res.ctypes.data))
+        res = np.zeros(n_frames, _lib.ALIGN_RESULT_DTYPE)
+        self._check(self.lib.lf_map_align(self.m, h, ctypes.byref(s), n, n_frames, idx, dist, pp, ctypes.byref(config), 1, res.ctypes.data))
         return self._poses_out(res), res
 
     def align_timing(self):
         """(ms, launches) of the alignment kernel since the previous call (needs set_profiling(True)); resets."""
-        ms, ln = ctypes.c_double(), ctypes.c_int32()
-        self._check(self.lib.lf_map_align_timing(self.m, ctypes.byref(ms), ctypes.byref(ln)))
-        return ms.value, ln.value
+        return self._stage_timing(self.lib.lf_map_align_timing)
 
     # ------------------------------------------------------------------ a batch's trajectory smoothed against the map (lf_map_smooth)
     def smooth_config(self, align=None, **overrides):
         """The library's default `_lib.LfSmoothConfig` (lf_map_smooth_default_config) with the overrides applied: odo_xy, odo_theta,
         anchor_xy, anchor_theta, and any field of align_config (iterations, gate, prior_xy, ...); align: an `_lib.LfAlignConfig` that
         replaces the default one before the overrides."""
-        c = _lib.LfSmoothConfig()
-        self.lib.lf_map_smooth_default_config(ctypes.byref(c))
-        if align is not None:
-            ctypes.memmove(ctypes.byref(c.align), ctypes.byref(align), ctypes.sizeof(_lib.LfAlignConfig))
-        own = dict((k, t) for k, t in _lib.LfSmoothConfig._fields_ if k != "align")
-        kinds = dict((k, t) for k, t in _lib.LfAlignConfig._fields_)
-        for k, val in overrides.items():
-            if k in own:
-                setattr(c, k, float(val))
-            elif k in kinds:
-                setattr(c.align, k, int(val) if kinds[k] is ctypes.c_int32 else float(val))
-            else:
-                raise TypeError("smooth_config: unknown field %r" % (k,))
-        return c
+        return self._config("smooth_config", _lib.LfSmoothConfig, self.lib.lf_map_smooth_default_config, overrides, nested=("align", align))
 
     @staticmethod
     def _chains(chains, n_frames):
@@ -226,13 +236,7 @@ class LineAssociator(object):
         """Smooth the poses of a batch against the map as it stands (lf_map_smooth): the arguments of `align`, and chains, the
         (n_chains + 1) offsets that split the frames into runs of consecutive frames (None: one chain).  Returns (poses_out,
         results, chain_status): results as `align` returns them, chain_status (n_chains,) int32.  The map is not changed."""
-        n, n_frames = int(seg.n), len(seg.frame_offset) - 1
-        keep_alive, pp = self._poses(poses, n_frames)
-        s, alive = self._host_segs(seg, ("frame_offset", "color", "keep", "ground"))
-        idx = np.ascontiguousarray(idx, np.int32)
-        dist = None if dist is None else np.ascontiguousarray(dist, np.float32)
-        if len(idx) != n or (dist is not None and len(dist) != n):
-            raise ValueError("smooth: idx and dist hold one value per segment")
+        n, n_frames, pp, s, idx, dist, alive = self._solver_host("smooth", seg, idx, dist, poses)
         config = self.smooth_config() if config is None else config
         co, cp, nc = self._chains(chains, n_frames)
         res, cs = np.zeros(n_frames, _lib.ALIGN_RESULT_DTYPE), np.zeros(max(nc, 0), np.int32)
@@ -242,33 +246,23 @@ class LineAssociator(object):
 
     def smooth_device(self, fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, poses, config=None, chains=None):
         """`smooth` for a batch that is resident on the device (out_ptrs as for step_device; idx_ptr / dist_ptr device arrays)."""
-        keep_alive, pp = self._poses(poses, n_frames)
-        s = self._segs(out_ptrs)
+        h, s, n, n_frames, idx, dist, pp, alive = self._solver_device(fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, poses)
         config = self.smooth_config() if config is None else config
-        co, cp, nc = self._chains(chains, int(n_frames))
-        res, cs = np.zeros(int(n_frames), _lib.ALIGN_RESULT_DTYPE), np.zeros(max(nc, 0), np.int32)
-        self._check(self.lib.lf_map_smooth(self.m, fe.h if fe is not None else None, ctypes.byref(s), int(n), int(n_frames), int(idx_ptr),
-                                           dist_ptr and int(dist_ptr), pp, cp, nc, ctypes.byref(config), 1, res.ctypes.data, cs.ctypes.data))
+        co, cp, nc = self._chains(chains, n_frames)
+        res, cs = np.zeros(n_frames, _lib.ALIGN_RESULT_DTYPE), np.zeros(max(nc, 0), np.int32)
+        self._check(self.lib.lf_map_smooth(self.m, h, ctypes.byref(s), n, n_frames, idx, dist, pp, cp, nc, ctypes.byref(config), 1,
+                                           res.ctypes.data, cs.ctypes.data))
         return self._poses_out(res), res, cs
 
     def smooth_timing(self):
         """(ms, launches) of the smoother since the previous call (needs set_profiling(True)); one launch is one call's iterations."""
-        ms, ln = ctypes.c_double(), ctypes.c_int32()
-        self._check(self.lib.lf_map_smooth_timing(self.m, ctypes.byref(ms), ctypes.byref(ln)))
-        return ms.value, ln.value
+        return self._stage_timing(self.lib.lf_map_smooth_timing)
 
     # ------------------------------------------------------------------ frames localised without a prior pose (lf_map_localize)
     def localize_config(self, **overrides):
         """The library's default `_lib.LfLocalizeConfig` (lf_map_localize_default_config) with the overrides applied: max_pairs, flips,
         min_inliers, min_hits, color_match, gate, min_sin, max_dist."""
-        c = _lib.LfLocalizeConfig()
-        self.lib.lf_map_localize_default_config(ctypes.byref(c))
-        kinds = dict((k, t) for k, t in _lib.LfLocalizeConfig._fields_ if k != "reserved_")
-        for k, val in overrides.items():
-            if k not in kinds:
-                raise TypeError("localize_config: unknown field %r" % (k,))
-            setattr(c, k, int(val) if kinds[k] is ctypes.c_int32 else float(val))
-        return c
+        return self._config("localize_config", _lib.LfLocalizeConfig, self.lib.lf_map_localize_default_config, overrides)
 
     def localize(self, seg, idx, dist, config=None, fallback=None, refine=None):
         """A pose per frame from the frame's associations and the map's geometry alone (lf_map_localize): seg, idx and dist as for
@@ -276,13 +270,7 @@ class LineAssociator(object):
         (n_frames, 3) float64, results): results is a record array of `_lib.LOCALIZE_RESULT_DTYPE`, one lf_localize_result per frame
         (status: `_lib.ALIGN_STATUS`).  refine: an `_lib.LfAlignConfig` -- `align` runs afterwards with poses_out as its poses, and
         the call returns (aligned poses, results, align results).  The map is not changed."""
-        n, n_frames = int(seg.n), len(seg.frame_offset) - 1
-        keep_alive, pp = self._poses(fallback, n_frames)
-        s, alive = self._host_segs(seg, ("frame_offset", "color", "keep", "ground"))
-        idx = np.ascontiguousarray(idx, np.int32)
-        dist = None if dist is None else np.ascontiguousarray(dist, np.float32)
-        if len(idx) != n or (dist is not None and len(dist) != n):
-            raise ValueError("localize: idx and dist hold one value per segment")
+        n, n_frames, pp, s, idx, dist, alive = self._solver_host("localize", seg, idx, dist, fallback)
         config = self.localize_config() if config is None else config
         res = np.zeros(n_frames, _lib.LOCALIZE_RESULT_DTYPE)
         self._check(self.lib.lf_map_localize(self.m, None, ctypes.byref(s), n, n_frames, idx.ctypes.data,
@@ -294,12 +282,10 @@ class LineAssociator(object):
 
     def localize_device(self, fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, config=None, fallback=None, refine=None):
         """`localize` for a batch that is resident on the device (out_ptrs as for step_device; idx_ptr / dist_ptr device arrays)."""
-        keep_alive, pp = self._poses(fallback, int(n_frames))
-        s = self._segs(out_ptrs)
+        h, s, n, n_frames, idx, dist, pp, alive = self._solver_device(fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, fallback)
         config = self.localize_config() if config is None else config
-        res = np.zeros(int(n_frames), _lib.LOCALIZE_RESULT_DTYPE)
-        self._check(self.lib.lf_map_localize(self.m, fe.h if fe is not None else None, ctypes.byref(s), int(n), int(n_frames), int(idx_ptr),
-                                             dist_ptr and int(dist_ptr), pp, ctypes.byref(config), 1, res.ctypes.data))
+        res = np.zeros(n_frames, _lib.LOCALIZE_RESULT_DTYPE)
+        self._check(self.lib.lf_map_localize(self.m, h, ctypes.byref(s), n, n_frames, idx, dist, pp, ctypes.byref(config), 1, res.ctypes.data))
         if refine is None:
             return self._poses_out(res), res
         poses_out, aligned = self.align_device(fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, self._poses_out(res), refine)
@@ -307,9 +293,7 @@ class LineAssociator(object):
 
     def localize_timing(self):
         """(ms, launches) of the localisation kernel since the previous call (needs set_profiling(True)); resets."""
-        ms, ln = ctypes.c_double(), ctypes.c_int32()
-        self._check(self.lib.lf_map_localize_timing(self.m, ctypes.byref(ms), ctypes.byref(ln)))
-        return ms.value, ln.value
+        return self._stage_timing(self.lib.lf_map_localize_timing)
 
     @staticmethod
     def carry(poses, last_odometry, last_corrected):
