@@ -834,6 +834,72 @@ LF_API int lf_map_localize(lf_map* m, lf_handle* h, const lf_segments* segs, int
  * its own: lf_map_get_timing, lf_map_align_timing and lf_map_smooth_timing are unchanged. */
 LF_API int lf_map_localize_timing(lf_map* m, double* ms, int32_t* launches);
 
+/* ---- the live map culled and compacted on the device: lf_map_prune -------------------------------------
+ * lf_map can only grow or overwrite: under LF_MAP_APPEND every observation of a line is another entry, under LF_MAP_MERGE an
+ * observation from another viewpoint has another code and lands next to its twin, a spurious detection stays until the ring
+ * reaches it, and the ring overwrites the OLDEST entry, not the worst.  lf_map_prune decides per entry whether it stays and
+ * rewrites the map so that the survivors are dense, in age order, with their matrix-core operands in place.  The reference's map
+ * is an append-only list (src/show_map/src/show_map.py:28-42): this is the package's OWN contract, written so that a sequential
+ * restatement (tests/map_prune_ref.py) and the kernels (k_map_prune.hip) agree bit for bit.  A map that is never pruned behaves
+ * exactly as before.
+ *
+ *   logical order     entry l = 0 .. size - 1 is the physical entry (start + l) mod capacity; start = head when the ring is full
+ *                     (size == capacity under LF_MAP_RING), else 0: oldest first, the order in which the ring would overwrite.
+ *   exempt            an entry with keep_seeded != 0 and last_seen < 0 (lf_map_seed's), or whose colour's bit of color_mask is
+ *                     clear (bits 0 .. 2: colours 0 .. 2, bit 3: every other colour), is never dropped by any rule.  It may
+ *                     still cover others.
+ *   rules             an entry that is not exempt is counted under the FIRST rule that drops it, in this order:
+ *     stale           last_seen < stale_before                                  (stale_before == INT32_MIN: off)
+ *     weak            hits < min_hits and last_seen < weak_before               (min_hits <= 1: off)
+ *     box             use_box != 0 and BOTH endpoints outside the box; outside(P) = x < x_min || x > x_max || y < y_min || y > y_max
+ *     covered         cover_distance > 0, among the entries the three rules above left (exempt ones included): i is covered when
+ *                     some j != i has the same colour byte, a squared length L2 = dx dx + dy dy != 0 (dx = x1 - x0, dy = y1 - y0),
+ *                     rank(j) > rank(i) with rank the lexicographic triple (hits, last_seen, logical index), and BOTH endpoints P
+ *                     of i pass, with (ux, uy) = P - (x0, y0) of j, cr = ux dy - uy dx, s = ux dx + uy dy:
+ *                         cr cr <= (cover_distance cover_distance) L2, and
+ *                         if s < 0: s s <= (cover_slack cover_slack) L2;  else if s > L2: (s - L2) (s - L2) <= (cover_slack cover_slack) L2.
+ *                     All f64, unfused, products and sums as written, no square root and no division.  A comparison with a NaN
+ *                     is false: such an entry neither covers nor is covered, and is not outside the box.  The predicate reads the
+ *                     map as it stood before the call, so the outcome does not depend on the order of evaluation, and the
+ *                     top-ranked entry of a pile of duplicates always survives.
+ *   afterwards        the survivors sit at 0 .. size_after - 1 in logical order with code, colour, ground, hits and last_seen
+ *                     unchanged and their operands re-packed; the rows [size_after, size_before) are zero again (entries and
+ *                     operands: lf_map_associate lets rows past the size contribute nothing); size = size_after, head =
+ *                     size_after mod capacity; the lifetime totals and the failing-update counters are untouched.  With every
+ *                     rule off an unwrapped map stays byte-identical and a wrapped ring is rotated so that its oldest entry is 0.
+ *   remap             optional, [capacity] int32, host or device (remap_on_device): for every PHYSICAL index before the call the
+ *                     index after it, or -1 for a dropped or unused row: for callers that hold idx arrays of an earlier
+ *                     association.
+ * The call runs on the map's stream in call order with updates and associations, waits for that stream and returns with `res`
+ * filled in: a maintenance call, like lf_map_size.  A pending failing update is reported first, exactly as lf_map_size does it:
+ * the error is returned, nothing is done, call again.  LF_ERR_BAD_ARG, touching nothing, the reason in lf_map_last_error: a NULL
+ * c or res; a negative cover_slack; with use_box a box that is not finite or has x_min > x_max or y_min > y_max; a cover_distance
+ * or (cover rule on) cover_slack that is not finite; the cover rule on and cover_max_entries < 1 or more survivors of the three
+ * rules before it than cover_max_entries (the rule is all pairs: a spatial grid for larger maps is not built).
+ * Replicas: the result is a pure function of the map and the configuration, so ranks of a multi-GPU run that call it with the
+ * same configuration between the same two steps keep identical maps; no collective is needed. */
+typedef struct lf_prune_config {
+    int32_t min_hits;            /* weak rule: hits < min_hits AND last_seen < weak_before -> dropped; <= 1: off */
+    int32_t weak_before;
+    int32_t stale_before;        /* stale rule: last_seen < stale_before -> dropped; INT32_MIN: off */
+    int32_t keep_seeded;         /* 1: entries with last_seen < 0 (lf_map_seed's) are never dropped; default 1 */
+    int32_t color_mask;          /* entries whose colour's bit is clear are never dropped; default 0xF */
+    int32_t use_box;             /* box rule: both endpoints outside box -> dropped */
+    double  box[4];              /* x_min, y_min, x_max, y_max, map frame */
+    double  cover_distance;      /* cover rule, metres; <= 0: off */
+    double  cover_slack;         /* metres an endpoint may lie beyond the covering entry's ends; >= 0 */
+    int32_t cover_max_entries;   /* default 131072 */
+    int32_t reserved_;           /* 0 */
+} lf_prune_config;
+typedef struct lf_prune_result { int32_t size_before, size_after, n_stale, n_weak, n_box, n_covered; } lf_prune_result;
+LF_API int lf_sizeof_prune_config(void);
+LF_API int lf_sizeof_prune_result(void);
+LF_API void lf_map_prune_default_config(lf_prune_config* c);     /* every rule off: a prune that only re-orders */
+LF_API int lf_map_prune(lf_map* m, const lf_prune_config* c, lf_prune_result* res, int32_t* remap, int remap_on_device);
+/* ms and launches (one launch = one prune, all its kernels) accumulated since the previous call, with profiling on; resets them.
+ * A stage of its own: lf_map_get_timing and the solvers' timing calls are unchanged. */
+LF_API int lf_map_prune_timing(lf_map* m, double* ms, int32_t* launches);
+
 /* ---- Histogram lane filter: lane pose from ground segments -----------------------------------------
  * LaneFilterHistogram (src/lane_filter/include/lane_filter/lane_filter.py:12-161) as lane_filter_node.processSegments
  * drives it (src/lane_filter/src/lane_filter_node.py:49-87): per frame predict(dt, v, w) -> update(segments) ->

@@ -47,6 +47,7 @@ EXPORTS = (
     "lf_sizeof_smooth_config", "lf_map_smooth_default_config", "lf_map_smooth", "lf_map_step_smoothed", "lf_map_step_smoothed_host",
     "lf_map_smooth_timing",
     "lf_sizeof_localize_config", "lf_sizeof_localize_result", "lf_map_localize_default_config", "lf_map_localize", "lf_map_localize_timing",
+    "lf_sizeof_prune_config", "lf_sizeof_prune_result", "lf_map_prune_default_config", "lf_map_prune", "lf_map_prune_timing",
 )
 LF_ALIGN_OK, LF_ALIGN_FEW, LF_ALIGN_DEGENERATE, LF_ALIGN_REJECTED = 0, 1, 2, 3
 ALIGN_STATUS = ("ok", "few", "degenerate", "rejected")
@@ -202,6 +203,19 @@ class LfLocalizeResult(ctypes.Structure):
 # the same layout as a numpy record: what LineAssociator.localize returns
 LOCALIZE_RESULT_DTYPE = [("x", "<f8"), ("y", "<f8"), ("theta", "<f8"), ("cost", "<f8"), ("n_pairs", "<i4"), ("n_candidates", "<i4"),
                          ("n_hypotheses", "<i4"), ("n_inliers", "<i4"), ("seg_a", "<i4"), ("seg_b", "<i4"), ("flip", "<i4"), ("status", "<i4")]
+
+
+class LfPruneConfig(ctypes.Structure):
+    """ctypes mirror of `lf_prune_config` (include/lanefront.h)."""
+    _fields_ = [("min_hits", ctypes.c_int32), ("weak_before", ctypes.c_int32), ("stale_before", ctypes.c_int32), ("keep_seeded", ctypes.c_int32),
+                ("color_mask", ctypes.c_int32), ("use_box", ctypes.c_int32), ("box", ctypes.c_double * 4), ("cover_distance", ctypes.c_double),
+                ("cover_slack", ctypes.c_double), ("cover_max_entries", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
+
+
+class LfPruneResult(ctypes.Structure):
+    """ctypes mirror of `lf_prune_result` (include/lanefront.h)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("size_before", "size_after", "n_stale", "n_weak", "n_box", "n_covered")]
+
 
 _lib = None
 
@@ -363,6 +377,14 @@ def load():
     lib.lf_map_localize.argtypes = [vp, vp, ctypes.POINTER(LfSegments), ci, ci, vp, vp, vp, ctypes.POINTER(LfLocalizeConfig), ci, vp]
     lib.lf_map_localize_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
     for f in ("lf_sizeof_localize_config", "lf_sizeof_localize_result", "lf_map_localize", "lf_map_localize_timing"):
+        getattr(lib, f).restype = ci
+    lib.lf_sizeof_prune_config.argtypes = []
+    lib.lf_sizeof_prune_result.argtypes = []
+    lib.lf_map_prune_default_config.argtypes = [ctypes.POINTER(LfPruneConfig)]
+    lib.lf_map_prune_default_config.restype = None
+    lib.lf_map_prune.argtypes = [vp, ctypes.POINTER(LfPruneConfig), ctypes.POINTER(LfPruneResult), vp, ci]
+    lib.lf_map_prune_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
+    for f in ("lf_sizeof_prune_config", "lf_sizeof_prune_result", "lf_map_prune", "lf_map_prune_timing"):
         getattr(lib, f).restype = ci
     lib.lf_descriptor_default_params.argtypes = [ctypes.POINTER(LfDescriptorParams)]
     lib.lf_descriptor_default_params.restype = None

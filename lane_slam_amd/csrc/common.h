@@ -197,6 +197,29 @@ __host__ __device__ inline uint32_t assoc_fp4_expand(uint32_t byte)
     t = (t | (t << 3)) & 0x11111111u;
     return (t << 3) | 0x22222222u;
 }
+#ifdef __HIPCC__
+// One map row's operands from the 32 threads that own it (b = 0 .. 31, `byte` the row's code byte b): the code's e2m1 nibbles, and,
+// from the first eight threads, the colour row of the FP4 gated kernel: -6.0 (e2m1 0xF) in the nibbles 0..2 of the OTHER colours,
+// first dword; zeros after.  What k_map_apply writes for an updated entry and k_map_prune.hip for a moved one.  colour points at the
+// row's colour byte: only the first eight threads read it.
+__device__ __forceinline__ void assoc_map_write_row(int8_t* mx, int8_t* mcx, size_t pos, int b, uint32_t byte, const uint8_t* colour_byte)
+{
+    *reinterpret_cast<uint32_t*>(mx + assoc_map_offset_fp4(pos, 4 * b)) = assoc_fp4_expand(byte);
+    if (b < 8) {
+        const int colour = *colour_byte;
+        uint32_t w = 0;
+        if (b == 0 && colour < 3)
+            for (int g = 0; g < 3; ++g) if (g != colour) w |= 0xFu << (4 * g);
+        *reinterpret_cast<uint32_t*>(mcx + pos * 32 + 4 * b) = w;
+    }
+}
+// the same row as an unused one: all-zero operands (distance 128, no colour)
+__device__ __forceinline__ void assoc_map_zero_row(int8_t* mx, int8_t* mcx, size_t pos, int b)
+{
+    *reinterpret_cast<uint32_t*>(mx + assoc_map_offset_fp4(pos, 4 * b)) = 0u;
+    if (b < 8) *reinterpret_cast<uint32_t*>(mcx + pos * 32 + 4 * b) = 0u;
+}
+#endif
 // Owning, move-only memory: the destructor frees.  DevArray holds device memory (hipMalloc), HostArray pinned host memory
 // (hipHostMalloc).  alloc() frees what the buffer held first; a caller that must wait for a stream before that does so itself.
 // p converts to T*, so a buffer is passed to launches and copies as it is; pointers into it are views that own nothing.

@@ -243,15 +243,7 @@ __global__ void k_map_apply(MapDev m, const uint8_t* __restrict__ blocks, int n_
     const uint8_t* row = blocks + ((size_t)blk * block_rows + 1 + r) * kRow;
     const uint32_t byte = row[b];
     m.code[(size_t)pos * 32 + b] = (uint8_t)byte;
-    *reinterpret_cast<uint32_t*>(m.mx + assoc_map_offset_fp4((size_t)pos, 4 * b)) = assoc_fp4_expand(byte);
-    if (b < 8) {
-        // colour row of the FP4 gated kernel: -6.0 (e2m1 0xF) in the nibbles 0..2 of the OTHER colours, first dword; zeros after
-        const int c = row[72];
-        uint32_t w = 0;
-        if (b == 0 && c < 3)
-            for (int g = 0; g < 3; ++g) if (g != c) w |= 0xFu << (4 * g);
-        *reinterpret_cast<uint32_t*>(m.mcx + (size_t)pos * 32 + 4 * b) = w;
-    }
+    assoc_map_write_row(m.mx, m.mcx, (size_t)pos, b, byte, row + 72);
     if (b == 0) {
         m.color[pos] = row[72];
         const double* rg = reinterpret_cast<const double*>(row + 32);

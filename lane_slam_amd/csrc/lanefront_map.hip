@@ -9,7 +9,7 @@
 static char g_map_create_err[512] = "no error";
 
 // make the host mirror current: wait for the copy queued behind the last update (block = false: only look)
-static int refresh_state(lf_map* m, bool block = true)
+int refresh_state(lf_map* m, bool block)
 {
     if (m->state_pending) {
         if (block) LF_HIP_CHECK(m, hipEventSynchronize(m->ev_state));
@@ -29,7 +29,7 @@ static int refresh_state(lf_map* m, bool block = true)
     return LF_OK;
 }
 
-static int queue_state_copy(lf_map* m)
+int queue_state_copy(lf_map* m)
 {
     LF_HIP_CHECK(m, hipMemcpyAsync(m->h_state, m->d.state, 16 * sizeof(int), hipMemcpyDeviceToHost, m->stream));
     LF_HIP_CHECK(m, hipMemcpyAsync(m->h_state + 16, m->d.totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));

@@ -1,6 +1,6 @@
 // The live map's handle, for the translation units of lf_map_*: the map itself (lanefront_map.hip), its two views
 // (lanefront_map_render.hip, lanefront_map_camera.hip), the pose alignment (lanefront_map_align.hip) and the trajectory smoother
-// (lanefront_map_smooth.hip); the localisation without a prior pose (lanefront_map_localize.hip).  The three pose solvers share one
+// (lanefront_map_smooth.hip); the localisation without a prior pose (lanefront_map_localize.hip); the culling (lanefront_map_prune.hip).  The three pose solvers share one
 // front end (argument check, batch opener, prior-pose upload, result fetch) and the two solving steps one body and, with
 // lf_map_step_host, one host-form wrapper: all of it lives in lanefront_map_align.hip and is declared at the end of this file.
 #pragma once
@@ -35,6 +35,12 @@ struct MapCameraState {
     CallClock clock{LF_MAP_RENDER_STAGES};                   // lf_map_render_camera_timing
 };
 
+// what lf_map_prune keeps between calls (lanefront_map_prune.hip): scratch that grows on demand, no second copy of the map
+struct MapPruneState {
+    DevBuf reason, rank, wg, counters, rec, s_code, s_color, s_ground, s_hits, s_last, remap;
+    HostArray<int> h_counters;                               // pinned: the counters of k_map_prune.h
+};
+
 }  // namespace lf
 
 using namespace lf;
@@ -67,8 +73,9 @@ struct lf_map : lf::Core {
     std::vector<double> h_pose;
     std::vector<int32_t> h_chains;
     // per-stage timing: the stages of lf_map_get_timing, then kMapAlignStage (lf_map_align_timing), kMapSmoothStage
-    // (lf_map_smooth_timing) and kMapLocalizeStage (lf_map_localize_timing); past 4096 outstanding records a bracket goes untimed
-    StageClock clock{LF_MAP_N_STAGES + 3, 4096, false};
+    // (lf_map_smooth_timing), kMapLocalizeStage (lf_map_localize_timing) and kMapPruneStage (lf_map_prune_timing); past 4096 outstanding records a bracket goes untimed
+    StageClock clock{LF_MAP_N_STAGES + 4, 4096, false};
+    std::unique_ptr<lf::MapPruneState> prune;     // lf_map_prune (lanefront_map_prune.hip), made by its first call
     std::unique_ptr<lf::MapRenderState> render;   // lf_map_render / lf_map_bounds (lanefront_map_render.hip), made by their first call
     std::unique_ptr<lf::MapCameraState> camera;   // lf_map_render_camera (lanefront_map_camera.hip), likewise
 };
@@ -76,8 +83,13 @@ struct lf_map : lf::Core {
 constexpr int kMapAlignStage = LF_MAP_N_STAGES;
 constexpr int kMapSmoothStage = LF_MAP_N_STAGES + 1;
 constexpr int kMapLocalizeStage = LF_MAP_N_STAGES + 2;
+constexpr int kMapPruneStage = LF_MAP_N_STAGES + 3;
 
 // ---- lanefront_map.hip's sequencing, for the translation units of the pose solvers
+// make the host mirror current: wait for the copy queued behind the last update (block = false: only look); a failing update the
+// host has not returned an error for yet is reported here, once
+int refresh_state(lf_map* m, bool block = true);
+int queue_state_copy(lf_map* m);                  // the state's copy into the pinned mirror, behind what is queued so far
 int after_handle(lf_map* m, lf_handle* h);        // the map's stream waits for everything queued so far on the handle's stream
 int release_handle(lf_map* m, lf_handle* h);      // the handle's later work waits for what the map has queued so far
 // rows_hint: how many segment rows the blocks really hold when the host knows it (-1: assume they are full)

@@ -295,6 +295,48 @@ class LineAssociator(object):
         """(ms, launches) of the localisation kernel since the previous call (needs set_profiling(True)); resets."""
         return self._stage_timing(self.lib.lf_map_localize_timing)
 
+    # ------------------------------------------------------------------ the map culled and compacted (lf_map_prune)
+    def prune_config(self, **overrides):
+        """The library's default `_lib.LfPruneConfig` (lf_map_prune_default_config: every rule off) with the overrides applied:
+        min_hits, weak_before, stale_before, keep_seeded, color_mask, use_box, box (x_min, y_min, x_max, y_max; sets use_box unless
+        it is given too), cover_distance, cover_slack, cover_max_entries."""
+        box = overrides.pop("box", None)
+        c = self._config("prune_config", _lib.LfPruneConfig, self.lib.lf_map_prune_default_config, overrides)
+        if box is not None:
+            for k, v in enumerate(np.asarray(box, np.float64).reshape(4)):
+                c.box[k] = float(v)
+            if "use_box" not in overrides:
+                c.use_box = 1
+        return c
+
+    def _prune(self, config, overrides, remap_ptr, on_device):
+        if config is not None and overrides:
+            raise TypeError("prune: give a config or overrides, not both")
+        config = self.prune_config(**overrides) if config is None else config
+        res = _lib.LfPruneResult()
+        self._check(self.lib.lf_map_prune(self.m, ctypes.byref(config), ctypes.byref(res), remap_ptr, on_device))
+        return {"size_before": res.size_before, "size_after": res.size_after,
+                "dropped": {"stale": res.n_stale, "weak": res.n_weak, "box": res.n_box, "covered": res.n_covered}}
+
+    def prune(self, config=None, remap=False, **overrides):
+        """Cull the map and compact the survivors, oldest first (lf_map_prune; waits for the map's stream).  config: an
+        `_lib.LfPruneConfig` (prune_config), or its fields as overrides.  Returns {'size_before', 'size_after', 'dropped': {'stale',
+        'weak', 'box', 'covered'}}, and with remap=True also 'remap': (capacity,) int32, for every index before the call the index
+        after it or -1 (for idx arrays of an earlier `associate`)."""
+        r = np.empty(self.capacity, np.int32) if remap else None
+        out = self._prune(config, overrides, None if r is None else r.ctypes.data, 0)
+        if remap:
+            out["remap"] = r
+        return out
+
+    def prune_device(self, remap_ptr=None, config=None, **overrides):
+        """`prune` with remap written to device memory at remap_ptr ((capacity,) int32; None: not wanted)."""
+        return self._prune(config, overrides, int(remap_ptr) if remap_ptr else None, 1)
+
+    def prune_timing(self):
+        """(ms, launches) of the prunes since the previous call (needs set_profiling(True)); one launch is one prune."""
+        return self._stage_timing(self.lib.lf_map_prune_timing)
+
     @staticmethod
     def carry(poses, last_odometry, last_corrected):
         """The next batch's odometry poses (n, 3) with the previous batch's correction applied: the rigid motion that takes

@@ -5,13 +5,16 @@ receives the kept segments (append-only, src/show_map/src/show_map.py:28-42) -> 
 wire bodies.  The first batch is checked against the oracle (pixels, segments, matches); the rest is timed.
 
     python tools/replay_demo.py [--frames 1024] [--batch 128] [--threads 32] [--geometry fullres|parity] [--map-jpeg map.jpg]
-                                [--overlay-jpeg DIR] [--align | --smooth | --localize]
+                                [--overlay-jpeg DIR] [--align | --smooth | --localize] [--prune EVERY[:min_hits[:age]]]
 
 --map-jpeg writes the final map as the reference's README shows it (show_map's coloured segments seen from above, lf_map_render
 fitted to the map) as a JPEG: rendered and encoded on the device, only the file's bytes cross the bus.
 --overlay-jpeg replays the frames once more when the map is final: each batch is decoded, rectified (lf_rectify_batch), has the map
 drawn into it as the camera sees it (lf_map_render_camera; the replay has no odometry, so every frame's pose is the identity, as the
 map's entries are in the robot frame) and is encoded on the device; the files go to DIR/%06d.jpg.
+--prune EVERY[:min_hits[:age]] culls the map every EVERY steps (lf_map_prune): entries with fewer than min_hits hits (default 2) that
+were last seen more than `age` steps ago (default 8) go, and so does every entry that a better one of its colour covers within 0.02 m,
+show_map's marker width; the seeded entries stay.  Each prune prints its result line.
 """
 import argparse, io, os, sys, time
 import numpy as np
@@ -45,7 +48,16 @@ mode.add_argument("--localize", action="store_true",
 mode.add_argument("--align", action="store_true",
                 help="correct every batch's poses against the map before the update (lf_map_step_aligned, the default configuration) and "
                      "print, per batch, how many frames came back with each status")
+ap.add_argument("--prune", default=None, metavar="EVERY[:min_hits[:age]]",
+                help="prune the map every EVERY steps: weak rule min_hits (default 2) for entries last seen more than age (default 8) steps "
+                     "ago, cover rule at 0.02 m; prints each result")
 args = ap.parse_args()
+prune_every, prune_min_hits, prune_age = 0, 2, 8
+if args.prune:
+    parts = [int(v) for v in args.prune.split(":")]
+    if not 1 <= len(parts) <= 3 or parts[0] < 1:
+        ap.error("--prune takes EVERY[:min_hits[:age]] with EVERY >= 1")
+    prune_every, prune_min_hits, prune_age = parts + [2, 8][len(parts) - 1:]
 torch.cuda.init()
 B = args.batch
 cfg = default_config(args.geometry)
@@ -122,6 +134,10 @@ for b0 in range(0, args.frames - B + 1, B):
         else:
             live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), step=b0 // B)
         live.synchronize()
+        step = b0 // B
+        if prune_every and (step + 1) % prune_every == 0:
+            r = live.prune(min_hits=prune_min_hits, weak_before=step - prune_age, cover_distance=0.02)
+            print("step %d pruned: %d -> %d entries (weak %d, covered %d)" % (step, r["size_before"], r["size_after"], r["dropped"]["weak"], r["dropped"]["covered"]))
         n_matched += int((di >= 0).sum().item())
         n_kept += int(seg.keep.sum())
     for stage in (sm.DETECTOR, sm.GROUND, sm.FILTERED):
