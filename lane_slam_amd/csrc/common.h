@@ -15,7 +15,7 @@ constexpr float kNotDef = -1024.0f; // LSD NOTDEF marker (angle plane, degrees)
 #define LF_LABEL_ITEMS 8192
 #endif
 constexpr int kLabelItems = LF_LABEL_ITEMS;   // problems up to AT LEAST this many defined pixels are split into connected components (LsdParams::label_items:
-                                    // a third of the LSD image, see lanefront_api.hip)
+                                    // a third of the LSD image, see LsdState::init in lanefront_lsd.hip)
 #ifndef LF_LABEL_LDS
 #define LF_LABEL_LDS 6144
 #endif
@@ -60,7 +60,7 @@ struct LsdParams {
     int label_items_max; // = label_items (rounds 2 - 3: a handle moved label_items up to this)
     int label_lds;      // problems of up to this many defined pixels are labelled in LDS, the others in the region scratch (k_lsd_label)
     int rec_cap;        // entries per problem of every per-problem list (records, compact arrays, seed lists, sort scratch): the stride of those
-                        // arrays.  Hs * Ws holds any problem; a batch handle starts lower and grows when a batch needs more (lanefront_api.hip)
+                        // arrays.  Hs * Ws holds any problem; a batch handle starts lower and grows when a batch needs more (lanefront_api.hip: init_lsd, lf_wait)
     // Round 6: what a region that STARTS at a pixel begins its two float sums with -- (float) cos / sin of the pixel's angle as a double
     // (region_grow adds every other pixel with the cosine of the angle rounded to float: the c_cs / c_sn pairs).  k_lsd_grad works it out
     // per record beside those, k_lsd_order gathers it ([rec_cap] float pairs per problem, like c_cs), k_lsd_grow loads the seed's pair

@@ -310,7 +310,7 @@ __global__ __launch_bounds__(LG_T) void k_lsd_grad(LsdParams p, ResizeTables rt,
         // one record per defined pixel; cos/sin of the float-rounded angle (what region growing
         // accumulates) evaluated on full waves.  Record order is arbitrary (k_lsd_order sorts by address).
         // (a problem with more records than the handle's lists hold: nothing is written, the need is reported, the host grows the
-        // lists and runs the batch again -- lanefront_api.hip: lsd_records_retry)
+        // lists and runs the batch again -- lanefront_api.hip: lf_wait, lf_set_image)
         const bool rec_fit = rec_base + nd <= p.rec_cap, low_fit = low_base + n_lo <= p.rec_cap;
         if (threadIdx.x == 0 && rec_need) {
             if (!rec_fit) atomicMax(rec_need, rec_base + nd);

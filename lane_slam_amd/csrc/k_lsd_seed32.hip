@@ -1833,7 +1833,7 @@ __global__ __launch_bounds__(ST, LF_SEED_OCC) void k_lsd_seed32(LsdParams p, int
     const int nl = n_low[pc];
     // The problem's lists hold rec_cap entries: the explicit list (at most nd + nl) must fit, and so must the low records (k_lsd_grad wrote
     // none of them otherwise).  A problem that does not fit is dropped from this batch (no seeds: k_lsd_grow leaves it alone) and its need
-    // reported; the host grows the lists and runs the batch again (lanefront_api.hip: lsd_records_retry).
+    // reported; the host grows the lists and runs the batch again (lanefront_api.hip: lf_wait, lf_set_image).
     if (nl > p.rec_cap || nd + nl > p.rec_cap) {
         if (t == 0) { atomicMax(rec_need, nd + nl); n_rec[pc] = 0; norder[pc] = 0; }
         return;

@@ -1,4 +1,5 @@
-// Host side of the anti-instagram estimate (k_ai.hip) and the setter of the transform k_pre applies.
+// Host side of the anti-instagram estimate (k_ai.hip), the setter of the transform k_pre applies, and the colour clustering the
+// estimate is made of as an entry point of its own (lf_kmeans, k_kmeans.hip).
 #include <math.h>
 #include "lanefront_handle.h"
 
@@ -45,9 +46,7 @@ extern "C" int lf_ai_transform_batch(lf_handle* h, const uint8_t* frames, int n_
     launch_ai_transform(strips, stride, n_frames, S, cols, static_cast<uint8_t*>(h->ai_lab.p), fo, fc, fs,
                         static_cast<lf_ai_transform*>(h->ai_out.p), s);
     LF_HIP_CHECK(h, hipGetLastError());
-    LF_HIP_CHECK(h, hipMemcpyAsync(out, h->ai_out.p, (size_t)n_frames * sizeof(lf_ai_transform), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    return LF_OK;
+    return fetch(h, { { out, h->ai_out.p, (size_t)n_frames * sizeof(lf_ai_transform) } });
 }
 
 extern "C" int lf_set_ai_transform(lf_handle* h, const double scale[3], const double shift[3])
@@ -79,5 +78,44 @@ extern "C" int lf_get_ai_transform(const lf_handle* h, double scale[3], double s
     if (!h) return LF_ERR_NOT_INITIALISED;
     if (!scale || !shift) return LF_ERR_BAD_ARG;
     for (int i = 0; i < 3; ++i) { scale[i] = h->cfg.ai_scale[i]; shift[i] = h->cfg.ai_shift[i]; }
+    return LF_OK;
+}
+
+// anti-instagram colour clustering (k_kmeans.hip): kmeans.py:22-47
+extern "C" int lf_kmeans(lf_handle* h, const uint8_t* bgr_points, int n, int on_device, int k, const double* init_centers, int max_iter,
+                         double tol, double* centers_out, long long* counts_out, double* inertia_out, int* n_iter_out)
+{
+    if (!h) return LF_ERR_NOT_INITIALISED;
+    if (!bgr_points || !init_centers || !centers_out || !counts_out || n < 1 || k < 1 || k > 16 || max_iter < 1) {
+        lf_set_error(h, LF_ERR_BAD_ARG, "lf_kmeans: null argument, n < 1, max_iter < 1 or k outside 1..16");
+        return LF_ERR_BAD_ARG;
+    }
+    if (n > (1 << 24)) {      // k_kmeans' per-wave 32-bit colour sums (64 lanes x n / 1024 points x 255) stay exact up to here
+        lf_set_error(h, LF_ERR_UNSUPPORTED, "lf_kmeans: more than 2^24 points (%d) are not supported", n);
+        return LF_ERR_UNSUPPORTED;
+    }
+    LF_HIP_CHECK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    int rc;
+    // f64 scratch: [0 .. 3k) init, [64 .. 64 + 3k] centres + inertia; counts: [k] + the status word behind them
+    if ((rc = scratch(h, h->km_lab, (size_t)n)) || (rc = scratch(h, h->km_f64, 128 * sizeof(double))) || (rc = scratch(h, h->km_cnt, 32 * sizeof(long long)))) return rc;
+    Staging st(h);
+    const uint8_t* dp = st.in(on_device, bgr_points, (size_t)n * 3, h->km_pts);
+    st.in(0, init_centers, (size_t)k * 3 * sizeof(double), h->km_f64);
+    if ((rc = st.upload()) != LF_OK) return rc;
+    double* f64 = static_cast<double*>(h->km_f64.p);
+    long long* cnt = static_cast<long long*>(h->km_cnt.p);
+    int* status = reinterpret_cast<int*>(cnt + 16);
+    launch_kmeans(dp, n, k, f64, max_iter, tol, static_cast<uint8_t*>(h->km_lab.p), f64 + 64, cnt, status, s);
+    LF_HIP_CHECK(h, hipGetLastError());
+    double res[49];
+    long long hc[17];
+    if ((rc = fetch(h, { { res, f64 + 64, (size_t)(3 * k + 1) * sizeof(double) }, { hc, cnt, 17 * sizeof(long long) } })) != LF_OK) return rc;
+    const int iters = *reinterpret_cast<int*>(&hc[16]);
+    if (iters < 0) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_kmeans: a cluster stayed empty (fewer distinct samples than clusters)"); return LF_ERR_BAD_ARG; }
+    for (int j = 0; j < 3 * k; ++j) centers_out[j] = res[j];
+    for (int j = 0; j < k; ++j) counts_out[j] = hc[j];
+    if (inertia_out) *inertia_out = res[3 * k];
+    if (n_iter_out) *n_iter_out = iters;
     return LF_OK;
 }

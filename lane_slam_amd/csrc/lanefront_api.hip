@@ -1,4 +1,6 @@
-// lanefront C ABI (include/lanefront.h): handle, device memory plan, stage sequencing.
+// lanefront C ABI (include/lanefront.h): the handle's life cycle and device memory plan, the parameter setters, the sequencing of
+// a batch's stages (run_detect, run_segments, lf_process_batch*, lf_wait), the plugin path and the timing.  The searches live in
+// lanefront_matcher.hip, the SegmentList glue in lanefront_msgs.hip, the debug entries in lanefront_debug.hip.
 // Host-side constants that enter the arithmetic (Gaussian taps, rho, LOG_NT, resize taps,
 // HSV division tables, LBD weights) are computed here with the same deterministic
 // routines (detmath.h) the kernels use, so they carry the same bits as the CPU oracle's.
@@ -8,10 +10,7 @@
 #include <math.h>
 #include <vector>
 #include <new>
-#include <atomic>
-#include <chrono>
 #include <cstdlib>
-#include <functional>
 #include "lanefront_handle.h"
 
 using namespace lf;
@@ -21,9 +20,6 @@ static const char* kStageNames[LF_N_STAGES] = {
     "lsd_order", "lsd_grow", "segments(normal+project+sanity)", "lbd_gray_blur_sobel", "lbd_descriptor",
     "assoc_pack", "assoc_mfma", "misc", "jpeg(idct+upsample+color)", "lsd_label(components+launch order)",
     "hough(probabilistic lines)", "dense(sobel-vote lines)" };
-
-
-
 
 extern "C" void lf_set_error(lf_handle* h, int code, const char* fmt, ...)
 {
@@ -35,10 +31,7 @@ extern "C" void lf_set_error(lf_handle* h, int code, const char* fmt, ...)
 
 static char g_create_err[512] = "no error";
 
-
-
 static int cv_round_host(double v) { return dm::round_half_even(v); }
-
 
 static int build_params(lf_handle* h)
 {
@@ -378,7 +371,6 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
     return LF_OK;
 }
 
-
 int lf::run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe)
 {
     hipStream_t s = h->stream;
@@ -509,21 +501,13 @@ extern "C" int lf_process_batch(lf_handle* h, const uint8_t* frames, int n_frame
     rc = lf_wait(h, &total);
     if (n_segments) *n_segments = total;
     if (rc != LF_OK) return rc;
-    hipStream_t s = h->stream;
-    if (!out_on_device) {
-        const size_t n = (size_t)total;
-        if (out->frame_offset) LF_HIP_CHECK(h, hipMemcpyAsync(out->frame_offset, h->d_frame_offset, (n_frames + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-        if (out->lines) LF_HIP_CHECK(h, hipMemcpyAsync(out->lines, dev.lines, n * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (out->normals) LF_HIP_CHECK(h, hipMemcpyAsync(out->normals, dev.normals, n * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (out->color) LF_HIP_CHECK(h, hipMemcpyAsync(out->color, dev.color, n, hipMemcpyDeviceToHost, s));
-        if (out->pixels_normalized) LF_HIP_CHECK(h, hipMemcpyAsync(out->pixels_normalized, dev.pixels_normalized, n * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (out->ground) LF_HIP_CHECK(h, hipMemcpyAsync(out->ground, dev.ground, n * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out->keep) LF_HIP_CHECK(h, hipMemcpyAsync(out->keep, dev.keep, n, hipMemcpyDeviceToHost, s));
-        if (describe && out->desc) LF_HIP_CHECK(h, hipMemcpyAsync(out->desc, dev.desc, n * 72 * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (describe && out->code) LF_HIP_CHECK(h, hipMemcpyAsync(out->code, dev.code, n * 32, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    }
-    return LF_OK;
+    if (out_on_device) return LF_OK;
+    const size_t n = (size_t)total;
+    return fetch(h, { { out->frame_offset, h->d_frame_offset.p, (n_frames + 1) * sizeof(int) }, { out->lines, dev.lines, n * 4 * sizeof(float) },
+                      { out->normals, dev.normals, n * 2 * sizeof(float) }, { out->color, dev.color, n },
+                      { out->pixels_normalized, dev.pixels_normalized, n * 4 * sizeof(float) }, { out->ground, dev.ground, n * 4 * sizeof(double) },
+                      { out->keep, dev.keep, n }, { describe ? out->desc : nullptr, dev.desc, n * 72 * sizeof(float) },
+                      { describe ? out->code : nullptr, dev.code, n * 32 } });
 }
 
 constexpr int kPlugEager = 1024;     // segments fetched with the image (more than a frame has at the plugin's geometries)
@@ -602,7 +586,6 @@ extern "C" int lf_detect_lines(lf_handle* h, int color, float* lines4, double* n
     if (!h->plugin_ready) { lf_set_error(h, LF_ERR_NOT_INITIALISED, "lf_detect_lines before lf_set_image"); return LF_ERR_NOT_INITIALISED; }
     if (!n_out) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_detect_lines: n_out is null"); return LF_ERR_BAD_ARG; }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
     int n = h->h_counts[color];
     if (n > h->cap_lines) { lf_set_error(h, LF_ERR_CAPACITY, "%s found %d lines, max_lines_per_color is %d", detector_name(h->detector), n, h->cap_lines); return LF_ERR_CAPACITY; }
     if (n > cap) { lf_set_error(h, LF_ERR_CAPACITY, "%d lines exceed caller capacity %d", n, cap); return LF_ERR_CAPACITY; }
@@ -620,264 +603,11 @@ extern "C" int lf_detect_lines(lf_handle* h, int color, float* lines4, double* n
         *n_out = n;
         return LF_OK;
     }
-    if (n > 0) {
-        if (lines4) LF_HIP_CHECK(h, hipMemcpyAsync(lines4, h->d_out.lines + off * 4, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (normals2) LF_HIP_CHECK(h, hipMemcpyAsync(normals2, h->d_normals64 + off * 2, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (centers2) LF_HIP_CHECK(h, hipMemcpyAsync(centers2, h->d_centers + off * 2, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
-    if (area_or_null) LF_HIP_CHECK(h, hipMemcpyAsync(area_or_null, static_cast<uint8_t*>(h->dbg_masks.p) + (size_t)color * h->P, h->P, hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
+    const size_t c = (size_t)n;
+    if (const int rc = fetch(h, { { lines4, h->d_out.lines + off * 4, c * 4 * sizeof(float) }, { normals2, h->d_normals64 + off * 2, c * 2 * sizeof(double) },
+                                  { centers2, h->d_centers + off * 2, c * 2 * sizeof(float) },
+                                  { area_or_null, static_cast<uint8_t*>(h->dbg_masks.p) + (size_t)color * h->P, h->P } })) return rc;
     *n_out = n;
-    return LF_OK;
-}
-
-extern "C" int lf_associate(lf_handle* h, const uint8_t* query32, int nq, const uint8_t* map32, int nm,
-                            int32_t* idx, float* dist, int on_device)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (nq < 0 || nm < 0 || (nq > 0 && (!query32 || !idx || !dist)) || (nm > 0 && !map32)) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_associate: bad argument"); return LF_ERR_BAD_ARG; }
-    if (nm > (1 << 21)) { lf_set_error(h, LF_ERR_UNSUPPORTED, "map larger than 2^21 entries"); return LF_ERR_UNSUPPORTED; }
-    if (nq == 0) return LF_OK;
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    if (nm == 0) {
-        // descriptor matrices cannot be void (binary_descriptor_matcher.cpp:201-205): report "no match"
-        std::vector<int32_t> hi(nq, -1); std::vector<float> hd(nq, -1.f);
-        if (on_device) {
-            LF_HIP_CHECK(h, hipMemcpyAsync(idx, hi.data(), nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            LF_HIP_CHECK(h, hipMemcpyAsync(dist, hd.data(), nq * sizeof(float), hipMemcpyHostToDevice, s));
-            LF_HIP_CHECK(h, hipStreamSynchronize(s));
-        } else { memcpy(idx, hi.data(), nq * sizeof(int32_t)); memcpy(dist, hd.data(), nq * sizeof(float)); }
-        return LF_OK;
-    }
-    const size_t nm_pad = assoc_rows_padded_m(nm);
-    int rc;
-    if ((rc = scratch(h, h->a_mx, nm_pad * 256)) != LF_OK) return rc;     // 256 B per 128-B row: the tile loop's LDS-DMA read-ahead is not shown to stay within 128 B x nm_pad
-    const bool ties = h->tie_rule == LF_TIE_MIHASHER;
-    if (ties && (rc = scratch(h, h->a_best, (size_t)nq * 8)) != LF_OK) return rc;
-    const uint8_t *dq = query32, *dmp = map32;
-    int32_t* didx = idx; float* ddist = dist;
-    if (!on_device) {
-        if ((rc = scratch(h, h->a_q, (size_t)nq * 32)) || (rc = scratch(h, h->a_m, (size_t)nm * 32)) ||
-            (rc = scratch(h, h->a_idx, (size_t)nq * 4)) || (rc = scratch(h, h->a_dist, (size_t)nq * 4))) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->a_q.p, query32, (size_t)nq * 32, hipMemcpyHostToDevice, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->a_m.p, map32, (size_t)nm * 32, hipMemcpyHostToDevice, s));
-        dq = (const uint8_t*)h->a_q.p; dmp = (const uint8_t*)h->a_m.p; didx = (int32_t*)h->a_idx.p; ddist = (float*)h->a_dist.p;
-    }
-    {
-        StageClock::Scope t(h, h->clock, ST_ASSOC);
-        h->a_ws.tie_res = ties ? static_cast<unsigned long long*>(h->a_best.p) : nullptr;      // (the distance pass then lists the queries of the tie pass)
-        LF_HIP_CHECK(h, launch_assoc(dq, nq, dmp, nm, (int8_t*)h->a_mx.p, h->a_ws, didx, ddist, s));
-        if (ties)
-            LF_HIP_CHECK(h, launch_assoc_ties(dq, nullptr, nq, (const int8_t*)h->a_mx.p, dmp, nullptr, nm, nullptr, 0, h->a_ws,
-                                              static_cast<unsigned long long*>(h->a_best.p), didx, ddist, s));
-    }
-    LF_HIP_CHECK(h, hipGetLastError());
-    if (!on_device) {
-        LF_HIP_CHECK(h, hipMemcpyAsync(idx, didx, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(dist, ddist, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    }
-    return LF_OK;
-}
-
-extern "C" int lf_set_tie_rule(lf_handle* h, int tie_rule)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (tie_rule != LF_TIE_LOWEST && tie_rule != LF_TIE_MIHASHER) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_tie_rule: unknown rule %d", tie_rule); return LF_ERR_BAD_ARG; }
-    h->tie_rule = tie_rule;
-    return LF_OK;
-}
-
-extern "C" int lf_associate_float(lf_handle* h, const float* query72, int nq, const float* map72, int nm,
-                                  int32_t* idx, float* dist, int on_device)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (nq <= 0 || nm <= 0 || !query72 || !map72 || !idx || !dist) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_associate_float: bad argument"); return LF_ERR_BAD_ARG; }
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    int rc;
-    if ((rc = scratch(h, h->a_best, assoc_float_scratch_bytes(nq, nm))) || (rc = scratch(h, h->a_qn, (size_t)nq * 4)) || (rc = scratch(h, h->a_mn, (size_t)nm * 4))) return rc;
-    const float *dq = query72, *dmp = map72;
-    int32_t* didx = idx; float* ddist = dist;
-    if (!on_device) {
-        if ((rc = scratch(h, h->a_q, (size_t)nq * 288)) || (rc = scratch(h, h->a_m, (size_t)nm * 288)) ||
-            (rc = scratch(h, h->a_idx, (size_t)nq * 4)) || (rc = scratch(h, h->a_dist, (size_t)nq * 4))) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->a_q.p, query72, (size_t)nq * 288, hipMemcpyHostToDevice, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->a_m.p, map72, (size_t)nm * 288, hipMemcpyHostToDevice, s));
-        dq = (const float*)h->a_q.p; dmp = (const float*)h->a_m.p; didx = (int32_t*)h->a_idx.p; ddist = (float*)h->a_dist.p;
-    }
-    {
-        StageClock::Scope t(h, h->clock, ST_ASSOC);
-        LF_HIP_CHECK(h, launch_assoc_float(dq, nq, dmp, nm, (float*)h->a_qn.p, (float*)h->a_mn.p, h->a_best.p, didx, ddist, s));
-    }
-    LF_HIP_CHECK(h, hipGetLastError());
-    if (!on_device) {
-        LF_HIP_CHECK(h, hipMemcpyAsync(idx, didx, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(dist, ddist, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    }
-    return LF_OK;
-}
-
-// knnMatch / radiusMatch (binary_descriptor_matcher.cpp:258-335, 428-504): k_knn.hip
-extern "C" int lf_select_queries(lf_handle* h, const uint8_t* query32, int nq, const uint8_t* mask, uint8_t* selected32, int32_t* query_idx,
-                                 int* n_selected, int on_device)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (nq < 0 || !n_selected || (nq > 0 && (!query32 || !mask || !selected32 || !query_idx))) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_select_queries: bad argument"); return LF_ERR_BAD_ARG; }
-    *n_selected = 0;
-    if (nq == 0) return LF_OK;
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    int rc;
-    if ((rc = scratch(h, h->kn_total, 4 * sizeof(int))) != LF_OK) return rc;
-    const uint8_t *dq = query32, *dmask = mask;
-    uint8_t* dsel = selected32; int32_t* dqi = query_idx;
-    if (!on_device) {
-        if ((rc = scratch(h, h->a_q, (size_t)nq * 32)) || (rc = scratch(h, h->a_m, (size_t)nq * 33)) || (rc = scratch(h, h->a_idx, (size_t)nq * 4))) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->a_q.p, query32, (size_t)nq * 32, hipMemcpyHostToDevice, s));
-        uint8_t* m8 = static_cast<uint8_t*>(h->a_m.p) + (size_t)nq * 32;
-        LF_HIP_CHECK(h, hipMemcpyAsync(m8, mask, (size_t)nq, hipMemcpyHostToDevice, s));
-        dq = static_cast<const uint8_t*>(h->a_q.p); dmask = m8; dsel = static_cast<uint8_t*>(h->a_m.p); dqi = static_cast<int32_t*>(h->a_idx.p);
-    }
-    launch_select_queries(dq, dmask, nq, dsel, dqi, static_cast<int*>(h->kn_total.p), s);
-    LF_HIP_CHECK(h, hipGetLastError());
-    int n = 0;
-    LF_HIP_CHECK(h, hipMemcpyAsync(&n, h->kn_total.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    *n_selected = n;
-    if (!on_device && n > 0) {
-        LF_HIP_CHECK(h, hipMemcpyAsync(selected32, dsel, (size_t)n * 32, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(query_idx, dqi, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    }
-    return LF_OK;
-}
-
-extern "C" int lf_knn_match(lf_handle* h, const uint8_t* query32, int nq, const uint8_t* map32, int nm, int k, int32_t* idx, float* dist,
-                            int on_device)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (nq < 0 || nm < 0 || k < 1 || k > 16 || (nq > 0 && (!query32 || !idx || !dist)) || (nm > 0 && !map32)) {
-        lf_set_error(h, LF_ERR_BAD_ARG, "lf_knn_match: bad argument (k must be 1..16)");
-        return LF_ERR_BAD_ARG;
-    }
-    if (nm > (1 << 24)) { lf_set_error(h, LF_ERR_UNSUPPORTED, "lf_knn_match: map larger than 2^24 entries"); return LF_ERR_UNSUPPORTED; }
-    if (nq == 0) return LF_OK;
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    int rc;
-    const uint8_t *dq = query32, *dm_ = map32;
-    int32_t* didx = idx; float* ddist = dist;
-    const size_t out = (size_t)nq * k;
-    if (!on_device) {
-        if ((rc = scratch(h, h->a_q, (size_t)nq * 32)) || (rc = scratch(h, h->a_m, (size_t)(nm > 0 ? nm : 1) * 32)) ||
-            (rc = scratch(h, h->a_idx, out * 4)) || (rc = scratch(h, h->a_dist, out * 4))) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->a_q.p, query32, (size_t)nq * 32, hipMemcpyHostToDevice, s));
-        if (nm > 0) LF_HIP_CHECK(h, hipMemcpyAsync(h->a_m.p, map32, (size_t)nm * 32, hipMemcpyHostToDevice, s));
-        dq = (const uint8_t*)h->a_q.p; dm_ = (const uint8_t*)h->a_m.p; didx = (int32_t*)h->a_idx.p; ddist = (float*)h->a_dist.p;
-    }
-    { StageClock::Scope t(h, h->clock, ST_ASSOC); launch_knn(dq, nq, dm_, nm, k, 128, h->tie_rule == LF_TIE_MIHASHER, didx, ddist, s); }
-    LF_HIP_CHECK(h, hipGetLastError());
-    if (!on_device) {
-        LF_HIP_CHECK(h, hipMemcpyAsync(idx, didx, out * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(dist, ddist, out * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    }
-    return LF_OK;
-}
-
-extern "C" int lf_radius_match(lf_handle* h, const uint8_t* query32, int nq, const uint8_t* map32, int nm, float max_distance,
-                               int32_t* offsets, int32_t* idx, float* dist, int cap, int* total_out, int on_device)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (nq < 0 || nm < 0 || cap < 0 || !offsets || (cap > 0 && (!idx || !dist)) || (nq > 0 && !query32) || (nm > 0 && !map32) || !(max_distance >= 0)) {
-        lf_set_error(h, LF_ERR_BAD_ARG, "lf_radius_match: bad argument");
-        return LF_ERR_BAD_ARG;
-    }
-    if (nm > (1 << 24)) { lf_set_error(h, LF_ERR_UNSUPPORTED, "lf_radius_match: map larger than 2^24 entries"); return LF_ERR_UNSUPPORTED; }
-    // K = N results are only ever collected up to D = 128 bits (Mihasher, :721), then filtered by maxDistance (:474)
-    int md = max_distance >= 128.f ? 128 : (int)max_distance;
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    if (nq == 0) { if (on_device) LF_HIP_CHECK(h, hipMemsetAsync(offsets, 0, sizeof(int32_t), s)); else offsets[0] = 0; if (total_out) *total_out = 0; return LF_OK; }
-    int rc;
-    if ((rc = scratch(h, h->kn_hist, (size_t)nq * 129 * 4)) || (rc = scratch(h, h->kn_count, (size_t)nq * 4)) || (rc = scratch(h, h->kn_off, (size_t)(nq + 1) * 4)) ||
-        (rc = scratch(h, h->kn_total, 16))) return rc;
-    const uint8_t *dq = query32, *dm_ = map32;
-    int32_t *doff = offsets, *didx = idx; float* ddist = dist;
-    if (!on_device) {
-        if ((rc = scratch(h, h->a_q, (size_t)nq * 32)) || (rc = scratch(h, h->a_m, (size_t)(nm > 0 ? nm : 1) * 32)) ||
-            (rc = scratch(h, h->a_idx, (size_t)(cap > 0 ? cap : 1) * 4)) || (rc = scratch(h, h->a_dist, (size_t)(cap > 0 ? cap : 1) * 4))) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->a_q.p, query32, (size_t)nq * 32, hipMemcpyHostToDevice, s));
-        if (nm > 0) LF_HIP_CHECK(h, hipMemcpyAsync(h->a_m.p, map32, (size_t)nm * 32, hipMemcpyHostToDevice, s));
-        dq = (const uint8_t*)h->a_q.p; dm_ = (const uint8_t*)h->a_m.p; doff = (int32_t*)h->kn_off.p; didx = (int32_t*)h->a_idx.p; ddist = (float*)h->a_dist.p;
-    }
-    {
-        StageClock::Scope t(h, h->clock, ST_ASSOC);
-        launch_radius(dq, nq, dm_, nm, md, (int32_t*)h->kn_hist.p, (int32_t*)h->kn_count.p, doff, (int*)h->kn_total.p, cap, h->tie_rule == LF_TIE_MIHASHER, didx, ddist, s);
-    }
-    LF_HIP_CHECK(h, hipGetLastError());
-    int total = 0;
-    LF_HIP_CHECK(h, hipMemcpyAsync(&total, h->kn_total.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    if (!on_device) LF_HIP_CHECK(h, hipMemcpyAsync(offsets, doff, (size_t)(nq + 1) * 4, hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    if (total_out) *total_out = total;
-    if (total > cap) { lf_set_error(h, LF_ERR_CAPACITY, "lf_radius_match: %d matches exceed the capacity %d (offsets are complete: size the arrays from them)", total, cap); return LF_ERR_CAPACITY; }
-    if (!on_device && total > 0) {
-        LF_HIP_CHECK(h, hipMemcpyAsync(idx, didx, (size_t)total * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(dist, ddist, (size_t)total * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    }
-    return LF_OK;
-}
-
-// LSD alone on a caller-supplied binary image (any non-zero byte = edge pixel): the LSD stages
-// of the pipeline (gradient -> order -> grow) with the colour mask forced to all ones.  Test and
-// diagnosis entry; lines are in working-image pixels before normal-based reordering, exactly what
-// cv2's detect() would return for this image under the oracle's restatement.
-// anti-instagram colour clustering (k_kmeans.hip): kmeans.py:22-47
-extern "C" int lf_kmeans(lf_handle* h, const uint8_t* bgr_points, int n, int on_device, int k, const double* init_centers, int max_iter,
-                         double tol, double* centers_out, long long* counts_out, double* inertia_out, int* n_iter_out)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (!bgr_points || !init_centers || !centers_out || !counts_out || n < 1 || k < 1 || k > 16 || max_iter < 1) {
-        lf_set_error(h, LF_ERR_BAD_ARG, "lf_kmeans: null argument, n < 1, max_iter < 1 or k outside 1..16");
-        return LF_ERR_BAD_ARG;
-    }
-    if (n > (1 << 24)) {      // k_kmeans' per-wave 32-bit colour sums (64 lanes x n / 1024 points x 255) stay exact up to here
-        lf_set_error(h, LF_ERR_UNSUPPORTED, "lf_kmeans: more than 2^24 points (%d) are not supported", n);
-        return LF_ERR_UNSUPPORTED;
-    }
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    int rc;
-    // f64 scratch: [0 .. 3k) init, [64 .. 64 + 3k] centres + inertia; counts: [k] + the status word behind them
-    if ((rc = scratch(h, h->km_lab, (size_t)n)) || (rc = scratch(h, h->km_f64, 128 * sizeof(double))) || (rc = scratch(h, h->km_cnt, 32 * sizeof(long long)))) return rc;
-    const uint8_t* dp = bgr_points;
-    if (!on_device) {
-        if ((rc = scratch(h, h->km_pts, (size_t)n * 3)) != LF_OK) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->km_pts.p, bgr_points, (size_t)n * 3, hipMemcpyHostToDevice, s));
-        dp = static_cast<const uint8_t*>(h->km_pts.p);
-    }
-    double* f64 = static_cast<double*>(h->km_f64.p);
-    long long* cnt = static_cast<long long*>(h->km_cnt.p);
-    int* status = reinterpret_cast<int*>(cnt + 16);
-    LF_HIP_CHECK(h, hipMemcpyAsync(f64, init_centers, (size_t)k * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    launch_kmeans(dp, n, k, f64, max_iter, tol, static_cast<uint8_t*>(h->km_lab.p), f64 + 64, cnt, status, s);
-    LF_HIP_CHECK(h, hipGetLastError());
-    double res[49];
-    long long hc[17];
-    LF_HIP_CHECK(h, hipMemcpyAsync(res, f64 + 64, (size_t)(3 * k + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipMemcpyAsync(hc, cnt, 17 * sizeof(long long), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    const int iters = *reinterpret_cast<int*>(&hc[16]);
-    if (iters < 0) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_kmeans: a cluster stayed empty (fewer distinct samples than clusters)"); return LF_ERR_BAD_ARG; }
-    for (int j = 0; j < 3 * k; ++j) centers_out[j] = res[j];
-    for (int j = 0; j < k; ++j) counts_out[j] = hc[j];
-    if (inertia_out) *inertia_out = res[3 * k];
-    if (n_iter_out) *n_iter_out = iters;
     return LF_OK;
 }
 
@@ -901,148 +631,10 @@ extern "C" int lf_suggested_depth(const lf_handle* h)
     return h->lsd.grow_lds_level == 0 && !h->lsd.grow_mixed ? 8 : 18;
 }
 
-extern "C" int lf_debug_std_sort(lf_handle* h, const int32_t* keys, int n, int32_t* order)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (!keys || !order || n < 1 || n >= (1 << 20)) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_debug_std_sort: bad argument (1 <= n < 2^20)"); return LF_ERR_BAD_ARG; }
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    std::vector<uint32_t> e((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        if (keys[i] < 0 || keys[i] > 1023) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_debug_std_sort: keys must be in [0, 1023]"); return LF_ERR_BAD_ARG; }
-        e[i] = ((uint32_t)keys[i] << 20) | (uint32_t)(i + 1);
-    }
-    int rc;
-    const size_t words = std_sort_debug_words(n);
-    if ((rc = scratch(h, h->a_q, (size_t)n * 4)) || (rc = scratch(h, h->a_m, words * 4)) || (rc = scratch(h, h->a_best, 64))) return rc;
-    LF_HIP_CHECK(h, hipMemcpyAsync(h->a_q.p, e.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    launch_std_sort_debug(static_cast<const uint32_t*>(h->a_q.p), static_cast<uint32_t*>(h->a_m.p), n, static_cast<int*>(h->a_best.p), s);
-    LF_HIP_CHECK(h, hipGetLastError());
-    int cnt = 0;
-    LF_HIP_CHECK(h, hipMemcpyAsync(&cnt, h->a_best.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    // the sorted non-zero keys sit in the `out` area of the work buffer (k_lsd_seed32.hip: seed_work): 4 * cap words in
-    const size_t cap = words / 12;
-    if (cnt > 0) LF_HIP_CHECK(h, hipMemcpy(e.data(), static_cast<uint32_t*>(h->a_m.p) + 4 * cap, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < cnt; ++i) order[i] = (int32_t)(e[i] & 0xfffffu);
-    // the elements with key 0 (the detector's flat pixels) are anonymous: listed behind, by index
-    {
-        int k = cnt;
-        for (int i = 0; i < n; ++i) if (keys[i] == 0) order[k++] = i;
-    }
-    return LF_OK;
-}
-
-extern "C" int lf_debug_lsd_binary(lf_handle* h, const uint8_t* img, int rows, int cols, float* lines4, int cap, int* n_out)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (!img || !lines4 || !n_out || rows != h->Hc || cols != h->W) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_debug_lsd_binary: bad argument (image must be %dx%d)", h->Hc, h->W); return LF_ERR_BAD_ARG; }
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    if ((size_t)h->lsd.params.rec_cap < h->lsd.Ps) {        // (a debug entry: any binary image must fit -- whole-image lists from here on)
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
-        const int rc = h->lsd.grow_lists(h, (int)h->lsd.Ps);
-        if (rc != LF_OK) return rc;
-    }
-    const size_t nw = (size_t)h->Hc * h->Ww;
-    std::vector<uint32_t> bits(nw, 0u), ones(nw * 3, 0xffffffffu);
-    for (int y = 0; y < rows; ++y)
-        for (int x = 0; x < cols; ++x)
-            if (img[(size_t)y * cols + x]) bits[(size_t)y * h->Ww + (x >> 5)] |= 1u << (x & 31);
-    LF_HIP_CHECK(h, hipMemcpyAsync(h->d_strong, bits.data(), nw * 4, hipMemcpyHostToDevice, s));
-    LF_HIP_CHECK(h, hipMemcpyAsync(h->d_maskbits, ones.data(), nw * 12, hipMemcpyHostToDevice, s));
-    LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_maxgrad, 0, 3 * sizeof(unsigned long long), s));
-    h->lsd.grad(1, h->d_strong, h->d_maskbits, false, s);
-    h->lsd.order(1, 0, s);
-    h->lsd.label(1, false, s);
-    h->lsd.grow(1, h->d_slot_lines, h->d_counts, kGrowLdsKb[h->lsd.grow_lds_level], true, false, s);
-    LF_HIP_CHECK(h, hipGetLastError());
-    int n = 0;
-    LF_HIP_CHECK(h, hipMemcpyAsync(&n, h->d_counts, sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    h->last_frames = 1;
-    h->plugin_ready = false;
-    *n_out = n;
-    if (n > h->cap_lines) { lf_set_error(h, LF_ERR_CAPACITY, "LSD found %d lines, max_lines_per_color is %d", n, h->cap_lines); return LF_ERR_CAPACITY; }
-    if (n > cap) { lf_set_error(h, LF_ERR_CAPACITY, "%d lines exceed caller capacity %d", n, cap); return LF_ERR_CAPACITY; }
-    if (n > 0) LF_HIP_CHECK(h, hipMemcpy(lines4, h->d_slot_lines, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    return LF_OK;
-}
-
 extern "C" int lf_lsd_size(const lf_handle* h, int* rows, int* cols)
 {
     if (!h || !rows || !cols) return LF_ERR_BAD_ARG;
     *rows = h->lsd.params.Hs; *cols = h->lsd.params.Ws;
-    return LF_OK;
-}
-
-extern "C" int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t bytes)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (!dst) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_debug_fetch: null dst"); return LF_ERR_BAD_ARG; }
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    const size_t n = (size_t)h->last_frames;
-    const void* src = nullptr;
-    size_t avail = 0;
-    switch (buffer_id) {
-    case LF_BUF_BGR: {
-        int rc = scratch(h, h->dbg_bgr, n * h->P * 3);
-        if (rc != LF_OK) return rc;
-        launch_bgrx_to_bgr((int)(n * h->P), h->d_bgr, (uint8_t*)h->dbg_bgr.p, s);
-        src = h->dbg_bgr.p; avail = n * h->P * 3; break;
-    }
-    case LF_BUF_MASKS: {
-        int rc = scratch(h, h->dbg_masks, n * 3 * h->P);
-        if (rc != LF_OK) return rc;
-        launch_edges_u8(h->canny, (int)(n * 3), h->d_maskbits, (uint8_t*)h->dbg_masks.p, s);     // same bit-plane layout as the edge map
-        src = h->dbg_masks.p; avail = n * 3 * h->P; break;
-    }
-    case LF_BUF_EDGES:
-        launch_edges_u8(h->canny, (int)n, h->d_strong, h->d_edges_u8, s);
-        src = h->d_edges_u8; avail = n * h->P; break;
-    case LF_BUF_LSD_ANGLE:
-    case LF_BUF_LSD_MODGRAD: {
-        // the pipeline keeps no dense LSD planes: rebuild them from the compact arrays
-        const LsdState& L = h->lsd;
-        int rc = scratch(h, h->dbg_ang, n * 3 * L.Ps * sizeof(float));
-        if (rc == LF_OK) rc = scratch(h, h->dbg_mod, n * 3 * L.Ps * sizeof(double));
-        if (rc != LF_OK) return rc;
-        launch_lsd_dense_debug(L.params, (int)n, L.d_norder, L.d_cxy, L.d_cdeg, L.d_cmod, (float*)h->dbg_ang.p, (double*)h->dbg_mod.p, s);
-        if (buffer_id == LF_BUF_LSD_ANGLE) { src = h->dbg_ang.p; avail = n * 3 * L.Ps * sizeof(float); }
-        else { src = h->dbg_mod.p; avail = n * 3 * L.Ps * sizeof(double); }
-        break;
-    }
-    case LF_BUF_LSD_ORDER: {
-        // [frames][3][Hs * Ws] for the caller; the handle's lists have rec_cap entries per problem
-        const size_t row = h->lsd.Ps * sizeof(uint32_t), have = (size_t)h->lsd.params.rec_cap * sizeof(uint32_t);
-        if (bytes > n * 3 * row) { lf_set_error(h, LF_ERR_CAPACITY, "buffer %d holds %zu bytes, %zu requested", buffer_id, n * 3 * row, bytes); return LF_ERR_CAPACITY; }
-        LF_HIP_CHECK(h, hipMemcpy2DAsync(dst, row, h->lsd.d_order_a, have, have, bytes / row, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
-        return LF_OK;
-    }
-    case LF_BUF_LSD_NORDER: src = h->lsd.d_norder; avail = n * 3 * sizeof(int); break;
-    case LF_BUF_LBD_DX:
-    case LF_BUF_LBD_DY: {
-        // the pipeline keeps dx and dy interleaved: split them for the caller
-        int rc = scratch(h, h->dbg_dx, n * h->P * sizeof(int16_t));
-        if (rc == LF_OK) rc = scratch(h, h->dbg_dy, n * h->P * sizeof(int16_t));
-        if (rc != LF_OK) return rc;
-        launch_lbd_split_debug(n * h->P, h->d_dxy, (int16_t*)h->dbg_dx.p, (int16_t*)h->dbg_dy.p, s);
-        src = buffer_id == LF_BUF_LBD_DX ? h->dbg_dx.p : h->dbg_dy.p;
-        avail = n * h->P * sizeof(int16_t);
-        break;
-    }
-    case LF_BUF_LSD_COUNTS: src = h->d_counts; avail = n * 3 * sizeof(int); break;
-    case LF_BUF_LSD_NLOW:
-        if (!h->lsd.d_nlow) { memset(dst, 0, bytes < n * 3 * sizeof(int) ? bytes : n * 3 * sizeof(int)); return LF_OK; }
-        src = h->lsd.d_nlow; avail = n * 3 * sizeof(int); break;
-    case LF_BUF_LSD_SCRATCH: src = h->lsd.d_reg; avail = n * 3 * lsd_grow_reg_stride(h->lsd.params) * sizeof(uint32_t); break;
-    default: lf_set_error(h, LF_ERR_BAD_ARG, "unknown buffer id %d", buffer_id); return LF_ERR_BAD_ARG;
-    }
-    if (bytes > avail) { lf_set_error(h, LF_ERR_CAPACITY, "buffer %d holds %zu bytes, %zu requested", buffer_id, avail, bytes); return LF_ERR_CAPACITY; }
-    LF_HIP_CHECK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
     return LF_OK;
 }
 
@@ -1073,286 +665,6 @@ extern "C" int lf_get_timing(lf_handle* h, double* ms_per_stage, int32_t* launch
     for (int i = 0; i < n && i < LF_N_STAGES; ++i) {
         if (ms_per_stage) ms_per_stage[i] = h->clock.ms[i];
         if (launches_per_stage) launches_per_stage[i] = h->clock.launches[i];
-    }
-    return LF_OK;
-}
-
-// ---------------------------------------------------------------------------------------- JPEG ingest
-extern "C" int lf_jpeg_info(const uint8_t* jpeg, size_t jpeg_size, int* rows, int* cols, int* components, int* hmax, int* vmax)
-{
-    if (!jpeg) return LF_ERR_BAD_ARG;
-    return lf::jpeg::peek(jpeg, jpeg_size, rows, cols, components, hmax, vmax);
-}
-
-extern "C" int lf_frames_buffer(lf_handle* h, uint8_t** device_ptr, size_t* bytes)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (device_ptr) *device_ptr = h->d_frames;
-    if (bytes) *bytes = h->frames_bytes;
-    return LF_OK;
-}
-
-extern "C" int lf_jpeg_decode_batch(lf_handle* h, const uint8_t* const* jpeg, const size_t* jpeg_size, int n_frames,
-                                    int rows, int cols, uint8_t* frames, int frames_on_device, int n_threads,
-                                    int* frame_status)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (!jpeg || !jpeg_size || !frames || n_frames < 1 || rows < 1 || cols < 1 || rows > 65535 || cols > 65535) {
-        lf_set_error(h, LF_ERR_BAD_ARG, "lf_jpeg_decode_batch: null argument, n_frames < 1 or bad size %dx%d", rows, cols);
-        return LF_ERR_BAD_ARG;
-    }
-    if (n_frames > 65535) { lf_set_error(h, LF_ERR_CAPACITY, "lf_jpeg_decode_batch: at most 65535 frames per call"); return LF_ERR_CAPACITY; }
-    if (frames_on_device && frames == h->d_frames &&
-        (size_t)n_frames * rows * cols * 3 > h->frames_bytes) {
-        lf_set_error(h, LF_ERR_CAPACITY, "lf_jpeg_decode_batch: %d frames of %dx%d do not fit the handle's frame buffer (%d of %dx%d)",
-                     n_frames, rows, cols, h->max_frames, h->cfg.in_rows, h->cfg.in_cols);
-        return LF_ERR_CAPACITY;
-    }
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    if (!h->jpeg) {
-        h->jpeg.reset(new (std::nothrow) JpegState());
-        if (!h->jpeg) { lf_set_error(h, LF_ERR_HIP, "out of host memory"); return LF_ERR_HIP; }
-        LF_HIP_CHECK(h, hipEventCreateWithFlags(&h->jpeg->staged, hipEventDisableTiming));
-    }
-    JpegState& J = *h->jpeg;
-    hipStream_t s = h->stream;
-    static const bool trace = getenv("LF_JPEG_TRACE") != nullptr;       // diagnostic: per-phase host times on stderr
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
-    const auto t_begin = now();
-    double t_decode = 0, t_wait = 0, t_pack = 0;
-    if ((int)J.frames.size() < n_frames) J.frames.resize((size_t)n_frames);
-
-    // ---- host: entropy decoding, one frame per task
-    int nt = n_threads > 0 ? n_threads : (n_frames < 64 ? n_frames : 64);
-    if (nt > n_frames) nt = n_frames;
-    {
-        std::atomic<int> next(0);
-        J.pool.run(nt, [&](int) {
-            for (;;) {
-                const int i = next.fetch_add(1);
-                if (i >= n_frames) break;
-                lf::jpeg::FrameCoefs& fc = J.frames[(size_t)i];
-                if (!jpeg[i]) { fc.status = LF_ERR_BAD_ARG; fc.hdr.valid = 0; fc.hdr.nblocks = 0; fc.n_entries = 0; continue; }
-                // a stream of another size than the batch was declared with is refused right after its headers
-                // (LF_ERR_BAD_ARG), before any host buffer is sized from the stream's own fields
-                (void)lf::jpeg::decode_coefficients(jpeg[i], jpeg_size[i], fc, rows, cols);
-                if (fc.status != LF_OK) { fc.hdr.valid = 0; fc.hdr.nblocks = 0; fc.n_entries = 0; }
-            }
-        });
-    }
-    t_decode = ms_since(t_begin);
-    // ---- layout of the batch
-    size_t total_entries = 0, total_blocks = 0;
-    int max_blocks = 0, n_failed = 0, first_error = LF_OK;
-    for (int i = 0; i < n_frames; ++i) {
-        lf::jpeg::FrameCoefs& fc = J.frames[(size_t)i];
-        if (frame_status) frame_status[i] = fc.status;
-        if (fc.status != LF_OK) { ++n_failed; if (first_error == LF_OK) first_error = fc.status; }
-        fc.hdr.entry_base = (uint32_t)total_entries;
-        fc.hdr.block_base = (uint32_t)total_blocks;
-        total_entries += fc.n_entries;
-        total_blocks += (size_t)fc.hdr.nblocks;
-        if (fc.hdr.nblocks > max_blocks) max_blocks = fc.hdr.nblocks;
-    }
-    if (total_entries >= (1ull << 32) || total_blocks >= (1ull << 32)) { lf_set_error(h, LF_ERR_CAPACITY, "batch too large"); return LF_ERR_CAPACITY; }
-    const size_t hdr_bytes = (size_t)n_frames * sizeof(lf::jpeg::FrameHeader);
-    const size_t blk_bytes = (total_blocks + 1) * sizeof(uint32_t);
-    const size_t ent_bytes = (total_entries + 1) * sizeof(uint32_t);
-    const size_t off_blk = (hdr_bytes + 255) & ~(size_t)255, off_ent = (off_blk + blk_bytes + 255) & ~(size_t)255;
-    const size_t stage_bytes = off_ent + ent_bytes;
-    // the previous call's copy out of the staging buffer must have completed before it is rewritten
-    const auto t_w = now();
-    if (J.staged_pending) { LF_HIP_CHECK(h, hipEventSynchronize(J.staged)); J.staged_pending = false; }
-    t_wait = ms_since(t_w);
-    if (J.h_stage.bytes < stage_bytes) LF_HIP_CHECK(h, J.h_stage.alloc(stage_bytes + stage_bytes / 4 + 4096));
-    const auto t_p = now();
-    {
-        // pack headers | block ends | entries into the pinned staging buffer, frames in parallel
-        uint8_t* st = static_cast<uint8_t*>(J.h_stage.p);
-        std::atomic<int> next(0);
-        J.pool.run(nt, [&](int) {
-            for (;;) {
-                const int i = next.fetch_add(1);
-                if (i >= n_frames) break;
-                const lf::jpeg::FrameCoefs& fc = J.frames[(size_t)i];
-                memcpy(st + (size_t)i * sizeof(lf::jpeg::FrameHeader), &fc.hdr, sizeof(lf::jpeg::FrameHeader));
-                if (fc.hdr.nblocks) memcpy(st + off_blk + (size_t)fc.hdr.block_base * 4, fc.block_end.data(), (size_t)fc.hdr.nblocks * 4);
-                if (fc.n_entries) memcpy(st + off_ent + (size_t)fc.hdr.entry_base * 4, fc.entries.data(), fc.n_entries * 4);
-            }
-        });
-    }
-    t_pack = ms_since(t_p);
-    // ---- device
-    JpegGeom g;
-    g.rows = rows; g.cols = cols;
-    g.Wp = (cols + 15) / 16 * 16;
-    g.Hp = (rows + 15) / 16 * 16;
-    int rc;
-    if ((rc = scratch(h, J.planes, (size_t)n_frames * 3 * g.Wp * g.Hp)) != LF_OK) return rc;
-    if ((rc = scratch(h, J.hdrs, stage_bytes)) != LF_OK) return rc;       // one device image of the staging buffer
-    uint8_t* d_stage = static_cast<uint8_t*>(J.hdrs.p);
-    LF_HIP_CHECK(h, hipMemcpyAsync(d_stage, J.h_stage, stage_bytes, hipMemcpyHostToDevice, s));
-    LF_HIP_CHECK(h, hipEventRecord(J.staged, s));
-    J.staged_pending = true;
-    uint8_t* d_out = frames;
-    const size_t out_bytes = (size_t)n_frames * rows * cols * 3;
-    if (!frames_on_device) {
-        if ((rc = scratch(h, J.out, out_bytes)) != LF_OK) return rc;
-        d_out = static_cast<uint8_t*>(J.out.p);
-    }
-    {
-        StageClock::Scope t(h, h->clock, ST_JPEG);
-        launch_jpeg_decode(g, n_frames, max_blocks, reinterpret_cast<const lf::jpeg::FrameHeader*>(d_stage),
-                           reinterpret_cast<const uint32_t*>(d_stage + off_ent), reinterpret_cast<const uint32_t*>(d_stage + off_blk),
-                           static_cast<uint8_t*>(J.planes.p), d_out, s);
-    }
-    LF_HIP_CHECK(h, hipGetLastError());
-    if (!frames_on_device) {
-        LF_HIP_CHECK(h, hipMemcpyAsync(frames, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
-        J.staged_pending = false;
-    }
-    if (trace)
-        fprintf(stderr, "lf_jpeg_decode_batch: %d frames, %d threads: decode %.2f ms, wait %.2f, pack %.2f (%.1f MB), total host %.2f ms\n",
-                n_frames, nt, t_decode, t_wait, t_pack, stage_bytes / 1e6, ms_since(t_begin));
-    if (n_failed && !frame_status) {
-        lf_set_error(h, first_error, "%d of %d JPEG streams could not be decoded (first status %d)", n_failed, n_frames, first_error);
-        return LF_ERR_DECODE;
-    }
-    return LF_OK;
-}
-
-// ---------------------------------------------------------------------------------------- SegmentList glue
-extern "C" int lf_serialize_segments(lf_handle* h, const lf_segments* segs, int segs_on_device, int n_frames, int stage,
-                                     uint8_t* out, size_t out_capacity, int out_on_device, int64_t* frame_byte_offset)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (!segs || !out || !frame_byte_offset || n_frames < 1 || stage < LF_MSG_DETECTOR || stage > LF_MSG_FILTERED || !segs->frame_offset || !segs->color) {
-        lf_set_error(h, LF_ERR_BAD_ARG, "lf_serialize_segments: null argument, n_frames < 1 or unknown stage");
-        return LF_ERR_BAD_ARG;
-    }
-    if (stage == LF_MSG_DETECTOR ? (!segs->pixels_normalized || !segs->normals) : (!segs->ground || (stage == LF_MSG_FILTERED && !segs->keep))) {
-        lf_set_error(h, LF_ERR_BAD_ARG, "lf_serialize_segments: the arrays of stage %d are missing", stage);
-        return LF_ERR_BAD_ARG;
-    }
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    const int* d_fo = segs->frame_offset;
-    const uint8_t* d_color = segs->color;
-    const float* d_pn = segs->pixels_normalized;
-    const float* d_nm = segs->normals;
-    const double* d_gr = segs->ground;
-    const uint8_t* d_keep = segs->keep;
-    int rc;
-    if (!segs_on_device) {
-        const int total = segs->frame_offset[n_frames];
-        if (total < 0) { lf_set_error(h, LF_ERR_BAD_ARG, "negative segment count"); return LF_ERR_BAD_ARG; }
-        const size_t n = (size_t)total;
-        if ((rc = scratch(h, h->m_fo, (size_t)(n_frames + 1) * sizeof(int))) != LF_OK) return rc;
-        if ((rc = scratch(h, h->m_color, n + 1)) != LF_OK) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->m_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->m_color.p, segs->color, n, hipMemcpyHostToDevice, s));
-        d_fo = static_cast<const int*>(h->m_fo.p);
-        d_color = static_cast<const uint8_t*>(h->m_color.p);
-        if (stage == LF_MSG_DETECTOR) {
-            if ((rc = scratch(h, h->m_pn, n * 16 + 16)) != LF_OK) return rc;
-            if ((rc = scratch(h, h->m_nm, n * 8 + 8)) != LF_OK) return rc;
-            LF_HIP_CHECK(h, hipMemcpyAsync(h->m_pn.p, segs->pixels_normalized, n * 16, hipMemcpyHostToDevice, s));
-            LF_HIP_CHECK(h, hipMemcpyAsync(h->m_nm.p, segs->normals, n * 8, hipMemcpyHostToDevice, s));
-            d_pn = static_cast<const float*>(h->m_pn.p);
-            d_nm = static_cast<const float*>(h->m_nm.p);
-        } else {
-            if ((rc = scratch(h, h->m_gr, n * 32 + 32)) != LF_OK) return rc;
-            LF_HIP_CHECK(h, hipMemcpyAsync(h->m_gr.p, segs->ground, n * 32, hipMemcpyHostToDevice, s));
-            d_gr = static_cast<const double*>(h->m_gr.p);
-            if (stage == LF_MSG_FILTERED) {
-                if ((rc = scratch(h, h->m_keep, n + 1)) != LF_OK) return rc;
-                LF_HIP_CHECK(h, hipMemcpyAsync(h->m_keep.p, segs->keep, n, hipMemcpyHostToDevice, s));
-                d_keep = static_cast<const uint8_t*>(h->m_keep.p);
-            }
-        }
-    }
-    if ((rc = scratch(h, h->m_counts, (size_t)n_frames * sizeof(int))) != LF_OK) return rc;
-    if ((rc = scratch(h, h->m_boff, (size_t)(n_frames + 1) * sizeof(long long))) != LF_OK) return rc;
-    launch_msg_layout(n_frames, stage, d_fo, d_keep, static_cast<int*>(h->m_counts.p), static_cast<long long*>(h->m_boff.p), s);
-    static_assert(sizeof(long long) == sizeof(int64_t), "byte offsets are int64");
-    LF_HIP_CHECK(h, hipMemcpyAsync(frame_byte_offset, h->m_boff.p, (size_t)(n_frames + 1) * sizeof(long long), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    const size_t need = (size_t)frame_byte_offset[n_frames];
-    if (need > out_capacity) {
-        lf_set_error(h, LF_ERR_CAPACITY, "lf_serialize_segments: %zu bytes needed, %zu available", need, out_capacity);
-        return LF_ERR_CAPACITY;
-    }
-    uint8_t* d_out = out;
-    if (!out_on_device) {
-        if ((rc = scratch(h, h->m_body, need + 16)) != LF_OK) return rc;
-        d_out = static_cast<uint8_t*>(h->m_body.p);
-    }
-    launch_msg_write(n_frames, stage, d_fo, d_color, d_pn, d_nm, d_gr, d_keep, static_cast<const int*>(h->m_counts.p),
-                     static_cast<const long long*>(h->m_boff.p), d_out, s);
-    LF_HIP_CHECK(h, hipGetLastError());
-    if (!out_on_device) {
-        LF_HIP_CHECK(h, hipMemcpyAsync(out, d_out, need, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    }
-    return LF_OK;
-}
-
-extern "C" int lf_deserialize_segments(lf_handle* h, const uint8_t* bodies, int bodies_on_device, const int64_t* frame_byte_offset,
-                                       int n_frames, lf_segments* out, int out_on_device, int* n_segments)
-{
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    if (!bodies || !frame_byte_offset || !out || n_frames < 1 || !out->frame_offset) {
-        lf_set_error(h, LF_ERR_BAD_ARG, "lf_deserialize_segments: null argument or n_frames < 1");
-        return LF_ERR_BAD_ARG;
-    }
-    for (int f = 0; f < n_frames; ++f)
-        if (frame_byte_offset[f + 1] < frame_byte_offset[f] + 4) { lf_set_error(h, LF_ERR_DECODE, "body %d is shorter than its count field", f); return LF_ERR_DECODE; }
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    const size_t bytes = (size_t)frame_byte_offset[n_frames];
-    const size_t max_segs = bytes / 73 + 1;
-    int rc;
-    const uint8_t* d_body = bodies;
-    if (!bodies_on_device) {
-        if ((rc = scratch(h, h->m_body, bytes + 16)) != LF_OK) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->m_body.p, bodies, bytes, hipMemcpyHostToDevice, s));
-        d_body = static_cast<const uint8_t*>(h->m_body.p);
-    }
-    if ((rc = scratch(h, h->m_boff, (size_t)(n_frames + 1) * sizeof(long long))) != LF_OK) return rc;
-    if ((rc = scratch(h, h->m_bad, sizeof(int))) != LF_OK) return rc;
-    LF_HIP_CHECK(h, hipMemcpyAsync(h->m_boff.p, frame_byte_offset, (size_t)(n_frames + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-    LF_HIP_CHECK(h, hipMemsetAsync(h->m_bad.p, 0, sizeof(int), s));
-    lf_segments dev = *out;
-    if (!out_on_device) {
-        if ((rc = scratch(h, h->m_fo, (size_t)(n_frames + 1) * sizeof(int))) != LF_OK) return rc;
-        dev.frame_offset = static_cast<int32_t*>(h->m_fo.p);
-        dev.color = nullptr; dev.pixels_normalized = nullptr; dev.normals = nullptr; dev.ground = nullptr;
-        if (out->color) { if ((rc = scratch(h, h->m_color, max_segs)) != LF_OK) return rc; dev.color = static_cast<uint8_t*>(h->m_color.p); }
-        if (out->pixels_normalized) { if ((rc = scratch(h, h->m_pn, max_segs * 16)) != LF_OK) return rc; dev.pixels_normalized = static_cast<float*>(h->m_pn.p); }
-        if (out->normals) { if ((rc = scratch(h, h->m_nm, max_segs * 8)) != LF_OK) return rc; dev.normals = static_cast<float*>(h->m_nm.p); }
-        if (out->ground) { if ((rc = scratch(h, h->m_gr, max_segs * 32)) != LF_OK) return rc; dev.ground = static_cast<double*>(h->m_gr.p); }
-    }
-    const int cap = out->capacity;
-    launch_msg_read(n_frames, cap, d_body, static_cast<const long long*>(h->m_boff.p), dev.frame_offset, static_cast<int*>(h->m_bad.p),
-                    dev.color, dev.pixels_normalized, dev.normals, dev.ground, s);
-    LF_HIP_CHECK(h, hipGetLastError());
-    int bad = 0, total = 0;
-    LF_HIP_CHECK(h, hipMemcpyAsync(&bad, h->m_bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipMemcpyAsync(&total, dev.frame_offset + n_frames, sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    if (n_segments) *n_segments = total;
-    if (bad) { lf_set_error(h, LF_ERR_DECODE, "a SegmentList body's count does not match its length"); return LF_ERR_DECODE; }
-    if (total > cap) { lf_set_error(h, LF_ERR_CAPACITY, "%d segments exceed the output capacity %d", total, cap); return LF_ERR_CAPACITY; }
-    if (!out_on_device) {
-        const size_t n = (size_t)total;
-        LF_HIP_CHECK(h, hipMemcpyAsync(out->frame_offset, dev.frame_offset, (size_t)(n_frames + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-        if (out->color && n) LF_HIP_CHECK(h, hipMemcpyAsync(out->color, dev.color, n, hipMemcpyDeviceToHost, s));
-        if (out->pixels_normalized && n) LF_HIP_CHECK(h, hipMemcpyAsync(out->pixels_normalized, dev.pixels_normalized, n * 16, hipMemcpyDeviceToHost, s));
-        if (out->normals && n) LF_HIP_CHECK(h, hipMemcpyAsync(out->normals, dev.normals, n * 8, hipMemcpyDeviceToHost, s));
-        if (out->ground && n) LF_HIP_CHECK(h, hipMemcpyAsync(out->ground, dev.ground, n * 32, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
     }
     return LF_OK;
 }

@@ -1,9 +1,10 @@
 // What the three opaque handles of the C ABI (lf_handle, lf_map, lf_lane_filter) share on the host: the fields every one of them
-// carries, the error text, the HIP check, the device check of their creators, the two kinds of clock, the scratch grower and the
-// ordering of one stream behind another.  Host code only; common.h does not include it (tests/hostsim builds lsd_grow.h on the CPU).
+// carries, the error text, the HIP check, the device check of their creators, the two kinds of clock, the scratch grower, the
+// staging of a caller's host arrays and the ordering of one stream behind another.  Host code only; common.h does not include it (tests/hostsim builds lsd_grow.h on the CPU).
 #pragma once
 #include <stdarg.h>
 #include <stdio.h>
+#include <initializer_list>
 #include <vector>
 #include "common.h"
 
@@ -65,6 +66,78 @@ inline int scratch(Core* c, DevArray<T>& b, size_t bytes)
     LF_HIP_CHECK(c, b.alloc(bytes + bytes / 4 + 256));
     return LF_OK;
 }
+
+// One entry of a fetch: `bytes` at the device address `src` to the host address `dst`.
+struct Fetch { void* dst; const void* src; size_t bytes; };
+
+// Results to the host: one copy per entry on the core's stream, then ONE wait for the stream.  Skipped: an entry with a null
+// destination, a null source or no bytes (an array the caller did not ask for, or the call did not make), and one whose source is
+// its destination -- a device caller's own array, as Staging::out named it.  A fetch that has nothing to copy does not wait
+// either: the device form of a call returns with its work queued.
+inline int fetch(Core* c, std::initializer_list<Fetch> list)
+{
+    bool queued = false;
+    for (const Fetch& f : list) {
+        if (!f.dst || !f.src || !f.bytes || f.dst == f.src) continue;
+        LF_HIP_CHECK(c, hipMemcpyAsync(f.dst, f.src, f.bytes, hipMemcpyDeviceToHost, c->stream));
+        queued = true;
+    }
+    if (queued) LF_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return LF_OK;
+}
+
+// The arrays of one call that its caller holds on the host or on the device (the entry point's on_device flags).  An array on the
+// device is the caller's own, and nothing is queued for it.  For one on the host in() and out() name a scratch buffer of the
+// handle and grow it, and upload() then queues the copies of the inputs: every growth of a call comes before its first copy
+// (scratch() may wait for the stream and free, and where one fails nothing has been queued).  fetch() brings the outputs back.
+struct Staging {
+    explicit Staging(Core* c) : c_(c) {}
+
+    // the device address of an input of `bytes`; its scratch buffer holds at least `room` bytes, so that an empty input has an
+    // address all the same
+    template <typename T, typename B>
+    const T* in(int on_device, const T* src, size_t bytes, DevArray<B>& buf, size_t room = 0)
+    {
+        if (on_device) return src;
+        grow(buf, bytes > room ? bytes : room);
+        if (bytes) up_.push_back({ buf.p, src, bytes });
+        return static_cast<const T*>(static_cast<const void*>(buf.p));
+    }
+
+    // (an input named through a pointer to non-const, such as a field of lf_segments)
+    template <typename T, typename B>
+    T* in(int on_device, T* src, size_t bytes, DevArray<B>& buf, size_t room = 0)
+    {
+        return const_cast<T*>(in(on_device, static_cast<const T*>(src), bytes, buf, room));
+    }
+
+    // the device address of an output of `bytes`
+    template <typename T, typename B>
+    T* out(int on_device, T* dst, size_t bytes, DevArray<B>& buf)
+    {
+        if (on_device) return dst;
+        grow(buf, bytes);
+        return static_cast<T*>(static_cast<void*>(buf.p));
+    }
+
+    // the first failed growth, or the inputs named so far on their way
+    int upload()
+    {
+        if (rc_ != LF_OK) return rc_;
+        for (const Up& u : up_) LF_HIP_CHECK(c_, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, c_->stream));
+        up_.clear();
+        return LF_OK;
+    }
+
+private:
+    struct Up { void* dst; const void* src; size_t bytes; };
+    Core* c_;
+    std::vector<Up> up_;
+    int rc_ = LF_OK;
+
+    template <typename B>
+    void grow(DevArray<B>& buf, size_t bytes) { if (rc_ == LF_OK) rc_ = scratch(c_, buf, bytes); }
+};
 
 // stream `waits` waits for everything queued so far on stream `on`; ev is an event of the core's, kept for this
 inline int stream_after(Core* c, hipEvent_t ev, hipStream_t waits, hipStream_t on)

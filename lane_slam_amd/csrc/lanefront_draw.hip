@@ -8,8 +8,8 @@ using namespace lf;
 namespace {
 
 // The segment arrays the kernel reads, on the device.  Host segments are checked here (offsets, every line's coordinates and
-// colour) and staged; device segments are read as they are (the kernel skips what it would refuse).
-int draw_segments(lf_handle* h, const char* who, int n_frames, const lf_segments* seg, int seg_on_device, const int32_t** fo,
+// colour) and named to the call's staging; device segments are read as they are (the kernel skips what it would refuse).
+int draw_segments(lf_handle* h, Staging& st, const char* who, int n_frames, const lf_segments* seg, int seg_on_device, const int32_t** fo,
                   const float** lines, const uint8_t** color, int* capacity)
 {
     if (!seg->frame_offset || !seg->lines || !seg->color) {
@@ -39,53 +39,39 @@ int draw_segments(lf_handle* h, const char* who, int n_frames, const lf_segments
             }
         if (seg->color[i] > 2) { lf_set_error(h, LF_ERR_BAD_ARG, "%s: line %d has colour %d (> 2)", who, i, seg->color[i]); return LF_ERR_BAD_ARG; }
     }
-    int rc;
-    const size_t rows = n > 0 ? (size_t)n : 1;
-    if ((rc = scratch(h, h->dr_fo, (size_t)(n_frames + 1) * sizeof(int32_t))) || (rc = scratch(h, h->dr_lines, rows * 4 * sizeof(float))) ||
-        (rc = scratch(h, h->dr_color, rows)))
-        return rc;
-    hipStream_t s = h->stream;
-    LF_HIP_CHECK(h, hipMemcpyAsync(h->dr_fo.p, o, (size_t)(n_frames + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (n > 0) {
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->dr_lines.p, seg->lines, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->dr_color.p, seg->color, (size_t)n, hipMemcpyHostToDevice, s));
-    }
-    *fo = static_cast<const int32_t*>(h->dr_fo.p);
-    *lines = static_cast<const float*>(h->dr_lines.p);
-    *color = static_cast<const uint8_t*>(h->dr_color.p);
+    const size_t rows = (size_t)n;
+    *fo = st.in(0, o, (size_t)(n_frames + 1) * sizeof(int32_t), h->dr_fo);
+    *lines = st.in(0, seg->lines, rows * 4 * sizeof(float), h->dr_lines, 4 * sizeof(float));
+    *color = st.in(0, seg->color, rows, h->dr_color, 1);
     *capacity = n;
     return LF_OK;
 }
 
-// Launch, then deliver: a host output is copied back and waited for; device segments with a host output also report a line
-// the kernel refused
-int draw_run(lf_handle* h, const char* who, const void* src, bool src_bgrx, int n_frames, int rows, int cols, const lf_segments* seg,
-             int seg_on_device, uint8_t* out, int out_on_device)
+// Stage, launch, then deliver: host images go to the staging image, where the kernel draws in place, and a host output is copied
+// back and waited for; device segments with a host output also report a line the kernel refused.  host_bgr: the caller's images
+// where they are on the host, else null (src is then on the device).
+int draw_run(lf_handle* h, const char* who, const void* src, bool src_bgrx, const uint8_t* host_bgr, int n_frames, int rows, int cols,
+             const lf_segments* seg, int seg_on_device, uint8_t* out, int out_on_device)
 {
     const int32_t* fo; const float* lines; const uint8_t* color; int cap;
-    int rc = draw_segments(h, who, n_frames, seg, seg_on_device, &fo, &lines, &color, &cap);
+    Staging st(h);
+    int rc = draw_segments(h, st, who, n_frames, seg, seg_on_device, &fo, &lines, &color, &cap);
     if (rc != LF_OK) return rc;
     hipStream_t s = h->stream;
     const size_t bytes = (size_t)n_frames * rows * cols * 3;
-    uint8_t* dst = out;
-    if (!out_on_device) {
-        if ((rc = scratch(h, h->dr_img, bytes)) != LF_OK) return rc;
-        dst = static_cast<uint8_t*>(h->dr_img.p);
-        if (!src_bgrx && src == out) src = dst;          // (lf_draw_lines_image staged the caller's image there)
-    }
+    uint8_t* dst = st.out(out_on_device, out, bytes, h->dr_img);
+    if (host_bgr) src = st.in(0, host_bgr, bytes, h->dr_img);
     int* bad = nullptr;
+    if (seg_on_device && !out_on_device && (rc = scratch(h, h->dr_bad, sizeof(int))) != LF_OK) return rc;
+    if ((rc = st.upload()) != LF_OK) return rc;
     if (seg_on_device && !out_on_device) {
-        if ((rc = scratch(h, h->dr_bad, sizeof(int))) != LF_OK) return rc;
         bad = static_cast<int*>(h->dr_bad.p);
         LF_HIP_CHECK(h, hipMemsetAsync(bad, 0, sizeof(int), s));
     }
     launch_draw(src, src_bgrx, dst, n_frames, rows, cols, fo, lines, color, cap, bad, s);
     LF_HIP_CHECK(h, hipGetLastError());
-    if (out_on_device) return LF_OK;
     int bad_h = 0;
-    LF_HIP_CHECK(h, hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, s));
-    if (bad) LF_HIP_CHECK(h, hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
+    if ((rc = fetch(h, { { out, dst, bytes }, { &bad_h, bad, sizeof(int) } })) != LF_OK) return rc;
     if (bad_h) {
         lf_set_error(h, LF_ERR_BAD_ARG, "%s: a line truncates outside +-%d px or has a colour above 2 (not drawn)", who, draw::kLimit);
         return LF_ERR_BAD_ARG;
@@ -115,7 +101,7 @@ extern "C" int lf_draw_lines(lf_handle* h, int n_frames, const lf_segments* seg,
         return LF_ERR_BAD_ARG;
     }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
-    return draw_run(h, "lf_draw_lines", h->d_bgr.p, true, n_frames, h->Hc, h->W, seg, seg_on_device, out_bgr, out_on_device);
+    return draw_run(h, "lf_draw_lines", h->d_bgr.p, true, nullptr, n_frames, h->Hc, h->W, seg, seg_on_device, out_bgr, out_on_device);
 }
 
 extern "C" int lf_draw_lines_image(lf_handle* h, const uint8_t* bgr, int n_frames, int rows, int cols, const lf_segments* seg, int seg_on_device,
@@ -132,14 +118,6 @@ extern "C" int lf_draw_lines_image(lf_handle* h, const uint8_t* bgr, int n_frame
         return LF_ERR_BAD_ARG;
     }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
-    const uint8_t* src = bgr;
-    if (!images_on_device) {
-        // the host image goes to the staging buffer, and the kernel draws there in place
-        const size_t bytes = (size_t)n_frames * rows * cols * 3;
-        int rc = scratch(h, h->dr_img, bytes);
-        if (rc != LF_OK) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(h->dr_img.p, bgr, bytes, hipMemcpyHostToDevice, h->stream));
-        src = out_bgr;                                   // draw_run maps it to the staging buffer
-    }
-    return draw_run(h, "lf_draw_lines_image", src, false, n_frames, rows, cols, seg, seg_on_device, out_bgr, images_on_device);
+    return draw_run(h, "lf_draw_lines_image", bgr, false, images_on_device ? nullptr : bgr, n_frames, rows, cols, seg, seg_on_device, out_bgr,
+                    images_on_device);
 }

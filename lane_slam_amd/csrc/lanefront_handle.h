@@ -1,5 +1,7 @@
 // lanefront's host side: the handle, its substates and the few helpers the translation units of the C ABI share
-// (lanefront_api.hip, lanefront_lsd.hip, lanefront_keylines.hip, lanefront_lsdkl.hip, lanefront_matcher.hip, lanefront_jpeg_gpu.hip).
+// (lanefront_api.hip, lanefront_lsd.hip, lanefront_keylines.hip, lanefront_lsdkl.hip, lanefront_matcher.hip, lanefront_jpeg_gpu.hip,
+// lanefront_msgs.hip, lanefront_debug.hip, lanefront_hough.hip, lanefront_dense.hip, lanefront_ai.hip, lanefront_draw.hip,
+// lanefront_jenc.hip, lanefront_rectify.hip).
 // Host code only; common.h does not include it (tests/hostsim builds lsd_grow.h on the CPU).
 #pragma once
 #include <stdio.h>
@@ -236,7 +238,7 @@ struct lf_handle : lf::Core {
     std::unique_ptr<lf::MatcherState> matcher;    // BinaryDescriptorMatcher's dataset (lanefront_matcher.hip)
     // pinned host scalars
     lf::HostArray<int> h_pinned;     // [0] total segments, [1] overflow ... [6] entries the per-problem lists would have needed (d_overflow[5])
-    const uint8_t* pend_in = nullptr; int pend_n = 0; lf_segments pend_out; bool pend_describe = false;   // the batch in flight (lsd_records_retry)
+    const uint8_t* pend_in = nullptr; int pend_n = 0; lf_segments pend_out; bool pend_describe = false;   // the batch in flight (lf_wait runs it again when the LSD lists were too short)
     int last_frames = 0;
     bool plugin_ready = false;
     bool pending = false;

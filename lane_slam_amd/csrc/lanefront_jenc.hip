@@ -142,8 +142,10 @@ extern "C" int lf_jpeg_encode_batch(lf_handle* h, const uint8_t* bgr, int bgr_on
         (rc = scratch(h, e.total, n * sizeof(uint32_t))) || (rc = scratch(h, e.bitbuf, n * g.words * sizeof(uint32_t))) ||
         (rc = scratch(h, e.ff, n * g.chunks * sizeof(uint32_t))))
         return rc;
-    if (!bgr_on_device && (rc = scratch(h, e.in, n * rows * cols * 3))) return rc;
-    if (!out_on_device && ((rc = scratch(h, e.out, n * stage_stride)) || (rc = scratch(h, e.sizes, n * sizeof(uint32_t))))) return rc;
+    Staging st(h);
+    const uint8_t* src = st.in(bgr_on_device, bgr, n * rows * cols * 3, e.in);
+    uint8_t* dst = st.out(out_on_device, out, n * stage_stride, e.out);
+    uint32_t* dsz = st.out(out_on_device, out_size, n * sizeof(uint32_t), e.sizes);
     if (!e.h_tab.p) LF_HIP_CHECK(h, e.h_tab.alloc(sizeof(jenc::Tables)));
     if (!out_on_device && e.h_sizes.bytes < n * sizeof(uint32_t)) LF_HIP_CHECK(h, e.h_sizes.alloc(n * sizeof(uint32_t)));
     if (e.rows != rows || e.cols != cols || e.quality != quality) {
@@ -153,13 +155,7 @@ extern "C" int lf_jpeg_encode_batch(lf_handle* h, const uint8_t* bgr, int bgr_on
         LF_HIP_CHECK(h, hipMemcpyAsync(e.tab.p, e.h_tab.p, sizeof(jenc::Tables), hipMemcpyHostToDevice, s));
         e.rows = rows; e.cols = cols; e.quality = quality;
     }
-    const uint8_t* src = bgr;
-    if (!bgr_on_device) {
-        LF_HIP_CHECK(h, hipMemcpyAsync(e.in.p, bgr, n * rows * cols * 3, hipMemcpyHostToDevice, s));
-        src = static_cast<const uint8_t*>(e.in.p);
-    }
-    uint8_t* dst = out_on_device ? out : static_cast<uint8_t*>(e.out.p);
-    uint32_t* dsz = out_on_device ? out_size : static_cast<uint32_t*>(e.sizes.p);
+    if ((rc = st.upload()) != LF_OK) return rc;
     const size_t dstride = out_on_device ? out_stride : stage_stride;
     const jenc::Tables* tab = static_cast<const jenc::Tables*>(e.tab.p);
     int16_t* coef = static_cast<int16_t*>(e.coef.p);

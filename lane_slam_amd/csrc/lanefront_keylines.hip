@@ -112,56 +112,48 @@ static int kl_prepare(lf_handle* h, int n_octaves, int scan)
 }
 
 // ---- the KeyLine block and the batch state both detectors share (lf_lsd_keylines_batch_ex: lanefront_lsdkl.hip)
-template <typename T>
-static int kl_stage(lf_handle* h, DevBuf& b, size_t bytes, bool need, T*& dev)
-{
-    const int rc = need ? scratch(h, b, bytes) : LF_OK;
-    dev = need && rc == LF_OK ? static_cast<T*>(b.p) : nullptr;
-    return rc;
-}
-
 int KlArrays::stage(lf_handle* h, const lf_keylines& out, bool describe, lf_keylines* dev)
 {
     const size_t c = (size_t)out.capacity;
     *dev = out;
-    int rc;
-    if ((rc = kl_stage(h, start_end, c * 16, out.start_end, dev->start_end)) || (rc = kl_stage(h, in_octave, c * 16, true, dev->in_octave)) ||
-        (rc = kl_stage(h, angle, c * 4, true, dev->angle)) || (rc = kl_stage(h, num_pixels, c * 4, true, dev->num_pixels)) ||
-        (rc = kl_stage(h, line_length, c * 4, out.line_length, dev->line_length)) || (rc = kl_stage(h, octave, c * 4, true, dev->octave)) ||
-        (rc = kl_stage(h, class_id, c * 4, out.class_id, dev->class_id)) || (rc = kl_stage(h, response, c * 4, out.response, dev->response)) ||
-        (rc = kl_stage(h, size, c * 4, out.size, dev->size)) || (rc = kl_stage(h, pt, c * 8, out.pt, dev->pt)) ||
-        (rc = kl_stage(h, salience, c * 4, out.salience, dev->salience)) || (rc = kl_stage(h, desc, c * 288, describe && out.desc, dev->desc)) ||
-        (rc = kl_stage(h, code, c * 32, describe && out.code, dev->code)))
-        return rc;
-    return LF_OK;
+    Staging st(h);
+    if (out.start_end) dev->start_end = st.out(0, out.start_end, c * 16, start_end);
+    dev->in_octave = st.out(0, out.in_octave, c * 16, in_octave);
+    dev->angle = st.out(0, out.angle, c * 4, angle);
+    dev->num_pixels = st.out(0, out.num_pixels, c * 4, num_pixels);
+    if (out.line_length) dev->line_length = st.out(0, out.line_length, c * 4, line_length);
+    dev->octave = st.out(0, out.octave, c * 4, octave);
+    if (out.class_id) dev->class_id = st.out(0, out.class_id, c * 4, class_id);
+    if (out.response) dev->response = st.out(0, out.response, c * 4, response);
+    if (out.size) dev->size = st.out(0, out.size, c * 4, size);
+    if (out.pt) dev->pt = st.out(0, out.pt, c * 8, pt);
+    if (out.salience) dev->salience = st.out(0, out.salience, c * 4, salience);
+    dev->desc = describe && out.desc ? st.out(0, out.desc, c * 288, desc) : nullptr;
+    dev->code = describe && out.code ? st.out(0, out.code, c * 32, code) : nullptr;
+    return st.upload();
 }
 
 int KlArrays::all(lf_handle* h, int capacity, KlOut* ko)
 {
     const size_t c = (size_t)capacity;
-    int rc;
-    if ((rc = kl_stage(h, start_end, c * 16, true, ko->start_end)) || (rc = kl_stage(h, in_octave, c * 16, true, ko->in_octave)) ||
-        (rc = kl_stage(h, angle, c * 4, true, ko->angle)) || (rc = kl_stage(h, num_pixels, c * 4, true, ko->num_pixels)) ||
-        (rc = kl_stage(h, line_length, c * 4, true, ko->line_length)) || (rc = kl_stage(h, octave, c * 4, true, ko->octave)) ||
-        (rc = kl_stage(h, class_id, c * 4, true, ko->class_id)) || (rc = kl_stage(h, response, c * 4, true, ko->response)) ||
-        (rc = kl_stage(h, size, c * 4, true, ko->size)) || (rc = kl_stage(h, pt, c * 8, true, ko->pt)) ||
-        (rc = kl_stage(h, salience, c * 4, true, ko->salience)) || (rc = kl_stage(h, frame, c * 4, true, ko->frame)))
-        return rc;
-    return LF_OK;
+    Staging st(h);
+    ko->start_end = st.out(0, ko->start_end, c * 16, start_end); ko->in_octave = st.out(0, ko->in_octave, c * 16, in_octave);
+    ko->angle = st.out(0, ko->angle, c * 4, angle); ko->num_pixels = st.out(0, ko->num_pixels, c * 4, num_pixels);
+    ko->line_length = st.out(0, ko->line_length, c * 4, line_length); ko->octave = st.out(0, ko->octave, c * 4, octave);
+    ko->class_id = st.out(0, ko->class_id, c * 4, class_id); ko->response = st.out(0, ko->response, c * 4, response);
+    ko->size = st.out(0, ko->size, c * 4, size); ko->pt = st.out(0, ko->pt, c * 8, pt);
+    ko->salience = st.out(0, ko->salience, c * 4, salience); ko->frame = st.out(0, ko->frame, c * 4, frame);
+    return st.upload();
 }
 
 int KlArrays::copy_back(lf_handle* h, const lf_keylines& dev, const lf_keylines& out, int n, int n_frames)
 {
-    hipStream_t s = h->stream;
-    const struct { void* dst; const void* src; size_t bytes; } arrays[] = {
-        { out.start_end, dev.start_end, 16 }, { out.in_octave, dev.in_octave, 16 }, { out.angle, dev.angle, 4 }, { out.num_pixels, dev.num_pixels, 4 },
-        { out.line_length, dev.line_length, 4 }, { out.octave, dev.octave, 4 }, { out.class_id, dev.class_id, 4 }, { out.response, dev.response, 4 },
-        { out.size, dev.size, 4 }, { out.pt, dev.pt, 8 }, { out.salience, dev.salience, 4 }, { out.desc, dev.desc, 288 }, { out.code, dev.code, 32 } };
-    if (out.frame_offset) LF_HIP_CHECK(h, hipMemcpyAsync(out.frame_offset, dev.frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyDeviceToHost, s));
-    for (const auto& a : arrays)
-        if (a.dst && a.src && n) LF_HIP_CHECK(h, hipMemcpyAsync(a.dst, a.src, (size_t)n * a.bytes, hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    return LF_OK;
+    const size_t c = (size_t)n;
+    return fetch(h, { { out.frame_offset, dev.frame_offset, (size_t)(n_frames + 1) * 4 }, { out.start_end, dev.start_end, c * 16 },
+                      { out.in_octave, dev.in_octave, c * 16 }, { out.angle, dev.angle, c * 4 }, { out.num_pixels, dev.num_pixels, c * 4 },
+                      { out.line_length, dev.line_length, c * 4 }, { out.octave, dev.octave, c * 4 }, { out.class_id, dev.class_id, c * 4 },
+                      { out.response, dev.response, c * 4 }, { out.size, dev.size, c * 4 }, { out.pt, dev.pt, c * 8 },
+                      { out.salience, dev.salience, c * 4 }, { out.desc, dev.desc, c * 288 }, { out.code, dev.code, c * 32 } });
 }
 
 KlOut lf::kl_out(const lf_keylines& k, int32_t* frame)
@@ -184,11 +176,9 @@ int KlBatch::alloc(lf_handle* h)
 
 int KlBatch::upload(lf_handle* h, DevBuf& buf, const uint8_t* planes, int n, const uint8_t** d)
 {
-    int rc;
-    if ((rc = scratch(h, buf, (size_t)h->max_frames * h->P)) != LF_OK) return rc;
-    LF_HIP_CHECK(h, hipMemcpyAsync(buf.p, planes, h->P * n, hipMemcpyHostToDevice, h->stream));
-    *d = static_cast<const uint8_t*>(buf.p);
-    return LF_OK;
+    Staging st(h);
+    *d = st.in(0, planes, h->P * n, buf, (size_t)h->max_frames * h->P);
+    return st.upload();
 }
 
 int KlBatch::images(lf_handle* h, const uint8_t* images, int n, int input_kind, int on_device, const uint8_t** d)
@@ -482,9 +472,7 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
     std::vector<int32_t> staged;
     if (on_device) {
         staged.resize(2 * nn);
-        LF_HIP_CHECK(h, hipMemcpyAsync(staged.data(), octave, nn * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(staged.data() + nn, line_frame, nn * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(h, hipStreamSynchronize(s));
+        if ((rc = fetch(h, { { staged.data(), octave, nn * 4 }, { staged.data() + nn, line_frame, nn * 4 } })) != LF_OK) return rc;
         h_oct = staged.data(); h_frame = staged.data() + nn;
     }
     int max_oct = 0;
@@ -497,28 +485,17 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
         lf_set_error(h, LF_ERR_UNSUPPORTED, "lf_describe_keylines: reductionRatio %d: cv::pyrDown only takes a destination within 2 pixels of half the source (the reference raises cv::Exception here)", h->desc_params.reduction_ratio);
         return LF_ERR_UNSUPPORTED;
     }
-    const uint8_t* d_gray = gray;
-    const int32_t *d_frame = line_frame, *d_npx = num_pixels, *d_oct = octave;
-    const float *d_io = in_octave4, *d_ang = angle;
-    float* d_desc = desc72; uint8_t* d_code = code32;
-    if (!on_device) {
-        if ((rc = scratch(h, k->batch.gray, (size_t)h->max_frames * P0)) || (rc = scratch(h, k->d_frame, nn * 4)) || (rc = scratch(h, k->d_io, nn * 16)) ||
-            (rc = scratch(h, k->d_angle, nn * 4)) || (rc = scratch(h, k->d_npx, nn * 4)) || (rc = scratch(h, k->d_oct, nn * 4)) ||
-            (rc = scratch(h, k->d_desc, nn * 288)) || (rc = scratch(h, k->d_code, nn * 32)))
-            return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(k->batch.gray.p, gray, P0 * n_frames, hipMemcpyHostToDevice, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(k->d_frame.p, line_frame, nn * 4, hipMemcpyHostToDevice, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(k->d_io.p, in_octave4, nn * 16, hipMemcpyHostToDevice, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(k->d_angle.p, angle, nn * 4, hipMemcpyHostToDevice, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(k->d_npx.p, num_pixels, nn * 4, hipMemcpyHostToDevice, s));
-        LF_HIP_CHECK(h, hipMemcpyAsync(k->d_oct.p, octave, nn * 4, hipMemcpyHostToDevice, s));
-        d_gray = static_cast<const uint8_t*>(k->batch.gray.p);
-        d_frame = static_cast<const int32_t*>(k->d_frame.p); d_io = static_cast<const float*>(k->d_io.p); d_ang = static_cast<const float*>(k->d_angle.p);
-        d_npx = static_cast<const int32_t*>(k->d_npx.p); d_oct = static_cast<const int32_t*>(k->d_oct.p);
-        d_desc = desc72 ? static_cast<float*>(k->d_desc.p) : nullptr; d_code = code32 ? static_cast<uint8_t*>(k->d_code.p) : nullptr;
-    }
-    if ((rc = scratch(h, k->d_n, 16)) != LF_OK) return rc;
-    LF_HIP_CHECK(h, hipMemcpyAsync(k->d_n.p, &n, sizeof(int), hipMemcpyHostToDevice, s));
+    Staging st(h);
+    const uint8_t* d_gray = st.in(on_device, gray, P0 * n_frames, k->batch.gray, (size_t)h->max_frames * P0);
+    const int32_t* d_frame = st.in(on_device, line_frame, nn * 4, k->d_frame);
+    const float* d_io = st.in(on_device, in_octave4, nn * 16, k->d_io);
+    const float* d_ang = st.in(on_device, angle, nn * 4, k->d_angle);
+    const int32_t* d_npx = st.in(on_device, num_pixels, nn * 4, k->d_npx);
+    const int32_t* d_oct = st.in(on_device, octave, nn * 4, k->d_oct);
+    float* d_desc = desc72 ? st.out(on_device, desc72, nn * 288, k->d_desc) : nullptr;
+    uint8_t* d_code = code32 ? st.out(on_device, code32, nn * 32, k->d_code) : nullptr;
+    st.in(0, &n, sizeof(int), k->d_n, 16);
+    if ((rc = st.upload()) != LF_OK) return rc;
     // computeGaussianPyramid (:350-371) + computeSobel (:374-398): level 0 = GaussianBlur(5x5, sigma 1), level o = pyrDown
     LbdPlanes pl;
     for (int o = 0; o < LF_MAX_OCTAVES; ++o) { pl.base[o] = nullptr; pl.W[o] = 0; pl.H[o] = 0; }
@@ -557,11 +534,8 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
                             h->desc_params.width_of_band);
     }
     LF_HIP_CHECK(h, hipGetLastError());
-    if (!on_device) {
-        if (desc72) LF_HIP_CHECK(h, hipMemcpyAsync(desc72, d_desc, nn * 288, hipMemcpyDeviceToHost, s));
-        if (code32) LF_HIP_CHECK(h, hipMemcpyAsync(code32, d_code, nn * 32, hipMemcpyDeviceToHost, s));
-    }
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
+    if ((rc = fetch(h, { { desc72, d_desc, nn * 288 }, { code32, d_code, nn * 32 } })) != LF_OK) return rc;
+    if (on_device) LF_HIP_CHECK(h, hipStreamSynchronize(s));       // (the device form waits as well)
     return LF_OK;
 }
 
@@ -593,9 +567,7 @@ extern "C" int lf_keylines_debug_fetch(lf_handle* h, int octave, int what, void*
     }
     if (!src || bytes > have) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_keylines_debug_fetch: buffer %d of octave %d holds %zu bytes (asked %zu)", what, octave, have, bytes); return LF_ERR_BAD_ARG; }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
-    LF_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-    LF_HIP_CHECK(h, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-    return LF_OK;
+    return fetch(h, { { dst, src, bytes } });
 }
 
 // ---- the EDLines detector behind lf_process_batch[_async] (lf_set_detector): stages a-1 .. a-4 of a batch with the

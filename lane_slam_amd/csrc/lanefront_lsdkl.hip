@@ -249,7 +249,7 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
     LF_HIP_CHECK(h, hipStreamSynchronize(s));
     for (int o = 0; o < n_octaves && !level_counts_bad; ++o) {
         std::vector<int> c((size_t)n_frames * 3);
-        LF_HIP_CHECK(h, hipMemcpy(c.data(), k->level[o].counts, c.size() * sizeof(int), hipMemcpyDeviceToHost));
+        if ((rc = fetch(h, { { c.data(), k->level[o].counts.p, c.size() * sizeof(int) } })) != LF_OK) return rc;
         for (int f = 0; f < n_frames; ++f) if (c[3 * (size_t)f] > h->cap_lines) { level_counts_bad = c[3 * (size_t)f]; break; }
     }
     const int total = b.h_pinned[0];

@@ -216,24 +216,11 @@ extern "C" int lf_map_seed(lf_map* m, const uint8_t* code32, const uint8_t* colo
     if (n == 0) return LF_OK;
     LF_HIP_CHECK(m, hipSetDevice(m->device));
     int rc;
-    const uint8_t *dcode = code32, *dcolor = color;
-    const double* dground = ground4;
-    if (!on_device) {
-        if ((rc = scratch(m, m->seed_code, (size_t)n * 32)) != LF_OK) return rc;
-        LF_HIP_CHECK(m, hipMemcpyAsync(m->seed_code.p, code32, (size_t)n * 32, hipMemcpyHostToDevice, m->stream));
-        dcode = static_cast<const uint8_t*>(m->seed_code.p);
-        if (color) {
-            if ((rc = scratch(m, m->seed_color, (size_t)n)) != LF_OK) return rc;
-            LF_HIP_CHECK(m, hipMemcpyAsync(m->seed_color.p, color, (size_t)n, hipMemcpyHostToDevice, m->stream));
-            dcolor = static_cast<const uint8_t*>(m->seed_color.p);
-        }
-        if (ground4) {
-            if ((rc = scratch(m, m->seed_ground, (size_t)n * 32)) != LF_OK) return rc;
-            LF_HIP_CHECK(m, hipMemcpyAsync(m->seed_ground.p, ground4, (size_t)n * 32, hipMemcpyHostToDevice, m->stream));
-            dground = static_cast<const double*>(m->seed_ground.p);
-        }
-    }
-    if ((rc = scratch(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) != LF_OK) return rc;
+    Staging st(m);
+    const uint8_t* dcode = st.in(on_device, code32, (size_t)n * 32, m->seed_code);
+    const uint8_t* dcolor = color ? st.in(on_device, color, (size_t)n, m->seed_color) : nullptr;
+    const double* dground = ground4 ? st.in(on_device, ground4, (size_t)n * 32, m->seed_ground) : nullptr;
+    if ((rc = scratch(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) || (rc = st.upload())) return rc;
     launch_map_seed_block(n, dcode, dcolor, dground, static_cast<uint8_t*>(m->own_block.p), m->stream);
     rc = update_blocks(m, static_cast<const uint8_t*>(m->own_block.p), 1, n + 1, 1, n);
     if (rc != LF_OK) return rc;
@@ -273,20 +260,13 @@ extern "C" int lf_map_associate(lf_map* m, lf_handle* h, const uint8_t* code32, 
     const int size = (int)bound;
     if ((rc = after_handle(m, h)) != LF_OK) return rc;
     hipStream_t s = m->stream;
-    const uint8_t *dq = code32, *dc = color;
-    int32_t* didx = idx; float* ddist = dist;
-    if (!on_device) {
-        if ((rc = scratch(m, m->q_in, (size_t)n * 32)) || (rc = scratch(m, m->idx_out, (size_t)n * 4)) || (rc = scratch(m, m->dist_out, (size_t)n * 4))) return rc;
-        LF_HIP_CHECK(m, hipMemcpyAsync(m->q_in.p, code32, (size_t)n * 32, hipMemcpyHostToDevice, s));
-        dq = static_cast<const uint8_t*>(m->q_in.p);
-        if (color) {
-            if ((rc = scratch(m, m->c_in, (size_t)n)) != LF_OK) return rc;
-            LF_HIP_CHECK(m, hipMemcpyAsync(m->c_in.p, color, (size_t)n, hipMemcpyHostToDevice, s));
-            dc = static_cast<const uint8_t*>(m->c_in.p);
-        }
-        didx = static_cast<int32_t*>(m->idx_out.p); ddist = static_cast<float*>(m->dist_out.p);
-    }
+    Staging st(m);
+    const uint8_t* dq = st.in(on_device, code32, (size_t)n * 32, m->q_in);
+    const uint8_t* dc = color ? st.in(on_device, color, (size_t)n, m->c_in) : nullptr;
+    int32_t* didx = st.out(on_device, idx, (size_t)n * 4, m->idx_out);
+    float* ddist = st.out(on_device, dist, (size_t)n * 4, m->dist_out);
     if (m->tie_rule == LF_TIE_MIHASHER && (rc = scratch(m, m->tie_res, (size_t)n * 8)) != LF_OK) return rc;
+    if ((rc = st.upload()) != LF_OK) return rc;
     if (size == 0) {
         // descriptor matrices cannot be void (binary_descriptor_matcher.cpp:201-205): report "no match"
         launch_assoc_nomatch(n, didx, ddist, s);
@@ -304,12 +284,7 @@ extern "C" int lf_map_associate(lf_map* m, lf_handle* h, const uint8_t* code32, 
     }
     LF_HIP_CHECK(m, hipGetLastError());
     if ((rc = release_handle(m, h)) != LF_OK) return rc;
-    if (!on_device) {
-        LF_HIP_CHECK(m, hipMemcpyAsync(idx, didx, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(m, hipMemcpyAsync(dist, ddist, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(m, hipStreamSynchronize(s));
-    }
-    return LF_OK;
+    return fetch(m, { { idx, didx, (size_t)n * 4 }, { dist, ddist, (size_t)n * 4 } });
 }
 
 extern "C" int lf_map_set_tie_rule(lf_map* m, int tie_rule)
@@ -400,15 +375,7 @@ extern "C" int lf_map_fetch(lf_map* m, int first, int n, uint8_t* code32, uint8_
     if (!m) return LF_ERR_NOT_INITIALISED;
     if (first < 0 || n < 0 || (long long)first + n > m->cfg.capacity) { set_error(m, LF_ERR_BAD_ARG, "lf_map_fetch: range [%d, %d) outside the map's capacity %d", first, first + n, m->cfg.capacity); return LF_ERR_BAD_ARG; }
     LF_HIP_CHECK(m, hipSetDevice(m->device));
-    hipStream_t s = m->stream;
     const size_t f = (size_t)first, c = (size_t)n;
-    if (n > 0) {
-        if (code32) LF_HIP_CHECK(m, hipMemcpyAsync(code32, m->d.code + f * 32, c * 32, hipMemcpyDeviceToHost, s));
-        if (color) LF_HIP_CHECK(m, hipMemcpyAsync(color, m->d.color + f, c, hipMemcpyDeviceToHost, s));
-        if (ground4) LF_HIP_CHECK(m, hipMemcpyAsync(ground4, m->d.ground + f * 4, c * 32, hipMemcpyDeviceToHost, s));
-        if (hits) LF_HIP_CHECK(m, hipMemcpyAsync(hits, m->d.hits + f, c * 4, hipMemcpyDeviceToHost, s));
-        if (last_seen) LF_HIP_CHECK(m, hipMemcpyAsync(last_seen, m->d.last_seen + f, c * 4, hipMemcpyDeviceToHost, s));
-    }
-    LF_HIP_CHECK(m, hipStreamSynchronize(s));
-    return LF_OK;
+    return fetch(m, { { code32, m->d.code + f * 32, c * 32 }, { color, m->d.color + f, c }, { ground4, m->d.ground + f * 4, c * 32 },
+                      { hits, m->d.hits + f, c * 4 }, { last_seen, m->d.last_seen + f, c * 4 } });
 }

@@ -45,54 +45,6 @@ int align_check_call(lf_map* m, const char* who, const lf_segments* segs, int n,
     return LF_OK;
 }
 
-namespace {
-
-// queue the copies of the host arrays a solver reads (frame_offset, ground, color, keep, idx, dist) into the map's staging
-// buffers; d, didx and ddist then name the device copies
-int solver_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist, lf_segments* d,
-                      const int32_t** didx, const float** ddist)
-{
-    int rc;
-    hipStream_t s = m->stream;
-    const size_t c = (size_t)n;
-    if ((rc = scratch(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = scratch(m, m->st_ground, c * 32)) ||
-        (rc = scratch(m, m->st_idx, c * 4)) || (segs->color && (rc = scratch(m, m->st_color, c))) ||
-        (segs->keep && (rc = scratch(m, m->st_keep, c))) || (dist && (rc = scratch(m, m->st_dist, c * 4)))) return rc;
-    LF_HIP_CHECK(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
-    LF_HIP_CHECK(m, hipMemcpyAsync(m->st_ground.p, segs->ground, c * 32, hipMemcpyHostToDevice, s));
-    LF_HIP_CHECK(m, hipMemcpyAsync(m->st_idx.p, idx, c * 4, hipMemcpyHostToDevice, s));
-    d->frame_offset = static_cast<int32_t*>(m->st_fo.p); d->ground = static_cast<double*>(m->st_ground.p);
-    *didx = static_cast<const int32_t*>(m->st_idx.p);
-    if (segs->color) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_color.p, segs->color, c, hipMemcpyHostToDevice, s)); d->color = static_cast<uint8_t*>(m->st_color.p); }
-    if (segs->keep) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_keep.p, segs->keep, c, hipMemcpyHostToDevice, s)); d->keep = static_cast<uint8_t*>(m->st_keep.p); }
-    if (dist) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_dist.p, dist, c * 4, hipMemcpyHostToDevice, s)); *ddist = static_cast<const float*>(m->st_dist.p); }
-    return LF_OK;
-}
-
-// the staging of a step's host form: frame_offset and, of code, color, keep and ground, those present go up; st_idx and st_dist
-// are sized
-int step_stage_host(lf_map* m, const lf_segments* segs, int n, int n_frames, lf_segments* d)
-{
-    int rc;
-    hipStream_t s = m->stream;
-    const size_t c = (size_t)(n > 0 ? n : 1);
-    if ((rc = scratch(m, m->st_fo, (size_t)(n_frames + 1) * 4)) || (rc = scratch(m, m->st_code, c * 32)) || (rc = scratch(m, m->st_color, c)) ||
-        (rc = scratch(m, m->st_keep, c)) || (rc = scratch(m, m->st_ground, c * 32)) || (rc = scratch(m, m->st_idx, c * 4)) ||
-        (rc = scratch(m, m->st_dist, c * 4))) return rc;
-    LF_HIP_CHECK(m, hipMemcpyAsync(m->st_fo.p, segs->frame_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
-    d->frame_offset = static_cast<int32_t*>(m->st_fo.p);
-    if (n > 0) {
-        LF_HIP_CHECK(m, hipMemcpyAsync(m->st_code.p, segs->code, (size_t)n * 32, hipMemcpyHostToDevice, s));
-        d->code = static_cast<uint8_t*>(m->st_code.p);
-        if (segs->color) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_color.p, segs->color, (size_t)n, hipMemcpyHostToDevice, s)); d->color = static_cast<uint8_t*>(m->st_color.p); }
-        if (segs->keep) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_keep.p, segs->keep, (size_t)n, hipMemcpyHostToDevice, s)); d->keep = static_cast<uint8_t*>(m->st_keep.p); }
-        if (segs->ground) { LF_HIP_CHECK(m, hipMemcpyAsync(m->st_ground.p, segs->ground, (size_t)n * 32, hipMemcpyHostToDevice, s)); d->ground = static_cast<double*>(m->st_ground.p); }
-    }
-    return LF_OK;
-}
-
-}  // namespace
-
 ma::Batch batch_view(const lf_segments* d, int n, int n_frames, const int32_t* idx, const float* dist)
 {
     ma::Batch b = {};
@@ -109,10 +61,17 @@ int open_batch(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_fr
     if ((rc = after_handle(m, h)) != LF_OK) return rc;
     lf_segments d;
     memset(&d, 0, sizeof(d));
-    if (on_device) {
-        d.frame_offset = segs->frame_offset; d.ground = segs->ground; d.color = segs->color; d.keep = segs->keep;
-    } else if (n > 0) {
-        if ((rc = solver_stage_host(m, segs, n, n_frames, idx, dist, &d, &idx, &dist)) != LF_OK) return rc;
+    if (on_device || n > 0) {
+        // the arrays a solver reads: a host caller's go to the map's staging buffers
+        const size_t c = (size_t)n;
+        Staging st(m);
+        d.frame_offset = st.in(on_device, segs->frame_offset, (size_t)(n_frames + 1) * 4, m->st_fo);
+        d.ground = st.in(on_device, segs->ground, c * 32, m->st_ground);
+        idx = st.in(on_device, idx, c * 4, m->st_idx);
+        if (segs->color) d.color = st.in(on_device, segs->color, c, m->st_color);
+        if (segs->keep) d.keep = st.in(on_device, segs->keep, c, m->st_keep);
+        if (dist) dist = st.in(on_device, dist, c * 4, m->st_dist);
+        if ((rc = st.upload()) != LF_OK) return rc;
     }
     *b = batch_view(&d, n, n_frames, idx, dist);
     return LF_OK;
@@ -122,18 +81,10 @@ int upload_prior_pose(lf_map* m, const double* pose, int n_frames, const double*
 {
     int rc;
     const size_t bytes = (size_t)n_frames * 3 * sizeof(double);
-    if ((rc = scratch(m, m->prior_pose, bytes)) != LF_OK) return rc;
-    if (pose) LF_HIP_CHECK(m, hipMemcpyAsync(m->prior_pose.p, pose, bytes, hipMemcpyHostToDevice, m->stream));
-    else LF_HIP_CHECK(m, hipMemsetAsync(m->prior_pose.p, 0, bytes, m->stream));
-    *d_pose = static_cast<const double*>(m->prior_pose.p);
-    return LF_OK;
-}
-
-int fetch_results(lf_map* m, void* dst, const DevBuf& src, size_t bytes, void* dst2, const DevBuf* src2, size_t bytes2)
-{
-    LF_HIP_CHECK(m, hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, m->stream));
-    if (dst2) LF_HIP_CHECK(m, hipMemcpyAsync(dst2, src2->p, bytes2, hipMemcpyDeviceToHost, m->stream));
-    LF_HIP_CHECK(m, hipStreamSynchronize(m->stream));
+    Staging st(m);
+    *d_pose = pose ? st.in(0, pose, bytes, m->prior_pose) : st.out<const double>(0, nullptr, bytes, m->prior_pose);
+    if ((rc = st.upload()) != LF_OK) return rc;
+    if (!pose) LF_HIP_CHECK(m, hipMemsetAsync(m->prior_pose.p, 0, bytes, m->stream));
     return LF_OK;
 }
 
@@ -163,17 +114,23 @@ int step_from_host(lf_map* m, const lf_segments* segs, int n, int n_frames, int3
 {
     int rc;
     LF_HIP_CHECK(m, hipSetDevice(m->device));
-    hipStream_t s = m->stream;
     lf_segments d;
     memset(&d, 0, sizeof(d));
-    if ((rc = step_stage_host(m, segs, n, n_frames, &d)) != LF_OK) return rc;
-    if ((rc = device_form(&d, static_cast<int32_t*>(m->st_idx.p), static_cast<float*>(m->st_dist.p))) != LF_OK) return rc;
+    // frame_offset and, of code, color, keep and ground, those present go up
+    const size_t c = (size_t)n;
+    Staging st(m);
+    d.frame_offset = st.in(0, segs->frame_offset, (size_t)(n_frames + 1) * 4, m->st_fo);
     if (n > 0) {
-        LF_HIP_CHECK(m, hipMemcpyAsync(idx, m->st_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(m, hipMemcpyAsync(dist, m->st_dist.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        d.code = st.in(0, segs->code, c * 32, m->st_code);
+        if (segs->color) d.color = st.in(0, segs->color, c, m->st_color);
+        if (segs->keep) d.keep = st.in(0, segs->keep, c, m->st_keep);
+        if (segs->ground) d.ground = st.in(0, segs->ground, c * 32, m->st_ground);
     }
-    LF_HIP_CHECK(m, hipStreamSynchronize(s));
-    return LF_OK;
+    int32_t* d_idx = st.out(0, idx, (c ? c : 1) * 4, m->st_idx);
+    float* d_dist = st.out(0, dist, (c ? c : 1) * 4, m->st_dist);
+    if ((rc = st.upload()) != LF_OK) return rc;
+    if ((rc = device_form(&d, d_idx, d_dist)) != LF_OK) return rc;
+    return fetch(m, { { idx, d_idx, c * 4 }, { dist, d_dist, c * 4 } });
 }
 
 namespace {
@@ -220,7 +177,7 @@ extern "C" int lf_map_align(lf_map* m, lf_handle* h, const lf_segments* segs, in
     if ((rc = open_batch(m, h, segs, n, n_frames, idx, dist, on_device, &b)) != LF_OK) return rc;
     if ((rc = queue_align(m, b, frame_pose, cfg)) != LF_OK) return rc;
     if ((rc = release_handle(m, h)) != LF_OK) return rc;
-    return fetch_results(m, results, m->al_res, (size_t)n_frames * sizeof(lf_align_result));
+    return fetch(m, { { results, m->al_res.p, (size_t)n_frames * sizeof(lf_align_result) } });
 }
 
 extern "C" int lf_map_step_aligned(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const double* frame_pose,
@@ -232,7 +189,7 @@ extern "C" int lf_map_step_aligned(lf_map* m, lf_handle* h, const lf_segments* s
     rc = step_solved(m, h, "lf_map_step_aligned", segs, n, n_frames, step, idx, dist,
                      [&](const ma::Batch& b) { return queue_align(m, b, frame_pose, cfg); });
     if (rc != LF_OK) return rc;
-    return fetch_results(m, results, m->al_res, (size_t)n_frames * sizeof(lf_align_result));
+    return fetch(m, { { results, m->al_res.p, (size_t)n_frames * sizeof(lf_align_result) } });
 }
 
 extern "C" int lf_map_step_aligned_host(lf_map* m, const lf_segments* segs, int n, int n_frames, const double* frame_pose,

@@ -99,7 +99,12 @@ extern "C" int lf_map_render_camera(lf_map* m, const lf_camera_view* v, const do
     hipStream_t s = m->stream;
     int rc;
     if ((rc = scratch(m, e->tiles, n_tiles * 3 * sizeof(unsigned))) || (rc = scratch(m, e->counters, n_counters * sizeof(int))) ||
-        (rc = scratch(m, e->pose, (size_t)n_frames * 4 * sizeof(double))) || (!on_device && (rc = scratch(m, e->frames, image_bytes)))) return rc;
+        (rc = scratch(m, e->pose, (size_t)n_frames * 4 * sizeof(double)))) return rc;
+    // (a host caller's frames are painted where they were staged)
+    Staging st(m);
+    const uint8_t* d_src = src ? st.in(on_device, src, image_bytes, e->frames) : nullptr;
+    uint8_t* d_out = st.out(on_device, out, image_bytes, e->frames);
+    if ((rc = st.upload()) != LF_OK) return rc;
     if (e->h_counters.bytes < n_counters * sizeof(int)) {
         LF_HIP_CHECK(m, hipStreamSynchronize(s));
         LF_HIP_CHECK(m, e->h_counters.alloc((size_t)(mc::kCounterBase + 3 * mc::kMaxFrames) * sizeof(int)));
@@ -143,13 +148,6 @@ extern "C" int lf_map_render_camera(lf_map* m, const lf_camera_view* v, const do
     }
     if ((rc = scratch(m, e->rec, (size_t)(total ? total : 1) * sizeof(mc::Record))) != LF_OK) return rc;
     mc::Record* rec = static_cast<mc::Record*>(e->rec.p);
-    const uint8_t* d_src = src;
-    uint8_t* d_out = out;
-    if (!on_device) {
-        d_out = static_cast<uint8_t*>(e->frames.p);
-        d_src = src ? d_out : nullptr;
-        if (src) LF_HIP_CHECK(m, hipMemcpyAsync(d_out, src, image_bytes, hipMemcpyHostToDevice, s));
-    }
     {
         CallClock::Scope t(e->clock, 2);
         mc::launch_project(dv, m->d, pose4, n_frames, cursor, counters, rec, s);
@@ -160,10 +158,7 @@ extern "C" int lf_map_render_camera(lf_map* m, const lf_camera_view* v, const do
     }
     LF_HIP_CHECK(m, hipGetLastError());
     e->rendered = true;
-    if (!on_device) {
-        LF_HIP_CHECK(m, hipMemcpyAsync(out, d_out, image_bytes, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(m, hipStreamSynchronize(s));
-    }
+    if ((rc = fetch(m, { { out, d_out, image_bytes } })) != LF_OK) return rc;
     if (counts) memcpy(counts, hc + mc::kCounterBase, (size_t)n_frames * 3 * sizeof(int32_t));
     return LF_OK;
 }

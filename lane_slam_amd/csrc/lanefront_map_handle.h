@@ -1,7 +1,7 @@
 // The live map's handle, for the translation units of lf_map_*: the map itself (lanefront_map.hip), its two views
 // (lanefront_map_render.hip, lanefront_map_camera.hip), the pose alignment (lanefront_map_align.hip) and the trajectory smoother
 // (lanefront_map_smooth.hip); the localisation without a prior pose (lanefront_map_localize.hip); the culling (lanefront_map_prune.hip).  The three pose solvers share one
-// front end (argument check, batch opener, prior-pose upload, result fetch) and the two solving steps one body and, with
+// front end (argument check, batch opener, prior-pose upload) and the two solving steps one body and, with
 // lf_map_step_host, one host-form wrapper: all of it lives in lanefront_map_align.hip and is declared at the end of this file.
 #pragma once
 #include <functional>
@@ -115,8 +115,6 @@ int open_batch(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_fr
 // queue the upload of [n_frames][3] prior poses into m->prior_pose; pose null: +0 everywhere.  (Every call that queues this copy
 // waits for the stream before it returns: pose has left the host by then.)
 int upload_prior_pose(lf_map* m, const double* pose, int n_frames, const double** d_pose);
-// copy a solver's results to the host (and a second array when dst2 is given), then wait for the map's stream
-int fetch_results(lf_map* m, void* dst, const DevBuf& src, size_t bytes, void* dst2 = nullptr, const DevBuf* src2 = nullptr, size_t bytes2 = 0);
 
 // ---- the steps that solve between association and update (lf_map_step_aligned, lf_map_step_smoothed) and the host forms
 // associate, queue the solver (it leaves x, y, cos, sin per frame in m->pose), pack the block with those poses, update the map.

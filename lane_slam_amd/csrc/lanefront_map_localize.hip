@@ -53,5 +53,5 @@ extern "C" int lf_map_localize(lf_map* m, lf_handle* h, const lf_segments* segs,
     }
     LF_HIP_CHECK(m, hipGetLastError());
     if ((rc = release_handle(m, h)) != LF_OK) return rc;
-    return fetch_results(m, results, m->lo_res, res_bytes);
+    return fetch(m, { { results, m->lo_res.p, res_bytes } });
 }

@@ -57,14 +57,16 @@ extern "C" int lf_map_prune(lf_map* m, const lf_prune_config* c, lf_prune_result
         (rc = scratch(m, st.wg, ((n + pr::kWg - 1) / pr::kWg) * sizeof(int))) || (rc = scratch(m, st.s_code, n * 32)) || (rc = scratch(m, st.s_color, n)) ||
         (rc = scratch(m, st.s_ground, n * 4 * sizeof(double))) || (rc = scratch(m, st.s_hits, n * sizeof(int))) || (rc = scratch(m, st.s_last, n * sizeof(int))))
         return rc;
-    if (remap && !remap_on_device && (rc = scratch(m, st.remap, (size_t)cap * sizeof(int32_t))) != LF_OK) return rc;
+    Staging host(m);
+    int32_t* d_remap = remap ? host.out(remap_on_device, remap, (size_t)cap * sizeof(int32_t), st.remap) : nullptr;
+    if ((rc = host.upload()) != LF_OK) return rc;
     pr::Work w;
     memset(&w, 0, sizeof(w));
     w.reason = static_cast<uint8_t*>(st.reason.p); w.rank = static_cast<int*>(st.rank.p); w.wg = static_cast<int*>(st.wg.p);
     w.counters = static_cast<int*>(st.counters.p);
     w.s_code = static_cast<uint8_t*>(st.s_code.p); w.s_color = static_cast<uint8_t*>(st.s_color.p); w.s_ground = static_cast<double*>(st.s_ground.p);
     w.s_hits = static_cast<int*>(st.s_hits.p); w.s_last = static_cast<int*>(st.s_last.p);
-    w.remap = !remap ? nullptr : remap_on_device ? remap : static_cast<int32_t*>(st.remap.p);
+    w.remap = d_remap;
     {
         StageClock::Scope t(m, m->clock, kMapPruneStage);
         LF_HIP_CHECK(m, hipMemsetAsync(w.counters, 0, pr::kNCounters * sizeof(int), s));

@@ -102,8 +102,10 @@ extern "C" int lf_map_render(lf_map* m, const lf_map_view* v, const double* traj
     const size_t image_bytes = (size_t)v->rows * v->cols * 3;
     hipStream_t s = m->stream;
     if ((rc = scratch(m, e->px, (size_t)n_lines * sizeof(int4))) || (rc = scratch(m, e->tiles, (size_t)n_tiles * 3 * sizeof(unsigned))) ||
-        (rc = scratch(m, e->counters, mr::kCounterInts * sizeof(int))) || (n_traj && (rc = scratch(m, e->traj, (size_t)n_points * 2 * sizeof(double)))) ||
-        (!out_on_device && (rc = scratch(m, e->out, image_bytes)))) return rc;
+        (rc = scratch(m, e->counters, mr::kCounterInts * sizeof(int)))) return rc;
+    Staging st(m);
+    if (n_traj) st.in(0, trajectory, (size_t)n_points * 2 * sizeof(double), e->traj);
+    uint8_t* d_out = st.out(out_on_device, out, image_bytes, e->out);
     e->rendered = false;
     if ((rc = e->clock.begin(m)) != LF_OK) return rc;
     unsigned* tile_count = static_cast<unsigned*>(e->tiles.p);
@@ -112,7 +114,7 @@ extern "C" int lf_map_render(lf_map* m, const lf_map_view* v, const double* traj
     int* counters = static_cast<int*>(e->counters.p);
     int4* px = static_cast<int4*>(e->px.p);
     // (the caller's points are on the device before this call returns: the wait for the total below comes after their copy)
-    if (n_traj) LF_HIP_CHECK(m, hipMemcpyAsync(e->traj.p, trajectory, (size_t)n_points * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = st.upload()) != LF_OK) return rc;
     LF_HIP_CHECK(m, hipMemsetAsync(tile_count, 0, (size_t)n_tiles * sizeof(unsigned), s));
     LF_HIP_CHECK(m, hipMemsetAsync(counters, 0, mr::kCounterInts * sizeof(int), s));
     {
@@ -135,7 +137,6 @@ extern "C" int lf_map_render(lf_map* m, const lf_map_view* v, const double* traj
     }
     if ((rc = scratch(m, e->list, (size_t)(total ? total : 1) * sizeof(unsigned))) != LF_OK) return rc;
     unsigned* list = static_cast<unsigned*>(e->list.p);
-    uint8_t* d_out = out_on_device ? out : static_cast<uint8_t*>(e->out.p);
     {
         CallClock::Scope t(e->clock, 2);
         mr::launch_bin(dv, m->d, n_traj, px, cursor, list, s);
@@ -146,13 +147,8 @@ extern "C" int lf_map_render(lf_map* m, const lf_map_view* v, const double* traj
     }
     LF_HIP_CHECK(m, hipGetLastError());
     e->n_drawn = hc[0]; e->n_skipped = hc[1]; e->rendered = true;
-    if (!out_on_device) {
-        LF_HIP_CHECK(m, hipMemcpyAsync(out, d_out, image_bytes, hipMemcpyDeviceToHost, s));
-        LF_HIP_CHECK(m, hipEventRecord(e->done, s));
-        LF_HIP_CHECK(m, hipStreamSynchronize(s));
-    } else {
-        LF_HIP_CHECK(m, hipEventRecord(e->done, s));
-    }
+    if ((rc = fetch(m, { { out, d_out, image_bytes } })) != LF_OK) return rc;
+    LF_HIP_CHECK(m, hipEventRecord(e->done, s));
     if (n_drawn) *n_drawn = e->n_drawn;
     if (n_skipped) *n_skipped = e->n_skipped;
     return LF_OK;

@@ -68,7 +68,7 @@ int queue_smooth(lf_map* m, const ma::Batch& view, const double* frame_pose, con
 
 int fetch_smoothed(lf_map* m, int n_frames, int n_chains, lf_align_result* results, int32_t* chain_status)
 {
-    return fetch_results(m, results, m->al_res, (size_t)n_frames * sizeof(lf_align_result), chain_status, &m->sm_status, (size_t)n_chains * 4);
+    return fetch(m, { { results, m->al_res.p, (size_t)n_frames * sizeof(lf_align_result) }, { chain_status, m->sm_status.p, (size_t)n_chains * 4 } });
 }
 
 }  // namespace

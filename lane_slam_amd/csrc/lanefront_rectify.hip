@@ -241,14 +241,10 @@ extern "C" int lf_rectify_batch(lf_handle* h, const uint8_t* src, int src_on_dev
     if ((rc = ensure_map(h, "lf_rectify_batch")) != LF_OK) return rc;
     RectState& e = *h->rect;
     hipStream_t s = h->stream;
-    if (!src_on_device && (rc = scratch(h, e.in, src_bytes))) return rc;
-    if (!dst_on_device && (rc = scratch(h, e.out, dst_bytes))) return rc;
-    const uint8_t* d_src = src;
-    if (!src_on_device) {
-        LF_HIP_CHECK(h, hipMemcpyAsync(e.in.p, src, src_bytes, hipMemcpyHostToDevice, s));
-        d_src = static_cast<const uint8_t*>(e.in.p);
-    }
-    uint8_t* d_dst = dst_on_device ? dst : static_cast<uint8_t*>(e.out.p);
+    Staging st(h);
+    const uint8_t* d_src = st.in(src_on_device, src, src_bytes, e.in);
+    uint8_t* d_dst = st.out(dst_on_device, dst, dst_bytes, e.out);
+    if ((rc = st.upload()) != LF_OK) return rc;
     rect::Map m;
     m.xy = static_cast<const short2*>(e.xy.p); m.frac = static_cast<const uint16_t*>(e.frac.p); m.tab = static_cast<const int16_t*>(e.tab.p);
     m.w = e.w; m.h = e.h;
@@ -268,10 +264,7 @@ extern "C" int lf_rectify_batch(lf_handle* h, const uint8_t* src, int src_on_dev
         rect::launch_remap(m, d_src, n_frames, rows, cols, channels, d_dst, (int)split, s);
     }
     LF_HIP_CHECK(h, hipGetLastError());
-    if (dst_on_device) return LF_OK;
-    LF_HIP_CHECK(h, hipMemcpyAsync(dst, d_dst, dst_bytes, hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    return LF_OK;
+    return fetch(h, { { dst, d_dst, dst_bytes } });
 }
 
 extern "C" int lf_rectify_timing(lf_handle* h, double* ms_per_stage, int n)

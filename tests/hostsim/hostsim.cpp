@@ -129,7 +129,7 @@ extern "C" int hs_lsd_detect(const double* scaled, int H, int W, double rho, dou
                             cap, reg_lds, 0, nullptr);
 }
 
-// host parameters exactly as the product computes them (lanefront_api.hip make_lsd_params)
+// host parameters exactly as the product computes them (lanefront_lsd.hip: LsdState::init)
 extern "C" void hs_lsd_params(double ang_th, double quant, int Hs, int Ws, double* rho, double* prec, double* p,
                               double* log_nt, int* min_reg_size)
 {
