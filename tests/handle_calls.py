@@ -102,9 +102,10 @@ def run_keylines(fe, kind, images, n_octaves, gray, describe=True, params=None, 
     return res
 
 
-def describe_device(fe, gray, line_frame, in_octave, angle, num_pixels, octave):
+def describe_device(fe, gray, line_frame, in_octave, angle, num_pixels, octave, want=("desc", "code")):
     """lf_describe_keylines with on_device = 1: every array a torch device tensor, desc / code sentinel-filled (EXTRA rows behind the
-    lines must stay so).  Returns the C return code and (desc, code) on the host."""
+    lines must stay so).  Returns the C return code and (desc, code) on the host.  want: the outputs asked for -- the other is passed
+    as NULL and must come back untouched."""
     dev = torch.device("cuda", 0)
     n = len(octave)
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, np.dtype(dt))).to(dev)     # noqa: E731
@@ -115,21 +116,27 @@ def describe_device(fe, gray, line_frame, in_octave, angle, num_pixels, octave):
     torch.cuda.synchronize()
     rc = fe.lib.lf_describe_keylines(fe.h, ct.c_void_p(g.data_ptr()), int(g.shape[0]), ct.c_void_p(fr.data_ptr()), ct.c_void_p(io.data_ptr()),
                                      ct.c_void_p(ang.data_ptr()), ct.c_void_p(npx.data_ptr()), ct.c_void_p(oc.data_ptr()), n,
-                                     ct.c_void_p(desc.data_ptr()), ct.c_void_p(code.data_ptr()), 1)
+                                     ct.c_void_p(desc.data_ptr()) if "desc" in want else None,
+                                     ct.c_void_p(code.data_ptr()) if "code" in want else None, 1)
     torch.cuda.synchronize()
     d, c = desc.cpu().numpy(), code.cpu().numpy()
     assert (d[n:] == np.float32(SENTINEL["f4"])).all() and (c[n:] == SENTINEL["u1"]).all(), "lf_describe_keylines wrote behind its lines"
+    assert "desc" in want or (d == np.float32(SENTINEL["f4"])).all(), "lf_describe_keylines wrote descriptors nobody asked for"
+    assert "code" in want or (c == SENTINEL["u1"]).all(), "lf_describe_keylines wrote codes nobody asked for"
     return rc, d[:n], c[:n]
 
 
-def describe_host(fe, gray, line_frame, in_octave, angle, num_pixels, octave):
-    """lf_describe_keylines with host arrays, desc / code sentinel-filled: (rc, desc, code)."""
+def describe_host(fe, gray, line_frame, in_octave, angle, num_pixels, octave, want=("desc", "code")):
+    """lf_describe_keylines with host arrays, desc / code sentinel-filled: (rc, desc, code).  want: as for describe_device."""
     gray = np.ascontiguousarray(gray, np.uint8)
     n = len(octave)
     c32 = lambda a, dt: np.ascontiguousarray(a, np.dtype(dt))      # noqa: E731
     fr, io, ang, npx, oc = c32(line_frame, "i4"), c32(np.reshape(in_octave, (-1, 4)), "f4"), c32(angle, "f4"), c32(num_pixels, "i4"), c32(octave, "i4")
     desc, code = filled((n + EXTRA, 72), "f4"), filled((n + EXTRA, 32), "u1")
     p = lambda a: a.ctypes.data_as(ct.c_void_p)                     # noqa: E731
-    rc = fe.lib.lf_describe_keylines(fe.h, p(gray), gray.shape[0], p(fr), p(io), p(ang), p(npx), p(oc), n, p(desc), p(code), 0)
+    rc = fe.lib.lf_describe_keylines(fe.h, p(gray), gray.shape[0], p(fr), p(io), p(ang), p(npx), p(oc), n, p(desc) if "desc" in want else None,
+                                     p(code) if "code" in want else None, 0)
     assert (desc[n:] == np.float32(SENTINEL["f4"])).all() and (code[n:] == SENTINEL["u1"]).all(), "lf_describe_keylines wrote behind its lines"
+    assert "desc" in want or (desc == np.float32(SENTINEL["f4"])).all(), "lf_describe_keylines wrote descriptors nobody asked for"
+    assert "code" in want or (code == SENTINEL["u1"]).all(), "lf_describe_keylines wrote codes nobody asked for"
     return rc, desc[:n], code[:n]
