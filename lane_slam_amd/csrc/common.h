@@ -78,6 +78,18 @@ struct SegParams {
     int rectified_input;   // GroundProjection.rectified_input: the pixels are rectified already, a-7 applies the homography alone
 };
 
+// What a batch of the front end reports (LsdState::d_status): ONE 32-byte copy takes it to pinned host memory (lf_handle::h_status)
+struct BatchStatus {
+    int32_t lines_overflow;      // k_seg_offsets: some problem has more lines than cap_lines
+    int32_t over_small, over_medium;   // k_seg_offsets: problems whose defined pixels exceed k_lsd_grow's LDS slice at its small / medium size (LsdState::adapt_slice)
+    int32_t max_defined;         // k_seg_offsets: the largest problem's defined pixels
+    int32_t detector_failures;   // k_ed_slots: frames on which the EDLines detector gave up
+    int32_t rec_need;            // k_lsd_grad, k_lsd_seed32: entries the per-problem lists would have needed (LsdState::grow_lists)
+    int32_t reserved;
+    int32_t total;               // k_seg_offsets: the batch's segments
+};
+static_assert(sizeof(BatchStatus) == 32, "BatchStatus is eight words");
+
 // device resize tables for the LSD bilinear step (cv::resize INTER_LINEAR on CV_64F)
 struct ResizeTables {
     const int* xofs;      // [Ws]
@@ -160,7 +172,7 @@ void launch_lsd_grow(const LsdParams& p, int n_frames, const uint32_t* order, co
 int lsd_grow_def_lds(const LsdParams& p, int lds_kb);   // defined pixels of a problem that fit k_lsd_grow's LDS slice of lds_kb KB
 constexpr int kGrowLdsKb[3] = { 13, 28, 40 };           // the slice sizes a handle moves between (k_lsd_grow.hip)
 void launch_seg_offsets(int n_frames, int cap_lines, const int* counts, int* seg_offset, int* frame_offset,
-                        int* overflow, const int* norder, int cap_small, int cap_medium, hipStream_t s);
+                        BatchStatus* status, const int* norder, int cap_small, int cap_medium, hipStream_t s);
 // LineDetector2Dense's per-pixel lines (k_dense.hip): slots [pc][cap] of lines (exact ints as floats) and (nx, ny, x, y) records
 void launch_dense(int Hc, int W, int Ww, int cap_lines, float thr, int n_problems, const uint32_t* strong, const uint32_t* maskbits,
                   const uint32_t* bwbits, float* slot_lines, float* rec, int* counts, hipStream_t s);

@@ -1602,19 +1602,19 @@ void launch_kl_assemble(const EdAll& all, int n_octaves, int n_frames, const int
         hipLaunchKernelGGL(k_kl_assemble<true>, dim3(n_frames), dim3(256), 0, s, all, n_octaves, frame_offset, capacity, out, big, big_stride, lds_lines);
 }
 
-// exclusive scan of the per-frame counts -> frame_offset [n_frames + 1]; total and overflow flag into pinned[0..1]
-__global__ void k_kl_offsets(int n_frames, const int* __restrict__ frame_count, int capacity, int* __restrict__ frame_offset, int* __restrict__ totals)
+// exclusive scan of the per-frame counts -> frame_offset [n_frames + 1]; the batch's KlTotals
+__global__ void k_kl_offsets(int n_frames, const int* __restrict__ frame_count, int capacity, int* __restrict__ frame_offset, KlTotals* __restrict__ totals)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int acc = 0;
     for (int f = 0; f < n_frames; ++f) { frame_offset[f] = acc; acc += frame_count[f]; }
     frame_offset[n_frames] = acc;
-    totals[0] = acc;
-    totals[1] = acc > capacity ? 1 : 0;
-    totals[2] = acc > capacity ? 0 : acc;        // what the descriptor stage may walk: nothing when the output overflows
+    totals->total = acc;
+    totals->overflow = acc > capacity ? 1 : 0;
+    totals->describe_n = acc > capacity ? 0 : acc;
 }
 
-void launch_kl_offsets(int n_frames, const int* frame_count, int capacity, int* frame_offset, int* totals, hipStream_t s)
+void launch_kl_offsets(int n_frames, const int* frame_count, int capacity, int* frame_offset, KlTotals* totals, hipStream_t s)
 {
     hipLaunchKernelGGL(k_kl_offsets, dim3(1), dim3(64), 0, s, n_frames, frame_count, capacity, frame_offset, totals);
 }
@@ -1697,7 +1697,7 @@ __global__ __launch_bounds__(256) void k_kl_mask_move(const int* __restrict__ fo
     }
 }
 
-void launch_kl_mask(int n_frames, const int* fo_src, int* fo_dst, int* totals, int capacity, const uint8_t* masks, int rows, int cols, uint8_t* erased,
+void launch_kl_mask(int n_frames, const int* fo_src, int* fo_dst, KlTotals* totals, int capacity, const uint8_t* masks, int rows, int cols, uint8_t* erased,
                     int* kept_count, const KlOut& src, const KlOut& dst, hipStream_t s)
 {
     hipLaunchKernelGGL(k_kl_mask_flags, dim3(n_frames), dim3(256), 0, s, fo_src, src.start_end, masks, rows, cols, capacity, erased, kept_count);

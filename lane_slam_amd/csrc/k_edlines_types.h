@@ -33,13 +33,16 @@ struct EdAll { EdOct o[LF_MAX_OCTAVES]; };
 
 struct EdFitParams { int anchor_threshold, scan, min_line_len; double fit_err; };
 
+// What k_kl_offsets reports of a KeyLine batch: its KeyLines, whether they exceed the output, what LBD may walk (nothing if they do)
+struct KlTotals { int32_t total, overflow, describe_n; };
+
 struct KlOut {
     float* start_end; float* in_octave; float* angle; int32_t* num_pixels; float* line_length; int32_t* octave;
     int32_t* class_id; float* response; float* size; float* pt; float* salience; int32_t* frame;
 };
 
 
-void launch_kl_mask(int n_frames, const int* fo_src, int* fo_dst, int* totals, int capacity, const uint8_t* masks, int rows, int cols, uint8_t* erased,
+void launch_kl_mask(int n_frames, const int* fo_src, int* fo_dst, KlTotals* totals, int capacity, const uint8_t* masks, int rows, int cols, uint8_t* erased,
                     int* kept_count, const KlOut& src, const KlOut& dst, hipStream_t s);
 size_t ed_anchor_words(int W, int H);
 void launch_ed_grad(int H, int W, int n_frames, const uint8_t* src, const int* taps5, int grad_threshold, uint8_t* blur,
@@ -52,7 +55,7 @@ size_t ed_detect_lds_bytes(int W, int H, int scan, bool* marks_in_lds);
 int launch_ed_detect(const EdAll& all, const EdFitParams& fp, int n_octaves, int n_frames, size_t lds_bytes, hipStream_t s);
 void launch_ed_slots(const EdAll& all, int n_frames, const uint32_t* maskbits, int Ww, int cap_lines, float* slot_lines, int* counts, int* failed, hipStream_t s);
 void launch_kl_count(const EdAll& all, int n_octaves, int n_frames, int* frame_count, int* status, hipStream_t s);
-void launch_kl_offsets(int n_frames, const int* frame_count, int capacity, int* frame_offset, int* totals, hipStream_t s);
+void launch_kl_offsets(int n_frames, const int* frame_count, int capacity, int* frame_offset, KlTotals* totals, hipStream_t s);
 void launch_kl_assemble(const EdAll& all, int n_octaves, int n_frames, const int* frame_offset, int capacity, const KlOut& out, uint8_t* big, int big_stride,
                         int lds_lines, hipStream_t s);
 

@@ -15,12 +15,9 @@
 
 namespace lf {
 
-// overflow[0]: some problem has more lines than cap_lines.  overflow[1], [2]: problems whose defined pixels exceed the region
-// growing kernel's LDS slice at its small / medium size (the host sizes the next batch's slices from them, k_lsd_grow.hip);
-// overflow[3]: the largest problem's defined pixels; overflow[7]: the batch's segment total (so that ONE copy of the eight words
-// takes everything lf_wait needs to the host)
+// writes the batch's BatchStatus (common.h) but for detector_failures and rec_need
 __global__ void k_seg_offsets(int n_frames, int cap_lines, const int* __restrict__ counts, int* __restrict__ seg_offset,
-                              int* __restrict__ frame_offset, int* __restrict__ overflow, const int* __restrict__ norder, int cap_small, int cap_medium)
+                              int* __restrict__ frame_offset, BatchStatus* __restrict__ status, const int* __restrict__ norder, int cap_small, int cap_medium)
 {
     // single workgroup exclusive scan over n_frames*3 clipped counts
     __shared__ int carry;
@@ -35,7 +32,7 @@ __global__ void k_seg_offsets(int n_frames, int cap_lines, const int* __restrict
         int v = 0;
         if (i < n) {
             v = counts[i]; if (v > cap_lines) { v = cap_lines; ovf = 1; }
-            if (norder) { const int nd = norder[i]; if (nd > cap_small) atomicAdd(overflow + 1, 1); if (nd > cap_medium) atomicAdd(overflow + 2, 1); atomicMax(overflow + 3, nd); }
+            if (norder) { const int nd = norder[i]; if (nd > cap_small) atomicAdd(&status->over_small, 1); if (nd > cap_medium) atomicAdd(&status->over_medium, 1); atomicMax(&status->max_defined, nd); }
         }
         int inc = v;
 #pragma unroll
@@ -53,16 +50,16 @@ __global__ void k_seg_offsets(int n_frames, int cap_lines, const int* __restrict
         if (t == blockDim.x - 1) carry = off + inc;
         __syncthreads();
     }
-    if (t == 0) { seg_offset[n] = carry; frame_offset[n_frames] = carry; overflow[7] = carry; }
-    if (ovf) atomicOr(overflow, 1);
+    if (t == 0) { seg_offset[n] = carry; frame_offset[n_frames] = carry; status->total = carry; }
+    if (ovf) atomicOr(&status->lines_overflow, 1);
 }
 
 void launch_seg_offsets(int n_frames, int cap_lines, const int* counts, int* seg_offset, int* frame_offset,
-                        int* overflow, const int* norder, int cap_small, int cap_medium, hipStream_t s)
+                        BatchStatus* status, const int* norder, int cap_small, int cap_medium, hipStream_t s)
 {
     // four waves: a 1024-thread workgroup waits for a CU with sixteen free wave slots in a busy pipeline
     hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(256), 0, s, n_frames, cap_lines, counts, seg_offset,
-                       frame_offset, overflow, norder, cap_small, cap_medium);
+                       frame_offset, status, norder, cap_small, cap_medium);
 }
 
 __device__ __forceinline__ int check_bounds(int v, int bound) { return v < 0 ? 0 : (v >= bound ? bound - 1 : v); }

@@ -13,7 +13,7 @@ extern "C" int lf_ai_transform_batch(lf_handle* h, const uint8_t* frames, int n_
         lf_set_error(h, LF_ERR_BAD_ARG, "lf_ai_transform_batch: null argument, n_frames < 1 or an empty frame (%d x %d)", rows, cols);
         return LF_ERR_BAD_ARG;
     }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (const int rc = refuse_in_flight(h)) return rc;
     const int S = rows < 100 ? rows : 100;                     // image[-100:] (kmeans.py:24)
     const long long n = (long long)S * cols;
     if (n > (1 << 24)) {      // the limit of lf_kmeans (k_kmeans.h: per-wave 32-bit colour sums)
@@ -53,7 +53,7 @@ extern "C" int lf_set_ai_transform(lf_handle* h, const double scale[3], const do
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
     if (!scale || !shift) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_ai_transform: null argument"); return LF_ERR_BAD_ARG; }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (const int rc = refuse_in_flight(h)) return rc;
     float sc[3], sh[3];
     for (int i = 0; i < 3; ++i) {
         sc[i] = (float)scale[i]; sh[i] = (float)shift[i];          // scaleandshift2 casts each value to float32 (scale_and_shift.py:28-29)

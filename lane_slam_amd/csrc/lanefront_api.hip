@@ -151,7 +151,7 @@ extern "C" int lf_set_descriptor_params(lf_handle* h, const lf_descriptor_params
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
     if (!p) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_descriptor_params: null argument"); return LF_ERR_BAD_ARG; }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (const int rc = refuse_in_flight(h)) return rc;
     if (p->width_of_band < 1 || p->width_of_band > lbd_max_width_of_band()) {
         lf_set_error(h, LF_ERR_UNSUPPORTED, "widthOfBand %d outside 1..%d", p->width_of_band, lbd_max_width_of_band());
         return LF_ERR_UNSUPPORTED;
@@ -217,7 +217,7 @@ static int alloc_buffers(lf_handle* h)
     o.lines = h->out_lines; o.normals = h->out_normals; o.color = h->out_color; o.pixels_normalized = h->out_pixels_normalized;
     o.ground = h->out_ground; o.keep = h->out_keep; o.desc = h->out_desc; o.code = h->out_code;
     o.frame_offset = h->d_frame_offset;
-    LF_HIP_CHECK(h, h->h_pinned.alloc(16 * sizeof(int)));
+    LF_HIP_CHECK(h, h->h_status.alloc(sizeof(BatchStatus)));
     return LF_OK;
 }
 
@@ -295,14 +295,7 @@ int lf::run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_worki
     if (h->lsd.lists_lost) { lf_set_error(h, LF_ERR_HIP, "the handle lost its LSD lists to an out-of-memory growth (lf_wait / lf_set_image reported it)"); return LF_ERR_HIP; }
     h->overflow_zeroed = false;          // (set at the successful END only: an error exit must not leave run_segments believing the overflow words are zero)
     h->draw_frames = 0;                  // k_pre rewrites d_bgr: lf_draw_lines waits for the next completed batch
-    PreParams pp = h->pre;
-    if (from_working_image) {
-        // plugin path: the caller already resized, cropped and colour-corrected (line_detector_node.py:163-180)
-        pp.in_rows = h->Hc; pp.in_cols = h->W; pp.img_rows = h->Hc; pp.img_cols = h->W; pp.top_cutoff = 0;
-        pp.resize = 0;
-        for (int i = 0; i < 3; ++i) { pp.ai_scale[i] = 1.f; pp.ai_shift[i] = 0.f; }
-        pp.identity_ai = 1;
-    }
+    const PreParams pp = from_working_image ? plugin_working_pre(h) : h->pre;
     const bool dense = h->detector == LF_DETECTOR_DENSE;
     if (dense) {
         int rc = dense_prepare(h);
@@ -376,10 +369,10 @@ int lf::run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe)
     hipStream_t s = h->stream;
     {
         StageClock::Scope t(h, h->clock, ST_SEGMENTS);
-        if (!h->overflow_zeroed) LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_overflow, 0, 4 * sizeof(int), s));
+        if (!h->overflow_zeroed) LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_status, 0, offsetof(BatchStatus, detector_failures), s));     // lines_overflow .. max_defined
         h->overflow_zeroed = false;
         launch_seg_offsets(n, h->cap_lines, h->d_counts, h->d_seg_offset, dev_out.frame_offset ? dev_out.frame_offset : h->d_frame_offset,
-                           h->lsd.d_overflow, h->slot_mode != SEG_FLOAT ? nullptr : h->lsd.d_norder, lsd_grow_def_lds(h->lsd.params, kGrowLdsKb[0]),
+                           h->lsd.d_status, h->slot_mode != SEG_FLOAT ? nullptr : h->lsd.d_norder, lsd_grow_def_lds(h->lsd.params, kGrowLdsKb[0]),
                            lsd_grow_def_lds(h->lsd.params, kGrowLdsKb[1]), s);
         launch_segments(h->seg, n, h->d_slot_lines, h->d_counts, h->d_seg_offset,
                         h->slot_mode == SEG_DENSE ? reinterpret_cast<const uint32_t*>(h->d_dense_rec.p) : h->d_maskbits.p, h->Ww, dev_out,
@@ -398,6 +391,9 @@ int lf::run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe)
     return LF_OK;
 }
 
+// a batch's status travels to pinned host memory behind its kernels, in ONE copy
+static int fetch_status(lf_handle* h) { LF_HIP_CHECK(h, hipMemcpyAsync(h->h_status, h->lsd.d_status, sizeof(BatchStatus), hipMemcpyDeviceToHost, h->stream)); return LF_OK; }
+
 // queue a-1..a-9 for a batch on the handle's stream; device outputs only; no host sync
 extern "C" int lf_process_batch_async(lf_handle* h, const uint8_t* frames, int n_frames, int frames_on_device,
                                       lf_segments* out_dev, int describe)
@@ -406,7 +402,7 @@ extern "C" int lf_process_batch_async(lf_handle* h, const uint8_t* frames, int n
     if (!frames || !out_dev || n_frames < 1) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_process_batch: null argument or n_frames < 1"); return LF_ERR_BAD_ARG; }
     if (n_frames > h->max_frames) { lf_set_error(h, LF_ERR_CAPACITY, "n_frames %d exceeds max_frames %d", n_frames, h->max_frames); return LF_ERR_CAPACITY; }
     if (describe && (!out_dev->lines)) { lf_set_error(h, LF_ERR_BAD_ARG, "describe needs out->lines"); return LF_ERR_BAD_ARG; }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is already in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (h->flight.kind != InFlight::NONE) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is already in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const size_t frame_bytes = (size_t)h->cfg.in_rows * h->cfg.in_cols * 3;
@@ -428,16 +424,33 @@ extern "C" int lf_process_batch_async(lf_handle* h, const uint8_t* frames, int n
     int rc = h->detector == LF_DETECTOR_EDLINES ? run_detect_edlines(h, d_in, n_frames) : run_detect(h, d_in, n_frames, false);
     if (rc != LF_OK) return rc;
     rc = run_segments(h, n_frames, *out_dev, describe != 0);
-    if (rc != LF_OK) return rc;
-    // total + overflow flag travel to pinned host memory behind the kernels
-    // one copy: overflow[0..3] -> h_pinned[1..4], the detector's failure count -> [5], the segment total (overflow[7]) -> [8]
-    LF_HIP_CHECK(h, hipMemcpyAsync(&h->h_pinned[1], h->lsd.d_overflow, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
-    h->pending = true;
-    h->pending_keylines = false;
-    h->pending_problems = n_frames * 3;
-    h->pending_capacity = out_dev->capacity;
-    h->pend_in = d_in; h->pend_n = n_frames; h->pend_out = *out_dev; h->pend_describe = describe != 0;
+    if (rc != LF_OK || (rc = fetch_status(h)) != LF_OK) return rc;
+    h->flight = InFlight{ InFlight::SEGMENTS, d_in, n_frames, *out_dev, describe != 0, n_frames * 3, out_dev->capacity };
     return LF_OK;
+}
+
+// Detect and segment n frames into dev -- and again with longer lists while a problem did not fit the per-problem LSD lists (the
+// inputs are still where they were).  queued: the first pass is on the stream and waited for already (lf_wait).  copies() queues
+// what the caller reads behind the kernels, BatchStatus::rec_need among it, before the ONE synchronisation of a pass.
+template <typename Copies>
+static int detect_until_fit(lf_handle* h, const uint8_t* d_in, int n, bool from_working_image, const lf_segments& dev, bool describe, bool queued, Copies copies)
+{
+    // (run_detect_edlines leaves rec_need as the last LSD batch left it; the other detectors' batches zero it)
+    const bool lists_used = from_working_image || h->detector != LF_DETECTOR_EDLINES;
+    for (int attempt = 0;; ++attempt) {
+        if (!queued) {
+            int rc = run_detect(h, d_in, n, from_working_image);
+            if (rc == LF_OK) rc = run_segments(h, n, dev, describe);
+            if (rc == LF_OK) rc = copies();
+            if (rc != LF_OK) return rc;
+            LF_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+        }
+        queued = false;
+        const int need = h->h_status.p->rec_need;
+        if (!lists_used || need <= h->lsd.params.rec_cap) return LF_OK;
+        if (attempt == 4) { lf_set_error(h, LF_ERR_CAPACITY, "the LSD lists keep overflowing (%d entries needed)", need); return LF_ERR_CAPACITY; }
+        if (const int rc = h->lsd.grow_lists(h, need)) return rc;
+    }
 }
 
 extern "C" int lf_wait(lf_handle* h, int* n_segments)
@@ -445,34 +458,28 @@ extern "C" int lf_wait(lf_handle* h, int* n_segments)
     if (!h) return LF_ERR_NOT_INITIALISED;
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     LF_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-    if (!h->pending) { if (n_segments) *n_segments = 0; return LF_OK; }
-    h->pending = false;
-    if (h->pending_keylines) {
-        h->pending_keylines = false;
-        int total_kl = 0, overflow = 0;
-        keylines_pending_result(h, &total_kl, &overflow);
-        if (n_segments) *n_segments = total_kl;
-        if (overflow) { lf_set_error(h, LF_ERR_CAPACITY, "%d KeyLines exceed the output capacity %d", total_kl, h->pending_capacity); return LF_ERR_CAPACITY; }
+    const InFlight f = h->flight;
+    h->flight = InFlight{};
+    switch (f.kind) {
+    case InFlight::NONE: if (n_segments) *n_segments = 0; return LF_OK;
+    case InFlight::KEYLINES: {
+        const KlTotals t = h->kl ? *h->kl->batch.h_pinned : KlTotals{};
+        if (n_segments) *n_segments = t.total;
+        if (t.overflow) { lf_set_error(h, LF_ERR_CAPACITY, "%d KeyLines exceed the output capacity %d", t.total, f.capacity); return LF_ERR_CAPACITY; }
         return LF_OK;
     }
-    for (int attempt = 0; h->detector == LF_DETECTOR_LSD && h->h_pinned[6] > h->lsd.params.rec_cap; ++attempt) {
-        // a problem did not fit the per-problem lists: grow them and run the batch again (its inputs are still where they were)
-        if (attempt == 4) { lf_set_error(h, LF_ERR_CAPACITY, "the LSD lists keep overflowing (%d entries needed)", h->h_pinned[6]); return LF_ERR_CAPACITY; }
-        int rc = h->lsd.grow_lists(h, h->h_pinned[6]);
-        if (rc == LF_OK) rc = run_detect(h, h->pend_in, h->pend_n, false);
-        if (rc == LF_OK) rc = run_segments(h, h->pend_n, h->pend_out, h->pend_describe);
-        if (rc != LF_OK) return rc;
-        LF_HIP_CHECK(h, hipMemcpyAsync(&h->h_pinned[1], h->lsd.d_overflow, 8 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        LF_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    case InFlight::SEGMENTS: break;
     }
-    h->detector_failures = h->detector == LF_DETECTOR_EDLINES ? h->h_pinned[5] : 0;
+    if (const int rc = detect_until_fit(h, f.in, f.n, false, f.out, f.describe, true, [h] { return fetch_status(h); })) return rc;
+    const BatchStatus& st = *h->h_status;
+    h->detector_failures = h->detector == LF_DETECTOR_EDLINES ? st.detector_failures : 0;
     h->draw_frames = 0;
-    const int total = h->h_pinned[8];
+    const int total = st.total;
     if (n_segments) *n_segments = total;
-    if (h->pending_problems > 0) h->lsd.adapt_slice(h->h_pinned[2], h->h_pinned[3], h->pending_problems);
-    if (h->h_pinned[1]) { lf_set_error(h, LF_ERR_CAPACITY, "%s %s run produced more than max_lines_per_color=%d lines", h->detector == LF_DETECTOR_DENSE ? "a" : "an", detector_name(h->detector), h->cap_lines); return LF_ERR_CAPACITY; }
-    if (total > h->pending_capacity) { lf_set_error(h, LF_ERR_CAPACITY, "%d segments exceed the output capacity %d", total, h->pending_capacity); return LF_ERR_CAPACITY; }
-    h->draw_frames = h->pend_n;          // d_bgr holds this batch's corrected images (lf_draw_lines)
+    h->lsd.adapt_slice(st.over_small, st.over_medium, f.problems);
+    if (st.lines_overflow) { lf_set_error(h, LF_ERR_CAPACITY, "%s %s run produced more than max_lines_per_color=%d lines", h->detector == LF_DETECTOR_DENSE ? "a" : "an", detector_name(h->detector), h->cap_lines); return LF_ERR_CAPACITY; }
+    if (total > f.capacity) { lf_set_error(h, LF_ERR_CAPACITY, "%d segments exceed the output capacity %d", total, f.capacity); return LF_ERR_CAPACITY; }
+    h->draw_frames = f.n;          // d_bgr holds this batch's corrected images (lf_draw_lines)
     return LF_OK;
 }
 
@@ -524,11 +531,24 @@ int lf::plugin_stage_image(lf_handle* h, const uint8_t* bgr, int rows, int cols,
     return LF_OK;
 }
 
-// queue the copies of everything lf_detect_lines returns behind the kernels; layout of plug_host:
-// [lines eager x 16][normals64 eager x 16][centers eager x 8][3 mask images]
-int lf::plugin_fetch_results(lf_handle* h)
+PreParams lf::plugin_working_pre(const lf_handle* h)
+{
+    PreParams pp = h->pre;          // (line_detector_node.py:163-180 has done these)
+    pp.in_rows = h->Hc; pp.in_cols = h->W; pp.img_rows = h->Hc; pp.img_cols = h->W; pp.top_cutoff = 0; pp.resize = 0;
+    for (int i = 0; i < 3; ++i) { pp.ai_scale[i] = 1.f; pp.ai_shift[i] = 0.f; }
+    pp.identity_ai = 1;
+    return pp;
+}
+
+// What both lf_set_image* queue behind run_segments: Detections.area = the colour masks as 0/255 bytes (line_detector_lsd.py:127-133),
+// expanded once for the three colours from the bit planes mask_bits; then the copies of everything lf_detect_lines returns; layout
+// of plug_host: [lines eager x 16][normals64 eager x 16][centers eager x 8][3 mask images]
+int lf::plugin_finish(lf_handle* h, const uint32_t* mask_bits)
 {
     hipStream_t s = h->stream;
+    if (const int rc = scratch(h, h->dbg_masks, 3 * h->P)) return rc;
+    launch_edges_u8(h->canny, 3, mask_bits, (uint8_t*)h->dbg_masks.p, s);
+    h->h_counts.resize(3); h->h_seg_offset.resize(4);
     const int eager = kPlugEager < 3 * h->cap_lines ? kPlugEager : 3 * h->cap_lines;
     const size_t need = (size_t)eager * 40 + 3 * h->P;
     if (h->plug_host.bytes < need) LF_HIP_CHECK(h, h->plug_host.alloc(need));
@@ -538,6 +558,8 @@ int lf::plugin_fetch_results(lf_handle* h)
     LF_HIP_CHECK(h, hipMemcpyAsync(p + (size_t)eager * 16, h->d_normals64, (size_t)eager * 16, hipMemcpyDeviceToHost, s));
     LF_HIP_CHECK(h, hipMemcpyAsync(p + (size_t)eager * 32, h->d_centers, (size_t)eager * 8, hipMemcpyDeviceToHost, s));
     LF_HIP_CHECK(h, hipMemcpyAsync(p + (size_t)eager * 40, h->dbg_masks.p, 3 * h->P, hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(h, hipMemcpyAsync(h->h_counts.data(), h->d_counts, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(h, hipMemcpyAsync(h->h_seg_offset.data(), h->d_seg_offset, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
     return LF_OK;
 }
 
@@ -548,32 +570,20 @@ extern "C" int lf_set_image(lf_handle* h, const uint8_t* bgr, int rows, int cols
     if (rows != h->Hc || cols != h->W) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_image: image is %dx%d, handle expects %dx%d", rows, cols, h->Hc, h->W); return LF_ERR_BAD_ARG; }
     if (row_stride_bytes < cols * 3) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_image: row stride %d < %d", row_stride_bytes, cols * 3); return LF_ERR_BAD_ARG; }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
     h->plugin_ready = false;
     int rc = plugin_stage_image(h, bgr, rows, cols, row_stride_bytes);
     if (rc != LF_OK) return rc;
-    for (int attempt = 0;; ++attempt) {
-    rc = run_detect(h, h->d_frames, 1, true);
-    if (rc != LF_OK) return rc;
     lf_segments dev = h->d_out;
     dev.desc = nullptr; dev.code = nullptr;
-    rc = run_segments(h, 1, dev, false);
+    // (a handle made for batches holds short per-problem lists: detected again when this image needs more.  LineDetector2Dense
+    // returns the undilated mask, line_detector2.py:104-107)
+    rc = detect_until_fit(h, h->d_frames, 1, true, dev, false, false, [h]() -> int {
+        const int e = plugin_finish(h, h->detector == LF_DETECTOR_DENSE ? h->d_bwbits.p : h->d_maskbits.p);
+        if (e != LF_OK) return e;
+        LF_HIP_CHECK(h, hipMemcpyAsync(&h->h_status.p->rec_need, &h->lsd.d_status->rec_need, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        return LF_OK;            // (counts, segments and masks are on the host after the pass's one synchronisation)
+    });
     if (rc != LF_OK) return rc;
-    // Detections.area = the dilated colour mask as 0/255 bytes (line_detector_lsd.py:127-133): expanded once for the
-    // three colours from the bit planes.  LineDetector2Dense returns the undilated mask (line_detector2.py:104-107).
-    if ((rc = scratch(h, h->dbg_masks, 3 * h->P)) != LF_OK) return rc;
-    launch_edges_u8(h->canny, 3, h->detector == LF_DETECTOR_DENSE ? h->d_bwbits.p : h->d_maskbits.p, (uint8_t*)h->dbg_masks.p, s);
-    h->h_counts.resize(3); h->h_seg_offset.resize(4);
-    if ((rc = plugin_fetch_results(h)) != LF_OK) return rc;
-    LF_HIP_CHECK(h, hipMemcpyAsync(h->h_counts.data(), h->d_counts, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipMemcpyAsync(h->h_seg_offset.data(), h->d_seg_offset, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipMemcpyAsync(&h->h_pinned[6], h->lsd.d_overflow + 5, sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipStreamSynchronize(s));          // the ONE synchronisation of an image: counts, segments and masks are on the host
-    // (a handle made for batches holds short per-problem lists: grow them and detect again when this image needs more)
-    if (h->h_pinned[6] <= h->lsd.params.rec_cap) break;
-    if (attempt == 4) { lf_set_error(h, LF_ERR_CAPACITY, "the LSD lists keep overflowing (%d entries needed)", h->h_pinned[6]); return LF_ERR_CAPACITY; }
-    if ((rc = h->lsd.grow_lists(h, h->h_pinned[6])) != LF_OK) return rc;
-    }
     h->plugin_ready = true;
     return LF_OK;
 }

@@ -14,7 +14,7 @@ extern "C" int lf_set_dense_params(lf_handle* h, const lf_dense_params* p)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
     if (!p) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_dense_params: null params"); return LF_ERR_BAD_ARG; }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (const int rc = refuse_in_flight(h)) return rc;
     if (!(p->sobel_threshold >= 0)) {
         lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_dense_params: sobel_threshold %g must be a number >= 0", p->sobel_threshold);
         return LF_ERR_BAD_ARG;

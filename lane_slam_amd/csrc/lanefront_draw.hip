@@ -87,7 +87,7 @@ extern "C" int lf_draw_lines(lf_handle* h, int n_frames, const lf_segments* seg,
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
     if (!seg || !out_bgr) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_draw_lines: null argument"); return LF_ERR_BAD_ARG; }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (const int rc = refuse_in_flight(h)) return rc;
     if (h->draw_frames < 1) {
         lf_set_error(h, LF_ERR_BAD_ARG, "lf_draw_lines: the handle holds no completed batch (lf_process_batch / lf_wait)");
         return LF_ERR_BAD_ARG;
@@ -112,7 +112,7 @@ extern "C" int lf_draw_lines_image(lf_handle* h, const uint8_t* bgr, int n_frame
         lf_set_error(h, LF_ERR_BAD_ARG, "lf_draw_lines_image: null argument or n_frames < 1");
         return LF_ERR_BAD_ARG;
     }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (const int rc = refuse_in_flight(h)) return rc;
     if (!draw_size_ok(rows, cols)) {
         lf_set_error(h, LF_ERR_BAD_ARG, "lf_draw_lines_image: images of %d x %d (1 .. %d px a side)", rows, cols, draw::kLimit);
         return LF_ERR_BAD_ARG;

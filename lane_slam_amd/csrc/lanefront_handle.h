@@ -72,13 +72,15 @@ struct KlArrays {
     static int copy_back(lf_handle* h, const lf_keylines& dev, const lf_keylines& out, int n, int n_frames);
 };
 
-// One batch of a KeyLine detector: KeyLines per frame, their offsets, the totals (KeyLines, overflow) and the frame of every KeyLine
+// One batch of a KeyLine detector: KeyLines per frame, their offsets, the totals (KlTotals) and the frame of every KeyLine
 // on the device, the totals read back, and the staging of a host caller's images, masks and KeyLines.
 struct KlBatch {
-    DevBuf frame_count, frame_offset, totals, line_frame;
+    DevBuf frame_count, frame_offset, line_frame;
+    DevArray<KlTotals> totals;
     DevBuf gray, masks;             // a host caller's gray images / masks, max_frames working-size planes
     KlArrays staged;                // a host caller's KeyLines
-    HostArray<int> h_pinned;        // totals [2], then (EDLines) the frame status [max_frames]
+    HostArray<KlTotals> h_pinned;   // the totals, then (EDLines) the frame status [max_frames]
+    int32_t* h_frame_status() const { return reinterpret_cast<int32_t*>(h_pinned.p + 1); }
     int alloc(lf_handle* h);        // all but line_frame (KlBatch::keylines) and the staging
     // the batch's images on the device: the caller's, or a copy of a host caller's -- raw frames (input_kind 0) into h->d_frames,
     // for the caller's k_pre; gray images (1) into `gray`
@@ -141,9 +143,10 @@ struct LsdState {
     DevArray<int> d_row_start, d_norder, d_comp_count, d_comp_key, d_perm;
     DevArray<float> d_tmp_lines;                      // lines in completion order + their seed positions (k_lsd_grow)
     DevArray<int> d_tmp_tags;
-    DevArray<uint8_t> d_zero; size_t zero_bytes = 0;  // d_maxgrad | d_nrec | d_nlow | d_tile_count | d_overflow: the counters a batch starts from zero, ONE memset (each memset is a dispatch of its own and waited 0.3 ms in a busy pipeline)
+    DevArray<uint8_t> d_zero; size_t zero_bytes = 0;  // d_maxgrad | d_nrec | d_nlow | d_tile_count | d_status: the counters a batch starts from zero, ONE memset (each memset is a dispatch of its own and waited 0.3 ms in a busy pipeline)
     unsigned long long* d_maxgrad = nullptr;
-    int *d_nrec = nullptr, *d_nlow = nullptr, *d_tile_count = nullptr, *d_overflow = nullptr;      // (d_nlow: seed order OPENCV32 only)
+    int *d_nrec = nullptr, *d_nlow = nullptr, *d_tile_count = nullptr;      // (d_nlow: seed order OPENCV32 only)
+    BatchStatus* d_status = nullptr;                  // what a batch reports to the host
     int lists_grown = 0;         // times the per-problem lists were reallocated
     bool lists_lost = false;     // grow_lists ran out of memory twice: no per-problem lists, detection refuses
     bool grow_mixed = false;     // the last batch had problems beyond the slice in numbers (> 1 %): one launch with both kinds of problem code
@@ -180,6 +183,13 @@ struct LsdKlState {
     KlBatch batch;                        // its own: lf_keylines_frame_status reads the EDLines batch's h_pinned
 };
 
+// The batch in flight: lf_process_batch_async's (lf_wait runs it again when the LSD lists were too short) or lf_keylines_batch_async's
+struct InFlight {
+    enum Kind { NONE, SEGMENTS, KEYLINES } kind = NONE;
+    const uint8_t* in = nullptr; int n = 0; lf_segments out{}; bool describe = false;
+    int problems = 0, capacity = 0;
+};
+
 struct MatcherState {
     DevBuf codes;                  // the set: [total][32]
     std::vector<std::pair<int, int> > index_map;   // indexesMap: (first row, image number), keys ascending
@@ -210,7 +220,7 @@ struct lf_handle : lf::Core {
     lf::DevBuf dbg_bgr;
     lf::DevArray<uint32_t> d_strong, d_weak, d_maskbits;
     lf::DevArray<int> d_sdiv, d_hdiv;
-    bool overflow_zeroed = false;         // the batch's one memset of lsd.d_zero covered the overflow words (run_segments)
+    bool overflow_zeroed = false;         // the batch's one memset of lsd.d_zero covered the words k_seg_offsets adds to (run_segments)
     lf::DevBuf dbg_ang, dbg_mod;
     lf::DevArray<int> d_counts, d_seg_offset, d_frame_offset;
     lf::DevArray<float> d_slot_lines;
@@ -236,17 +246,14 @@ struct lf_handle : lf::Core {
     lf::DevBuf kn_hist, kn_count, kn_off, kn_total;       // radiusMatch scratch
     lf::AssocScratch a_ws;
     std::unique_ptr<lf::MatcherState> matcher;    // BinaryDescriptorMatcher's dataset (lanefront_matcher.hip)
-    // pinned host scalars
-    lf::HostArray<int> h_pinned;     // [0] total segments, [1] overflow ... [6] entries the per-problem lists would have needed (d_overflow[5])
-    const uint8_t* pend_in = nullptr; int pend_n = 0; lf_segments pend_out; bool pend_describe = false;   // the batch in flight (lf_wait runs it again when the LSD lists were too short)
+    lf::HostArray<lf::BatchStatus> h_status;      // pinned: lsd.d_status as the last batch left it
+    lf::InFlight flight;
     int last_frames = 0;
     bool plugin_ready = false;
-    bool pending = false;
     // plugin path: what lf_detect_lines hands out is fetched ONCE per image, behind the kernels of lf_set_image, into pinned host
     // memory (the first kPlugEager segments of the SegmentList + the three mask images): lf_detect_lines is then a host copy
     lf::HostArray<uint8_t> plug_host, plug_in;
     int plug_eager = 0;
-    bool pending_keylines = false;        // the batch in flight is lf_keylines_batch_async's: lf_wait reads the KeyLine state
     int detector = LF_DETECTOR_LSD;       // what lf_process_batch runs for a-2 .. a-4 (lf_set_detector)
     lf_edlines_params ed_params;
     int detector_failures = 0;            // frames of the last completed batch on which the EDLines detector gave up
@@ -262,8 +269,6 @@ struct lf_handle : lf::Core {
     lf::SegMode slot_mode = lf::SEG_FLOAT;      // what the slots of the last detect hold: which a-5 k_segments applies
     int tie_rule = LF_TIE_MIHASHER;   // lf_associate: the reference's rule unless lf_set_tie_rule says otherwise
     int env_kl_lds_lines = 0;    // LF_KL_LDS_LINES (test hook of the KeyLine grouping, lanefront_keylines.hip)
-    int pending_problems = 0;
-    int pending_capacity = 0;
     std::vector<int> h_counts, h_seg_offset;
     std::unique_ptr<lf::JpegState> jpeg;
     std::unique_ptr<lf::JencState> jenc;  // lf_jpeg_encode_batch (lanefront_jenc.hip), allocated on first use
@@ -307,14 +312,19 @@ inline void seg_camera(lf_handle* h)
 // lanefront_api.hip
 int run_detect(lf_handle* h, const uint8_t* d_frames, int n, bool from_working_image);
 int run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe);
+inline int refuse_in_flight(lf_handle* h)      // what an entry point that must not run beside a queued batch starts with
+{
+    if (h->flight.kind != InFlight::NONE) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    return LF_OK;
+}
 int plugin_stage_image(lf_handle* h, const uint8_t* bgr, int rows, int cols, int row_stride_bytes);
-int plugin_fetch_results(lf_handle* h);
+PreParams plugin_working_pre(const lf_handle* h);   // k_pre's parameters for an image the caller has resized, cropped and colour-corrected
+int plugin_finish(lf_handle* h, const uint32_t* mask_bits);
 // lanefront_hough.hip
 int hough_prepare(lf_handle* h);
 // lanefront_dense.hip
 int dense_prepare(lf_handle* h);
 // lanefront_keylines.hip
 int run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n);
-void keylines_pending_result(lf_handle* h, int* total, int* overflow);
 
 }  // namespace lf

@@ -26,7 +26,7 @@ extern "C" int lf_set_hough_params(lf_handle* h, const lf_hough_params* p)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
     if (!p) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_hough_params: null params"); return LF_ERR_BAD_ARG; }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (const int rc = refuse_in_flight(h)) return rc;
     if (!hough_params_ok(*p)) {
         lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_hough_params: threshold %d must be >= 1, min_line_length %d and max_line_gap %d >= 0",
                      p->threshold, p->min_line_length, p->max_line_gap);

@@ -169,8 +169,8 @@ int KlBatch::alloc(lf_handle* h)
 {
     const size_t B = (size_t)h->max_frames;
     int rc;
-    if ((rc = scratch(h, frame_count, B * 4)) || (rc = scratch(h, frame_offset, (B + 1) * 4)) || (rc = scratch(h, totals, 16))) return rc;
-    if (!h_pinned) LF_HIP_CHECK(h, h_pinned.alloc((2 + B) * sizeof(int)));
+    if ((rc = scratch(h, frame_count, B * 4)) || (rc = scratch(h, frame_offset, (B + 1) * 4)) || (rc = scratch(h, totals, sizeof(KlTotals)))) return rc;
+    if (!h_pinned) LF_HIP_CHECK(h, h_pinned.alloc(sizeof(KlTotals) + B * sizeof(int32_t)));
     return LF_OK;
 }
 
@@ -218,7 +218,7 @@ int lf::kl_batch_check(lf_handle* h, const char* who, const uint8_t* images, con
         return LF_ERR_BAD_ARG;
     }
     if (n_frames > h->max_frames) { lf_set_error(h, LF_ERR_CAPACITY, "n_frames %d exceeds max_frames %d", n_frames, h->max_frames); return LF_ERR_CAPACITY; }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (const int rc = refuse_in_flight(h)) return rc;
     return LF_OK;
 }
 
@@ -305,12 +305,6 @@ static int keylines_batch_impl(lf_handle* h, const uint8_t* images, int n_frames
                                const lf_edlines_params* params_or_null, lf_keylines* out, int out_on_device, int describe,
                                int* n_keylines, int32_t* frame_status, bool async_only, const uint8_t* masks = nullptr, int masks_on_device = 0);
 
-void lf::keylines_pending_result(lf_handle* h, int* total, int* overflow)
-{
-    *total = h->kl ? h->kl->batch.h_pinned[0] : 0;
-    *overflow = h->kl ? h->kl->batch.h_pinned[1] : 0;
-}
-
 extern "C" int lf_keylines_batch(lf_handle* h, const uint8_t* images, int n_frames, int input_kind, int images_on_device, int n_octaves,
                                  const lf_edlines_params* params_or_null, lf_keylines* out, int out_on_device, int describe,
                                  int* n_keylines, int32_t* frame_status)
@@ -343,8 +337,8 @@ extern "C" int lf_keylines_frame_status(lf_handle* h, int32_t* frame_status, int
     if (!h) return LF_ERR_NOT_INITIALISED;
     KlState* k = h->kl.get();
     if (!k || !frame_status || n_frames < 0 || n_frames > k->last_frames) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_keylines_frame_status: no such batch"); return LF_ERR_BAD_ARG; }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
-    for (int f = 0; f < n_frames; ++f) frame_status[f] = k->batch.h_pinned[2 + f];
+    if (const int rc = refuse_in_flight(h)) return rc;
+    memcpy(frame_status, k->batch.h_frame_status(), (size_t)n_frames * sizeof(int32_t));
     return LF_OK;
 }
 
@@ -387,7 +381,7 @@ static int keylines_batch_impl(lf_handle* h, const uint8_t* images, int n_frames
     {
         StageClock::Scope t(h, h->clock, ST_SEGMENTS);
         launch_kl_count(all, n_octaves, n_frames, static_cast<int*>(b.frame_count.p), static_cast<int*>(k->status.p), s);
-        launch_kl_offsets(n_frames, static_cast<const int*>(b.frame_count.p), cap_out, dev.frame_offset, static_cast<int*>(b.totals.p), s);
+        launch_kl_offsets(n_frames, static_cast<const int*>(b.frame_count.p), cap_out, dev.frame_offset, b.totals, s);
         const KlOut ko_final = kl_out(dev, static_cast<int32_t*>(b.line_frame.p));
         KlOut ko = ko_final;
         int* d_fo = dev.frame_offset;
@@ -397,7 +391,7 @@ static int keylines_batch_impl(lf_handle* h, const uint8_t* images, int n_frames
                 (rc = scratch(h, k->m_erased, (size_t)cap_out)) || (rc = scratch(h, k->m_kept, (size_t)h->max_frames * 4)) || (rc = k->unmasked.all(h, cap_out, &ko)))
                 return rc;
             d_fo = static_cast<int*>(k->m_fo.p);
-            launch_kl_offsets(n_frames, static_cast<const int*>(b.frame_count.p), cap_out, d_fo, static_cast<int*>(k->m_totals.p), s);
+            launch_kl_offsets(n_frames, static_cast<const int*>(b.frame_count.p), cap_out, d_fo, static_cast<KlTotals*>(k->m_totals.p), s);
         }
         int big_stride = 0;
         for (int o = 0; o < n_octaves; ++o) big_stride += k->oct[o].max_lines;
@@ -409,7 +403,7 @@ static int keylines_batch_impl(lf_handle* h, const uint8_t* images, int n_frames
         if (masks) {
             const uint8_t* dmask = masks;
             if (!masks_on_device && (rc = b.upload(h, b.masks, masks, n_frames, &dmask)) != LF_OK) return rc;
-            launch_kl_mask(n_frames, d_fo, dev.frame_offset, static_cast<int*>(b.totals.p), cap_out, dmask, h->Hc, h->W, static_cast<uint8_t*>(k->m_erased.p),
+            launch_kl_mask(n_frames, d_fo, dev.frame_offset, b.totals, cap_out, dmask, h->Hc, h->W, static_cast<uint8_t*>(k->m_erased.p),
                            static_cast<int*>(k->m_kept.p), ko, ko_final, s);
         }
     }
@@ -420,29 +414,26 @@ static int keylines_batch_impl(lf_handle* h, const uint8_t* images, int n_frames
             pl.base[o] = o < n_octaves ? static_cast<const uint32_t*>(k->oct[o].dxy.p) : nullptr;
             pl.W[o] = o < n_octaves ? k->oct[o].W : 0; pl.H[o] = o < n_octaves ? k->oct[o].H : 0;
         }
-        launch_lbd_keylines(pl, cap_out, n_frames, static_cast<const int*>(b.totals.p) + 2, dev.in_octave, dev.angle, dev.num_pixels, dev.octave,
+        launch_lbd_keylines(pl, cap_out, n_frames, &b.totals.p->describe_n, dev.in_octave, dev.angle, dev.num_pixels, dev.octave,
                             static_cast<const int*>(b.line_frame.p), h->d_gauss_g, h->d_gauss_l, dev.desc, dev.code, s, h->desc_params.width_of_band);
     }
     LF_HIP_CHECK(h, hipGetLastError());
-    int unmasked[2] = { 0, 0 };
-    if (masks) LF_HIP_CHECK(h, hipMemcpyAsync(unmasked, k->m_totals.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipMemcpyAsync(b.h_pinned, b.totals.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipMemcpyAsync(b.h_pinned + 2, k->status.p, (size_t)n_frames * sizeof(int), hipMemcpyDeviceToHost, s));
+    KlTotals unmasked{};
+    if (masks) LF_HIP_CHECK(h, hipMemcpyAsync(&unmasked, k->m_totals.p, sizeof(KlTotals), hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(h, hipMemcpyAsync(b.h_pinned, b.totals, sizeof(KlTotals), hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(h, hipMemcpyAsync(b.h_frame_status(), k->status.p, (size_t)n_frames * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     k->last_octaves = n_octaves; k->last_frames = n_frames;
     if (async_only) {
         // lf_keylines_batch_async: everything is queued; lf_wait picks up the total, the overflow flag and the frame status
-        h->pending = true;
-        h->pending_keylines = true;
-        h->pending_problems = 0;
-        h->pending_capacity = cap_out;
+        h->flight = InFlight{ InFlight::KEYLINES, images, n_frames, {}, describe != 0, 0, cap_out };
         return LF_OK;
     }
     LF_HIP_CHECK(h, hipStreamSynchronize(s));
-    const int total = b.h_pinned[0];
+    const int total = b.h_pinned.p->total;
     if (n_keylines) *n_keylines = total;
-    if (frame_status) for (int f = 0; f < n_frames; ++f) frame_status[f] = b.h_pinned[2 + f];
-    if (masks && unmasked[1]) { lf_set_error(h, LF_ERR_CAPACITY, "%d KeyLines (before the mask) exceed the output capacity %d", unmasked[0], cap_out); return LF_ERR_CAPACITY; }
-    if (b.h_pinned[1]) { lf_set_error(h, LF_ERR_CAPACITY, "%d KeyLines exceed the output capacity %d", total, cap_out); return LF_ERR_CAPACITY; }
+    if (frame_status) memcpy(frame_status, b.h_frame_status(), (size_t)n_frames * sizeof(int32_t));
+    if (masks && unmasked.overflow) { lf_set_error(h, LF_ERR_CAPACITY, "%d KeyLines (before the mask) exceed the output capacity %d", unmasked.total, cap_out); return LF_ERR_CAPACITY; }
+    if (b.h_pinned.p->overflow) { lf_set_error(h, LF_ERR_CAPACITY, "%d KeyLines exceed the output capacity %d", total, cap_out); return LF_ERR_CAPACITY; }
     return out_on_device ? LF_OK : KlArrays::copy_back(h, dev, *out, total, n_frames);
 }
 
@@ -457,7 +448,7 @@ extern "C" int lf_describe_keylines(lf_handle* h, const uint8_t* gray, int n_fra
     }
     if (n_frames > h->max_frames) { lf_set_error(h, LF_ERR_CAPACITY, "n_frames %d exceeds max_frames %d", n_frames, h->max_frames); return LF_ERR_CAPACITY; }
     // the octave buffers re-ensured below are the ones a queued lf_keylines_batch_async reads
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (const int rc = refuse_in_flight(h)) return rc;
     if (n == 0) return LF_OK;
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
@@ -586,10 +577,11 @@ int lf::run_detect_edlines(lf_handle* h, const uint8_t* d_frames, int n)
     if ((rc = kl_run_octaves(h, h->d_gray, n, 1, P, all)) != LF_OK) return rc;
     LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_norder, 0, (size_t)n * 3 * sizeof(int), s));        // (LSD's slice statistics: nothing to learn from this batch)
     h->slot_mode = SEG_FLOAT;
-    LF_HIP_CHECK(h, hipMemsetAsync(h->lsd.d_overflow + 4, 0, sizeof(int), s));
+    int32_t* failures = &h->lsd.d_status->detector_failures;
+    LF_HIP_CHECK(h, hipMemsetAsync(failures, 0, sizeof(*failures), s));
     {
         StageClock::Scope t(h, h->clock, ST_SEGMENTS);
-        launch_ed_slots(all, n, h->d_maskbits, h->Ww, h->cap_lines, h->d_slot_lines, h->d_counts, h->lsd.d_overflow + 4, s);
+        launch_ed_slots(all, n, h->d_maskbits, h->Ww, h->cap_lines, h->d_slot_lines, h->d_counts, failures, s);
     }
     h->kl->last_octaves = 1; h->kl->last_frames = n;
     h->last_frames = n;
@@ -600,7 +592,7 @@ extern "C" int lf_set_detector(lf_handle* h, int detector, const lf_edlines_para
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
     if (detector != LF_DETECTOR_LSD && detector != LF_DETECTOR_EDLINES && detector != LF_DETECTOR_HOUGH && detector != LF_DETECTOR_DENSE) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_detector: unknown detector %d", detector); return LF_ERR_BAD_ARG; }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (const int rc = refuse_in_flight(h)) return rc;
     lf_edlines_params P;
     lf_edlines_default_params(&P);
     if (params_or_null) P = *params_or_null;
@@ -654,12 +646,8 @@ extern "C" int lf_set_image_edlines(lf_handle* h, const uint8_t* bgr, int rows, 
     if ((rc = plugin_stage_image(h, bgr, rows, cols, row_stride_bytes)) != LF_OK) return rc;
     if ((rc = kl_prepare(h, 1, P.scan_intervals)) != LF_OK) return rc;
     KlState* k = h->kl.get();
-    PreParams pp = h->pre;         // the caller already resized, cropped and colour-corrected (line_detector_node.py:163-180)
-    pp.in_rows = h->Hc; pp.in_cols = h->W; pp.img_rows = h->Hc; pp.img_cols = h->W; pp.top_cutoff = 0; pp.resize = 0;
-    for (int i = 0; i < 3; ++i) { pp.ai_scale[i] = 1.f; pp.ai_shift[i] = 0.f; }
-    pp.identity_ai = 1;
     h->draw_frames = 0;                  // d_bgr is rewritten (lf_draw_lines)
-    { StageClock::Scope t(h, h->clock, ST_PRE); launch_pre(pp, h->d_frames, 1, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s); }
+    { StageClock::Scope t(h, h->clock, ST_PRE); launch_pre(plugin_working_pre(h), h->d_frames, 1, h->d_bgr, h->d_gray, h->d_maskbits, h->d_sdiv, h->d_hdiv, s); }
     EdAll all;
     if ((rc = kl_run_octaves(h, h->d_gray, 1, 1, P, all)) != LF_OK) return rc;
     launch_ed_slots(all, 1, h->d_maskbits, h->Ww, h->cap_lines, h->d_slot_lines, h->d_counts, nullptr, s);
@@ -668,13 +656,8 @@ extern "C" int lf_set_image_edlines(lf_handle* h, const uint8_t* bgr, int rows, 
     lf_segments dev = h->d_out;
     dev.desc = nullptr; dev.code = nullptr;
     if ((rc = run_segments(h, 1, dev, false)) != LF_OK) return rc;
-    if ((rc = scratch(h, h->dbg_masks, 3 * h->P)) != LF_OK) return rc;
-    launch_edges_u8(h->canny, 3, h->d_maskbits, (uint8_t*)h->dbg_masks.p, s);
-    h->h_counts.resize(3); h->h_seg_offset.resize(4);
-    if ((rc = plugin_fetch_results(h)) != LF_OK) return rc;
+    if ((rc = plugin_finish(h, h->d_maskbits)) != LF_OK) return rc;
     int st[4] = { 0, 0, 0, 0 };
-    LF_HIP_CHECK(h, hipMemcpyAsync(h->h_counts.data(), h->d_counts, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-    LF_HIP_CHECK(h, hipMemcpyAsync(h->h_seg_offset.data(), h->d_seg_offset, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
     LF_HIP_CHECK(h, hipMemcpyAsync(st, k->oct[0].counts.p, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
     LF_HIP_CHECK(h, hipStreamSynchronize(s));
     k->last_octaves = 1; k->last_frames = 1;

@@ -8,6 +8,12 @@
 
 namespace lf {
 
+// LsdState::d_zero for nprob problems, d_maxgrad | d_nrec | d_nlow | d_tile_count [4] | status: the byte offsets of its parts
+struct CounterBlock {
+    size_t nrec, nlow, tile_count, status, bytes;
+    explicit CounterBlock(size_t nprob) : nrec(nprob * 8), nlow(nrec + nprob * 4), tile_count(nlow + nprob * 4), status(tile_count + 16), bytes(status + sizeof(BatchStatus)) {}
+};
+
 int LsdState::init(lf_handle* h, int Hc, int W, const lf_lsd_options& o, int seed_order_, int max_frames_, int cap_lines)
 {
     seed_order = seed_order_;
@@ -138,14 +144,14 @@ int LsdState::init(lf_handle* h, int Hc, int W, const lf_lsd_options& o, int see
         dalloc(h, &d_tmp_lines, cap * 4) || dalloc(h, &d_tmp_tags, cap) || dalloc(h, &d_norder, nprob))
         return LF_ERR_HIP;
     // ---- the counter block, zeroed once here
-    zero_bytes = nprob * 8 + nprob * 4 + nprob * 4 + 16 + 32;
+    const CounterBlock cb(nprob);
+    zero_bytes = cb.bytes;
     if (dalloc(h, &d_zero, zero_bytes)) return LF_ERR_HIP;
     d_maxgrad = reinterpret_cast<unsigned long long*>(d_zero.p);
-    d_nrec = reinterpret_cast<int*>(d_zero + nprob * 8);
-    int* nlow = d_nrec + nprob;
-    if (seed_order == LF_LSD_SEED_OPENCV32) d_nlow = nlow;
-    d_tile_count = nlow + nprob;
-    d_overflow = d_tile_count + 4;
+    d_nrec = reinterpret_cast<int*>(d_zero + cb.nrec);
+    if (seed_order == LF_LSD_SEED_OPENCV32) d_nlow = reinterpret_cast<int*>(d_zero + cb.nlow);
+    d_tile_count = reinterpret_cast<int*>(d_zero + cb.tile_count);
+    d_status = reinterpret_cast<BatchStatus*>(d_zero + cb.status);
     LF_HIP_CHECK(h, hipMemset(d_zero, 0, zero_bytes));
     // ---- test and tuning overrides of k_lsd_grow, clamped
     if (const char* ev = getenv("LF_GROW_LDS_LEVEL")) { const int v = atoi(ev); env_lds_level = v < 0 ? 0 : (v > 2 ? 2 : v); }
@@ -187,7 +193,7 @@ int LsdState::alloc_lists(lf_handle* h, int rec_cap)
     return LF_OK;
 }
 
-// The per-problem lists of the LSD stages hold LsdParams::rec_cap entries.  When a batch had a problem with more (d_overflow[5], read
+// The per-problem lists of the LSD stages hold LsdParams::rec_cap entries.  When a batch had a problem with more (BatchStatus::rec_need, read
 // by the caller: the largest need), that problem was dropped on the device; here the lists are reallocated with room to spare and the
 // caller runs the batch again.  The stream must be idle.  Results never depend on the capacity -- only whether a batch runs twice.
 int LsdState::grow_lists(lf_handle* h, int need)
@@ -221,7 +227,7 @@ void LsdState::adapt_slice(int over_small, int over_medium, int problems)
 void LsdState::grad(int n, const uint32_t* edge_bits, const uint32_t* mask_bits, bool counters_zeroed, hipStream_t s)
 {
     launch_lsd_grad(params, rt, n, edge_bits, mask_bits, d_raddr, d_rdeg, d_rmod, d_rcs, d_rsn, d_nrec, d_maxgrad, max_nsx, max_nsy,
-                    d_tile_list, d_tile_count, d_laddr, d_lmod, d_nlow, d_overflow + 5, counters_zeroed, s);
+                    d_tile_list, d_tile_count, d_laddr, d_lmod, d_nlow, &d_status->rec_need, counters_zeroed, s);
 }
 
 void LsdState::grad_gray(int n, const uint8_t* gray, hipStream_t s)
@@ -236,7 +242,7 @@ void LsdState::order(int n, int big, hipStream_t s)
                      d_norder, d_cxy, d_cdeg, d_cmod, d_ccs, d_csn, d_row_start, s);
     // OpenCV >= 3.2: the seeds in the order std::sort leaves them in (the compact arrays and row starts stay as they are)
     if (seed_order == LF_LSD_SEED_OPENCV32)
-        launch_lsd_seed32(params, n, d_nrec, d_norder, d_overflow + 5, d_maxgrad, d_cxy, d_cmod, d_laddr, d_lmod, d_nlow, d_sort_a, d_sort_b,
+        launch_lsd_seed32(params, n, d_nrec, d_norder, &d_status->rec_need, d_maxgrad, d_cxy, d_cmod, d_laddr, d_lmod, d_nlow, d_sort_a, d_sort_b,
                           d_order_a, d_order_b, big, s);
 }
 

@@ -240,10 +240,10 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
     lf_keylines dev;
     if ((rc = b.alloc(h)) != LF_OK || (rc = b.keylines(h, "lf_lsd_keylines_batch", *out, out_on_device, describe, &dev)) != LF_OK) return rc;
     hipLaunchKernelGGL(k_lsdkl_count, dim3(n_frames), dim3(64), 0, s, L, n_octaves, n_frames, static_cast<int*>(b.frame_count.p));
-    launch_kl_offsets(n_frames, static_cast<const int*>(b.frame_count.p), cap_out, dev.frame_offset, static_cast<int*>(b.totals.p), s);
+    launch_kl_offsets(n_frames, static_cast<const int*>(b.frame_count.p), cap_out, dev.frame_offset, b.totals, s);
     hipLaunchKernelGGL(k_lsdkl_fill, dim3(n_frames), dim3(64), 0, s, L, n_octaves, dev.frame_offset, cap_out, kl_out(dev, static_cast<int32_t*>(b.line_frame.p)));
     LF_HIP_CHECK(h, hipGetLastError());
-    LF_HIP_CHECK(h, hipMemcpyAsync(b.h_pinned, b.totals.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    LF_HIP_CHECK(h, hipMemcpyAsync(b.h_pinned, b.totals, sizeof(KlTotals), hipMemcpyDeviceToHost, s));
     // a level whose LSD found more lines than max_lines_per_color: reported like the front end's own overflow
     int level_counts_bad = 0;
     LF_HIP_CHECK(h, hipStreamSynchronize(s));
@@ -252,10 +252,10 @@ extern "C" int lf_lsd_keylines_batch_ex(lf_handle* h, const uint8_t* images, int
         if ((rc = fetch(h, { { c.data(), k->level[o].counts.p, c.size() * sizeof(int) } })) != LF_OK) return rc;
         for (int f = 0; f < n_frames; ++f) if (c[3 * (size_t)f] > h->cap_lines) { level_counts_bad = c[3 * (size_t)f]; break; }
     }
-    const int total = b.h_pinned[0];
+    const int total = b.h_pinned.p->total;
     if (n_keylines) *n_keylines = total;
     if (level_counts_bad) { lf_set_error(h, LF_ERR_CAPACITY, "an LSD run on a pyramid level produced %d lines, max_lines_per_color is %d", level_counts_bad, h->cap_lines); return LF_ERR_CAPACITY; }
-    if (b.h_pinned[1]) { lf_set_error(h, LF_ERR_CAPACITY, "%d KeyLines exceed the output capacity %d", total, cap_out); return LF_ERR_CAPACITY; }
+    if (b.h_pinned.p->overflow) { lf_set_error(h, LF_ERR_CAPACITY, "%d KeyLines exceed the output capacity %d", total, cap_out); return LF_ERR_CAPACITY; }
     if (describe && total > 0 && (dev.desc || dev.code)) {
         // BinaryDescriptor::compute on these KeyLines: its own (blurred) pyramid over the same gray image
         if ((rc = lf_describe_keylines(h, gray0, n_frames, static_cast<const int32_t*>(b.line_frame.p), dev.in_octave, dev.angle, dev.num_pixels, dev.octave, total,

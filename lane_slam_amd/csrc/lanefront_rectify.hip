@@ -175,7 +175,7 @@ extern "C" int lf_set_camera(lf_handle* h, const double* K, const double* D, con
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
     if (!K || !D || !R || !P) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_set_camera: null argument"); return LF_ERR_BAD_ARG; }
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (const int rc = refuse_in_flight(h)) return rc;
     lf_config c = h->cfg;
     memcpy(c.K, K, sizeof(c.K)); memcpy(c.D, D, sizeof(c.D)); memcpy(c.R, R, sizeof(c.R)); memcpy(c.P, P, sizeof(c.P));
     c.cam_w = cam_w; c.cam_h = cam_h;
@@ -190,7 +190,7 @@ extern "C" int lf_set_camera(lf_handle* h, const double* K, const double* D, con
 extern "C" int lf_set_rectified_input(lf_handle* h, int flag)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;
-    if (h->pending) { lf_set_error(h, LF_ERR_BAD_ARG, "a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (const int rc = refuse_in_flight(h)) return rc;
     h->seg.rectified_input = flag ? 1 : 0;
     return LF_OK;
 }
