@@ -1313,6 +1313,15 @@ LF_API int lf_debug_probe(lf_handle* h, int width, int write, size_t bytes, int 
 /* LSD stages alone on a binary image of the handle's working size (non-zero = edge pixel, colour
  * mask forced to all ones); host pointers; lines before normal-based endpoint ordering */
 LF_API int lf_debug_lsd_binary(lf_handle* h, const uint8_t* img, int rows, int cols, float* lines4, int cap, int* n_out);
+/* the per-segment stage alone (normal and endpoint order, normalisation, ground projection, line sanity, compaction) on the
+ * caller's lines in place of a detector's; host pointers.  mode 0: float lines, the arithmetic behind LF_DETECTOR_LSD and
+ * LF_DETECTOR_EDLINES; mode 1: HoughLinesP's int lines held as floats, the arithmetic behind LF_DETECTOR_HOUGH.
+ * counts [n_frames * 3] (frame major, colour minor), lines4 [n_frames * 3][max_lines_per_color][4] in working-image pixels: a
+ * count above max_lines_per_color is the detector's overflow, LF_ERR_CAPACITY.  masks [n_frames * 3][Hc][W], non-zero = on, are
+ * the dilated colour masks the normals are signed by; NULL keeps what the handle holds.  out and n_segments as lf_process_batch
+ * with host outputs and no descriptors (a NULL array is not computed; out->desc and out->code are not read) */
+LF_API int lf_debug_segments(lf_handle* h, int mode, int n_frames, const int32_t* counts, const float* lines4, const uint8_t* masks,
+                             lf_segments* out, int* n_segments);
 /* the sort emulation behind lsd_seed_order = LF_LSD_SEED_OPENCV32 alone: order[i] = index of the element that
  * std::sort(begin, end, [](a, b) { return a.key > b.key; }) of libstdc++ leaves at place i, for n keys in [0, 1023] in their
  * initial order (host pointers; n < 2^20).  Elements with key 0 are the detector's flat pixels -- never seeds, anonymous on the

@@ -10,6 +10,7 @@
 //
 // Also compacts the fixed-capacity LSD slots [frame][colour][cap] into the frame-major,
 // colour-minor SegmentList order.  Byte traffic is negligible (~130 B per segment).
+#include <limits.h>
 #include "common.h"
 #include "lane_vote.h"
 
@@ -63,6 +64,18 @@ void launch_seg_offsets(int n_frames, int cap_lines, const int* counts, int* seg
 }
 
 __device__ __forceinline__ int check_bounds(int v, int bound) { return v < 0 ? 0 : (v >= bound ? bound - 1 : v); }
+
+// numpy's astype('int') under the reference's runtime (x86-64: a truncating conversion to int64): a NaN, an infinity or a value
+// past 2^63 becomes the most negative integer -- which check_bounds turns into 0, where the device's own conversion saturates an
+// infinity to the far bound (a line so short that its squared length underflows has an infinite normal) --, a finite value past
+// int32 keeps its sign.  Only check_bounds reads the result, so int32 saturation stands for the int64 in between.
+template <typename T>
+__device__ __forceinline__ int trunc_int(T v)
+{
+    const T a = v < 0 ? -v : v;
+    if (!(a < (T)9223372036854775808.)) return INT_MIN;
+    return v >= (T)2147483648. ? INT_MAX : (v <= (T)-2147483648. ? INT_MIN : (int)v);
+}
 
 __device__ void ground_point(const SegParams& p, double vx, double vy, double& gx, double& gy)
 {
@@ -139,8 +152,8 @@ __global__ void k_segments(SegParams p, int n_frames, const float* __restrict__ 
         const double dx = (double)(iy2 - iy1) / len;
         const double dy = (double)(ix1 - ix2) / len;
         const int cx = (ix1 + ix2) >> 1, cy = (iy1 + iy2) >> 1;          // (x1+x2)/2 on int arrays under Python 2: floor division
-        int x3 = (int)((double)cx - 3. * dx), y3 = (int)((double)cy - 3. * dy);
-        int x4 = (int)((double)cx + 3. * dx), y4 = (int)((double)cy + 3. * dy);
+        int x3 = trunc_int((double)cx - 3. * dx), y3 = trunc_int((double)cy - 3. * dy);
+        int x4 = trunc_int((double)cx + 3. * dx), y4 = trunc_int((double)cy + 3. * dy);
         x3 = check_bounds(x3, p.W); y3 = check_bounds(y3, p.Hc);
         x4 = check_bounds(x4, p.W); y4 = check_bounds(y4, p.Hc);
         const uint32_t* bw = maskbits + (size_t)pc * p.Hc * Ww;
@@ -163,8 +176,8 @@ __global__ void k_segments(SegParams p, int n_frames, const float* __restrict__ 
     const float dx = dm::fdiv(y2 - y1, len);
     const float dy = dm::fdiv(x1 - x2, len);
     const float cx = (x1 + x2) / 2, cy = (y1 + y2) / 2;
-    int x3 = (int)(cx - 3.f * dx), y3 = (int)(cy - 3.f * dy);
-    int x4 = (int)(cx + 3.f * dx), y4 = (int)(cy + 3.f * dy);
+    int x3 = trunc_int(cx - 3.f * dx), y3 = trunc_int(cy - 3.f * dy);
+    int x4 = trunc_int(cx + 3.f * dx), y4 = trunc_int(cy + 3.f * dy);
     x3 = check_bounds(x3, p.W); y3 = check_bounds(y3, p.Hc);
     x4 = check_bounds(x4, p.W); y4 = check_bounds(y4, p.Hc);
     // bw = the dilated colour mask, kept as a bit plane (k_pre)

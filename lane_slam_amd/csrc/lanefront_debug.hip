@@ -1,5 +1,5 @@
 // lanefront C ABI, the test and diagnosis entry points of a handle (k_debug.hip): the seed-order sort on caller keys, LSD alone on a
-// binary image and the read-back of a handle's intermediate buffers.
+// binary image, the per-segment stage alone on caller lines and the read-back of a handle's intermediate buffers.
 #include <string.h>
 #include <vector>
 #include "lanefront_handle.h"
@@ -74,6 +74,68 @@ extern "C" int lf_debug_lsd_binary(lf_handle* h, const uint8_t* img, int rows, i
     if (n > h->cap_lines) { lf_set_error(h, LF_ERR_CAPACITY, "LSD found %d lines, max_lines_per_color is %d", n, h->cap_lines); return LF_ERR_CAPACITY; }
     if (n > cap) { lf_set_error(h, LF_ERR_CAPACITY, "%d lines exceed caller capacity %d", n, cap); return LF_ERR_CAPACITY; }
     return fetch(h, { { lines4, h->d_slot_lines.p, (size_t)n * 4 * sizeof(float) } });
+}
+
+// The per-segment stage alone (k_segments.hip: a-5 .. a-8 and the compaction) on caller-supplied lines, counts and masks: the
+// slots are filled from the host and run_segments does what it does behind a detector.  Test entry; what it returns is what
+// lf_process_batch with host outputs returns for a detector that had found these lines.
+extern "C" int lf_debug_segments(lf_handle* h, int mode, int n_frames, const int32_t* counts, const float* lines4, const uint8_t* masks,
+                                 lf_segments* out, int* n_segments)
+{
+    if (!h) return LF_ERR_NOT_INITIALISED;
+    if (h->flight.kind != InFlight::NONE) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_debug_segments: a batch is in flight on this handle: call lf_wait first"); return LF_ERR_BAD_ARG; }
+    if (!counts || !lines4 || !out || n_frames < 1 || n_frames > h->max_frames || (mode != 0 && mode != 1)) {
+        lf_set_error(h, LF_ERR_BAD_ARG, "lf_debug_segments: bad argument (1 <= n_frames <= %d, mode 0 or 1, counts, lines4 and out not null)", h->max_frames);
+        return LF_ERR_BAD_ARG;
+    }
+    const size_t nprob = (size_t)n_frames * 3;
+    for (size_t i = 0; i < nprob; ++i)
+        if (counts[i] < 0) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_debug_segments: counts[%zu] = %d is negative", i, counts[i]); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    LF_HIP_CHECK(h, hipMemcpyAsync(h->d_counts, counts, nprob * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    LF_HIP_CHECK(h, hipMemcpyAsync(h->d_slot_lines, lines4, nprob * h->cap_lines * 4 * sizeof(float), hipMemcpyHostToDevice, s));
+    std::vector<uint32_t> bits;
+    if (masks) {
+        const size_t nw = (size_t)h->Hc * h->Ww;
+        bits.assign(nprob * nw, 0u);
+        for (size_t pc = 0; pc < nprob; ++pc)
+            for (int y = 0; y < h->Hc; ++y)
+                for (int x = 0; x < h->W; ++x)
+                    if (masks[(pc * h->Hc + y) * h->W + x]) bits[pc * nw + (size_t)y * h->Ww + (x >> 5)] |= 1u << (x & 31);
+        LF_HIP_CHECK(h, hipMemcpyAsync(h->d_maskbits, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    lf_segments dev = h->d_out;
+    dev.capacity = out->capacity < h->out_capacity ? out->capacity : h->out_capacity;
+    if (dev.capacity < 0) dev.capacity = 0;
+    if (!out->lines) dev.lines = nullptr;
+    if (!out->normals) dev.normals = nullptr;
+    if (!out->color) dev.color = nullptr;
+    if (!out->pixels_normalized) dev.pixels_normalized = nullptr;
+    if (!out->ground) dev.ground = nullptr;
+    if (!out->keep) dev.keep = nullptr;
+    dev.desc = nullptr; dev.code = nullptr;
+    dev.frame_offset = h->d_frame_offset;
+    // which a-5 run_segments applies; every detector says again what its slots hold, so the next batch is not touched.  The status
+    // words are zeroed by run_segments (overflow_zeroed false); its LSD list statistics (over_small ..) are the last LSD batch's
+    // d_norder again and are not used here: the slice of k_lsd_grow does not adapt to a debug call
+    h->slot_mode = mode == 1 ? SEG_HOUGH : SEG_FLOAT;
+    h->overflow_zeroed = false;
+    h->plugin_ready = false;
+    h->last_frames = n_frames;
+    int rc = run_segments(h, n_frames, dev, false);
+    BatchStatus st{};
+    if (rc == LF_OK) rc = fetch(h, { { &st, h->lsd.d_status, sizeof(BatchStatus) } });      // (waits: `bits` may go)
+    if (rc != LF_OK) { (void)hipStreamSynchronize(s); return rc; }
+    const int total = st.total;
+    if (n_segments) *n_segments = total;
+    if (st.lines_overflow) { lf_set_error(h, LF_ERR_CAPACITY, "lf_debug_segments: a count exceeds max_lines_per_color=%d", h->cap_lines); return LF_ERR_CAPACITY; }
+    if (total > dev.capacity) { lf_set_error(h, LF_ERR_CAPACITY, "lf_debug_segments: %d segments exceed the output capacity %d", total, dev.capacity); return LF_ERR_CAPACITY; }
+    const size_t n = (size_t)total;
+    return fetch(h, { { out->frame_offset, h->d_frame_offset.p, ((size_t)n_frames + 1) * sizeof(int) }, { out->lines, dev.lines, n * 4 * sizeof(float) },
+                      { out->normals, dev.normals, n * 2 * sizeof(float) }, { out->color, dev.color, n },
+                      { out->pixels_normalized, dev.pixels_normalized, n * 4 * sizeof(float) }, { out->ground, dev.ground, n * 4 * sizeof(double) },
+                      { out->keep, dev.keep, n } });
 }
 
 extern "C" int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t bytes)

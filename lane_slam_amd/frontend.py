@@ -786,6 +786,46 @@ class FrontEnd(object):
         self._check(self.lib.lf_debug_lsd_binary(self.h, _ptr(img), img.shape[0], img.shape[1], _ptr(lines), cap, ctypes.byref(n)))
         return lines[:n.value].copy()
 
+    def debug_segments(self, counts, lines, masks=None, mode="float", out=None, capacity=None):
+        """The per-segment stage alone on the caller's lines (lf_debug_segments; tests / diagnosis).  counts: int32 (n, 3);
+        lines: float32 (n, 3, max_lines_per_color, 4) in working-image pixels; masks: uint8 (n, 3, rows, cols) or None (the
+        handle's own stay); mode "float" (the LSD / EDLines arithmetic) or "hough" (int lines).  out: a dict of the host arrays to
+        fill, any of frame_offset, lines, normals, color, pixels_normalized, ground, keep (a missing one is not computed);
+        by default all of them, for `capacity` segments (default: every slot).  Returns a host `Segments` whose arrays are
+        views of them.  A LanefrontError carries the total in its n_segments."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1, 3)
+        n = counts.shape[0]
+        lines = np.ascontiguousarray(lines, dtype=np.float32)
+        if lines.size != n * 3 * self.cap_lines * 4:
+            raise ValueError("lines must be (%d, 3, %d, 4), got %r" % (n, self.cap_lines, lines.shape))
+        if masks is not None:
+            masks = np.ascontiguousarray(masks, dtype=np.uint8)
+            if masks.shape != (n, 3, self.rows, self.cols):
+                raise ValueError("masks must be (%d, 3, %d, %d), got %r" % (n, self.rows, self.cols, masks.shape))
+        cap = n * 3 * self.cap_lines if capacity is None else int(capacity)
+        if out is None:
+            out = {"frame_offset": np.zeros(n + 1, np.int32), "lines": np.empty((cap, 4), np.float32), "normals": np.empty((cap, 2), np.float32),
+                   "color": np.empty(cap, np.uint8), "pixels_normalized": np.empty((cap, 4), np.float32),
+                   "ground": np.empty((cap, 4), np.float64), "keep": np.empty(cap, np.uint8)}
+        s = _lib.LfSegments()
+        s.capacity = cap
+        for k, v in out.items():
+            setattr(s, k, v.ctypes.data)
+        total = ctypes.c_int(-1)
+        rc = self.lib.lf_debug_segments(self.h, {"float": 0, "hough": 1}.get(mode, mode), n, _ptr(counts), _ptr(lines),
+                                        None if masks is None else _ptr(masks), ctypes.byref(s), ctypes.byref(total))
+        if rc != 0:
+            e = LanefrontError(rc, self.lib.lf_last_error(self.h).decode())
+            e.n_segments = total.value
+            raise e
+        seg = Segments()
+        seg.n = total.value
+        seg.frame_offset = out.get("frame_offset")
+        for k in ("lines", "normals", "color", "pixels_normalized", "ground", "keep"):
+            setattr(seg, k, out[k][:seg.n] if k in out else None)
+        seg.desc = seg.code = None
+        return seg
+
     def set_profiling(self, on):
         self._check(self.lib.lf_set_profiling(self.h, int(bool(on))))
 

@@ -12,9 +12,20 @@
  * numpy semantics: lines are float32, so length/dx/dy/centers and the sample
  * coordinates are float32; astype('int') truncates toward zero; normals become
  * float64 holding float32 values; the ordering test is evaluated in float64.
+ * astype('int') converts to int64 (x86-64, cvttss2si): a NaN, an infinity or a value
+ * past 2^63 becomes the most negative integer, which _checkBounds turns into 0; a
+ * finite value past int32 keeps its sign.  Only the bounds check reads the result, so
+ * int32 saturation stands for the int64 in between.
  * PINNED by tests/golden/find_normal.npz (the reference's own code run here).
  */
+#include <limits.h>
 static int check_bounds(int v, int bound) { if (v < 0) v = 0; if (v >= bound) v = bound - 1; return v; }
+static int trunc_int(float v)
+{
+    const float a = v < 0 ? -v : v;
+    if (!(a < 9223372036854775808.f)) return INT_MIN;
+    return v >= 2147483648.f ? INT_MAX : (v <= -2147483648.f ? INT_MIN : (int)v);
+}
 
 void lfo_find_normals(const uint8_t* bw, int rows, int cols, float* lines, int n,
                       double* normals, float* centers)
@@ -26,8 +37,8 @@ void lfo_find_normals(const uint8_t* bw, int rows, int cols, float* lines, int n
         float dx = (y2 - y1) / len;
         float dy = (x1 - x2) / len;
         float cx = (x1 + x2) / 2, cy = (y1 + y2) / 2;
-        int x3 = (int)(cx - 3.f * dx), y3 = (int)(cy - 3.f * dy);
-        int x4 = (int)(cx + 3.f * dx), y4 = (int)(cy + 3.f * dy);
+        int x3 = trunc_int(cx - 3.f * dx), y3 = trunc_int(cy - 3.f * dy);
+        int x4 = trunc_int(cx + 3.f * dx), y4 = trunc_int(cy + 3.f * dy);
         x3 = check_bounds(x3, cols); y3 = check_bounds(y3, rows);
         x4 = check_bounds(x4, cols); y4 = check_bounds(y4, rows);
         int sign = (bw[(size_t)y3 * cols + x3] > 0 && bw[(size_t)y4 * cols + x4] == 0) ? 1 : -1;
