@@ -5,6 +5,7 @@
 #include <vector>
 #include "lanefront_handle.h"
 #include "lsd_bitplane.h"
+#include "k_lsd_grad.h"
 
 namespace lf {
 
@@ -103,30 +104,15 @@ int LsdState::init(lf_handle* h, int Hc, int W, const lf_lsd_options& o, int see
         y0[dy] = sy < 0 ? 0 : (sy > Hc - 1 ? Hc - 1 : sy);
         y1[dy] = sy + 1 < 0 ? 0 : (sy + 1 > Hc - 1 ? Hc - 1 : sy + 1);
     }
-    // LDS footprint of the worst tile
-    const int GT = 32;
-    int mx = 0, my = 0;
-    for (int X0 = 0; X0 < Ws; X0 += GT) {
-        int X1 = X0 + GT < Ws - 1 ? X0 + GT : Ws - 1;
-        int lo = xofs[X0], hi = xofs[X1] + 1 < W - 1 ? xofs[X1] + 1 : W - 1;
-        if (hi - lo + 1 > mx) mx = hi - lo + 1;
-    }
-    for (int Y0 = 0; Y0 < Hs; Y0 += GT) {
-        int Y1 = Y0 + GT < Hs - 1 ? Y0 + GT : Hs - 1;
-        int lo = y0[Y0], hi = y1[Y1];
-        if (hi - lo + 1 > my) my = hi - lo + 1;
-    }
-    max_nsx = mx; max_nsy = my;
+    // the tiles of k_lsd_grad (k_lsd_grad.h): the worst one's raw footprint, its wave's LDS slice, what a list entry can name
+    lsd_grad_footprint(xofs.data(), y0.data(), y1.data(), W, Ws, Hs, &max_nsx, &max_nsy);
     {
-        const int hh = L.half;
-        // same carve as launch_lsd_grad: F|Hb|pixel list share one region, Bl|Sc the other
-        const size_t szF = (size_t)(my + 2 * hh) * mx, szBl = (size_t)my * mx;
-        const size_t szHb = (size_t)my * (GT + 1), szSc = (size_t)(GT + 1) * (GT + 1);
-        size_t regA = szF > szHb ? szF : szHb;
-        if (regA < (size_t)2 * GT * GT) regA = (size_t)2 * GT * GT;
-        const size_t regB = szBl > szSc ? szBl : szSc;
-        size_t lds = sizeof(double) * (regA + regB);
-        if (lds > 64 * 1024) { lf_set_error(h, LF_ERR_UNSUPPORTED, "lsd_scale %.3f needs %zu B of LDS per tile (max 65536)", L.scale, lds); return LF_ERR_UNSUPPORTED; }
+        const size_t lds = lsd_grad_carve(L.half, max_nsx, max_nsy).bytes + kLsdGradStaticLds;
+        if (lds > kLsdGradMaxLds) { lf_set_error(h, LF_ERR_UNSUPPORTED, "lsd_scale %.3f needs %zu B of LDS per tile (max %zu)", L.scale, lds, kLsdGradMaxLds); return LF_ERR_UNSUPPORTED; }
+        if (lsd_tiles_x(Ws) > kLsdMaxTilesPerSide || lsd_tiles_y(Hs) > kLsdMaxTilesPerSide || max_frames * 3 > kLsdMaxTileProblems || L.Ww > kLsdMaxWordCols) {
+            lf_set_error(h, LF_ERR_UNSUPPORTED, "LSD image %d x %d of %d frames: more tiles than a tile list entry names", Ws, Hs, max_frames);
+            return LF_ERR_UNSUPPORTED;
+        }
     }
     if (dalloc(h, &d_xofs, Ws) || dalloc(h, &d_y0, Hs) || dalloc(h, &d_y1, Hs) || dalloc(h, &d_xa, 2 * (size_t)Ws) || dalloc(h, &d_yb, 2 * (size_t)Hs))
         return LF_ERR_HIP;
@@ -138,7 +124,7 @@ int LsdState::init(lf_handle* h, int Hc, int W, const lf_lsd_options& o, int see
     rt.xofs = d_xofs; rt.xa = d_xa; rt.y0 = d_y0; rt.y1 = d_y1; rt.yb = d_yb; rt.xmax = xmax;
     // ---- the fixed per-problem arrays
     const size_t nprob = (size_t)max_frames * 3, cap = nprob * (size_t)cap_lines;
-    if (dalloc(h, &d_tile_list, nprob * (size_t)(((Ws + 31) / 32) * ((Hs + 31) / 32))) ||
+    if (dalloc(h, &d_tile_list, nprob * (size_t)(lsd_tiles_x(Ws) * lsd_tiles_y(Hs))) ||
         dalloc(h, &d_gused, nprob * ((Ps + 31) / 32)) || dalloc(h, &d_row_start, nprob * (size_t)(Hs + 1)) ||
         dalloc(h, &d_comp_list, nprob * (size_t)kCompCap) || dalloc(h, &d_comp_count, nprob) || dalloc(h, &d_perm, nprob) || dalloc(h, &d_comp_key, nprob) ||
         dalloc(h, &d_tmp_lines, cap * 4) || dalloc(h, &d_tmp_tags, cap) || dalloc(h, &d_norder, nprob))
