@@ -69,6 +69,35 @@ struct LsdParams {
     float* c_sd = nullptr;
 };
 
+// The per-problem arrays of the LSD stages as views: raw pointers that own nothing (the owner is LsdState, lanefront_handle.h),
+// grouped by the stage that writes them.  The fields carry the names the kernels' parameters have; arrays have rec_cap entries
+// per problem unless said.
+struct LsdRecords {                 // k_lsd_grad -> k_lsd_order, k_lsd_seed32
+    uint32_t* r_addr; float* r_deg; double* r_mod; double* r_cs; double* r_sn;
+    int* n_rec;                     // [problems]
+    unsigned long long* maxgrad;    // [problems]
+    uint32_t* l_addr; double* l_mod; int* n_low;     // the "low" records: pixels with a non-zero but undefined gradient (seed order OPENCV32; null otherwise)
+    uint32_t* list; int* list_count;                 // the tile list k_lsd_grad works through (k_lsd_grad.h)
+    int max_nsx, max_nsy;                            // ... and the worst tile's raw footprint
+};
+struct LsdCompact {                 // k_lsd_order / k_lsd_seed32 -> k_lsd_label, k_lsd_grow
+    unsigned long long* sort_a; unsigned long long* sort_b;      // sort scratch
+    uint32_t* order_a; uint32_t* order_b;                        // the seed list (order_a) and its scratch
+    int* norder;                    // [problems] defined pixels
+    uint32_t* c_xy; float* c_deg; double* c_mod;
+    double* c_cs; double* c_sn;     // (cos, sin) pairs in ONE array of 2 * rec_cap entries per problem: c_sn = c_cs + 1 (k_lsd_order.hip)
+    int* row_start;                 // [problems][Hs + 1]
+};
+struct LsdComponents {              // k_lsd_label -> k_lsd_grow
+    uint16_t* c_label;
+    uint16_t* comp_list; int* comp_count; int* comp_key;         // [problems][comp_cap], [problems], [problems]
+    int comp_cap;                   // the stride of comp_list -- not how many components k_lsd_label lists (LF_DIAG_COMP_CAP lowers that)
+    int* perm;                      // [problems] k_lsd_grow's launch order (k_lsd_rank), or null: the natural one
+    uint32_t* reg;                  // the region scratch, lsd_grow_reg_stride() per problem (k_lsd_label's tables until k_lsd_grow runs)
+    uint32_t* gused;                // [problems][Hs * Ws / 32] USED bits of the entries beyond k_lsd_grow's LDS
+    float* tmp_lines; int* tmp_tags;                             // [problems][cap_lines] lines in completion order and their seed positions
+};
+
 struct SegParams {
     int Hc, W, img_rows, img_cols, top_cutoff, cap_lines;
     double rx, ry, cut;
@@ -139,36 +168,23 @@ void launch_canny(const CannyParams& p, const uint32_t* bgr, int n_frames, uint3
 int launch_hysteresis(const CannyParams& p, int n_frames, uint32_t* strong, const uint32_t* weak, hipStream_t s);
 void launch_bgrx_to_bgr(int n_pix, const uint32_t* bgrx, uint8_t* bgr, hipStream_t s);
 void launch_edges_u8(const CannyParams& p, int n_frames, const uint32_t* bits, uint8_t* edges, hipStream_t s);
-void launch_lsd_grad(const LsdParams& p, const ResizeTables& rt, int n_frames, const uint32_t* edge_bits,
-                     const uint32_t* mask_bits, uint32_t* r_addr, float* r_deg, double* r_mod, double* r_cs, double* r_sn,
-                     int* n_rec, unsigned long long* maxgrad, int max_nsx, int max_nsy, uint32_t* list, int* list_count,
-                     uint32_t* l_addr, double* l_mod, int* n_low, int* rec_need, bool counters_zeroed, hipStream_t s);
-void launch_lsd_grad_gray(const LsdParams& p, const ResizeTables& rt, int n_frames, const uint8_t* gray, uint32_t* r_addr, float* r_deg,
-                          double* r_mod, double* r_cs, double* r_sn, int* n_rec, unsigned long long* maxgrad, int max_nsx, int max_nsy,
-                          uint32_t* list, int* list_count, uint32_t* l_addr, double* l_mod, int* n_low, hipStream_t s);
-// the seed order of OpenCV >= 3.2 (k_lsd_seed32.hip): rewrites order_a after launch_lsd_order; l_*: k_lsd_grad's "low" records
+// the LSD stages: the views above, then what is per call (rec_need: BatchStatus::rec_need on the device, or null)
+void launch_lsd_grad(const LsdParams& p, const ResizeTables& rt, const LsdRecords& r, int n_frames, const uint32_t* edge_bits,
+                     const uint32_t* mask_bits, int* rec_need, bool counters_zeroed, hipStream_t s);
+void launch_lsd_grad_gray(const LsdParams& p, const ResizeTables& rt, const LsdRecords& r, int n_frames, const uint8_t* gray, hipStream_t s);
+// the seed order of OpenCV >= 3.2 (k_lsd_seed32.hip): rewrites order_a after launch_lsd_order
 bool lsd_seed32_supported(const LsdParams& p);
-void launch_lsd_seed32(const LsdParams& p, int n_frames, int* n_rec, int* norder, int* rec_need, const unsigned long long* maxgrad, const uint32_t* c_xy,
-                       const double* c_mod, const uint32_t* l_addr, double* l_mod, const int* n_low,
-                       unsigned long long* sort_a, unsigned long long* sort_b, uint32_t* order_a, uint32_t* order_b, int big, hipStream_t s);
+void launch_lsd_seed32(const LsdParams& p, const LsdRecords& r, const LsdCompact& c, int n_frames, int* rec_need, int big, hipStream_t s);
 size_t std_sort_debug_words(int n);
 void launch_std_sort_debug(const uint32_t* E, uint32_t* work, int n, int* count, hipStream_t s);
-void launch_lsd_order(const LsdParams& p, int n_frames, const uint32_t* r_addr, const float* r_deg, const double* r_mod,
-                      const double* r_cs, const double* r_sn, int* n_rec, const unsigned long long* maxgrad,
-                      unsigned long long* sort_a, unsigned long long* sort_b, uint32_t* order_a, uint32_t* order_b,
-                      int* norder, uint32_t* c_xy, float* c_deg, double* c_mod, double* c_cs, double* c_sn,
-                      int* row_start, hipStream_t s);
-void launch_lsd_dense_debug(const LsdParams& p, int n_frames, const int* norder, const uint32_t* c_xy, const float* c_deg,
-                            const double* c_mod, float* ang, double* mod, hipStream_t s);
-void launch_lsd_rank(int n_prob, const int* norder, int* perm, hipStream_t s);
-void launch_lsd_label(const LsdParams& p, int n_frames, const int* norder, const uint32_t* c_xy, const int* row_start,
-                      uint16_t* c_label, uint16_t* comp_list, int* comp_count, int* comp_key, uint32_t* scratch, hipStream_t s);
+void launch_lsd_order(const LsdParams& p, const LsdRecords& r, const LsdCompact& c, int n_frames, hipStream_t s);
+void launch_lsd_dense_debug(const LsdParams& p, const LsdCompact& c, int n_frames, float* ang, double* mod, hipStream_t s);
+void launch_lsd_rank(const LsdComponents& m, int n_prob, hipStream_t s);
+void launch_lsd_label(const LsdParams& p, const LsdCompact& c, const LsdComponents& m, int n_frames, hipStream_t s);
 size_t lsd_grow_reg_stride(const LsdParams& p);
-void launch_lsd_grow(const LsdParams& p, int n_frames, const uint32_t* order, const int* norder, const uint32_t* c_xy,
-                     const float* c_deg, const double* c_mod, const double* c_cs, const double* c_sn,
-                     const int* row_start, const uint16_t* c_label, const uint16_t* comp_list, const int* comp_count, int comp_cap,
-                     uint32_t* reg, uint32_t* gused, float* tmp_lines, int* tmp_tags, float* lines, int* counts, const int* perm,
-                     int lds_kb, bool mixed, int bitmap, hipStream_t s);   // bitmap: 0 = row-list form, 1 = bit-plane form, > 1 = bit-plane form with that many USED bits (tests)
+// lines, counts: the caller's slots; bitmap: 0 = row-list form, 1 = bit-plane form, > 1 = bit-plane form with that many USED bits (tests)
+void launch_lsd_grow(const LsdParams& p, const LsdCompact& c, const LsdComponents& m, int n_frames, float* lines, int* counts,
+                     int lds_kb, bool mixed, int bitmap, hipStream_t s);
 int lsd_grow_def_lds(const LsdParams& p, int lds_kb);   // defined pixels of a problem that fit k_lsd_grow's LDS slice of lds_kb KB
 constexpr int kGrowLdsKb[3] = { 13, 28, 40 };           // the slice sizes a handle moves between (k_lsd_grow.hip)
 void launch_seg_offsets(int n_frames, int cap_lines, const int* counts, int* seg_offset, int* frame_offset,

@@ -423,36 +423,31 @@ __global__ __launch_bounds__(64 * LG_WAVES) void k_lsd_grad(LsdParams p, ResizeT
 
 // the grid of k_lsd_grad: as many waves as the LDS of 256 CUs holds slices (of 150 KB each: other kernels' workgroups
 // stay resident beside them), in workgroups of LG_WAVES waves or as many as one workgroup's 64 KB hold
-static void launch_grad_tiles(const LsdParams& p, const ResizeTables& rt, const uint32_t* edge_bits, const uint32_t* mask_bits,
-                              const uint8_t* gray, uint32_t* r_addr, float* r_deg, double* r_mod, double* r_cs, double* r_sn,
-                              int* n_rec, unsigned long long* maxgrad, int max_nsx, int max_nsy, const uint32_t* list,
-                              const int* list_count, uint32_t* l_addr, double* l_mod, int* n_low, int* rec_need, hipStream_t s)
+static void launch_grad_tiles(const LsdParams& p, const ResizeTables& rt, const LsdRecords& r, const uint32_t* edge_bits, const uint32_t* mask_bits,
+                              const uint8_t* gray, int* rec_need, hipStream_t s)
 {
-    const size_t slice = lsd_grad_carve(p.half, max_nsx, max_nsy).bytes;
+    const size_t slice = lsd_grad_carve(p.half, r.max_nsx, r.max_nsy).bytes;
     int waves = (int)((kLsdGradMaxLds - kLsdGradStaticLds) / slice);       // >= 1: LsdState::init refuses larger tiles
     waves = waves < 1 ? 1 : (waves > LG_WAVES ? LG_WAVES : waves);
     const size_t lds = slice * waves;
     int per_cu = (int)((150 * 1024) / (lds + kLsdGradStaticLds + 512));
     const int most = 32 / waves;                                           // wave slots of a CU
     per_cu = per_cu < 1 ? 1 : (per_cu > most ? most : per_cu);
-    hipLaunchKernelGGL(k_lsd_grad, dim3(256 * per_cu), dim3(64 * waves), lds, s, p, rt, edge_bits, mask_bits, r_addr, r_deg, r_mod, r_cs,
-                       r_sn, n_rec, maxgrad, max_nsx, max_nsy, list, list_count, l_addr, l_mod, n_low, gray, rec_need);
+    hipLaunchKernelGGL(k_lsd_grad, dim3(256 * per_cu), dim3(64 * waves), lds, s, p, rt, edge_bits, mask_bits, r.r_addr, r.r_deg, r.r_mod,
+                       r.r_cs, r.r_sn, r.n_rec, r.maxgrad, r.max_nsx, r.max_nsy, r.list, r.list_count, r.l_addr, r.l_mod, r.n_low, gray, rec_need);
 }
 
-void launch_lsd_grad(const LsdParams& p, const ResizeTables& rt, int n_frames, const uint32_t* edge_bits,
-                     const uint32_t* mask_bits, uint32_t* r_addr, float* r_deg, double* r_mod, double* r_cs, double* r_sn,
-                     int* n_rec, unsigned long long* maxgrad, int max_nsx, int max_nsy, uint32_t* list, int* list_count,
-                     uint32_t* l_addr, double* l_mod, int* n_low, int* rec_need, bool counters_zeroed, hipStream_t s)
+void launch_lsd_grad(const LsdParams& p, const ResizeTables& rt, const LsdRecords& r, int n_frames, const uint32_t* edge_bits,
+                     const uint32_t* mask_bits, int* rec_need, bool counters_zeroed, hipStream_t s)
 {
     if (!counters_zeroed) {                                  // (the batch path zeroes all of a batch's counters with one memset)
-        (void)hipMemsetAsync(list_count, 0, sizeof(int), s);
-        (void)hipMemsetAsync(n_rec, 0, (size_t)n_frames * 3 * sizeof(int), s);
-        if (n_low) (void)hipMemsetAsync(n_low, 0, (size_t)n_frames * 3 * sizeof(int), s);
+        (void)hipMemsetAsync(r.list_count, 0, sizeof(int), s);
+        (void)hipMemsetAsync(r.n_rec, 0, (size_t)n_frames * 3 * sizeof(int), s);
+        if (r.n_low) (void)hipMemsetAsync(r.n_low, 0, (size_t)n_frames * 3 * sizeof(int), s);
     }
-    hipLaunchKernelGGL(k_lsd_classify, dim3(n_frames * 3), dim3(64 * LC_WAVES), 0, s, p, rt, edge_bits, mask_bits, list, list_count,
+    hipLaunchKernelGGL(k_lsd_classify, dim3(n_frames * 3), dim3(64 * LC_WAVES), 0, s, p, rt, edge_bits, mask_bits, r.list, r.list_count,
                        lsd_tiles_y(p.Hs));
-    launch_grad_tiles(p, rt, edge_bits, mask_bits, nullptr, r_addr, r_deg, r_mod, r_cs, r_sn, n_rec, maxgrad, max_nsx, max_nsy, list, list_count,
-                      l_addr, l_mod, n_low, rec_need, s);
+    launch_grad_tiles(p, rt, r, edge_bits, mask_bits, nullptr, rec_need, s);
 }
 
 // every tile of colour 0 of every frame: the tile list of a gray image (nothing to classify)
@@ -467,16 +462,13 @@ __global__ void k_lsd_list_all(int n_frames, int ntx, int nty, uint32_t* __restr
 }
 
 // LSD front half on GRAY images [n_frames][Hc][W] (problem f * 3 holds frame f; problems f * 3 + 1, f * 3 + 2 stay empty)
-void launch_lsd_grad_gray(const LsdParams& p, const ResizeTables& rt, int n_frames, const uint8_t* gray, uint32_t* r_addr, float* r_deg,
-                          double* r_mod, double* r_cs, double* r_sn, int* n_rec, unsigned long long* maxgrad, int max_nsx, int max_nsy,
-                          uint32_t* list, int* list_count, uint32_t* l_addr, double* l_mod, int* n_low, hipStream_t s)
+void launch_lsd_grad_gray(const LsdParams& p, const ResizeTables& rt, const LsdRecords& r, int n_frames, const uint8_t* gray, hipStream_t s)
 {
     const int ntx = lsd_tiles_x(p.Ws), nty = lsd_tiles_y(p.Hs);
-    (void)hipMemsetAsync(n_rec, 0, (size_t)n_frames * 3 * sizeof(int), s);
-    if (n_low) (void)hipMemsetAsync(n_low, 0, (size_t)n_frames * 3 * sizeof(int), s);
-    hipLaunchKernelGGL(k_lsd_list_all, dim3((n_frames * ntx * nty + 255) / 256), dim3(256), 0, s, n_frames, ntx, nty, list, list_count);
-    launch_grad_tiles(p, rt, nullptr, nullptr, gray, r_addr, r_deg, r_mod, r_cs, r_sn, n_rec, maxgrad, max_nsx, max_nsy, list, list_count,
-                      l_addr, l_mod, n_low, nullptr, s);
+    (void)hipMemsetAsync(r.n_rec, 0, (size_t)n_frames * 3 * sizeof(int), s);
+    if (r.n_low) (void)hipMemsetAsync(r.n_low, 0, (size_t)n_frames * 3 * sizeof(int), s);
+    hipLaunchKernelGGL(k_lsd_list_all, dim3((n_frames * ntx * nty + 255) / 256), dim3(256), 0, s, n_frames, ntx, nty, r.list, r.list_count);
+    launch_grad_tiles(p, rt, r, nullptr, nullptr, gray, nullptr, s);
 }
 
 }  // namespace lf

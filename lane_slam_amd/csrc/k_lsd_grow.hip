@@ -339,34 +339,34 @@ int lsd_grow_def_lds(const LsdParams& p, int lds_kb)
 // bounded (flat-access, HBM-backed) path, and a 28 KB slice is worth +13 - 30 % frames/s there (-7 % on the synthetic frames;
 // 20 KB: half of that, 40 KB: no more) -- so the host moves a handle between kGrowLdsKb[] by the share of overflowing problems
 // it saw in the last batch.
-void launch_lsd_grow(const LsdParams& p, int n_frames, const uint32_t* order, const int* norder, const uint32_t* c_xy,
-                     const float* c_deg, const double* c_mod, const double* c_cs, const double* c_sn,
-                     const int* row_start, const uint16_t* c_label, const uint16_t* comp_list, const int* comp_count, int comp_cap,
-                     uint32_t* reg, uint32_t* gused, float* tmp_lines, int* tmp_tags, float* lines, int* counts, const int* perm,
+void launch_lsd_grow(const LsdParams& p, const LsdCompact& c, const LsdComponents& m, int n_frames, float* lines, int* counts,
                      int lds_kb, bool mixed, int bitmap, hipStream_t s)
 {
     int reg_lds, def_lds;
     size_t lds;
     lsd_grow_slice(p, lds_kb > 0 ? lds_kb : LFG_LDS_KB, reg_lds, def_lds, lds);
-#define LF_GROW_LAUNCH(MODE)                                                                                                                   \
-    hipLaunchKernelGGL(k_lsd_grow<MODE>, dim3(n_frames * 3), dim3(64 * GROW_WAVES), lds, s, p, order, norder, c_xy, c_deg, c_mod, c_cs,        \
-                       c_sn, row_start, c_label, comp_list, comp_count, comp_cap, reg, lsd_grow_reg_stride(p), gused, tmp_lines,               \
-                       tmp_tags, lines, counts, reg_lds, def_lds, perm, def_lds)
+    const size_t reg_stride = lsd_grow_reg_stride(p);
+    const dim3 grid(n_frames * 3), block(64 * GROW_WAVES);
+    // the views are unpacked here, once per kernel (the three instances of k_lsd_grow<MODE> have one type)
+    const auto row_lists = [&](decltype(&k_lsd_grow<2>) kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, lds, s, p, c.order_a, c.norder, c.c_xy, c.c_deg, c.c_mod, c.c_cs, c.c_sn, c.row_start, m.c_label,
+                           m.comp_list, m.comp_count, m.comp_cap, m.reg, reg_stride, m.gused, m.tmp_lines, m.tmp_tags, lines, counts, reg_lds,
+                           def_lds, m.perm, def_lds);
+    };
     size_t bm_lds = 0;
     int bm_used = 0;
     if (bitmap && lsd_grow_bitmap_slice(p, reg_lds, bitmap > 1 ? bitmap : 0, bm_used, bm_lds)) {
-        hipLaunchKernelGGL(k_lsd_grow_bm, dim3(n_frames * 3), dim3(64 * GROW_WAVES), bm_lds, s, p, order, norder, c_xy, c_deg, c_mod, c_cs,
-                           c_sn, row_start, c_label, comp_list, comp_count, comp_cap, reg, lsd_grow_reg_stride(p), gused, tmp_lines,
-                           tmp_tags, lines, counts, reg_lds, bm_used, perm);
+        hipLaunchKernelGGL(k_lsd_grow_bm, grid, block, bm_lds, s, p, c.order_a, c.norder, c.c_xy, c.c_deg, c.c_mod, c.c_cs, c.c_sn, c.row_start, m.c_label,
+                           m.comp_list, m.comp_count, m.comp_cap, m.reg, reg_stride, m.gused, m.tmp_lines, m.tmp_tags, lines, counts, reg_lds, bm_used, m.perm);
         // what it left (none, on every frame measured): the bounded code with its tables in global memory (k_lsd_grow_zl)
-        hipLaunchKernelGGL(k_lsd_grow_zl, dim3(n_frames * 3), dim3(64 * GROW_WAVES), 0, s, p, order, norder, c_xy, c_deg, c_mod, c_cs,
-                           c_sn, row_start, c_label, comp_list, comp_count, comp_cap, reg, lsd_grow_reg_stride(p), gused, tmp_lines,
-                           tmp_tags, lines, counts, bm_used, perm);
-        return;
+        hipLaunchKernelGGL(k_lsd_grow_zl, grid, block, 0, s, p, c.order_a, c.norder, c.c_xy, c.c_deg, c.c_mod, c.c_cs, c.c_sn, c.row_start, m.c_label,
+                           m.comp_list, m.comp_count, m.comp_cap, m.reg, reg_stride, m.gused, m.tmp_lines, m.tmp_tags, lines, counts, bm_used, m.perm);
+    } else if (mixed) {
+        row_lists(k_lsd_grow<2>);
+    } else {
+        row_lists(k_lsd_grow<0>);
+        row_lists(k_lsd_grow<1>);
     }
-    if (mixed) { LF_GROW_LAUNCH(2); }
-    else { LF_GROW_LAUNCH(0); LF_GROW_LAUNCH(1); }
-#undef LF_GROW_LAUNCH
 }
 
 }  // namespace lf

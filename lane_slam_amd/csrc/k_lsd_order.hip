@@ -449,11 +449,7 @@ __global__ __launch_bounds__(OBT) void k_lsd_order_bm(LsdParams p, const uint32_
     walk(true);
 }
 
-void launch_lsd_order(const LsdParams& p, int n_frames, const uint32_t* r_addr, const float* r_deg, const double* r_mod,
-                      const double* r_cs, const double* r_sn, int* n_rec, const unsigned long long* maxgrad,
-                      unsigned long long* sort_a, unsigned long long* sort_b, uint32_t* order_a, uint32_t* order_b,
-                      int* norder, uint32_t* c_xy, float* c_deg, double* c_mod, double* c_cs, double* c_sn,
-                      int* row_start, hipStream_t s)
+void launch_lsd_order(const LsdParams& p, const LsdRecords& r, const LsdCompact& c, int n_frames, hipStream_t s)
 {
     // the bit-plane form wherever the plane fits its LDS budget and the bins its counters (LF_ORDER_SORT=1: the sorting kernel of
     // rounds 1 - 3, for A/B; LF_ORDER_HBM=1: every problem down the bit-plane kernel's HBM branch, for the tests)
@@ -464,8 +460,8 @@ void launch_lsd_order(const LsdParams& p, int n_frames, const uint32_t* r_addr, 
     if (blds < (size_t)(OBT / 64) * OB_BINS * 2) blds = (size_t)(OBT / 64) * OB_BINS * 2;
     if (blds < (size_t)8 * OBT * 4) blds = (size_t)8 * OBT * 4;
     if (!old_form && p.n_bins <= OB_BINS && blds <= 40 * 1024 && Ps < ((size_t)1 << 20)) {
-        hipLaunchKernelGGL(k_lsd_order_bm, dim3(n_frames * 3), dim3(OBT), blds, s, p, r_addr, r_deg, r_mod, r_cs, r_sn, n_rec, maxgrad,
-                           sort_a, sort_b, order_a, order_b, norder, c_xy, c_deg, c_mod, c_cs, c_sn, row_start, force_hbm);
+        hipLaunchKernelGGL(k_lsd_order_bm, dim3(n_frames * 3), dim3(OBT), blds, s, p, r.r_addr, r.r_deg, r.r_mod, r.r_cs, r.r_sn, r.n_rec,
+                           r.maxgrad, c.sort_a, c.sort_b, c.order_a, c.order_b, c.norder, c.c_xy, c.c_deg, c.c_mod, c.c_cs, c.c_sn, c.row_start, force_hbm);
         return;
     }
     const size_t lds = ((size_t)2 * LDS_ITEMS + 2 * (size_t)(p.Hs + 2) + 2 * (OT / 64) * 32) * sizeof(uint32_t);
@@ -473,8 +469,8 @@ void launch_lsd_order(const LsdParams& p, int n_frames, const uint32_t* r_addr, 
     // (a refusal surfaces through hipGetLastError() in the caller's LF_HIP_CHECK after the launch)
     if (lds > 48 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_lsd_order), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_lsd_order, dim3(n_frames * 3), dim3(OT), lds, s, p, r_addr, r_deg, r_mod, r_cs, r_sn, n_rec, maxgrad,
-                       sort_a, sort_b, order_a, order_b, norder, c_xy, c_deg, c_mod, c_cs, c_sn, row_start);
+    hipLaunchKernelGGL(k_lsd_order, dim3(n_frames * 3), dim3(OT), lds, s, p, r.r_addr, r.r_deg, r.r_mod, r.r_cs, r.r_sn, r.n_rec, r.maxgrad,
+                       c.sort_a, c.sort_b, c.order_a, c.order_b, c.norder, c.c_xy, c.c_deg, c.c_mod, c.c_cs, c.c_sn, c.row_start);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -754,9 +750,9 @@ __global__ __launch_bounds__(256) void k_lsd_rank(int n_prob, const int* __restr
     }
 }
 
-void launch_lsd_rank(int n_prob, const int* norder, int* perm, hipStream_t s)
+void launch_lsd_rank(const LsdComponents& m, int n_prob, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_lsd_rank, dim3(1), dim3(256), 0, s, n_prob, norder, perm);
+    hipLaunchKernelGGL(k_lsd_rank, dim3(1), dim3(256), 0, s, n_prob, m.comp_key, m.perm);
 }
 
 // one launch, the form chosen per problem (both fit 24 KB of dynamic LDS; two launches cost a busy pipeline ~2 ms of a batch's latency)
@@ -778,8 +774,7 @@ __global__ __launch_bounds__(LT) void k_lsd_label(LsdParams p, const int* __rest
     }
 }
 
-void launch_lsd_label(const LsdParams& p, int n_frames, const int* norder, const uint32_t* c_xy, const int* row_start,
-                      uint16_t* c_label, uint16_t* comp_list, int* comp_count, int* comp_key, uint32_t* scratch, hipStream_t s)
+void launch_lsd_label(const LsdParams& p, const LsdCompact& c, const LsdComponents& m, int n_frames, hipStream_t s)
 {
     size_t lds = (size_t)p.label_lds * (2 + 2);
     const size_t plane = bitplane_lds_words((size_t)p.Hs * p.Ws) * 4;
@@ -790,7 +785,8 @@ void launch_lsd_label(const LsdParams& p, int n_frames, const int* norder, const
     // LF_DIAG_COMP_CAP: a smaller component list, so that tests reach the "more components than the list holds" fallback
     static const int comp_cap = getenv("LF_DIAG_COMP_CAP") ? max(1, min(kCompCap, atoi(getenv("LF_DIAG_COMP_CAP")))) : kCompCap;
     const size_t stride = lsd_grow_reg_stride(p);               // the region scratch is free until k_lsd_grow runs
-    hipLaunchKernelGGL(k_lsd_label, dim3(n_frames * 3), dim3(LT), lds, s, p, norder, c_xy, row_start, c_label, comp_list, comp_count, comp_key, comp_cap, scratch, stride, plane_fits);
+    hipLaunchKernelGGL(k_lsd_label, dim3(n_frames * 3), dim3(LT), lds, s, p, c.norder, c.c_xy, c.row_start, m.c_label, m.comp_list, m.comp_count,
+                       m.comp_key, comp_cap, m.reg, stride, plane_fits);
 }
 
 // Debug only: dense angle / magnitude planes rebuilt from the compact arrays (NOTDEF / 0 elsewhere).
@@ -811,10 +807,9 @@ __global__ void k_lsd_dense_debug(LsdParams p, const int* __restrict__ norder, c
     }
 }
 
-void launch_lsd_dense_debug(const LsdParams& p, int n_frames, const int* norder, const uint32_t* c_xy, const float* c_deg,
-                            const double* c_mod, float* ang, double* mod, hipStream_t s)
+void launch_lsd_dense_debug(const LsdParams& p, const LsdCompact& c, int n_frames, float* ang, double* mod, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_lsd_dense_debug, dim3(n_frames * 3), dim3(1024), 0, s, p, norder, c_xy, c_deg, c_mod, ang, mod);
+    hipLaunchKernelGGL(k_lsd_dense_debug, dim3(n_frames * 3), dim3(1024), 0, s, p, c.norder, c.c_xy, c.c_deg, c.c_mod, ang, mod);
 }
 
 }  // namespace lf

@@ -2043,9 +2043,7 @@ bool lsd_seed32_supported(const LsdParams& p)
 
 // big != 0: dense problems are expected (LSD of a gray image: most pixels have a gradient) -- the row tables of the dense phase
 // cover the whole image in LDS when they fit
-void launch_lsd_seed32(const LsdParams& p, int n_frames, int* n_rec, int* norder, int* rec_need, const unsigned long long* maxgrad, const uint32_t* c_xy,
-                       const double* c_mod, const uint32_t* l_addr, double* l_mod, const int* n_low,
-                       unsigned long long* sort_a, unsigned long long* sort_b, uint32_t* order_a, uint32_t* order_b, int big, hipStream_t s)
+void launch_lsd_seed32(const LsdParams& p, const LsdRecords& r, const LsdCompact& c, int n_frames, int* rec_need, int big, hipStream_t s)
 {
     const long long n = (long long)(p.Hs - 1) * (p.Ws - 1);
     int rows_cap = kRowsLds;
@@ -2061,10 +2059,10 @@ void launch_lsd_seed32(const LsdParams& p, int n_frames, int* n_rec, int* norder
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_lsd_seed32_dense), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
     static const char* diag_skip = getenv("LF_DIAG_SKIP");     // diagnostic only (what-if timing, results are wrong): "seedchain", "seeddense"
     if (!(diag_skip && strstr(diag_skip, "seedchain")))
-    hipLaunchKernelGGL(k_lsd_seed32, dim3(n_frames * 3), dim3(ST), lds, s, p, n_rec, norder, rec_need, maxgrad, c_xy, c_mod, l_addr, l_mod, n_low,
-                       sort_a, sort_b, order_a, order_b, plane_ok, (int)(lds / 4));
+    hipLaunchKernelGGL(k_lsd_seed32, dim3(n_frames * 3), dim3(ST), lds, s, p, r.n_rec, c.norder, rec_need, r.maxgrad, c.c_xy, c.c_mod, r.l_addr, r.l_mod,
+                       r.n_low, c.sort_a, c.sort_b, c.order_a, c.order_b, plane_ok, (int)(lds / 4));
     if (!(diag_skip && (strstr(diag_skip, "seeddense") || strstr(diag_skip, "seedchain"))))
-    hipLaunchKernelGGL(k_lsd_seed32_dense, dim3(n_frames * 3), dim3(DT), lds2, s, p, n_rec, l_mod, sort_a, sort_b, order_a, order_b, rows_cap);
+    hipLaunchKernelGGL(k_lsd_seed32_dense, dim3(n_frames * 3), dim3(DT), lds2, s, p, r.n_rec, r.l_mod, c.sort_a, c.sort_b, c.order_a, c.order_b, rows_cap);
 }
 
 // words of device scratch k_std_sort_debug needs for n elements

@@ -170,7 +170,7 @@ extern "C" int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t byt
         int rc = scratch(h, h->dbg_ang, n * 3 * L.Ps * sizeof(float));
         if (rc == LF_OK) rc = scratch(h, h->dbg_mod, n * 3 * L.Ps * sizeof(double));
         if (rc != LF_OK) return rc;
-        launch_lsd_dense_debug(L.params, (int)n, L.d_norder, L.d_cxy, L.d_cdeg, L.d_cmod, (float*)h->dbg_ang.p, (double*)h->dbg_mod.p, s);
+        launch_lsd_dense_debug(L.params, L.compact(), (int)n, (float*)h->dbg_ang.p, (double*)h->dbg_mod.p, s);
         if (buffer_id == LF_BUF_LSD_ANGLE) { src = h->dbg_ang.p; avail = n * 3 * L.Ps * sizeof(float); }
         else { src = h->dbg_mod.p; avail = n * 3 * L.Ps * sizeof(double); }
         break;

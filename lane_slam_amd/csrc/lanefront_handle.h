@@ -138,7 +138,6 @@ struct LsdState {
     DevArray<double> d_rmod, d_rcs, d_rsn, d_cmod, d_ccs, d_lmod;
     DevArray<unsigned long long> d_sort_a, d_sort_b;
     DevArray<uint16_t> d_clabel, d_comp_list;         // connected components (k_lsd_label)
-    double* d_csn = nullptr;                          // d_ccs + 1
     DevArray<uint32_t> d_tile_list, d_gused;
     DevArray<int> d_row_start, d_norder, d_comp_count, d_comp_key, d_perm;
     DevArray<float> d_tmp_lines;                      // lines in completion order + their seed positions (k_lsd_grow)
@@ -161,6 +160,10 @@ struct LsdState {
     void free_lists();
     int grow_lists(lf_handle* h, int need);
     void adapt_slice(int over_small, int over_medium, int problems);
+    // the arrays as the launchers take them (common.h); use_perm false: k_lsd_grow in the natural launch order
+    LsdRecords records() const;
+    LsdCompact compact() const;
+    LsdComponents components(bool use_perm = true) const;
     // the stages on n frames; the caller zeroes the counters
     void grad(int n, const uint32_t* edge_bits, const uint32_t* mask_bits, bool counters_zeroed, hipStream_t s);
     void grad_gray(int n, const uint8_t* gray, hipStream_t s);

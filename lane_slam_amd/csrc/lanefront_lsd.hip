@@ -152,7 +152,7 @@ void LsdState::free_lists()
     for (auto* b : { &d_rdeg, &d_cdeg, &d_rsd, &d_csd }) b->reset();
     for (auto* b : { &d_rmod, &d_rcs, &d_rsn, &d_cmod, &d_ccs, &d_lmod }) b->reset();
     d_sort_a.reset(); d_sort_b.reset(); d_clabel.reset();
-    params.r_sd = nullptr; params.c_sd = nullptr; d_csn = nullptr;
+    params.r_sd = nullptr; params.c_sd = nullptr;
 }
 
 int LsdState::alloc_lists(lf_handle* h, int rec_cap)
@@ -171,7 +171,6 @@ int LsdState::alloc_lists(lf_handle* h, int rec_cap)
         dalloc(h, &d_cmod, nprob * S) || dalloc(h, &d_ccs, nprob * S * 2) || dalloc(h, &d_reg, nprob * lsd_grow_reg_stride(L)) ||
         dalloc(h, &d_clabel, nprob * S))
         return LF_ERR_HIP;
-    d_csn = d_ccs + 1;          // (cos, sin) pairs in one array: k_lsd_order.hip
     if (dalloc(h, &d_rsd, nprob * S * 2) || dalloc(h, &d_csd, nprob * S * 2)) return LF_ERR_HIP;
     L.r_sd = d_rsd; L.c_sd = d_csd;
     if (seed_order == LF_LSD_SEED_OPENCV32 && (dalloc(h, &d_laddr, nprob * S) || dalloc(h, &d_lmod, nprob * S)))
@@ -210,39 +209,66 @@ void LsdState::adapt_slice(int over_small, int over_medium, int problems)
     grow_mixed = (grow_lds_level == 0 ? over_small : over_medium) * 100 > problems;
 }
 
+// The views of the arrays above (common.h): every owner is named in one of them and nowhere else below
+LsdRecords LsdState::records() const
+{
+    LsdRecords v{};
+    v.r_addr = d_raddr; v.r_deg = d_rdeg; v.r_mod = d_rmod; v.r_cs = d_rcs; v.r_sn = d_rsn;
+    v.n_rec = d_nrec; v.maxgrad = d_maxgrad;
+    v.l_addr = d_laddr; v.l_mod = d_lmod; v.n_low = d_nlow;
+    v.list = d_tile_list; v.list_count = d_tile_count;
+    v.max_nsx = max_nsx; v.max_nsy = max_nsy;
+    return v;
+}
+
+LsdCompact LsdState::compact() const
+{
+    LsdCompact v{};
+    v.sort_a = d_sort_a; v.sort_b = d_sort_b; v.order_a = d_order_a; v.order_b = d_order_b;
+    v.norder = d_norder;
+    v.c_xy = d_cxy; v.c_deg = d_cdeg; v.c_mod = d_cmod;
+    v.c_cs = d_ccs; v.c_sn = d_ccs ? d_ccs + 1 : nullptr;        // (cos, sin) pairs in one array: k_lsd_order.hip
+    v.row_start = d_row_start;
+    return v;
+}
+
+LsdComponents LsdState::components(bool use_perm) const
+{
+    LsdComponents v{};
+    v.c_label = d_clabel;
+    v.comp_list = d_comp_list; v.comp_count = d_comp_count; v.comp_key = d_comp_key; v.comp_cap = kCompCap;
+    v.perm = use_perm ? d_perm.p : nullptr;
+    v.reg = d_reg; v.gused = d_gused;
+    v.tmp_lines = d_tmp_lines; v.tmp_tags = d_tmp_tags;
+    return v;
+}
+
 void LsdState::grad(int n, const uint32_t* edge_bits, const uint32_t* mask_bits, bool counters_zeroed, hipStream_t s)
 {
-    launch_lsd_grad(params, rt, n, edge_bits, mask_bits, d_raddr, d_rdeg, d_rmod, d_rcs, d_rsn, d_nrec, d_maxgrad, max_nsx, max_nsy,
-                    d_tile_list, d_tile_count, d_laddr, d_lmod, d_nlow, &d_status->rec_need, counters_zeroed, s);
+    launch_lsd_grad(params, rt, records(), n, edge_bits, mask_bits, &d_status->rec_need, counters_zeroed, s);
 }
 
 void LsdState::grad_gray(int n, const uint8_t* gray, hipStream_t s)
 {
-    launch_lsd_grad_gray(params, rt, n, gray, d_raddr, d_rdeg, d_rmod, d_rcs, d_rsn, d_nrec, d_maxgrad, max_nsx, max_nsy,
-                         d_tile_list, d_tile_count, d_laddr, d_lmod, d_nlow, s);
+    launch_lsd_grad_gray(params, rt, records(), n, gray, s);
 }
 
 void LsdState::order(int n, int big, hipStream_t s)
 {
-    launch_lsd_order(params, n, d_raddr, d_rdeg, d_rmod, d_rcs, d_rsn, d_nrec, d_maxgrad, d_sort_a, d_sort_b, d_order_a, d_order_b,
-                     d_norder, d_cxy, d_cdeg, d_cmod, d_ccs, d_csn, d_row_start, s);
+    launch_lsd_order(params, records(), compact(), n, s);
     // OpenCV >= 3.2: the seeds in the order std::sort leaves them in (the compact arrays and row starts stay as they are)
-    if (seed_order == LF_LSD_SEED_OPENCV32)
-        launch_lsd_seed32(params, n, d_nrec, d_norder, &d_status->rec_need, d_maxgrad, d_cxy, d_cmod, d_laddr, d_lmod, d_nlow, d_sort_a, d_sort_b,
-                          d_order_a, d_order_b, big, s);
+    if (seed_order == LF_LSD_SEED_OPENCV32) launch_lsd_seed32(params, records(), compact(), n, &d_status->rec_need, big, s);
 }
 
 void LsdState::label(int n, bool rank, hipStream_t s)
 {
-    launch_lsd_label(params, n, d_norder, d_cxy, d_row_start, d_clabel, d_comp_list, d_comp_count, d_comp_key, d_reg, s);
-    if (rank) launch_lsd_rank(n * 3, d_comp_key, d_perm, s);
+    launch_lsd_label(params, compact(), components(), n, s);
+    if (rank) launch_lsd_rank(components(), n * 3, s);
 }
 
 void LsdState::grow(int n, float* lines, int* counts, int lds_kb, bool mixed, bool use_perm, hipStream_t s)
 {
-    launch_lsd_grow(params, n, d_order_a, d_norder, d_cxy, d_cdeg, d_cmod, d_ccs, d_csn, d_row_start, d_clabel, d_comp_list, d_comp_count,
-                    kCompCap, d_reg, d_gused, d_tmp_lines, d_tmp_tags, lines, counts, use_perm ? d_perm : nullptr, lds_kb, mixed,
-                    env_bitmap, s);
+    launch_lsd_grow(params, compact(), components(use_perm), n, lines, counts, lds_kb, mixed, env_bitmap, s);
 }
 
 }  // namespace lf
