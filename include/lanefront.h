@@ -900,6 +900,70 @@ LF_API int lf_map_prune(lf_map* m, const lf_prune_config* c, lf_prune_result* re
  * A stage of its own: lf_map_get_timing and the solvers' timing calls are unchanged. */
 LF_API int lf_map_prune_timing(lf_map* m, double* ms, int32_t* launches);
 
+/* ---- association gated by the prior pose: lf_map_associate_near ------------------------------------------
+ * lf_map_associate returns the entry nearest in Hamming distance over the WHOLE map, and colour is its only gate.  A lane map is
+ * made of look-alike marks, so that search picks entries anywhere on the track and the solvers discard most pairs at their own
+ * gate.  lf_map_associate_near looks only where the segment can be: it takes the frames' prior poses, puts every segment into the
+ * map frame and searches the entries near it, through a hash grid over the entries' midpoints that every call builds on the
+ * device from the map as it stands (a step changes the map anyway).  The reference has no associator: this is
+ * the package's OWN contract, written so that a sequential restatement (tests/map_near_ref.py, a brute force over all rows) and
+ * the kernels (k_map_near.hip) agree bit for bit.  Nothing of the map is changed.  All f64, unfused, in the order written here.
+ *
+ * segs supplies frame_offset, code and ground (robot frame), and color when the map gates by colour; keep is not read.
+ *   frame             frame f holds the segments frame_offset[f] <= i < frame_offset[f + 1], the offsets clamped to 0 .. n as
+ *                     lf_map_align clamps them.  A segment that several frames hold belongs to the lowest of them; one that no
+ *                     frame holds has no candidates.
+ *   pose              (x, y, th) = frame_pose[3 f ..]; (sn, cs) = sin, cos of th by the library's routine ON THE HOST, as
+ *                     lf_map_pack_block takes them.  Both endpoints (px, py) = ground[4 i + 2 e ..] of the segment:
+ *                     qx = x + (cs px - sn py), qy = y + (sn px + cs py).  frame_pose NULL: every pose is (+0, +0, +0).
+ *   segment           sx = qx1 - qx0, sy = qy1 - qy0, S2 = sx sx + sy sy;  qmx = (qx0 + qx1) 0.5, qmy = (qy0 + qy1) 0.5.  qx0, qy0, qx1,
+ *                     qy1 are finite and S2 is finite and > 0: otherwise the segment has no candidates.
+ *   entry t           0 <= t < the map's size (the physical row, as lf_map_associate counts): Ax Ay Bx By are finite;  ex = Bx - Ax,
+ *                     ey = By - Ay, L2 = ex ex + ey ey is finite and > 0;  emx = (Ax + Bx) 0.5, emy = (Ay + By) 0.5.
+ *   candidate         entry t is a candidate of segment i when ALL hold (a comparison with a NaN fails):
+ *                       ddx = qmx - emx, ddy = qmy - emy, d2 = ddx ddx + ddy ddy;  d2 <= r2, r2 = radius radius;
+ *                       max_sin < 1:  cr = sx ey - sy ex;  cr cr <= (max_sin max_sin) (S2 L2);
+ *                       max_offset finite:  o = (qmx - Ax) ey - (qmy - Ay) ex;  o o <= (max_offset max_offset) L2;
+ *                       hits[t] >= min_hits;
+ *                       the map's color_gating on: color[i] == the entry's colour, or either of them is >= 3.
+ *   n_near[i]         the number of candidates.
+ *   idx, dist         as lf_map_associate shapes them.  Among the candidates with h <= the map's max_distance, h = the number of
+ *                     set bits of code[i] xor the entry's code, the winner is the one with the smallest triple (h, d2, t), d2
+ *                     compared as f64: idx[i] = t, dist[i] = (float)h.  No such candidate: idx[i] = -1, dist[i] = -1.f.
+ *                     The map's tie rule (lf_map_set_tie_rule) does NOT apply: Mihasher's discovery order is a property of a search
+ *                     over the whole map and has no meaning inside a gate; the nearer midpoint, then the lower row, decides.
+ *   an empty map      idx = -1, dist = -1.f and n_near = 0 everywhere.
+ * LF_ERR_BAD_ARG, touching nothing: NULL segs, cfg, idx or dist with n > 0; n < 0; n_frames outside 1 .. 4096; n > 0 without
+ * segs->frame_offset, segs->code or segs->ground; colour gating on and no segs->color; a pose that is not finite; a radius that is
+ * not finite or <= 0; a max_offset that is <= 0 or NaN; a max_sin outside 0 .. 1 or NaN; min_hits < 0.
+ *
+ * The call is queued on the map's stream in call order with updates and associations, without a host wait inside; with host
+ * arrays (on_device = 0) it returns when idx, dist and n_near are in place.
+ *
+ * lf_map_set_near: while a configuration is set, lf_map_step, lf_map_step_aligned, lf_map_step_smoothed and their _host forms
+ * associate by this rule with the call's frame_pose (NULL: +0) in place of lf_map_associate; everything after the association
+ * (the solver, lf_map_pack_block, lf_map_update) is unchanged, so a step under the gate leaves a map byte-identical to
+ * lf_map_associate_near followed by the separate calls with the same idx / dist.  Those steps then refuse what this call refuses.
+ * lf_map_associate itself has no geometry to gate and is unaffected. */
+typedef struct lf_near_config {
+    double  radius;       /* metres, finite, > 0: the midpoints are at most this far apart; default 0.25 */
+    double  max_offset;   /* metres, > 0 or +inf (not tested): the segment's midpoint lies at most this far from the entry's line; default 0.10 */
+    double  max_sin;      /* 0 .. 1; 1: not tested.  |sin| of the angle between the two lines; default 0.5 */
+    int32_t min_hits;     /* entries with fewer hits are not candidates; default 1 */
+    int32_t reserved_;    /* 0 */
+} lf_near_config;
+LF_API int lf_sizeof_near_config(void);
+LF_API void lf_map_near_default_config(lf_near_config* c);
+/* segs' arrays, idx, dist and n_near are device (on_device = 1) or host (0) arrays; h as for lf_map_associate */
+LF_API int lf_map_associate_near(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames,
+                          const double* frame_pose /* host [n_frames][3] or NULL */, const lf_near_config* cfg,
+                          int32_t* idx, float* dist, int32_t* n_near /* or NULL */, int on_device);
+LF_API int lf_map_set_near(lf_map* m, const lf_near_config* cfg /* NULL: off, the default */);
+LF_API int lf_map_get_near(const lf_map* m, lf_near_config* cfg);   /* 1: set (and *cfg is it), 0: off */
+/* ms and launches accumulated since the previous call, with profiling on; resets them: [0] the index build (one launch = one
+ * build, all its kernels), [1] the query.  Stages of their own: lf_map_get_timing and the other timing calls are unchanged. */
+LF_API int lf_map_near_timing(lf_map* m, double ms[2], int32_t launches[2]);
+
 /* ---- Histogram lane filter: lane pose from ground segments -----------------------------------------
  * LaneFilterHistogram (src/lane_filter/include/lane_filter/lane_filter.py:12-161) as lane_filter_node.processSegments
  * drives it (src/lane_filter/src/lane_filter_node.py:49-87): per frame predict(dt, v, w) -> update(segments) ->

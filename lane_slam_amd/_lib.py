@@ -48,6 +48,7 @@ EXPORTS = (
     "lf_map_smooth_timing",
     "lf_sizeof_localize_config", "lf_sizeof_localize_result", "lf_map_localize_default_config", "lf_map_localize", "lf_map_localize_timing",
     "lf_sizeof_prune_config", "lf_sizeof_prune_result", "lf_map_prune_default_config", "lf_map_prune", "lf_map_prune_timing",
+    "lf_sizeof_near_config", "lf_map_near_default_config", "lf_map_associate_near", "lf_map_set_near", "lf_map_get_near", "lf_map_near_timing",
 )
 LF_ALIGN_OK, LF_ALIGN_FEW, LF_ALIGN_DEGENERATE, LF_ALIGN_REJECTED = 0, 1, 2, 3
 ALIGN_STATUS = ("ok", "few", "degenerate", "rejected")
@@ -215,6 +216,12 @@ class LfPruneConfig(ctypes.Structure):
 class LfPruneResult(ctypes.Structure):
     """ctypes mirror of `lf_prune_result` (include/lanefront.h)."""
     _fields_ = [(k, ctypes.c_int32) for k in ("size_before", "size_after", "n_stale", "n_weak", "n_box", "n_covered")]
+
+
+class LfNearConfig(ctypes.Structure):
+    """ctypes mirror of `lf_near_config` (include/lanefront.h)."""
+    _fields_ = [("radius", ctypes.c_double), ("max_offset", ctypes.c_double), ("max_sin", ctypes.c_double), ("min_hits", ctypes.c_int32),
+                ("reserved_", ctypes.c_int32)]
 
 
 _lib = None
@@ -386,6 +393,15 @@ def load():
     lib.lf_map_prune.argtypes = [vp, ctypes.POINTER(LfPruneConfig), ctypes.POINTER(LfPruneResult), vp, ci]
     lib.lf_map_prune_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
     for f in ("lf_sizeof_prune_config", "lf_sizeof_prune_result", "lf_map_prune", "lf_map_prune_timing"):
+        getattr(lib, f).restype = ci
+    lib.lf_sizeof_near_config.argtypes = []
+    lib.lf_map_near_default_config.argtypes = [ctypes.POINTER(LfNearConfig)]
+    lib.lf_map_near_default_config.restype = None
+    lib.lf_map_associate_near.argtypes = [vp, vp, ctypes.POINTER(LfSegments), ci, ci, vp, ctypes.POINTER(LfNearConfig), vp, vp, vp, ci]
+    lib.lf_map_set_near.argtypes = [vp, ctypes.POINTER(LfNearConfig)]
+    lib.lf_map_get_near.argtypes = [vp, ctypes.POINTER(LfNearConfig)]
+    lib.lf_map_near_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
+    for f in ("lf_sizeof_near_config", "lf_map_associate_near", "lf_map_set_near", "lf_map_get_near", "lf_map_near_timing"):
         getattr(lib, f).restype = ci
     lib.lf_descriptor_default_params.argtypes = [ctypes.POINTER(LfDescriptorParams)]
     lib.lf_descriptor_default_params.restype = None

@@ -345,7 +345,7 @@ extern "C" int lf_map_step(lf_map* m, lf_handle* h, const lf_segments* segs, int
     if (!m) return LF_ERR_NOT_INITIALISED;
     if (!segs || n < 0 || (n > 0 && (!idx || !dist))) { set_error(m, LF_ERR_BAD_ARG, "lf_map_step: bad argument"); return LF_ERR_BAD_ARG; }
     int rc;
-    if (n > 0 && (rc = lf_map_associate(m, h, segs->code, segs->color, n, idx, dist, 1)) != LF_OK) return rc;
+    if ((rc = associate_for_step(m, h, "lf_map_step", segs, n, n_frames, frame_pose, idx, dist)) != LF_OK) return rc;
     LF_HIP_CHECK(m, hipSetDevice(m->device));
     if ((rc = scratch(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) != LF_OK) return rc;
     if ((rc = lf_map_pack_block(m, h, segs, n, n_frames, idx, dist, frame_pose, step, static_cast<uint8_t*>(m->own_block.p), n + 1)) != LF_OK) return rc;

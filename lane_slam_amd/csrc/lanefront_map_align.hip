@@ -88,12 +88,12 @@ int upload_prior_pose(lf_map* m, const double* pose, int n_frames, const double*
     return LF_OK;
 }
 
-int step_solved(lf_map* m, lf_handle* h, const char* who, const lf_segments* segs, int n, int n_frames, int step, int32_t* idx, float* dist,
-                const std::function<int(const ma::Batch&)>& queue_solver)
+int step_solved(lf_map* m, lf_handle* h, const char* who, const lf_segments* segs, int n, int n_frames, const double* frame_pose, int step,
+                int32_t* idx, float* dist, const std::function<int(const ma::Batch&)>& queue_solver)
 {
     int rc;
     if (n > 0 && (!dist || !segs->code)) { set_error(m, LF_ERR_BAD_ARG, "%s: code and dist are required", who); return LF_ERR_BAD_ARG; }
-    if (n > 0 && (rc = lf_map_associate(m, h, segs->code, segs->color, n, idx, dist, 1)) != LF_OK) return rc;
+    if ((rc = associate_for_step(m, h, who, segs, n, n_frames, frame_pose, idx, dist)) != LF_OK) return rc;
     LF_HIP_CHECK(m, hipSetDevice(m->device));
     if ((rc = scratch(m, m->own_block, (size_t)(n + 1) * LF_BLOCK_ROW_BYTES)) != LF_OK) return rc;
     if ((rc = after_handle(m, h)) != LF_OK) return rc;
@@ -186,7 +186,7 @@ extern "C" int lf_map_step_aligned(lf_map* m, lf_handle* h, const lf_segments* s
     if (!m) return LF_ERR_NOT_INITIALISED;
     int rc;
     if ((rc = align_check_call(m, "lf_map_step_aligned", segs, n, n_frames, idx, frame_pose, cfg, results)) != LF_OK) return rc;
-    rc = step_solved(m, h, "lf_map_step_aligned", segs, n, n_frames, step, idx, dist,
+    rc = step_solved(m, h, "lf_map_step_aligned", segs, n, n_frames, frame_pose, step, idx, dist,
                      [&](const ma::Batch& b) { return queue_align(m, b, frame_pose, cfg); });
     if (rc != LF_OK) return rc;
     return fetch(m, { { results, m->al_res.p, (size_t)n_frames * sizeof(lf_align_result) } });

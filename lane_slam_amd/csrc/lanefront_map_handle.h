@@ -1,6 +1,7 @@
 // The live map's handle, for the translation units of lf_map_*: the map itself (lanefront_map.hip), its two views
 // (lanefront_map_render.hip, lanefront_map_camera.hip), the pose alignment (lanefront_map_align.hip) and the trajectory smoother
-// (lanefront_map_smooth.hip); the localisation without a prior pose (lanefront_map_localize.hip); the culling (lanefront_map_prune.hip).  The three pose solvers share one
+// (lanefront_map_smooth.hip); the localisation without a prior pose (lanefront_map_localize.hip); the culling (lanefront_map_prune.hip);
+// the association gated by the prior pose (lanefront_map_near.hip).  The three pose solvers share one
 // front end (argument check, batch opener, prior-pose upload) and the two solving steps one body and, with
 // lf_map_step_host, one host-form wrapper: all of it lives in lanefront_map_align.hip and is declared at the end of this file.
 #pragma once
@@ -11,6 +12,13 @@
 #include "k_map_align.h"
 
 namespace lf {
+
+// what lf_map_associate_near keeps between calls (lanefront_map_near.hip): the index of the map, rebuilt by every call, and the
+// poses' x, y, cos, sin; scratch that grows on demand
+struct MapNearState {
+    DevBuf start, cursor, bucket, rec, pose, near_out;      // k_map_near.h's Index; pose [n_frames][4]; near_out: a host caller's n_near staged
+    std::vector<double> h_pose;
+};
 
 // what lf_map_render and lf_map_bounds keep between calls: every buffer grows on demand and is reused
 struct MapRenderState {
@@ -73,8 +81,12 @@ struct lf_map : lf::Core {
     std::vector<double> h_pose;
     std::vector<int32_t> h_chains;
     // per-stage timing: the stages of lf_map_get_timing, then kMapAlignStage (lf_map_align_timing), kMapSmoothStage
-    // (lf_map_smooth_timing), kMapLocalizeStage (lf_map_localize_timing) and kMapPruneStage (lf_map_prune_timing); past 4096 outstanding records a bracket goes untimed
-    StageClock clock{LF_MAP_N_STAGES + 4, 4096, false};
+    // (lf_map_smooth_timing), kMapLocalizeStage (lf_map_localize_timing), kMapPruneStage (lf_map_prune_timing) and kMapNearIndexStage,
+    // kMapNearQueryStage (lf_map_near_timing); past 4096 outstanding records a bracket goes untimed
+    StageClock clock{LF_MAP_N_STAGES + 6, 4096, false};
+    bool near_on = false;                         // lf_map_set_near: the steps associate by lf_map_associate_near's rule with near_cfg
+    lf_near_config near_cfg = {};
+    std::unique_ptr<lf::MapNearState> near;       // lf_map_associate_near (lanefront_map_near.hip), made by its first call
     std::unique_ptr<lf::MapPruneState> prune;     // lf_map_prune (lanefront_map_prune.hip), made by its first call
     std::unique_ptr<lf::MapRenderState> render;   // lf_map_render / lf_map_bounds (lanefront_map_render.hip), made by their first call
     std::unique_ptr<lf::MapCameraState> camera;   // lf_map_render_camera (lanefront_map_camera.hip), likewise
@@ -84,6 +96,8 @@ constexpr int kMapAlignStage = LF_MAP_N_STAGES;
 constexpr int kMapSmoothStage = LF_MAP_N_STAGES + 1;
 constexpr int kMapLocalizeStage = LF_MAP_N_STAGES + 2;
 constexpr int kMapPruneStage = LF_MAP_N_STAGES + 3;
+constexpr int kMapNearIndexStage = LF_MAP_N_STAGES + 4;
+constexpr int kMapNearQueryStage = LF_MAP_N_STAGES + 5;
 
 // ---- lanefront_map.hip's sequencing, for the translation units of the pose solvers
 // make the host mirror current: wait for the copy queued behind the last update (block = false: only look); a failing update the
@@ -96,6 +110,11 @@ int release_handle(lf_map* m, lf_handle* h);      // the handle's later work wai
 int update_blocks(lf_map* m, const uint8_t* blocks, int n_blocks, int block_rows, int force_append, long long rows_hint = -1);
 // one stage of the map's clock since the previous call; resets it (the three lf_map_*_timing exports)
 int take_stage(lf_map* m, int stage, double* ms, int32_t* launches);
+
+// ---- a step's association (lanefront_map_near.hip): lf_map_associate of segs->code / segs->color, or, while lf_map_set_near holds a
+// configuration, lf_map_associate_near's rule with frame_pose (null: +0).  Device arrays; who: the exported call, for the error text
+int associate_for_step(lf_map* m, lf_handle* h, const char* who, const lf_segments* segs, int n, int n_frames, const double* frame_pose,
+                       int32_t* idx, float* dist);
 
 // ---- the pose solvers' front end (lanefront_map_align.hip), shared by lf_map_align, lf_map_smooth and lf_map_localize
 // what the three calls check alike; LF_ERR_BAD_ARG with the reason in the map's error text, or LF_OK; nothing is touched.
@@ -118,8 +137,9 @@ int upload_prior_pose(lf_map* m, const double* pose, int n_frames, const double*
 
 // ---- the steps that solve between association and update (lf_map_step_aligned, lf_map_step_smoothed) and the host forms
 // associate, queue the solver (it leaves x, y, cos, sin per frame in m->pose), pack the block with those poses, update the map.
-// who: the exported call, for the error text
-int step_solved(lf_map* m, lf_handle* h, const char* who, const lf_segments* segs, int n, int n_frames, int step, int32_t* idx, float* dist,
+// who: the exported call, for the error text; frame_pose: the call's prior poses, for an association gated by them
+int step_solved(lf_map* m, lf_handle* h, const char* who, const lf_segments* segs, int n, int n_frames, const double* frame_pose, int step,
+                int32_t* idx, float* dist,
                 const std::function<int(const ma::Batch&)>& queue_solver);
 // a step's host form: frame_offset, code, color, keep and ground (those present) go up, device_form runs on the copies with the
 // staged idx and dist, idx and dist come down and the stream is waited for

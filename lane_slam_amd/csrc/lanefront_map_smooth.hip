@@ -107,7 +107,7 @@ extern "C" int lf_map_step_smoothed(lf_map* m, lf_handle* h, const lf_segments* 
     if (!m) return LF_ERR_NOT_INITIALISED;
     int rc;
     if ((rc = check_call(m, "lf_map_step_smoothed", segs, n, n_frames, idx, frame_pose, chain_offset, n_chains, cfg, results)) != LF_OK) return rc;
-    rc = step_solved(m, h, "lf_map_step_smoothed", segs, n, n_frames, step, idx, dist,
+    rc = step_solved(m, h, "lf_map_step_smoothed", segs, n, n_frames, frame_pose, step, idx, dist,
                      [&](const ma::Batch& b) { return queue_smooth(m, b, frame_pose, chain_offset, n_chains, cfg); });
     if (rc != LF_OK) return rc;
     return fetch_smoothed(m, n_frames, n_chains, results, chain_status);

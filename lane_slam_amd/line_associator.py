@@ -337,6 +337,56 @@ class LineAssociator(object):
         """(ms, launches) of the prunes since the previous call (needs set_profiling(True)); one launch is one prune."""
         return self._stage_timing(self.lib.lf_map_prune_timing)
 
+    # ------------------------------------------------------------------ association gated by the prior pose (lf_map_associate_near)
+    def near_config(self, **overrides):
+        """The library's default `_lib.LfNearConfig` (lf_map_near_default_config) with the overrides applied: radius, max_offset,
+        max_sin, min_hits."""
+        return self._config("near_config", _lib.LfNearConfig, self.lib.lf_map_near_default_config, overrides)
+
+    def associate_near(self, seg, poses=None, config=None, counts=False):
+        """Associate the segments of a host `Segments` block with the map entries NEAR them (lf_map_associate_near): poses
+        (n_frames, 3) map -> duck (x, y, theta) per frame put the segments into the map frame (None: they are in it already);
+        seg's frame_offset, code and ground are read, color when the map gates by colour.  Returns (idx, dist) as `associate`
+        does; counts=True: (idx, dist, n_near), n_near the candidates each segment had.  The map is not changed."""
+        n, n_frames = int(seg.n), len(seg.frame_offset) - 1
+        keep_alive, pp = self._poses(poses, n_frames)
+        s, alive = self._host_segs(seg, ("frame_offset", "code", "color", "ground"))
+        config = self.near_config() if config is None else config
+        idx, dist = np.empty(n, np.int32), np.empty(n, np.float32)
+        near = np.empty(n, np.int32) if counts else None
+        self._check(self.lib.lf_map_associate_near(self.m, None, ctypes.byref(s), n, n_frames, pp, ctypes.byref(config), idx.ctypes.data,
+                                                   dist.ctypes.data, None if near is None else near.ctypes.data, 0))
+        return (idx, dist, near) if counts else (idx, dist)
+
+    def associate_near_device(self, fe, out_ptrs, n, n_frames, idx_ptr, dist_ptr, poses=None, config=None, n_near_ptr=None):
+        """`associate_near` for a batch that is resident on the device (out_ptrs as for step_device; idx_ptr, dist_ptr and
+        n_near_ptr device arrays of n values, n_near_ptr None: not wanted); queued on the map's stream."""
+        keep_alive, pp = self._poses(poses, int(n_frames))
+        config = self.near_config() if config is None else config
+        self._check(self.lib.lf_map_associate_near(self.m, fe.h if fe is not None else None, ctypes.byref(self._segs(out_ptrs)), int(n),
+                                                   int(n_frames), pp, ctypes.byref(config), int(idx_ptr), int(dist_ptr),
+                                                   int(n_near_ptr) if n_near_ptr else None, 1))
+
+    def set_near(self, config):
+        """While an `_lib.LfNearConfig` is set, `step` and `step_device` (plain, align=, smooth=) associate by `associate_near`'s
+        rule with the step's poses in place of `associate`; None: off, the default (lf_map_set_near)."""
+        self._check(self.lib.lf_map_set_near(self.m, None if config is None else ctypes.byref(config)))
+
+    def get_near(self):
+        """The `_lib.LfNearConfig` that `set_near` holds, or None."""
+        c = _lib.LfNearConfig()
+        rc = self.lib.lf_map_get_near(self.m, ctypes.byref(c))
+        if rc < 0:
+            self._check(rc)
+        return c if rc == 1 else None
+
+    def near_timing(self):
+        """{'index': (ms, launches), 'query': (ms, launches)} of the gated associations since the previous call (needs
+        set_profiling(True)); one launch of 'index' is one build of the hash grid, all its kernels."""
+        ms, ln = (ctypes.c_double * 2)(), (ctypes.c_int32 * 2)()
+        self._check(self.lib.lf_map_near_timing(self.m, ms, ln))
+        return {"index": (ms[0], ln[0]), "query": (ms[1], ln[1])}
+
     @staticmethod
     def carry(poses, last_odometry, last_corrected):
         """The next batch's odometry poses (n, 3) with the previous batch's correction applied: the rigid motion that takes

@@ -6,6 +6,7 @@ wire bodies.  The first batch is checked against the oracle (pixels, segments, m
 
     python tools/replay_demo.py [--frames 1024] [--batch 128] [--threads 32] [--geometry fullres|parity] [--map-jpeg map.jpg]
                                 [--overlay-jpeg DIR] [--align | --smooth | --localize] [--prune EVERY[:min_hits[:age]]]
+                                [--near RADIUS[:max_offset[:max_sin]]]
 
 --map-jpeg writes the final map as the reference's README shows it (show_map's coloured segments seen from above, lf_map_render
 fitted to the map) as a JPEG: rendered and encoded on the device, only the file's bytes cross the bus.
@@ -15,6 +16,10 @@ map's entries are in the robot frame) and is encoded on the device; the files go
 --prune EVERY[:min_hits[:age]] culls the map every EVERY steps (lf_map_prune): entries with fewer than min_hits hits (default 2) that
 were last seen more than `age` steps ago (default 8) go, and so does every entry that a better one of its colour covers within 0.02 m,
 show_map's marker width; the seeded entries stay.  Each prune prints its result line.
+--near RADIUS[:max_offset[:max_sin]] gates every step's association by the frames' poses (lf_map_set_near: only entries whose
+midpoint lies within RADIUS metres of the segment's are looked at; max_offset and max_sin default to the library's).  At the end it
+prints the matched share of segments and the mean number of candidates per segment (n_near), and under --align the share of frames
+whose status is `ok`, and the endpoints they used, with the gate and, from a second map fed the same stream, without it.
 """
 import argparse, io, os, sys, time
 import numpy as np
@@ -51,7 +56,16 @@ mode.add_argument("--align", action="store_true",
 ap.add_argument("--prune", default=None, metavar="EVERY[:min_hits[:age]]",
                 help="prune the map every EVERY steps: weak rule min_hits (default 2) for entries last seen more than age (default 8) steps "
                      "ago, cover rule at 0.02 m; prints each result")
+ap.add_argument("--near", default=None, metavar="RADIUS[:max_offset[:max_sin]]",
+                help="gate every step's association by the frames' poses (lf_map_set_near); prints the matched share and the mean n_near, "
+                     "and under --align the share of ok frames with and without the gate")
 args = ap.parse_args()
+near_fields = None
+if args.near:
+    parts = [float(v) for v in args.near.split(":")]
+    if not 1 <= len(parts) <= 3:
+        ap.error("--near takes RADIUS[:max_offset[:max_sin]]")
+    near_fields = dict(zip(("radius", "max_offset", "max_sin"), parts))
 prune_every, prune_min_hits, prune_age = 0, 2, 8
 if args.prune:
     parts = [int(v) for v in args.prune.split(":")]
@@ -86,13 +100,23 @@ for f in (0, B // 2, B - 1):
     s = seg.frame(f)
     assert s.n == r["n"] and np.array_equal(s.lines, r["lines"]) and np.array_equal(s.keep, r["keep"]) and np.array_equal(s.code, r["code"])
 idx, dist = live.associate(seg.code, seg.color)
-oi, od = o.match(seg.code[:200], live.fetch(0, live.state()["size"])["code"])
+oi, od, _ = o.match_mih(seg.code[:200], live.fetch(0, live.state()["size"])["code"])     # the map's default tie rule is the reference's
 assert np.array_equal(idx[:200], oi) and np.array_equal(dist[:200], od)
 bodies, off = sm.serialize_segments(fe, seg, sm.FILTERED)
 assert sm.split_segment_list(sm.segment_list_message(sm.header_bytes(0, 0, 0, "cam"), bodies[off[0]:off[1]]))[5].shape[0] == int(seg.keep[seg.frame_offset[0]:seg.frame_offset[1]].sum())
 print("first batch verified against the oracle: %d segments in %d frames, %d kept" % (seg.n, B, int(seg.keep.sum())))
 
 # ---- replay
+near_cfg = shadow = None
+if near_fields:
+    near_cfg = live.near_config(**near_fields)
+    live.set_near(near_cfg)
+    if args.align:
+        # the same stream into a second map without the gate, for the share of ok frames on both sides
+        shadow = LineAssociator(capacity=args.map + 65536, policy="append", kept_only=True)
+        shadow.seed(synth.random_codes(args.map, 1234))
+n_near_sum = 0
+ok_frames, used_endpoints, all_frames = [0, 0], [0, 0], 0
 t0 = time.perf_counter()
 n_seg = n_kept = n_matched = wire = 0
 last_odometry = last_corrected = (0.0, 0.0, 0.0)
@@ -105,6 +129,14 @@ for b0 in range(0, args.frames - B + 1, B):
         dd = torch.zeros(seg.n, dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()
         ptrs = {k: v.data_ptr() for k, v in d.items()}
+        if near_cfg is not None:
+            # the candidates per segment against the map as this step finds it (the step's own association does not report them)
+            dn = torch.zeros(seg.n, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            pr = LineAssociator.carry(np.zeros((B, 3)), last_odometry, last_corrected) if args.smooth else None
+            live.associate_near_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), pr, near_cfg, dn.data_ptr())
+            live.synchronize()
+            n_near_sum += int(dn.sum().item())
         if args.smooth:
             # (the replay has no odometry: every pose is the identity before the previous batch's correction is carried into it; a
             # chain that finds nothing to hold on to is DEGENERATE and keeps its poses)
@@ -131,6 +163,16 @@ for b0 in range(0, args.frames - B + 1, B):
                                    align=live.align_config())[3]
             counts = np.bincount(res["status"], minlength=4)
             print("batch %d aligned: %s" % (b0 // B, ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, counts))))
+            all_frames += B
+            ok_frames[0] += int(counts[0]); used_endpoints[0] += int(res["n_used"][res["status"] == 0].sum())
+            if shadow is not None:
+                si = torch.zeros(seg.n, dtype=torch.int32, device="cuda")
+                sd = torch.zeros(seg.n, dtype=torch.float32, device="cuda")
+                torch.cuda.synchronize()
+                sres = shadow.step_device(None, ptrs, seg.n, B, si.data_ptr(), sd.data_ptr(), poses=np.zeros((B, 3)), step=b0 // B,
+                                          align=shadow.align_config())[3]
+                shadow.synchronize()
+                ok_frames[1] += int((sres["status"] == 0).sum()); used_endpoints[1] += int(sres["n_used"][sres["status"] == 0].sum())
         else:
             live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), step=b0 // B)
         live.synchronize()
@@ -148,6 +190,14 @@ dt = time.perf_counter() - t0
 nb = (args.frames // B) * B
 print("replayed %d frames in %.2f s: %.0f frames/s (synchronous, host-resident results, one handle); %d segments, %d kept, "
       "%d matched within 128 bits, map %d codes, %.1f MB of SegmentList bodies" % (nb, dt, nb / dt, n_seg, n_kept, n_matched, live.state()["size"], wire / 1e6))
+if near_cfg is not None:
+    print("near (radius %g m, max_offset %g m, max_sin %g): %.1f %% of the segments matched, %.2f candidates per segment (mean n_near)"
+          % (near_cfg.radius, near_cfg.max_offset, near_cfg.max_sin, 100.0 * n_matched / max(n_seg, 1), n_near_sum / max(n_seg, 1)))
+    if args.align and all_frames:
+        print("aligned frames that end ok: %.1f %% with the gate (%d endpoints used), %.1f %% without it (%d endpoints used), of %d frames"
+              % (100.0 * ok_frames[0] / all_frames, used_endpoints[0], 100.0 * ok_frames[1] / all_frames, used_endpoints[1], all_frames))
+elif args.align and all_frames:
+    print("aligned frames that end ok: %.1f %% (%d endpoints used), of %d frames" % (100.0 * ok_frames[0] / all_frames, used_endpoints[0], all_frames))
 
 if args.map_jpeg:
     side = args.map_size
