@@ -24,6 +24,7 @@
 // cut into `subs` pieces of whole tile groups so that the few pieces still fill the chip.
 #include "common.h"
 #include "mih_rank.h"
+#include "scan.h"
 
 namespace lf {
 
@@ -171,9 +172,7 @@ __device__ __forceinline__ void assoc_ties_body(const uint8_t* __restrict__ q, c
             for (int p0 = 0; p0 < n_pieces; p0 += 256) {
                 const int p = p0 + threadIdx.x;
                 const int v = p < n_pieces ? cnt[p] : 0;
-                int inc = v;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) { const int n = __shfl_up(inc, d); if (lane >= d) inc += n; }
+                const int inc = wave_incl_scan(v, lane);
                 if (lane == 63) s_wsum[wave] = inc;
                 __syncthreads();
                 int base = carry;

@@ -14,6 +14,7 @@
 // per-word counts places the survivors after those of earlier words, and the running base carries over to the next 256 words.
 // counts[pc] is the full count; only the first cap_lines go to the slots (the rest is LF_ERR_CAPACITY in lf_wait).
 #include "common.h"
+#include "scan.h"
 
 namespace lf {
 
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(kDenseThreads) void k_dense(int Hc, int W, int Ww, 
 {
     __shared__ int wsum[kDenseThreads / 64];
     const int pc = blockIdx.x, f = pc / 3;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const size_t plane = (size_t)Hc * Ww;
     const uint32_t* E = strong + (size_t)f * plane;
     const uint32_t* M = maskbits + (size_t)pc * plane;
@@ -90,18 +91,9 @@ __global__ __launch_bounds__(kDenseThreads) void k_dense(int Hc, int W, int Ww, 
             }
         }
         // exclusive scan of the per-word counts over the workgroup
-        const int c = __popc(keep);
-        int inc = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int off = base, total = 0;
-#pragma unroll
-        for (int w = 0; w < kDenseThreads / 64; ++w) { const int v = wsum[w]; off += w < wave ? v : 0; total += v; }
-        __syncthreads();                                        // (wsum is rewritten by the next chunk)
+        int total;
+        int pos = base + wg_excl_scan<kDenseThreads>((int)__popc(keep), wsum, &total);
         base += total;
-        int pos = off + inc - c;
         while (keep && pos < cap_lines) {
             const int b = __builtin_ctz(keep);
             keep &= keep - 1u;

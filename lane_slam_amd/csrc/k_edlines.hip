@@ -34,6 +34,7 @@
 //                 octaves below, lanes = lines), orders KeyLines by (class, octave) and fills the output rows.
 #include "common.h"
 #include "k_edlines_types.h"
+#include "scan.h"
 
 namespace lf {
 
@@ -1003,9 +1004,7 @@ __global__ __launch_bounds__(ED_THREADS) void k_ed_detect(EdAll all, EdFitParams
         const int wi = start + tid;
         const uint32_t word = wi < n_cwords ? flags[wi] : 0u;
         const int c = __popc(word);
-        int incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+        const int incl = wave_incl_scan(c, lane);
         if (lane == 63) s_wave_count[wave] = incl;
         __syncthreads();
         int off = s_base;
@@ -1297,9 +1296,7 @@ __global__ __launch_bounds__(ED_THREADS) void k_ed_detect(EdAll all, EdFitParams
         for (int e0i = 0; e0i < n_edges; e0i += 64) {
             const int e = e0i + lane;
             const int c = e < n_edges ? e_kept[e] : 0;
-            int incl = c;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+            const int incl = wave_incl_scan(c, lane);
             const int base = run + incl - c;
             bool over = false;
             if (e < n_edges) {

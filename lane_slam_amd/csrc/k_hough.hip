@@ -25,6 +25,7 @@
 // live in LDS.
 #include <math.h>
 #include "k_hough.h"
+#include "scan.h"
 
 namespace lf {
 
@@ -149,9 +150,7 @@ __global__ __launch_bounds__(64) void k_hough(HoughParams p, int n_problems, con
                 const int w = w0 + lane;
                 uint32_t v = w < nw ? mask[w] : 0u;
                 const int c = __popc(v);
-                int inc = c;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
+                const int inc = wave_incl_scan(c, lane);
                 int k = base + inc - c;
                 const int i = w / Ww, j0 = (w - i * Ww) * 32;
                 while (v) { const int b = __builtin_ctz(v); v &= v - 1; pts[k++] = ((uint32_t)i << 16) | (uint32_t)(j0 + b); }

@@ -9,6 +9,7 @@
 // Integer arithmetic only, in the 32-bit widths libjpeg uses.
 #include "common.h"
 #include "k_jenc.h"
+#include "scan.h"
 
 namespace lf {
 namespace jenc {
@@ -219,40 +220,11 @@ __global__ __launch_bounds__(256) void k_je_size(const int16_t* __restrict__ coe
     dcdiff[(size_t)f * g.blocks + b] = (int16_t)diff;
 }
 
-// exclusive scan of v over the workgroup (blockDim.x a multiple of 64, at most 1024); *total: the sum
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* sWave, uint32_t* total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
-    __syncthreads();                                  // (sWave may still be read from the call before)
-    if (lane == 63) sWave[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0, sum = 0;
-    for (int k = 0; k < n_waves; ++k) {
-        if (k == wave) base = sum;
-        sum += sWave[k];
-    }
-    *total = sum;
-    return base + inc - v;
-}
-
 __global__ __launch_bounds__(1024) void k_je_scan_bits(uint32_t* __restrict__ bits, Geom g, uint32_t* __restrict__ total_bits)
 {
     __shared__ uint32_t sWave[16];
     uint32_t* v = bits + (size_t)blockIdx.x * g.blocks;
-    uint32_t carry = 0;
-    for (int base = 0; base < g.blocks; base += 1024) {
-        const int k = base + threadIdx.x;
-        uint32_t total;
-        const uint32_t e = block_excl_scan(k < g.blocks ? v[k] : 0u, sWave, &total);
-        if (k < g.blocks) v[k] = carry + e;
-        carry += total;
-    }
+    const uint32_t carry = wg_scan_turns<1024>(g.blocks, sWave, [&](int k) { return v[k]; }, [&](int k, uint32_t e) { v[k] = e; });
     if (threadIdx.x == 0) total_bits[blockIdx.x] = min(carry, (uint32_t)g.words * 32u);      // (never more: kBlockBytesMax)
 }
 
@@ -318,7 +290,7 @@ __global__ __launch_bounds__(256) void k_je_ff_count(const uint32_t* __restrict_
 #pragma unroll
     for (int k = 0; k < 16; ++k) cnt += k < n && by[k] == 0xFF;
     uint32_t sum;
-    (void)block_excl_scan(cnt, sWave, &sum);
+    (void)wg_excl_scan<256>(cnt, sWave, &sum);
     if (threadIdx.x == 0) ff[(size_t)f * g.chunks + blockIdx.x] = sum;
 }
 
@@ -330,14 +302,7 @@ __global__ __launch_bounds__(256) void k_je_ff_scan(const uint32_t* __restrict__
     const uint32_t n_bytes = (total_bits[f] + 7) >> 3;
     const int used = (int)((n_bytes + kChunkBytes - 1) / kChunkBytes);
     uint32_t* v = ff + (size_t)f * g.chunks;
-    uint32_t carry = 0;
-    for (int base = 0; base < used; base += 256) {
-        const int k = base + threadIdx.x;
-        uint32_t total;
-        const uint32_t e = block_excl_scan(k < used ? v[k] : 0u, sWave, &total);
-        if (k < used) v[k] = carry + e;
-        carry += total;
-    }
+    const uint32_t carry = wg_scan_turns<256>(used, sWave, [&](int k) { return v[k]; }, [&](int k, uint32_t e) { v[k] = e; });
     if (threadIdx.x == 0) {
         const unsigned long long size = (unsigned long long)tab->header_len + n_bytes + carry + 2;
         out_size[f] = size <= out_stride ? (uint32_t)size : 0u;
@@ -365,7 +330,7 @@ __global__ __launch_bounds__(256) void k_je_write(const uint32_t* __restrict__ b
 #pragma unroll
     for (int k = 0; k < 16; ++k) cnt += k < n && by[k] == 0xFF;
     uint32_t sum;
-    const uint32_t before = block_excl_scan(cnt, sWave, &sum);
+    const uint32_t before = wg_excl_scan<256>(cnt, sWave, &sum);
     // (size fits out_stride, and header + bytes + stuffing + EOI == size: every store below stays inside the frame's slot)
     uint8_t* p = dst + hl + first + ff[(size_t)f * g.chunks + blockIdx.x] + before;
 #pragma unroll

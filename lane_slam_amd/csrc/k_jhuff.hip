@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "jpeg_entropy.h"
+#include "scan.h"
 
 namespace lf {
 
@@ -582,9 +583,7 @@ __device__ __forceinline__ void jh_frame(JhShared& sh, jpeg::DevFrame& F, JhInfo
     for (int base = 0; base < n_sub; base += JH_T) {
         const int u = base + t;
         const int v = u < n_sub ? (int)u_nblk[u] : 0;
-        int inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int a = __shfl_up(inc, d); if (lane >= d) inc += a; }
+        const int inc = wave_incl_scan(v, lane);
         if (lane == 63) s_wsum[wave] = inc;
         __syncthreads();
         int off = s_carry;

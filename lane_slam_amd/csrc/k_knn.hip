@@ -13,6 +13,7 @@
 // ONE LANE PER QUERY, the query code in eight registers, map codes staged through LDS 256 at a time (every lane reads the
 // same address: a broadcast), XOR + popcount.  11 k queries x 66 k map codes = 1.2 ms; exact integer arithmetic.
 #include "common.h"
+#include "scan.h"
 #include "mih_rank.h"
 
 namespace lf {
@@ -196,26 +197,8 @@ __global__ void k_radius_scan(int nq, int max_distance, int32_t* __restrict__ hi
 __global__ __launch_bounds__(1024) void k_radius_offsets(int nq, const int32_t* __restrict__ count, int32_t* __restrict__ offsets, int* __restrict__ total)
 {
     __shared__ int wsum[16];
-    __shared__ int carry;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nq; base += 1024) {
-        const int i = base + t;
-        const int v = i < nq ? count[i] : 0;
-        int inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int off = carry;
-        for (int w = 0; w < wave; ++w) off += wsum[w];
-        if (i < nq) offsets[i] = off + inc - v;
-        __syncthreads();
-        if (t == 1023) carry = off + inc;
-        __syncthreads();
-    }
-    if (t == 0) { offsets[nq] = carry; *total = carry; }
+    const int sum = wg_scan_turns<1024>(nq, wsum, [&](int i) { return count[i]; }, [&](int i, int ex) { offsets[i] = ex; });
+    if (threadIdx.x == 0) { offsets[nq] = sum; *total = sum; }
 }
 
 // pass 2: every match goes to the cursor of its (query, distance) bucket: distance ascending, index ascending inside

@@ -25,6 +25,7 @@
 #include "common.h"
 #include <type_traits>
 #include "lsd_bitplane.h"
+#include "scan.h"
 
 namespace lf {
 using std::max;
@@ -46,16 +47,6 @@ constexpr int OT = LF_ORDER_THREADS;          // threads of k_lsd_order
 constexpr int OBT = LF_ORDER_BM_THREADS;      // threads of k_lsd_order_bm
 constexpr int NB = 16;           // buckets per pass of k_lsd_order (4-bit digits; [16][512] u32 = 32 KB LDS)
 constexpr int LDS_ITEMS = 8192;  // problems up to this many defined pixels are ordered entirely in LDS (2 x 32 KB, dynamic)
-
-__device__ __forceinline__ int wave_incl_scan(int v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        int n = __shfl_up(v, d);
-        if (lane >= d) v += n;
-    }
-    return v;
-}
 
 template <typename T, int NB = 16, int NT = OT>
 __device__ __forceinline__ void radix_pass(const T* __restrict__ src, T* __restrict__ dst, int n, int shift,

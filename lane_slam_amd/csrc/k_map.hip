@@ -25,6 +25,7 @@
 //           whatever is there, including an entry refreshed in pass 1) or at size + rank while it fits (FULL_ERROR)
 //           (parallel: rank = exclusive scan of the append flags)
 #include "common.h"
+#include "scan.h"
 
 namespace lf {
 
@@ -155,31 +156,14 @@ __global__ __launch_bounds__(kMapWg) void k_map_plan(MapDev m, const uint8_t* __
                                                    int* __restrict__ wg_count)
 {
     __shared__ int wave_sum[kMapWg / 64];
-    __shared__ int carry_sh;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry_sh = 0;
-    __syncthreads();
-    for (int start = 0; start < n_wg; start += kMapWg) {
-        const int i = start + tid;
-        const int v = i < n_wg ? wg_count[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        int off = carry_sh;
-        for (int w = 0; w < wave; ++w) off += wave_sum[w];
-        if (i < n_wg) wg_count[i] = off + incl - v;
-        __syncthreads();
-        if (tid == kMapWg - 1) carry_sh = off + incl;
-        __syncthreads();
-    }
+    const int tid = threadIdx.x;
+    const int n_app = wg_scan_turns<kMapWg>(n_wg, wave_sum, [&](int i) { return wg_count[i]; }, [&](int i, int ex) { wg_count[i] = ex; });
     if (tid == 0) {
         // every block of one update carries the same step number; block 0's is taken
         const uint32_t* hd = reinterpret_cast<const uint32_t*>(blocks);
         const int step = n_blocks > 0 ? (int)hd[2] : 0;
         const int size0 = m.state[0], head0 = m.state[1];
-        const int n_app = carry_sh, n_ref = m.state[9];
+        const int n_ref = m.state[9];
         int new_size, new_head, flags = m.state[10];
         if (m.when_full == LF_MAP_RING) {
             const long long sz = (long long)size0 + n_app;

@@ -15,6 +15,7 @@
 //                  writes each output with a plain vector store.
 #include "k_map_pairs.h"
 #include "k_map_near.h"
+#include "scan.h"
 
 namespace lf {
 namespace nr {
@@ -47,28 +48,20 @@ __global__ __launch_bounds__(kWg) void k_near_bin(MapDevice md, double cell, Ind
 __global__ __launch_bounds__(kScanWg) void k_near_scan(Index ix)
 {
     __shared__ int wave_sum[kScanWg / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int buckets = (int)ix.mask + 1;          // a multiple of kMinBuckets = 4 kScanWg
     int carry = 0;                                 // the same in every lane
     for (int first = 0; first < buckets; first += kMinBuckets) {
-        const int i = first + 4 * tid;
+        const int i = first + 4 * (int)threadIdx.x;
         const int4 v = *reinterpret_cast<const int4*>(ix.start + i);
-        const int mine = (v.x + v.y) + (v.z + v.w);
-        int incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        int off = carry, all = 0;
-        for (int w = 0; w < kScanWg / 64; ++w) { const int n = wave_sum[w]; if (w < wave) off += n; all += n; }
+        int all;
         int4 o;
-        o.x = off + incl - mine; o.y = o.x + v.x; o.z = o.y + v.y; o.w = o.z + v.z;
+        o.x = carry + wg_excl_scan<kScanWg>((v.x + v.y) + (v.z + v.w), wave_sum, &all);
+        o.y = o.x + v.x; o.z = o.y + v.y; o.w = o.z + v.z;
         *reinterpret_cast<int4*>(ix.start + i) = o;
         *reinterpret_cast<int4*>(ix.cursor + i) = o;
         carry += all;
-        __syncthreads();                           // wave_sum is written again in the next turn
     }
-    if (tid == 0) ix.start[buckets] = carry;
+    if (threadIdx.x == 0) ix.start[buckets] = carry;
 }
 
 __global__ __launch_bounds__(kWg) void k_near_fill(MapDevice md, double cell, Index ix)

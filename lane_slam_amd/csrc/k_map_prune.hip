@@ -15,6 +15,7 @@
 //   k_prune_scatter  32 threads per old row: rows below the new size come back from the copies with their operands re-expanded
 //                    (assoc_map_write_row, what k_map_apply uses), the vacated rows are zeroed; one thread writes state[0..1]
 #include "k_map_prune.h"
+#include "scan.h"
 
 namespace lf {
 namespace pr {
@@ -56,26 +57,8 @@ __global__ __launch_bounds__(kWg) void k_prune_rank(int size, const uint8_t* __r
 __global__ __launch_bounds__(kWg) void k_prune_scan(int n_wg, int* __restrict__ wg, int* __restrict__ total)
 {
     __shared__ int wave_sum[kWg / 64];
-    __shared__ int carry_sh;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry_sh = 0;
-    __syncthreads();
-    for (int first = 0; first < n_wg; first += kWg) {
-        const int i = first + tid;
-        const int v = i < n_wg ? wg[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        int off = carry_sh;
-        for (int w = 0; w < wave; ++w) off += wave_sum[w];
-        if (i < n_wg) wg[i] = off + incl - v;
-        __syncthreads();
-        if (tid == kWg - 1) carry_sh = off + incl;
-        __syncthreads();
-    }
-    if (tid == 0) *total = carry_sh;
+    const int sum = wg_scan_turns<kWg>(n_wg, wave_sum, [&](int i) { return wg[i]; }, [&](int i, int ex) { wg[i] = ex; });
+    if (threadIdx.x == 0) *total = sum;
 }
 
 __global__ __launch_bounds__(kWg) void k_prune_records(lf_prune_config c, MapDevice m, int size, int start, const int* __restrict__ rank,

@@ -4,6 +4,7 @@
 // order in which lanes arrive: a maximum has none.
 #pragma once
 #include "k_map_render.h"
+#include "scan.h"
 
 namespace lf {
 namespace mr {
@@ -141,8 +142,7 @@ __device__ inline void paint_records(unsigned long long* plane, unsigned n_rec, 
             long long ia, ib;
             if (step_range(L, (long long)(L.xmajor ? c0 : r0) - h1, (long long)(L.xmajor ? c1 : r1) + h0, ia, ib)) { cnt = (int)(ib - ia + 1); i0 = (int)ia; }
         }
-        int inc = cnt;
-        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
+        const int inc = wave_incl_scan(cnt, lane);
         const int total = __shfl(inc, 63);
         for (int first = 0; first < total; first += 64) {
             const int item = first + lane;

@@ -70,26 +70,18 @@ __global__ void __launch_bounds__(kWg) k_mr_project(const View v, const int capa
 __global__ void __launch_bounds__(1024) k_mr_scan(const int n_tiles, const unsigned* __restrict__ tile_count, unsigned* __restrict__ tile_start,
                                                   unsigned* __restrict__ cursor, int* __restrict__ counters)
 {
-    __shared__ unsigned long long s_sum[1024];
+    __shared__ unsigned long long wave_sum[16];
     const int t = threadIdx.x, per = (n_tiles + 1023) / 1024, a = t * per;
-    unsigned long long sum = 0;
+    unsigned long long sum = 0, total;
     for (int k = 0; k < per; ++k) if (a + k < n_tiles) sum += tile_count[a + k];
-    s_sum[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const unsigned long long o = t >= d ? s_sum[t - d] : 0ull;
-        __syncthreads();
-        s_sum[t] += o;
-        __syncthreads();
-    }
-    unsigned long long run = s_sum[t] - sum;
+    unsigned long long run = wg_excl_scan<1024>(sum, wave_sum, &total);
     for (int k = 0; k < per; ++k)
         if (a + k < n_tiles) {
             tile_start[a + k] = (unsigned)run;       // (a total that does not fit is refused by the host before these are used)
             cursor[a + k] = (unsigned)run;
             run += tile_count[a + k];
         }
-    if (t == 1023) { counters[2] = (int)(unsigned)(s_sum[t] & 0xffffffffull); counters[3] = (int)(unsigned)(s_sum[t] >> 32); }
+    if (t == 0) { counters[2] = (int)(unsigned)(total & 0xffffffffull); counters[3] = (int)(unsigned)(total >> 32); }
 }
 
 __global__ void __launch_bounds__(kWg) k_mr_bin(const View v, const long long n_lines, const int4* __restrict__ px, unsigned* __restrict__ cursor,

@@ -13,45 +13,28 @@
 #include <limits.h>
 #include "common.h"
 #include "lane_vote.h"
+#include "scan.h"
 
 namespace lf {
+
+constexpr int kSegOffsetsThreads = 256;      // k_seg_offsets' workgroup: its launch and its scan
 
 // writes the batch's BatchStatus (common.h) but for detector_failures and rec_need
 __global__ void k_seg_offsets(int n_frames, int cap_lines, const int* __restrict__ counts, int* __restrict__ seg_offset,
                               int* __restrict__ frame_offset, BatchStatus* __restrict__ status, const int* __restrict__ norder, int cap_small, int cap_medium)
 {
     // single workgroup exclusive scan over n_frames*3 clipped counts
-    __shared__ int carry;
-    __shared__ int wsum[16];
+    __shared__ int wsum[kSegOffsetsThreads / 64];
     const int n = n_frames * 3;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) carry = 0;
-    __syncthreads();
     int ovf = 0;
-    for (int base = 0; base < n; base += blockDim.x) {
-        int i = base + t;
-        int v = 0;
-        if (i < n) {
-            v = counts[i]; if (v > cap_lines) { v = cap_lines; ovf = 1; }
+    const int total = wg_scan_turns<kSegOffsetsThreads>(n, wsum,
+        [&](int i) {
+            int v = counts[i]; if (v > cap_lines) { v = cap_lines; ovf = 1; }
             if (norder) { const int nd = norder[i]; if (nd > cap_small) atomicAdd(&status->over_small, 1); if (nd > cap_medium) atomicAdd(&status->over_medium, 1); atomicMax(&status->max_defined, nd); }
-        }
-        int inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int off = carry;
-        for (int w = 0; w < wave; ++w) off += wsum[w];
-        if (i < n) {
-            int ex = off + inc - v;
-            seg_offset[i] = ex;
-            if (i % 3 == 0) frame_offset[i / 3] = ex;
-        }
-        __syncthreads();
-        if (t == blockDim.x - 1) carry = off + inc;
-        __syncthreads();
-    }
-    if (t == 0) { seg_offset[n] = carry; frame_offset[n_frames] = carry; status->total = carry; }
+            return v;
+        },
+        [&](int i, int ex) { seg_offset[i] = ex; if (i % 3 == 0) frame_offset[i / 3] = ex; });
+    if (threadIdx.x == 0) { seg_offset[n] = total; frame_offset[n_frames] = total; status->total = total; }
     if (ovf) atomicOr(&status->lines_overflow, 1);
 }
 
@@ -59,7 +42,7 @@ void launch_seg_offsets(int n_frames, int cap_lines, const int* counts, int* seg
                         BatchStatus* status, const int* norder, int cap_small, int cap_medium, hipStream_t s)
 {
     // four waves: a 1024-thread workgroup waits for a CU with sixteen free wave slots in a busy pipeline
-    hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(256), 0, s, n_frames, cap_lines, counts, seg_offset,
+    hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(kSegOffsetsThreads), 0, s, n_frames, cap_lines, counts, seg_offset,
                        frame_offset, status, norder, cap_small, cap_medium);
 }
 

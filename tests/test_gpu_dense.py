@@ -112,6 +112,24 @@ def test_batched_path_matches_the_composition(geometry, thr):
     fe.close()
 
 
+# k_dense ranks a problem's survivors over its 32-pixel words, 256 words a chunk: working images of 85 x 96, 64 x 128, 257 x 32 and
+# 171 x 96 pixels below the cutoff are 255, 256, 257 and 513 words (one chunk short of a word, full, carried into a second and a
+# third).  Cluttered frames: survivors in every chunk.
+@pytest.mark.parametrize("rows,cols", [(85, 96), (64, 128), (257, 32), (171, 96)])
+def test_word_counts_around_a_chunk_of_the_rank_scan(rows, cols):
+    cfg = default_config("parity")
+    cfg["img_size"], cfg["top_cutoff"] = [rows + 3, cols], 3
+    frames = np.concatenate([_clutter(cfg, 4, 21), synth.make_batch(2, 21)])
+    want = _want(cfg, frames, 40, describe=False)
+    lines = np.concatenate([w["lines"] for w in want])
+    in_last_word = (np.maximum(lines[:, 1], lines[:, 3]) == rows - 1) & ((lines[:, 0] + lines[:, 2]) / 2 >= cols - 26)
+    assert len(lines) > 400 and in_last_word.any() and (np.minimum(lines[:, 1], lines[:, 3]) <= 6).any()
+    fe = FrontEnd(cfg, max_frames=len(frames), max_lines_per_color=_cap(want))
+    fe.set_detector("dense", _conf(40))
+    _check(fe.process_batch(frames, describe=False), want, describe=False)
+    fe.close()
+
+
 def test_pipelined_handles_equal_the_waiting_call():
     cfg = default_config("parity")
     frames = np.concatenate([synth.make_batch(24, 900), _clutter(cfg, 8, 3)])

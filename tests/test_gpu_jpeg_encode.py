@@ -114,6 +114,19 @@ def test_batch_256_fullres_overlays(fe):
         assert got[i] == want[order[i]], (i,) + _diff(got[i], want[order[i]])
 
 
+# k_je_scan_bits scans a frame's block lengths 1024 a turn, and a frame has six blocks per MCU: 10 MCUs (60 blocks, inside one wave),
+# 170 (1020, the most that one turn holds), 171 (1026, the first to carry into a second turn) and 342 (2052, into a third)
+@pytest.mark.parametrize("rows,cols", [(32, 80), (160, 272), (144, 304), (288, 304)])
+def test_block_counts_around_a_turn_of_the_length_scan(fe, rows, cols):
+    rng = np.random.default_rng(rows * cols)
+    frames = synth.make_batch(2, 60)[:, 100:100 + rows, 200:200 + cols].copy()
+    frames[1, rows // 4:rows // 2, cols // 4:cols // 2] = rng.integers(0, 256, (rows // 2 - rows // 4, cols // 2 - cols // 4, 3), dtype=np.uint8)
+    want = [R.encode(f, 95) for f in frames]
+    got = fe.encode_jpeg_batch(frames)
+    for i in range(2):
+        assert got[i] == want[i], (i,) + _diff(got[i], want[i])
+
+
 def test_batch_32_1080p(fe):
     """32 frames of 1920 x 1080 -- not whole MCUs high: a bottom row of dummy blocks -- equal jpeg_enc_ref, sizes too."""
     rng = np.random.default_rng(5)

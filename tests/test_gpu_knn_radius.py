@@ -93,7 +93,7 @@ def _sweep_case(nq, nm):
     return q, m, planted
 
 
-SWEEP = [(1, 255), (1, 257), (255, 17), (255, 513), (256, 16), (256, 512), (257, 15), (257, 2100), (1023, 1), (1023, 257),
+SWEEP = [(1, 255), (1, 257), (63, 17), (64, 257), (65, 16), (255, 17), (255, 513), (256, 16), (256, 512), (257, 15), (257, 2100), (1023, 1), (1023, 257),
          (1024, 255), (1024, 513), (1025, 1), (1025, 15), (1025, 256), (1025, 2100), (2049, 16), (2049, 255), (2049, 257),
          (2049, 513), (3000, 17), (3000, 512), (3000, 2100)]
 ALL_K = {(1025, 15), (257, 2100), (1025, 256), (256, 16)}          # k = 1 .. 16; nm = 15 is smaller than k = 16
@@ -111,11 +111,11 @@ def test_the_sweep_meets_every_size_on_both_sides_of_the_tile():
 @pytest.mark.parametrize("nq,nm", SWEEP)
 def test_shape_sweep(oracle, fe, nq, nm):
     """Tile (256 codes), workgroup (256 queries) and offsets-chunk (1 024 queries) edges.  radiusMatch at 128 on every shape above 1 024
-    queries: the carry of k_radius_offsets."""
+    queries: the carry of k_radius_offsets; and on the shapes of 63, 64 and 65 queries: its step from one wave to the next."""
     q, m, planted = _sweep_case(nq, nm)
     ref = _Ref(oracle, q, m)
     ks = range(1, 17) if (nq, nm) in ALL_K else (1, 1 + (nq + nm) % 15, 16)
-    radii = (128.0, 9.0) if nq > 1024 else (9.0,)
+    radii = (128.0, 9.0) if nq > 1024 or nq in (63, 64, 65) else (9.0,)
     for rule in RULES:
         fe.set_tie_rule(rule)
         for k in ks:

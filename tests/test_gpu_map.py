@@ -179,6 +179,40 @@ def test_map_update_matches_oracle(policy, when_full, cap):
     a.close()
 
 
+class _HostSegments(object):
+    """one frame's segments as LineAssociator.step reads them"""
+
+    def __init__(self, code, color, ground):
+        self.n = len(color)
+        self.frame_offset = np.array([0, self.n], np.int32)
+        self.code, self.color, self.ground, self.keep = code, color, ground, np.ones(self.n, np.uint8)
+
+
+# k_map_plan adds up the appends of an update's 256-row workgroups, 256 of them a turn: 63, 64 and 65 workgroups (a wave's end),
+# 255, 256 and 257 (a turn's end) and 513 (the carry into a third turn); every update of the tests above is its one-value case.
+# About half the rows are exact copies of map entries (merge distance 0: they refresh), the others append, in no pattern.
+@pytest.mark.parametrize("n", [16128, 16384, 16640, 65280, 65536, 65537, 131073])
+def test_update_sizes_where_the_scan_of_the_append_counts_turns(n):
+    from oracle.oracle import OracleMap
+    rng = np.random.default_rng(n)
+    kw = dict(capacity=n + 64, color_gating=False, max_distance=128, policy="merge", kept_only=False, merge_distance=0)
+    a, o = LineAssociator(**kw), OracleMap(**kw)
+    base = _codes(rng, 64)
+    a.seed(base)
+    o.seed(base)
+    code = _codes(rng, n)
+    copies = rng.random(n) < 0.5
+    code[copies] = base[rng.integers(0, 64, int(copies.sum()))]
+    color, ground = rng.integers(0, 3, n).astype(np.uint8), rng.normal(size=(n, 4))
+    gi, gd = a.step(_HostSegments(code, color, ground), None, 1)
+    oi, od = o.step(code, color, np.ones(n, np.uint8), ground, 1)
+    assert np.array_equal(gi, oi) and np.array_equal(gd, od)
+    _same_map(a, o)
+    st = o.state()
+    assert st["total_refreshed"] == copies.sum() and st["size"] == 64 + n - copies.sum() and n // 3 < copies.sum() < 2 * n // 3
+    a.close()
+
+
 def _upload(torch, dev, c):
     return {"frame_offset": torch.from_numpy(c["frame_offset"]).to(dev), "code": torch.from_numpy(c["code"]).to(dev),
             "color": torch.from_numpy(c["color"]).to(dev), "keep": torch.from_numpy(c["keep"]).to(dev),

@@ -163,6 +163,19 @@ def test_entry_counts(n):
     a.close()
 
 
+def test_more_tiles_than_the_scan_has_lanes(parity_map):
+    """41 frames of 5 x 5 tiles: 1025 tiles, so that k_mr_scan's 1024 lanes take two tiles each and the last tiles' lists start
+    behind every frame before."""
+    a = parity_map
+    rows, cols, n = 300, 290, 41
+    view = parity_view(rows, cols, 0, 2)
+    poses = POSES[np.arange(n) % 3] + np.linspace(0.0, 0.05, n)[:, None]
+    src = random_frames(n, rows, cols, seed=5)
+    img, counts, _ = check(a, view, poses, src)
+    assert all((img[f] != src[f]).any() for f in range(n))
+    assert (-(-rows // 64)) * (-(-cols // 64)) * n == 1025
+
+
 def test_source_and_destination_forms(parity_map):
     a = parity_map
     rows, cols = 95, 81

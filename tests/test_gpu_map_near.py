@@ -115,6 +115,18 @@ def test_sparse_cells_and_table_collisions():
     a.close()
 
 
+# k_near_scan scans the table's buckets 4096 a turn, and the table is the power of two of at least twice the map's size: 2049
+# entries are the first to take two turns, 4097 the first to take four, 8192 fill the table of four.  The entries hash all over the
+# table, so the running sum carried into every later turn decides where three quarters of the segments find their entry.
+@pytest.mark.parametrize("n", [2049, 4097, 8192])
+def test_tables_of_more_than_one_scan_turn(n):
+    m, size, seg = N.sparse_case(seed=9 + n, n=n, ns=256)
+    a = seeded(m, size, cap=n)
+    got = check(a, seg)
+    assert got[2].max() == 1 and 50 < got[2].sum() < 150 and (got[0] >= 0).sum() > 50
+    a.close()
+
+
 @pytest.mark.parametrize("gating", [False, True])
 def test_colour_gating(gating):
     (code, color, ground), seg, poses = N.small_case(21)

@@ -166,6 +166,20 @@ def test_cover_at_the_sizes_where_the_kernel_changes_its_path(n):
     a.close()
 
 
+# k_prune_scan adds up the survivors of the map's 256-row workgroups, 256 of them a turn: 63, 64 and 65 workgroups (a wave's end),
+# 255, 256 and 257 (a turn's end) and 513 (the carry into a third turn); the maps above of up to 256 rows are its one-value case.
+# Seeded entries, the colours 0 and 1 dropped as stale: about half survive, in no pattern.
+@pytest.mark.parametrize("n", [16128, 16384, 16640, 65280, 65536, 65537, 131073])
+def test_sizes_where_the_scan_of_the_workgroup_counts_turns(n):
+    m, _ = P.random_map(n, 7000 + n % 1000)
+    a = LineAssociator(capacity=n, policy="append", kept_only=False, when_full="error")
+    a.seed(m["code"][:n], m["color"][:n], m["ground"][:n])
+    assert a.state()["size"] == n
+    got = check(a, P.FULL_ERROR, stale_before=0, keep_seeded=0, color_mask=0x3)
+    assert n // 3 < got["size_after"] < 2 * n // 3 and got["dropped"]["stale"] == n - got["size_after"]
+    a.close()
+
+
 def test_everything_off_leaves_an_unwrapped_map_alone_and_rotates_a_ring():
     m, n = P.random_map(150, 31, cap=256)
     a = build(m, n, 3, cap=256)

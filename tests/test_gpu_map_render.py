@@ -139,6 +139,26 @@ def test_tile_edges(rows, cols):
     a.close()
 
 
+# k_mr_scan: one workgroup of 1024 lanes, a lane per chunk of ceil(n_tiles / 1024) tiles of 64 x 64 pixels.  1, 63, 64 and 65 tiles
+# (a wave's end); 1023, 1024 and 1025 (the last lane, then two tiles a lane); 2050 = 41 x 50 (three a lane: 2049 = 3 x 683 has no
+# view, a side is at most 128 tiles).  Short lines all over the view and in its first, its last and a middle tile: the lists of a
+# tile hold the right lines only where every start before it is right.
+@pytest.mark.parametrize("tiles_down,tiles_across", [(1, 1), (7, 9), (8, 8), (5, 13), (33, 31), (32, 32), (25, 41), (41, 50)])
+def test_tile_counts(tiles_down, tiles_across):
+    rows, cols = 64 * tiles_down - 14, 64 * tiles_across - 9
+    rng = np.random.default_rng(tiles_down * 128 + tiles_across)
+    n = 300
+    u, v = rng.integers(-20, cols + 20, n), rng.integers(-20, rows + 20, n)
+    ends = np.stack([u, v, u + rng.integers(-40, 41, n), v + rng.integers(-40, 41, n)], axis=1)
+    ends[:3] = [(2, 3, 30, 20), (cols - 3, rows - 2, cols - 25, rows - 30), (cols // 2, rows // 2, cols // 2 + 35, rows // 2 - 20)]
+    g = np.array([seg(rows, *e) for e in ends.tolist()])
+    a = make_map([], capacity=n, seed=(g, rng.integers(0, 3, n)))
+    view = pix_view(rows, cols, 3)
+    img = check(a, view, device_too=False)
+    assert all((img[r, c] != 48).any() for r, c in ((3, 2), (rows - 2, cols - 3), (rows // 2, cols // 2)))
+    a.close()
+
+
 @pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 257])
 def test_entry_counts(n):
     rng = np.random.default_rng(n)

@@ -276,6 +276,49 @@ def test_scan_carry_across_a_pass_of_the_offsets_kernel():
     fe.close()
 
 
+def _scan_edge_batch(cfg, n_frames, cap):
+    """Counts of 0 and 1 (the last problem always 1: the total moves with the last lane), lines drawn from the edge pool."""
+    rng = np.random.default_rng(sr.SEED + 100 + n_frames)
+    counts = rng.integers(0, 2, (n_frames, 3)).astype(np.int32)
+    counts[-1, 2] = 1
+    _, pool, _ = sr.edge_lines(cfg)
+    lines = np.ascontiguousarray(pool.reshape(-1, 4)[rng.permutation(pool.size // 4)[:n_frames * 3 * cap]].reshape(n_frames, 3, cap, 4))
+    masks = ((rng.random((n_frames, 3) + sr.work_size(cfg)) < 0.5) * 255).astype(np.uint8)
+    return counts, lines, masks
+
+
+@pytest.mark.parametrize("n_frames", [1, 21, 22, 85, 86, 171])
+def test_offsets_scan_edges(n_frames):
+    """k_seg_offsets scans n = 3 n_frames counts in turns of 256: n = 3, 63, 66 (a wave's end), 255, 258 (a turn's end) and 513
+    (the carry into a third turn).  frame_offset is the exclusive sum of the counts, every row in its place."""
+    cfg = default_config("parity")
+    cap = 2
+    counts, lines, masks = _scan_edge_batch(cfg, n_frames, cap)
+    fe = FrontEnd(cfg, max_frames=n_frames, max_lines_per_color=cap)
+    seg = fe.debug_segments(counts, lines, masks)
+    fe.close()
+    ref = sr.expected_batch(cfg, counts, lines, masks, cap)
+    assert np.array_equal(ref["frame_offset"], np.concatenate([[0], np.cumsum(counts.sum(axis=1))])) and ref["n"] == counts.sum() >= 1
+    _assert_segments(seg, ref, "%d frames" % n_frames)
+
+
+@pytest.mark.parametrize("n_frames", [1, 21, 22, 85, 86, 171])
+def test_offsets_scan_edges_over_the_cap(n_frames):
+    """The same batches with one count above max_lines_per_color, in the first turn's first wave or in the last turn: LF_ERR_CAPACITY
+    and the total of the clipped counts."""
+    cfg = default_config("parity")
+    cap = 2
+    counts, lines, masks = _scan_edge_batch(cfg, n_frames, cap)
+    fe = FrontEnd(cfg, max_frames=n_frames, max_lines_per_color=cap)
+    for f, c in ((0, 0), (n_frames - 1, 2)):
+        over = counts.copy()
+        over[f, c] = cap + 1
+        with pytest.raises(LanefrontError) as e:
+            fe.debug_segments(over, lines, masks)
+        assert e.value.code == LF_ERR_CAPACITY and e.value.n_segments == int(np.minimum(over, cap).sum())
+    fe.close()
+
+
 def _same(a, b):
     assert a.n == b.n and np.array_equal(a.frame_offset, b.frame_offset)
     for k in FIELDS + ("desc", "code"):
