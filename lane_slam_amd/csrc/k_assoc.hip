@@ -23,6 +23,7 @@
 //       the search on v_mfma_f32_32x32x2_f32 ranks, fp64 direct sums give the distance and decide what it cannot (below).
 #include <cstdio>
 #include "common.h"
+#include "wave.h"
 #include "k_assoc_loop.inc"
 // The tile loops set m0 before every global_load_lds and say so in their clobber lists, so that the compiler's
 // merging of its own m0 set-ups never reaches across an asm statement; clang notes that m0 is a reserved register.
@@ -131,7 +132,7 @@ __device__ __forceinline__ void assoc_publish_and_merge(unsigned int mine, int m
                 const bool on = best_ham > 0 && t[k] != 0x7fffffffu && (int)(t[k] >> 22) == best_ham;
                 const unsigned long long bo = __ballot(on);
                 if (lane == 0 && writes_piece) tie_counts[(size_t)c * n_pieces + piece] = __popcll(bo);
-                if (on) tie_pieces[((size_t)c * n_pieces + piece) * 64 + __popcll(bo & ((1ull << lane) - 1ull))] = qq;
+                if (on) tie_pieces[((size_t)c * n_pieces + piece) * 64 + lanes_below(bo, lane)] = qq;
             }
         }
     }
@@ -512,9 +513,7 @@ __device__ __forceinline__ double float_dist2_direct8(const float* __restrict__ 
     double s = 0;
 #pragma unroll
     for (int k = 0; k < 9; ++k) { const double d = (double)a[9 * sub + k] - (double)b[9 * sub + k]; s = fma(d, d, s); }
-#pragma unroll
-    for (int d = 4; d >= 1; d >>= 1) s += __shfl_xor(s, d);
-    return s;
+    return wave_reduce<8>(s, op_add());
 }
 
 struct __attribute__((aligned(16))) ExactCand { double d2; int col; int pad; };

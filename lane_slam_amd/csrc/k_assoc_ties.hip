@@ -25,6 +25,7 @@
 #include "common.h"
 #include "mih_rank.h"
 #include "scan.h"
+#include "wave.h"
 
 namespace lf {
 
@@ -126,8 +127,7 @@ __device__ __forceinline__ void assoc_ties_body(const uint8_t* __restrict__ q, c
     for (int c = wave; c < splits; c += 4) {               // one wave per chunk adds its counts up
         int tot = 0;
         for (int p = lane; p < n_pieces; p += 64) tot += counts[(size_t)c * n_pieces + p];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d);
+        tot = wave_reduce(tot, op_add());
         if (lane == 0) s_items[c + 1] = ((tot + TQW - 1) / TQW) * subs;
     }
     __syncthreads();

@@ -16,6 +16,7 @@
 //   a sweep changes nothing.  The fixpoint is unique, so the result does not depend on
 //   sweep order (== the reference's stack-based flood fill).
 #include "common.h"
+#include "wave.h"
 
 namespace lf {
 
@@ -98,8 +99,8 @@ __device__ __forceinline__ int canny_mag_at(const uint32_t* __restrict__ img, in
 }
 
 // lane i takes v of lane i - 1 (i + 1); the vacated lane 0 (63) takes `edge`
-__device__ __forceinline__ int canny_from_left(int v, int edge) { return __builtin_amdgcn_update_dpp(edge, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ int canny_from_right(int v, int edge) { return __builtin_amdgcn_update_dpp(edge, v, 0x130, 0xf, 0xf, false); }
+__device__ __forceinline__ int canny_from_left(int v, int edge) { return dpp<0x138, 0xf, false>(edge, v); }
+__device__ __forceinline__ int canny_from_right(int v, int edge) { return dpp<0x130, 0xf, false>(edge, v); }
 
 struct CannyBand {
     const uint32_t* img;       // this frame's working image

@@ -35,6 +35,7 @@
 #include "common.h"
 #include "k_edlines_types.h"
 #include "scan.h"
+#include "wave.h"
 
 namespace lf {
 
@@ -517,7 +518,6 @@ void launch_pyrdown(int H, int W, int n_frames, const uint8_t* src, uint8_t* dst
 // ------------------------------------------------------------------------------------------------ k_ed_detect
 enum { UpDir = 1, RightDir = 2, DownDir = 3, LeftDir = 4 };
 
-typedef __attribute__((address_space(3))) uint32_t ed_lds_u32;
 
 // the edge marks: a bit plane in LDS (reached through the LDS address space: a flat access to LDS takes the slow path and
 // waits on both memory counters), or in global memory for octave images beyond the LDS budget (there every access is an
@@ -527,18 +527,18 @@ struct EdMarks {
     uint32_t* p; bool in_lds;
     __device__ __forceinline__ bool get(int i) const
     {
-        const uint32_t w = in_lds ? ((ed_lds_u32*)p)[i >> 5] : __hip_atomic_load(p + (i >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t w = in_lds ? ((lds_u32*)p)[i >> 5] : __hip_atomic_load(p + (i >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return (w >> (i & 31)) & 1u;
     }
     // per-lane i (the lanes of a wave may name bits of one word)
     __device__ __forceinline__ void set(int i) const
     {
-        if (in_lds) __hip_atomic_fetch_or((ed_lds_u32*)p + (i >> 5), 1u << (i & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (in_lds) __hip_atomic_fetch_or((lds_u32*)p + (i >> 5), 1u << (i & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         else __hip_atomic_fetch_or(p + (i >> 5), 1u << (i & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __device__ __forceinline__ void clear(int i) const
     {
-        if (in_lds) __hip_atomic_fetch_and((ed_lds_u32*)p + (i >> 5), ~(1u << (i & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (in_lds) __hip_atomic_fetch_and((lds_u32*)p + (i >> 5), ~(1u << (i & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         else __hip_atomic_fetch_and(p + (i >> 5), ~(1u << (i & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 };
@@ -676,8 +676,8 @@ __device__ __forceinline__ bool ed_walk(EdWalk& c, unsigned x0, unsigned y0, int
         // in one word (9 bits each), then the same word of the rows above and below.  Values from beyond the window's
         // edge are never used (bit 0 of the record)
         const int g9 = (int)((v & 0xffu) | ((v >> 7) & 0x100u));
-        const int gW = __builtin_amdgcn_update_dpp(0, g9, 0x111, 0xf, 0xf, true);     // row_shr:1: from lane - 1
-        const int gE = __builtin_amdgcn_update_dpp(0, g9, 0x101, 0xf, 0xf, true);     // row_shl:1: from lane + 1
+        const int gW = dpp<0x111>(0, g9);     // row_shr:1: from lane - 1
+        const int gE = dpp<0x101>(0, g9);     // row_shl:1: from lane + 1
         const int R = gW | (g9 << 9) | (gE << 18);
         const int RN = __builtin_amdgcn_ds_bpermute(((lane - 8) & 63) << 2, R), RS = __builtin_amdgcn_ds_bpermute(((lane + 8) & 63) << 2, R);
         const int nNW = RN & 0x1ff, nN = (RN >> 9) & 0x1ff, nNE = (RN >> 18) & 0x1ff, nSW = RS & 0x1ff, nS = (RS >> 9) & 0x1ff, nSE = (RS >> 18) & 0x1ff;
@@ -833,40 +833,6 @@ __device__ __noinline__ double ed_nfa(int n, int k, double p, double logNT)
     return -dm::dlog10(bin_tail) - logNT;
 }
 
-// sums over the wave: four DPP exchanges inside the rows of 16 lanes (lane pairs, pairs of pairs, mirrored halves, mirrored
-// rows), then the four rows through scalar registers -- the six-step __shfl_xor butterfly is twelve trips through the LDS
-// crossbar per 64-bit sum, and a line fit makes four of them
-template <int CTRL>
-__device__ __forceinline__ int ed_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-    v += ed_dpp<0xB1>(v);            // quad_perm [1,0,3,2]
-    v += ed_dpp<0x4E>(v);            // quad_perm [2,3,0,1]
-    v += ed_dpp<0x141>(v);           // row_half_mirror
-    v += ed_dpp<0x140>(v);           // row_mirror: every lane of a row holds the row's sum
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
-}
-template <int CTRL>
-__device__ __forceinline__ long long ed_dpp_ll(long long v)
-{
-    const int lo = ed_dpp<CTRL>((int)(v & 0xffffffffll)), hi = ed_dpp<CTRL>((int)(v >> 32));
-    return ((long long)hi << 32) | (unsigned int)lo;
-}
-__device__ __forceinline__ long long ed_readlane_ll(long long v, int l)
-{
-    const int lo = __builtin_amdgcn_readlane((int)(v & 0xffffffffll), l), hi = __builtin_amdgcn_readlane((int)(v >> 32), l);
-    return ((long long)hi << 32) | (unsigned int)lo;
-}
-__device__ __forceinline__ long long wave_sum_ll(long long v)
-{
-    v += ed_dpp_ll<0xB1>(v);
-    v += ed_dpp_ll<0x4E>(v);
-    v += ed_dpp_ll<0x141>(v);
-    v += ed_dpp_ll<0x140>(v);
-    return ed_readlane_ll(v, 0) + ed_readlane_ll(v, 16) + ed_readlane_ll(v, 32) + ed_readlane_ll(v, 48);
-}
-__device__ __forceinline__ double ed_readlane_d(double v, int l) { return __longlong_as_double(ed_readlane_ll(__double_as_longlong(v), l)); }
-
 struct EdFit { float ATA[4], ATV[2]; };
 
 // [sum a^2, sum a; sum a, n], [sum a b, sum b] over chain[s, s + n): exact integer sums, rounded once to float
@@ -879,7 +845,7 @@ __device__ __forceinline__ void ed_sums(const uint32_t* __restrict__ chain, unsi
         const long long A = horizontal ? X : Y, B = horizontal ? Y : X;
         saa += A * A; sa += A; sab += A * B; sb += B;
     }
-    saa = wave_sum_ll(saa); sa = wave_sum_ll(sa); sab = wave_sum_ll(sab); sb = wave_sum_ll(sb);
+    saa = wave_sum(saa); sa = wave_sum(sa); sab = wave_sum(sab); sb = wave_sum(sb);
     m4[0] = (float)saa; m4[1] = (float)sa; m4[2] = (float)sa; m4[3] = (float)n;
     v2[0] = (float)sab; v2[1] = (float)sb;
 }
@@ -1149,7 +1115,7 @@ __global__ __launch_bounds__(ED_THREADS) void k_ed_detect(EdAll all, EdFitParams
                     c2 = c * c;
                 }
                 double err = 0;
-                for (int i = 0; i < minLen; ++i) err += ed_readlane_d(c2, __builtin_amdgcn_readfirstlane(i));
+                for (int i = 0; i < minLen; ++i) err += readlane(c2, __builtin_amdgcn_readfirstlane(i));
                 lineFitErr = dm::dsqrt(err);
                 if (lineFitErr <= thr) break;
                 S += 2;
@@ -1226,7 +1192,7 @@ __global__ __launch_bounds__(ED_THREADS) void k_ed_detect(EdAll all, EdFitParams
                 const int gwo = ed_div4_half_even((vx < 0 ? -vx : vx) + (vy < 0 ? -vy : vy));
                 sal += (bi & 1u) ? ((gwo >> 8) & 0xff) : (gwo & 0xff);
             }
-            mgx = wave_sum_i(mgx); mgy = wave_sum_i(mgy);
+            mgx = wave_sum(mgx); mgy = wave_sum(mgy);
             const double adx = fabs(q1), ady = fabs(q0);
             float direction = 0.f;
             bool ok = !(mgx == 0 && mgy == 0);
@@ -1249,14 +1215,14 @@ __global__ __launch_bounds__(ED_THREADS) void k_ed_detect(EdAll all, EdFitParams
                         const double dis = fabs((double)direction - pd);
                         if (fabs(2 * PI - dis) < 0.392699 || dis < 0.392699) kk++;
                     }
-                    kk = wave_sum_i(kk);
+                    kk = wave_sum(kk);
                     ok = __builtin_amdgcn_readfirstlane((int)(ed_nfa(n, kk, 0.125, logNT) > 0)) != 0;
                 }
             }
             if (ok) {
                 const double a1 = q1 * q1, a2 = q0 * q0, a3 = q0 * q1, a4 = q2 * q0, a5 = q2 * q1;
                 const uint32_t pa = chain[lstart], pb = chain[S - 1];
-                sal = wave_sum_i(sal);
+                sal = wave_sum(sal);
                 int slot = 0;
                 if (lane == 0) slot = atomicAdd(&s_temp_next, 1);
                 slot = __builtin_amdgcn_readfirstlane(slot);
@@ -1472,7 +1438,7 @@ __global__ __launch_bounds__(256) void k_kl_assemble(EdAll all, int n_octaves, c
             }
             // new class ids in line order: exclusive count of the fresh lines before this one
             const unsigned long long bal = __ballot(fresh);
-            const int before = __popcll(bal & ((1ull << lane) - 1ull));
+            const int before = lanes_below(bal, lane);
             if (lane == 0) s_wave[wave] = __popcll(bal);
             __syncthreads();
             int off = s_next_class;
@@ -1568,7 +1534,7 @@ __global__ __launch_bounds__(64) void k_ed_slots(EdAll all, const uint32_t* __re
         }
         for (int c = 0; c < 3; ++c) {
             const unsigned long long bal = __ballot((member >> c) & 1);
-            const int pos = cnt[c] + __popcll(bal & ((1ull << lane) - 1ull));
+            const int pos = cnt[c] + lanes_below(bal, lane);
             if (((member >> c) & 1) && pos < cap_lines)
                 for (int q = 0; q < 4; ++q) sl[((size_t)c * cap_lines + pos) * 4 + q] = io[q];
             cnt[c] += __popcll(bal);
@@ -1678,7 +1644,7 @@ __global__ __launch_bounds__(256) void k_kl_mask_move(const int* __restrict__ fo
         const unsigned long long bk = __ballot(keep);
         if (lane == 0) s_k[wave] = __popcll(bk);
         __syncthreads();
-        int r = done + __popcll(bk & ((1ull << lane) - 1ull));
+        int r = done + lanes_below(bk, lane);
         for (int k = 0; k < wave; ++k) r += s_k[k];
         if (keep) {
             const size_t a = (size_t)base + j, b = (size_t)out0 + r;

@@ -26,6 +26,7 @@
 #include <math.h>
 #include "k_hough.h"
 #include "scan.h"
+#include "wave.h"
 
 namespace lf {
 
@@ -85,13 +86,6 @@ __device__ __forceinline__ int hough_r(int j, int i, float c, float s)
     return (int)__builtin_rintf(v);          // round half to even in the default rounding mode
 }
 
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const unsigned o = __shfl_xor(v, d); v = o > v ? o : v; }
-    return v;
-}
-
 __device__ __forceinline__ bool mask_bit(const uint32_t* mask, int Ww, int i, int j)
 {
     return (mask[i * Ww + (j >> 5)] >> (j & 31)) & 1u;
@@ -136,7 +130,7 @@ __global__ __launch_bounds__(64) void k_hough(HoughParams p, int n_problems, con
             npts += __popc(v);
         }
 #pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) npts += __shfl_xor(npts, d);
+        for (int d = 32; d >= 1; d >>= 1) npts += __shfl_xor(npts, d);       // (as wave_reduce it schedules differently and measured slower)
         __threadfence();                     // the previous problem's un-votes are done before the cells are cleared
         for (int c = lane; c < p.cells; c += 64) acc[c] = 0;
         __threadfence();
@@ -178,7 +172,7 @@ __global__ __launch_bounds__(64) void k_hough(HoughParams p, int n_problems, con
                 const unsigned kq = val > 0 ? ((unsigned)val << 8) | (unsigned)(255 - (lane + 64 * q)) : 0u;
                 key = kq > key ? kq : key;
             }
-            key = wave_max_u32(key);
+            key = wave_reduce(key, op_max());
             if ((int)(key >> 8) < p.threshold) continue;
             const int max_n = 255 - (int)(key & 255u);
             const int xflag = tab->walk[3 * max_n], dx0 = tab->walk[3 * max_n + 1], dy0 = tab->walk[3 * max_n + 2];

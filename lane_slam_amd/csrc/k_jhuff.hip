@@ -347,7 +347,7 @@ __device__ __forceinline__ void jh_frame(JhShared& sh, jpeg::DevFrame& F, JhInfo
             __syncthreads();
             int off = s_carry;
             for (int w = 0; w < wave; ++w) off += s_wsum[w];
-            if (head) sh.s_dlist[off + __popcll(bm & ((1ull << lane) - 1ull))] = (uint16_t)u;
+            if (head) sh.s_dlist[off + lanes_below(bm, lane)] = (uint16_t)u;
             __syncthreads();
             if (t == JH_T - 1) s_carry = off + __popcll(bm);
             __syncthreads();
@@ -479,7 +479,7 @@ __device__ __forceinline__ void jh_frame(JhShared& sh, jpeg::DevFrame& F, JhInfo
                     int base = 0;
                     if (lane == 0) base = atomicAdd(&sh.s_nd, __popcll(bm));
                     base = __builtin_amdgcn_readfirstlane(base);
-                    if (dirty) sh.s_dlist[base + __popcll(bm & ((1ull << lane) - 1ull))] = (uint16_t)u;
+                    if (dirty) sh.s_dlist[base + lanes_below(bm, lane)] = (uint16_t)u;
                 }
             }
             __syncthreads();

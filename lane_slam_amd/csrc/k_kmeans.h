@@ -2,6 +2,7 @@
 // frame, lf_ai_transform_batch): the arithmetic the oracle (oracle/lf_oracle_kmeans.c) restates, see k_kmeans.hip.
 #pragma once
 #include "common.h"
+#include "wave.h"
 
 namespace lf {
 
@@ -41,9 +42,7 @@ struct KmAcc {
     {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            unsigned int x = v[i];
-            for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-            v[i] = x;
+            v[i] = wave_reduce(v[i], op_add());
         }
         if ((threadIdx.x & 63) == 0)
             for (int j = 0; j < k && j < 4; ++j) {

@@ -252,7 +252,7 @@ __global__ __launch_bounds__(1024) void k_select_queries(const uint8_t* __restri
         int off = s_base;
         for (int w = 0; w < wave; ++w) off += s_wave[w];
         if (keep) {
-            const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
+            const int pos = off + lanes_below(bal, lane);
             const uint4* src = reinterpret_cast<const uint4*>(query + (size_t)i * 32);
             uint4* dst = reinterpret_cast<uint4*>(out + (size_t)pos * 32);
             dst[0] = src[0]; dst[1] = src[1];

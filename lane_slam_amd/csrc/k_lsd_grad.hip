@@ -27,6 +27,7 @@
 // the blur / resample / gradient element-operations of a 16 x 16 tiling are 0.74 of a 32 x 32 one.
 #include "common.h"
 #include "k_lsd_grad.h"
+#include "wave.h"
 
 namespace lf {
 
@@ -50,11 +51,6 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// how many lanes below this one have their bit set in a ballot
-__device__ __forceinline__ int lanes_below(unsigned long long m)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 
 // ---- pass 1: list the tiles whose raw footprint contains edge_color pixels ------------------
@@ -137,7 +133,7 @@ __global__ __launch_bounds__(64 * LC_WAVES) void k_lsd_classify(LsdParams p, Res
         int slot = strip_base[ty];
         for (int c = 0; c < CH; ++c) {
             const unsigned long long m = listed[ty][c];
-            if ((m >> lane) & 1ull) list[slot + lanes_below(m)] = lsd_tile_entry(pc, ty, c * 64 + lane);
+            if ((m >> lane) & 1ull) list[slot + lanes_below_me(m)] = lsd_tile_entry(pc, ty, c * 64 + lane);
             slot += __popcll(m);
         }
     }
@@ -356,19 +352,18 @@ __global__ __launch_bounds__(64 * LG_WAVES) void k_lsd_grad(LsdParams p, ResizeT
                 // the level-line angle waits for the trigonometry pass: there every lane has a defined pixel (here one
                 // pixel in six does, and the arc tangent would run for the whole wave)
                 if (norm > local_max) local_max = norm;
-                const int slot = nd + lanes_below(m_def);
+                const int slot = nd + lanes_below_me(m_def);
                 dl[slot] = make_uint2((uint32_t)((size_t)dy * p.Ws + dx), (uint32_t)(oy * SCW + ox));
                 dln[slot] = norm;
             }
             low_norm[t] = norm;
-            low_slot[t] = is_low ? n_lo + lanes_below(m_low) : -1;
+            low_slot[t] = is_low ? n_lo + lanes_below_me(m_low) : -1;
             nd += __popcll(m_def);
             n_lo += __popcll(m_low);
         }
         // one global atomic per tile: positive doubles order like their bit patterns
         unsigned long long tile_max = local_max > 0.0 ? (unsigned long long)__double_as_longlong(local_max) : 0ull;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { unsigned long long o = __shfl_xor(tile_max, d); tile_max = o > tile_max ? o : tile_max; }
+        tile_max = wave_reduce(tile_max, op_max());
         int rec_base = 0, low_base = 0;
         if (lane == 0) {
             if (tile_max) atomicMax(maxgrad + pc, tile_max);

@@ -26,6 +26,7 @@
 #include <type_traits>
 #include "lsd_bitplane.h"
 #include "scan.h"
+#include "wave.h"
 
 namespace lf {
 using std::max;
@@ -481,9 +482,7 @@ void launch_lsd_order(const LsdParams& p, const LsdRecords& r, const LsdCompact&
 //   c_label[e]      root of entry e                     (u16; problems of more than label_items entries: all 0)
 //   comp_list[k]    roots of the components with >= min_reg_size pixels, by size descending, root ascending
 //   comp_count      how many
-// (the parent array lives in LDS and is addressed as such: a volatile access through a generic pointer is a flat load)
-typedef __attribute__((address_space(3))) uint32_t uf_lds_u32;
-typedef volatile uf_lds_u32 uf_lds_vu32;
+// (the parent array lives in LDS and is addressed as such, wave.h: a volatile access through a generic pointer is a flat load)
 // The union-find's storage.  UfLds: the LDS tables (problems of up to label_lds entries).  UfGlb (round 4): the same tables in the
 // problem's region scratch in global memory, for the problems beyond that -- every access an agent-scope atomic (served by the L2:
 // the vector L1 is not coherent with the atomics that re-parent nodes).  Slower per access, but such a workgroup asks for no
@@ -491,21 +490,20 @@ typedef volatile uf_lds_u32 uf_lds_vu32;
 // that needed 147 KB (24 k entries) only started once a whole CU had drained -- 18 ms in the queue against 0.6 ms of work
 // (tools/pipe_overlap.py on camera frames), which capped the whole pipeline.
 struct UfLds {                       // component sizes: u32 words
-    uf_lds_vu32* P;
+    volatile lds_u32* P;
     __device__ __forceinline__ uint32_t get(uint32_t i) const { return P[i]; }
     __device__ __forceinline__ void set(uint32_t i, uint32_t v) const { P[i] = v; }
-    __device__ __forceinline__ void add(uint32_t i, uint32_t v) const { (void)__hip_atomic_fetch_add((uf_lds_u32*)&P[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    __device__ __forceinline__ void add(uint32_t i, uint32_t v) const { (void)__hip_atomic_fetch_add((lds_u32*)&P[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 };
-typedef __attribute__((address_space(3))) uint16_t uf_lds_u16;
 struct UfLds16 {                     // parents: u16 (an LDS problem has at most label_lds <= 65535 entries); min by compare-and-swap on the word
-    volatile uf_lds_u16* P;
+    volatile lds_u16* P;
     __device__ __forceinline__ uint32_t get(uint32_t i) const { return P[i]; }
     __device__ __forceinline__ void set(uint32_t i, uint32_t v) const { P[i] = (uint16_t)v; }
     __device__ __forceinline__ uint32_t min(uint32_t i, uint32_t v) const
     {
-        uf_lds_u32* w = (uf_lds_u32*)P + (i >> 1);
+        lds_u32* w = (lds_u32*)P + (i >> 1);
         const uint32_t sh = (i & 1u) * 16u;
-        uint32_t cur = *(volatile uf_lds_u32*)w;
+        uint32_t cur = *(volatile lds_u32*)w;
         for (;;) {
             const uint32_t old = (cur >> sh) & 0xffffu;
             if (v >= old) return old;
@@ -586,7 +584,7 @@ __device__ __forceinline__ void lsd_label_problem(const LsdParams& p, const int*
     typename std::conditional<GLB, UfGlb, UfLds16>::type parent;
     typename std::conditional<GLB, UfGlb, UfLds>::type csize2;
     if constexpr (GLB) { parent.P = gtab; csize2.P = gtab + ((n + 1) & ~1); }
-    else { parent.P = (volatile uf_lds_u16*)dyn_lds; csize2.P = (uf_lds_vu32*)(dyn_lds + LS / 2); }
+    else { parent.P = (volatile lds_u16*)dyn_lds; csize2.P = (volatile lds_u32*)(dyn_lds + LS / 2); }
     auto xs = [&](int k) -> int { if constexpr (GLB) return (int)(c_xy[o + k] & 0xffffu); else return (int)xs_lds[k]; };
     const int* rs = row_start + (size_t)pc * (p.Hs + 1);
     if (t == 0) { n_roots = 0; rest_total = 0; }

@@ -57,6 +57,7 @@
 #include <cstring>
 #include "common.h"
 #include "lsd_bitplane.h"
+#include "scan.h"
 
 namespace lf {
 
@@ -119,14 +120,7 @@ __device__ __forceinline__ uint32_t key_of(uint32_t v) { return v >> 20; }
 // compare_norm(a, b) = a.norm > b.norm
 __device__ __forceinline__ bool comp(uint32_t a, uint32_t b) { return key_of(a) > key_of(b); }
 
-// Everything the partition passes keep in LDS is addressed AS LDS (address space 3): through a generic pointer every table access
-// is a flat instruction -- the long way to LDS, and a wait for whatever global access is in flight (v2 of this kernel spent most
-// of its time there: 50 us per partition).
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef __attribute__((address_space(3))) uint16_t lds_u16;
-typedef __attribute__((address_space(3))) unsigned long long lds_u64;
-typedef __attribute__((address_space(3))) int lds_i32;
-template <typename T> __device__ __forceinline__ T* as_lds(void* generic) { return (T*)(__attribute__((address_space(3))) void*)generic; }
+// (everything the partition passes keep in LDS is addressed as LDS: wave.h)
 __device__ __forceinline__ void lds_add(lds_i32* p, int v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_min(lds_i32* p, int v) { (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_or(lds_i32* p, int v) { (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -134,34 +128,7 @@ __device__ __forceinline__ void lds_or(lds_i32* p, int v) { (void)__hip_atomic_f
 __device__ __forceinline__ void tab_add(lds_i32* p, int v) { lds_add(p, v); }
 __device__ __forceinline__ void tab_min(lds_i32* p, int v) { lds_min(p, v); }
 
-// Wave scans and reductions as DPP (row shifts inside the rows of 16 lanes, then row broadcasts): ~50 cycles instead of six trips through
-// the LDS crossbar (__shfl_up compiles to ds_bpermute_b32: ~100 cycles apiece in a lone wave, and the partitions are chains of them)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_or_zero(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false); }
-__device__ __forceinline__ int wave_incl_scan_i(int v, int /*lane*/)
-{
-    v += dpp_or_zero<0x111, 0xf>(v);          // row_shr:1 (lanes without a source add 0)
-    v += dpp_or_zero<0x112, 0xf>(v);          // row_shr:2
-    v += dpp_or_zero<0x114, 0xf>(v);          // row_shr:4
-    v += dpp_or_zero<0x118, 0xf>(v);          // row_shr:8
-    v += dpp_or_zero<0x142, 0xa>(v);          // row_bcast:15 into rows 1 and 3
-    v += dpp_or_zero<0x143, 0xc>(v);          // row_bcast:31 into rows 2 and 3
-    return v;
-}
-__device__ __forceinline__ int wave_last(int v) { return __builtin_amdgcn_readlane(v, 63); }
-__device__ __forceinline__ int wave_sum_i(int v) { return wave_last(wave_incl_scan_i(v, 0)); }
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_or_max(int v) { return __builtin_amdgcn_update_dpp(0x7fffffff, v, CTRL, ROW_MASK, 0xf, false); }
-__device__ __forceinline__ int wave_min_i(int v)
-{
-    v = min(v, dpp_or_max<0x111, 0xf>(v));
-    v = min(v, dpp_or_max<0x112, 0xf>(v));
-    v = min(v, dpp_or_max<0x114, 0xf>(v));
-    v = min(v, dpp_or_max<0x118, 0xf>(v));
-    v = min(v, dpp_or_max<0x142, 0xa>(v));
-    v = min(v, dpp_or_max<0x143, 0xc>(v));
-    return wave_last(v);
-}
+// (wave scans and reductions are the DPP forms of scan.h and wave.h: this kernel's partitions are chains of them, run by a lone wave)
 
 // __move_median_to_first(result = f, a = f + 1, b = mid, c = l - 1)
 __device__ __forceinline__ void median_to_first(uint32_t* E, int f, int l)
@@ -249,16 +216,16 @@ __device__ __forceinline__ int partition_tail(EP E, int org, int lo, int hi, T64
 {
     const int R = (hi - lo + 63) >> 6;
     const unsigned long long le = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);      // lanes <= this one
-    const unsigned long long lt = (1ull << lane) - 1ull;                                // lanes < this one
+    const unsigned long long lt = lane_mask_lt(lane);                                   // lanes < this one
     // (2) exclusive prefix of the L counts (first wave of the team), inclusive suffix of the R counts (its second wave)
     if (w == 0) {
         int carry = 0;
         for (int r0 = 0; r0 < R; r0 += 64) {
             const int r = r0 + lane;
             const int c = r < R ? PL[r] : 0;
-            const int inc = wave_incl_scan_i(c, lane);
+            const int inc = wave_incl_scan_dpp(c);
             if (r < R) PL[r] = carry + inc - c;
-            carry += wave_last(inc);
+            carry += readlane(inc, 63);
         }
     }
     if (w == (COOP ? 1 : 0)) {
@@ -266,9 +233,9 @@ __device__ __forceinline__ int partition_tail(EP E, int org, int lo, int hi, T64
         for (int r0 = 0; r0 < R; r0 += 64) {
             const int r = R - 1 - (r0 + lane);                 // from the last row backwards
             const int c = r >= 0 ? SX[r] : 0;
-            const int inc = wave_incl_scan_i(c, lane);
+            const int inc = wave_incl_scan_dpp(c);
             if (r >= 0) SX[r] = carry + inc;
-            carry += wave_last(inc);
+            carry += readlane(inc, 63);
         }
         if (lane == 0) SX[R] = 0;
     }
@@ -441,7 +408,7 @@ __device__ __forceinline__ void wave_window(lds_u32* D, uint32_t* D_generic, int
     int f = 0, l = n, d = depth;
     bool done = false;
     const unsigned long long le = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);      // lanes <= this one
-    const unsigned long long lt = (1ull << lane) - 1ull;                                // lanes < this one
+    const unsigned long long lt = lane_mask_lt(lane);                                   // lanes < this one
     for (;;) {
         const unsigned long long segm = (l >= 64 ? ~0ull : ((1ull << l) - 1ull)) & ~((1ull << f) - 1ull);
         const unsigned long long sb = __ballot(in && (v & 0xfffffu) != 0u);
@@ -496,11 +463,6 @@ __device__ __forceinline__ void wave_window(lds_u32* D, uint32_t* D_generic, int
 // back as v_readlane with the (uniform) row number, the cut is followed in scalar registers while the rows go by (first L, first L
 // that stays, leftmost swapped R), four rows' loads are in flight at a time.  What is left in LDS: the two place lists of the
 // swapped elements (u16, under their ranks) and the pairwise swaps.  Returns the cut, -1 when the range holds no seed.
-__device__ __forceinline__ unsigned long long readlane64(unsigned long long x, int r)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, r), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), r);
-    return ((unsigned long long)hi << 32) | lo;
-}
 __device__ __forceinline__ int wave_partition(lds_u32* D, int f, int l, lds_u16* Lpos, lds_u16* Rpos, int lane)
 {
     const int lo = f + 1, hi = l;
@@ -515,7 +477,7 @@ __device__ __forceinline__ int wave_partition(lds_u32* D, int f, int l, lds_u16*
     team_sync<false>();
     const uint32_t kp = key_of(pivot);
     const unsigned long long le = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);      // lanes <= this one
-    const unsigned long long lt = (1ull << lane) - 1ull;                                // lanes < this one
+    const unsigned long long lt = lane_mask_lt(lane);                                   // lanes < this one
     // (1) the ballots of every row; lane r keeps row r's
     unsigned long long myBL = 0ull, myBR = 0ull;
     unsigned long long seeds = (pivot & 0xfffffu) != 0u ? 1ull : 0ull;
@@ -536,14 +498,14 @@ __device__ __forceinline__ int wave_partition(lds_u32* D, int f, int l, lds_u16*
     if (seeds == 0ull) return -1;
     // (2) L elements in the rows in front of row r, R elements in the rows behind it
     const int cl = __popcll(myBL), cr = __popcll(myBR);
-    const int myPL = wave_incl_scan_i(cl, lane) - cl;
-    const int incr = wave_incl_scan_i(cr, lane);
-    const int mySX = wave_last(incr) - incr;
+    const int myPL = wave_incl_scan_dpp(cl) - cl;
+    const int incr = wave_incl_scan_dpp(cr);
+    const int mySX = readlane(incr, 63) - incr;
     // (3) ranks; the swapped elements publish their places under their ranks; the cut's ingredients in passing
     int K = 0, firstL = 0x7fffffff, firstStay = 0x7fffffff, RK = 0x7fffffff;
     for (int r = 0; r < R; ++r) {
-        const unsigned long long bl = readlane64(myBL, r), br = readlane64(myBR, r);
-        const int pl = __builtin_amdgcn_readlane(myPL, r), sx = __builtin_amdgcn_readlane(mySX, r);
+        const unsigned long long bl = readlane(myBL, r), br = readlane(myBR, r);
+        const int pl = readlane(myPL, r), sx = readlane(mySX, r);
         const int i = lo + r * 64 + lane;
         const bool isL = (bl >> lane) & 1ull, isR = (br >> lane) & 1ull;
         const int kl = pl + __popcll(bl & le), r_right = sx + __popcll(br & ~le);
@@ -898,9 +860,9 @@ __device__ __forceinline__ int wave_scan_rows(CT cnt, int R, int lane)
     for (int r0 = 0; r0 < R; r0 += 64) {
         const int r = r0 + lane;
         const int c = r < R ? (int)cnt[r] : 0;
-        const int inc = wave_incl_scan_i(c, lane);
+        const int inc = wave_incl_scan_dpp(c);
         if (r < R) cnt[r] = carry + inc - c;
-        carry += wave_last(inc);
+        carry += readlane(inc, 63);
     }
     return carry;
 }
@@ -1002,7 +964,7 @@ __device__ __forceinline__ int plane_counts(const Plane& pl, lds_i32* wave_tot)
     const int w0 = tid * per < pl.pairs ? tid * per : pl.pairs, w1 = w0 + per < pl.pairs ? w0 + per : pl.pairs;
     int mine = 0;
     for (int q = w0; q < w1; ++q) mine += __popcll(pl.bits[2 * q]) + __popcll(pl.bits[2 * q + 1]);
-    const int incl = wave_incl_scan_i(mine, lane);
+    const int incl = wave_incl_scan_dpp(mine);
     if (lane == 63) wave_tot[wave] = incl;
     __syncthreads();
     int basev = incl - mine, total = 0;
@@ -1030,7 +992,7 @@ constexpr uint32_t kDeadSlot = 0xffffffffu;
 #define LF_SEED_SEL 4
 #endif
 constexpr int kSel = LF_SEED_SEL;           // selects / list slots a thread works on side by side (registers: the kernel must keep three waves per SIMD)
-__device__ __forceinline__ void chain_step_plane(const SeedWork& W, __attribute__((address_space(3))) ChainState* cs, lds_u32* lds,
+__device__ __forceinline__ void chain_step_plane(const SeedWork& W, lds_of<ChainState>* cs, lds_u32* lds,
                                                  uint32_t (&pr)[kEPT], bool& regs_ok)
 {
     const int t = threadIdx.x, lane = t & 63;
@@ -1238,7 +1200,7 @@ __device__ __forceinline__ void chain_step_plane(const SeedWork& W, __attribute_
                 }
             }
         }
-        mymin = wave_min_i(mymin);
+        mymin = wave_min_bcast(mymin);
         if (lane == 0 && wk) { lds_add((lds_i32*)&cs->K, wk); lds_min((lds_i32*)&cs->minR, mymin); }
     }
     __syncthreads();
@@ -1321,7 +1283,7 @@ __device__ __forceinline__ void chain_step_plane(const SeedWork& W, __attribute_
             for (int u = 0; u < kST; ++u) {
                 const bool emit = (emask >> u) & 1u;
                 const unsigned long long be = __ballot(emit);
-                if (emit) { const int dst = base_ + __popcll(be & ((1ull << lane) - 1ull)); P2[dst] = pp[u]; V2[dst] = tv[u]; }
+                if (emit) { const int dst = base_ + lanes_below(be, lane); P2[dst] = pp[u]; V2[dst] = tv[u]; }
                 base_ += __popcll(be);
             }
         }
@@ -1349,8 +1311,7 @@ __device__ __forceinline__ void chain_step_plane(const SeedWork& W, __attribute_
 template <bool PL>
 __device__ __forceinline__ void sparse_chain(const SeedWork& W, lds_u32* Pl, lds_u32* tab, ChainState* cs_generic, int n, int m0, int nseeds, lds_u32* plane_lds, int plane_lds_words)
 {
-    typedef __attribute__((address_space(3))) ChainState lds_cs;
-    lds_cs* cs = (lds_cs*)(__attribute__((address_space(3))) void*)cs_generic;
+    lds_of<ChainState>* cs = as_lds<lds_of<ChainState>>(cs_generic);
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     if (t == 0) {
         cs->f = 0; cs->l = n; cs->depth = 2 * (31 - __clz(n)); cs->a = 0; cs->b = m0; cs->seeds = nseeds; cs->cur = 0; cs->e_used = 0; cs->n_ranges = 0; cs->stop = 0;
@@ -1522,7 +1483,7 @@ __device__ __forceinline__ void sparse_chain(const SeedWork& W, lds_u32* Pl, lds
 #define TBG(r) (PL ? lBG[r] : gBG[r])
 #define TCA(r) (PL ? lCA[r] : gCA[r])
 #define TCG(r) (PL ? lCG[r] : gCG[r])
-            const unsigned long long ltm = (1ull << lane) - 1ull;
+            const unsigned long long ltm = lane_mask_lt(lane);
             for (int r = w; r < R; r += SW) {
                 const int i = a1 + r * 64 + lane;
                 const uint32_t v = i < b ? V[i] : 0u;
@@ -1570,7 +1531,7 @@ __device__ __forceinline__ void sparse_chain(const SeedWork& W, lds_u32* Pl, lds
                     }
                     const unsigned long long bo = __ballot(ok);
                     wk += __popcll(bo);
-                    if (bo) wmin = min(wmin, __builtin_amdgcn_readlane(pos, __ffsll((long long)bo) - 1));
+                    if (bo) wmin = min(wmin, readlane(pos, __ffsll((long long)bo) - 1));
                 }
                 if (lane == 0) {
                     if (wk) lds_add((lds_i32*)&cs->K, wk);
@@ -1680,16 +1641,16 @@ __device__ __forceinline__ void seed_radix_pass(const uint32_t* __restrict__ src
         int carry = 0;
         for (int c = 0; c < NT / 64; ++c) {
             const int v = (int)cnt[b * NT + c * 64 + lane];
-            const int inc = wave_incl_scan_i(v, lane);
+            const int inc = wave_incl_scan_dpp(v);
             cnt[b * NT + c * 64 + lane] = (uint32_t)(carry + inc - v);
-            carry += wave_last(inc);
+            carry += readlane(inc, 63);
         }
         if (lane == 0) tot[b] = carry;
     }
     __syncthreads();
     if (wave == 0) {
         const int v = lane < SNB ? tot[lane] : 0;
-        const int inc = wave_incl_scan_i(v, lane);
+        const int inc = wave_incl_scan_dpp(v);
         if (lane < SNB) base[lane] = inc - v;
     }
     __syncthreads();
@@ -1760,7 +1721,7 @@ __device__ __forceinline__ void seed32_dense(const SeedWork& W, int n_seeds, int
         const uint32_t v = i < M ? W.E[i] : 0u;
         const bool seed = (v & 0xfffffu) != 0u;
         const unsigned long long bb = __ballot(seed);
-        if (seed) B[rowc[r] + __popcll(bb & ((1ull << lane) - 1ull))] = ((uint32_t)((n_bins - 1) - (int)key_of(v)) << 20) | ((v & 0xfffffu) - 1u);
+        if (seed) B[rowc[r] + lanes_below(bb, lane)] = ((uint32_t)((n_bins - 1) - (int)key_of(v)) << 20) | ((v & 0xfffffu) - 1u);
     }
     __syncthreads();
     // ... and the final insertion sort: stable by bin, highest bin first (every seed is in E once)
@@ -1784,7 +1745,7 @@ __device__ __forceinline__ void plane_scan(uint32_t* lds, int words, int* wave_t
     const int w0 = tid * per < pairs ? tid * per : pairs, w1 = w0 + per < pairs ? w0 + per : pairs;
     int mine = 0;
     for (int q = w0; q < w1; ++q) mine += __builtin_popcountll(bits64[2 * q]) + __builtin_popcountll(bits64[2 * q + 1]);
-    const int incl = wave_incl_scan_i(mine, lane);
+    const int incl = wave_incl_scan_dpp(mine);
     if (lane == 63) wave_tot[wave] = incl;
     __syncthreads();
     int basev = incl - mine;
@@ -1879,7 +1840,7 @@ __global__ __launch_bounds__(ST, LF_SEED_OCC) void k_lsd_seed32(LsdParams p, int
                 ++mine;
             }
         }
-        mine = wave_sum_i(mine);
+        mine = wave_sum_bcast(mine);
         if (lane == 0 && mine) atomicAdd(&n_list, mine);
         __syncthreads();
     } else {
@@ -1905,7 +1866,7 @@ __global__ __launch_bounds__(ST, LF_SEED_OCC) void k_lsd_seed32(LsdParams p, int
             int wbase = 0;
             if (lane == 0 && bo) wbase = atomicAdd(&n_list, __popcll(bo));
             wbase = __builtin_amdgcn_readfirstlane(wbase);
-            if (on) LA[wbase + __popcll(bo & ((1ull << lane) - 1ull))] = item;
+            if (on) LA[wbase + lanes_below(bo, lane)] = item;
         }
         __syncthreads();
         const int nlz = n_list;
@@ -1985,7 +1946,7 @@ __global__ __launch_bounds__(ST, LF_SEED_OCC) void k_std_sort_debug(const uint32
         const uint32_t v = i < n ? E[i] : 0u;
         const bool on = key_of(v) != 0u;
         const unsigned long long bb = __ballot(on);
-        if (on) { const int idx = rowc[r] + __popcll(bb & ((1ull << lane) - 1ull)); W.P0[idx] = (uint32_t)i; W.V0[idx] = v; }
+        if (on) { const int idx = rowc[r] + lanes_below(bb, lane); W.P0[idx] = (uint32_t)i; W.V0[idx] = v; }
     }
     __syncthreads();
     const int m = m_sh;

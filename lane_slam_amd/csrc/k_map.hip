@@ -132,7 +132,7 @@ __global__ __launch_bounds__(kMapWg) void k_map_classify(MapDev m, const uint8_t
         }
     }
     const unsigned long long bal = __ballot(is_app);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    const int before = lanes_below(bal, lane);
     if (lane == 0) wave_count[wave] = __popcll(bal);
     const unsigned long long rbal = __ballot(is_ref);
     __syncthreads();

@@ -15,6 +15,7 @@
 //                  from its h (the same operations, the same bits) and writes the result.  No float atomics anywhere.
 #include "k_map_pairs.h"
 #include "k_map_localize.h"
+#include "wave.h"
 
 namespace lf {
 namespace lo {
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void k_map_localize(lf_localize_config c,
             if (w < wave) place += n;
             all += n;
         }
-        place += __popcll(mask & ((1ull << lane) - 1ull));
+        place += lanes_below(mask, lane);
         if (p.ok && place < max_pairs) {
             cand[place] = p;
             cand_seg[place] = i;

@@ -16,6 +16,7 @@
 #include "k_map_pairs.h"
 #include "k_map_near.h"
 #include "scan.h"
+#include "wave.h"
 
 namespace lf {
 namespace nr {
@@ -98,8 +99,7 @@ __global__ __launch_bounds__(kWg) void k_near_query(Rule c, MapDevice md, Index 
             if (o0 <= i && i < o1) { f = k; break; }
         }
     }
-#pragma unroll
-    for (int d = kGroup / 2; d >= 1; d >>= 1) { const int o = __shfl_xor(f, d); f = o < f ? o : f; }
+    f = wave_reduce<kGroup>(f, op_min());
 
     // the segment in the map frame
     Seg s = { 0.0, 0.0, 0.0, 0.0, 0.0 };

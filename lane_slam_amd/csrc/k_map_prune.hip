@@ -39,7 +39,7 @@ __global__ __launch_bounds__(kWg) void k_prune_rank(int size, const uint8_t* __r
     const int r = l < size ? (int)reason[l] : -1;
     const bool keep = r == kKeep;
     const unsigned long long bal = __ballot(keep);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    const int before = lanes_below(bal, lane);
     if (lane == 0) wave_count[wave] = __popcll(bal);
     if (final_pass) {
         for (int k = kStale; k <= kCovered; ++k) {

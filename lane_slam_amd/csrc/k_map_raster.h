@@ -117,7 +117,7 @@ __device__ inline unsigned wave_add(unsigned* ctr, unsigned t, bool active, int 
         unsigned base = 0;
         if (lane == leader) base = atomicAdd(&ctr[t0], (unsigned)__popcll(same));
         base = (unsigned)__shfl((int)base, leader);
-        if (mine) pos = base + (unsigned)__popcll(same & ((1ull << lane) - 1ull));
+        if (mine) pos = base + lanes_below(same, lane);
         todo &= ~same;
     }
     return pos;

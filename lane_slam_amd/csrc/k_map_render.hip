@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(kWg) k_mr_bounds(const View v, const int has_v
         }
     const unsigned long long b = __ballot(any);
     if (!b) return;
-    for (int d = 32; d; d >>= 1) {
+    for (int d = 32; d; d >>= 1) {            // (the four butterflies step together: as four wave_reduce calls they run one after the other)
         xmin = fmin(xmin, __shfl_xor(xmin, d)); ymin = fmin(ymin, __shfl_xor(ymin, d));
         xmax = fmax(xmax, __shfl_xor(xmax, d)); ymax = fmax(ymax, __shfl_xor(ymax, d));
     }

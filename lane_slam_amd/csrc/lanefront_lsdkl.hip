@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <string>
 #include "lanefront_handle.h"
+#include "wave.h"
 
 using namespace lf;
 
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(64) void k_lsdkl_fill(LsdKlLevels L, int n_octaves,
             bool keep_len = false, keep_mask = false;
             if (l < cnt) lsdkl_line(L, o, f, l, e, len, keep_len, keep_mask);
             const unsigned long long bl = __ballot(keep_len), bo = __ballot(keep_len && keep_mask);
-            const unsigned long long below = (1ull << lane) - 1ull;
+            const unsigned long long below = lane_mask_lt(lane);
             if (keep_len && keep_mask) {
                 const float e0 = e[0], e1 = e[1], e2 = e[2], e3 = e[3];
                 const size_t k = (size_t)base + out0 + __popcll(bo & below);

@@ -29,6 +29,7 @@
 
 #ifndef LF_HOST_SIM
 #include <hip/hip_runtime.h>
+#include "wave.h"
 #define LFG_DEV __device__ __forceinline__
 #define LFG_NL 64
 #else
@@ -50,93 +51,20 @@ constexpr double NOTDEF_D = -1024.0;
 
 // ------------------------------------------------------------------ wave primitives
 #ifndef LF_HOST_SIM
-// the lanes for which p holds, as the condition mask the compiler already has (HIP's __ballot(int) goes through a 0 / 1 register and
-// a compare: three instructions and a vector -> scalar dependency per ballot, eight ballots per accept span)
-LFG_DEV unsigned long long lfg_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+// (cross-lane reads, reductions and uni() are wave.h's; the one-lane host build has its own below, under the same names)
 LFG_DEV int lane_id() { return (int)(threadIdx.x & 63u); }
-LFG_DEV int rl_i(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
-LFG_DEV float rl_f(float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
-LFG_DEV double rl_d(double v, int src)
-{
-    long long b = __double_as_longlong(v);
-    int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), src);
-    int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-// (sums and maxima over the wave use DPP exchanges inside the rows of 16 lanes and scalar registers across the four rows; see
-// wave_max_d below)
-template <int CTRL>
-LFG_DEV int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-LFG_DEV int wave_sum_i(int v)
-{
-    v += dpp_i<0xB1>(v);            // quad_perm [1,0,3,2]
-    v += dpp_i<0x4E>(v);            // quad_perm [2,3,0,1]
-    v += dpp_i<0x141>(v);           // row_half_mirror
-    v += dpp_i<0x140>(v);           // row_mirror: every lane of a row holds the row's sum
-    return rl_i(v, 0) + rl_i(v, 16) + rl_i(v, 32) + rl_i(v, 48);
-}
-// Maximum / minimum of a double over the wave: four DPP exchanges inside the rows of 16 lanes (lane pairs, pairs of pairs,
-// mirrored halves, mirrored rows: afterwards every lane of a row holds the row's value), then the four rows through scalar
-// registers.  (The butterfly of six __shfl_xor is twelve trips through the LDS crossbar per call; region2rect makes four calls
-// per region and most regions are a dozen pixels.)  Order free: the operands are finite.
-template <int CTRL>
-LFG_DEV double dpp_d(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, true);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-LFG_DEV double wave_max_d(double v)
-{
-    double o;
-    o = dpp_d<0xB1>(v); v = o > v ? o : v;           // quad_perm [1,0,3,2]
-    o = dpp_d<0x4E>(v); v = o > v ? o : v;           // quad_perm [2,3,0,1]
-    o = dpp_d<0x141>(v); v = o > v ? o : v;          // row_half_mirror
-    o = dpp_d<0x140>(v); v = o > v ? o : v;          // row_mirror
-    const double r0 = rl_d(v, 0), r1 = rl_d(v, 16), r2 = rl_d(v, 32), r3 = rl_d(v, 48);
-    const double a = r1 > r0 ? r1 : r0, b = r3 > r2 ? r3 : r2;
-    return b > a ? b : a;
-}
-LFG_DEV double wave_min_d(double v)
-{
-    double o;
-    o = dpp_d<0xB1>(v); v = o < v ? o : v;
-    o = dpp_d<0x4E>(v); v = o < v ? o : v;
-    o = dpp_d<0x141>(v); v = o < v ? o : v;
-    o = dpp_d<0x140>(v); v = o < v ? o : v;
-    const double r0 = rl_d(v, 0), r1 = rl_d(v, 16), r2 = rl_d(v, 32), r3 = rl_d(v, 48);
-    const double a = r1 < r0 ? r1 : r0, b = r3 < r2 ? r3 : r2;
-    return b < a ? b : a;
-}
-LFG_DEV int wave_max_i(int v)
-{
-    int o;
-    o = dpp_i<0xB1>(v); v = o > v ? o : v;
-    o = dpp_i<0x4E>(v); v = o > v ? o : v;
-    o = dpp_i<0x141>(v); v = o > v ? o : v;
-    o = dpp_i<0x140>(v); v = o > v ? o : v;
-    const int a = max(rl_i(v, 0), rl_i(v, 16)), b = max(rl_i(v, 32), rl_i(v, 48));
-    return max(a, b);
-}
 LFG_DEV void mem_fence() { __threadfence_block(); }
-// A condition that is the same in every lane, said so: computed from values that live in vector registers (a double compared with a
-// double) it counts as divergent for the compiler, and a loop that can be left through it becomes a loop over an exec mask -- every value
-// it carries (the region size, the phase) moves to vector registers, every inner loop bound becomes a vector compare, every exit a chain
-// of mask operations (13 cycles per dependent scalar instruction for a wave alone on its SIMD, tools/probe/lone_wave_issue.hip).
-LFG_DEV bool uni(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
-LFG_DEV int uni_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
 #else
 LFG_DEV bool uni(bool b) { return b; }
 LFG_DEV int uni_i(int v) { return v; }
-LFG_DEV int wave_max_i(int v) { return v; }
+LFG_DEV int wave_max(int v) { return v; }
 LFG_DEV int lane_id() { return 0; }
-LFG_DEV int rl_i(int v, int) { return v; }
-LFG_DEV float rl_f(float v, int) { return v; }
-LFG_DEV double rl_d(double v, int) { return v; }
-LFG_DEV int wave_sum_i(int v) { return v; }
-LFG_DEV double wave_max_d(double v) { return v; }
-LFG_DEV double wave_min_d(double v) { return v; }
+LFG_DEV int readlane(int v, int) { return v; }
+LFG_DEV float readlane(float v, int) { return v; }
+LFG_DEV double readlane(double v, int) { return v; }
+LFG_DEV int wave_sum(int v) { return v; }
+LFG_DEV double wave_max(double v) { return v; }
+LFG_DEV double wave_min(double v) { return v; }
 LFG_DEV void mem_fence() {}
 #endif
 
@@ -223,12 +151,12 @@ LFG_DEV void reg_set(const Ctx& c, int i, uint32_t v)
 // the store to complete (s_waitcnt vmcnt(0) lgkmcnt(0) in the loop).
 template <bool LO> LFG_DEV uint32_t reg_get_t(const Ctx& c, int i)
 {
-    if (LO) return ((__attribute__((address_space(3))) uint32_t*)c.lreg)[i];
+    if (LO) return as_lds<lds_u32>(c.lreg)[i];
     return reg_get(c, i);
 }
 template <bool LO> LFG_DEV void reg_put_t(const Ctx& c, int i, uint32_t v)       // the calling lane's slot
 {
-    if (LO) ((__attribute__((address_space(3))) uint32_t*)c.lreg)[i] = v;
+    if (LO) as_lds<lds_u32>(c.lreg)[i] = v;
     else if (i < c.reg_lds) c.lreg[i] = v; else c.greg[i] = v;
 }
 #endif
@@ -291,33 +219,31 @@ LFG_DEV int find_e(const Ctx& c, int x, int y)
 // k_lsd_grow<false> (every problem of the 640x480 geometries) sets used_lds to "infinite": the HBM halves fold away and these
 // are plain LDS operations -- kernel alone 2.79 -> 2.61 ms, +3 % frames/s (same-call A/B; the same treatment of the region
 // lists, whose HBM tail is real, measured slower: the per-lane branch costs more than the flat access).
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-LFG_DEV lds_u32* as_lds(uint32_t* p) { return (lds_u32*)p; }
 // (`e < 0x7fffffff` does not fold -- e might be INT_MAX for all the compiler knows -- and left a branch and the global half of
 // every USED operation in the all-in-LDS kernels; the equality does)
 LFG_DEV bool used_in_lds(const Ctx& c, int e) { return c.used_lds == 0x7fffffff || e < c.used_lds; }
 LFG_DEV bool used_get(const Ctx& c, int e)
 {
     uint32_t w;
-    if (used_in_lds(c, e)) w = as_lds(c.usedc)[e >> 5]; else w = c.gused[e >> 5];
+    if (used_in_lds(c, e)) w = as_lds<lds_u32>(c.usedc)[e >> 5]; else w = c.gused[e >> 5];
     return (w >> (e & 31)) & 1u;
 }
 // atomics without return value: no read-modify-write round trip on the sequential path
 LFG_DEV void used_or(const Ctx& c, int e)                // the calling lane's entry
 {
-    if (used_in_lds(c, e)) __hip_atomic_fetch_or(as_lds(c.usedc) + (e >> 5), 1u << (e & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (used_in_lds(c, e)) __hip_atomic_fetch_or(as_lds<lds_u32>(c.usedc) + (e >> 5), 1u << (e & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     else atomicOr(&c.gused[e >> 5], 1u << (e & 31));
 }
 LFG_DEV void used_set(const Ctx& c, int e) { if (lane_id() == 0) used_or(c, e); }
 LFG_DEV void used_and(const Ctx& c, int e)               // the calling lane's entry
 {
-    if (used_in_lds(c, e)) __hip_atomic_fetch_and(as_lds(c.usedc) + (e >> 5), ~(1u << (e & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (used_in_lds(c, e)) __hip_atomic_fetch_and(as_lds<lds_u32>(c.usedc) + (e >> 5), ~(1u << (e & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     else atomicAnd(&c.gused[e >> 5], ~(1u << (e & 31)));
 }
 LFG_DEV void used_clr(const Ctx& c, int e)
 {
     if (lane_id() == 0) {
-        if (used_in_lds(c, e)) __hip_atomic_fetch_and(as_lds(c.usedc) + (e >> 5), ~(1u << (e & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (used_in_lds(c, e)) __hip_atomic_fetch_and(as_lds<lds_u32>(c.usedc) + (e >> 5), ~(1u << (e & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         else atomicAnd(&c.gused[e >> 5], ~(1u << (e & 31)));
     }
 }
@@ -446,7 +372,7 @@ LFG_DEV void region_grow(const Ctx& c, int sx, int sy, int seed_e, int& reg_size
     {
         const int ax = k9 - 4, ay = slot - 3;
         const bool adj = lane < 63 && ax >= -1 && ax <= 1 && ay >= -1 && ay <= 1 && (ax != 0 || ay != 0);
-        firstm = lfg_ballot(adj && w_e >= 0 && !used_get(c, w_e));                          // (measured: without the branch around the LDS read, + 2 %)
+        firstm = wave_ballot(adj && w_e >= 0 && !used_get(c, w_e));                          // (measured: without the branch around the LDS read, + 2 %)
         if (c.min_reg_size > 1 && firstm == 0ull) {
             reg_size = 1;
             reg_angle = NOTDEF_D;
@@ -513,7 +439,7 @@ LFG_DEV void region_grow(const Ctx& c, int sx, int sy, int seed_e, int& reg_size
         dg = __shfl(w_deg, widx);
         ck = __shfl(w_cs, widx); sk = __shfl(w_sn, widx);
         LFG_T1(c, 12)
-        LFG_CNT(c, 15, lfg_ballot(inb && !inwin) != 0ull)
+        LFG_CNT(c, 15, wave_ballot(inb && !inwin) != 0ull)
         if (!inwin) {
             e = inb ? find_e(c, xx, yy) : -1;
             if (e >= 0) { dg = c.deg[e]; cs_sn(c, e, ck, sk); }      // fetched whether USED or not: the USED test below is an LDS round trip that need not sit in front of the trip to the compact arrays
@@ -521,7 +447,7 @@ LFG_DEV void region_grow(const Ctx& c, int sx, int sy, int seed_e, int& reg_size
         // the candidates -- defined and free at batch start -- as a LANE MASK (wave-uniform integers from here on: a per-lane bool
         // that survives a branch comes back through a 0 / 1 register and a compare every time it is balloted, three instructions
         // and a vector -> scalar dependency, eight times per span)
-        candm = lfg_ballot((e >= 0) & !used_get(c, e < 0 ? 0 : e));      // (no branch around the LDS read)
+        candm = wave_ballot((e >= 0) & !used_get(c, e < 0 ? 0 : e));      // (no branch around the LDS read)
         }
         const double a = (double)dg * DEG2RAD;
         LFG_T1(c, 13)
@@ -559,7 +485,7 @@ LFG_DEV void region_grow(const Ctx& c, int sx, int sy, int seed_e, int& reg_size
             unsigned long long nearM = 0ull, midM = ~0ull;    // everything undecided = the reference's loop, lane by lane
             if (bulk_ok) {
                 // division free: ad <= prec - EPS - (pi/2) m / smax  <=>  (ad - prec + EPS) smax + (pi/2) m <= 0
-                const float hm = 1.5707964f * (float)(int)__popcll(lfg_ballot(ad <= precf) & cb);
+                const float hm = 1.5707964f * (float)(int)__popcll(wave_ballot(ad <= precf) & cb);
                 const float sx_ = sumdx < 0.f ? -sumdx : sumdx, sy_ = sumdy < 0.f ? -sumdy : sumdy;
                 const float smax = sx_ > sy_ ? sx_ : sy_;
                 // the pair with the wider near band, chosen by SELECTS: both pairs as thresholds (delta a shade above (pi/2) m / smax -- the
@@ -569,8 +495,8 @@ LFG_DEV void region_grow(const Ctx& c, int sx, int sy, int seed_e, int& reg_size
                 const float tn_mag = precf - EPSF - delta;
                 const bool mag = tn_mag > tn_cone;
                 const float tn = mag ? tn_mag : tn_cone, tf = mag ? precf + EPSF + delta : tf_cone;
-                nearM = lfg_ballot(ad <= tn);
-                midM = ~nearM & lfg_ballot(ad <= tf);
+                nearM = wave_ballot(ad <= tn);
+                midM = ~nearM & wave_ballot(ad <= tf);
             }
             const unsigned long long maskM = midM & cb;
             // the span = the lanes in front of the first undecided one (all of them when there is none): the bits below maskM's lowest
@@ -583,7 +509,7 @@ LFG_DEV void region_grow(const Ctx& c, int sx, int sy, int seed_e, int& reg_size
                 if (maskN & (maskN - 1ull)) {
                     for (unsigned long long mm = maskN; mm != 0ull;) {
                         const int j = __builtin_ctzll(mm);
-                        const unsigned long long same = lfg_ballot(key == (uint32_t)rl_i((int)key, j)) & mm & ~(1ull << j);
+                        const unsigned long long same = wave_ballot(key == (uint32_t)readlane((int)key, j)) & mm & ~(1ull << j);
                         maskA &= ~same;
                         mm &= ~(same | (1ull << j));
                     }
@@ -599,8 +525,8 @@ LFG_DEV void region_grow(const Ctx& c, int sx, int sy, int seed_e, int& reg_size
                 // the float sums take the accepted vectors in list order: (float)((double)sum + cos), one by one
                 for (unsigned long long mm = maskA; mm != 0ull; mm &= mm - 1ull) {
                     const int j = __builtin_ctzll(mm);
-                    sumdx = (float)((double)sumdx + rl_d(ck, j));
-                    sumdy = (float)((double)sumdy + rl_d(sk, j));
+                    sumdx = (float)((double)sumdx + readlane(ck, j));
+                    sumdy = (float)((double)sumdy + readlane(sk, j));
                 }
                 reg_angle = (double)dm::fast_atan2_deg(sumdy, sumdx) * DEG2RAD;
                 added = true;
@@ -612,7 +538,7 @@ LFG_DEV void region_grow(const Ctx& c, int sx, int sy, int seed_e, int& reg_size
                 // later offers of the pixels just accepted are no longer candidates (measured: striking them by key in the loop
                 // above instead of this trip to the USED bits made the kernel 1.5 % slower)
                 mem_fence();
-                candm &= ~lfg_ballot((e >= 0) & used_get(c, e < 0 ? 0 : e));
+                candm &= ~wave_ballot((e >= 0) & used_get(c, e < 0 ? 0 : e));
             }
             // the undecided lane: the reference's comparison under the angle of this moment
             // (measured: the same comparison on lane L's angle as a wave-uniform value -- readlane, scalar branches -- made the
@@ -622,7 +548,7 @@ LFG_DEV void region_grow(const Ctx& c, int sx, int sy, int seed_e, int& reg_size
             // of all spans on the refined, narrow-tolerance growths).  (`later` is settled before the branch: nothing of this is live
             // across the accept code)
             const bool hitL = [&]() {
-                const unsigned long long hits = lfg_ballot(aligned_val(a, reg_angle, prec)) & candm;
+                const unsigned long long hits = wave_ballot(aligned_val(a, reg_angle, prec)) & candm;
                 const unsigned long long behind = ~(maskM ^ (maskM - 1ull));     // the lanes behind the undecided one
                 const bool hit = (hits >> L) & 1ull;
                 const unsigned long long h2 = hits & behind;
@@ -630,15 +556,15 @@ LFG_DEV void region_grow(const Ctx& c, int sx, int sy, int seed_e, int& reg_size
                 return hit;
             }();
             if (hitL) {
-                const int eL = rl_i(e, L);
-                const int ay = rl_i(yy, L), ax = rl_i(xx, L);
+                const int eL = readlane(e, L);
+                const int ay = readlane(yy, L), ax = readlane(xx, L);
                 used_set(c, eL);
                 if (lane == 0) reg_put_t<LO>(c, n, ((uint32_t)ay << 16) | (uint32_t)ax);
                 ++n;
-                sumdx = (float)((double)sumdx + rl_d(ck, L));
-                sumdy = (float)((double)sumdy + rl_d(sk, L));
+                sumdx = (float)((double)sumdx + readlane(ck, L));
+                sumdy = (float)((double)sumdy + readlane(sk, L));
                 reg_angle = (double)dm::fast_atan2_deg(sumdy, sumdx) * DEG2RAD;
-                candm &= ~lfg_ballot(e == eL);            // the same pixel seen from a later point is now USED
+                candm &= ~wave_ballot(e == eL);            // the same pixel seen from a later point is now USED
                 added = true;
                 LFG_CNT(c, 19, 1)
             } else { LFG_CNT(c, 29, 1) }
@@ -749,14 +675,14 @@ LFG_DEV void region2rect_t(const Ctx& c, int reg_size, double reg_angle, double 
         ordered_sums3(acc, xw, yw, w, cnt);
 #else
         for (int j = 0; j < cnt; ++j) {
-            x += rl_d(xw, j);
-            y += rl_d(yw, j);
-            sum += rl_d(w, j);
+            x += readlane(xw, j);
+            y += readlane(yw, j);
+            sum += readlane(w, j);
         }
 #endif
     }
 #ifndef LF_HOST_SIM
-    x = rl_d(acc, 0); y = rl_d(acc, 1); sum = rl_d(acc, 2);
+    x = readlane(acc, 0); y = readlane(acc, 1); sum = readlane(acc, 2);
     acc = 0.0;
 #endif
     x /= sum;
@@ -780,14 +706,14 @@ LFG_DEV void region2rect_t(const Ctx& c, int reg_size, double reg_angle, double 
         ordered_sums3(acc, tyy, txx, -txy, cnt);             // (Ixy -= t is Ixy += -t, bit for bit)
 #else
         for (int j = 0; j < cnt; ++j) {
-            Ixx += rl_d(tyy, j);
-            Iyy += rl_d(txx, j);
-            Ixy -= rl_d(txy, j);
+            Ixx += readlane(tyy, j);
+            Iyy += readlane(txx, j);
+            Ixy -= readlane(txy, j);
         }
 #endif
     }
 #ifndef LF_HOST_SIM
-    Ixx = rl_d(acc, 0); Iyy = rl_d(acc, 1); Ixy = rl_d(acc, 2);
+    Ixx = readlane(acc, 0); Iyy = readlane(acc, 1); Ixy = readlane(acc, 2);
 #endif
     const double lambda = 0.5 * (Ixx + Iyy - dm::dsqrt((Ixx - Iyy) * (Ixx - Iyy) + 4.0 * Ixy * Ixy));
     double theta = (dabs(Ixx) > dabs(Iyy)) ? (double)dm::fast_atan2_deg((float)(lambda - Ixx), (float)Ixy)
@@ -807,8 +733,8 @@ LFG_DEV void region2rect_t(const Ctx& c, int reg_size, double reg_angle, double 
         if (l > l_max) l_max = l; else if (l < l_min) l_min = l;
         if (w > w_max) w_max = w; else if (w < w_min) w_min = w;
     }
-    l_max = wave_max_d(l_max); l_min = wave_min_d(l_min);
-    w_max = wave_max_d(w_max); w_min = wave_min_d(w_min);
+    l_max = wave_max(l_max); l_min = wave_min(l_min);
+    w_max = wave_max(w_max); w_min = wave_min(w_min);
     rec.x1 = x + l_min * dx;
     rec.y1 = y + l_min * dy;
     rec.x2 = x + l_max * dx;
@@ -864,7 +790,7 @@ LFG_DEV void reduce_radius_step(const Ctx& c, int& reg_size, double xc, double y
         const int px = (int)(pk & 0xffffu), py = (int)(pk >> 16);
         const bool out = v && dist_sq(xc, yc, (double)px, (double)py) > radSq;
         if (out) used_and(c, find_e(c, px, py));
-        m += __popcll(lfg_ballot(v && !out));
+        m += __popcll(wave_ballot(v && !out));
     }
     if (m == n) return;
     int hb = 0, fb = n;                 // front places scanned so far: [0, hb); back places scanned so far: [fb, n)
@@ -876,7 +802,7 @@ LFG_DEV void reduce_radius_step(const Ctx& c, int& reg_size, double xc, double y
             const bool v = i < m;
             const uint32_t pk = v ? reg_get(c, i) : 0u;
             const bool out = v && dist_sq(xc, yc, (double)(int)(pk & 0xffffu), (double)(int)(pk >> 16)) > radSq;
-            const unsigned long long mk = lfg_ballot(out);
+            const unsigned long long mk = wave_ballot(out);
             hq = wave_compact(i, mk);
             nh = __popcll(mk);
             hb += LFG_NL;
@@ -888,7 +814,7 @@ LFG_DEV void reduce_radius_step(const Ctx& c, int& reg_size, double xc, double y
             const bool v = i >= m;
             const uint32_t pk = v ? reg_get(c, i) : 0u;
             const bool keep = v && !(dist_sq(xc, yc, (double)(int)(pk & 0xffffu), (double)(int)(pk >> 16)) > radSq);
-            const unsigned long long mk = lfg_ballot(keep);
+            const unsigned long long mk = wave_ballot(keep);
             fq = wave_compact((int)pk, mk);
             nf = __popcll(mk);
             fb -= LFG_NL;
@@ -954,9 +880,9 @@ LFG_DEV double refine_tau(const Ctx& c, int reg_size, const Rect& rec, int& x0, 
             ang_d = diff; ang_d2 = diff * diff;
         }
         ordered_sums3(acc, ang_d, ang_d2, -0.0, cnt);
-        n += __popcll(lfg_ballot(sel));
+        n += __popcll(wave_ballot(sel));
     }
-    sum = rl_d(acc, 0); s_sum = rl_d(acc, 1);
+    sum = readlane(acc, 0); s_sum = readlane(acc, 1);
 #else
     for (int base = 0; base < reg_size; base += LFG_NL) {
         const int i = base + lane;
@@ -967,13 +893,13 @@ LFG_DEV double refine_tau(const Ctx& c, int reg_size, const Rect& rec, int& x0, 
         const float af = v ? c.deg[ei] : NOTDEF_F;
         const int cnt = reg_size - base < LFG_NL ? reg_size - base : LFG_NL;
         for (int j = 0; j < cnt; ++j) {
-            const uint32_t q = (uint32_t)rl_i((int)pk, j);
+            const uint32_t q = (uint32_t)readlane((int)pk, j);
             const int qx = (int)(q & 0xffffu), qy = (int)(q >> 16);
 #ifdef LF_HOST_SIM
-            used_clr(c, rl_i(ei, j));
+            used_clr(c, readlane(ei, j));
 #endif
             if (dist_(xc, yc, (double)qx, (double)qy) < rec.width) {
-                const double angle = angle_of(rl_f(af, j));
+                const double angle = angle_of(readlane(af, j));
                 const double ang_d = angle_diff_signed(angle, ang_c);
                 sum += ang_d;
                 s_sum += ang_d * ang_d;
@@ -1206,8 +1132,8 @@ LFG_DEV double rect_nfa(const Ctx& c, const Rect& rec)
             if (stop) break;
         }
     }
-    total_pts = wave_sum_i(total_pts);
-    alg_pts = wave_sum_i(alg_pts);
+    total_pts = wave_sum(total_pts);
+    alg_pts = wave_sum(alg_pts);
     LFG_T1(c, 4)
 #if defined(LFG_STAMPS) && !defined(LF_HOST_SIM)
     c.stamps[7] += (1ull << 40) + (unsigned long long)total_pts;
@@ -1359,7 +1285,7 @@ LFG_DEV void rect_nfa5(const Ctx& c, const Rect& base, int stage, bool* valid, d
         }
     }
 #pragma unroll
-    for (int k = 0; k < 5; ++k) { tot[k] = wave_sum_i(tot[k]); alg[k] = wave_sum_i(alg[k]); }
+    for (int k = 0; k < 5; ++k) { tot[k] = wave_sum(tot[k]); alg[k] = wave_sum(alg[k]); }
     LFG_T1(c, 4)
 #if defined(LFG_STAMPS) && !defined(LF_HOST_SIM)
     c.stamps[7] += (1ull << 40) + (unsigned long long)tot[0];
@@ -1375,7 +1301,7 @@ LFG_DEV void rect_nfa5(const Ctx& c, const Rect& base, int stage, bool* valid, d
     if (g > 4) on = false;
     const double r = on ? nfa(c, n_, k_, p_) : -1e300;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) v[k] = rl_d(r, 8 * k);
+    for (int k = 0; k < 5; ++k) v[k] = readlane(r, 8 * k);
 #else
     for (int k = 0; k < 5; ++k) v[k] = valid[k] ? nfa(c, tot[k], alg[k], pp[k]) : -1e300;
 #endif
@@ -1530,19 +1456,19 @@ LFG_DEV int detect(const Ctx& c, const uint32_t* order, int n_order, float* line
         const uint32_t seed_xy = sv ? c.gxy[my_e] : 0u;               // beside the label, not behind it: one round trip per chunk less
         const float seed_dg = sv ? c.deg[my_e] : 0.f;                  // ... and the seed's angle (region_grow: pre_deg)
         if (sv && c.label) sv = (int)c.label[my_e] == c.root;          // seeds of other components are not ours
-        const unsigned long long svm = lfg_ballot(sv);                 // our seeds of this chunk, as a lane mask (see the accept loop)
+        const unsigned long long svm = wave_ballot(sv);                 // our seeds of this chunk, as a lane mask (see the accept loop)
         if (svm == 0ull) continue;
         LFG_T1(c, 8)
         unsigned long long pending = ~0ull;
       for (;;) {
         mem_fence();
-        const unsigned long long fr = svm & ~lfg_ballot(used_get(c, my_e)) & pending;      // (lanes without a seed read entry 0: masked)
+        const unsigned long long fr = svm & ~wave_ballot(used_get(c, my_e)) & pending;      // (lanes without a seed read entry 0: masked)
         if (fr == 0ull) break;
         const int sl = __builtin_ctzll(fr);
         pending = sl >= 63 ? 0ull : (~0ull << (sl + 1));
-        const int se = rl_i(my_e, sl);
-        const uint32_t sxy = (uint32_t)rl_i((int)seed_xy, sl);
-        const float sdg = rl_f(seed_dg, sl);
+        const int se = readlane(my_e, sl);
+        const uint32_t sxy = (uint32_t)readlane((int)seed_xy, sl);
+        const float sdg = readlane(seed_dg, sl);
         const int tag = base + sl;
         LFG_T1(c, 0)
 #else

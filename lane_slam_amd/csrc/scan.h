@@ -10,11 +10,14 @@
 //                                                   the form for "offsets from counts" kernels.  A kernel that packs several
 //                                                   values per thread (k_near_scan, k_mr_scan) calls wg_excl_scan on the sums.
 //
-// k_lsd_seed32.hip deliberately keeps a scan family of its own (scan, sum and minimum in DPP row operations, with its LDS
-// address-space helpers): it runs as a lone wave, where each __shfl_up goes through the LDS crossbar (ds_bpermute_b32) at about a
-// hundred cycles.  Whether another kernel gains from the DPP form is a question of speed, to be tried in wave_incl_scan alone.
+// wave_incl_scan_dpp(v) is the same scan in DPP row operations (wave.h's wave_incl_dpp: four row shifts, two row broadcasts, ~50
+// cycles).  Which form where: a __shfl_up goes through the LDS crossbar (ds_bpermute_b32), which a wave among many on its SIMD
+// hides behind the other waves and a lone wave waits out at about a hundred cycles a step.  So k_lsd_seed32, whose partitions are
+// chains of scans run by a lone wave, uses the DPP form, and every other kernel the __shfl_up form.  Whether another kernel gains
+// from the DPP form is a question of speed, to be tried at that site.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "wave.h"
 
 namespace lf {
 
@@ -26,6 +29,8 @@ __device__ __forceinline__ T wave_incl_scan(T v, int lane)
     for (int d = 1; d < 64; d <<= 1) { const T o = __shfl_up(v, d); if (lane >= d) v += o; }
     return v;
 }
+// the same for an int in DPP row operations: for a lone wave (above)
+__device__ __forceinline__ int wave_incl_scan_dpp(int v) { return wave_incl_dpp<0>(v, op_add()); }
 
 // exclusive scan of v over a workgroup of kThreads threads that all call this together; wave_sum: kThreads / 64 words of LDS;
 // *total: the sum, the same in every thread

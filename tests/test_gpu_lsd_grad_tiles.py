@@ -137,6 +137,21 @@ def test_single_pixels_beside_the_seams(cases):
     assert n_defined > 0
 
 
+@pytest.mark.parametrize("y,x,blob,lane", [(35, 1, [[1, 1, 0]], 0), (47, 78, [[0, 0, 1], [0, 1, 0], [1, 1, 1]], 63)])
+def test_the_largest_gradient_in_the_first_and_the_last_lane_of_a_tile(cases, y, x, blob, lane):
+    """The problem's largest gradient, which scales the seed order's bins, is a maximum over a tile's wave: here one pixel holds
+    it alone, and that pixel is the wave's lane 0 / lane 63 (pixel i of a tile, row-major, belongs to lane i % 64)."""
+    case = cases(GEOMETRIES[0])
+    img = np.zeros((case.fe.rows, case.fe.cols), np.uint8)
+    blob = np.array(blob, np.uint8) * 255
+    img[y:y + blob.shape[0], x:x + blob.shape[1]] = blob
+    planes = _oracle_planes(case.o, img)
+    mod = np.where(planes[3], planes[1], -1.0)
+    ys, xs = np.nonzero(mod == mod.max())
+    assert len(ys) == 1 and ((ys[0] % TILE) * TILE + xs[0] % TILE) % 64 == lane, (ys, xs)
+    _check(case, img, (y, x), planes)
+
+
 def test_empty_image_lists_no_tile(cases):
     case = cases(GEOMETRIES[0])
     img = np.zeros((case.fe.rows, case.fe.cols), np.uint8)

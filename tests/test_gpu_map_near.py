@@ -138,6 +138,22 @@ def test_colour_gating(gating):
     a.close()
 
 
+# k_near_query finds a segment's frame as a minimum over its group of sixteen lanes (lane g looks at frames g, g + 16, ...), four
+# groups to a wave.  With one or two segments a frame, the segments of frames 15 | 16 and 31 | 32 sit in neighbouring groups: the
+# last lane of one holds 15 (31), the first lane of the next 16 (32), and a minimum that reached across would take the
+# neighbour's lower frame and with it the neighbour's pose.
+def test_frames_in_the_first_and_last_lane_of_a_group():
+    (code, color, ground), seg, poses = N.small_case(27, ns=40, n_frames=33)
+    m, size = N.make_map(code, color, ground)
+    fr = N.frame_of(seg.frame_offset, seg.n)
+    edge = np.isin(fr, (0, 15, 16, 31, 32))
+    assert len(set(fr[edge])) == 5 and len(set(np.round(poses[:, 2], 3))) == 33
+    a = seeded(m, size)
+    got = check(a, seg, poses, **N.WIDE)
+    assert (got[2][edge] > 0).all()
+    a.close()
+
+
 def test_min_hits_on_a_merge_map_whose_hits_vary():
     (code, color, ground), seg, poses = N.small_case(22)
     a = LineAssociator(capacity=512, policy="merge", merge_distance=0, kept_only=False, when_full="error")

@@ -335,6 +335,21 @@ def test_bounds():
     e.close()
 
 
+@pytest.mark.parametrize("where", [(0, 63, 64, 127), (63, 0, 127, 64), (64, 127, 0, 63), (127, 64, 63, 0)])
+def test_bounds_that_one_lane_at_the_end_of_a_wave_holds(where):
+    """Each of the four bounds is a minimum or maximum over a wave of 64 entries: here each is held by one entry alone, and the four
+    sit in the first and the last lane of the map's first two waves."""
+    rng = np.random.default_rng(33)
+    g = rng.uniform(10.0, 20.0, (128, 4))
+    g[where[0], 0], g[where[1], 3], g[where[2], 2], g[where[3], 1] = 3.25, 41.5, 57.75, -8.125      # x_min, y_max, x_max, y_min
+    a = make_map([], capacity=128, seed=(g, np.zeros(128, np.uint8)))
+    m = fetched(a)
+    got = a.bounds()
+    assert got == R.bounds(m["ground"], m["color"], m["hits"], m["last_seen"]) and got[1] == 128
+    assert sorted(got[0]) == [-8.125, 3.25, 41.5, 57.75]
+    a.close()
+
+
 def test_view_fit_puts_every_selected_endpoint_inside():
     rng = np.random.default_rng(31)
     g = rng.uniform(-40, 90, (50, 4)) * np.array([1, 0.3, 1, 0.3])

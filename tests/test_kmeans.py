@@ -81,6 +81,31 @@ def test_gpu_kmeans_is_bit_identical_to_oracle(golden, k):
             assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and got[2] == want[2] and got[3] == want[3]
 
 
+def _lone_member_points(first):
+    """128 points, one per thread of the fit's first two waves: cluster 0 is the point of lane 0 alone and cluster 1 the point of
+    lane 63 alone, in the wave that starts at point `first`; clusters 2 and 3 share the rest."""
+    rng = np.random.default_rng(41)
+    pts = np.where(rng.random((128, 1)) < 0.5, [[200, 40, 40]], [[40, 40, 200]]).astype(np.uint8) + rng.integers(0, 9, (128, 3), dtype=np.uint8)
+    pts[first] = (40, 200, 40)
+    pts[first + 63] = (250, 250, 250)
+    return pts, [[40, 200, 40], [250, 250, 250], [200, 40, 40], [40, 40, 200]]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("first", (0, 64))
+def test_gpu_kmeans_counts_a_cluster_that_one_lane_at_the_end_of_a_wave_holds(first):
+    """A cluster's count and colour sums are sums over a wave (KmAcc::flush): here the whole sum is one lane's, the wave's first or
+    last."""
+    from lane_slam_amd import FrontEnd, default_config
+    pts, init = _lone_member_points(first)
+    want = O.kmeans(pts, init)
+    assert list(want[1][:2]) == [1, 1] and np.array_equal(want[0][0], pts[first]) and np.array_equal(want[0][1], pts[first + 63])
+    fe = FrontEnd(default_config("parity"), max_frames=1, max_lines_per_color=64)
+    got = fe.kmeans(pts, init)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and got[2] == want[2] and got[3] == want[3]
+    fe.close()
+
+
 @pytest.mark.gpu
 def test_runKMeans_mirrors_the_reference_interface(golden):
     from lane_slam_amd import anti_instagram as ai
