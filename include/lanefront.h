@@ -1371,6 +1371,47 @@ LF_API int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t bytes);
  * which = 0 exp 1 log 2 sin 3 cos 4 atan 5 asin 6 log10 7 sinh_small 8 atan2(a,b) 9 pow(a,b)
  *         10 sqrt 11 a/b 12 fastAtan2(float a, float b) 13 sqrtf 14 float a/b */
 LF_API int lf_debug_detmath(lf_handle* h, int which, const double* a, const double* b_or_null, double* y, int n);
+/* one cross-lane primitive of csrc/wave.h or csrc/scan.h alone, on the caller's values (host arrays), for the tests:
+ *   op                        type (value of one slot)        arg                              out plane 0 [, 1]
+ *   LF_WAVE_READLANE          any of the six                  source lane 0 .. 63              readlane(v, arg)
+ *   LF_WAVE_DPP               INT, LONG, DOUBLE               control index | BOUND_CTRL << 8  dpp<CTRL, ROW_MASK, BOUND_CTRL>(old, v), old = bits
+ *                                                                                              0xA5C3F00D9E3779B9; index 0 .. 9 = 0xB1 0x4E 0x141 0x140
+ *                                                                                              0x111 0x112 0x114 0x118, 0x142 (rows 0xa), 0x143 (rows 0xc)
+ *   LF_WAVE_SUM               INT, LONG                       0                                wave_sum(v)
+ *   LF_WAVE_MAX               INT, DOUBLE                     0                                wave_max(v)
+ *   LF_WAVE_MIN               DOUBLE                          0                                wave_min(v)
+ *   LF_WAVE_INCL_SCAN_DPP     INT                             0                                wave_incl_scan_dpp(v)
+ *   LF_WAVE_INCL_MIN_DPP      INT                             0                                wave_incl_dpp<INT_MAX>(v, op_min)
+ *   LF_WAVE_SUM_BCAST, LF_WAVE_MIN_BCAST   INT                0                                wave_sum_bcast(v), wave_min_bcast(v)
+ *   LF_WAVE_INCL_SCAN         INT, UINT, ULONG                0                                wave_incl_scan(v, lane)
+ *   LF_WAVE_REDUCE            any of the six                  kWidth | (0 add 1 min 2 max) << 8    wave_reduce<kWidth>(v, op)
+ *   LF_WAVE_BALLOT            ULONG                           0                                wave_ballot(v & 1)
+ *   LF_WAVE_LANE_MASK_LT      ULONG                           0                                lane_mask_lt(lane)
+ *   LF_WAVE_LANES_BELOW       ULONG (a ballot)                0                                lanes_below(v, lane), lanes_below_me(v)
+ *   LF_WAVE_BALLOT_BRANCH     ULONG                           0                                inside `if (v & 2)`: wave_ballot(v & 1), lanes_below_me
+ *                                                                                              of it; all ones in the lanes outside
+ *   LF_WAVE_UNI               ULONG                           0                                uni_i(low half) | uni(bit 32) << 32 with every lane
+ *                                                                                              active; inside `if (bit 63)`, uni_i(~low half) |
+ *                                                                                              uni(bit 33) << 32 (all ones in the lanes outside)
+ *   LF_WAVE_WG_EXCL_SCAN      INT, UINT, ULONG                calls 1 .. 3                     wg_excl_scan<block> `arg` times back to back over the same
+ *                                                                                              LDS words, call c on in plane c: planes 2c (the scan) and
+ *                                                                                              2c + 1 (the total, from every thread)
+ *   LF_WAVE_WG_SCAN_TURNS     INT, UINT, ULONG                count 0 .. 4 * block             wg_scan_turns<block>(count) in place: workgroup b scans
+ *                                                                                              slots [4 * block * b, + count) of in's 4 planes taken as one
+ *                                                                                              array; they come back in out's planes 0 .. 3, the total from
+ *                                                                                              every thread in plane 4
+ * in: 4 planes, out: 6 planes of n_threads 8-byte slots, one slot per thread and plane, a value as its bits (32-bit types in the low
+ * half, the high half 0 on output); planes an operation does not write come back 0.  diverge = 1 (not the two workgroup scans): the
+ * odd lanes take their input from in's plane 1, inside a lane-dependent branch just before the call.  block: the workgroup size,
+ * 64, 256 or 1024; n_threads: a multiple of it, at most 65536. */
+enum { LF_WAVE_INT = 0, LF_WAVE_UINT = 1, LF_WAVE_FLOAT = 2, LF_WAVE_DOUBLE = 3, LF_WAVE_LONG = 4, LF_WAVE_ULONG = 5 };
+enum {
+    LF_WAVE_READLANE = 0, LF_WAVE_DPP = 1, LF_WAVE_SUM = 2, LF_WAVE_MAX = 3, LF_WAVE_MIN = 4, LF_WAVE_INCL_SCAN_DPP = 5,
+    LF_WAVE_INCL_MIN_DPP = 6, LF_WAVE_SUM_BCAST = 7, LF_WAVE_MIN_BCAST = 8, LF_WAVE_INCL_SCAN = 9, LF_WAVE_REDUCE = 10,
+    LF_WAVE_BALLOT = 11, LF_WAVE_LANE_MASK_LT = 12, LF_WAVE_LANES_BELOW = 13, LF_WAVE_BALLOT_BRANCH = 14, LF_WAVE_UNI = 15,
+    LF_WAVE_WG_EXCL_SCAN = 16, LF_WAVE_WG_SCAN_TURNS = 17
+};
+LF_API int lf_debug_wave(lf_handle* h, int op, int type, int arg, int diverge, const uint64_t* in, uint64_t* out, int n_threads, int block);
 /* counter calibration: stream `bytes` of a scratch buffer `reps` times with `width` (4 / 8 / 12 / 16) bytes per lane
  * per access (write != 0: stores, 4 or 16); run under `rocprofv3 --pmc FETCH_SIZE` / `WRITE_SIZE` (tools/fetch_probe.py) */
 LF_API int lf_debug_probe(lf_handle* h, int width, int write, size_t bytes, int reps);

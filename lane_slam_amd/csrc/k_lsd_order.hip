@@ -126,12 +126,14 @@ __device__ __forceinline__ void stable_pass5(const uint32_t* src, Dst* dst, int 
         __builtin_amdgcn_wave_barrier();
     }
     __syncthreads();
-    if (t < 32) {
+    if (t < 64) {                                    // the whole first wave scans (scan.h: every lane active); lanes 32 .. 63 add 0
         uint32_t tot = 0;
-        for (int k = 0; k < W; ++k) tot += wrun[k * 32 + t];
+        if (t < 32)
+            for (int k = 0; k < W; ++k) tot += wrun[k * 32 + t];
         uint32_t inc = (uint32_t)wave_incl_scan((int)tot, t);
         uint32_t run = inc - tot;
-        for (int k = 0; k < W; ++k) { wbase[k * 32 + t] = run; run += wrun[k * 32 + t]; }
+        if (t < 32)
+            for (int k = 0; k < W; ++k) { wbase[k * 32 + t] = run; run += wrun[k * 32 + t]; }
     }
     __syncthreads();
 #pragma unroll

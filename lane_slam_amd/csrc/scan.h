@@ -15,6 +15,11 @@
 // hides behind the other waves and a lone wave waits out at about a hundred cycles a step.  So k_lsd_seed32, whose partitions are
 // chains of scans run by a lone wave, uses the DPP form, and every other kernel the __shfl_up form.  Whether another kernel gains
 // from the DPP form is a question of speed, to be tried at that site.
+//
+// Precondition, for all of them: every lane of the wave is active at the call (wave.h), and for the two workgroup forms every
+// thread of the workgroup reaches the call (they hold barriers): uniform control flow, no early return above, a lane or thread
+// with nothing to add passes 0.  wg_excl_scan begins with a barrier of its own, so it may be called again at once with the same
+// wave_sum words.  Tested alone, with wave.h, by tests/test_gpu_wave_scan.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "wave.h"

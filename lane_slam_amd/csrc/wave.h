@@ -15,6 +15,15 @@
 //                                          of kWidth lanes; every lane of a group ends with the group's value.  For a wave among
 //                                          many, whose neighbours hide the crossbar's latency.
 //   lanes_below(ballot, lane)              this lane's rank among the lanes of a ballot (lanes_below_me(ballot): by v_mbcnt)
+//
+// Precondition: dpp, wave_sum / wave_max / wave_min and wave_incl_dpp with its two _bcast forms are defined only with all 64
+// lanes of the wave active: a lane that is switched off hands its partners 0 or whatever its register held, and takes no part
+// itself.  wave_reduce<kWidth> needs its groups whole: every lane of a group of kWidth active or none (k_assoc_float_exact's
+// loop over the map rows ends group by group).
+// So: call them from uniform control flow -- no early return above the call, not inside a branch or a loop whose condition
+// differs between lanes -- in a workgroup of whole waves, and give a lane that has nothing to contribute the operation's neutral
+// element.  wave_ballot, lanes_below_me, uni and uni_i are well defined under any mask: they see the active lanes only.
+// tests/test_gpu_wave_scan.py runs each of them alone (lf_debug_wave, k_debug.hip) against tests/wave_ref.py, lane by lane.
 #pragma once
 #include <hip/hip_runtime.h>
 
