@@ -20,7 +20,10 @@ namespace lf {
 
 constexpr int kDenseThreads = 256;
 
-__device__ __forceinline__ int reflect101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }   // n >= 3, |overhang| <= 2
+// BORDER_REFLECT_101 with ONE bounce: n >= 3, |overhang| <= 2.  tile_filter.h's reflect101 is the loop for any overhang; in this
+// stencil (ten calls per tested pixel) the loop form doubles k_dense's code (6.5 -> 13.2 KB, 52 -> 167 branches) and spills 19 SGPRs
+// (profiles/filter_objects.txt), so the one-bounce form stays, under a name of its own.
+__device__ __forceinline__ int reflect101_once(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
 // bits x-2 .. x+2 of a bit-plane row (bit k = column x - 2 + k), reflect-101 at the two-pixel borders
 __device__ __forceinline__ uint32_t window5(const uint32_t* __restrict__ row, int x, int W)
@@ -34,7 +37,7 @@ __device__ __forceinline__ uint32_t window5(const uint32_t* __restrict__ row, in
     uint32_t v = 0;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        const int xx = reflect101(x - 2 + k, W);
+        const int xx = reflect101_once(x - 2 + k, W);
         v |= ((row[xx >> 5] >> (xx & 31)) & 1u) << k;
     }
     return v;
@@ -47,7 +50,7 @@ __device__ __forceinline__ void dense_gradient(const uint32_t* __restrict__ U, i
     int sx = 0, sy = 0;
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
-        const uint32_t w = window5(U + (size_t)reflect101(y - 2 + j, Hc) * Ww, x, W);
+        const uint32_t w = window5(U + (size_t)reflect101_once(y - 2 + j, Hc) * Ww, x, W);
         const int b0 = w & 1, b1 = (w >> 1) & 1, b2 = (w >> 2) & 1, b3 = (w >> 3) & 1, b4 = (w >> 4) & 1;
         const int d = 2 * (b3 - b1) + (b4 - b0);               // [-1, -2, 0, 2, 1] along the row
         const int s = b0 + 4 * b1 + 6 * b2 + 4 * b3 + b4;      // [1, 4, 6, 4, 1] along the row

@@ -6,8 +6,8 @@
 // re-designed for the MI355X; oracle/lf_oracle_edlines.c is the sequential statement these kernels are held to, bit
 // for bit (tests/test_gpu_edlines.py).
 //
-//   k_ed_grad     streaming, one 64x64 tile per workgroup, built like k_lbd_grad (four pixels per lane, packed 16-bit
-//                 filters, v_dot2 column filter) with the octave's run-time taps: 5x5 fixed-point Gaussian -> blurred u8
+//   k_ed_grad     streaming, one 64x64 tile per workgroup, k_lbd_grad's phases (tile_filter.h: four pixels per lane, packed
+//                 16-bit filters, v_dot2 column filter) with the octave's run-time taps: 5x5 fixed-point Gaussian -> blurred u8
 //                 plane (the next octave is resized from it), Sobel 3x3 -> dx | dy << 16 per pixel (the plane k_lbd
 //                 gathers from: the descriptor of a detected line uses the DETECTOR's gradients, :1079-1090), and the
 //                 thresholded gradient / 4 (round half to even) with the pixel's direction in bit 15 (u16 plane).
@@ -34,20 +34,15 @@
 //                 octaves below, lanes = lines), orders KeyLines by (class, octave) and fills the output rows.
 #include "common.h"
 #include "k_edlines_types.h"
+#include "nfa.h"
 #include "scan.h"
+#include "tile_filter.h"
 #include "wave.h"
 
 namespace lf {
 
 constexpr int ET_W = 64, ET_H = 64;                 // k_ed_grad tile
 constexpr int kHorizontal = 0x8000;                 // bit 15 of the g plane: |dx| < |dy|
-
-__device__ __forceinline__ int ed_reflect101(int p, int n)
-{
-    if (n == 1) return 0;
-    while (p < 0 || p >= n) { if (p < 0) p = -p; else p = 2 * n - 2 - p; }
-    return p;
-}
 
 __device__ __forceinline__ int ed_div4_half_even(int v)
 {
@@ -56,9 +51,9 @@ __device__ __forceinline__ int ed_div4_half_even(int v)
 }
 
 // src u8 [B][H][W] -> blur u8, dxy u32, g u16.  taps: 5 ints, sum <= 257 (the row sums then fit 16 bits).
-// Built like k_lbd_grad (k_lbd.hip), which computes the same blur + Sobel for the LSD path's descriptor: 64 x 64 tiles,
-// four horizontally adjacent pixels per lane in every phase, two values per instruction in packed 16-bit halves, the
-// row-filtered tile stored as ROW PAIRS per column -- the operand of v_dot2_u32_u16 in the column filter.  What differs:
+// The same three phases as k_lbd_grad (k_lbd.hip), which computes this blur + Sobel for the LSD path's descriptor, from
+// tile_filter.h: 64 x 64 tiles, four horizontally adjacent pixels per lane in every phase, two values per instruction in
+// packed 16-bit halves, the row-filtered tile stored as ROW PAIRS per column.  What differs and stays here:
 // the taps are the octave's (run-time), the image is any size (octave widths are not multiples of four: rows are not
 // dword-aligned, so the source is read with unaligned dword loads and the outputs fall back to narrower stores), and
 // two more planes are written -- the blurred image (the next octave is resized from it) and the thresholded gradient
@@ -94,7 +89,7 @@ __global__ __launch_bounds__(256) void k_ed_grad(int H, int W, const uint8_t* __
     const int tid = threadIdx.x;
     const size_t fo = (size_t)f * H * W;
     const uint8_t* img = src + fo;
-    auto reflect_row = [&](int ty) { return (uint32_t)ed_reflect101(y0 + ty - 3, H) * (uint32_t)W; };
+    auto reflect_row = [&](int ty) { return (uint32_t)reflect101(y0 + ty - 3, H) * (uint32_t)W; };
     const bool interior = x0 >= 3 && x0 + 69 <= W;           // wave-uniform: all 72 columns x0-3 .. x0+68 lie inside the row
     if (interior) {
         const uint8_t* base = img + (x0 - 3);
@@ -113,34 +108,15 @@ __global__ __launch_bounds__(256) void k_ed_grad(int H, int W, const uint8_t* __
             if (xa >= 0 && xa + 3 < W) __builtin_memcpy(&packed, img + (row + (uint32_t)xa), 4);
             else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) packed |= (uint32_t)img[row + (uint32_t)ed_reflect101(xa + k, W)] << (8 * k);
+                for (int k = 0; k < 4; ++k) packed |= (uint32_t)img[row + (uint32_t)reflect101(xa + k, W)] << (8 * k);
             }
             *reinterpret_cast<uint32_t*>(gray + ty * GW + 4 * g) = packed;
         }
     }
     __syncthreads();
-    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+    const RuntimeTaps taps = { { t0, t1, t2, t3, t4 } };
     if constexpr (PACKED) {
-        // horizontal 5-tap: outputs c..c+3 (c = 4g) need gray[c .. c+7] = two dwords; the same four columns of two consecutive rows
-        const us2 c0 = { (unsigned short)t0, (unsigned short)t0 }, c1 = { (unsigned short)t1, (unsigned short)t1 }, c2 = { (unsigned short)t2, (unsigned short)t2 },
-                  c3 = { (unsigned short)t3, (unsigned short)t3 }, c4 = { (unsigned short)t4, (unsigned short)t4 };
-        for (int idx = tid; idx < (GH / 2) * RG; idx += 256) {
-            const int m = idx / RG, g = idx - m * RG;
-            uint32_t o02[2], o13[2];
-    #pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const uint32_t* sp = reinterpret_cast<const uint32_t*>(gray + (2 * m + r) * GW + 4 * g);
-                const uint32_t lo = sp[0], hi = sp[1];
-                const us2 E = __builtin_bit_cast(us2, lo & 0x00ff00ffu), O = __builtin_bit_cast(us2, (lo >> 8) & 0x00ff00ffu);
-                const us2 E2 = __builtin_bit_cast(us2, hi & 0x00ff00ffu), O2 = __builtin_bit_cast(us2, (hi >> 8) & 0x00ff00ffu);
-                const us2 P24 = { E.y, E2.x }, P35 = { O.y, O2.x };
-                o02[r] = __builtin_bit_cast(uint32_t, c0 * E + c1 * O + c2 * P24 + c3 * P35 + c4 * E2);      // (out0, out2)
-                o13[r] = __builtin_bit_cast(uint32_t, c0 * O + c1 * P24 + c2 * P35 + c3 * E2 + c4 * O2);     // (out1, out3)
-            }
-            const uint4 q = make_uint4(__builtin_amdgcn_perm(o02[1], o02[0], 0x05040100u), __builtin_amdgcn_perm(o13[1], o13[0], 0x05040100u),
-                                       __builtin_amdgcn_perm(o02[1], o02[0], 0x07060302u), __builtin_amdgcn_perm(o13[1], o13[0], 0x07060302u));
-            *reinterpret_cast<uint4*>(rowp + m * RW + 4 * g) = q;
-        }
+        tile_row_filter<GH, GW, RW>(gray, rowp, taps, tid);
     } else {
         // the same with one 32-bit sum per pixel
         const uint32_t t[5] = { (uint32_t)t0, (uint32_t)t1, (uint32_t)t2, (uint32_t)t3, (uint32_t)t4 };
@@ -159,44 +135,7 @@ __global__ __launch_bounds__(256) void k_ed_grad(int H, int W, const uint8_t* __
     }
     __syncthreads();
     if constexpr (PACKED) {
-        // vertical 5-tap, (acc + 2^15) >> 16, saturate -> blurred u8: rows 2m and 2m + 1 from the pairs m, m + 1, m + 2
-        {
-            constexpr int VPAIRS = 3, VSEG = (BH / 2 + VPAIRS - 1) / VPAIRS;
-            static_assert(VSEG * RG <= 256, "one lane per (column group, segment)");
-            const us2 k01 = { (unsigned short)t0, (unsigned short)t1 }, k23 = { (unsigned short)t2, (unsigned short)t3 }, k4_ = { (unsigned short)t4, 0 };
-            const us2 k_0 = { 0, (unsigned short)t0 }, k12 = { (unsigned short)t1, (unsigned short)t2 }, k34 = { (unsigned short)t3, (unsigned short)t4 };
-            const int g = tid % RG, seg = tid / RG;
-            if (seg < VSEG) {
-                const int m0 = seg * VPAIRS;
-                uint4 Pp[3];
-                auto fetch = [&](int m) { return *reinterpret_cast<const uint4*>(rowp + (m < GH / 2 ? m : GH / 2 - 1) * RW + 4 * g); };
-                Pp[0] = fetch(m0); Pp[1] = fetch(m0 + 1);
-    #pragma unroll
-                for (int i = 0; i < VPAIRS; ++i) {
-                    const int m = m0 + i;
-                    Pp[(i + 2) % 3] = fetch(m + 2);
-                    if (2 * m < BH) {
-                        const uint4 A = Pp[i % 3], B = Pp[(i + 1) % 3], C = Pp[(i + 2) % 3];
-                        const uint32_t a[4] = { A.x, A.y, A.z, A.w }, bb[4] = { B.x, B.y, B.z, B.w }, cc[4] = { C.x, C.y, C.z, C.w };
-                        uint32_t even = 0, odd = 0;
-    #pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            uint32_t e = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, a[k]), k01, 1u << 15, false);
-                            e = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, bb[k]), k23, e, false);
-                            e = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, cc[k]), k4_, e, false);
-                            uint32_t o = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, a[k]), k_0, 1u << 15, false);
-                            o = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, bb[k]), k12, o, false);
-                            o = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, cc[k]), k34, o, false);
-                            e >>= 16; o >>= 16;
-                            even |= (e > 255u ? 255u : e) << (8 * k);
-                            odd |= (o > 255u ? 255u : o) << (8 * k);
-                        }
-                        *reinterpret_cast<uint32_t*>(blur + (2 * m) * BW_ + 4 * g) = even;
-                        *reinterpret_cast<uint32_t*>(blur + (2 * m + 1) * BW_ + 4 * g) = odd;
-                    }
-                }
-            }
-        }
+        tile_col_filter<GH, RW, BH, BW_>(rowp, blur, taps, tid);
     } else {
         const uint32_t t[5] = { (uint32_t)t0, (uint32_t)t1, (uint32_t)t2, (uint32_t)t3, (uint32_t)t4 };
         for (int idx = tid; idx < BH * RG; idx += 256) {
@@ -220,38 +159,19 @@ __global__ __launch_bounds__(256) void k_ed_grad(int H, int W, const uint8_t* __
         constexpr int SROWS = ET_H / 16;
         const int g = tid & 15, seg = tid >> 4;
         const int lx = 4 * g, gx = x0 + lx, ry0 = seg * SROWS;
-        typedef short s2 __attribute__((ext_vector_type(2)));
-        s2 Pq[3][4];
+        tf_s2 Pq[3][4];
         uint32_t mid[3];                                    // the row's own four blurred bytes (columns lx+1 .. lx+4)
-        auto unpack = [&](int row, s2 (&d)[4], uint32_t& centre) {
-            const uint32_t* sp = reinterpret_cast<const uint32_t*>(blur + row * BW_ + lx);   // columns lx .. lx+7 <-> x-1 ..
-            const uint32_t lo = sp[0], hi = sp[1];
-            const s2 E = __builtin_bit_cast(s2, lo & 0x00ff00ffu), O = __builtin_bit_cast(s2, (lo >> 8) & 0x00ff00ffu);
-            const s2 E2 = __builtin_bit_cast(s2, hi & 0x00ff00ffu), O2 = __builtin_bit_cast(s2, (hi >> 8) & 0x00ff00ffu);
-            d[0] = E; d[1] = O; d[2] = s2{ E.y, E2.x }; d[3] = s2{ O.y, O2.x };
-            centre = (lo >> 8) | (hi << 24);
-        };
-        unpack(ry0, Pq[0], mid[0]);
-        unpack(ry0 + 1, Pq[1], mid[1]);
-        auto a_plus_2b = [](s2 a, s2 b) {
-            s2 d;
-            const uint32_t two = 0x00020002u;
-            asm("v_pk_mad_i16 %0, %1, %2, %3" : "=v"(d) : "v"(b), "v"(two), "v"(a));
-            return d;
-        };
+        sobel_unpack<BW_>(blur, ry0, lx, Pq[0], &mid[0]);
+        sobel_unpack<BW_>(blur, ry0 + 1, lx, Pq[1], &mid[1]);
         const bool wide = (W & 3) == 0;                      // rows of the output planes are 4-pixel aligned
         const size_t o00 = fo + (size_t)(y0 + ry0) * W + gx;
 #pragma unroll
         for (int i = 0; i < SROWS; ++i) {
             const int ry = ry0 + i, gy = y0 + ry;
-            unpack(ry + 2, Pq[(i + 2) % 3], mid[(i + 2) % 3]);
+            sobel_unpack<BW_>(blur, ry + 2, lx, Pq[(i + 2) % 3], &mid[(i + 2) % 3]);
             if (gx < W && gy < H) {
-                s2 S[4], D[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { S[c] = a_plus_2b(Pq[i % 3][c], Pq[(i + 1) % 3][c]) + Pq[(i + 2) % 3][c]; D[c] = Pq[(i + 2) % 3][c] - Pq[i % 3][c]; }
-                const s2 vx02 = S[2] - S[0], vx13 = S[3] - S[1];
-                const s2 vy02 = a_plus_2b(D[0], D[1]) + D[2], vy13 = a_plus_2b(D[1], D[2]) + D[3];
-                const int vx[4] = { vx02.x, vx13.x, vx02.y, vx13.y }, vy[4] = { vy02.x, vy13.x, vy02.y, vy13.y };
+                const SobelXY v = sobel_row(Pq[i % 3], Pq[(i + 1) % 3], Pq[(i + 2) % 3]);
+                const int vx[4] = { v.vx02.x, v.vx13.x, v.vx02.y, v.vx13.y }, vy[4] = { v.vy02.x, v.vy13.x, v.vy02.y, v.vy13.y };
                 uint32_t w[4], gq[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -366,7 +286,7 @@ __global__ __launch_bounds__(256) void k_ed_blur_rows(int H, int W, const uint8_
     const uint8_t* row = src + ((size_t)blockIdx.z * H + y) * W;
     const int r = t.n / 2;
     int sum = 0;
-    for (int j = -r; j <= r; ++j) sum += t.k[j + r] * (int)row[ed_reflect101(x + j, W)];
+    for (int j = -r; j <= r; ++j) sum += t.k[j + r] * (int)row[reflect101(x + j, W)];
     tmp[((size_t)blockIdx.z * H + y) * W + x] = sum;
 }
 __global__ __launch_bounds__(256) void k_ed_blur_cols(int H, int W, const int* __restrict__ tmp, EdTaps t, uint8_t* __restrict__ dst)
@@ -376,7 +296,7 @@ __global__ __launch_bounds__(256) void k_ed_blur_cols(int H, int W, const int* _
     const int* img = tmp + (size_t)blockIdx.z * H * W;
     const int r = t.n / 2;
     int sum = 0;
-    for (int j = -r; j <= r; ++j) sum += t.k[j + r] * img[(size_t)ed_reflect101(y + j, H) * W + x];
+    for (int j = -r; j <= r; ++j) sum += t.k[j + r] * img[(size_t)reflect101(y + j, H) * W + x];
     const int v = (sum + (1 << 15)) >> 16;
     dst[((size_t)blockIdx.z * H + y) * W + x] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
 }
@@ -500,10 +420,10 @@ __global__ void k_pyrdown(int H, int W, const uint8_t* __restrict__ src, uint8_t
     int s = 0;
 #pragma unroll
     for (int j = -2; j <= 2; ++j) {
-        const uint8_t* row = S + (size_t)ed_reflect101(2 * dy + j, H) * W;
+        const uint8_t* row = S + (size_t)reflect101(2 * dy + j, H) * W;
         int r = 0;
 #pragma unroll
-        for (int i = -2; i <= 2; ++i) r += k[i + 2] * (int)row[ed_reflect101(2 * dx + i, W)];
+        for (int i = -2; i <= 2; ++i) r += k[i + 2] * (int)row[reflect101(2 * dx + i, W)];
         s += k[j + 2] * r;
     }
     dst[((size_t)blockIdx.z * DH + dy) * DW + dx] = (uint8_t)((s + 128) >> 8);
@@ -783,55 +703,9 @@ __device__ __forceinline__ bool ed_walk(EdWalk& c, unsigned x0, unsigned y0, int
 }
 
 // ---- NFA (descriptor_custom.hpp:630-813), lane-uniform
-__device__ __noinline__ double ed_log_gamma(double x)
-{
-    if (x > 15.0)
-        return 0.918938533204673 + (x - 0.5) * dm::dlog(x) - x + 0.5 * x * dm::dlog(x * dm::dsinh_small(1 / x) + 1 / (810.0 * dm::dpow(x, 6.0)));
-    const double q[7] = { 75122.6331530, 80916.6278952, 36308.2951477, 8687.24529705, 1168.92649479, 83.8676043424, 2.50662827511 };
-    double a = (x + 0.5) * dm::dlog(x + 5.5) - (x + 5.5);
-    double b = 0.0;
-    for (int n = 0; n < 7; n++) {
-        a -= dm::dlog(x + (double)n);
-        b += q[n] * dm::dpow(x, (double)n);
-    }
-    return a + dm::dlog(b);
-}
-
-__device__ __forceinline__ bool ed_double_equal(double a, double b)
-{
-    if (a == b) return true;
-    const double abs_diff = fabs(a - b), aa = fabs(a), bb = fabs(b);
-    double abs_max = aa > bb ? aa : bb;
-    if (abs_max < 2.2250738585072014e-308) abs_max = 2.2250738585072014e-308;
-    return (abs_diff / abs_max) <= (100.0 * 2.2204460492503131e-16);
-}
-
-__device__ __noinline__ double ed_nfa(int n, int k, double p, double logNT)
-{
-    const double tolerance = 0.1;
-    if (n == 0 || k == 0) return -logNT;
-    if (n == k) return -logNT - (double)n * dm::dlog10(p);
-    const double p_term = p / (1.0 - p);
-    const double log1term = ed_log_gamma((double)n + 1.0) - ed_log_gamma((double)k + 1.0) - ed_log_gamma((double)(n - k) + 1.0)
-                          + (double)k * dm::dlog(p) + (double)(n - k) * dm::dlog(1.0 - p);
-    double term = dm::dexp(log1term);
-    if (ed_double_equal(term, 0.0)) {
-        if ((double)k > (double)n * p) return -log1term / 2.30258509299404568402 - logNT;
-        return -logNT;
-    }
-    double bin_tail = term;
-    for (int i = k + 1; i <= n; i++) {
-        const double bin_term = (double)(n - i + 1) / (double)i;
-        const double mult_term = bin_term * p_term;
-        term *= mult_term;
-        bin_tail += term;
-        if (bin_term < 1.0) {
-            const double err = term * ((1.0 - dm::dpow(mult_term, (double)(n - i + 1))) / (1.0 - mult_term) - 1.0);
-            if (err < tolerance * fabs(-dm::dlog10(bin_tail) - logNT) * bin_tail) break;
-        }
-    }
-    return -dm::dlog10(bin_tail) - logNT;
-}
+// (both out of line: one lane-uniform evaluation per fitted line, reached from the fitting loop of k_ed_detect)
+__device__ __noinline__ double ed_log_gamma(double x) { return log_gamma(x); }
+__device__ __noinline__ double ed_nfa(int n, int k, double p, double logNT) { return nfa_tail<false, ed_log_gamma>(n, k, p, logNT); }      // (nfa.h: EDLines' first term is log_gamma(n + 1))
 
 struct EdFit { float ATA[4], ATV[2]; };
 

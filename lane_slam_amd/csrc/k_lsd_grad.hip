@@ -27,19 +27,13 @@
 // the blur / resample / gradient element-operations of a 16 x 16 tiling are 0.74 of a 32 x 32 one.
 #include "common.h"
 #include "k_lsd_grad.h"
+#include "tile_filter.h"
 #include "wave.h"
 
 namespace lf {
 
 constexpr int GTW = kLsdTileW, GTH = kLsdTileH;
 constexpr int SCW = GTW + 1;                       // row stride of the resized planes Hb and Sc (one more sample: the 2x2 gradient)
-
-__device__ __forceinline__ int reflect101(int p, int n)
-{
-    if (n == 1) return 0;
-    while (p < 0 || p >= n) { p = p < 0 ? -p : 2 * (n - 1) - p; }
-    return p;
-}
 
 // idx / n for idx < 4096, n < 128 without a division: (idx * (2^19 / n + 1)) >> 19 (checked exhaustively); the tile
 // phases below are flat loops over (row, column) pairs, so that all 64 lanes work whatever the tile's width is

@@ -26,6 +26,7 @@
 #pragma once
 #include <type_traits>
 #include "detmath.h"
+#include "nfa.h"
 
 #ifndef LF_HOST_SIM
 #include <hip/hip_runtime.h>
@@ -302,20 +303,8 @@ LFG_DEV double angle_diff_signed(double a, double b)
     while (uni(diff > PI_)) diff -= M_2__PI_;
     return diff;
 }
-LFG_DEV double dabs(double v) { return v < 0 ? -v : v; }
 LFG_DEV double dist_sq(double x1, double y1, double x2, double y2) { return (x2 - x1) * (x2 - x1) + (y2 - y1) * (y2 - y1); }
 LFG_DEV double dist_(double x1, double y1, double x2, double y2) { return dm::dsqrt(dist_sq(x1, y1, x2, y2)); }
-
-LFG_DEV bool double_equal(double a, double b)
-{
-    if (a == b) return true;
-    double abs_diff = dabs(a - b);
-    double aa = dabs(a), bb = dabs(b);
-    double abs_max = (aa > bb) ? aa : bb;
-    const double DBL_MIN_ = 2.2250738585072014e-308, DBL_EPS_ = 2.2204460492503131e-16;
-    if (abs_max < DBL_MIN_) abs_max = DBL_MIN_;
-    return (abs_diff / abs_max) <= (100.0 * DBL_EPS_);
-}
 
 // ------------------------------------------------------------------ region_grow
 // seed_e: compact entry of the seed pixel (sx, sy)
@@ -913,26 +902,6 @@ LFG_DEV double refine_tau(const Ctx& c, int reg_size, const Rect& rec, int& x0, 
 }
 
 // ------------------------------------------------------------------ NFA
-LFG_DEV double log_gamma_lanczos(double x)
-{
-    const double q[7] = { 75122.6331530, 80916.6278952, 36308.2951477, 8687.24529705,
-                          1168.92649479, 83.8676043424, 2.50662827511 };
-    double a = (x + 0.5) * dm::dlog(x + 5.5) - (x + 5.5);
-    double b = 0;
-#pragma unroll
-    for (int n = 0; n < 7; ++n) {
-        a -= dm::dlog(x + (double)n);
-        b += q[n] * dm::dpow(x, (double)n);
-    }
-    return a + dm::dlog(b);
-}
-LFG_DEV double log_gamma_windschitl(double x)
-{
-    return 0.918938533204673 + (x - 0.5) * dm::dlog(x) - x
-         + 0.5 * x * dm::dlog(x * dm::dsinh_small(1 / x) + 1 / (810.0 * dm::dpow(x, 6.0)));
-}
-LFG_DEV double log_gamma(double x) { return x > 15.0 ? log_gamma_windschitl(x) : log_gamma_lanczos(x); }
-
 // The NFA arithmetic (log-gamma, binomial tail: a few hundred f64 operations through the deterministic routines) is
 // reached from six places once everything is inlined; kept OUT of line it exists once, and the kernel's hot loops
 // stay inside the instruction cache (the kernel was 116 KB of code against a 64 KB cache shared by two CUs).
@@ -941,32 +910,7 @@ __device__ __noinline__
 #else
 static
 #endif
-double nfa_eval(int n, int k, double p, double LOG_NT)
-{
-    if (n == 0 || k == 0) return -LOG_NT;
-    if (n == k) return -LOG_NT - (double)n * dm::dlog10(p);
-    const double p_term = p / (1 - p);
-    const double log1term = ((double)n + 1) - log_gamma((double)k + 1) - log_gamma((double)(n - k) + 1)
-                          + (double)k * dm::dlog(p) + (double)(n - k) * dm::dlog(1.0 - p);
-    double term = dm::dexp(log1term);
-    if (double_equal(term, 0)) {
-        if (k > n * p) return -log1term / 2.30258509299404568402 - LOG_NT;
-        else return -LOG_NT;
-    }
-    double bin_tail = term;
-    const double tolerance = 0.1;
-    for (int i = k + 1; i <= n; ++i) {
-        const double bin_term = (double)(n - i + 1) / (double)i;
-        const double mult_term = bin_term * p_term;
-        term *= mult_term;
-        bin_tail += term;
-        if (bin_term < 1) {
-            const double err = term * ((1 - dm::dpow(mult_term, (double)(n - i + 1))) / (1 - mult_term) - 1);
-            if (err < tolerance * dabs(-dm::dlog10(bin_tail) - LOG_NT) * bin_tail) break;
-        }
-    }
-    return -dm::dlog10(bin_tail) - LOG_NT;
-}
+double nfa_eval(int n, int k, double p, double LOG_NT) { return nfa_tail<true>(n, k, p, LOG_NT); }      // (nfa.h: LSD's first term is plain)
 LFG_DEV double nfa(const Ctx& c, int n, int k, double p) { return nfa_eval(n, k, p, c.log_nt); }
 
 // Row geometry of one rectangle: everything rect_nfa's scan-line walk needs, all integers.

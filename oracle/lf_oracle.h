@@ -96,6 +96,8 @@ void lfo_antiqsort_keys(int n, int32_t* keys);
 /* full detector: lines (x1,y1,x2,y2) float32, returns count (<= cap); extra = width,prec,nfa per line or NULL */
 int lfo_lsd_detect(const lfo_config* c, const uint8_t* img, int rows, int cols,
                    float* lines4, double* extra3, int cap);
+/* the detector's NFA of a rectangle with n pixels, k of them aligned (test helper, like lfo_ed_nfa) */
+double lfo_lsd_nfa(int n, int k, double p, double log_nt);
 
 /* ---- per-segment stages (lf_oracle_segments.c) ---- */
 /* a-5: normals (f64, value-equal to the f32 product), centers f32, lines reordered in place */

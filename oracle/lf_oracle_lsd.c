@@ -416,9 +416,10 @@ static double log_gamma_windschitl(double x)
 }
 static double log_gamma(double x) { return x > 15.0 ? log_gamma_windschitl(x) : log_gamma_lanczos(x); }
 
-static double nfa(const Lsd* L, int n, int k, double p)
+/* exported for tests/test_nfa_cpu.py, next to lfo_ed_nfa.  The first term is n + 1 itself here and log_gamma(n + 1) there: each
+ * detector as its own source has it (lane_slam_amd/csrc/nfa.h). */
+double lfo_lsd_nfa(int n, int k, double p, double LOG_NT)
 {
-    const double LOG_NT = L->LOG_NT;
     if (n == 0 || k == 0) return -LOG_NT;
     if (n == k) return -LOG_NT - (double)n * lfo_log10(p);
     double p_term = p / (1 - p);
@@ -443,6 +444,7 @@ static double nfa(const Lsd* L, int n, int k, double p)
     }
     return -lfo_log10(bin_tail) - LOG_NT;
 }
+static double nfa(const Lsd* L, int n, int k, double p) { return lfo_lsd_nfa(n, k, p, L->LOG_NT); }
 
 typedef struct { int x, y; int taken; } Edge;
 static int edge_less(const Edge* a, const Edge* b)

@@ -616,6 +616,7 @@ def _edlib():
     lib.lfo_edlines_run.restype = ctypes.c_void_p
     lib.lfo_edlines_array.restype = ctypes.c_void_p
     lib.lfo_ed_nfa.restype = ctypes.c_double
+    lib.lfo_lsd_nfa.restype = ctypes.c_double
     return lib
 
 
@@ -660,6 +661,11 @@ def pyrdown_u8(img):
 
 def ed_nfa(n, k, p, log_nt):
     return _edlib().lfo_ed_nfa(int(n), int(k), ctypes.c_double(p), ctypes.c_double(log_nt))
+
+
+def lsd_nfa(n, k, p, log_nt):
+    """The LSD oracle's NFA (lf_oracle_lsd.c): the same tail with n + 1 where ed_nfa has log_gamma(n + 1)."""
+    return _edlib().lfo_lsd_nfa(int(n), int(k), ctypes.c_double(p), ctypes.c_double(log_nt))
 
 
 _ED_ARRAYS = [("dx", np.int16), ("dy", np.int16), ("g", np.int16), ("gwo", np.int16), ("dir", np.uint8), ("edge", np.uint8),

@@ -369,6 +369,12 @@ GEOMETRIES = collections.OrderedDict([
     ("63x96", dict(img_size=(75, 96), top_cutoff=12, octaves=3)),          # odd planes: 63x96, 31x48, 15x24
     ("128x32", dict(img_size=(131, 32), top_cutoff=3, octaves=3)),         # narrower than one tile: 128x32, 64x16, 32x8
 ])
+# describe-only: in no front-end parametrisation (the detector finds no line in an image this small) and not in the octaves_* family.
+# 8 rows are the fewest lf_describe_keylines builds a level for, so this geometry has ONE octave (the next, 4x16, is "too small":
+# tests/test_gpu_descriptor_params.py); the whole image is one tile cut on all four sides, shorter than the tile's halo is tall.
+DESCRIBE_ONLY = collections.OrderedDict([
+    ("8x32", dict(img_size=(10, 32), top_cutoff=2, octaves=1)),
+])
 LENGTHS = (1, 2, 7, 8, 9, 15, 16, 17, 63, 64, 65, 255, 1000)
 WRAPS = (0, -3, 32768 + 5, 65536 + 9)
 PI32 = float(np.float32(np.pi))
@@ -377,8 +383,12 @@ CYCLE = 37
 BIG_N = 16384 + 5                  # launch_lbd_keylines caps its grid at 4096 workgroups of 4 lines: five lines of a second lap
 
 
+def geometry_of(geometry):
+    return GEOMETRIES[geometry] if geometry in GEOMETRIES else DESCRIBE_ONLY[geometry]
+
+
 def shape_of(geometry):
-    g = GEOMETRIES[geometry]
+    g = geometry_of(geometry)
     return g["img_size"][0] - g["top_cutoff"], g["img_size"][1]
 
 
@@ -544,6 +554,20 @@ def _cycle(rng):
     return [b.case()]
 
 
+def _tiny(rng):
+    """(drawn last: the cases above keep the lines they always had)"""
+    rows, cols = shape_of("8x32")
+    im = images(rng, rows, cols)
+    b = _Builder("tiny_8x32", "tiny", "8x32", 7, [im["noise"], im["checker1"]])
+    for i in range(24):
+        b.line(i & 1, (rng.uniform(-3, cols + 3), rng.uniform(-3, rows + 3)), rng.uniform(-np.pi, np.pi), int(rng.integers(1, cols)))
+    for f in (0, 1):                                             # along every border and through two corners
+        for mid, ang, n in (((cols / 2.0, 0.0), 0.0, 30), ((cols / 2.0, rows - 1.0), 0.0, 30), ((0.0, rows / 2.0), np.pi / 2, 8),
+                            ((cols - 1.0, rows / 2.0), np.pi / 2, 8), ((2.0, 2.0), np.pi / 4, 9), ((cols - 3.0, rows - 3.0), -3 * np.pi / 4, 9)):
+            b.line(f, mid, ang, n)
+    return [b.case()]
+
+
 _CASES = None
 _REFS = {}
 
@@ -552,14 +576,14 @@ def cases():
     global _CASES
     if _CASES is None:
         rng = np.random.default_rng(SEED)
-        made = _lengths(rng) + _angles(rng) + _positions(rng) + _image_cases(rng) + _octaves(rng) + _widths(rng) + _random(rng) + _cycle(rng)
+        made = _lengths(rng) + _angles(rng) + _positions(rng) + _image_cases(rng) + _octaves(rng) + _widths(rng) + _random(rng) + _cycle(rng) + _tiny(rng)
         _CASES = collections.OrderedDict((c.name, c) for c in made)
     return _CASES
 
 
 def case_names():
     return (["lengths", "angles", "positions", "images_a", "images_b", "images_c"] + ["octaves_" + g for g in GEOMETRIES] +
-            ["width_%d" % w for w in WIDTHS] + ["random", "cycle37"])
+            ["width_%d" % w for w in WIDTHS] + ["random", "cycle37", "tiny_8x32"])
 
 
 def reference(name):

@@ -1,6 +1,7 @@
 """k_lbd.hip against the float64 reference of tests/lbd_ref.py, through the public API, on hand-made lines: every length around the
 8-step gather, (short) numOfPixels and its wrap-around, every angle and position (across borders and corners, wholly outside, exact
-halves), every image kind, every octave plane of three working sizes (odd planes, an image narrower than one tile), every band
+halves), every image kind, every octave plane of three working sizes (odd planes, an image narrower than one tile), an 8 x 32 image
+(the fewest rows the describe path builds a level for: one tile cut on all four sides, its halo rows reflected many times), every band
 width (the compile-time kernel and the multi-lap one), one line and 16 389 of them, host and device arrays, one output or both --
 and the front end's own kernel shape on detected lines.
 
@@ -25,8 +26,8 @@ pytestmark = pytest.mark.gpu
 
 def config(geometry):
     cfg = default_config("parity")
-    cfg["img_size"] = list(R.GEOMETRIES[geometry]["img_size"])
-    cfg["top_cutoff"] = R.GEOMETRIES[geometry]["top_cutoff"]
+    cfg["img_size"] = list(R.geometry_of(geometry)["img_size"])
+    cfg["top_cutoff"] = R.geometry_of(geometry)["top_cutoff"]
     return cfg
 
 

@@ -38,8 +38,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 def hostsim():
     so = os.path.join(HERE, "hostsim", "_build", "libhostsim.so")
     src = os.path.join(HERE, "hostsim", "hostsim.cpp")
-    hdr = os.path.join(HERE, "..", "lane_slam_amd", "csrc", "lsd_grow.h")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+    hdrs = [os.path.join(HERE, "..", "lane_slam_amd", "csrc", h) for h in ("lsd_grow.h", "nfa.h")]
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in [src] + hdrs):
         os.makedirs(os.path.dirname(so), exist_ok=True)
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", so, src])
     lib = ctypes.CDLL(so)
