@@ -964,6 +964,71 @@ LF_API int lf_map_get_near(const lf_map* m, lf_near_config* cfg);   /* 1: set (a
  * build, all its kernels), [1] the query.  Stages of their own: lf_map_get_timing and the other timing calls are unchanged. */
 LF_API int lf_map_near_timing(lf_map* m, double ms[2], int32_t launches[2]);
 
+/* ---- the live map's lane lines: lf_map_lanes ---------------------------------------------------------------
+ * The map is a list of loose segments: no entry knows which other entries belong to the same painted line.  lf_map_lanes groups
+ * the entries into lane lines: connected components of collinear, same-coloured, neighbouring entries, found on the device through
+ * the hash grid of lf_map_associate_near (built per call from the map as it stands).  The support count per entry is a filter
+ * for spurious detections (an entry that no neighbour supports), the lane table is the map's answer to "which lane lines are
+ * here".  The reference has no such stage: this is the package's OWN contract, written so that a sequential restatement
+ * (tests/map_lanes_ref.py: all pairs, no grid) and the kernels (k_map_lanes.hip) agree bit for bit.  Nothing of the map is
+ * changed.  All geometry is f64, unfused, in the order written; no square root, no division; a comparison with a NaN fails.
+ *
+ *   entry t, eligible   t is a physical row, 0 <= t < size, as lf_map_associate_near counts rows.  Eligible: the near contract's
+ *                       "entry t" holds (finite endpoints, L2 finite and > 0) and its midpoint is finite; hits[t] >= min_hits;
+ *                       the colour's bit of color_mask is set (bits 0 .. 2: colours 0 .. 2, bit 3: every other colour).
+ *   link(i, j), i != j  both are eligible, their colour BYTES are equal (as in lf_map_prune's cover rule: not the near contract's
+ *                       colour agreement), and the near contract's geometric candidate test holds BOTH ways: with entry i in the
+ *                       role of the segment (sx = Bx - Ax, sy = By - Ay, S2 = sx sx + sy sy, qm = its midpoint, no pose) and entry
+ *                       j as the entry,  d2 <= r2;  max_sin < 1: cr cr <= (max_sin max_sin) (S2 L2);  max_offset finite:
+ *                       o o <= (max_offset max_offset) L2;  and the same with the roles swapped.  (d2 and cr cr come out
+ *                       bit-identical both ways -- the differences are exact negations and the products commute -- the offset
+ *                       test does not: hence both directions, and a relation that is symmetric by construction.)
+ *   component           a connected component of the link graph over the eligible entries; a lone eligible entry is one of one.
+ *   lane                a component with at least min_entries members.  Lanes are numbered 0, 1, .. by ascending first_row.
+ *   outputs             rows < size: n_links[t] = the entries linked with t (0: not eligible); support[t] = the members of t's
+ *                       component (0: not eligible); lane_of[t] = the lane's number, -1: not eligible or the component is too
+ *                       small.  Rows in [size, capacity): lane_of -1, n_links 0, support 0.  res->n_links counts every undirected
+ *                       link once.  Every value is an integer count or sum, or a min / max over finite values: no output depends
+ *                       on the order of evaluation, and two calls on the same map give the same bytes.
+ *   capacity            lanes not NULL and n_lanes > max_lanes: LF_ERR_CAPACITY with res and the three per-row arrays filled in and
+ *                       lanes untouched; the table is never truncated.  Otherwise lanes[0 .. n_lanes) are written.
+ * A maintenance call like lf_map_prune: it runs on the map's stream in call order, waits and returns with res filled in.  A
+ * pending failing update is reported first, exactly as lf_map_size does it.  The map's entries, operands, size, head and totals
+ * are untouched; an empty map gives zeros and -1s and returns LF_OK.  lane_of, n_links, support ([capacity] int32 each) and lanes
+ * are device (on_device = 1) or host (0) arrays; each may be NULL.
+ * LF_ERR_BAD_ARG, touching nothing, the reason in lf_map_last_error: NULL c or res; a radius that is not finite or <= 0; a
+ * max_offset that is <= 0 or NaN; a max_sin outside 0 .. 1 or NaN; min_hits < 0; min_entries < 1; max_lanes < 0, or lanes given
+ * with max_lanes == 0.
+ * Replicas: the result is a pure function of the map and the configuration, so the ranks of a multi-GPU run agree without a
+ * collective. */
+typedef struct lf_lanes_config {
+    double  radius;        /* metres, finite, > 0: two linked entries' midpoints are at most this far apart; default 0.25 */
+    double  max_offset;    /* metres, > 0 or +inf (not tested): each midpoint lies at most this far from the OTHER entry's line; default 0.05 */
+    double  max_sin;       /* 0 .. 1; 1: not tested; default 0.25 */
+    int32_t min_hits;      /* entries with fewer hits are not eligible; default 1 */
+    int32_t min_entries;   /* a component with fewer members is not a lane; >= 1; default 3 */
+    int32_t color_mask;    /* bits 0..2: colours 0..2, bit 3: every other colour; clear bit = not eligible; default 0xF */
+    int32_t reserved_;     /* 0 */
+} lf_lanes_config;
+typedef struct lf_lane {           /* 56 bytes */
+    int32_t first_row;             /* the smallest physical row of the lane: its identity */
+    int32_t color;                 /* the members' colour byte */
+    int32_t n_entries, reserved_;
+    int64_t hits;                  /* sum of the members' hits */
+    double  box[4];                /* x_min, y_min, x_max, y_max over both endpoints of all members, each value v + 0.0 (no -0) */
+} lf_lane;
+typedef struct lf_lanes_result { int32_t size, n_eligible, n_components, n_lanes; int64_t n_links; } lf_lanes_result;
+LF_API int lf_sizeof_lanes_config(void);
+LF_API int lf_sizeof_lane(void);
+LF_API int lf_sizeof_lanes_result(void);
+LF_API void lf_map_lanes_default_config(lf_lanes_config* c);
+LF_API int lf_map_lanes(lf_map* m, const lf_lanes_config* c, lf_lanes_result* res,
+                        int32_t* lane_of /* [capacity] or NULL */, int32_t* n_links /* [capacity] or NULL */,
+                        int32_t* support /* [capacity] or NULL */, lf_lane* lanes /* [max_lanes] or NULL */, int max_lanes, int on_device);
+/* ms and launches accumulated since the previous call, with profiling on; resets them: [0] the index build, [1] link + label +
+ * table (one launch = one call's kernels of that stage).  Stages of their own: the other timing calls are unchanged. */
+LF_API int lf_map_lanes_timing(lf_map* m, double ms[2], int32_t launches[2]);
+
 /* ---- Histogram lane filter: lane pose from ground segments -----------------------------------------
  * LaneFilterHistogram (src/lane_filter/include/lane_filter/lane_filter.py:12-161) as lane_filter_node.processSegments
  * drives it (src/lane_filter/src/lane_filter_node.py:49-87): per frame predict(dt, v, w) -> update(segments) ->

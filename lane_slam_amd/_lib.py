@@ -49,6 +49,7 @@ EXPORTS = (
     "lf_sizeof_localize_config", "lf_sizeof_localize_result", "lf_map_localize_default_config", "lf_map_localize", "lf_map_localize_timing",
     "lf_sizeof_prune_config", "lf_sizeof_prune_result", "lf_map_prune_default_config", "lf_map_prune", "lf_map_prune_timing",
     "lf_sizeof_near_config", "lf_map_near_default_config", "lf_map_associate_near", "lf_map_set_near", "lf_map_get_near", "lf_map_near_timing",
+    "lf_sizeof_lanes_config", "lf_sizeof_lane", "lf_sizeof_lanes_result", "lf_map_lanes_default_config", "lf_map_lanes", "lf_map_lanes_timing",
 )
 LF_ALIGN_OK, LF_ALIGN_FEW, LF_ALIGN_DEGENERATE, LF_ALIGN_REJECTED = 0, 1, 2, 3
 ALIGN_STATUS = ("ok", "few", "degenerate", "rejected")
@@ -222,6 +223,28 @@ class LfNearConfig(ctypes.Structure):
     """ctypes mirror of `lf_near_config` (include/lanefront.h)."""
     _fields_ = [("radius", ctypes.c_double), ("max_offset", ctypes.c_double), ("max_sin", ctypes.c_double), ("min_hits", ctypes.c_int32),
                 ("reserved_", ctypes.c_int32)]
+
+
+class LfLanesConfig(ctypes.Structure):
+    """ctypes mirror of `lf_lanes_config` (include/lanefront.h)."""
+    _fields_ = [("radius", ctypes.c_double), ("max_offset", ctypes.c_double), ("max_sin", ctypes.c_double), ("min_hits", ctypes.c_int32),
+                ("min_entries", ctypes.c_int32), ("color_mask", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
+
+
+class LfLane(ctypes.Structure):
+    """ctypes mirror of `lf_lane` (include/lanefront.h)."""
+    _fields_ = [("first_row", ctypes.c_int32), ("color", ctypes.c_int32), ("n_entries", ctypes.c_int32), ("reserved_", ctypes.c_int32),
+                ("hits", ctypes.c_int64), ("box", ctypes.c_double * 4)]
+
+
+# the same layout as a numpy record: what LineAssociator.lanes returns
+LANE_DTYPE = [("first_row", "<i4"), ("color", "<i4"), ("n_entries", "<i4"), ("reserved_", "<i4"), ("hits", "<i8"), ("box", "<f8", (4,))]
+
+
+class LfLanesResult(ctypes.Structure):
+    """ctypes mirror of `lf_lanes_result` (include/lanefront.h)."""
+    _fields_ = [("size", ctypes.c_int32), ("n_eligible", ctypes.c_int32), ("n_components", ctypes.c_int32), ("n_lanes", ctypes.c_int32),
+                ("n_links", ctypes.c_int64)]
 
 
 _lib = None
@@ -404,6 +427,14 @@ def load():
     lib.lf_map_get_near.argtypes = [vp, ctypes.POINTER(LfNearConfig)]
     lib.lf_map_near_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
     for f in ("lf_sizeof_near_config", "lf_map_associate_near", "lf_map_set_near", "lf_map_get_near", "lf_map_near_timing"):
+        getattr(lib, f).restype = ci
+    for f in ("lf_sizeof_lanes_config", "lf_sizeof_lane", "lf_sizeof_lanes_result"):
+        getattr(lib, f).argtypes = []
+    lib.lf_map_lanes_default_config.argtypes = [ctypes.POINTER(LfLanesConfig)]
+    lib.lf_map_lanes_default_config.restype = None
+    lib.lf_map_lanes.argtypes = [vp, ctypes.POINTER(LfLanesConfig), ctypes.POINTER(LfLanesResult), vp, vp, vp, vp, ci, ci]
+    lib.lf_map_lanes_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
+    for f in ("lf_sizeof_lanes_config", "lf_sizeof_lane", "lf_sizeof_lanes_result", "lf_map_lanes", "lf_map_lanes_timing"):
         getattr(lib, f).restype = ci
     lib.lf_descriptor_default_params.argtypes = [ctypes.POINTER(LfDescriptorParams)]
     lib.lf_descriptor_default_params.restype = None

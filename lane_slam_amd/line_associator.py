@@ -8,6 +8,7 @@ BinaryDescriptorMatcher::match semantics (ref: src/line_descriptor/src/binary_de
 matrix cores, optionally gated by Segment.color, and updated from the association results (append, or refresh the
 matched entry).  All of it runs in liblanefront.so (lf_map_*); this class only marshals arguments.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -17,6 +18,9 @@ from . import _lib
 BLOCK_ROW_BYTES = 80
 _POLICY = {"append": 0, "merge": 1}
 _WHEN_FULL = {"ring": 0, "error": 1}
+# what LineAssociator.lanes and lanes_device return
+Lanes = collections.namedtuple("Lanes", ("result", "lane_of", "n_links", "support", "lanes"))
+LANE_BYTES = ctypes.sizeof(_lib.LfLane)
 
 
 class LineAssociator(object):
@@ -29,6 +33,7 @@ class LineAssociator(object):
         if policy not in _POLICY or when_full not in _WHEN_FULL:
             raise ValueError("policy must be 'append' or 'merge', when_full 'ring' or 'error'")
         self.capacity = int(capacity)
+        self._device = int(device)
         self.color_gating = bool(color_gating)
         c = _lib.LfMapConfig(self.capacity, int(self.color_gating), int(max_distance), _POLICY[policy], int(bool(kept_only)),
                              int(merge_distance), _WHEN_FULL[when_full])
@@ -386,6 +391,76 @@ class LineAssociator(object):
         ms, ln = (ctypes.c_double * 2)(), (ctypes.c_int32 * 2)()
         self._check(self.lib.lf_map_near_timing(self.m, ms, ln))
         return {"index": (ms[0], ln[0]), "query": (ms[1], ln[1])}
+
+    # ------------------------------------------------------------------ the map's lane lines (lf_map_lanes)
+    @staticmethod
+    def lanes_config(**overrides):
+        """The library's default `_lib.LfLanesConfig` (lf_map_lanes_default_config) with the overrides applied: radius, max_offset,
+        max_sin, min_hits, min_entries, color_mask."""
+        c = _lib.LfLanesConfig()
+        _lib.load().lf_map_lanes_default_config(ctypes.byref(c))
+        kinds = dict((k, t) for k, t in _lib.LfLanesConfig._fields_ if k != "reserved_")
+        for k, val in overrides.items():
+            if k not in kinds:
+                raise TypeError("lanes_config: unknown field %r" % (k,))
+            setattr(c, k, int(val) if kinds[k] is ctypes.c_int32 else float(val))
+        return c
+
+    def _lanes(self, config, lane_of, n_links, support, lanes, max_lanes, on_device):
+        res = _lib.LfLanesResult()
+        self._check(self.lib.lf_map_lanes(self.m, ctypes.byref(config), ctypes.byref(res), lane_of, n_links, support, lanes, int(max_lanes),
+                                          on_device))
+        return {k: int(getattr(res, k)) for k, _ in _lib.LfLanesResult._fields_}
+
+    def lanes(self, config=None):
+        """Group the map's entries into lane lines (lf_map_lanes; waits for the map's stream; the map is not changed).  config: an
+        `_lib.LfLanesConfig` (lanes_config).  Returns the named tuple (result, lane_of, n_links, support, lanes): result is
+        {'size', 'n_eligible', 'n_components', 'n_lanes', 'n_links'}; lane_of, n_links and support are (capacity,) int32, one value
+        per physical row (lane_of -1: in no lane; support: the members of the row's component, the filter for entries that no
+        neighbour supports); lanes is a record array of `_lib.LANE_DTYPE`, one lf_lane per lane in ascending first_row."""
+        config = self.lanes_config() if config is None else config
+        max_lanes = max(1, self.capacity // max(1, config.min_entries))          # a lane has at least min_entries rows
+        lane_of, n_links, support = (np.empty(self.capacity, np.int32) for _ in range(3))
+        table = np.zeros(max_lanes, _lib.LANE_DTYPE)
+        res = self._lanes(config, lane_of.ctypes.data, n_links.ctypes.data, support.ctypes.data, table.ctypes.data, max_lanes, 0)
+        return Lanes(res, lane_of, n_links, support, table[:res["n_lanes"]])
+
+    def lanes_device(self, config=None, lane_of=None, n_links=None, support=None, lanes=None):
+        """`lanes` with the outputs in device memory, as torch tensors that the library writes in place (no copy): lane_of, n_links
+        and support (capacity,) int32, lanes (max_lanes, 56) uint8, one lf_lane (`_lib.LANE_DTYPE`) per row.  None: a new tensor on
+        the map's device; False: not wanted (NULL).  Returns the named tuple (result, lane_of, n_links, support, lanes) of the same
+        tensors, lanes cut to its n_lanes rows (a view).  Raises LanefrontError (code -2) when lanes has fewer rows than the map
+        has lanes: the three arrays are filled in then, lanes is untouched.  The call waits for the map's stream; work of the
+        caller's own that is still queued on the tensors it passes must have finished."""
+        import torch
+        config = self.lanes_config() if config is None else config
+        dev = torch.device("cuda", self._device)
+
+        def rows(t):
+            if t is False:
+                return None
+            if t is None:
+                return torch.empty(self.capacity, dtype=torch.int32, device=dev)
+            if t.dtype != torch.int32 or t.numel() < self.capacity or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("lanes_device: a per-row tensor is a contiguous int32 device tensor of capacity values")
+            return t
+        lane_of, n_links, support = rows(lane_of), rows(n_links), rows(support)
+        if lanes is None:
+            lanes = torch.empty((max(1, self.capacity // max(1, config.min_entries)), LANE_BYTES), dtype=torch.uint8, device=dev)
+        elif lanes is False:
+            lanes = None
+        elif lanes.dtype != torch.uint8 or lanes.dim() != 2 or lanes.shape[1] != LANE_BYTES or not lanes.is_contiguous() or not lanes.is_cuda:
+            raise ValueError("lanes_device: lanes is a contiguous (max_lanes, %d) uint8 device tensor" % LANE_BYTES)
+        ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+        res = self._lanes(config, ptr(lane_of), ptr(n_links), ptr(support), ptr(lanes), 0 if lanes is None else lanes.shape[0], 1)
+        return Lanes(res, lane_of, n_links, support, None if lanes is None else lanes[:res["n_lanes"]])
+
+    def lanes_timing(self):
+        """{'index': (ms, launches), 'table': (ms, launches)} of the `lanes` calls since the previous call (needs
+        set_profiling(True)): the build of the hash grid, and link + label + table; one launch is one call's kernels of that stage."""
+        ms, ln = (ctypes.c_double * 2)(), (ctypes.c_int32 * 2)()
+        self._check(self.lib.lf_map_lanes_timing(self.m, ms, ln))
+        return {"index": (ms[0], ln[0]), "table": (ms[1], ln[1])}
 
     @staticmethod
     def carry(poses, last_odometry, last_corrected):

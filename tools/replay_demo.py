@@ -6,7 +6,7 @@ wire bodies.  The first batch is checked against the oracle (pixels, segments, m
 
     python tools/replay_demo.py [--frames 1024] [--batch 128] [--threads 32] [--geometry fullres|parity] [--map-jpeg map.jpg]
                                 [--overlay-jpeg DIR] [--align | --smooth | --localize] [--prune EVERY[:min_hits[:age]]]
-                                [--near RADIUS[:max_offset[:max_sin]]]
+                                [--near RADIUS[:max_offset[:max_sin]]] [--lanes RADIUS[:max_offset[:max_sin[:min_entries]]]]
 
 --map-jpeg writes the final map as the reference's README shows it (show_map's coloured segments seen from above, lf_map_render
 fitted to the map) as a JPEG: rendered and encoded on the device, only the file's bytes cross the bus.
@@ -20,6 +20,8 @@ show_map's marker width; the seeded entries stay.  Each prune prints its result 
 midpoint lies within RADIUS metres of the segment's are looked at; max_offset and max_sin default to the library's).  At the end it
 prints the matched share of segments and the mean number of candidates per segment (n_near), and under --align the share of frames
 whose status is `ok`, and the endpoints they used, with the gate and, from a second map fed the same stream, without it.
+--lanes RADIUS[:max_offset[:max_sin[:min_entries]]] groups the final map into lane lines (lf_map_lanes; the fields left out default
+to the library's) and prints one line per lane -- number, colour, entries, hits, box -- and the count of entries in no lane.
 """
 import argparse, io, os, sys, time
 import numpy as np
@@ -59,7 +61,17 @@ ap.add_argument("--prune", default=None, metavar="EVERY[:min_hits[:age]]",
 ap.add_argument("--near", default=None, metavar="RADIUS[:max_offset[:max_sin]]",
                 help="gate every step's association by the frames' poses (lf_map_set_near); prints the matched share and the mean n_near, "
                      "and under --align the share of ok frames with and without the gate")
+ap.add_argument("--lanes", default=None, metavar="RADIUS[:max_offset[:max_sin[:min_entries]]]",
+                help="after the replay, group the map into lane lines (lf_map_lanes) and print one line per lane and the entries in no lane")
 args = ap.parse_args()
+lanes_fields = None
+if args.lanes:
+    parts = args.lanes.split(":")
+    if not 1 <= len(parts) <= 4:
+        ap.error("--lanes takes RADIUS[:max_offset[:max_sin[:min_entries]]]")
+    lanes_fields = dict(zip(("radius", "max_offset", "max_sin"), (float(v) for v in parts[:3])))
+    if len(parts) == 4:
+        lanes_fields["min_entries"] = int(parts[3])
 near_fields = None
 if args.near:
     parts = [float(v) for v in args.near.split(":")]
@@ -198,6 +210,17 @@ if near_cfg is not None:
               % (100.0 * ok_frames[0] / all_frames, used_endpoints[0], 100.0 * ok_frames[1] / all_frames, used_endpoints[1], all_frames))
 elif args.align and all_frames:
     print("aligned frames that end ok: %.1f %% (%d endpoints used), of %d frames" % (100.0 * ok_frames[0] / all_frames, used_endpoints[0], all_frames))
+
+if lanes_fields:
+    lc = live.lanes_config(**lanes_fields)
+    got = live.lanes(lc)
+    r = got.result
+    print("lanes (radius %g m, max_offset %g m, max_sin %g, min_entries %d): %d of %d entries eligible, %d links, %d components, %d lanes"
+          % (lc.radius, lc.max_offset, lc.max_sin, lc.min_entries, r["n_eligible"], r["size"], r["n_links"], r["n_components"], r["n_lanes"]))
+    for k, lane in enumerate(got.lanes):
+        print("lane %d: colour %d, %d entries, %d hits, box x %.3f .. %.3f m, y %.3f .. %.3f m"
+              % (k, lane["color"], lane["n_entries"], lane["hits"], lane["box"][0], lane["box"][2], lane["box"][1], lane["box"][3]))
+    print("entries in no lane: %d (%d of them eligible)" % (int((got.lane_of[:r["size"]] < 0).sum()), int(((got.lane_of[:r["size"]] < 0) & (got.support[:r["size"]] > 0)).sum())))
 
 if args.map_jpeg:
     side = args.map_size
