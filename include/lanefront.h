@@ -1029,6 +1029,96 @@ LF_API int lf_map_lanes(lf_map* m, const lf_lanes_config* c, lf_lanes_result* re
  * table (one launch = one call's kernels of that stage).  Stages of their own: the other timing calls are unchanged. */
 LF_API int lf_map_lanes_timing(lf_map* m, double ms[2], int32_t launches[2]);
 
+/* ---- the live map's lane lines as ordered polylines: lf_map_polylines ------------------------------------
+ * lf_map_lanes leaves a lane an unordered set of rows.  lf_map_polylines adds the geometry: a lane's entries are thinned to a few
+ * vertices on a grid, each vertex links to at most one neighbour ahead and one behind, and the resulting paths and cycles are
+ * written out as ordered polylines with a `closed` flag.  The reference has no such stage: this is the package's OWN contract,
+ * written so that a sequential restatement (tests/map_polylines_ref.py: dictionaries, no hash table) and the kernels
+ * (k_map_polylines.hip) agree bit for bit.  Nothing of the map is changed.  All geometry is f64, unfused, in the order written:
+ * + - * /, the correctly rounded square root, round-half-even to int64 (llrint) and integers; no trigonometry; a comparison with a
+ * NaN fails.
+ *
+ *   A  lanes            lane_of[t] is exactly what lf_map_lanes gives under c->lanes.
+ *   B  home cells       Entry t PARTICIPATES when lane_of[t] >= 0 and its midpoint's cell hx = cell_of(mx, cell), hy = cell_of(my,
+ *                       cell) (the near contract's floor(v / cell) clamped to int32; mx = (ax + bx) * 0.5) lies strictly inside
+ *                       (INT32_MIN + reach + 1, INT32_MAX - reach - 1) in both axes.  count(lane, cx, cy): the participating entries
+ *                       with that lane and home cell.
+ *   C  migration        ex = bx - ax, ey = by - ay; the entry is HORIZONTAL when ex*ex >= ey*ey, and its lateral axis is y then,
+ *                       otherwise x.  Among the three cells at lateral offset d in {-1, 0, +1} from its home cell the entry is
+ *                       ASSIGNED to the one with the largest count; among equal counts the smallest d wins (two equal cells side
+ *                       by side collapse into one).  The counts are the home counts of B: one level, no chains.  (cx, cy) is the
+ *                       assigned cell.  (Without this step a line that runs along a cell boundary falls into fragments.)
+ *   D  vertices         A vertex is the set of participating entries with equal (lane, cx, cy): first_row (the smallest member
+ *                       row, its identity), n_entries, hits (int64 sum), and four int64 sums over the members:
+ *                         SX of llrint((mx - (double)cx * cell) * 65536.0),  SY the same of my and cy,
+ *                         SC of llrint(((ex*ex - ey*ey) / l2) * 65536.0),  SS of llrint(((2.0 * (ex*ey)) / l2) * 65536.0),
+ *                       l2 = ex*ex + ey*ey.  Every summand is below 2^22 in size: the sums are exact and no output depends on
+ *                       the order of evaluation.
+ *   E  vertex values    x = (double)cx * cell + ((double)SX / (double)n_entries) * 0x1p-16, y likewise.  The tangent is the half
+ *                       angle of the summed double-angle vector with tx >= 0: C = (double)SC, S = (double)SS, h = sqrt(C*C + S*S);
+ *                       h == 0: tx = ty = 0, the vertex has NO DIRECTION; otherwise c = C / h, s = S / h and
+ *                         c >= 0:    tx = sqrt((1.0 + c) * 0.5), ty = (s * 0.5) / tx
+ *                         otherwise: r = sqrt((1.0 - c) * 0.5), ty = s < 0 ? -r : r, tx = (s * 0.5) / ty.
+ *   F  neighbours       The candidates of a vertex v with a direction: the vertices u != v of v's lane that have a direction,
+ *                       |cx_u - cx_v| <= reach, |cy_u - cy_v| <= reach and d2 = ddx*ddx + ddy*ddy <= max_gap*max_gap with ddx =
+ *                       x_u - x_v, ddy = y_u - y_v.  With a = ddx*tx_v + ddy*ty_v: fwd(v) is the candidate with a > 0 and the
+ *                       smallest (d2, first_row_u), bwd(v) the same with a < 0; a == 0 is on neither side.  An EDGE {v, u} exists
+ *                       when u is fwd(v) or bwd(v) AND v is fwd(u) or bwd(u): a vertex has at most two edges, and the edge graph
+ *                       is a disjoint union of paths, cycles and single vertices.
+ *   G  polylines        Each connected component of the edge graph is one polyline; polylines are numbered by ascending smallest
+ *                       first_row among their vertices.  A path starts at whichever of its two ends has the smaller first_row.  A
+ *                       cycle (closed = 1) starts at its vertex of smallest first_row and goes first to whichever neighbour has
+ *                       the smaller first_row.  A single vertex is a polyline of one.
+ *   outputs             vertex_of[t]: the entry's vertex as an index into vertices; -1 for entries that do not participate and
+ *                       for rows in [size, capacity).  vertices[n_vertices] in polyline order: polyline k owns [first_vertex,
+ *                       first_vertex + n_vertices).  polylines[n_polylines].  Two calls on the same map give the same bytes.
+ *   capacity            a table given and too small (n_vertices > max_vertices or n_polylines > max_polylines): LF_ERR_CAPACITY
+ *                       with res and vertex_of filled in and BOTH tables untouched; nothing is truncated.
+ *   limits              Copies of a line spread laterally come out as ONE polyline wherever they lie in the grid while their
+ *                       lateral sigma is at most a fifth of `cell`; beyond that it depends on the position (a band centred on a
+ *                       cell boundary falls into pieces first), and at 0.4 cells no position is safe: step C has one level, and
+ *                       the tail beyond the lighter of two equal rows moves INTO that row.  Enlarge `cell` for wider bands.
+ * The calling form is lf_map_lanes': a maintenance call on the map's stream, it waits, a pending failing update is reported first,
+ * the map is untouched, an empty map gives LF_OK with zeros and -1s, the arrays are device (on_device = 1) or host (0) arrays and
+ * each may be NULL, and the replicas of a multi-GPU run agree without a collective.
+ * LF_ERR_BAD_ARG, touching nothing: everything lf_map_lanes refuses (of c->lanes); a cell that is not finite or outside 2^-10 ..
+ * 16; a max_gap that is not finite or <= 0; a reach outside 1 .. 8; a negative capacity; a table given with capacity 0. */
+typedef struct lf_polylines_config {
+    lf_lanes_config lanes; /* the lane rule, as lf_map_lanes takes it */
+    double  cell;          /* metres, finite, 2^-10 .. 16: the vertices' grid; default 0.10 */
+    double  max_gap;       /* metres, finite, > 0: two linked vertices are at most this far apart; default 0.30 */
+    int32_t reach;         /* cells, 1 .. 8: a pair more than this many cells apart in either axis is never a candidate; default 3 */
+    int32_t reserved_;     /* 0 */
+} lf_polylines_config;
+typedef struct lf_polyline_vertex { /* 64 bytes */
+    int32_t lane;                  /* the lane's number, as lf_map_lanes numbers them */
+    int32_t first_row;             /* the smallest member row: the vertex's identity */
+    int32_t n_entries;
+    int32_t polyline;              /* the polyline that owns it */
+    int32_t cx, cy;                /* its cell */
+    int64_t hits;                  /* sum of the members' hits */
+    double  x, y, tx, ty;          /* E; each value v + 0.0 (no -0); tx = ty = 0: no direction */
+} lf_polyline_vertex;
+typedef struct lf_polyline {       /* 32 bytes */
+    int32_t lane, first_vertex, n_vertices, closed;
+    int32_t first_row;             /* the smallest first_row among its vertices */
+    int32_t n_entries;
+    int64_t hits;
+} lf_polyline;
+typedef struct lf_polylines_result { int32_t size, n_lanes, n_participating, n_vertices, n_polylines, n_closed, n_edges, reserved_; } lf_polylines_result;
+LF_API int lf_sizeof_polylines_config(void);
+LF_API int lf_sizeof_polyline_vertex(void);
+LF_API int lf_sizeof_polyline(void);
+LF_API int lf_sizeof_polylines_result(void);
+LF_API void lf_map_polylines_default_config(lf_polylines_config* c);
+LF_API int lf_map_polylines(lf_map* m, const lf_polylines_config* c, lf_polylines_result* res, int32_t* vertex_of /* [capacity] or NULL */,
+                            lf_polyline_vertex* vertices /* [max_vertices] or NULL */, int max_vertices,
+                            lf_polyline* polylines /* [max_polylines] or NULL */, int max_polylines, int on_device);
+/* ms and launches accumulated since the previous call, with profiling on; resets them: [0] the lanes stage (index, link, label),
+ * [1] the vertices (cells, migration, sums, values), [2] links + order + outputs.  Stages of their own: lf_map_lanes_timing and the
+ * other timing calls are unchanged. */
+LF_API int lf_map_polylines_timing(lf_map* m, double ms[3], int32_t launches[3]);
+
 /* ---- Histogram lane filter: lane pose from ground segments -----------------------------------------
  * LaneFilterHistogram (src/lane_filter/include/lane_filter/lane_filter.py:12-161) as lane_filter_node.processSegments
  * drives it (src/lane_filter/src/lane_filter_node.py:49-87): per frame predict(dt, v, w) -> update(segments) ->

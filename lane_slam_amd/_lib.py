@@ -50,6 +50,8 @@ EXPORTS = (
     "lf_sizeof_prune_config", "lf_sizeof_prune_result", "lf_map_prune_default_config", "lf_map_prune", "lf_map_prune_timing",
     "lf_sizeof_near_config", "lf_map_near_default_config", "lf_map_associate_near", "lf_map_set_near", "lf_map_get_near", "lf_map_near_timing",
     "lf_sizeof_lanes_config", "lf_sizeof_lane", "lf_sizeof_lanes_result", "lf_map_lanes_default_config", "lf_map_lanes", "lf_map_lanes_timing",
+    "lf_sizeof_polylines_config", "lf_sizeof_polyline_vertex", "lf_sizeof_polyline", "lf_sizeof_polylines_result",
+    "lf_map_polylines_default_config", "lf_map_polylines", "lf_map_polylines_timing",
 )
 LF_ALIGN_OK, LF_ALIGN_FEW, LF_ALIGN_DEGENERATE, LF_ALIGN_REJECTED = 0, 1, 2, 3
 ALIGN_STATUS = ("ok", "few", "degenerate", "rejected")
@@ -247,6 +249,37 @@ class LfLanesResult(ctypes.Structure):
                 ("n_links", ctypes.c_int64)]
 
 
+class LfPolylinesConfig(ctypes.Structure):
+    """ctypes mirror of `lf_polylines_config` (include/lanefront.h)."""
+    _fields_ = [("lanes", LfLanesConfig), ("cell", ctypes.c_double), ("max_gap", ctypes.c_double), ("reach", ctypes.c_int32),
+                ("reserved_", ctypes.c_int32)]
+
+
+class LfPolylineVertex(ctypes.Structure):
+    """ctypes mirror of `lf_polyline_vertex` (include/lanefront.h)."""
+    _fields_ = [("lane", ctypes.c_int32), ("first_row", ctypes.c_int32), ("n_entries", ctypes.c_int32), ("polyline", ctypes.c_int32),
+                ("cx", ctypes.c_int32), ("cy", ctypes.c_int32), ("hits", ctypes.c_int64), ("x", ctypes.c_double), ("y", ctypes.c_double),
+                ("tx", ctypes.c_double), ("ty", ctypes.c_double)]
+
+
+class LfPolyline(ctypes.Structure):
+    """ctypes mirror of `lf_polyline` (include/lanefront.h)."""
+    _fields_ = [("lane", ctypes.c_int32), ("first_vertex", ctypes.c_int32), ("n_vertices", ctypes.c_int32), ("closed", ctypes.c_int32),
+                ("first_row", ctypes.c_int32), ("n_entries", ctypes.c_int32), ("hits", ctypes.c_int64)]
+
+
+# the same layouts as numpy records: what LineAssociator.polylines returns
+POLYLINE_VERTEX_DTYPE = [("lane", "<i4"), ("first_row", "<i4"), ("n_entries", "<i4"), ("polyline", "<i4"), ("cx", "<i4"), ("cy", "<i4"),
+                         ("hits", "<i8"), ("x", "<f8"), ("y", "<f8"), ("tx", "<f8"), ("ty", "<f8")]
+POLYLINE_DTYPE = [("lane", "<i4"), ("first_vertex", "<i4"), ("n_vertices", "<i4"), ("closed", "<i4"), ("first_row", "<i4"), ("n_entries", "<i4"),
+                  ("hits", "<i8")]
+
+
+class LfPolylinesResult(ctypes.Structure):
+    """ctypes mirror of `lf_polylines_result` (include/lanefront.h)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("size", "n_lanes", "n_participating", "n_vertices", "n_polylines", "n_closed", "n_edges", "reserved_")]
+
+
 _lib = None
 
 
@@ -436,6 +469,15 @@ def load():
     lib.lf_map_lanes_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
     for f in ("lf_sizeof_lanes_config", "lf_sizeof_lane", "lf_sizeof_lanes_result", "lf_map_lanes", "lf_map_lanes_timing"):
         getattr(lib, f).restype = ci
+    for f in ("lf_sizeof_polylines_config", "lf_sizeof_polyline_vertex", "lf_sizeof_polyline", "lf_sizeof_polylines_result"):
+        getattr(lib, f).argtypes = []
+        getattr(lib, f).restype = ci
+    lib.lf_map_polylines_default_config.argtypes = [ctypes.POINTER(LfPolylinesConfig)]
+    lib.lf_map_polylines_default_config.restype = None
+    lib.lf_map_polylines.argtypes = [vp, ctypes.POINTER(LfPolylinesConfig), ctypes.POINTER(LfPolylinesResult), vp, vp, ci, vp, ci, ci]
+    lib.lf_map_polylines.restype = ci
+    lib.lf_map_polylines_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
+    lib.lf_map_polylines_timing.restype = ci
     lib.lf_descriptor_default_params.argtypes = [ctypes.POINTER(LfDescriptorParams)]
     lib.lf_descriptor_default_params.restype = None
     lib.lf_set_descriptor_params.argtypes = [vp, ctypes.POINTER(LfDescriptorParams)]

@@ -4,6 +4,7 @@
 // exactly the gate that argument covers.
 #pragma once
 #include "k_map_near.h"
+#include "k_map_pairs.h"
 
 namespace lf {
 namespace ln {
@@ -23,6 +24,10 @@ struct Rule { nr::Rule geo; int min_entries, color_mask; };
 
 // the bit of color_mask that a colour byte answers to
 LF_NR_HD int colour_bit(int colour) { return 1 << (colour < 3 ? colour : 3); }
+
+// the reason lf_map_lanes refuses a configuration with, or null; the kernels' rule of one that passed (lanefront_map_lanes.hip)
+const char* bad_config(const lf_lanes_config* c);
+Rule make_rule(const lf_lanes_config* c);
 
 #if defined(__HIPCC__)
 // Device arrays of one call, [bound] each (box [bound][4]); everything belongs to the map's handle.
@@ -52,6 +57,41 @@ struct Work {
     int* counters;                         // [kNCounters]
     int bound;                             // the host's size of the map: sizes the grids and the arrays
 };
+
+// ---- what k_map_polylines.hip shares with k_map_lanes.hip
+// the rows the kernels may touch: the map's size as the device knows it, never beyond what the host sized the arrays for
+__device__ __forceinline__ int rows(const MapDevice& md, int bound)
+{
+    const int size = ma::map_size(md);
+    return size < bound ? size : bound;
+}
+
+__device__ __forceinline__ int peek(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of x while the forest changes; halves the path behind it (k_map_lanes.h: at most x turns)
+__device__ __forceinline__ int find(int* parent, int x)
+{
+    for (;;) {
+        const int p = peek(parent + x);
+        if (p == x) return x;
+        const int gp = peek(parent + p);
+        if (gp == p) return p;
+        atomicMin(parent + x, gp);
+        x = gp;
+    }
+}
+
+// a and b become one tree whose root is its smallest row (k_map_lanes.h: a + b falls from turn to turn)
+__device__ __forceinline__ void unite(int* parent, int a, int b)
+{
+    for (;;) {
+        a = find(parent, a);
+        b = find(parent, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        if (atomicCAS(parent + a, a, b) == a) return;
+    }
+}
 
 // the caller's arrays, device addresses; each may be null
 struct Out { int32_t* lane_of; int32_t* n_links; int32_t* support; lf_lane* lanes; int max_lanes; };

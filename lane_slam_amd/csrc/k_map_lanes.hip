@@ -28,13 +28,6 @@ namespace ln {
 
 namespace {
 
-// the rows the kernels may touch: the map's size as the device knows it, never beyond what the host sized the arrays for
-__device__ __forceinline__ int rows(const MapDevice& md, int bound)
-{
-    const int size = ma::map_size(md);
-    return size < bound ? size : bound;
-}
-
 // a finite double as a key that orders as the doubles do (-0 below +0)
 __device__ __forceinline__ unsigned long long key_of(double v)
 {
@@ -45,33 +38,6 @@ __device__ __forceinline__ double value_of(unsigned long long k)
 {
     const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
     return __longlong_as_double((long long)u);
-}
-
-__device__ __forceinline__ int peek(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of x while the forest changes; halves the path behind it (k_map_lanes.h: at most x turns)
-__device__ __forceinline__ int find(int* parent, int x)
-{
-    for (;;) {
-        const int p = peek(parent + x);
-        if (p == x) return x;
-        const int gp = peek(parent + p);
-        if (gp == p) return p;
-        atomicMin(parent + x, gp);
-        x = gp;
-    }
-}
-
-// a and b become one tree whose root is its smallest row (k_map_lanes.h: a + b falls from turn to turn)
-__device__ __forceinline__ void unite(int* parent, int a, int b)
-{
-    for (;;) {
-        a = find(parent, a);
-        b = find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        if (atomicCAS(parent + a, a, b) == a) return;
-    }
 }
 
 // an entry in the role of the near contract's segment

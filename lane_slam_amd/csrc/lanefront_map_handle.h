@@ -1,7 +1,8 @@
 // The live map's handle, for the translation units of lf_map_*: the map itself (lanefront_map.hip), its two views
 // (lanefront_map_render.hip, lanefront_map_camera.hip), the pose alignment (lanefront_map_align.hip) and the trajectory smoother
 // (lanefront_map_smooth.hip); the localisation without a prior pose (lanefront_map_localize.hip); the culling (lanefront_map_prune.hip);
-// the association gated by the prior pose (lanefront_map_near.hip); the lane lines (lanefront_map_lanes.hip).  The three pose solvers share one
+// the association gated by the prior pose (lanefront_map_near.hip); the lane lines (lanefront_map_lanes.hip) and their polylines
+// (lanefront_map_polylines.hip).  The three pose solvers share one
 // front end (argument check, batch opener, prior-pose upload) and the two solving steps one body and, with
 // lf_map_step_host, one host-form wrapper: all of it lives in lanefront_map_align.hip and is declared at the end of this file.
 #pragma once
@@ -24,6 +25,14 @@ struct MapNearState {
 struct MapLanesState {
     DevBuf work, counters, lane_of, n_links, support, lanes;     // k_map_lanes.h's Work, carved from one buffer; a host caller's outputs staged
     HostArray<int> h_counters;                               // pinned: the counters of k_map_lanes.h
+};
+
+// what lf_map_polylines keeps between calls (lanefront_map_polylines.hip): scratch that grows on demand; the lanes stage runs into
+// work arrays of this state's own, the index lives in MapNearState's buffers
+struct MapPolylinesState {
+    DevBuf lanes_work, lanes_counters, lane_of;              // k_map_lanes.h's Work and counters, and its lane_of [capacity]
+    DevBuf work, counters, vertex_of, vertices, polylines;   // k_map_polylines.h's Work, carved from one buffer; a host caller's outputs staged
+    HostArray<int> h_counters;                               // pinned: the counters of k_map_lanes.h, then those of k_map_polylines.h
 };
 
 // what lf_map_render and lf_map_bounds keep between calls: every buffer grows on demand and is reused
@@ -88,13 +97,14 @@ struct lf_map : lf::Core {
     std::vector<int32_t> h_chains;
     // per-stage timing: the stages of lf_map_get_timing, then kMapAlignStage (lf_map_align_timing), kMapSmoothStage
     // (lf_map_smooth_timing), kMapLocalizeStage (lf_map_localize_timing), kMapPruneStage (lf_map_prune_timing) and kMapNearIndexStage,
-    // kMapNearQueryStage (lf_map_near_timing), kMapLanesIndexStage, kMapLanesTableStage (lf_map_lanes_timing); past 4096
-    // outstanding records a bracket goes untimed
-    StageClock clock{LF_MAP_N_STAGES + 8, 4096, false};
+    // kMapNearQueryStage (lf_map_near_timing), kMapLanesIndexStage, kMapLanesTableStage (lf_map_lanes_timing), kMapPolylinesLanesStage,
+    // kMapPolylinesVerticesStage, kMapPolylinesLinksStage (lf_map_polylines_timing); past 4096 outstanding records a bracket goes untimed
+    StageClock clock{LF_MAP_N_STAGES + 11, 4096, false};
     bool near_on = false;                         // lf_map_set_near: the steps associate by lf_map_associate_near's rule with near_cfg
     lf_near_config near_cfg = {};
     std::unique_ptr<lf::MapNearState> near;       // lf_map_associate_near (lanefront_map_near.hip), made by its first call
     std::unique_ptr<lf::MapLanesState> lanes;     // lf_map_lanes (lanefront_map_lanes.hip), made by its first call
+    std::unique_ptr<lf::MapPolylinesState> polylines;   // lf_map_polylines (lanefront_map_polylines.hip), made by its first call
     std::unique_ptr<lf::MapPruneState> prune;     // lf_map_prune (lanefront_map_prune.hip), made by its first call
     std::unique_ptr<lf::MapRenderState> render;   // lf_map_render / lf_map_bounds (lanefront_map_render.hip), made by their first call
     std::unique_ptr<lf::MapCameraState> camera;   // lf_map_render_camera (lanefront_map_camera.hip), likewise
@@ -108,6 +118,9 @@ constexpr int kMapNearIndexStage = LF_MAP_N_STAGES + 4;
 constexpr int kMapNearQueryStage = LF_MAP_N_STAGES + 5;
 constexpr int kMapLanesIndexStage = LF_MAP_N_STAGES + 6;
 constexpr int kMapLanesTableStage = LF_MAP_N_STAGES + 7;
+constexpr int kMapPolylinesLanesStage = LF_MAP_N_STAGES + 8;
+constexpr int kMapPolylinesVerticesStage = LF_MAP_N_STAGES + 9;
+constexpr int kMapPolylinesLinksStage = LF_MAP_N_STAGES + 10;
 
 // ---- lanefront_map.hip's sequencing, for the translation units of the pose solvers
 // make the host mirror current: wait for the copy queued behind the last update (block = false: only look); a failing update the

@@ -6,7 +6,8 @@
 #include "lanefront_map_handle.h"
 #include "k_map_lanes.h"
 
-namespace {
+namespace lf {
+namespace ln {
 
 const char* bad_config(const lf_lanes_config* c)
 {
@@ -18,7 +19,20 @@ const char* bad_config(const lf_lanes_config* c)
     return nullptr;
 }
 
-}  // namespace
+Rule make_rule(const lf_lanes_config* c)
+{
+    Rule r;
+    memset(&r, 0, sizeof(r));
+    r.geo.r2 = c->radius * c->radius; r.geo.ms2 = c->max_sin * c->max_sin; r.geo.mo2 = c->max_offset * c->max_offset;
+    r.geo.cell = nr::cell_size(c->radius);
+    r.geo.test_sin = c->max_sin < 1; r.geo.test_offset = isfinite(c->max_offset) ? 1 : 0;
+    r.geo.min_hits = c->min_hits;
+    r.min_entries = c->min_entries; r.color_mask = c->color_mask;
+    return r;
+}
+
+}  // namespace ln
+}  // namespace lf
 
 extern "C" int lf_sizeof_lanes_config(void) { return (int)sizeof(lf_lanes_config); }
 extern "C" int lf_sizeof_lane(void) { return (int)sizeof(lf_lane); }
@@ -44,7 +58,7 @@ extern "C" int lf_map_lanes(lf_map* m, const lf_lanes_config* c, lf_lanes_result
     if (!m) return LF_ERR_NOT_INITIALISED;
     const char* who = "lf_map_lanes";
     if (!c || !res) { set_error(m, LF_ERR_BAD_ARG, "%s: null configuration or result", who); return LF_ERR_BAD_ARG; }
-    if (const char* why = bad_config(c)) { set_error(m, LF_ERR_BAD_ARG, "%s: bad configuration (%s)", who, why); return LF_ERR_BAD_ARG; }
+    if (const char* why = ln::bad_config(c)) { set_error(m, LF_ERR_BAD_ARG, "%s: bad configuration (%s)", who, why); return LF_ERR_BAD_ARG; }
     if (max_lanes < 0 || (lanes && max_lanes == 0)) { set_error(m, LF_ERR_BAD_ARG, "%s: max_lanes is >= 0, and >= 1 with a table", who); return LF_ERR_BAD_ARG; }
     LF_HIP_CHECK(m, hipSetDevice(m->device));
     int rc;
@@ -77,13 +91,7 @@ extern "C" int lf_map_lanes(lf_map* m, const lf_lanes_config* c, lf_lanes_result
     o.max_lanes = max_lanes;
     if ((rc = host.upload()) != LF_OK) return rc;
 
-    ln::Rule r;
-    memset(&r, 0, sizeof(r));
-    r.geo.r2 = c->radius * c->radius; r.geo.ms2 = c->max_sin * c->max_sin; r.geo.mo2 = c->max_offset * c->max_offset;
-    r.geo.cell = nr::cell_size(c->radius);
-    r.geo.test_sin = c->max_sin < 1; r.geo.test_offset = isfinite(c->max_offset) ? 1 : 0;
-    r.geo.min_hits = c->min_hits;
-    r.min_entries = c->min_entries; r.color_mask = c->color_mask;
+    const ln::Rule r = ln::make_rule(c);
     nr::Index ix;
     ix.start = static_cast<int*>(ns.start.p); ix.cursor = static_cast<int*>(ns.cursor.p); ix.bucket = static_cast<int*>(ns.bucket.p);
     ix.rec = static_cast<nr::Rec*>(ns.rec.p); ix.mask = (uint32_t)(buckets - 1); ix.bound = (int)bound;

@@ -1,0 +1,167 @@
+// lanefront C ABI, the live map's lane lines as ordered polylines (include/lanefront.h "lf_map_polylines"): the checks, the
+// scratch, the staging of host outputs and the sequence on the map's stream -- the index of the map as it stands (k_map_near.hip's,
+// in the near state's buffers), the lanes stage (ln::launch_lanes into work arrays of this call's own), then k_map_polylines.hip's
+// kernels -- and ONE host wait at the end, for `res`.  A host caller's two tables come down behind that wait, when their lengths
+// are known: two blocking copies more (a table that turns out too small must stay untouched, so nothing is copied ahead).
+#include <math.h>
+#include <string.h>
+#include "lanefront_map_handle.h"
+#include "k_map_polylines.h"
+
+namespace {
+
+const char* bad_config(const lf_polylines_config* c)
+{
+    if (const char* why = ln::bad_config(&c->lanes)) return why;
+    if (!isfinite(c->cell) || !(c->cell >= 0x1p-10 && c->cell <= 16.0)) return "cell is finite and 2^-10 .. 16";
+    if (!isfinite(c->max_gap) || !(c->max_gap > 0)) return "max_gap is finite and > 0";
+    if (c->reach < 1 || c->reach > 8) return "reach is 1 .. 8";
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" int lf_sizeof_polylines_config(void) { return (int)sizeof(lf_polylines_config); }
+extern "C" int lf_sizeof_polyline_vertex(void) { return (int)sizeof(lf_polyline_vertex); }
+extern "C" int lf_sizeof_polyline(void) { return (int)sizeof(lf_polyline); }
+extern "C" int lf_sizeof_polylines_result(void) { return (int)sizeof(lf_polylines_result); }
+
+extern "C" void lf_map_polylines_default_config(lf_polylines_config* c)
+{
+    if (!c) return;
+    memset(c, 0, sizeof(*c));
+    lf_map_lanes_default_config(&c->lanes);
+    c->cell = 0.10; c->max_gap = 0.30; c->reach = 3;
+}
+
+extern "C" int lf_map_polylines_timing(lf_map* m, double* ms, int32_t* launches)
+{
+    if (!m) return LF_ERR_NOT_INITIALISED;
+    m->clock.take(ms, launches, 3, kMapPolylinesLanesStage, 3);
+    return LF_OK;
+}
+
+extern "C" int lf_map_polylines(lf_map* m, const lf_polylines_config* c, lf_polylines_result* res, int32_t* vertex_of, lf_polyline_vertex* vertices,
+                                int max_vertices, lf_polyline* polylines, int max_polylines, int on_device)
+{
+    if (!m) return LF_ERR_NOT_INITIALISED;
+    const char* who = "lf_map_polylines";
+    if (!c || !res) { set_error(m, LF_ERR_BAD_ARG, "%s: null configuration or result", who); return LF_ERR_BAD_ARG; }
+    if (const char* why = bad_config(c)) { set_error(m, LF_ERR_BAD_ARG, "%s: bad configuration (%s)", who, why); return LF_ERR_BAD_ARG; }
+    if (max_vertices < 0 || (vertices && max_vertices == 0)) { set_error(m, LF_ERR_BAD_ARG, "%s: max_vertices is >= 0, and >= 1 with a table", who); return LF_ERR_BAD_ARG; }
+    if (max_polylines < 0 || (polylines && max_polylines == 0)) { set_error(m, LF_ERR_BAD_ARG, "%s: max_polylines is >= 0, and >= 1 with a table", who); return LF_ERR_BAD_ARG; }
+    LF_HIP_CHECK(m, hipSetDevice(m->device));
+    int rc;
+    // the map's size as it is behind everything queued so far; a failing update is reported first, as lf_map_size does
+    if ((rc = refresh_state(m)) != LF_OK) return rc;
+    const int cap = m->cfg.capacity;
+    const int size = m->h_state[0] < cap ? m->h_state[0] : cap;
+    const size_t bound = (size_t)(size > 0 ? size : 0);
+    if (!m->polylines) m->polylines.reset(new lf::MapPolylinesState());
+    if (!m->near) m->near.reset(new lf::MapNearState());
+    lf::MapPolylinesState& st = *m->polylines;
+    lf::MapNearState& ns = *m->near;
+    hipStream_t s = m->stream;
+    constexpr int kCounters = ln::kNCounters + pl::kNCounters;
+    if (!st.h_counters.p) LF_HIP_CHECK(m, st.h_counters.alloc(kCounters * sizeof(int)));
+    size_t buckets = nr::kMinBuckets, slots = pl::kMinSlots;
+    while (buckets < 2 * bound) buckets <<= 1;
+    while (slots < 2 * bound) slots <<= 1;
+    const size_t row_bytes = (size_t)cap * sizeof(int32_t);
+    if ((rc = scratch(m, st.counters, kCounters * sizeof(int))) || (rc = scratch(m, st.lane_of, row_bytes))) return rc;
+    if (bound > 0 &&
+        ((rc = scratch(m, st.lanes_work, bound * ln::kWorkBytesPerRow)) || (rc = scratch(m, st.work, bound * pl::kWorkBytesPerRow + slots * pl::kWorkBytesPerSlot)) ||
+         (rc = scratch(m, ns.start, (buckets + 4) * sizeof(int))) || (rc = scratch(m, ns.cursor, buckets * sizeof(int))) ||
+         (rc = scratch(m, ns.bucket, bound * sizeof(int))) || (rc = scratch(m, ns.rec, bound * sizeof(nr::Rec)))))
+        return rc;
+    Staging host(m);
+    pl::Out o;
+    o.vertex_of = vertex_of ? host.out(on_device, vertex_of, row_bytes, st.vertex_of) : nullptr;
+    o.vertices = vertices ? host.out(on_device, vertices, (size_t)max_vertices * sizeof(lf_polyline_vertex), st.vertices) : nullptr;
+    o.polylines = polylines ? host.out(on_device, polylines, (size_t)max_polylines * sizeof(lf_polyline), st.polylines) : nullptr;
+    o.max_vertices = max_vertices; o.max_polylines = max_polylines;
+    if ((rc = host.upload()) != LF_OK) return rc;
+
+    const ln::Rule lr = ln::make_rule(&c->lanes);
+    pl::Rule r;
+    memset(&r, 0, sizeof(r));
+    r.cell = c->cell; r.gap2 = c->max_gap * c->max_gap; r.reach = c->reach;
+    nr::Index ix;
+    ix.start = static_cast<int*>(ns.start.p); ix.cursor = static_cast<int*>(ns.cursor.p); ix.bucket = static_cast<int*>(ns.bucket.p);
+    ix.rec = static_cast<nr::Rec*>(ns.rec.p); ix.mask = (uint32_t)(buckets - 1); ix.bound = (int)bound;
+    int* counters = static_cast<int*>(st.counters.p);
+    ln::Work lw;
+    memset(&lw, 0, sizeof(lw));
+    lw.counters = counters; lw.bound = (int)bound;
+    ln::Out lo;
+    memset(&lo, 0, sizeof(lo));
+    lo.lane_of = static_cast<int32_t*>(st.lane_of.p);
+    pl::Work w;
+    memset(&w, 0, sizeof(w));
+    w.lane_of = lo.lane_of; w.counters = counters + ln::kNCounters; w.bound = (int)bound; w.slots = (int)slots;
+    unsigned long long* zeroed = nullptr;
+    if (bound > 0) {
+        // the lanes stage's arrays as lf_map_lanes carves them: the 8-byte arrays first, then the six of ints
+        lw.box = static_cast<unsigned long long*>(st.lanes_work.p);
+        lw.hsum = lw.box + 4 * bound;
+        lw.parent = reinterpret_cast<int*>(lw.hsum + bound);
+        lw.root = lw.parent + bound; lw.elig = lw.root + bound; lw.nl = lw.elig + bound; lw.cnt = lw.nl + bound; lw.lane_no = lw.cnt + bound;
+        // this call's: the records, the 8-byte arrays, the slots' (what starts at 0 together, then what starts at -1), the rows'
+        w.tmpv = static_cast<lf_polyline_vertex*>(st.work.p);
+        w.phits = reinterpret_cast<unsigned long long*>(w.tmpv + bound);
+        zeroed = w.phits + bound;
+        w.ssum = zeroed; w.shits = w.ssum + 4 * slots;
+        w.cnt1 = reinterpret_cast<int*>(w.shits + slots); w.sn = w.cnt1 + slots;
+        w.own1 = w.sn + slots; w.own2 = w.own1 + slots;
+        w.sfirst = w.own2 + slots; w.svid = w.sfirst + slots;
+        int* p = w.svid + slots;
+        for (int** a : { &w.part, &w.hx, &w.hy, &w.cx, &w.cy, &w.rslot, &w.vslot, &w.fwd, &w.bwd, &w.parent, &w.root, &w.psize, &w.phead, &w.pn,
+                         &w.pid, &w.pfirst, &w.pos }) { *a = p; p += bound; }
+        w.nb = p;
+    }
+    LF_HIP_CHECK(m, hipMemsetAsync(counters, 0, kCounters * sizeof(int), s));
+    {
+        StageClock::Scope t(m, m->clock, kMapPolylinesLanesStage);
+        if (bound > 0) {
+            LF_HIP_CHECK(m, hipMemsetAsync(ix.start, 0, (buckets + 1) * sizeof(int), s));
+            nr::launch_near_index(m->d, lr.geo.cell, ix, s);
+        }
+        ln::launch_lanes(lr, m->d, ix, lw, lo, s);
+    }
+    if (bound > 0) {
+        StageClock::Scope t(m, m->clock, kMapPolylinesVerticesStage);
+        LF_HIP_CHECK(m, hipMemsetAsync(zeroed, 0, slots * (5 * 8 + 2 * 4), s));
+        LF_HIP_CHECK(m, hipMemsetAsync(w.own1, 0xFF, slots * 2 * sizeof(int), s));
+        LF_HIP_CHECK(m, hipMemsetAsync(w.sfirst, 0x7F, slots * sizeof(int), s));
+        pl::launch_vertices(r, m->d, w, s);
+    }
+    {
+        StageClock::Scope t(m, m->clock, kMapPolylinesLinksStage);
+        pl::launch_polylines(r, m->d, w, o, s);
+    }
+    LF_HIP_CHECK(m, hipGetLastError());
+    LF_HIP_CHECK(m, hipMemcpyAsync(st.h_counters, counters, kCounters * sizeof(int), hipMemcpyDeviceToHost, s));
+    // vertex_of of a host caller rides behind the counters; the wait is the call's only one
+    if ((rc = fetch(m, { { vertex_of, o.vertex_of, row_bytes } })) != LF_OK) return rc;
+    LF_HIP_CHECK(m, hipStreamSynchronize(s));
+    const int* hc = st.h_counters;
+    const int* pc = hc + ln::kNCounters;
+    res->size = size > 0 ? size : 0; res->n_lanes = hc[ln::kNLanes];
+    res->n_participating = pc[pl::kNParticipating]; res->n_vertices = pc[pl::kNVertices]; res->n_polylines = pc[pl::kNPolylines];
+    res->n_closed = pc[pl::kNClosed]; res->n_edges = pc[pl::kNEdges]; res->reserved_ = 0;
+    if (pc[pl::kNDropped] != 0) {                // cannot be: the tables hold twice the rows (k_map_polylines.hip slot_of)
+        set_error(m, LF_ERR_CAPACITY, "%s: internal: %d rows found no slot in a table of %d", who, pc[pl::kNDropped], (int)slots);
+        return LF_ERR_CAPACITY;
+    }
+    if ((vertices && res->n_vertices > max_vertices) || (polylines && res->n_polylines > max_polylines)) {
+        set_error(m, LF_ERR_CAPACITY, "%s: the map has %d vertices in %d polylines and the tables hold max_vertices = %d, max_polylines = %d; the tables were not written",
+                  who, res->n_vertices, res->n_polylines, max_vertices, max_polylines);
+        return LF_ERR_CAPACITY;
+    }
+    // a host caller's tables: only now are their lengths known (the device form's were written in place)
+    if (vertices && !on_device && res->n_vertices > 0)
+        LF_HIP_CHECK(m, hipMemcpy(vertices, o.vertices, (size_t)res->n_vertices * sizeof(lf_polyline_vertex), hipMemcpyDeviceToHost));
+    if (polylines && !on_device && res->n_polylines > 0)
+        LF_HIP_CHECK(m, hipMemcpy(polylines, o.polylines, (size_t)res->n_polylines * sizeof(lf_polyline), hipMemcpyDeviceToHost));
+    return LF_OK;
+}

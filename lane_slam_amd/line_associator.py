@@ -21,6 +21,10 @@ _WHEN_FULL = {"ring": 0, "error": 1}
 # what LineAssociator.lanes and lanes_device return
 Lanes = collections.namedtuple("Lanes", ("result", "lane_of", "n_links", "support", "lanes"))
 LANE_BYTES = ctypes.sizeof(_lib.LfLane)
+# what LineAssociator.polylines and polylines_device return
+Polylines = collections.namedtuple("Polylines", ("result", "vertex_of", "vertices", "polylines"))
+POLYLINE_VERTEX_BYTES = ctypes.sizeof(_lib.LfPolylineVertex)
+POLYLINE_BYTES = ctypes.sizeof(_lib.LfPolyline)
 
 
 class LineAssociator(object):
@@ -461,6 +465,97 @@ class LineAssociator(object):
         ms, ln = (ctypes.c_double * 2)(), (ctypes.c_int32 * 2)()
         self._check(self.lib.lf_map_lanes_timing(self.m, ms, ln))
         return {"index": (ms[0], ln[0]), "table": (ms[1], ln[1])}
+
+    # ------------------------------------------------------------------ the lane lines as ordered polylines (lf_map_polylines)
+    @staticmethod
+    def polylines_config(**overrides):
+        """The library's default `_lib.LfPolylinesConfig` (lf_map_polylines_default_config) with the overrides applied: cell,
+        max_gap, reach, and the fields of lanes_config, which go to the embedded lane rule."""
+        c = _lib.LfPolylinesConfig()
+        _lib.load().lf_map_polylines_default_config(ctypes.byref(c))
+        for k, val in overrides.items():
+            for where, fields in ((c, _lib.LfPolylinesConfig._fields_), (c.lanes, _lib.LfLanesConfig._fields_)):
+                kinds = dict((f, t) for f, t in fields if f not in ("reserved_", "lanes"))
+                if k in kinds:
+                    setattr(where, k, int(val) if kinds[k] is ctypes.c_int32 else float(val))
+                    break
+            else:
+                raise TypeError("polylines_config: unknown field %r" % (k,))
+        return c
+
+    def _polylines(self, config, vertex_of, vertices, max_vertices, polylines, max_polylines, on_device):
+        res = _lib.LfPolylinesResult()
+        rc = self.lib.lf_map_polylines(self.m, ctypes.byref(config), ctypes.byref(res), vertex_of, vertices, int(max_vertices), polylines,
+                                       int(max_polylines), on_device)
+        self._check(rc)
+        return {k: int(getattr(res, k)) for k, _ in _lib.LfPolylinesResult._fields_}
+
+    def polylines(self, config=None):
+        """Order each lane line of the map into polylines (lf_map_polylines; waits for the map's stream; the map is not changed).
+        config: an `_lib.LfPolylinesConfig` (polylines_config).  Returns the named tuple (result, vertex_of, vertices, polylines):
+        result is {'size', 'n_lanes', 'n_participating', 'n_vertices', 'n_polylines', 'n_closed', 'n_edges', 'reserved_'}; vertex_of
+        is (capacity,) int32, each physical row's vertex as an index into vertices (-1: none); vertices is a record array of
+        `_lib.POLYLINE_VERTEX_DTYPE` in polyline order and polylines one of `_lib.POLYLINE_DTYPE`: polyline k owns
+        vertices[first_vertex : first_vertex + n_vertices] (`polyline_xy`).  The tables are sized from a first call's result."""
+        config = self.polylines_config() if config is None else config
+        vertex_of = np.empty(self.capacity, np.int32)
+        res = self._polylines(config, vertex_of.ctypes.data, None, 0, None, 0, 0)
+        vt = np.zeros(max(1, res["n_vertices"]), _lib.POLYLINE_VERTEX_DTYPE)
+        pt = np.zeros(max(1, res["n_polylines"]), _lib.POLYLINE_DTYPE)
+        res = self._polylines(config, vertex_of.ctypes.data, vt.ctypes.data, len(vt), pt.ctypes.data, len(pt), 0)
+        return Polylines(res, vertex_of, vt[:res["n_vertices"]], pt[:res["n_polylines"]])
+
+    def polylines_device(self, config=None, vertex_of=None, vertices=None, polylines=None):
+        """`polylines` with the outputs in device memory, as torch tensors that the library writes in place (no copy): vertex_of
+        (capacity,) int32, vertices (max_vertices, 64) uint8, one lf_polyline_vertex (`_lib.POLYLINE_VERTEX_DTYPE`) per row,
+        polylines (max_polylines, 32) uint8, one lf_polyline (`_lib.POLYLINE_DTYPE`) per row.  None: a new tensor on the map's
+        device (a table: sized from a first call's result); False: not wanted (NULL).  Returns the named tuple (result, vertex_of,
+        vertices, polylines) of the same tensors, the tables cut to their records (views).  Raises LanefrontError (code -2) when a
+        table has fewer rows than the map has records: vertex_of is filled in then, both tables are untouched."""
+        import torch
+        config = self.polylines_config() if config is None else config
+        dev = torch.device("cuda", self._device)
+        if vertex_of is None:
+            vertex_of = torch.empty(self.capacity, dtype=torch.int32, device=dev)
+        elif vertex_of is False:
+            vertex_of = None
+        elif vertex_of.dtype != torch.int32 or vertex_of.numel() < self.capacity or not vertex_of.is_contiguous() or not vertex_of.is_cuda:
+            raise ValueError("polylines_device: vertex_of is a contiguous int32 device tensor of capacity values")
+        ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+        if vertices is None or polylines is None:
+            first = self._polylines(config, None, None, 0, None, 0, 1)
+            if vertices is None:
+                vertices = torch.empty((max(1, first["n_vertices"]), POLYLINE_VERTEX_BYTES), dtype=torch.uint8, device=dev)
+            if polylines is None:
+                polylines = torch.empty((max(1, first["n_polylines"]), POLYLINE_BYTES), dtype=torch.uint8, device=dev)
+        tables = []
+        for name, t, width in (("vertices", vertices, POLYLINE_VERTEX_BYTES), ("polylines", polylines, POLYLINE_BYTES)):
+            if t is False:
+                t = None
+            elif t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] != width or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("polylines_device: %s is a contiguous (n, %d) uint8 device tensor" % (name, width))
+            tables.append(t)
+        vertices, polylines = tables
+        res = self._polylines(config, ptr(vertex_of), ptr(vertices), 0 if vertices is None else vertices.shape[0], ptr(polylines),
+                              0 if polylines is None else polylines.shape[0], 1)
+        return Polylines(res, vertex_of, None if vertices is None else vertices[:res["n_vertices"]],
+                         None if polylines is None else polylines[:res["n_polylines"]])
+
+    @staticmethod
+    def polyline_xy(result, k):
+        """polyline k of a `polylines` result as an (n, 2) float64 array of x, y, in the polyline's order (closed: the first vertex
+        is not repeated)"""
+        p = result.polylines[k]
+        v = result.vertices[int(p["first_vertex"]):int(p["first_vertex"]) + int(p["n_vertices"])]
+        return np.stack([v["x"], v["y"]], axis=1)
+
+    def polylines_timing(self):
+        """{'lanes': (ms, launches), 'vertices': (ms, launches), 'links': (ms, launches)} of the `polylines` calls since the
+        previous call (needs set_profiling(True)): the lanes stage (index, link, label), the vertices, and links + order + outputs;
+        one launch is one call's kernels of that stage."""
+        ms, ln = (ctypes.c_double * 3)(), (ctypes.c_int32 * 3)()
+        self._check(self.lib.lf_map_polylines_timing(self.m, ms, ln))
+        return {"lanes": (ms[0], ln[0]), "vertices": (ms[1], ln[1]), "links": (ms[2], ln[2])}
 
     @staticmethod
     def carry(poses, last_odometry, last_corrected):

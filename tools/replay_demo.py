@@ -7,6 +7,7 @@ wire bodies.  The first batch is checked against the oracle (pixels, segments, m
     python tools/replay_demo.py [--frames 1024] [--batch 128] [--threads 32] [--geometry fullres|parity] [--map-jpeg map.jpg]
                                 [--overlay-jpeg DIR] [--align | --smooth | --localize] [--prune EVERY[:min_hits[:age]]]
                                 [--near RADIUS[:max_offset[:max_sin]]] [--lanes RADIUS[:max_offset[:max_sin[:min_entries]]]]
+                                [--polylines CELL[:max_gap[:reach]]]
 
 --map-jpeg writes the final map as the reference's README shows it (show_map's coloured segments seen from above, lf_map_render
 fitted to the map) as a JPEG: rendered and encoded on the device, only the file's bytes cross the bus.
@@ -22,6 +23,9 @@ prints the matched share of segments and the mean number of candidates per segme
 whose status is `ok`, and the endpoints they used, with the gate and, from a second map fed the same stream, without it.
 --lanes RADIUS[:max_offset[:max_sin[:min_entries]]] groups the final map into lane lines (lf_map_lanes; the fields left out default
 to the library's) and prints one line per lane -- number, colour, entries, hits, box -- and the count of entries in no lane.
+--polylines CELL[:max_gap[:reach]] orders each lane line of the final map into polylines (lf_map_polylines; the lane rule is
+--lanes' fields, or the library's; the fields left out default to the library's) and prints one line per polyline -- number, lane,
+vertices, closed or open, entries, hits, both ends, length.
 """
 import argparse, io, os, sys, time
 import numpy as np
@@ -63,7 +67,18 @@ ap.add_argument("--near", default=None, metavar="RADIUS[:max_offset[:max_sin]]",
                      "and under --align the share of ok frames with and without the gate")
 ap.add_argument("--lanes", default=None, metavar="RADIUS[:max_offset[:max_sin[:min_entries]]]",
                 help="after the replay, group the map into lane lines (lf_map_lanes) and print one line per lane and the entries in no lane")
+ap.add_argument("--polylines", default=None, metavar="CELL[:max_gap[:reach]]",
+                help="after the replay, order each lane line of the map into polylines (lf_map_polylines, the lane rule from --lanes' fields) "
+                     "and print one line per polyline")
 args = ap.parse_args()
+polylines_fields = None
+if args.polylines:
+    parts = args.polylines.split(":")
+    if not 1 <= len(parts) <= 3:
+        ap.error("--polylines takes CELL[:max_gap[:reach]]")
+    polylines_fields = dict(zip(("cell", "max_gap"), (float(v) for v in parts[:2])))
+    if len(parts) == 3:
+        polylines_fields["reach"] = int(parts[2])
 lanes_fields = None
 if args.lanes:
     parts = args.lanes.split(":")
@@ -267,3 +282,16 @@ if args.overlay_jpeg:
         n_files += B
     print("overlay: %d frames %d x %d -> %s (%d bytes); per frame %.1f segments drawn, %.1f behind the camera, %.1f skipped"
           % (n_files, cam_h, cam_w, args.overlay_jpeg, n_bytes, drawn[0] / max(n_files, 1), drawn[2] / max(n_files, 1), drawn[1] / max(n_files, 1)))
+
+if polylines_fields:
+    pc = live.polylines_config(**dict(lanes_fields or {}, **polylines_fields))
+    got = live.polylines(pc)
+    r = got.result
+    print("polylines (cell %g m, max_gap %g m, reach %d): %d lanes, %d of %d entries participate, %d vertices, %d edges, %d polylines (%d closed)"
+          % (pc.cell, pc.max_gap, pc.reach, r["n_lanes"], r["n_participating"], r["size"], r["n_vertices"], r["n_edges"], r["n_polylines"], r["n_closed"]))
+    for k, p in enumerate(got.polylines):
+        xy = live.polyline_xy(got, k)
+        ring = np.vstack([xy, xy[:1]]) if p["closed"] else xy
+        print("polyline %d: lane %d, %d vertices, %s, %d entries, %d hits, from (%.3f, %.3f) to (%.3f, %.3f) m, %.3f m long"
+              % (k, p["lane"], p["n_vertices"], "closed" if p["closed"] else "open", p["n_entries"], p["hits"], xy[0, 0], xy[0, 1], xy[-1, 0], xy[-1, 1],
+                 float(np.hypot(*np.diff(ring, axis=0).T).sum())))
