@@ -1573,6 +1573,13 @@ LF_API int lf_debug_probe(lf_handle* h, int width, int write, size_t bytes, int 
 /* LSD stages alone on a binary image of the handle's working size (non-zero = edge pixel, colour
  * mask forced to all ones); host pointers; lines before normal-based endpoint ordering */
 LF_API int lf_debug_lsd_binary(lf_handle* h, const uint8_t* img, int rows, int cols, float* lines4, int cap, int* n_out);
+/* Canny's hysteresis alone on the caller's planes; host pointers.  planes_u8 [n_frames][rows][cols]: 0 = none, 1 = weak (above
+ * the low threshold and a local maximum), 2 = strong (above the high one as well; a strong pixel counts as weak too).  rows and
+ * cols are the call's own, any size >= 1 -- not the handle's working image -- and select the kernel as a handle of that
+ * geometry would; every frame of the call is one workgroup.  edges_u8_out [n_frames][rows][cols]: 255 where a weak pixel is
+ * 8-connected to a strong one through weak pixels, 0 elsewhere.  LF_ERR_BAD_ARG for a null pointer, a size below 1 or a value
+ * above 2; LF_ERR_UNSUPPORTED for a row too wide for the strip budget, as lf_create */
+LF_API int lf_debug_hysteresis(lf_handle* h, const uint8_t* planes_u8, int n_frames, int rows, int cols, uint8_t* edges_u8_out);
 /* the per-segment stage alone (normal and endpoint order, normalisation, ground projection, line sanity, compaction) on the
  * caller's lines in place of a detector's; host pointers.  mode 0: float lines, the arithmetic behind LF_DETECTOR_LSD and
  * LF_DETECTOR_EDLINES; mode 1: HoughLinesP's int lines held as floats, the arithmetic behind LF_DETECTOR_HOUGH.

@@ -138,6 +138,56 @@ extern "C" int lf_debug_segments(lf_handle* h, int mode, int n_frames, const int
                       { out->keep, dev.keep, n } });
 }
 
+// Hysteresis alone (k_canny.hip: launch_hysteresis and whichever of its kernels the shape selects) on caller-supplied planes,
+// 0 = none, 1 = weak, 2 = strong.  The geometry is the call's, not the handle's: the bit planes are packed here (a strong pixel
+// is weak as well, so strong is a subset of weak whatever the caller wrote), live in buffers of the call's own and go through
+// launch_edges_u8 on the way back.  Test entry.
+extern "C" int lf_debug_hysteresis(lf_handle* h, const uint8_t* planes, int n_frames, int rows, int cols, uint8_t* edges)
+{
+    if (!h) return LF_ERR_NOT_INITIALISED;
+    if (!planes || !edges || n_frames < 1 || rows < 1 || cols < 1 || (size_t)n_frames * (size_t)rows * (size_t)cols > ((size_t)1 << 28)) {
+        lf_set_error(h, LF_ERR_BAD_ARG, "lf_debug_hysteresis: bad argument (planes and edges not null, n_frames, rows, cols >= 1, at most 2^28 pixels)");
+        return LF_ERR_BAD_ARG;
+    }
+    CannyParams p;
+    p.Hc = rows; p.W = cols; p.Ww = (cols + 31) / 32; p.low = 0; p.high = 0;
+    // the same limit lf_create checks (build_params): a strip is at least one row and its two halo rows
+    if ((size_t)p.Hc * p.Ww > 8 * 1024 && (8192 / p.Ww < 1 || (int)((60 * 1024 / 4) / (2 * (size_t)p.Ww)) - 1 < 1)) {
+        lf_set_error(h, LF_ERR_UNSUPPORTED, "img_cols %d: one row of the edge bit planes exceeds the hysteresis strip budget", cols);
+        return LF_ERR_UNSUPPORTED;
+    }
+    const size_t nw = (size_t)n_frames * rows * p.Ww, npx = (size_t)n_frames * rows * cols;
+    std::vector<uint32_t> weak(nw, 0u), strong(nw, 0u);
+    for (size_t fy = 0; fy < (size_t)n_frames * rows; ++fy)
+        for (int x = 0; x < cols; ++x) {
+            const uint8_t v = planes[fy * cols + x];
+            if (v > 2) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_debug_hysteresis: plane values are 0 (none), 1 (weak) or 2 (strong), got %d", (int)v); return LF_ERR_BAD_ARG; }
+            if (v) weak[fy * p.Ww + (x >> 5)] |= 1u << (x & 31);
+            if (v == 2) strong[fy * p.Ww + (x >> 5)] |= 1u << (x & 31);
+        }
+    LF_HIP_CHECK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DevArray<uint32_t> d_weak, d_strong;
+    DevArray<uint8_t> d_edges;
+    LF_HIP_CHECK(h, d_weak.alloc(nw * 4));
+    LF_HIP_CHECK(h, d_strong.alloc(nw * 4));
+    LF_HIP_CHECK(h, d_edges.alloc(npx));
+    LF_HIP_CHECK(h, hipMemcpyAsync(d_weak, weak.data(), nw * 4, hipMemcpyHostToDevice, s));
+    LF_HIP_CHECK(h, hipMemcpyAsync(d_strong, strong.data(), nw * 4, hipMemcpyHostToDevice, s));
+    int rc = LF_OK;
+    if (launch_hysteresis(p, n_frames, d_strong, d_weak, s) != 0) {
+        lf_set_error(h, LF_ERR_UNSUPPORTED, "img_cols %d: one row of the edge bit planes exceeds the hysteresis strip budget", cols);
+        rc = LF_ERR_UNSUPPORTED;
+    } else {
+        launch_edges_u8(p, n_frames, d_strong, d_edges, s);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { lf_set_error(h, LF_ERR_HIP, "lf_debug_hysteresis: %s", hipGetErrorString(e)); rc = LF_ERR_HIP; }
+        else rc = fetch(h, { { edges, d_edges.p, npx } });
+    }
+    (void)hipStreamSynchronize(s);      // the host vectors and the call's buffers go with the call
+    return rc;
+}
+
 extern "C" int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t bytes)
 {
     if (!h) return LF_ERR_NOT_INITIALISED;

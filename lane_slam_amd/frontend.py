@@ -786,6 +786,18 @@ class FrontEnd(object):
         self._check(self.lib.lf_debug_lsd_binary(self.h, _ptr(img), img.shape[0], img.shape[1], _ptr(lines), cap, ctypes.byref(n)))
         return lines[:n.value].copy()
 
+    def debug_hysteresis(self, planes):
+        """Canny's hysteresis alone (lf_debug_hysteresis; tests / diagnosis).  planes: uint8 (n, rows, cols) or (rows, cols) with
+        0 = none, 1 = weak, 2 = strong, of any size: the kernel is chosen for these rows and cols, not for the handle's working
+        image.  Returns the edges, uint8 0 / 255 of the same shape."""
+        planes = np.ascontiguousarray(planes, dtype=np.uint8)
+        p3 = planes[None] if planes.ndim == 2 else planes
+        if p3.ndim != 3:
+            raise ValueError("planes must be (n, rows, cols) or (rows, cols), got %r" % (planes.shape,))
+        edges = np.empty(p3.shape, np.uint8)
+        self._check(self.lib.lf_debug_hysteresis(self.h, _ptr(p3), p3.shape[0], p3.shape[1], p3.shape[2], _ptr(edges)))
+        return edges.reshape(planes.shape)
+
     def debug_segments(self, counts, lines, masks=None, mode="float", out=None, capacity=None):
         """The per-segment stage alone on the caller's lines (lf_debug_segments; tests / diagnosis).  counts: int32 (n, 3);
         lines: float32 (n, 3, max_lines_per_color, 4) in working-image pixels; masks: uint8 (n, 3, rows, cols) or None (the
