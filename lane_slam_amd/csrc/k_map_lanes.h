@@ -3,8 +3,9 @@
 // nr::cell_size(radius), its records and its conservativeness argument -- a link requires d2 <= r2 between midpoints, which is
 // exactly the gate that argument covers.
 #pragma once
+#include <stddef.h>
+#include <initializer_list>
 #include "k_map_near.h"
-#include "k_map_pairs.h"
 
 namespace lf {
 namespace ln {
@@ -29,8 +30,8 @@ LF_NR_HD int colour_bit(int colour) { return 1 << (colour < 3 ? colour : 3); }
 const char* bad_config(const lf_lanes_config* c);
 Rule make_rule(const lf_lanes_config* c);
 
-#if defined(__HIPCC__)
-// Device arrays of one call, [bound] each (box [bound][4]); everything belongs to the map's handle.
+// Device arrays of one call, [bound] each (box [bound][4]); everything belongs to the map's handle.  The struct and its carving
+// are plain C++: they compile for the host as k_map_near.h's cell function does.
 //
 // The union-find.  parent[t] <= t always: parent[t] == t is a root, and every other value is a smaller row of the same component.
 // Two statements change it, both atomic read-modify-writes at device scope:
@@ -58,14 +59,28 @@ struct Work {
     int bound;                             // the host's size of the map: sizes the grids and the arrays
 };
 
-// ---- what k_map_polylines.hip shares with k_map_lanes.hip
-// the rows the kernels may touch: the map's size as the device knows it, never beyond what the host sized the arrays for
-__device__ __forceinline__ int rows(const MapDevice& md, int bound)
+// Arrays handed out one behind the other from one allocation (ln::carve, pl::carve and nothing else); base null: only their size
+struct Carver {
+    char* base; size_t used;
+    template <class T> void take(T*& p, size_t n)
+    {
+        p = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used += n * sizeof(T);
+    }
+};
+
+// w's arrays for `bound` rows out of `base` (null: none, only the size); returns the bytes they take, which is what the host
+// sizes the allocation with.  The 8-byte arrays come first, so every pointer is naturally aligned behind an 8-byte aligned base
+inline size_t carve(Work* w, void* base, size_t bound)
 {
-    const int size = ma::map_size(md);
-    return size < bound ? size : bound;
+    Carver c = { static_cast<char*>(base), 0 };
+    c.take(w->box, 4 * bound); c.take(w->hsum, bound);
+    for (int** a : { &w->parent, &w->root, &w->elig, &w->nl, &w->cnt, &w->lane_no }) c.take(*a, bound);
+    return c.used;
 }
 
+#if defined(__HIPCC__)
+// ---- what k_map_polylines.hip shares with k_map_lanes.hip (and nr::rows)
 __device__ __forceinline__ int peek(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // the root of x while the forest changes; halves the path behind it (k_map_lanes.h: at most x turns)
@@ -95,9 +110,6 @@ __device__ __forceinline__ void unite(int* parent, int a, int b)
 
 // the caller's arrays, device addresses; each may be null
 struct Out { int32_t* lane_of; int32_t* n_links; int32_t* support; lf_lane* lanes; int max_lanes; };
-
-// bytes of the Work arrays per row, and their carving from one allocation of bound rows
-constexpr size_t kWorkBytesPerRow = 4 * 8 + 8 + 6 * 4;
 
 // everything behind the index: eligibility and the forest's start, links and unions, roots and their sums, the lanes' numbers,
 // the outputs.  bound == 0 (an empty map): only the outputs' kernel, which reads none of w's arrays but the counters

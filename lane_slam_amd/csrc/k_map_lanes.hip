@@ -5,12 +5,9 @@
 //   k_lanes_init    one thread per row: eligibility, and the start of everything the later kernels add to -- every row its own root,
 //                   no members, no hits, an empty box, no lane
 //   k_lanes_link    kGroup lanes per row, 64 / kGroup rows per wave.  The group takes the row as the near contract's segment and
-//                   walks the 3 x 3 cells around its midpoint as k_near_query does: a bucket is visited FOR a cell and only the
-//                   records OF THAT CELL are looked at (a bucket holds other cells' rows and two of the nine cells may share a
-//                   bucket: otherwise an entry is counted twice), and a neighbour beyond the int32 clamp is skipped (no midpoint has
-//                   such a cell; wrapped round it would name the cell at the other end of the range).  Hits, the colour byte and
-//                   the geometry both ways decide a link; every linked j counts for n_links, and a linked j < i is united with i in
-//                   the forest of k_map_lanes.h (each link is met from both ends: the higher end unites)
+//                   walks the index around its midpoint as k_near_query does (k_map_near.h for_each_near_record).  Hits, the
+//                   colour byte and the geometry both ways decide a link; every linked j counts for n_links, and a linked j < i is
+//                   united with i in the forest of k_map_lanes.h (each link is met from both ends: the higher end unites)
 //   k_lanes_reduce  one thread per row: its root (the forest stands still by now), then integer atomics at the root's slot -- the
 //                   members, the hits (64 bits), the box as atomicMin / atomicMax over order-preserving keys of the finite
 //                   endpoints.  The workgroup's eligible rows, roots and links are summed first: one atomic per wave and counter
@@ -18,7 +15,6 @@
 //                   in row order, one row per lane and turn
 //   k_lanes_write   one thread per row of the CAPACITY: lane_of and support through the root, n_links; -1, 0, 0 past the size; the
 //                   thread of a lane's root writes lanes[k], unless the table does not hold them all
-#include "k_map_pairs.h"
 #include "k_map_lanes.h"
 #include "scan.h"
 #include "wave.h"
@@ -40,16 +36,6 @@ __device__ __forceinline__ double value_of(unsigned long long k)
     return __longlong_as_double((long long)u);
 }
 
-// an entry in the role of the near contract's segment
-__device__ __forceinline__ nr::Seg as_segment(double ax, double ay, double bx, double by)
-{
-    nr::Seg s;
-    s.sx = bx - ax; s.sy = by - ay;
-    s.S2 = s.sx * s.sx + s.sy * s.sy;
-    s.qmx = (ax + bx) * 0.5; s.qmy = (ay + by) * 0.5;
-    return s;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(kWg) void k_lanes_init(Rule c, MapDevice md, Work w)
@@ -57,7 +43,7 @@ __global__ __launch_bounds__(kWg) void k_lanes_init(Rule c, MapDevice md, Work w
     const int t = blockIdx.x * kWg + threadIdx.x;
     if (t >= w.bound) return;
     int e = 0;
-    if (t < rows(md, w.bound)) {
+    if (t < nr::rows(md, w.bound)) {
         const double2 a = *reinterpret_cast<const double2*>(md.ground + (size_t)t * 4);
         const double2 b = *reinterpret_cast<const double2*>(md.ground + (size_t)t * 4 + 2);
         e = nr::entry_valid(a.x, a.y, b.x, b.y) && md.hits[t] >= c.geo.min_hits && (c.color_mask & colour_bit(md.color[t])) != 0;
@@ -74,7 +60,7 @@ __global__ __launch_bounds__(kWg) void k_lanes_link(Rule c, MapDevice md, nr::In
 {
     const int g = threadIdx.x & (kGroup - 1);
     const int i = (blockIdx.x * kWg + threadIdx.x) / kGroup;
-    const int n = rows(md, w.bound);
+    const int n = nr::rows(md, w.bound);
     const bool ok = i < n && w.elig[i] != 0;
 
     // the row as the segment (the loads are one address per group: broadcasts)
@@ -85,36 +71,22 @@ __global__ __launch_bounds__(kWg) void k_lanes_link(Rule c, MapDevice md, nr::In
         const double2 a = *reinterpret_cast<const double2*>(md.ground + (size_t)i * 4);
         const double2 b = *reinterpret_cast<const double2*>(md.ground + (size_t)i * 4 + 2);
         ax = a.x; ay = a.y; bx = b.x; by = b.y;
-        s = as_segment(ax, ay, bx, by);
+        s = nr::as_segment(ax, ay, bx, by);
         colour = md.color[i];
     }
 
     int count = 0;
     if (ok) {
-        const int32_t cx = nr::cell_of(s.qmx, c.geo.cell), cy = nr::cell_of(s.qmy, c.geo.cell);
-        for (int dy = -1; dy <= 1; ++dy) {
-            const long long wy = (long long)cy + dy;
-            if (wy < INT32_MIN || wy > INT32_MAX) continue;          // no midpoint has a cell beyond the clamp
-            for (int dx = -1; dx <= 1; ++dx) {
-                const long long wx = (long long)cx + dx;
-                if (wx < INT32_MIN || wx > INT32_MAX) continue;
-                const uint32_t b = nr::bucket_of((int32_t)wx, (int32_t)wy, ix.mask);
-                const int end = ix.start[b + 1];
-                for (int j = ix.start[b] + g; j < end; j += kGroup) {
-                    const nr::Rec* rp = ix.rec + j;
-                    const int4 v = *reinterpret_cast<const int4*>(&rp->row);           // row, hits, colour, cx
-                    if (v.w != (int32_t)wx || rp->cy != (int32_t)wy) continue;          // another cell's row in this bucket
-                    if (v.x == i || v.y < c.geo.min_hits || v.z != colour) continue;    // (an equal colour byte has i's bit of the mask)
-                    const double2 ea = *reinterpret_cast<const double2*>(&rp->ax);
-                    const double2 eb = *reinterpret_cast<const double2*>(&rp->bx);
-                    double d2;
-                    if (!nr::near_geometry(c.geo, s, ea.x, ea.y, eb.x, eb.y, d2)) continue;
-                    if (!nr::near_geometry(c.geo, as_segment(ea.x, ea.y, eb.x, eb.y), ax, ay, bx, by, d2)) continue;
-                    count += 1;
-                    if (v.x < i) unite(w.parent, i, v.x);
-                }
-            }
-        }
+        nr::for_each_near_record<kGroup>(ix, nr::cell_of(s.qmx, c.geo.cell), nr::cell_of(s.qmy, c.geo.cell), g, [&](const nr::Rec* rp, int row, int hits, int theirs) {
+            if (row == i || hits < c.geo.min_hits || theirs != colour) return;          // (an equal colour byte has i's bit of the mask)
+            const double2 ea = *reinterpret_cast<const double2*>(&rp->ax);
+            const double2 eb = *reinterpret_cast<const double2*>(&rp->bx);
+            double d2;
+            if (!nr::near_geometry(c.geo, s, ea.x, ea.y, eb.x, eb.y, d2)) return;
+            if (!nr::near_geometry(c.geo, nr::as_segment(ea.x, ea.y, eb.x, eb.y), ax, ay, bx, by, d2)) return;
+            count += 1;
+            if (row < i) unite(w.parent, i, row);
+        });
     }
     count = wave_reduce<kGroup>(count, op_add());
     if (i < n && g == 0) w.nl[i] = count;
@@ -123,7 +95,7 @@ __global__ __launch_bounds__(kWg) void k_lanes_link(Rule c, MapDevice md, nr::In
 __global__ __launch_bounds__(kWg) void k_lanes_reduce(MapDevice md, Work w)
 {
     const int t = blockIdx.x * kWg + threadIdx.x;
-    const bool e = t < rows(md, w.bound) && w.elig[t] != 0;
+    const bool e = t < nr::rows(md, w.bound) && w.elig[t] != 0;
     int n_elig = 0, n_root = 0;
     long long n_links = 0;
     if (e) {
@@ -154,7 +126,7 @@ __global__ __launch_bounds__(kWg) void k_lanes_reduce(MapDevice md, Work w)
 __global__ __launch_bounds__(kScanWg) void k_lanes_number(Rule c, MapDevice md, Work w)
 {
     __shared__ int wave_sum[kScanWg / 64];
-    const int n = rows(md, w.bound);
+    const int n = nr::rows(md, w.bound);
     auto is_lane = [&](int t) { return (w.elig[t] != 0 && w.root[t] == t && w.cnt[t] >= c.min_entries) ? 1 : 0; };
     const int total = wg_scan_turns<kScanWg>(n, wave_sum, is_lane, [&](int t, int before) { if (is_lane(t)) w.lane_no[t] = before; });
     if (threadIdx.x == 0) w.counters[kNLanes] = total;
@@ -165,7 +137,7 @@ __global__ __launch_bounds__(kWg) void k_lanes_write(MapDevice md, Work w, Out o
     const int t = blockIdx.x * kWg + threadIdx.x;
     if (t >= md.capacity) return;
     int lane = -1, support = 0, links = 0;
-    if (t < rows(md, w.bound) && w.elig[t] != 0) {
+    if (t < nr::rows(md, w.bound) && w.elig[t] != 0) {
         const int r = w.root[t];
         support = w.cnt[r]; lane = w.lane_no[r]; links = w.nl[t];
         if (r == t && lane >= 0 && o.lanes && w.counters[kNLanes] <= o.max_lanes) {

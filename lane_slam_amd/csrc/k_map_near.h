@@ -1,11 +1,11 @@
 // Association gated by the prior pose (k_map_near.hip, lanefront_map_near.hip): include/lanefront.h "lf_map_associate_near" is the
 // contract, tests/map_near_ref.py its sequential restatement (a brute force over all rows).  Shared by the kernels and the host
-// side; the cell function, the hash and the candidate test also compile for the host (plain C++: define nothing, include
-// <stdint.h> and include/lanefront.h first).
+// side; the cell function, the hash, the candidate test and the configurations' shared geometry also compile for the host
+// (plain C++: define nothing, include <stdint.h> and include/lanefront.h first).
 #pragma once
 #include <stdint.h>
 #if defined(__HIPCC__)
-#include "common.h"
+#include "k_map_pairs.h"
 #define LF_NR_HD __host__ __device__ inline
 #else
 #define LF_NR_HD inline
@@ -76,8 +76,39 @@ struct Rule {
     int min_hits, gating, max_distance;    // the configuration's, the map's and the map's
 };
 
+// the reason a configuration's shared geometry is refused with, or null (lf_near_config's and lf_lanes_config's fields alike)
+inline const char* bad_geometry(double radius, double max_offset, double max_sin, int min_hits)
+{
+    if (!finite_d(radius) || !(radius > 0)) return "radius is finite and > 0";
+    if (!(max_offset > 0)) return "max_offset is > 0 or +inf";
+    if (!(max_sin >= 0 && max_sin <= 1)) return "max_sin is 0 .. 1";
+    if (min_hits < 0) return "min_hits is >= 0";
+    return nullptr;
+}
+
+// the rule of a geometry that passed; gating and max_distance are 0: the map's, for the caller that reads them
+inline Rule make_geometry(double radius, double max_offset, double max_sin, int min_hits)
+{
+    Rule c = {};
+    c.r2 = radius * radius; c.ms2 = max_sin * max_sin; c.mo2 = max_offset * max_offset;
+    c.cell = cell_size(radius);
+    c.test_sin = max_sin < 1; c.test_offset = finite_d(max_offset) ? 1 : 0;
+    c.min_hits = min_hits;
+    return c;
+}
+
 // a segment in the map frame: the contract's "segment"
 struct Seg { double sx, sy, S2, qmx, qmy; };
+
+// the segment from a to b
+LF_NR_HD Seg as_segment(double ax, double ay, double bx, double by)
+{
+    Seg s;
+    s.sx = bx - ax; s.sy = by - ay;
+    s.S2 = s.sx * s.sx + s.sy * s.sy;
+    s.qmx = (ax + bx) * 0.5; s.qmy = (ay + by) * 0.5;
+    return s;
+}
 
 // the contract's "candidate" but for hits and colour; d2 comes back for the winner's order
 LF_NR_HD bool near_geometry(const Rule& c, const Seg& s, double ax, double ay, double bx, double by, double& d2)
@@ -126,6 +157,43 @@ struct Query {
     int n, n_frames;
     int32_t* idx; float* dist; int32_t* n_near;      // n_near may be null
 };
+
+// the rows the kernels may touch: the map's size as the device knows it, never beyond what the host sized the arrays for
+__device__ __forceinline__ int rows(const MapDevice& md, int bound)
+{
+    const int size = ma::map_size(md);
+    return size < bound ? size : bound;
+}
+
+// The walk of the index, by a group of kLanes lanes of which this one is lane g: the 3 x 3 cells around (cx, cy), for each cell
+// its bucket's records, the lanes striding over them, and f(rp, row, hits, colour) for every record OF THAT CELL.
+// The index has two traps, and both are avoided here and nowhere else.  Double counting: a bucket holds other cells' rows, and
+// two of the nine cells may share a bucket, so a bucket is visited FOR a cell and only that cell's records are looked at -- every
+// entry is met exactly once.  The clamp: a neighbour beyond the int32 range is skipped (no midpoint has such a cell; wrapped
+// round it would name the cell at the other end of the range), which takes the sum in 64 bits.
+// row, hits, colour and cx are one 16-byte load, typed as the compiler's own vector so that it stays one once f is inlined (as an
+// int4 it is taken apart into a load of cx and, behind the cell test, a second one of the rest: one more round trip per record).
+template <int kLanes, class F>
+__device__ __forceinline__ void for_each_near_record(const Index& ix, int32_t cx, int32_t cy, int g, F&& f)
+{
+    for (int dy = -1; dy <= 1; ++dy) {
+        const long long wy = (long long)cy + dy;
+        if (wy < INT32_MIN || wy > INT32_MAX) continue;
+        for (int dx = -1; dx <= 1; ++dx) {
+            const long long wx = (long long)cx + dx;
+            if (wx < INT32_MIN || wx > INT32_MAX) continue;
+            const uint32_t b = bucket_of((int32_t)wx, (int32_t)wy, ix.mask);
+            const int end = ix.start[b + 1];
+            for (int j = ix.start[b] + g; j < end; j += kLanes) {
+                const Rec* rp = ix.rec + j;
+                typedef int v4i __attribute__((ext_vector_type(4)));
+                const v4i v = *reinterpret_cast<const v4i*>(&rp->row);
+                if (v.w != (int32_t)wx || rp->cy != (int32_t)wy) continue;          // another cell's row in this bucket
+                f(rp, v.x, v.y, v.z);
+            }
+        }
+    }
+}
 
 // the buckets' counts (start[] is zero before), their scan, the records
 void launch_near_index(const MapDevice& md, double cell, const Index& ix, hipStream_t s);

@@ -7,13 +7,11 @@
 //   k_near_fill    one thread per row: a slot from its bucket's cursor, then the 64-byte record (endpoints, row, hits, colour, cell).
 //                  The order inside a bucket is arrival order; no result depends on it
 //   k_near_query   kGroup lanes per segment, 64 / kGroup segments per wave.  Every lane of a group makes the segment in the map frame
-//                  (the loads are one address per group: broadcasts), then the group walks the 3 x 3 cells around the midpoint: for
-//                  each cell its bucket's records, the lanes striding over them, and only the records OF THAT CELL are looked at
-//                  (a bucket holds other cells' rows, and two of the nine cells may share a bucket: this way every entry is met
-//                  exactly once).  The 32-byte code of an entry is fetched from the map only for a record that passed the geometry,
-//                  hits and colour.  The group's counts are summed and its (h, d2, row) keys reduced with cross-lane moves; one lane
-//                  writes each output with a plain vector store.
-#include "k_map_pairs.h"
+//                  (the loads are one address per group: broadcasts), then the group walks the index around the midpoint
+//                  (k_map_near.h for_each_near_record, which meets every entry of the 3 x 3 cells exactly once).  The 32-byte code
+//                  of an entry is fetched from the map only for a record that passed the geometry, hits and colour.  The group's
+//                  counts are summed and its (h, d2, row) keys reduced with cross-lane moves; one lane writes each output with a
+//                  plain vector store.
 #include "k_map_near.h"
 #include "scan.h"
 #include "wave.h"
@@ -21,21 +19,10 @@
 namespace lf {
 namespace nr {
 
-namespace {
-
-// the rows the kernels may touch: the map's size as the device knows it, never beyond what the host sized the arrays for
-__device__ __forceinline__ int rows(const MapDevice& md, const Index& ix)
-{
-    const int size = ma::map_size(md);
-    return size < ix.bound ? size : ix.bound;
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(kWg) void k_near_bin(MapDevice md, double cell, Index ix)
 {
     const int t = blockIdx.x * kWg + threadIdx.x;
-    if (t >= rows(md, ix)) return;
+    if (t >= rows(md, ix.bound)) return;
     const double2 a = *reinterpret_cast<const double2*>(md.ground + (size_t)t * 4);
     const double2 b = *reinterpret_cast<const double2*>(md.ground + (size_t)t * 4 + 2);
     int bucket = -1;
@@ -68,7 +55,7 @@ __global__ __launch_bounds__(kScanWg) void k_near_scan(Index ix)
 __global__ __launch_bounds__(kWg) void k_near_fill(MapDevice md, double cell, Index ix)
 {
     const int t = blockIdx.x * kWg + threadIdx.x;
-    if (t >= rows(md, ix)) return;
+    if (t >= rows(md, ix.bound)) return;
     const int bucket = ix.bucket[t];
     if (bucket < 0) return;
     const double2 a = *reinterpret_cast<const double2*>(md.ground + (size_t)t * 4);
@@ -113,9 +100,7 @@ __global__ __launch_bounds__(kWg) void k_near_query(Rule c, MapDevice md, Index 
         const double px0 = gr[0], py0 = gr[1], px1 = gr[2], py1 = gr[3];
         const double qx0 = x + (cs * px0 - sn * py0), qy0 = y + (sn * px0 + cs * py0);
         const double qx1 = x + (cs * px1 - sn * py1), qy1 = y + (sn * px1 + cs * py1);
-        s.sx = qx1 - qx0; s.sy = qy1 - qy0;
-        s.S2 = s.sx * s.sx + s.sy * s.sy;
-        s.qmx = (qx0 + qx1) * 0.5; s.qmy = (qy0 + qy1) * 0.5;
+        s = as_segment(qx0, qy0, qx1, qy1);
         // (a midpoint that overflows is infinitely far from every entry: no candidates either way)
         ok = ma::finite(qx0) && ma::finite(qy0) && ma::finite(qx1) && ma::finite(qy1) && ma::finite(s.S2) && s.S2 > 0.0 &&
              ma::finite(s.qmx) && ma::finite(s.qmy);
@@ -130,35 +115,21 @@ __global__ __launch_bounds__(kWg) void k_near_query(Rule c, MapDevice md, Index 
     int count = 0, best_h = INT32_MAX, best_t = INT32_MAX;
     double best_d2 = 0.0;
     if (ok) {
-        const int32_t cx = cell_of(s.qmx, c.cell), cy = cell_of(s.qmy, c.cell);
-        for (int dy = -1; dy <= 1; ++dy) {
-            const long long wy = (long long)cy + dy;
-            if (wy < INT32_MIN || wy > INT32_MAX) continue;          // no midpoint has a cell beyond the clamp
-            for (int dx = -1; dx <= 1; ++dx) {
-                const long long wx = (long long)cx + dx;
-                if (wx < INT32_MIN || wx > INT32_MAX) continue;
-                const uint32_t b = bucket_of((int32_t)wx, (int32_t)wy, ix.mask);
-                const int end = ix.start[b + 1];
-                for (int j = ix.start[b] + g; j < end; j += kGroup) {
-                    const Rec* rp = ix.rec + j;
-                    const int4 w = *reinterpret_cast<const int4*>(&rp->row);           // row, hits, colour, cx
-                    if (w.w != (int32_t)wx || rp->cy != (int32_t)wy) continue;          // another cell's row in this bucket
-                    const double2 a = *reinterpret_cast<const double2*>(&rp->ax);
-                    const double2 e = *reinterpret_cast<const double2*>(&rp->bx);
-                    double d2;
-                    if (!near_geometry(c, s, a.x, a.y, e.x, e.y, d2)) continue;
-                    if (w.y < c.min_hits) continue;
-                    if (c.gating && !colours_agree(colour, w.z)) continue;
-                    count += 1;
-                    const uint4* mp = reinterpret_cast<const uint4*>(md.code + (size_t)w.x * 32);
-                    const uint4 m0 = mp[0], m1 = mp[1];
-                    const int h = (__popc(qc[0] ^ m0.x) + __popc(qc[1] ^ m0.y)) + (__popc(qc[2] ^ m0.z) + __popc(qc[3] ^ m0.w)) +
-                                  (__popc(qc[4] ^ m1.x) + __popc(qc[5] ^ m1.y)) + (__popc(qc[6] ^ m1.z) + __popc(qc[7] ^ m1.w));
-                    if (h > c.max_distance) continue;
-                    if (h < best_h || (h == best_h && (d2 < best_d2 || (d2 == best_d2 && w.x < best_t)))) { best_h = h; best_d2 = d2; best_t = w.x; }
-                }
-            }
-        }
+        for_each_near_record<kGroup>(ix, cell_of(s.qmx, c.cell), cell_of(s.qmy, c.cell), g, [&](const Rec* rp, int row, int hits, int theirs) {
+            const double2 a = *reinterpret_cast<const double2*>(&rp->ax);
+            const double2 e = *reinterpret_cast<const double2*>(&rp->bx);
+            double d2;
+            if (!near_geometry(c, s, a.x, a.y, e.x, e.y, d2)) return;
+            if (hits < c.min_hits) return;
+            if (c.gating && !colours_agree(colour, theirs)) return;
+            count += 1;
+            const uint4* mp = reinterpret_cast<const uint4*>(md.code + (size_t)row * 32);
+            const uint4 m0 = mp[0], m1 = mp[1];
+            const int h = (__popc(qc[0] ^ m0.x) + __popc(qc[1] ^ m0.y)) + (__popc(qc[2] ^ m0.z) + __popc(qc[3] ^ m0.w)) +
+                          (__popc(qc[4] ^ m1.x) + __popc(qc[5] ^ m1.y)) + (__popc(qc[6] ^ m1.z) + __popc(qc[7] ^ m1.w));
+            if (h > c.max_distance) return;
+            if (h < best_h || (h == best_h && (d2 < best_d2 || (d2 == best_d2 && row < best_t)))) { best_h = h; best_d2 = d2; best_t = row; }
+        });
     }
 
     // the group's count and its smallest (h, d2, row)

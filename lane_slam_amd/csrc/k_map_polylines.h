@@ -30,8 +30,7 @@ LF_NR_HD uint32_t slot_hash(int32_t lane, int32_t cx, int32_t cy)
     return h;
 }
 
-#if defined(__HIPCC__)
-// Device arrays of one call; everything belongs to the map's handle.
+// Device arrays of one call; everything belongs to the map's handle.  (The struct and its carving are plain C++, as ln::Work's.)
 //
 // The two tables (home cells, then assigned cells) are open-addressing tables of int32 OWNER ROWS: a slot is claimed with
 // atomicCAS(-1 -> row), and a prober compares its key with the key of the owner's own row, so no 96-bit keys are stored.  A key's
@@ -70,12 +69,24 @@ struct Work {
     int bound, slots;
 };
 
+// w's arrays for `bound` rows and `slots` slots out of `base` (null: none, only the size), as ln::carve: the vertex records
+// (8-byte aligned) and the 8-byte arrays first.  The caller's memsets rely on three runs staying together and in this order:
+// what starts at 0 (ssum .. sn), what starts at -1 (own1, own2), then sfirst
+inline size_t carve(Work* w, void* base, size_t bound, size_t slots)
+{
+    ln::Carver c = { static_cast<char*>(base), 0 };
+    c.take(w->tmpv, bound); c.take(w->phits, bound);
+    c.take(w->ssum, 4 * slots); c.take(w->shits, slots);
+    for (int** a : { &w->cnt1, &w->sn, &w->own1, &w->own2, &w->sfirst, &w->svid }) c.take(*a, slots);
+    for (int** a : { &w->part, &w->hx, &w->hy, &w->cx, &w->cy, &w->rslot, &w->vslot, &w->fwd, &w->bwd, &w->parent, &w->root, &w->psize, &w->phead,
+                     &w->pn, &w->pid, &w->pfirst, &w->pos }) c.take(*a, bound);
+    c.take(w->nb, 2 * bound);
+    return c.used;
+}
+
+#if defined(__HIPCC__)
 // the caller's arrays, device addresses; each may be null
 struct Out { int32_t* vertex_of; lf_polyline_vertex* vertices; int max_vertices; lf_polyline* polylines; int max_polylines; };
-
-// bytes of the Work arrays per row and per slot, and their carving (lanefront_map_polylines.hip)
-constexpr size_t kWorkBytesPerRow = sizeof(lf_polyline_vertex) + 8 + 19 * 4;
-constexpr size_t kWorkBytesPerSlot = 5 * 8 + 6 * 4;
 
 // B and C, then D and E.  The caller has set own1, own2 to -1, cnt1, sn, shits, ssum to 0 and sfirst to 0x7f bytes.  bound > 0
 void launch_vertices(const Rule& c, const MapDevice& md, const Work& w, hipStream_t s);

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(kWg) void k_pl_home(Rule c, MapDevice md, Work w)
 {
     const int t = blockIdx.x * kWg + threadIdx.x;
     int part = 0, hx = 0, hy = 0;
-    if (t < ln::rows(md, w.bound) && w.lane_of[t] >= 0) {
+    if (t < nr::rows(md, w.bound) && w.lane_of[t] >= 0) {
         const double2 a = *reinterpret_cast<const double2*>(md.ground + (size_t)t * 4);
         const double2 b = *reinterpret_cast<const double2*>(md.ground + (size_t)t * 4 + 2);
         hx = nr::cell_of((a.x + b.x) * 0.5, c.cell);
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kWg) void k_pl_home(Rule c, MapDevice md, Work w)
 __global__ __launch_bounds__(kWg) void k_pl_count(MapDevice md, Work w)
 {
     const int t = blockIdx.x * kWg + threadIdx.x;
-    if (t >= ln::rows(md, w.bound) || !w.part[t]) return;
+    if (t >= nr::rows(md, w.bound) || !w.part[t]) return;
     const Keys k = { w.lane_of, w.hx, w.hy };
     const int s = slot_of<true>(w.own1, w.slots, k, w.lane_of[t], w.hx[t], w.hy[t], t);
     if (s >= 0) atomicAdd(w.cnt1 + s, 1);
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(kWg) void k_pl_count(MapDevice md, Work w)
 __global__ __launch_bounds__(kWg) void k_pl_assign(MapDevice md, Work w)
 {
     const int t = blockIdx.x * kWg + threadIdx.x;
-    if (t >= ln::rows(md, w.bound) || !w.part[t]) return;
+    if (t >= nr::rows(md, w.bound) || !w.part[t]) return;
     const double2 a = *reinterpret_cast<const double2*>(md.ground + (size_t)t * 4);
     const double2 b = *reinterpret_cast<const double2*>(md.ground + (size_t)t * 4 + 2);
     const double ex = b.x - a.x, ey = b.y - a.y;
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(kWg) void k_pl_assign(MapDevice md, Work w)
 __global__ __launch_bounds__(kWg) void k_pl_vertex(Rule c, MapDevice md, Work w)
 {
     const int t = blockIdx.x * kWg + threadIdx.x;
-    const bool on = t < ln::rows(md, w.bound) && w.part[t] != 0;
+    const bool on = t < nr::rows(md, w.bound) && w.part[t] != 0;
     int s = -1, first = kNone, n = 0;
     long long hits = 0, qx = 0, qy = 0, qc = 0, qs = 0;
     if (on) {
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(kWg) void k_pl_vertex(Rule c, MapDevice md, Work w)
 __global__ __launch_bounds__(kScanWg) void k_pl_number(MapDevice md, Work w)
 {
     __shared__ int wave_sums[kScanWg / 64];
-    const int n = ln::rows(md, w.bound);
+    const int n = nr::rows(md, w.bound);
     auto is_head = [&](int t) { const int s = w.part[t] ? w.rslot[t] : -1; return (s >= 0 && w.sfirst[s] == t) ? 1 : 0; };
     const int total = wg_scan_turns<kScanWg>(n, wave_sums, is_head, [&](int t, int before) {
         if (is_head(t)) { const int s = w.rslot[t]; w.svid[s] = before; w.vslot[before] = s; }
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(kWg) void k_pl_write(MapDevice md, Work w, Out o)
     const int np = w.counters[kNPolylines];
     if (o.vertex_of) {
         int at = -1;
-        if (t < ln::rows(md, w.bound) && w.part[t] && w.rslot[t] >= 0) at = w.pos[w.svid[w.rslot[t]]];
+        if (t < nr::rows(md, w.bound) && w.part[t] && w.rslot[t] >= 0) at = w.pos[w.svid[w.rslot[t]]];
         o.vertex_of[t] = at;
     }
     const bool fits = !(o.vertices && nv > o.max_vertices) && !(o.polylines && np > o.max_polylines);

@@ -29,6 +29,15 @@ int refresh_state(lf_map* m, bool block)
     return LF_OK;
 }
 
+int settled_size(lf_map* m, size_t* size)
+{
+    const int rc = refresh_state(m);
+    if (rc != LF_OK) return rc;
+    const int n = m->h_state[0] < m->cfg.capacity ? m->h_state[0] : m->cfg.capacity;
+    *size = (size_t)(n > 0 ? n : 0);
+    return LF_OK;
+}
+
 int queue_state_copy(lf_map* m)
 {
     LF_HIP_CHECK(m, hipMemcpyAsync(m->h_state, m->d.state, 16 * sizeof(int), hipMemcpyDeviceToHost, m->stream));
@@ -71,15 +80,15 @@ extern "C" int lf_map_set_profiling(lf_map* m, int enabled)
     return LF_OK;
 }
 
-int take_stage(lf_map* m, int stage, double* ms, int32_t* launches)
+int take_stages(lf_map* m, int first, int n, double* ms, int32_t* launches)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    m->clock.take(ms, launches, 1, stage, 1);
+    m->clock.take(ms, launches, n, first, n);
     return LF_OK;
 }
 
 // the alignment kernel's stage (lanefront_map_align.hip), kept apart from lf_map_get_timing's table
-extern "C" int lf_map_align_timing(lf_map* m, double* ms, int32_t* launches) { return take_stage(m, kMapAlignStage, ms, launches); }
+extern "C" int lf_map_align_timing(lf_map* m, double* ms, int32_t* launches) { return take_stages(m, kMapAlignStage, 1, ms, launches); }
 
 // ms accumulated and launches counted per stage since the last call; resets both
 extern "C" int lf_map_get_timing(lf_map* m, double* ms_per_stage, int32_t* launches_per_stage, int n)

@@ -2,7 +2,8 @@
 // (lanefront_map_render.hip, lanefront_map_camera.hip), the pose alignment (lanefront_map_align.hip) and the trajectory smoother
 // (lanefront_map_smooth.hip); the localisation without a prior pose (lanefront_map_localize.hip); the culling (lanefront_map_prune.hip);
 // the association gated by the prior pose (lanefront_map_near.hip); the lane lines (lanefront_map_lanes.hip) and their polylines
-// (lanefront_map_polylines.hip).  The three pose solvers share one
+// (lanefront_map_polylines.hip).  The last three share one index of the map, k_map_near.h's: build_index
+// (lanefront_map_near.hip, declared below) is the only code that sizes, grows, fills and queues it.  The three pose solvers share one
 // front end (argument check, batch opener, prior-pose upload) and the two solving steps one body and, with
 // lf_map_step_host, one host-form wrapper: all of it lives in lanefront_map_align.hip and is declared at the end of this file.
 #pragma once
@@ -11,11 +12,12 @@
 #include <vector>
 #include "lanefront_core.h"
 #include "k_map_align.h"
+#include "k_map_near.h"
 
 namespace lf {
 
-// what lf_map_associate_near keeps between calls (lanefront_map_near.hip): the index of the map, rebuilt by every call, and the
-// poses' x, y, cos, sin; scratch that grows on demand
+// what lf_map_associate_near keeps between calls (lanefront_map_near.hip): the index of the map, rebuilt by every build_index, and
+// the poses' x, y, cos, sin; scratch that grows on demand
 struct MapNearState {
     DevBuf start, cursor, bucket, rec, pose, near_out;      // k_map_near.h's Index; pose [n_frames][4]; near_out: a host caller's n_near staged
     std::vector<double> h_pose;
@@ -68,6 +70,15 @@ struct MapPruneState {
 
 using namespace lf;
 
+// the stages of the map's clock behind lf_map_get_timing's: one or more per lf_map_*_timing export, in the order they report them
+enum MapStage {
+    kMapAlignStage = LF_MAP_N_STAGES, kMapSmoothStage, kMapLocalizeStage, kMapPruneStage,
+    kMapNearIndexStage, kMapNearQueryStage,
+    kMapLanesIndexStage, kMapLanesTableStage,
+    kMapPolylinesLanesStage, kMapPolylinesVerticesStage, kMapPolylinesLinksStage,
+    kMapStageCount
+};
+
 struct lf_map : lf::Core {
     lf_map_config cfg;
     int tie_rule = LF_TIE_MIHASHER;          // the reference's tie rule (round 5)
@@ -95,11 +106,8 @@ struct lf_map : lf::Core {
     DevBuf lo_res;                           // lf_map_localize: the results [n_frames]
     std::vector<double> h_pose;
     std::vector<int32_t> h_chains;
-    // per-stage timing: the stages of lf_map_get_timing, then kMapAlignStage (lf_map_align_timing), kMapSmoothStage
-    // (lf_map_smooth_timing), kMapLocalizeStage (lf_map_localize_timing), kMapPruneStage (lf_map_prune_timing) and kMapNearIndexStage,
-    // kMapNearQueryStage (lf_map_near_timing), kMapLanesIndexStage, kMapLanesTableStage (lf_map_lanes_timing), kMapPolylinesLanesStage,
-    // kMapPolylinesVerticesStage, kMapPolylinesLinksStage (lf_map_polylines_timing); past 4096 outstanding records a bracket goes untimed
-    StageClock clock{LF_MAP_N_STAGES + 11, 4096, false};
+    // per-stage timing: the stages of lf_map_get_timing, then MapStage's; past 4096 outstanding records a bracket goes untimed
+    StageClock clock{kMapStageCount, 4096, false};
     bool near_on = false;                         // lf_map_set_near: the steps associate by lf_map_associate_near's rule with near_cfg
     lf_near_config near_cfg = {};
     std::unique_ptr<lf::MapNearState> near;       // lf_map_associate_near (lanefront_map_near.hip), made by its first call
@@ -110,18 +118,6 @@ struct lf_map : lf::Core {
     std::unique_ptr<lf::MapCameraState> camera;   // lf_map_render_camera (lanefront_map_camera.hip), likewise
 };
 
-constexpr int kMapAlignStage = LF_MAP_N_STAGES;
-constexpr int kMapSmoothStage = LF_MAP_N_STAGES + 1;
-constexpr int kMapLocalizeStage = LF_MAP_N_STAGES + 2;
-constexpr int kMapPruneStage = LF_MAP_N_STAGES + 3;
-constexpr int kMapNearIndexStage = LF_MAP_N_STAGES + 4;
-constexpr int kMapNearQueryStage = LF_MAP_N_STAGES + 5;
-constexpr int kMapLanesIndexStage = LF_MAP_N_STAGES + 6;
-constexpr int kMapLanesTableStage = LF_MAP_N_STAGES + 7;
-constexpr int kMapPolylinesLanesStage = LF_MAP_N_STAGES + 8;
-constexpr int kMapPolylinesVerticesStage = LF_MAP_N_STAGES + 9;
-constexpr int kMapPolylinesLinksStage = LF_MAP_N_STAGES + 10;
-
 // ---- lanefront_map.hip's sequencing, for the translation units of the pose solvers
 // make the host mirror current: wait for the copy queued behind the last update (block = false: only look); a failing update the
 // host has not returned an error for yet is reported here, once
@@ -131,8 +127,17 @@ int after_handle(lf_map* m, lf_handle* h);        // the map's stream waits for 
 int release_handle(lf_map* m, lf_handle* h);      // the handle's later work waits for what the map has queued so far
 // rows_hint: how many segment rows the blocks really hold when the host knows it (-1: assume they are full)
 int update_blocks(lf_map* m, const uint8_t* blocks, int n_blocks, int block_rows, int force_append, long long rows_hint = -1);
-// one stage of the map's clock since the previous call; resets it (the three lf_map_*_timing exports)
-int take_stage(lf_map* m, int stage, double* ms, int32_t* launches);
+// the map's size behind everything queued so far, from 0 to the capacity: a blocking refresh_state, so a failing update is reported
+// first, as lf_map_size does
+int settled_size(lf_map* m, size_t* size);
+// n stages of the map's clock from `first` on since the previous call; resets them (the lf_map_*_timing exports)
+int take_stages(lf_map* m, int first, int n, double* ms, int32_t* launches);
+
+// ---- the index of the map as it stands (lanefront_map_near.hip), for lf_map_associate_near, lf_map_lanes and lf_map_polylines
+// bound > 0 rows: makes m->near if it is missing, sizes the table (a power of two of buckets, at least nr::kMinBuckets and twice the
+// rows), grows the four buffers, fills *ix, and queues the table's memset and nr::launch_near_index on the map's stream as one
+// launch of `stage` (stage < 0: inside the bracket the caller holds open).  bound == 0: *ix is empty and nothing is queued
+int build_index(lf_map* m, size_t bound, double cell, int stage, nr::Index* ix);
 
 // ---- a step's association (lanefront_map_near.hip): lf_map_associate of segs->code / segs->color, or, while lf_map_set_near holds a
 // configuration, lf_map_associate_near's rule with frame_pose (null: +0).  Device arrays; who: the exported call, for the error text

@@ -1,6 +1,6 @@
 // lanefront C ABI, the live map's lane lines (include/lanefront.h "lf_map_lanes"): the checks, the scratch, the staging of host
-// outputs and the sequence on the map's stream -- the index of the map as it stands (k_map_near.hip's, in the near state's
-// buffers), then k_map_lanes.hip's kernels -- and ONE host wait at the end, for `res`.
+// outputs and the sequence on the map's stream -- the index of the map as it stands (build_index, lanefront_map_near.hip), then
+// k_map_lanes.hip's kernels -- and ONE host wait at the end, for `res`.
 #include <math.h>
 #include <string.h>
 #include "lanefront_map_handle.h"
@@ -11,10 +11,7 @@ namespace ln {
 
 const char* bad_config(const lf_lanes_config* c)
 {
-    if (!isfinite(c->radius) || !(c->radius > 0)) return "radius is finite and > 0";
-    if (!(c->max_offset > 0)) return "max_offset is > 0 or +inf";
-    if (!(c->max_sin >= 0 && c->max_sin <= 1)) return "max_sin is 0 .. 1";
-    if (c->min_hits < 0) return "min_hits is >= 0";
+    if (const char* why = nr::bad_geometry(c->radius, c->max_offset, c->max_sin, c->min_hits)) return why;
     if (c->min_entries < 1) return "min_entries is >= 1";
     return nullptr;
 }
@@ -23,10 +20,7 @@ Rule make_rule(const lf_lanes_config* c)
 {
     Rule r;
     memset(&r, 0, sizeof(r));
-    r.geo.r2 = c->radius * c->radius; r.geo.ms2 = c->max_sin * c->max_sin; r.geo.mo2 = c->max_offset * c->max_offset;
-    r.geo.cell = nr::cell_size(c->radius);
-    r.geo.test_sin = c->max_sin < 1; r.geo.test_offset = isfinite(c->max_offset) ? 1 : 0;
-    r.geo.min_hits = c->min_hits;
+    r.geo = nr::make_geometry(c->radius, c->max_offset, c->max_sin, c->min_hits);
     r.min_entries = c->min_entries; r.color_mask = c->color_mask;
     return r;
 }
@@ -45,12 +39,7 @@ extern "C" void lf_map_lanes_default_config(lf_lanes_config* c)
     c->radius = 0.25; c->max_offset = 0.05; c->max_sin = 0.25; c->min_hits = 1; c->min_entries = 3; c->color_mask = 0xF;
 }
 
-extern "C" int lf_map_lanes_timing(lf_map* m, double* ms, int32_t* launches)
-{
-    if (!m) return LF_ERR_NOT_INITIALISED;
-    m->clock.take(ms, launches, 2, kMapLanesIndexStage, 2);
-    return LF_OK;
-}
+extern "C" int lf_map_lanes_timing(lf_map* m, double* ms, int32_t* launches) { return take_stages(m, kMapLanesIndexStage, 2, ms, launches); }
 
 extern "C" int lf_map_lanes(lf_map* m, const lf_lanes_config* c, lf_lanes_result* res, int32_t* lane_of, int32_t* n_links, int32_t* support,
                             lf_lane* lanes, int max_lanes, int on_device)
@@ -62,26 +51,17 @@ extern "C" int lf_map_lanes(lf_map* m, const lf_lanes_config* c, lf_lanes_result
     if (max_lanes < 0 || (lanes && max_lanes == 0)) { set_error(m, LF_ERR_BAD_ARG, "%s: max_lanes is >= 0, and >= 1 with a table", who); return LF_ERR_BAD_ARG; }
     LF_HIP_CHECK(m, hipSetDevice(m->device));
     int rc;
-    // the map's size as it is behind everything queued so far; a failing update is reported first, as lf_map_size does
-    if ((rc = refresh_state(m)) != LF_OK) return rc;
-    const int cap = m->cfg.capacity;
-    const int size = m->h_state[0] < cap ? m->h_state[0] : cap;
-    const size_t bound = (size_t)(size > 0 ? size : 0);
+    size_t bound;
+    if ((rc = settled_size(m, &bound)) != LF_OK) return rc;
     if (!m->lanes) m->lanes.reset(new lf::MapLanesState());
-    if (!m->near) m->near.reset(new lf::MapNearState());
     lf::MapLanesState& st = *m->lanes;
-    lf::MapNearState& ns = *m->near;
     hipStream_t s = m->stream;
     if (!st.h_counters.p) LF_HIP_CHECK(m, st.h_counters.alloc(ln::kNCounters * sizeof(int)));
-    size_t buckets = nr::kMinBuckets;
-    while (buckets < 2 * bound) buckets <<= 1;
+    ln::Work w;
+    memset(&w, 0, sizeof(w));
     if ((rc = scratch(m, st.counters, ln::kNCounters * sizeof(int))) != LF_OK) return rc;
-    if (bound > 0 &&
-        ((rc = scratch(m, st.work, bound * ln::kWorkBytesPerRow)) || (rc = scratch(m, ns.start, (buckets + 4) * sizeof(int))) ||
-         (rc = scratch(m, ns.cursor, buckets * sizeof(int))) || (rc = scratch(m, ns.bucket, bound * sizeof(int))) ||
-         (rc = scratch(m, ns.rec, bound * sizeof(nr::Rec)))))
-        return rc;
-    const size_t row_bytes = (size_t)cap * sizeof(int32_t);
+    if (bound > 0 && (rc = scratch(m, st.work, ln::carve(&w, nullptr, bound))) != LF_OK) return rc;
+    const size_t row_bytes = (size_t)m->cfg.capacity * sizeof(int32_t);
     Staging host(m);
     ln::Out o;
     o.lane_of = lane_of ? host.out(on_device, lane_of, row_bytes, st.lane_of) : nullptr;
@@ -92,22 +72,10 @@ extern "C" int lf_map_lanes(lf_map* m, const lf_lanes_config* c, lf_lanes_result
     if ((rc = host.upload()) != LF_OK) return rc;
 
     const ln::Rule r = ln::make_rule(c);
-    nr::Index ix;
-    ix.start = static_cast<int*>(ns.start.p); ix.cursor = static_cast<int*>(ns.cursor.p); ix.bucket = static_cast<int*>(ns.bucket.p);
-    ix.rec = static_cast<nr::Rec*>(ns.rec.p); ix.mask = (uint32_t)(buckets - 1); ix.bound = (int)bound;
-    ln::Work w;
-    memset(&w, 0, sizeof(w));
     w.counters = static_cast<int*>(st.counters.p); w.bound = (int)bound;
-    if (bound > 0) {
-        // the 8-byte arrays first, then the six of ints
-        w.box = static_cast<unsigned long long*>(st.work.p);
-        w.hsum = w.box + 4 * bound;
-        w.parent = reinterpret_cast<int*>(w.hsum + bound);
-        w.root = w.parent + bound; w.elig = w.root + bound; w.nl = w.elig + bound; w.cnt = w.nl + bound; w.lane_no = w.cnt + bound;
-        StageClock::Scope t(m, m->clock, kMapLanesIndexStage);
-        LF_HIP_CHECK(m, hipMemsetAsync(ix.start, 0, (buckets + 1) * sizeof(int), s));
-        nr::launch_near_index(m->d, r.geo.cell, ix, s);
-    }
+    if (bound > 0) ln::carve(&w, st.work.p, bound);
+    nr::Index ix;
+    if ((rc = build_index(m, bound, r.geo.cell, kMapLanesIndexStage, &ix)) != LF_OK) return rc;
     {
         StageClock::Scope t(m, m->clock, kMapLanesTableStage);
         LF_HIP_CHECK(m, hipMemsetAsync(w.counters, 0, ln::kNCounters * sizeof(int), s));
@@ -119,7 +87,7 @@ extern "C" int lf_map_lanes(lf_map* m, const lf_lanes_config* c, lf_lanes_result
     if ((rc = fetch(m, { { lane_of, o.lane_of, row_bytes }, { n_links, o.n_links, row_bytes }, { support, o.support, row_bytes } })) != LF_OK) return rc;
     LF_HIP_CHECK(m, hipStreamSynchronize(s));
     const int* hc = st.h_counters;
-    res->size = size > 0 ? size : 0; res->n_eligible = hc[ln::kNEligible]; res->n_components = hc[ln::kNComponents]; res->n_lanes = hc[ln::kNLanes];
+    res->size = (int)bound; res->n_eligible = hc[ln::kNEligible]; res->n_components = hc[ln::kNComponents]; res->n_lanes = hc[ln::kNLanes];
     unsigned long long both_ends;
     memcpy(&both_ends, hc + ln::kNLinks, sizeof(both_ends));
     res->n_links = (int64_t)(both_ends / 2);

@@ -30,7 +30,7 @@ extern "C" void lf_map_localize_default_config(lf_localize_config* c)
     c->gate = 0.10; c->min_sin = 0.2; c->max_dist = INFINITY;
 }
 
-extern "C" int lf_map_localize_timing(lf_map* m, double* ms, int32_t* launches) { return take_stage(m, kMapLocalizeStage, ms, launches); }
+extern "C" int lf_map_localize_timing(lf_map* m, double* ms, int32_t* launches) { return take_stages(m, kMapLocalizeStage, 1, ms, launches); }
 
 extern "C" int lf_map_localize(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist,
                                const double* fallback_pose, const lf_localize_config* cfg, int on_device, lf_localize_result* results)

@@ -1,22 +1,22 @@
 // lanefront C ABI, association gated by the prior pose (include/lanefront.h "lf_map_associate_near"): the checks, the staging of host
 // arrays, the poses' cos / sin on the host, and the sequence of k_map_near.hip's kernels on the map's stream: the index of the map
 // as it stands, then the query.  No host wait inside.  Also the one place where a step chooses its association
-// (associate_for_step): lf_map_associate, or this rule while lf_map_set_near holds a configuration.
+// (associate_for_step): lf_map_associate, or this rule while lf_map_set_near holds a configuration.  And the owner of the index
+// on the host (build_index), which lf_map_lanes and lf_map_polylines call too.
 #include <math.h>
 #include <string.h>
+#include <optional>
 #include "lanefront_map_handle.h"
 #include "detmath.h"
-#include "k_map_near.h"
 
 namespace {
 
-const char* bad_config(const lf_near_config* c)
+const char* bad_config(const lf_near_config* c) { return nr::bad_geometry(c->radius, c->max_offset, c->max_sin, c->min_hits); }
+
+lf::MapNearState& near_state(lf_map* m)
 {
-    if (!isfinite(c->radius) || !(c->radius > 0)) return "radius is finite and > 0";
-    if (!(c->max_offset > 0)) return "max_offset is > 0 or +inf";
-    if (!(c->max_sin >= 0 && c->max_sin <= 1)) return "max_sin is 0 .. 1";
-    if (c->min_hits < 0) return "min_hits is >= 0";
-    return nullptr;
+    if (!m->near) m->near.reset(new lf::MapNearState());
+    return *m->near;
 }
 
 // what lf_map_associate_near refuses; nothing is touched
@@ -40,7 +40,8 @@ int queue_near(lf_map* m, const int* frame_offset, const uint8_t* code, const ui
     int rc;
     hipStream_t s = m->stream;
     // the map's size behind everything queued so far is read on the device; the host sizes grids and arrays from an upper bound,
-    // as lf_map_associate does
+    // as lf_map_associate does: what the mirror shows without a wait plus the rows of updates still in flight.  (Not
+    // settled_size, which waits for the exact size: no host wait here.)
     if ((rc = refresh_state(m, false)) != LF_OK) return rc;
     long long bound = (long long)m->h_state[0] + (m->state_pending ? m->rows_in_flight : 0);
     if (bound > m->cfg.capacity) bound = m->cfg.capacity;
@@ -50,14 +51,8 @@ int queue_near(lf_map* m, const int* frame_offset, const uint8_t* code, const ui
         LF_HIP_CHECK(m, hipGetLastError());
         return LF_OK;
     }
-    if (!m->near) m->near.reset(new lf::MapNearState());
-    lf::MapNearState& st = *m->near;
-    size_t buckets = nr::kMinBuckets;
-    while (buckets < 2 * (size_t)bound) buckets <<= 1;
-    if ((rc = scratch(m, st.start, (buckets + 4) * sizeof(int))) || (rc = scratch(m, st.cursor, buckets * sizeof(int))) ||
-        (rc = scratch(m, st.bucket, (size_t)bound * sizeof(int))) || (rc = scratch(m, st.rec, (size_t)bound * sizeof(nr::Rec))) ||
-        (rc = scratch(m, st.pose, (size_t)n_frames * 4 * sizeof(double))))
-        return rc;
+    lf::MapNearState& st = near_state(m);
+    if ((rc = scratch(m, st.pose, (size_t)n_frames * 4 * sizeof(double))) != LF_OK) return rc;
     // cos / sin with the library's deterministic routines on the host, as lf_map_pack_block takes them; no poses: +0 everywhere
     st.h_pose.resize((size_t)n_frames * 4);
     for (int f = 0; f < n_frames; ++f) {
@@ -68,24 +63,14 @@ int queue_near(lf_map* m, const int* frame_offset, const uint8_t* code, const ui
     }
     LF_HIP_CHECK(m, hipMemcpyAsync(st.pose.p, st.h_pose.data(), (size_t)n_frames * 4 * sizeof(double), hipMemcpyHostToDevice, s));
 
-    nr::Rule c;
-    memset(&c, 0, sizeof(c));
-    c.r2 = cfg->radius * cfg->radius; c.ms2 = cfg->max_sin * cfg->max_sin; c.mo2 = cfg->max_offset * cfg->max_offset;
-    c.cell = nr::cell_size(cfg->radius);
-    c.test_sin = cfg->max_sin < 1; c.test_offset = isfinite(cfg->max_offset) ? 1 : 0;
-    c.min_hits = cfg->min_hits; c.gating = m->cfg.color_gating ? 1 : 0; c.max_distance = m->cfg.max_distance;
+    nr::Rule c = nr::make_geometry(cfg->radius, cfg->max_offset, cfg->max_sin, cfg->min_hits);
+    c.gating = m->cfg.color_gating ? 1 : 0; c.max_distance = m->cfg.max_distance;
     nr::Index ix;
-    ix.start = static_cast<int*>(st.start.p); ix.cursor = static_cast<int*>(st.cursor.p); ix.bucket = static_cast<int*>(st.bucket.p);
-    ix.rec = static_cast<nr::Rec*>(st.rec.p); ix.mask = (uint32_t)(buckets - 1); ix.bound = (int)bound;
+    if ((rc = build_index(m, (size_t)bound, c.cell, kMapNearIndexStage, &ix)) != LF_OK) return rc;
     nr::Query q;
     q.frame_offset = frame_offset; q.code = code; q.color = color; q.ground = ground;
     q.pose4 = static_cast<const double*>(st.pose.p); q.n = n; q.n_frames = n_frames;
     q.idx = idx; q.dist = dist; q.n_near = n_near;
-    {
-        StageClock::Scope t(m, m->clock, kMapNearIndexStage);
-        LF_HIP_CHECK(m, hipMemsetAsync(ix.start, 0, (buckets + 1) * sizeof(int), s));
-        nr::launch_near_index(m->d, c.cell, ix, s);
-    }
     {
         StageClock::Scope t(m, m->clock, kMapNearQueryStage);
         nr::launch_near_query(c, m->d, ix, q, s);
@@ -95,6 +80,28 @@ int queue_near(lf_map* m, const int* frame_offset, const uint8_t* code, const ui
 }
 
 }  // namespace
+
+int build_index(lf_map* m, size_t bound, double cell, int stage, nr::Index* ix)
+{
+    memset(ix, 0, sizeof(*ix));
+    if (bound == 0) return LF_OK;
+    lf::MapNearState& st = near_state(m);
+    size_t buckets = nr::kMinBuckets;
+    while (buckets < 2 * bound) buckets <<= 1;
+    int rc;
+    // start holds one whole int4 more than the buckets: k_near_scan reads and writes it in int4s, and start[buckets] (the valid
+    // rows) lies behind the last of them
+    if ((rc = scratch(m, st.start, (buckets + 4) * sizeof(int))) || (rc = scratch(m, st.cursor, buckets * sizeof(int))) ||
+        (rc = scratch(m, st.bucket, bound * sizeof(int))) || (rc = scratch(m, st.rec, bound * sizeof(nr::Rec))))
+        return rc;
+    ix->start = static_cast<int*>(st.start.p); ix->cursor = static_cast<int*>(st.cursor.p); ix->bucket = static_cast<int*>(st.bucket.p);
+    ix->rec = static_cast<nr::Rec*>(st.rec.p); ix->mask = (uint32_t)(buckets - 1); ix->bound = (int)bound;
+    std::optional<StageClock::Scope> t;
+    if (stage >= 0) t.emplace(m, m->clock, stage);
+    LF_HIP_CHECK(m, hipMemsetAsync(ix->start, 0, (buckets + 1) * sizeof(int), m->stream));
+    nr::launch_near_index(m->d, cell, *ix, m->stream);
+    return LF_OK;
+}
 
 int associate_for_step(lf_map* m, lf_handle* h, const char* who, const lf_segments* segs, int n, int n_frames, const double* frame_pose,
                        int32_t* idx, float* dist)
@@ -118,12 +125,7 @@ extern "C" void lf_map_near_default_config(lf_near_config* c)
     c->radius = 0.25; c->max_offset = 0.10; c->max_sin = 0.5; c->min_hits = 1;
 }
 
-extern "C" int lf_map_near_timing(lf_map* m, double* ms, int32_t* launches)
-{
-    if (!m) return LF_ERR_NOT_INITIALISED;
-    m->clock.take(ms, launches, 2, kMapNearIndexStage, 2);
-    return LF_OK;
-}
+extern "C" int lf_map_near_timing(lf_map* m, double* ms, int32_t* launches) { return take_stages(m, kMapNearIndexStage, 2, ms, launches); }
 
 extern "C" int lf_map_set_near(lf_map* m, const lf_near_config* cfg)
 {
@@ -159,8 +161,7 @@ extern "C" int lf_map_associate_near(lf_map* m, lf_handle* h, const lf_segments*
     const uint8_t* d_color = (m->cfg.color_gating && segs->color) ? st.in(on_device, segs->color, c, m->st_color) : nullptr;
     int32_t* d_idx = st.out(on_device, idx, c * 4, m->st_idx);
     float* d_dist = st.out(on_device, dist, c * 4, m->st_dist);
-    if (!m->near) m->near.reset(new lf::MapNearState());
-    int32_t* d_near = n_near ? st.out(on_device, n_near, c * 4, m->near->near_out) : nullptr;
+    int32_t* d_near = n_near ? st.out(on_device, n_near, c * 4, near_state(m).near_out) : nullptr;
     if ((rc = st.upload()) != LF_OK) return rc;
     if ((rc = queue_near(m, d_fo, d_code, d_color, d_ground, n, n_frames, frame_pose, cfg, d_idx, d_dist, d_near)) != LF_OK) return rc;
     if ((rc = release_handle(m, h)) != LF_OK) return rc;

@@ -1,6 +1,6 @@
 // lanefront C ABI, the live map's lane lines as ordered polylines (include/lanefront.h "lf_map_polylines"): the checks, the
-// scratch, the staging of host outputs and the sequence on the map's stream -- the index of the map as it stands (k_map_near.hip's,
-// in the near state's buffers), the lanes stage (ln::launch_lanes into work arrays of this call's own), then k_map_polylines.hip's
+// scratch, the staging of host outputs and the sequence on the map's stream -- the index of the map as it stands (build_index,
+// lanefront_map_near.hip), the lanes stage (ln::launch_lanes into work arrays of this call's own), then k_map_polylines.hip's
 // kernels -- and ONE host wait at the end, for `res`.  A host caller's two tables come down behind that wait, when their lengths
 // are known: two blocking copies more (a table that turns out too small must stay untouched, so nothing is copied ahead).
 #include <math.h>
@@ -34,12 +34,7 @@ extern "C" void lf_map_polylines_default_config(lf_polylines_config* c)
     c->cell = 0.10; c->max_gap = 0.30; c->reach = 3;
 }
 
-extern "C" int lf_map_polylines_timing(lf_map* m, double* ms, int32_t* launches)
-{
-    if (!m) return LF_ERR_NOT_INITIALISED;
-    m->clock.take(ms, launches, 3, kMapPolylinesLanesStage, 3);
-    return LF_OK;
-}
+extern "C" int lf_map_polylines_timing(lf_map* m, double* ms, int32_t* launches) { return take_stages(m, kMapPolylinesLanesStage, 3, ms, launches); }
 
 extern "C" int lf_map_polylines(lf_map* m, const lf_polylines_config* c, lf_polylines_result* res, int32_t* vertex_of, lf_polyline_vertex* vertices,
                                 int max_vertices, lf_polyline* polylines, int max_polylines, int on_device)
@@ -52,27 +47,22 @@ extern "C" int lf_map_polylines(lf_map* m, const lf_polylines_config* c, lf_poly
     if (max_polylines < 0 || (polylines && max_polylines == 0)) { set_error(m, LF_ERR_BAD_ARG, "%s: max_polylines is >= 0, and >= 1 with a table", who); return LF_ERR_BAD_ARG; }
     LF_HIP_CHECK(m, hipSetDevice(m->device));
     int rc;
-    // the map's size as it is behind everything queued so far; a failing update is reported first, as lf_map_size does
-    if ((rc = refresh_state(m)) != LF_OK) return rc;
-    const int cap = m->cfg.capacity;
-    const int size = m->h_state[0] < cap ? m->h_state[0] : cap;
-    const size_t bound = (size_t)(size > 0 ? size : 0);
+    size_t bound;
+    if ((rc = settled_size(m, &bound)) != LF_OK) return rc;
     if (!m->polylines) m->polylines.reset(new lf::MapPolylinesState());
-    if (!m->near) m->near.reset(new lf::MapNearState());
     lf::MapPolylinesState& st = *m->polylines;
-    lf::MapNearState& ns = *m->near;
     hipStream_t s = m->stream;
     constexpr int kCounters = ln::kNCounters + pl::kNCounters;
     if (!st.h_counters.p) LF_HIP_CHECK(m, st.h_counters.alloc(kCounters * sizeof(int)));
-    size_t buckets = nr::kMinBuckets, slots = pl::kMinSlots;
-    while (buckets < 2 * bound) buckets <<= 1;
+    size_t slots = pl::kMinSlots;
     while (slots < 2 * bound) slots <<= 1;
-    const size_t row_bytes = (size_t)cap * sizeof(int32_t);
+    ln::Work lw;
+    memset(&lw, 0, sizeof(lw));
+    pl::Work w;
+    memset(&w, 0, sizeof(w));
+    const size_t row_bytes = (size_t)m->cfg.capacity * sizeof(int32_t);
     if ((rc = scratch(m, st.counters, kCounters * sizeof(int))) || (rc = scratch(m, st.lane_of, row_bytes))) return rc;
-    if (bound > 0 &&
-        ((rc = scratch(m, st.lanes_work, bound * ln::kWorkBytesPerRow)) || (rc = scratch(m, st.work, bound * pl::kWorkBytesPerRow + slots * pl::kWorkBytesPerSlot)) ||
-         (rc = scratch(m, ns.start, (buckets + 4) * sizeof(int))) || (rc = scratch(m, ns.cursor, buckets * sizeof(int))) ||
-         (rc = scratch(m, ns.bucket, bound * sizeof(int))) || (rc = scratch(m, ns.rec, bound * sizeof(nr::Rec)))))
+    if (bound > 0 && ((rc = scratch(m, st.lanes_work, ln::carve(&lw, nullptr, bound))) || (rc = scratch(m, st.work, pl::carve(&w, nullptr, bound, slots)))))
         return rc;
     Staging host(m);
     pl::Out o;
@@ -86,53 +76,30 @@ extern "C" int lf_map_polylines(lf_map* m, const lf_polylines_config* c, lf_poly
     pl::Rule r;
     memset(&r, 0, sizeof(r));
     r.cell = c->cell; r.gap2 = c->max_gap * c->max_gap; r.reach = c->reach;
-    nr::Index ix;
-    ix.start = static_cast<int*>(ns.start.p); ix.cursor = static_cast<int*>(ns.cursor.p); ix.bucket = static_cast<int*>(ns.bucket.p);
-    ix.rec = static_cast<nr::Rec*>(ns.rec.p); ix.mask = (uint32_t)(buckets - 1); ix.bound = (int)bound;
     int* counters = static_cast<int*>(st.counters.p);
-    ln::Work lw;
-    memset(&lw, 0, sizeof(lw));
     lw.counters = counters; lw.bound = (int)bound;
     ln::Out lo;
     memset(&lo, 0, sizeof(lo));
     lo.lane_of = static_cast<int32_t*>(st.lane_of.p);
-    pl::Work w;
-    memset(&w, 0, sizeof(w));
     w.lane_of = lo.lane_of; w.counters = counters + ln::kNCounters; w.bound = (int)bound; w.slots = (int)slots;
-    unsigned long long* zeroed = nullptr;
     if (bound > 0) {
-        // the lanes stage's arrays as lf_map_lanes carves them: the 8-byte arrays first, then the six of ints
-        lw.box = static_cast<unsigned long long*>(st.lanes_work.p);
-        lw.hsum = lw.box + 4 * bound;
-        lw.parent = reinterpret_cast<int*>(lw.hsum + bound);
-        lw.root = lw.parent + bound; lw.elig = lw.root + bound; lw.nl = lw.elig + bound; lw.cnt = lw.nl + bound; lw.lane_no = lw.cnt + bound;
-        // this call's: the records, the 8-byte arrays, the slots' (what starts at 0 together, then what starts at -1), the rows'
-        w.tmpv = static_cast<lf_polyline_vertex*>(st.work.p);
-        w.phits = reinterpret_cast<unsigned long long*>(w.tmpv + bound);
-        zeroed = w.phits + bound;
-        w.ssum = zeroed; w.shits = w.ssum + 4 * slots;
-        w.cnt1 = reinterpret_cast<int*>(w.shits + slots); w.sn = w.cnt1 + slots;
-        w.own1 = w.sn + slots; w.own2 = w.own1 + slots;
-        w.sfirst = w.own2 + slots; w.svid = w.sfirst + slots;
-        int* p = w.svid + slots;
-        for (int** a : { &w.part, &w.hx, &w.hy, &w.cx, &w.cy, &w.rslot, &w.vslot, &w.fwd, &w.bwd, &w.parent, &w.root, &w.psize, &w.phead, &w.pn,
-                         &w.pid, &w.pfirst, &w.pos }) { *a = p; p += bound; }
-        w.nb = p;
+        ln::carve(&lw, st.lanes_work.p, bound);
+        pl::carve(&w, st.work.p, bound, slots);
     }
     LF_HIP_CHECK(m, hipMemsetAsync(counters, 0, kCounters * sizeof(int), s));
     {
         StageClock::Scope t(m, m->clock, kMapPolylinesLanesStage);
-        if (bound > 0) {
-            LF_HIP_CHECK(m, hipMemsetAsync(ix.start, 0, (buckets + 1) * sizeof(int), s));
-            nr::launch_near_index(m->d, lr.geo.cell, ix, s);
-        }
+        nr::Index ix;
+        if ((rc = build_index(m, bound, lr.geo.cell, -1, &ix)) != LF_OK) return rc;      // (-1: inside this bracket)
         ln::launch_lanes(lr, m->d, ix, lw, lo, s);
     }
     if (bound > 0) {
         StageClock::Scope t(m, m->clock, kMapPolylinesVerticesStage);
-        LF_HIP_CHECK(m, hipMemsetAsync(zeroed, 0, slots * (5 * 8 + 2 * 4), s));
-        LF_HIP_CHECK(m, hipMemsetAsync(w.own1, 0xFF, slots * 2 * sizeof(int), s));
-        LF_HIP_CHECK(m, hipMemsetAsync(w.sfirst, 0x7F, slots * sizeof(int), s));
+        // what starts at 0 (ssum up to own1), at -1 (own1 and own2, up to sfirst) and at 0x7f7f7f7f (sfirst, up to svid): pl::carve
+        const auto bytes = [](const void* from, const void* to) { return (size_t)(static_cast<const char*>(to) - static_cast<const char*>(from)); };
+        LF_HIP_CHECK(m, hipMemsetAsync(w.ssum, 0, bytes(w.ssum, w.own1), s));
+        LF_HIP_CHECK(m, hipMemsetAsync(w.own1, 0xFF, bytes(w.own1, w.sfirst), s));
+        LF_HIP_CHECK(m, hipMemsetAsync(w.sfirst, 0x7F, bytes(w.sfirst, w.svid), s));
         pl::launch_vertices(r, m->d, w, s);
     }
     {
@@ -146,7 +113,7 @@ extern "C" int lf_map_polylines(lf_map* m, const lf_polylines_config* c, lf_poly
     LF_HIP_CHECK(m, hipStreamSynchronize(s));
     const int* hc = st.h_counters;
     const int* pc = hc + ln::kNCounters;
-    res->size = size > 0 ? size : 0; res->n_lanes = hc[ln::kNLanes];
+    res->size = (int)bound; res->n_lanes = hc[ln::kNLanes];
     res->n_participating = pc[pl::kNParticipating]; res->n_vertices = pc[pl::kNVertices]; res->n_polylines = pc[pl::kNPolylines];
     res->n_closed = pc[pl::kNClosed]; res->n_edges = pc[pl::kNEdges]; res->reserved_ = 0;
     if (pc[pl::kNDropped] != 0) {                // cannot be: the tables hold twice the rows (k_map_polylines.hip slot_of)

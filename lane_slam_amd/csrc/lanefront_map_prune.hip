@@ -33,7 +33,7 @@ extern "C" void lf_map_prune_default_config(lf_prune_config* c)
     c->stale_before = INT32_MIN; c->keep_seeded = 1; c->color_mask = 0xF; c->cover_max_entries = 131072;
 }
 
-extern "C" int lf_map_prune_timing(lf_map* m, double* ms, int32_t* launches) { return take_stage(m, kMapPruneStage, ms, launches); }
+extern "C" int lf_map_prune_timing(lf_map* m, double* ms, int32_t* launches) { return take_stages(m, kMapPruneStage, 1, ms, launches); }
 
 extern "C" int lf_map_prune(lf_map* m, const lf_prune_config* c, lf_prune_result* res, int32_t* remap, int remap_on_device)
 {

@@ -84,7 +84,7 @@ extern "C" void lf_map_smooth_default_config(lf_smooth_config* c)
     c->anchor_xy = 0.0; c->anchor_theta = 0.0;
 }
 
-extern "C" int lf_map_smooth_timing(lf_map* m, double* ms, int32_t* launches) { return take_stage(m, kMapSmoothStage, ms, launches); }
+extern "C" int lf_map_smooth_timing(lf_map* m, double* ms, int32_t* launches) { return take_stages(m, kMapSmoothStage, 1, ms, launches); }
 
 extern "C" int lf_map_smooth(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const int32_t* idx, const float* dist,
                              const double* frame_pose, const int32_t* chain_offset, int n_chains, const lf_smooth_config* cfg, int on_device,

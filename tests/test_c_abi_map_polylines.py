@@ -67,6 +67,27 @@ def test_c_client_gets_the_default_config(tmp_path):
     assert [float.fromhex(x) for x in got[7:9]] == [P.DEFAULTS["cell"], P.DEFAULTS["max_gap"]] and [int(x) for x in got[9:]] == [P.DEFAULTS["reach"], 0]
 
 
+def test_the_work_arrays_are_carved_inside_their_buffers(tmp_path):
+    """tests/c_abi/map_work_carve.cpp, plain C++ under AddressSanitizer and UBSan: ln::carve and pl::carve size their buffers by the
+    same statements that hand the arrays out, so an array added to a Work struct cannot overrun the next one unseen.  The program
+    checks sizes, bounds, overlaps, alignment and the end of the last array (its header says how); here: it passes at every pair,
+    and the sizes are the rows' and slots' bytes that the structs' comments add up to."""
+    exe = str(tmp_path / "map_work_carve")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "lane_slam_amd", "csrc"), "-o", exe,
+                           os.path.join(HERE, "c_abi", "map_work_carve.cpp")])
+    pairs = [(bound, slots) for slots in (64, 128) for bound in (1, 2, 63, 64)]
+    p = subprocess.run([exe] + [str(v) for pair in pairs for v in pair], capture_output=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert p.returncode == 0, (p.stdout + p.stderr).decode()[-2000:]
+    got = [ln.split() for ln in p.stdout.decode().split("\n") if ln]
+    vertex = ctypes.sizeof(_lib.LfPolylineVertex)
+    want = []
+    for bound, slots in pairs:
+        want.append(["lanes", bound, slots, bound * (4 * 8 + 8 + 6 * 4), 8])                 # box [bound][4], hsum, six arrays of ints
+        want.append(["polylines", bound, slots, bound * (vertex + 8 + 19 * 4) + slots * (5 * 8 + 6 * 4), 28])
+    assert got == [[str(v) for v in w] for w in want]
+
+
 @pytest.mark.gpu
 def test_one_call_from_c_equals_the_restatement_and_one_is_refused(tmp_path):
     p = subprocess.run([build_client(tmp_path), "run"], capture_output=True)

@@ -268,6 +268,31 @@ def test_a_pending_failing_update_is_reported_first_once():
     a.close()
 
 
+def test_three_calls_with_three_radii_share_the_index_buffers():
+    """lf_map_associate_near, lf_map_lanes and lf_map_polylines build the index of the map in the same buffers of the handle
+    (build_index, lanefront_map_near.hip), each with the cell of its own radius: called in turn on one map, each still gives the
+    bytes of its restatement, whatever table the call before left behind, and again after a step has appended rows."""
+    import test_gpu_map_lanes as TL
+    import test_gpu_map_near as TN
+    (code, color, ground), seg, poses = N.small_case(31)
+    m, size = N.make_map(code, color, ground)
+    a = seeded(m, size, cap=1024)
+    wide, middle = dict(radius=1.0, min_entries=2), dict(radius=0.5)          # near: its default, 0.25
+    TN.check(a, seg, poses)
+    lanes = TL.check(a, **wide)
+    check(a, **middle)
+    assert TL.as_bytes(TL.check(a, **wide)) == TL.as_bytes(lanes)
+    TN.check(a, seg, poses)
+    a.step(seg, poses, 1)
+    grown = a.state()["size"]
+    assert size < grown <= size + seg.n
+    got = check(a, **middle)
+    assert got.result["size"] == grown
+    TN.check(a, seg, poses)
+    assert TL.check(a, **wide).result["size"] == grown
+    a.close()
+
+
 def test_timing_counts_the_launches():
     m, size = L.chain_case(96, "forward")
     a = seeded(m, size, cap=128)

@@ -36,11 +36,11 @@ kernel below is launched with a workgroup of whole waves (its __launch_bounds__ 
                          pixel loop, one wave per tile); <64> op_max unsigned k_hough.hip:175 (the `continue` above tests the wave's
                          one point; the loop over q is unrolled and uniform); <64> op_add unsigned k_kmeans.h:45 (KmAcc::flush, under
                          the uniform `k <= 4`, after reconverged point loops); <64> op_add int k_assoc_ties.hip:130 (loop over
-                         c = wave: whole waves); <kGroup = 16> op_min int k_map_near.hip:102 (no return above; a dead segment keeps
+                         c = wave: whole waves); <kGroup = 16> op_min int k_map_near.hip:89 (no return above; a dead segment keeps
                          INT32_MAX)
   wg_excl_scan           <1024> unsigned long long k_map_render.hip:77 (no branch above); <kDenseThreads = 256> int k_dense.hip:95
                          (loop over w0, uniform; idle threads pass 0); <256> uint32_t k_jenc.hip:293, :333 (the returns above test
-                         blockIdx and per-frame words only); <kScanWg = 1024> int k_map_near.hip:59 (uniform loop)
+                         blockIdx and per-frame words only); <kScanWg = 1024> int k_map_near.hip:46 (uniform loop)
   wg_scan_turns          <kWg = 256> int k_map_prune.hip:60; <1024> int k_knn.hip:200; <1024> uint32_t k_jenc.hip:227; <256> uint32_t
                          k_jenc.hip:305; <kSegOffsetsThreads = 256> int k_segments.hip:30 (launched with that constant);
                          <kMapWg = 256> int k_map.hip:160 -- one-workgroup kernels, no branch or return above the call
