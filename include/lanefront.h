@@ -1119,6 +1119,83 @@ LF_API int lf_map_polylines(lf_map* m, const lf_polylines_config* c, lf_polyline
  * other timing calls are unchanged. */
 LF_API int lf_map_polylines_timing(lf_map* m, double ms[3], int32_t launches[3]);
 
+/* ---- where the robot is in its lane, from the live map's polylines: lf_map_lane_pose ----------------------
+ * lf_map_polylines gives every lane line as ordered vertices; lf_map_align, lf_map_smooth and lf_map_localize give a map-frame pose
+ * per frame.  lf_map_lane_pose joins the two: per frame the lateral offset d and the heading phi relative to the white line on the
+ * robot's right and the yellow line on its left -- the two numbers of duckietown_msgs/LanePose, which the reference's lane_filter
+ * votes for per frame from loose segments (lf_lane_filter_*) -- here from geometry alone, whatever the current frame happens to
+ * see.  The reference has no such stage: this is the package's OWN contract, written so that a sequential restatement
+ * (tests/map_lane_pose_ref.py: every edge for every frame) and the kernels (k_map_lane_pose.hip) agree bit for bit.  All
+ * arithmetic is f64, unfused, in the order written: + - * /, the correctly rounded square root, the library's sin / cos (computed
+ * on the host, as lf_map_associate_near's) and the library's atan2 (on the device); a comparison with a NaN fails; every stored
+ * double is written as v + 0.0 (no -0).
+ *
+ *   A  polylines        vertices and polylines are exactly what lf_map_polylines gives under c->polylines, in work arrays of the
+ *                       call's own that hold the settled size: the call never returns LF_ERR_CAPACITY for them.  res->polylines
+ *                       is that call's result.
+ *   B  edges            Vertex index i starts an edge to j = i + 1 when both belong to the same polyline; the last vertex of a
+ *                       closed polyline with at least 3 vertices starts an edge to that polyline's first_vertex.  a = (x_i, y_i),
+ *                       b = (x_j, y_j), ux = bx - ax, uy = by - ay, L2 = ux*ux + uy*uy.  The edge's colour is the colour byte of
+ *                       map row vertices[i].first_row (all members of a lane share it).  An edge is ELIGIBLE when the colour is 0
+ *                       (white) or 1 (yellow), its polyline has at least min_vertices vertices and L2 > 0.  res->n_edges[c]: the
+ *                       eligible edges of colour c.
+ *   C  per frame        (x, y, th) = frame_pose[3f ..], (sn, cs) = sin, cos of th.  For every eligible edge:
+ *                         px = x - ax;  py = y - ay;  t = px*ux + py*uy
+ *                         t <= 0:   qx = px, qy = py
+ *                         t >= L2:  qx = x - bx, qy = y - by
+ *                         else:     r = t / L2;  qx = px - r*ux;  qy = py - r*uy
+ *                         d2 = qx*qx + qy*qy                      a candidate needs d2 <= radius*radius
+ *                         hd = cs*ux + sn*uy;  hc = cs*uy - sn*ux
+ *                         max_sin < 1:                            a candidate needs hc*hc <= (max_sin*max_sin) * L2
+ *                         o = hd < 0 ? -1.0 : 1.0                 the edge is taken in the direction of travel
+ *                         s = (o*ux)*qy - (o*uy)*qx               > 0: the robot is to the left of the line
+ *                       sides == 1: a white edge needs s > 0 and a yellow edge s < 0 (s == 0 is on neither side); sides == 0: the
+ *                       sign of s is not tested.  The winner per colour is the candidate with the smallest (d2, i).
+ *   D  a winner         line_dist = sqrt(d2);  l = s / sqrt(L2);  line_d = l + offset_c (white_offset, yellow_offset);
+ *                       line_phi = atan2(-(o*hc), o*hd).  (th = 0.3 and an edge along +x: line_phi = 0.3.)
+ *   E  the lane pose    both colours found: d = (line_d[0] + line_d[1]) * 0.5, phi likewise, width = l_white - l_yellow; one
+ *                       found: its line_d and line_phi, width = 0; none: every double is 0 and every index -1.  status bit 0:
+ *                       white found, bit 1: yellow found; in_lane = status != 0 and |d| <= max_d.  res->n_posed: the frames with
+ *                       status != 0.
+ * The calling form is lf_map_polylines': a maintenance call on the map's stream, it waits once, a pending failing update is reported
+ * first, the map is untouched (and lf_map_lanes and lf_map_polylines on the same handle give their old bytes afterwards), an empty
+ * map gives LF_OK with zeros and -1s in poses and res filled in, poses is a device (on_device = 1) or host (0) array, frame_pose is
+ * a host array, and the replicas of a multi-GPU run agree without a collective.
+ * LF_ERR_BAD_ARG, touching nothing, the reason in lf_map_last_error: everything lf_map_polylines refuses of c->polylines; NULL c, res,
+ * frame_pose or poses; n_frames outside 1 .. 4096; a pose that is not finite; a radius that is not finite or <= 0; a max_sin outside
+ * 0 .. 1 or NaN; a white_offset or yellow_offset that is not finite; a max_d that is negative or NaN; min_vertices < 2; sides other
+ * than 0 or 1. */
+typedef struct lf_lane_pose_config {
+    lf_polylines_config polylines;  /* the polyline rule, as lf_map_polylines takes it */
+    double  radius;        /* metres, finite, > 0: a line's closest point is at most this far from the robot; default 0.5 */
+    double  max_sin;       /* 0 .. 1; 1: not tested: |sin| of the angle between heading and edge; default 0.75 */
+    double  white_offset;  /* metres, finite: the white line's lateral position relative to the lane centre, left positive;
+                              default -(0.23/2 + 0.05/2) = -0.14 (lanewidth, linewidth_white of the lane filter's default.yaml) */
+    double  yellow_offset; /* default +(0.23/2 + 0.025/2) = +0.1275 */
+    double  max_d;         /* metres, >= 0 or +inf: in_lane needs |d| <= max_d; default 0.115 */
+    int32_t min_vertices;  /* >= 2: polylines with fewer vertices give no edges; default 3 */
+    int32_t sides;         /* 1 (default): white counts only on the robot's right, yellow only on its left; 0: either side */
+} lf_lane_pose_config;
+typedef struct lf_map_lane_pose_record {   /* 96 bytes, one per frame (lf_lane_pose is the histogram filter's) */
+    double  d, phi, width;              /* the lane pose; width = distance between the two lines when both were found, else 0 */
+    double  line_d[2], line_phi[2], line_dist[2];   /* per colour 0 = white, 1 = yellow; 0 when not found */
+    int32_t vertex[2];                  /* the winning edge = index of its first vertex in polyline order; -1: none */
+    int32_t polyline[2];                /* its polyline; -1: none */
+    int32_t status;                     /* bit 0: white found, bit 1: yellow found */
+    int32_t in_lane;                    /* status != 0 and |d| <= max_d */
+} lf_map_lane_pose_record;
+typedef struct lf_lane_pose_result { lf_polylines_result polylines; int32_t n_edges[2]; int32_t n_posed, reserved_; } lf_lane_pose_result;
+LF_API int lf_sizeof_lane_pose_config(void);
+LF_API int lf_sizeof_lane_pose(void);
+LF_API int lf_sizeof_lane_pose_result(void);
+LF_API void lf_map_lane_pose_default_config(lf_lane_pose_config* c);
+LF_API int lf_map_lane_pose(lf_map* m, const lf_lane_pose_config* c, const double* frame_pose /* host [n_frames][3] */, int n_frames,
+                            lf_lane_pose_result* res, lf_map_lane_pose_record* poses /* [n_frames] */, int on_device);
+/* ms and launches accumulated since the previous call, with profiling on; resets them: [0] the polylines stages (one launch = one
+ * call's lanes, vertices and links), [1] edges + query.  Stages of their own: lf_map_polylines_timing and the other timing calls are
+ * unchanged. */
+LF_API int lf_map_lane_pose_timing(lf_map* m, double ms[2], int32_t launches[2]);
+
 /* ---- Histogram lane filter: lane pose from ground segments -----------------------------------------
  * LaneFilterHistogram (src/lane_filter/include/lane_filter/lane_filter.py:12-161) as lane_filter_node.processSegments
  * drives it (src/lane_filter/src/lane_filter_node.py:49-87): per frame predict(dt, v, w) -> update(segments) ->

@@ -52,6 +52,8 @@ EXPORTS = (
     "lf_sizeof_lanes_config", "lf_sizeof_lane", "lf_sizeof_lanes_result", "lf_map_lanes_default_config", "lf_map_lanes", "lf_map_lanes_timing",
     "lf_sizeof_polylines_config", "lf_sizeof_polyline_vertex", "lf_sizeof_polyline", "lf_sizeof_polylines_result",
     "lf_map_polylines_default_config", "lf_map_polylines", "lf_map_polylines_timing",
+    "lf_sizeof_lane_pose_config", "lf_sizeof_lane_pose", "lf_sizeof_lane_pose_result",
+    "lf_map_lane_pose_default_config", "lf_map_lane_pose", "lf_map_lane_pose_timing",
 )
 LF_ALIGN_OK, LF_ALIGN_FEW, LF_ALIGN_DEGENERATE, LF_ALIGN_REJECTED = 0, 1, 2, 3
 ALIGN_STATUS = ("ok", "few", "degenerate", "rejected")
@@ -280,6 +282,29 @@ class LfPolylinesResult(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("size", "n_lanes", "n_participating", "n_vertices", "n_polylines", "n_closed", "n_edges", "reserved_")]
 
 
+class LfLanePoseConfig(ctypes.Structure):
+    """ctypes mirror of `lf_lane_pose_config` (include/lanefront.h)."""
+    _fields_ = [("polylines", LfPolylinesConfig), ("radius", ctypes.c_double), ("max_sin", ctypes.c_double), ("white_offset", ctypes.c_double),
+                ("yellow_offset", ctypes.c_double), ("max_d", ctypes.c_double), ("min_vertices", ctypes.c_int32), ("sides", ctypes.c_int32)]
+
+
+class LfMapLanePose(ctypes.Structure):
+    """ctypes mirror of `lf_map_lane_pose_record` (include/lanefront.h); `LfLanePose` is the histogram filter's."""
+    _fields_ = [("d", ctypes.c_double), ("phi", ctypes.c_double), ("width", ctypes.c_double), ("line_d", ctypes.c_double * 2),
+                ("line_phi", ctypes.c_double * 2), ("line_dist", ctypes.c_double * 2), ("vertex", ctypes.c_int32 * 2),
+                ("polyline", ctypes.c_int32 * 2), ("status", ctypes.c_int32), ("in_lane", ctypes.c_int32)]
+
+
+# the same layout as a numpy record: what LineAssociator.lane_pose returns
+LANE_POSE_DTYPE = [("d", "<f8"), ("phi", "<f8"), ("width", "<f8"), ("line_d", "<f8", (2,)), ("line_phi", "<f8", (2,)), ("line_dist", "<f8", (2,)),
+                   ("vertex", "<i4", (2,)), ("polyline", "<i4", (2,)), ("status", "<i4"), ("in_lane", "<i4")]
+
+
+class LfLanePoseResult(ctypes.Structure):
+    """ctypes mirror of `lf_lane_pose_result` (include/lanefront.h)."""
+    _fields_ = [("polylines", LfPolylinesResult), ("n_edges", ctypes.c_int32 * 2), ("n_posed", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
+
+
 _lib = None
 
 
@@ -480,6 +505,15 @@ def load():
     lib.lf_map_polylines.restype = ci
     lib.lf_map_polylines_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
     lib.lf_map_polylines_timing.restype = ci
+    for f in ("lf_sizeof_lane_pose_config", "lf_sizeof_lane_pose", "lf_sizeof_lane_pose_result"):
+        getattr(lib, f).argtypes = []
+        getattr(lib, f).restype = ci
+    lib.lf_map_lane_pose_default_config.argtypes = [ctypes.POINTER(LfLanePoseConfig)]
+    lib.lf_map_lane_pose_default_config.restype = None
+    lib.lf_map_lane_pose.argtypes = [vp, ctypes.POINTER(LfLanePoseConfig), vp, ci, ctypes.POINTER(LfLanePoseResult), vp, ci]
+    lib.lf_map_lane_pose.restype = ci
+    lib.lf_map_lane_pose_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
+    lib.lf_map_lane_pose_timing.restype = ci
     lib.lf_descriptor_default_params.argtypes = [ctypes.POINTER(LfDescriptorParams)]
     lib.lf_descriptor_default_params.restype = None
     lib.lf_set_descriptor_params.argtypes = [vp, ctypes.POINTER(LfDescriptorParams)]

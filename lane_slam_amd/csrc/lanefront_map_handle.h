@@ -1,8 +1,9 @@
 // The live map's handle, for the translation units of lf_map_*: the map itself (lanefront_map.hip), its two views
 // (lanefront_map_render.hip, lanefront_map_camera.hip), the pose alignment (lanefront_map_align.hip) and the trajectory smoother
 // (lanefront_map_smooth.hip); the localisation without a prior pose (lanefront_map_localize.hip); the culling (lanefront_map_prune.hip);
-// the association gated by the prior pose (lanefront_map_near.hip); the lane lines (lanefront_map_lanes.hip) and their polylines
-// (lanefront_map_polylines.hip).  The last three share one index of the map, k_map_near.h's: build_index
+// the association gated by the prior pose (lanefront_map_near.hip); the lane lines (lanefront_map_lanes.hip), their polylines
+// (lanefront_map_polylines.hip) and the lane pose from them (lanefront_map_lane_pose.hip, which runs the polylines' stages through
+// queue_polylines, declared below).  The last four share one index of the map, k_map_near.h's: build_index
 // (lanefront_map_near.hip, declared below) is the only code that sizes, grows, fills and queues it.  The three pose solvers share one
 // front end (argument check, batch opener, prior-pose upload) and the two solving steps one body and, with
 // lf_map_step_host, one host-form wrapper: all of it lives in lanefront_map_align.hip and is declared at the end of this file.
@@ -13,6 +14,7 @@
 #include "lanefront_core.h"
 #include "k_map_align.h"
 #include "k_map_near.h"
+#include "k_map_polylines.h"
 
 namespace lf {
 
@@ -34,7 +36,15 @@ struct MapLanesState {
 struct MapPolylinesState {
     DevBuf lanes_work, lanes_counters, lane_of;              // k_map_lanes.h's Work and counters, and its lane_of [capacity]
     DevBuf work, counters, vertex_of, vertices, polylines;   // k_map_polylines.h's Work, carved from one buffer; a host caller's outputs staged
-    HostArray<int> h_counters;                               // pinned: the counters of k_map_lanes.h, then those of k_map_polylines.h
+    HostArray<int> h_counters;                               // pinned: kPolylinesCounters words (below)
+};
+
+// what lf_map_lane_pose keeps between calls (lanefront_map_lane_pose.hip): the polylines' two tables for the settled size, the edge
+// records carved from one buffer, the poses' x, y, cos, sin, a host caller's output staged.  The stages before them run in
+// MapPolylinesState's buffers
+struct MapLanePoseState {
+    DevBuf vertices, polylines, edges, pose, out;
+    std::vector<double> h_pose;
 };
 
 // what lf_map_render and lf_map_bounds keep between calls: every buffer grows on demand and is reused
@@ -76,6 +86,7 @@ enum MapStage {
     kMapNearIndexStage, kMapNearQueryStage,
     kMapLanesIndexStage, kMapLanesTableStage,
     kMapPolylinesLanesStage, kMapPolylinesVerticesStage, kMapPolylinesLinksStage,
+    kMapLanePosePolylinesStage, kMapLanePoseQueryStage,
     kMapStageCount
 };
 
@@ -113,6 +124,7 @@ struct lf_map : lf::Core {
     std::unique_ptr<lf::MapNearState> near;       // lf_map_associate_near (lanefront_map_near.hip), made by its first call
     std::unique_ptr<lf::MapLanesState> lanes;     // lf_map_lanes (lanefront_map_lanes.hip), made by its first call
     std::unique_ptr<lf::MapPolylinesState> polylines;   // lf_map_polylines (lanefront_map_polylines.hip), made by its first call
+    std::unique_ptr<lf::MapLanePoseState> lane_pose;    // lf_map_lane_pose (lanefront_map_lane_pose.hip), made by its first call
     std::unique_ptr<lf::MapPruneState> prune;     // lf_map_prune (lanefront_map_prune.hip), made by its first call
     std::unique_ptr<lf::MapRenderState> render;   // lf_map_render / lf_map_bounds (lanefront_map_render.hip), made by their first call
     std::unique_ptr<lf::MapCameraState> camera;   // lf_map_render_camera (lanefront_map_camera.hip), likewise
@@ -138,6 +150,20 @@ int take_stages(lf_map* m, int first, int n, double* ms, int32_t* launches);
 // rows), grows the four buffers, fills *ix, and queues the table's memset and nr::launch_near_index on the map's stream as one
 // launch of `stage` (stage < 0: inside the bracket the caller holds open).  bound == 0: *ix is empty and nothing is queued
 int build_index(lf_map* m, size_t bound, double cell, int stage, nr::Index* ix);
+
+// ---- the polylines' stages (lanefront_map_polylines.hip), for lf_map_polylines and lf_map_lane_pose
+// the device counters of one run: k_map_lanes.h's, then k_map_polylines.h's, then kTailCounters words of the caller's own
+constexpr int kTailCounters = 8;
+constexpr int kPolylinesCounters = ln::kNCounters + pl::kNCounters + kTailCounters;
+const char* polylines_bad_config(const lf_polylines_config* c);     // the reason lf_map_polylines refuses it with, or null
+lf::MapPolylinesState& polylines_state(lf_map* m);                   // made by the first call
+// Queue index, lanes, vertices, links and outputs for `bound` rows (settled_size) on the map's stream: the work arrays are
+// MapPolylinesState's, grown here, the tables are o's DEVICE arrays (each may be null).  All counters are zeroed first and stay on
+// the device: *counters is their address, for the caller's own kernels and its one copy into st.h_counters.  stages: the three
+// stages of the map's clock to bracket with, or null inside a bracket that the caller holds open.  No host wait
+int queue_polylines(lf_map* m, const lf_polylines_config* c, size_t bound, const pl::Out& o, const int* stages, int** counters);
+// behind the caller's wait: *res from st.h_counters; LF_ERR_CAPACITY (internal, cannot be) when a row found no slot
+int polylines_result(lf_map* m, const char* who, size_t bound, lf_polylines_result* res);
 
 // ---- a step's association (lanefront_map_near.hip): lf_map_associate of segs->code / segs->color, or, while lf_map_set_near holds a
 // configuration, lf_map_associate_near's rule with frame_pose (null: +0).  Device arrays; who: the exported call, for the error text

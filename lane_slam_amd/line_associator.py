@@ -25,6 +25,7 @@ LANE_BYTES = ctypes.sizeof(_lib.LfLane)
 Polylines = collections.namedtuple("Polylines", ("result", "vertex_of", "vertices", "polylines"))
 POLYLINE_VERTEX_BYTES = ctypes.sizeof(_lib.LfPolylineVertex)
 POLYLINE_BYTES = ctypes.sizeof(_lib.LfPolyline)
+LANE_POSE_BYTES = ctypes.sizeof(_lib.LfMapLanePose)
 
 
 class LineAssociator(object):
@@ -556,6 +557,70 @@ class LineAssociator(object):
         ms, ln = (ctypes.c_double * 3)(), (ctypes.c_int32 * 3)()
         self._check(self.lib.lf_map_polylines_timing(self.m, ms, ln))
         return {"lanes": (ms[0], ln[0]), "vertices": (ms[1], ln[1]), "links": (ms[2], ln[2])}
+
+    # ------------------------------------------------------------------ the lane pose from the polylines (lf_map_lane_pose)
+    @staticmethod
+    def lane_pose_config(**overrides):
+        """The library's default `_lib.LfLanePoseConfig` (lf_map_lane_pose_default_config) with the overrides applied: radius,
+        max_sin, white_offset, yellow_offset, max_d, min_vertices, sides, and the fields of polylines_config, which go to the
+        embedded polyline rule -- but for the lane rule's own `radius` and `max_sin`, which these names do not reach: set them with
+        lanes_radius and lanes_max_sin."""
+        c = _lib.LfLanePoseConfig()
+        _lib.load().lf_map_lane_pose_default_config(ctypes.byref(c))
+        for k, val in overrides.items():
+            name = k
+            places = ((c, _lib.LfLanePoseConfig._fields_), (c.polylines, _lib.LfPolylinesConfig._fields_), (c.polylines.lanes, _lib.LfLanesConfig._fields_))
+            if k in ("lanes_radius", "lanes_max_sin"):
+                name, places = k[len("lanes_"):], places[2:]
+            for where, fields in places:
+                kinds = dict((f, t) for f, t in fields if f not in ("reserved_", "lanes", "polylines"))
+                if name in kinds:
+                    setattr(where, name, int(val) if kinds[name] is ctypes.c_int32 else float(val))
+                    break
+            else:
+                raise TypeError("lane_pose_config: unknown field %r" % (k,))
+        return c
+
+    def _lane_pose(self, config, poses, out, on_device):
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        res = _lib.LfLanePoseResult()
+        self._check(self.lib.lf_map_lane_pose(self.m, ctypes.byref(config), poses.ctypes.data, len(poses), ctypes.byref(res), out, on_device))
+        r = {k: int(getattr(res.polylines, k)) for k, _ in _lib.LfPolylinesResult._fields_}
+        return {"polylines": r, "n_edges": (int(res.n_edges[0]), int(res.n_edges[1])), "n_posed": int(res.n_posed), "reserved_": int(res.reserved_)}
+
+    def lane_pose(self, poses, config=None):
+        """Where each pose is in its lane, from the map's polylines (lf_map_lane_pose; waits for the map's stream; the map is not
+        changed).  poses: (n_frames, 3) map-frame x, y, theta, as `align`, `smooth` and `localize` return them; config: an
+        `_lib.LfLanePoseConfig` (lane_pose_config).  Returns (result, poses_out): result is {'polylines': the polylines' result,
+        'n_edges': (white, yellow), 'n_posed', 'reserved_'}, poses_out a record array of `_lib.LANE_POSE_DTYPE`, one per frame:
+        d, phi, width, per colour (0 white, 1 yellow) line_d, line_phi, line_dist, vertex and polyline, status (bit 0 white found,
+        bit 1 yellow found) and in_lane."""
+        config = self.lane_pose_config() if config is None else config
+        n = np.asarray(poses).size // 3
+        out = np.zeros(max(1, n), _lib.LANE_POSE_DTYPE)
+        res = self._lane_pose(config, poses, out.ctypes.data, 0)
+        return res, out[:n]
+
+    def lane_pose_device(self, poses, config=None, out=None):
+        """`lane_pose` with the output in device memory: out is a contiguous torch uint8 (n_frames, 96) tensor on the map's device,
+        one lf_map_lane_pose_record (`_lib.LANE_POSE_DTYPE`) per row, which the library writes in place (None: a new one).  poses
+        stay a host array.  Returns (result, out)."""
+        import torch
+        config = self.lane_pose_config() if config is None else config
+        n = np.asarray(poses).size // 3
+        if out is None:
+            out = torch.empty((max(1, n), LANE_POSE_BYTES), dtype=torch.uint8, device=torch.device("cuda", self._device))
+        elif out.dtype != torch.uint8 or out.dim() != 2 or out.shape[1] != LANE_POSE_BYTES or out.shape[0] < n or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("lane_pose_device: out is a contiguous (n_frames, %d) uint8 device tensor" % LANE_POSE_BYTES)
+        res = self._lane_pose(config, poses, out.data_ptr(), 1)
+        return res, out
+
+    def lane_pose_timing(self):
+        """{'polylines': (ms, launches), 'query': (ms, launches)} of the `lane_pose` calls since the previous call (needs
+        set_profiling(True)): the polylines' stages (lanes, vertices, links) as one, and edges + query."""
+        ms, ln = (ctypes.c_double * 2)(), (ctypes.c_int32 * 2)()
+        self._check(self.lib.lf_map_lane_pose_timing(self.m, ms, ln))
+        return {"polylines": (ms[0], ln[0]), "query": (ms[1], ln[1])}
 
     @staticmethod
     def carry(poses, last_odometry, last_corrected):

@@ -53,6 +53,16 @@ def compressed_image_message(header, jpg_bytes):
     return bytes(header) + struct.pack("<I", len(fmt)) + fmt + struct.pack("<I", len(data)) + data
 
 
+LANE_POSE_NORMAL, LANE_POSE_ERROR = 0, 1
+
+
+def lane_pose_message(header, d, phi, in_lane, sigma_d=0.0, sigma_phi=0.0, status=LANE_POSE_NORMAL):
+    """The serialised duckietown_msgs/LanePose (ref: src/duckietown_msgs/msg/LanePose.msg:1-7) that lane_filter_node publishes:
+    header_bytes(...) + f32 d | f32 sigma_d | f32 phi | f32 sigma_phi | i32 status | bool in_lane (one byte, 0 or 1), in the message's
+    field order.  d, phi and in_lane: e.g. one record of LineAssociator.lane_pose or one pose of the histogram filter."""
+    return bytes(header) + struct.pack("<ffffiB", float(d), float(sigma_d), float(phi), float(sigma_phi), int(status), 1 if in_lane else 0)
+
+
 def split_segment_list(msg):
     """(seq, secs, nsecs, frame_id, body bytes, records view) of a serialised SegmentList."""
     msg = bytes(msg)

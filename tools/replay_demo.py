@@ -7,7 +7,7 @@ wire bodies.  The first batch is checked against the oracle (pixels, segments, m
     python tools/replay_demo.py [--frames 1024] [--batch 128] [--threads 32] [--geometry fullres|parity] [--map-jpeg map.jpg]
                                 [--overlay-jpeg DIR] [--align | --smooth | --localize] [--prune EVERY[:min_hits[:age]]]
                                 [--near RADIUS[:max_offset[:max_sin]]] [--lanes RADIUS[:max_offset[:max_sin[:min_entries]]]]
-                                [--polylines CELL[:max_gap[:reach]]]
+                                [--polylines CELL[:max_gap[:reach]]] [--lane-pose RADIUS[:max_sin]] [--lane-filter]
 
 --map-jpeg writes the final map as the reference's README shows it (show_map's coloured segments seen from above, lf_map_render
 fitted to the map) as a JPEG: rendered and encoded on the device, only the file's bytes cross the bus.
@@ -26,6 +26,11 @@ to the library's) and prints one line per lane -- number, colour, entries, hits,
 --polylines CELL[:max_gap[:reach]] orders each lane line of the final map into polylines (lf_map_polylines; the lane rule is
 --lanes' fields, or the library's; the fields left out default to the library's) and prints one line per polyline -- number, lane,
 vertices, closed or open, entries, hits, both ends, length.
+--lane-pose RADIUS[:max_sin] asks the map, behind every batch's update, where the poses that the step used are in their lane
+(lf_map_lane_pose; the polyline and lane rules are --polylines' and --lanes' fields, or the library's) and prints per batch the frames
+with a pose, the frames in lane, the median d and phi of the posed frames and the last frame's (d, phi, in_lane).  --lane-filter
+runs the histogram lane filter (lf_lane_filter_*, the reference's default configuration, no odometry: update only) over the same
+batches' segments; with both flags the filter's values stand beside the map's: two independent paths to the same two numbers.
 """
 import argparse, io, os, sys, time
 import numpy as np
@@ -70,7 +75,19 @@ ap.add_argument("--lanes", default=None, metavar="RADIUS[:max_offset[:max_sin[:m
 ap.add_argument("--polylines", default=None, metavar="CELL[:max_gap[:reach]]",
                 help="after the replay, order each lane line of the map into polylines (lf_map_polylines, the lane rule from --lanes' fields) "
                      "and print one line per polyline")
+ap.add_argument("--lane-pose", default=None, metavar="RADIUS[:max_sin]",
+                help="behind every batch's update, the lane pose of the poses the step used, from the map's polylines (lf_map_lane_pose, the "
+                     "rules from --polylines' and --lanes' fields); prints one line per batch")
+ap.add_argument("--lane-filter", action="store_true",
+                help="run the histogram lane filter over every batch's segments (update only: the replay has no odometry) and print its last "
+                     "frame's (d, phi, in_lane) per batch, beside --lane-pose's when both are given")
 args = ap.parse_args()
+lane_pose_fields = None
+if args.lane_pose:
+    parts = [float(v) for v in args.lane_pose.split(":")]
+    if not 1 <= len(parts) <= 2:
+        ap.error("--lane-pose takes RADIUS[:max_sin]")
+    lane_pose_fields = dict(zip(("radius", "max_sin"), parts))
 polylines_fields = None
 if args.polylines:
     parts = args.polylines.split(":")
@@ -142,6 +159,14 @@ if near_fields:
         # the same stream into a second map without the gate, for the share of ok frames on both sides
         shadow = LineAssociator(capacity=args.map + 65536, policy="append", kept_only=True)
         shadow.seed(synth.random_codes(args.map, 1234))
+lane_pose_cfg = lane_filter = None
+if lane_pose_fields:
+    # (the lane rule's radius and max_sin go by the names lanes_radius and lanes_max_sin: LineAssociator.lane_pose_config)
+    rules = dict(polylines_fields or {}, **{("lanes_" + k if k in ("radius", "max_sin") else k): v for k, v in (lanes_fields or {}).items()})
+    lane_pose_cfg = live.lane_pose_config(**dict(rules, **lane_pose_fields))
+if args.lane_filter:
+    from lane_slam_amd.lane_filter import DEFAULT_CONFIGURATION, LaneFilterBatch, UPDATE
+    lane_filter = LaneFilterBatch(DEFAULT_CONFIGURATION, n_streams=1, max_frames=B)
 n_near_sum = 0
 ok_frames, used_endpoints, all_frames = [0, 0], [0, 0], 0
 t0 = time.perf_counter()
@@ -150,6 +175,7 @@ last_odometry = last_corrected = (0.0, 0.0, 0.0)
 for b0 in range(0, args.frames - B + 1, B):
     fe.decode_jpeg_batch(msgs[b0:b0 + B], n_threads=args.threads, device_ptr=dev_frames)
     seg = fe.process_batch(dev_frames, n_frames=B)
+    used_poses = np.zeros((B, 3))
     if seg.n:
         d = {k: torch.from_numpy(np.ascontiguousarray(getattr(seg, k))).cuda() for k in ("frame_offset", "code", "color", "keep", "ground")}
         di = torch.zeros(seg.n, dtype=torch.int32, device="cuda")
@@ -170,6 +196,7 @@ for b0 in range(0, args.frames - B + 1, B):
             poses = LineAssociator.carry(np.zeros((B, 3)), last_odometry, last_corrected)
             out = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=poses, step=b0 // B, smooth=live.smooth_config())
             last_odometry, last_corrected = (0.0, 0.0, 0.0), tuple(out[2][-1])
+            used_poses = np.asarray(out[2], np.float64)
             counts = np.bincount(out[3]["status"], minlength=4)
             print("batch %d smoothed: %s" % (b0 // B, ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, counts))))
         elif args.localize:
@@ -179,6 +206,7 @@ for b0 in range(0, args.frames - B + 1, B):
             located, loc = live.localize_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), fallback=np.tile(last_corrected, (B, 1)))
             out = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=located, step=b0 // B, align=live.align_config())
             last_corrected = tuple(out[2][-1])
+            used_poses = np.asarray(out[2], np.float64)
             counts, found = np.bincount(loc["status"], minlength=4), loc["n_inliers"][loc["status"] == 0]
             print("batch %d localised: %s; inliers of the ok frames %s; aligned: %s"
                   % (b0 // B, ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, counts)),
@@ -186,8 +214,9 @@ for b0 in range(0, args.frames - B + 1, B):
                      ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, np.bincount(out[3]["status"], minlength=4)))))
         elif args.align:
             # (the replay has no odometry: every prior is the identity, and the seeded map has no geometry to align with)
-            res = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=np.zeros((B, 3)), step=b0 // B,
-                                   align=live.align_config())[3]
+            out = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=np.zeros((B, 3)), step=b0 // B,
+                                   align=live.align_config())
+            res, used_poses = out[3], np.asarray(out[2], np.float64)
             counts = np.bincount(res["status"], minlength=4)
             print("batch %d aligned: %s" % (b0 // B, ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, counts))))
             all_frames += B
@@ -209,6 +238,18 @@ for b0 in range(0, args.frames - B + 1, B):
             print("step %d pruned: %d -> %d entries (weak %d, covered %d)" % (step, r["size_before"], r["size_after"], r["dropped"]["weak"], r["dropped"]["covered"]))
         n_matched += int((di >= 0).sum().item())
         n_kept += int(seg.keep.sum())
+    told = []
+    if lane_pose_cfg is not None:
+        lres, lp = live.lane_pose(used_poses, lane_pose_cfg)
+        posed = lp[lp["status"] != 0]
+        told.append("map: %d of %d frames posed (%d white, %d yellow edges), %d in lane, median d %+.4f m phi %+.4f rad, last frame (d %+.4f, phi %+.4f, in_lane %d)"
+                    % (lres["n_posed"], B, lres["n_edges"][0], lres["n_edges"][1], int(lp["in_lane"].sum()),
+                       np.median(posed["d"]) if len(posed) else 0.0, np.median(posed["phi"]) if len(posed) else 0.0, lp["d"][-1], lp["phi"][-1], lp["in_lane"][-1]))
+    if lane_filter is not None:
+        fp = lane_filter.step(seg, np.zeros((B, 3)), phases=UPDATE)["poses"]
+        told.append("filter: last frame (d %+.4f, phi %+.4f, in_lane %d), %d votes" % (fp["d"][-1], fp["phi"][-1], fp["in_lane"][-1], int(fp["n_votes"].sum())))
+    if told:
+        print("batch %d lane pose: %s" % (b0 // B, " | ".join(told)))
     for stage in (sm.DETECTOR, sm.GROUND, sm.FILTERED):
         bodies, off = sm.serialize_segments(fe, seg, stage)
         wire += bodies.size
