@@ -249,6 +249,8 @@ LF_API int lf_get_dense_params(const lf_handle* h, lf_dense_params* p);
  *                    by search radius, then substring, then the position of the differing bits in its enumeration
  *                    (:681-741), then train index.  Costs a second matrix pass that ranks only the ties (k_assoc_ties.hip).
  *                    THE DEFAULT of lf_associate and of the live map (lf_map_*): it is what BinaryDescriptorMatcher::match returns.
+ *                    At most 261 888 queries per call (lf_associate, lf_map_associate): more is LF_ERR_UNSUPPORTED, nothing is
+ *                    queued and the handle goes on working; LF_TIE_LOWEST has no such limit.
  *   LF_TIE_LOWEST    the lowest map index; one pass (an A/B option; the default of the live map until round 4).
  */
 #define LF_TIE_LOWEST 0
@@ -1672,6 +1674,11 @@ LF_API int lf_debug_segments(lf_handle* h, int mode, int n_frames, const int32_t
  * device (the sparse form keeps only the non-zero keys): the elements with a non-zero key come first, in std::sort's order, the
  * zero-key ones follow by index (std::sort leaves them behind the others too, in an order nothing observes) */
 LF_API int lf_debug_std_sort(lf_handle* h, const int32_t* keys, int n, int32_t* order);
+/* how lf_associate / lf_map_associate lay out an association of nq queries against nm map rows (1 <= nq, 1 <= nm <= 2^21; no
+ * handle, no device): out = { small shape (nq <= 12288: 128 queries per workgroup; else 256), queries per workgroup, workgroup
+ * columns, map chunks, rows per chunk, map rows padded to 64 }.  Both passes take this one plan; the tests assert through it
+ * that their sizes reach the kernel form and the chunk length they were written for.  LF_ERR_BAD_ARG outside the ranges */
+LF_API int lf_debug_assoc_plan(int nq, int nm, int32_t out[6]);
 /* scaled LSD image size for this handle */
 LF_API int lf_lsd_size(const lf_handle* h, int* rows, int* cols);
 /* How many batches (handles) a caller should keep in flight for the content this handle saw last: region growing is a chain

@@ -211,6 +211,54 @@ void launch_lbd(int Hc, int W, int n_seg_cap, const int* n_seg, const float* lin
 int lbd_max_width_of_band();
 // ---- associator (k_assoc.hip): packed operands = [rows][128] e2m1 code nibbles (+ [rows][32] colour rows when gated)
 size_t assoc_rows_padded_m(int nm);
+// The shape and the split of one association, the ONE place both passes (launch_assoc_core, launch_assoc_ties) take them from;
+// pure host arithmetic (lf_debug_assoc_plan shows it to the tests: tests/test_assoc_plan_cpu.py, tests/test_gpu_assoc_shapes.py).
+#ifndef LF_ASSOC_SMALL_MAX
+#define LF_ASSOC_SMALL_MAX 12288
+#endif
+constexpr int kAssocSmallMax = LF_ASSOC_SMALL_MAX;   // associations of up to this many queries take the small shape
+constexpr int kAssocTileRows = 64;                   // map entries per LDS tile
+constexpr int kMaxBlocksPerChunk = 512;              // the in-accumulator block counter t has 9 bits: 512 blocks of 32 columns
+constexpr int kAssocMaxSplits = 128;                 // chunks the tie pass takes (its s_items)
+struct AssocPlan {
+    bool small;       // 128 queries per workgroup (one row block per wave); big: 256
+    int qw;           // queries per workgroup of the distance pass
+    int qblocks;      // its workgroup columns, ceil(nq / qw)
+    int splits;       // map chunks (its workgroup rows), none empty
+    int m_chunk;      // rows per chunk, whole tiles, at most kMaxBlocksPerChunk * 32
+    int nm_pad;       // the map's rows padded to whole tiles
+    int qblocks256() const { return small ? (qblocks + 1) / 2 : qblocks; }      // what the scratch sizes and the tie pass count in
+};
+inline AssocPlan assoc_plan(int nq, int nm)
+{
+    AssocPlan p;
+    p.nm_pad = (int)(((size_t)nm + kAssocTileRows - 1) / kAssocTileRows * kAssocTileRows);
+    const int tiles = p.nm_pad / kAssocTileRows;
+    const int min_splits = (p.nm_pad + (kMaxBlocksPerChunk * 32) - 1) / (kMaxBlocksPerChunk * 32);
+    // The shape: big = 256 queries per workgroup (two row blocks per wave, six tile buffers: 54 KB, 239 registers -- the fastest alone);
+    // small = 128 (one row block, three buffers: 29 KB, ~160 registers -- the one that finds room beside other batches' region growing).
+    // Small up to kAssocSmallMax queries (the pipelined front end's batches), big beyond.
+    p.small = nq <= kAssocSmallMax;
+    p.qw = p.small ? 128 : 256;
+    p.qblocks = (nq + p.qw - 1) / p.qw;
+    // 2 workgroups are resident per CU: split the map so that the grid is one round of the 512 slots -- long chunks
+    // amortise the query expansion and the final cross-lane reduction (measured: 512 > 1024 > 768 > 256); the small shape: 3 per CU
+    const int slots = p.small ? 1024 : 512;
+    int splits = p.qblocks > 0 ? slots / p.qblocks : kAssocMaxSplits;
+    if (splits > kAssocMaxSplits) splits = kAssocMaxSplits;   // one or two query blocks: more, shorter chunks only lengthen the merge (32 -> 19 us at 256 x 50 000)
+    if (splits < min_splits) splits = min_splits;
+    if (splits > tiles) splits = tiles;
+    if (splits < 1) splits = 1;
+    p.m_chunk = (tiles + splits - 1) / splits * kAssocTileRows;
+    p.splits = (p.nm_pad + p.m_chunk - 1) / p.m_chunk;
+    return p;
+}
+// the tie pass keeps a chunk's running piece counts (four per 256-query block, and the total) in one of its tile buffers
+inline bool assoc_ties_fit(const AssocPlan& p)
+{
+    const size_t tgroup = p.small ? 1 : 2;
+    return p.splits <= kAssocMaxSplits && (size_t)p.qblocks256() * 4 + 1 <= tgroup * 8192 / 4;
+}
 // Packed map operand layout: one e2m1 nibble per code bit, 128 bytes per map row, blocked by the associator's 64-row LDS tile,
 // [8 KB tile][16-byte chunk][row][16 B]: byte `byte` (0..127) of map row `row` lives at
 __host__ __device__ inline size_t assoc_map_offset_fp4(size_t row, int byte)

@@ -19,6 +19,9 @@
 //       codes into registers, map chunk streamed by LDS-DMA through tile buffers, hand-scheduled tile loop (k_assoc_loop.inc,
 //       tools/gen_assoc_loop.py), per-chunk key rows written through and merged by the last workgroup to arrive; ties
 //       resolve to the lowest map index.  Algorithmic ops: 2*N*M*256.
+//       Tests: tests/test_gpu_assoc_shapes.py launches the four forms (small / big x ungated / gated), and the four of the tie
+//       pass, each at the plan it asserts through lf_debug_assoc_plan -- every value 0 .. 511 of t on both shapes, the carries
+//       between its octal digits, the distance, padding, gating and max_distance edges; tests/test_assoc_plan_cpu.py the plan.
 //   k_assoc_float (+ k_sqnorm72, k_assoc_float_finish, k_assoc_float_exact, k_assoc_float_exact_merge): 72-d float LBD, Euclidean;
 //       the search on v_mfma_f32_32x32x2_f32 ranks, fp64 direct sums give the distance and decide what it cannot (below).
 #include <cstdio>
@@ -42,12 +45,8 @@ __device__ unsigned long long g_assoc_stamps[8 * 8192];
 #define LF_STAMP(k) do { } while (0)
 #endif
 constexpr int AQW = 256;      // queries per workgroup (4 waves x 64)
-constexpr int AM = 64;         // map entries per LDS tile
-constexpr int kMaxBlocksPerChunk = 512;   // the in-accumulator block counter t has 9 bits
-#ifndef LF_ASSOC_SMALL_MAX
-#define LF_ASSOC_SMALL_MAX 12288
-#endif
-constexpr int kAssocSmallMax = LF_ASSOC_SMALL_MAX;   // associations of up to this many queries take the small shape (launch_assoc_core)
+constexpr int AM = kAssocTileRows;         // map entries per LDS tile
+// (kMaxBlocksPerChunk, the nine bits of the block counter t, and kAssocSmallMax, the shape threshold: common.h, assoc_plan)
 
 // Packs map rows for lf_associate's raw-map form (the live map keeps its rows packed: k_map.hip).  One thread per
 // (row, code byte): one e2m1 nibble per bit (padding rows: zeros = the value 0.0, "distance 128").
@@ -404,27 +403,14 @@ void launch_assoc_pack_map(const uint8_t* codes, int n, int n_pad, int8_t* x, hi
 hipError_t launch_assoc_core(const uint8_t* q, const uint8_t* qcolor, int nq, const int8_t* mx, const int8_t* mcx, int nm,
                        const int* nm_dev, int gating, int max_distance, AssocScratch& w, int32_t* idx, float* dist, hipStream_t s)
 {
-    const int nm_pad = (int)assoc_rows_padded_m(nm);
-    const int tiles = nm_pad / AM;
-    const int min_splits = (nm_pad + (kMaxBlocksPerChunk * 32) - 1) / (kMaxBlocksPerChunk * 32);
-    // The shape: big = 256 queries per workgroup (two row blocks per wave, six tile buffers: 54 KB, 239 registers -- the fastest alone);
-    // small = 128 (one row block, three buffers: 29 KB, ~160 registers -- the one that finds room beside other batches' region growing).
-    // Small up to kAssocSmallMax queries (the pipelined front end's batches), big beyond.
-    const bool small = nq <= kAssocSmallMax;
-    const int qw = small ? AQW / 2 : AQW;
-    const int qblocks = (nq + qw - 1) / qw;
-    // 2 workgroups are resident per CU: split the map so that the grid is one round of the 512 slots -- long chunks
-    // amortise the query expansion and the final cross-lane reduction (measured: 512 > 1024 > 768 > 256); the small shape: 3 per CU
-    const int slots = small ? 1024 : 512;
-    int splits = slots / qblocks;
-    if (splits > 128) splits = 128;            // one or two query blocks: more, shorter chunks only lengthen the merge (32 -> 19 us at 256 x 50 000)
-    if (splits < min_splits) splits = min_splits;
-    if (splits > tiles) splits = tiles;
-    if (splits < 1) splits = 1;
-    const int m_chunk = (tiles + splits - 1) / splits * AM;
-    splits = (nm_pad + m_chunk - 1) / m_chunk;
-    const int qblocks256 = (nq + AQW - 1) / AQW;                   // what the scratch sizes and the tie pass count in
-    hipError_t e = assoc_scratch_reserve(w, (size_t)qblocks256, (size_t)splits, (size_t)qblocks, s);
+    // the shape (small / big) and the split of the map: assoc_plan (common.h), the same plan the tie pass takes
+    const AssocPlan plan = assoc_plan(nq, nm);
+    const bool small = plan.small;
+    const int nm_pad = plan.nm_pad, qblocks = plan.qblocks, splits = plan.splits, m_chunk = plan.m_chunk;
+    const int qblocks256 = plan.qblocks256();                      // what the scratch sizes and the tie pass count in
+    // (a tie pass is to follow and could not take this plan: nothing is queued -- the API's entries refuse such a size before they get here)
+    if (w.tie_res && !assoc_ties_fit(plan)) return hipErrorInvalidValue;
+    hipError_t e =assoc_scratch_reserve(w, (size_t)qblocks256, (size_t)splits, (size_t)qblocks, s);
     if (e != hipSuccess) return e;
     w.qblocks = qblocks256; w.splits = splits; w.m_chunk = m_chunk;
     // the tie pass's lists are written by this launch's merge step when the caller asked for them (w.tie_res: the result words)

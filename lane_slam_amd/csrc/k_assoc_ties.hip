@@ -307,15 +307,17 @@ hipError_t launch_assoc_ties(const uint8_t* q, const uint8_t* qcolor, int nq, co
                              int nm, const int* nm_dev, int gating, AssocScratch& w, unsigned long long* res, int32_t* idx, const float* dist, hipStream_t s)
 {
     if (nq <= 0 || nm <= 0) return hipSuccess;
-    const int nm_pad = (int)assoc_rows_padded_m(nm);
-    const int qblocks = (nq + 255) / 256;                                   // the distance pass's query blocks (256 queries each)
-    const int splits = w.splits, m_chunk = w.m_chunk;                      // the distance pass's split of the map: its lists are laid out by it
-    // the distance pass must have been launched with w.tie_res = res: its merge step wrote the lists and reset the result words
-    if (splits < 1 || splits > 128 || w.qblocks != qblocks || w.tie_res != res || !w.tie_list) return hipErrorInvalidValue;
-    // the shape: SMALL up to 12 288 queries (a front end's batch: the pass must find room between other kernels), BIG beyond
-    const bool small = nq <= 12288;
+    // the distance pass's plan (assoc_plan, common.h): its split of the map lays the lists out, its shape is this pass's
+    const AssocPlan plan = assoc_plan(nq, nm);
+    const int nm_pad = plan.nm_pad;
+    const int qblocks = plan.qblocks256();                                  // the distance pass's query blocks (256 queries each)
+    const int splits = plan.splits, m_chunk = plan.m_chunk;
+    // the distance pass must have been launched with w.tie_res = res, for these sizes: its merge step wrote the lists and reset the result words
+    if (splits < 1 || w.splits != splits || w.m_chunk != m_chunk || w.qblocks != qblocks || w.tie_res != res || !w.tie_list) return hipErrorInvalidValue;
+    // the shape: SMALL up to kAssocSmallMax queries (a front end's batch: the pass must find room between other kernels), BIG beyond
+    const bool small = plan.small;
     const int trb = small ? 1 : 2, tgroup = small ? 1 : 2;
-    if ((size_t)qblocks * 4 + 1 > (size_t)tgroup * 8192 / 4) return hipErrorInvalidValue;      // (the running piece counts of a chunk sit in one tile buffer)
+    if (!assoc_ties_fit(plan)) return hipErrorInvalidValue;      // (at most 128 chunks; the running piece counts of a chunk sit in one tile buffer)
     const int n_pieces = qblocks * 4;
     const int* pieces = w.tie_list;
     const int* counts = w.tie_list + (size_t)splits * n_pieces * 64;

@@ -255,3 +255,13 @@ extern "C" int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t byt
     if (bytes > avail) { lf_set_error(h, LF_ERR_CAPACITY, "buffer %d holds %zu bytes, %zu requested", buffer_id, avail, bytes); return LF_ERR_CAPACITY; }
     return fetch(h, { { dst, src, bytes } });
 }
+
+// The associator's plan for nq queries against nm map rows (assoc_plan, common.h: what launch_assoc_core and launch_assoc_ties
+// both take): pure host arithmetic, no handle, no device.
+extern "C" int lf_debug_assoc_plan(int nq, int nm, int32_t out[6])
+{
+    if (!out || nq < 1 || nm < 1 || nm > (1 << 21)) return LF_ERR_BAD_ARG;
+    const AssocPlan p = assoc_plan(nq, nm);
+    out[0] = p.small ? 1 : 0; out[1] = p.qw; out[2] = p.qblocks; out[3] = p.splits; out[4] = p.m_chunk; out[5] = p.nm_pad;
+    return LF_OK;
+}

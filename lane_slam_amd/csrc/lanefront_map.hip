@@ -267,6 +267,11 @@ extern "C" int lf_map_associate(lf_map* m, lf_handle* h, const uint8_t* code32, 
     long long bound = (long long)m->h_state[0] + (m->state_pending ? m->rows_in_flight : 0);
     if (bound > m->cfg.capacity) bound = m->cfg.capacity;
     const int size = (int)bound;
+    // the tie pass has room for 1023 blocks of 256 queries (k_assoc_ties.hip); refused here, before anything is queued
+    if (m->tie_rule == LF_TIE_MIHASHER && size > 0 && !assoc_ties_fit(assoc_plan(n, size))) {
+        set_error(m, LF_ERR_UNSUPPORTED, "lf_map_associate: %d queries are more than the tie pass of LF_TIE_MIHASHER takes (261888): split the batch or use LF_TIE_LOWEST", n);
+        return LF_ERR_UNSUPPORTED;
+    }
     if ((rc = after_handle(m, h)) != LF_OK) return rc;
     hipStream_t s = m->stream;
     Staging st(m);

@@ -29,6 +29,11 @@ extern "C" int lf_associate(lf_handle* h, const uint8_t* query32, int nq, const 
     if (nq < 0 || nm < 0 || (nq > 0 && (!query32 || !idx || !dist)) || (nm > 0 && !map32)) { lf_set_error(h, LF_ERR_BAD_ARG, "lf_associate: bad argument"); return LF_ERR_BAD_ARG; }
     if (nm > (1 << 21)) { lf_set_error(h, LF_ERR_UNSUPPORTED, "map larger than 2^21 entries"); return LF_ERR_UNSUPPORTED; }
     if (nq == 0) return LF_OK;
+    // the tie pass has room for 1023 blocks of 256 queries (k_assoc_ties.hip); refused here, before anything is queued
+    if (h->tie_rule == LF_TIE_MIHASHER && nm > 0 && !assoc_ties_fit(assoc_plan(nq, nm))) {
+        lf_set_error(h, LF_ERR_UNSUPPORTED, "lf_associate: %d queries are more than the tie pass of LF_TIE_MIHASHER takes (261888): split the batch or use LF_TIE_LOWEST", nq);
+        return LF_ERR_UNSUPPORTED;
+    }
     LF_HIP_CHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     if (nm == 0) {

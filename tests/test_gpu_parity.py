@@ -601,8 +601,9 @@ def test_configuration_variants(variant):
 
 @pytest.mark.gpu
 def test_associate_large_map_and_many_ties():
-    """Maps beyond 4096 column blocks per workgroup chunk (the in-accumulator block counter has 12 bits, so the
-    launcher must split them) and heavy duplication: ties must resolve to the lowest map index everywhere."""
+    """Maps beyond 512 column blocks (16 384 rows) per workgroup chunk (the in-accumulator block counter has nine bits, so
+    the launcher must split them) and heavy duplication: ties must resolve to the lowest map index everywhere.  (The
+    counter's upper values: tests/test_gpu_assoc_shapes.py.)"""
     from oracle.oracle import Oracle
     o = Oracle(default_config("parity"))
     fe = FrontEnd(default_config("parity"))
