@@ -1198,6 +1198,123 @@ LF_API int lf_map_lane_pose(lf_map* m, const lf_lane_pose_config* c, const doubl
  * unchanged. */
 LF_API int lf_map_lane_pose_timing(lf_map* m, double ms[2], int32_t launches[2]);
 
+/* ---- loop closures: a pose graph solved on the device, the map moved with it: lf_map_graph_solve, lf_map_correct ----
+ * lf_map_localize gives the pose of the current frame in a part of the map that was drawn a lap ago; lf_map_smooth is a block
+ * tridiagonal solve over consecutive frames of one batch, into which an edge between two far-apart poses does not fit, and a map
+ * entry's endpoints stay where drifting odometry put them.  The reference's README names "a pose graph with loop-closure
+ * constraints" among its future improvements (the sentence the smoother's comment cites); nothing of it is in the reference, so
+ * these two calls are the package's OWN contract, written so that a sequential restatement (tests/map_graph_ref.py) and the
+ * kernels (k_map_graph.hip) agree bit for bit.  lf_map_graph_solve spreads a discrepancy over a trajectory of KEY poses;
+ * lf_map_correct moves every map entry by the rigid correction of the key pose that observed it.
+ *
+ * lf_map_graph_solve: a general SE(2) pose graph.  Edges are given by node index, so odometry and loop closures are the same
+ * thing.  Gauss-Newton, with block-Jacobi preconditioned conjugate gradients as the linear solver.  The call runs on the map's
+ * stream in call order; it reads nothing of the map and changes nothing of it.  All f64, unfused, in the order written here; sin,
+ * cos and sqrt as in lf_map_align, "finite" likewise.
+ *
+ *   iterate           (x, y, th) per node, at first pose[3 i ..] = (x0, y0, th0).
+ *   edge k            from i = edge_ij[2 k] to j = edge_ij[2 k + 1] with z = edge_z[3 k ..] and W = diag(w0, w1, w2) = edge_w[3 k ..]:
+ *                     lf_map_smooth's edge with z given instead of derived.  (s, c) = sin, cos of th_i;  ux = x_j - x_i, uy = y_j -
+ *                     y_i;  px = c ux + s uy, py = (-s) ux + c uy;  e = (px - zx, py - zy, wrap((th_j - th_i) - zt)),
+ *                     wrap(a) = a - TWO_PI rint(a / TWO_PI), TWO_PI = 0x1.921fb54442d18p+2, rint to nearest even (odometry's theta
+ *                     is not wrapped, and a loop is closed a whole turn later).  Jf (with respect to node i) and Jn (node j) are
+ *                     lf_map_smooth's, and so are A^T W B and A^T W e, term for term.
+ *   chi-square        s = ((w0 e0) e0 + (w1 e1) e1) + (w2 e2) e2.  robust[k] != 0 and s > huber huber: rho = huber / sqrt(s), else
+ *                     rho = 1;  then w0 = w0 rho, w1 = w1 rho, w2 = w2 rho (rho = 1 included) in everything below.  The edge's cost
+ *                     term is rho s.  The coupling C_k = Jf^T W Jn, all nine values.
+ *   adjacency         a node's incident edges are those with i or j equal to it, in increasing k; a multi-edge once per copy.
+ *   node i            D (symmetric 3 x 3, only its upper triangle 00 01 02 11 12 22) and b (3) start at +0, a FREE node's D00, D11,
+ *                     D22 at `damping`.  Over the incident edges in increasing k:  the node is the edge's i: D += Jf^T W Jf, b -=
+ *                     Jf^T W e;  it is the edge's j: D += Jn^T W Jn, b -= Jn^T W e  (X += M is X = X + M, entry by entry).  A free
+ *                     node's D is factored once per Gauss-Newton step by solve3's LDL^T with its pivot test; solve3(D, v) below
+ *                     applies that factor (lf_map_smooth's solve3; a t that is not finite does not fail here, the sums catch it).
+ *                     One failing pivot: the call is LF_ALIGN_DEGENERATE, it stops and keeps the iterate it had.
+ *   fixed             fixed[i] != 0 (NULL: node 0 only): the node takes no step; its r, z, p and t are +0 throughout, its D is not
+ *                     factored, and it takes part in the products and the sums like any other node.
+ *   sums              dot(a, v) over nodes: 1024 partials, all +0; node i adds (a0 v0 + a1 v1) + a2 v2 to partial i mod 1024, in
+ *                     increasing i; then s[l] = s[l] + s[l + h] for l < h, h = 512, 256, .., 1; s[0] is the sum.  The cost is the
+ *                     same sum of the edges' terms, edge k to partial k mod 1024.
+ *   CG                per Gauss-Newton step:  t = +0, r = b, z_i = solve3(D_i, r_i), p = z, rz = rz0 = dot(r, z).  rz0 == 0: the
+ *                     step is t = +0 and is accepted.  Else iterations n = 1, 2, ..:
+ *                     (1) q_i = D_i p_i as three rows, q[0] = (D00 p0 + D01 p1) + D02 p2, q[1] = (D01 p0 + D11 p1) + D12 p2,
+ *                         q[2] = (D02 p0 + D12 p1) + D22 p2;  then over the incident edges in increasing k, o the edge's other end:
+ *                         the node is the edge's i: q[r] = q[r] + ((C[r][0] o0 + C[r][1] o1) + C[r][2] o2) with o = p_j;  it is the
+ *                         edge's j: q[r] = q[r] + ((C[0][r] o0 + C[1][r] o1) + C[2][r] o2) with o = p_i;  r = 0, 1, 2.
+ *                     (2) pq = dot(p, q).  pq not finite or not > 0: LF_ALIGN_DEGENERATE.
+ *                     (3) alpha = rz / pq;  free nodes: t = t + alpha p, r = r - alpha q, z = solve3(D, r);  rz' = dot(r, z);
+ *                         result.cg_iterations += 1.
+ *                     (4) rz' not finite: LF_ALIGN_DEGENERATE.   (5) rz' <= (cg_tol cg_tol) rz0: stop.
+ *                     (6) n == the cap (cg_iterations, or 3 n_nodes when that is 0): stop, result.cg_capped += 1.
+ *                     (7) beta = rz' / rz;  free nodes: p = z + beta p;  rz = rz'.
+ *                     A t with a component that is not finite: LF_ALIGN_DEGENERATE.  Else every free node takes x = x + t0, y = y +
+ *                     t1, th = th + t2 and result.iterations += 1.
+ *   step g            = 0 .. iterations - 1: the edges at the iterate (cost0 = their cost when g = 0), the nodes, CG, the step.
+ *   afterwards        one more pass over the edges at the iterate gives cost and edge_chi2[k] = s (without rho).  Then the limits,
+ *                     whatever the status, as in lf_map_smooth: one node with shift > max_shift or turn > max_turn against its
+ *                     input pose: LF_ALIGN_REJECTED, every pose is the input again, bit for bit, cost = cost0 and edge_chi2 is
+ *                     taken at the input poses.
+ * A free node without any edge has D = damping alone: with damping = 0 its first pivot fails and the call is DEGENERATE in step 0.
+ * A graph that no fixed node and no damping holds has a singular system; as for lf_map_smooth's chains, it is DEGENERATE only
+ * where a pivot or pq comes out <= 0, which rounding decides: fix a node or give a damping.
+ * LF_ERR_BAD_ARG, touching nothing: NULL pose, cfg, pose_out or res; n_nodes outside 1 .. 4096; n_edges outside 0 .. 65536;
+ * n_edges > 0 without edge_ij, edge_z or edge_w; an edge with i == j or an index outside 0 .. n_nodes - 1; a non-finite pose or z;
+ * a negative or NaN w; iterations outside 1 .. 32; cg_iterations outside 0 .. 16384; a cg_tol, damping, max_shift or max_turn that
+ * is negative or NaN; a huber that is <= 0 or NaN.
+ * One launch of one workgroup runs all of it: block-Jacobi CG is the simplest solver whose order of operations can be written
+ * down and replayed, and on a long chain it needs a number of iterations of the order of the node count.  It returns when
+ * pose_out, edge_chi2 and res (host) are in place. */
+typedef struct lf_graph_config {
+    int32_t iterations;          /* Gauss-Newton steps, 1 .. 32; default 5 */
+    int32_t cg_iterations;       /* cap per Gauss-Newton step, 0 .. 16384; 0 (default) = 3 x n_nodes */
+    double  cg_tol;              /* >= 0: CG stops when rz <= cg_tol^2 rz0; default 1e-10, a starting value no log has tuned */
+    double  damping;             /* >= 0: added to every diagonal entry of every free node's D; default 0 */
+    double  huber;               /* > 0 or +inf (off, default): edges flagged robust with chi2 s > huber^2 weigh huber / sqrt(s) */
+    double  max_shift, max_turn; /* >= 0, default +inf: as lf_map_align's limits, against the input poses */
+} lf_graph_config;
+typedef struct lf_graph_result {
+    double  cost0, cost;         /* at the input poses / at the returned poses */
+    int32_t status;              /* LF_ALIGN_OK / LF_ALIGN_DEGENERATE / LF_ALIGN_REJECTED */
+    int32_t iterations;          /* accepted Gauss-Newton steps */
+    int32_t cg_iterations;       /* CG iterations over all steps */
+    int32_t cg_capped;           /* Gauss-Newton steps whose CG ran into the cap */
+} lf_graph_result;
+LF_API int lf_sizeof_graph_config(void);
+LF_API int lf_sizeof_graph_result(void);
+LF_API void lf_map_graph_default_config(lf_graph_config* c);
+LF_API int lf_map_graph_solve(lf_map* m, const double* pose /* host [n_nodes][3] */, int n_nodes,
+                              const int32_t* edge_ij /* host [n_edges][2] */, const double* edge_z /* [n_edges][3] */,
+                              const double* edge_w /* [n_edges][3]: w_xy, w_xy', w_theta, each >= 0 */,
+                              const uint8_t* robust /* [n_edges] or NULL: none */, int n_edges,
+                              const uint8_t* fixed /* [n_nodes] or NULL: node 0 only */,
+                              const lf_graph_config* cfg, double* pose_out /* host [n_nodes][3] */,
+                              double* edge_chi2 /* host [n_edges] or NULL */, lf_graph_result* res);
+
+/* lf_map_correct: every entry in use is moved by the rigid motion that takes its key pose `from` to `to`; the entry's last_seen step
+ * is the key.  In place, queued on the map's stream in call order with updates and associations.
+ *   keys              per key k: dth = to.th - from.th, (sn, cs) = sin, cos of dth (lf_map_align's routine).
+ *   an entry          in use (physical index < size) with last_seen = s takes the largest k with key_step[k] <= s; steps at or
+ *                     past the last key take the last key.  It is left exactly as it is when s < key_step[0] (seeded entries:
+ *                     their last_seen is -1), or when its key's `to` equals its `from` in all three bit patterns.  Otherwise,
+ *                     for each endpoint (px, py):  ux = px - from.x, uy = py - from.y;  X = to.x + (cs ux - sn uy),
+ *                     Y = to.y + (sn ux + cs uy).  A coordinate that is not finite goes through the same operations; an X or Y
+ *                     that comes out NaN is written as the quiet NaN 0x7ff8000000000000.
+ *   nothing else      changes: code, colour, hits, last_seen, order, the matrix-core operands and lf_map_size's counters stay.
+ *   res               n_moved: the entries rewritten;  n_left: the entries in use that were left;  max_shift: the largest FINITE
+ *                     d = sqrt(dx dx + dy dy), dx = X - px, dy = Y - py, over the endpoints rewritten, taken by bit pattern
+ *                     (as lf_map_lane_pose takes its nearest edge); +0 without one.
+ * No structure of the library caches the entries' geometry across calls (the grid index, the lanes, the polylines and both renders
+ * are rebuilt by every call), so nothing has to be invalidated.  LF_ERR_BAD_ARG, touching nothing: a NULL pointer; n_keys outside
+ * 1 .. 4096; steps that are not strictly increasing; a non-finite pose.  It returns when res is in place.
+ * Replicas: the correction is a pure function of the map and the arguments, so ranks of a multi-GPU run that call it with the same
+ * arguments between the same two steps keep identical maps; no collective is needed. */
+typedef struct lf_correct_result { int32_t n_moved, n_left; double max_shift; } lf_correct_result;
+LF_API int lf_map_correct(lf_map* m, const int32_t* key_step /* host [n_keys], strictly increasing */,
+                          const double* from_pose, const double* to_pose /* host [n_keys][3] */, int n_keys,
+                          lf_correct_result* res);
+/* ms and launches accumulated since the previous call, with profiling on; resets them: [0] lf_map_graph_solve (one launch = one
+ * call), [1] lf_map_correct.  Stages of their own: the other timing calls are unchanged. */
+LF_API int lf_map_graph_timing(lf_map* m, double ms[2], int32_t launches[2]);
+
 /* ---- Histogram lane filter: lane pose from ground segments -----------------------------------------
  * LaneFilterHistogram (src/lane_filter/include/lane_filter/lane_filter.py:12-161) as lane_filter_node.processSegments
  * drives it (src/lane_filter/src/lane_filter_node.py:49-87): per frame predict(dt, v, w) -> update(segments) ->

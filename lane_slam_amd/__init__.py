@@ -9,6 +9,8 @@ The package is a thin host-side mirror of the reference's interfaces for this pa
                         describe_keylines <-> BinaryDescriptor::detect / compute with octaves (SURVEY 8f-4)
   LineAssociator   <->  line_associator node (a stub in the reference) + show_map's segment store: device-resident
                         live map, MFMA Hamming association, colour gating, append / merge updates (lf_map_*)
+  PoseGraph             loop closures: key poses, odometry and loop edges, solved on the device (LineAssociator.graph_solve)
+                        and applied to the map (LineAssociator.correct)
   BinaryDescriptorMatcher <-> the matcher's dataset form (add / train / match / knnMatch / radiusMatch over several train images, imgIdx)
   LaneFilterHistogram <-> lane_filter.LaneFilterHistogram: the histogram lane filter (lane pose from ground segments) on the
                         device; LaneFilterBatch runs many filter streams over a FrontEnd batch's segments
@@ -21,8 +23,9 @@ from .config import (COLOR_NAMES, DEFAULT_DETECTOR_CONFIGURATION, RED, WHITE, YE
 from .frontend import FrontEnd, LanefrontError, Segments
 from .lane_filter import LaneFilterBatch, LaneFilterHistogram
 from .line_associator import LineAssociator
+from .pose_graph import PoseGraph
 from .matcher import BinaryDescriptorMatcher, BinaryDescriptorParams, DMatch
 from .line_detector_hip import Detections, LineDetector2Dense, LineDetectorEDLines, LineDetectorHIP, LineDetectorHSV, LineDetectorInterface
 
-__all__ = ["LaneFilterBatch", "LaneFilterHistogram", "BinaryDescriptorMatcher", "BinaryDescriptorParams", "DMatch", "LineAssociator", "FrontEnd", "LanefrontError", "Segments", "LineDetectorHIP", "LineDetectorHSV", "LineDetector2Dense", "LineDetectorEDLines", "LineDetectorInterface", "Detections",
+__all__ = ["LaneFilterBatch", "LaneFilterHistogram", "BinaryDescriptorMatcher", "BinaryDescriptorParams", "DMatch", "LineAssociator", "PoseGraph", "FrontEnd", "LanefrontError", "Segments", "LineDetectorHIP", "LineDetectorHSV", "LineDetector2Dense", "LineDetectorEDLines", "LineDetectorInterface", "Detections",
            "default_config", "DEFAULT_DETECTOR_CONFIGURATION", "WHITE", "YELLOW", "RED", "COLOR_NAMES"]

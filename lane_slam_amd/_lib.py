@@ -54,6 +54,8 @@ EXPORTS = (
     "lf_map_polylines_default_config", "lf_map_polylines", "lf_map_polylines_timing",
     "lf_sizeof_lane_pose_config", "lf_sizeof_lane_pose", "lf_sizeof_lane_pose_result",
     "lf_map_lane_pose_default_config", "lf_map_lane_pose", "lf_map_lane_pose_timing",
+    "lf_sizeof_graph_config", "lf_sizeof_graph_result", "lf_map_graph_default_config", "lf_map_graph_solve", "lf_map_correct",
+    "lf_map_graph_timing",
 )
 LF_ALIGN_OK, LF_ALIGN_FEW, LF_ALIGN_DEGENERATE, LF_ALIGN_REJECTED = 0, 1, 2, 3
 ALIGN_STATUS = ("ok", "few", "degenerate", "rejected")
@@ -305,6 +307,23 @@ class LfLanePoseResult(ctypes.Structure):
     _fields_ = [("polylines", LfPolylinesResult), ("n_edges", ctypes.c_int32 * 2), ("n_posed", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
 
 
+class LfGraphConfig(ctypes.Structure):
+    """ctypes mirror of `lf_graph_config` (include/lanefront.h)."""
+    _fields_ = [("iterations", ctypes.c_int32), ("cg_iterations", ctypes.c_int32), ("cg_tol", ctypes.c_double), ("damping", ctypes.c_double),
+                ("huber", ctypes.c_double), ("max_shift", ctypes.c_double), ("max_turn", ctypes.c_double)]
+
+
+class LfGraphResult(ctypes.Structure):
+    """ctypes mirror of `lf_graph_result` (include/lanefront.h)."""
+    _fields_ = [("cost0", ctypes.c_double), ("cost", ctypes.c_double), ("status", ctypes.c_int32), ("iterations", ctypes.c_int32),
+                ("cg_iterations", ctypes.c_int32), ("cg_capped", ctypes.c_int32)]
+
+
+class LfCorrectResult(ctypes.Structure):
+    """ctypes mirror of `lf_correct_result` (include/lanefront.h)."""
+    _fields_ = [("n_moved", ctypes.c_int32), ("n_left", ctypes.c_int32), ("max_shift", ctypes.c_double)]
+
+
 _lib = None
 
 
@@ -514,6 +533,15 @@ def load():
     lib.lf_map_lane_pose.restype = ci
     lib.lf_map_lane_pose_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
     lib.lf_map_lane_pose_timing.restype = ci
+    lib.lf_sizeof_graph_config.argtypes = []
+    lib.lf_sizeof_graph_result.argtypes = []
+    lib.lf_map_graph_default_config.argtypes = [ctypes.POINTER(LfGraphConfig)]
+    lib.lf_map_graph_default_config.restype = None
+    lib.lf_map_graph_solve.argtypes = [vp, vp, ci, vp, vp, vp, vp, ci, vp, ctypes.POINTER(LfGraphConfig), vp, vp, ctypes.POINTER(LfGraphResult)]
+    lib.lf_map_correct.argtypes = [vp, vp, vp, vp, ci, ctypes.POINTER(LfCorrectResult)]
+    lib.lf_map_graph_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
+    for f in ("lf_sizeof_graph_config", "lf_sizeof_graph_result", "lf_map_graph_solve", "lf_map_correct", "lf_map_graph_timing"):
+        getattr(lib, f).restype = ci
     lib.lf_descriptor_default_params.argtypes = [ctypes.POINTER(LfDescriptorParams)]
     lib.lf_descriptor_default_params.restype = None
     lib.lf_set_descriptor_params.argtypes = [vp, ctypes.POINTER(LfDescriptorParams)]

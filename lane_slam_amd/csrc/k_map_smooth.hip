@@ -7,8 +7,9 @@
 // and keeps the chain's state; in the last iteration it tests the limits and writes the results.  The nodes live in device
 // memory (a chain of 4096 nodes does not fit the LDS); they are written and read again by different waves of the workgroup, in
 // the order the barriers' workgroup-scope fences give, through plain pointers and ordinary loads.  A chain that has stopped is
-// skipped by both kernels until the last solve.
-#include "k_map_pairs.h"
+// skipped by both kernels until the last solve.  The factor's statements (products, Jacobians, solve3) are k_map_edge.h's, which
+// lf_map_graph_solve's kernel shares.
+#include "k_map_edge.h"
 #include "k_map_smooth.h"
 
 namespace lf {
@@ -17,17 +18,9 @@ namespace ms {
 namespace {
 
 using ma::finite;
-
-// (A^T W B)[r][c] and (A^T W e)[r] for row-major 3 x 3 A, B and the diagonal W, in the contract's order
-__device__ __forceinline__ double atwb(const double* A, const double* w, const double* B, int r, int c)
-{
-    return ((A[r] * w[0]) * B[c] + (A[3 + r] * w[1]) * B[3 + c]) + (A[6 + r] * w[2]) * B[6 + c];
-}
-__device__ __forceinline__ double atwe(const double* A, const double* w, const double* e, int r)
-{
-    return ((A[r] * w[0]) * e[0] + (A[3 + r] * w[1]) * e[1]) + (A[6 + r] * w[2]) * e[2];
-}
-__device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
+using me::add_factor;
+using me::atwb;
+using me::dot3;
 
 // the odometry factor of the edge f -> f + 1: its residual and Jacobians at the iterate
 __device__ __forceinline__ void edge(const double* pose0, const lf_align_result* res, int f, double* Jf, double* Jn, double* e)
@@ -43,21 +36,7 @@ __device__ __forceinline__ void edge(const double* pose0, const lf_align_result*
     const double ux = res[f + 1].x - res[f].x, uy = res[f + 1].y - res[f].y;
     const double px = c * ux + s * uy, py = (-s) * ux + c * uy;
     e[0] = px - zx; e[1] = py - zy; e[2] = (thn - thf) - zt;
-    Jf[0] = -c; Jf[1] = -s; Jf[2] = py;
-    Jf[3] = s; Jf[4] = -c; Jf[5] = -px;
-    Jf[6] = 0.0; Jf[7] = 0.0; Jf[8] = -1.0;
-    Jn[0] = c; Jn[1] = s; Jn[2] = 0.0;
-    Jn[3] = -s; Jn[4] = c; Jn[5] = 0.0;
-    Jn[6] = 0.0; Jn[7] = 0.0; Jn[8] = 1.0;
-}
-
-// D += A^T W A (upper triangle), b -= A^T W e
-__device__ __forceinline__ void add_factor(double* D, double* b, const double* A, const double* w, const double* e)
-{
-    D[0] = D[0] + atwb(A, w, A, 0, 0); D[1] = D[1] + atwb(A, w, A, 0, 1); D[2] = D[2] + atwb(A, w, A, 0, 2);
-    D[3] = D[3] + atwb(A, w, A, 1, 1); D[4] = D[4] + atwb(A, w, A, 1, 2);
-    D[5] = D[5] + atwb(A, w, A, 2, 2);
-    b[0] = b[0] - atwe(A, w, e, 0); b[1] = b[1] - atwe(A, w, e, 1); b[2] = b[2] - atwe(A, w, e, 2);
+    me::jacobians(s, c, px, py, Jf, Jn);
 }
 
 // node i of the chain that starts at frame o0: the map sums, the prior, the anchor, the edge from i - 1, the edge to i + 1
@@ -250,14 +229,12 @@ __global__ __launch_bounds__(kSolveThreads) void k_map_smooth_solve(lf_smooth_co
             __syncthreads();
         }
         if (tid == 0) {
-            ma::Ldl f;
-            double t0 = 0.0, t1 = 0.0, t2 = 0.0;
-            if (!(ma::ldl_factor(nodes->D[0], nodes->D[1], nodes->D[2], nodes->D[3], nodes->D[4], nodes->D[5], f) &&
-                  ma::ldl_apply(f, nodes->b[0], nodes->b[1], nodes->b[2], t0, t1, t2))) {
-                t0 = t1 = t2 = 0.0;
+            double t[3] = { 0.0, 0.0, 0.0 };
+            if (!me::solve3(nodes->D, nodes->b, t)) {
+                t[0] = t[1] = t[2] = 0.0;
                 s_fail = 1;
             }
-            nodes->t[0] = t0; nodes->t[1] = t1; nodes->t[2] = t2;
+            nodes->t[0] = t[0]; nodes->t[1] = t[1]; nodes->t[2] = t[2];
         }
         __syncthreads();
         int top = 1;

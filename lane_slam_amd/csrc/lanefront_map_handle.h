@@ -3,7 +3,8 @@
 // (lanefront_map_smooth.hip); the localisation without a prior pose (lanefront_map_localize.hip); the culling (lanefront_map_prune.hip);
 // the association gated by the prior pose (lanefront_map_near.hip); the lane lines (lanefront_map_lanes.hip), their polylines
 // (lanefront_map_polylines.hip) and the lane pose from them (lanefront_map_lane_pose.hip, which runs the polylines' stages through
-// queue_polylines, declared below).  The last four share one index of the map, k_map_near.h's: build_index
+// queue_polylines, declared below); the pose graph and the map's correction by it (lanefront_map_graph.hip).  The gated association,
+// the lanes, the polylines and the lane pose share one index of the map, k_map_near.h's: build_index
 // (lanefront_map_near.hip, declared below) is the only code that sizes, grows, fills and queues it.  The three pose solvers share one
 // front end (argument check, batch opener, prior-pose upload) and the two solving steps one body and, with
 // lf_map_step_host, one host-form wrapper: all of it lives in lanefront_map_align.hip and is declared at the end of this file.
@@ -76,6 +77,14 @@ struct MapPruneState {
     HostArray<int> h_counters;                               // pinned: the counters of k_map_prune.h
 };
 
+// what lf_map_graph_solve and lf_map_correct keep between calls (lanefront_map_graph.hip): a solve's inputs as one block and its work
+// arrays as another, a correction's keys with its counters; scratch that grows on demand, and the host blocks the copies run from and to
+struct MapGraphState {
+    DevBuf in, work, keys;
+    std::vector<uint8_t> h_in, h_keys;
+    std::vector<double> h_out;
+};
+
 }  // namespace lf
 
 using namespace lf;
@@ -87,6 +96,7 @@ enum MapStage {
     kMapLanesIndexStage, kMapLanesTableStage,
     kMapPolylinesLanesStage, kMapPolylinesVerticesStage, kMapPolylinesLinksStage,
     kMapLanePosePolylinesStage, kMapLanePoseQueryStage,
+    kMapGraphSolveStage, kMapCorrectStage,
     kMapStageCount
 };
 
@@ -125,6 +135,7 @@ struct lf_map : lf::Core {
     std::unique_ptr<lf::MapLanesState> lanes;     // lf_map_lanes (lanefront_map_lanes.hip), made by its first call
     std::unique_ptr<lf::MapPolylinesState> polylines;   // lf_map_polylines (lanefront_map_polylines.hip), made by its first call
     std::unique_ptr<lf::MapLanePoseState> lane_pose;    // lf_map_lane_pose (lanefront_map_lane_pose.hip), made by its first call
+    std::unique_ptr<lf::MapGraphState> graph;     // lf_map_graph_solve, lf_map_correct (lanefront_map_graph.hip), made by their first call
     std::unique_ptr<lf::MapPruneState> prune;     // lf_map_prune (lanefront_map_prune.hip), made by its first call
     std::unique_ptr<lf::MapRenderState> render;   // lf_map_render / lf_map_bounds (lanefront_map_render.hip), made by their first call
     std::unique_ptr<lf::MapCameraState> camera;   // lf_map_render_camera (lanefront_map_camera.hip), likewise

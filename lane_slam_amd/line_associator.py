@@ -622,6 +622,57 @@ class LineAssociator(object):
         self._check(self.lib.lf_map_lane_pose_timing(self.m, ms, ln))
         return {"polylines": (ms[0], ln[0]), "query": (ms[1], ln[1])}
 
+    # ------------------------------------------------------------------ loop closures (lf_map_graph_solve, lf_map_correct)
+    def graph_config(self, **overrides):
+        """The library's default `_lib.LfGraphConfig` (lf_map_graph_default_config) with the overrides applied: iterations,
+        cg_iterations, cg_tol, damping, huber, max_shift, max_turn."""
+        return self._config("graph_config", _lib.LfGraphConfig, self.lib.lf_map_graph_default_config, overrides)
+
+    def graph_solve(self, poses, edges, z, w, robust=None, fixed=None, config=None):
+        """Solve an SE(2) pose graph on the device (lf_map_graph_solve): poses (n_nodes, 3) the key poses, edges (n_edges, 2) int32
+        node indices i -> j, z (n_edges, 3) the measured pose of j in i's frame, w (n_edges, 3) the weights of its three residuals,
+        robust (n_edges,) flags the edges the Huber weight applies to (None: none), fixed (n_nodes,) the nodes that stay (None:
+        node 0).  Returns (poses_out (n_nodes, 3), result, chi2): result is {'cost0', 'cost', 'status', 'iterations',
+        'cg_iterations', 'cg_capped'} (status: `_lib.ALIGN_STATUS`), chi2 (n_edges,) every edge's chi-square at poses_out.  The map
+        is neither read nor changed."""
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        edges = np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+        z, w = np.ascontiguousarray(z, np.float64).reshape(-1, 3), np.ascontiguousarray(w, np.float64).reshape(-1, 3)
+        n, m = len(poses), len(edges)
+        if len(z) != m or len(w) != m:
+            raise ValueError("graph_solve: z and w hold three values per edge")
+        robust = None if robust is None else np.ascontiguousarray(robust, np.uint8).reshape(-1)
+        fixed = None if fixed is None else np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+        if (robust is not None and len(robust) != m) or (fixed is not None and len(fixed) != n):
+            raise ValueError("graph_solve: robust holds one flag per edge, fixed one per node")
+        config = self.graph_config() if config is None else config
+        out, chi2, res = np.zeros((n, 3), np.float64), np.zeros(m, np.float64), _lib.LfGraphResult()
+        self._check(self.lib.lf_map_graph_solve(self.m, poses.ctypes.data, n, edges.ctypes.data, z.ctypes.data, w.ctypes.data,
+                                                None if robust is None else robust.ctypes.data, m,
+                                                None if fixed is None else fixed.ctypes.data, ctypes.byref(config), out.ctypes.data,
+                                                chi2.ctypes.data, ctypes.byref(res)))
+        return out, {k: getattr(res, k) for k, _ in _lib.LfGraphResult._fields_}, chi2
+
+    def correct(self, key_steps, from_poses, to_poses):
+        """Move every map entry by the rigid correction of the key pose that observed it (lf_map_correct; in place, waits for the
+        map's stream): key_steps (n_keys,) strictly increasing steps, from_poses / to_poses (n_keys, 3) each key's pose when the map
+        was drawn and its corrected pose.  An entry takes the last key at or before its last_seen.  Returns {'n_moved', 'n_left',
+        'max_shift'}."""
+        steps = np.ascontiguousarray(key_steps, np.int32).reshape(-1)
+        fr, to = np.ascontiguousarray(from_poses, np.float64).reshape(-1, 3), np.ascontiguousarray(to_poses, np.float64).reshape(-1, 3)
+        if len(fr) != len(steps) or len(to) != len(steps):
+            raise ValueError("correct: one from pose and one to pose per key")
+        res = _lib.LfCorrectResult()
+        self._check(self.lib.lf_map_correct(self.m, steps.ctypes.data, fr.ctypes.data, to.ctypes.data, len(steps), ctypes.byref(res)))
+        return {"n_moved": res.n_moved, "n_left": res.n_left, "max_shift": res.max_shift}
+
+    def graph_timing(self):
+        """{'solve': (ms, launches), 'correct': (ms, launches)} of the `graph_solve` and `correct` calls since the previous call
+        (needs set_profiling(True)); resets."""
+        ms, ln = (ctypes.c_double * 2)(), (ctypes.c_int32 * 2)()
+        self._check(self.lib.lf_map_graph_timing(self.m, ms, ln))
+        return {"solve": (ms[0], ln[0]), "correct": (ms[1], ln[1])}
+
     @staticmethod
     def carry(poses, last_odometry, last_corrected):
         """The next batch's odometry poses (n, 3) with the previous batch's correction applied: the rigid motion that takes

@@ -8,6 +8,7 @@ wire bodies.  The first batch is checked against the oracle (pixels, segments, m
                                 [--overlay-jpeg DIR] [--align | --smooth | --localize] [--prune EVERY[:min_hits[:age]]]
                                 [--near RADIUS[:max_offset[:max_sin]]] [--lanes RADIUS[:max_offset[:max_sin[:min_entries]]]]
                                 [--polylines CELL[:max_gap[:reach]]] [--lane-pose RADIUS[:max_sin]] [--lane-filter]
+                                [--close-loops N]
 
 --map-jpeg writes the final map as the reference's README shows it (show_map's coloured segments seen from above, lf_map_render
 fitted to the map) as a JPEG: rendered and encoded on the device, only the file's bytes cross the bus.
@@ -31,6 +32,10 @@ vertices, closed or open, entries, hits, both ends, length.
 with a pose, the frames in lane, the median d and phi of the posed frames and the last frame's (d, phi, in_lane).  --lane-filter
 runs the histogram lane filter (lf_lane_filter_*, the reference's default configuration, no odometry: update only) over the same
 batches' segments; with both flags the filter's values stand beside the map's: two independent paths to the same two numbers.
+--close-loops N (with --localize) keeps a pose graph with one key per batch (lane_slam_amd.PoseGraph: the pose the batch's first frame
+was stepped with).  When that frame was localised with at least the configured inliers in a part of the map that is at least N keys
+old, the loop edge is added, the graph is solved on the device (lf_map_graph_solve) and the map moved (lf_map_correct); it prints the
+cost before and after, the largest shift of an endpoint and the solver's and the correction's milliseconds.
 """
 import argparse, io, os, sys, time
 import numpy as np
@@ -78,10 +83,15 @@ ap.add_argument("--polylines", default=None, metavar="CELL[:max_gap[:reach]]",
 ap.add_argument("--lane-pose", default=None, metavar="RADIUS[:max_sin]",
                 help="behind every batch's update, the lane pose of the poses the step used, from the map's polylines (lf_map_lane_pose, the "
                      "rules from --polylines' and --lanes' fields); prints one line per batch")
+ap.add_argument("--close-loops", type=int, default=None, metavar="N",
+                help="with --localize: one pose-graph key per batch; a first frame localised in a part of the map at least N keys old closes "
+                     "a loop (lf_map_graph_solve, lf_map_correct); prints cost0 -> cost, the shift and the milliseconds")
 ap.add_argument("--lane-filter", action="store_true",
                 help="run the histogram lane filter over every batch's segments (update only: the replay has no odometry) and print its last "
                      "frame's (d, phi, in_lane) per batch, beside --lane-pose's when both are given")
 args = ap.parse_args()
+if args.close_loops is not None and (not args.localize or args.close_loops < 1):
+    ap.error("--close-loops N goes with --localize, N >= 1")
 lane_pose_fields = None
 if args.lane_pose:
     parts = [float(v) for v in args.lane_pose.split(":")]
@@ -167,6 +177,11 @@ if lane_pose_fields:
 if args.lane_filter:
     from lane_slam_amd.lane_filter import DEFAULT_CONFIGURATION, LaneFilterBatch, UPDATE
     lane_filter = LaneFilterBatch(DEFAULT_CONFIGURATION, n_streams=1, max_frames=B)
+pose_graph = None
+if args.close_loops is not None:
+    from lane_slam_amd import PoseGraph
+    pose_graph = PoseGraph()
+    live.set_profiling(True)
 n_near_sum = 0
 ok_frames, used_endpoints, all_frames = [0, 0], [0, 0], 0
 t0 = time.perf_counter()
@@ -212,6 +227,26 @@ for b0 in range(0, args.frames - B + 1, B):
                   % (b0 // B, ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, counts)),
                      "min %d median %d max %d" % (found.min(), np.median(found), found.max()) if len(found) else "-",
                      ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, np.bincount(out[3]["status"], minlength=4)))))
+            if pose_graph is not None:
+                # one key per batch: the pose its first frame was stepped with; its entries carry the step as last_seen
+                key = pose_graph.add_key(b0 // B, used_poses[0])
+                first = di[:int(seg.frame_offset[1])].cpu().numpy()
+                if loc["status"][0] == 0 and loc["n_inliers"][0] >= live.localize_config().min_inliers:
+                    old = pose_graph.entries_before(live, first, key - args.close_loops)
+                    seen_from = pose_graph.key_of_entries(live, old)
+                    if seen_from >= 0:
+                        pose_graph.loop_from_localize(seen_from, key, located[0])
+                        live.graph_timing()
+                        _, gres, _ = pose_graph.solve(live)
+                        moved = pose_graph.apply(live) if gres["status"] == 0 else None
+                        gt = live.graph_timing()
+                        print("batch %d closes a loop with key %d: %s, cost %.6g -> %.6g in %d steps and %d CG iterations (%.3f ms); %s"
+                              % (b0 // B, seen_from, _lib.ALIGN_STATUS[gres["status"]], gres["cost0"], gres["cost"], gres["iterations"],
+                                 gres["cg_iterations"], gt["solve"][0],
+                                 "the map is left" if moved is None else "%d entries moved by up to %.4f m (%.3f ms)"
+                                 % (moved["n_moved"], moved["max_shift"], gt["correct"][0])))
+                        if moved is not None:
+                            last_corrected = tuple(pose_graph.key_pose[-1])
         elif args.align:
             # (the replay has no odometry: every prior is the identity, and the seeded map has no geometry to align with)
             out = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=np.zeros((B, 3)), step=b0 // B,
