@@ -431,9 +431,16 @@ LF_API int lf_map_size(lf_map* m, int* size, int* head, int64_t* total_appended,
 /* Nearest map entry of n queries (a-10 semantics + the map's gating / max_distance).  color may be NULL when
  * gating is off.  h: the handle whose stream produced the query arrays (the map's stream waits for it, and the
  * handle's next batch waits until the map has read them), or NULL when the caller has ordered that itself.
- * on_device applies to all four arrays; with host arrays the call returns when idx / dist are in place. */
+ * on_device applies to all four arrays; with host arrays the call returns when idx / dist are in place.
+ * When code32 (and color, if given) are the device arrays of the block h's last batch was queued with, the map first copies that
+ * batch's code, color, keep, ground and frame_offset into memory of its own and reads the copies: the handle's next batch then
+ * waits for the copy only, and an lf_map_pack_block (or the rest of an lf_map_step) of the same arrays, with no batch queued on h
+ * in between, reads the copies too.  The results are the same; lf_map_snapshot_counts says which way the calls went. */
 LF_API int lf_map_associate(lf_map* m, lf_handle* h, const uint8_t* code32, const uint8_t* color, int n,
                      int32_t* idx, float* dist, int on_device);
+/* calls with a handle since the map was made: associations that copied the batch first, block packings that read such a copy, and
+ * calls of either kind that read the caller's arrays as they are (NULL outputs are skipped) */
+LF_API int lf_map_snapshot_counts(lf_map* m, int64_t* taken, int64_t* reused, int64_t* fallback);
 /* tie rule of the map's associations (lf_map_associate, lf_map_step*): LF_TIE_MIHASHER unless set; with LF_TIE_MIHASHER and
  * colour gating the reference's discovery order applies among the entries the query may match */
 LF_API int lf_map_set_tie_rule(lf_map* m, int tie_rule);
@@ -1714,7 +1721,9 @@ typedef enum lf_buffer_id {
     LF_BUF_LBD_DY = 8,       /* i16 [frames][Hc][W]                                        */
     LF_BUF_LSD_COUNTS = 9,   /* i32 [frames][3]          lines per run                    */
     LF_BUF_LSD_SCRATCH = 10, /* u32 [frames][3][Hs*Ws]   region-list scratch (diagnostic builds park counters here) */
-    LF_BUF_LSD_NLOW = 11     /* i32 [frames][3]   pixels with a non-zero gradient below the threshold (the low records of lsd_seed_order = OPENCV32; 0 otherwise) */
+    LF_BUF_LSD_NLOW = 11,    /* i32 [frames][3]   pixels with a non-zero gradient below the threshold (the low records of lsd_seed_order = OPENCV32; 0 otherwise) */
+    LF_BUF_LSD_COMP_KEY = 12, /* i32 [frames][3]  launch-order key of every run: the size of its largest connected component (k_lsd_label) */
+    LF_BUF_LSD_PERM = 13     /* i32 [frames][3]   region growing's launch order: the runs by descending key, equal keys by ascending run (k_lsd_rank) */
 } lf_buffer_id;
 /* copy an intermediate buffer of the last batch to host memory (synchronises) */
 LF_API int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t bytes);

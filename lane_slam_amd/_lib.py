@@ -14,7 +14,8 @@ LF_N_STAGES = 16
 LF_MAP_N_STAGES = 4
 LF_MSG_DETECTOR, LF_MSG_GROUND, LF_MSG_FILTERED = 0, 1, 2
 (LF_BUF_BGR, LF_BUF_MASKS, LF_BUF_EDGES, LF_BUF_LSD_ANGLE, LF_BUF_LSD_MODGRAD, LF_BUF_LSD_ORDER,
- LF_BUF_LSD_NORDER, LF_BUF_LBD_DX, LF_BUF_LBD_DY, LF_BUF_LSD_COUNTS, LF_BUF_LSD_SCRATCH, LF_BUF_LSD_NLOW) = range(12)
+ LF_BUF_LSD_NORDER, LF_BUF_LBD_DX, LF_BUF_LBD_DY, LF_BUF_LSD_COUNTS, LF_BUF_LSD_SCRATCH, LF_BUF_LSD_NLOW,
+ LF_BUF_LSD_COMP_KEY, LF_BUF_LSD_PERM) = range(14)
 
 # every symbol include/lanefront.h declares
 EXPORTS = (
@@ -24,7 +25,7 @@ EXPORTS = (
     "lf_debug_fetch", "lf_debug_detmath", "lf_debug_wave", "lf_debug_probe", "lf_debug_lsd_binary", "lf_debug_segments", "lf_debug_hysteresis", "lf_lsd_size", "lf_set_profiling", "lf_get_timing", "lf_reset_timing", "lf_stage_name",
     "lf_map_create", "lf_map_destroy", "lf_map_last_error", "lf_map_get_stream", "lf_map_synchronize", "lf_map_seed", "lf_map_size",
     "lf_map_associate", "lf_map_pack_block", "lf_map_update", "lf_map_step", "lf_map_step_host", "lf_map_fetch",
-    "lf_map_set_profiling", "lf_map_get_timing", "lf_map_stage_name",
+    "lf_map_set_profiling", "lf_map_get_timing", "lf_map_stage_name", "lf_map_snapshot_counts",
     "lf_descriptor_default_params", "lf_set_descriptor_params", "lf_get_descriptor_params",
     "lf_edlines_default_params", "lf_keylines_batch", "lf_describe_keylines", "lf_keylines_debug_fetch", "lf_set_image_edlines", "lf_knn_match", "lf_radius_match", "lf_jpeg_decode_batch_gpu", "lf_jpeg_decode_batch_gpu_async", "lf_jpeg_status", "lf_jpeg_decode_for_detect_async",
     "lf_set_tie_rule", "lf_map_set_tie_rule", "lf_debug_std_sort", "lf_debug_assoc_plan", "lf_suggested_depth", "lf_lsd_list_capacity", "lf_lsd_scratch_stride", "lf_set_detector", "lf_detector_failures", "lf_keylines_batch_async", "lf_keylines_frame_status", "lf_lsd_keylines_batch", "lf_select_queries",
@@ -446,6 +447,8 @@ def load():
     lib.lf_map_get_timing.restype = ci
     lib.lf_map_stage_name.argtypes = [ci]
     lib.lf_map_stage_name.restype = ctypes.c_char_p
+    lib.lf_map_snapshot_counts.argtypes = [vp, i64p, i64p, i64p]
+    lib.lf_map_snapshot_counts.restype = ci
     lib.lf_map_default_view.argtypes = [ctypes.POINTER(LfMapView)]
     lib.lf_map_default_view.restype = None
     lib.lf_map_bounds.argtypes = [vp, ctypes.POINTER(LfMapView), vp, ctypes.POINTER(ci)]

@@ -387,6 +387,17 @@ void launch_map_pack_block(int n, int n_frames, const int* frame_offset, const u
                            const uint8_t* keep, const double* ground, const int32_t* idx, const float* dist,
                            const double* pose4, int step, uint8_t* block, hipStream_t s);
 void launch_map_overflow_block(int n, int n_frames, int step, uint8_t* block, hipStream_t s);
+// k_map_snapshot: up to five arrays copied in one launch, 16 bytes a thread.  src null or bytes 0: nothing for that array
+constexpr int kSnapshotArrays = 5;
+struct MapSnapshotCopy {
+    const uint8_t* src[kSnapshotArrays];
+    uint8_t* dst[kSnapshotArrays];
+    uint32_t bytes[kSnapshotArrays];       // each below 4 GB
+    uint32_t end16[kSnapshotArrays];       // the threads up to and with array k (map_snapshot_plan)
+};
+// fills end16; false (nothing may be launched) when an array that has bytes is not 16-byte aligned at both ends, or is too long
+bool map_snapshot_plan(MapSnapshotCopy* c);
+void launch_map_snapshot(const MapSnapshotCopy& c, hipStream_t s);
 void launch_map_seed_block(int n, const uint8_t* code, const uint8_t* color, const double* ground, uint8_t* block, hipStream_t s);
 void launch_map_update(const MapDevice& md, const uint8_t* blocks, int n_blocks, int block_rows, int force_append, int* act,
                        hipStream_t s);

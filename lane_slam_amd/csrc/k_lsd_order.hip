@@ -722,28 +722,55 @@ __device__ __forceinline__ void lsd_label_problem(const LsdParams& p, const int*
 // Launch order of k_lsd_grow's workgroups: problems with the largest connected component first (k_lsd_label's comp_key;
 // longest first: when the chip is
 // full of another batch's growing waves, the workgroups of this launch start as slots free up, and the long problems
-// should not be the last to start).  rank by counting: n_prob <= 768.
-__global__ __launch_bounds__(256) void k_lsd_rank(int n_prob, const int* __restrict__ norder, int* __restrict__ perm)
+// should not be the last to start).  rank by counting: descending key, equal keys by ascending problem index; any n_prob.
+//
+// Workgroups of ONE wave, one problem per lane (a workgroup of sixteen waves waited for a CU with sixteen free wave slots: see
+// k_hysteresis_cols; four waves that took three problems each walked the keys one dependent LDS read at a time, 58 us for 768
+// keys).  Every wave stages the keys in LDS itself, kRankTile at a time, and reads them back as 16-byte vectors, all lanes the
+// same address (a broadcast), eight reads in flight per turn of the loop.  The staged keys are padded to a multiple of 32 with
+// INT_MIN, which no key exceeds and no problem behind the last one ties with: the loop has no remainder.
+constexpr int kRankTile = 1024, kRankWave = 64;
+__global__ __launch_bounds__(kRankWave) void k_lsd_rank(int n_prob, const int* __restrict__ norder, int* __restrict__ perm)
 {
-    // one workgroup of four waves (1024 threads waited for a CU with sixteen free wave slots: see k_hysteresis_cols)
-    __shared__ int nd[1024];
-    if (n_prob > 1024) {                                     // (never: 3 x 256 frames; kept general)
-        for (int i = threadIdx.x; i < n_prob; i += 256) perm[i] = i;
-        return;
+    __shared__ int4 nd[kRankTile / 4];
+    const int i = blockIdx.x * kRankWave + threadIdx.x;
+    const int mine = i < n_prob ? norder[i] : 0;
+    int rank = 0;
+    for (int base = 0; base < n_prob; base += kRankTile) {
+        const int m = min(kRankTile, n_prob - base);
+        const int nq = ((m + 31) / 32) * 8;                  // int4 words of this tile, padded to eight a turn
+        if (base) __syncthreads();                           // (the previous tile has been read)
+        for (int q = threadIdx.x; q < nq; q += kRankWave) {
+            const int j = base + 4 * q;
+            int4 v;
+            if (j + 4 <= n_prob) v = *reinterpret_cast<const int4*>(norder + j);     // (base and 4 q keep it 16-byte aligned)
+            else {
+                v.x = j < n_prob ? norder[j] : INT_MIN;
+                v.y = j + 1 < n_prob ? norder[j + 1] : INT_MIN;
+                v.z = j + 2 < n_prob ? norder[j + 2] : INT_MIN;
+                v.w = INT_MIN;
+            }
+            nd[q] = v;
+        }
+        __syncthreads();
+        const int before = i - base;                         // keys of this tile at positions below it belong to earlier problems
+#pragma unroll 8
+        for (int q = 0; q < nq; ++q) {
+            const int4 v = nd[q];
+            const int j = 4 * q;
+            rank += (v.x > mine || (v.x == mine && j < before)) ? 1 : 0;
+            rank += (v.y > mine || (v.y == mine && j + 1 < before)) ? 1 : 0;
+            rank += (v.z > mine || (v.z == mine && j + 2 < before)) ? 1 : 0;
+            rank += (v.w > mine || (v.w == mine && j + 3 < before)) ? 1 : 0;
+        }
     }
-    for (int i = threadIdx.x; i < n_prob; i += 256) nd[i] = norder[i];
-    __syncthreads();
-    for (int i = threadIdx.x; i < n_prob; i += 256) {
-        const int mine = nd[i];
-        int rank = 0;
-        for (int j = 0; j < n_prob; ++j) rank += (nd[j] > mine || (nd[j] == mine && j < i)) ? 1 : 0;
-        perm[rank] = i;
-    }
+    if (i < n_prob) perm[rank] = i;
 }
 
 void launch_lsd_rank(const LsdComponents& m, int n_prob, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_lsd_rank, dim3(1), dim3(256), 0, s, n_prob, m.comp_key, m.perm);
+    if (n_prob < 1) return;
+    hipLaunchKernelGGL(k_lsd_rank, dim3((n_prob + kRankWave - 1) / kRankWave), dim3(kRankWave), 0, s, n_prob, m.comp_key, m.perm);
 }
 
 // one launch, the form chosen per problem (both fit 24 KB of dynamic LDS; two launches cost a busy pipeline ~2 ms of a batch's latency)

@@ -278,6 +278,46 @@ void launch_map_pack_block(int n, int n_frames, const int* frame_offset, const u
                        keep, ground, idx, dist, pose4, step, block);
 }
 
+// A batch's map inputs (code, color, keep, ground, frame_offset) copied into the map's own scratch, so that the handle that made
+// them may go on while the association and the block packing still read them (lanefront_map.hip).  One launch for the five
+// arrays: a thread moves 16 bytes of the array its number falls into (sources and destinations are 16-byte aligned); the last
+// thread of an array whose length is no multiple of 16 moves the remainder byte by byte and reads nothing behind the array.
+__global__ __launch_bounds__(256) void k_map_snapshot(MapSnapshotCopy c)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint8_t* src = nullptr;
+    uint8_t* dst = nullptr;
+    uint32_t bytes = 0, first = 0, begin = 0;
+#pragma unroll
+    for (int k = 0; k < kSnapshotArrays; ++k) {
+        if (t >= begin && t < c.end16[k]) { src = c.src[k]; dst = c.dst[k]; bytes = c.bytes[k]; first = begin; }
+        begin = c.end16[k];
+    }
+    if (!src) return;
+    const uint32_t o = (t - first) * 16u;
+    if (o + 16u <= bytes) *reinterpret_cast<uint4*>(dst + o) = *reinterpret_cast<const uint4*>(src + o);
+    else for (uint32_t b = o; b < bytes; ++b) dst[b] = src[b];
+}
+
+bool map_snapshot_plan(MapSnapshotCopy* c)
+{
+    unsigned long long end = 0;
+    for (int k = 0; k < kSnapshotArrays; ++k) {
+        if (!c->src[k]) c->bytes[k] = 0;
+        if (c->bytes[k] && ((reinterpret_cast<uintptr_t>(c->src[k]) | reinterpret_cast<uintptr_t>(c->dst[k])) & 15u)) return false;
+        end += (c->bytes[k] + 15ull) / 16;
+        if (end >= (1ull << 31)) return false;
+        c->end16[k] = (uint32_t)end;
+    }
+    return true;
+}
+
+void launch_map_snapshot(const MapSnapshotCopy& c, hipStream_t s)
+{
+    const uint32_t threads = c.end16[kSnapshotArrays - 1];
+    if (threads) hipLaunchKernelGGL(k_map_snapshot, dim3((threads + 255) / 256), dim3(256), 0, s, c);
+}
+
 __global__ void k_map_overflow_block(int n, int n_frames, int step, uint8_t* __restrict__ block)
 {
     uint32_t* hd = reinterpret_cast<uint32_t*>(block);

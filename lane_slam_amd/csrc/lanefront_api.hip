@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <math.h>
+#include <atomic>
 #include <vector>
 #include <new>
 #include <cstdlib>
@@ -394,6 +395,11 @@ int lf::run_segments(lf_handle* h, int n, lf_segments dev_out, bool describe)
 // a batch's status travels to pinned host memory behind its kernels, in ONE copy
 static int fetch_status(lf_handle* h) { LF_HIP_CHECK(h, hipMemcpyAsync(h->h_status, h->lsd.d_status, sizeof(BatchStatus), hipMemcpyDeviceToHost, h->stream)); return LF_OK; }
 
+// serial numbers of the batches of every handle of the process (LastBatch)
+static std::atomic<unsigned long long> g_batch_serial{0};
+
+LastBatch lf::last_batch_of(const lf_handle* h) { return h ? h->last_batch : LastBatch{}; }
+
 // queue a-1..a-9 for a batch on the handle's stream; device outputs only; no host sync
 extern "C" int lf_process_batch_async(lf_handle* h, const uint8_t* frames, int n_frames, int frames_on_device,
                                       lf_segments* out_dev, int describe)
@@ -421,6 +427,8 @@ extern "C" int lf_process_batch_async(lf_handle* h, const uint8_t* frames, int n
         d_in = h->d_frames;
     }
     h->plugin_ready = false;
+    // (before the first kernel that writes the block: from here on an older snapshot of these arrays is another batch's)
+    h->last_batch = LastBatch{ *out_dev, n_frames, g_batch_serial.fetch_add(1, std::memory_order_relaxed) + 1 };
     int rc = h->detector == LF_DETECTOR_EDLINES ? run_detect_edlines(h, d_in, n_frames) : run_detect(h, d_in, n_frames, false);
     if (rc != LF_OK) return rc;
     rc = run_segments(h, n_frames, *out_dev, describe != 0);

@@ -147,6 +147,15 @@ inline int stream_after(Core* c, hipEvent_t ev, hipStream_t waits, hipStream_t o
     return LF_OK;
 }
 
+// What a handle remembers of the batch it queued last (lf_process_batch_async): the caller's device block, the frames, and a serial
+// number no other batch of any handle has.  The live map compares it with its snapshot of a batch's arrays (lanefront_map.hip).
+struct LastBatch {
+    lf_segments out{};
+    int n_frames = 0;
+    unsigned long long serial = 0;           // 0: no batch yet
+};
+LastBatch last_batch_of(const lf_handle* h);     // lanefront_api.hip; h null: none
+
 // Per-stage time accumulated over many calls, with HIP events recorded on the core's stream.  Events are only recorded inside
 // the pipeline (no host synchronisation); resolve() turns them into milliseconds.  A launch is counted whether or not the core
 // is profiling.  At most `cap` records stay outstanding: then a clock either resolves them on the spot (resolve_when_full) or

@@ -249,6 +249,8 @@ extern "C" int lf_debug_fetch(lf_handle* h, int buffer_id, void* dst, size_t byt
     case LF_BUF_LSD_NLOW:
         if (!h->lsd.d_nlow) { memset(dst, 0, bytes < n * 3 * sizeof(int) ? bytes : n * 3 * sizeof(int)); return LF_OK; }
         src = h->lsd.d_nlow; avail = n * 3 * sizeof(int); break;
+    case LF_BUF_LSD_COMP_KEY: src = h->lsd.d_comp_key; avail = n * 3 * sizeof(int); break;
+    case LF_BUF_LSD_PERM: src = h->lsd.d_perm; avail = n * 3 * sizeof(int); break;
     case LF_BUF_LSD_SCRATCH: src = h->lsd.d_reg; avail = n * 3 * lsd_grow_reg_stride(h->lsd.params) * sizeof(uint32_t); break;
     default: lf_set_error(h, LF_ERR_BAD_ARG, "unknown buffer id %d", buffer_id); return LF_ERR_BAD_ARG;
     }

@@ -251,6 +251,7 @@ struct lf_handle : lf::Core {
     std::unique_ptr<lf::MatcherState> matcher;    // BinaryDescriptorMatcher's dataset (lanefront_matcher.hip)
     lf::HostArray<lf::BatchStatus> h_status;      // pinned: lsd.d_status as the last batch left it
     lf::InFlight flight;
+    lf::LastBatch last_batch;             // the batch queued last, in flight or not (lanefront_map.hip's snapshot path asks for it)
     int last_frames = 0;
     bool plugin_ready = false;
     // plugin path: what lf_detect_lines hands out is fetched ONCE per image, behind the kernels of lf_set_image, into pinned host

@@ -250,6 +250,83 @@ extern "C" int lf_map_size(lf_map* m, int* size, int* head, int64_t* total_appen
     return rc;
 }
 
+// ---- the snapshot path (MapSnapshot): a handle's batch is copied, the handle released, and the map reads the copies
+// The scratch holds at least this many segments from the first snapshot on (a rank's block in the flagship run), or the handle's
+// whole block where that is smaller: it is sized once and grows, through scratch(), only for a batch with more.
+constexpr int kSnapshotRows = 16384;
+
+// the arrays lf_map_associate was given are those of the device block of the batch h queued last
+static bool snapshot_applies(const LastBatch& lb, const uint8_t* code32, const uint8_t* color, int n)
+{
+    return lb.serial != 0 && lb.out.code && code32 == lb.out.code && (!color || color == lb.out.color) && n <= lb.out.capacity &&
+           lb.n_frames >= 1 && (size_t)n * 32 < ((size_t)1 << 31);
+}
+
+// behind after_handle: queue the copy of the batch's five arrays.  *taken false with LF_OK: an array is not 16-byte aligned, and
+// nothing was queued (the caller reads the arrays where they are and releases the handle behind its last kernel)
+static int take_snapshot(lf_map* m, lf_handle* h, const LastBatch& lb, int n, bool* taken)
+{
+    *taken = false;
+    MapSnapshot& sp = m->snap;
+    sp.h = nullptr;
+    const int floor_rows = lb.out.capacity < kSnapshotRows ? lb.out.capacity : kSnapshotRows;
+    const size_t rows = (size_t)(n > floor_rows ? n : floor_rows), r16 = (rows + 15) & ~(size_t)15;     // r16: every array starts on 16 bytes
+    const size_t fo_bytes = lb.out.frame_offset ? ((size_t)lb.n_frames + 1) * sizeof(int) : 0;
+    if (const int rc = scratch(m, sp.buf, r16 * 66 + ((fo_bytes + 15) & ~(size_t)15))) return rc;
+    uint8_t* base = static_cast<uint8_t*>(sp.buf.p);
+    const size_t sn = (size_t)n;
+    MapSnapshotCopy c = {};
+    const void* src[kSnapshotArrays] = { lb.out.code, lb.out.ground, lb.out.color, lb.out.keep, lb.out.frame_offset };
+    const size_t bytes[kSnapshotArrays] = { sn * 32, sn * 32, sn, sn, fo_bytes };
+    const size_t at[kSnapshotArrays] = { 0, r16 * 32, r16 * 64, r16 * 65, r16 * 66 };
+    for (int k = 0; k < kSnapshotArrays; ++k) {
+        c.src[k] = static_cast<const uint8_t*>(src[k]);
+        c.dst[k] = base + at[k];
+        c.bytes[k] = (uint32_t)bytes[k];
+    }
+    if (!map_snapshot_plan(&c)) return LF_OK;
+    launch_map_snapshot(c, m->stream);
+    LF_HIP_CHECK(m, hipGetLastError());
+    sp.h = h; sp.serial = lb.serial; sp.n = n; sp.n_frames = lb.n_frames; sp.user = lb.out;
+    sp.copy = lf_segments{};
+    sp.copy.capacity = n;
+    sp.copy.code = lb.out.code ? c.dst[0] : nullptr;
+    sp.copy.ground = lb.out.ground ? reinterpret_cast<double*>(c.dst[1]) : nullptr;
+    sp.copy.color = lb.out.color ? c.dst[2] : nullptr;
+    sp.copy.keep = lb.out.keep ? c.dst[3] : nullptr;
+    sp.copy.frame_offset = lb.out.frame_offset ? reinterpret_cast<int32_t*>(c.dst[4]) : nullptr;
+    *taken = true;
+    return LF_OK;
+}
+
+// lf_map_pack_block's arrays are the snapshot's: the same handle, no batch queued on it since, the same n, and every array of segs
+// either the block's (its copy is read) or absent.  *d: the arrays to read
+static bool snapshot_serves(const lf_map* m, const lf_handle* h, const lf_segments* segs, int n, int n_frames, bool needs_frames, lf_segments* d)
+{
+    const MapSnapshot& sp = m->snap;
+    if (!h || sp.h != h || last_batch_of(h).serial != sp.serial || n != sp.n || n < 1) return false;
+    if (segs->code != sp.user.code) return false;
+    if ((segs->color && segs->color != sp.user.color) || (segs->keep && segs->keep != sp.user.keep) ||
+        (segs->ground && segs->ground != sp.user.ground) || (segs->frame_offset && segs->frame_offset != sp.user.frame_offset)) return false;
+    if (needs_frames && n_frames > sp.n_frames) return false;
+    *d = lf_segments{};
+    d->code = sp.copy.code;
+    d->color = segs->color ? sp.copy.color : nullptr;
+    d->keep = segs->keep ? sp.copy.keep : nullptr;
+    d->ground = segs->ground ? sp.copy.ground : nullptr;
+    d->frame_offset = segs->frame_offset ? sp.copy.frame_offset : nullptr;
+    return true;
+}
+
+extern "C" int lf_map_snapshot_counts(lf_map* m, int64_t* taken, int64_t* reused, int64_t* fallback)
+{
+    if (!m) return LF_ERR_NOT_INITIALISED;
+    if (taken) *taken = m->snap.taken;
+    if (reused) *reused = m->snap.reused;
+    if (fallback) *fallback = m->snap.fallback;
+    return LF_OK;
+}
+
 extern "C" int lf_map_associate(lf_map* m, lf_handle* h, const uint8_t* code32, const uint8_t* color, int n,
                                 int32_t* idx, float* dist, int on_device)
 {
@@ -274,9 +351,17 @@ extern "C" int lf_map_associate(lf_map* m, lf_handle* h, const uint8_t* code32, 
     }
     if ((rc = after_handle(m, h)) != LF_OK) return rc;
     hipStream_t s = m->stream;
+    // a handle's own batch: its arrays are copied first and the handle goes on behind the copy; everything below reads the copy
+    bool snapped = false;
+    if (h && on_device) {
+        const LastBatch lb = last_batch_of(h);
+        if (snapshot_applies(lb, code32, color, n) && (rc = take_snapshot(m, h, lb, n, &snapped)) != LF_OK) return rc;
+        if (snapped && (rc = release_handle(m, h)) != LF_OK) return rc;
+        ++(snapped ? m->snap.taken : m->snap.fallback);
+    }
     Staging st(m);
-    const uint8_t* dq = st.in(on_device, code32, (size_t)n * 32, m->q_in);
-    const uint8_t* dc = color ? st.in(on_device, color, (size_t)n, m->c_in) : nullptr;
+    const uint8_t* dq = snapped ? m->snap.copy.code : st.in(on_device, code32, (size_t)n * 32, m->q_in);
+    const uint8_t* dc = !color ? nullptr : snapped ? m->snap.copy.color : st.in(on_device, color, (size_t)n, m->c_in);
     int32_t* didx = st.out(on_device, idx, (size_t)n * 4, m->idx_out);
     float* ddist = st.out(on_device, dist, (size_t)n * 4, m->dist_out);
     if (m->tie_rule == LF_TIE_MIHASHER && (rc = scratch(m, m->tie_res, (size_t)n * 8)) != LF_OK) return rc;
@@ -297,7 +382,7 @@ extern "C" int lf_map_associate(lf_map* m, lf_handle* h, const uint8_t* code32, 
         }
     }
     LF_HIP_CHECK(m, hipGetLastError());
-    if ((rc = release_handle(m, h)) != LF_OK) return rc;
+    if (!snapped && (rc = release_handle(m, h)) != LF_OK) return rc;
     return fetch(m, { { idx, didx, (size_t)n * 4 }, { dist, ddist, (size_t)n * 4 } });
 }
 
@@ -329,7 +414,11 @@ extern "C" int lf_map_pack_block(lf_map* m, lf_handle* h, const lf_segments* seg
         set_error(m, LF_ERR_CAPACITY, "lf_map_pack_block: %d segments do not fit a block of %d rows (header + %d); only a header with the overflow marker was written", n, block_rows, block_rows - 1);
         return LF_ERR_CAPACITY;
     }
-    if ((rc = after_handle(m, h)) != LF_OK) return rc;
+    // the batch lf_map_associate copied: its copies are read and the handle, released behind the copy, is left alone
+    lf_segments d = *segs;
+    const bool snapped = snapshot_serves(m, h, segs, n, n_frames, frame_pose && segs->frame_offset, &d);
+    if (h) ++(snapped ? m->snap.reused : m->snap.fallback);
+    if (!snapped && (rc = after_handle(m, h)) != LF_OK) return rc;
     const double* dpose = nullptr;
     if (frame_pose) {
         // cos / sin with the library's deterministic routines (detmath.h), the same the oracle uses
@@ -346,11 +435,10 @@ extern "C" int lf_map_pack_block(lf_map* m, lf_handle* h, const lf_segments* seg
     }
     {
         StageClock::Scope t(m, m->clock, 2);
-        launch_map_pack_block(n, n_frames, segs->frame_offset, segs->code, segs->color, segs->keep, segs->ground, idx, dist, dpose, step,
-                              block, m->stream);
+        launch_map_pack_block(n, n_frames, d.frame_offset, d.code, d.color, d.keep, d.ground, idx, dist, dpose, step, block, m->stream);
     }
     LF_HIP_CHECK(m, hipGetLastError());
-    return release_handle(m, h);
+    return snapped ? LF_OK : release_handle(m, h);
 }
 
 extern "C" int lf_map_step(lf_map* m, lf_handle* h, const lf_segments* segs, int n, int n_frames, const double* frame_pose,

@@ -85,6 +85,19 @@ struct MapGraphState {
     std::vector<double> h_out;
 };
 
+// What lf_map_associate keeps of the batch it was called with through a handle (lanefront_map.hip): the batch's map inputs --
+// code, color, keep, ground, frame_offset -- copied into `buf` by k_map_snapshot behind the handle's kernels.  The handle is
+// released behind that copy, not behind the association: the distance pass, the tie pass and the lf_map_pack_block of the same
+// batch read the copies.  One snapshot at a time; the next one is queued behind this one's readers on the map's stream.
+struct MapSnapshot {
+    DevBuf buf;
+    const lf_handle* h = nullptr;            // null: no snapshot
+    unsigned long long serial = 0;           // LastBatch::serial of the batch
+    int n = 0, n_frames = 0;                 // segments copied; frames of the batch (frame_offset holds n_frames + 1)
+    lf_segments user{}, copy{};              // the handle's block; where its five arrays' copies are (null where the block has none)
+    long long taken = 0, reused = 0, fallback = 0;     // lf_map_snapshot_counts
+};
+
 }  // namespace lf
 
 using namespace lf;
@@ -119,6 +132,7 @@ struct lf_map : lf::Core {
     AssocScratch ws;
     DevBuf act, own_block, pose, q_in, c_in, idx_out, dist_out, seed_code, seed_color, seed_ground, tie_res;
     DevBuf st_fo, st_code, st_color, st_keep, st_ground, st_idx, st_dist;     // staging of the host-form steps and of the solvers' host arrays
+    lf::MapSnapshot snap;                    // lf_map_associate's copy of a handle's batch, reused by lf_map_pack_block
     DevBuf prior_pose;                       // the solvers' prior (localize: fallback) poses [n_frames][3]; one solver runs per call
     DevBuf al_res;                           // lf_map_align, lf_map_smooth: the results [n_frames]
     // lf_map_smooth: the chains' offsets [n_chains + 1] and each frame's chain [n_frames], the map sums [n_frames][9], the nodes

@@ -771,6 +771,8 @@ class FrontEnd(object):
             _lib.LF_BUF_LBD_DY: ((n_frames, self.rows, self.cols), np.int16),
             _lib.LF_BUF_LSD_COUNTS: ((n_frames, 3), np.int32),
             _lib.LF_BUF_LSD_NLOW: ((n_frames, 3), np.int32),
+            _lib.LF_BUF_LSD_COMP_KEY: ((n_frames, 3), np.int32),
+            _lib.LF_BUF_LSD_PERM: ((n_frames, 3), np.int32),
             _lib.LF_BUF_LSD_SCRATCH: ((n_frames, 3, int(self.lib.lf_lsd_scratch_stride(self.h))), np.uint32),     # follows the list capacity (k_lsd_grow.hip lsd_grow_reg_stride)
         }
         shape, dt = shapes[buffer_id]

@@ -86,6 +86,13 @@ class LineAssociator(object):
         self._check(self.lib.lf_map_get_timing(self.m, ms.ctypes.data, ln.ctypes.data, _lib.LF_MAP_N_STAGES))
         return {self.lib.lf_map_stage_name(i).decode(): (float(ms[i]), int(ln[i])) for i in range(_lib.LF_MAP_N_STAGES)}
 
+    def snapshot_counts(self):
+        """{'taken', 'reused', 'fallback'}: calls with a FrontEnd since the map was made -- associations that copied the batch's
+        arrays first (lf_map_associate), block packings that read such a copy, calls that read the caller's arrays as they are."""
+        t, r, f = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        self._check(self.lib.lf_map_snapshot_counts(self.m, ctypes.byref(t), ctypes.byref(r), ctypes.byref(f)))
+        return {"taken": t.value, "reused": r.value, "fallback": f.value}
+
     # ------------------------------------------------------------------ host arrays
     def seed(self, codes, colors=None, ground=None):
         codes = np.ascontiguousarray(codes, np.uint8).reshape(-1, 32)
