@@ -141,6 +141,14 @@ LF_API int lf_synchronize(lf_handle* h);
 /* the handle's HIP stream (a hipStream_t) for callers that order their own device work against the handle's with
  * events instead of host synchronisation (e.g. torch.cuda.ExternalStream); the stream stays owned by the handle */
 LF_API int lf_get_stream(lf_handle* h, void** hip_stream);
+/* The HIP priority of the handle's stream (hipStreamGetPriority) and the device's range (hipDeviceGetStreamPriorityRange; any
+ * pointer may be NULL).  A handle's stream has the normal priority, a live map's the greatest where the device has a range
+ * (least != greatest).  The runtime puts a new stream on the hardware queue with the fewest streams (GPU_MAX_HW_QUEUES queues,
+ * four by default) and streams on one queue serialise, so the first lf_create of a process on a device also makes
+ * GPU_MAX_HW_QUEUES - 1 idle streams that are kept until the process ends (none with more than eight queues): with the default
+ * stream they fill one level of the queues, and the handles' streams are dealt evenly from there on -- eight handles on four
+ * queues two each, not 3 / 2 / 2 / 1.  The variable is read, never set. */
+LF_API int lf_stream_priority(const lf_handle* h, int* priority, int* least, int* greatest);
 
 /* ---- plugin path: replaces LineDetectorLSD (line_detector_lsd.py:11-142) ---
  * lf_set_image  <-> LineDetectorLSD.setImage(bgr)      (:135-139)
@@ -177,7 +185,10 @@ LF_API int lf_process_batch(lf_handle* h, const uint8_t* frames, int n_frames, i
  * lets one batch's latency-bound LSD region growing overlap the next batch's streaming
  * kernels.  One batch in flight per handle.  Device frames and the out_dev arrays must stay valid and unchanged until lf_wait
  * returns: when a batch needs longer per-problem lists than the handle holds, lf_wait grows them and runs the batch a second
- * time from the same inputs into the same outputs (lf_lsd_list_capacity). */
+ * time from the same inputs into the same outputs (lf_lsd_list_capacity).
+ * What lf_wait covers: it waits for the handle's stream -- the batch, whatever was queued on the stream before it (a JPEG decode
+ * into the frame buffer) and whatever the caller queued on lf_get_stream's stream behind it up to the call.  With no batch in
+ * flight it returns LF_OK and a count of 0. */
 LF_API int lf_process_batch_async(lf_handle* h, const uint8_t* frames, int n_frames, int frames_on_device,
                            lf_segments* out_dev, int describe);
 LF_API int lf_wait(lf_handle* h, int* n_segments);
@@ -422,6 +433,9 @@ LF_API int lf_map_create(int device_id, const lf_map_config* cfg, lf_map** out);
 LF_API void lf_map_destroy(lf_map* m);
 LF_API const char* lf_map_last_error(const lf_map* m);      /* m == NULL: the last lf_map_create failure */
 LF_API int lf_map_get_stream(lf_map* m, void** hip_stream);
+/* the priority of the map's stream and the device's range (lf_stream_priority): the GREATEST priority, the map's kernels being
+ * the one serial chain of a pipelined front end */
+LF_API int lf_map_stream_priority(const lf_map* m, int* priority, int* least, int* greatest);
 LF_API int lf_map_synchronize(lf_map* m);
 /* append n entries as they are (color NULL: 255 = matches every colour; ground NULL: zeros); hits 1, last_seen -1 */
 LF_API int lf_map_seed(lf_map* m, const uint8_t* code32, const uint8_t* color, const double* ground4, int n, int on_device);

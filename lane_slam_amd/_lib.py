@@ -57,6 +57,7 @@ EXPORTS = (
     "lf_map_lane_pose_default_config", "lf_map_lane_pose", "lf_map_lane_pose_timing",
     "lf_sizeof_graph_config", "lf_sizeof_graph_result", "lf_map_graph_default_config", "lf_map_graph_solve", "lf_map_correct",
     "lf_map_graph_timing",
+    "lf_stream_priority", "lf_map_stream_priority",
 )
 LF_ALIGN_OK, LF_ALIGN_FEW, LF_ALIGN_DEGENERATE, LF_ALIGN_REJECTED = 0, 1, 2, 3
 ALIGN_STATUS = ("ok", "few", "degenerate", "rejected")
@@ -352,6 +353,9 @@ def load():
     lib.lf_synchronize.argtypes = [vp]
     lib.lf_get_stream.argtypes = [vp, ctypes.POINTER(vp)]
     lib.lf_get_stream.restype = ci
+    for f in ("lf_stream_priority", "lf_map_stream_priority"):
+        getattr(lib, f).argtypes = [vp] + [ctypes.POINTER(ci)] * 3
+        getattr(lib, f).restype = ci
     lib.lf_set_image.argtypes = [vp, vp, ci, ci, ci]
     lib.lf_detect_lines.argtypes = [vp, ci, vp, vp, vp, vp, ci, ctypes.POINTER(ci)]
     lib.lf_process_batch.argtypes = [vp, vp, ci, ci, ctypes.POINTER(LfSegments), ci, ci, ctypes.POINTER(ci)]

@@ -262,7 +262,8 @@ extern "C" int lf_create(const lf_config* cfg, int device_id, int max_frames, in
         if (hipSetDevice(device_id) != hipSuccess) { lf_set_error(h, LF_ERR_HIP, "hipSetDevice(%d) failed", device_id); rc = LF_ERR_HIP; break; }
         if ((rc = build_params(h)) != LF_OK) break;
         if ((rc = init_lsd(h)) != LF_OK) break;
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { lf_set_error(h, LF_ERR_HIP, "hipStreamCreate failed"); rc = LF_ERR_HIP; break; }
+        // (a BATCH stream: the handles of a process are dealt evenly over the hardware queues, lanefront_core.h)
+        if (create_stream(&h->stream, StreamClass::BATCH) != hipSuccess) { lf_set_error(h, LF_ERR_HIP, "hipStreamCreate failed"); rc = LF_ERR_HIP; break; }
         if ((rc = upload_tables(h)) != LF_OK) break;
         if ((rc = alloc_buffers(h)) != LF_OK) break;
     } while (0);
@@ -273,6 +274,12 @@ extern "C" int lf_create(const lf_config* cfg, int device_id, int max_frames, in
     }
     *out = h;
     return LF_OK;
+}
+
+extern "C" int lf_stream_priority(const lf_handle* h, int* priority, int* least, int* greatest)
+{
+    if (!h) return LF_ERR_NOT_INITIALISED;
+    return stream_priority(const_cast<lf_handle*>(h), priority, least, greatest);
 }
 
 extern "C" int lf_synchronize(lf_handle* h)

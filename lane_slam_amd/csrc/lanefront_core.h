@@ -4,7 +4,9 @@
 #pragma once
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <initializer_list>
+#include <mutex>
 #include <vector>
 #include "common.h"
 
@@ -53,6 +55,65 @@ inline int check_device(int device_id, const char* who, char* buf, size_t size)
         return LF_ERR_HIP;
     }
     if (device_id < 0 || device_id >= ndev) { snprintf(buf, size, "%s: device %d out of range (%d devices)", who, device_id, ndev); return LF_ERR_BAD_ARG; }
+    return LF_OK;
+}
+
+// The two classes of stream the library makes.  The runtime gives every stream one of the process's hardware queues (GPU_MAX_HW_QUEUES
+// of them for the normal priority, four by default; another priority has queues of its own), a new stream the queue with the fewest
+// streams, and streams that share a queue serialise.
+//   CHAIN  lf_map's: one stream, the serial chain of a pipelined front end (lf_map_create) -- the greatest priority where the device
+//          has a range, and with it a queue of its own.
+//   BATCH  lf_handle's: many streams, each a pipeline of independent batches, at the normal priority.  What matters is that they are
+//          dealt EVENLY: eight handles on four queues that already carry the default stream land 3 / 2 / 2 / 1, and the queue with three
+//          sets the cycle of all.  So the first BATCH stream of a device is preceded by idle streams that fill the level the default
+//          stream has begun (pad_normal_streams); from there on the handles are dealt 2 / 2 / 2 / 2, eighteen of them 5 / 5 / 4 / 4.
+//          (The least priority would give the handles a pool of their own without any padding, and does: it was measured 10 % slower
+//          than the uneven placement)
+enum class StreamClass { BATCH, CHAIN };
+
+// Idle streams, made once per device and kept for the life of the process, that make the normal-priority streams which are no
+// handle's -- the default stream and these -- a multiple of the hardware queue count.  GPU_MAX_HW_QUEUES is read, never set; with
+// more than eight queues nothing is made (a handful of handles rarely share a queue there, and the idle streams would be many).  An
+// application with normal-priority streams of its own that are not a multiple of the queue count shifts the deal by as many.
+inline hipError_t pad_normal_streams()
+{
+    static std::mutex mu;
+    static bool padded[64] = {};
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess || dev < 0 || dev >= 64) return e;
+    std::lock_guard<std::mutex> lock(mu);
+    if (padded[dev]) return hipSuccess;
+    const char* q = getenv("GPU_MAX_HW_QUEUES");
+    const int queues = q && *q ? atoi(q) : 4;
+    for (int i = 1; i < queues && queues <= 8; ++i) {          // (the default stream is the first of the level)
+        hipStream_t idle = nullptr;
+        if ((e = hipStreamCreateWithFlags(&idle, hipStreamNonBlocking)) != hipSuccess) return e;
+    }
+    padded[dev] = true;
+    return hipSuccess;
+}
+
+// a stream of the class on the current device
+inline hipError_t create_stream(hipStream_t* s, StreamClass cls)
+{
+    int least = 0, greatest = 0;
+    if (cls == StreamClass::CHAIN && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
+        return hipStreamCreateWithPriority(s, hipStreamNonBlocking, greatest);
+    if (cls == StreamClass::BATCH) { const hipError_t e = pad_normal_streams(); if (e != hipSuccess) return e; }
+    return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+}
+
+// the priority of the core's stream and the device's range (least == greatest: the device has one); any of them may be null
+inline int stream_priority(Core* c, int* priority, int* least, int* greatest)
+{
+    int p = 0, lo = 0, hi = 0;
+    LF_HIP_CHECK(c, hipSetDevice(c->device));
+    LF_HIP_CHECK(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
+    LF_HIP_CHECK(c, hipStreamGetPriority(c->stream, &p));
+    if (priority) *priority = p;
+    if (least) *least = lo;
+    if (greatest) *greatest = hi;
     return LF_OK;
 }
 

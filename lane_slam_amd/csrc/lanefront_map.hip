@@ -135,11 +135,7 @@ extern "C" int lf_map_create(int device_id, const lf_map_config* cfg, lf_map** o
         // The map's steps are the one serial chain of a pipelined front end (step k's association needs step k - 1's update): its
         // kernels go to a HIGH-PRIORITY stream, so that their workgroups (76 KB of LDS each) are not the last to find room between the
         // region-growing workgroups of the batches in flight (a plain stream where the device has no priority range)
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
-            TRY(hipStreamCreateWithPriority(&m->stream, hipStreamNonBlocking, greatest));
-        else
-            TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+        TRY(create_stream(&m->stream, StreamClass::CHAIN));
     }
     TRY(hipEventCreateWithFlags(&m->ev_state, hipEventDisableTiming));
     TRY(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
@@ -184,6 +180,12 @@ extern "C" int lf_map_get_stream(lf_map* m, void** hip_stream)
     if (!hip_stream) { set_error(m, LF_ERR_BAD_ARG, "lf_map_get_stream: null argument"); return LF_ERR_BAD_ARG; }
     *hip_stream = static_cast<void*>(m->stream);
     return LF_OK;
+}
+
+extern "C" int lf_map_stream_priority(const lf_map* m, int* priority, int* least, int* greatest)
+{
+    if (!m) return LF_ERR_NOT_INITIALISED;
+    return stream_priority(const_cast<lf_map*>(m), priority, least, greatest);
 }
 
 extern "C" int lf_map_synchronize(lf_map* m)

@@ -103,6 +103,14 @@ class FrontEnd(object):
         self._check(self.lib.lf_get_stream(self.h, ctypes.byref(p)))
         return p.value or 0
 
+    def stream_priority(self):
+        """(priority, least, greatest): the HIP priority of the handle's stream and the device's range (lf_stream_priority).
+        A handle's stream has the normal priority (0); the first handle of a process also makes the idle streams that deal the
+        handles' streams evenly over the hardware queues (include/lanefront.h)."""
+        p, lo, hi = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        self._check(self.lib.lf_stream_priority(self.h, ctypes.byref(p), ctypes.byref(lo), ctypes.byref(hi)))
+        return p.value, lo.value, hi.value
+
     # ------------------------------------------------------------------ host arrays
     def process_batch(self, frames, describe=True, n_frames=None):
         """frames: uint8 (n, in_rows, in_cols, 3) BGR on the host -- or, with n_frames given, the device

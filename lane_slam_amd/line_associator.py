@@ -73,6 +73,13 @@ class LineAssociator(object):
         self._check(self.lib.lf_map_get_stream(self.m, ctypes.byref(p)))
         return p.value or 0
 
+    def stream_priority(self):
+        """(priority, least, greatest): the HIP priority of the map's stream and the device's range (lf_map_stream_priority).
+        Where the device has a range, the map's stream has the greatest priority."""
+        p, lo, hi = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        self._check(self.lib.lf_map_stream_priority(self.m, ctypes.byref(p), ctypes.byref(lo), ctypes.byref(hi)))
+        return p.value, lo.value, hi.value
+
     def synchronize(self):
         self._check(self.lib.lf_map_synchronize(self.m))
 
