@@ -1790,7 +1790,9 @@ LF_API int lf_debug_wave(lf_handle* h, int op, int type, int arg, int diverge, c
  * per access (write != 0: stores, 4 or 16); run under `rocprofv3 --pmc FETCH_SIZE` / `WRITE_SIZE` (tools/fetch_probe.py) */
 LF_API int lf_debug_probe(lf_handle* h, int width, int write, size_t bytes, int reps);
 /* LSD stages alone on a binary image of the handle's working size (non-zero = edge pixel, colour
- * mask forced to all ones); host pointers; lines before normal-based endpoint ordering */
+ * mask forced to all ones); host pointers; lines before normal-based endpoint ordering.  Region growing runs in the
+ * form the handle was created under (LF_GROW_BITMAP, LF_GROW_LDS_LEVEL, LF_GROW_MIXED); left alone: the bit plane, behind
+ * it the mixed launch at the handle's current slice */
 LF_API int lf_debug_lsd_binary(lf_handle* h, const uint8_t* img, int rows, int cols, float* lines4, int cap, int* n_out);
 /* Canny's hysteresis alone on the caller's planes; host pointers.  planes_u8 [n_frames][rows][cols]: 0 = none, 1 = weak (above
  * the low threshold and a local maximum), 2 = strong (above the high one as well; a strong pixel counts as weak too).  rows and

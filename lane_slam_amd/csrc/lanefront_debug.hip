@@ -64,7 +64,9 @@ extern "C" int lf_debug_lsd_binary(lf_handle* h, const uint8_t* img, int rows, i
     h->lsd.grad(1, h->d_strong, h->d_maskbits, false, s);
     h->lsd.order(1, 0, s);
     h->lsd.label(1, false, s);
-    h->lsd.grow(1, h->d_slot_lines, h->d_counts, kGrowLdsKb[h->lsd.grow_lds_level], true, false, s);
+    // (the slice and the launch form follow LF_GROW_LDS_LEVEL / LF_GROW_MIXED as a batch's do; left alone, the mixed launch)
+    h->lsd.grow(1, h->d_slot_lines, h->d_counts, kGrowLdsKb[h->lsd.env_lds_level >= 0 ? h->lsd.env_lds_level : h->lsd.grow_lds_level],
+                h->lsd.env_mixed >= 0 ? h->lsd.env_mixed != 0 : true, false, s);
     LF_HIP_CHECK(h, hipGetLastError());
     int n = 0;
     if (const int rc = fetch(h, { { &n, h->d_counts.p, sizeof(int) } })) return rc;

@@ -96,6 +96,37 @@ void lfo_antiqsort_keys(int n, int32_t* keys);
 /* full detector: lines (x1,y1,x2,y2) float32, returns count (<= cap); extra = width,prec,nfa per line or NULL */
 int lfo_lsd_detect(const lfo_config* c, const uint8_t* img, int rows, int cols,
                    float* lines4, double* extra3, int cap);
+/* Optional census of what an input makes the detector do: for tests that must know their images reach a path.  Off by default, and
+ * with it off lfo_lsd_detect runs the code it always ran.  lfo_lsd_census_enable(1) zeroes the block and counts every later
+ * lfo_lsd_detect of this process into it, ..._enable(0) stops and zeroes; ..._fetch copies the block out.  Not thread safe.
+ *   decisions: in region_grow, every look at a neighbour that is not used yet and has a defined angle.  d = | n_theta - prec |, with
+ *   n_theta the folded angle difference is_aligned compares and prec the tolerance of that call (tau for refine's regrowth).
+ *   regions: every call of region_grow, by its tolerance (strictly inside (4 * 0.0043633, 0.7) or not: the first kind from the
+ *   detector's seed loop, the second from refine) and by its final size; the bins are tried in order, the first that fits counts:
+ *     [0] 1   [1] < min_reg_size   [2] == min_reg_size   [3] <= 63   [4] 64..65   [5] 66..192   [6] 193..255   [7] 256   [8] 257..
+ *   evaluation: per region of at least min_reg_size points. */
+typedef struct {
+    int64_t decisions;
+    int64_t mid_accepted, mid_rejected;       /* d < 0.0043633 rad */
+    int64_t near_accepted, near_rejected;     /* d < 2e-4 rad */
+    int64_t wrap_accepted;                    /* accepted after the > 3 pi / 2 fold */
+    int64_t seed_prec_inside, seed_prec_outside;
+    int64_t regrow_prec_inside, regrow_prec_outside;
+    int64_t size_bin[9];
+    int64_t size_max;
+    int64_t evaluated;
+    int64_t refine_entered;                   /* refine went past its first density test */
+    int64_t reduce_iterations;                /* reduce_region_radius loop bodies, all calls */
+    int64_t reduce_iterations_max;            /* ... the most in one call */
+    int64_t density_rejected;                 /* refine returned 0 */
+    int64_t improve_kept[6];                  /* rect_improve: the stage whose rectangle was kept, [0] none */
+    int64_t improve_reached[6];               /* rect_improve: the last stage entered, [0] the first return */
+    int64_t improve_first_return;             /* rect_improve: log_nfa > log_eps before any stage */
+    int64_t improve_last_guard;               /* rect_improve: steps of stage 5 its width guard held back */
+    int64_t size_one_short;                   /* regions of min_reg_size - 1 points (counted in size_bin[1] too) */
+} lfo_lsd_census;
+void lfo_lsd_census_enable(int on);
+void lfo_lsd_census_fetch(lfo_lsd_census* out);
 /* the detector's NFA of a rectangle with n pixels, k of them aligned (test helper, like lfo_ed_nfa) */
 double lfo_lsd_nfa(int n, int k, double p, double log_nt);
 

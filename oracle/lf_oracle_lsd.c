@@ -243,6 +243,57 @@ static inline int double_equal(double a, double b)
     return (abs_diff / abs_max) <= (REL_ERR_FACTOR * DBL_EPSILON);
 }
 
+/* ---- optional census (lf_oracle.h: lfo_lsd_census): what the inputs of a test reach.  Off, nothing below is touched. ---- */
+#define CENSUS_MID 0.0043633
+#define CENSUS_NEAR 2e-4
+static int g_census_on = 0;
+static lfo_lsd_census g_census;
+void lfo_lsd_census_enable(int on)
+{
+    g_census_on = on != 0;
+    memset(&g_census, 0, sizeof g_census);
+}
+void lfo_lsd_census_fetch(lfo_lsd_census* out) { *out = g_census; }
+
+/* one decision of region_grow on a neighbour that is not used yet: counted when its level-line angle is defined */
+static void census_decision(const Lsd* L, int address, double theta, double prec, int accepted)
+{
+    const double a = L->angles[address];
+    if (a == NOTDEF) return;
+    double n_theta = fabs(theta - a);
+    int folded = 0;
+    if (n_theta > M_3_2_PI) { n_theta = fabs(n_theta - M_2__PI); folded = 1; }
+    const double d = fabs(n_theta - prec);
+    lfo_lsd_census* s = &g_census;
+    s->decisions++;
+    if (d < CENSUS_MID) { if (accepted) s->mid_accepted++; else s->mid_rejected++; }
+    if (d < CENSUS_NEAR) { if (accepted) s->near_accepted++; else s->near_rejected++; }
+    if (accepted && folded) s->wrap_accepted++;
+}
+static void census_region(int n, double prec, int min_reg_size, int regrown)
+{
+    lfo_lsd_census* s = &g_census;
+    const int inside = prec > 4 * CENSUS_MID && prec < 0.7;
+    if (regrown) { if (inside) s->regrow_prec_inside++; else s->regrow_prec_outside++; }
+    else { if (inside) s->seed_prec_inside++; else s->seed_prec_outside++; }
+    /* the first bin that fits, in the order of lf_oracle.h */
+    int b;
+    if (n == 1) b = 0;
+    else if (n < min_reg_size) b = 1;
+    else if (n == min_reg_size) b = 2;
+    else if (n <= 63) b = 3;
+    else if (n <= 65) b = 4;
+    else if (n <= 192) b = 5;
+    else if (n <= 255) b = 6;
+    else if (n == 256) b = 7;
+    else b = 8;
+    s->size_bin[b]++;
+    if (n == min_reg_size - 1) s->size_one_short++;
+    if (n > s->size_max) s->size_max = n;
+}
+static int g_census_min_reg = 0;      /* the detector's min_reg_size, for the size bins */
+static int g_census_regrow = 0;       /* region_grow called by refine */
+
 static inline int is_aligned(const Lsd* L, int address, double theta, double prec)
 {
     if (address < 0) return 0;
@@ -276,7 +327,10 @@ static void region_grow(Lsd* L, int sx, int sy, RegPt* reg, int* reg_size, doubl
         for (int yy = yy_min; yy <= yy_max; ++yy) {
             int c_addr = xx_min + yy * W;
             for (int xx = xx_min; xx <= xx_max; ++xx, ++c_addr) {
-                if (L->used[c_addr] != 1 && is_aligned(L, c_addr, *reg_angle, prec)) {
+                if (L->used[c_addr] == 1) continue;
+                const int aligned = is_aligned(L, c_addr, *reg_angle, prec);
+                if (g_census_on) census_decision(L, c_addr, *reg_angle, prec, aligned);
+                if (aligned) {
                     L->used[c_addr] = 1;
                     RegPt* rp = &reg[n];
                     rp->x = xx; rp->y = yy; rp->addr = c_addr;
@@ -293,6 +347,7 @@ static void region_grow(Lsd* L, int sx, int sy, RegPt* reg, int* reg_size, doubl
         }
     }
     *reg_size = n;
+    if (g_census_on) census_region(n, prec, g_census_min_reg, g_census_regrow);
 }
 
 static double get_theta(const RegPt* reg, int reg_size, double x, double y, double reg_angle, double prec)
@@ -353,7 +408,9 @@ static int reduce_region_radius(Lsd* L, RegPt* reg, int* reg_size, double reg_an
     double radSq1 = distSq(xc, yc, rec->x1, rec->y1);
     double radSq2 = distSq(xc, yc, rec->x2, rec->y2);
     double radSq = radSq1 > radSq2 ? radSq1 : radSq2;
+    int iters = 0;
     while (density < density_th) {
+        if (g_census_on) { g_census.reduce_iterations++; if (++iters > g_census.reduce_iterations_max) g_census.reduce_iterations_max = iters; }
         radSq *= 0.75 * 0.75;
         for (int i = 0; i < *reg_size; ++i) {
             if (distSq(xc, yc, (double)reg[i].x, (double)reg[i].y) > radSq) {
@@ -374,6 +431,7 @@ static int refine(Lsd* L, RegPt* reg, int* reg_size, double reg_angle, double pr
 {
     double density = (double)(*reg_size) / (dist(rec->x1, rec->y1, rec->x2, rec->y2) * rec->width);
     if (density >= density_th) return 1;
+    if (g_census_on) g_census.refine_entered++;
     double xc = (double)reg[0].x, yc = (double)reg[0].y;
     const double ang_c = reg[0].angle;
     double sum = 0, s_sum = 0;
@@ -389,7 +447,9 @@ static int refine(Lsd* L, RegPt* reg, int* reg_size, double reg_angle, double pr
     }
     double mean_angle = sum / (double)n;
     double tau = 2.0 * sqrt((s_sum - 2.0 * mean_angle * sum) / (double)n + mean_angle * mean_angle);
+    g_census_regrow = 1;
     region_grow(L, reg[0].x, reg[0].y, reg, reg_size, &reg_angle, tau);
+    g_census_regrow = 0;
     if (*reg_size < 2) return 0;
     region2rect(reg, *reg_size, reg_angle, prec, p, rec);
     density = (double)(*reg_size) / (dist(rec->x1, rec->y1, rec->x2, rec->y2) * rec->width);
@@ -516,30 +576,36 @@ static double rect_nfa(const Lsd* L, const Rect* rec)
     return nfa(L, total_pts, alg_pts, rec->p);
 }
 
-static double rect_improve(const Lsd* L, Rect* rec, double LOG_EPS)
+/* kept: the stage (1-5) whose rectangle *rec holds at the end, 0 when none beat the first; first: the first return was taken;
+   guard: times the last stage's width guard held a step back; reached: the last stage entered */
+static double rect_improve_staged(const Lsd* L, Rect* rec, double LOG_EPS, int* kept, int* first, int* guard, int* reached)
 {
+    *kept = 0; *first = 0; *guard = 0; *reached = 0;
     double delta = 0.5;
     double delta_2 = delta / 2.0;
     double log_nfa = rect_nfa(L, rec);
-    if (log_nfa > LOG_EPS) return log_nfa;
+    if (log_nfa > LOG_EPS) { *first = 1; return log_nfa; }
     Rect r = *rec;
+    *reached = 1;
     for (int n = 0; n < 5; ++n) {
         r.p /= 2;
         r.prec = r.p * LSD_PI;
         double v = rect_nfa(L, &r);
-        if (v > log_nfa) { log_nfa = v; *rec = r; }
+        if (v > log_nfa) { log_nfa = v; *rec = r; *kept = 1; }
     }
     if (log_nfa > LOG_EPS) return log_nfa;
     r = *rec;
+    *reached = 2;
     for (int n = 0; n < 5; ++n) {
         if ((r.width - delta) >= 0.5) {
             r.width -= delta;
             double v = rect_nfa(L, &r);
-            if (v > log_nfa) { *rec = r; log_nfa = v; }
+            if (v > log_nfa) { *rec = r; log_nfa = v; *kept = 2; }
         }
     }
     if (log_nfa > LOG_EPS) return log_nfa;
     r = *rec;
+    *reached = 3;
     for (int n = 0; n < 5; ++n) {
         if ((r.width - delta) >= 0.5) {
             r.x1 += -r.dy * delta_2;
@@ -548,11 +614,12 @@ static double rect_improve(const Lsd* L, Rect* rec, double LOG_EPS)
             r.y2 += r.dx * delta_2;
             r.width -= delta;
             double v = rect_nfa(L, &r);
-            if (v > log_nfa) { *rec = r; log_nfa = v; }
+            if (v > log_nfa) { *rec = r; log_nfa = v; *kept = 3; }
         }
     }
     if (log_nfa > LOG_EPS) return log_nfa;
     r = *rec;
+    *reached = 4;
     for (int n = 0; n < 5; ++n) {
         if ((r.width - delta) >= 0.5) {
             r.x1 -= -r.dy * delta_2;
@@ -561,18 +628,32 @@ static double rect_improve(const Lsd* L, Rect* rec, double LOG_EPS)
             r.y2 -= r.dx * delta_2;
             r.width -= delta;
             double v = rect_nfa(L, &r);
-            if (v > log_nfa) { *rec = r; log_nfa = v; }
+            if (v > log_nfa) { *rec = r; log_nfa = v; *kept = 4; }
         }
     }
     if (log_nfa > LOG_EPS) return log_nfa;
     r = *rec;
+    *reached = 5;
     for (int n = 0; n < 5; ++n) {
         if ((r.width - delta) >= 0.5) {
             r.p /= 2;
             r.prec = r.p * LSD_PI;
             double v = rect_nfa(L, &r);
-            if (v > log_nfa) { *rec = r; log_nfa = v; }
-        }
+            if (v > log_nfa) { *rec = r; log_nfa = v; *kept = 5; }
+        } else ++*guard;
+    }
+    return log_nfa;
+}
+
+static double rect_improve(const Lsd* L, Rect* rec, double LOG_EPS)
+{
+    int kept, first, guard, reached;
+    const double log_nfa = rect_improve_staged(L, rec, LOG_EPS, &kept, &first, &guard, &reached);
+    if (g_census_on) {
+        g_census.improve_kept[kept]++;
+        g_census.improve_reached[reached]++;
+        g_census.improve_first_return += first;
+        g_census.improve_last_guard += guard;
     }
     return log_nfa;
 }
@@ -599,6 +680,7 @@ int lfo_lsd_detect(const lfo_config* c, const uint8_t* img, int rows, int cols,
     L.LOG_NT = 5 * (lfo_log10((double)W) + lfo_log10((double)H)) / 2 + lfo_log10(11.0);
     const int min_reg_size = (int)(-L.LOG_NT / lfo_log10(p));
     int n_lines = 0;
+    g_census_min_reg = min_reg_size;
     for (int i = 0; i < n_order; ++i) {
         int adx = order[i];
         if (used[adx] != 0 || angles[adx] == NOTDEF) continue;
@@ -607,10 +689,14 @@ int lfo_lsd_detect(const lfo_config* c, const uint8_t* img, int rows, int cols,
         region_grow(&L, adx % W, adx / W, reg, &reg_size, &reg_angle, prec);
         if (reg_size < min_reg_size) continue;
         Rect rec;
+        if (g_census_on) g_census.evaluated++;
         region2rect(reg, reg_size, reg_angle, prec, p, &rec);
         double log_nfa = -1;
         if (c->lsd_refine > 0) {
-            if (!refine(&L, reg, &reg_size, reg_angle, prec, p, &rec, c->lsd_density_th)) continue;
+            if (!refine(&L, reg, &reg_size, reg_angle, prec, p, &rec, c->lsd_density_th)) {
+                if (g_census_on) g_census.density_rejected++;
+                continue;
+            }
             if (c->lsd_refine >= 2) {
                 log_nfa = rect_improve(&L, &rec, c->lsd_log_eps);
                 if (log_nfa <= c->lsd_log_eps) continue;

@@ -58,6 +58,30 @@ class _FrameOut(ctypes.Structure):
     ]
 
 
+class LsdCensus(ctypes.Structure):
+    """ctypes mirror of `lfo_lsd_census` (oracle/lf_oracle.h)."""
+    _fields_ = [
+        ("decisions", ctypes.c_int64),
+        ("mid_accepted", ctypes.c_int64), ("mid_rejected", ctypes.c_int64),
+        ("near_accepted", ctypes.c_int64), ("near_rejected", ctypes.c_int64),
+        ("wrap_accepted", ctypes.c_int64),
+        ("seed_prec_inside", ctypes.c_int64), ("seed_prec_outside", ctypes.c_int64),
+        ("regrow_prec_inside", ctypes.c_int64), ("regrow_prec_outside", ctypes.c_int64),
+        ("size_bin", ctypes.c_int64 * 9), ("size_max", ctypes.c_int64),
+        ("evaluated", ctypes.c_int64), ("refine_entered", ctypes.c_int64),
+        ("reduce_iterations", ctypes.c_int64), ("reduce_iterations_max", ctypes.c_int64),
+        ("density_rejected", ctypes.c_int64),
+        ("improve_kept", ctypes.c_int64 * 6), ("improve_reached", ctypes.c_int64 * 6),
+        ("improve_first_return", ctypes.c_int64), ("improve_last_guard", ctypes.c_int64),
+        ("size_one_short", ctypes.c_int64),
+    ]
+
+    def as_dict(self):
+        """Plain ints and lists, field by field."""
+        return {k: (list(getattr(self, k)) if hasattr(getattr(self, k), "__len__") else int(getattr(self, k)))
+                for k, _ in self._fields_}
+
+
 def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
@@ -187,13 +211,22 @@ class Oracle(object):
                                       _p(ang), _p(mod), _p(order))
         return ang, mod, order[:n]
 
-    def lsd(self, img, cap=4096, extra=False):
+    def lsd(self, img, cap=4096, extra=False, census=False):
+        """census=True: the counters of lfo_lsd_census for this one call (a dict) follow the lines in the result."""
         img = np.ascontiguousarray(img, dtype=np.uint8)
         lines = np.empty((cap, 4), np.float32)
         ex = np.empty((cap, 3), np.float64)
+        if census:
+            self.lib.lfo_lsd_census_enable(1)
         n = self.lib.lfo_lsd_detect(ctypes.byref(self.c), _p(img), img.shape[0], img.shape[1],
                                     _p(lines), _p(ex), cap)
-        return (lines[:n].copy(), ex[:n].copy()) if extra else lines[:n].copy()
+        out = (lines[:n].copy(), ex[:n].copy()) if extra else (lines[:n].copy(),)
+        if census:
+            cs = LsdCensus()
+            self.lib.lfo_lsd_census_fetch(ctypes.byref(cs))
+            self.lib.lfo_lsd_census_enable(0)
+            out += (cs.as_dict(),)
+        return out if len(out) > 1 else out[0]
 
     # ---- per segment
     def find_normals(self, bw, lines):

@@ -70,7 +70,7 @@ def _run(hs, o, ec, reg_lds, by_components=False, n_components=None):
 def test_product_lsd_logic_matches_oracle(hostsim, oracle_parity):
     o = oracle_parity
     total = 0
-    for seed in range(10):             # seed 7 holds a thin rectangle that stops at rect_improve's last-stage width guard
+    for seed in range(10):             # (rect_improve's last-stage width guard is met by design in lsd_grow_cases.zigzag: test_lsd_grow_cases_cpu.py::test_evaluation_paths)
         bgr = o.preprocess(synth.make_frame(seed))
         bw = o.color_masks(o.bgr2hsv(bgr))
         edges = o.canny(bgr)
