@@ -13,7 +13,8 @@ Every default below is a constant of the reference, cited by file:line
 * sanity constants    src/line_sanity/src/line_sanity_node.py:17-23
 """
 import copy
-import ctypes
+
+from ._lib import LfConfig      # lf_config, as include/lanefront.h declares it
 
 # LSD seed order inside a gradient bin (include/lanefront.h, lf_config.lsd_seed_order): OpenCV 3.0 / 3.1 keep raster order,
 # 3.2 ... 3.4.5 (ROS Kinetic's 3.3.1) leave what std::sort leaves
@@ -91,30 +92,6 @@ def default_config(geometry="parity", in_size=(480, 640)):
                    "d_min": -0.15, "d_max": 0.3, "phi_min": -1.5, "phi_max": 1.5},
     }
     return cfg
-
-
-class LfConfig(ctypes.Structure):
-    """ctypes mirror of `lf_config` (include/lanefront.h)."""
-    _fields_ = [
-        ("in_rows", ctypes.c_int32), ("in_cols", ctypes.c_int32),
-        ("img_rows", ctypes.c_int32), ("img_cols", ctypes.c_int32),
-        ("top_cutoff", ctypes.c_int32),
-        ("ai_scale", ctypes.c_float * 3), ("ai_shift", ctypes.c_float * 3),
-        ("hsv_lo", (ctypes.c_int32 * 3) * 4), ("hsv_hi", (ctypes.c_int32 * 3) * 4),
-        ("dilation_kernel_size", ctypes.c_int32),
-        ("canny_lo", ctypes.c_double), ("canny_hi", ctypes.c_double),
-        ("lsd_refine", ctypes.c_int32), ("lsd_n_bins", ctypes.c_int32),
-        ("lsd_scale", ctypes.c_double), ("lsd_sigma_scale", ctypes.c_double),
-        ("lsd_quant", ctypes.c_double), ("lsd_ang_th", ctypes.c_double),
-        ("lsd_log_eps", ctypes.c_double), ("lsd_density_th", ctypes.c_double),
-        ("H", ctypes.c_double * 9), ("K", ctypes.c_double * 9), ("D", ctypes.c_double * 5),
-        ("R", ctypes.c_double * 9), ("P", ctypes.c_double * 12),
-        ("cam_w", ctypes.c_int32), ("cam_h", ctypes.c_int32),
-        ("lanewidth", ctypes.c_double), ("linewidth_white", ctypes.c_double),
-        ("linewidth_yellow", ctypes.c_double), ("d_min", ctypes.c_double),
-        ("d_max", ctypes.c_double), ("phi_min", ctypes.c_double), ("phi_max", ctypes.c_double),
-        ("lsd_seed_order", ctypes.c_int32), ("reserved0", ctypes.c_int32),
-    ]
 
 
 def fill_struct(s, cfg):

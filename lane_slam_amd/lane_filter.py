@@ -26,8 +26,7 @@ from .frontend import LanefrontError
 PARAM_NAMES = _lib.LANE_FILTER_PARAMS
 PREDICT, UPDATE = _lib.LF_LANE_FILTER_PREDICT, _lib.LF_LANE_FILTER_UPDATE
 WHITE, YELLOW, RED = 0, 1, 2
-POSE_DTYPE = np.dtype([("d", "f8"), ("phi", "f8"), ("max", "f8"), ("in_lane", "i4"), ("has_ml", "i4"), ("n_votes", "i4"),
-                       ("reserved", "i4")])
+POSE_DTYPE = np.dtype(_lib.LfLanePose)
 
 # src/duckietown/config/baseline/lane_filter/lane_filter_node/default.yaml
 DEFAULT_CONFIGURATION = dict(mean_d_0=0, mean_phi_0=0, sigma_d_0=0.1, sigma_phi_0=0.1, delta_d=0.02, delta_phi=0.1, d_max=0.3,

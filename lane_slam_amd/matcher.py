@@ -13,10 +13,6 @@ from . import _lib
 DMatch = collections.namedtuple("DMatch", "queryIdx trainIdx imgIdx distance")
 
 
-class _LfDmatch(ctypes.Structure):
-    _fields_ = [("queryIdx", ctypes.c_int32), ("trainIdx", ctypes.c_int32), ("imgIdx", ctypes.c_int32), ("distance", ctypes.c_float)]
-
-
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
@@ -116,7 +112,7 @@ class BinaryDescriptorMatcher(object):
     def match(self, queryDescriptors, masks=None):
         q = np.ascontiguousarray(queryDescriptors, dtype=np.uint8).reshape(-1, 32)
         arr, keep = self._masks(masks, q.shape[0])
-        out = (_LfDmatch * max(1, q.shape[0]))()
+        out = (_lib.LfDmatch * max(1, q.shape[0]))()
         n = ctypes.c_int()
         self.fe._check(self.lib.lf_matcher_match(self.fe.h, _ptr(q), q.shape[0], arr, out, ctypes.byref(n)))
         return self._list(out, 0, n.value)
@@ -124,7 +120,7 @@ class BinaryDescriptorMatcher(object):
     def knnMatch(self, queryDescriptors, k, masks=None, compactResult=False):
         q = np.ascontiguousarray(queryDescriptors, dtype=np.uint8).reshape(-1, 32)
         arr, keep = self._masks(masks, q.shape[0])
-        out = (_LfDmatch * max(1, q.shape[0] * int(k)))()
+        out = (_lib.LfDmatch * max(1, q.shape[0] * int(k)))()
         off = np.zeros(q.shape[0] + 1, np.int32)
         nl = ctypes.c_int()
         self.fe._check(self.lib.lf_matcher_knn_match(self.fe.h, _ptr(q), q.shape[0], int(k), arr, int(bool(compactResult)), _ptr(off), out, ctypes.byref(nl)))
@@ -137,7 +133,7 @@ class BinaryDescriptorMatcher(object):
         nl, total = ctypes.c_int(), ctypes.c_int()
         cap = max(1024, 4 * q.shape[0])
         while True:
-            out = (_LfDmatch * cap)()
+            out = (_lib.LfDmatch * cap)()
             rc = self.lib.lf_matcher_radius_match(self.fe.h, _ptr(q), q.shape[0], ctypes.c_float(maxDistance), arr, int(bool(compactResult)), _ptr(off),
                                                   out, cap, ctypes.byref(nl), ctypes.byref(total))
             if rc == -2 and total.value > cap:          # LF_ERR_CAPACITY: size and repeat

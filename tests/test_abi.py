@@ -26,6 +26,21 @@ def test_library_exports_every_declared_symbol():
     assert lib.lf_abi_version() == 5
 
 
+def test_every_declared_function_has_its_argument_list():
+    """argtypes is set on every entry point, with exactly as many parameters as the prototype has commas + 1 (none for `void`)"""
+    from lane_slam_amd import _lib
+    lib = _lib.load()
+    src = open(os.path.join(ROOT, "include", "lanefront.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    protos = dict(re.findall(r"\bLF_API\s[^;(]*?\b(lf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src))
+    assert sorted(protos) == _declared() and len(protos) == len(_lib.EXPORTS)
+    for name, params in protos.items():
+        argtypes = getattr(lib, name).argtypes
+        assert argtypes is not None, name
+        assert len(argtypes) == (0 if params.strip() == "void" else params.count(",") + 1), name
+        assert all(t is not None for t in argtypes), name
+
+
 def test_config_struct_matches_header_field_order():
     from lane_slam_amd.config import LfConfig
     src = open(os.path.join(ROOT, "include", "lanefront.h")).read()
