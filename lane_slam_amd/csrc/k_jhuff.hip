@@ -6,17 +6,23 @@
 //
 // A Huffman stream has no random access: where a code starts is only known once everything before it is decoded.  But
 // it SELF-SYNCHRONISES: a decoder started at a wrong position falls into step with the true sequence of codes after a
-// few symbols.  So the scan is cut into subsequences of 128 bytes, one thread each:
-//   k_jh_unstuff   per frame: removes the stuffed zeros (FF 00 -> FF) and the restart markers, notes where every restart
+// few symbols.  So the clean scan is cut into subsequences of JH_SB = 48 bytes:
+//   jh_unstuff_body  per frame: removes the stuffed zeros (FF 00 -> FF) and the restart markers, notes where every restart
 //                  interval begins (an interval starts byte aligned, at an MCU boundary, with a known decoder state) and
-//                  where the scan ends -- three passes over ~50 KB, prefix counts by ballot / LDS
-//   k_jh_decode    per frame, 256 threads.  Pass 0: every thread decodes its subsequence from an ASSUMED state (first
-//                  bit, start of an MCU) and records the state in which it crosses into the next subsequence.  Passes
-//                  1, 2, ...: a thread whose predecessor handed over a different state than the one it started from decodes
-//                  again from that state; when nothing changes any more every subsequence has its true entry state
-//                  (subsequence 0 of an interval is exact from the start, so after pass p the first p + 1 are: at most as
-//                  many passes as subsequences; measured on 640x480 camera-like frames: 14 - 25, because the block's place in the MCU, part of the
-//                  state, never re-synchronises by itself -- DESIGN.md section 8).  Then the blocks completed per subsequence are
+//                  where the scan ends -- three passes over ~50 KB in chunks of 128 raw bytes per thread, prefix counts by
+//                  shuffle / LDS.  At the head of k_jh_decode (its 512 threads, the raw scan in LDS) when every raw scan of
+//                  the batch fits LDS; otherwise, and under LF_JH_SPLIT, the kernel k_jh_unstuff (256 threads) in front
+//   k_jh_decode    per frame, JH_TD = 512 threads.  Pass 0: the scan is decoded once per place in the MCU -- units of `sup`
+//                  subsequences, one lane per (unit, hypothesis "block h, coefficient 0 at the unit's first bit"), the state
+//                  noted where it crosses into every subsequence; the units' place maps are composed by a scan, which names
+//                  the hypothesis each unit is entered with.  Passes 1, 2, ...: a subsequence whose predecessor hands over
+//                  another state than the one it was entered with adopts the notes of the hypothesis that crossed in exactly
+//                  that state, or is decoded again from it (compacted: a dirty list of up to JH_DL = 2 048 subsequences;
+//                  larger scans run every subsequence as its own unit, unlisted); when nothing changes any more every
+//                  subsequence has its true entry state (subsequence 0 of an interval is exact from the start, so after
+//                  pass p the first p + 1 are: at most as many passes as subsequences; measured on 640x480 camera-like
+//                  frames: 3 - 5, and 22 - 31 before the scan was decoded once per place, because the block's place in the
+//                  MCU, part of the state, never re-synchronises by itself -- DESIGN.md section 8).  Then the blocks completed per subsequence are
 //                  prefix-summed and a last decode writes the quantised coefficients (int16, natural order, dense 64 per
 //                  block; DC still as differences) and performs the checks of a sequential decoder: invalid code, run past
 //                  63, DC size > 11, reading beyond the interval, a restart interval of the wrong length.  Last, DC
@@ -693,7 +699,7 @@ __global__ __launch_bounds__(JH_TD) void k_jh_decode(jpeg::DevFrame* __restrict_
     uint8_t* clean = clean_all + F.clean_off;
     uint32_t* sb = seg_begin_all + F.seg_off;
     if (unstuff_here) {
-        // the frame's raw scan through LDS (every scan of the batch fits: the host has checked), unstuffed into `clean` by all 1 024
+        // the frame's raw scan through LDS (every scan of the batch fits: the host has checked), unstuffed into `clean` by all JH_TD
         // threads: k_jh_unstuff's 256 took 0.17 ms per batch for it, and a launch
         const uint32_t L = F.scan_len;
         const uint32_t* src = reinterpret_cast<const uint32_t*>(bytes + F.scan_off);     // scan_off is a multiple of 16
