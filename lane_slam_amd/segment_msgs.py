@@ -63,6 +63,25 @@ def lane_pose_message(header, d, phi, in_lane, sigma_d=0.0, sigma_phi=0.0, statu
     return bytes(header) + struct.pack("<ffffiB", float(d), float(sigma_d), float(phi), float(sigma_phi), int(status), 1 if in_lane else 0)
 
 
+def wheels_cmd_message(header, vel_left, vel_right):
+    """The serialised duckietown_msgs/WheelsCmdStamped (Header header | float32 vel_left | float32 vel_right) the odometry node
+    subscribes to (odometry.py:46): header_bytes(...) + f32 vel_left | f32 vel_right."""
+    return bytes(header) + struct.pack("<ff", float(vel_left), float(vel_right))
+
+
+def wheels_cmd_from_message(msg):
+    """(seq, secs, nsecs, frame_id, vel_left, vel_right) of a serialised WheelsCmdStamped: the inverse of wheels_cmd_message.  The
+    velocities are the message's float32 values as Python floats, which is what Odometry.step takes."""
+    msg = bytes(msg)
+    if len(msg) < 16:
+        raise ValueError("WheelsCmdStamped: %d bytes are no header" % len(msg))
+    seq, secs, nsecs, n = struct.unpack_from("<IIII", msg, 0)
+    if len(msg) != 16 + n + 8:
+        raise ValueError("WheelsCmdStamped: %d bytes for a frame_id of %d" % (len(msg), n))
+    vel_left, vel_right = struct.unpack_from("<ff", msg, 16 + n)
+    return seq, secs, nsecs, msg[16:16 + n].decode(), vel_left, vel_right
+
+
 def split_segment_list(msg):
     """(seq, secs, nsecs, frame_id, body bytes, records view) of a serialised SegmentList."""
     msg = bytes(msg)

@@ -8,13 +8,14 @@ wire bodies.  The first batch is checked against the oracle (pixels, segments, m
                                 [--overlay-jpeg DIR] [--align | --smooth | --localize] [--prune EVERY[:min_hits[:age]]]
                                 [--near RADIUS[:max_offset[:max_sin]]] [--lanes RADIUS[:max_offset[:max_sin[:min_entries]]]]
                                 [--polylines CELL[:max_gap[:reach]]] [--lane-pose RADIUS[:max_sin]] [--lane-filter]
-                                [--close-loops N]
+                                [--close-loops N] [--wheels FILE.npz]
 
 --map-jpeg writes the final map as the reference's README shows it (show_map's coloured segments seen from above, lf_map_render
 fitted to the map) as a JPEG: rendered and encoded on the device, only the file's bytes cross the bus.
 --overlay-jpeg replays the frames once more when the map is final: each batch is decoded, rectified (lf_rectify_batch), has the map
-drawn into it as the camera sees it (lf_map_render_camera; the replay has no odometry, so every frame's pose is the identity, as the
-map's entries are in the robot frame) and is encoded on the device; the files go to DIR/%06d.jpg.
+drawn into it as the camera sees it (lf_map_render_camera; without --wheels every frame's pose is the identity, as the map's
+entries are then in the robot frame; with it, the pose the frame's batch was stepped with) and is encoded on the device; the files
+go to DIR/%06d.jpg.
 --prune EVERY[:min_hits[:age]] culls the map every EVERY steps (lf_map_prune): entries with fewer than min_hits hits (default 2) that
 were last seen more than `age` steps ago (default 8) go, and so does every entry that a better one of its colour covers within 0.02 m,
 show_map's marker width; the seeded entries stay.  Each prune prints its result line.
@@ -30,12 +31,18 @@ vertices, closed or open, entries, hits, both ends, length.
 --lane-pose RADIUS[:max_sin] asks the map, behind every batch's update, where the poses that the step used are in their lane
 (lf_map_lane_pose; the polyline and lane rules are --polylines' and --lanes' fields, or the library's) and prints per batch the frames
 with a pose, the frames in lane, the median d and phi of the posed frames and the last frame's (d, phi, in_lane).  --lane-filter
-runs the histogram lane filter (lf_lane_filter_*, the reference's default configuration, no odometry: update only) over the same
-batches' segments; with both flags the filter's values stand beside the map's: two independent paths to the same two numbers.
+runs the histogram lane filter (lf_lane_filter_*, the reference's default configuration; update only without --wheels, predict and
+update with it) over the same batches' segments; with both flags the filter's values stand beside the map's: two independent paths
+to the same two numbers.
 --close-loops N (with --localize) keeps a pose graph with one key per batch (lane_slam_amd.PoseGraph: the pose the batch's first frame
 was stepped with).  When that frame was localised with at least the configured inliers in a part of the map that is at least N keys
 old, the loop edge is added, the graph is solved on the device (lf_map_graph_solve) and the map moved (lf_map_correct); it prints the
 cost before and after, the largest shift of an endpoint and the solver's and the correction's milliseconds.
+--wheels FILE.npz gives the replay its odometry (lane_slam_amd.Odometry, lf_odometry_*): the file holds a log's wheel commands
+(stamp_ns int64, vel_left, vel_right) and one stamp per replayed frame (frame_stamp_ns).  Every batch's poses are then the
+odometry's at its frames' stamps (the right-handed flip_y form) instead of zeros, --map-jpeg draws the driven trajectory in blue,
+and --lane-filter predicts with (dt, v = (Vl + Vr) / 2, w = (Vr - Vl) / l) of the command each frame's pose comes from before it
+updates: the odometry's kinematics, not the car_cmd the lane_filter node listens to.  Without the flag nothing changes.
 """
 import argparse, io, os, sys, time
 import numpy as np
@@ -87,8 +94,12 @@ ap.add_argument("--close-loops", type=int, default=None, metavar="N",
                 help="with --localize: one pose-graph key per batch; a first frame localised in a part of the map at least N keys old closes "
                      "a loop (lf_map_graph_solve, lf_map_correct); prints cost0 -> cost, the shift and the milliseconds")
 ap.add_argument("--lane-filter", action="store_true",
-                help="run the histogram lane filter over every batch's segments (update only: the replay has no odometry) and print its last "
-                     "frame's (d, phi, in_lane) per batch, beside --lane-pose's when both are given")
+                help="run the histogram lane filter over every batch's segments (update only without --wheels; with it, predict from the "
+                     "odometry's kinematics first: dt, v = (Vl + Vr) / 2 and w = (Vr - Vl) / l of the command behind each frame's pose, not the "
+                     "node's car_cmd) and print its last frame's (d, phi, in_lane) per batch, beside --lane-pose's when both are given")
+ap.add_argument("--wheels", default=None, metavar="FILE.npz",
+                help="a log's wheel commands and frame stamps (keys stamp_ns, vel_left, vel_right, frame_stamp_ns): every batch's poses come "
+                     "from the odometry on the device instead of zeros, and --map-jpeg draws the trajectory")
 args = ap.parse_args()
 if args.close_loops is not None and (not args.localize or args.close_loops < 1):
     ap.error("--close-loops N goes with --localize, N >= 1")
@@ -175,8 +186,19 @@ if lane_pose_fields:
     rules = dict(polylines_fields or {}, **{("lanes_" + k if k in ("radius", "max_sin") else k): v for k, v in (lanes_fields or {}).items()})
     lane_pose_cfg = live.lane_pose_config(**dict(rules, **lane_pose_fields))
 if args.lane_filter:
-    from lane_slam_amd.lane_filter import DEFAULT_CONFIGURATION, LaneFilterBatch, UPDATE
+    from lane_slam_amd.lane_filter import DEFAULT_CONFIGURATION, LaneFilterBatch, PREDICT, UPDATE
     lane_filter = LaneFilterBatch(DEFAULT_CONFIGURATION, n_streams=1, max_frames=B)
+odometry = wheels = None
+if args.wheels:
+    from lane_slam_amd import Odometry
+    with np.load(args.wheels) as z:
+        wheels = {k: np.ascontiguousarray(z[k], np.int64 if k.endswith("stamp_ns") else np.float64).reshape(-1)
+                  for k in ("stamp_ns", "vel_left", "vel_right", "frame_stamp_ns")}
+    if len(wheels["frame_stamp_ns"]) < (args.frames // B) * B:
+        ap.error("--wheels: %d frame stamps for %d replayed frames" % (len(wheels["frame_stamp_ns"]), (args.frames // B) * B))
+    # (x, -y, theta): the reference's odometry moves along (cos theta, -sin theta); the map's pose solvers are right-handed
+    odometry = Odometry(n_streams=1, max_commands=max(len(wheels["stamp_ns"]), 1), max_frames=B, flip_y=True)
+    wheels_used = 0                      # the commands the odometry has taken so far
 pose_graph = None
 if args.close_loops is not None:
     from lane_slam_amd import PoseGraph
@@ -187,10 +209,24 @@ ok_frames, used_endpoints, all_frames = [0, 0], [0, 0], 0
 t0 = time.perf_counter()
 n_seg = n_kept = n_matched = wire = 0
 last_odometry = last_corrected = (0.0, 0.0, 0.0)
+stepped_poses = []                       # per batch, the poses the map was updated with (the overlay draws the map from them)
 for b0 in range(0, args.frames - B + 1, B):
     fe.decode_jpeg_batch(msgs[b0:b0 + B], n_threads=args.threads, device_ptr=dev_frames)
     seg = fe.process_batch(dev_frames, n_frames=B)
-    used_poses = np.zeros((B, 3))
+    batch_poses, dt_v_w = np.zeros((B, 3)), None
+    if odometry is not None:
+        # the commands up to the batch's last frame; a frame behind the call's first command holds the pose the odometry stood at
+        fs = wheels["frame_stamp_ns"][b0:b0 + B]
+        upto = int(np.searchsorted(wheels["stamp_ns"], fs.max(), side="right"))
+        cut = slice(wheels_used, max(upto, wheels_used))
+        batch_poses = odometry.step(wheels["stamp_ns"][cut], wheels["vel_left"][cut], wheels["vel_right"][cut], fs)
+        cmd = np.where(odometry.last["frame_cmd"] >= 0, odometry.last["frame_cmd"] + wheels_used, -1)
+        wheels_used = cut.stop
+        # the kinematics of the command behind each frame's pose: its gap to the command before it, its speed and its turn rate
+        gap = np.where(cmd > 0, (wheels["stamp_ns"][cmd] - wheels["stamp_ns"][np.maximum(cmd - 1, 0)]) / 1e9, 0.0)
+        vl, vr = np.where(cmd >= 0, wheels["vel_left"][cmd], 0.0), np.where(cmd >= 0, wheels["vel_right"][cmd], 0.0)
+        dt_v_w = np.stack([gap, (vl + vr) / 2, (vr - vl) / odometry.wheel_distance], axis=1)
+    used_poses = batch_poses.copy()
     if seg.n:
         d = {k: torch.from_numpy(np.ascontiguousarray(getattr(seg, k))).cuda() for k in ("frame_offset", "code", "color", "keep", "ground")}
         di = torch.zeros(seg.n, dtype=torch.int32, device="cuda")
@@ -201,16 +237,16 @@ for b0 in range(0, args.frames - B + 1, B):
             # the candidates per segment against the map as this step finds it (the step's own association does not report them)
             dn = torch.zeros(seg.n, dtype=torch.int32, device="cuda")
             torch.cuda.synchronize()
-            pr = LineAssociator.carry(np.zeros((B, 3)), last_odometry, last_corrected) if args.smooth else None
+            pr = LineAssociator.carry(batch_poses, last_odometry, last_corrected) if args.smooth else (batch_poses if odometry is not None else None)
             live.associate_near_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), pr, near_cfg, dn.data_ptr())
             live.synchronize()
             n_near_sum += int(dn.sum().item())
         if args.smooth:
-            # (the replay has no odometry: every pose is the identity before the previous batch's correction is carried into it; a
-            # chain that finds nothing to hold on to is DEGENERATE and keeps its poses)
-            poses = LineAssociator.carry(np.zeros((B, 3)), last_odometry, last_corrected)
+            # (without --wheels every pose is the identity before the previous batch's correction is carried into it; a chain that
+            # finds nothing to hold on to is DEGENERATE and keeps its poses)
+            poses = LineAssociator.carry(batch_poses, last_odometry, last_corrected)
             out = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=poses, step=b0 // B, smooth=live.smooth_config())
-            last_odometry, last_corrected = (0.0, 0.0, 0.0), tuple(out[2][-1])
+            last_odometry, last_corrected = tuple(batch_poses[-1]), tuple(out[2][-1])
             used_poses = np.asarray(out[2], np.float64)
             counts = np.bincount(out[3]["status"], minlength=4)
             print("batch %d smoothed: %s" % (b0 // B, ", ".join("%d %s" % (c, k) for k, c in zip(_lib.ALIGN_STATUS, counts))))
@@ -248,8 +284,8 @@ for b0 in range(0, args.frames - B + 1, B):
                         if moved is not None:
                             last_corrected = tuple(pose_graph.key_pose[-1])
         elif args.align:
-            # (the replay has no odometry: every prior is the identity, and the seeded map has no geometry to align with)
-            out = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=np.zeros((B, 3)), step=b0 // B,
+            # (without --wheels every prior is the identity, and the seeded map has no geometry to align with)
+            out = live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=batch_poses, step=b0 // B,
                                    align=live.align_config())
             res, used_poses = out[3], np.asarray(out[2], np.float64)
             counts = np.bincount(res["status"], minlength=4)
@@ -260,12 +296,12 @@ for b0 in range(0, args.frames - B + 1, B):
                 si = torch.zeros(seg.n, dtype=torch.int32, device="cuda")
                 sd = torch.zeros(seg.n, dtype=torch.float32, device="cuda")
                 torch.cuda.synchronize()
-                sres = shadow.step_device(None, ptrs, seg.n, B, si.data_ptr(), sd.data_ptr(), poses=np.zeros((B, 3)), step=b0 // B,
+                sres = shadow.step_device(None, ptrs, seg.n, B, si.data_ptr(), sd.data_ptr(), poses=batch_poses, step=b0 // B,
                                           align=shadow.align_config())[3]
                 shadow.synchronize()
                 ok_frames[1] += int((sres["status"] == 0).sum()); used_endpoints[1] += int(sres["n_used"][sres["status"] == 0].sum())
         else:
-            live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), step=b0 // B)
+            live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=batch_poses if odometry is not None else None, step=b0 // B)
         live.synchronize()
         step = b0 // B
         if prune_every and (step + 1) % prune_every == 0:
@@ -273,6 +309,7 @@ for b0 in range(0, args.frames - B + 1, B):
             print("step %d pruned: %d -> %d entries (weak %d, covered %d)" % (step, r["size_before"], r["size_after"], r["dropped"]["weak"], r["dropped"]["covered"]))
         n_matched += int((di >= 0).sum().item())
         n_kept += int(seg.keep.sum())
+    stepped_poses.append(used_poses)
     told = []
     if lane_pose_cfg is not None:
         lres, lp = live.lane_pose(used_poses, lane_pose_cfg)
@@ -281,7 +318,7 @@ for b0 in range(0, args.frames - B + 1, B):
                     % (lres["n_posed"], B, lres["n_edges"][0], lres["n_edges"][1], int(lp["in_lane"].sum()),
                        np.median(posed["d"]) if len(posed) else 0.0, np.median(posed["phi"]) if len(posed) else 0.0, lp["d"][-1], lp["phi"][-1], lp["in_lane"][-1]))
     if lane_filter is not None:
-        fp = lane_filter.step(seg, np.zeros((B, 3)), phases=UPDATE)["poses"]
+        fp = (lane_filter.step(seg, np.zeros((B, 3)), phases=UPDATE) if dt_v_w is None else lane_filter.step(seg, dt_v_w, phases=PREDICT | UPDATE))["poses"]
         told.append("filter: last frame (d %+.4f, phi %+.4f, in_lane %d), %d votes" % (fp["d"][-1], fp["phi"][-1], fp["in_lane"][-1], int(fp["n_votes"].sum())))
     if told:
         print("batch %d lane pose: %s" % (b0 // B, " | ".join(told)))
@@ -320,7 +357,8 @@ if args.map_jpeg:
     files = torch.zeros(stride, dtype=torch.uint8, device="cuda")
     sizes = torch.zeros(1, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
-    n_drawn, n_skipped, view = live.render_device(image.data_ptr(), rows=side, cols=side, view="fit", min_last_seen=0)     # (the seeded codes have no place)
+    n_drawn, n_skipped, view = live.render_device(image.data_ptr(), rows=side, cols=side, view="fit", min_last_seen=0,     # (the seeded codes have no place)
+                                                  trajectory=odometry.trajectory(0) if odometry is not None else None)
     live.synchronize()
     fe.encode_jpeg_device(image.data_ptr(), 1, side, side, files.data_ptr(), stride, sizes.data_ptr())
     fe.synchronize()
@@ -346,7 +384,7 @@ if args.overlay_jpeg:
         fe.decode_jpeg_batch(msgs[b0:b0 + B], n_threads=args.threads, device_ptr=dev_frames)
         fe.rectify_device(dev_frames, B, in_rows, in_cols, 3, rect.data_ptr())
         fe.synchronize()                                              # (the map's stream does not wait for the handle's)
-        drawn += live.render_camera_device(rect.data_ptr(), rect.data_ptr(), B, None, view).sum(axis=0)
+        drawn += live.render_camera_device(rect.data_ptr(), rect.data_ptr(), B, stepped_poses[b0 // B] if odometry is not None else None, view).sum(axis=0)
         live.synchronize()
         fe.encode_jpeg_device(rect.data_ptr(), B, cam_h, cam_w, files.data_ptr(), stride, sizes.data_ptr())
         fe.synchronize()
