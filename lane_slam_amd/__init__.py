@@ -16,6 +16,8 @@ The package is a thin host-side mirror of the reference's interfaces for this pa
                         device; LaneFilterBatch runs many filter streams over a FrontEnd batch's segments
   OdometryNode     <->  odometry.OdometryNode: wheel commands to the `map -> duck` pose; Odometry integrates a whole log's commands
                         for many robots in one call and samples the poses at the frames' stamps (include/lanefront_odometry.h)
+  FrameMotion           the relative motion between frames of a batch from their own segments and LBD codes, with no map: match,
+                        hypothesis search and Gauss-Newton refinement for many pairs in one launch (include/lanefront_motion.h)
   FrontEnd         <->  batch form of line_detector_node / ground_projection_node /
                         line_sanity_node callbacks + BinaryDescriptor / BinaryDescriptorMatcher
 There is no CPU fallback: importing works anywhere, but creating a detector without the
@@ -25,10 +27,11 @@ from .config import (COLOR_NAMES, DEFAULT_DETECTOR_CONFIGURATION, RED, WHITE, YE
 from .frontend import FrontEnd, LanefrontError, Segments
 from .lane_filter import LaneFilterBatch, LaneFilterHistogram
 from .line_associator import LineAssociator
+from .motion import FrameMotion
 from .odometry import Odometry, OdometryNode
 from .pose_graph import PoseGraph
 from .matcher import BinaryDescriptorMatcher, BinaryDescriptorParams, DMatch
 from .line_detector_hip import Detections, LineDetector2Dense, LineDetectorEDLines, LineDetectorHIP, LineDetectorHSV, LineDetectorInterface
 
-__all__ = ["LaneFilterBatch", "LaneFilterHistogram", "Odometry", "OdometryNode", "BinaryDescriptorMatcher", "BinaryDescriptorParams", "DMatch", "LineAssociator", "PoseGraph", "FrontEnd", "LanefrontError", "Segments", "LineDetectorHIP", "LineDetectorHSV", "LineDetector2Dense", "LineDetectorEDLines", "LineDetectorInterface", "Detections",
+__all__ = ["LaneFilterBatch", "LaneFilterHistogram", "FrameMotion", "Odometry", "OdometryNode", "BinaryDescriptorMatcher", "BinaryDescriptorParams", "DMatch", "LineAssociator", "PoseGraph", "FrontEnd", "LanefrontError", "Segments", "LineDetectorHIP", "LineDetectorHSV", "LineDetector2Dense", "LineDetectorEDLines", "LineDetectorInterface", "Detections",
            "default_config", "DEFAULT_DETECTOR_CONFIGURATION", "WHITE", "YELLOW", "RED", "COLOR_NAMES"]

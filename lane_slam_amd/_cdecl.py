@@ -35,10 +35,12 @@ class Header(object):
     declaration order, opaque (the names of types declared without a body) and functions {name: Function} for the prototypes that
     start with `api`.  Typing rule: scalars by their C type; a pointer field, and a pointer parameter to an opaque type, a scalar,
     void or another pointer, is an address (c_void_p); a pointer parameter to a struct with a body is POINTER(its class); an array
-    parameter is a pointer; a void return is None and a `const char*` return c_char_p."""
+    parameter is a pointer; a void return is None and a `const char*` return c_char_p.  base: the Header of a header that `text`
+    includes: its structs, opaque types and constants may be named here, and stay its own."""
 
-    def __init__(self, text, api="LF_API"):
+    def __init__(self, text, api="LF_API", base=None):
         self.api, self.constants, self.structs, self.opaque, self.functions = api, {}, {}, [], {}
+        self.base = base
         statements = self._statements(self._preprocess(text))
         prototypes = [s for s in statements if s.startswith(api + " ")]
         for s in statements:                 # types first: a prototype may name a struct that is defined after it
@@ -52,6 +54,8 @@ class Header(object):
         word = word.strip()
         if word in self.constants:
             return self.constants[word]
+        if self.base is not None and word in self.base.constants:
+            return self.base.constants[word]
         m = re.match(r"^\(?\s*(-?\s*(?:0[xX][0-9a-fA-F]+|\d+))[uUlL]*\s*\)?$", word)
         if not m:
             raise CDeclError("not an integer constant: %r in `%s`" % (word, where))
@@ -130,6 +134,8 @@ class Header(object):
             return None, self.structs[name]
         if name == "void" or name in self.opaque:
             return None, None
+        if self.base is not None:
+            return self.base._base(name, where)
         raise CDeclError("unknown type %r in `%s`" % (name, where))
 
     def _struct(self, c_name, body, where):

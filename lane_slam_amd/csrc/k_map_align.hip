@@ -13,22 +13,6 @@
 namespace lf {
 namespace ma {
 
-namespace {
-
-// the contract's solve: the priors, then the LDL^T; false: a pivot or a component of t is not finite or the pivot is <= 0
-__device__ __forceinline__ bool solve(const lf_align_config& c, const Sums& s, double x, double y, double th, double x0, double y0, double th0,
-                                      double& t0, double& t1, double& t2)
-{
-    const double a00 = s.n00 + c.prior_xy, a11 = s.n11 + c.prior_xy, a22 = s.n22 + c.prior_theta;
-    const double a01 = s.n01, a02 = s.n02, a12 = s.n12;
-    const double b0 = -(s.g0 + c.prior_xy * (x - x0)), b1 = -(s.g1 + c.prior_xy * (y - y0)), b2 = -(s.g2 + c.prior_theta * (th - th0));
-    Ldl f;
-    if (!ldl_factor(a00, a01, a02, a11, a12, a22, f)) return false;
-    return ldl_apply(f, b0, b1, b2, t0, t1, t2);
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(kPartials) void k_map_align(lf_align_config c, MapDevice md, Batch b)
 {
     const int f = blockIdx.x, lane = threadIdx.x;

@@ -1,7 +1,8 @@
 // The device statements lf_map_align and lf_map_smooth share (include/lanefront.h "lf_map_align" is their contract): a frame's
 // pairs, an endpoint's contribution to the partial sums, the fold of the 64 partials and the 3 x 3 LDL^T.  k_map_align.hip and
 // k_map_smooth.hip include it and run the same statements; k_map_localize.hip takes the map's size, the frame's range and the
-// pairs from it.  All three are built with -ffp-contract=off.
+// pairs from it; k_frame_motion.hip runs the endpoint sums, the fold and the solve over pairs it makes itself with line_of.  All
+// four are built with -ffp-contract=off.
 #pragma once
 #include "detmath.h"
 #include "k_map_align.h"
@@ -148,6 +149,31 @@ __device__ __forceinline__ bool ldl_apply(const Ldl& f, double b0, double b1, do
     t1 = e1 - f.l21 * t2;
     t0 = (e0 - f.l10 * t1) - f.l20 * t2;
     return finite(t0) && finite(t1) && finite(t2);
+}
+
+// the contract's solve of one frame's step: the priors, then the LDL^T; false: a pivot or a component of t is not finite or the
+// pivot is <= 0
+__device__ __forceinline__ bool solve(const lf_align_config& c, const Sums& s, double x, double y, double th, double x0, double y0, double th0,
+                                      double& t0, double& t1, double& t2)
+{
+    const double a00 = s.n00 + c.prior_xy, a11 = s.n11 + c.prior_xy, a22 = s.n22 + c.prior_theta;
+    const double a01 = s.n01, a02 = s.n02, a12 = s.n12;
+    const double b0 = -(s.g0 + c.prior_xy * (x - x0)), b1 = -(s.g1 + c.prior_xy * (y - y0)), b2 = -(s.g2 + c.prior_theta * (th - th0));
+    Ldl f;
+    if (!ldl_factor(a00, a01, a02, a11, a12, a22, f)) return false;
+    return ldl_apply(f, b0, b1, b2, t0, t1, t2);
+}
+
+// the contract's line of a segment with the finite ground values ax, ay, bx, by (gather's statements for an entry); false: l2 is
+// not finite or not > 0
+__device__ __forceinline__ bool line_of(double ax, double ay, double bx, double by, Line& p)
+{
+    const double dx = bx - ax, dy = by - ay;
+    const double l2 = dx * dx + dy * dy;
+    if (!(finite(l2) && l2 > 0.0)) return false;
+    const double len = dm::dsqrt(l2);
+    p.nx = (-dy) / len; p.ny = dx / len; p.ax = ax; p.ay = ay;
+    return true;
 }
 
 }  // namespace ma

@@ -8,7 +8,7 @@ wire bodies.  The first batch is checked against the oracle (pixels, segments, m
                                 [--overlay-jpeg DIR] [--align | --smooth | --localize] [--prune EVERY[:min_hits[:age]]]
                                 [--near RADIUS[:max_offset[:max_sin]]] [--lanes RADIUS[:max_offset[:max_sin[:min_entries]]]]
                                 [--polylines CELL[:max_gap[:reach]]] [--lane-pose RADIUS[:max_sin]] [--lane-filter]
-                                [--close-loops N] [--wheels FILE.npz]
+                                [--close-loops N] [--wheels FILE.npz] [--visual-odometry[=prior]] [--camera]
 
 --map-jpeg writes the final map as the reference's README shows it (show_map's coloured segments seen from above, lf_map_render
 fitted to the map) as a JPEG: rendered and encoded on the device, only the file's bytes cross the bus.
@@ -43,6 +43,13 @@ cost before and after, the largest shift of an endpoint and the solver's and the
 odometry's at its frames' stamps (the right-handed flip_y form) instead of zeros, --map-jpeg draws the driven trajectory in blue,
 and --lane-filter predicts with (dt, v = (Vl + Vr) / 2, w = (Vr - Vl) / l) of the command each frame's pose comes from before it
 updates: the odometry's kinematics, not the car_cmd the lane_filter node listens to.  Without the flag nothing changes.
+--visual-odometry steps the map with poses chained from the frames' own relative motions (lane_slam_amd.FrameMotion,
+lf_motion_estimate: every batch's consecutive pairs in one launch) instead of --wheels' poses or zeros; a pair that is not `ok`
+contributes no motion.  --visual-odometry=prior (with --wheels) hands each pair the wheels' relative motion as its prior with
+prior_xy = 1: a pair the search cannot settle is refined from the prior, one that is not `ok` keeps the wheels' motion.  A batch's
+first frame continues from the previous batch's last pose (by the wheels' motion across the boundary when there are wheels).  Per
+batch it prints the pairs by status and by source.  --camera replays the committed camera frames (tests/golden/real_jpegs.npz, 28
+streams, cycled) instead of the synthetic ones.
 """
 import argparse, io, os, sys, time
 import numpy as np
@@ -100,7 +107,12 @@ ap.add_argument("--lane-filter", action="store_true",
 ap.add_argument("--wheels", default=None, metavar="FILE.npz",
                 help="a log's wheel commands and frame stamps (keys stamp_ns, vel_left, vel_right, frame_stamp_ns): every batch's poses come "
                      "from the odometry on the device instead of zeros, and --map-jpeg draws the trajectory")
+ap.add_argument("--visual-odometry", nargs="?", const="chain", default=None, choices=["chain", "prior"],
+                help="step the map with poses chained from frame-to-frame motions (lf_motion_estimate); =prior: refined from --wheels' motions")
+ap.add_argument("--camera", action="store_true", help="replay the committed camera frames (tests/golden/real_jpegs.npz) instead of synthetic ones")
 args = ap.parse_args()
+if args.visual_odometry == "prior" and not args.wheels:
+    ap.error("--visual-odometry=prior goes with --wheels")
 if args.close_loops is not None and (not args.localize or args.close_loops < 1):
     ap.error("--close-loops N goes with --localize, N >= 1")
 lane_pose_fields = None
@@ -147,7 +159,10 @@ for i in range(32):
     b = io.BytesIO()
     Image.fromarray(synth.make_frame(9000 + i)[..., ::-1].copy()).save(b, "JPEG", quality=80, subsampling=2)
     streams.append(b.getvalue())
-msgs = [streams[i % 32] for i in range(args.frames)]
+if args.camera:
+    with np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "real_jpegs.npz")) as z:
+        streams = [bytes(z["jpeg%02d" % k]) for k in range(len(z["names"]))]
+msgs = [streams[i % len(streams)] for i in range(args.frames)]
 
 fe = FrontEnd(cfg, max_frames=B, max_lines_per_color=512)
 dev_frames, _ = fe.frames_buffer()
@@ -199,6 +214,13 @@ if args.wheels:
     # (x, -y, theta): the reference's odometry moves along (cos theta, -sin theta); the map's pose solvers are right-handed
     odometry = Odometry(n_streams=1, max_commands=max(len(wheels["stamp_ns"]), 1), max_frames=B, flip_y=True)
     wheels_used = 0                      # the commands the odometry has taken so far
+frame_motion = None
+if args.visual_odometry:
+    from lane_slam_amd import FrameMotion, motion
+    frame_motion = FrameMotion(max_pairs=max(B - 1, 1))
+    motion_cfg = FrameMotion.config(prior_xy=1.0) if args.visual_odometry == "prior" else FrameMotion.config()
+    last_visual = last_wheels = np.zeros(3)             # the previous batch's last pose: chained, and the wheels'
+have_poses = odometry is not None or frame_motion is not None
 pose_graph = None
 if args.close_loops is not None:
     from lane_slam_amd import PoseGraph
@@ -226,6 +248,19 @@ for b0 in range(0, args.frames - B + 1, B):
         gap = np.where(cmd > 0, (wheels["stamp_ns"][cmd] - wheels["stamp_ns"][np.maximum(cmd - 1, 0)]) / 1e9, 0.0)
         vl, vr = np.where(cmd >= 0, wheels["vel_left"][cmd], 0.0), np.where(cmd >= 0, wheels["vel_right"][cmd], 0.0)
         dt_v_w = np.stack([gap, (vl + vr) / 2, (vr - vl) / odometry.wheel_distance], axis=1)
+    if frame_motion is not None:
+        prior = motion.relative(batch_poses) if args.visual_odometry == "prior" else None
+        mres = frame_motion.estimate(seg, prior=prior, config=motion_cfg)
+        z = np.stack([mres["x"], mres["y"], mres["theta"]], axis=1)
+        z[mres["status"] != motion.OK] = 0.0 if prior is None else prior[mres["status"] != motion.OK]
+        across = motion.relative(np.stack([last_wheels, batch_poses[0]])) if odometry is not None else np.zeros((1, 3))
+        last_wheels = batch_poses[-1].copy()
+        batch_poses = motion.chain(z, motion.chain(across, last_visual)[1])
+        last_visual = batch_poses[-1].copy()
+        print("batch %d visual odometry: pairs by status %s, by source %s, median matches %d, last pose (%.3f, %.3f, %.3f)" % (
+            b0 // B, dict(zip(_lib.ALIGN_STATUS, np.bincount(mres["status"], minlength=4).tolist())),
+            dict(zip(("none", "search", "prior"), np.bincount(mres["source"], minlength=3).tolist())), int(np.median(mres["n_matches"])) if len(mres) else 0,
+            batch_poses[-1][0], batch_poses[-1][1], batch_poses[-1][2]))
     used_poses = batch_poses.copy()
     if seg.n:
         d = {k: torch.from_numpy(np.ascontiguousarray(getattr(seg, k))).cuda() for k in ("frame_offset", "code", "color", "keep", "ground")}
@@ -237,7 +272,7 @@ for b0 in range(0, args.frames - B + 1, B):
             # the candidates per segment against the map as this step finds it (the step's own association does not report them)
             dn = torch.zeros(seg.n, dtype=torch.int32, device="cuda")
             torch.cuda.synchronize()
-            pr = LineAssociator.carry(batch_poses, last_odometry, last_corrected) if args.smooth else (batch_poses if odometry is not None else None)
+            pr = LineAssociator.carry(batch_poses, last_odometry, last_corrected) if args.smooth else (batch_poses if have_poses else None)
             live.associate_near_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), pr, near_cfg, dn.data_ptr())
             live.synchronize()
             n_near_sum += int(dn.sum().item())
@@ -301,7 +336,7 @@ for b0 in range(0, args.frames - B + 1, B):
                 shadow.synchronize()
                 ok_frames[1] += int((sres["status"] == 0).sum()); used_endpoints[1] += int(sres["n_used"][sres["status"] == 0].sum())
         else:
-            live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=batch_poses if odometry is not None else None, step=b0 // B)
+            live.step_device(None, ptrs, seg.n, B, di.data_ptr(), dd.data_ptr(), poses=batch_poses if have_poses else None, step=b0 // B)
         live.synchronize()
         step = b0 // B
         if prune_every and (step + 1) % prune_every == 0:
@@ -384,7 +419,7 @@ if args.overlay_jpeg:
         fe.decode_jpeg_batch(msgs[b0:b0 + B], n_threads=args.threads, device_ptr=dev_frames)
         fe.rectify_device(dev_frames, B, in_rows, in_cols, 3, rect.data_ptr())
         fe.synchronize()                                              # (the map's stream does not wait for the handle's)
-        drawn += live.render_camera_device(rect.data_ptr(), rect.data_ptr(), B, stepped_poses[b0 // B] if odometry is not None else None, view).sum(axis=0)
+        drawn += live.render_camera_device(rect.data_ptr(), rect.data_ptr(), B, stepped_poses[b0 // B] if have_poses else None, view).sum(axis=0)
         live.synchronize()
         fe.encode_jpeg_device(rect.data_ptr(), B, cam_h, cam_w, files.data_ptr(), stride, sizes.data_ptr())
         fe.synchronize()
