@@ -18,6 +18,8 @@ The package is a thin host-side mirror of the reference's interfaces for this pa
                         for many robots in one call and samples the poses at the frames' stamps (include/lanefront_odometry.h)
   FrameMotion           the relative motion between frames of a batch from their own segments and LBD codes, with no map: match,
                         hypothesis search and Gauss-Newton refinement for many pairs in one launch (include/lanefront_motion.h)
+  KeyFrames             a store of key frames on the device across batches: which stored places a frame looks like (loop-closure
+                        candidates), and the frame's motion against a stored key (include/lanefront_places.h)
   FrontEnd         <->  batch form of line_detector_node / ground_projection_node /
                         line_sanity_node callbacks + BinaryDescriptor / BinaryDescriptorMatcher
 There is no CPU fallback: importing works anywhere, but creating a detector without the
@@ -29,9 +31,10 @@ from .lane_filter import LaneFilterBatch, LaneFilterHistogram
 from .line_associator import LineAssociator
 from .motion import FrameMotion
 from .odometry import Odometry, OdometryNode
+from .places import KeyFrames
 from .pose_graph import PoseGraph
 from .matcher import BinaryDescriptorMatcher, BinaryDescriptorParams, DMatch
 from .line_detector_hip import Detections, LineDetector2Dense, LineDetectorEDLines, LineDetectorHIP, LineDetectorHSV, LineDetectorInterface
 
-__all__ = ["LaneFilterBatch", "LaneFilterHistogram", "FrameMotion", "Odometry", "OdometryNode", "BinaryDescriptorMatcher", "BinaryDescriptorParams", "DMatch", "LineAssociator", "PoseGraph", "FrontEnd", "LanefrontError", "Segments", "LineDetectorHIP", "LineDetectorHSV", "LineDetector2Dense", "LineDetectorEDLines", "LineDetectorInterface", "Detections",
+__all__ = ["LaneFilterBatch", "LaneFilterHistogram", "FrameMotion", "KeyFrames", "Odometry", "OdometryNode", "BinaryDescriptorMatcher", "BinaryDescriptorParams", "DMatch", "LineAssociator", "PoseGraph", "FrontEnd", "LanefrontError", "Segments", "LineDetectorHIP", "LineDetectorHSV", "LineDetector2Dense", "LineDetectorEDLines", "LineDetectorInterface", "Detections",
            "default_config", "DEFAULT_DETECTOR_CONFIGURATION", "WHITE", "YELLOW", "RED", "COLOR_NAMES"]

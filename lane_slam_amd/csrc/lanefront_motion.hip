@@ -32,7 +32,10 @@ struct lf_motion : lf::Core {
 
 static char g_motion_create_err[512] = "no error";
 
-static const char* bad_config(const lf_motion_config* c)
+namespace lf { const char* motion_bad_config(const lf_motion_config* c); }
+
+// why the configuration is refused, or null (lf_places_motion refuses what lf_motion_estimate refuses: k_places.h declares it)
+const char* lf::motion_bad_config(const lf_motion_config* c)
 {
     if (c->max_distance < 0 || c->max_distance > 256 || c->min_margin < 0 || c->min_margin > 256) return "max_distance and min_margin are 0 .. 256";
     if (c->max_pairs < 2 || c->max_pairs > fm::kMaxPairs) return "max_pairs is 2 .. 128";
@@ -126,7 +129,7 @@ extern "C" int lf_motion_estimate(lf_motion* mo, lf_handle* h, const lf_segments
     for (int k = 0; prior && k < 3 * n_pairs; ++k)
         if (!isfinite(prior[k])) MOTION_REFUSE("the prior of pair %d is not finite", k / 3);
     if (n > 0 && (!segs->frame_offset || !segs->ground || !segs->code)) MOTION_REFUSE("frame_offset, ground and code are required");
-    if (const char* why = bad_config(cfg)) MOTION_REFUSE("bad configuration (%s)", why);
+    if (const char* why = motion_bad_config(cfg)) MOTION_REFUSE("bad configuration (%s)", why);
     if (n_pairs == 0) return LF_OK;
 
     LF_HIP_CHECK(mo, hipSetDevice(mo->device));

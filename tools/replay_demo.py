@@ -9,6 +9,7 @@ wire bodies.  The first batch is checked against the oracle (pixels, segments, m
                                 [--near RADIUS[:max_offset[:max_sin]]] [--lanes RADIUS[:max_offset[:max_sin[:min_entries]]]]
                                 [--polylines CELL[:max_gap[:reach]]] [--lane-pose RADIUS[:max_sin]] [--lane-filter]
                                 [--close-loops N] [--wheels FILE.npz] [--visual-odometry[=prior]] [--camera]
+                                [--place-loops[=EVERY]]
 
 --map-jpeg writes the final map as the reference's README shows it (show_map's coloured segments seen from above, lf_map_render
 fitted to the map) as a JPEG: rendered and encoded on the device, only the file's bytes cross the bus.
@@ -50,6 +51,12 @@ prior_xy = 1: a pair the search cannot settle is refined from the prior, one tha
 first frame continues from the previous batch's last pose (by the wheels' motion across the boundary when there are wheels).  Per
 batch it prints the pairs by status and by source.  --camera replays the committed camera frames (tests/golden/real_jpegs.npz, 28
 streams, cycled) instead of the synthetic ones.
+--place-loops[=EVERY] finds the loops by place recognition (lane_slam_amd.KeyFrames, lf_places_*): every batch's first frame becomes a
+key of a store that stays on the device and a node of a pose graph of its own (the pose the frame was stepped with).  The frame is
+first queried against the keys that are at least EVERY keys old (default 2: its own neighbourhood stays out of the answer), every hit
+is verified and measured by the motion against the stored key (lf_places_motion), and the accepted ones (places.loops) become loop edges
+key -> frame; the graph is then solved on the device and the map moved, as under --close-loops.  Per batch it prints the hits, the
+accepted loops and the solve.
 """
 import argparse, io, os, sys, time
 import numpy as np
@@ -110,9 +117,14 @@ ap.add_argument("--wheels", default=None, metavar="FILE.npz",
 ap.add_argument("--visual-odometry", nargs="?", const="chain", default=None, choices=["chain", "prior"],
                 help="step the map with poses chained from frame-to-frame motions (lf_motion_estimate); =prior: refined from --wheels' motions")
 ap.add_argument("--camera", action="store_true", help="replay the committed camera frames (tests/golden/real_jpegs.npz) instead of synthetic ones")
+ap.add_argument("--place-loops", nargs="?", const=2, default=None, type=int, metavar="EVERY",
+                help="one key frame per batch on the device; each batch's first frame is queried against the keys at least EVERY keys old (default 2), the "
+                     "hits are verified by lf_places_motion and the accepted ones close loops in a pose graph (lf_places_*)")
 args = ap.parse_args()
 if args.visual_odometry == "prior" and not args.wheels:
     ap.error("--visual-odometry=prior goes with --wheels")
+if args.place_loops is not None and args.place_loops < 1:
+    ap.error("--place-loops=EVERY: EVERY >= 1")
 if args.close_loops is not None and (not args.localize or args.close_loops < 1):
     ap.error("--close-loops N goes with --localize, N >= 1")
 lane_pose_fields = None
@@ -226,6 +238,11 @@ if args.close_loops is not None:
     from lane_slam_amd import PoseGraph
     pose_graph = PoseGraph()
     live.set_profiling(True)
+key_frames = None
+if args.place_loops is not None:
+    from lane_slam_amd import FrameMotion, KeyFrames, PoseGraph, places
+    key_frames = KeyFrames(max_keys=max(args.frames // B, 1), max_segments=max(args.frames // B, 1) * 4096, max_queries=places.MAX_TOP_K)      # (a query's hits are one motion call's pairs)
+    place_graph, place_cfg, place_motion_cfg = PoseGraph(), KeyFrames.config(), FrameMotion.config()
 n_near_sum = 0
 ok_frames, used_endpoints, all_frames = [0, 0], [0, 0], 0
 t0 = time.perf_counter()
@@ -345,6 +362,25 @@ for b0 in range(0, args.frames - B + 1, B):
         n_matched += int((di >= 0).sum().item())
         n_kept += int(seg.keep.sum())
     stepped_poses.append(used_poses)
+    if key_frames is not None:
+        # the batch's first frame: a node, a query against the keys that are old enough, and then a key itself
+        node = place_graph.add_key(b0 // B, used_poses[0])
+        hits = key_frames.query(seg, [0], max(node - args.place_loops + 1, 0), place_cfg)
+        qk = places.pairs_of(hits)
+        found = []
+        if len(qk):
+            pres = key_frames.motion(seg, np.stack([qk[:, 1], np.zeros(len(qk), np.int32)], axis=1), config=place_motion_cfg)
+            found = places.loops(hits, pres, min_inliers=place_motion_cfg.min_inliers)
+        assert key_frames.add(seg, [0]) == node
+        line = "batch %d places: %d keys, hits %s, %d accepted" % (b0 // B, node, [(int(h["key"]), int(h["score"])) for h in hits[0] if h["key"] >= 0], len(found))
+        for _, k, z, info in found:
+            place_graph.add_loop(k, node, z, places.weights(info))
+        if found:
+            _, gres, _ = place_graph.solve(live)
+            moved = place_graph.apply(live) if gres["status"] == 0 else None
+            line += "; loops with keys %s: %s, cost %.6g -> %.6g, %s" % ([k for _, k, _, _ in found], _lib.ALIGN_STATUS[gres["status"]], gres["cost0"], gres["cost"],
+                                                                      "the map is left" if moved is None else "%d entries moved by up to %.4f m" % (moved["n_moved"], moved["max_shift"]))
+        print(line)
     told = []
     if lane_pose_cfg is not None:
         lres, lp = live.lane_pose(used_poses, lane_pose_cfg)
