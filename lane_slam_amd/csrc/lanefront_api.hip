@@ -30,7 +30,7 @@ extern "C" void lf_set_error(lf_handle* h, int code, const char* fmt, ...)
     va_end(ap);
 }
 
-static char g_create_err[512] = "no error";
+static CreateError g_create_err;
 
 static int cv_round_host(double v) { return dm::round_half_even(v); }
 
@@ -232,27 +232,22 @@ extern "C" int lf_get_stream(lf_handle* h, void** hip_stream)
     return LF_OK;
 }
 
-extern "C" const char* lf_last_error(const lf_handle* h) { return h ? h->err : g_create_err; }
+extern "C" const char* lf_last_error(const lf_handle* h) { return h ? h->err : g_create_err.text; }
 
 extern "C" const char* lf_stage_name(int stage) { return (stage >= 0 && stage < LF_N_STAGES) ? kStageNames[stage] : "?"; }
 
 extern "C" void lf_destroy(lf_handle* h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    close_core(h, {});
     delete h;                    // the buffers and the substates free themselves
 }
 
 extern "C" int lf_create(const lf_config* cfg, int device_id, int max_frames, int max_lines_per_color, lf_handle** out)
 {
-    if (!cfg || !out || max_frames < 1 || max_lines_per_color < 1) {
-        snprintf(g_create_err, sizeof(g_create_err), "lf_create: bad argument");
-        return LF_ERR_BAD_ARG;
-    }
+    if (!cfg || !out || max_frames < 1 || max_lines_per_color < 1) return g_create_err.refuse("lf_create: bad argument");
     *out = nullptr;
-    if (const int rc = check_device(device_id, "lf_create", g_create_err, sizeof(g_create_err))) return rc;
+    if (const int rc = g_create_err.check_device(device_id, "lf_create")) return rc;
     lf_handle* h = new (std::nothrow) lf_handle();
     if (!h) return LF_ERR_HIP;
     h->cfg = *cfg; h->device = device_id; h->max_frames = max_frames; h->cap_lines = max_lines_per_color;
@@ -267,11 +262,7 @@ extern "C" int lf_create(const lf_config* cfg, int device_id, int max_frames, in
         if ((rc = upload_tables(h)) != LF_OK) break;
         if ((rc = alloc_buffers(h)) != LF_OK) break;
     } while (0);
-    if (rc != LF_OK) {
-        snprintf(g_create_err, sizeof(g_create_err), "%s", h->err);
-        lf_destroy(h);
-        return rc;
-    }
+    if (rc != LF_OK) return g_create_err.fail(h, rc, lf_destroy);
     *out = h;
     return LF_OK;
 }
@@ -284,10 +275,7 @@ extern "C" int lf_stream_priority(const lf_handle* h, int* priority, int* least,
 
 extern "C" int lf_synchronize(lf_handle* h)
 {
-    if (!h) return LF_ERR_NOT_INITIALISED;
-    LF_HIP_CHECK(h, hipSetDevice(h->device));
-    LF_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-    return LF_OK;
+    return h ? core_synchronize(h) : LF_ERR_NOT_INITIALISED;
 }
 
 // what lf_wait / lf_detect_lines call the handle's detector in their capacity messages

@@ -1,6 +1,10 @@
-// What the three opaque handles of the C ABI (lf_handle, lf_map, lf_lane_filter) share on the host: the fields every one of them
-// carries, the error text, the HIP check, the device check of their creators, the two kinds of clock, the scratch grower, the
-// staging of a caller's host arrays and the ordering of one stream behind another.  Host code only; common.h does not include it (tests/hostsim builds lsd_grow.h on the CPU).
+// What the six opaque handles of the C ABI (lf_handle, lf_map, lf_lane_filter, lf_odometry, lf_motion, lf_places) share on the host:
+// the fields every one of them carries, the error text, the HIP check, and one life cycle -- a creator's error buffer and its
+// check (CreateError, LF_CREATE_TRY), the device, stream and events of a handle (open_core, close_core), the bodies of
+// *_synchronize, *_set_profiling and *_get_timing (core_*) -- then the three classes of stream, the two kinds of clock, the
+// scratch grower, the staging of a caller's host arrays and the ordering of a handle's stream against an lf_handle's
+// (after_handle, release_handle).  A new handle type derives from Core and writes only what is its own.
+// Host code only; common.h does not include it (tests/hostsim builds lsd_grow.h on the CPU).
 #pragma once
 #include <stdarg.h>
 #include <stdio.h>
@@ -45,20 +49,57 @@ __attribute__((format(printf, 3, 4))) inline void set_error(Core* c, int code, c
         }                                                                                                                    \
     } while (0)
 
-// a creator's check of device_id: LF_OK, or the message, with the creator's name in front, in its own buffer
-inline int check_device(int device_id, const char* who, char* buf, size_t size)
-{
-    int ndev = 0;
-    const hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        snprintf(buf, size, "%s: no HIP device (%s); lanefront has no CPU fallback", who, e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-        return LF_ERR_HIP;
-    }
-    if (device_id < 0 || device_id >= ndev) { snprintf(buf, size, "%s: device %d out of range (%d devices)", who, device_id, ndev); return LF_ERR_BAD_ARG; }
-    return LF_OK;
-}
+// Why a handle type's last creator failed: what its *_last_error(NULL) returns.  One object per type, so that a failing creator
+// of one type leaves the text of every other type alone.
+struct CreateError {
+    char text[512] = "no error";
 
-// The two classes of stream the library makes.  The runtime gives every stream one of the process's hardware queues (GPU_MAX_HW_QUEUES
+    // a refused argument: the text, and LF_ERR_BAD_ARG
+    __attribute__((format(printf, 2, 3))) int refuse(const char* fmt, ...)
+    {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(text, sizeof(text), fmt, ap);
+        va_end(ap);
+        return LF_ERR_BAD_ARG;
+    }
+
+    // a creator's check of device_id: LF_OK, or the message with the creator's name in front
+    int check_device(int device_id, const char* who)
+    {
+        int ndev = 0;
+        const hipError_t e = hipGetDeviceCount(&ndev);
+        if (e != hipSuccess || ndev <= 0) {
+            snprintf(text, sizeof(text), "%s: no HIP device (%s); lanefront has no CPU fallback", who, e != hipSuccess ? hipGetErrorString(e) : "device count 0");
+            return LF_ERR_HIP;
+        }
+        return device_id < 0 || device_id >= ndev ? refuse("%s: device %d out of range (%d devices)", who, device_id, ndev) : LF_OK;
+    }
+
+    // a half-made handle failed with rc: its text is kept, the handle destroyed
+    template <typename Handle>
+    int fail(Handle* h, int rc, void (*destroy)(Handle*))
+    {
+        snprintf(text, sizeof(text), "%s", h->err);
+        destroy(h);
+        return rc;
+    }
+};
+
+// a creator's HIP call: `fail` is its `[&](int rc) { return <the type's CreateError>.fail(handle, rc, <the type's destroyer>); }`
+#define LF_CREATE_TRY(core, fail, expr)                                                                                      \
+    do {                                                                                                                     \
+        hipError_t _e = (expr);                                                                                              \
+        if (_e != hipSuccess) {                                                                                              \
+            lf::set_error((core), LF_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));                                \
+            return fail(LF_ERR_HIP);                                                                                         \
+        }                                                                                                                    \
+    } while (0)
+
+// (the configurations' doubles: neither infinite nor NaN)
+inline bool is_finite(double x) { return x - x == 0; }
+
+// The three classes of stream the library makes.  The runtime gives every stream one of the process's hardware queues (GPU_MAX_HW_QUEUES
 // of them for the normal priority, four by default; another priority has queues of its own), a new stream the queue with the fewest
 // streams, and streams that share a queue serialise.
 //   CHAIN  lf_map's: one stream, the serial chain of a pipelined front end (lf_map_create) -- the greatest priority where the device
@@ -69,7 +110,10 @@ inline int check_device(int device_id, const char* who, char* buf, size_t size)
 //          stream has begun (pad_normal_streams); from there on the handles are dealt 2 / 2 / 2 / 2, eighteen of them 5 / 5 / 4 / 4.
 //          (The least priority would give the handles a pool of their own without any padding, and does: it was measured 10 % slower
 //          than the uneven placement)
-enum class StreamClass { BATCH, CHAIN };
+//   PLAIN  lf_lane_filter's, lf_odometry's, lf_motion's and lf_places': one stream of short side work at the normal priority, made
+//          as it comes, without the padding: it takes the queue with the fewest streams at that moment.  (As BATCH streams they
+//          would take part in the deal of the handles and shift it.)
+enum class StreamClass { BATCH, CHAIN, PLAIN };
 
 // Idle streams, made once per device and kept for the life of the process, that make the normal-priority streams which are no
 // handle's -- the default stream and these -- a multiple of the hardware queue count.  GPU_MAX_HW_QUEUES is read, never set; with
@@ -114,6 +158,42 @@ inline int stream_priority(Core* c, int* priority, int* least, int* greatest)
     if (priority) *priority = p;
     if (least) *least = lo;
     if (greatest) *greatest = hi;
+    return LF_OK;
+}
+
+// A creator's first step, c->err set where it fails: the device, the core's stream of the class, and the events named, each made
+// without timing.  (lf_create orders its own: it validates the configuration between the device and the stream.)
+inline int open_core(Core* c, int device, StreamClass cls, std::initializer_list<hipEvent_t*> events)
+{
+    auto fail = [](int rc) { return rc; };
+    c->device = device;
+    LF_CREATE_TRY(c, fail, hipSetDevice(device));
+    LF_CREATE_TRY(c, fail, create_stream(&c->stream, cls));
+    for (hipEvent_t* ev : events) LF_CREATE_TRY(c, fail, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    return LF_OK;
+}
+
+// A destroyer's: waits for the core's stream, then destroys the events named (null: never made) and the stream.  The owner deletes
+// its handle afterwards; the buffers free themselves.
+inline void close_core(Core* c, std::initializer_list<hipEvent_t> events)
+{
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+}
+
+// the bodies of *_synchronize and *_set_profiling behind their null checks (*_get_timing's: core_take_timing, below the clocks)
+inline int core_synchronize(Core* c)
+{
+    LF_HIP_CHECK(c, hipSetDevice(c->device));
+    LF_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return LF_OK;
+}
+
+inline int core_set_profiling(Core* c, int on)
+{
+    c->profiling = on != 0;
     return LF_OK;
 }
 
@@ -207,6 +287,22 @@ inline int stream_after(Core* c, hipEvent_t ev, hipStream_t waits, hipStream_t o
     LF_HIP_CHECK(c, hipStreamWaitEvent(waits, ev, 0));
     return LF_OK;
 }
+
+// The order of a core's stream against the stream of the lf_handle whose batch it reads (h null: nothing to order).  `who` is
+// what stands before "bad handle" in the error text: the entry point and ": ", or "".
+inline int order_with_handle(Core* c, hipEvent_t ev, lf_handle* h, const char* who, bool core_waits)
+{
+    if (!h) return LF_OK;
+    void* s = nullptr;
+    if (lf_get_stream(h, &s) != LF_OK) { set_error(c, LF_ERR_BAD_ARG, "%sbad handle", who); return LF_ERR_BAD_ARG; }
+    const hipStream_t hs = static_cast<hipStream_t>(s);
+    return core_waits ? stream_after(c, ev, c->stream, hs) : stream_after(c, ev, hs, c->stream);
+}
+
+// the core's stream waits for everything queued so far on the handle's stream
+inline int after_handle(Core* c, hipEvent_t ev, lf_handle* h, const char* who) { return order_with_handle(c, ev, h, who, true); }
+// the handle's later work (its next batch overwrites the segment arrays) waits for what the core has queued so far
+inline int release_handle(Core* c, hipEvent_t ev, lf_handle* h, const char* who) { return order_with_handle(c, ev, h, who, false); }
 
 // What a handle remembers of the batch it queued last (lf_process_batch_async): the caller's device block, the frames, and a serial
 // number no other batch of any handle has.  The live map compares it with its snapshot of a batch's arrays (lanefront_map.hip).
@@ -311,6 +407,14 @@ private:
         return true;
     }
 };
+
+// the body of *_get_timing behind its null check: every stage of the clock read and reset, the first n of them given out
+inline int core_take_timing(Core* c, StageClock& clock, double* ms, int32_t* launches, int n)
+{
+    LF_HIP_CHECK(c, hipSetDevice(c->device));
+    clock.take(ms, launches, n);
+    return LF_OK;
+}
 
 // The per-stage times of the LAST call of one entry point: a pair of events per stage, made by the first profiled call and
 // reused by the later ones.

@@ -32,7 +32,7 @@ struct lf_lane_filter : lf::Core {
 static const char* kLfStageNames[LF_LANE_FILTER_N_STAGES] = { "lf_vote", "lf_chain" };
 extern "C" const char* lf_lane_filter_stage_name(int stage) { return (stage >= 0 && stage < LF_LANE_FILTER_N_STAGES) ? kLfStageNames[stage] : "?"; }
 
-static char g_lf_create_err[512] = "no error";
+static CreateError g_lf_create_err;
 
 extern "C" void lf_lane_filter_default_config(lf_lane_filter_config* c)
 {
@@ -44,7 +44,7 @@ extern "C" void lf_lane_filter_default_config(lf_lane_filter_config* c)
     c->sigma_d_mask = 1.0; c->sigma_phi_mask = 2.0;
 }
 
-extern "C" const char* lf_lane_filter_last_error(const lf_lane_filter* lf) { return lf ? lf->err : g_lf_create_err; }
+extern "C" const char* lf_lane_filter_last_error(const lf_lane_filter* lf) { return lf ? lf->err : g_lf_create_err.text; }
 
 extern "C" int lf_lane_filter_grid(const lf_lane_filter* lf, int* rows, int* cols)
 {
@@ -57,10 +57,7 @@ extern "C" int lf_lane_filter_grid(const lf_lane_filter* lf, int* rows, int* col
 extern "C" void lf_lane_filter_destroy(lf_lane_filter* lf)
 {
     if (!lf) return;
-    (void)hipSetDevice(lf->device);
-    if (lf->stream) (void)hipStreamSynchronize(lf->stream);
-    for (hipEvent_t e : { lf->ev_in, lf->ev_out, lf->ev_staged, lf->ev_done }) if (e) (void)hipEventDestroy(e);
-    if (lf->stream) (void)hipStreamDestroy(lf->stream);
+    close_core(lf, { lf->ev_in, lf->ev_out, lf->ev_staged, lf->ev_done });
     delete lf;                   // the buffers free themselves
 }
 
@@ -78,8 +75,6 @@ static int grow_host(lf_lane_filter* lf, HostArray<T>& b, size_t bytes)
     LF_HIP_CHECK(lf, b.alloc(bytes + bytes / 4 + 256));
     return LF_OK;
 }
-
-static bool is_finite(double x) { return x - x == 0; }
 
 extern "C" int lf_lane_filter_set_tables(lf_lane_filter* lf, const double* sin_phi, const double* w_d, const double* w_phi,
                                          const double* initial_belief)
@@ -143,31 +138,25 @@ static void default_tables(const lf_lane_filter_config& c, const LfGrid& g, doub
 
 extern "C" int lf_lane_filter_create(int device_id, const lf_lane_filter_config* cfg, int n_streams, int max_frames, lf_lane_filter** out)
 {
-    if (!cfg || !out) { snprintf(g_lf_create_err, sizeof(g_lf_create_err), "lf_lane_filter_create: null argument"); return LF_ERR_BAD_ARG; }
+    CreateError& err = g_lf_create_err;
+    if (!cfg || !out) return err.refuse("lf_lane_filter_create: null argument");
     *out = nullptr;
     const lf_lane_filter_config& c = *cfg;
     const double* all = &c.mean_d_0;
-    for (int k = 0; k < 17; ++k) if (!is_finite(all[k])) { snprintf(g_lf_create_err, sizeof(g_lf_create_err), "lf_lane_filter_create: configuration field %d is not finite", k); return LF_ERR_BAD_ARG; }
+    for (int k = 0; k < 17; ++k) if (!is_finite(all[k])) return err.refuse("lf_lane_filter_create: configuration field %d is not finite", k);
     if (!(c.delta_d > 0) || !(c.delta_phi > 0) || !(c.d_max > c.d_min) || !(c.phi_max > c.phi_min) || !(c.sigma_d_0 > 0) ||
         !(c.sigma_phi_0 > 0) || !(c.sigma_d_mask > 1e-15) || !(c.sigma_phi_mask > 1e-15) || (int)(4.0 * c.sigma_d_mask + 0.5) > LF_LF_MAX_RADIUS ||
-        (int)(4.0 * c.sigma_phi_mask + 0.5) > LF_LF_MAX_RADIUS) {
-        snprintf(g_lf_create_err, sizeof(g_lf_create_err), "lf_lane_filter_create: bad configuration (delta_d, delta_phi, sigma_d_0, sigma_phi_0 > 0; d_max > d_min; "
-                  "phi_max > phi_min; sigma_d_mask, sigma_phi_mask in (1e-15, 63.6])");
-        return LF_ERR_BAD_ARG;
-    }
+        (int)(4.0 * c.sigma_phi_mask + 0.5) > LF_LF_MAX_RADIUS)
+        return err.refuse("lf_lane_filter_create: bad configuration (delta_d, delta_phi, sigma_d_0, sigma_phi_0 > 0; d_max > d_min; "
+                          "phi_max > phi_min; sigma_d_mask, sigma_phi_mask in (1e-15, 63.6])");
     const double fr = ceil((c.d_max - c.d_min) / c.delta_d), fc = ceil((c.phi_max - c.phi_min) / c.delta_phi);
-    if (!(fr * fc <= LF_LF_MAX_CELLS)) {
-        snprintf(g_lf_create_err, sizeof(g_lf_create_err), "lf_lane_filter_create: a %.0f x %.0f grid exceeds %d cells", fr, fc, LF_LF_MAX_CELLS);
-        return LF_ERR_BAD_ARG;
-    }
-    if (n_streams < 1 || n_streams > 65536 || max_frames < 1 || max_frames > (1 << 20)) {
-        snprintf(g_lf_create_err, sizeof(g_lf_create_err), "lf_lane_filter_create: n_streams %d in [1, 65536], max_frames %d in [1, 2^20]", n_streams, max_frames);
-        return LF_ERR_BAD_ARG;
-    }
-    if (const int rc = check_device(device_id, "lf_lane_filter_create", g_lf_create_err, sizeof(g_lf_create_err))) return rc;
+    if (!(fr * fc <= LF_LF_MAX_CELLS)) return err.refuse("lf_lane_filter_create: a %.0f x %.0f grid exceeds %d cells", fr, fc, LF_LF_MAX_CELLS);
+    if (n_streams < 1 || n_streams > 65536 || max_frames < 1 || max_frames > (1 << 20))
+        return err.refuse("lf_lane_filter_create: n_streams %d in [1, 65536], max_frames %d in [1, 2^20]", n_streams, max_frames);
+    if (const int rc = err.check_device(device_id, "lf_lane_filter_create")) return rc;
     lf_lane_filter* lf = new (std::nothrow) lf_lane_filter();
     if (!lf) return LF_ERR_HIP;
-    lf->cfg = c; lf->device = device_id; lf->n_streams = n_streams; lf->max_frames = max_frames;
+    lf->cfg = c; lf->n_streams = n_streams; lf->max_frames = max_frames;
     LfGrid& g = lf->g;
     memset(&g, 0, sizeof(g));
     g.rows = (int)fr; g.cols = (int)fc; g.cells = g.rows * g.cols;
@@ -177,27 +166,24 @@ extern "C" int lf_lane_filter_create(int device_id, const lf_lane_filter_config*
     int plan[LF_LF_MAX_PLAN];
     const int packed = lane_filter_sum_plan(g.cells, plan);
     g.n_leaves = packed & 0xffff; g.n_prog = packed >> 16;
-    auto fail = [&](int rc) { snprintf(g_lf_create_err, sizeof(g_lf_create_err), "%s", lf->err); lf_lane_filter_destroy(lf); return rc; };
-#define TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error(lf, LF_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); return fail(LF_ERR_HIP); } } while (0)
-    TRY(hipSetDevice(device_id));
-    TRY(hipStreamCreateWithFlags(&lf->stream, hipStreamNonBlocking));
-    for (hipEvent_t* ev : { &lf->ev_in, &lf->ev_out, &lf->ev_staged, &lf->ev_done }) TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    auto fail = [&](int rc) { return err.fail(lf, rc, lf_lane_filter_destroy); };
+    if (const int rc = open_core(lf, device_id, StreamClass::PLAIN, { &lf->ev_in, &lf->ev_out, &lf->ev_staged, &lf->ev_done })) return fail(rc);
     const size_t cells = g.cells, mf = max_frames;
-    TRY(lf->belief.alloc(cells * n_streams * sizeof(double)));
-    TRY(lf->init.alloc(cells * sizeof(double)));
-    TRY(lf->sinp.alloc(cells * sizeof(double)));
-    TRY(lf->wd.alloc((g.r_d + 1) * sizeof(double)));
-    TRY(lf->wphi.alloc((g.r_phi + 1) * sizeof(double)));
-    TRY(lf->plan.alloc(LF_LF_MAX_PLAN * sizeof(int)));
-    TRY(lf->counts.alloc(cells * mf * sizeof(int)));
-    TRY(lf->n_votes.alloc(mf * sizeof(int)));
-    TRY(lf->fstream.alloc(mf * sizeof(int)));
-    TRY(lf->dtvw.alloc(mf * 3 * sizeof(double)));
-    TRY(lf->poses.alloc(mf * sizeof(LfPoseDev)));
-    TRY(lf->h_dtvw.alloc(mf * 3 * sizeof(double)));
-    TRY(lf->h_fstream.alloc(mf * sizeof(int)));
-    TRY(lf->h_poses.alloc(mf * sizeof(LfPoseDev)));
-    TRY(hipMemcpy(lf->plan, plan, LF_LF_MAX_PLAN * sizeof(int), hipMemcpyHostToDevice));
+    LF_CREATE_TRY(lf, fail, lf->belief.alloc(cells * n_streams * sizeof(double)));
+    LF_CREATE_TRY(lf, fail, lf->init.alloc(cells * sizeof(double)));
+    LF_CREATE_TRY(lf, fail, lf->sinp.alloc(cells * sizeof(double)));
+    LF_CREATE_TRY(lf, fail, lf->wd.alloc((g.r_d + 1) * sizeof(double)));
+    LF_CREATE_TRY(lf, fail, lf->wphi.alloc((g.r_phi + 1) * sizeof(double)));
+    LF_CREATE_TRY(lf, fail, lf->plan.alloc(LF_LF_MAX_PLAN * sizeof(int)));
+    LF_CREATE_TRY(lf, fail, lf->counts.alloc(cells * mf * sizeof(int)));
+    LF_CREATE_TRY(lf, fail, lf->n_votes.alloc(mf * sizeof(int)));
+    LF_CREATE_TRY(lf, fail, lf->fstream.alloc(mf * sizeof(int)));
+    LF_CREATE_TRY(lf, fail, lf->dtvw.alloc(mf * 3 * sizeof(double)));
+    LF_CREATE_TRY(lf, fail, lf->poses.alloc(mf * sizeof(LfPoseDev)));
+    LF_CREATE_TRY(lf, fail, lf->h_dtvw.alloc(mf * 3 * sizeof(double)));
+    LF_CREATE_TRY(lf, fail, lf->h_fstream.alloc(mf * sizeof(int)));
+    LF_CREATE_TRY(lf, fail, lf->h_poses.alloc(mf * sizeof(LfPoseDev)));
+    LF_CREATE_TRY(lf, fail, hipMemcpy(lf->plan, plan, LF_LF_MAX_PLAN * sizeof(int), hipMemcpyHostToDevice));
     {
         double* sinp = new (std::nothrow) double[3 * cells + g.r_d + g.r_phi + 2];
         if (!sinp) { set_error(lf, LF_ERR_HIP, "out of host memory"); return fail(LF_ERR_HIP); }
@@ -208,17 +194,13 @@ extern "C" int lf_lane_filter_create(int device_id, const lf_lane_filter_config*
         if (rc != LF_OK) return fail(rc);
     }
     if (lf_lane_filter_reset(lf, -1, nullptr) != LF_OK) return fail(LF_ERR_HIP);
-#undef TRY
     *out = lf;
     return LF_OK;
 }
 
 extern "C" int lf_lane_filter_synchronize(lf_lane_filter* lf)
 {
-    if (!lf) return LF_ERR_NOT_INITIALISED;
-    LF_HIP_CHECK(lf, hipSetDevice(lf->device));
-    LF_HIP_CHECK(lf, hipStreamSynchronize(lf->stream));
-    return LF_OK;
+    return lf ? core_synchronize(lf) : LF_ERR_NOT_INITIALISED;
 }
 
 extern "C" int lf_lane_filter_get_belief(lf_lane_filter* lf, int stream, double* belief)
@@ -290,7 +272,6 @@ extern "C" int lf_lane_filter_step(lf_lane_filter* lf, lf_handle* h, const lf_se
         const uint8_t* col = segs->color;
         const double* gr = segs->ground;
         int cap = segs->capacity;
-        void* hs = nullptr;                   // the handle's stream, when its segments are read where it wrote them
         if (!segs_on_device) {
             const size_t ns = (size_t)(n_segs > 0 ? n_segs : 1);
             if ((rc = grow_host(lf, lf->h_fo, (n_frames + 1) * sizeof(int))) != LF_OK || (rc = grow_host(lf, lf->h_color, ns)) != LF_OK ||
@@ -306,9 +287,8 @@ extern "C" int lf_lane_filter_step(lf_lane_filter* lf, lf_handle* h, const lf_se
                 LF_HIP_CHECK(lf, hipMemcpyAsync(lf->seg_ground, lf->h_ground, (size_t)n_segs * 4 * sizeof(double), hipMemcpyHostToDevice, s));
             }
             fo = lf->seg_fo; col = lf->seg_color; gr = lf->seg_ground; cap = n_segs;
-        } else if (h) {
-            if (lf_get_stream(h, &hs) != LF_OK) { set_error(lf, LF_ERR_BAD_ARG, "lf_lane_filter_step: bad handle"); return LF_ERR_BAD_ARG; }
-            if ((rc = stream_after(lf, lf->ev_in, s, static_cast<hipStream_t>(hs))) != LF_OK) return rc;
+        } else if ((rc = after_handle(lf, lf->ev_in, h, "lf_lane_filter_step: ")) != LF_OK) {      // (its segments are read where it wrote them)
+            return rc;
         }
         {
             StageClock::Scope tm(lf, lf->clock, 0);
@@ -316,7 +296,7 @@ extern "C" int lf_lane_filter_step(lf_lane_filter* lf, lf_handle* h, const lf_se
         }
         LF_HIP_CHECK(lf, hipGetLastError());
         // the handle's next batch overwrites the segment arrays: it waits for the votes
-        if (segs_on_device && h && (rc = stream_after(lf, lf->ev_out, static_cast<hipStream_t>(hs), s)) != LF_OK) return rc;
+        if (segs_on_device && (rc = release_handle(lf, lf->ev_out, h, "lf_lane_filter_step: ")) != LF_OK) return rc;
     }
     LF_HIP_CHECK(lf, hipEventRecord(lf->ev_staged, s));
     lf->staged_pending = true;
@@ -344,16 +324,11 @@ extern "C" int lf_lane_filter_step(lf_lane_filter* lf, lf_handle* h, const lf_se
 
 extern "C" int lf_lane_filter_set_profiling(lf_lane_filter* lf, int enabled)
 {
-    if (!lf) return LF_ERR_NOT_INITIALISED;
-    lf->profiling = enabled != 0;
-    return LF_OK;
+    return lf ? core_set_profiling(lf, enabled) : LF_ERR_NOT_INITIALISED;
 }
 
 // ms accumulated and launches counted per kernel since the last call; resets both
 extern "C" int lf_lane_filter_get_timing(lf_lane_filter* lf, double* ms_per_stage, int32_t* launches_per_stage, int n)
 {
-    if (!lf) return LF_ERR_NOT_INITIALISED;
-    LF_HIP_CHECK(lf, hipSetDevice(lf->device));
-    lf->clock.take(ms_per_stage, launches_per_stage, n);
-    return LF_OK;
+    return lf ? core_take_timing(lf, lf->clock, ms_per_stage, launches_per_stage, n) : LF_ERR_NOT_INITIALISED;
 }

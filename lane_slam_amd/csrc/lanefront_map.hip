@@ -6,7 +6,7 @@
 #include <vector>
 #include "lanefront_map_handle.h"
 
-static char g_map_create_err[512] = "no error";
+static CreateError g_map_create_err;
 
 // make the host mirror current: wait for the copy queued behind the last update (block = false: only look)
 int refresh_state(lf_map* m, bool block)
@@ -47,24 +47,6 @@ int queue_state_copy(lf_map* m)
     return LF_OK;
 }
 
-// the map's stream waits for everything queued so far on the handle's stream
-int after_handle(lf_map* m, lf_handle* h)
-{
-    if (!h) return LF_OK;
-    void* hs = nullptr;
-    if (lf_get_stream(h, &hs) != LF_OK) { set_error(m, LF_ERR_BAD_ARG, "bad handle"); return LF_ERR_BAD_ARG; }
-    return stream_after(m, m->ev_in, m->stream, static_cast<hipStream_t>(hs));
-}
-
-// the handle's later work (its next batch overwrites the segment arrays) waits for what the map has queued so far
-int release_handle(lf_map* m, lf_handle* h)
-{
-    if (!h) return LF_OK;
-    void* hs = nullptr;
-    if (lf_get_stream(h, &hs) != LF_OK) { set_error(m, LF_ERR_BAD_ARG, "bad handle"); return LF_ERR_BAD_ARG; }
-    return stream_after(m, m->ev_out, static_cast<hipStream_t>(hs), m->stream);
-}
-
 static const char* kMapStageNames[LF_MAP_N_STAGES] = { "assoc_pack_queries", "assoc_mfma", "map_pack_block", "map_update" };   // stage 0 is gone (queries are expanded inside the association kernel): always 0 calls
 
 extern "C" const char* lf_map_stage_name(int stage) { return (stage >= 0 && stage < LF_MAP_N_STAGES) ? kMapStageNames[stage] : "?"; }
@@ -72,7 +54,7 @@ extern "C" const char* lf_map_stage_name(int stage) { return (stage >= 0 && stag
 extern "C" int lf_map_set_profiling(lf_map* m, int enabled)
 {
     if (!m) return LF_ERR_NOT_INITIALISED;
-    m->profiling = enabled != 0;
+    core_set_profiling(m, enabled);
     if (m->profiling) {                       // fill the event pool now, not inside the first profiled steps
         (void)hipSetDevice(m->device);
         m->clock.prefill(512);
@@ -98,76 +80,63 @@ extern "C" int lf_map_get_timing(lf_map* m, double* ms_per_stage, int32_t* launc
     return LF_OK;
 }
 
-extern "C" const char* lf_map_last_error(const lf_map* m) { return m ? m->err : g_map_create_err; }
+extern "C" const char* lf_map_last_error(const lf_map* m) { return m ? m->err : g_map_create_err.text; }
 
 extern "C" void lf_map_destroy(lf_map* m)
 {
     if (!m) return;
-    (void)hipSetDevice(m->device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
-    for (hipEvent_t e : { m->ev_state, m->ev_in, m->ev_out }) if (e) (void)hipEventDestroy(e);
-    if (m->stream) (void)hipStreamDestroy(m->stream);
+    close_core(m, { m->ev_state, m->ev_in, m->ev_out });
     delete m;                    // the buffers free themselves
 }
 
 extern "C" int lf_map_create(int device_id, const lf_map_config* cfg, lf_map** out)
 {
-    if (!cfg || !out) { snprintf(g_map_create_err, sizeof(g_map_create_err), "lf_map_create: null argument"); return LF_ERR_BAD_ARG; }
+    if (!cfg || !out) return g_map_create_err.refuse("lf_map_create: null argument");
     *out = nullptr;
     if (cfg->capacity < 64 || cfg->capacity > (1 << 21) || cfg->max_distance < 0 || cfg->max_distance > 128 ||
         (cfg->policy != LF_MAP_APPEND && cfg->policy != LF_MAP_MERGE) || (cfg->when_full != LF_MAP_RING && cfg->when_full != LF_MAP_FULL_ERROR) ||
-        (cfg->policy == LF_MAP_MERGE && (cfg->merge_distance < 0 || cfg->merge_distance > cfg->max_distance))) {
-        snprintf(g_map_create_err, sizeof(g_map_create_err), "lf_map_create: bad configuration (capacity %d in [64, 2^21], max_distance %d in [0,128], policy %d, when_full %d, merge_distance %d <= max_distance)",
-                  cfg->capacity, cfg->max_distance, cfg->policy, cfg->when_full, cfg->merge_distance);
-        return LF_ERR_BAD_ARG;
-    }
-    if (const int rc = check_device(device_id, "lf_map_create", g_map_create_err, sizeof(g_map_create_err))) return rc;
+        (cfg->policy == LF_MAP_MERGE && (cfg->merge_distance < 0 || cfg->merge_distance > cfg->max_distance)))
+        return g_map_create_err.refuse("lf_map_create: bad configuration (capacity %d in [64, 2^21], max_distance %d in [0,128], policy %d, when_full %d, merge_distance %d <= max_distance)",
+                                       cfg->capacity, cfg->max_distance, cfg->policy, cfg->when_full, cfg->merge_distance);
+    if (const int rc = g_map_create_err.check_device(device_id, "lf_map_create")) return rc;
     lf_map* m = new (std::nothrow) lf_map();
     if (!m) return LF_ERR_HIP;
-    m->cfg = *cfg; m->device = device_id;
+    m->cfg = *cfg;
     memset(&m->d, 0, sizeof(m->d));
-    auto fail = [&](int rc) { snprintf(g_map_create_err, sizeof(g_map_create_err), "%s", m->err); lf_map_destroy(m); return rc; };
+    auto fail = [&](int rc) { return g_map_create_err.fail(m, rc, lf_map_destroy); };
     const size_t cap = (size_t)cfg->capacity;
     m->cap_pad = assoc_rows_padded_m(cfg->capacity);
-#define TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error(m, LF_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); return fail(LF_ERR_HIP); } } while (0)
-    TRY(hipSetDevice(device_id));
-    {
-        // The map's steps are the one serial chain of a pipelined front end (step k's association needs step k - 1's update): its
-        // kernels go to a HIGH-PRIORITY stream, so that their workgroups (76 KB of LDS each) are not the last to find room between the
-        // region-growing workgroups of the batches in flight (a plain stream where the device has no priority range)
-        TRY(create_stream(&m->stream, StreamClass::CHAIN));
-    }
-    TRY(hipEventCreateWithFlags(&m->ev_state, hipEventDisableTiming));
-    TRY(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
-    TRY(hipEventCreateWithFlags(&m->ev_out, hipEventDisableTiming));
-    TRY(m->code.alloc(cap * 32));
-    TRY(m->color.alloc(cap));
-    TRY(m->ground.alloc(cap * 4 * sizeof(double)));
-    TRY(m->hits.alloc(cap * sizeof(int)));
-    TRY(m->last_seen.alloc(cap * sizeof(int)));
-    TRY(m->winner.alloc(cap * sizeof(int)));
-    TRY(m->mx.alloc(m->cap_pad * 256));      // 256 B per 128-B row: the tile loop's LDS-DMA read-ahead is not shown to stay within 128 B x cap_pad
-    TRY(m->mcx.alloc(m->cap_pad * 32));
-    TRY(m->state.alloc(16 * sizeof(int)));
-    TRY(m->totals.alloc(2 * sizeof(unsigned long long)));
-    TRY(m->h_state.alloc(24 * sizeof(int)));
+    // The map's steps are the one serial chain of a pipelined front end (step k's association needs step k - 1's update): its
+    // kernels go to a HIGH-PRIORITY stream, so that their workgroups (76 KB of LDS each) are not the last to find room between the
+    // region-growing workgroups of the batches in flight (a plain stream where the device has no priority range)
+    if (const int rc = open_core(m, device_id, StreamClass::CHAIN, { &m->ev_state, &m->ev_in, &m->ev_out })) return fail(rc);
+    LF_CREATE_TRY(m, fail, m->code.alloc(cap * 32));
+    LF_CREATE_TRY(m, fail, m->color.alloc(cap));
+    LF_CREATE_TRY(m, fail, m->ground.alloc(cap * 4 * sizeof(double)));
+    LF_CREATE_TRY(m, fail, m->hits.alloc(cap * sizeof(int)));
+    LF_CREATE_TRY(m, fail, m->last_seen.alloc(cap * sizeof(int)));
+    LF_CREATE_TRY(m, fail, m->winner.alloc(cap * sizeof(int)));
+    LF_CREATE_TRY(m, fail, m->mx.alloc(m->cap_pad * 256));      // 256 B per 128-B row: the tile loop's LDS-DMA read-ahead is not shown to stay within 128 B x cap_pad
+    LF_CREATE_TRY(m, fail, m->mcx.alloc(m->cap_pad * 32));
+    LF_CREATE_TRY(m, fail, m->state.alloc(16 * sizeof(int)));
+    LF_CREATE_TRY(m, fail, m->totals.alloc(2 * sizeof(unsigned long long)));
+    LF_CREATE_TRY(m, fail, m->h_state.alloc(24 * sizeof(int)));
     m->d.code = m->code; m->d.color = m->color; m->d.ground = m->ground; m->d.hits = m->hits; m->d.last_seen = m->last_seen;
     m->d.winner = m->winner; m->d.mx = m->mx; m->d.mcx = m->mcx; m->d.state = m->state; m->d.totals = m->totals;
     memset(m->h_state, 0, 24 * sizeof(int));
     // rows beyond the map's size must read as "all zero" operands (distance 128): zero everything once
-    TRY(hipMemsetAsync(m->d.mx, 0, m->cap_pad * 256, m->stream));
-    TRY(hipMemsetAsync(m->d.mcx, 0, m->cap_pad * 32, m->stream));
-    TRY(hipMemsetAsync(m->d.code, 0, cap * 32, m->stream));
-    TRY(hipMemsetAsync(m->d.color, 0, cap, m->stream));
-    TRY(hipMemsetAsync(m->d.ground, 0, cap * 4 * sizeof(double), m->stream));
-    TRY(hipMemsetAsync(m->d.hits, 0, cap * sizeof(int), m->stream));
-    TRY(hipMemsetAsync(m->d.last_seen, 0, cap * sizeof(int), m->stream));
-    TRY(hipMemsetAsync(m->d.state, 0, 16 * sizeof(int), m->stream));
-    TRY(hipMemsetAsync(m->d.totals, 0, 2 * sizeof(unsigned long long), m->stream));
+    LF_CREATE_TRY(m, fail, hipMemsetAsync(m->d.mx, 0, m->cap_pad * 256, m->stream));
+    LF_CREATE_TRY(m, fail, hipMemsetAsync(m->d.mcx, 0, m->cap_pad * 32, m->stream));
+    LF_CREATE_TRY(m, fail, hipMemsetAsync(m->d.code, 0, cap * 32, m->stream));
+    LF_CREATE_TRY(m, fail, hipMemsetAsync(m->d.color, 0, cap, m->stream));
+    LF_CREATE_TRY(m, fail, hipMemsetAsync(m->d.ground, 0, cap * 4 * sizeof(double), m->stream));
+    LF_CREATE_TRY(m, fail, hipMemsetAsync(m->d.hits, 0, cap * sizeof(int), m->stream));
+    LF_CREATE_TRY(m, fail, hipMemsetAsync(m->d.last_seen, 0, cap * sizeof(int), m->stream));
+    LF_CREATE_TRY(m, fail, hipMemsetAsync(m->d.state, 0, 16 * sizeof(int), m->stream));
+    LF_CREATE_TRY(m, fail, hipMemsetAsync(m->d.totals, 0, 2 * sizeof(unsigned long long), m->stream));
     launch_fill_i32(m->d.winner, cap, -1, m->stream);
-    TRY(hipGetLastError());
-    TRY(hipStreamSynchronize(m->stream));
-#undef TRY
+    LF_CREATE_TRY(m, fail, hipGetLastError());
+    LF_CREATE_TRY(m, fail, hipStreamSynchronize(m->stream));
     m->d.capacity = cfg->capacity; m->d.policy = cfg->policy; m->d.kept_only = cfg->kept_only;
     m->d.merge_distance = cfg->merge_distance; m->d.when_full = cfg->when_full;
     *out = m;
@@ -190,10 +159,7 @@ extern "C" int lf_map_stream_priority(const lf_map* m, int* priority, int* least
 
 extern "C" int lf_map_synchronize(lf_map* m)
 {
-    if (!m) return LF_ERR_NOT_INITIALISED;
-    LF_HIP_CHECK(m, hipSetDevice(m->device));
-    LF_HIP_CHECK(m, hipStreamSynchronize(m->stream));
-    return LF_OK;
+    return m ? core_synchronize(m) : LF_ERR_NOT_INITIALISED;
 }
 
 int update_blocks(lf_map* m, const uint8_t* blocks, int n_blocks, int block_rows, int force_append, long long rows_hint)

@@ -160,8 +160,10 @@ struct lf_map : lf::Core {
 // host has not returned an error for yet is reported here, once
 int refresh_state(lf_map* m, bool block = true);
 int queue_state_copy(lf_map* m);                  // the state's copy into the pinned mirror, behind what is queued so far
-int after_handle(lf_map* m, lf_handle* h);        // the map's stream waits for everything queued so far on the handle's stream
-int release_handle(lf_map* m, lf_handle* h);      // the handle's later work waits for what the map has queued so far
+// lanefront_core.h's with the map's two events: the map's stream waits for everything queued so far on the handle's stream; the
+// handle's later work waits for what the map has queued so far
+inline int after_handle(lf_map* m, lf_handle* h) { return lf::after_handle(m, m->ev_in, h, ""); }
+inline int release_handle(lf_map* m, lf_handle* h) { return lf::release_handle(m, m->ev_out, h, ""); }
 // rows_hint: how many segment rows the blocks really hold when the host knows it (-1: assume they are full)
 int update_blocks(lf_map* m, const uint8_t* blocks, int n_blocks, int block_rows, int force_append, long long rows_hint = -1);
 // the map's size behind everything queued so far, from 0 to the capacity: a blocking refresh_state, so a failing update is reported

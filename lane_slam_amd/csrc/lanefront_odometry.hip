@@ -36,9 +36,7 @@ struct lf_odometry : lf::Core {
     StageClock clock{ODO_N_STAGES, 4096, false};
 };
 
-static char g_odo_create_err[512] = "no error";
-
-static bool is_finite(double x) { return x - x == 0; }
+static CreateError g_odo_create_err;
 
 static const char* check_config(const lf_odometry_config& c, char* buf, size_t size)
 {
@@ -60,16 +58,13 @@ extern "C" void lf_odometry_default_config(lf_odometry_config* c)
     c->flip_y = 0;
 }
 
-extern "C" const char* lf_odometry_last_error(const lf_odometry* od) { return od ? od->err : g_odo_create_err; }
+extern "C" const char* lf_odometry_last_error(const lf_odometry* od) { return od ? od->err : g_odo_create_err.text; }
 
 extern "C" void lf_odometry_destroy(lf_odometry* od)
 {
     if (!od) return;
-    (void)hipSetDevice(od->device);
-    if (od->stream) (void)hipStreamSynchronize(od->stream);
-    if (od->ev_staged) (void)hipEventDestroy(od->ev_staged);
-    if (od->stream) (void)hipStreamDestroy(od->stream);
-    delete od;                   // the buffers free themselves
+    close_core(od, { od->ev_staged });
+    delete od;                  // the buffers free themselves
 }
 
 // the bytes of one step's input block: the 8-byte arrays first
@@ -108,34 +103,28 @@ extern "C" int lf_odometry_get_state(lf_odometry* od, int stream, lf_odometry_st
 
 extern "C" int lf_odometry_create(int device_id, const lf_odometry_config* cfg, int n_streams, int max_commands, int max_frames, lf_odometry** out)
 {
-    if (!cfg || !out) { snprintf(g_odo_create_err, sizeof(g_odo_create_err), "lf_odometry_create: null argument"); return LF_ERR_BAD_ARG; }
+    if (!cfg || !out) return g_odo_create_err.refuse("lf_odometry_create: null argument");
     *out = nullptr;
     char why[256];
-    if (check_config(*cfg, why, sizeof(why))) { snprintf(g_odo_create_err, sizeof(g_odo_create_err), "lf_odometry_create: %s", why); return LF_ERR_BAD_ARG; }
-    if (n_streams < 1 || n_streams > LF_ODOMETRY_MAX_STREAMS || max_commands < 1 || max_commands > kOdoMaxCommands || max_frames < 1 || max_frames > kOdoMaxFrames) {
-        snprintf(g_odo_create_err, sizeof(g_odo_create_err), "lf_odometry_create: n_streams %d in [1, %d], max_commands %d in [1, 2^22], max_frames %d in [1, 2^22]",
-                 n_streams, LF_ODOMETRY_MAX_STREAMS, max_commands, max_frames);
-        return LF_ERR_BAD_ARG;
-    }
-    if (const int rc = check_device(device_id, "lf_odometry_create", g_odo_create_err, sizeof(g_odo_create_err))) return rc;
+    if (check_config(*cfg, why, sizeof(why))) return g_odo_create_err.refuse("lf_odometry_create: %s", why);
+    if (n_streams < 1 || n_streams > LF_ODOMETRY_MAX_STREAMS || max_commands < 1 || max_commands > kOdoMaxCommands || max_frames < 1 || max_frames > kOdoMaxFrames)
+        return g_odo_create_err.refuse("lf_odometry_create: n_streams %d in [1, %d], max_commands %d in [1, 2^22], max_frames %d in [1, 2^22]", n_streams,
+                                       LF_ODOMETRY_MAX_STREAMS, max_commands, max_frames);
+    if (const int rc = g_odo_create_err.check_device(device_id, "lf_odometry_create")) return rc;
     lf_odometry* od = new (std::nothrow) lf_odometry();
     if (!od) return LF_ERR_HIP;
-    od->cfg = *cfg; od->device = device_id; od->n_streams = n_streams; od->max_commands = max_commands; od->max_frames = max_frames;
+    od->cfg = *cfg; od->n_streams = n_streams; od->max_commands = max_commands; od->max_frames = max_frames;
     od->last_stamp.assign(n_streams, 0); od->seen.resize(n_streams); od->cursor.resize(n_streams + 1);
-    auto fail = [&](int rc) { snprintf(g_odo_create_err, sizeof(g_odo_create_err), "%s", od->err); lf_odometry_destroy(od); return rc; };
-#define TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error(od, LF_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); return fail(LF_ERR_HIP); } } while (0)
-    TRY(hipSetDevice(device_id));
-    TRY(hipStreamCreateWithFlags(&od->stream, hipStreamNonBlocking));
-    TRY(hipEventCreateWithFlags(&od->ev_staged, hipEventDisableTiming));
+    auto fail = [&](int rc) { return g_odo_create_err.fail(od, rc, lf_odometry_destroy); };
+    if (const int rc = open_core(od, device_id, StreamClass::PLAIN, { &od->ev_staged })) return fail(rc);
     const size_t n = max_commands, total = in_bytes(n, max_frames, n_streams);
-    TRY(od->h_in.alloc(total));
-    TRY(od->d_in.alloc(total));
-    TRY(od->flags.alloc(n));
-    TRY(od->work.alloc(7 * n * sizeof(double)));
-    TRY(od->pose.alloc(3 * n * sizeof(double)));
-    TRY(od->start.alloc(3 * (size_t)n_streams * sizeof(double)));
-    TRY(od->state.alloc((size_t)n_streams * sizeof(lf_odometry_state)));
-#undef TRY
+    LF_CREATE_TRY(od, fail, od->h_in.alloc(total));
+    LF_CREATE_TRY(od, fail, od->d_in.alloc(total));
+    LF_CREATE_TRY(od, fail, od->flags.alloc(n));
+    LF_CREATE_TRY(od, fail, od->work.alloc(7 * n * sizeof(double)));
+    LF_CREATE_TRY(od, fail, od->pose.alloc(3 * n * sizeof(double)));
+    LF_CREATE_TRY(od, fail, od->start.alloc(3 * (size_t)n_streams * sizeof(double)));
+    LF_CREATE_TRY(od, fail, od->state.alloc((size_t)n_streams * sizeof(lf_odometry_state)));
     if (const int rc = lf_odometry_reset(od, -1, nullptr)) return fail(rc);
     *out = od;
     return LF_OK;
@@ -143,10 +132,7 @@ extern "C" int lf_odometry_create(int device_id, const lf_odometry_config* cfg, 
 
 extern "C" int lf_odometry_synchronize(lf_odometry* od)
 {
-    if (!od) return LF_ERR_NOT_INITIALISED;
-    LF_HIP_CHECK(od, hipSetDevice(od->device));
-    LF_HIP_CHECK(od, hipStreamSynchronize(od->stream));
-    return LF_OK;
+    return od ? core_synchronize(od) : LF_ERR_NOT_INITIALISED;
 }
 
 #define ODO_REFUSE(...) do { set_error(od, LF_ERR_BAD_ARG, "lf_odometry_step: " __VA_ARGS__); return LF_ERR_BAD_ARG; } while (0)
@@ -244,15 +230,10 @@ extern "C" int lf_odometry_step(lf_odometry* od, int n_commands, const int64_t* 
 
 extern "C" int lf_odometry_set_profiling(lf_odometry* od, int on)
 {
-    if (!od) return LF_ERR_NOT_INITIALISED;
-    od->profiling = on != 0;
-    return LF_OK;
+    return od ? core_set_profiling(od, on) : LF_ERR_NOT_INITIALISED;
 }
 
 extern "C" int lf_odometry_get_timing(lf_odometry* od, double* ms, int32_t* launches, int n_stages)
 {
-    if (!od) return LF_ERR_NOT_INITIALISED;
-    LF_HIP_CHECK(od, hipSetDevice(od->device));
-    od->clock.take(ms, launches, n_stages);
-    return LF_OK;
+    return od ? core_take_timing(od, od->clock, ms, launches, n_stages) : LF_ERR_NOT_INITIALISED;
 }

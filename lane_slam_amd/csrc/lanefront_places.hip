@@ -10,11 +10,12 @@
 #include <new>
 #include <vector>
 #include "k_places.h"
-#include "lanefront_core.h"
+#include "lanefront_frames.h"
 
 using namespace lf;
 
 static_assert(sizeof(lf_places_config) == 32 && sizeof(lf_place_hit) == 16, "lanefront_places.h states these sizes");
+static_assert(pc::kGatherInts == 3, "lanefront_frames.h's KeyPairs reads the gather jobs");
 
 constexpr int kPlacesStages = 3;           // k_places_score, k_places_top, k_frame_motion
 
@@ -44,7 +45,7 @@ struct lf_places : lf::Core {
     pc::Store store() const { return pc::Store{ key_offset.p, ground.p, color.p, keep.p, code.p, count }; }
 };
 
-static char g_places_create_err[512] = "no error";
+static CreateError g_places_create_err;
 
 static const char* bad_config(const lf_places_config* c)
 {
@@ -66,54 +67,42 @@ extern "C" void lf_places_default_config(lf_places_config* c)
     c->top_k = 4; c->min_score = 3; c->key_gap = 0;
 }
 
-extern "C" const char* lf_places_last_error(const lf_places* pl) { return pl ? pl->err : g_places_create_err; }
+extern "C" const char* lf_places_last_error(const lf_places* pl) { return pl ? pl->err : g_places_create_err.text; }
 
 extern "C" void lf_places_destroy(lf_places* pl)
 {
     if (!pl) return;
-    (void)hipSetDevice(pl->device);
-    if (pl->stream) (void)hipStreamSynchronize(pl->stream);
-    if (pl->ev_in) (void)hipEventDestroy(pl->ev_in);
-    if (pl->ev_out) (void)hipEventDestroy(pl->ev_out);
-    if (pl->stream) (void)hipStreamDestroy(pl->stream);
+    close_core(pl, { pl->ev_in, pl->ev_out });
     delete pl;                   // the buffers free themselves
 }
 
 extern "C" int lf_places_create(int device_id, int max_keys, int max_segments, int max_queries, lf_places** out)
 {
-    if (!out) { snprintf(g_places_create_err, sizeof(g_places_create_err), "lf_places_create: null argument"); return LF_ERR_BAD_ARG; }
+    if (!out) return g_places_create_err.refuse("lf_places_create: null argument");
     *out = nullptr;
     if (max_keys < 1 || max_keys > LF_PLACES_MAX_KEYS || max_segments < 1 || max_segments > LF_PLACES_MAX_SEGMENTS || max_queries < 1 ||
-        max_queries > LF_PLACES_MAX_QUERIES || (long long)max_keys * max_queries > LF_PLACES_MAX_SCORES) {
-        snprintf(g_places_create_err, sizeof(g_places_create_err),
-                 "lf_places_create: max_keys %d in [1, %d], max_segments %d in [1, %d], max_queries %d in [1, %d], max_keys * max_queries <= %d", max_keys,
-                 LF_PLACES_MAX_KEYS, max_segments, LF_PLACES_MAX_SEGMENTS, max_queries, LF_PLACES_MAX_QUERIES, LF_PLACES_MAX_SCORES);
-        return LF_ERR_BAD_ARG;
-    }
-    if (const int rc = check_device(device_id, "lf_places_create", g_places_create_err, sizeof(g_places_create_err))) return rc;
+        max_queries > LF_PLACES_MAX_QUERIES || (long long)max_keys * max_queries > LF_PLACES_MAX_SCORES)
+        return g_places_create_err.refuse("lf_places_create: max_keys %d in [1, %d], max_segments %d in [1, %d], max_queries %d in [1, %d], max_keys * max_queries <= %d",
+                                          max_keys, LF_PLACES_MAX_KEYS, max_segments, LF_PLACES_MAX_SEGMENTS, max_queries, LF_PLACES_MAX_QUERIES, LF_PLACES_MAX_SCORES);
+    if (const int rc = g_places_create_err.check_device(device_id, "lf_places_create")) return rc;
     lf_places* pl = new (std::nothrow) lf_places();
     if (!pl) return LF_ERR_HIP;
-    pl->device = device_id; pl->max_keys = max_keys; pl->max_segments = max_segments; pl->max_queries = max_queries;
+    pl->max_keys = max_keys; pl->max_segments = max_segments; pl->max_queries = max_queries;
     pl->h_key_offset.assign(1, 0);
-    auto fail = [&](int rc) { snprintf(g_places_create_err, sizeof(g_places_create_err), "%s", pl->err); lf_places_destroy(pl); return rc; };
-#define TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error(pl, LF_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); return fail(LF_ERR_HIP); } } while (0)
-    TRY(hipSetDevice(device_id));
-    TRY(hipStreamCreateWithFlags(&pl->stream, hipStreamNonBlocking));
-    TRY(hipEventCreateWithFlags(&pl->ev_in, hipEventDisableTiming));
-    TRY(hipEventCreateWithFlags(&pl->ev_out, hipEventDisableTiming));
+    auto fail = [&](int rc) { return g_places_create_err.fail(pl, rc, lf_places_destroy); };
+    if (const int rc = open_core(pl, device_id, StreamClass::PLAIN, { &pl->ev_in, &pl->ev_out })) return fail(rc);
     const size_t ns = (size_t)max_segments, nq = (size_t)max_queries;
-    TRY(pl->key_offset.alloc(((size_t)max_keys + 1) * sizeof(int)));
-    TRY(pl->ground.alloc(ns * 32));
-    TRY(pl->code.alloc(ns * 32));
-    TRY(pl->color.alloc(ns));
-    TRY(pl->keep.alloc(ns));
-    TRY(pl->hits.alloc(nq * LF_PLACES_MAX_TOP_K * sizeof(lf_place_hit)));
-    TRY(pl->jobs.alloc(nq * pc::kQueryInts * sizeof(int)));
-    TRY(pl->mjobs.alloc(nq * (fm::kJobInts * sizeof(int) + 3 * sizeof(double))));
-    TRY(pl->res.alloc(nq * sizeof(lf_motion_result)));
-    TRY(hipMemsetAsync(pl->key_offset.p, 0, sizeof(int), pl->stream));
-    TRY(hipStreamSynchronize(pl->stream));
-#undef TRY
+    LF_CREATE_TRY(pl, fail, pl->key_offset.alloc(((size_t)max_keys + 1) * sizeof(int)));
+    LF_CREATE_TRY(pl, fail, pl->ground.alloc(ns * 32));
+    LF_CREATE_TRY(pl, fail, pl->code.alloc(ns * 32));
+    LF_CREATE_TRY(pl, fail, pl->color.alloc(ns));
+    LF_CREATE_TRY(pl, fail, pl->keep.alloc(ns));
+    LF_CREATE_TRY(pl, fail, pl->hits.alloc(nq * LF_PLACES_MAX_TOP_K * sizeof(lf_place_hit)));
+    LF_CREATE_TRY(pl, fail, pl->jobs.alloc(nq * pc::kQueryInts * sizeof(int)));
+    LF_CREATE_TRY(pl, fail, pl->mjobs.alloc(motion_jobs_bytes(max_queries, true)));
+    LF_CREATE_TRY(pl, fail, pl->res.alloc(nq * sizeof(lf_motion_result)));
+    LF_CREATE_TRY(pl, fail, hipMemsetAsync(pl->key_offset.p, 0, sizeof(int), pl->stream));
+    LF_CREATE_TRY(pl, fail, hipStreamSynchronize(pl->stream));
     *out = pl;
     return LF_OK;
 }
@@ -121,10 +110,9 @@ extern "C" int lf_places_create(int device_id, int max_keys, int max_segments, i
 extern "C" int lf_places_synchronize(lf_places* pl)
 {
     if (!pl) return LF_ERR_BAD_ARG;
-    LF_HIP_CHECK(pl, hipSetDevice(pl->device));
-    LF_HIP_CHECK(pl, hipStreamSynchronize(pl->stream));
-    pl->queued = false;
-    return LF_OK;
+    const int rc = core_synchronize(pl);
+    if (rc == LF_OK) pl->queued = false;
+    return rc;
 }
 
 extern "C" int lf_places_count(const lf_places* pl, int32_t* n_keys, int32_t* n_segments)
@@ -147,57 +135,23 @@ namespace {
 
 #define PLACES_REFUSE(who, ...) do { set_error(pl, LF_ERR_BAD_ARG, who ": " __VA_ARGS__); return LF_ERR_BAD_ARG; } while (0)
 
-// what every entry point that reads a batch refuses about it, or null
-const char* bad_batch(const lf_segments* segs, int n, int n_frames)
-{
-    if (!segs) return "null segs";
-    if (n < 0 || n_frames < 1 || n_frames > ma::kMaxFrames) return "n < 0 or n_frames outside 1 .. 4096";
-    if (n > 0 && (!segs->frame_offset || !segs->ground || !segs->code)) return "frame_offset, ground and code are required";
-    return nullptr;
-}
+const char* const kWho = "lf_places: ";     // before "bad handle"
 
 // A call begins: the device, the uploads an earlier call left queued from the host vectors (they are about to be rewritten), the
 // order behind h, and the frames' offsets on the host.
-int begin_call(lf_places* pl, lf_handle* h, void** hs, const lf_segments* segs, int n, int n_frames, int on_device)
+int begin_call(lf_places* pl, lf_handle* h, const lf_segments* segs, int n, int n_frames, int on_device)
 {
     LF_HIP_CHECK(pl, hipSetDevice(pl->device));
     if (pl->queued) { LF_HIP_CHECK(pl, hipStreamSynchronize(pl->stream)); pl->queued = false; }
-    *hs = nullptr;
-    if (h) {
-        if (lf_get_stream(h, hs) != LF_OK) { set_error(pl, LF_ERR_BAD_ARG, "lf_places: bad handle"); return LF_ERR_BAD_ARG; }
-        if (const int rc = stream_after(pl, pl->ev_in, pl->stream, static_cast<hipStream_t>(*hs))) return rc;
-    }
-    pl->h_fo.assign((size_t)n_frames + 1, 0);
-    if (n > 0) {
-        if (on_device) {
-            LF_HIP_CHECK(pl, hipMemcpyAsync(pl->h_fo.data(), segs->frame_offset, ((size_t)n_frames + 1) * 4, hipMemcpyDeviceToHost, pl->stream));
-            LF_HIP_CHECK(pl, hipStreamSynchronize(pl->stream));
-        } else {
-            memcpy(pl->h_fo.data(), segs->frame_offset, ((size_t)n_frames + 1) * 4);
-        }
-    }
-    return LF_OK;
-}
-
-// frame f's segments, clamped as the contract clamps them
-void range_of(const lf_places* pl, int n, int f, int* o)
-{
-    const int lo = pl->h_fo[f], hi = pl->h_fo[f + 1];
-    o[0] = lo < 0 ? 0 : (lo > n ? n : lo);
-    o[1] = hi < o[0] ? o[0] : (hi > n ? n : hi);
+    if (const int rc = after_handle(pl, pl->ev_in, h, kWho)) return rc;
+    return fetch_frame_offsets(pl, segs, n, n_frames, on_device, pl->h_fo);
 }
 
 // the batch's arrays on the device: the caller's own, or copies queued by st.upload()
 pc::Frames frames_of(lf_places* pl, Staging& st, const lf_segments* segs, int n, int on_device)
 {
     pc::Frames f = { nullptr, nullptr, nullptr, nullptr };
-    const size_t c = (size_t)n;
-    if (n > 0) {
-        f.ground = st.in(on_device, segs->ground, c * 32, pl->st_ground);
-        f.code = st.in(on_device, segs->code, c * 32, pl->st_code);
-        if (segs->color) f.color = st.in(on_device, segs->color, c, pl->st_color);
-        if (segs->keep) f.keep = st.in(on_device, segs->keep, c, pl->st_keep);
-    }
+    stage_frames(st, segs, n, on_device, pl->st_ground, pl->st_code, pl->st_color, pl->st_keep, &f);
     return f;
 }
 
@@ -240,14 +194,13 @@ extern "C" int lf_places_add(lf_places* pl, lf_handle* h, const lf_segments* seg
         set_error(pl, LF_ERR_CAPACITY, "lf_places_add: %d keys and %d more are over max_keys = %d", pl->count, n_add, pl->max_keys);
         return LF_ERR_CAPACITY;
     }
-    void* hs;
     int rc;
-    if ((rc = begin_call(pl, h, &hs, segs, n, n_frames, on_device))) return rc;
+    if ((rc = begin_call(pl, h, segs, n, n_frames, on_device))) return rc;
     pl->h_jobs.resize((size_t)n_add * pc::kGatherInts);
     size_t total = 0;
     for (int k = 0; k < n_add; ++k) {
         int r[2];
-        range_of(pl, n, frames ? frames[k] : k, r);
+        frame_range(pl->h_fo.data(), n, frames ? frames[k] : k, r);
         int* j = pl->h_jobs.data() + (size_t)k * pc::kGatherInts;
         j[0] = r[0]; j[1] = r[1] - r[0];
         total += (size_t)j[1];
@@ -277,7 +230,7 @@ extern "C" int lf_places_add(lf_places* pl, lf_handle* h, const lf_segments* seg
     }
     *first_key = pl->count;
     pl->count += n_add; pl->used += (int)total;
-    if (h && (rc = stream_after(pl, pl->ev_out, static_cast<hipStream_t>(hs), pl->stream))) return rc;
+    if ((rc = release_handle(pl, pl->ev_out, h, kWho))) return rc;
     if (on_device) { pl->queued = true; return LF_OK; }
     LF_HIP_CHECK(pl, hipStreamSynchronize(pl->stream));        // a host caller's arrays are its own again
     return LF_OK;
@@ -312,13 +265,12 @@ extern "C" int lf_places_query(lf_places* pl, lf_handle* h, const lf_segments* s
         for (size_t r = 0; r < (size_t)n_queries * cfg->top_k; ++r) hits[r] = lf_place_hit{ -1, 0, 0, 0 };
         return LF_OK;
     }
-    void* hs;
     int rc;
-    if ((rc = begin_call(pl, h, &hs, segs, n, n_frames, on_device))) return rc;
+    if ((rc = begin_call(pl, h, segs, n, n_frames, on_device))) return rc;
     pl->h_jobs.resize((size_t)n_queries * pc::kQueryInts);
     for (int k = 0; k < n_queries; ++k) {
         int* j = pl->h_jobs.data() + (size_t)k * pc::kQueryInts;
-        range_of(pl, n, query_frames ? query_frames[k] : k, j);
+        frame_range(pl->h_fo.data(), n, query_frames ? query_frames[k] : k, j);
         const int lim = key_limit ? key_limit[k] : pl->count;
         j[2] = lim < 0 ? 0 : (lim > pl->count ? pl->count : lim);
         j[3] = 0;
@@ -340,7 +292,7 @@ extern "C" int lf_places_query(lf_places* pl, lf_handle* h, const lf_segments* s
         pc::launch_places_top(*cfg, q, pl->stream);
     }
     LF_HIP_CHECK(pl, hipGetLastError());
-    if (h && (rc = stream_after(pl, pl->ev_out, static_cast<hipStream_t>(hs), pl->stream))) return rc;
+    if ((rc = release_handle(pl, pl->ev_out, h, kWho))) return rc;
     return fetch(pl, { { hits, pl->hits.p, hit_bytes }, { scores, pl->score.p, score_bytes } });
 }
 
@@ -360,9 +312,8 @@ extern "C" int lf_places_motion(lf_places* pl, lf_handle* h, const lf_segments* 
         if (!isfinite(prior[k])) PLACES_REFUSE("lf_places_motion", "the prior of pair %d is not finite", k / 3);
     if (const char* why = motion_bad_config(cfg)) PLACES_REFUSE("lf_places_motion", "bad configuration (%s)", why);
     if (n_pairs == 0) return LF_OK;
-    void* hs;
     int rc;
-    if ((rc = begin_call(pl, h, &hs, segs, n, n_frames, on_device))) return rc;
+    if ((rc = begin_call(pl, h, segs, n, n_frames, on_device))) return rc;
     // every frame named goes behind the keys once
     pl->stage_at.assign((size_t)n_frames, -1);
     pl->h_jobs.clear();
@@ -371,7 +322,7 @@ extern "C" int lf_places_motion(lf_places* pl, lf_handle* h, const lf_segments* 
         const int f = pair_kf[2 * p + 1];
         if (pl->stage_at[f] >= 0) continue;
         int r[2];
-        range_of(pl, n, f, r);
+        frame_range(pl->h_fo.data(), n, f, r);
         pl->stage_at[f] = (int)(pl->h_jobs.size() / pc::kGatherInts);
         pl->h_jobs.push_back(r[0]); pl->h_jobs.push_back(r[1] - r[0]); pl->h_jobs.push_back(0);
         staged += (size_t)(r[1] - r[0]);
@@ -383,27 +334,16 @@ extern "C" int lf_places_motion(lf_places* pl, lf_handle* h, const lf_segments* 
     const int n_staged = (int)(pl->h_jobs.size() / pc::kGatherInts);
     for (int k = 0, at = pl->max_segments; k < n_staged; ++k) { pl->h_jobs[(size_t)k * pc::kGatherInts + 2] = at; at += pl->h_jobs[(size_t)k * pc::kGatherInts + 1]; }
     // the pairs' ranges in the store's arrays, and where each pair's matches go
-    const size_t job_bytes = (size_t)n_pairs * fm::kJobInts * sizeof(int), prior_bytes = prior ? (size_t)n_pairs * 3 * sizeof(double) : 0;
-    pl->h_mjobs.resize(prior_bytes + job_bytes);               // (the doubles first)
-    if (prior) memcpy(pl->h_mjobs.data(), prior, prior_bytes);
-    int* job = reinterpret_cast<int*>(pl->h_mjobs.data() + prior_bytes);
-    size_t n_match = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-        int* j = job + (size_t)p * fm::kJobInts;
-        const int* g = pl->h_jobs.data() + (size_t)pl->stage_at[pair_kf[2 * p + 1]] * pc::kGatherInts;
-        j[0] = pl->h_key_offset[pair_kf[2 * p]]; j[1] = pl->h_key_offset[pair_kf[2 * p] + 1];
-        j[2] = g[2]; j[3] = g[2] + g[1];
-        if (n_match + (size_t)g[1] > 0x7fffffffu) {
-            set_error(pl, LF_ERR_CAPACITY, "lf_places_motion: the pairs' frames hold more than 2^31 segments in all");
-            return LF_ERR_CAPACITY;
-        }
-        j[4] = (int)n_match;
-        n_match += (size_t)g[1];
+    pl->h_mjobs.resize(motion_jobs_bytes(n_pairs, prior));
+    const long long n_match = build_motion_jobs(pl->h_mjobs.data(), n_pairs, prior, KeyPairs{ pl->h_key_offset.data(), pair_kf, pl->stage_at.data(), pl->h_jobs.data() });
+    if (n_match < 0) {
+        set_error(pl, LF_ERR_CAPACITY, "lf_places_motion: the pairs' frames hold more than 2^31 segments in all");
+        return LF_ERR_CAPACITY;
     }
     Staging st(pl);
     const pc::Frames f = frames_of(pl, st, segs, n, on_device);
     if ((rc = st.upload()) || (rc = grow_room(pl, staged)) || (rc = scratch(pl, pl->jobs, pl->h_jobs.size() * sizeof(int))) ||
-        (rc = scratch(pl, pl->match, (n_match + 1) * sizeof(int))))
+        (rc = scratch(pl, pl->match, ((size_t)n_match + 1) * sizeof(int))))
         return rc;
     LF_HIP_CHECK(pl, hipMemcpyAsync(pl->jobs.p, pl->h_jobs.data(), pl->h_jobs.size() * sizeof(int), hipMemcpyHostToDevice, pl->stream));
     LF_HIP_CHECK(pl, hipMemcpyAsync(pl->mjobs.p, pl->h_mjobs.data(), pl->h_mjobs.size(), hipMemcpyHostToDevice, pl->stream));
@@ -411,29 +351,18 @@ extern "C" int lf_places_motion(lf_places* pl, lf_handle* h, const lf_segments* 
     fm::Batch b;
     memset(&b, 0, sizeof(b));
     b.ground = pl->ground.p; b.color = pl->color.p; b.keep = pl->keep.p; b.code = pl->code.p;
-    b.prior = prior ? reinterpret_cast<const double*>(pl->mjobs.p) : nullptr;
-    b.job = reinterpret_cast<const int*>(pl->mjobs.p + prior_bytes);
-    b.match = pl->match; b.res = pl->res; b.cand = nullptr; b.n_pairs = n_pairs;
-    {
-        StageClock::Scope tm(pl, pl->clock, 2);
-        fm::launch_frame_motion(*cfg, b, pl->stream);
-    }
-    LF_HIP_CHECK(pl, hipGetLastError());
-    if (h && (rc = stream_after(pl, pl->ev_out, static_cast<hipStream_t>(hs), pl->stream))) return rc;
+    b.match = pl->match; b.res = pl->res; b.cand = nullptr;
+    if ((rc = launch_motion(pl, pl->clock, 2, *cfg, b, pl->mjobs.p, n_pairs, prior != nullptr))) return rc;
+    if ((rc = release_handle(pl, pl->ev_out, h, kWho))) return rc;
     return fetch(pl, { { results, pl->res.p, (size_t)n_pairs * sizeof(lf_motion_result) } });
 }
 
 extern "C" int lf_places_set_profiling(lf_places* pl, int on)
 {
-    if (!pl) return LF_ERR_BAD_ARG;
-    pl->profiling = on != 0;
-    return LF_OK;
+    return pl ? core_set_profiling(pl, on) : LF_ERR_BAD_ARG;
 }
 
 extern "C" int lf_places_get_timing(lf_places* pl, double* ms, int32_t* launches, int n_stages)
 {
-    if (!pl) return LF_ERR_BAD_ARG;
-    LF_HIP_CHECK(pl, hipSetDevice(pl->device));
-    pl->clock.take(ms, launches, n_stages);
-    return LF_OK;
+    return pl ? core_take_timing(pl, pl->clock, ms, launches, n_stages) : LF_ERR_BAD_ARG;
 }

@@ -20,8 +20,8 @@ import math
 
 import numpy as np
 
-from . import _lib
-from .frontend import LanefrontError
+from . import _handle, _lib
+from .frontend import LanefrontError  # noqa: F401  (raised by LaneFilterBatch's calls; callers catch lane_filter.LanefrontError)
 
 PARAM_NAMES = _lib.LANE_FILTER_PARAMS
 PREDICT, UPDATE = _lib.LF_LANE_FILTER_PREDICT, _lib.LF_LANE_FILTER_UPDATE
@@ -83,41 +83,24 @@ def _dev_ptr(v):
     return int(v.data_ptr()) if hasattr(v, "data_ptr") else int(v)
 
 
-class LaneFilterBatch(object):
+class LaneFilterBatch(_handle.Handle):
     """n_streams histogram lane filters on one device (lf_lane_filter_*).  Raises without the HIP library or a GPU."""
+    PREFIX = "lf_lane_filter"
+    f = property(lambda self: self.h)              # the handle's earlier name
+    # the kernels of lf_lane_filter_get_timing, as the library names them
+    STAGES = property(lambda self: tuple(self.lib.lf_lane_filter_stage_name(i).decode() for i in range(_lib.LF_LANE_FILTER_N_STAGES)))
 
     def __init__(self, configuration, n_streams=1, max_frames=256, device=0, tables=None):
         self.configuration = check_configuration(configuration)
-        self.lib = _lib.load()
         self.c = _lib.LfLaneFilterConfig(*[float(self.configuration[k]) for k in PARAM_NAMES])
         self.n_streams, self.max_frames = int(n_streams), int(max_frames)
-        self.f = ctypes.c_void_p()
-        rc = self.lib.lf_lane_filter_create(int(device), ctypes.byref(self.c), self.n_streams, self.max_frames, ctypes.byref(self.f))
-        if rc != 0:
-            msg = self.lib.lf_lane_filter_last_error(None).decode()
-            self.f = None
-            raise LanefrontError(rc, msg)
+        self._create(int(device), ctypes.byref(self.c), self.n_streams, self.max_frames)
         r, cc = ctypes.c_int(), ctypes.c_int()
         self.lib.lf_lane_filter_grid(self.f, ctypes.byref(r), ctypes.byref(cc))
         self.rows, self.cols = r.value, cc.value
         self.tables = reference_tables(self.configuration) if tables is None else tuple(np.ascontiguousarray(t, np.float64) for t in tables)
         self.set_tables(*self.tables)
         self.reset(-1)
-
-    def close(self):
-        if getattr(self, "f", None):
-            self.lib.lf_lane_filter_destroy(self.f)
-            self.f = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != 0:
-            raise LanefrontError(rc, self.lib.lf_lane_filter_last_error(self.f).decode())
 
     def set_tables(self, sin_phi=None, w_d=None, w_phi=None, initial_belief=None):
         keep = [None if t is None else np.ascontiguousarray(t, np.float64) for t in (sin_phi, w_d, w_phi, initial_belief)]
@@ -139,9 +122,6 @@ class LaneFilterBatch(object):
         out = np.empty((self.rows, self.cols), np.float64)
         self._check(self.lib.lf_lane_filter_get_belief(self.f, int(stream), out.ctypes.data))
         return out
-
-    def synchronize(self):
-        self._check(self.lib.lf_lane_filter_synchronize(self.f))
 
     def step(self, segments, dt_v_w, streams=None, phases=PREDICT | UPDATE, beliefs=False, likelihoods=False, fe=None,
              capacity=None, wait=True):
@@ -190,16 +170,6 @@ class LaneFilterBatch(object):
             None if st is None else st.ctypes.data, dtvw.ctypes.data, int(phases), poses.ctypes.data if wait else None,
             out["belief"].ctypes.data if beliefs else None, out["ml"].ctypes.data if likelihoods else None))
         return out if wait else None
-
-    def set_profiling(self, on):
-        self._check(self.lib.lf_lane_filter_set_profiling(self.f, int(bool(on))))
-
-    def timing(self):
-        """{kernel: (ms, launches)} accumulated since the previous call (lf_lane_filter_get_timing)."""
-        n = _lib.LF_LANE_FILTER_N_STAGES
-        ms, cnt = np.zeros(n, np.float64), np.zeros(n, np.int32)
-        self._check(self.lib.lf_lane_filter_get_timing(self.f, ms.ctypes.data, cnt.ctypes.data, n))
-        return {self.lib.lf_lane_filter_stage_name(i).decode(): (float(ms[i]), int(cnt[i])) for i in range(n)}
 
     def poses(self, n_frames):
         """The last step's poses (waits for it)."""

@@ -15,16 +15,11 @@ import os
 
 import numpy as np
 
-from . import _cdecl, _lib
-from .frontend import LanefrontError
+from . import _handle, _lib
+from .frontend import LanefrontError  # noqa: F401  (raised by FrameMotion's calls; callers catch motion.LanefrontError)
 
 HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "lanefront_motion.h")
-if not os.path.exists(HEADER_PATH):
-    raise RuntimeError(
-        "lanefront: %s is missing. The binding is read from the header, so the package is used from its source tree (the "
-        "directory that holds include/ next to lane_slam_amd/). There is no hand-written table to fall back to." % HEADER_PATH)
-with open(HEADER_PATH) as _f:
-    HEADER = _cdecl.Header(_f.read(), base=_lib.HEADER)       # lf_handle and lf_segments are lanefront.h's
+HEADER, load = _handle.bind("lanefront_motion.h", base=_lib.HEADER)      # lf_handle and lf_segments are lanefront.h's
 
 EXPORTS = tuple(HEADER.functions)
 LfMotionConfig, LfMotionResult = HEADER.structs["lf_motion_config"], HEADER.structs["lf_motion_result"]
@@ -34,23 +29,6 @@ SOURCES = {"none": HEADER.constants["LF_MOTION_SOURCE_NONE"], "search": HEADER.c
            "prior": HEADER.constants["LF_MOTION_SOURCE_PRIOR"]}
 OK = 0                                      # LF_ALIGN_OK (include/lanefront.h)
 STAGES = ("k_frame_motion",)
-
-_bound = None
-
-
-def load():
-    """liblanefront.so with the motion entry points typed from the header"""
-    global _bound
-    if _bound is None:
-        lib = _lib.load()
-        missing = [n for n in EXPORTS if not hasattr(lib, n)]
-        if missing:
-            raise RuntimeError("lanefront: %s lacks %r; rebuild the HIP library (make -C lane_slam_amd/csrc)" % (_lib.SO_PATH, missing))
-        for name, fn in HEADER.functions.items():
-            f = getattr(lib, name)
-            f.argtypes, f.restype = fn.argtypes, fn.restype
-        _bound = lib
-    return _bound
 
 
 def relative(poses, pairs=None):
@@ -102,33 +80,13 @@ def _xyt(results):
     return np.asarray(r, np.float64).reshape(-1, 3)
 
 
-class FrameMotion(object):
+class FrameMotion(_handle.Handle):
     """Relative motions between frames of a batch (lf_motion_*).  Raises without the HIP library or a GPU."""
+    PREFIX, STAGES, _load = "lf_motion", STAGES, staticmethod(load)
 
     def __init__(self, max_pairs=4095, device=0):
-        self.lib = load()
         self.max_pairs = int(max_pairs)
-        self.h = ctypes.c_void_p()
-        rc = self.lib.lf_motion_create(int(device), self.max_pairs, ctypes.byref(self.h))
-        if rc != 0:
-            msg = self.lib.lf_motion_last_error(None).decode()
-            self.h = None
-            raise LanefrontError(rc, msg)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.lf_motion_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != 0:
-            raise LanefrontError(rc, self.lib.lf_motion_last_error(self.h).decode())
+        self._create(int(device), self.max_pairs)
 
     @staticmethod
     def config(**overrides):
@@ -151,22 +109,7 @@ class FrameMotion(object):
         prior: (n_pairs, 3) expected motions (`relative` of the odometry's poses) or None; config: `FrameMotion.config(...)`.
         Returns a record array of RESULT_DTYPE; candidates=True: (results, (n_pairs, 128, 3) int32 rows (segment of b, segment of a,
         Hamming distance), -1 where unused)."""
-        if isinstance(seg, tuple):
-            out_ptrs, n, n_frames = seg
-            s, alive, on_device = _lib.LfSegments(), None, 1
-            for k, v in out_ptrs.items():
-                setattr(s, k, int(v))
-            n, n_frames = int(n), int(n_frames)
-        else:
-            n, n_frames, on_device = int(seg.n), len(seg.frame_offset) - 1, 0
-            s, alive = _lib.LfSegments(), []
-            s.capacity = n
-            for k in ("frame_offset", "ground", "color", "keep", "code"):
-                v = getattr(seg, k, None)
-                if v is not None:
-                    a = np.ascontiguousarray(v)
-                    alive.append(a)
-                    setattr(s, k, a.ctypes.data)
+        s, n, n_frames, on_device, alive = _handle.segments_arg(seg)
         ab = None if pairs is None else np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         n_pairs = n_frames - 1 if ab is None else len(ab)
         pr = None if prior is None else np.ascontiguousarray(prior, np.float64).reshape(-1, 3)
@@ -180,15 +123,3 @@ class FrameMotion(object):
                                                 ctypes.byref(config), on_device, res.ctypes.data_as(ctypes.POINTER(LfMotionResult)),
                                                 None if cand is None else cand.ctypes.data))
         return (res, cand) if candidates else res
-
-    def synchronize(self):
-        self._check(self.lib.lf_motion_synchronize(self.h))
-
-    def set_profiling(self, on):
-        self._check(self.lib.lf_motion_set_profiling(self.h, int(bool(on))))
-
-    def timing(self):
-        """{stage: (ms, launches)} accumulated since the previous call (lf_motion_get_timing)"""
-        ms, cnt = np.zeros(len(STAGES), np.float64), np.zeros(len(STAGES), np.int32)
-        self._check(self.lib.lf_motion_get_timing(self.h, ms.ctypes.data, cnt.ctypes.data, len(STAGES)))
-        return {name: (float(ms[i]), int(cnt[i])) for i, name in enumerate(STAGES)}

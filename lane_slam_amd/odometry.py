@@ -17,16 +17,11 @@ import time
 
 import numpy as np
 
-from . import _cdecl, _lib
-from .frontend import LanefrontError
+from . import _handle, _lib
+from .frontend import LanefrontError  # noqa: F401  (raised by Odometry's calls; callers catch odometry.LanefrontError)
 
 HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "lanefront_odometry.h")
-if not os.path.exists(HEADER_PATH):
-    raise RuntimeError(
-        "lanefront: %s is missing. The binding is read from the header, so the package is used from its source tree (the "
-        "directory that holds include/ next to lane_slam_amd/). There is no hand-written table to fall back to." % HEADER_PATH)
-with open(HEADER_PATH) as _f:
-    HEADER = _cdecl.Header(_f.read())
+HEADER, load = _handle.bind("lanefront_odometry.h")
 
 EXPORTS = tuple(HEADER.functions)
 LfOdometryConfig, LfOdometryState = HEADER.structs["lf_odometry_config"], HEADER.structs["lf_odometry_state"]
@@ -36,61 +31,24 @@ STATE_DTYPE = np.dtype(LfOdometryState)
 # the stages of lf_odometry_get_timing, in the header's order
 STAGES = ("k_odo_prepare", "k_odo_heading", "k_odo_terms", "k_odo_position", "k_odo_sample")
 
-_bound = None
-
-
-def load():
-    """liblanefront.so with the odometry entry points typed from the header"""
-    global _bound
-    if _bound is None:
-        lib = _lib.load()
-        missing = [n for n in EXPORTS if not hasattr(lib, n)]
-        if missing:
-            raise RuntimeError("lanefront: %s lacks %r; rebuild the HIP library (make -C lane_slam_amd/csrc)" % (_lib.SO_PATH, missing))
-        for name, fn in HEADER.functions.items():
-            f = getattr(lib, name)
-            f.argtypes, f.restype = fn.argtypes, fn.restype
-        _bound = lib
-    return _bound
-
 
 def _dev_ptr(v):
     return int(v.data_ptr()) if hasattr(v, "data_ptr") else int(v)
 
 
-class Odometry(object):
+class Odometry(_handle.Handle):
     """n_streams dead-reckoning streams on one device (lf_odometry_*).  Raises without the HIP library or a GPU."""
+    PREFIX, STAGES, _load = "lf_odometry", STAGES, staticmethod(load)
 
     def __init__(self, n_streams=1, max_commands=65536, max_frames=4096, device=0, wheel_distance=0.5, dt_max=0.3, stamps="nsecs", flip_y=False):
         if stamps not in STAMP_MODES:
             raise ValueError("stamps must be one of %r, got %r" % (sorted(STAMP_MODES), stamps))
-        self.lib = load()
         self.n_streams, self.max_commands, self.max_frames = int(n_streams), int(max_commands), int(max_frames)
         self.wheel_distance, self.dt_max, self.stamps, self.flip_y = float(wheel_distance), float(dt_max), stamps, bool(flip_y)
         self.c = LfOdometryConfig(self.wheel_distance, self.dt_max, STAMP_MODES[stamps], int(self.flip_y))
-        self.h = ctypes.c_void_p()
-        rc = self.lib.lf_odometry_create(int(device), ctypes.byref(self.c), self.n_streams, self.max_commands, self.max_frames, ctypes.byref(self.h))
-        if rc != 0:
-            msg = self.lib.lf_odometry_last_error(None).decode()
-            self.h = None
-            raise LanefrontError(rc, msg)
+        self._create(int(device), ctypes.byref(self.c), self.n_streams, self.max_commands, self.max_frames)
         self._traj = [[] for _ in range(self.n_streams)]
         self.last = None
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.lf_odometry_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != 0:
-            raise LanefrontError(rc, self.lib.lf_odometry_last_error(self.h).decode())
 
     @staticmethod
     def _inputs(stamp_ns, vel_left, vel_right, frame_stamp_ns, cmd_stream, frame_stream):
@@ -135,9 +93,6 @@ class Odometry(object):
         self._check(self.lib.lf_odometry_step(self.h, st.shape[0], st.ctypes.data, vl.ctypes.data, vr.ctypes.data, None if cs is None else cs.ctypes.data,
                                               fs.shape[0], fs.ctypes.data, None if fr is None else fr.ctypes.data, ptr[0], ptr[1], ptr[2], ptr[3], 1))
 
-    def synchronize(self):
-        self._check(self.lib.lf_odometry_synchronize(self.h))
-
     def state(self, stream=0):
         """dict(x, y, theta, last_t, last_stamp_ns, n_commands, n_driven) of a stream (waits for queued work); y as the outputs
         carry it (negated with flip_y)"""
@@ -162,15 +117,6 @@ class Odometry(object):
         showTraj appends (the blue line of LineAssociator.render)"""
         parts = self._traj[int(stream)]
         return np.concatenate(parts) if parts else np.zeros((0, 2), np.float64)
-
-    def set_profiling(self, on):
-        self._check(self.lib.lf_odometry_set_profiling(self.h, int(bool(on))))
-
-    def timing(self):
-        """{stage: (ms, launches)} accumulated since the previous call (lf_odometry_get_timing)"""
-        ms, cnt = np.zeros(len(STAGES), np.float64), np.zeros(len(STAGES), np.int32)
-        self._check(self.lib.lf_odometry_get_timing(self.h, ms.ctypes.data, cnt.ctypes.data, len(STAGES)))
-        return {name: (float(ms[i]), int(cnt[i])) for i, name in enumerate(STAGES)}
 
 
 class OdometryNode(object):

@@ -13,16 +13,12 @@ import os
 
 import numpy as np
 
-from . import _cdecl, _lib, motion
-from .frontend import LanefrontError
+from . import _handle, _lib, motion
+from .frontend import LanefrontError  # noqa: F401  (raised by KeyFrames' calls; callers catch places.LanefrontError)
 
 HEADER_PATH = os.path.join(os.path.dirname(_lib.HEADER_PATH), "lanefront_places.h")
-if not os.path.exists(HEADER_PATH):
-    raise RuntimeError(
-        "lanefront: %s is missing. The binding is read from the header, so the package is used from its source tree (the "
-        "directory that holds include/ next to lane_slam_amd/). There is no hand-written table to fall back to." % HEADER_PATH)
-with open(HEADER_PATH) as _f:
-    HEADER = _cdecl.Header(_f.read(), base=motion.HEADER)     # lf_motion_config and lf_motion_result are lanefront_motion.h's
+# (lf_motion_config and lf_motion_result are lanefront_motion.h's, and lf_places_motion takes them: the motion's entry points are typed first)
+HEADER, load = _handle.bind("lanefront_places.h", base=motion.HEADER, parent_load=motion.load)
 
 EXPORTS = tuple(HEADER.functions)
 LfPlacesConfig, LfPlaceHit = HEADER.structs["lf_places_config"], HEADER.structs["lf_place_hit"]
@@ -30,23 +26,6 @@ HIT_DTYPE = np.dtype(LfPlaceHit)
 MAX_KEYS, MAX_SEGMENTS = HEADER.constants["LF_PLACES_MAX_KEYS"], HEADER.constants["LF_PLACES_MAX_SEGMENTS"]
 MAX_QUERIES, MAX_TOP_K = HEADER.constants["LF_PLACES_MAX_QUERIES"], HEADER.constants["LF_PLACES_MAX_TOP_K"]
 STAGES = ("k_places_score", "k_places_top", "k_frame_motion")
-
-_bound = None
-
-
-def load():
-    """liblanefront.so with the places entry points typed from the header"""
-    global _bound
-    if _bound is None:
-        lib = motion.load()
-        missing = [n for n in EXPORTS if not hasattr(lib, n)]
-        if missing:
-            raise RuntimeError("lanefront: %s lacks %r; rebuild the HIP library (make -C lane_slam_amd/csrc)" % (_lib.SO_PATH, missing))
-        for name, fn in HEADER.functions.items():
-            f = getattr(lib, name)
-            f.argtypes, f.restype = fn.argtypes, fn.restype
-        _bound = lib
-    return _bound
 
 
 def loops(hits, results, min_inliers=6):
@@ -78,52 +57,16 @@ def pairs_of(hits):
     return np.stack([q, hits["key"][q, r]], axis=1).astype(np.int32).reshape(-1, 2)
 
 
-def _segments(seg):
-    """(LfSegments, n, n_frames, on_device, what must stay alive) of a host block or a (device pointers, n, n_frames) tuple"""
-    s = _lib.LfSegments()
-    if isinstance(seg, tuple):
-        out_ptrs, n, n_frames = seg
-        for k, v in out_ptrs.items():
-            setattr(s, k, int(v))
-        return s, int(n), int(n_frames), 1, None
-    n, n_frames, alive = int(seg.n), len(seg.frame_offset) - 1, []
-    s.capacity = n
-    for k in ("frame_offset", "ground", "color", "keep", "code"):
-        v = getattr(seg, k, None)
-        if v is not None:
-            a = np.ascontiguousarray(v)
-            alive.append(a)
-            setattr(s, k, a.ctypes.data)
-    return s, n, n_frames, 0, alive
+_segments = _handle.segments_arg
 
 
-class KeyFrames(object):
+class KeyFrames(_handle.Handle):
     """A store of key frames on the device and the queries against it (lf_places_*).  Raises without the HIP library or a GPU."""
+    PREFIX, STAGES, _load = "lf_places", STAGES, staticmethod(load)
 
     def __init__(self, max_keys=4096, max_segments=1 << 18, max_queries=256, device=0):
-        self.lib = load()
         self.max_keys, self.max_segments, self.max_queries = int(max_keys), int(max_segments), int(max_queries)
-        self.h = ctypes.c_void_p()
-        rc = self.lib.lf_places_create(int(device), self.max_keys, self.max_segments, self.max_queries, ctypes.byref(self.h))
-        if rc != 0:
-            msg = self.lib.lf_places_last_error(None).decode()
-            self.h = None
-            raise LanefrontError(rc, msg)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.lf_places_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != 0:
-            raise LanefrontError(rc, self.lib.lf_places_last_error(self.h).decode())
+        self._create(int(device), self.max_keys, self.max_segments, self.max_queries)
 
     @staticmethod
     def config(**overrides):
@@ -200,15 +143,3 @@ class KeyFrames(object):
                                               None if pr is None else pr.ctypes.data, ctypes.byref(config), on_device,
                                               res.ctypes.data_as(ctypes.POINTER(motion.LfMotionResult))))
         return res
-
-    def synchronize(self):
-        self._check(self.lib.lf_places_synchronize(self.h))
-
-    def set_profiling(self, on):
-        self._check(self.lib.lf_places_set_profiling(self.h, int(bool(on))))
-
-    def timing(self):
-        """{stage: (ms, launches)} accumulated since the previous call (lf_places_get_timing)"""
-        ms, cnt = np.zeros(len(STAGES), np.float64), np.zeros(len(STAGES), np.int32)
-        self._check(self.lib.lf_places_get_timing(self.h, ms.ctypes.data, cnt.ctypes.data, len(STAGES)))
-        return {name: (float(ms[i]), int(cnt[i])) for i, name in enumerate(STAGES)}

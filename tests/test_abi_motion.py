@@ -121,7 +121,7 @@ def test_a_missing_header_raises_as_the_first_one_does(tmp_path):
     import sys
     pkg = tmp_path / "tree" / "lane_slam_amd"
     pkg.mkdir(parents=True)
-    for name in ("_cdecl.py", "_lib.py", "motion.py"):
+    for name in ("_cdecl.py", "_lib.py", "_handle.py", "motion.py"):
         shutil.copy(os.path.join(ROOT, "lane_slam_amd", name), str(pkg / name))
     (pkg / "__init__.py").write_text("")
     (pkg / "frontend.py").write_text("class LanefrontError(RuntimeError):\n    pass\n")
